@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py — LM iterations/s of the full-BA hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config C4]
+  python bench.py --gpus N --steps K --warmup W [--config C4] [--full]
+                  [--dump-outputs DIR]
 
 A "step" is one LM iteration (linearise -> Schur -> dense reduced solve ->
 back-substitution/update -> trial cost -> trust-region control; reference
@@ -16,6 +17,14 @@ either by torchrun (RANK / WORLD_SIZE in the environment) or as plain
 `python bench.py --gpus N`: the script then starts the N ranks itself, as
 child processes, before anything touches the GPU.  Inputs are resident in HBM
 before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full`
+adds what takes runs of its own: the instrumented per-stage / per-kernel pass
+with the roofline figures, the end-to-end Solve() of a fresh handle and the CPU
+baselines (`--no-roofline` / `--no-cpu-baseline` drop parts of it).
+`--dump-outputs DIR` writes what the timed path computed after its last step
+(the poses and points a caller receives) as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -141,6 +150,32 @@ def self_launch(n):
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # all .npy files of one --dump-outputs together
+
+
+def dump_outputs(outdir, poses, points):
+    """--dump-outputs: what a caller of the timed path receives after its last
+    step, the poses (n_pose x 12) and points (n_pt x 3), float64.  The per-
+    iteration records are not outputs: with the thresholds off the run passes
+    convergence, and once a weakly constrained landmark has run away the trial
+    cost, rho and step of the record go non-finite by the reference's control
+    law, while the rejected trial point never reaches the parameters.  Past the
+    size limit the points are a fixed, seeded sample of rows
+    (points_sample_rows.npy names them)."""
+    os.makedirs(outdir, exist_ok=True)
+    out = {"poses": np.ascontiguousarray(poses, dtype=np.float64)}
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values()) - (1 << 20)
+    if points.nbytes > room:
+        k = room // (points.itemsize * points.shape[1] + 8)
+        sel = np.sort(np.random.default_rng(0).choice(points.shape[0], k, replace=False))
+        out["points_sample_rows"] = sel.astype(np.float64)
+        points = points[sel]
+    out["points"] = points
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def bench_stream(args, pr, sc, t_gen):
     """LM iterations/s of the streamed solve (include/ba_hip.h ba_stream_*): the
     landmark-side data lives in pinned host memory and crosses PCIe twice per
@@ -180,6 +215,8 @@ def bench_stream(args, pr, sc, t_gen):
     i1 = st.info()
     rows, n_done, _, _ = st.lm_sync(cap=args.warmup + args.steps + 1)
     assert n_done == args.warmup + args.steps, n_done
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, st.get_poses(), st.get_points())
     up = (i1["bytes_h2d"] - i0["bytes_h2d"]) / args.steps
     down = (i1["bytes_d2h"] - i0["bytes_d2h"]) / args.steps
     n_obs = int(pr["obs_cam"].shape[0])
@@ -239,9 +276,20 @@ def main():
                     help="with one rank: still run the N > 1 code path (process group, RCCL "
                          "exchange from C++, separate control kernel, final landmark gather) — "
                          "what a one-GPU box can rehearse of the multi-GPU bench with real RCCL")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: instrumented "
+                         "per-stage / per-kernel pass and roofline, end-to-end Solve(), "
+                         "CPU baselines (a plain run times the steps only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the instrumented pass and the end-to-end Solve()")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the poses and points as "
+                         "DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -365,6 +413,13 @@ def main():
     if os.environ.get("BA_BENCH_DUMP_ROWS"):  # developer aid: the trajectory of every rank
         sys.stderr.write("rank %d: %s\n" % (rank, " ".join(
             "%d:%.6g" % (r.iteration_status, r.trial_cost) for r in rows)))
+    if args.dump_outputs:
+        # before anything below runs more iterations on the handle; a sharded run
+        # gathers its landmarks first (every rank takes part)
+        if sharded:
+            p.gather_points()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, p.get_poses(), p.get_points()[0])
 
     ms_per_step = elapsed / args.steps * 1e3
     result = {
@@ -404,11 +459,11 @@ def main():
         "host_prep_s": {"scene_gen": t_gen, "finalize_upload": t_fin},
     }
 
-    # ---- per-stage / per-kernel device times + roofline: a separate
+    # ---- (--full) per-stage / per-kernel device times + roofline: a separate
     # instrumented pass (hipEvents around every launch, on the stream the
     # kernels run on) over the same problem, so that the headline region stays
     # un-instrumented ------------------------------------------------------
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         p.enable_stage_timing(True)
         p.get_stage_ms(reset=True)
         p.get_kernel_ms(reset=True)
@@ -523,10 +578,10 @@ def main():
                         "MFMA issue peak on this part: %.1f TFLOP/s "
                         "(tools/mfma_f64_peak.hip)" % (di["levels"], FP64_MFMA_MEASURED_TFLOPS)}
 
-    # ---- the whole Solve() of a caller: finalize (host plan + uploads) + 50 LM
+    # ---- (--full) the whole Solve() of a caller: finalize (host plan + uploads) + 50 LM
     # iterations with the reference's default thresholds + write-back, fresh handle,
     # host arrays as inputs (PCIe inside) — what Summary::total_time covers --------
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline:
         t_a = time.perf_counter()
         q = BaProblem(local_rank)
         q.set_cameras(pr["cam_intr"], pr["cam_T"])
@@ -554,8 +609,8 @@ def main():
             "resolve_update_values": t_e - t_d, "resolve_total": t_f - t_d}
         q.close()
 
-    # ---- CPU baseline: the oracle on the box's host cores, 1 thread -------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    # ---- (--full) CPU baseline: the oracle on the box's host cores, 1 thread -------
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle_py as O   # the checker: this leg only
         o = O.Oracle(pr)
         # SURVEY.md 8(d) / BASELINE.md 3: median of >= 5 iterations after the first —

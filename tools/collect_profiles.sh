@@ -6,8 +6,8 @@
 T=${1:-r03_v1}
 O=gpurun_out
 export TMPDIR=/tmp
-python bench.py > $O/${T}_c4_bench.json 2> $O/${T}_c4_bench.err && \
-python bench.py --sigma 0.5 --no-cpu-baseline > $O/${T}_c4_sigma05_bench.json 2> /dev/null && \
+python bench.py --full > $O/${T}_c4_bench.json 2> $O/${T}_c4_bench.err && \
+python bench.py --full --sigma 0.5 --no-cpu-baseline > $O/${T}_c4_sigma05_bench.json 2> /dev/null && \
 rocprofv3 --kernel-trace --stats -d $O/prof_$T --output-format csv -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-roofline > $O/prof_$T.log 2>&1 && \
 python tools/timeline.py $O/prof_$T > $O/${T}_c4_timeline.txt 2>&1 && \
 cp $O/prof_$T/*/*kernel_stats.csv $O/${T}_c4_kernel_stats.csv && rm -f $O/prof_$T/*/*kernel_trace.csv && \
@@ -15,7 +15,7 @@ rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch_$T --output-format csv
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write_$T --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline > $O/pmc_write_$T.log 2>&1 && \
 python tools/pmc_summary.py $O/pmc_fetch_$T $O/pmc_write_$T > $O/${T}_c4_pmc_fetch_write.txt 2>&1 && \
 rm -rf $O/pmc_fetch_$T $O/pmc_write_$T && \
-for c in C3 C2 C1 C4R W20 DENSE1K; do python bench.py --config $c > $O/${T}_$(echo $c | tr A-Z a-z)_bench.json 2>/dev/null; done
+for c in C3 C2 C1 C4R W20 DENSE1K; do python bench.py --full --config $c > $O/${T}_$(echo $c | tr A-Z a-z)_bench.json 2>/dev/null; done
 python bench.py --config C4 --stream 4 --steps 10 --warmup 2 > $O/${T}_c4_stream4_bench.json 2>/dev/null
 # N > 1 as the driver starts it (plain python): two ranks REHEARSE on the one card (gloo, host-staged)
 BA_BENCH_BACKEND=gloo python bench.py --gpus 2 --config C3 --no-cpu-baseline --no-roofline > $O/${T}_c3_gpus2_rehearsal.json 2>/dev/null
