@@ -166,6 +166,16 @@ SIGNATURES = {
                                        C.POINTER(BaPoIter), C.c_int,
                                        C.POINTER(C.c_int), C.POINTER(C.c_int),
                                        _F]),
+    "ba_pose_only_mono3": (C.c_int, [_P, _F, _F, C.c_int, C.c_float, C.c_float,
+                                     C.c_float, C.c_float, _F, _F, _F, _U8,
+                                     C.POINTER(BaOptions), C.POINTER(BaPoIter),
+                                     C.c_int, C.POINTER(C.c_int),
+                                     C.POINTER(C.c_int), _F]),
+    "ba_pose_only_stereo3": (C.c_int, [_P, _F, _F, _F, C.c_int, _F, _F, _F, _F,
+                                       _F, _F, _U8, _U8, C.POINTER(BaOptions),
+                                       C.POINTER(BaPoIter), C.c_int,
+                                       C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                       _F]),
 }
 
 _lib = None

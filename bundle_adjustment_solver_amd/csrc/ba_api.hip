@@ -1559,7 +1559,8 @@ PoLayout po_layout(int n, int icap, bool stereo) {
 int po_run(ba_handle *h, bool stereo, const float *X3, const float *uv2, const float *uvr2, int n,
            float fx, float fy, float cx, float cy, const float *camr16, float *T12, uint8_t *mask,
            uint8_t *mask_r, const ba_options *opt, ba_po_iter *iters, int cap, int *n_iter,
-           int *converged, float *debug_T12) {
+           int *converged, float *debug_T12, const ba::Po3Params *p3 = nullptr) {
+  // p3 != nullptr: the planar 3-DoF kernel (T12 = world_to_current, camr unused)
   if (use_device(h)) return -1;
   static_assert(sizeof(ba::PoIter) == sizeof(ba_po_iter), "po iter layout");
   const int max_it = opt->max_num_iterations;
@@ -1580,7 +1581,7 @@ int po_run(ba_handle *h, bool stereo, const float *X3, const float *uv2, const f
   std::memcpy(hb + L.uv, uv2, (size_t)n * 2 * sizeof(float));
   if (stereo) {
     std::memcpy(hb + L.uvr, uvr2, (size_t)n * 2 * sizeof(float));
-    std::memcpy(hb + L.camr, camr16, 16 * sizeof(float));
+    if (camr16) std::memcpy(hb + L.camr, camr16, 16 * sizeof(float));
     std::memcpy(hb + L.maskr, mask_r, (size_t)n);
   }
   std::memcpy(hb + L.T, T12, 12 * sizeof(float));
@@ -1590,7 +1591,15 @@ int po_run(ba_handle *h, bool stereo, const float *X3, const float *uv2, const f
   HIP_TRY(hipMemcpyAsync(db, hb, L.h2d_end, hipMemcpyHostToDevice, s));
   float *dT = (float *)(db + L.T), *ddbg = debug_T12 ? (float *)(db + L.dbg) : nullptr;
   int rc;
-  if (stereo)
+  if (p3)
+    rc = ba::pose_only_planar3_device(
+        stereo, (const float *)(db + L.X), (const float *)(db + L.uv),
+        stereo ? (const float *)(db + L.uvr) : nullptr, n, fx, fy, cx, cy, *p3, dT, db + L.mask,
+        stereo ? db + L.maskr : nullptr, opt->threshold_huber_loss, opt->threshold_step_size,
+        opt->threshold_cost_change, opt->threshold_outlier_rejection, max_it,
+        (ba::PoIter *)(db + L.iters), icap, (int *)(db + L.meta), ddbg, (int *)(db + L.gsw),
+        h->po_part, s);
+  else if (stereo)
     rc = ba::pose_only_stereo6_device(
         (const float *)(db + L.X), (const float *)(db + L.uv), (const float *)(db + L.uvr), n, fx, fy,
         cx, cy, (const float *)(db + L.camr), dT, db + L.mask, db + L.maskr, opt->threshold_huber_loss,
@@ -1656,6 +1665,90 @@ int ba_pose_only_stereo6(ba_handle *h, const float *X3, const float *uv2,
                      camr[4 + r * 3 + 2] * T_lr12[11]);
   return po_run(h, true, X3, uv2, uvr2, n, intr_l4[0], intr_l4[1], intr_l4[2], intr_l4[3], camr, T12,
                 mask, mask_r, opt, iters, cap, n_iter, converged, debug_T12);
+}
+
+// ---- planar 3-DoF (reference :401-900) ----------------------------------------
+namespace {
+// fp32 rigid transforms in the reference's Eigen operation order: R (9,
+// row-major) then t (3), like the 12-float ABI poses
+struct Iso {
+  float R[9], t[3];
+};
+Iso iso12(const float *T12) {
+  Iso A;
+  for (int k = 0; k < 9; ++k) A.R[k] = T12[k];
+  for (int k = 0; k < 3; ++k) A.t[k] = T12[9 + k];
+  return A;
+}
+Iso iso_mul(const Iso &A, const Iso &B) {
+  Iso C;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c)
+      C.R[r * 3 + c] = A.R[r * 3 + 0] * B.R[0 * 3 + c] + A.R[r * 3 + 1] * B.R[1 * 3 + c] +
+                       A.R[r * 3 + 2] * B.R[2 * 3 + c];
+    C.t[r] = (A.R[r * 3 + 0] * B.t[0] + A.R[r * 3 + 1] * B.t[1] + A.R[r * 3 + 2] * B.t[2]) + A.t[r];
+  }
+  return C;
+}
+Iso iso_inv(const Iso &A) {
+  Iso B;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) B.R[r * 3 + c] = A.R[c * 3 + r];
+  for (int r = 0; r < 3; ++r)
+    B.t[r] = -(B.R[r * 3 + 0] * A.t[0] + B.R[r * 3 + 1] * A.t[1] + B.R[r * 3 + 2] * A.t[2]);
+  return B;
+}
+// the host-side set-up of both planar solvers (reference :446-460 / :674-692)
+ba::Po3Params po3_params(const float *T_bc12, const float *T_wl12, const float *T12,
+                         const float *T_lr12, const float *intr_r4) {
+  ba::Po3Params P;
+  const Iso Tbc = iso12(T_bc12), Tcb = iso_inv(Tbc);
+  const Iso prior = iso_mul(iso_inv(iso12(T12)), iso12(T_wl12));   // pose_c2c1_prior
+  const Iso Pb = iso_mul(iso_mul(Tbc, prior), Tcb);                 // pose_b2b1
+  P.theta0[0] = Pb.t[0];
+  P.theta0[1] = Pb.t[1];
+  P.theta0[2] = std::atan2(Pb.R[3], Pb.R[0]);
+  std::memcpy(P.Rcb, Tcb.R, sizeof(P.Rcb));
+  std::memcpy(P.tcb, Tcb.t, sizeof(P.tcb));
+  std::memcpy(P.Rbc, Tbc.R, sizeof(P.Rbc));
+  std::memcpy(P.tbc, Tbc.t, sizeof(P.tbc));
+  Iso Trl{};
+  if (T_lr12) Trl = iso_inv(iso12(T_lr12));
+  std::memcpy(P.Rrl, Trl.R, sizeof(P.Rrl));
+  std::memcpy(P.trl, Trl.t, sizeof(P.trl));
+  const Iso Rrb = iso_mul(Trl, Tcb);  // only its rotation is used: R_rl * R_cb
+  std::memcpy(P.Rrb, Rrb.R, sizeof(P.Rrb));
+  for (int k = 0; k < 4; ++k) P.cam_r[k] = intr_r4 ? intr_r4[k] : 0.0f;
+  return P;
+}
+}  // namespace
+
+int ba_pose_only_mono3(ba_handle *h, const float *X3, const float *uv2, int n,
+                       float fx, float fy, float cx, float cy,
+                       const float *T_bc12, const float *T_wl12, float *T12,
+                       uint8_t *mask, const ba_options *opt, ba_po_iter *iters,
+                       int cap, int *n_iter, int *converged,
+                       float *debug_T12) {
+  if (!h || !X3 || !uv2 || n <= 0 || !T_bc12 || !T_wl12 || !T12 || !mask || !opt)
+    return fail("ba_pose_only_mono3: bad argument");
+  const ba::Po3Params P = po3_params(T_bc12, T_wl12, T12, nullptr, nullptr);
+  return po_run(h, false, X3, uv2, nullptr, n, fx, fy, cx, cy, nullptr, T12, mask, nullptr, opt,
+                iters, cap, n_iter, converged, debug_T12, &P);
+}
+
+int ba_pose_only_stereo3(ba_handle *h, const float *X3, const float *uvl2,
+                         const float *uvr2, int n, const float *intr_l4,
+                         const float *intr_r4, const float *T_bc12,
+                         const float *T_lr12, const float *T_wl12, float *T12,
+                         uint8_t *mask_l, uint8_t *mask_r, const ba_options *opt,
+                         ba_po_iter *iters, int cap, int *n_iter, int *converged,
+                         float *debug_T12) {
+  if (!h || !X3 || !uvl2 || !uvr2 || n <= 0 || !intr_l4 || !intr_r4 || !T_bc12 || !T_lr12 ||
+      !T_wl12 || !T12 || !mask_l || !mask_r || !opt)
+    return fail("ba_pose_only_stereo3: bad argument");
+  const ba::Po3Params P = po3_params(T_bc12, T_wl12, T12, T_lr12, intr_r4);
+  return po_run(h, true, X3, uvl2, uvr2, n, intr_l4[0], intr_l4[1], intr_l4[2], intr_l4[3],
+                nullptr, T12, mask_l, mask_r, opt, iters, cap, n_iter, converged, debug_T12, &P);
 }
 
 }  // extern "C"

@@ -389,6 +389,22 @@ int pose_only_stereo6_device(const float *dX3, const float *duvl2, const float *
                              float thr_step, float thr_cost, float thr_out, int max_it,
                              PoIter *d_iters, int cap, int *d_meta, float *d_debug,
                              int *d_gsync, float *d_partial, hipStream_t s);
+// planar 3-DoF (reference core/pose_only_bundle_adjustment_solver.cpp:401-900):
+// everything the host derives in fp32 from the poses, passed by value
+struct Po3Params {
+  float theta0[3];       // prior (x, y, psi) of pose_b2b1
+  float Rcb[9], tcb[3];  // camera_to_base = base_to_camera^-1 (left camera)
+  float Rbc[9], tbc[3];  // base_to_camera (write-back)
+  float Rrl[9], trl[3];  // right_to_left = left_to_right^-1 (stereo)
+  float Rrb[9];          // R_rl * R_cb: the right camera's Jacobian rotation (:678-679)
+  float cam_r[4];        // right fx, fy, cx, cy (stereo)
+};
+int pose_only_planar3_device(bool stereo, const float *dX3, const float *duvl2,
+                             const float *duvr2, int n, float fx, float fy, float cx, float cy,
+                             const Po3Params &P, float *dT12, uint8_t *dmask_l, uint8_t *dmask_r,
+                             float thr_huber, float thr_step, float thr_cost, float thr_out,
+                             int max_it, PoIter *d_iters, int cap, int *d_meta, float *d_debug,
+                             int *d_gsync, float *d_partial, hipStream_t s);
 
 }  // namespace ba
 #endif

@@ -8,6 +8,8 @@
                          window of consecutive poses.
 * pose_only_scene      — config C5: reference
                          test/test_compare_ceres_vs_native.cpp:20-95.
+* planar_pose_only_scene — planar 3-DoF pose-only (wheeled base, forward
+                         camera), mono or stereo.
 All quantities are in USER units (metres, pixels, world->camera 4x4 poses);
 the solver facade applies the reference's 0.01 scaling.
 """
@@ -436,4 +438,68 @@ def pose_only_stereo_scene(n=10_000, seed=SEED_BASE + 6, pixel_sigma=0.0,
     miss = rng.uniform(size=n) < right_missing_frac
     uvr[miss] = -1.0
     sc.update(uv_right=uvr, T_lr=T_lr, right_missing=miss)
+    return sc
+
+
+def planar_T(theta):
+    """4x4 pose_b2b1 of the planar parameters (x, y, psi): rotation psi about
+    the base z axis, translation (x, y, 0) (reference
+    core/pose_only_bundle_adjustment_solver.cpp:484-489)."""
+    T = np.eye(4)
+    T[:3, :3] = _rot("z", theta[2])
+    T[:2, 3] = theta[:2]
+    return T
+
+
+def planar_pose_only_scene(n=10_000, seed=SEED_BASE + 7, pixel_sigma=0.0,
+                           stereo=False, right_missing_frac=0.2):
+    """Planar 3-DoF pose-only scene (reference
+    core/pose_only_bundle_adjustment_solver.cpp:401-900 conventions): a wheeled
+    base carries a forward-looking camera (optical axis along base x, image x
+    along -base y, image y along -base z, 0.3 m above the base origin); between
+    the last and the current frame the base moves by theta = (x, y, psi),
+    |t| <= 0.3 m, |psi| <= 0.2 rad.  The points X are base-1 coordinates in
+    front of the camera.  world_to_last (T_wl) is the camera of a base at a
+    planar world pose W_b1; world_to_current (T_wc_init) is chosen so that the
+    reference's prior, T_bc * (T_wc^-1 * T_wl) * T_bc^-1, is pose_b2b1 of the
+    perturbed theta_init.  T_out_true is what the reference writes back at the
+    true theta: pose_b2b1^-1 * T_bc (:549-551).  Stereo: the right camera sees
+    left_to_right^-1 * X_left with left_to_right = translate(+0.12, 0, 0); a
+    fraction of the points has no right match (pixel -1)."""
+    rng = np.random.default_rng(seed)
+    T_bc = np.eye(4)
+    T_bc[:3, :3] = [[0, 0, 1], [-1, 0, 0], [0, -1, 0]]
+    T_bc[:3, 3] = [0.0, 0.0, 0.3]
+    theta_true = np.array([rng.uniform(0.05, 0.25), rng.uniform(-0.15, 0.15),
+                           rng.uniform(-0.2, 0.2)])
+    theta_init = theta_true + np.array([rng.uniform(-0.01, 0.01),      # odometry prior
+                                        rng.uniform(-0.01, 0.01),
+                                        rng.uniform(-0.003, 0.003)])
+    z = rng.uniform(1.5, 12.0, n)
+    Xc = np.stack([rng.uniform(-0.5, 0.5, n) * z, rng.uniform(-0.35, 0.35, n) * z,
+                   z], axis=1)                        # current camera
+    Xb2 = Xc @ T_bc[:3, :3].T + T_bc[:3, 3]
+    Pi = _inv(planar_T(theta_true))
+    X = (Xb2 @ Pi[:3, :3].T + Pi[:3, 3]).astype(np.float32)
+    uv = np.stack([FX * Xc[:, 0] / Xc[:, 2] + CX, FY * Xc[:, 1] / Xc[:, 2] + CY], 1)
+    if pixel_sigma > 0:
+        uv = uv + rng.normal(0, pixel_sigma, uv.shape)
+    W_b1 = planar_T([2.0, -1.0, 0.3])
+    T_wl = W_b1 @ T_bc
+    T_wc_init = W_b1 @ _inv(planar_T(theta_init)) @ T_bc
+    T_out_true = _inv(planar_T(theta_true)) @ T_bc
+    f32 = lambda a: np.asarray(a, np.float32)
+    sc = dict(X=X, uv=f32(uv), fx=FX, fy=FY, cx=CX, cy=CY, T_bc=f32(T_bc),
+              T_wl=f32(T_wl), T_wc_init=f32(T_wc_init), theta_true=theta_true,
+              theta_init=theta_init, T_out_true=f32(T_out_true))
+    if stereo:
+        T_lr = np.eye(4)
+        T_lr[0, 3] = BASELINE
+        Xr = Xc - T_lr[:3, 3]
+        uvr = np.stack([FX * Xr[:, 0] / Xr[:, 2] + CX, FY * Xr[:, 1] / Xr[:, 2] + CY], 1)
+        if pixel_sigma > 0:
+            uvr = uvr + rng.normal(0, pixel_sigma, uvr.shape)
+        miss = rng.uniform(size=n) < right_missing_frac
+        uvr[miss] = -1.0
+        sc.update(uv_right=f32(uvr), T_lr=f32(T_lr), right_missing=miss)
     return sc

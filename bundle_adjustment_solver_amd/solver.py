@@ -2,7 +2,7 @@
 
 Mirrors (names, argument meaning, error behaviour):
   * FullBundleAdjustmentSolver   reference core/full_bundle_adjustment_solver.h:127-146
-  * PoseOnlyBundleAdjustmentSolver.Solve_Monocular_6Dof
+  * PoseOnlyBundleAdjustmentSolver.Solve_{Monocular,Stereo}_{6Dof,Planar3Dof}
                                  reference core/pose_only_bundle_adjustment_solver.h:25-67
   * Options / Summary / OptimizationInfo / IterationStatus / SolverType
                                  reference core/solver_option_and_summary.h:25-93
@@ -567,6 +567,85 @@ class BaProblem:
                            rows[i].abs_step) for i in range(nrows)],
                     debug=dbg[:min(n_it.value, cap)] if want_debug else None)
 
+    def _pose_only_out(self, rc, T, masks, rows, n_it, conv, cap, dbg):
+        nrows = n_it.value - 1 if conv.value else n_it.value
+        nrows = max(0, min(nrows, cap))
+        out = dict(T12=T, n_iter=n_it.value, converged=bool(conv.value),
+                   success=(rc == 0),
+                   rows=[(rows[i].cost, rows[i].cost_change, rows[i].abs_step)
+                         for i in range(nrows)],
+                   debug=dbg[:min(n_it.value, cap)] if dbg is not None else None)
+        out.update({k: m.astype(bool) for k, m in masks.items()})
+        return out
+
+    def pose_only_mono3(self, X3, uv2, fx, fy, cx, cy, T_bc12, T_wl12, T12,
+                        mask, opt, cap=None, want_debug=False):
+        """Planar 3-DoF, reference core/pose_only_bundle_adjustment_solver.cpp:
+        401-615.  X3 in base-1 coordinates; T_bc12 = pose_base_to_camera,
+        T_wl12 = pose_world_to_last, T12 = pose_world_to_current (returned
+        updated as "T12")."""
+        X = np.ascontiguousarray(X3, np.float32).reshape(-1, 3)
+        uv = np.ascontiguousarray(uv2, np.float32).reshape(-1, 2)
+        if uv.shape[0] != X.shape[0]:
+            raise RuntimeError(  # reference :426-432
+                "In PoseOnlyBundleAdjustmentSolver::"
+                "SolveMonocularPoseOnlyBundleAdjustment3Dof(), "
+                "world_position_list.size() != current_pixel_list.size()")
+        n = X.shape[0]
+        Tbc = np.ascontiguousarray(T_bc12, np.float32).reshape(12)
+        Twl = np.ascontiguousarray(T_wl12, np.float32).reshape(12)
+        T = np.ascontiguousarray(T12, np.float32).reshape(12).copy()
+        m = np.ascontiguousarray(mask, np.uint8).copy()
+        cap = cap or max(1, opt.max_num_iterations)
+        rows = (BaPoIter * cap)()
+        n_it = C.c_int(0)
+        conv = C.c_int(0)
+        dbg = np.zeros((cap, 12), np.float32) if want_debug else None
+        rc = check(self.lib.ba_pose_only_mono3(
+            self.h, _fp(X), _fp(uv), n, fx, fy, cx, cy, _fp(Tbc), _fp(Twl),
+            _fp(T), _up(m), C.byref(opt), rows, cap, C.byref(n_it),
+            C.byref(conv), _fp(dbg) if want_debug else None),
+            "ba_pose_only_mono3")
+        return self._pose_only_out(rc, T, {"mask": m}, rows, n_it, conv, cap, dbg)
+
+    def pose_only_stereo3(self, X3, uvl2, uvr2, intr_l, intr_r, T_bc12,
+                          T_lr12, T_wl12, T12, mask_l, mask_r, opt, cap=None,
+                          want_debug=False):
+        """Planar 3-DoF stereo, reference core/pose_only_bundle_adjustment_
+        solver.cpp:617-900 (a right pixel with a negative coordinate: no right
+        edge for that point, :785)."""
+        X = np.ascontiguousarray(X3, np.float32).reshape(-1, 3)
+        ul = np.ascontiguousarray(uvl2, np.float32).reshape(-1, 2)
+        ur = np.ascontiguousarray(uvr2, np.float32).reshape(-1, 2)
+        for side, u in (("left", ul), ("right", ur)):
+            if u.shape[0] != X.shape[0]:
+                raise RuntimeError(  # reference :647-660
+                    "In PoseOnlyBundleAdjustmentSolver::"
+                    "SolveMonocularPoseOnlyBundleAdjustment3Dof(), "
+                    "world_position_list.size() != %s_current_pixel_list.size()"
+                    % side)
+        n = X.shape[0]
+        il = np.ascontiguousarray(intr_l, np.float32).reshape(4)
+        ir = np.ascontiguousarray(intr_r, np.float32).reshape(4)
+        Tbc = np.ascontiguousarray(T_bc12, np.float32).reshape(12)
+        Tlr = np.ascontiguousarray(T_lr12, np.float32).reshape(12)
+        Twl = np.ascontiguousarray(T_wl12, np.float32).reshape(12)
+        T = np.ascontiguousarray(T12, np.float32).reshape(12).copy()
+        ml = np.ascontiguousarray(mask_l, np.uint8).copy()
+        mr = np.ascontiguousarray(mask_r, np.uint8).copy()
+        cap = cap or max(1, opt.max_num_iterations)
+        rows = (BaPoIter * cap)()
+        n_it = C.c_int(0)
+        conv = C.c_int(0)
+        dbg = np.zeros((cap, 12), np.float32) if want_debug else None
+        rc = check(self.lib.ba_pose_only_stereo3(
+            self.h, _fp(X), _fp(ul), _fp(ur), n, _fp(il), _fp(ir), _fp(Tbc),
+            _fp(Tlr), _fp(Twl), _fp(T), _up(ml), _up(mr), C.byref(opt), rows,
+            cap, C.byref(n_it), C.byref(conv),
+            _fp(dbg) if want_debug else None), "ba_pose_only_stereo3")
+        return self._pose_only_out(rc, T, {"mask_l": ml, "mask_r": mr}, rows,
+                                   n_it, conv, cap, dbg)
+
 
 class BaStream:
     """Observation streaming (include/ba_hip.h ba_stream_*): the
@@ -1076,7 +1155,7 @@ class FullBundleAdjustmentSolver:
 
 class PoseOnlyBundleAdjustmentSolver:
     """Mirror of reference core/pose_only_bundle_adjustment_solver.h:25-67
-    (monocular and stereo 6-DoF entry points)."""
+    (monocular and stereo, 6-DoF and planar 3-DoF entry points)."""
 
     def __init__(self, device=0):
         self._p = BaProblem(device)
@@ -1198,6 +1277,120 @@ class PoseOnlyBundleAdjustmentSolver:
             summary.total_time_in_millisecond_ = \
                 (time.perf_counter() - t0) * 1e3
         return res["success"]
+
+
+    def _finish_pose_only(self, res, pose, masks, summary, t0):
+        """Debug poses, masks, pose write-back and Summary rows of a pose-only
+        solve, as the 6-DoF methods above do them."""
+        self.debug_poses_ = [_T12_to_44(d)[0] for d in res["debug"]]
+        for mask, key in masks:
+            if isinstance(mask, list):
+                mask[:] = [bool(v) for v in res[key]]
+            else:
+                mask[...] = res[key]
+        if res["success"]:
+            pose[...] = _T12_to_44(res["T12"])[0]
+        if summary is not None:
+            for cost, dchg, step in res["rows"]:
+                info = OptimizationInfo()
+                info.cost = cost
+                info.cost_change = abs(dchg)
+                info.average_reprojection_error = cost
+                info.abs_step = step
+                info.abs_gradient = 0
+                info.damping_term = -1
+                info.iter_time = 0.0
+                info.iteration_status = IterationStatus.UPDATE
+                summary.optimization_info_list_.append(info)
+            summary.convergence_status_ = res["converged"]
+            summary.total_time_in_millisecond_ = \
+                (time.perf_counter() - t0) * 1e3
+        return res["success"]
+
+    @staticmethod
+    def _begin_summary(options, summary):
+        if summary is not None:     # reference :419-424
+            summary.max_iteration_ = options.iteration_handle.max_num_iterations
+            summary.threshold_cost_change_ = \
+                options.convergence_handle.threshold_cost_change
+            summary.threshold_step_size_ = \
+                options.convergence_handle.threshold_step_size
+            summary.convergence_status_ = True
+
+    @staticmethod
+    def _fit_mask(mask, n):
+        m = np.ones(n, np.uint8)    # resize(n, true): earlier values kept
+        k = min(len(mask), n)
+        m[:k] = np.asarray(mask[:k], np.uint8)
+        return m
+
+    def Solve_Monocular_Planar3Dof(self, world_position_list,
+                                   matched_pixel_list, fx, fy, cx, cy,
+                                   pose_base_to_camera, pose_world_to_last,
+                                   pose_world_to_current, mask_inlier,
+                                   options, summary=None):
+        """reference core/pose_only_bundle_adjustment_solver.cpp:401-615.
+        Poses are 4x4 arrays; `pose_world_to_current` is updated in place
+        (with pose_b2b1^-1 * pose_base_to_camera, :549-551), `mask_inlier` a
+        list/array resized to n (True) and updated in place.  The positions
+        are base-1 coordinates (the reference does not warp them)."""
+        t0 = time.perf_counter()
+        self._begin_summary(options, summary)
+        self.debug_poses_ = []
+        X = np.asarray(world_position_list, np.float32).reshape(-1, 3)
+        uv = np.asarray(matched_pixel_list, np.float32).reshape(-1, 2)
+        if X.shape[0] != uv.shape[0]:
+            raise RuntimeError(
+                "In PoseOnlyBundleAdjustmentSolver::"
+                "SolveMonocularPoseOnlyBundleAdjustment3Dof(), "
+                "world_position_list.size() != current_pixel_list.size()")
+        n = X.shape[0]
+        to12 = lambda T: _T44_to_12(np.asarray(T, np.float64)).astype(np.float32)
+        res = self._p.pose_only_mono3(
+            X, uv, fx, fy, cx, cy, to12(pose_base_to_camera),
+            to12(pose_world_to_last), to12(pose_world_to_current),
+            self._fit_mask(mask_inlier, n), options.to_c(), want_debug=True)
+        return self._finish_pose_only(res, pose_world_to_current,
+                                      ((mask_inlier, "mask"),), summary, t0)
+
+    def Solve_Stereo_Planar3Dof(self, world_position_list,
+                                matched_left_pixel_list,
+                                matched_right_pixel_list, fx_left, fy_left,
+                                cx_left, cy_left, fx_right, fy_right,
+                                cx_right, cy_right, base_to_camera_pose,
+                                left_to_right_pose, world_to_last_pose,
+                                world_to_current_pose, mask_inlier_left,
+                                mask_inlier_right, options, summary=None):
+        """reference core/pose_only_bundle_adjustment_solver.cpp:617-900.
+        As Solve_Monocular_Planar3Dof, plus the right camera at
+        left_to_right_pose^-1 * left; a right pixel with a negative coordinate
+        means "not matched in the right image"."""
+        t0 = time.perf_counter()
+        self._begin_summary(options, summary)
+        self.debug_poses_ = []
+        X = np.asarray(world_position_list, np.float32).reshape(-1, 3)
+        ul = np.asarray(matched_left_pixel_list, np.float32).reshape(-1, 2)
+        ur = np.asarray(matched_right_pixel_list, np.float32).reshape(-1, 2)
+        for side, u in (("left", ul), ("right", ur)):
+            if X.shape[0] != u.shape[0]:
+                raise RuntimeError(
+                    "In PoseOnlyBundleAdjustmentSolver::"
+                    "SolveMonocularPoseOnlyBundleAdjustment3Dof(), "
+                    "world_position_list.size() != %s_current_pixel_list.size()"
+                    % side)
+        n = X.shape[0]
+        to12 = lambda T: _T44_to_12(np.asarray(T, np.float64)).astype(np.float32)
+        res = self._p.pose_only_stereo3(
+            X, ul, ur, [fx_left, fy_left, cx_left, cy_left],
+            [fx_right, fy_right, cx_right, cy_right], to12(base_to_camera_pose),
+            to12(left_to_right_pose), to12(world_to_last_pose),
+            to12(world_to_current_pose), self._fit_mask(mask_inlier_left, n),
+            self._fit_mask(mask_inlier_right, n), options.to_c(),
+            want_debug=True)
+        return self._finish_pose_only(
+            res, world_to_current_pose,
+            ((mask_inlier_left, "mask_l"), (mask_inlier_right, "mask_r")),
+            summary, t0)
 
 
 class FullBundleAdjustmentSolverRefactor(FullBundleAdjustmentSolver):

@@ -1,7 +1,7 @@
 // PoseOnlyBundleAdjustmentSolver — C++ facade of the pose-only path over the
-// HIP C ABI.  Mirrors the monocular 6-DoF entry point of the reference
-// (core/pose_only_bundle_adjustment_solver.h:25-67); the planar 3-DoF and
-// stereo variants are out of scope this round.
+// HIP C ABI.  Mirrors all four entry points of the reference
+// (core/pose_only_bundle_adjustment_solver.h:25-67): monocular and stereo, planar
+// 3-DoF and 6-DoF, with the reference's signatures.
 #ifndef BA_FACADE_POSE_ONLY_BUNDLE_ADJUSTMENT_SOLVER_H_
 #define BA_FACADE_POSE_ONLY_BUNDLE_ADJUSTMENT_SOLVER_H_
 
@@ -21,6 +21,25 @@ class PoseOnlyBundleAdjustmentSolver {
   PoseOnlyBundleAdjustmentSolver();
   ~PoseOnlyBundleAdjustmentSolver();
   PoseOnlyBundleAdjustmentSolver(const PoseOnlyBundleAdjustmentSolver &) = delete;
+
+  // reference core/pose_only_bundle_adjustment_solver.h:28-48, .cpp:401-615 / :617-900
+  bool Solve_Monocular_Planar3Dof(const std::vector<Eigen::Vector3f> &world_position_list,
+                                  const std::vector<Eigen::Vector2f> &matched_pixel_list, const float fx,
+                                  const float fy, const float cx, const float cy,
+                                  const Eigen::Isometry3f &pose_base_to_camera,
+                                  const Eigen::Isometry3f &pose_world_to_last,
+                                  Eigen::Isometry3f &pose_world_to_current, std::vector<bool> &mask_inlier,
+                                  Options options, Summary *summary = nullptr);
+  bool Solve_Stereo_Planar3Dof(const std::vector<Eigen::Vector3f> &world_position_list,
+                               const std::vector<Eigen::Vector2f> &matched_left_pixel_list,
+                               const std::vector<Eigen::Vector2f> &matched_right_pixel_list, const float fx_left,
+                               const float fy_left, const float cx_left, const float cy_left, const float fx_right,
+                               const float fy_right, const float cx_right, const float cy_right,
+                               const Eigen::Isometry3f &base_to_camera_pose,
+                               const Eigen::Isometry3f &left_to_right_pose,
+                               const Eigen::Isometry3f &world_to_last_pose, Eigen::Isometry3f &world_to_current_pose,
+                               std::vector<bool> &mask_inlier_left, std::vector<bool> &mask_inlier_right,
+                               Options options, Summary *summary = nullptr);
 
   bool Solve_Monocular_6Dof(const std::vector<Eigen::Vector3f> &reference_position_list,
                             const std::vector<Eigen::Vector2f> &matched_pixel_list, const float fx, const float fy,

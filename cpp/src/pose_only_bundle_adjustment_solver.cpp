@@ -1,4 +1,5 @@
-// Reference: core/pose_only_bundle_adjustment_solver.cpp:8-170 (monocular), :172-399 (stereo).
+// Reference: core/pose_only_bundle_adjustment_solver.cpp:8-170 (monocular), :172-399 (stereo),
+// :401-615 (monocular planar 3-DoF), :617-900 (stereo planar 3-DoF).
 #include "core/pose_only_bundle_adjustment_solver.h"
 
 #include <stdexcept>
@@ -200,6 +201,193 @@ bool PoseOnlyBundleAdjustmentSolver::Solve_Stereo_6Dof(
   }
   if (summary != nullptr) {
     const int n_rows = converged ? n_iter - 1 : n_iter;  // no row on the converging iteration
+    for (int k = 0; k < n_rows && k < cap; ++k) {
+      OptimizationInfo info;
+      info.cost = rows[k].cost;
+      info.cost_change = rows[k].cost_change;
+      info.average_reprojection_error = rows[k].cost;
+      info.abs_step = rows[k].abs_step;
+      info.abs_gradient = 0;
+      info.damping_term = -1;
+      info.iter_time = 0.0;
+      info.iteration_status = IterationStatus::UPDATE;
+      summary->optimization_info_list_.push_back(info);
+    }
+    summary->convergence_status_ = converged != 0;
+    summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
+  }
+  return is_success;
+}
+
+namespace {
+void Pack12(const Eigen::Isometry3f &T, float *o) {
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) o[3 * r + c] = T.linear()(r, c);
+    o[9 + r] = T.translation()(r);
+  }
+}
+Eigen::Isometry3f Unpack12(const float *o) {
+  Eigen::Isometry3f T;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) T.linear()(r, c) = o[3 * r + c];
+    T.translation()(r) = o[9 + r];
+  }
+  return T;
+}
+ba_options ToC(const Options &options) {
+  ba_options o;
+  o.threshold_step_size = options.convergence_handle.threshold_step_size;
+  o.threshold_cost_change = options.convergence_handle.threshold_cost_change;
+  o.threshold_huber_loss = options.outlier_handle.threshold_huber_loss;
+  o.threshold_outlier_rejection = options.outlier_handle.threshold_outlier_rejection;
+  o.max_num_iterations = options.iteration_handle.max_num_iterations;
+  o.initial_lambda = options.trust_region_handle.initial_lambda;
+  o.decrease_ratio_lambda = options.trust_region_handle.decrease_ratio_lambda;
+  o.increase_ratio_lambda = options.trust_region_handle.increase_ratio_lambda;
+  o.gauss_newton = 0;
+  return o;
+}
+}  // namespace
+
+bool PoseOnlyBundleAdjustmentSolver::Solve_Monocular_Planar3Dof(
+    const std::vector<Eigen::Vector3f> &world_position_list, const std::vector<Eigen::Vector2f> &matched_pixel_list,
+    const float fx, const float fy, const float cx, const float cy, const Eigen::Isometry3f &pose_base_to_camera,
+    const Eigen::Isometry3f &pose_world_to_last, Eigen::Isometry3f &pose_world_to_current,
+    std::vector<bool> &mask_inlier, Options options, Summary *summary) {
+  timer::StopWatch stopwatch("SolveMonocularPoseOnlyBundleAdjustment3Dof");
+  stopwatch.Start();
+  if (summary != nullptr) {  // :419-424 / :640-645
+    summary->max_iteration_ = options.iteration_handle.max_num_iterations;
+    summary->threshold_cost_change_ = options.convergence_handle.threshold_cost_change;
+    summary->threshold_step_size_ = options.convergence_handle.threshold_step_size;
+    summary->convergence_status_ = true;
+  }
+  debug_poses_.resize(0);
+  if (world_position_list.size() != matched_pixel_list.size())  // :426-432
+    throw std::runtime_error(
+        "In PoseOnlyBundleAdjustmentSolver::SolveMonocularPoseOnlyBundleAdjustment3Dof(), "
+        "world_position_list.size() != current_pixel_list.size()");
+  const int n = static_cast<int>(world_position_list.size());
+  mask_inlier.resize(n, true);
+  if (n == 0) return true;  // as Solve_Monocular_6Dof
+  if (!handle_ && ba_create(&handle_, 0) < 0) throw std::runtime_error(ba_last_error());
+
+  std::vector<float> X(3 * n), uv(2 * n);
+  std::vector<uint8_t> mask(n);
+  for (int k = 0; k < n; ++k) {
+    for (int r = 0; r < 3; ++r) X[3 * k + r] = world_position_list[k](r);
+    uv[2 * k] = matched_pixel_list[k](0);
+    uv[2 * k + 1] = matched_pixel_list[k](1);
+    mask[k] = mask_inlier[k] ? 1 : 0;
+  }
+  float Tbc[12], Twl[12], T12[12];
+  Pack12(pose_base_to_camera, Tbc);
+  Pack12(pose_world_to_last, Twl);
+  Pack12(pose_world_to_current, T12);
+  const ba_options o = ToC(options);
+  const int cap = o.max_num_iterations > 0 ? o.max_num_iterations : 1;
+  std::vector<ba_po_iter> rows(cap);
+  std::vector<float> dbg(static_cast<size_t>(cap) * 12);
+  int n_iter = 0, converged = 0;
+  const int rc = ba_pose_only_mono3(handle_, X.data(), uv.data(), n, fx, fy, cx, cy, Tbc, Twl, T12, mask.data(), &o,
+                                    rows.data(), cap, &n_iter, &converged, dbg.data());
+  if (rc < 0) throw std::runtime_error(ba_last_error());
+  for (int k = 0; k < n; ++k) mask_inlier[k] = mask[k] != 0;
+  for (int it = 0; it < n_iter && it < cap; ++it) debug_poses_.push_back(Unpack12(&dbg[12 * it]));
+  const bool is_success = (rc == 0);
+  if (is_success)
+    pose_world_to_current = Unpack12(T12);
+  else
+    std::cout << "!! WARNING !! poseonly BA yields NAN value!!\n";
+  if (summary != nullptr) {  // :569-591, :598-602: no row on the converging iteration
+    const int n_rows = converged ? n_iter - 1 : n_iter;
+    for (int k = 0; k < n_rows && k < cap; ++k) {
+      OptimizationInfo info;
+      info.cost = rows[k].cost;
+      info.cost_change = rows[k].cost_change;
+      info.average_reprojection_error = rows[k].cost;
+      info.abs_step = rows[k].abs_step;
+      info.abs_gradient = 0;
+      info.damping_term = -1;
+      info.iter_time = 0.0;
+      info.iteration_status = IterationStatus::UPDATE;
+      summary->optimization_info_list_.push_back(info);
+    }
+    summary->convergence_status_ = converged != 0;
+    summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
+  }
+  return is_success;
+}
+
+bool PoseOnlyBundleAdjustmentSolver::Solve_Stereo_Planar3Dof(
+    const std::vector<Eigen::Vector3f> &world_position_list,
+    const std::vector<Eigen::Vector2f> &matched_left_pixel_list,
+    const std::vector<Eigen::Vector2f> &matched_right_pixel_list, const float fx_left, const float fy_left,
+    const float cx_left, const float cy_left, const float fx_right, const float fy_right, const float cx_right,
+    const float cy_right, const Eigen::Isometry3f &base_to_camera_pose, const Eigen::Isometry3f &left_to_right_pose,
+    const Eigen::Isometry3f &world_to_last_pose, Eigen::Isometry3f &world_to_current_pose,
+    std::vector<bool> &mask_inlier_left, std::vector<bool> &mask_inlier_right, Options options, Summary *summary) {
+  timer::StopWatch stopwatch("SolveMonocularPoseOnlyBundleAdjustment3Dof");
+  stopwatch.Start();
+  if (summary != nullptr) {  // :419-424 / :640-645
+    summary->max_iteration_ = options.iteration_handle.max_num_iterations;
+    summary->threshold_cost_change_ = options.convergence_handle.threshold_cost_change;
+    summary->threshold_step_size_ = options.convergence_handle.threshold_step_size;
+    summary->convergence_status_ = true;
+  }
+  debug_poses_.resize(0);
+  if (world_position_list.size() != matched_left_pixel_list.size())  // :647-653
+    throw std::runtime_error(
+        "In PoseOnlyBundleAdjustmentSolver::SolveMonocularPoseOnlyBundleAdjustment3Dof(), "
+        "world_position_list.size() != left_current_pixel_list.size()");
+  if (world_position_list.size() != matched_right_pixel_list.size())  // :654-660
+    throw std::runtime_error(
+        "In PoseOnlyBundleAdjustmentSolver::SolveMonocularPoseOnlyBundleAdjustment3Dof(), "
+        "world_position_list.size() != right_current_pixel_list.size()");
+  const int n = static_cast<int>(world_position_list.size());
+  mask_inlier_left.resize(n, true);
+  mask_inlier_right.resize(n, true);
+  if (n == 0) return true;  // as Solve_Stereo_6Dof
+  if (!handle_ && ba_create(&handle_, 0) < 0) throw std::runtime_error(ba_last_error());
+
+  std::vector<float> X(3 * n), uvl(2 * n), uvr(2 * n);
+  std::vector<uint8_t> ml(n), mr(n);
+  for (int k = 0; k < n; ++k) {
+    for (int r = 0; r < 3; ++r) X[3 * k + r] = world_position_list[k](r);
+    uvl[2 * k] = matched_left_pixel_list[k](0);
+    uvl[2 * k + 1] = matched_left_pixel_list[k](1);
+    uvr[2 * k] = matched_right_pixel_list[k](0);
+    uvr[2 * k + 1] = matched_right_pixel_list[k](1);
+    ml[k] = mask_inlier_left[k] ? 1 : 0;
+    mr[k] = mask_inlier_right[k] ? 1 : 0;
+  }
+  float Tbc[12], Tlr[12], Twl[12], T12[12];
+  Pack12(base_to_camera_pose, Tbc);
+  Pack12(left_to_right_pose, Tlr);
+  Pack12(world_to_last_pose, Twl);
+  Pack12(world_to_current_pose, T12);
+  const float il[4] = {fx_left, fy_left, cx_left, cy_left};
+  const float ir[4] = {fx_right, fy_right, cx_right, cy_right};
+  const ba_options o = ToC(options);
+  const int cap = o.max_num_iterations > 0 ? o.max_num_iterations : 1;
+  std::vector<ba_po_iter> rows(cap);
+  std::vector<float> dbg(static_cast<size_t>(cap) * 12);
+  int n_iter = 0, converged = 0;
+  const int rc = ba_pose_only_stereo3(handle_, X.data(), uvl.data(), uvr.data(), n, il, ir, Tbc, Tlr, Twl, T12,
+                                      ml.data(), mr.data(), &o, rows.data(), cap, &n_iter, &converged, dbg.data());
+  if (rc < 0) throw std::runtime_error(ba_last_error());
+  for (int k = 0; k < n; ++k) {
+    mask_inlier_left[k] = ml[k] != 0;
+    mask_inlier_right[k] = mr[k] != 0;
+  }
+  for (int it = 0; it < n_iter && it < cap; ++it) debug_poses_.push_back(Unpack12(&dbg[12 * it]));
+  const bool is_success = (rc == 0);
+  if (is_success)
+    world_to_current_pose = Unpack12(T12);
+  else
+    std::cout << "!! WARNING !! poseonly BA yields NAN value!!\n";
+  if (summary != nullptr) {  // :569-591, :598-602: no row on the converging iteration
+    const int n_rows = converged ? n_iter - 1 : n_iter;
     for (int k = 0; k < n_rows && k < cap; ++k) {
       OptimizationInfo info;
       info.cost = rows[k].cost;

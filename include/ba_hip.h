@@ -341,6 +341,32 @@ int ba_pose_only_stereo6(ba_handle *h, const float *X3, const float *uvl2,
                          ba_po_iter *iters, int cap, int *n_iter, int *converged,
                          float *debug_T12);
 
+/* ---- pose-only, planar 3-DoF (fp32), monocular and stereo ----------------- */
+/* Solve_Monocular_Planar3Dof / Solve_Stereo_Planar3Dof, reference
+ * core/pose_only_bundle_adjustment_solver.cpp:401-615 / :617-900.  The unknown
+ * is (x, y, psi) of pose_b2b1 (base-1 -> base-2); its prior is
+ * T_bc * (T12^-1 * T_wl) * T_bc^-1.  X3 are base-1 coordinates.  T_bc12 =
+ * pose_base_to_camera, T_wl12 = pose_world_to_last, T12 in/out =
+ * pose_world_to_current, written as pose_b2b1^-1 * T_bc after at least one
+ * iteration when the pose is not NaN (else left unchanged, return 1).
+ * max_num_iterations = 0: T12 unchanged, converged, no rows, return 0.
+ * Stereo: intr_*4 = fx,fy,cx,cy; T_lr12 = left_to_right_pose; a right pixel
+ * with a negative coordinate means "no right observation" (:785).  Masks are n
+ * bytes each, in/out (sticky false). */
+int ba_pose_only_mono3(ba_handle *h, const float *X3, const float *uv2, int n,
+                       float fx, float fy, float cx, float cy,
+                       const float *T_bc12, const float *T_wl12, float *T12,
+                       uint8_t *mask, const ba_options *opt, ba_po_iter *iters,
+                       int cap, int *n_iter, int *converged,
+                       float *debug_T12);
+int ba_pose_only_stereo3(ba_handle *h, const float *X3, const float *uvl2,
+                         const float *uvr2, int n, const float *intr_l4,
+                         const float *intr_r4, const float *T_bc12,
+                         const float *T_lr12, const float *T_wl12, float *T12,
+                         uint8_t *mask_l, uint8_t *mask_r, const ba_options *opt,
+                         ba_po_iter *iters, int cap, int *n_iter, int *converged,
+                         float *debug_T12);
+
 #ifdef __cplusplus
 }
 #endif

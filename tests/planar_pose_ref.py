@@ -1,0 +1,259 @@
+"""CPU restatement (numpy float32) of the reference's planar 3-DoF pose-only
+solvers, core/pose_only_bundle_adjustment_solver.cpp:401-615 (mono) and
+:617-900 (stereo), with helpers :1202-1278 and :1454-1583.
+
+Test infrastructure only: the product path (bundle_adjustment_solver_amd/)
+never imports it.  One line per reference statement where that is practical;
+the per-point loop is vectorised, so the sums are accumulated in a different
+order than the reference's sequential loop (fp32 sums differ at ~1e-6).
+Quirks kept on purpose: the psi column of the Jacobian uses the INPUT point,
+the update is left-multiplicative while x, y are re-read and psi is summed,
+the Huber branch adds only error_u and the other only error_v, the inlier
+masks are sticky-false, the write-back is pose_b2b1^-1 * base_to_camera."""
+import numpy as np
+
+F = np.float32
+
+
+# ---- fp32 rigid transforms: (R [3,3], t [3]) -------------------------------
+def iso(T44):
+    T = np.asarray(T44, F)
+    return T[:3, :3].copy(), T[:3, 3].copy()
+
+
+def iso_mul(A, B):
+    (Ra, ta), (Rb, tb) = A, B
+    return (Ra @ Rb).astype(F), ((Ra @ tb) + ta).astype(F)
+
+
+def iso_inv(A):
+    R, t = A
+    Rt = R.T.copy()
+    return Rt, (-(Rt @ t)).astype(F)
+
+
+def iso44(A):
+    T = np.eye(4, dtype=F)
+    T[:3, :3], T[:3, 3] = A
+    return T
+
+
+def iso12(A):
+    return np.concatenate([A[0].reshape(9), A[1]]).astype(F)
+
+
+def planar_iso(x, y, psi):
+    """pose_b2b1 of (x, y, psi) (:484-489)."""
+    c, s = F(np.cos(F(psi))), F(np.sin(F(psi)))
+    R = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]], F)
+    return R, np.array([x, y, 0], F)
+
+
+def prior_theta(T_bc, T_wl, T_wc):
+    """:446-460 — pose_b2b1 = T_bc * (T_wc^-1 * T_wl) * T_bc^-1, theta from it."""
+    Tbc = iso(T_bc)
+    Tcb = iso_inv(Tbc)
+    prior = iso_mul(iso_inv(iso(T_wc)), iso(T_wl))
+    R, t = iso_mul(iso_mul(Tbc, prior), Tcb)
+    return np.array([t[0], t[1], np.arctan2(R[1, 0], R[0, 0])], F)
+
+
+# ---- per-edge terms ----------------------------------------------------------
+def jacobian_residual(L, X, uv, fx, fy, cx, cy, R_cb, c, s):
+    """:1454-1515, vectorised over points.  L = points in this camera, X = the
+    input (base-1) points.  Returns r [n,2], Ju [n,3], Jv [n,3]."""
+    fx, fy, cx, cy = F(fx), F(fy), F(cx), F(cy)
+    r11, r12, r21, r22, r31, r32 = (R_cb[0, 0], R_cb[0, 1], R_cb[1, 0], R_cb[1, 1],
+                                    R_cb[2, 0], R_cb[2, 1])
+    inverse_z = F(1) / L[:, 2]
+    x_inverse_z = L[:, 0] * inverse_z
+    y_inverse_z = L[:, 1] * inverse_z
+    fx_x_inverse_z = fx * x_inverse_z
+    fy_y_inverse_z = fy * y_inverse_z
+    projected_u = fx_x_inverse_z + cx
+    projected_v = fy_y_inverse_z + cy
+    r = np.stack([projected_u - uv[:, 0], projected_v - uv[:, 1]], 1)
+    alpha_1 = fx * inverse_z
+    alpha_2 = -fx_x_inverse_z * inverse_z
+    beta_1 = fy * inverse_z
+    beta_2 = -fy_y_inverse_z * inverse_z
+    xb, yb = X[:, 0], X[:, 1]
+    A = -s * xb - c * yb
+    B = c * xb - s * yb
+    Ju0 = alpha_1 * r11 + alpha_2 * r31
+    Ju1 = alpha_1 * r12 + alpha_2 * r32
+    Jv0 = beta_1 * r21 + beta_2 * r31
+    Jv1 = beta_1 * r22 + beta_2 * r32
+    Ju = np.stack([Ju0, Ju1, Ju0 * A + Ju1 * B], 1)
+    Jv = np.stack([Jv0, Jv1, Jv0 * A + Jv1 * B], 1)
+    return r.astype(F), Ju.astype(F), Jv.astype(F)
+
+
+def residual(theta, X, uv, fx, fy, cx, cy, T_cam_b1):
+    """Reprojection residual at theta for a camera whose pose relative to base-2
+    is T_cam_b1(theta) = T_cam_base * pose_b2b1(theta) (no Jacobian)."""
+    L = warp(iso_mul(T_cam_b1, planar_iso(*theta)), X)
+    iz = F(1) / L[:, 2]
+    return np.stack([F(fx) * (L[:, 0] * iz) + F(cx) - uv[:, 0],
+                     F(fy) * (L[:, 1] * iz) + F(cy) - uv[:, 1]], 1)
+
+
+def warp(P, X):
+    R, t = P
+    return (X @ R.T + t).astype(F)
+
+
+def gradient_hessian(r, Ju, Jv, thr_huber):
+    """:1516-1583 — per-edge upper H (6: 00 01 02 11 12 22), gradient JtWr (3),
+    error (Q9: Huber adds only error_u, otherwise only error_v) and the
+    non-weighted error."""
+    thr = F(thr_huber)
+    ru, rv = r[:, 0], r[:, 1]
+    ars = np.abs(ru) + np.abs(rv)
+    hub = ars >= thr
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = np.where(hub, thr / ars, F(1)).astype(F)
+    wJu = np.where(hub[:, None], w[:, None] * Ju, Ju)
+    wJv = np.where(hub[:, None], w[:, None] * Jv, Jv)
+    H = np.stack([wJu[:, a] * Ju[:, b] + wJv[:, a] * Jv[:, b]
+                  for a, b in ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))], 1)
+    wru = np.where(hub, w * ru, ru)
+    wrv = np.where(hub, w * rv, rv)
+    g = wru[:, None] * Ju + wrv[:, None] * Jv
+    err = np.where(hub, wru * ru, rv * rv)
+    return H.astype(F), g.astype(F), err.astype(F), ars.astype(F)
+
+
+def ldlt_solve(A, b):
+    """Eigen's LDLT (pivoted on the largest remaining diagonal) solve, fp32."""
+    n = A.shape[0]
+    m = np.array(A, F)
+    d = np.array(b, F)
+    tr = list(range(n))
+    for k in range(n):
+        big = k + int(np.argmax(np.abs(np.diag(m)[k:])))
+        tr[k] = big
+        if big != k:
+            m[[k, big], :k] = m[[big, k], :k]
+            m[big + 1:, [k, big]] = m[big + 1:, [big, k]]
+            m[k, k], m[big, big] = m[big, big], m[k, k]
+            for i in range(k + 1, big):
+                m[i, k], m[big, i] = m[big, i], m[i, k]
+        if k > 0:
+            tmp = (np.diag(m)[:k] * m[k, :k]).astype(F)
+            m[k, k] -= F(m[k, :k] @ tmp)
+            if k + 1 < n:
+                m[k + 1:, k] -= (m[k + 1:, :k] @ tmp).astype(F)
+        if k == 0 and m[0, 0] == 0:
+            tr = list(range(n))
+            break
+        if k + 1 < n and m[k, k] != 0:
+            m[k + 1:, k] /= m[k, k]
+    for i in range(n):
+        if tr[i] != i:
+            d[i], d[tr[i]] = d[tr[i]], d[i]
+    for i in range(n):
+        d[i] -= F(m[i, :i] @ d[:i])
+    for i in range(n):
+        d[i] = d[i] / m[i, i] if abs(m[i, i]) > np.finfo(F).tiny else F(0)
+    for i in range(n - 1, -1, -1):
+        d[i] -= F(m[i + 1:, i] @ d[i + 1:])
+    for i in range(n - 1, -1, -1):
+        if tr[i] != i:
+            d[i], d[tr[i]] = d[tr[i]], d[i]
+    return d
+
+
+# ---- the solvers ---------------------------------------------------------------
+def solve(X, uv, fx, fy, cx, cy, T_bc, T_wl, T_wc, mask, max_iter=50,
+          thr_step=1e-5, thr_cost=1e-5, huber=1.0, outlier=2.0, uv_right=None,
+          intr_r=None, T_lr=None, mask_r=None):
+    """Solve_Monocular_Planar3Dof (uv_right None) or Solve_Stereo_Planar3Dof.
+    Poses are 4x4; returns the dict the GPU path returns (T12 = the
+    world_to_current written back, or the input when not written)."""
+    stereo = uv_right is not None
+    X = np.asarray(X, F).reshape(-1, 3)
+    uv = np.asarray(uv, F).reshape(-1, 2)
+    n = X.shape[0]
+    mask = np.asarray(mask, bool).copy()
+    inverse_n_pts = F(1) / F(n)
+    Tbc = iso(T_bc)
+    Tcb = iso_inv(Tbc)                                   # :446
+    R_cb = Tcb[0]
+    if stereo:
+        uvr = np.asarray(uv_right, F).reshape(-1, 2)
+        mask_r = np.asarray(mask_r, bool).copy()
+        Trl = iso_inv(iso(T_lr))                         # :674
+        R_rb = (Trl[0] @ Tcb[0]).astype(F)               # :678-679
+        has_r = ~((uvr[:, 0] < 0) | (uvr[:, 1] < 0))     # :785
+    theta = prior_theta(T_bc, T_wl, T_wc)                # :450-466
+    T_out = iso(T_wc)
+    err_prev = F(1e10)
+    lam = F(1e-5)
+    converged, success = True, True
+    rows, debug = [], []
+    n_iter = 0
+    Pb = None
+    for iteration in range(max_iter):
+        c, s = F(np.cos(theta[2])), F(np.sin(theta[2]))   # :484-485
+        Pb = planar_iso(theta[0], theta[1], theta[2])
+        Pl = iso_mul(Tcb, Pb)                             # :490 / :724
+        Hu, g, err, ars = gradient_hessian(
+            *jacobian_residual(warp(Pl, X), X, uv, fx, fy, cx, cy, R_cb, c, s), huber)
+        mask &= ~(ars >= F(outlier))
+        JtWJ = Hu.sum(0, dtype=F)
+        mJtWr = -g.sum(0, dtype=F)
+        err_curr = err.sum(dtype=F)
+        count_r = 0
+        if stereo:
+            Pr = iso_mul(Trl, Pl)                         # :726-727
+            Hr, gr, er, arr = gradient_hessian(
+                *jacobian_residual(warp(Pr, X)[has_r], X[has_r], uvr[has_r],
+                                   intr_r[0], intr_r[1], intr_r[2], intr_r[3],
+                                   R_rb, c, s), huber)
+            mask_r[np.nonzero(has_r)[0][arr >= F(outlier)]] = False
+            JtWJ = JtWJ + Hr.sum(0, dtype=F)
+            mJtWr = mJtWr - gr.sum(0, dtype=F)
+            err_curr = err_curr + er.sum(dtype=F)
+            count_r = int(has_r.sum())
+        H = np.zeros((3, 3), F)
+        H[np.triu_indices(3)] = JtWJ
+        H = np.triu(H) + np.triu(H, 1).T                  # :531
+        for i in range(3):
+            H[i, i] *= F(1) + lam                         # :532
+        delta = ldlt_solve(H, mJtWr)                      # :534
+        dx, dy, dpsi = delta
+        D = planar_iso(dx, dy, dpsi)                      # :536-542
+        Pb = iso_mul(D, Pb)                               # :543
+        theta = np.array([Pb[1][0], Pb[1][1], theta[2] + dpsi], F)   # :545-547
+        W = iso_mul(iso_inv(Pb), Tbc)                     # :549-550
+        debug.append(iso12(W))
+        T_out = W
+        if stereo:
+            err_curr = F(err_curr / (F(n + count_r) * F(0.5)))  # :842
+        else:
+            err_curr = F(err_curr * (inverse_n_pts * F(0.5)))    # :553
+        delta_error = F(abs(err_curr - err_prev))
+        step = F(np.sqrt(F(dx * dx + dy * dy + dpsi * dpsi)))
+        n_iter = iteration + 1
+        if step < F(thr_step) or delta_error < F(thr_cost):
+            converged = True
+            break
+        if iteration == max_iter - 1:
+            converged = False
+        rows.append((float(err_curr), float(delta_error), float(step)))
+        err_prev = err_curr
+    T12_in = iso12(iso(T_wc))
+    if Pb is None:                      # max_iter = 0 (undefined in the reference)
+        T12 = T12_in
+    elif np.isnan(np.linalg.norm(Pb[0])):
+        T12, success = T12_in, False    # :604-612
+    else:
+        T12 = iso12(T_out)
+    out = dict(T12=T12, n_iter=n_iter, converged=converged, success=success,
+               rows=rows, debug=np.array(debug, F).reshape(-1, 12), theta=theta)
+    if stereo:
+        out.update(mask_l=mask, mask_r=mask_r)
+    else:
+        out.update(mask=mask)
+    return out
