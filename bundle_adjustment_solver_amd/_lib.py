@@ -125,6 +125,13 @@ SIGNATURES = {
     "ba_lm_iterate": (C.c_int, [_P, C.c_int]),
     "ba_lm_sync": (C.c_int, [_P, C.POINTER(BaIterInfo), C.c_int,
                              C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ba_gd_begin": (C.c_int, [_P, C.POINTER(BaOptions)]),
+    "ba_gd_iterate": (C.c_int, [_P, C.c_int]),
+    "ba_gd_sync": (C.c_int, [_P, C.POINTER(BaIterInfo), C.c_int,
+                             C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ba_solve_gd": (C.c_int, [_P, C.POINTER(BaOptions), C.POINTER(BaIterInfo),
+                              C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ba_gd_get_gradient": (C.c_int, [_P, _D, _D]),
     "ba_stage_cost": (C.c_int, [_P, _D]),
     "ba_stage_linearize": (C.c_int, [_P, C.c_double, C.c_double]),
     "ba_stage_schur": (C.c_int, [_P]),

@@ -775,6 +775,7 @@ int ba_update_values(ba_handle *h, const double *T_jw12, const double *X3) {
   }
   h->gathered_valid = false;
   h->lm_begun = false;   // the blocks on the device belong to the old values: ba_lm_begin linearises again
+  h->gd_begun = false;   // (the GD index stays: it depends on the structure only)
   h->tiles_ready = false;
   return 0;
 }
@@ -859,6 +860,7 @@ int ba_lm_begin(ba_handle *h, const ba_options *opt) {
   join_side(h);
   int done_after = 0;
   if (ba::lm_prepare_ctrl(h, opt, &done_after)) return -1;
+  h->gd_begun = false;
   // first linearisation, at the starting point; previous_cost =
   // EvaluateCurrentCost() (reference :707) is the sum of its residual norms
   enqueue_linearize(h, 0);
@@ -876,6 +878,8 @@ int ba_lm_begin(ba_handle *h, const ba_options *opt) {
 }
 
 int ba_lm_iterate(ba_handle *h, int n) {
+  if (h && !h->lm_begun && h->gd_begun)
+    return fail("ba_lm_iterate: the handle is in a gradient-descent loop (ba_gd_begin); call ba_lm_begin first");
   if (!h || !h->lm_begun) return fail("ba_lm_iterate: call ba_lm_begin first");
   if (use_device(h)) return -1;
   h->gathered_valid = false;
@@ -956,6 +960,167 @@ int ba_solve(ba_handle *h, const ba_options *opt, ba_iter_info *out, int cap,
   }
   int rc = ba_lm_sync(h, out, cap, n_iter, converged);
   return rc < 0 ? -1 : 0;
+}
+
+// ---------------------------------------------------------------------------
+// gradient descent, FullBundleAdjustmentSolverRefactor::SolveByGradientDescent
+// (reference core/full_bundle_adjustment_solver_refactor.cpp:1075-1367)
+
+// Device state of the GD loop, built once per ba_finalize on the first GD call: the
+// pose-major index of every real observation of an optimisable pose (stable in the
+// landmark-major order, padded slots left out), its chunks and the partial-sum arrays.
+// The LM path's lists and buffers are not touched.
+static int gd_prepare(ba_handle *h, const char *who) {
+  if (h->world > 1 || h->ar_fn)
+    return fail(std::string(who) + ": gradient descent runs on one GPU; this handle is sharded "
+                "(ba_set_shard with world > 1, or an all-reduce hook is set)");
+  if (h->gd_ready) return 0;
+  const ba::Plan &pl = h->plan;
+  const ba::DevProblem &d = h->d;
+  const int N = pl.N;
+  std::vector<int64_t> ptr((size_t)N + 1, 0);
+  auto real = [&](int64_t s) { return pl.obs_uv[2 * s] == pl.obs_uv[2 * s]; };  // (uv = NaN: padded slot)
+  for (int64_t s = 0; s < pl.n_obs; ++s) {
+    const int j = pl.obs_idx[4 * s + 1];
+    if (j < N && real(s)) ptr[j + 1]++;
+  }
+  for (int j = 0; j < N; ++j) ptr[j + 1] += ptr[j];
+  const int64_t n = ptr[N];
+  std::vector<int32_t> pobs((size_t)n * 2);
+  std::vector<double> puv((size_t)n * 2);
+  {
+    std::vector<int64_t> cur(ptr.begin(), ptr.end() - 1);
+    for (int64_t s = 0; s < pl.n_obs; ++s) {
+      const int j = pl.obs_idx[4 * s + 1];
+      if (j >= N || !real(s)) continue;
+      const int64_t o = cur[j]++;
+      pobs[2 * o + 0] = pl.obs_idx[4 * s + 0];  // camera
+      pobs[2 * o + 1] = pl.obs_idx[4 * s + 2];  // point
+      puv[2 * o + 0] = pl.obs_uv[2 * s + 0];
+      puv[2 * o + 1] = pl.obs_uv[2 * s + 1];
+    }
+  }
+  std::vector<int32_t> chunk_pose, pose_chunk_ptr((size_t)N + 1, 0);
+  std::vector<int64_t> chunk_begin, chunk_end;
+  for (int j = 0; j < N; ++j) {
+    for (int64_t b = ptr[j]; b < ptr[j + 1]; b += ba::kGdChunk) {
+      chunk_pose.push_back(j);
+      chunk_begin.push_back(b);
+      chunk_end.push_back(std::min<int64_t>(b + ba::kGdChunk, ptr[j + 1]));
+    }
+    pose_chunk_ptr[j + 1] = (int32_t)chunk_pose.size();
+  }
+  ba::GdDev &g = h->gd;
+  g = ba::GdDev{};
+  g.n_chunk = (int)chunk_pose.size();
+  const int64_t n_fix = d.n_obs - d.n_obs_lm;
+  g.n_fix_blk = n_fix > 0 ? (int)std::min<int64_t>(ba::kGdFixGrid, (n_fix + 255) / 256) : 0;
+  g.n_cost_part = d.n_bchunk + g.n_fix_blk;
+  g.n_upd_pose_blk = (N + 255) / 256;
+  g.n_upd_blk = g.n_upd_pose_blk + (d.M + 255) / 256;
+  h->kind(0);
+  static_assert(sizeof(int2) == 8 && sizeof(double2) == 16, "layout");
+  if (h->dalloc(&g.pobs, (size_t)n) || h->dalloc(&g.puv, (size_t)n) || h->upload(&g.chunk_pose, chunk_pose) ||
+      h->upload(&g.chunk_begin, chunk_begin) || h->upload(&g.chunk_end, chunk_end) ||
+      h->upload(&g.pose_chunk_ptr, pose_chunk_ptr) || h->dalloc(&g.ppart, (size_t)g.n_chunk * 6) ||
+      h->dalloc(&g.a, (size_t)N * 6) || h->dalloc(&g.b, (size_t)d.M * 3) ||
+      h->dalloc(&g.cost_part, (size_t)g.n_cost_part) || h->dalloc(&g.step_part, (size_t)g.n_upd_blk * 2))
+    return -1;
+  if (n > 0) {
+    HIP_TRY(hipMemcpy(g.pobs, pobs.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g.puv, puv.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemset(g.a, 0, std::max<size_t>(1, (size_t)N * 6) * sizeof(double)));
+  HIP_TRY(hipMemset(g.b, 0, std::max<size_t>(1, (size_t)d.M * 3) * sizeof(double)));
+  h->gd_ready = true;
+  return 0;
+}
+
+int ba_gd_begin(ba_handle *h, const ba_options *opt) {
+  if (!h || !opt) return fail("ba_gd_begin: bad argument");
+  if (!h->finalized && ba_finalize(h)) return -1;
+  if (use_device(h)) return -1;
+  if (gd_prepare(h, "ba_gd_begin")) return -1;
+  if (h->plan.n_obs_global < 1) return fail("ba_gd_begin: num_observations < 1");  // reference :1269
+  join_side(h);
+  int done_after = 0;
+  if (ba::lm_prepare_ctrl(h, opt, &done_after)) return -1;  // (lambda stays initial_lambda: the rows' damping term)
+  h->lm_begun = false;
+  // previous_cost = EvaluateCurrentCost() (reference :1158) and the first gradient
+  ba::launch_gd_pass(h->d, h->gd, h->stream);
+  ba::launch_gd_control(h->d, h->gd, 0, h->stream);
+  if (done_after) {
+    if (pull_ctrl(h)) return -1;
+    h->hc.done = 1;
+    if (push_ctrl(h)) return -1;
+  }
+  HIP_TRY(hipGetLastError());
+  h->gd_begun = true;
+  return 0;
+}
+
+int ba_gd_iterate(ba_handle *h, int n) {
+  if (!h) return fail("ba_gd_iterate: null handle");
+  if (!h->gd_begun)
+    return fail(h->lm_begun ? "ba_gd_iterate: the handle is in an LM loop (ba_lm_begin); call ba_gd_begin first"
+                            : "ba_gd_iterate: call ba_gd_begin first");
+  if (use_device(h)) return -1;
+  h->gathered_valid = false;
+  for (int k = 0; k < n; ++k) {
+    ba::launch_gd_update(h->d, h->gd, h->stream);
+    ba::launch_gd_pass(h->d, h->gd, h->stream);
+    ba::launch_gd_control(h->d, h->gd, 1, h->stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int ba_gd_sync(ba_handle *h, ba_iter_info *out, int cap, int *n_iter, int *converged) {
+  if (!h) return fail("ba_gd_sync: null handle");
+  if (!h->gd_begun) return fail("ba_gd_sync: call ba_gd_begin first");
+  if (use_device(h)) return -1;
+  if (pull_ctrl(h)) return -1;
+  const int n = h->hc.iter;
+  if (n_iter) *n_iter = n;
+  if (converged) *converged = h->hc.converged;
+  if (out && cap > 0 && n > 0) {
+    const int m = std::min(std::min(n, cap), h->d.log_cap);
+    HIP_TRY(hipMemcpy(out, h->d.log, (size_t)m * sizeof(ba_iter_info), hipMemcpyDeviceToHost));
+  }
+  return h->hc.done ? 1 : 0;
+}
+
+int ba_solve_gd(ba_handle *h, const ba_options *opt, ba_iter_info *out, int cap, int *n_iter, int *converged) {
+  if (ba_gd_begin(h, opt)) return -1;
+  int done = opt->max_num_iterations <= 0;
+  int issued = 0;
+  while (!done) {
+    const int batch = std::min(8, opt->max_num_iterations - issued);
+    if (batch <= 0) break;
+    if (ba_gd_iterate(h, batch)) return -1;
+    issued += batch;
+    const int rc = ba_gd_sync(h, nullptr, 0, nullptr, nullptr);
+    if (rc < 0) return -1;
+    done = rc;
+  }
+  const int rc = ba_gd_sync(h, out, cap, n_iter, converged);
+  return rc < 0 ? -1 : 0;
+}
+
+int ba_gd_get_gradient(ba_handle *h, double *a6, double *b3) {
+  if (!h || !h->finalized) return fail("ba_gd_get_gradient: not finalized");
+  if (!h->gd_ready) return fail("ba_gd_get_gradient: call ba_gd_begin first");
+  if (use_device(h)) return -1;
+  const ba::Plan &pl = h->plan;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (a6 && pl.N > 0) HIP_TRY(hipMemcpy(a6, h->gd.a, (size_t)pl.N * 6 * sizeof(double), hipMemcpyDeviceToHost));
+  if (b3) {
+    std::vector<double> b;
+    if (download(b, h->gd.b, (size_t)pl.M * 3, h->stream)) return -1;
+    for (int i = 0; i < pl.M; ++i)
+      std::memcpy(b3 + (size_t)pl.iopt_of_user[pl.pt_user_of_int[i]] * 3, &b[(size_t)i * 3], 3 * sizeof(double));
+  }
+  return 0;
 }
 
 // ---------------------------------------------------------------------------

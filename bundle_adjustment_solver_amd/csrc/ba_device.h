@@ -195,6 +195,8 @@ constexpr int kBsChunks = 4;     // chunks per chunk-role workgroup of k_backsub
 constexpr int kCostGrid = 1792;  // 7 waves/SIMD resident on 256 CUs
 constexpr int kLmGrid = 1024;
 constexpr int kPoseGrid = 16;
+constexpr int kGdFixGrid = 1024;     // k_gd_points workgroups for the observations of fixed landmarks
+constexpr int kGdChunk = 512;        // observations per k_gd_poses wave (one pose's list is cut into chunks)
 constexpr int kSlotStride = 42;  // 6x6 block of B Cinv B^T + 6 of B Cinv b
 // dense workspace per 64-column block: L11 (64x64) + four 16x16 tile inverses
 
@@ -261,6 +263,38 @@ void launch_scalars_and_control(const DevProblem &d, int cost_src, hipStream_t s
                                 int finalize_sel = -1);  // single GPU; finalize_sel >= 0: + k_pose_finalize workgroups
 void launch_control(const DevProblem &d, hipStream_t s);
 void launch_init_ctrl_cost(const DevProblem &d, hipStream_t s);
+
+// ---- gradient descent (FullBundleAdjustmentSolverRefactor::SolveByGradientDescent) ----
+// Device state of the first-order loop (ba_gd_*), allocated on the first GD call after
+// ba_finalize.  It reads the problem's parameter buffer ctrl->cur and updates it in
+// place; the LM blocks, lists and schedules are not touched.
+struct GdDev {
+  // pose-major index of EVERY real observation of an optimisable pose (the LM
+  // pose-major list leaves out the covisibility groups; padded slots are not in it),
+  // landmark-major order inside a pose, cut into chunks of one pose each
+  int2 *pobs;       // {camera, point}
+  double2 *puv;
+  int32_t *chunk_pose;
+  int64_t *chunk_begin, *chunk_end;
+  int32_t *pose_chunk_ptr;  // N+1
+  int n_chunk;
+  double *ppart;      // n_chunk*6: sum of Q^T w r per chunk
+  double *a;          // N*6: a_j = -sum Q^T w r (unclipped)
+  double *b;          // M*3: b_i = -sum R^T w r (unclipped)
+  double *cost_part;  // n_cost_part: sum of ||r|| per k_gd_points workgroup
+  int n_cost_part;    // n_bchunk landmark chunks, then n_fix_blk blocks of fixed-landmark observations
+  int n_fix_blk;
+  double *step_part;  // n_upd_blk*2: {sum ||a_j||, sum ||b_i||} of the clipped blocks per workgroup
+  int n_upd_pose_blk, n_upd_blk;
+};
+// pass over the observations at the current parameters: cost partials, b_i (landmark
+// chunks) and the pose chunk partials
+void launch_gd_pass(const DevProblem &d, const GdDev &g, hipStream_t s);
+// mode 0: initial cost (previous_cost of reference :1158); 1: log row, stop rule.
+// Both also sum the pose chunk partials into a_j.
+void launch_gd_control(const DevProblem &d, const GdDev &g, int mode, hipStream_t s);
+// clip, T_jw <- exp(a_j) T_jw, X_i <- X_i + b_i, step-norm partials
+void launch_gd_update(const DevProblem &d, const GdDev &g, hipStream_t s);
 
 // ---- dense solver (ba_dense.hip) ----
 // Factor the npad x npad lower matrix in d.L (with the rhs carried as row

@@ -103,6 +103,12 @@ struct ba_handle {
   ba::DenseSchedule sched;   // level schedule of the reduced-system Cholesky
   ba::DenseDev ddev;
   std::vector<int> pose_col_h;
+  // gradient descent (ba_gd_*): device state built on the first GD call after
+  // ba_finalize (in `allocs`: freed with the problem), and which loop the
+  // controller belongs to — ba_lm_iterate and ba_gd_iterate refuse each other's
+  bool gd_ready = false;
+  bool gd_begun = false;
+  ba::GdDev gd{};
   // pose-only scratch (grown on demand, reused across calls)
   // pose-only: one device buffer + its pinned host mirror (po_run), barrier scratch
   uint8_t *po_dev = nullptr, *po_host = nullptr;
@@ -178,6 +184,9 @@ struct ba_handle {
     gbuf_bound = false;
     pt_user_dev = nullptr;
     gathered_valid = false;
+    gd_ready = false;
+    gd_begun = false;
+    gd = ba::GdDev{};
     finalized = false;
   }
 };

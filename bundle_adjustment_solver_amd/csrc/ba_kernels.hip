@@ -2089,6 +2089,46 @@ __device__ __forceinline__ void st_sc1(double *p, double v) {
   else
     *p = v;
 }
+// se3 exponential of x = (v, w) (reference :1370-1409): exp(x) = [dR, dt] with dR the
+// Rodrigues rotation of w and dt = V v.  Shared by the LM pose update and the
+// gradient-descent update (k_gd_update), so both move a pose by the same arithmetic.
+__device__ __forceinline__ void se3_exp(const double v0, const double v1, const double v2, const double w0,
+                                        const double w1, const double w2, double dR[9], double dt[3]) {
+  const double theta = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+  const double wx[9] = {0, -w2, w1, w2, 0, -w0, -w1, w0, 0};
+  double wx2[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      wx2[r * 3 + c] = wx[r * 3 + 0] * wx[0 * 3 + c] +
+                       wx[r * 3 + 1] * wx[1 * 3 + c] +
+                       wx[r * 3 + 2] * wx[2 * 3 + c];
+  double ca, cb, va, vb;
+  if (theta < 1e-7) {
+    ca = 1.0;
+    cb = 0.5;
+    va = 0.5;
+    vb = 0.33333333333333333333333333;
+  } else {
+    const double st = sin(theta), ct = cos(theta);
+    ca = st / theta;
+    cb = (1.0 - ct) / (theta * theta);
+    va = cb;
+    vb = (theta - st) / (theta * theta * theta);
+  }
+  double V[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const double id = (k % 4 == 0) ? 1.0 : 0.0;
+    dR[k] = id + ca * wx[k] + cb * wx2[k];
+    V[k] = id + va * wx[k] + vb * wx2[k];
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    dt[r] = V[r * 3 + 0] * v0 + V[r * 3 + 1] * v1 + V[r * 3 + 2] * v2;
+}
+
 // (SC1 — k_backsub_lin: the new poses are read by workgroups of the same launch on other XCDs,
 //  whose L2 is a different one: they leave with sc1 stores)
 template <bool SC1 = false>
@@ -2107,39 +2147,8 @@ __device__ __forceinline__ void pose_update_body(const DevProblem &d, const int 
     const double *xj = d.x + (size_t)j * 6;
     const double v0 = xj[0], v1 = xj[1], v2 = xj[2];
     const double w0 = xj[3], w1 = xj[4], w2 = xj[5];
-    const double theta = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-    const double wx[9] = {0, -w2, w1, w2, 0, -w0, -w1, w0, 0};
-    double wx2[9];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        wx2[r * 3 + c] = wx[r * 3 + 0] * wx[0 * 3 + c] +
-                         wx[r * 3 + 1] * wx[1 * 3 + c] +
-                         wx[r * 3 + 2] * wx[2 * 3 + c];
-    double ca, cb, va, vb;
-    if (theta < 1e-7) {
-      ca = 1.0;
-      cb = 0.5;
-      va = 0.5;
-      vb = 0.33333333333333333333333333;
-    } else {
-      const double st = sin(theta), ct = cos(theta);
-      ca = st / theta;
-      cb = (1.0 - ct) / (theta * theta);
-      va = cb;
-      vb = (theta - st) / (theta * theta * theta);
-    }
-    double dR[9], V[9], dt[3];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const double id = (k % 4 == 0) ? 1.0 : 0.0;
-      dR[k] = id + ca * wx[k] + cb * wx2[k];
-      V[k] = id + va * wx[k] + vb * wx2[k];
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      dt[r] = V[r * 3 + 0] * v0 + V[r * 3 + 1] * v1 + V[r * 3 + 2] * v2;
+    double dR[9], dt[3];
+    se3_exp(v0, v1, v2, w0, w1, w2, dR, dt);
     const double *T = Tc + (size_t)j * 12;
     double *To = Tt + (size_t)j * 12;
 #pragma unroll
@@ -2943,6 +2952,297 @@ __global__ void k_control(DevProblem d) {
   control_step(d);
 }
 
+// --------------------------------------------------------------------------
+// Gradient descent of the refactored solver (reference
+// core/full_bundle_adjustment_solver_refactor.cpp:1075-1367).  One iteration is
+//   k_gd_update   clip a_j, b_i to norm <= 1e-3, T_jw <- exp(a_j) T_jw, X_i += b_i
+//                 (in place, every step accepted), step-norm partials
+//   k_gd_points   pass over the landmark-major list at the new point: sum of ||r||
+//                 (all observations, :375-427) and b_i = -sum R^T w r, per landmark in
+//                 list order
+//   k_gd_poses    pass over the GD pose-major index: per chunk sum of Q^T w r
+//   k_gd_control  a_j from the chunk partials; the log row of the iteration, the stop
+//                 rule (:1269-1311)
+// so that the cost at p_{k+1} (the iteration's current_cost) and the gradient of the
+// next iteration come out of one pass.  Fixed grids, fixed summation order, no atomics.
+// --------------------------------------------------------------------------
+constexpr int kGdCtrlBlock = 1024;
+constexpr double kGdMaxStep = 0.001;  // max_pose_step = max_point_step (:1272-1273)
+
+template <bool LDSCAM>
+__global__ __launch_bounds__(kBlock) void k_gd_points(DevProblem d, GdDev gd) {
+  __shared__ double Gb[kBlock * 3];
+  __shared__ double cams_s[kCamLds * 16];
+  __shared__ int lq[kSchurLandmarks + 1];
+  __shared__ double smc[4];
+  const int tid = threadIdx.x;
+  if (d.ctrl->done) return;
+  const int buf = d.ctrl->cur;
+  const double huber = d.ctrl->huber;
+  const double *__restrict__ poses = d.poses[buf];
+  const double *__restrict__ pts = d.pts[buf];
+  if (LDSCAM) stage_cams(d, cams_s);
+  double cost_acc = 0.0;
+  if ((int)blockIdx.x >= d.n_bchunk) {
+    // observations of fixed landmarks: the cost only
+    __syncthreads();  // cams_s
+    const int64_t stride = (int64_t)gd.n_fix_blk * kBlock;
+    for (int64_t s = d.n_obs_lm + (int64_t)(blockIdx.x - d.n_bchunk) * kBlock + tid; s < d.n_obs; s += stride) {
+      const int4 id = d.obs_idx[s];
+      const double2 uv = d.obs_uv[s];
+      if (uv.x != uv.x) continue;  // padded slot of a masked group (uv = NaN)
+      double cam[16];
+      load_cam<LDSCAM>(d, cams_s, id.x, cam);
+      const double *X = pts + (size_t)id.z * 3;
+      ObsGeom g;
+      project(cam, poses + (size_t)id.y * 12, X[0], X[1], X[2], uv.x, uv.y, g);
+      cost_acc += sqrt(g.r0 * g.r0 + g.r1 * g.r1);
+    }
+    const double tot = block_sum(cost_acc, smc);
+    if (tid == 0) gd.cost_part[blockIdx.x] = tot;
+    return;
+  }
+  // one landmark chunk (<= kSchurLandmarks landmarks): one thread per observation puts
+  // R^T w r in LDS, one thread per (landmark, component) adds its observations in order
+  const DevProblem::LmChunk lc = d.lm_chunk[blockIdx.x];
+  const int64_t ob = lc.ob, oe = lc.ob + lc.no;
+  if (tid <= lc.nl) lq[tid] = (tid < lc.nl) ? (int)(d.lm_obs_ptr[lc.l0 + tid] - ob) : lc.no;
+  double bsum = 0.0;
+  const int li = tid / 3, v = tid - 3 * (tid / 3);
+  __syncthreads();  // cams_s, lq
+  for (int64_t t0 = ob; t0 < oe; t0 += kBlock) {
+    const int64_t s = t0 + tid;
+    double g0 = 0.0, g1 = 0.0, g2 = 0.0;
+    if (s < oe) {
+      const int4 id = d.obs_idx[s];
+      const double2 uv = d.obs_uv[s];
+      if (uv.x == uv.x) {  // (padded slots of masked groups: no observation)
+#pragma clang fp contract(fast)
+        double cam[16];
+        load_cam<LDSCAM>(d, cams_s, id.x, cam);
+        const double *T = poses + (size_t)id.y * 12;
+        const double *X = pts + (size_t)id.z * 3;
+        ObsGeom g;
+        project(cam, T, X[0], X[1], X[2], uv.x, uv.y, g);
+        cost_acc += sqrt(g.r0 * g.r0 + g.r1 * g.r1);
+        double w, G[6], Rm[6];
+        weight_and_G(cam, g, huber, w, G);
+        make_R(G, T, Rm);
+        const double wr0 = w * g.r0, wr1 = w * g.r1;
+        g0 = Rm[0] * wr0 + Rm[3] * wr1;
+        g1 = Rm[1] * wr0 + Rm[4] * wr1;
+        g2 = Rm[2] * wr0 + Rm[5] * wr1;
+      }
+    }
+    Gb[tid * 3 + 0] = g0;
+    Gb[tid * 3 + 1] = g1;
+    Gb[tid * 3 + 2] = g2;
+    __syncthreads();
+    if (li < lc.nl) {
+      const int o0 = (int)(t0 - ob);
+      const int a = max(lq[li], o0), b = min(lq[li + 1], o0 + kBlock);
+      double acc = 0.0;
+      for (int k = a; k < b; ++k) acc += Gb[(k - o0) * 3 + v];
+      bsum += acc;
+    }
+    __syncthreads();
+  }
+  if (li < lc.nl) gd.b[(size_t)(lc.l0 + li) * 3 + v] = -bsum;  // reference :1262  b_i -= R^T (w r)
+  const double tot = block_sum(cost_acc, smc);
+  if (tid == 0) gd.cost_part[blockIdx.x] = tot;
+}
+static_assert(kSchurLandmarks * 3 <= kBlock, "one thread per (landmark, component) of a chunk");
+
+// one WAVE per chunk of one pose's observations (the GD pose-major index): 6 sums
+template <bool LDSCAM>
+__global__ __launch_bounds__(kBlock) void k_gd_poses(DevProblem d, GdDev gd) {
+  __shared__ double cams_s[kCamLds * 16];
+  if (LDSCAM) stage_cams(d, cams_s);
+  const int lane = threadIdx.x & 63;
+  const int ch = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
+  const bool live = ch < gd.n_chunk;
+  __syncthreads();  // cams_s
+  if (d.ctrl->done || !live) return;
+  const int64_t b = gd.chunk_begin[ch], e = gd.chunk_end[ch];
+  const int j = gd.chunk_pose[ch];
+  const int buf = d.ctrl->cur;
+  const double huber = d.ctrl->huber;
+  const double *__restrict__ pts = d.pts[buf];
+  double T[12];
+  {
+    const double *Tp = d.poses[buf] + (size_t)j * 12;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = Tp[k];
+  }
+  double acc[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) acc[k] = 0.0;
+  for (int64_t s = b + lane; s < e; s += 64) {
+#pragma clang fp contract(fast)
+    const int2 id = gd.pobs[s];
+    const double2 uv = gd.puv[s];
+    const double *X = pts + (size_t)id.y * 3;
+    double cam[16];
+    load_cam<LDSCAM>(d, cams_s, id.x, cam);
+    ObsGeom g;
+    project(cam, T, X[0], X[1], X[2], uv.x, uv.y, g);
+    double w, G[6], Q[12];
+    weight_and_G(cam, g, huber, w, G);
+    make_Q(G, g.Xij, Q);
+    const double wr0 = w * g.r0, wr1 = w * g.r1;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) acc[c] = fma(Q[c], wr0, fma(Q[6 + c], wr1, acc[c]));
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const double tot = wave_sum(acc[k]);
+    if (lane == 0) gd.ppart[(size_t)ch * 6 + k] = tot;
+  }
+}
+
+// One thread per optimised pose (workgroups [0, n_upd_pose_blk)) or point (the rest):
+// clip (:1275-1282), update in place (:482-503), norm of the clipped block (:1294-1300).
+__global__ __launch_bounds__(kBlock) void k_gd_update(DevProblem d, GdDev gd) {
+  __shared__ double sm[8];
+  if (d.ctrl->done) return;
+  const int buf = d.ctrl->cur;
+  double np = 0.0, nq = 0.0;
+  if ((int)blockIdx.x < gd.n_upd_pose_blk) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j < d.N) {
+      double x[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) x[k] = gd.a[(size_t)j * 6 + k];
+      double n2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) n2 += x[k] * x[k];
+      const double nrm = sqrt(n2);
+      if (nrm > kGdMaxStep) {
+        const double sc = kGdMaxStep / nrm;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x[k] = x[k] * sc;
+      }
+      double c2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) c2 += x[k] * x[k];
+      np = sqrt(c2);
+      double dR[9], dt[3];
+      se3_exp(x[0], x[1], x[2], x[3], x[4], x[5], dR, dt);
+      double *T = d.poses[buf] + (size_t)j * 12;
+      double Ti[12], To[12];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) Ti[k] = T[k];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          To[r * 3 + c] = dR[r * 3 + 0] * Ti[0 * 3 + c] + dR[r * 3 + 1] * Ti[1 * 3 + c] + dR[r * 3 + 2] * Ti[2 * 3 + c];
+        To[9 + r] = dR[r * 3 + 0] * Ti[9] + dR[r * 3 + 1] * Ti[10] + dR[r * 3 + 2] * Ti[11] + dt[r];
+      }
+#pragma unroll
+      for (int k = 0; k < 12; ++k) T[k] = To[k];
+    }
+  } else {
+    const int i = (blockIdx.x - gd.n_upd_pose_blk) * kBlock + threadIdx.x;
+    if (i < d.M) {
+      double y0 = gd.b[(size_t)i * 3 + 0], y1 = gd.b[(size_t)i * 3 + 1], y2 = gd.b[(size_t)i * 3 + 2];
+      const double nrm = sqrt(y0 * y0 + y1 * y1 + y2 * y2);
+      if (nrm > kGdMaxStep) {
+        const double sc = kGdMaxStep / nrm;
+        y0 = y0 * sc;
+        y1 = y1 * sc;
+        y2 = y2 * sc;
+      }
+      nq = sqrt(y0 * y0 + y1 * y1 + y2 * y2);
+      double *X = d.pts[buf] + (size_t)i * 3;
+      X[0] = X[0] + y0;
+      X[1] = X[1] + y1;
+      X[2] = X[2] + y2;
+    }
+  }
+  block_sum2(np, nq, sm);
+  if (threadIdx.x == 0) {
+    gd.step_part[2 * blockIdx.x + 0] = np;
+    gd.step_part[2 * blockIdx.x + 1] = nq;
+  }
+}
+
+// Workgroup 0: the scalars and the controller (one thread decides).  Workgroups 1..:
+// a_j = -(sum of the pose's chunk partials in chunk order), one thread per (pose,
+// component) — they do not look at ctrl->done (summing again is idempotent).
+__global__ __launch_bounds__(kGdCtrlBlock) void k_gd_control(DevProblem d, GdDev gd, int mode) {
+  if (blockIdx.x > 0) {
+    const int t = (blockIdx.x - 1) * kGdCtrlBlock + threadIdx.x;
+    if (t >= d.N * 6) return;
+    const int j = t / 6, c = t - 6 * (t / 6);
+    double s = 0.0;
+    for (int ch = gd.pose_chunk_ptr[j]; ch < gd.pose_chunk_ptr[j + 1]; ++ch) s += gd.ppart[(size_t)ch * 6 + c];
+    gd.a[t] = -s;  // reference :1253  a_j -= Q^T (w r)
+    return;
+  }
+  DevCtrl *ctl = d.ctrl;
+  if (ctl->done) return;
+  double c = 0.0, sp = 0.0, sq = 0.0;
+  for (int k = threadIdx.x; k < gd.n_cost_part; k += kGdCtrlBlock) c += gd.cost_part[k];
+  if (mode == 1)
+    for (int k = threadIdx.x; k < gd.n_upd_blk; k += kGdCtrlBlock) {
+      sp += gd.step_part[2 * k + 0];
+      sq += gd.step_part[2 * k + 1];
+    }
+  __shared__ double sm3[3][kGdCtrlBlock / 64];
+  {
+    const double w0 = wave_sum(c), w1 = wave_sum(sp), w2 = wave_sum(sq);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) {
+      sm3[0][wv] = w0;
+      sm3[1][wv] = w1;
+      sm3[2][wv] = w2;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double cost = 0.0, sum_a = 0.0, sum_b = 0.0;
+  for (int w = 0; w < kGdCtrlBlock / 64; ++w) {
+    cost += sm3[0][w];
+    sum_a += sm3[1][w];
+    sum_b += sm3[2][w];
+  }
+  const unsigned long long now = wall_clock64();
+  if (mode == 0) {  // previous_cost = EvaluateCurrentCost() (:1158)
+    ctl->prev_cost = cost;
+    ctl->t_last = now;
+    return;
+  }
+  const double previous_cost = ctl->prev_cost;
+  const double n_obs = (double)d.n_obs_global;
+  const double cost_change = fabs(cost - previous_cost);
+  // (:1294-1304) both sums start at 0.01
+  const double step_pose = 0.01 + sum_a, step_point = 0.01 + sum_b;
+  const double avg_step = (step_point + step_pose) / (double)(d.N + d.M_global);
+  bool conv = (avg_step < ctl->thr_step) || (cost_change < ctl->thr_cost);
+  if (ctl->iter >= ctl->max_iter - 1) conv = false;
+  if (ctl->iter < d.log_cap) {
+    DevIterRec &I = d.log[ctl->iter];
+    I.cost = cost;
+    I.cost_change = cost_change;
+    I.average_reprojection_error = cost / n_obs;  // (no sqrt, unlike the LM rows)
+    I.abs_gradient = 0.0;
+    I.abs_step = avg_step;
+    I.damping_term = ctl->lambda;  // initial_lambda, never changed
+    I.iter_time_ms = (double)(now - ctl->t_last) * 1e-5;  // 100 MHz clock
+    I.iteration_status = 0;        // UPDATE: every step is taken
+    I.pad_ = 0;
+    I.rho = 0.0;
+    I.model_change = 0.0;
+    I.trial_cost = cost;
+  }
+  ctl->t_last = now;
+  ctl->prev_cost = cost;
+  ctl->iter += 1;
+  ctl->converged = conv ? 1 : 0;
+  if (conv || ctl->iter >= ctl->max_iter) ctl->done = 1;
+}
+
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 }  // namespace
@@ -3110,6 +3410,33 @@ void launch_init_ctrl_cost(const DevProblem &d, hipStream_t s) {
 // initial-cost scalar reduction (mode 0)
 void launch_scalars_cost_only(const DevProblem &d, int cost_src, hipStream_t s) {
   BA_LAUNCH(K_SCALARS, k_scalars, dim3(1), dim3(kScalBlock), s, d, 0, cost_src, -1);
+}
+
+void launch_gd_pass(const DevProblem &d, const GdDev &g, hipStream_t s) {
+  const bool lds = d.n_cam <= kCamLds;
+  const int nb = d.n_bchunk + g.n_fix_blk;
+  if (nb > 0) {
+    if (lds)
+      hipLaunchKernelGGL(k_gd_points<true>, dim3(nb), dim3(kBlock), 0, s, d, g);
+    else
+      hipLaunchKernelGGL(k_gd_points<false>, dim3(nb), dim3(kBlock), 0, s, d, g);
+  }
+  if (g.n_chunk > 0) {
+    const dim3 grid(cdiv(g.n_chunk, kBlock / 64));
+    if (lds)
+      hipLaunchKernelGGL(k_gd_poses<true>, grid, dim3(kBlock), 0, s, d, g);
+    else
+      hipLaunchKernelGGL(k_gd_poses<false>, grid, dim3(kBlock), 0, s, d, g);
+  }
+}
+
+void launch_gd_control(const DevProblem &d, const GdDev &g, int mode, hipStream_t s) {
+  hipLaunchKernelGGL(k_gd_control, dim3(1 + cdiv((int64_t)d.N * 6, kGdCtrlBlock)), dim3(kGdCtrlBlock), 0, s, d, g,
+                     mode);
+}
+
+void launch_gd_update(const DevProblem &d, const GdDev &g, hipStream_t s) {
+  if (g.n_upd_blk > 0) hipLaunchKernelGGL(k_gd_update, dim3(g.n_upd_blk), dim3(kBlock), 0, s, d, g);
 }
 
 }  // namespace ba

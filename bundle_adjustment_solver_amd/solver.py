@@ -348,6 +348,40 @@ class BaProblem:
         return ([rows[i] for i in range(min(n.value, cap))], n.value,
                 bool(conv.value), bool(rc))
 
+    # -- gradient descent (reference ..._refactor.cpp:1075-1367) --
+    def solve_gd(self, opt, cap=None):
+        cap = cap or max(1, opt.max_num_iterations)
+        rows = (BaIterInfo * cap)()
+        n = C.c_int(0)
+        conv = C.c_int(0)
+        check(self.lib.ba_solve_gd(self.h, C.byref(opt), rows, cap, C.byref(n),
+                                   C.byref(conv)), "ba_solve_gd")
+        return [rows[i] for i in range(min(n.value, cap))], bool(conv.value)
+
+    def gd_begin(self, opt):
+        check(self.lib.ba_gd_begin(self.h, C.byref(opt)), "ba_gd_begin")
+
+    def gd_iterate(self, n):
+        check(self.lib.ba_gd_iterate(self.h, n), "ba_gd_iterate")
+
+    def gd_sync(self, cap=0):
+        rows = (BaIterInfo * max(cap, 1))()
+        n = C.c_int(0)
+        conv = C.c_int(0)
+        rc = check(self.lib.ba_gd_sync(self.h, rows, cap, C.byref(n),
+                                       C.byref(conv)), "ba_gd_sync")
+        return ([rows[i] for i in range(min(n.value, cap))], n.value,
+                bool(conv.value), bool(rc))
+
+    def gd_gradient(self):
+        """Unclipped (a, b) at the current parameters: a (N, 6) in opt-pose
+        order, b (M, 3) in opt-point order (the layout of get_A / get_C)."""
+        a = np.zeros((self.N, 6))
+        b = np.zeros((self.M_global, 3))
+        check(self.lib.ba_gd_get_gradient(self.h, _dp(a), _dp(b)),
+              "ba_gd_get_gradient")
+        return a, b
+
     # -- stages --
     def stage_cost(self):
         v = C.c_double(0)
@@ -1105,7 +1139,13 @@ class FullBundleAdjustmentSolver:
         c_opt = options.to_c()
         c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
         rows, converged = p.solve(c_opt)
-        # write back through the user's objects (reference :1011-1022)
+        return self._finish_solve(rows, converged, summary, t0)
+
+    def _finish_solve(self, rows, converged, summary, t0):
+        """Write the solution back through the user's objects (reference
+        :1011-1022) and fill the Summary rows; shared by Solve and
+        FullBundleAdjustmentSolverRefactor.SolveByGradientDescent."""
+        p = self._problem
         T_jw = p.get_poses()
         T44 = _T12_to_44(T_jw)
         T44[:, :3, 3] *= INVERSE_SCALER
@@ -1398,7 +1438,8 @@ class FullBundleAdjustmentSolverRefactor(FullBundleAdjustmentSolver):
     117-136: the same device path behind the refactored names, plus the
     solver_type switch of its Solve (reference ..._refactor.cpp:944-982):
     LEVENBERG_MARQUARDT, or GAUSS_NEWTON = every step accepted with lambda fixed
-    at initial_lambda (the default of Options)."""
+    at initial_lambda (the default of Options); and
+    SolveByGradientDescent (reference ..._refactor.cpp:1075-1367)."""
 
     def RegisterCamera(self, camera_id, camera):
         return self.AddCamera(camera_id, camera)
@@ -1419,6 +1460,21 @@ class FullBundleAdjustmentSolverRefactor(FullBundleAdjustmentSolver):
                            "LEVENBERG_MARQUARDT")
 
     def SolveByGradientDescent(self, options, summary=None):
-        raise NotImplementedError(
-            "SolveByGradientDescent (reference ..._refactor.cpp:1073-1370) is "
-            "not on the MI355X hot path")
+        """reference ..._refactor.cpp:1075-1367: first-order steps, each
+        pose / point block clipped to norm 1e-3 (scaled units), every step
+        taken; rows as documented at ba_solve_gd (include/ba_hip.h).
+        solver_type, decrease / increase_ratio_lambda are ignored."""
+        t0 = time.perf_counter()
+        if summary is not None:
+            summary.max_iteration_ = options.iteration_handle.max_num_iterations
+            summary.threshold_cost_change_ = \
+                options.convergence_handle.threshold_cost_change
+            summary.threshold_step_size_ = \
+                options.convergence_handle.threshold_step_size
+            summary.convergence_status_ = True
+        self.FinalizeParameters()
+        if self.verbose:
+            self.GetSolverStatistics()
+        self.CheckPoseAndPointConnectivity()            # reference :1161
+        rows, converged = self._problem.solve_gd(options.to_c())
+        return self._finish_solve(rows, converged, summary, t0)

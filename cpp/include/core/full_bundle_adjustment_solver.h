@@ -109,6 +109,10 @@ class FullBundleAdjustmentSolver {
   bool OwnsPoint(const _BA_Point *point) const;
 
  private:
+  // SolveByGradientDescent of the refactored class runs through Run (same handle,
+  // write-back and Summary as Solve)
+  friend class FullBundleAdjustmentSolverRefactor;
+  bool Run(Options options, Summary *summary, bool gradient_descent);
   // stderr warnings about weakly connected poses / points (reference
   // core/full_bundle_adjustment_solver.cpp:310-341), called by Solve
   void CheckPoseAndPointConnectivity();

@@ -2,7 +2,8 @@
 // the reference (core/full_bundle_adjustment_solver_refactor.h:36-136): the same
 // device path as FullBundleAdjustmentSolver behind RegisterCamera /
 // RegisterWorldToBodyPose / RegisterWorldPoint, plus the solver_type switch of
-// its Solve (reference ..._refactor.cpp:944-982).  Reference test/
+// its Solve (reference ..._refactor.cpp:944-982) and its first-order
+// SolveByGradientDescent (:1075-1367, ba_solve_gd).  Reference test/
 // test_ba_refactor.cpp compiles against this header unchanged.
 #ifndef BA_FACADE_FULL_BUNDLE_ADJUSTMENT_SOLVER_REFACTOR_H_
 #define BA_FACADE_FULL_BUNDLE_ADJUSTMENT_SOLVER_REFACTOR_H_
@@ -66,7 +67,9 @@ class FullBundleAdjustmentSolverRefactor {
   // solver_type LEVENBERG_MARQUARDT or GAUSS_NEWTON (the default of Options);
   // anything else throws std::runtime_error
   bool Solve(Options options, Summary *summary = nullptr);
-  // reference ..._refactor.cpp:1073-1370: not on the MI355X path, throws
+  // reference ..._refactor.cpp:1075-1367 (ba_solve_gd): first-order steps, each pose /
+  // point block clipped to norm 1e-3 in the solver's scaled units, every step taken;
+  // solver_type and the lambda ratios are ignored, damping_term = initial_lambda
   bool SolveByGradientDescent(Options options, Summary *summary = nullptr);
 
   std::string GetSolverStatistics() const;

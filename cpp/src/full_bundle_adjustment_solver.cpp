@@ -293,6 +293,13 @@ void FullBundleAdjustmentSolver::CheckPoseAndPointConnectivity() {  // :310-341
 }
 
 bool FullBundleAdjustmentSolver::Solve(Options options, Summary *summary) {  // :630-1044
+  return Run(options, summary, false);
+}
+
+// gradient_descent: FullBundleAdjustmentSolverRefactor::SolveByGradientDescent (reference
+// core/full_bundle_adjustment_solver_refactor.cpp:1075-1367, ba_solve_gd) instead of the LM
+// loop; the write-back and the Summary are the same
+bool FullBundleAdjustmentSolver::Run(Options options, Summary *summary, bool gradient_descent) {
   timer::StopWatch stopwatch("BundleAdjustmentSolver::Solve");
   stopwatch.Start();
   if (summary != nullptr) {
@@ -317,7 +324,10 @@ bool FullBundleAdjustmentSolver::Solve(Options options, Summary *summary) {  // 
   o.gauss_newton = gauss_newton_ ? 1 : 0;
   std::vector<ba_iter_info> rows(static_cast<size_t>(std::max(1, o.max_num_iterations)));
   int n_iter = 0, converged = 0;
-  Check(ba_solve(handle_, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged), "ba_solve");
+  if (gradient_descent)
+    Check(ba_solve_gd(handle_, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged), "ba_solve_gd");
+  else
+    Check(ba_solve(handle_, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged), "ba_solve");
 
   // write back through the caller's pointers (:1011-1022)
   std::vector<double> T(12 * poses_.size()), X(3 * points_.size());

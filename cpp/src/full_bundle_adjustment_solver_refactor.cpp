@@ -47,8 +47,8 @@ bool FullBundleAdjustmentSolverRefactor::Solve(Options options, Summary *summary
   return impl_.Solve(options, summary);
 }
 
-bool FullBundleAdjustmentSolverRefactor::SolveByGradientDescent(Options, Summary *) {
-  throw std::runtime_error("FullBundleAdjustmentSolverRefactor::SolveByGradientDescent is not provided by the MI355X path");
+bool FullBundleAdjustmentSolverRefactor::SolveByGradientDescent(Options options, Summary *summary) {  // :1075-1367
+  return impl_.Run(options, summary, true);
 }
 
 std::string FullBundleAdjustmentSolverRefactor::GetSolverStatistics() const { return impl_.GetSolverStatistics(); }

@@ -181,6 +181,37 @@ int ba_lm_iterate(ba_handle *h, int n);
 int ba_lm_sync(ba_handle *h, ba_iter_info *out, int cap, int *n_iter,
                int *converged);
 
+/* ---- gradient descent ----------------------------------------------------- */
+/* FullBundleAdjustmentSolverRefactor::SolveByGradientDescent, reference
+ * core/full_bundle_adjustment_solver_refactor.cpp:1075-1367: per iteration
+ * a_j = -sum Q_ij^T w r_ij (optimisable poses), b_i = -sum R_ij^T w r_ij
+ * (optimisable points), each block clipped to norm <= 1e-3 (scaled units),
+ * T_jw <- exp(a_j) T_jw and X_i <- X_i + b_i, every step taken.  The rows:
+ * cost = sum ||r|| at the new parameters (every observation), cost_change =
+ * |cost - previous|, average_reprojection_error = cost / observations (no
+ * sqrt), abs_step = (0.01 + sum ||a_j|| + 0.01 + sum ||b_i||) / (N + M) of
+ * the clipped blocks, abs_gradient = 0, damping_term = initial_lambda,
+ * iteration_status = UPDATE, rho = 0, model_change = 0, trial_cost = cost.
+ * Stop: converged if abs_step < threshold_step_size or cost_change <
+ * threshold_cost_change, never on the last allowed iteration.  gauss_newton,
+ * decrease_ratio_lambda and increase_ratio_lambda are ignored.  Single GPU:
+ * a sharded handle (ba_set_shard world > 1, or an all-reduce hook) is refused.
+ * The parameters are updated in place: ba_get_poses / ba_get_points return
+ * the GD result and a following ba_solve starts from it.  The same
+ * begin / iterate / sync split as the LM loop; ba_lm_iterate after
+ * ba_gd_begin and ba_gd_iterate after ba_lm_begin fail. */
+int ba_gd_begin(ba_handle *h, const ba_options *opt);   /* :1109-1158 */
+int ba_gd_iterate(ba_handle *h, int n);                 /* enqueue n iterations */
+/* returns 1 when the loop has finished, 0 when not, < 0 on error */
+int ba_gd_sync(ba_handle *h, ba_iter_info *out, int cap, int *n_iter,
+               int *converged);
+int ba_solve_gd(ba_handle *h, const ba_options *opt, ba_iter_info *out,
+                int cap, int *n_iter, int *converged);  /* :1075-1367 */
+/* the unclipped gradient at the current parameters (computed by the last pass
+ * over the observations: after ba_gd_begin the starting point's), in the order
+ * and layout of ba_get_A's a6 and ba_get_C's b3 */
+int ba_gd_get_gradient(ba_handle *h, double *a6, double *b3);
+
 /* ---- stage entry points (parity tests, per-stage timing) --------------- */
 int ba_stage_cost(ba_handle *h, double *cost);            /* :381-433 */
 int ba_stage_linearize(ba_handle *h, double lambda,
