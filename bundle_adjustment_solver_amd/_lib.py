@@ -68,6 +68,13 @@ class BaPoIter(C.Structure):
                 ("abs_step", C.c_float)]
 
 
+class BaPoResult(C.Structure):
+    """ba_po_result — one problem of a batched pose-only solve (status 0 = pose
+    written, 1 = NaN pose left unchanged, 2 = malformed problem)."""
+    _fields_ = [("n_iter", C.c_int), ("converged", C.c_int),
+                ("n_rows", C.c_int), ("status", C.c_int)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                            C.c_int64, C.c_void_p)
 
@@ -183,6 +190,21 @@ SIGNATURES = {
                                        C.POINTER(BaPoIter), C.c_int,
                                        C.POINTER(C.c_int), C.POINTER(C.c_int),
                                        _F]),
+    "ba_pose_only_mono6_batch": (C.c_int, [_P, C.c_int, _I32, _F, _F, _F, _F, _U8,
+                                           C.POINTER(BaOptions), C.POINTER(BaPoIter),
+                                           C.c_int, C.POINTER(BaPoResult), _F]),
+    "ba_pose_only_stereo6_batch": (C.c_int, [_P, C.c_int, _I32, _F, _F, _F, _F, _F,
+                                             _F, _F, _U8, _U8, C.POINTER(BaOptions),
+                                             C.POINTER(BaPoIter), C.c_int,
+                                             C.POINTER(BaPoResult), _F]),
+    # device pointers (c_void_p) and a hipStream_t
+    "ba_pose_only_mono6_batch_device": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P,
+                                                  C.POINTER(BaOptions), _P, C.c_int,
+                                                  _P, _P, _P]),
+    "ba_pose_only_stereo6_batch_device": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P,
+                                                    _P, _P, _P, C.POINTER(BaOptions),
+                                                    _P, C.c_int, _P, _P, _P]),
+    "ba_right_camera_record": (C.c_int, [_F, _F, _F]),
 }
 
 _lib = None

@@ -1721,6 +1721,31 @@ PoLayout po_layout(int n, int icap, bool stereo) {
   return L;
 }
 
+// grow the pose-only buffer pair to `bytes` (not in `allocs`: freed here and in
+// free_device)
+int po_reserve(ba_handle *h, size_t bytes) {
+  if (bytes <= h->po_cap) return 0;
+  if (h->po_dev) (void)hipFree(h->po_dev);
+  if (h->po_host) (void)hipHostFree(h->po_host);
+  h->po_dev = h->po_host = nullptr;
+  h->po_cap = 0;
+  HIP_TRY(hipMalloc((void **)&h->po_dev, bytes));
+  HIP_TRY(hipHostMalloc((void **)&h->po_host, bytes, hipHostMallocDefault));
+  h->po_cap = bytes;
+  return 0;
+}
+
+// right camera record of the stereo 6-DoF solvers: fx fy cx cy, then
+// pose_right_to_left = left_to_right^-1 (reference :226) as R (9, row-major) and t (3)
+void po_right_camera(const float *intr_r4, const float *T_lr12, float *camr) {
+  for (int k = 0; k < 4; ++k) camr[k] = intr_r4[k];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) camr[4 + r * 3 + c] = T_lr12[c * 3 + r];
+  for (int r = 0; r < 3; ++r)
+    camr[13 + r] = -(camr[4 + r * 3 + 0] * T_lr12[9] + camr[4 + r * 3 + 1] * T_lr12[10] +
+                     camr[4 + r * 3 + 2] * T_lr12[11]);
+}
+
 int po_run(ba_handle *h, bool stereo, const float *X3, const float *uv2, const float *uvr2, int n,
            float fx, float fy, float cx, float cy, const float *camr16, float *T12, uint8_t *mask,
            uint8_t *mask_r, const ba_options *opt, ba_po_iter *iters, int cap, int *n_iter,
@@ -1731,15 +1756,7 @@ int po_run(ba_handle *h, bool stereo, const float *X3, const float *uv2, const f
   const int max_it = opt->max_num_iterations;
   const int icap = std::max(1, std::max(cap, max_it));
   const PoLayout L = po_layout(n, icap, stereo);
-  if (L.end > h->po_cap) {  // grow the buffer pair (not in `allocs`: freed here and in free_device)
-    if (h->po_dev) (void)hipFree(h->po_dev);
-    if (h->po_host) (void)hipHostFree(h->po_host);
-    h->po_dev = h->po_host = nullptr;
-    h->po_cap = 0;
-    HIP_TRY(hipMalloc((void **)&h->po_dev, L.end));
-    HIP_TRY(hipHostMalloc((void **)&h->po_host, L.end, hipHostMallocDefault));
-    h->po_cap = L.end;
-  }
+  if (po_reserve(h, L.end)) return -1;
   if (!h->po_part && h->dalloc(&h->po_part, (size_t)ba::pose_only_partial_floats())) return -1;
   uint8_t *hb = h->po_host, *db = h->po_dev;
   std::memcpy(hb + L.X, X3, (size_t)n * 3 * sizeof(float));
@@ -1819,15 +1836,8 @@ int ba_pose_only_stereo6(ba_handle *h, const float *X3, const float *uv2,
   if (!h || !X3 || !uv2 || !uvr2 || n <= 0 || !intr_l4 || !intr_r4 || !T_lr12 || !T12 ||
       !mask || !mask_r || !opt)
     return fail("ba_pose_only_stereo6: bad argument");
-  // right camera record: fx fy cx cy, then pose_right_to_left = left_to_right^-1
-  // (reference :226) as R (9, row-major) and t (3)
   float camr[16];
-  for (int k = 0; k < 4; ++k) camr[k] = intr_r4[k];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) camr[4 + r * 3 + c] = T_lr12[c * 3 + r];
-  for (int r = 0; r < 3; ++r)
-    camr[13 + r] = -(camr[4 + r * 3 + 0] * T_lr12[9] + camr[4 + r * 3 + 1] * T_lr12[10] +
-                     camr[4 + r * 3 + 2] * T_lr12[11]);
+  po_right_camera(intr_r4, T_lr12, camr);
   return po_run(h, true, X3, uv2, uvr2, n, intr_l4[0], intr_l4[1], intr_l4[2], intr_l4[3], camr, T12,
                 mask, mask_r, opt, iters, cap, n_iter, converged, debug_T12);
 }
@@ -1914,6 +1924,184 @@ int ba_pose_only_stereo3(ba_handle *h, const float *X3, const float *uvl2,
   const ba::Po3Params P = po3_params(T_bc12, T_wl12, T12, T_lr12, intr_r4);
   return po_run(h, true, X3, uvl2, uvr2, n, intr_l4[0], intr_l4[1], intr_l4[2], intr_l4[3],
                 nullptr, T12, mask_l, mask_r, opt, iters, cap, n_iter, converged, debug_T12, &P);
+}
+
+}  // extern "C"
+
+// ---- batched 6-DoF pose-only (one workgroup per problem) ----------------------
+namespace {
+// one pinned staging buffer mirroring one device buffer, as po_run:
+//   [offsets | X | uv | uv_right | intrinsics | right cameras | T | mask | mask_right]  <- H2D
+//                                               [ T | mask | mask_right | results | iters | debug ]  <- D2H
+struct PoBatchLayout {
+  size_t off, X, uv, uvr, intr, camr, T, mask, maskr, h2d_end, res, iters, dbg, end;
+};
+PoBatchLayout po_batch_layout(int B, int64_t N, int cap, bool stereo, bool want_iters, bool want_dbg) {
+  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  PoBatchLayout L;
+  size_t o = 0;
+  L.off = o;    o = al(o + (size_t)(B + 1) * sizeof(int32_t));
+  L.X = o;      o = al(o + (size_t)N * 3 * sizeof(float));
+  L.uv = o;     o = al(o + (size_t)N * 2 * sizeof(float));
+  L.uvr = o;    o = al(o + (stereo ? (size_t)N * 2 * sizeof(float) : 0));
+  L.intr = o;   o = al(o + (size_t)B * 4 * sizeof(float));
+  L.camr = o;   o = al(o + (stereo ? (size_t)B * 16 * sizeof(float) : 0));
+  L.T = o;      o = al(o + (size_t)B * 12 * sizeof(float));
+  L.mask = o;   o = al(o + (size_t)N);
+  L.maskr = o;  o = al(o + (stereo ? (size_t)N : 0));
+  L.h2d_end = o;
+  L.res = o;    o = al(o + (size_t)B * sizeof(ba_po_result));
+  L.iters = o;  o = al(o + (want_iters ? (size_t)B * cap * sizeof(ba_po_iter) : 0));
+  L.dbg = o;    o = al(o + (want_dbg ? (size_t)B * cap * 12 * sizeof(float) : 0));
+  L.end = o;
+  return L;
+}
+
+// host-side checks shared by both host-array entry points (nothing runs on failure)
+int po_batch_check(const char *fn, ba_handle *h, int B, const int32_t *offsets, int cap) {
+  const std::string f(fn);
+  if (B < 1) return fail(f + ": B must be >= 1");
+  if (!offsets) return fail(f + ": null offsets");
+  if (offsets[0] != 0) return fail(f + ": offsets[0] must be 0");
+  for (int b = 0; b < B; ++b)
+    if (offsets[b + 1] <= offsets[b])
+      return fail(f + ": offsets must be strictly increasing (problem " + std::to_string(b) + ")");
+  if (cap < 0) return fail(f + ": cap must be >= 0");
+  if (!h) return fail(f + ": null handle");
+  return 0;
+}
+
+int po_batch_run(const char *fn, ba_handle *h, bool stereo, int B, const int32_t *offsets,
+                 const float *X3, const float *uvl2, const float *uvr2, const float *intr_l4,
+                 const float *intr_r4, const float *T_lr12, float *T12, uint8_t *mask_l,
+                 uint8_t *mask_r, const ba_options *opt, ba_po_iter *iters, int cap,
+                 ba_po_result *res, float *debug_T12) {
+  if (use_device(h)) return -1;
+  const int64_t N = offsets[B];
+  const bool want_it = iters && cap > 0, want_dbg = debug_T12 && cap > 0;
+  const PoBatchLayout L = po_batch_layout(B, N, cap, stereo, want_it, want_dbg);
+  if (po_reserve(h, L.end)) return -1;
+  uint8_t *hb = h->po_host, *db = h->po_dev;
+  std::memcpy(hb + L.off, offsets, (size_t)(B + 1) * sizeof(int32_t));
+  std::memcpy(hb + L.X, X3, (size_t)N * 3 * sizeof(float));
+  std::memcpy(hb + L.uv, uvl2, (size_t)N * 2 * sizeof(float));
+  std::memcpy(hb + L.intr, intr_l4, (size_t)B * 4 * sizeof(float));
+  std::memcpy(hb + L.T, T12, (size_t)B * 12 * sizeof(float));
+  std::memcpy(hb + L.mask, mask_l, (size_t)N);
+  if (stereo) {
+    std::memcpy(hb + L.uvr, uvr2, (size_t)N * 2 * sizeof(float));
+    float *camr = (float *)(hb + L.camr);
+    for (int b = 0; b < B; ++b) po_right_camera(intr_r4 + 4 * b, T_lr12 + 12 * b, camr + 16 * b);
+    std::memcpy(hb + L.maskr, mask_r, (size_t)N);
+  }
+  hipStream_t s = h->stream;
+  HIP_TRY(hipMemcpyAsync(db, hb, L.h2d_end, hipMemcpyHostToDevice, s));
+  ba_po_iter *dit = want_it ? (ba_po_iter *)(db + L.iters) : nullptr;
+  float *ddbg = want_dbg ? (float *)(db + L.dbg) : nullptr;
+  const int32_t *doff = (const int32_t *)(db + L.off);
+  ba_po_result *dres = (ba_po_result *)(db + L.res);
+  const int rc =
+      stereo ? ba_pose_only_stereo6_batch_device(
+                   h, B, doff, (const float *)(db + L.X), (const float *)(db + L.uv),
+                   (const float *)(db + L.uvr), (const float *)(db + L.intr),
+                   (const float *)(db + L.camr), (float *)(db + L.T), db + L.mask, db + L.maskr, opt,
+                   dit, cap, dres, ddbg, (void *)s)
+             : ba_pose_only_mono6_batch_device(h, B, doff, (const float *)(db + L.X),
+                                               (const float *)(db + L.uv), (const float *)(db + L.intr),
+                                               (float *)(db + L.T), db + L.mask, opt, dit, cap, dres,
+                                               ddbg, (void *)s);
+  if (rc) return fail(std::string(fn) + ": " + g_err);
+  HIP_TRY(hipMemcpyAsync(hb + L.T, db + L.T, L.end - L.T, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const ba_po_result *hr = (const ba_po_result *)(hb + L.res);
+  std::memcpy(T12, hb + L.T, (size_t)B * 12 * sizeof(float));  // unchanged where not written
+  std::memcpy(mask_l, hb + L.mask, (size_t)N);
+  if (stereo) std::memcpy(mask_r, hb + L.maskr, (size_t)N);
+  if (res) std::memcpy(res, hr, (size_t)B * sizeof(ba_po_result));
+  for (int b = 0; b < B; ++b) {
+    const int rows = std::min(hr[b].n_rows, cap), its = std::min(hr[b].n_iter, cap);
+    if (want_it && rows > 0)
+      std::memcpy(iters + (size_t)b * cap, hb + L.iters + (size_t)b * cap * sizeof(ba_po_iter),
+                  (size_t)rows * sizeof(ba_po_iter));
+    if (want_dbg && its > 0)
+      std::memcpy(debug_T12 + (size_t)b * cap * 12, hb + L.dbg + (size_t)b * cap * 12 * sizeof(float),
+                  (size_t)its * 12 * sizeof(float));
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int ba_pose_only_mono6_batch_device(ba_handle *h, int B, const int32_t *offsets, const float *X3,
+                                    const float *uv2, const float *intr4, float *T12, uint8_t *mask,
+                                    const ba_options *opt, ba_po_iter *iters, int cap,
+                                    ba_po_result *res, float *debug_T12, void *hip_stream) {
+  if (!h || B < 1 || !offsets || !X3 || !uv2 || !intr4 || !T12 || !mask || !opt || !res || cap < 0)
+    return fail("ba_pose_only_mono6_batch_device: bad argument");
+  if (use_device(h)) return -1;
+  static_assert(sizeof(ba::PoIter) == sizeof(ba_po_iter), "po iter layout");
+  static_assert(sizeof(ba_po_result) == 4 * sizeof(int), "po result layout");
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  if (ba::pose_only6_batch_device(false, B, offsets, X3, uv2, nullptr, intr4, nullptr, T12, mask,
+                                  nullptr, opt->threshold_huber_loss, opt->threshold_step_size,
+                                  opt->threshold_cost_change, opt->threshold_outlier_rejection,
+                                  opt->max_num_iterations, cap > 0 ? (ba::PoIter *)iters : nullptr,
+                                  cap, (int *)res, cap > 0 ? debug_T12 : nullptr, s))
+    return fail("ba_pose_only_mono6_batch_device: kernel launch failed");
+  return 0;
+}
+
+int ba_pose_only_stereo6_batch_device(ba_handle *h, int B, const int32_t *offsets, const float *X3,
+                                      const float *uvl2, const float *uvr2, const float *intr_l4,
+                                      const float *camr16, float *T12, uint8_t *mask_l,
+                                      uint8_t *mask_r, const ba_options *opt, ba_po_iter *iters,
+                                      int cap, ba_po_result *res, float *debug_T12,
+                                      void *hip_stream) {
+  if (!h || B < 1 || !offsets || !X3 || !uvl2 || !uvr2 || !intr_l4 || !camr16 || !T12 || !mask_l ||
+      !mask_r || !opt || !res || cap < 0)
+    return fail("ba_pose_only_stereo6_batch_device: bad argument");
+  if (use_device(h)) return -1;
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  if (ba::pose_only6_batch_device(true, B, offsets, X3, uvl2, uvr2, intr_l4, camr16, T12, mask_l,
+                                  mask_r, opt->threshold_huber_loss, opt->threshold_step_size,
+                                  opt->threshold_cost_change, opt->threshold_outlier_rejection,
+                                  opt->max_num_iterations, cap > 0 ? (ba::PoIter *)iters : nullptr,
+                                  cap, (int *)res, cap > 0 ? debug_T12 : nullptr, s))
+    return fail("ba_pose_only_stereo6_batch_device: kernel launch failed");
+  return 0;
+}
+
+int ba_right_camera_record(const float *intr_r4, const float *T_lr12, float *camr16) {
+  if (!intr_r4 || !T_lr12 || !camr16) return fail("ba_right_camera_record: bad argument");
+  po_right_camera(intr_r4, T_lr12, camr16);
+  return 0;
+}
+
+int ba_pose_only_mono6_batch(ba_handle *h, int B, const int32_t *offsets, const float *X3,
+                             const float *uv2, const float *intr4, float *T12, uint8_t *mask,
+                             const ba_options *opt, ba_po_iter *iters, int cap, ba_po_result *res,
+                             float *debug_T12) {
+  const char *fn = "ba_pose_only_mono6_batch";
+  if (po_batch_check(fn, h, B, offsets, cap)) return -1;
+  if (!X3 || !uv2 || !intr4 || !T12 || !mask || !opt || !res)
+    return fail(std::string(fn) + ": bad argument");
+  return po_batch_run(fn, h, false, B, offsets, X3, uv2, nullptr, intr4, nullptr, nullptr, T12, mask,
+                      nullptr, opt, iters, cap, res, debug_T12);
+}
+
+int ba_pose_only_stereo6_batch(ba_handle *h, int B, const int32_t *offsets, const float *X3,
+                               const float *uvl2, const float *uvr2, const float *intr_l4,
+                               const float *intr_r4, const float *T_lr12, float *T12,
+                               uint8_t *mask_l, uint8_t *mask_r, const ba_options *opt,
+                               ba_po_iter *iters, int cap, ba_po_result *res, float *debug_T12) {
+  const char *fn = "ba_pose_only_stereo6_batch";
+  if (po_batch_check(fn, h, B, offsets, cap)) return -1;
+  if (!X3 || !uvl2 || !uvr2 || !intr_l4 || !intr_r4 || !T_lr12 || !T12 || !mask_l || !mask_r || !opt ||
+      !res)
+    return fail(std::string(fn) + ": bad argument");
+  return po_batch_run(fn, h, true, B, offsets, X3, uvl2, uvr2, intr_l4, intr_r4, T_lr12, T12, mask_l,
+                      mask_r, opt, iters, cap, res, debug_T12);
 }
 
 }  // extern "C"

@@ -423,6 +423,16 @@ int pose_only_stereo6_device(const float *dX3, const float *duvl2, const float *
                              float thr_step, float thr_cost, float thr_out, int max_it,
                              PoIter *d_iters, int cap, int *d_meta, float *d_debug,
                              int *d_gsync, float *d_partial, hipStream_t s);
+// B independent 6-DoF problems, one workgroup each (k_pose_only6<STEREO, true>);
+// device pointers laid out as in ba_pose_only_{mono,stereo}6_batch_device
+// (d_camr16 = B right-camera records, stereo only; d_res = B ba_po_result).
+// Enqueue only.
+int pose_only6_batch_device(bool stereo, int B, const int *d_offsets, const float *dX3,
+                            const float *duvl2, const float *duvr2, const float *d_intr_l4,
+                            const float *d_camr16, float *dT12, uint8_t *dmask_l, uint8_t *dmask_r,
+                            float thr_huber, float thr_step, float thr_cost, float thr_out,
+                            int max_it, PoIter *d_iters, int cap, int *d_res, float *d_debug,
+                            hipStream_t s);
 // planar 3-DoF (reference core/pose_only_bundle_adjustment_solver.cpp:401-900):
 // everything the host derives in fp32 from the poses, passed by value
 struct Po3Params {

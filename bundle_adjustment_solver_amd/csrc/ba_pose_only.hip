@@ -206,15 +206,56 @@ __device__ __forceinline__ void po_grid_barrier(int *gsync, int target) {
 // EVERY workgroup adds the partials in the same order and runs the same 6x6
 // solve, so all hold the same pose and take the same convergence decision
 // without a second barrier or a broadcast.  Workgroup 0 writes the outputs.
-template <bool STEREO>
+//
+// BATCH (ba_pose_only_{mono,stereo}6_batch): B independent problems, one
+// workgroup each, launched with B workgroups.  The arguments are then per-batch
+// arrays, re-pointed at problem b = blockIdx.x on entry: gsync = offsets (B+1;
+// the problem's points are [offsets[b], offsets[b+1])), partial = intrinsics
+// (B x 4), cam_r = right-camera records (B x 16), T12 (B x 12), iters (B x cap),
+// debug_T12 (B x cap x 12), meta = ba_po_result records (B x 4 ints: status 0 =
+// pose written, 1 = NaN, 2 = empty range and nothing else written); n and
+// fx..cy are unused.  G = 1 and block 0 at compile time: no exchange, no grid
+// barrier, no workgroup waits for another (any B is safe), and the arithmetic is
+// that of a one-workgroup launch of k_pose_only6<STEREO, false>.
+template <bool STEREO, bool BATCH>
 __global__ __launch_bounds__(kPoThreads) void k_pose_only6(
     const float *__restrict__ X3, const float *__restrict__ uv2,
     const float *__restrict__ uvr2, int n, float fx, float fy, float cx, float cy,
     const float *__restrict__ cam_r, float *T12, uint8_t *mask, uint8_t *maskr,
     float thr_huber, float thr_step, float thr_cost, float thr_out, int max_it,
     PoIter *iters, int cap, int *meta, float *debug_T12, int *gsync, float *partial) {
-  const int G = gridDim.x;
-  const bool lead = blockIdx.x == 0;
+  if constexpr (BATCH) {
+    const unsigned b = blockIdx.x;
+    const int o = gsync[b];
+    n = gsync[b + 1] - o;
+    meta += 4 * (size_t)b;
+    if (n <= 0) {
+      if (threadIdx.x == 0) {
+        meta[0] = 0;
+        meta[1] = 0;
+        meta[2] = 0;
+        meta[3] = 2;
+      }
+      return;
+    }
+    X3 += 3 * (size_t)o;
+    uv2 += 2 * (size_t)o;
+    mask += o;
+    if (STEREO) {
+      uvr2 += 2 * (size_t)o;
+      maskr += o;
+      cam_r += 16 * (size_t)b;
+    }
+    fx = partial[4 * b];
+    fy = partial[4 * b + 1];
+    cx = partial[4 * b + 2];
+    cy = partial[4 * b + 3];
+    T12 += 12 * (size_t)b;
+    if (iters) iters += (size_t)b * cap;
+    if (debug_T12) debug_T12 += (size_t)b * cap * 12;
+  }
+  const int G = BATCH ? 1 : gridDim.x;
+  const bool lead = BATCH ? true : blockIdx.x == 0;
   __shared__ float red[kPoWaves][kNred];
   __shared__ float tots[kNred];
   __shared__ float Hs[36], gs[6], tmps[6];
@@ -239,7 +280,7 @@ __global__ __launch_bounds__(kPoThreads) void k_pose_only6(
       meta[0] = 0;
       meta[1] = 1;
       meta[2] = 0;
-      meta[3] = 1;
+      meta[3] = BATCH ? 0 : 1;
     }
   }
   int n_rows = 0;  // Summary rows logged so far (thread 0)
@@ -263,7 +304,7 @@ __global__ __launch_bounds__(kPoThreads) void k_pose_only6(
     // memory latency instead of four (the inputs are re-read from L2 in every
     // Gauss-Newton iteration)
     const int gstride = G * kPoThreads;
-    for (int p0 = blockIdx.x * kPoThreads + tid; p0 < n; p0 += 4 * gstride) {
+    for (int p0 = (BATCH ? 0u : blockIdx.x) * kPoThreads + tid; p0 < n; p0 += 4 * gstride) {
       float Xb[4][3], ub[4][2], urb[4][2];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -414,7 +455,7 @@ __global__ __launch_bounds__(kPoThreads) void k_pose_only6(
     float nrm = 0.0f;
     for (int k = 0; k < 9; ++k) nrm += pose[k] * pose[k];
     if (isnan(nrm)) {
-      meta[3] = 0;  // reference :159-167: do not update on NaN
+      meta[3] = BATCH ? 1 : 0;  // reference :159-167: do not update on NaN
     } else {
       for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) T12[r * 3 + c] = pose[c * 3 + r];
@@ -718,7 +759,7 @@ int pose_only_mono6_device(const float *dX3, const float *duv2, int n, float fx,
                            PoIter *d_iters, int cap, int *d_meta,
                            float *d_debug, int *d_gsync, float *d_partial, hipStream_t s) {
   // d_gsync must be zero on entry (the caller's single H2D copy covers it)
-  hipLaunchKernelGGL(k_pose_only6<false>, dim3(po_groups(n)), dim3(kPoThreads), 0, s, dX3, duv2,
+  hipLaunchKernelGGL((k_pose_only6<false, false>), dim3(po_groups(n)), dim3(kPoThreads), 0, s, dX3, duv2,
                      (const float *)nullptr, n, fx, fy, cx, cy, (const float *)nullptr, dT12,
                      dmask, (uint8_t *)nullptr, thr_huber, thr_step, thr_cost, thr_out, max_it,
                      d_iters, cap, d_meta, d_debug, d_gsync, d_partial);
@@ -732,10 +773,32 @@ int pose_only_stereo6_device(const float *dX3, const float *duvl2, const float *
                              PoIter *d_iters, int cap, int *d_meta, float *d_debug,
                              int *d_gsync, float *d_partial, hipStream_t s) {
   // d_gsync must be zero on entry (the caller's single H2D copy covers it)
-  hipLaunchKernelGGL(k_pose_only6<true>, dim3(po_groups(n)), dim3(kPoThreads), 0, s, dX3, duvl2,
+  hipLaunchKernelGGL((k_pose_only6<true, false>), dim3(po_groups(n)), dim3(kPoThreads), 0, s, dX3, duvl2,
                      duvr2, n, fx, fy, cx, cy, d_cam_r16, dT12, dmask_l, dmask_r, thr_huber,
                      thr_step, thr_cost, thr_out, max_it, d_iters, cap, d_meta, d_debug, d_gsync,
                      d_partial);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int pose_only6_batch_device(bool stereo, int B, const int *d_offsets, const float *dX3,
+                            const float *duvl2, const float *duvr2, const float *d_intr_l4,
+                            const float *d_camr16, float *dT12, uint8_t *dmask_l, uint8_t *dmask_r,
+                            float thr_huber, float thr_step, float thr_cost, float thr_out,
+                            int max_it, PoIter *d_iters, int cap, int *d_res, float *d_debug,
+                            hipStream_t s) {
+  // per-batch arrays in the slots k_pose_only6<STEREO, true> re-points (see there)
+  int *offs = const_cast<int *>(d_offsets);
+  float *intr = const_cast<float *>(d_intr_l4);
+  if (stereo)
+    hipLaunchKernelGGL((k_pose_only6<true, true>), dim3(B), dim3(kPoThreads), 0, s, dX3, duvl2,
+                       duvr2, 0, 0.0f, 0.0f, 0.0f, 0.0f, d_camr16, dT12, dmask_l, dmask_r,
+                       thr_huber, thr_step, thr_cost, thr_out, max_it, d_iters, cap, d_res, d_debug,
+                       offs, intr);
+  else
+    hipLaunchKernelGGL((k_pose_only6<false, true>), dim3(B), dim3(kPoThreads), 0, s, dX3, duvl2,
+                       (const float *)nullptr, 0, 0.0f, 0.0f, 0.0f, 0.0f, (const float *)nullptr,
+                       dT12, dmask_l, (uint8_t *)nullptr, thr_huber, thr_step, thr_cost, thr_out,
+                       max_it, d_iters, cap, d_res, d_debug, offs, intr);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

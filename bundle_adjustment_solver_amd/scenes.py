@@ -441,6 +441,75 @@ def pose_only_stereo_scene(n=10_000, seed=SEED_BASE + 6, pixel_sigma=0.0,
     return sc
 
 
+def pose_only_batch_scene(B, n_min, n_max, seed, stereo=False, pixel_sigma=0.0,
+                          right_missing_frac=0.0, outlier_frac=0.0):
+    """B independent 6-DoF pose-only problems for the batched solvers
+    (ba_pose_only_{mono,stereo}6_batch), concatenated: problem b owns rows
+    [offsets[b], offsets[b+1]) of X / uv (/ uv_right, right_missing).  Each has
+    n_min..n_max points drawn by pose_only_scene / pose_only_stereo_scene, its
+    own intrinsics (fx 300..600), a true pose near the scene's (+-0.05 rad,
+    +-0.1 m), a start pose near the true one (+-0.03 rad, +-0.05 m), and, in
+    stereo, its own baseline (0.10..0.15 m); pixels get `pixel_sigma` noise and
+    an `outlier_frac` of the points a gross error of 20..60 px.  Seeded."""
+    rng = np.random.default_rng(seed)
+    ns = rng.integers(n_min, n_max + 1, B)
+    offsets = np.zeros(B + 1, np.int32)
+    offsets[1:] = np.cumsum(ns)
+
+    def perturb(T, ang, lin):
+        a = rng.uniform(-ang, ang, 3)
+        P = np.eye(4)
+        P[:3, :3] = _rot("x", a[0]) @ _rot("y", a[1]) @ _rot("z", a[2])
+        P[:3, 3] = rng.uniform(-lin, lin, 3)
+        return (T.astype(np.float64) @ P).astype(np.float32)
+
+    def project(L, k):
+        inv_z = (np.float32(1.0) / L[:, 2]).astype(np.float32)
+        return np.stack([k[0] * L[:, 0] * inv_z + k[2], k[1] * L[:, 1] * inv_z + k[3]],
+                        axis=1).astype(np.float32)
+
+    Xs, uvs, uvrs, miss = [], [], [], []
+    intr = np.zeros((B, 4), np.float32)
+    T_lr = np.tile(np.eye(4, dtype=np.float32), (B, 1, 1))
+    T_true = np.zeros((B, 4, 4), np.float32)
+    T_init = np.zeros((B, 4, 4), np.float32)
+    for b in range(B):
+        n = int(ns[b])
+        sub = int(rng.integers(1 << 30))
+        sc = (pose_only_stereo_scene(n, seed=sub, right_missing_frac=right_missing_frac)
+              if stereo else pose_only_scene(n, seed=sub))
+        fx = rng.uniform(300.0, 600.0)
+        intr[b] = [fx, fx * rng.uniform(0.98, 1.02), rng.uniform(300.0, 340.0),
+                   rng.uniform(220.0, 260.0)]
+        T_true[b] = perturb(sc["T_true"], 0.05, 0.1)
+        T_init[b] = perturb(T_true[b], 0.03, 0.05)
+        Ti = _inv(T_true[b].astype(np.float64)).astype(np.float32)
+        L = sc["X"] @ Ti[:3, :3].T + Ti[:3, 3]
+        uv = project(L, intr[b])
+        bad = rng.uniform(size=n) < outlier_frac
+        err = rng.uniform(20.0, 60.0, (n, 2)) * rng.choice([-1.0, 1.0], (n, 2))
+        if pixel_sigma > 0:
+            uv = uv + rng.normal(0, pixel_sigma, uv.shape)
+        uvs.append((uv + bad[:, None] * err).astype(np.float32))
+        Xs.append(sc["X"])
+        if stereo:
+            T_lr[b, 0, 3] = rng.uniform(0.10, 0.15)
+            Tr = _inv(T_lr[b].astype(np.float64)).astype(np.float32)
+            uvr = project(L @ Tr[:3, :3].T + Tr[:3, 3], intr[b])
+            if pixel_sigma > 0:
+                uvr = uvr + rng.normal(0, pixel_sigma, uvr.shape)
+            uvr = (uvr + bad[:, None] * err[:, ::-1]).astype(np.float32)
+            uvr[sc["right_missing"]] = -1.0
+            uvrs.append(uvr)
+            miss.append(sc["right_missing"])
+    out = dict(B=B, offsets=offsets, n=ns.astype(np.int32), X=np.concatenate(Xs),
+               uv=np.concatenate(uvs), intr=intr, T_true=T_true, T_init=T_init)
+    if stereo:
+        out.update(uv_right=np.concatenate(uvrs), intr_r=intr.copy(), T_lr=T_lr,
+                   right_missing=np.concatenate(miss))
+    return out
+
+
 def planar_T(theta):
     """4x4 pose_b2b1 of the planar parameters (x, y, psi): rotation psi about
     the base z axis, translation (x, y, 0) (reference

@@ -18,7 +18,7 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import BaIterInfo, BaOptions, BaPoIter, check
+from ._lib import BaIterInfo, BaOptions, BaPoIter, BaPoResult, check
 
 SCALER = 0.01          # reference core/full_bundle_adjustment_solver.cpp:38
 INVERSE_SCALER = 1.0 / SCALER
@@ -219,6 +219,7 @@ class BaProblem:
         h = C.c_void_p()
         check(self.lib.ba_create(C.byref(h), device), "ba_create")
         self.h = h
+        self.device = device
         self._keep = []
         self.n_pose = self.n_pt = 0
         self.N = self.M = 0
@@ -611,6 +612,169 @@ class BaProblem:
                    debug=dbg[:min(n_it.value, cap)] if dbg is not None else None)
         out.update({k: m.astype(bool) for k, m in masks.items()})
         return out
+
+    # -- batched 6-DoF pose-only (ba_pose_only_{mono,stereo}6_batch) --
+    @staticmethod
+    def _batch_out(T, masks, rows, res, cap, dbg):
+        """One dict per problem, in the shape of pose_only_mono6's result."""
+        out = []
+        for b, r in enumerate(res):
+            nrows = max(0, min(r.n_rows, cap))
+            d = dict(T12=T[b], n_iter=r.n_iter, converged=bool(r.converged),
+                     success=(r.status == 0), status=r.status,
+                     rows=[tuple(float(v) for v in rows[b, i]) for i in range(nrows)],
+                     debug=dbg[b, :min(r.n_iter, cap)] if dbg is not None else None)
+            d.update({k: m[b] for k, m in masks.items()})
+            out.append(d)
+        return out
+
+    def pose_only_mono6_batch(self, offsets, X3, uv2, intr4, T12, mask, opt,
+                              cap=None, want_debug=False):
+        """B monocular 6-DoF problems in one launch.  offsets (B+1, int32):
+        problem b owns rows [offsets[b], offsets[b+1]) of X3 / uv2 / mask;
+        intr4 (B, 4) = fx fy cx cy, T12 (B, 12).  Returns one dict per problem
+        (T12, mask, n_iter, converged, success, status, rows, debug)."""
+        off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        B = off.size - 1
+        X = np.ascontiguousarray(X3, np.float32).reshape(-1, 3)
+        uv = np.ascontiguousarray(uv2, np.float32).reshape(-1, 2)
+        K = np.ascontiguousarray(intr4, np.float32).reshape(-1, 4)
+        T = np.ascontiguousarray(T12, np.float32).reshape(-1, 12).copy()
+        m = np.ascontiguousarray(mask, np.uint8).reshape(-1).copy()
+        if B >= 1 and not (off[-1] == X.shape[0] == uv.shape[0] == m.size and
+                           K.shape[0] == T.shape[0] == B):
+            raise ValueError("pose_only_mono6_batch: array sizes do not match offsets")
+        cap = cap or max(1, opt.max_num_iterations)
+        rows = np.zeros((max(B, 0), cap, 3), np.float32)
+        res = (BaPoResult * max(B, 1))()
+        dbg = np.zeros((max(B, 0), cap, 12), np.float32) if want_debug else None
+        check(self.lib.ba_pose_only_mono6_batch(
+            self.h, B, _ip(off), _fp(X), _fp(uv), _fp(K), _fp(T), _up(m),
+            C.byref(opt), rows.ctypes.data_as(C.POINTER(BaPoIter)), cap, res,
+            _fp(dbg) if want_debug else None), "ba_pose_only_mono6_batch")
+        masks = {"mask": [m[off[b]:off[b + 1]].astype(bool) for b in range(B)]}
+        return self._batch_out(T, masks, rows, list(res)[:B], cap, dbg)
+
+    def pose_only_stereo6_batch(self, offsets, X3, uvl2, uvr2, intr_l4, intr_r4,
+                                T_lr12, T12, mask_l, mask_r, opt, cap=None,
+                                want_debug=False):
+        """B stereo 6-DoF problems in one launch; as pose_only_mono6_batch plus
+        uvr2 (a negative coordinate: no right match), intr_r4 (B, 4), T_lr12
+        (B, 12) and the right masks."""
+        off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        B = off.size - 1
+        X = np.ascontiguousarray(X3, np.float32).reshape(-1, 3)
+        ul = np.ascontiguousarray(uvl2, np.float32).reshape(-1, 2)
+        ur = np.ascontiguousarray(uvr2, np.float32).reshape(-1, 2)
+        Kl = np.ascontiguousarray(intr_l4, np.float32).reshape(-1, 4)
+        Kr = np.ascontiguousarray(intr_r4, np.float32).reshape(-1, 4)
+        Tlr = np.ascontiguousarray(T_lr12, np.float32).reshape(-1, 12)
+        T = np.ascontiguousarray(T12, np.float32).reshape(-1, 12).copy()
+        ml = np.ascontiguousarray(mask_l, np.uint8).reshape(-1).copy()
+        mr = np.ascontiguousarray(mask_r, np.uint8).reshape(-1).copy()
+        if B >= 1 and not (off[-1] == X.shape[0] == ul.shape[0] == ur.shape[0] ==
+                           ml.size == mr.size and
+                           Kl.shape[0] == Kr.shape[0] == Tlr.shape[0] == T.shape[0] == B):
+            raise ValueError("pose_only_stereo6_batch: array sizes do not match offsets")
+        cap = cap or max(1, opt.max_num_iterations)
+        rows = np.zeros((max(B, 0), cap, 3), np.float32)
+        res = (BaPoResult * max(B, 1))()
+        dbg = np.zeros((max(B, 0), cap, 12), np.float32) if want_debug else None
+        check(self.lib.ba_pose_only_stereo6_batch(
+            self.h, B, _ip(off), _fp(X), _fp(ul), _fp(ur), _fp(Kl), _fp(Kr),
+            _fp(Tlr), _fp(T), _up(ml), _up(mr), C.byref(opt),
+            rows.ctypes.data_as(C.POINTER(BaPoIter)), cap, res,
+            _fp(dbg) if want_debug else None), "ba_pose_only_stereo6_batch")
+        masks = {"mask_l": [ml[off[b]:off[b + 1]].astype(bool) for b in range(B)],
+                 "mask_r": [mr[off[b]:off[b + 1]].astype(bool) for b in range(B)]}
+        return self._batch_out(T, masks, rows, list(res)[:B], cap, dbg)
+
+    def _tensor_args(self, what, specs):
+        """Check (name, tensor, dtype) triples: on this handle's GPU, the dtype,
+        contiguous.  Raises ValueError."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        for name, t, dtype in specs:
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("%s: %s must be a torch.Tensor" % (what, name))
+            if t.dtype != dtype:
+                raise ValueError("%s: %s must be %s, got %s" % (what, name, dtype, t.dtype))
+            if t.device != dev:
+                raise ValueError("%s: %s must be on %s, got %s" % (what, name, dev, t.device))
+            if not t.is_contiguous():
+                raise ValueError("%s: %s must be contiguous" % (what, name))
+
+    @staticmethod
+    def right_camera_records(intr_r4, T_lr12):
+        """(B, 16) right-camera records of ba_pose_only_stereo6_batch_device from
+        intr_r4 (B, 4) and T_lr12 (B, 12) torch tensors, on their device and
+        stream: the fp32 operations of ba_right_camera_record, one rounding each
+        (so the same bits)."""
+        import torch
+        B = T_lr12.shape[0]
+        R = T_lr12[:, :9].reshape(B, 3, 3).transpose(1, 2)   # left_to_right^-1
+        t = T_lr12[:, 9:]
+        tr = -((R[:, :, 0] * t[:, 0:1] + R[:, :, 1] * t[:, 1:2]) + R[:, :, 2] * t[:, 2:3])
+        return torch.cat([intr_r4, R.reshape(B, 9), tr], 1).contiguous()
+
+    def _batch_tensors(self, stereo, offsets, X3, uvl2, uvr2, intr_l4, intr_r4,
+                       T_lr12, T12, mask_l, mask_r, opt, cap, want_debug):
+        import torch
+        what = "pose_only_%s6_batch_tensors" % ("stereo" if stereo else "mono")
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        specs = [("offsets", offsets, i32), ("X3", X3, f32), ("uv2", uvl2, f32),
+                 ("intr4", intr_l4, f32), ("T12", T12, f32), ("mask", mask_l, u8)]
+        if stereo:
+            specs += [("uvr2", uvr2, f32), ("intr_r4", intr_r4, f32),
+                      ("T_lr12", T_lr12, f32), ("mask_r", mask_r, u8)]
+        self._tensor_args(what, specs)
+        B = offsets.numel() - 1
+        if B < 1:
+            raise ValueError("%s: offsets must hold B + 1 >= 2 values" % what)
+        dev = offsets.device
+        cap = cap or max(1, opt.max_num_iterations)
+        T = T12.clone()
+        ml = mask_l.clone()
+        res = torch.zeros((B, 4), dtype=i32, device=dev)
+        rows = torch.zeros((B, cap, 3), dtype=f32, device=dev)
+        dbg = torch.zeros((B, cap, 12), dtype=f32, device=dev) if want_debug else None
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        out = dict(T12=T, res=res, rows=rows, debug=dbg)
+        if stereo:
+            mr = mask_r.clone()
+            camr = self.right_camera_records(intr_r4, T_lr12)
+            check(self.lib.ba_pose_only_stereo6_batch_device(
+                self.h, B, p(offsets), p(X3), p(uvl2), p(uvr2), p(intr_l4), p(camr),
+                p(T), p(ml), p(mr), C.byref(opt), p(rows), cap, p(res), p(dbg),
+                stream), what)
+            out.update(mask_l=ml, mask_r=mr)
+        else:
+            check(self.lib.ba_pose_only_mono6_batch_device(
+                self.h, B, p(offsets), p(X3), p(uvl2), p(intr_l4), p(T), p(ml),
+                C.byref(opt), p(rows), cap, p(res), p(dbg), stream), what)
+            out.update(mask=ml)
+        return out
+
+    def pose_only_mono6_batch_tensors(self, offsets, X3, uv2, intr4, T12, mask,
+                                      opt, cap=None, want_debug=False):
+        """pose_only_mono6_batch on torch tensors already on this handle's GPU
+        (offsets int32, masks uint8, the rest float32, contiguous), enqueued on
+        torch.cuda.current_stream() without a host sync.  Returns new tensors:
+        T12 (B, 12), mask (N,), res (B, 4 int32: n_iter, converged, n_rows,
+        status), rows (B, cap, 3: cost, cost_change, abs_step), debug (B, cap,
+        12) or None."""
+        return self._batch_tensors(False, offsets, X3, uv2, None, intr4, None,
+                                   None, T12, mask, None, opt, cap, want_debug)
+
+    def pose_only_stereo6_batch_tensors(self, offsets, X3, uvl2, uvr2, intr_l4,
+                                        intr_r4, T_lr12, T12, mask_l, mask_r,
+                                        opt, cap=None, want_debug=False):
+        """The stereo counterpart of pose_only_mono6_batch_tensors (masks
+        returned as mask_l / mask_r); the right-camera records are built on the
+        device (right_camera_records)."""
+        return self._batch_tensors(True, offsets, X3, uvl2, uvr2, intr_l4, intr_r4,
+                                   T_lr12, T12, mask_l, mask_r, opt, cap, want_debug)
 
     def pose_only_mono3(self, X3, uv2, fx, fy, cx, cy, T_bc12, T_wl12, T12,
                         mask, opt, cap=None, want_debug=False):
@@ -1363,6 +1527,96 @@ class PoseOnlyBundleAdjustmentSolver:
         k = min(len(mask), n)
         m[:k] = np.asarray(mask[:k], np.uint8)
         return m
+
+    def _solve_6dof_batch(self, frames, options, stereo):
+        t0 = time.perf_counter()
+        f32 = lambda a, k: np.asarray(a, np.float32).reshape(-1, k)
+        to12 = lambda T: _T44_to_12(np.asarray(T, np.float64)).astype(np.float32)
+        prep = []
+        for fr in frames:        # every size check before any device use
+            X = f32(fr["reference_position_list"], 3)
+            if stereo:
+                uvs = [f32(fr["matched_left_pixel_list"], 2),
+                       f32(fr["matched_right_pixel_list"], 2)]
+                tag = "SolveStereoPoseOnlyBundleAdjustment6Dof"
+            else:
+                uvs = [f32(fr["matched_pixel_list"], 2)]
+                tag = "SolveMonocularPoseOnlyBundleAdjustment6Dof"
+            if any(u.shape[0] != X.shape[0] for u in uvs):
+                raise RuntimeError(
+                    "In PoseOnlyBundleAdjustmentSolver::%s(), "
+                    "world_position_list.size() != current_pixel_list.size()" % tag)
+            prep.append((X, uvs))
+        self.debug_poses_ = []
+        mkeys = (("mask_inlier_left", "mask_l"), ("mask_inlier_right", "mask_r")) \
+            if stereo else (("mask_inlier", "mask"),)
+        pkey = "reference_to_current_left_pose" if stereo else "reference_to_current_pose"
+        live = []
+        for k, (fr, (X, uvs)) in enumerate(zip(frames, prep)):
+            self._begin_summary(options, fr.get("summary"))
+            if X.shape[0] == 0:     # nothing to solve: masks resized, pose kept
+                for mk, _ in mkeys:
+                    self._write_mask(fr[mk], np.zeros(0, bool))
+            else:
+                live.append(k)
+        ok = [True] * len(frames)
+        if not live:
+            return ok
+        ns = [prep[k][0].shape[0] for k in live]
+        off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int32)
+        cat = lambda j: np.concatenate([prep[k][1][j] for k in live])
+        X = np.concatenate([prep[k][0] for k in live])
+        T = np.stack([to12(frames[k][pkey]) for k in live])
+        masks = [np.concatenate([self._fit_mask(frames[k][mk], prep[k][0].shape[0])
+                                 for k in live]) for mk, _ in mkeys]
+        if stereo:
+            il = [[frames[k]["fx_left"], frames[k]["fy_left"], frames[k]["cx_left"],
+                   frames[k]["cy_left"]] for k in live]
+            ir = [[frames[k]["fx_right"], frames[k]["fy_right"], frames[k]["cx_right"],
+                   frames[k]["cy_right"]] for k in live]
+            Tlr = np.stack([to12(frames[k]["left_to_right_pose"]) for k in live])
+            res = self._p.pose_only_stereo6_batch(off, X, cat(0), cat(1), il, ir, Tlr, T,
+                                                  masks[0], masks[1], options.to_c())
+        else:
+            intr = [[frames[k]["fx"], frames[k]["fy"], frames[k]["cx"], frames[k]["cy"]]
+                    for k in live]
+            res = self._p.pose_only_mono6_batch(off, X, cat(0), intr, T, masks[0],
+                                                options.to_c())
+        for k, r in zip(live, res):
+            fr = frames[k]
+            r["debug"] = []
+            ok[k] = self._finish_pose_only(r, fr[pkey], [(fr[mk], rk) for mk, rk in mkeys],
+                                           fr.get("summary"), t0)
+        self.debug_poses_ = []
+        return ok
+
+    @staticmethod
+    def _write_mask(mask, values):
+        if isinstance(mask, list):
+            mask[:] = [bool(v) for v in values]
+        else:
+            mask[...] = values
+
+    def Solve_Monocular_6Dof_Batch(self, frames, options):
+        """Many Solve_Monocular_6Dof problems in one GPU launch
+        (ba_pose_only_mono6_batch).  `frames` is a list of dicts keyed by
+        Solve_Monocular_6Dof's parameter names (reference_position_list,
+        matched_pixel_list, fx, fy, cx, cy, reference_to_current_pose,
+        mask_inlier, and optionally summary); poses, masks and summaries are
+        updated in place as that method updates them, and every frame gets
+        the bits the single call would give it (frames of <= 2048 points).
+        Returns the per-frame success flags.  A frame without points is left
+        as is (mask emptied, success).  GetDebugPoses() is empty afterwards."""
+        return self._solve_6dof_batch(frames, options, False)
+
+    def Solve_Stereo_6Dof_Batch(self, frames, options):
+        """Many Solve_Stereo_6Dof problems in one GPU launch
+        (ba_pose_only_stereo6_batch); frames are dicts keyed by that method's
+        parameter names (reference_position_list, matched_left_pixel_list,
+        matched_right_pixel_list, fx_left .. cy_right, left_to_right_pose,
+        reference_to_current_left_pose, mask_inlier_left, mask_inlier_right,
+        and optionally summary).  As Solve_Monocular_6Dof_Batch."""
+        return self._solve_6dof_batch(frames, options, True)
 
     def Solve_Monocular_Planar3Dof(self, world_position_list,
                                    matched_pixel_list, fx, fy, cx, cy,

@@ -56,6 +56,37 @@ class PoseOnlyBundleAdjustmentSolver {
                          Eigen::Isometry3f &reference_to_current_left_pose, std::vector<bool> &mask_inlier_left,
                          std::vector<bool> &mask_inlier_right, Options options, Summary *summary = nullptr);
 
+  // Many 6-DoF problems in one GPU launch (ba_pose_only_{mono,stereo}6_batch):
+  // one frame = the arguments of one Solve_Monocular_6Dof / Solve_Stereo_6Dof
+  // call, its in/out pose and masks, its Summary and its success flag, updated
+  // as the single call updates them (a frame of <= 2048 points gets the single
+  // call's bits).  Every size check comes before any device use.  Returns true
+  // when every frame succeeded.  Frames without points are left as they are
+  // (success).  GetDebugPoses() is empty afterwards.
+  struct MonocularFrame6Dof {
+    std::vector<Eigen::Vector3f> reference_position_list;
+    std::vector<Eigen::Vector2f> matched_pixel_list;
+    float fx{0.0f}, fy{0.0f}, cx{0.0f}, cy{0.0f};
+    Eigen::Isometry3f reference_to_current_pose;
+    std::vector<bool> mask_inlier;
+    Summary summary;
+    bool success{false};
+  };
+  struct StereoFrame6Dof {
+    std::vector<Eigen::Vector3f> reference_position_list;
+    std::vector<Eigen::Vector2f> matched_left_pixel_list;
+    std::vector<Eigen::Vector2f> matched_right_pixel_list;
+    float fx_left{0.0f}, fy_left{0.0f}, cx_left{0.0f}, cy_left{0.0f};
+    float fx_right{0.0f}, fy_right{0.0f}, cx_right{0.0f}, cy_right{0.0f};
+    Eigen::Isometry3f left_to_right_pose;
+    Eigen::Isometry3f reference_to_current_left_pose;
+    std::vector<bool> mask_inlier_left, mask_inlier_right;
+    Summary summary;
+    bool success{false};
+  };
+  bool Solve_Monocular_6Dof_Batch(std::vector<MonocularFrame6Dof> &frames, Options options);
+  bool Solve_Stereo_6Dof_Batch(std::vector<StereoFrame6Dof> &frames, Options options);
+
   const std::vector<Eigen::Isometry3f> &GetDebugPoses() const;
 
  private:

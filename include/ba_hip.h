@@ -398,6 +398,68 @@ int ba_pose_only_stereo3(ba_handle *h, const float *X3, const float *uvl2,
                          ba_po_iter *iters, int cap, int *n_iter, int *converged,
                          float *debug_T12);
 
+/* ---- batched pose-only 6-DoF (fp32): many problems in one launch ---------- */
+/* B independent Solve_Monocular_6Dof / Solve_Stereo_6Dof problems, one
+ * 1024-thread workgroup each, no grid barrier (any B is safe).  Problem b owns
+ * points [offsets[b], offsets[b+1]) of the concatenated X3 / uv2 (uvr2) / mask
+ * arrays, intrinsics intr4 + 4b (intr_l4, intr_r4 for stereo), T_lr12 + 12b
+ * (stereo), pose T12 + 12b (in/out), Summary rows iters + b*cap and debug poses
+ * debug_T12 + 12*b*cap (both optional, at most cap rows each); one ba_options
+ * for the whole batch.  res[b] receives its result.  A problem of n <= 2048
+ * points gives bit for bit what the single call gives it; larger ones agree to
+ * fp32 rounding (the single call spreads them over several workgroups, which
+ * sums in another order, and is faster for them).  max_num_iterations <= 0:
+ * every pose unchanged, converged, no rows.
+ * Host arrays: B >= 1, offsets[0] == 0 and strictly increasing offsets are
+ * checked first (else -1, nothing runs); one H2D copy, one launch, one D2H copy
+ * and a sync on the handle's stream.  Returns 0 when every problem was
+ * processed, whatever its status, and -1 on a runtime error. */
+typedef struct {
+  int n_iter, converged, n_rows, status;
+  /* n_rows = Summary rows logged (rows stored: min(n_rows, cap));
+   * status: 0 = pose written, 1 = NaN pose (input left unchanged, as the single
+   * call's return 1), 2 = malformed problem (device entry points only:
+   * offsets[b+1] <= offsets[b]; nothing else written) */
+} ba_po_result;
+int ba_pose_only_mono6_batch(ba_handle *h, int B, const int32_t *offsets,
+                             const float *X3, const float *uv2,
+                             const float *intr4, float *T12, uint8_t *mask,
+                             const ba_options *opt, ba_po_iter *iters, int cap,
+                             ba_po_result *res, float *debug_T12);
+int ba_pose_only_stereo6_batch(ba_handle *h, int B, const int32_t *offsets,
+                               const float *X3, const float *uvl2,
+                               const float *uvr2, const float *intr_l4,
+                               const float *intr_r4, const float *T_lr12,
+                               float *T12, uint8_t *mask_l, uint8_t *mask_r,
+                               const ba_options *opt, ba_po_iter *iters,
+                               int cap, ba_po_result *res, float *debug_T12);
+/* The same on DEVICE pointers (offsets and res included), enqueued on
+ * hip_stream (NULL = the handle's stream) with no copy and no synchronisation;
+ * only the pointers and B are checked on the host.  Stereo takes B prepared
+ * right-camera records camr16 (B x 16, from ba_right_camera_record) instead of
+ * intr_r4 and T_lr12. */
+int ba_pose_only_mono6_batch_device(ba_handle *h, int B, const int32_t *offsets,
+                                    const float *X3, const float *uv2,
+                                    const float *intr4, float *T12,
+                                    uint8_t *mask, const ba_options *opt,
+                                    ba_po_iter *iters, int cap,
+                                    ba_po_result *res, float *debug_T12,
+                                    void *hip_stream);
+int ba_pose_only_stereo6_batch_device(ba_handle *h, int B,
+                                      const int32_t *offsets, const float *X3,
+                                      const float *uvl2, const float *uvr2,
+                                      const float *intr_l4, const float *camr16,
+                                      float *T12, uint8_t *mask_l,
+                                      uint8_t *mask_r, const ba_options *opt,
+                                      ba_po_iter *iters, int cap,
+                                      ba_po_result *res, float *debug_T12,
+                                      void *hip_stream);
+/* Host helper: the right-camera record of one stereo problem, {fx, fy, cx, cy
+ * of intr_r4, then left_to_right^-1 as R (9, row-major) and t (3)}, with the
+ * fp32 expressions ba_pose_only_stereo6 uses. */
+int ba_right_camera_record(const float *intr_r4, const float *T_lr12,
+                           float *camr16);
+
 #ifdef __cplusplus
 }
 #endif
