@@ -205,6 +205,21 @@ SIGNATURES = {
                                                     _P, _P, _P, C.POINTER(BaOptions),
                                                     _P, C.c_int, _P, _P, _P]),
     "ba_right_camera_record": (C.c_int, [_F, _F, _F]),
+    "ba_pose_only_mono3_batch": (C.c_int, [_P, C.c_int, _I32, _F, _F, _F, _F, _F, _F, _U8,
+                                           C.POINTER(BaOptions), C.POINTER(BaPoIter),
+                                           C.c_int, C.POINTER(BaPoResult), _F]),
+    "ba_pose_only_stereo3_batch": (C.c_int, [_P, C.c_int, _I32, _F, _F, _F, _F, _F, _F,
+                                             _F, _F, _F, _U8, _U8, C.POINTER(BaOptions),
+                                             C.POINTER(BaPoIter), C.c_int,
+                                             C.POINTER(BaPoResult), _F]),
+    # device pointers (c_void_p) and a hipStream_t
+    "ba_pose_only_mono3_batch_device": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P,
+                                                  C.POINTER(BaOptions), _P, C.c_int,
+                                                  _P, _P, _P]),
+    "ba_pose_only_stereo3_batch_device": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P,
+                                                    _P, _P, _P, C.POINTER(BaOptions),
+                                                    _P, C.c_int, _P, _P, _P]),
+    "ba_planar_record": (C.c_int, [_F, _F, _F, _F, _F, _F]),
 }
 
 _lib = None

@@ -1928,15 +1928,18 @@ int ba_pose_only_stereo3(ba_handle *h, const float *X3, const float *uvl2,
 
 }  // extern "C"
 
-// ---- batched 6-DoF pose-only (one workgroup per problem) ----------------------
+// ---- batched pose-only, 6-DoF and planar 3-DoF (one workgroup per problem) ---
 namespace {
 // one pinned staging buffer mirroring one device buffer, as po_run:
-//   [offsets | X | uv | uv_right | intrinsics | right cameras | T | mask | mask_right]  <- H2D
-//                                               [ T | mask | mask_right | results | iters | debug ]  <- D2H
+//   [offsets | X | uv | uv_right | intrinsics | records | T | mask | mask_right]  <- H2D
+//                                          [ T | mask | mask_right | results | iters | debug ]  <- D2H
+// records: rec_floats per problem (6-DoF stereo: the 16-float right cameras,
+// 6-DoF mono: none, planar: the 52-float Po3Params)
 struct PoBatchLayout {
-  size_t off, X, uv, uvr, intr, camr, T, mask, maskr, h2d_end, res, iters, dbg, end;
+  size_t off, X, uv, uvr, intr, rec, T, mask, maskr, h2d_end, res, iters, dbg, end;
 };
-PoBatchLayout po_batch_layout(int B, int64_t N, int cap, bool stereo, bool want_iters, bool want_dbg) {
+PoBatchLayout po_batch_layout(int B, int64_t N, int cap, bool stereo, int rec_floats, bool want_iters,
+                              bool want_dbg) {
   auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
   PoBatchLayout L;
   size_t o = 0;
@@ -1945,7 +1948,7 @@ PoBatchLayout po_batch_layout(int B, int64_t N, int cap, bool stereo, bool want_
   L.uv = o;     o = al(o + (size_t)N * 2 * sizeof(float));
   L.uvr = o;    o = al(o + (stereo ? (size_t)N * 2 * sizeof(float) : 0));
   L.intr = o;   o = al(o + (size_t)B * 4 * sizeof(float));
-  L.camr = o;   o = al(o + (stereo ? (size_t)B * 16 * sizeof(float) : 0));
+  L.rec = o;    o = al(o + (size_t)B * rec_floats * sizeof(float));
   L.T = o;      o = al(o + (size_t)B * 12 * sizeof(float));
   L.mask = o;   o = al(o + (size_t)N);
   L.maskr = o;  o = al(o + (stereo ? (size_t)N : 0));
@@ -1971,15 +1974,20 @@ int po_batch_check(const char *fn, ba_handle *h, int B, const int32_t *offsets, 
   return 0;
 }
 
-int po_batch_run(const char *fn, ba_handle *h, bool stereo, int B, const int32_t *offsets,
+// planar: the records come from T_bc12 / T_wl12 / T12 (and T_lr12 / intr_r4 in
+// stereo) through po3_params, as in the single calls; 6-DoF stereo: the right
+// cameras from intr_r4 / T_lr12
+int po_batch_run(const char *fn, ba_handle *h, bool stereo, bool planar, int B, const int32_t *offsets,
                  const float *X3, const float *uvl2, const float *uvr2, const float *intr_l4,
-                 const float *intr_r4, const float *T_lr12, float *T12, uint8_t *mask_l,
-                 uint8_t *mask_r, const ba_options *opt, ba_po_iter *iters, int cap,
-                 ba_po_result *res, float *debug_T12) {
+                 const float *intr_r4, const float *T_lr12, const float *T_bc12, const float *T_wl12,
+                 float *T12, uint8_t *mask_l, uint8_t *mask_r, const ba_options *opt,
+                 ba_po_iter *iters, int cap, ba_po_result *res, float *debug_T12) {
   if (use_device(h)) return -1;
   const int64_t N = offsets[B];
   const bool want_it = iters && cap > 0, want_dbg = debug_T12 && cap > 0;
-  const PoBatchLayout L = po_batch_layout(B, N, cap, stereo, want_it, want_dbg);
+  constexpr int kRec3 = sizeof(ba::Po3Params) / sizeof(float);
+  const int rec_floats = planar ? kRec3 : (stereo ? 16 : 0);
+  const PoBatchLayout L = po_batch_layout(B, N, cap, stereo, rec_floats, want_it, want_dbg);
   if (po_reserve(h, L.end)) return -1;
   uint8_t *hb = h->po_host, *db = h->po_dev;
   std::memcpy(hb + L.off, offsets, (size_t)(B + 1) * sizeof(int32_t));
@@ -1988,10 +1996,19 @@ int po_batch_run(const char *fn, ba_handle *h, bool stereo, int B, const int32_t
   std::memcpy(hb + L.intr, intr_l4, (size_t)B * 4 * sizeof(float));
   std::memcpy(hb + L.T, T12, (size_t)B * 12 * sizeof(float));
   std::memcpy(hb + L.mask, mask_l, (size_t)N);
+  float *rec = (float *)(hb + L.rec);
+  if (planar) {
+    for (int b = 0; b < B; ++b) {
+      const ba::Po3Params P = po3_params(T_bc12 + 12 * b, T_wl12 + 12 * b, T12 + 12 * b,
+                                         stereo ? T_lr12 + 12 * b : nullptr,
+                                         stereo ? intr_r4 + 4 * b : nullptr);
+      std::memcpy(rec + (size_t)kRec3 * b, &P, sizeof(P));
+    }
+  } else if (stereo) {
+    for (int b = 0; b < B; ++b) po_right_camera(intr_r4 + 4 * b, T_lr12 + 12 * b, rec + 16 * b);
+  }
   if (stereo) {
     std::memcpy(hb + L.uvr, uvr2, (size_t)N * 2 * sizeof(float));
-    float *camr = (float *)(hb + L.camr);
-    for (int b = 0; b < B; ++b) po_right_camera(intr_r4 + 4 * b, T_lr12 + 12 * b, camr + 16 * b);
     std::memcpy(hb + L.maskr, mask_r, (size_t)N);
   }
   hipStream_t s = h->stream;
@@ -2000,16 +2017,23 @@ int po_batch_run(const char *fn, ba_handle *h, bool stereo, int B, const int32_t
   float *ddbg = want_dbg ? (float *)(db + L.dbg) : nullptr;
   const int32_t *doff = (const int32_t *)(db + L.off);
   ba_po_result *dres = (ba_po_result *)(db + L.res);
-  const int rc =
-      stereo ? ba_pose_only_stereo6_batch_device(
-                   h, B, doff, (const float *)(db + L.X), (const float *)(db + L.uv),
-                   (const float *)(db + L.uvr), (const float *)(db + L.intr),
-                   (const float *)(db + L.camr), (float *)(db + L.T), db + L.mask, db + L.maskr, opt,
-                   dit, cap, dres, ddbg, (void *)s)
-             : ba_pose_only_mono6_batch_device(h, B, doff, (const float *)(db + L.X),
-                                               (const float *)(db + L.uv), (const float *)(db + L.intr),
-                                               (float *)(db + L.T), db + L.mask, opt, dit, cap, dres,
-                                               ddbg, (void *)s);
+  const float *dX = (const float *)(db + L.X), *duv = (const float *)(db + L.uv);
+  const float *duvr = (const float *)(db + L.uvr), *dintr = (const float *)(db + L.intr);
+  const float *drec = (const float *)(db + L.rec);
+  float *dT = (float *)(db + L.T);
+  int rc;
+  if (planar)
+    rc = stereo ? ba_pose_only_stereo3_batch_device(h, B, doff, dX, duv, duvr, dintr, drec, dT,
+                                                    db + L.mask, db + L.maskr, opt, dit, cap, dres,
+                                                    ddbg, (void *)s)
+                : ba_pose_only_mono3_batch_device(h, B, doff, dX, duv, dintr, drec, dT, db + L.mask,
+                                                  opt, dit, cap, dres, ddbg, (void *)s);
+  else
+    rc = stereo ? ba_pose_only_stereo6_batch_device(h, B, doff, dX, duv, duvr, dintr, drec, dT,
+                                                    db + L.mask, db + L.maskr, opt, dit, cap, dres,
+                                                    ddbg, (void *)s)
+                : ba_pose_only_mono6_batch_device(h, B, doff, dX, duv, dintr, dT, db + L.mask, opt,
+                                                  dit, cap, dres, ddbg, (void *)s);
   if (rc) return fail(std::string(fn) + ": " + g_err);
   HIP_TRY(hipMemcpyAsync(hb + L.T, db + L.T, L.end - L.T, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -2086,8 +2110,8 @@ int ba_pose_only_mono6_batch(ba_handle *h, int B, const int32_t *offsets, const 
   if (po_batch_check(fn, h, B, offsets, cap)) return -1;
   if (!X3 || !uv2 || !intr4 || !T12 || !mask || !opt || !res)
     return fail(std::string(fn) + ": bad argument");
-  return po_batch_run(fn, h, false, B, offsets, X3, uv2, nullptr, intr4, nullptr, nullptr, T12, mask,
-                      nullptr, opt, iters, cap, res, debug_T12);
+  return po_batch_run(fn, h, false, false, B, offsets, X3, uv2, nullptr, intr4, nullptr, nullptr,
+                      nullptr, nullptr, T12, mask, nullptr, opt, iters, cap, res, debug_T12);
 }
 
 int ba_pose_only_stereo6_batch(ba_handle *h, int B, const int32_t *offsets, const float *X3,
@@ -2100,8 +2124,84 @@ int ba_pose_only_stereo6_batch(ba_handle *h, int B, const int32_t *offsets, cons
   if (!X3 || !uvl2 || !uvr2 || !intr_l4 || !intr_r4 || !T_lr12 || !T12 || !mask_l || !mask_r || !opt ||
       !res)
     return fail(std::string(fn) + ": bad argument");
-  return po_batch_run(fn, h, true, B, offsets, X3, uvl2, uvr2, intr_l4, intr_r4, T_lr12, T12, mask_l,
-                      mask_r, opt, iters, cap, res, debug_T12);
+  return po_batch_run(fn, h, true, false, B, offsets, X3, uvl2, uvr2, intr_l4, intr_r4, T_lr12,
+                      nullptr, nullptr, T12, mask_l, mask_r, opt, iters, cap, res, debug_T12);
+}
+
+// ---- batched planar 3-DoF -----------------------------------------------------
+int ba_planar_record(const float *T_bc12, const float *T_wl12, const float *T12,
+                     const float *T_lr12, const float *intr_r4, float *rec52) {
+  if (!T_bc12 || !T_wl12 || !T12 || !rec52 || (!T_lr12) != (!intr_r4))
+    return fail("ba_planar_record: bad argument");
+  const ba::Po3Params P = po3_params(T_bc12, T_wl12, T12, T_lr12, intr_r4);
+  std::memcpy(rec52, &P, sizeof(P));
+  return 0;
+}
+
+int ba_pose_only_mono3_batch_device(ba_handle *h, int B, const int32_t *offsets, const float *X3,
+                                    const float *uv2, const float *intr4, const float *rec52,
+                                    float *T12, uint8_t *mask, const ba_options *opt,
+                                    ba_po_iter *iters, int cap, ba_po_result *res, float *debug_T12,
+                                    void *hip_stream) {
+  if (!h || B < 1 || !offsets || !X3 || !uv2 || !intr4 || !rec52 || !T12 || !mask || !opt || !res ||
+      cap < 0)
+    return fail("ba_pose_only_mono3_batch_device: bad argument");
+  if (use_device(h)) return -1;
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  if (ba::pose_only3_batch_device(false, B, offsets, X3, uv2, nullptr, intr4, rec52, T12, mask,
+                                  nullptr, opt->threshold_huber_loss, opt->threshold_step_size,
+                                  opt->threshold_cost_change, opt->threshold_outlier_rejection,
+                                  opt->max_num_iterations, cap > 0 ? (ba::PoIter *)iters : nullptr,
+                                  cap, (int *)res, cap > 0 ? debug_T12 : nullptr, s))
+    return fail("ba_pose_only_mono3_batch_device: kernel launch failed");
+  return 0;
+}
+
+int ba_pose_only_stereo3_batch_device(ba_handle *h, int B, const int32_t *offsets, const float *X3,
+                                      const float *uvl2, const float *uvr2, const float *intr_l4,
+                                      const float *rec52, float *T12, uint8_t *mask_l,
+                                      uint8_t *mask_r, const ba_options *opt, ba_po_iter *iters,
+                                      int cap, ba_po_result *res, float *debug_T12,
+                                      void *hip_stream) {
+  if (!h || B < 1 || !offsets || !X3 || !uvl2 || !uvr2 || !intr_l4 || !rec52 || !T12 || !mask_l ||
+      !mask_r || !opt || !res || cap < 0)
+    return fail("ba_pose_only_stereo3_batch_device: bad argument");
+  if (use_device(h)) return -1;
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  if (ba::pose_only3_batch_device(true, B, offsets, X3, uvl2, uvr2, intr_l4, rec52, T12, mask_l,
+                                  mask_r, opt->threshold_huber_loss, opt->threshold_step_size,
+                                  opt->threshold_cost_change, opt->threshold_outlier_rejection,
+                                  opt->max_num_iterations, cap > 0 ? (ba::PoIter *)iters : nullptr,
+                                  cap, (int *)res, cap > 0 ? debug_T12 : nullptr, s))
+    return fail("ba_pose_only_stereo3_batch_device: kernel launch failed");
+  return 0;
+}
+
+int ba_pose_only_mono3_batch(ba_handle *h, int B, const int32_t *offsets, const float *X3,
+                             const float *uv2, const float *intr4, const float *T_bc12,
+                             const float *T_wl12, float *T12, uint8_t *mask, const ba_options *opt,
+                             ba_po_iter *iters, int cap, ba_po_result *res, float *debug_T12) {
+  const char *fn = "ba_pose_only_mono3_batch";
+  if (po_batch_check(fn, h, B, offsets, cap)) return -1;
+  if (!X3 || !uv2 || !intr4 || !T_bc12 || !T_wl12 || !T12 || !mask || !opt || !res)
+    return fail(std::string(fn) + ": bad argument");
+  return po_batch_run(fn, h, false, true, B, offsets, X3, uv2, nullptr, intr4, nullptr, nullptr,
+                      T_bc12, T_wl12, T12, mask, nullptr, opt, iters, cap, res, debug_T12);
+}
+
+int ba_pose_only_stereo3_batch(ba_handle *h, int B, const int32_t *offsets, const float *X3,
+                               const float *uvl2, const float *uvr2, const float *intr_l4,
+                               const float *intr_r4, const float *T_bc12, const float *T_lr12,
+                               const float *T_wl12, float *T12, uint8_t *mask_l, uint8_t *mask_r,
+                               const ba_options *opt, ba_po_iter *iters, int cap, ba_po_result *res,
+                               float *debug_T12) {
+  const char *fn = "ba_pose_only_stereo3_batch";
+  if (po_batch_check(fn, h, B, offsets, cap)) return -1;
+  if (!X3 || !uvl2 || !uvr2 || !intr_l4 || !intr_r4 || !T_bc12 || !T_lr12 || !T_wl12 || !T12 ||
+      !mask_l || !mask_r || !opt || !res)
+    return fail(std::string(fn) + ": bad argument");
+  return po_batch_run(fn, h, true, true, B, offsets, X3, uvl2, uvr2, intr_l4, intr_r4, T_lr12,
+                      T_bc12, T_wl12, T12, mask_l, mask_r, opt, iters, cap, res, debug_T12);
 }
 
 }  // extern "C"

@@ -443,12 +443,23 @@ struct Po3Params {
   float Rrb[9];          // R_rl * R_cb: the right camera's Jacobian rotation (:678-679)
   float cam_r[4];        // right fx, fy, cx, cy (stereo)
 };
+// the 52-float planar record of ba_planar_record / the batched planar solvers
+static_assert(sizeof(Po3Params) == 52 * sizeof(float), "Po3Params must be 52 floats");
 int pose_only_planar3_device(bool stereo, const float *dX3, const float *duvl2,
                              const float *duvr2, int n, float fx, float fy, float cx, float cy,
                              const Po3Params &P, float *dT12, uint8_t *dmask_l, uint8_t *dmask_r,
                              float thr_huber, float thr_step, float thr_cost, float thr_out,
                              int max_it, PoIter *d_iters, int cap, int *d_meta, float *d_debug,
                              int *d_gsync, float *d_partial, hipStream_t s);
+// B independent planar problems, one workgroup each (k_pose_only3<STEREO, true>);
+// device pointers laid out as in ba_pose_only_{mono,stereo}3_batch_device
+// (d_rec52 = B Po3Params records; d_res = B ba_po_result).  Enqueue only.
+int pose_only3_batch_device(bool stereo, int B, const int *d_offsets, const float *dX3,
+                            const float *duvl2, const float *duvr2, const float *d_intr_l4,
+                            const float *d_rec52, float *dT12, uint8_t *dmask_l, uint8_t *dmask_r,
+                            float thr_huber, float thr_step, float thr_cost, float thr_out,
+                            int max_it, PoIter *d_iters, int cap, int *d_res, float *d_debug,
+                            hipStream_t s);
 
 }  // namespace ba
 #endif

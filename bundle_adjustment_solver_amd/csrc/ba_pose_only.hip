@@ -546,15 +546,56 @@ __device__ __forceinline__ void po3_set_pose(const float *th, const Po3Params &P
 // The input points are base-1 coordinates; X_c = T_cb * T_b2b1(theta) * X.
 // T12 (world_to_current) is only written, with pose_b2b1^-1 * base_to_camera
 // (:549-551, :604-612), when at least one iteration ran and the pose is not NaN.
-template <bool STEREO>
+//
+// BATCH (ba_pose_only_{mono,stereo}3_batch): B independent problems, one
+// workgroup each, as k_pose_only6<STEREO, true>: gsync = offsets (B+1),
+// partial = left intrinsics (B x 4), recs = the planar records (B x Po3Params,
+// built on the host: the prior's psi is a host atan2), T12 (B x 12), iters
+// (B x cap), debug_T12 (B x cap x 12), meta = ba_po_result records (status 0 =
+// pose written, 1 = NaN, 2 = empty range and nothing else written); n, fx..cy
+// and P1 are unused.  G = 1 at compile time: the arithmetic of a one-workgroup
+// launch of k_pose_only3<STEREO, false>.  Single calls pass recs = nullptr.
+template <bool STEREO, bool BATCH>
 __global__ __launch_bounds__(kPoThreads) void k_pose_only3(
     const float *__restrict__ X3, const float *__restrict__ uv2,
     const float *__restrict__ uvr2, int n, float fx, float fy, float cx, float cy,
-    const Po3Params P, float *T12, uint8_t *mask, uint8_t *maskr, float thr_huber,
+    const Po3Params P1, float *T12, uint8_t *mask, uint8_t *maskr, float thr_huber,
     float thr_step, float thr_cost, float thr_out, int max_it, PoIter *iters, int cap,
-    int *meta, float *debug_T12, int *gsync, float *partial) {
-  const int G = gridDim.x;
-  const bool lead = blockIdx.x == 0;
+    int *meta, float *debug_T12, int *gsync, float *partial,
+    const Po3Params *__restrict__ recs) {
+  if constexpr (BATCH) {
+    const unsigned b = blockIdx.x;
+    const int o = gsync[b];
+    n = gsync[b + 1] - o;
+    meta += 4 * (size_t)b;
+    if (n <= 0) {
+      if (threadIdx.x == 0) {
+        meta[0] = 0;
+        meta[1] = 0;
+        meta[2] = 0;
+        meta[3] = 2;
+      }
+      return;
+    }
+    X3 += 3 * (size_t)o;
+    uv2 += 2 * (size_t)o;
+    mask += o;
+    if (STEREO) {
+      uvr2 += 2 * (size_t)o;
+      maskr += o;
+    }
+    recs += b;
+    fx = partial[4 * b];
+    fy = partial[4 * b + 1];
+    cx = partial[4 * b + 2];
+    cy = partial[4 * b + 3];
+    T12 += 12 * (size_t)b;
+    if (iters) iters += (size_t)b * cap;
+    if (debug_T12) debug_T12 += (size_t)b * cap * 12;
+  }
+  const Po3Params &P = BATCH ? *recs : P1;
+  const int G = BATCH ? 1 : gridDim.x;
+  const bool lead = BATCH ? true : blockIdx.x == 0;
   __shared__ float red[kPoWaves][kNred3];
   __shared__ float tots[kNred3];
   __shared__ float Hs[9], gs[3], tmps[3];
@@ -578,7 +619,7 @@ __global__ __launch_bounds__(kPoThreads) void k_pose_only3(
       meta[0] = 0;
       meta[1] = 1;
       meta[2] = 0;
-      meta[3] = 1;
+      meta[3] = BATCH ? 0 : 1;
     }
   }
   int n_rows = 0;  // Summary rows logged so far (thread 0)
@@ -606,7 +647,7 @@ __global__ __launch_bounds__(kPoThreads) void k_pose_only3(
     // stereo, where four would spill
     constexpr int kU = STEREO ? 2 : 4;
     const int gstride = G * kPoThreads;
-    for (int p0 = blockIdx.x * kPoThreads + tid; p0 < n; p0 += kU * gstride) {
+    for (int p0 = (BATCH ? 0u : blockIdx.x) * kPoThreads + tid; p0 < n; p0 += kU * gstride) {
       float Xb[kU][3], ub[kU][2], urb[kU][2];
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
@@ -735,7 +776,7 @@ __global__ __launch_bounds__(kPoThreads) void k_pose_only3(
   }
   if (tid == 0 && lead && ctl[1] > 0) {
     if (s_nan) {
-      meta[3] = 0;  // :604-612: do not update on NaN
+      meta[3] = BATCH ? 1 : 0;  // :604-612: do not update on NaN
     } else {
       for (int q = 0; q < 12; ++q) T12[q] = wpose[q];
     }
@@ -811,14 +852,39 @@ int pose_only_planar3_device(bool stereo, const float *dX3, const float *duvl2,
   // d_gsync must be zero on entry (the caller's single H2D copy covers it)
   static_assert(kNred3 <= kNred, "partial-sum buffer sized for the 6-DoF sums");
   if (stereo)
-    hipLaunchKernelGGL(k_pose_only3<true>, dim3(po_groups(n)), dim3(kPoThreads), 0, s, dX3, duvl2,
-                       duvr2, n, fx, fy, cx, cy, P, dT12, dmask_l, dmask_r, thr_huber, thr_step,
-                       thr_cost, thr_out, max_it, d_iters, cap, d_meta, d_debug, d_gsync, d_partial);
+    hipLaunchKernelGGL((k_pose_only3<true, false>), dim3(po_groups(n)), dim3(kPoThreads), 0, s, dX3,
+                       duvl2, duvr2, n, fx, fy, cx, cy, P, dT12, dmask_l, dmask_r, thr_huber, thr_step,
+                       thr_cost, thr_out, max_it, d_iters, cap, d_meta, d_debug, d_gsync, d_partial,
+                       (const Po3Params *)nullptr);
   else
-    hipLaunchKernelGGL(k_pose_only3<false>, dim3(po_groups(n)), dim3(kPoThreads), 0, s, dX3, duvl2,
-                       (const float *)nullptr, n, fx, fy, cx, cy, P, dT12, dmask_l,
+    hipLaunchKernelGGL((k_pose_only3<false, false>), dim3(po_groups(n)), dim3(kPoThreads), 0, s, dX3,
+                       duvl2, (const float *)nullptr, n, fx, fy, cx, cy, P, dT12, dmask_l,
                        (uint8_t *)nullptr, thr_huber, thr_step, thr_cost, thr_out, max_it, d_iters,
-                       cap, d_meta, d_debug, d_gsync, d_partial);
+                       cap, d_meta, d_debug, d_gsync, d_partial, (const Po3Params *)nullptr);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int pose_only3_batch_device(bool stereo, int B, const int *d_offsets, const float *dX3,
+                            const float *duvl2, const float *duvr2, const float *d_intr_l4,
+                            const float *d_rec52, float *dT12, uint8_t *dmask_l, uint8_t *dmask_r,
+                            float thr_huber, float thr_step, float thr_cost, float thr_out,
+                            int max_it, PoIter *d_iters, int cap, int *d_res, float *d_debug,
+                            hipStream_t s) {
+  // per-batch arrays in the slots k_pose_only3<STEREO, true> re-points (see there)
+  int *offs = const_cast<int *>(d_offsets);
+  float *intr = const_cast<float *>(d_intr_l4);
+  const Po3Params *recs = reinterpret_cast<const Po3Params *>(d_rec52);
+  const Po3Params unused{};
+  if (stereo)
+    hipLaunchKernelGGL((k_pose_only3<true, true>), dim3(B), dim3(kPoThreads), 0, s, dX3, duvl2,
+                       duvr2, 0, 0.0f, 0.0f, 0.0f, 0.0f, unused, dT12, dmask_l, dmask_r, thr_huber,
+                       thr_step, thr_cost, thr_out, max_it, d_iters, cap, d_res, d_debug, offs, intr,
+                       recs);
+  else
+    hipLaunchKernelGGL((k_pose_only3<false, true>), dim3(B), dim3(kPoThreads), 0, s, dX3, duvl2,
+                       (const float *)nullptr, 0, 0.0f, 0.0f, 0.0f, 0.0f, unused, dT12, dmask_l,
+                       (uint8_t *)nullptr, thr_huber, thr_step, thr_cost, thr_out, max_it, d_iters,
+                       cap, d_res, d_debug, offs, intr, recs);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

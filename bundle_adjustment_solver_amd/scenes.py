@@ -521,7 +521,8 @@ def planar_T(theta):
 
 
 def planar_pose_only_scene(n=10_000, seed=SEED_BASE + 7, pixel_sigma=0.0,
-                           stereo=False, right_missing_frac=0.2):
+                           stereo=False, right_missing_frac=0.2, intr=None,
+                           height=0.3, baseline=BASELINE):
     """Planar 3-DoF pose-only scene (reference
     core/pose_only_bundle_adjustment_solver.cpp:401-900 conventions): a wheeled
     base carries a forward-looking camera (optical axis along base x, image x
@@ -534,11 +535,14 @@ def planar_pose_only_scene(n=10_000, seed=SEED_BASE + 7, pixel_sigma=0.0,
     perturbed theta_init.  T_out_true is what the reference writes back at the
     true theta: pose_b2b1^-1 * T_bc (:549-551).  Stereo: the right camera sees
     left_to_right^-1 * X_left with left_to_right = translate(+0.12, 0, 0); a
-    fraction of the points has no right match (pixel -1)."""
+    fraction of the points has no right match (pixel -1).  intr = (fx, fy, cx,
+    cy), the camera height and the stereo baseline default to FX..CY, 0.3 m and
+    BASELINE; they draw nothing from the generator."""
     rng = np.random.default_rng(seed)
+    fx, fy, cx, cy = (FX, FY, CX, CY) if intr is None else (float(v) for v in intr)
     T_bc = np.eye(4)
     T_bc[:3, :3] = [[0, 0, 1], [-1, 0, 0], [0, -1, 0]]
-    T_bc[:3, 3] = [0.0, 0.0, 0.3]
+    T_bc[:3, 3] = [0.0, 0.0, height]
     theta_true = np.array([rng.uniform(0.05, 0.25), rng.uniform(-0.15, 0.15),
                            rng.uniform(-0.2, 0.2)])
     theta_init = theta_true + np.array([rng.uniform(-0.01, 0.01),      # odometry prior
@@ -550,7 +554,7 @@ def planar_pose_only_scene(n=10_000, seed=SEED_BASE + 7, pixel_sigma=0.0,
     Xb2 = Xc @ T_bc[:3, :3].T + T_bc[:3, 3]
     Pi = _inv(planar_T(theta_true))
     X = (Xb2 @ Pi[:3, :3].T + Pi[:3, 3]).astype(np.float32)
-    uv = np.stack([FX * Xc[:, 0] / Xc[:, 2] + CX, FY * Xc[:, 1] / Xc[:, 2] + CY], 1)
+    uv = np.stack([fx * Xc[:, 0] / Xc[:, 2] + cx, fy * Xc[:, 1] / Xc[:, 2] + cy], 1)
     if pixel_sigma > 0:
         uv = uv + rng.normal(0, pixel_sigma, uv.shape)
     W_b1 = planar_T([2.0, -1.0, 0.3])
@@ -558,17 +562,69 @@ def planar_pose_only_scene(n=10_000, seed=SEED_BASE + 7, pixel_sigma=0.0,
     T_wc_init = W_b1 @ _inv(planar_T(theta_init)) @ T_bc
     T_out_true = _inv(planar_T(theta_true)) @ T_bc
     f32 = lambda a: np.asarray(a, np.float32)
-    sc = dict(X=X, uv=f32(uv), fx=FX, fy=FY, cx=CX, cy=CY, T_bc=f32(T_bc),
+    sc = dict(X=X, uv=f32(uv), fx=fx, fy=fy, cx=cx, cy=cy, T_bc=f32(T_bc),
               T_wl=f32(T_wl), T_wc_init=f32(T_wc_init), theta_true=theta_true,
               theta_init=theta_init, T_out_true=f32(T_out_true))
     if stereo:
         T_lr = np.eye(4)
-        T_lr[0, 3] = BASELINE
+        T_lr[0, 3] = baseline
         Xr = Xc - T_lr[:3, 3]
-        uvr = np.stack([FX * Xr[:, 0] / Xr[:, 2] + CX, FY * Xr[:, 1] / Xr[:, 2] + CY], 1)
+        uvr = np.stack([fx * Xr[:, 0] / Xr[:, 2] + cx, fy * Xr[:, 1] / Xr[:, 2] + cy], 1)
         if pixel_sigma > 0:
             uvr = uvr + rng.normal(0, pixel_sigma, uvr.shape)
         miss = rng.uniform(size=n) < right_missing_frac
         uvr[miss] = -1.0
         sc.update(uv_right=f32(uvr), T_lr=f32(T_lr), right_missing=miss)
     return sc
+
+
+def planar_pose_only_batch_scene(B, n_min, n_max, seed, stereo=False, pixel_sigma=0.0,
+                                 right_missing_frac=0.0, outlier_frac=0.0):
+    """B independent planar 3-DoF problems for the batched planar solvers
+    (ba_pose_only_{mono,stereo}3_batch), concatenated: problem b owns rows
+    [offsets[b], offsets[b+1]) of X / uv (/ uv_right, right_missing).  Each is a
+    planar_pose_only_scene of n_min..n_max points with its own theta_true and
+    theta_init (drawn by that scene), intrinsics (fx 300..600), camera height
+    (0.2..0.5 m) and, in stereo, baseline (0.10..0.15 m); pixels get
+    `pixel_sigma` noise and an `outlier_frac` of the points a gross error of
+    20..60 px (a missing right pixel stays -1).  Per-problem arrays: intr,
+    T_bc, T_wl, T_wc_init, T_out_true, theta_true, theta_init (and intr_r,
+    T_lr).  Seeded."""
+    rng = np.random.default_rng(seed)
+    ns = rng.integers(n_min, n_max + 1, B)
+    offsets = np.zeros(B + 1, np.int32)
+    offsets[1:] = np.cumsum(ns)
+    keys = ("T_bc", "T_wl", "T_wc_init", "T_out_true", "theta_true", "theta_init")
+    per = {k: [] for k in keys}
+    Xs, uvs, uvrs, miss, intr, T_lr = [], [], [], [], [], []
+    for b in range(B):
+        n = int(ns[b])
+        sub = int(rng.integers(1 << 30))
+        fx = rng.uniform(300.0, 600.0)
+        K = [fx, fx * rng.uniform(0.98, 1.02), rng.uniform(300.0, 340.0),
+             rng.uniform(220.0, 260.0)]
+        height = rng.uniform(0.2, 0.5)
+        baseline = rng.uniform(0.10, 0.15)
+        sc = planar_pose_only_scene(n, seed=sub, pixel_sigma=pixel_sigma, stereo=stereo,
+                                    right_missing_frac=right_missing_frac, intr=K,
+                                    height=height, baseline=baseline)
+        bad = rng.uniform(size=n) < outlier_frac
+        err = rng.uniform(20.0, 60.0, (n, 2)) * rng.choice([-1.0, 1.0], (n, 2))
+        Xs.append(sc["X"])
+        uvs.append((sc["uv"] + bad[:, None] * err).astype(np.float32))
+        intr.append(K)
+        for k in keys:
+            per[k].append(sc[k])
+        if stereo:
+            uvr = (sc["uv_right"] + bad[:, None] * err[:, ::-1]).astype(np.float32)
+            uvr[sc["right_missing"]] = -1.0
+            uvrs.append(uvr)
+            miss.append(sc["right_missing"])
+            T_lr.append(sc["T_lr"])
+    out = dict(B=B, offsets=offsets, n=ns.astype(np.int32), X=np.concatenate(Xs),
+               uv=np.concatenate(uvs), intr=np.asarray(intr, np.float32))
+    out.update({k: np.stack(v) for k, v in per.items()})
+    if stereo:
+        out.update(uv_right=np.concatenate(uvrs), intr_r=out["intr"].copy(),
+                   T_lr=np.stack(T_lr), right_missing=np.concatenate(miss))
+    return out

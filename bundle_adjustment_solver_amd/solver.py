@@ -628,6 +628,18 @@ class BaProblem:
             out.append(d)
         return out
 
+    @staticmethod
+    def _batch_buffers(what, B, sizes_ok, opt, cap, want_debug):
+        """The size check and the output buffers of a numpy batch call: rows
+        (B, cap, 3), the ba_po_result array and debug poses (B, cap, 12)."""
+        if B >= 1 and not sizes_ok:
+            raise ValueError("%s: array sizes do not match offsets" % what)
+        cap = cap or max(1, opt.max_num_iterations)
+        rows = np.zeros((max(B, 0), cap, 3), np.float32)
+        res = (BaPoResult * max(B, 1))()
+        dbg = np.zeros((max(B, 0), cap, 12), np.float32) if want_debug else None
+        return cap, rows, res, dbg
+
     def pose_only_mono6_batch(self, offsets, X3, uv2, intr4, T12, mask, opt,
                               cap=None, want_debug=False):
         """B monocular 6-DoF problems in one launch.  offsets (B+1, int32):
@@ -641,13 +653,10 @@ class BaProblem:
         K = np.ascontiguousarray(intr4, np.float32).reshape(-1, 4)
         T = np.ascontiguousarray(T12, np.float32).reshape(-1, 12).copy()
         m = np.ascontiguousarray(mask, np.uint8).reshape(-1).copy()
-        if B >= 1 and not (off[-1] == X.shape[0] == uv.shape[0] == m.size and
-                           K.shape[0] == T.shape[0] == B):
-            raise ValueError("pose_only_mono6_batch: array sizes do not match offsets")
-        cap = cap or max(1, opt.max_num_iterations)
-        rows = np.zeros((max(B, 0), cap, 3), np.float32)
-        res = (BaPoResult * max(B, 1))()
-        dbg = np.zeros((max(B, 0), cap, 12), np.float32) if want_debug else None
+        cap, rows, res, dbg = self._batch_buffers(
+            "pose_only_mono6_batch", B,
+            off[-1] == X.shape[0] == uv.shape[0] == m.size and
+            K.shape[0] == T.shape[0] == B, opt, cap, want_debug)
         check(self.lib.ba_pose_only_mono6_batch(
             self.h, B, _ip(off), _fp(X), _fp(uv), _fp(K), _fp(T), _up(m),
             C.byref(opt), rows.ctypes.data_as(C.POINTER(BaPoIter)), cap, res,
@@ -672,14 +681,11 @@ class BaProblem:
         T = np.ascontiguousarray(T12, np.float32).reshape(-1, 12).copy()
         ml = np.ascontiguousarray(mask_l, np.uint8).reshape(-1).copy()
         mr = np.ascontiguousarray(mask_r, np.uint8).reshape(-1).copy()
-        if B >= 1 and not (off[-1] == X.shape[0] == ul.shape[0] == ur.shape[0] ==
-                           ml.size == mr.size and
-                           Kl.shape[0] == Kr.shape[0] == Tlr.shape[0] == T.shape[0] == B):
-            raise ValueError("pose_only_stereo6_batch: array sizes do not match offsets")
-        cap = cap or max(1, opt.max_num_iterations)
-        rows = np.zeros((max(B, 0), cap, 3), np.float32)
-        res = (BaPoResult * max(B, 1))()
-        dbg = np.zeros((max(B, 0), cap, 12), np.float32) if want_debug else None
+        cap, rows, res, dbg = self._batch_buffers(
+            "pose_only_stereo6_batch", B,
+            off[-1] == X.shape[0] == ul.shape[0] == ur.shape[0] == ml.size == mr.size and
+            Kl.shape[0] == Kr.shape[0] == Tlr.shape[0] == T.shape[0] == B, opt, cap,
+            want_debug)
         check(self.lib.ba_pose_only_stereo6_batch(
             self.h, B, _ip(off), _fp(X), _fp(ul), _fp(ur), _fp(Kl), _fp(Kr),
             _fp(Tlr), _fp(T), _up(ml), _up(mr), C.byref(opt),
@@ -718,16 +724,24 @@ class BaProblem:
         return torch.cat([intr_r4, R.reshape(B, 9), tr], 1).contiguous()
 
     def _batch_tensors(self, stereo, offsets, X3, uvl2, uvr2, intr_l4, intr_r4,
-                       T_lr12, T12, mask_l, mask_r, opt, cap, want_debug):
+                       T_lr12, T12, mask_l, mask_r, opt, cap, want_debug, rec=None):
+        # rec given: the planar 3-DoF batch (B x 52 records, see planar_records)
         import torch
-        what = "pose_only_%s6_batch_tensors" % ("stereo" if stereo else "mono")
+        planar = rec is not None
+        what = "pose_only_%s%d_batch_tensors" % ("stereo" if stereo else "mono",
+                                                3 if planar else 6)
         f32, i32, u8 = torch.float32, torch.int32, torch.uint8
         specs = [("offsets", offsets, i32), ("X3", X3, f32), ("uv2", uvl2, f32),
                  ("intr4", intr_l4, f32), ("T12", T12, f32), ("mask", mask_l, u8)]
         if stereo:
-            specs += [("uvr2", uvr2, f32), ("intr_r4", intr_r4, f32),
-                      ("T_lr12", T_lr12, f32), ("mask_r", mask_r, u8)]
+            specs += [("uvr2", uvr2, f32), ("mask_r", mask_r, u8)]
+            if not planar:
+                specs += [("intr_r4", intr_r4, f32), ("T_lr12", T_lr12, f32)]
+        if planar:
+            specs += [("rec", rec, f32)]
         self._tensor_args(what, specs)
+        if planar and tuple(rec.shape) != (offsets.numel() - 1, 52):
+            raise ValueError("%s: rec must be (B, 52), got %s" % (what, tuple(rec.shape)))
         B = offsets.numel() - 1
         if B < 1:
             raise ValueError("%s: offsets must hold B + 1 >= 2 values" % what)
@@ -741,7 +755,20 @@ class BaProblem:
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         out = dict(T12=T, res=res, rows=rows, debug=dbg)
-        if stereo:
+        if planar:
+            mr = mask_r.clone() if stereo else None
+            if stereo:
+                check(self.lib.ba_pose_only_stereo3_batch_device(
+                    self.h, B, p(offsets), p(X3), p(uvl2), p(uvr2), p(intr_l4), p(rec),
+                    p(T), p(ml), p(mr), C.byref(opt), p(rows), cap, p(res), p(dbg),
+                    stream), what)
+                out.update(mask_l=ml, mask_r=mr)
+            else:
+                check(self.lib.ba_pose_only_mono3_batch_device(
+                    self.h, B, p(offsets), p(X3), p(uvl2), p(intr_l4), p(rec), p(T),
+                    p(ml), C.byref(opt), p(rows), cap, p(res), p(dbg), stream), what)
+                out.update(mask=ml)
+        elif stereo:
             mr = mask_r.clone()
             camr = self.right_camera_records(intr_r4, T_lr12)
             check(self.lib.ba_pose_only_stereo6_batch_device(
@@ -775,6 +802,116 @@ class BaProblem:
         device (right_camera_records)."""
         return self._batch_tensors(True, offsets, X3, uvl2, uvr2, intr_l4, intr_r4,
                                    T_lr12, T12, mask_l, mask_r, opt, cap, want_debug)
+
+    # -- batched planar 3-DoF (ba_pose_only_{mono,stereo}3_batch) --
+    def pose_only_mono3_batch(self, offsets, X3, uv2, intr4, T_bc12, T_wl12, T12,
+                              mask, opt, cap=None, want_debug=False):
+        """B monocular planar 3-DoF problems in one launch.  offsets (B+1,
+        int32): problem b owns rows [offsets[b], offsets[b+1]) of X3 (base-1
+        coordinates) / uv2 / mask; intr4 (B, 4) = fx fy cx cy, T_bc12, T_wl12
+        and T12 = world_to_current (B, 12).  Returns one dict per problem, as
+        pose_only_mono6_batch."""
+        off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        B = off.size - 1
+        X = np.ascontiguousarray(X3, np.float32).reshape(-1, 3)
+        uv = np.ascontiguousarray(uv2, np.float32).reshape(-1, 2)
+        K = np.ascontiguousarray(intr4, np.float32).reshape(-1, 4)
+        Tbc = np.ascontiguousarray(T_bc12, np.float32).reshape(-1, 12)
+        Twl = np.ascontiguousarray(T_wl12, np.float32).reshape(-1, 12)
+        T = np.ascontiguousarray(T12, np.float32).reshape(-1, 12).copy()
+        m = np.ascontiguousarray(mask, np.uint8).reshape(-1).copy()
+        cap, rows, res, dbg = self._batch_buffers(
+            "pose_only_mono3_batch", B,
+            off[-1] == X.shape[0] == uv.shape[0] == m.size and
+            K.shape[0] == Tbc.shape[0] == Twl.shape[0] == T.shape[0] == B, opt, cap,
+            want_debug)
+        check(self.lib.ba_pose_only_mono3_batch(
+            self.h, B, _ip(off), _fp(X), _fp(uv), _fp(K), _fp(Tbc), _fp(Twl), _fp(T),
+            _up(m), C.byref(opt), rows.ctypes.data_as(C.POINTER(BaPoIter)), cap, res,
+            _fp(dbg) if want_debug else None), "ba_pose_only_mono3_batch")
+        masks = {"mask": [m[off[b]:off[b + 1]].astype(bool) for b in range(B)]}
+        return self._batch_out(T, masks, rows, list(res)[:B], cap, dbg)
+
+    def pose_only_stereo3_batch(self, offsets, X3, uvl2, uvr2, intr_l4, intr_r4,
+                                T_bc12, T_lr12, T_wl12, T12, mask_l, mask_r, opt,
+                                cap=None, want_debug=False):
+        """B stereo planar 3-DoF problems in one launch; as pose_only_mono3_batch
+        plus uvr2 (a negative coordinate: no right match), intr_r4 (B, 4),
+        T_lr12 (B, 12) and the right masks."""
+        off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        B = off.size - 1
+        X = np.ascontiguousarray(X3, np.float32).reshape(-1, 3)
+        ul = np.ascontiguousarray(uvl2, np.float32).reshape(-1, 2)
+        ur = np.ascontiguousarray(uvr2, np.float32).reshape(-1, 2)
+        Kl = np.ascontiguousarray(intr_l4, np.float32).reshape(-1, 4)
+        Kr = np.ascontiguousarray(intr_r4, np.float32).reshape(-1, 4)
+        Tbc = np.ascontiguousarray(T_bc12, np.float32).reshape(-1, 12)
+        Tlr = np.ascontiguousarray(T_lr12, np.float32).reshape(-1, 12)
+        Twl = np.ascontiguousarray(T_wl12, np.float32).reshape(-1, 12)
+        T = np.ascontiguousarray(T12, np.float32).reshape(-1, 12).copy()
+        ml = np.ascontiguousarray(mask_l, np.uint8).reshape(-1).copy()
+        mr = np.ascontiguousarray(mask_r, np.uint8).reshape(-1).copy()
+        cap, rows, res, dbg = self._batch_buffers(
+            "pose_only_stereo3_batch", B,
+            off[-1] == X.shape[0] == ul.shape[0] == ur.shape[0] == ml.size == mr.size and
+            Kl.shape[0] == Kr.shape[0] == Tbc.shape[0] == Tlr.shape[0] == Twl.shape[0] ==
+            T.shape[0] == B, opt, cap, want_debug)
+        check(self.lib.ba_pose_only_stereo3_batch(
+            self.h, B, _ip(off), _fp(X), _fp(ul), _fp(ur), _fp(Kl), _fp(Kr), _fp(Tbc),
+            _fp(Tlr), _fp(Twl), _fp(T), _up(ml), _up(mr), C.byref(opt),
+            rows.ctypes.data_as(C.POINTER(BaPoIter)), cap, res,
+            _fp(dbg) if want_debug else None), "ba_pose_only_stereo3_batch")
+        masks = {"mask_l": [ml[off[b]:off[b + 1]].astype(bool) for b in range(B)],
+                 "mask_r": [mr[off[b]:off[b + 1]].astype(bool) for b in range(B)]}
+        return self._batch_out(T, masks, rows, list(res)[:B], cap, dbg)
+
+    @staticmethod
+    def planar_records(T_bc12, T_wl12, T12, T_lr12=None, intr_r4=None):
+        """(B, 52) float32 planar records of the batched planar tensor path,
+        one per problem, from ba_planar_record (the host set-up of the single
+        planar calls: the prior's psi comes from the host's atan2, so the
+        records are built here, not on the device).  T_lr12 / intr_r4 (B, 12) /
+        (B, 4): stereo; None for mono (stereo fields zero)."""
+        lib = _lib.load()
+        Tbc = np.ascontiguousarray(T_bc12, np.float32).reshape(-1, 12)
+        Twl = np.ascontiguousarray(T_wl12, np.float32).reshape(-1, 12)
+        T = np.ascontiguousarray(T12, np.float32).reshape(-1, 12)
+        B = T.shape[0]
+        stereo = T_lr12 is not None
+        if stereo != (intr_r4 is not None):
+            raise ValueError("planar_records: give both T_lr12 and intr_r4, or neither")
+        Tlr = np.ascontiguousarray(T_lr12, np.float32).reshape(-1, 12) if stereo else None
+        Kr = np.ascontiguousarray(intr_r4, np.float32).reshape(-1, 4) if stereo else None
+        if not (Tbc.shape[0] == Twl.shape[0] == B and
+                (not stereo or Tlr.shape[0] == Kr.shape[0] == B)):
+            raise ValueError("planar_records: arrays must all hold B rows")
+        out = np.zeros((B, 52), np.float32)
+        for b in range(B):
+            check(lib.ba_planar_record(
+                _fp(Tbc[b]), _fp(Twl[b]), _fp(T[b]), _fp(Tlr[b]) if stereo else None,
+                _fp(Kr[b]) if stereo else None, _fp(out[b])), "ba_planar_record")
+        return out
+
+    def pose_only_mono3_batch_tensors(self, offsets, X3, uv2, intr4, rec, T12, mask,
+                                      opt, cap=None, want_debug=False):
+        """pose_only_mono3_batch on torch tensors already on this handle's GPU
+        (offsets int32, mask uint8, the rest float32, contiguous), enqueued on
+        torch.cuda.current_stream() without a host sync.  rec (B, 52) holds the
+        planar records (planar_records, moved to the device): the device entry
+        point never reads T12, the prior comes from the record.  Returns new
+        tensors as pose_only_mono6_batch_tensors; T12 keeps its input rows where
+        the single call would not write them."""
+        return self._batch_tensors(False, offsets, X3, uv2, None, intr4, None, None, T12,
+                                   mask, None, opt, cap, want_debug, rec=rec)
+
+    def pose_only_stereo3_batch_tensors(self, offsets, X3, uvl2, uvr2, intr_l4, rec,
+                                        T12, mask_l, mask_r, opt, cap=None,
+                                        want_debug=False):
+        """The stereo counterpart of pose_only_mono3_batch_tensors (records from
+        planar_records with T_lr12 and intr_r4; masks returned as mask_l /
+        mask_r)."""
+        return self._batch_tensors(True, offsets, X3, uvl2, uvr2, intr_l4, None, None, T12,
+                                   mask_l, mask_r, opt, cap, want_debug, rec=rec)
 
     def pose_only_mono3(self, X3, uv2, fx, fy, cx, cy, T_bc12, T_wl12, T12,
                         mask, opt, cap=None, want_debug=False):
@@ -1528,21 +1665,32 @@ class PoseOnlyBundleAdjustmentSolver:
         m[:k] = np.asarray(mask[:k], np.uint8)
         return m
 
-    def _solve_6dof_batch(self, frames, options, stereo):
+    def _solve_batch(self, frames, options, stereo, planar=False):
+        """The batch mirror methods: 6-DoF, or planar 3-DoF (the frames then
+        carry the planar methods' parameter names)."""
         t0 = time.perf_counter()
         f32 = lambda a, k: np.asarray(a, np.float32).reshape(-1, k)
         to12 = lambda T: _T44_to_12(np.asarray(T, np.float64)).astype(np.float32)
+        xkey = "world_position_list" if planar else "reference_position_list"
         prep = []
         for fr in frames:        # every size check before any device use
-            X = f32(fr["reference_position_list"], 3)
+            X = f32(fr[xkey], 3)
             if stereo:
                 uvs = [f32(fr["matched_left_pixel_list"], 2),
                        f32(fr["matched_right_pixel_list"], 2)]
-                tag = "SolveStereoPoseOnlyBundleAdjustment6Dof"
             else:
                 uvs = [f32(fr["matched_pixel_list"], 2)]
-                tag = "SolveMonocularPoseOnlyBundleAdjustment6Dof"
-            if any(u.shape[0] != X.shape[0] for u in uvs):
+            if planar:           # the single planar methods' messages
+                for side, u in zip(("left_", "right_") if stereo else ("",), uvs):
+                    if u.shape[0] != X.shape[0]:
+                        raise RuntimeError(
+                            "In PoseOnlyBundleAdjustmentSolver::"
+                            "SolveMonocularPoseOnlyBundleAdjustment3Dof(), "
+                            "world_position_list.size() != %scurrent_pixel_list.size()"
+                            % side)
+            elif any(u.shape[0] != X.shape[0] for u in uvs):
+                tag = ("SolveStereoPoseOnlyBundleAdjustment6Dof" if stereo else
+                       "SolveMonocularPoseOnlyBundleAdjustment6Dof")
                 raise RuntimeError(
                     "In PoseOnlyBundleAdjustmentSolver::%s(), "
                     "world_position_list.size() != current_pixel_list.size()" % tag)
@@ -1550,7 +1698,10 @@ class PoseOnlyBundleAdjustmentSolver:
         self.debug_poses_ = []
         mkeys = (("mask_inlier_left", "mask_l"), ("mask_inlier_right", "mask_r")) \
             if stereo else (("mask_inlier", "mask"),)
-        pkey = "reference_to_current_left_pose" if stereo else "reference_to_current_pose"
+        if planar:
+            pkey = "world_to_current_pose" if stereo else "pose_world_to_current"
+        else:
+            pkey = "reference_to_current_left_pose" if stereo else "reference_to_current_pose"
         live = []
         for k, (fr, (X, uvs)) in enumerate(zip(frames, prep)):
             self._begin_summary(options, fr.get("summary"))
@@ -1567,6 +1718,7 @@ class PoseOnlyBundleAdjustmentSolver:
         cat = lambda j: np.concatenate([prep[k][1][j] for k in live])
         X = np.concatenate([prep[k][0] for k in live])
         T = np.stack([to12(frames[k][pkey]) for k in live])
+        poses = lambda key: np.stack([to12(frames[k][key]) for k in live])
         masks = [np.concatenate([self._fit_mask(frames[k][mk], prep[k][0].shape[0])
                                  for k in live]) for mk, _ in mkeys]
         if stereo:
@@ -1574,14 +1726,24 @@ class PoseOnlyBundleAdjustmentSolver:
                    frames[k]["cy_left"]] for k in live]
             ir = [[frames[k]["fx_right"], frames[k]["fy_right"], frames[k]["cx_right"],
                    frames[k]["cy_right"]] for k in live]
-            Tlr = np.stack([to12(frames[k]["left_to_right_pose"]) for k in live])
-            res = self._p.pose_only_stereo6_batch(off, X, cat(0), cat(1), il, ir, Tlr, T,
-                                                  masks[0], masks[1], options.to_c())
+            Tlr = poses("left_to_right_pose")
+            if planar:
+                res = self._p.pose_only_stereo3_batch(
+                    off, X, cat(0), cat(1), il, ir, poses("base_to_camera_pose"), Tlr,
+                    poses("world_to_last_pose"), T, masks[0], masks[1], options.to_c())
+            else:
+                res = self._p.pose_only_stereo6_batch(off, X, cat(0), cat(1), il, ir, Tlr, T,
+                                                      masks[0], masks[1], options.to_c())
         else:
             intr = [[frames[k]["fx"], frames[k]["fy"], frames[k]["cx"], frames[k]["cy"]]
                     for k in live]
-            res = self._p.pose_only_mono6_batch(off, X, cat(0), intr, T, masks[0],
-                                                options.to_c())
+            if planar:
+                res = self._p.pose_only_mono3_batch(
+                    off, X, cat(0), intr, poses("pose_base_to_camera"),
+                    poses("pose_world_to_last"), T, masks[0], options.to_c())
+            else:
+                res = self._p.pose_only_mono6_batch(off, X, cat(0), intr, T, masks[0],
+                                                    options.to_c())
         for k, r in zip(live, res):
             fr = frames[k]
             r["debug"] = []
@@ -1607,7 +1769,7 @@ class PoseOnlyBundleAdjustmentSolver:
         the bits the single call would give it (frames of <= 2048 points).
         Returns the per-frame success flags.  A frame without points is left
         as is (mask emptied, success).  GetDebugPoses() is empty afterwards."""
-        return self._solve_6dof_batch(frames, options, False)
+        return self._solve_batch(frames, options, False)
 
     def Solve_Stereo_6Dof_Batch(self, frames, options):
         """Many Solve_Stereo_6Dof problems in one GPU launch
@@ -1616,7 +1778,32 @@ class PoseOnlyBundleAdjustmentSolver:
         matched_right_pixel_list, fx_left .. cy_right, left_to_right_pose,
         reference_to_current_left_pose, mask_inlier_left, mask_inlier_right,
         and optionally summary).  As Solve_Monocular_6Dof_Batch."""
-        return self._solve_6dof_batch(frames, options, True)
+        return self._solve_batch(frames, options, True)
+
+    def Solve_Monocular_Planar3Dof_Batch(self, frames, options):
+        """Many Solve_Monocular_Planar3Dof problems in one GPU launch
+        (ba_pose_only_mono3_batch).  `frames` is a list of dicts keyed by
+        Solve_Monocular_Planar3Dof's parameter names (world_position_list,
+        matched_pixel_list, fx, fy, cx, cy, pose_base_to_camera,
+        pose_world_to_last, pose_world_to_current, mask_inlier, and optionally
+        summary); poses, masks and summaries are updated in place as that
+        method updates them, and every frame gets the bits the single call
+        would give it (frames of <= 2048 points).  Returns the per-frame
+        success flags.  Every size check comes before any device use.  A frame
+        without points is left as is (mask emptied, success), where the single
+        planar call rejects n = 0 instead.  GetDebugPoses() is empty
+        afterwards."""
+        return self._solve_batch(frames, options, False, planar=True)
+
+    def Solve_Stereo_Planar3Dof_Batch(self, frames, options):
+        """Many Solve_Stereo_Planar3Dof problems in one GPU launch
+        (ba_pose_only_stereo3_batch); frames are dicts keyed by that method's
+        parameter names (world_position_list, matched_left_pixel_list,
+        matched_right_pixel_list, fx_left .. cy_right, base_to_camera_pose,
+        left_to_right_pose, world_to_last_pose, world_to_current_pose,
+        mask_inlier_left, mask_inlier_right, and optionally summary).  As
+        Solve_Monocular_Planar3Dof_Batch."""
+        return self._solve_batch(frames, options, True, planar=True)
 
     def Solve_Monocular_Planar3Dof(self, world_position_list,
                                    matched_pixel_list, fx, fy, cx, cy,

@@ -406,6 +406,29 @@ bool PoseOnlyBundleAdjustmentSolver::Solve_Stereo_Planar3Dof(
   return is_success;
 }
 
+// filled as the single calls fill it
+template <class Row, class Result>
+void PoseOnlyBundleAdjustmentSolver::FillBatchSummary(const Options &options, Summary &summary, const Row *rows,
+                                                      int cap, const Result &r, double ms) {
+  summary.max_iteration_ = options.iteration_handle.max_num_iterations;
+  summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change;
+  summary.threshold_step_size_ = options.convergence_handle.threshold_step_size;
+  for (int k = 0; k < r.n_rows && k < cap; ++k) {  // no row on the converging iteration
+    OptimizationInfo info;
+    info.cost = rows[k].cost;
+    info.cost_change = rows[k].cost_change;
+    info.average_reprojection_error = rows[k].cost;
+    info.abs_step = rows[k].abs_step;
+    info.abs_gradient = 0;
+    info.damping_term = -1;
+    info.iter_time = 0.0;
+    info.iteration_status = IterationStatus::UPDATE;
+    summary.optimization_info_list_.push_back(info);
+  }
+  summary.convergence_status_ = r.converged != 0;
+  summary.total_time_in_millisecond_ = ms;
+}
+
 bool PoseOnlyBundleAdjustmentSolver::Solve_Monocular_6Dof_Batch(std::vector<MonocularFrame6Dof> &frames,
                                                                 Options options) {
   timer::StopWatch stopwatch("SolveMonocularPoseOnlyBundleAdjustment6DofBatch");
@@ -455,27 +478,6 @@ bool PoseOnlyBundleAdjustmentSolver::Solve_Monocular_6Dof_Batch(std::vector<Mono
   if (ba_pose_only_mono6_batch(handle_, B, off.data(), X.data(), uv.data(), intr.data(), T12.data(), mask.data(),
                                &o, rows.data(), cap, res.data(), nullptr) < 0)
     throw std::runtime_error(ba_last_error());
-  // the frame's Summary, filled as the single 6-DoF calls fill it
-  auto fill_summary = [&options](Summary &summary, const ba_po_iter *rows, int cap, const ba_po_result &r,
-                                 double ms) {
-    summary.max_iteration_ = options.iteration_handle.max_num_iterations;
-    summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change;
-    summary.threshold_step_size_ = options.convergence_handle.threshold_step_size;
-    for (int k = 0; k < r.n_rows && k < cap; ++k) {  // no row on the converging iteration
-      OptimizationInfo info;
-      info.cost = rows[k].cost;
-      info.cost_change = rows[k].cost_change;
-      info.average_reprojection_error = rows[k].cost;
-      info.abs_step = rows[k].abs_step;
-      info.abs_gradient = 0;
-      info.damping_term = -1;
-      info.iter_time = 0.0;
-      info.iteration_status = IterationStatus::UPDATE;
-      summary.optimization_info_list_.push_back(info);
-    }
-    summary.convergence_status_ = r.converged != 0;
-    summary.total_time_in_millisecond_ = ms;
-  };
   const double ms = stopwatch.GetLapTimeFromStart();
   bool all = true;
   for (int i = 0; i < B; ++i) {
@@ -486,7 +488,7 @@ bool PoseOnlyBundleAdjustmentSolver::Solve_Monocular_6Dof_Batch(std::vector<Mono
       f.reference_to_current_pose = Unpack12(&T12[12 * (size_t)i]);
     else
       std::cout << "!! WARNING !! poseonly BA yields NAN value!!\n";
-    fill_summary(f.summary, &rows[(size_t)i * cap], cap, res[i], ms);
+    FillBatchSummary(options, f.summary, &rows[(size_t)i * cap], cap, res[i], ms);
     all = all && f.success;
   }
   return all;
@@ -557,27 +559,6 @@ bool PoseOnlyBundleAdjustmentSolver::Solve_Stereo_6Dof_Batch(std::vector<StereoF
                                  Tlr.data(), T12.data(), ml.data(), mr.data(), &o, rows.data(), cap, res.data(),
                                  nullptr) < 0)
     throw std::runtime_error(ba_last_error());
-  // the frame's Summary, filled as the single 6-DoF calls fill it
-  auto fill_summary = [&options](Summary &summary, const ba_po_iter *rows, int cap, const ba_po_result &r,
-                                 double ms) {
-    summary.max_iteration_ = options.iteration_handle.max_num_iterations;
-    summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change;
-    summary.threshold_step_size_ = options.convergence_handle.threshold_step_size;
-    for (int k = 0; k < r.n_rows && k < cap; ++k) {  // no row on the converging iteration
-      OptimizationInfo info;
-      info.cost = rows[k].cost;
-      info.cost_change = rows[k].cost_change;
-      info.average_reprojection_error = rows[k].cost;
-      info.abs_step = rows[k].abs_step;
-      info.abs_gradient = 0;
-      info.damping_term = -1;
-      info.iter_time = 0.0;
-      info.iteration_status = IterationStatus::UPDATE;
-      summary.optimization_info_list_.push_back(info);
-    }
-    summary.convergence_status_ = r.converged != 0;
-    summary.total_time_in_millisecond_ = ms;
-  };
   const double ms = stopwatch.GetLapTimeFromStart();
   bool all = true;
   for (int i = 0; i < B; ++i) {
@@ -591,7 +572,162 @@ bool PoseOnlyBundleAdjustmentSolver::Solve_Stereo_6Dof_Batch(std::vector<StereoF
       f.reference_to_current_left_pose = Unpack12(&T12[12 * (size_t)i]);
     else
       std::cout << "!! WARNING !! poseonly BA yields NAN value!!\n";
-    fill_summary(f.summary, &rows[(size_t)i * cap], cap, res[i], ms);
+    FillBatchSummary(options, f.summary, &rows[(size_t)i * cap], cap, res[i], ms);
+    all = all && f.success;
+  }
+  return all;
+}
+
+bool PoseOnlyBundleAdjustmentSolver::Solve_Monocular_Planar3Dof_Batch(
+    std::vector<MonocularFramePlanar3Dof> &frames, Options options) {
+  timer::StopWatch stopwatch("SolveMonocularPoseOnlyBundleAdjustment3DofBatch");
+  stopwatch.Start();
+  debug_poses_.resize(0);
+  for (const auto &f : frames)  // every size check before any device use (:426-432)
+    if (f.world_position_list.size() != f.matched_pixel_list.size())
+      throw std::runtime_error(
+          "In PoseOnlyBundleAdjustmentSolver::SolveMonocularPoseOnlyBundleAdjustment3Dof(), "
+          "world_position_list.size() != current_pixel_list.size()");
+  std::vector<int32_t> off(1, 0);
+  std::vector<int> live;
+  for (size_t b = 0; b < frames.size(); ++b) {
+    auto &f = frames[b];
+    const int n = static_cast<int>(f.world_position_list.size());
+    f.mask_inlier.resize(n, true);
+    f.summary = Summary();
+    f.success = true;
+    if (n == 0) {
+      f.summary.convergence_status_ = true;
+      continue;
+    }
+    live.push_back(static_cast<int>(b));
+    off.push_back(off.back() + n);
+  }
+  if (live.empty()) return true;
+  if (!handle_ && ba_create(&handle_, 0) < 0) throw std::runtime_error(ba_last_error());
+  const int B = static_cast<int>(live.size()), N = off.back();
+  std::vector<float> X(3 * (size_t)N), uv(2 * (size_t)N), intr(4 * (size_t)B);
+  std::vector<float> Tbc(12 * (size_t)B), Twl(12 * (size_t)B), T12(12 * (size_t)B);
+  std::vector<uint8_t> mask(N);
+  for (int i = 0; i < B; ++i) {
+    const auto &f = frames[live[i]];
+    for (int k = 0, p = off[i]; p < off[i + 1]; ++k, ++p) {
+      for (int r = 0; r < 3; ++r) X[3 * (size_t)p + r] = f.world_position_list[k](r);
+      uv[2 * (size_t)p] = f.matched_pixel_list[k](0);
+      uv[2 * (size_t)p + 1] = f.matched_pixel_list[k](1);
+      mask[p] = f.mask_inlier[k] ? 1 : 0;
+    }
+    const float K[4] = {f.fx, f.fy, f.cx, f.cy};
+    for (int q = 0; q < 4; ++q) intr[4 * (size_t)i + q] = K[q];
+    Pack12(f.pose_base_to_camera, &Tbc[12 * (size_t)i]);
+    Pack12(f.pose_world_to_last, &Twl[12 * (size_t)i]);
+    Pack12(f.pose_world_to_current, &T12[12 * (size_t)i]);
+  }
+  const ba_options o = ToC(options);
+  const int cap = o.max_num_iterations > 0 ? o.max_num_iterations : 1;
+  std::vector<ba_po_iter> rows((size_t)B * cap);
+  std::vector<ba_po_result> res(B);
+  if (ba_pose_only_mono3_batch(handle_, B, off.data(), X.data(), uv.data(), intr.data(), Tbc.data(), Twl.data(),
+                               T12.data(), mask.data(), &o, rows.data(), cap, res.data(), nullptr) < 0)
+    throw std::runtime_error(ba_last_error());
+  const double ms = stopwatch.GetLapTimeFromStart();
+  bool all = true;
+  for (int i = 0; i < B; ++i) {
+    auto &f = frames[live[i]];
+    for (int k = 0, p = off[i]; p < off[i + 1]; ++k, ++p) f.mask_inlier[k] = mask[p] != 0;
+    f.success = res[i].status == 0;
+    if (f.success)
+      f.pose_world_to_current = Unpack12(&T12[12 * (size_t)i]);
+    else
+      std::cout << "!! WARNING !! poseonly BA yields NAN value!!\n";
+    FillBatchSummary(options, f.summary, &rows[(size_t)i * cap], cap, res[i], ms);
+    all = all && f.success;
+  }
+  return all;
+}
+
+bool PoseOnlyBundleAdjustmentSolver::Solve_Stereo_Planar3Dof_Batch(std::vector<StereoFramePlanar3Dof> &frames,
+                                                                   Options options) {
+  timer::StopWatch stopwatch("SolveStereoPoseOnlyBundleAdjustment3DofBatch");
+  stopwatch.Start();
+  debug_poses_.resize(0);
+  for (const auto &f : frames) {  // every size check before any device use (:647-660)
+    if (f.world_position_list.size() != f.matched_left_pixel_list.size())
+      throw std::runtime_error(
+          "In PoseOnlyBundleAdjustmentSolver::SolveMonocularPoseOnlyBundleAdjustment3Dof(), "
+          "world_position_list.size() != left_current_pixel_list.size()");
+    if (f.world_position_list.size() != f.matched_right_pixel_list.size())
+      throw std::runtime_error(
+          "In PoseOnlyBundleAdjustmentSolver::SolveMonocularPoseOnlyBundleAdjustment3Dof(), "
+          "world_position_list.size() != right_current_pixel_list.size()");
+  }
+  std::vector<int32_t> off(1, 0);
+  std::vector<int> live;
+  for (size_t b = 0; b < frames.size(); ++b) {
+    auto &f = frames[b];
+    const int n = static_cast<int>(f.world_position_list.size());
+    f.mask_inlier_left.resize(n, true);
+    f.mask_inlier_right.resize(n, true);
+    f.summary = Summary();
+    f.success = true;
+    if (n == 0) {
+      f.summary.convergence_status_ = true;
+      continue;
+    }
+    live.push_back(static_cast<int>(b));
+    off.push_back(off.back() + n);
+  }
+  if (live.empty()) return true;
+  if (!handle_ && ba_create(&handle_, 0) < 0) throw std::runtime_error(ba_last_error());
+  const int B = static_cast<int>(live.size()), N = off.back();
+  std::vector<float> X(3 * (size_t)N), uvl(2 * (size_t)N), uvr(2 * (size_t)N);
+  std::vector<float> il(4 * (size_t)B), ir(4 * (size_t)B), Tbc(12 * (size_t)B), Tlr(12 * (size_t)B);
+  std::vector<float> Twl(12 * (size_t)B), T12(12 * (size_t)B);
+  std::vector<uint8_t> ml(N), mr(N);
+  for (int i = 0; i < B; ++i) {
+    const auto &f = frames[live[i]];
+    for (int k = 0, p = off[i]; p < off[i + 1]; ++k, ++p) {
+      for (int r = 0; r < 3; ++r) X[3 * (size_t)p + r] = f.world_position_list[k](r);
+      uvl[2 * (size_t)p] = f.matched_left_pixel_list[k](0);
+      uvl[2 * (size_t)p + 1] = f.matched_left_pixel_list[k](1);
+      uvr[2 * (size_t)p] = f.matched_right_pixel_list[k](0);
+      uvr[2 * (size_t)p + 1] = f.matched_right_pixel_list[k](1);
+      ml[p] = f.mask_inlier_left[k] ? 1 : 0;
+      mr[p] = f.mask_inlier_right[k] ? 1 : 0;
+    }
+    const float Kl[4] = {f.fx_left, f.fy_left, f.cx_left, f.cy_left};
+    const float Kr[4] = {f.fx_right, f.fy_right, f.cx_right, f.cy_right};
+    for (int q = 0; q < 4; ++q) {
+      il[4 * (size_t)i + q] = Kl[q];
+      ir[4 * (size_t)i + q] = Kr[q];
+    }
+    Pack12(f.base_to_camera_pose, &Tbc[12 * (size_t)i]);
+    Pack12(f.left_to_right_pose, &Tlr[12 * (size_t)i]);
+    Pack12(f.world_to_last_pose, &Twl[12 * (size_t)i]);
+    Pack12(f.world_to_current_pose, &T12[12 * (size_t)i]);
+  }
+  const ba_options o = ToC(options);
+  const int cap = o.max_num_iterations > 0 ? o.max_num_iterations : 1;
+  std::vector<ba_po_iter> rows((size_t)B * cap);
+  std::vector<ba_po_result> res(B);
+  if (ba_pose_only_stereo3_batch(handle_, B, off.data(), X.data(), uvl.data(), uvr.data(), il.data(), ir.data(),
+                                 Tbc.data(), Tlr.data(), Twl.data(), T12.data(), ml.data(), mr.data(), &o,
+                                 rows.data(), cap, res.data(), nullptr) < 0)
+    throw std::runtime_error(ba_last_error());
+  const double ms = stopwatch.GetLapTimeFromStart();
+  bool all = true;
+  for (int i = 0; i < B; ++i) {
+    auto &f = frames[live[i]];
+    for (int k = 0, p = off[i]; p < off[i + 1]; ++k, ++p) {
+      f.mask_inlier_left[k] = ml[p] != 0;
+      f.mask_inlier_right[k] = mr[p] != 0;
+    }
+    f.success = res[i].status == 0;
+    if (f.success)
+      f.world_to_current_pose = Unpack12(&T12[12 * (size_t)i]);
+    else
+      std::cout << "!! WARNING !! poseonly BA yields NAN value!!\n";
+    FillBatchSummary(options, f.summary, &rows[(size_t)i * cap], cap, res[i], ms);
     all = all && f.success;
   }
   return all;

@@ -460,6 +460,67 @@ int ba_pose_only_stereo6_batch_device(ba_handle *h, int B,
 int ba_right_camera_record(const float *intr_r4, const float *T_lr12,
                            float *camr16);
 
+/* ---- batched planar 3-DoF pose-only (fp32): many problems in one launch --- */
+/* B independent Solve_Monocular_Planar3Dof / Solve_Stereo_Planar3Dof problems,
+ * laid out and reported as the 6-DoF batch above (ba_po_result, one ba_options,
+ * no grid barrier, any B): problem b owns points [offsets[b], offsets[b+1]),
+ * intrinsics intr4 + 4b (intr_l4, intr_r4), T_bc12 + 12b, T_wl12 + 12b,
+ * T_lr12 + 12b (stereo) and pose T12 + 12b = world_to_current (in/out), rows
+ * iters + b*cap and debug poses debug_T12 + 12*b*cap (optional, at most cap
+ * each).  A problem of n <= 2048 points gives bit for bit what
+ * ba_pose_only_{mono,stereo}3 gives it; larger ones agree to fp32 rounding.
+ * T12 is written only where the single call writes it (at least one iteration
+ * and no NaN); max_num_iterations <= 0: every pose unchanged, converged, no
+ * rows.  Host arrays: B >= 1, offsets[0] == 0, strictly increasing offsets,
+ * cap >= 0 and a handle are checked first (else -1, nothing runs); then the
+ * records are built on the host, one H2D copy, one launch, one D2H copy and a
+ * sync on the handle's stream. */
+int ba_pose_only_mono3_batch(ba_handle *h, int B, const int32_t *offsets,
+                             const float *X3, const float *uv2,
+                             const float *intr4, const float *T_bc12,
+                             const float *T_wl12, float *T12, uint8_t *mask,
+                             const ba_options *opt, ba_po_iter *iters, int cap,
+                             ba_po_result *res, float *debug_T12);
+int ba_pose_only_stereo3_batch(ba_handle *h, int B, const int32_t *offsets,
+                               const float *X3, const float *uvl2,
+                               const float *uvr2, const float *intr_l4,
+                               const float *intr_r4, const float *T_bc12,
+                               const float *T_lr12, const float *T_wl12,
+                               float *T12, uint8_t *mask_l, uint8_t *mask_r,
+                               const ba_options *opt, ba_po_iter *iters,
+                               int cap, ba_po_result *res, float *debug_T12);
+/* The same on DEVICE pointers (offsets and res included), enqueued on
+ * hip_stream (NULL = the handle's stream) with no copy and no synchronisation;
+ * only the pointers and B are checked on the host.  They take B prepared
+ * planar records rec52 (B x 52, from ba_planar_record) instead of T_bc12,
+ * T_wl12, T_lr12 and intr_r4, and never READ T12: the prior comes from the
+ * record.  T12 is only written, where the single call would write it. */
+int ba_pose_only_mono3_batch_device(ba_handle *h, int B, const int32_t *offsets,
+                                    const float *X3, const float *uv2,
+                                    const float *intr4, const float *rec52,
+                                    float *T12, uint8_t *mask,
+                                    const ba_options *opt, ba_po_iter *iters,
+                                    int cap, ba_po_result *res,
+                                    float *debug_T12, void *hip_stream);
+int ba_pose_only_stereo3_batch_device(ba_handle *h, int B,
+                                      const int32_t *offsets, const float *X3,
+                                      const float *uvl2, const float *uvr2,
+                                      const float *intr_l4, const float *rec52,
+                                      float *T12, uint8_t *mask_l,
+                                      uint8_t *mask_r, const ba_options *opt,
+                                      ba_po_iter *iters, int cap,
+                                      ba_po_result *res, float *debug_T12,
+                                      void *hip_stream);
+/* Host helper: the per-problem set-up the single planar calls build on the host
+ * (the same function):
+ *   theta0 (3) | R_cb (9) t_cb (3) | R_bc (9) t_bc (3) | R_rl (9) t_rl (3) |
+ *   R_rl*R_cb (9) | right fx fy cx cy (4)  = 52 floats
+ * theta0 = (x, y, psi) of the prior pose_b2b1 = T_bc * (T12^-1 * T_wl) * T_bc^-1,
+ * psi by the host's atan2.  Mono: T_lr12 = intr_r4 = NULL (stereo fields zero);
+ * stereo: both given. */
+int ba_planar_record(const float *T_bc12, const float *T_wl12, const float *T12,
+                     const float *T_lr12, const float *intr_r4, float *rec52);
+
 #ifdef __cplusplus
 }
 #endif
