@@ -100,23 +100,9 @@ int enqueue_iteration(ba_handle *h) {
   if (!direct) ba::launch_scatter(d, s);
   ba::launch_dense_solve(d, h->sched, h->ddev, s);
   mark(h, 3);
-  // (single GPU, every free landmark grouped: back-substitution and trial-point linearisation
-  //  as roles of ONE launch — k_backsub_lin.  OPT-IN, BA_FUSE_BL=1: measured on MI355X the
-  //  interleaved roles do not fill each other's idle pipes — both kernels run two waves per
-  //  SIMD and are bound by the latency those two waves cannot hide, mixing them adds no wave:
-  //  C4 172.6 us with the roles one after the other (= 68.8 + 104, one launch gap saved: 0.4245
-  //  vs 0.428 ms per iteration), 177 / 189 / 203 / 227 us with a lead of 640 / 320 / 160 / 64
-  //  pieces.  Not under a captured graph: the generation number is a kernel argument)
-  static const bool fuse_env = getenv("BA_FUSE_BL") && getenv("BA_FUSE_BL")[0] == '1';
-  const bool fuse_bl = no_side && fuse_env && !h->use_graph && ba::can_fuse_backsub_lin(d) && h->ddev.bad_pivots;
-  if (fuse_bl)
-    ba::launch_backsub_lin(d, s, true, ++h->bl_gen, h->ddev.bad_pivots);
-  else
-    ba::launch_backsub_update(d, s, no_side);  // trial parameters, model terms, step norms
+  ba::launch_backsub_update(d, s, no_side);  // trial parameters, model terms, step norms
   mark(h, 4);
-  if (fuse_bl) {
-    h->tiles_ready = true;
-  } else if (no_side) {
+  if (no_side) {
     h->tiles_ready = true;
     ba::launch_lin_landmarks(d, 1, s);
   } else if (ov) {
@@ -195,6 +181,51 @@ int download(std::vector<T> &out, const T *dev, size_t n, hipStream_t s) {
   return 0;
 }
 
+// Device set-up of a dense schedule: the work lists of `dd`, its column -> x map col_x
+// (npad entries), the solution in column order xc, the dropped-pivot counter, the order,
+// flags and tickets of the dataflow sweeps and the k_chol_dag / k_chol_look items and
+// counters; reads the dense knobs.  Everything is allocated on the handle (h->upload /
+// h->dalloc, in h->allocs).
+int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::vector<int> &col_x,
+                          ba::DenseDev &dd) {
+  const size_t npad = col_x.size(), ncb = (size_t)std::max(1, sc.ncb);
+  if (h->upload(&dd.row_ptr, sc.row_ptr) || h->upload(&dd.rows, sc.rows) ||
+      h->upload(&dd.item_t, sc.item_t) || h->upload(&dd.item_I, sc.item_I) ||
+      h->upload(&dd.tgt_I, sc.tgt_I) || h->upload(&dd.tgt_J, sc.tgt_J) ||
+      h->upload(&dd.tgt_src_ptr, sc.tgt_src_ptr) || h->upload(&dd.src_t, sc.src_t) ||
+      h->upload(&dd.tgt_desc, sc.tgt_desc) || h->upload(&dd.back_desc, sc.back_desc) ||
+      h->upload(&dd.row_desc, sc.row_desc) || h->upload(&dd.col_x, col_x) ||
+      h->dalloc(&dd.xc, npad) || h->dalloc(&dd.bad_pivots, (size_t)1))
+    return -1;
+  HIP_TRY(hipMemset(dd.xc, 0, npad * sizeof(double)));
+  HIP_TRY(hipMemset(dd.bad_pivots, 0, sizeof(int)));
+  dd.read_env();
+  std::vector<int> order;
+  dd.flow_tail_t0 = ba::dense_flow_order(sc, dd, order);
+  dd.n_flow = (int)order.size();
+  dd.flow_gen = 0;
+  if (h->upload(&dd.flow_order, order) || h->dalloc(&dd.flow_flags, ncb) || h->dalloc(&dd.flow_ticket, (size_t)1) ||
+      h->dalloc(&dd.fwd_flags, ncb) || h->dalloc(&dd.fwd_ticket, (size_t)1))
+    return -1;
+  HIP_TRY(hipMemset(dd.flow_flags, 0, ncb * sizeof(int)));
+  HIP_TRY(hipMemset(dd.flow_ticket, 0, sizeof(int)));
+  HIP_TRY(hipMemset(dd.fwd_flags, 0, ncb * sizeof(int)));
+  HIP_TRY(hipMemset(dd.fwd_ticket, 0, sizeof(int)));
+  std::vector<int> items, pre, need, ntrsm, lneed;
+  if (ba::dense_dag_items(sc, dd, items, pre, need, ntrsm, lneed)) {
+    dd.n_dag_items = (int)items.size() / 2;
+    dd.n_fwd_cnt = (int)need.size();
+    if (h->upload(&dd.dag_items, items) || h->upload(&dd.upd_pre, pre) || h->upload(&dd.col_need, need) ||
+        h->upload(&dd.dag_ntrsm, ntrsm) || h->upload(&dd.look_need, lneed) || h->dalloc(&dd.fwd_cnt, need.size()) ||
+        h->dalloc(&dd.dag_dflags, need.size()) || h->dalloc(&dd.dag_tcnt, need.size()))
+      return -1;
+    HIP_TRY(hipMemset(dd.fwd_cnt, 0, need.size() * sizeof(int)));
+    HIP_TRY(hipMemset(dd.dag_dflags, 0, need.size() * sizeof(int)));
+    HIP_TRY(hipMemset(dd.dag_tcnt, 0, need.size() * sizeof(int)));
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -243,8 +274,6 @@ void ba_destroy(ba_handle *h) {
     (void)hipStreamSynchronize(h->side_stream);
     (void)hipStreamDestroy(h->side_stream);
   }
-  for (int k = 0; k < 3; ++k)
-    if (h->ev_look[k]) (void)hipEventDestroy(h->ev_look[k]);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -538,12 +567,6 @@ int ba_finalize(ba_handle *h) {
       return -1;
     h->kind(2);
     if (h->dalloc(&d.Apart2, (size_t)pl.n_apart2 * 27) || h->dalloc(&d.lin_dump, (size_t)ba::kLinDump)) return -1;
-    h->kind(0);
-    if (h->dalloc(&d.bl_flag, pl.lin_desc.size() + 1) || h->dalloc(&d.pose_flag, (size_t)ba::kPoseGrid)) return -1;
-    HIP_TRY(hipMemset(d.bl_flag, 0, (pl.lin_desc.size() + 1) * sizeof(int)));
-    HIP_TRY(hipMemset(d.pose_flag, 0, (size_t)ba::kPoseGrid * sizeof(int)));
-    h->bl_gen = 0;
-    h->kind(2);
     if (!pl.grp_pat.empty())
       HIP_TRY(hipMemcpy(d.grp_pat, pl.grp_pat.data(), pl.grp_pat.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     if (pl.n_apart2 > 0) HIP_TRY(hipMemset(d.Apart2, 0, (size_t)pl.n_apart2 * 27 * sizeof(double)));
@@ -662,66 +685,9 @@ int ba_finalize(ba_handle *h) {
     }
     const ba::DenseSchedule &sc = h->sched;
     ba::DenseDev &dd = h->ddev;
-    if (h->upload(&d.pose_col, h->pose_col_h) || h->upload(&d.col_x, col_x) ||
-        h->upload(&dd.row_ptr, sc.row_ptr) || h->upload(&dd.rows, sc.rows) ||
-        h->upload(&dd.item_t, sc.item_t) || h->upload(&dd.item_I, sc.item_I) ||
-        h->upload(&dd.tgt_I, sc.tgt_I) || h->upload(&dd.tgt_J, sc.tgt_J) ||
-        h->upload(&dd.tgt_src_ptr, sc.tgt_src_ptr) || h->upload(&dd.src_t, sc.src_t) ||
-        h->upload(&dd.tgt_desc, sc.tgt_desc) || h->upload(&dd.back_desc, sc.back_desc) ||
-        h->upload(&dd.row_desc, sc.row_desc) ||
-        h->dalloc(&dd.xc, (size_t)d.npad) || h->dalloc(&dd.bad_pivots, (size_t)1))
-      return -1;
-    HIP_TRY(hipMemset(dd.bad_pivots, 0, sizeof(int)));
-    if (sc.fused_ok &&
-        (h->upload(&dd.f_desc, sc.f_desc) || h->upload(&dd.f_pend, sc.f_pend) ||
-         h->dalloc(&dd.cbuf, (size_t)std::max(1, sc.n_contrib) * nb * nb)))
-      return -1;
-    dd.col_x = d.col_x;
-    dd.read_env();
-    dd.aux_stream = h->side_stream;
-    if (!h->ev_look[0]) {
-      for (int k = 0; k < 3; ++k) HIP_TRY(hipEventCreateWithFlags(&h->ev_look[k], hipEventDisableTiming));
-    }
-    dd.ev_m = h->ev_look[0];
-    dd.ev_x[0] = h->ev_look[1];
-    dd.ev_x[1] = h->ev_look[2];
-    {
-      std::vector<int> order;
-      dd.flow_tail_t0 = ba::dense_flow_order(sc, dd, order);
-      dd.n_flow = (int)order.size();
-      dd.flow_gen = 0;
-      if (h->upload(&dd.flow_order, order) || h->dalloc(&dd.flow_flags, (size_t)std::max(1, ncb)) ||
-          h->dalloc(&dd.flow_ticket, (size_t)1) || h->dalloc(&dd.fwd_flags, (size_t)std::max(1, ncb)) ||
-          h->dalloc(&dd.fwd_ticket, (size_t)1))
-        return -1;
-      HIP_TRY(hipMemset(dd.flow_flags, 0, (size_t)std::max(1, ncb) * sizeof(int)));
-      HIP_TRY(hipMemset(dd.flow_ticket, 0, sizeof(int)));
-      HIP_TRY(hipMemset(dd.fwd_flags, 0, (size_t)std::max(1, ncb) * sizeof(int)));
-      HIP_TRY(hipMemset(dd.fwd_ticket, 0, sizeof(int)));
-      std::vector<int> items, pre, need;
-      if (ba::dense_fwd_items(sc, dd, items, pre, need)) {
-        dd.n_fwd_items = (int)items.size() / 2;
-        dd.n_fwd_cnt = (int)need.size();
-        if (h->upload(&dd.fwd_items, items) || h->upload(&dd.upd_pre, pre) || h->upload(&dd.col_need, need) ||
-            h->dalloc(&dd.fwd_cnt, need.size()))
-          return -1;
-        HIP_TRY(hipMemset(dd.fwd_cnt, 0, need.size() * sizeof(int)));
-      }
-      std::vector<int> ntrsm, lneed;
-      if (ba::dense_dag_items(sc, dd, items, pre, need, ntrsm, lneed)) {
-        dd.n_dag_items = (int)items.size() / 2;
-        dd.n_fwd_cnt = (int)need.size();
-        if (times) fprintf(stderr, "[finalize] k_chol_dag: %d items\n", dd.n_dag_items);
-        if (h->upload(&dd.dag_items, items) || h->upload(&dd.upd_pre, pre) || h->upload(&dd.col_need, need) ||
-            h->upload(&dd.dag_ntrsm, ntrsm) || h->upload(&dd.look_need, lneed) || h->dalloc(&dd.fwd_cnt, need.size()) ||
-            h->dalloc(&dd.dag_dflags, need.size()) || h->dalloc(&dd.dag_tcnt, need.size()))
-          return -1;
-        HIP_TRY(hipMemset(dd.fwd_cnt, 0, need.size() * sizeof(int)));
-        HIP_TRY(hipMemset(dd.dag_dflags, 0, need.size() * sizeof(int)));
-        HIP_TRY(hipMemset(dd.dag_tcnt, 0, need.size() * sizeof(int)));
-      }
-    }
-    HIP_TRY(hipMemset(dd.xc, 0, (size_t)d.npad * sizeof(double)));
+    if (h->upload(&d.pose_col, h->pose_col_h) || upload_dense_schedule(h, sc, col_x, dd)) return -1;
+    d.col_x = dd.col_x;
+    if (times && dd.dag_items) fprintf(stderr, "[finalize] k_chol_dag: %d items\n", dd.n_dag_items);
     // tiles (re)initialised per iteration: factor pattern + diagonal + rhs row
     std::vector<int> ztI, ztJ;
     for (int p = 0; p < ncb; ++p) {
@@ -1467,8 +1433,8 @@ const char *ba_kernel_name(int id) {
   static const char *names[ba::K_COUNT] = {
       "k_cost", "k_lin_landmarks", "k_lin_poses", "k_pose_finalize", "k_dense_init",
       "k_schur_lds", "k_schur_partial", "k_schur_final", "k_scatter",
-      "k_chol_diag", "k_chol_trsm", "k_chol_update", "k_chol_back", "k_chol_level", "k_chol_diag_trsm", "k_chol_tail", "k_backsub_update",
-      "k_pose_update", "k_scalars", "k_control", "k_damp_invert", "k_schur_grp", "k_lin_grp", "k_backsub_lin"};
+      "k_chol_diag", "k_chol_trsm", "k_chol_update", "k_chol_back", "k_chol_diag_trsm", "k_chol_tail", "k_backsub_update",
+      "k_pose_update", "k_scalars", "k_control", "k_damp_invert", "k_schur_grp", "k_lin_grp"};
   return (id >= 0 && id < ba::K_COUNT) ? names[id] : "";
 }
 
@@ -1593,73 +1559,24 @@ int ba_dense_spd_solve(ba_handle *h, int n, const double *A, const double *b,
       L[(size_t)colmap[c] * ld + colmap[c]] = 1.0;
     }
   }
-  double *dL = nullptr, *dD = nullptr, *dx = nullptr;
+  // everything below is allocated on the handle and freed again on every return, so that
+  // repeated calls do not grow the handle's memory
+  struct Scratch {
+    ba_handle *h;
+    size_t mark;
+    int kind;
+    ~Scratch() {
+      for (size_t k = mark; k < h->allocs.size(); ++k) (void)hipFree(h->allocs[k]);
+      h->allocs.resize(mark);
+      h->alloc_kind = kind;
+    }
+  } scratch{h, h->allocs.size(), h->alloc_kind};
+  h->alloc_kind = 0;  // (resident allocations, also on a streaming handle)
   ba::DenseDev dd;
-  dd.read_env();
-  dd.aux_stream = h->side_stream;
-  if (!h->ev_look[0]) {
-    for (int k = 0; k < 3; ++k) HIP_TRY(hipEventCreateWithFlags(&h->ev_look[k], hipEventDisableTiming));
-  }
-  dd.ev_m = h->ev_look[0];
-  dd.ev_x[0] = h->ev_look[1];
-  dd.ev_x[1] = h->ev_look[2];
-  auto up = [&](int **p, const std::vector<int> &v) -> int {
-    HIP_TRY(hipMalloc((void **)p, std::max<size_t>(1, v.size()) * sizeof(int)));
-    if (!v.empty()) HIP_TRY(hipMemcpy(*p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
-    return 0;
-  };
-  if (up(&dd.row_ptr, sc.row_ptr) || up(&dd.rows, sc.rows) || up(&dd.item_t, sc.item_t) ||
-      up(&dd.item_I, sc.item_I) || up(&dd.tgt_I, sc.tgt_I) || up(&dd.tgt_J, sc.tgt_J) ||
-      up(&dd.tgt_src_ptr, sc.tgt_src_ptr) || up(&dd.src_t, sc.src_t) || up(&dd.col_x, col_x) ||
-      up(&dd.tgt_desc, sc.tgt_desc) || up(&dd.back_desc, sc.back_desc) || up(&dd.row_desc, sc.row_desc))
+  double *dL = nullptr, *dD = nullptr, *dx = nullptr;
+  if (upload_dense_schedule(h, sc, col_x, dd) || h->upload(&dL, L) ||
+      h->dalloc(&dD, (size_t)ncb * ba::dense_ws_per_block(nb)) || h->dalloc(&dx, (size_t)npad))
     return -1;
-  if (sc.fused_ok) {
-    if (up(&dd.f_desc, sc.f_desc) || up(&dd.f_pend, sc.f_pend)) return -1;
-    HIP_TRY(hipMalloc((void **)&dd.cbuf, (size_t)std::max(1, sc.n_contrib) * nb * nb * sizeof(double)));
-  }
-  HIP_TRY(hipMalloc((void **)&dd.xc, (size_t)npad * sizeof(double)));
-  {  // the dataflow backward sweep of the LM path (ordered form for dense patterns)
-    std::vector<int> order;
-    dd.flow_tail_t0 = ba::dense_flow_order(sc, dd, order);
-    dd.n_flow = (int)order.size();
-    dd.flow_gen = 0;
-    if (up(&dd.flow_order, order)) return -1;
-    HIP_TRY(hipMalloc((void **)&dd.flow_flags, (size_t)std::max(1, ncb) * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&dd.flow_ticket, sizeof(int)));
-    HIP_TRY(hipMemset(dd.flow_flags, 0, (size_t)std::max(1, ncb) * sizeof(int)));
-    HIP_TRY(hipMemset(dd.flow_ticket, 0, sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&dd.bad_pivots, sizeof(int)));
-    HIP_TRY(hipMemset(dd.bad_pivots, 0, sizeof(int)));
-    // the dataflow forward sweep (narrow patterns only: see dense_fwd_items)
-    HIP_TRY(hipMalloc((void **)&dd.fwd_flags, (size_t)std::max(1, ncb) * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&dd.fwd_ticket, sizeof(int)));
-    HIP_TRY(hipMemset(dd.fwd_flags, 0, (size_t)std::max(1, ncb) * sizeof(int)));
-    HIP_TRY(hipMemset(dd.fwd_ticket, 0, sizeof(int)));
-    std::vector<int> items, pre, need;
-    if (ba::dense_fwd_items(sc, dd, items, pre, need)) {
-      dd.n_fwd_items = (int)items.size() / 2;
-      dd.n_fwd_cnt = (int)need.size();
-      if (up(&dd.fwd_items, items) || up(&dd.upd_pre, pre) || up(&dd.col_need, need)) return -1;
-      HIP_TRY(hipMalloc((void **)&dd.fwd_cnt, need.size() * sizeof(int)));
-      HIP_TRY(hipMemset(dd.fwd_cnt, 0, need.size() * sizeof(int)));
-    }
-    std::vector<int> ntrsm, lneed;
-    if (ba::dense_dag_items(sc, dd, items, pre, need, ntrsm, lneed)) {
-      dd.n_dag_items = (int)items.size() / 2;
-      dd.n_fwd_cnt = (int)need.size();
-      if (up(&dd.dag_items, items) || up(&dd.upd_pre, pre) || up(&dd.col_need, need) || up(&dd.dag_ntrsm, ntrsm) ||
-          up(&dd.look_need, lneed))
-        return -1;
-      for (int **q : {&dd.fwd_cnt, &dd.dag_dflags, &dd.dag_tcnt}) {
-        HIP_TRY(hipMalloc((void **)q, need.size() * sizeof(int)));
-        HIP_TRY(hipMemset(*q, 0, need.size() * sizeof(int)));
-      }
-    }
-  }
-  HIP_TRY(hipMalloc((void **)&dL, L.size() * sizeof(double)));
-  HIP_TRY(hipMalloc((void **)&dD, (size_t)ncb * ba::dense_ws_per_block(nb) * sizeof(double)));
-  HIP_TRY(hipMalloc((void **)&dx, (size_t)npad * sizeof(double)));
-  HIP_TRY(hipMemcpy(dL, L.data(), L.size() * sizeof(double), hipMemcpyHostToDevice));
   hipEvent_t e0, e1;
   HIP_TRY(hipEventCreate(&e0));
   HIP_TRY(hipEventCreate(&e1));
@@ -1675,16 +1592,6 @@ int ba_dense_spd_solve(ba_handle *h, int n, const double *A, const double *b,
   HIP_TRY(hipMemcpy(&bad_h, dd.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
-  for (void *p : {(void *)dL, (void *)dD, (void *)dx, (void *)dd.xc, (void *)dd.row_ptr,
-                  (void *)dd.rows, (void *)dd.item_t, (void *)dd.item_I, (void *)dd.tgt_I,
-                  (void *)dd.tgt_J, (void *)dd.tgt_src_ptr, (void *)dd.src_t, (void *)dd.col_x,
-                  (void *)dd.tgt_desc, (void *)dd.back_desc, (void *)dd.row_desc, (void *)dd.f_desc,
-                  (void *)dd.f_pend, (void *)dd.cbuf, (void *)dd.flow_order, (void *)dd.flow_flags,
-                  (void *)dd.flow_ticket, (void *)dd.bad_pivots, (void *)dd.fwd_flags,
-                  (void *)dd.fwd_ticket, (void *)dd.fwd_items, (void *)dd.upd_pre, (void *)dd.col_need,
-                  (void *)dd.fwd_cnt, (void *)dd.dag_items, (void *)dd.dag_ntrsm, (void *)dd.dag_dflags,
-                  (void *)dd.dag_tcnt, (void *)dd.look_need})
-    (void)hipFree(p);
   HIP_TRY(hipGetLastError());
   if (bad_h >= ba::kFlowTimeout) return fail("ba_dense_spd_solve: a dataflow hand-off timed out");
   return 0;

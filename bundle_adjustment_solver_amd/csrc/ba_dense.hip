@@ -45,19 +45,6 @@ __global__ __launch_bounds__(256) void k_dense_init(double *L, int ld,
 }
 
 using tile16::readlane_f64;
-// -DBA_TILE16_OLD: the first form of the tile factorisation (developer comparison)
-#ifdef BA_TILE16_OLD
-#define BA_TILE16_POTRF tile16::tile16_potrf_inv
-#elif defined(BA_TILE16_CALL)
-// ONE copy of the routine per kernel instead of one per (unrolled) panel: the second
-// panel of a tile finds its ~8 KB of straight-line code in the instruction cache
-__device__ __attribute__((noinline)) int tile16_potrf_call(double g[4], int lane, double &dinv) {
-  return tile16::tile16_potrf_inv2(g, lane, dinv);
-}
-#define BA_TILE16_POTRF tile16_potrf_call
-#else
-#define BA_TILE16_POTRF tile16::tile16_potrf_inv2
-#endif
 // dropped pivots are counted per handle (ba_get_dropped_pivots); the integer
 // atomic runs only when a factorisation actually meets one
 __device__ __forceinline__ void count_bad_pivots(int *bad, int n, int lane) {
@@ -177,7 +164,7 @@ __global__ __launch_bounds__(256) void k_chol_tail(const double *L, int ld, int 
         g[j] = (r >= c) ? Lb[(16 * p + c) * LS + 16 * p + r] : 0.0;
       }
       double dinv;
-      count_bad_pivots(bad, BA_TILE16_POTRF(g, lane, dinv), lane);
+      count_bad_pivots(bad, tile16::tile16_potrf_inv2(g, lane, dinv), lane);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int c = 4 * j + q;
@@ -256,43 +243,7 @@ void launch_dense_init(double *L, int ld, const int *col_x, const int *zt_I,
 // target-centric update launch; then one backward launch per level.
 // NS = nb32 or nb64 (the kernels of the schedule's tile order).
 #define BA_DENSE_RUN(NS)                                                                    \
-  if (look) {                                                                               \
-    /* LOOKAHEAD (dense patterns, three-kernel path): the targets of level l that lie in a  \
-       column of level l + 1 are updated first; the factorisation + TRSM of level l + 1 then \
-       run on the auxiliary stream BESIDE the bulk of level l's update */                   \
-    const int nlv = sc.nlev - tail_levels;                                                  \
-    hipStream_t X = dd.aux_stream;                                                          \
-    for (int l = 0; l < nlv; ++l) {                                                         \
-      const int tg0 = sc.tgt_ptr[l], ng = sc.tgt_ptr[l + 1] - tg0, nf = sc.tgt_first[l];    \
-      if (l == 0) {                                                                         \
-        const int t0 = sc.lev_ptr[0], nt = sc.lev_ptr[1] - t0;                              \
-        const int it0 = sc.item_ptr[0], ni = sc.item_ptr[1] - it0;                          \
-        BA_LAUNCH(K_CHOL_DIAG, NS::k_chol_diag, dim3(nt), dim3(256), s, L, ld, t0, Ldiag, done, bad); \
-        if (ni > 0)                                                                         \
-          BA_LAUNCH(K_CHOL_TRSM, NS::k_chol_trsm, dim3(ni), dim3(NS::NP * 64), s, L, ld,    \
-                    row_limit, it0, dd.item_t, dd.item_I, Ldiag, done);                     \
-      } else {                                                                              \
-        (void)hipStreamWaitEvent(s, dd.ev_x[l & 1], 0);                                     \
-      }                                                                                     \
-      if (nf > 0)                                                                           \
-        BA_LAUNCH(K_CHOL_UPDATE, NS::k_chol_update, dim3(nf), dim3(256), s, L, ld, tg0,     \
-                  dd.tgt_desc, dd.src_t, done);                                             \
-      if (l + 1 < nlv) {                                                                    \
-        const int t1 = sc.lev_ptr[l + 1], nt1 = sc.lev_ptr[l + 2] - t1;                     \
-        const int it1 = sc.item_ptr[l + 1], ni1 = sc.item_ptr[l + 2] - it1;                 \
-        (void)hipEventRecord(dd.ev_m, s);                                                   \
-        (void)hipStreamWaitEvent(X, dd.ev_m, 0);                                            \
-        BA_LAUNCH(K_CHOL_DIAG, NS::k_chol_diag, dim3(nt1), dim3(256), X, L, ld, t1, Ldiag, done, bad); \
-        if (ni1 > 0)                                                                        \
-          BA_LAUNCH(K_CHOL_TRSM, NS::k_chol_trsm, dim3(ni1), dim3(NS::NP * 64), X, L, ld,   \
-                    row_limit, it1, dd.item_t, dd.item_I, Ldiag, done);                     \
-        (void)hipEventRecord(dd.ev_x[(l + 1) & 1], X);                                      \
-      }                                                                                     \
-      if (ng - nf > 0)                                                                      \
-        BA_LAUNCH(K_CHOL_UPDATE, NS::k_chol_update, dim3(ng - nf), dim3(256), s, L, ld,     \
-                  tg0 + nf, dd.tgt_desc, dd.src_t, done);                                   \
-    }                                                                                       \
-  } else if (look2) {                                                                       \
+  if (look2) {                                                                              \
     /* dense patterns: lookahead inside one launch per level (k_chol_look) */               \
     const int nlv = sc.nlev - tail_levels;                                                  \
     {                                                                                       \
@@ -324,22 +275,9 @@ void launch_dense_init(double *L, int ld, const int *col_x, const int *zt_I,
               dd.dag_ntrsm, Ldiag, dd.tgt_desc, dd.src_t, dd.upd_pre, dd.col_need, done,    \
               bad, dd.fwd_flags, dd.dag_dflags, dd.dag_tcnt, dd.fwd_cnt, dd.fwd_ticket,     \
               gen_now);                                                                     \
-  } else if (fwd_flow) {                                                                    \
-    /* every non-tail level — factorisation + TRSM and updates — in ONE dataflow launch */  \
-    BA_LAUNCH(K_CHOL_DIAG_TRSM, NS::k_chol_fwd_flow, dim3(dd.n_fwd_items), dim3(256), s, L, \
-              ld, npad, (const int2 *)dd.fwd_items, dd.n_fwd_items, dd.row_desc, dd.rows,   \
-              Ldiag, dd.tgt_desc, dd.src_t, dd.upd_pre, dd.col_need, done, bad,             \
-              dd.fwd_flags, dd.fwd_cnt,                                                     \
-              (dd.n_fwd_items <= kFlowResident && !dd.force_ticket) ? nullptr : dd.fwd_ticket, \
-              gen_now);                                                                     \
   } else                                                                                    \
   for (int l = 0; l < sc.nlev - tail_levels; ++l) {                                         \
     const int t0 = sc.lev_ptr[l], nt = sc.lev_ptr[l + 1] - t0;                              \
-    if (fused) {                                                                            \
-      BA_LAUNCH(K_CHOL_LEVEL, NS::k_chol_level, dim3(nt), dim3(256), s, L, ld, npad, t0,    \
-                dd.f_desc, dd.rows, dd.f_pend, dd.cbuf, Ldiag, done, bad);                       \
-      continue;                                                                             \
-    }                                                                                       \
     const int it0 = sc.item_ptr[l], ni = sc.item_ptr[l + 1] - it0;                          \
     if (split) {                                                                            \
       BA_LAUNCH(K_CHOL_DIAG, NS::k_chol_diag, dim3(nt), dim3(256), s, L, ld, t0, Ldiag, done, bad); \
@@ -377,13 +315,13 @@ void launch_dense_init(double *L, int ld, const int *col_x, const int *zt_I,
               npad, dd.flow_order, n_back, back_t_end, dd.back_desc, dd.rows, Ldiag, dd.xc, \
               x, dd.col_x, done, dd.flow_flags,                                             \
               (n_back <= kFlowResident && !dd.force_ticket) ? nullptr : dd.flow_ticket, gen_now, bad, \
-              (fwd_flow || dag || look2) ? dd.fwd_cnt : nullptr, dd.n_fwd_cnt);                               \
+              (dag || look2) ? dd.fwd_cnt : nullptr, dd.n_fwd_cnt);                               \
   } else if (flow_back && n_back > 0) {                                                     \
     BA_LAUNCH(K_CHOL_BACK, NS::k_chol_back_flow<false>, dim3(n_back), dim3(256), s, L, ld, npad, \
               dd.flow_order, n_back, back_t_end, dd.back_desc, dd.rows, Ldiag, dd.xc, x,    \
               dd.col_x, done, dd.flow_flags,                                                \
               (n_back <= kFlowResident && !dd.force_ticket) ? nullptr : dd.flow_ticket, gen_now, bad, \
-              (fwd_flow || dag || look2) ? dd.fwd_cnt : nullptr, dd.n_fwd_cnt);                               \
+              (dag || look2) ? dd.fwd_cnt : nullptr, dd.n_fwd_cnt);                               \
   } else                                                                                    \
   for (int l = sc.nlev - tail_levels - 1; l >= 0; --l) {                                    \
     const int t0 = sc.lev_ptr[l], nt = sc.lev_ptr[l + 1] - t0;                              \
@@ -397,9 +335,9 @@ void launch_dense_init(double *L, int ld, const int *col_x, const int *zt_I,
 constexpr int kFlowResident = 448;
 
 // Levels handed to k_chol_tail (the last ones, together 64 or 96 columns, at least two).
-static int dense_tail_levels(const DenseSchedule &sc, const DenseDev &dd, bool fused, int *cols_out) {
+static int dense_tail_levels(const DenseSchedule &sc, const DenseDev &dd, int *cols_out) {
   int tail_levels = 0, tail_cols = 0;
-  if (dd.want_tail && !fused) {
+  if (dd.want_tail) {
     for (int l = sc.nlev - 1; l >= 0; --l) {
       const int cols = (sc.lev_ptr[l + 1] - sc.lev_ptr[l]) * sc.nb;
       if (tail_cols + cols > kTailCols) break;
@@ -414,58 +352,25 @@ static int dense_tail_levels(const DenseSchedule &sc, const DenseDev &dd, bool f
 // Positions of the backward sweep's dataflow launch, top level first; returns the first
 // position of the tail block (= their number).
 int dense_flow_order(const DenseSchedule &sc, const DenseDev &dd, std::vector<int> &order) {
-  const bool fused = sc.fused_ok && dd.f_desc && dd.want_fused;
-  const int tail_levels = dense_tail_levels(sc, dd, fused, nullptr);
+  const int tail_levels = dense_tail_levels(sc, dd, nullptr);
   order.clear();
   for (int l = sc.nlev - tail_levels - 1; l >= 0; --l)
     for (int t = sc.lev_ptr[l]; t < sc.lev_ptr[l + 1]; ++t) order.push_back(t);
   return sc.lev_ptr[sc.nlev - tail_levels];
 }
 
-bool dense_fwd_items(const DenseSchedule &sc, const DenseDev &dd, std::vector<int> &items,
-                     std::vector<int> &pre, std::vector<int> &need) {
-  const bool fused = sc.fused_ok && dd.f_desc && dd.want_fused;
-  const bool split = dd.want_split || !dd.row_desc || sc.max_rows > 4 * (4 / (sc.nb / 16));
-  const int tail_levels = dense_tail_levels(sc, dd, fused, nullptr);
-  const int nlv = sc.nlev - tail_levels;
-  items.clear();
-  pre.assign(std::max<size_t>(1, sc.tgt_J.size()), 0);
-  need.assign((size_t)sc.ncb + 1, 0);
-  if (fused || split || nlv < 2) return false;
-  auto push = [&](int kind, int id) {
-    items.push_back(kind);
-    items.push_back(id);
-  };
-  // LOOKAHEAD order (as k_chol_dag): the targets of level l in a column of level l + 1 first,
-  // then the tiles of level l + 1, then the rest of level l's targets
-  const bool ahead = (int)sc.tgt_first.size() >= sc.nlev;
-  for (int t = sc.lev_ptr[0]; t < sc.lev_ptr[1]; ++t) push(0, t);
-  for (int l = 0; l < nlv; ++l) {
-    const int tg0 = sc.tgt_ptr[l], tg1 = sc.tgt_ptr[l + 1], nf = ahead ? sc.tgt_first[l] : tg1 - tg0;
-    // (targets of one level on one column do not wait for each other: count after the level)
-    for (int tg = tg0; tg < tg1; ++tg) pre[tg] = need[sc.tgt_J[tg]];
-    for (int tg = tg0; tg < tg0 + nf; ++tg) push(1, tg);
-    if (l + 1 < nlv)
-      for (int t = sc.lev_ptr[l + 1]; t < sc.lev_ptr[l + 2]; ++t) push(0, t);
-    for (int tg = tg0 + nf; tg < tg1; ++tg) push(1, tg);
-    for (int tg = tg0; tg < tg1; ++tg) ++need[sc.tgt_J[tg]];
-  }
-  return true;
-}
-
 bool dense_dag_items(const DenseSchedule &sc, const DenseDev &dd, std::vector<int> &items,
                      std::vector<int> &pre, std::vector<int> &need, std::vector<int> &ntrsm,
                      std::vector<int> &look_need) {
-  const bool fused = sc.fused_ok && dd.f_desc && dd.want_fused;
   const bool split = dd.want_split || !dd.row_desc || sc.max_rows > 4 * (4 / (sc.nb / 16));
-  const int tail_levels = dense_tail_levels(sc, dd, fused, nullptr);
+  const int tail_levels = dense_tail_levels(sc, dd, nullptr);
   const int nlv = sc.nlev - tail_levels;
   items.clear();
   pre.assign(std::max<size_t>(1, sc.tgt_J.size()), 0);
   need.assign((size_t)sc.ncb + 1, 0);
   ntrsm.assign((size_t)sc.ncb + 1, 0);
   look_need.assign((size_t)sc.ncb + 1, 0);
-  if (fused || !split || nlv < 2 || (int)sc.tgt_first.size() < sc.nlev) return false;
+  if (!split || nlv < 2 || (int)sc.tgt_first.size() < sc.nlev) return false;
   for (size_t q = 0; q < sc.item_t.size(); ++q) ++ntrsm[sc.item_t[q]];
   auto push = [&](int kind, int id) {
     items.push_back(kind);
@@ -495,12 +400,7 @@ void dense_factor_solve(double *L, int npad, int ld, double *Ldiag, double *x,
                         const DenseDev &dd, hipStream_t s) {
   int *bad = dd.bad_pivots;
   const int row_limit = npad + 16;  // rows that carry data (rhs = row npad)
-  // The fused one-launch-per-level path is opt-in (BA_DENSE_FUSED=1): on C4 it
-  // measured no faster than the three-kernel path (886 vs 876 us per LM
-  // iteration) because tiles that survive many levels collect long pending
-  // lists, which their single consumer then gathers serially.
   // (the knobs are read when the schedule is uploaded, not once per LM iteration)
-  const bool fused = sc.fused_ok && dd.f_desc && dd.want_fused;
   // BA_DENSE_SPLIT=1: separate diagonal and TRSM launches (the TRSM then spreads
   // over one workgroup per row tile: better for dense patterns with many row
   // tiles per column); default: the tile's workgroup also solves its row tiles
@@ -514,7 +414,7 @@ void dense_factor_solve(double *L, int npad, int ld, double *Ldiag, double *x,
   // the last levels (at least two, together at most kTailCols columns) are
   // handed to k_chol_tail: one launch instead of three per level (BA_DENSE_TAIL=0: off)
   int tail_cols = 0;
-  const int tail_levels = dense_tail_levels(sc, dd, fused, &tail_cols);
+  const int tail_levels = dense_tail_levels(sc, dd, &tail_cols);
   const int tail_c0 = tail_levels > 0 ? sc.lev_ptr[sc.nlev - tail_levels] * sc.nb : 0;
   // two (independent) tiles in the first level of the block: their panels go side by side
   const bool tail_pair = tail_levels > 0 && sc.nb == 32 &&
@@ -525,7 +425,7 @@ void dense_factor_solve(double *L, int npad, int ld, double *Ldiag, double *x,
   const int back_t_end = sc.lev_ptr[sc.nlev - tail_levels];
   const int n_back = back_t_end;
   const bool flow = dd.want_flow && dd.flow_ok && dd.flow_order && dd.n_flow == n_back &&
-                    dd.flow_tail_t0 == back_t_end && !fused;
+                    dd.flow_tail_t0 == back_t_end;
   const int gen_now = ++dd.flow_gen;  // generation number of this solve (flags are never reset)
   // Two forms of the dataflow BACKWARD sweep.  Narrow patterns: wait for all row tiles,
   // then gather (their factor tiles prefetched).  Many row tiles per column (dense
@@ -533,18 +433,9 @@ void dense_factor_solve(double *L, int npad, int ld, double *Ldiag, double *x,
   // hand-off (5.0 ms against 3.5 ms for one launch per level); the ORDERED form consumes
   // the row tiles one by one as their flags come up.
   const bool flow_back = flow && sc.max_rows <= 12;
-  // lookahead over the levels of the three-kernel path (see BA_DENSE_RUN): needs the
-  // auxiliary stream and its events; not under per-kernel timing (serial order) or capture
-  const bool look = split && !fused && dd.want_look && dd.flow_ok && dd.aux_stream && dd.ev_m &&
-                    !(g_ktimer && g_ktimer->on) && sc.nlev - tail_levels >= 3 &&
-                    (int)sc.tgt_first.size() >= sc.nlev;
-  // the forward sweep of all non-tail levels as one dataflow launch (opt-in, BA_DENSE_FWD_FLOW=1:
-  // see DenseDev::want_fwd_flow); its counters are zeroed again by the backward launch
-  const bool fwd_flow = flow && !split && !look && dd.want_fwd_flow && dd.fwd_flags && dd.fwd_items &&
-                        dd.n_fwd_items > 0 && dd.fwd_cnt && n_back > 0;
   // the three-kernel path (dense patterns) as one dataflow launch with lookahead (BA_DENSE_DAG=0:
   // three launches per level)
-  const bool dag = flow && split && !look && dd.want_dag && dd.dag_items && dd.n_dag_items > 0 &&
+  const bool dag = flow && split && dd.want_dag && dd.dag_items && dd.n_dag_items > 0 &&
                    (dd.n_dag_items <= DenseDev::kDagMaxItems || dd.force_dag) && !dd.force_look2 &&
                    dd.fwd_flags && dd.fwd_cnt && dd.dag_dflags && dd.dag_tcnt && n_back > 0;
   // ... and beyond that item count: lookahead inside one launch per level (BA_DENSE_LOOK2=0: off)
@@ -554,7 +445,7 @@ void dense_factor_solve(double *L, int npad, int ld, double *Ldiag, double *x,
   for (int l = 0; l + 1 < sc.nlev - tail_levels && look2_fits; ++l)
     look2_fits = (int)sc.tgt_first.size() > l &&
                  sc.tgt_first[l] + (sc.lev_ptr[l + 2] - sc.lev_ptr[l + 1]) + (sc.item_ptr[l + 2] - sc.item_ptr[l + 1]) <= kFlowResident;
-  const bool look2 = flow && split && !look && !dag && dd.want_look2 && look2_fits && dd.dag_dflags && dd.look_need &&
+  const bool look2 = flow && split && !dag && dd.want_look2 && look2_fits && dd.dag_dflags && dd.look_need &&
                      dd.fwd_cnt &&
                      sc.nlev - tail_levels >= 3 &&
                      (int)sc.tgt_first.size() >= sc.nlev;

@@ -26,13 +26,10 @@
 
 namespace ba {
 
-constexpr int kMaxContrib = 32768;    // contribution tiles (8 KiB each at order 32)
 // Tile order nb = 32 (5 poses + 2 padding columns) or 64 (10 poses + 4): chosen
 // per problem by ba_finalize from the two level schedules.
 inline int dense_poses_per_tile(int nb) { return nb == 32 ? 5 : 10; }
 inline int dense_ws_per_block(int nb) { return nb * nb + (nb / 16) * 256; }
-// row tiles a fused-level workgroup can keep in LDS (ba_dense_tile.inc: FR)
-inline int dense_max_fused_rows(int nb) { return nb == 32 ? 12 : 3; }
 
 struct DenseSchedule {
   int nb = 32;    // tile order the schedule was built for
@@ -55,21 +52,6 @@ struct DenseSchedule {
   //   row_desc[16 p ..] = { nrow (incl. the rhs block), row_begin, 0.., first eight row tiles at [8..15] }
   std::vector<int> row_desc;
   int max_rows = 0;  // most row tiles (incl. the rhs block) below any tile
-  // FUSED level schedule (one launch per level, see k_chol_level): every source
-  // tile writes its outer products P_a P_c^T as separate CONTRIBUTION tiles
-  // instead of updating the targets in place; a tile subtracts its pending
-  // contributions when it is consumed (as a diagonal tile or as a row tile of
-  // the column being eliminated).  Used when every tile has at most
-  // dense_max_fused_rows(nb) row tiles (incl. the rhs block) and the number of
-  // contribution tiles stays below kMaxContrib (banded / block-sparse systems);
-  // dense patterns keep the in-place three-kernel path.
-  //   f_desc[16 p ..] = { nrow, row_begin, pend_begin, pend_n, out_base, npairs, 0, 0,
-  //                       first eight row tiles (-1 pad) }
-  //   f_pend[2 k ..]  = { row slot a (-1: the diagonal tile), contribution id }:
-  //                     the pending contributions of position p's tiles
-  bool fused_ok = false;
-  int n_contrib = 0;
-  std::vector<int> f_desc, f_pend;
   double fill = 1.0;        // non-zero factor tiles / all lower tiles
   double flops = 0.0;       // executed flops of factor + solves (estimate)
 };

@@ -3,7 +3,6 @@
 // (32 or 64); everything here is generic in NB.
 constexpr int NP = NB / 16;                    // 16-column panels per tile
 constexpr int WS = NB * NB + NP * 256;         // workspace doubles per diagonal tile
-constexpr int FR = NB == 32 ? 12 : 3;          // row tiles a fused-level workgroup keeps in LDS
 static_assert(NB == 32 || NB == 64, "tile order");
 
 // Cholesky of the NB x NB tile held in LDS (Lb[c*LS + r], lower triangle) by
@@ -15,48 +14,6 @@ __device__ __forceinline__ void factor_tile_lds(double *Lb, double (*Eb)[16 * ES
                                                 int *bad) {
   const int lane = tid & 63, wv = tid >> 6;
   const int lr = lane & 15, lk = lane >> 4;
-#ifdef BA_TILE32_ON
-  // (build-time experiment, -DBA_TILE32_ON.)  32-column tiles: the whole tile by ONE wave on
-  // three 16x16 register tiles (tile16::tile32_potrf_inv: eight block steps in a row; no barrier,
-  // no LDS round trip between the two diagonal tiles).  A tile with a minor that is not safely
-  // positive is left untouched and takes the panel path below, which keeps the zeroed-column
-  // semantics.  MEASURED on MI355X: the level kernels are 1.5-2.5 us shorter per iteration under
-  // per-kernel timing (C4 105.6 -> 103.6 us, C2 121.5 -> 120.3), the free-running C4 iteration
-  // is 13 us LONGER in every A/B pair (0.431 -> 0.445 ms; C2 0.263 -> 0.261): off.
-  if (NP == 2) {
-    __shared__ int s_bad32;
-    if (wv == 0) {
-      const int r = lr, q = lk;
-      double g00[4], g10[4], g11[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = 4 * j + q;
-        g00[j] = (r >= c) ? Lb[c * LS + r] : 0.0;
-        g10[j] = Lb[c * LS + 16 + r];
-        g11[j] = (r >= c) ? Lb[(16 + c) * LS + 16 + r] : 0.0;
-      }
-      double dinv0, dinv1;
-      const int bad32 = tile16::tile32_potrf_inv(g00, g10, g11, lane, dinv0, dinv1);
-      if (!bad32) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int c = 4 * j + q;
-          if (r >= c) Lb[c * LS + r] = g00[j];
-          if (r < c) Eb[0][r * ES + c] = g00[j];
-          if (r == c) Eb[0][r * ES + c] = dinv0;
-          Lb[c * LS + 16 + r] = g10[j];
-          if (r >= c) Lb[(16 + c) * LS + 16 + r] = g11[j];
-          if (r < c) Eb[1][r * ES + c] = g11[j];
-          if (r == c) Eb[1][r * ES + c] = dinv1;
-        }
-      }
-      if (lane == 0) s_bad32 = bad32;
-    }
-    __syncthreads();
-    if (!s_bad32) return;
-    __syncthreads();  // (s_bad32 is read by everyone before the next call may write it)
-  }
-#endif
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     // (1) left-looking update of panel p: tile (ti,p) -= sum_kt L(ti,kt) L(p,kt)^T
@@ -88,7 +45,7 @@ __device__ __forceinline__ void factor_tile_lds(double *Lb, double (*Eb)[16 * ES
         g[j] = (r >= c) ? Lb[(16 * p + c) * LS + 16 * p + r] : 0.0;
       }
       double dinv;
-      count_bad_pivots(bad, BA_TILE16_POTRF(g, lane, dinv), lane);
+      count_bad_pivots(bad, tile16::tile16_potrf_inv2(g, lane, dinv), lane);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int c = 4 * j + q;
@@ -208,17 +165,12 @@ constexpr int RGD = 4 / NP;   // row tiles per pass of the four waves
 constexpr int PPRE = 4;       // passes whose operands are prefetched
 // (FLOW: the row tiles this workgroup solves are read by update workgroups of the SAME
 //  launch — k_chol_level_flow —: they leave with sc1 stores, like x in k_chol_back_flow)
-// FLOW: 0 = plain kernel; 1 = k_chol_level_flow (the row tiles leave with sc1 stores);
-// 2 = k_chol_fwd_flow, ALL levels in one launch: the tiles of this column were updated by
-// workgroups of the same launch — wait until the column's counter of finished updates has
-// reached `need`, then read the tiles with sc1 loads.
 template <int FLOW>
 __device__ __forceinline__ void diag_trsm_body(double *L, int ld, int npad, const int p,
                                                const int *__restrict__ row_desc,
                                                const int *__restrict__ rows,
                                                double *ws_all, const int *done,
-                                               int *bad, double *Lb, double (*Eb)[16 * ES],
-                                               const int *cnt = nullptr, int need = 0) {
+                                               int *bad, double *Lb, double (*Eb)[16 * ES]) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int lr = lane & 15, lk = lane >> 4;
   const int k0 = p * NB;
@@ -227,22 +179,12 @@ __device__ __forceinline__ void diag_trsm_body(double *L, int ld, int npad, cons
   const int4 d2 = dq[2], d3 = dq[3];  // first eight row tiles
   const int dn = done ? *done : 0;
   const int nrow = d0.x;
-  if (FLOW == 2 && need > 0 && !dn) {
-    int spins = 0;
-    while (__hip_atomic_load(&cnt[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > (1 << 22)) {  // ~ a second: give up, flag the solve as failed
-        if (bad && tid == 0) atomicAdd(bad, ::ba::kFlowTimeout);
-        break;
-      }
-    }
-  }
   double lv[NB * NB / 256];
 #pragma unroll
   for (int k = 0; k < NB * NB / 256; ++k) {
     const int e = tid + 256 * k;
     const int c = e / NB, r = e % NB;
-    lv[k] = (r >= c) ? ld_tile<(FLOW == 2)>(&L[(size_t)(k0 + c) * ld + k0 + r]) : 0.0;
+    lv[k] = (r >= c) ? L[(size_t)(k0 + c) * ld + k0 + r] : 0.0;
   }
   // this wave's rows of the first PPRE passes
   const int w = wv % NP, grp = wv / NP;
@@ -261,7 +203,7 @@ __device__ __forceinline__ void diag_trsm_body(double *L, int ld, int npad, cons
     for (int pp = 0; pp < NP; ++pp)
 #pragma unroll
       for (int g = 0; g < 4; ++g)
-        A0[ps][pp][g] = r0s[ps] >= 0 ? ld_tile<(FLOW == 2)>(&L[(size_t)(k0 + 16 * pp + lk + 4 * g) * ld + r0s[ps] + lr]) : 0.0;
+        A0[ps][pp][g] = r0s[ps] >= 0 ? L[(size_t)(k0 + 16 * pp + lk + 4 * g) * ld + r0s[ps] + lr] : 0.0;
   }
   if (dn) return;
 #pragma unroll
@@ -303,7 +245,7 @@ __device__ __forceinline__ void diag_trsm_body(double *L, int ld, int npad, cons
       for (int pp = 0; pp < NP; ++pp)
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-          Ain[pp][g] = r0 >= 0 ? ld_tile<(FLOW == 2)>(&L[(size_t)(k0 + 16 * pp + lk + 4 * g) * ld + r0 + lr]) : 0.0;
+          Ain[pp][g] = r0 >= 0 ? L[(size_t)(k0 + 16 * pp + lk + 4 * g) * ld + r0 + lr] : 0.0;
     }
     if (r0 < 0) continue;  // wave-uniform
     v4f64 X[NP];
@@ -613,50 +555,6 @@ __global__ __launch_bounds__(256, NB == 32 ? 2 : 1) void k_chol_level_flow(doubl
   }
 }
 
-// ---- the forward sweep of ALL levels (but the tail block) as ONE dataflow launch ----
-// Items in level order: the tiles of level 0, its update targets, the tiles of level 1, ...
-// (items[k] = {0, tile position} or {1, target index}).  A tile waits until the counter of
-// finished updates of its column has reached the number the schedule names (need), an
-// update waits for the flags of its source tiles and for the earlier levels' updates on its
-// target's column (pre); everything handed from workgroup to workgroup travels with sc1
-// stores / loads (see k_chol_back_flow).  Roles from tickets (or the block index when the
-// grid is resident): a workgroup only ever waits for earlier items.  The counters are zero
-// when a solve starts: the backward sweep's launch, which follows, zeroes them again.
-__global__ __launch_bounds__(256, NB == 32 ? 2 : 1) void k_chol_fwd_flow(double *L, int ld, int npad,
-                                                       const int2 *__restrict__ items, int n_items,
-                                                       const int *__restrict__ row_desc,
-                                                       const int *__restrict__ rows, double *ws_all,
-                                                       const int *__restrict__ tgt_desc,
-                                                       const int *__restrict__ src_t,
-                                                       const int *__restrict__ upd_pre,
-                                                       const int *__restrict__ col_need,
-                                                       const int *done, int *bad, int *flags, int *cnt,
-                                                       int *ticket, int gen) {
-  __shared__ double Lb[NB * LS];
-  __shared__ double Eb[NP][16 * ES];
-  __shared__ int s_k;
-  int k = blockIdx.x;
-  if (ticket) {
-    if (threadIdx.x == 0) {
-      const int kt = atomicAdd(ticket, 1);
-      if (kt == n_items - 1) *ticket = 0;
-      s_k = kt;
-    }
-    __syncthreads();
-    k = s_k;
-  }
-  const int2 it = items[k];
-  if (it.x == 0) {
-    diag_trsm_body<2>(L, ld, npad, it.y, row_desc, rows, ws_all, done, bad, Lb, Eb, cnt, col_need[it.y]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0 && !(done && *done))
-      __hip_atomic_store(&flags[it.y], gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    update_body<2>(L, ld, it.y, tgt_desc, src_t, done, flags, gen, bad, cnt, upd_pre[it.y]);
-  }
-}
-
 // ---- the forward sweep of the THREE-KERNEL path (dense patterns: many row tiles per
 // column) as one dataflow launch over all levels, with lookahead ----
 // Items {kind, index}: 0 = diagonal tile (position), 1 = TRSM item, 2 = update target, in
@@ -757,210 +655,6 @@ __global__ __launch_bounds__(256, 3) void k_chol_look(double *L, int ld, int row
   } else {
     update_body<0>(L, ld, tg0 + (k - nt1 - ni1), tgt_desc, src_t, done, nullptr, 0, nullptr);
   }
-}
-
-// ---- fused level: diagonal factorisation + TRSM + outer products ----------
-// One workgroup per SOURCE tile p of the level, one launch per level (instead
-// of diag / TRSM / update launches, each a dependent round trip):
-//   1. A_pp = base tile - its pending contribution tiles;  L_pp, E = chol(A_pp)
-//   2. every row tile I of p:  P_I = (A_Ip - pending) L_pp^-T  -> L (for the
-//      backward sweep) and LDS
-//   3. every pair (a >= c) of row tiles:  contribution tile  P_a P_c^T  -> cbuf
-// Nothing is updated in place, so no workgroup ever waits for another one of
-// the same launch; the sums are formed by the (single) consumer of each tile
-// in ascending contribution id: deterministic.
-constexpr int PS = NB + 1;
-constexpr int MT2 = NB / 16;
-constexpr int RG = 4 / NP;        // row tiles handled at once by the four waves
-constexpr int TE = NB * NB / 256; // tile elements per thread
-constexpr int PCH = 8;            // pending contributions fetched per batch
-__global__ __launch_bounds__(256) void k_chol_level(double *L, int ld, int npad, int t0,
-                                                    const int *__restrict__ f_desc,
-                                                    const int *__restrict__ rows,
-                                                    const int *__restrict__ f_pend,
-                                                    double *cbuf, double *ws_all,
-                                                    const int *done, int *bad) {
-  __shared__ double Lb[NB * LS];
-  __shared__ double Eb[NP][16 * ES];
-  __shared__ double Pb[FR][NB * PS];  // Pb[a][k*PS + row]
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int lr = lane & 15, lk = lane >> 4;
-#ifdef BA_DENSE_DBG
-  int dd_n = 0;
-#endif
-  DD_STAMP()
-  const int p = t0 + blockIdx.x;
-  const int k0 = p * NB;
-  const int4 *dq = (const int4 *)(f_desc + 16 * (size_t)p);
-  const int4 d0 = dq[0];  // nrow, row_begin, pend_begin, pend_n
-  const int4 d1 = dq[1];  // out_base, npairs
-  const int4 d2 = dq[2], d3 = dq[3];  // first eight row tiles
-  const int dn = done ? *done : 0;
-  const int nrow = d0.x;
-  if (dn) return;
-  // ---- 1. every tile of this column, requested at once: base values ----
-  // (dependent-load chain of the whole kernel: record -> bases + pending list
-  //  -> contribution tiles)
-  double lv[TE];
-#pragma unroll
-  for (int k = 0; k < TE; ++k) {
-    const int e = tid + 256 * k;
-    lv[k] = L[(size_t)(k0 + e / NB) * ld + k0 + e % NB];
-  }
-  for (int a0 = 0; a0 < nrow; a0 += 4) {  // four row tiles in flight
-    double rv[4][TE];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int a = a0 + j;
-      const int I = a >= nrow ? -1
-                  : a == 0 ? d2.x : a == 1 ? d2.y : a == 2 ? d2.z : a == 3 ? d2.w
-                  : a == 4 ? d3.x : a == 5 ? d3.y : a == 6 ? d3.z : a == 7 ? d3.w
-                  : rows[d0.y + a];
-#pragma unroll
-      for (int k = 0; k < TE; ++k) {
-        const int e = tid + 256 * k;
-        const int r = I * NB + e % NB;
-        rv[j][k] = (I >= 0 && r < npad + 16) ? L[(size_t)(k0 + e / NB) * ld + r] : 0.0;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int a = a0 + j;
-      if (a < nrow) {
-#pragma unroll
-        for (int k = 0; k < TE; ++k) {
-          const int e = tid + 256 * k;
-          Pb[a][(e / NB) * PS + e % NB] = rv[j][k];
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < TE; ++k) {
-    const int e = tid + 256 * k;
-    Lb[(e / NB) * LS + e % NB] = lv[k];
-  }
-  for (int e = tid; e < NP * 16 * ES; e += 256) (&Eb[0][0])[e] = 0.0;
-  DD_STAMP()
-  // ---- pending contributions, PCH tiles in flight, subtracted in list order ----
-  // (each thread owns the same tile elements for every tile: no barrier needed)
-  for (int q0 = 0; q0 < d0.w; q0 += PCH) {
-    double cv[PCH][TE];
-    int slot[PCH];
-#pragma unroll
-    for (int j = 0; j < PCH; ++j) {
-      const int q = q0 + j < d0.w ? q0 + j : d0.w - 1;
-      const int2 pe = ((const int2 *)f_pend)[d0.z + q];
-      slot[j] = q0 + j < d0.w ? pe.x : -2;
-      const double *C = cbuf + (size_t)pe.y * NB * NB;
-#pragma unroll
-      for (int k = 0; k < TE; ++k) cv[j][k] = C[tid + 256 * k];
-    }
-#pragma unroll
-    for (int j = 0; j < PCH; ++j) {
-      if (slot[j] == -2) continue;
-      double *dst = slot[j] < 0 ? Lb : Pb[slot[j]];
-      const int st = slot[j] < 0 ? LS : PS;
-#pragma unroll
-      for (int k = 0; k < TE; ++k) {
-        const int e = tid + 256 * k;
-        dst[(e / NB) * st + e % NB] -= cv[j][k];
-      }
-    }
-  }
-  __syncthreads();
-  DD_STAMP()
-  // ---- 2. factor the diagonal tile ----
-  factor_tile_lds(Lb, Eb, tid, bad);
-  DD_STAMP()
-  {
-    double *ws = ws_all + (size_t)p * WS;
-    for (int e = tid; e < NB * NB; e += 256) {
-      const int c = e / NB, r = e % NB;
-      ws[e] = (r >= c) ? Lb[c * LS + r] : 0.0;
-    }
-    for (int e = tid; e < NP * 256; e += 256) {
-      const int pp = e >> 8, k = (e >> 4) & 15, c = e & 15;
-      ws[NB * NB + e] = Eb[pp][k * ES + c];
-    }
-  }
-  DD_STAMP()
-  // ---- 3. TRSM of the row tiles, in place in LDS (wave group wv / NP: tile,
-  //         wave wv % NP: 16 of its rows) ----
-  for (int a0 = 0; a0 < nrow; a0 += RG) {
-    const int a = a0 + wv / NP, w = wv % NP;
-    if (a < nrow) {
-      const int I = a == 0 ? d2.x : a == 1 ? d2.y : a == 2 ? d2.z : a == 3 ? d2.w
-                  : a == 4 ? d3.x : a == 5 ? d3.y : a == 6 ? d3.z : a == 7 ? d3.w
-                  : rows[d0.y + a];
-      const int r0 = I * NB + 16 * w;
-      v4f64 A0[NP];
-#pragma unroll
-      for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) A0[pp][g] = Pb[a][(16 * pp + lk + 4 * g) * PS + 16 * w + lr];
-      v4f64 X[NP];
-#pragma unroll
-      for (int pp = 0; pp < NP; ++pp) {
-        v4f64 acc = A0[pp];
-#pragma unroll
-        for (int kq = 0; kq < pp; ++kq)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const double lo = -Lb[(16 * kq + lk + 4 * g) * LS + 16 * pp + lr];
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(lo, X[kq][g], acc, 0, 0, 0);
-          }
-        v4f64 out = (v4f64){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const double eo = Eb[pp][(lk + 4 * g) * ES + lr];
-          out = __builtin_amdgcn_mfma_f64_16x16x4f64(eo, acc[g], out, 0, 0, 0);
-        }
-        X[pp] = out;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          if (r0 < npad + 16) L[(size_t)(k0 + 16 * pp + lk + 4 * g) * ld + r0 + lr] = out[g];
-          Pb[a][(16 * pp + lk + 4 * g) * PS + 16 * w + lr] = out[g];
-        }
-      }
-    }
-  }
-  __syncthreads();
-  DD_STAMP()
-  // ---- 4. contribution tiles, one wave per pair (a >= c), rows[c] a real tile ----
-  for (int k = wv; k < d1.y; k += 4) {
-    int a = 0;
-    while ((a + 1) * (a + 2) / 2 <= k) ++a;
-    const int c = k - a * (a + 1) / 2;
-    v4f64 acc[MT2][MT2];
-#pragma unroll
-    for (int m = 0; m < MT2; ++m)
-#pragma unroll
-      for (int n = 0; n < MT2; ++n) acc[m][n] = (v4f64){0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-    for (int kk = 0; kk < NB / 4; ++kk) {
-      double av[MT2], bv[MT2];
-#pragma unroll
-      for (int m = 0; m < MT2; ++m) {
-        av[m] = Pb[c][(kk * 4 + lk) * PS + 16 * m + lr];
-        bv[m] = Pb[a][(kk * 4 + lk) * PS + 16 * m + lr];
-      }
-#pragma unroll
-      for (int m = 0; m < MT2; ++m)
-#pragma unroll
-        for (int n = 0; n < MT2; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[m], bv[n], acc[m][n], 0, 0, 0);
-    }
-    double *C = cbuf + (size_t)(d1.x + k) * NB * NB;
-#pragma unroll
-    for (int m = 0; m < MT2; ++m)
-#pragma unroll
-      for (int n = 0; n < MT2; ++n)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          C[(16 * m + lk + 4 * g) * NB + 16 * n + lr] = acc[m][n][g];
-  }
-  DD_STAMP()
 }
 
 // ---- backward sweep L^T x = z, one launch per level (reverse order) --------
@@ -1127,7 +821,7 @@ __global__ __launch_bounds__(256) void k_chol_back_flow(const double *L, int ld,
   __shared__ int s_t;
   const int tid = threadIdx.x;
   const int dn = done ? *done : 0;
-  // (the forward sweep's column counters, k_chol_fwd_flow: zero again for the next solve;
+  // (the forward sweep's column counters, k_chol_dag / k_chol_look: zero again for the next solve;
   //  that launch has completed — stream order — and a solve skipped by `done` leaves them zero)
   if (fwd_cnt && blockIdx.x == 0 && !dn)
     for (int e = tid; e < n_cnt; e += 256) fwd_cnt[e] = 0;

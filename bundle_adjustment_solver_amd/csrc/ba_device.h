@@ -117,7 +117,6 @@ struct DevProblem {
   int2 *grp_pat;
   double *Apart2;            // n_apart2 * 27 pose-side partial sums of the group pieces
   double *lin_dump;          // kLinDump doubles: target of k_lin_grp's lanes with nothing to store
-  int *bl_flag, *pose_flag;  // k_backsub_lin: "piece back-substituted" (n_lin_desc) / "poses updated" (kPoseGrid) flags
   int32_t *pose_gpart_ptr, *pose_gpart;  // rows of Apart2 per pose
   int lin_chunk0;            // k_lin_landmarks starts at this chunk (the chunks before are k_lin_grp's)
   int n_lin_cost;            // entries of lin_cost_part: n_bchunk + k_lin_grp pieces
@@ -206,8 +205,8 @@ constexpr int kSlotStride = 42;  // 6x6 block of B Cinv B^T + 6 of B Cinv b
 enum KernelId {
   K_COST = 0, K_LIN_LANDMARKS, K_LIN_POSES, K_POSE_FINALIZE, K_DENSE_INIT,
   K_SCHUR_LDS, K_SCHUR_PARTIAL, K_SCHUR_FINAL, K_SCATTER,
-  K_CHOL_DIAG, K_CHOL_TRSM, K_CHOL_UPDATE, K_CHOL_BACK, K_CHOL_LEVEL, K_CHOL_DIAG_TRSM, K_CHOL_TAIL, K_BACKSUB_UPDATE,
-  K_POSE_UPDATE, K_SCALARS, K_CONTROL, K_DAMP_INVERT, K_SCHUR_GRP, K_LIN_GRP, K_BACKSUB_LIN, K_COUNT
+  K_CHOL_DIAG, K_CHOL_TRSM, K_CHOL_UPDATE, K_CHOL_BACK, K_CHOL_DIAG_TRSM, K_CHOL_TAIL, K_BACKSUB_UPDATE,
+  K_POSE_UPDATE, K_SCALARS, K_CONTROL, K_DAMP_INVERT, K_SCHUR_GRP, K_LIN_GRP, K_COUNT
 };
 struct KernelTimer {
   bool on = false;
@@ -252,8 +251,6 @@ void launch_schur(const DevProblem &d, bool direct, bool with_init, hipStream_t 
 void launch_schur_accumulate(const DevProblem &d, hipStream_t s);
 void launch_schur_final(const DevProblem &d, bool direct, hipStream_t s);
 void launch_backsub_update(const DevProblem &d, hipStream_t s, bool zero_tiles = false);
-bool can_fuse_backsub_lin(const DevProblem &d);
-void launch_backsub_lin(const DevProblem &d, hipStream_t s, bool zero_tiles, int gen, int *bad);
 void launch_scatter(const DevProblem &d, hipStream_t s);
 // cost_src: 0 = the k_cost partials only (stage API), 1 = the k_lin_landmarks
 // partials (+ the k_cost partials of fixed-landmark observations, if any)
@@ -308,9 +305,6 @@ struct DenseDev {
   int *tgt_src_ptr = nullptr, *src_t = nullptr;  // their source panels
   int *tgt_desc = nullptr, *back_desc = nullptr; // 8-int inline records
   int *row_desc = nullptr;                       // 16-int records: row tiles of a position
-  // fused level path (DenseSchedule::fused_ok)
-  int *f_desc = nullptr, *f_pend = nullptr;
-  double *cbuf = nullptr;  // n_contrib contribution tiles (NB x NB, column-major)
   int *col_x = nullptr;   // npad: column -> index into x (6*pose + r) or -1
   double *xc = nullptr;   // npad: solution in column order
   int *bad_pivots = nullptr;  // device counter of non-positive pivots (or null)
@@ -320,21 +314,13 @@ struct DenseDev {
   // forward sweep, one dataflow launch per level (k_chol_level_flow): one flag per tile
   // ("factorised, row tiles solved"), the ticket counter
   int *fwd_flags = nullptr, *fwd_ticket = nullptr;
-  // forward sweep, ALL non-tail levels as one dataflow launch (k_chol_fwd_flow): the items
-  // {kind, index} in level order, per update target the updates of earlier levels on its
-  // column, per position all updates on its column, the columns' counters of finished updates
-  int *fwd_items = nullptr, *upd_pre = nullptr, *col_need = nullptr, *fwd_cnt = nullptr;
-  int n_fwd_items = 0, n_fwd_cnt = 0;
-  // OPT-IN (BA_DENSE_FWD_FLOW=1; default: one dataflow launch per level).  Measured on MI355X:
-  // the launch itself is shorter than the six it replaces (C4 104 vs 107 us, C2 112 vs 122,
-  // C3 80 vs 87 under per-kernel timing) but the free-running LM iteration is SLOWER (C4
-  // 0.438-0.446 vs 0.433 ms, C2 0.269 vs 0.266, C3 0.258 vs 0.2545): back-to-back launches
-  // on one stream cost less than the polling workgroups of the later levels, which hold
-  // their CU slots from the start of the launch
-  bool want_fwd_flow = false;
   // forward sweep of the three-kernel path as one dataflow launch with lookahead (k_chol_dag):
-  // items {kind, index}, TRSM items per position, "tile factorised" flags, per-column
-  // counters of finished TRSM items (shares upd_pre / col_need / fwd_cnt / fwd_flags / fwd_ticket)
+  // per update target the updates of earlier levels on its column, per position all updates
+  // on its column, the columns' counters of finished updates (n_fwd_cnt of them; also
+  // k_chol_look's), items {kind, index}, TRSM items per position, "tile factorised" flags,
+  // per-column counters of finished TRSM items (shares fwd_flags / fwd_ticket)
+  int *upd_pre = nullptr, *col_need = nullptr, *fwd_cnt = nullptr;
+  int n_fwd_cnt = 0;
   int *dag_items = nullptr, *dag_ntrsm = nullptr, *dag_dflags = nullptr, *dag_tcnt = nullptr;
   int *look_need = nullptr;  // k_chol_look: per position, the previous level's targets in its column
   int n_dag_items = 0;
@@ -352,24 +338,14 @@ struct DenseDev {
   bool flow_ok = true;  // false while a hipGraph is captured / replayed (the generation is a kernel argument)
   bool want_flow = true;
   bool force_ticket = false;  // BA_DENSE_TICKET=1: tickets even when the grid is resident (test knob)
-  // lookahead of the three-kernel (dense-pattern) path: an auxiliary stream and its events
-  // (owned by the handle).  OPT-IN (BA_DENSE_LOOKAHEAD=1): measured SLOWER on MI355X / ROCm
-  // 7.2 — two cross-stream event hops per level cost more than the factorisation they
-  // hide (n = 5970: 6.5 vs 5.0 ms; DENSE1K 8.1 vs 6.7 ms; C1 0.42 vs 0.31 ms)
-  hipStream_t aux_stream = nullptr;
-  hipEvent_t ev_m = nullptr, ev_x[2] = {nullptr, nullptr};
-  bool want_look = false;
-  // BA_DENSE_FUSED / BA_DENSE_SPLIT / BA_DENSE_TAIL as found when the schedule was uploaded
-  bool want_fused = false, want_split = false, want_tail = true;
+  // BA_DENSE_SPLIT / BA_DENSE_TAIL as found when the schedule was uploaded
+  bool want_split = false, want_tail = true;
   void read_env() {
-    const char *f = getenv("BA_DENSE_FUSED"), *s = getenv("BA_DENSE_SPLIT"), *t = getenv("BA_DENSE_TAIL");
-    want_fused = f && f[0] == '1';
+    const char *s = getenv("BA_DENSE_SPLIT"), *t = getenv("BA_DENSE_TAIL");
     want_split = s && s[0] == '1';
     want_tail = !(t && t[0] == '0');
     const char *fl = getenv("BA_DENSE_FLOW");
     want_flow = !(fl && fl[0] == '0');
-    const char *ff = getenv("BA_DENSE_FWD_FLOW");
-    want_fwd_flow = ff && ff[0] == '1';
     const char *dg = getenv("BA_DENSE_DAG");
     want_dag = !(dg && dg[0] == '0');
     force_dag = dg && dg[0] == '1';
@@ -378,8 +354,6 @@ struct DenseDev {
     force_look2 = l2 && l2[0] == '1';
     const char *tk = getenv("BA_DENSE_TICKET");
     force_ticket = tk && tk[0] == '1';
-    const char *la = getenv("BA_DENSE_LOOKAHEAD");
-    want_look = la && la[0] == '1';
   }
 };
 struct DenseSchedule;
@@ -391,13 +365,11 @@ void dense_factor_solve(double *L, int npad, int ld, double *Ldiag, double *x,
                         const DenseDev &dd, hipStream_t s);
 // positions of the dataflow backward sweep (top level first); returns the tail block's first position
 int dense_flow_order(const DenseSchedule &sc, const DenseDev &dd, std::vector<int> &order);
-// work list of the one-launch forward sweep (k_chol_fwd_flow): items = {kind, index} pairs in
-// level order (kind 0: tile position, 1: update target), pre[tg] = updates of earlier levels on
-// the target's column, need[p] = all updates on position p's column; false if the path does not apply
-bool dense_fwd_items(const DenseSchedule &sc, const DenseDev &dd, std::vector<int> &items,
-                     std::vector<int> &pre, std::vector<int> &need);
-// the same for the three-kernel path (k_chol_dag): kinds 0 tile / 1 TRSM item / 2 update target in
-// lookahead order, ntrsm[p] = TRSM items of position p
+// work list of the three-kernel path as one dataflow launch (k_chol_dag): items = {kind, index}
+// pairs in lookahead order (kind 0: tile position, 1: TRSM item, 2: update target), pre[tg] =
+// updates of earlier levels on the target's column, need[p] = all updates on position p's column,
+// ntrsm[p] = TRSM items of position p, look_need[p] = the previous level's first targets in
+// p's column (k_chol_look); false if the path does not apply
 bool dense_dag_items(const DenseSchedule &sc, const DenseDev &dd, std::vector<int> &items,
                      std::vector<int> &pre, std::vector<int> &need, std::vector<int> &ntrsm,
                      std::vector<int> &look_need);

@@ -49,7 +49,6 @@ struct ba_handle {
   // pose update beside the back-substitution), joined with events
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t ev_look[3] = {nullptr, nullptr, nullptr};  // lookahead of the dense three-kernel path
   bool overlap = true;
   // the side stream holds work of the last enqueued iteration (pose-side
   // linearisation at the trial point, reset of the factor tiles) that the main
@@ -98,7 +97,6 @@ struct ba_handle {
   bool ev_ok = false;
   double stage_ms[ST_N] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool lm_begun = false;
-  int bl_gen = 0;            // generation number of the k_backsub_lin launches (flags are never reset)
   ba::KernelTimer kt;        // per-kernel event timing (diagnostic mode)
   ba::DenseSchedule sched;   // level schedule of the reduced-system Cholesky
   ba::DenseDev ddev;

@@ -311,109 +311,6 @@ __device__ __forceinline__ int tile16_potrf_inv2(double g[4], int lane, double &
   return 0;
 }
 
-// ---- a 32x32 SPD tile by ONE wave: three 16x16 register tiles ---------------------
-// g00 / g11: diagonal tiles in the folded layout above (lower = A, strict upper = 0 ->
-// L^-T of THAT 16x16 tile); g10: the full off-diagonal tile, lane (r, q) reg j =
-// A[16 + r][4 j + q].  Eight block steps of the short chain in a row: the first four
-// also carry g10 (its Y product is a third MFMA with the same A operand) and update all
-// three tiles (rank-4 MFMAs: the A operand of a product is indexed by the TARGET column,
-// the B operand by the row); the last four are tile16_potrf_inv2's on g11.  Replaces, for
-// 32-column tiles, factor_tile_lds' potrf -> barrier -> TRSM -> barrier -> SYRK -> barrier
-// -> potrf: no barrier, no LDS round trip, one wave.  Returns non-zero (wave-uniform)
-// when a minor is not safely positive: the tiles are then untouched and the caller takes
-// the first path, which keeps the zeroed-column semantics.
-__device__ __forceinline__ int tile32_potrf_inv(double g00[4], double g10[4], double g11[4], int lane,
-                                                double &dinv0, double &dinv1) {
-  const int r = lane & 15, q = lane >> 4;
-  const double in00[4] = {g00[0], g00[1], g00[2], g00[3]}, in10[4] = {g10[0], g10[1], g10[2], g10[3]},
-               in11[4] = {g11[0], g11[1], g11[2], g11[3]};
-  const double b0 = q == 0 ? 1.0 : 0.0, b1 = q == 1 ? 1.0 : 0.0, b2 = q == 2 ? 1.0 : 0.0,
-               b3 = q == 3 ? 1.0 : 0.0;
-  double sc0[4], sc1[4];
-  bool bad = false;
-  const v4f64 zero4 = (v4f64){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb) {  // columns 0 .. 15
-    const int c0 = 4 * kb;
-    const BlockStep bs = tile16_block_step(g00[kb], c0, r, q, b0, b1, b2, b3, bad);
-    const int rb = r - c0;
-    const bool inb = rb >= 0 && rb < 4;
-    const double idr = selb(inb & (rb == q), 1.0, 0.0);
-    const double ya = __builtin_amdgcn_mfma_f64_16x16x4f64(bs.aop1, g00[kb], zero4, 0, 0, 0)[0];
-    const double yu = __builtin_amdgcn_mfma_f64_16x16x4f64(bs.aop1, idr, zero4, 0, 0, 0)[0];
-    const double y1 = __builtin_amdgcn_mfma_f64_16x16x4f64(bs.aop1, g10[kb], zero4, 0, 0, 0)[0];
-    sc0[kb] = bs.sck;
-    g00[kb] = selb(inb & (q > rb), yu, ya);
-    g10[kb] = y1;
-    // trailing columns of the first tile column (targets in g00 and g10): A operand by
-    // target column = the rows of g00 below the block
-    if (kb < 3) {
-      const double aop = selb(r > c0 + 3, -ya * bs.rq, 0.0);
-      const double bop = selb(inb, selb(q >= rb, yu, 0.0), ya);
-      v4f64 acc = (v4f64){g00[0], g00[1], g00[2], g00[3]};
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, bop, acc, 0, 0, 0);
-      v4f64 acc1 = (v4f64){g10[0], g10[1], g10[2], g10[3]};
-      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, y1, acc1, 0, 0, 0);
-#pragma unroll
-      for (int j = kb + 1; j < 4; ++j) {
-        const int c = 4 * j + q;
-        g00[j] = selb((r > c0 + 3) & (c > r), 0.0, acc[j]);
-        g10[j] = acc1[j];
-      }
-    }
-    // the second diagonal tile: target column = a row of g10 (all of them lie below the block)
-    {
-      v4f64 acc2 = (v4f64){g11[0], g11[1], g11[2], g11[3]};
-      acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(-y1 * bs.rq, y1, acc2, 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g11[j] = selb(4 * j + q > r, 0.0, acc2[j]);  // (its folded identity rows are not active yet)
-    }
-  }
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb) {  // columns 16 .. 31: the second diagonal tile alone
-    const int c0 = 4 * kb;
-    const BlockStep bs = tile16_block_step(g11[kb], c0, r, q, b0, b1, b2, b3, bad);
-    const int rb = r - c0;
-    const bool inb = rb >= 0 && rb < 4;
-    const double idr = selb(inb & (rb == q), 1.0, 0.0);
-    const double ya = __builtin_amdgcn_mfma_f64_16x16x4f64(bs.aop1, g11[kb], zero4, 0, 0, 0)[0];
-    const double yu = __builtin_amdgcn_mfma_f64_16x16x4f64(bs.aop1, idr, zero4, 0, 0, 0)[0];
-    sc1[kb] = bs.sck;
-    g11[kb] = selb(inb & (q > rb), yu, ya);
-    if (kb < 3) {
-      const double aop = selb(r > c0 + 3, -ya * bs.rq, 0.0);
-      const double bop = selb(inb, selb(q >= rb, yu, 0.0), ya);
-      v4f64 acc = (v4f64){g11[0], g11[1], g11[2], g11[3]};
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, bop, acc, 0, 0, 0);
-#pragma unroll
-      for (int j = kb + 1; j < 4; ++j) {
-        const int c = 4 * j + q;
-        g11[j] = selb((r > c0 + 3) & (c > r), 0.0, acc[j]);
-      }
-    }
-  }
-  if (bad) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      g00[j] = in00[j];
-      g10[j] = in10[j];
-      g11[j] = in11[j];
-    }
-    return 1;
-  }
-  dinv0 = 0.0;
-  dinv1 = 0.0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    g00[j] *= sc0[j];
-    g10[j] *= sc0[j];
-    g11[j] *= sc1[j];
-    dinv0 = selb(r == 4 * j + q, sc0[j], dinv0);
-    dinv1 = selb(r == 4 * j + q, sc1[j], dinv1);
-  }
-  return 0;
-}
-
 }  // namespace tile16
 }  // namespace ba
 #endif  // BA_TILE16_H_

@@ -291,27 +291,6 @@ def test_reproducible_bits(built):
             assert outs[0][2] == o[2]
 
 
-def test_fused_level_factorisation_matches_default_path(built):
-    """BA_DENSE_FUSED=1 (one launch per elimination level, contributions applied
-    lazily) must reproduce the default three-kernel factorisation."""
-    import os
-    sc = scenes.synthetic_ba_scene(40, 1500, 5, True, seed=11)
-    pr = scenes.scaled_problem(sc)
-    xs = []
-    for flag in ("0", "1"):
-        os.environ["BA_DENSE_FUSED"] = flag
-        try:
-            p = make_gpu(pr)
-            p.stage_linearize(100.0, 1.0)
-            p.stage_schur()
-            p.stage_solve_reduced()
-            xs.append(p.get_xy()[0].copy())
-        finally:
-            os.environ.pop("BA_DENSE_FUSED", None)
-    assert np.abs(xs[0]).max() > 0
-    assert np.abs(xs[0] - xs[1]).max() <= 1e-9 * np.abs(xs[0]).max()
-
-
 def test_cost_kernel_record_variants(built):
     """k_cost on the 8-byte {camera|pose, point} records (default) and on the
     16-byte records it falls back to for >= 65 536 cameras / poses
@@ -369,24 +348,17 @@ def test_one_stream_iteration_and_dataflow_sweep_equal_their_fallbacks(built):
     its reduced solve is ONE dataflow launch per level (k_chol_level_flow) and the
     backward sweep ONE dataflow launch (per-tile flags; roles from the block index when
     the grid is resident, from tickets otherwise: BA_DENSE_TICKET=1 forces tickets);
-    BA_FUSE_BL=1 (opt-in) runs back-substitution and trial-point linearisation as roles of
-    ONE launch (k_backsub_lin: per-piece flags, sc1 hand-offs; BA_BL_LEAD=8 interleaves them
-    finely so that the linearisation workgroups really wait for their flags); BA_GRAPH=1 replays
-    the iteration as a captured hipGraph (per-level launches: the generation number of the
-    dataflow launches is a kernel argument);
+    BA_GRAPH=1 replays the iteration as a captured hipGraph (per-level launches: the
+    generation number of the dataflow launches is a kernel argument);
     BA_FORCE_SIDE=1 (side stream with fork / join) and BA_DENSE_FLOW=0 (separate
     diag_trsm / update launches, one backward launch per level) are the paths every
-    other problem takes; BA_DENSE_FWD_FLOW=1 is the opt-in form that runs ALL levels of
-    the forward sweep as one dataflow launch (k_chol_fwd_flow: per-column counters of
-    finished updates).  Same arithmetic in the same order, so the trajectories must
+    other problem takes.  Same arithmetic in the same order, so the trajectories must
     agree bit for bit, iteration by iteration."""
     import os
     pr = scenes.scaled_problem(scenes.synthetic_ba_scene(150, 9000, 5, True, seed=33, pixel_sigma=0.3))
     runs = []
     for env in ({}, {"BA_FORCE_SIDE": "1"}, {"BA_DENSE_FLOW": "0"}, {"BA_FORCE_SIDE": "1", "BA_DENSE_FLOW": "0"},
-                {"BA_DENSE_TICKET": "1"}, {"BA_FUSE_BL": "1"}, {"BA_FUSE_BL": "1", "BA_BL_LEAD": "8"},
-                {"BA_DENSE_FWD_FLOW": "1"},
-                {"BA_DENSE_FWD_FLOW": "1", "BA_DENSE_TICKET": "1"}, {"BA_GRAPH": "1"}):
+                {"BA_DENSE_TICKET": "1"}, {"BA_GRAPH": "1"}):
         for k, v in env.items():
             os.environ[k] = v
         try:
