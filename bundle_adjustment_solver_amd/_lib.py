@@ -75,6 +75,14 @@ class BaPoResult(C.Structure):
                 ("n_rows", C.c_int), ("status", C.c_int)]
 
 
+class BaBatchResult(C.Structure):
+    """ba_batch_result — one problem of a batched full-BA solve (status 0 = solved,
+    1 = non-finite parameters, values left as given, 2 = over a limit, not solved)."""
+    _fields_ = [("n_iter", C.c_int), ("converged", C.c_int),
+                ("n_rows", C.c_int), ("status", C.c_int),
+                ("dropped_pivots", C.c_int)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                            C.c_int64, C.c_void_p)
 
@@ -82,6 +90,7 @@ _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _F = C.POINTER(C.c_float)
 _I32 = C.POINTER(C.c_int32)
+_I64 = C.POINTER(C.c_int64)
 _U8 = C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes): every symbol declared in include/ba_hip.h
@@ -220,6 +229,18 @@ SIGNATURES = {
                                                     _P, _P, _P, C.POINTER(BaOptions),
                                                     _P, C.c_int, _P, _P, _P]),
     "ba_planar_record": (C.c_int, [_F, _F, _F, _F, _F, _F]),
+    "ba_batch_create": (C.c_int, [C.POINTER(_P), _P, C.c_int, _I32, _I32, _I32, _I64,
+                                  _D, _D, _D, _U8, _D, _U8, _I32, _I32, _I32, _D]),
+    "ba_batch_destroy": (None, [_P]),
+    "ba_batch_solve": (C.c_int, [_P, C.POINTER(BaOptions), C.POINTER(BaIterInfo),
+                                 C.c_int, C.POINTER(BaBatchResult)]),
+    "ba_batch_update_values": (C.c_int, [_P, _D, _D]),
+    "ba_batch_get_poses": (C.c_int, [_P, _D]),
+    "ba_batch_get_points": (C.c_int, [_P, _D]),
+    "ba_batch_info": (C.c_int, [_P, _I64]),
+    "ba_batch_scratch_bytes": (C.c_int, [_P, _I64]),
+    "ba_batch_plan_problem": (C.c_int, [C.c_int, _U8, C.c_int, _U8, C.c_int64, _I32,
+                                        _I32, _I32, _I32, _U8, _I32, _I32]),
 }
 
 _lib = None

@@ -1,0 +1,887 @@
+// ba_batch.hip — batched full bundle adjustment: B independent small problems (sliding
+// windows), ONE persistent 256-thread workgroup each, the whole LM loop of
+// FullBundleAdjustmentSolver::Solve (reference core/full_bundle_adjustment_solver.cpp:
+// 705-1008) in one launch.  No grid barrier and no workgroup waits on another: a batch
+// larger than the device holds at once drains.  The arithmetic is the handle path's
+// (ba_device_fn.h, ba_chol_lds.h); the sums are ordered per problem only, so a problem
+// gives the same bits alone and at any position of any batch.
+//
+// Per iteration of one workgroup (fp64 throughout):
+//   landmark pass   one thread per optimisable landmark, its observations in insertion
+//                   order: C_i, b_i, and B_ji of the LAST observation of a (landmark, pose)
+//                   pair (reference :826)                               -> global scratch
+//   pose pass       one wave per optimisable pose, its observations strided over the
+//                   lanes, 27 wave sums: A_j, a_j                        -> LDS
+//                   (both passes are skipped after a SKIPPED step: the blocks are stored
+//                   undamped and are still the linearisation at the accepted point)
+//   damp / invert   C_i (1 + lambda) -> Cinv_i, Cinv_i b_i              -> global scratch
+//   Schur           one thread per half 6x6 block (3 rows) of the lower triangle of S, the
+//                   landmarks in ascending order through the (landmark, pose) -> pair table;
+//                   rhs_j = a_j - sum_i B_ji Cinv_i b_i                  -> LDS image
+//   reduced solve   chol_lds_factor_solve on the LDS image (<= 96 columns + rhs block)
+//   back-substitution, trial point, quadratic model, step norms; trial cost; control step
+//
+// Host side: ba_batch_create plans the structure once (stable landmark-major grouping,
+// pair lists, last-writer marks, one upload); ba_batch_solve is one launch and one sync.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ba_chol_lds.h"
+#include "ba_device_fn.h"
+#include "ba_handle.h"
+
+namespace ba {
+namespace {
+
+constexpr int kBatchBlock = 256;
+constexpr int kBatchMaxOpt = 16;    // optimisable poses: 6 * 16 = kTailCols columns
+constexpr int kBatchMaxPoses = 64;  // all poses: accepted + trial transforms in LDS (12 KiB)
+constexpr int kBatchMaxBlk = kBatchMaxOpt * (kBatchMaxOpt + 1) / 2;
+static_assert(6 * kBatchMaxOpt <= kTailCols, "the reduced system must fit the LDS image");
+
+struct BatchProb {  // one problem: sizes and element offsets into the concatenated arrays
+  int32_t n_cam, n_pose, N, n_pt, M, status, n_obs, P;
+  int64_t cam0, pose0, pt0, obs0, pair0;  // cameras, poses, points, observations, pairs
+  int64_t m0, tab0, pobs0, pptr0;         // opt landmarks, M*N table, pose-major list, its N+1 pointers
+};
+
+struct BatchDev {
+  const BatchProb *prob;
+  const double *cams;    // 16 per camera: fx fy cx cy R_cj t_cj
+  double *poses;         // 12 per pose, in/out
+  const int32_t *jopt;   // per pose: optimisable index or -1
+  double *pts[2];        // 3 per point; [0] in/out, [1] the other parameter buffer
+  const int32_t *opt_lm; // per optimisable landmark: its point (problem-local)
+  const int4 *lobs;      // landmark-major: {camera, pose, point, pair << 1 | last writer, or -1}
+  const double2 *luv;
+  const int32_t *lm_ptr;   // per point (+1 per problem): first observation (problem-local)
+  const int32_t *pair_ptr; // per optimisable landmark (+1 per problem): first pair
+  const int32_t *pair_j;   // per pair: optimisable pose
+  const int32_t *tab;      // per (optimisable landmark, optimisable pose): pair or -1
+  const int32_t *pobs;     // per optimisable pose, landmark-major: observation (problem-local)
+  const int32_t *pobs_ptr;
+  // scratch
+  double *C6, *b3, *Cinv6, *Cinvb3, *W18;
+  DevIterRec *rows;
+  int cap;
+  ba_batch_result *res;
+  // options (promoted as the handle path promotes them)
+  double lambda0, huber, thr_step, thr_cost, dec_ratio, inc_ratio;
+  int max_iter, gn;
+};
+
+template <int NPt>
+struct BatchLds {
+  static constexpr int nbt = 16 * NPt;
+  static constexpr int LS = nbt + 16 + 1;
+  double Lb[nbt * LS];
+  double Eb[NPt][16 * kTailES];
+  double xs[kTailCols];
+  double cams[kCamLds * 16];
+  double P[2][kBatchMaxPoses * 12];
+  double A[kBatchMaxOpt * 36];
+  double a[kBatchMaxOpt * 6];
+  double red[8];
+  double bc[4];  // trial cost, model estimate, sum |y|, sum |x| (thread 0 -> control step)
+  DevCtrl ctrl;
+  int32_t jopt[kBatchMaxPoses];
+  uint8_t blk_j[kBatchMaxBlk], blk_k[kBatchMaxBlk];
+};
+
+// sum of residual norms over every observation of the problem at parameter buffer `sel`
+template <class LDS>
+__device__ __forceinline__ double batch_cost(const BatchDev &d, const BatchProb &pr, LDS &s, const int sel) {
+  const int4 *ob = d.lobs + pr.obs0;
+  const double2 *uv = d.luv + pr.obs0;
+  const double *X = d.pts[sel] + pr.pt0 * 3;
+  double acc = 0.0;
+  for (int t = threadIdx.x; t < pr.n_obs; t += kBatchBlock) {
+    const int4 r = ob[t];
+    const double2 u = uv[t];
+    const double *Xp = X + (size_t)r.z * 3;
+    ObsGeom g;
+    project(s.cams + r.x * 16, s.P[sel] + r.y * 12, Xp[0], Xp[1], Xp[2], u.x, u.y, g);
+    acc += sqrt(g.r0 * g.r0 + g.r1 * g.r1);
+  }
+  return block_sum(acc, s.red);
+}
+
+template <int NPt>
+__global__ __launch_bounds__(kBatchBlock) void k_ba_batch(BatchDev d) {
+  using LDS = BatchLds<NPt>;
+  constexpr int nbt = LDS::nbt, LS = LDS::LS;
+  __shared__ LDS s;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const BatchProb pr = d.prob[blockIdx.x];
+  ba_batch_result *res = d.res + blockIdx.x;
+  if (pr.status != 0) {  // beyond a limit: not solved, nothing read or written but the result
+    if (tid == 0) {
+      res->n_iter = 0;
+      res->converged = 0;
+      res->n_rows = 0;
+      res->status = pr.status;
+      res->dropped_pivots = 0;
+    }
+    return;
+  }
+  const int N = pr.N, M = pr.M, n6 = 6 * N;
+  double *Pg = d.poses + pr.pose0 * 12;
+  double *X0 = d.pts[0] + pr.pt0 * 3, *X1 = d.pts[1] + pr.pt0 * 3;
+  // ---- stage the problem; refuse non-finite parameters -------------------------------
+  int bad_val = 0;
+  for (int k = tid; k < pr.n_cam * 16; k += kBatchBlock) s.cams[k] = d.cams[pr.cam0 * 16 + k];
+  for (int k = tid; k < pr.n_pose * 12; k += kBatchBlock) {
+    const double v = Pg[k];
+    s.P[0][k] = v;
+    s.P[1][k] = v;  // fixed poses are never written again
+    bad_val |= !isfinite(v);
+  }
+  for (int k = tid; k < pr.n_pose; k += kBatchBlock) s.jopt[k] = d.jopt[pr.pose0 + k];
+  for (int k = tid; k < pr.n_pt * 3; k += kBatchBlock) {
+    const double v = X0[k];
+    X1[k] = v;  // fixed points are never written again
+    bad_val |= !isfinite(v);
+  }
+  for (int k = tid; k < (int)(sizeof(s.Eb) / sizeof(double)); k += kBatchBlock) (&s.Eb[0][0])[k] = 0.0;
+  if (tid == 0) {
+    int b = 0;
+    for (int j = 0; j < N; ++j)
+      for (int k = 0; k <= j; ++k, ++b) {
+        s.blk_j[b] = (uint8_t)j;
+        s.blk_k[b] = (uint8_t)k;
+      }
+    res->dropped_pivots = 0;
+    DevCtrl &c = s.ctrl;
+    c.lambda = d.lambda0;
+    c.huber = d.huber;
+    c.thr_step = d.thr_step;
+    c.thr_cost = d.thr_cost;
+    c.dec_ratio = d.dec_ratio;
+    c.inc_ratio = d.inc_ratio;
+    c.max_iter = d.max_iter;
+    c.gn = d.gn;
+    c.cur = 0;
+    c.lcur = 0;
+    c.tcur = c.tlcur = 0;
+    c.done = 0;
+    c.iter = 0;
+    c.converged = 0;
+  }
+  if (__syncthreads_or(bad_val)) {
+    if (tid == 0) {
+      res->n_iter = 0;
+      res->converged = 0;
+      res->n_rows = 0;
+      res->status = 1;
+    }
+    return;
+  }
+  // ---- initial cost (reference :707-708) ----------------------------------------------
+  {
+    const double c0 = batch_cost(d, pr, s, 0);
+    if (tid == 0) {
+      s.ctrl.prev_cost = c0;
+      s.ctrl.t_last = wall_clock64();
+    }
+  }
+  __syncthreads();
+  const int4 *ob = d.lobs + pr.obs0;
+  const double2 *uvp = d.luv + pr.obs0;
+  const int32_t *lm_ptr = d.lm_ptr + pr.pt0 + blockIdx.x;
+  const int32_t *opt_lm = d.opt_lm + pr.m0;
+  const int32_t *pair_ptr = d.pair_ptr + pr.m0 + blockIdx.x;
+  const int32_t *pair_j = d.pair_j + pr.pair0;
+  const int32_t *tab = d.tab + pr.tab0;
+  double *C6 = d.C6 + pr.m0 * 6, *b3 = d.b3 + pr.m0 * 3;
+  double *Ci6 = d.Cinv6 + pr.m0 * 6, *Cib3 = d.Cinvb3 + pr.m0 * 3;
+  double *Wg = d.W18 + pr.pair0 * 18;
+  int cur = 0;
+  bool need_lin = true;
+  const double huber = d.huber;
+  while (true) {
+    const double *X = cur ? X1 : X0;
+    double *Xt = cur ? X0 : X1;
+    const double *Pc = s.P[cur];
+    double *Pt = s.P[cur ^ 1];
+    const double lp1 = 1.0 + s.ctrl.lambda;
+    if (need_lin) {
+      // ---- landmark side (reference :811-828) -----------------------------------------
+      for (int i = tid; i < M; i += kBatchBlock) {
+        const int q = opt_lm[i];
+        const double x0 = X[q * 3 + 0], x1 = X[q * 3 + 1], x2 = X[q * 3 + 2];
+        double C[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
+        const int o1 = lm_ptr[q + 1];
+        for (int t = lm_ptr[q]; t < o1; ++t) {
+          const int4 r = ob[t];
+          const double2 u = uvp[t];
+          const double *cam = s.cams + r.x * 16;
+          const double *T = Pc + r.y * 12;
+          ObsGeom g;
+          project(cam, T, x0, x1, x2, u.x, u.y, g);
+          double w, G[6], Rm[6];
+          weight_and_G(cam, g, huber, w, G);
+          make_R(G, T, Rm);
+          const double wr0 = w * g.r0, wr1 = w * g.r1;
+          C[0] += w * (Rm[0] * Rm[0] + Rm[3] * Rm[3]);
+          C[1] += w * (Rm[0] * Rm[1] + Rm[3] * Rm[4]);
+          C[2] += w * (Rm[0] * Rm[2] + Rm[3] * Rm[5]);
+          C[3] += w * (Rm[1] * Rm[1] + Rm[4] * Rm[4]);
+          C[4] += w * (Rm[1] * Rm[2] + Rm[4] * Rm[5]);
+          C[5] += w * (Rm[2] * Rm[2] + Rm[5] * Rm[5]);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) b[c] -= Rm[c] * wr0 + Rm[3 + c] * wr1;
+          if (r.w >= 0 && (r.w & 1)) {  // the pair's last observation: B_ji = w Q^T R survives
+            double Q[12];
+            make_Q(G, g.Xij, Q);
+            double *Wp = Wg + (size_t)(r.w >> 1) * 18;
+#pragma unroll
+            for (int rr = 0; rr < 6; ++rr)
+#pragma unroll
+              for (int c = 0; c < 3; ++c) Wp[rr * 3 + c] = w * (Q[rr] * Rm[c] + Q[6 + rr] * Rm[3 + c]);
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) C6[(size_t)i * 6 + k] = C[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) b3[(size_t)i * 3 + k] = b[k];
+      }
+      // ---- pose side (reference :789-809): one wave per optimisable pose ----------------
+      for (int j = wv; j < N; j += kBatchBlock / 64) {
+        const int32_t *pp = d.pobs_ptr + pr.pptr0 + j;
+        const int32_t *po = d.pobs + pr.pobs0;
+        double acc[27];
+#pragma unroll
+        for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+        const int e1 = pp[1];
+        for (int t = pp[0] + lane; t < e1; t += 64) {
+          const int so = po[t];
+          const int4 r = ob[so];
+          const double2 u = uvp[so];
+          const double *cam = s.cams + r.x * 16;
+          const double *Xp = X + (size_t)r.z * 3;
+          ObsGeom g;
+          project(cam, Pc + r.y * 12, Xp[0], Xp[1], Xp[2], u.x, u.y, g);
+          double w, G[6], Q[12];
+          weight_and_G(cam, g, huber, w, G);
+          make_Q(G, g.Xij, Q);
+          const double wr0 = w * g.r0, wr1 = w * g.r1;
+          int k = 0;
+#pragma unroll
+          for (int rr = 0; rr < 6; ++rr)
+#pragma unroll
+            for (int c = rr; c < 6; ++c, ++k) acc[k] += (w * Q[rr]) * Q[c] + (w * Q[6 + rr]) * Q[6 + c];
+#pragma unroll
+          for (int c = 0; c < 6; ++c) acc[21 + c] -= Q[c] * wr0 + Q[6 + c] * wr1;
+        }
+#pragma unroll
+        for (int k = 0; k < 27; ++k) acc[k] = wave_sum(acc[k]);
+        if (lane == 0) {
+          int k = 0;
+#pragma unroll
+          for (int rr = 0; rr < 6; ++rr)
+#pragma unroll
+            for (int c = rr; c < 6; ++c, ++k) {
+              s.A[j * 36 + rr * 6 + c] = acc[k];
+              s.A[j * 36 + c * 6 + rr] = acc[k];
+            }
+#pragma unroll
+          for (int c = 0; c < 6; ++c) s.a[j * 6 + c] = acc[21 + c];
+        }
+      }
+      __syncthreads();
+    }
+    // ---- damp and invert (reference :846-856); reset the LDS image --------------------
+    for (int i = tid; i < M; i += kBatchBlock) {
+      double cd[6], ci[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) cd[k] = C6[(size_t)i * 6 + k];
+      cd[0] *= lp1;
+      cd[3] *= lp1;
+      cd[5] *= lp1;
+      spd3_inverse(cd, ci);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) Ci6[(size_t)i * 6 + k] = ci[k];
+      const double b0 = b3[(size_t)i * 3], b1 = b3[(size_t)i * 3 + 1], b2 = b3[(size_t)i * 3 + 2];
+      Cib3[(size_t)i * 3 + 0] = ci[0] * b0 + ci[1] * b1 + ci[2] * b2;
+      Cib3[(size_t)i * 3 + 1] = ci[1] * b0 + ci[3] * b1 + ci[4] * b2;
+      Cib3[(size_t)i * 3 + 2] = ci[2] * b0 + ci[4] * b1 + ci[5] * b2;
+    }
+    for (int e = tid; e < nbt * LS; e += kBatchBlock) {
+      const int c = e / LS, r = e - c * LS;
+      s.Lb[e] = (r == c && c >= n6) ? 1.0 : 0.0;  // unit diagonal on padding columns
+    }
+    __syncthreads();
+    // ---- Schur complement (reference :858-888), lower triangle, into the LDS image ----
+    const int n_task = N * (N + 1);  // (block, half): rows 3h .. 3h+2 of block (j, k), j >= k
+    for (int task = tid; task < n_task; task += kBatchBlock) {
+      const int blk = task >> 1, h3 = (task & 1) * 3;
+      const int j = s.blk_j[blk], k = s.blk_k[blk];
+      double acc[18];
+#pragma unroll
+      for (int e = 0; e < 18; ++e) acc[e] = 0.0;
+      for (int i = 0; i < M; ++i) {
+        const int pj = tab[(size_t)i * N + j];
+        const int pk = tab[(size_t)i * N + k];
+        if (pj < 0 || pk < 0) continue;
+        const double *I = Ci6 + (size_t)i * 6;
+        const double i00 = I[0], i01 = I[1], i02 = I[2], i11 = I[3], i12 = I[4], i22 = I[5];
+        const double *Wj = Wg + (size_t)pj * 18 + h3 * 3;
+        double Wk[18];
+#pragma unroll
+        for (int e = 0; e < 18; ++e) Wk[e] = Wg[(size_t)pk * 18 + e];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          const double w0 = Wj[r * 3 + 0], w1 = Wj[r * 3 + 1], w2 = Wj[r * 3 + 2];
+          // V_ji = B_ji Cinv_i (reference :862), never stored
+          const double v0 = w0 * i00 + w1 * i01 + w2 * i02;
+          const double v1 = w0 * i01 + w1 * i11 + w2 * i12;
+          const double v2 = w0 * i02 + w1 * i12 + w2 * i22;
+#pragma unroll
+          for (int c = 0; c < 6; ++c) acc[r * 6 + c] += v0 * Wk[c * 3 + 0] + v1 * Wk[c * 3 + 1] + v2 * Wk[c * 3 + 2];
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          const int row = 6 * j + h3 + r, col = 6 * k + c;
+          if (row < col) continue;
+          double av = 0.0;
+          if (j == k) {
+            av = s.A[j * 36 + (h3 + r) * 6 + c];
+            if (h3 + r == c) av *= lp1;  // damped A_j (reference :833-844)
+          }
+          s.Lb[col * LS + row] = av - acc[r * 6 + c];
+        }
+    }
+    for (int t = tid; t < n6; t += kBatchBlock) {  // rhs_j = a_j - sum_i B_ji (Cinv_i b_i)
+      const int j = t / 6, r = t - 6 * j;
+      double acc = 0.0;
+      for (int i = 0; i < M; ++i) {
+        const int pj = tab[(size_t)i * N + j];
+        if (pj < 0) continue;
+        const double *Wj = Wg + (size_t)pj * 18 + r * 3;
+        const double *cb = Cib3 + (size_t)i * 3;
+        acc += Wj[0] * cb[0] + Wj[1] * cb[1] + Wj[2] * cb[2];
+      }
+      s.Lb[t * LS + nbt] = s.a[t] - acc;
+    }
+    __syncthreads();
+    // ---- reduced solve (reference :905) ------------------------------------------------
+    chol_lds_factor_solve<NPt, false, LS>(s.Lb, s.Eb, s.xs, &res->dropped_pivots);
+    __syncthreads();
+    // ---- back-substitution, trial point, model, step norms (reference :910-963) -------
+    double est = 0.0, sy = 0.0, estp = 0.0, sx = 0.0;
+    for (int i = tid; i < M; i += kBatchBlock) {
+      double u[3] = {0, 0, 0};
+      const int p1 = pair_ptr[i + 1];
+      for (int p = pair_ptr[i]; p < p1; ++p) {
+        const double *xj = s.xs + 6 * pair_j[p];
+        const double *W = Wg + (size_t)p * 18;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          double v = 0.0;
+#pragma unroll
+          for (int r = 0; r < 6; ++r) v += W[r * 3 + c] * xj[r];
+          u[c] += v;
+        }
+      }
+      const double *I = Ci6 + (size_t)i * 6;
+      const double *cb = Cib3 + (size_t)i * 3;
+      const double y0 = cb[0] - (I[0] * u[0] + I[1] * u[1] + I[2] * u[2]);
+      const double y1 = cb[1] - (I[1] * u[0] + I[3] * u[1] + I[4] * u[2]);
+      const double y2 = cb[2] - (I[2] * u[0] + I[4] * u[1] + I[5] * u[2]);
+      const int q = opt_lm[i];
+      Xt[q * 3 + 0] = X[q * 3 + 0] + y0;
+      Xt[q * 3 + 1] = X[q * 3 + 1] + y1;
+      Xt[q * 3 + 2] = X[q * 3 + 2] + y2;
+      const double *C = C6 + (size_t)i * 6;
+      const double *b = b3 + (size_t)i * 3;
+      const double c00 = C[0] * lp1, c11 = C[3] * lp1, c22 = C[5] * lp1;  // damped C_i (reference :447)
+      const double r0 = y0 * c00 + y1 * C[1] + y2 * C[2];
+      const double r1 = y0 * C[1] + y1 * c11 + y2 * C[4];
+      const double r2 = y0 * C[2] + y1 * C[4] + y2 * c22;
+      est += (b[0] * y0 + b[1] * y1 + b[2] * y2) + (r0 * y0 + r1 * y1 + r2 * y2) +
+             2.0 * (y0 * u[0] + y1 * u[1] + y2 * u[2]);
+      sy += sqrt(y0 * y0 + y1 * y1 + y2 * y2);
+    }
+    for (int p = tid; p < pr.n_pose; p += kBatchBlock) {
+      const int j = s.jopt[p];
+      if (j < 0) continue;
+      const double *xj = s.xs + 6 * j;
+      const double v0 = xj[0], v1 = xj[1], v2 = xj[2], w0 = xj[3], w1 = xj[4], w2 = xj[5];
+      double dR[9], dt[3];
+      se3_exp(v0, v1, v2, w0, w1, w2, dR, dt);
+      const double *T = Pc + p * 12;
+      double *To = Pt + p * 12;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          To[r * 3 + c] = dR[r * 3 + 0] * T[0 * 3 + c] + dR[r * 3 + 1] * T[1 * 3 + c] + dR[r * 3 + 2] * T[2 * 3 + c];
+        To[9 + r] = dR[r * 3 + 0] * T[9] + dR[r * 3 + 1] * T[10] + dR[r * 3 + 2] * T[11] + dt[r];
+      }
+      const double *aj = s.a + j * 6, *Aj = s.A + j * 36;
+      double e = 0.0;
+#pragma unroll
+      for (int r = 0; r < 6; ++r) e += aj[r] * xj[r];
+      double qd = 0.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double rowc = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) rowc += xj[r] * (r == c ? Aj[r * 6 + c] * lp1 : Aj[r * 6 + c]);
+        qd += rowc * xj[c];
+      }
+      estp += e + qd;
+      sx += sqrt(v0 * v0 + v1 * v1 + v2 * v2 + w0 * w0 + w1 * w1 + w2 * w2);
+    }
+    block_sum2(est, sy, s.red);
+    if (tid == 0) {
+      s.bc[1] = est;
+      s.bc[2] = sy;
+    }
+    block_sum2(estp, sx, s.red);
+    if (tid == 0) {
+      s.bc[1] += estp;
+      s.bc[3] = sx;
+    }
+    __syncthreads();  // the trial parameters are complete
+    // ---- trial cost, trust region, convergence, log row (reference :928-1007) ---------
+    const double tc = batch_cost(d, pr, s, cur ^ 1);
+    if (tid == 0)
+      lm_control_step(&s.ctrl, d.rows + (size_t)blockIdx.x * d.cap, d.cap, (double)pr.n_obs, N + M, tc, s.bc[1],
+                      s.bc[2], s.bc[3]);
+    __syncthreads();
+    const int ncur = s.ctrl.cur;
+    need_lin = ncur != cur;  // rejected: the undamped blocks still belong to the accepted point
+    cur = ncur;
+    if (s.ctrl.done) break;
+    __syncthreads();
+  }
+  __syncthreads();
+  // ---- write back: poses, and the points if the accepted buffer is the second one ------
+  for (int k = tid; k < pr.n_pose * 12; k += kBatchBlock) Pg[k] = s.P[cur][k];
+  if (cur)
+    for (int k = tid; k < pr.n_pt * 3; k += kBatchBlock) X0[k] = X1[k];
+  if (tid == 0) {
+    res->n_iter = s.ctrl.iter;
+    res->converged = s.ctrl.converged;
+    res->n_rows = s.ctrl.iter;
+    res->status = 0;
+  }
+}
+
+}  // namespace
+}  // namespace ba
+
+// ===========================================================================================
+// host side
+// ===========================================================================================
+using ba::fail;
+
+struct ba_batch {
+  ba_handle *h = nullptr;  // borrowed (device and stream): the handle outlives the batch
+  int B = 0;
+  int npt_class = 6;  // 16-column panels of the LDS image: 2, 4 or 6
+  int max_N = 0;
+  std::vector<ba::BatchProb> prob;
+  int64_t n_cam = 0, n_pose = 0, n_pt = 0, n_obs = 0, n_pair = 0, n_m = 0;
+  int64_t max_scratch = 0;
+  char *dev = nullptr;  // one allocation: structure | parameters | scratch
+  size_t dev_bytes = 0;
+  ba::BatchDev d{};
+  ba::DevIterRec *rows = nullptr;
+  size_t rows_cap = 0;  // records
+};
+
+namespace {
+
+// Structure of ONE problem (host only): the stable landmark-major order of its
+// observations, the (landmark, pose) pairs of optimisable members in (landmark, pose)
+// order, and per observation its pair and whether it is the pair's last writer.
+struct ProbPlan {
+  std::vector<int32_t> jopt, iopt, opt_lm, order, lm_ptr, pair_ptr, pair_j, obs_pair, tab, pobs, pobs_ptr;
+  std::vector<uint8_t> last;
+  int N = 0, M = 0;
+};
+
+// device scratch of one problem: C, b, Cinv, Cinv*b of its M landmarks (6+3+6+3 doubles),
+// W of its P pairs (18) and its trial points (3 each)
+int64_t scratch_bytes_of(const ba::BatchProb &P) {
+  return (int64_t)sizeof(double) * ((int64_t)P.M * 18 + (int64_t)P.P * 18 + (int64_t)P.n_pt * 3);
+}
+
+void plan_problem(int n_pose, const uint8_t *pose_fixed, int n_pt, const uint8_t *pt_fixed, int64_t n_obs,
+                  const int32_t *obs_pose, const int32_t *obs_pt, ProbPlan &pl) {
+  pl.jopt.assign(n_pose, -1);
+  pl.iopt.assign(n_pt, -1);
+  pl.N = pl.M = 0;
+  for (int p = 0; p < n_pose; ++p)
+    if (!(pose_fixed && pose_fixed[p])) pl.jopt[p] = pl.N++;
+  pl.opt_lm.clear();
+  for (int q = 0; q < n_pt; ++q)
+    if (!(pt_fixed && pt_fixed[q])) {
+      pl.iopt[q] = pl.M++;
+      pl.opt_lm.push_back(q);
+    }
+  pl.order.resize(n_obs);
+  for (int64_t k = 0; k < n_obs; ++k) pl.order[k] = (int32_t)k;
+  std::stable_sort(pl.order.begin(), pl.order.end(),
+                   [&](int32_t a, int32_t b) { return obs_pt[a] < obs_pt[b]; });
+  pl.lm_ptr.assign(n_pt + 1, 0);
+  for (int64_t k = 0; k < n_obs; ++k) pl.lm_ptr[obs_pt[k] + 1]++;
+  for (int q = 0; q < n_pt; ++q) pl.lm_ptr[q + 1] += pl.lm_ptr[q];
+  pl.pair_ptr.assign(pl.M + 1, 0);
+  pl.pair_j.clear();
+  pl.tab.assign((size_t)pl.M * pl.N, -1);
+  pl.obs_pair.assign(n_obs, -1);
+  pl.last.assign(n_obs, 0);
+  std::vector<int32_t> js;
+  for (int i = 0; i < pl.M; ++i) {
+    const int q = pl.opt_lm[i];
+    js.clear();
+    for (int t = pl.lm_ptr[q]; t < pl.lm_ptr[q + 1]; ++t) {
+      const int j = pl.jopt[obs_pose[pl.order[t]]];
+      if (j >= 0) js.push_back(j);
+    }
+    std::sort(js.begin(), js.end());
+    js.erase(std::unique(js.begin(), js.end()), js.end());
+    for (int32_t j : js) {
+      pl.tab[(size_t)i * pl.N + j] = (int32_t)pl.pair_j.size();
+      pl.pair_j.push_back(j);
+    }
+    pl.pair_ptr[i + 1] = (int32_t)pl.pair_j.size();
+    // the last observation (insertion order) of each pair is its writer (reference :826)
+    for (int t = pl.lm_ptr[q + 1] - 1; t >= pl.lm_ptr[q]; --t) {
+      const int j = pl.jopt[obs_pose[pl.order[t]]];
+      if (j < 0) continue;
+      const int32_t pid = pl.tab[(size_t)i * pl.N + j];
+      pl.obs_pair[t] = pid;
+      bool later = false;
+      for (int t2 = t + 1; t2 < pl.lm_ptr[q + 1] && !later; ++t2)
+        later = pl.obs_pair[t2] == pid;
+      pl.last[t] = later ? 0 : 1;
+    }
+  }
+  // pose-major index of the landmark-major list
+  pl.pobs_ptr.assign(pl.N + 1, 0);
+  for (int64_t t = 0; t < n_obs; ++t) {
+    const int j = pl.jopt[obs_pose[pl.order[t]]];
+    if (j >= 0) pl.pobs_ptr[j + 1]++;
+  }
+  for (int j = 0; j < pl.N; ++j) pl.pobs_ptr[j + 1] += pl.pobs_ptr[j];
+  pl.pobs.resize(pl.pobs_ptr[pl.N]);
+  std::vector<int32_t> fill(pl.pobs_ptr.begin(), pl.pobs_ptr.end() - 1);
+  for (int64_t t = 0; t < n_obs; ++t) {
+    const int j = pl.jopt[obs_pose[pl.order[t]]];
+    if (j >= 0) pl.pobs[fill[j]++] = (int32_t)t;
+  }
+}
+
+template <class T>
+size_t put(std::vector<char> &blob, const std::vector<T> &v) {
+  size_t o = (blob.size() + 255) & ~(size_t)255;
+  blob.resize(o + v.size() * sizeof(T));
+  if (!v.empty()) std::memcpy(blob.data() + o, v.data(), v.size() * sizeof(T));
+  return o;
+}
+
+int batch_check_offsets(const char *name, int B, const int64_t *off, bool strict) {
+  if (!off) return fail(std::string("ba_batch_create: null ") + name);
+  if (off[0] != 0) return fail(std::string("ba_batch_create: ") + name + "[0] must be 0");
+  for (int b = 0; b < B; ++b)
+    if (off[b + 1] < off[b] || (strict && off[b + 1] == off[b]))
+      return fail(std::string("ba_batch_create: ") + name + " must " + (strict ? "increase" : "not decrease") +
+                  " (problem " + std::to_string(b) + ")");
+  return 0;
+}
+
+size_t lds_bytes_of(int npt) {
+  return npt == 2 ? sizeof(ba::BatchLds<2>) : npt == 4 ? sizeof(ba::BatchLds<4>) : sizeof(ba::BatchLds<6>);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ba_batch_plan_problem(int n_pose, const uint8_t *pose_fixed, int n_pt, const uint8_t *pt_fixed, int64_t n_obs,
+                          const int32_t *obs_pose, const int32_t *obs_pt, int32_t *order, int32_t *obs_pair,
+                          uint8_t *last_writer, int32_t *pair_lm, int32_t *pair_pose) {
+  if (n_pose < 0 || n_pt < 0 || n_obs < 0 || n_obs > INT32_MAX) return fail("ba_batch_plan_problem: bad sizes");
+  if (n_obs > 0 && (!obs_pose || !obs_pt)) return fail("ba_batch_plan_problem: null observations");
+  for (int64_t k = 0; k < n_obs; ++k)
+    if (obs_pose[k] < 0 || obs_pose[k] >= n_pose || obs_pt[k] < 0 || obs_pt[k] >= n_pt)
+      return fail("ba_batch_plan_problem: observation " + std::to_string(k) + " out of range");
+  ProbPlan pl;
+  plan_problem(n_pose, pose_fixed, n_pt, pt_fixed, n_obs, obs_pose, obs_pt, pl);
+  for (int64_t t = 0; t < n_obs; ++t) {
+    if (order) order[t] = pl.order[t];
+    if (obs_pair) obs_pair[t] = pl.obs_pair[t];
+    if (last_writer) last_writer[t] = pl.last[t];
+  }
+  for (int i = 0; i < pl.M; ++i)
+    for (int p = pl.pair_ptr[i]; p < pl.pair_ptr[i + 1]; ++p) {
+      if (pair_lm) pair_lm[p] = i;
+      if (pair_pose) pair_pose[p] = pl.pair_j[p];
+    }
+  return (int)pl.pair_j.size();
+}
+
+int ba_batch_create(ba_batch **out, ba_handle *h, int B, const int32_t *cam_off, const int32_t *pose_off,
+                    const int32_t *pt_off, const int64_t *obs_off, const double *cam_intr4, const double *cam_T12,
+                    const double *pose_T12, const uint8_t *pose_fixed, const double *pt_X3, const uint8_t *pt_fixed,
+                    const int32_t *obs_cam, const int32_t *obs_pose, const int32_t *obs_pt, const double *obs_uv2) {
+  if (out) *out = nullptr;
+  if (!out) return fail("ba_batch_create: null out");
+  if (B < 1) return fail("ba_batch_create: B must be >= 1");
+  if (!cam_off || !pose_off || !pt_off || !obs_off) return fail("ba_batch_create: null offsets");
+  {
+    std::vector<int64_t> t(B + 1);
+    const int32_t *o32[3] = {cam_off, pose_off, pt_off};
+    const char *nm[3] = {"cam_off", "pose_off", "pt_off"};
+    for (int a = 0; a < 3; ++a) {
+      for (int b = 0; b <= B; ++b) t[b] = o32[a][b];
+      if (batch_check_offsets(nm[a], B, t.data(), false)) return -1;
+    }
+    if (batch_check_offsets("obs_off", B, obs_off, false)) return -1;
+  }
+  if (!cam_intr4 || !cam_T12 || !pose_T12 || !pt_X3) return fail("ba_batch_create: null parameter array");
+  if (obs_off[B] > 0 && (!obs_cam || !obs_pose || !obs_pt || !obs_uv2))
+    return fail("ba_batch_create: null observation array");
+  for (int b = 0; b < B; ++b) {
+    const int nc = cam_off[b + 1] - cam_off[b], np = pose_off[b + 1] - pose_off[b], nq = pt_off[b + 1] - pt_off[b];
+    if (obs_off[b + 1] - obs_off[b] > INT32_MAX)
+      return fail("ba_batch_create: problem " + std::to_string(b) + " has too many observations");
+    for (int64_t k = obs_off[b]; k < obs_off[b + 1]; ++k)
+      if (obs_cam[k] < 0 || obs_cam[k] >= nc || obs_pose[k] < 0 || obs_pose[k] >= np || obs_pt[k] < 0 ||
+          obs_pt[k] >= nq)
+        return fail("ba_batch_create: observation " + std::to_string(k - obs_off[b]) + " of problem " +
+                    std::to_string(b) + " has an index outside its problem");
+  }
+  if (!h) return fail("ba_batch_create: null handle");
+  if (h->world > 1 || h->ar_fn) return fail("ba_batch_create: a sharded handle cannot run a batch");
+  if (h->arena) return fail("ba_batch_create: a streamed handle cannot run a batch");
+
+  ba_batch *bt = new ba_batch();
+  bt->h = h;
+  bt->B = B;
+  bt->prob.resize(B);
+  bt->n_cam = cam_off[B];
+  bt->n_pose = pose_off[B];
+  bt->n_pt = pt_off[B];
+  bt->n_obs = obs_off[B];
+  std::vector<double> cams((size_t)bt->n_cam * 16);
+  for (int64_t c = 0; c < bt->n_cam; ++c) {
+    std::memcpy(&cams[c * 16], cam_intr4 + 4 * c, 4 * sizeof(double));
+    std::memcpy(&cams[c * 16 + 4], cam_T12 + 12 * c, 12 * sizeof(double));
+  }
+  std::vector<int32_t> jopt(bt->n_pose), opt_lm, lm_ptr, pair_ptr, pair_j, tab, pobs, pobs_ptr;
+  std::vector<int4> lobs(bt->n_obs);
+  std::vector<double2> luv(bt->n_obs);
+  lm_ptr.reserve(bt->n_pt + B);
+  ProbPlan pl;
+  for (int b = 0; b < B; ++b) {
+    ba::BatchProb &P = bt->prob[b];
+    P.n_cam = cam_off[b + 1] - cam_off[b];
+    P.n_pose = pose_off[b + 1] - pose_off[b];
+    P.n_pt = pt_off[b + 1] - pt_off[b];
+    P.n_obs = (int32_t)(obs_off[b + 1] - obs_off[b]);
+    P.cam0 = cam_off[b];
+    P.pose0 = pose_off[b];
+    P.pt0 = pt_off[b];
+    P.obs0 = obs_off[b];
+    plan_problem(P.n_pose, pose_fixed ? pose_fixed + P.pose0 : nullptr, P.n_pt, pt_fixed ? pt_fixed + P.pt0 : nullptr,
+                 P.n_obs, obs_pose + P.obs0, obs_pt + P.obs0, pl);
+    P.N = pl.N;
+    P.M = pl.M;
+    P.P = (int32_t)pl.pair_j.size();
+    P.status = (P.N > ba::kBatchMaxOpt || P.n_pose > ba::kBatchMaxPoses || P.n_cam > ba::kCamLds) ? 2 : 0;
+    P.pair0 = (int64_t)pair_j.size();
+    P.m0 = (int64_t)opt_lm.size();
+    P.tab0 = (int64_t)tab.size();
+    P.pobs0 = (int64_t)pobs.size();
+    P.pptr0 = (int64_t)pobs_ptr.size();
+    for (int p = 0; p < P.n_pose; ++p) jopt[P.pose0 + p] = pl.jopt[p];
+    for (int t = 0; t < P.n_obs; ++t) {
+      const int64_t k = P.obs0 + pl.order[t];
+      const int32_t pid = pl.obs_pair[t];
+      lobs[P.obs0 + t] = make_int4(obs_cam[k], obs_pose[k], obs_pt[k], pid < 0 ? -1 : (pid << 1 | pl.last[t]));
+      luv[P.obs0 + t] = make_double2(obs_uv2[2 * k], obs_uv2[2 * k + 1]);
+    }
+    opt_lm.insert(opt_lm.end(), pl.opt_lm.begin(), pl.opt_lm.end());
+    lm_ptr.insert(lm_ptr.end(), pl.lm_ptr.begin(), pl.lm_ptr.end());      // at pt0 + b
+    pair_ptr.insert(pair_ptr.end(), pl.pair_ptr.begin(), pl.pair_ptr.end());  // at m0 + b
+    pair_j.insert(pair_j.end(), pl.pair_j.begin(), pl.pair_j.end());
+    tab.insert(tab.end(), pl.tab.begin(), pl.tab.end());
+    pobs.insert(pobs.end(), pl.pobs.begin(), pl.pobs.end());
+    pobs_ptr.insert(pobs_ptr.end(), pl.pobs_ptr.begin(), pl.pobs_ptr.end());
+    if (P.status == 0) bt->max_N = std::max(bt->max_N, P.N);
+    bt->max_scratch = std::max(bt->max_scratch, scratch_bytes_of(P));
+  }
+  bt->n_pair = (int64_t)pair_j.size();
+  bt->n_m = (int64_t)opt_lm.size();
+  bt->npt_class = bt->max_N <= 5 ? 2 : bt->max_N <= 10 ? 4 : 6;
+
+  // one host image, one upload: structure | parameters; the scratch follows it on the device
+  std::vector<char> blob;
+  std::vector<double> poses(pose_T12, pose_T12 + (size_t)bt->n_pose * 12), pts(pt_X3, pt_X3 + (size_t)bt->n_pt * 3);
+  const size_t o_prob = put(blob, bt->prob), o_cams = put(blob, cams), o_jopt = put(blob, jopt),
+               o_optlm = put(blob, opt_lm), o_lobs = put(blob, lobs), o_luv = put(blob, luv),
+               o_lmptr = put(blob, lm_ptr), o_pptr = put(blob, pair_ptr), o_pj = put(blob, pair_j),
+               o_tab = put(blob, tab), o_pobs = put(blob, pobs), o_poptr = put(blob, pobs_ptr),
+               o_poses = put(blob, poses), o_pts = put(blob, pts);
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  size_t o = al(blob.size());
+  const size_t o_pts1 = o;  o = al(o + (size_t)bt->n_pt * 3 * sizeof(double));
+  const size_t o_C = o;     o = al(o + (size_t)bt->n_m * 6 * sizeof(double));
+  const size_t o_b = o;     o = al(o + (size_t)bt->n_m * 3 * sizeof(double));
+  const size_t o_Ci = o;    o = al(o + (size_t)bt->n_m * 6 * sizeof(double));
+  const size_t o_Cib = o;   o = al(o + (size_t)bt->n_m * 3 * sizeof(double));
+  const size_t o_W = o;     o = al(o + (size_t)bt->n_pair * 18 * sizeof(double));
+  const size_t o_res = o;   o = al(o + (size_t)B * sizeof(ba_batch_result));
+  bt->dev_bytes = o;
+  if (hipSetDevice(h->device) != hipSuccess || hipMalloc((void **)&bt->dev, bt->dev_bytes) != hipSuccess) {
+    delete bt;
+    return fail("ba_batch_create: device allocation of " + std::to_string(o) + " bytes failed");
+  }
+  if (hipMemcpy(bt->dev, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(bt->dev);
+    delete bt;
+    return fail("ba_batch_create: upload failed");
+  }
+  ba::BatchDev &d = bt->d;
+  char *D = bt->dev;
+  d.prob = (const ba::BatchProb *)(D + o_prob);
+  d.cams = (const double *)(D + o_cams);
+  d.jopt = (const int32_t *)(D + o_jopt);
+  d.opt_lm = (const int32_t *)(D + o_optlm);
+  d.lobs = (const int4 *)(D + o_lobs);
+  d.luv = (const double2 *)(D + o_luv);
+  d.lm_ptr = (const int32_t *)(D + o_lmptr);
+  d.pair_ptr = (const int32_t *)(D + o_pptr);
+  d.pair_j = (const int32_t *)(D + o_pj);
+  d.tab = (const int32_t *)(D + o_tab);
+  d.pobs = (const int32_t *)(D + o_pobs);
+  d.pobs_ptr = (const int32_t *)(D + o_poptr);
+  d.poses = (double *)(D + o_poses);
+  d.pts[0] = (double *)(D + o_pts);
+  d.pts[1] = (double *)(D + o_pts1);
+  d.C6 = (double *)(D + o_C);
+  d.b3 = (double *)(D + o_b);
+  d.Cinv6 = (double *)(D + o_Ci);
+  d.Cinvb3 = (double *)(D + o_Cib);
+  d.W18 = (double *)(D + o_W);
+  d.res = (ba_batch_result *)(D + o_res);
+  *out = bt;
+  return 0;
+}
+
+void ba_batch_destroy(ba_batch *b) {
+  if (!b) return;
+  if (b->dev) (void)hipFree(b->dev);
+  if (b->rows) (void)hipFree(b->rows);
+  delete b;
+}
+
+int ba_batch_update_values(ba_batch *b, const double *T_jw12, const double *X3) {
+  if (!b) return fail("ba_batch_update_values: null batch");
+  HIP_TRY(hipSetDevice(b->h->device));
+  hipStream_t s = b->h->stream;
+  if (T_jw12)
+    HIP_TRY(hipMemcpyAsync(b->d.poses, T_jw12, (size_t)b->n_pose * 12 * sizeof(double), hipMemcpyHostToDevice, s));
+  if (X3)
+    HIP_TRY(hipMemcpyAsync(b->d.pts[0], X3, (size_t)b->n_pt * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ba_batch_get_poses(ba_batch *b, double *T_jw12) {
+  if (!b || !T_jw12) return fail("ba_batch_get_poses: null argument");
+  HIP_TRY(hipSetDevice(b->h->device));
+  HIP_TRY(hipMemcpyAsync(T_jw12, b->d.poses, (size_t)b->n_pose * 12 * sizeof(double), hipMemcpyDeviceToHost,
+                         b->h->stream));
+  HIP_TRY(hipStreamSynchronize(b->h->stream));
+  return 0;
+}
+
+int ba_batch_get_points(ba_batch *b, double *X3) {
+  if (!b || !X3) return fail("ba_batch_get_points: null argument");
+  HIP_TRY(hipSetDevice(b->h->device));
+  HIP_TRY(hipMemcpyAsync(X3, b->d.pts[0], (size_t)b->n_pt * 3 * sizeof(double), hipMemcpyDeviceToHost,
+                         b->h->stream));
+  HIP_TRY(hipStreamSynchronize(b->h->stream));
+  return 0;
+}
+
+int ba_batch_info(ba_batch *b, int64_t out8[8]) {
+  if (!b || !out8) return fail("ba_batch_info: null argument");
+  out8[0] = b->max_scratch;
+  out8[1] = (int64_t)lds_bytes_of(b->npt_class);
+  out8[2] = ba::kBatchMaxOpt;
+  out8[3] = ba::kBatchMaxPoses;
+  out8[4] = ba::kCamLds;
+  out8[5] = 16 * b->npt_class;
+  out8[6] = (int64_t)b->dev_bytes;
+  out8[7] = b->B;
+  return 0;
+}
+
+int ba_batch_scratch_bytes(ba_batch *b, int64_t *bytes) {
+  if (!b || !bytes) return fail("ba_batch_scratch_bytes: null argument");
+  for (int p = 0; p < b->B; ++p) bytes[p] = scratch_bytes_of(b->prob[p]);
+  return 0;
+}
+
+int ba_batch_solve(ba_batch *b, const ba_options *opt, ba_iter_info *rows, int cap, ba_batch_result *res) {
+  if (!b) return fail("ba_batch_solve: null batch");
+  if (!opt) return fail("ba_batch_solve: null options");
+  if (!res) return fail("ba_batch_solve: null result array");
+  if (cap < 0) return fail("ba_batch_solve: cap must be >= 0");
+  const int B = b->B;
+  if (opt->max_num_iterations <= 0) {  // nothing changes, converged, no rows
+    for (int p = 0; p < B; ++p) res[p] = ba_batch_result{0, b->prob[p].status ? 0 : 1, 0, b->prob[p].status, 0};
+    return 0;
+  }
+  HIP_TRY(hipSetDevice(b->h->device));
+  hipStream_t s = b->h->stream;
+  const int dcap = rows ? cap : 0;
+  const size_t n_rows = (size_t)B * (size_t)dcap;
+  if (n_rows > b->rows_cap) {
+    if (b->rows) (void)hipFree(b->rows);
+    b->rows = nullptr;
+    b->rows_cap = 0;
+    HIP_TRY(hipMalloc((void **)&b->rows, n_rows * sizeof(ba::DevIterRec)));
+    b->rows_cap = n_rows;
+  }
+  ba::BatchDev d = b->d;
+  d.rows = b->rows;
+  d.cap = dcap;
+  d.lambda0 = (double)opt->initial_lambda;
+  d.huber = (double)opt->threshold_huber_loss;
+  d.thr_step = (double)opt->threshold_step_size;
+  d.thr_cost = (double)opt->threshold_cost_change;
+  d.dec_ratio = (double)opt->decrease_ratio_lambda;
+  d.inc_ratio = (double)opt->increase_ratio_lambda;
+  d.max_iter = opt->max_num_iterations;
+  d.gn = opt->gauss_newton ? 1 : 0;
+  if (b->npt_class == 2)
+    hipLaunchKernelGGL(ba::k_ba_batch<2>, dim3(B), dim3(ba::kBatchBlock), 0, s, d);
+  else if (b->npt_class == 4)
+    hipLaunchKernelGGL(ba::k_ba_batch<4>, dim3(B), dim3(ba::kBatchBlock), 0, s, d);
+  else
+    hipLaunchKernelGGL(ba::k_ba_batch<6>, dim3(B), dim3(ba::kBatchBlock), 0, s, d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(res, d.res, (size_t)B * sizeof(ba_batch_result), hipMemcpyDeviceToHost, s));
+  if (dcap > 0)
+    HIP_TRY(hipMemcpyAsync(rows, b->rows, n_rows * sizeof(ba_iter_info), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+}  // extern "C"

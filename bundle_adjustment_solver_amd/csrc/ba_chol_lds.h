@@ -1,0 +1,138 @@
+// ba_chol_lds.h — Cholesky factorisation and solve of a small SPD system held in LDS by
+// ONE 256-thread workgroup: the tail block of the level-scheduled reduced solve
+// (k_chol_tail, ba_dense.hip) and the whole reduced camera system of a batched window
+// problem (ba_batch.hip).  Internal.
+#ifndef BA_CHOL_LDS_H_
+#define BA_CHOL_LDS_H_
+
+#include "ba_device.h"
+#include "ba_tile16.h"
+
+namespace ba {
+
+constexpr int kTailCols = 96;
+constexpr int kTailLS = kTailCols + 16 + 1;  // column stride of the LDS image (rows + rhs block + pad)
+constexpr int kTailES = 17;
+
+// dropped pivots are counted per handle (ba_get_dropped_pivots) or per problem of a batch;
+// the integer atomic runs only when a factorisation actually meets one
+__device__ __forceinline__ void count_bad_pivots(int *bad, int n, int lane) {
+  if (bad && n > 0 && lane == 0) atomicAdd(bad, n);
+}
+
+// Lb[c*LS + r]: column-major lower image of nbt = 16*NPt columns (unit diagonal on padding
+// columns), rows nbt .. nbt+15 the rhs block (row nbt = rhs); Eb[p] receives E_pp = L_pp^-T
+// (zeroed by the caller); xs receives x.  Left-looking 16-column panels (MFMA panel update
+// and TRSM, wave 0 factors the 16x16 diagonal tiles), the rhs forward-substituted as one
+// more row tile, block back substitution by wave 0.  Unpivoted: a pivot <= 1e-300 zeroes
+// its column and solution component and is counted in *bad.  Starts after a barrier of the
+// caller; the caller synchronises before it reads xs.
+template <int NPt, bool PAIR, int LS>
+__device__ __forceinline__ void chol_lds_factor_solve(double *Lb, double (*Eb)[16 * kTailES], double *xs,
+                                                      int *bad) {
+  typedef double v4f64 __attribute__((ext_vector_type(4)));
+  constexpr int nbt = 16 * NPt, ES = kTailES;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+
+  // Macro-steps.  PAIR: the first level of the block has TWO 32-column tiles
+  // (panels 0,1 and 2,3).  Tiles of one level are independent (the tile between
+  // them is structurally zero), so their panels are processed side by side:
+  // {0,2}, {1,3}, then 4, 5 — four sequential 16x16 factorisations instead of six.
+  constexpr int NG = PAIR ? NPt - 2 : NPt;
+#pragma unroll
+  for (int m = 0; m < NG; ++m) {
+    const int p0 = PAIR ? (m < 2 ? m : m + 2) : m;
+    const bool two = PAIR && m < 2;
+    // this wave's panel: waves 0,1 -> p0 and waves 2,3 -> p0 + 2 in a paired step
+    const int p = (two && wv >= 2) ? p0 + 2 : p0;
+    const int w2 = two ? (wv & 1) : wv, nw = two ? 2 : 4;
+    // columns that can contribute to panel p: from its own tile on in a paired
+    // step (the other tile's columns are zero in these rows), else all earlier ones
+    const int kc0 = two ? 32 * (p >> 1) : 0;
+    // (1) left-looking update: tile (ti,p) -= sum_kt L(ti,kt) L(p,kt)^T, ti = p .. NPt
+    if (m > 0) {
+      for (int ti = p + w2; ti <= NPt; ti += nw) {
+        v4f64 acc;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[g] = Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr];
+        for (int kc = kc0; kc < 16 * p; kc += 4) {
+          const double a = -Lb[(kc + lk) * LS + 16 * p + lr];
+          const double b = Lb[(kc + lk) * LS + 16 * ti + lr];
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr] = acc[g];
+      }
+      __syncthreads();
+    }
+    // (2) factor the diagonal tile(s): wave 0 (and wave 2 for the second panel of a paired step)
+    if (wv == 0 || (two && wv == 2)) {
+      const int r = lr, q = lk;
+      double g[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = 4 * j + q;
+        g[j] = (r >= c) ? Lb[(16 * p + c) * LS + 16 * p + r] : 0.0;
+      }
+      double dinv;
+      count_bad_pivots(bad, tile16::tile16_potrf_inv2(g, lane, dinv), lane);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = 4 * j + q;
+        if (r >= c) Lb[(16 * p + c) * LS + 16 * p + r] = g[j];
+        if (r < c) Eb[p][r * ES + c] = g[j];
+        if (r == c) Eb[p][r * ES + c] = dinv;
+      }
+    }
+    __syncthreads();
+    // (3) TRSM of the tiles below (incl. the rhs block): X = T * E_pp
+    for (int ti = p + 1 + w2; ti <= NPt; ti += nw) {
+      v4f64 acc = (v4f64){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const double a = Eb[p][(lk + 4 * g) * ES + lr];
+        const double b = Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+      }
+      // all reads of this tile precede the writes within the wave
+#pragma unroll
+      for (int g = 0; g < 4; ++g) Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr] = acc[g];
+    }
+    __syncthreads();
+  }
+  // (4) L^T x = y by block back substitution (wave 0): y is row 0 of the rhs block,
+  //     x_p = E_pp (y_p - sum_{u>p} L_up^T x_u)
+  if (wv == 0) {
+    const int i = lr, q = lk;
+#pragma unroll
+    for (int p = NPt - 1; p >= 0; --p) {
+      double acc = 0.0;
+#pragma unroll
+      for (int u = p + 1; u < NPt; ++u)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const int row = 16 * u + 4 * q + rr;
+          acc += Lb[(16 * p + i) * LS + row] * xs[row];
+        }
+      acc += __shfl_xor(acc, 16, 64);
+      acc += __shfl_xor(acc, 32, 64);
+      const double wvv = Lb[(16 * p + i) * LS + nbt] - acc;
+      double px = 0.0;
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc) {
+        const int c2 = 4 * q + cc;
+        px += Eb[p][i * ES + c2] * __shfl(wvv, c2, 64);
+      }
+      px += __shfl_xor(px, 16, 64);
+      px += __shfl_xor(px, 32, 64);
+      if (q == 0) xs[16 * p + i] = px;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+  }
+}
+
+}  // namespace ba
+#endif  // BA_CHOL_LDS_H_

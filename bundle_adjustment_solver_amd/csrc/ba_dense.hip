@@ -15,6 +15,7 @@
 #include "ba_device.h"
 #include "ba_dense_sched.h"
 #include "ba_tile16.h"
+#include "ba_chol_lds.h"
 
 #include <cstdlib>
 #include <vector>
@@ -45,11 +46,6 @@ __global__ __launch_bounds__(256) void k_dense_init(double *L, int ld,
 }
 
 using tile16::readlane_f64;
-// dropped pivots are counted per handle (ba_get_dropped_pivots); the integer
-// atomic runs only when a factorisation actually meets one
-__device__ __forceinline__ void count_bad_pivots(int *bad, int n, int lane) {
-  if (bad && n > 0 && lane == 0) atomicAdd(bad, n);
-}
 
 #ifdef BA_DENSE_DBG
 __device__ long long g_dense_dbg[64];
@@ -83,9 +79,6 @@ extern "C" int ba_debug_read_dense(long long *out) {
 // factor_tile_lds (MFMA panel update and TRSM, wave 0 factors the 16x16
 // diagonal tiles), forward-substitutes the rhs as one more row tile, and runs
 // the block back substitution in the same launch; only x leaves.
-constexpr int kTailCols = 96;
-constexpr int kTailLS = kTailCols + 16 + 1;  // column stride of the LDS image (rows + rhs block + pad)
-constexpr int kTailES = 17;
 // NPt = 16-column panels of the block (compile time: the panel loops unroll and
 // their LDS reads pipeline; with run-time bounds the kernel was twice as slow).
 template <int NPt, bool PAIR>
@@ -100,8 +93,7 @@ __global__ __launch_bounds__(256) void k_chol_tail(const double *L, int ld, int 
   __shared__ double Eb[kTailCols / 16][16 * kTailES];    // Eb[p][k*ES + c] = E_pp[k][c], E_pp = L_pp^-T
   __shared__ double xs[kTailCols];
   constexpr int LS = kTailLS, ES = kTailES;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int lr = lane & 15, lk = lane >> 4;
+  const int tid = threadIdx.x;
   constexpr int nr = nbt + 16;  // rows of the LDS image; row tile NPt is the rhs block
   // the whole block is requested before anything waits (one load per
   // iteration followed by its LDS store would pay ~40 memory latencies in a row)
@@ -123,103 +115,7 @@ __global__ __launch_bounds__(256) void k_chol_tail(const double *L, int ld, int 
   }
   for (int e = tid; e < (kTailCols / 16) * 16 * ES; e += 256) (&Eb[0][0])[e] = 0.0;
   __syncthreads();
-  // Macro-steps.  PAIR: the first level of the block has TWO 32-column tiles
-  // (panels 0,1 and 2,3).  Tiles of one level are independent (the tile between
-  // them is structurally zero), so their panels are processed side by side:
-  // {0,2}, {1,3}, then 4, 5 — four sequential 16x16 factorisations instead of six.
-  constexpr int NG = PAIR ? NPt - 2 : NPt;
-#pragma unroll
-  for (int m = 0; m < NG; ++m) {
-    const int p0 = PAIR ? (m < 2 ? m : m + 2) : m;
-    const bool two = PAIR && m < 2;
-    // this wave's panel: waves 0,1 -> p0 and waves 2,3 -> p0 + 2 in a paired step
-    const int p = (two && wv >= 2) ? p0 + 2 : p0;
-    const int w2 = two ? (wv & 1) : wv, nw = two ? 2 : 4;
-    // columns that can contribute to panel p: from its own tile on in a paired
-    // step (the other tile's columns are zero in these rows), else all earlier ones
-    const int kc0 = two ? 32 * (p >> 1) : 0;
-    // (1) left-looking update: tile (ti,p) -= sum_kt L(ti,kt) L(p,kt)^T, ti = p .. NPt
-    if (m > 0) {
-      for (int ti = p + w2; ti <= NPt; ti += nw) {
-        v4f64 acc;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] = Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr];
-        for (int kc = kc0; kc < 16 * p; kc += 4) {
-          const double a = -Lb[(kc + lk) * LS + 16 * p + lr];
-          const double b = Lb[(kc + lk) * LS + 16 * ti + lr];
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr] = acc[g];
-      }
-      __syncthreads();
-    }
-    // (2) factor the diagonal tile(s): wave 0 (and wave 2 for the second panel of a paired step)
-    if (wv == 0 || (two && wv == 2)) {
-      const int r = lr, q = lk;
-      double g[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = 4 * j + q;
-        g[j] = (r >= c) ? Lb[(16 * p + c) * LS + 16 * p + r] : 0.0;
-      }
-      double dinv;
-      count_bad_pivots(bad, tile16::tile16_potrf_inv2(g, lane, dinv), lane);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = 4 * j + q;
-        if (r >= c) Lb[(16 * p + c) * LS + 16 * p + r] = g[j];
-        if (r < c) Eb[p][r * ES + c] = g[j];
-        if (r == c) Eb[p][r * ES + c] = dinv;
-      }
-    }
-    __syncthreads();
-    // (3) TRSM of the tiles below (incl. the rhs block): X = T * E_pp
-    for (int ti = p + 1 + w2; ti <= NPt; ti += nw) {
-      v4f64 acc = (v4f64){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const double a = Eb[p][(lk + 4 * g) * ES + lr];
-        const double b = Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr];
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-      }
-      // all reads of this tile precede the writes within the wave
-#pragma unroll
-      for (int g = 0; g < 4; ++g) Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr] = acc[g];
-    }
-    __syncthreads();
-  }
-  // (4) L^T x = y by block back substitution (wave 0): y is row 0 of the rhs block,
-  //     x_p = E_pp (y_p - sum_{u>p} L_up^T x_u)
-  if (wv == 0) {
-    const int i = lr, q = lk;
-#pragma unroll
-    for (int p = NPt - 1; p >= 0; --p) {
-      double acc = 0.0;
-#pragma unroll
-      for (int u = p + 1; u < NPt; ++u)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const int row = 16 * u + 4 * q + rr;
-          acc += Lb[(16 * p + i) * LS + row] * xs[row];
-        }
-      acc += __shfl_xor(acc, 16, 64);
-      acc += __shfl_xor(acc, 32, 64);
-      const double wvv = Lb[(16 * p + i) * LS + nbt] - acc;
-      double px = 0.0;
-#pragma unroll
-      for (int cc = 0; cc < 4; ++cc) {
-        const int c2 = 4 * q + cc;
-        px += Eb[p][i * ES + c2] * __shfl(wvv, c2, 64);
-      }
-      px += __shfl_xor(px, 16, 64);
-      px += __shfl_xor(px, 32, 64);
-      if (q == 0) xs[16 * p + i] = px;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-  }
+  chol_lds_factor_solve<NPt, PAIR, kTailLS>(Lb, Eb, xs, bad);
   __syncthreads();
   if (tid < nbt) {
     xc[c0 + tid] = xs[tid];

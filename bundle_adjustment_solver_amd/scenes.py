@@ -329,6 +329,22 @@ def pose_window_subscene(scene, p0, p1, n_fixed=5):
     return out
 
 
+def ba_batch_scene(B, n_pose=10, n_pt=300, stereo=True, seed=SEED_BASE + 9, pixel_sigma=0.0,
+                   n_fixed=2, pose_noise=0.05, point_noise=0.2):
+    """B independent window problems for the batched full-BA solver (ba_batch_*):
+    problem b is a synthetic scene of its own (synthetic_ba_scene, seed + 7919 * b) of
+    n_pose poses — the first n_fixed of them fixed at their true values — and n_pt
+    landmarks, every one seen by every pose in every camera, taken whole through
+    pose_window_subscene.  Returns a list of B scene dicts."""
+    out = []
+    for b in range(B):
+        big = synthetic_ba_scene(n_pose, n_pt, n_pose, stereo, seed + 7919 * b, n_fixed=n_fixed,
+                                 pixel_sigma=pixel_sigma, pose_noise=pose_noise,
+                                 point_noise=point_noise)
+        out.append(pose_window_subscene(big, 0, n_pose, n_fixed=n_fixed))
+    return out
+
+
 def scaled_problem(scene):
     """Apply the facade's host preprocessing (reference
     core/full_bundle_adjustment_solver.cpp:72-117,155-180): 0.01 scaling,

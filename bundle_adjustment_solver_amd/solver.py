@@ -982,6 +982,107 @@ class BaProblem:
                                    n_it, conv, cap, dbg)
 
 
+class BaBatch:
+    """B independent small full-BA problems solved in ONE launch, one persistent
+    workgroup each (ba_batch_* of include/ba_hip.h).  `problems`: a list of dicts in
+    the layout of scenes.scaled_problem (scaled units, problem-local indices).  The
+    structure is planned once; update_values + solve re-optimise new values.  Limits
+    per problem: 16 optimisable poses, 64 poses, 8 cameras (status 2 otherwise)."""
+
+    def __init__(self, problems, device=0):
+        self.lib = _lib.load()
+        self.b = None
+        self._owner = BaProblem(device)   # the handle: device and stream
+        self.B = len(problems)
+        cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate(
+            [np.asarray(p[key], dt).reshape((-1,) + w) for p in problems] or
+            [np.zeros((0,) + w, dt)], axis=0))
+        off = lambda key, dt: np.concatenate(
+            [[0], np.cumsum([len(p[key]) for p in problems])]).astype(dt)
+        self.cam_off = off("cam_intr", np.int32)
+        self.pose_off = off("pose_fixed", np.int32)
+        self.pt_off = off("pt_fixed", np.int32)
+        self.obs_off = off("obs_cam", np.int64)
+        a = dict(cam_intr=cat("cam_intr", np.float64, (4,)), cam_T=cat("cam_T", np.float64, (12,)),
+                 pose_T=cat("pose_T", np.float64, (12,)), pose_fixed=cat("pose_fixed", np.uint8, ()),
+                 pt_X=cat("pt_X", np.float64, (3,)), pt_fixed=cat("pt_fixed", np.uint8, ()),
+                 obs_cam=cat("obs_cam", np.int32, ()), obs_pose=cat("obs_pose", np.int32, ()),
+                 obs_pt=cat("obs_pt", np.int32, ()), obs_uv=cat("obs_uv", np.float64, (2,)))
+        self.n_pose, self.n_pt = a["pose_T"].shape[0], a["pt_X"].shape[0]
+        b = C.c_void_p()
+        check(self.lib.ba_batch_create(
+            C.byref(b), self._owner.h, self.B, _ip(self.cam_off), _ip(self.pose_off),
+            _ip(self.pt_off), self.obs_off.ctypes.data_as(C.POINTER(C.c_int64)),
+            _dp(a["cam_intr"]), _dp(a["cam_T"]), _dp(a["pose_T"]), _up(a["pose_fixed"]),
+            _dp(a["pt_X"]), _up(a["pt_fixed"]), _ip(a["obs_cam"]), _ip(a["obs_pose"]),
+            _ip(a["obs_pt"]), _dp(a["obs_uv"])), "ba_batch_create")
+        self.b = b
+
+    def close(self):
+        if self.b:
+            self.lib.ba_batch_destroy(self.b)
+            self.b = None
+        if self._owner is not None:
+            self._owner.close()
+            self._owner = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve(self, opt, cap=None):
+        """-> (rows, results): rows[p] = the logged ba_iter_info rows of problem p,
+        results[p] = its BaBatchResult."""
+        cap = max(1, opt.max_num_iterations) if cap is None else cap
+        rows = (BaIterInfo * max(1, self.B * cap))()
+        res = (_lib.BaBatchResult * self.B)()
+        check(self.lib.ba_batch_solve(self.b, C.byref(opt), rows, cap, res), "ba_batch_solve")
+        out = [[rows[p * cap + i] for i in range(min(res[p].n_rows, cap))]
+               for p in range(self.B)]
+        return out, [res[p] for p in range(self.B)]
+
+    def update_values(self, T_jw12=None, X3=None):
+        T = None if T_jw12 is None else np.ascontiguousarray(T_jw12, np.float64).reshape(-1, 12)
+        X = None if X3 is None else np.ascontiguousarray(X3, np.float64).reshape(-1, 3)
+        if T is not None and T.shape[0] != self.n_pose or X is not None and X.shape[0] != self.n_pt:
+            raise ValueError("update_values: the structure is fixed (same number of poses / points)")
+        check(self.lib.ba_batch_update_values(self.b, None if T is None else _dp(T),
+                                              None if X is None else _dp(X)),
+              "ba_batch_update_values")
+
+    def get_poses(self):
+        """every pose of the batch, concatenated user order [n_pose, 12]"""
+        T = np.zeros((self.n_pose, 12))
+        check(self.lib.ba_batch_get_poses(self.b, _dp(T)), "ba_batch_get_poses")
+        return T
+
+    def get_points(self):
+        X = np.zeros((self.n_pt, 3))
+        check(self.lib.ba_batch_get_points(self.b, _dp(X)), "ba_batch_get_points")
+        return X
+
+    def poses_of(self, p, T=None):
+        T = self.get_poses() if T is None else T
+        return T[self.pose_off[p]:self.pose_off[p + 1]]
+
+    def points_of(self, p, X=None):
+        X = self.get_points() if X is None else X
+        return X[self.pt_off[p]:self.pt_off[p + 1]]
+
+    def info(self):
+        o = (C.c_int64 * 8)()
+        check(self.lib.ba_batch_info(self.b, o), "ba_batch_info")
+        keys = ("scratch_bytes_max", "lds_bytes", "max_opt_poses", "max_poses", "max_cameras",
+                "image_columns", "device_bytes", "B")
+        out = dict(zip(keys, [int(v) for v in o]))
+        per = (C.c_int64 * self.B)()
+        check(self.lib.ba_batch_scratch_bytes(self.b, per), "ba_batch_scratch_bytes")
+        out["scratch_bytes"] = [int(v) for v in per]    # per problem
+        return out
+
+
 class BaStream:
     """Observation streaming (include/ba_hip.h ba_stream_*): the
     same problem-construction calls and LM loop as BaProblem for a problem whose
@@ -1442,12 +1543,74 @@ class FullBundleAdjustmentSolver:
         rows, converged = p.solve(c_opt)
         return self._finish_solve(rows, converged, summary, t0)
 
+    @staticmethod
+    def SolveBatch(solvers, options, summaries=None):
+        """Solve the registered problems of several solver objects in ONE launch
+        (ba_batch_solve: one persistent workgroup per problem, see BaBatch for the
+        limits), write every solver's poses and points back as Solve does and fill
+        one Summary each (summaries: a list as long as `solvers`, or None).  Returns
+        the per-problem BaBatchResult list; a problem whose status is not 0 (over a
+        limit, non-finite input) is left untouched."""
+        t0 = time.perf_counter()
+        solvers = list(solvers)
+        if not solvers:
+            return []
+        if summaries is not None and len(summaries) != len(solvers):
+            raise ValueError("SolveBatch: one Summary per solver")
+        if any(sv._shard[1] > 1 or sv._allreduce is not None for sv in solvers):
+            raise RuntimeError("SolveBatch: a solver with a shard or an all-reduce "
+                               "configured cannot be part of a batch")
+        probs = []
+        for sv in solvers:
+            intr, camT, T_jw, X, pf, qf, ocam, opose, opt, ouv = sv._host_arrays()
+            probs.append(dict(cam_intr=intr, cam_T=camT, pose_T=T_jw, pose_fixed=pf, pt_X=X,
+                              pt_fixed=qf, obs_cam=ocam, obs_pose=opose, obs_pt=opt, obs_uv=ouv))
+            sv.CheckPoseAndPointConnectivity()
+        c_opt = options.to_c()
+        c_opt.gauss_newton = 1 if solvers[0]._use_gauss_newton(options) else 0
+        batch = BaBatch(probs, solvers[0].device)
+        try:
+            rows, res = batch.solve(c_opt)
+            T_all, X_all = batch.get_poses(), batch.get_points()
+            for k, sv in enumerate(solvers):
+                summary = None if summaries is None else summaries[k]
+                if summary is not None:
+                    summary.max_iteration_ = options.iteration_handle.max_num_iterations
+                    summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change
+                    summary.threshold_step_size_ = options.convergence_handle.threshold_step_size
+                    summary.convergence_status_ = True
+                if res[k].status != 0:
+                    if summary is not None:
+                        summary.convergence_status_ = False
+                    continue
+                T_k, X_k = batch.poses_of(k, T_all).copy(), batch.points_of(k, X_all).copy()
+                sv._write_back(T_k, X_k, np.ones(X_k.shape[0], bool), rows[k],
+                               bool(res[k].converged), summary, t0)
+                # the registered values follow the solution, as after Solve
+                sv._pose_T_jw = [T_k]
+                sv._pt_X = [X_k]
+                if sv._problem is not None:
+                    sv._problem.update_values(sv._pose_T_jw[0], sv._pt_X[0])
+        finally:
+            batch.close()
+        return res
+
     def _finish_solve(self, rows, converged, summary, t0):
         """Write the solution back through the user's objects (reference
         :1011-1022) and fill the Summary rows; shared by Solve and
         FullBundleAdjustmentSolverRefactor.SolveByGradientDescent."""
         p = self._problem
         T_jw = p.get_poses()
+        if self._shard[1] > 1 and self._allreduce is not None:
+            # every rank writes back EVERY point (reference :1018-1022): one final
+            # sum-all-reduce of the owned rows
+            p.gather_points()
+        X, owned = p.get_points()
+        return self._write_back(T_jw, X, owned, rows, converged, summary, t0)
+
+    def _write_back(self, T_jw, X, owned, rows, converged, summary, t0):
+        """The second half of _finish_solve on given arrays (scaled units): T_jw
+        [n_pose, 12], X [n_pt, 3], owned = the points this rank may write."""
         T44 = _T12_to_44(T_jw)
         T44[:, :3, 3] *= INVERSE_SCALER
         T_wj = rigid_inverse(T44)
@@ -1458,11 +1621,6 @@ class FullBundleAdjustmentSolver:
                 obj[...] = T_wj[h]
             else:
                 obj[row] = T_wj[h]
-        if self._shard[1] > 1 and self._allreduce is not None:
-            # every rank writes back EVERY point (reference :1018-1022): one final
-            # sum-all-reduce of the owned rows
-            p.gather_points()
-        X, owned = p.get_points()
         Xu = X * INVERSE_SCALER
         opt_mask = np.ones(self.num_total_points_, bool)
         opt_mask[list(self._pt_fixed)] = False

@@ -76,6 +76,18 @@ class FullBundleAdjustmentSolver {
 
   bool Solve(Options options, Summary *summary = nullptr);
 
+  // (new) Solve the registered problems of several solver objects in ONE GPU launch
+  // (ba_batch_solve of include/ba_hip.h: one persistent workgroup per problem runs the
+  // whole LM loop; per problem at most 16 optimisable poses, 64 poses, 8 cameras).
+  // Every solver's poses and points are written back as Solve writes them and
+  // summaries (null, or resized to one Summary per solver) are filled.  A problem
+  // beyond a limit or with non-finite values is left untouched and its Summary reports
+  // convergence_status_ = false.  Returns true when every problem was solved.  The
+  // solvers need not be finalized and are not finalized by this call; the first
+  // solver's device is used.  Sharded solvers are refused (std::runtime_error).
+  static bool SolveBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, Options options,
+                         std::vector<Summary> *summaries = nullptr);
+
   // (new) Read the CURRENT values behind every registered pose / point pointer again
   // and hand them to the finalized problem (ba_update_values): re-optimising the same
   // graph with new values costs no second FinalizeParameters.  The reference keeps its
@@ -113,6 +125,12 @@ class FullBundleAdjustmentSolver {
   // write-back and Summary as Solve)
   friend class FullBundleAdjustmentSolverRefactor;
   bool Run(Options options, Summary *summary, bool gradient_descent);
+  // the solved values (scaled units, 12 doubles per pose, 3 per point) into the kept
+  // copies and through the caller's pointers (:1011-1022); fixed members and points with
+  // valid[q] == 0 are skipped.  Shared by Run and SolveBatch.
+  void WriteBack(const double *T_jw12, const double *X3, const uint8_t *valid);
+  // the options' thresholds and iteration limit into a Summary (nullptr: nothing)
+  static void BeginSummary(Summary *summary, const Options &options);
   // stderr warnings about weakly connected poses / points (reference
   // core/full_bundle_adjustment_solver.cpp:310-341), called by Solve
   void CheckPoseAndPointConnectivity();

@@ -292,6 +292,60 @@ void FullBundleAdjustmentSolver::CheckPoseAndPointConnectivity() {  // :310-341
   }
 }
 
+namespace {
+
+ba_options PackOptions(const Options &options, bool gauss_newton) {
+  ba_options o;
+  o.threshold_step_size = options.convergence_handle.threshold_step_size;
+  o.threshold_cost_change = options.convergence_handle.threshold_cost_change;
+  o.threshold_huber_loss = options.outlier_handle.threshold_huber_loss;
+  o.threshold_outlier_rejection = options.outlier_handle.threshold_outlier_rejection;
+  o.max_num_iterations = options.iteration_handle.max_num_iterations;
+  o.initial_lambda = options.trust_region_handle.initial_lambda;
+  o.decrease_ratio_lambda = options.trust_region_handle.decrease_ratio_lambda;
+  o.increase_ratio_lambda = options.trust_region_handle.increase_ratio_lambda;
+  o.gauss_newton = gauss_newton ? 1 : 0;
+  return o;
+}
+
+OptimizationInfo ToInfo(const ba_iter_info &row) {
+  OptimizationInfo info;
+  info.cost = row.cost;
+  info.cost_change = row.cost_change;
+  info.average_reprojection_error = row.average_reprojection_error;
+  info.abs_step = row.abs_step;
+  info.abs_gradient = 0;
+  info.damping_term = row.damping_term;
+  info.iter_time = row.iter_time_ms;
+  info.iteration_status = static_cast<IterationStatus>(row.iteration_status);
+  return info;
+}
+
+}  // namespace
+
+void FullBundleAdjustmentSolver::BeginSummary(Summary *summary, const Options &options) {
+  if (summary == nullptr) return;
+  summary->max_iteration_ = options.iteration_handle.max_num_iterations;
+  summary->threshold_cost_change_ = options.convergence_handle.threshold_cost_change;
+  summary->threshold_step_size_ = options.convergence_handle.threshold_step_size;
+  summary->convergence_status_ = true;
+}
+
+void FullBundleAdjustmentSolver::WriteBack(const double *T_jw12, const double *X3, const uint8_t *valid) {
+  for (size_t p = 0; p < poses_.size(); ++p) {
+    if (fixed_poses_.count(static_cast<int>(p))) continue;
+    _BA_Pose T_jw = Unpack12(&T_jw12[12 * p]);
+    T_jw_[p] = T_jw;
+    T_jw.translation() *= inverse_scaler_;
+    *poses_[p] = T_jw.inverse();
+  }
+  for (size_t q = 0; q < points_.size(); ++q) {
+    if (fixed_points_.count(static_cast<int>(q)) || !valid[q]) continue;
+    X_[q] = _BA_Point(X3[3 * q], X3[3 * q + 1], X3[3 * q + 2]);
+    *points_[q] = X_[q] * inverse_scaler_;
+  }
+}
+
 bool FullBundleAdjustmentSolver::Solve(Options options, Summary *summary) {  // :630-1044
   return Run(options, summary, false);
 }
@@ -302,26 +356,12 @@ bool FullBundleAdjustmentSolver::Solve(Options options, Summary *summary) {  // 
 bool FullBundleAdjustmentSolver::Run(Options options, Summary *summary, bool gradient_descent) {
   timer::StopWatch stopwatch("BundleAdjustmentSolver::Solve");
   stopwatch.Start();
-  if (summary != nullptr) {
-    summary->max_iteration_ = options.iteration_handle.max_num_iterations;
-    summary->threshold_cost_change_ = options.convergence_handle.threshold_cost_change;
-    summary->threshold_step_size_ = options.convergence_handle.threshold_step_size;
-    summary->convergence_status_ = true;
-  }
+  BeginSummary(summary, options);
   FinalizeParameters();
   if (verbose_) GetSolverStatistics();
   CheckPoseAndPointConnectivity();  // :703
 
-  ba_options o;
-  o.threshold_step_size = options.convergence_handle.threshold_step_size;
-  o.threshold_cost_change = options.convergence_handle.threshold_cost_change;
-  o.threshold_huber_loss = options.outlier_handle.threshold_huber_loss;
-  o.threshold_outlier_rejection = options.outlier_handle.threshold_outlier_rejection;
-  o.max_num_iterations = options.iteration_handle.max_num_iterations;
-  o.initial_lambda = options.trust_region_handle.initial_lambda;
-  o.decrease_ratio_lambda = options.trust_region_handle.decrease_ratio_lambda;
-  o.increase_ratio_lambda = options.trust_region_handle.increase_ratio_lambda;
-  o.gauss_newton = gauss_newton_ ? 1 : 0;
+  const ba_options o = PackOptions(options, gauss_newton_);
   std::vector<ba_iter_info> rows(static_cast<size_t>(std::max(1, o.max_num_iterations)));
   int n_iter = 0, converged = 0;
   if (gradient_descent)
@@ -341,35 +381,98 @@ bool FullBundleAdjustmentSolver::Run(Options options, Summary *summary, bool gra
     Check(ba_gather_points(handle_), "ba_gather_points");
     Check(ba_get_points(handle_, X.data(), valid.data()), "ba_get_points");
   }
-  for (size_t p = 0; p < poses_.size(); ++p) {
-    if (fixed_poses_.count(static_cast<int>(p))) continue;
-    _BA_Pose T_jw = Unpack12(&T[12 * p]);
-    T_jw_[p] = T_jw;
-    T_jw.translation() *= inverse_scaler_;
-    *poses_[p] = T_jw.inverse();
-  }
-  for (size_t q = 0; q < points_.size(); ++q) {
-    if (fixed_points_.count(static_cast<int>(q)) || !valid[q]) continue;
-    X_[q] = _BA_Point(X[3 * q], X[3 * q + 1], X[3 * q + 2]);
-    *points_[q] = X_[q] * inverse_scaler_;
-  }
+  WriteBack(T.data(), X.data(), valid.data());
   if (summary != nullptr) {
-    for (int k = 0; k < n_iter && k < static_cast<int>(rows.size()); ++k) {
-      OptimizationInfo info;
-      info.cost = rows[k].cost;
-      info.cost_change = rows[k].cost_change;
-      info.average_reprojection_error = rows[k].average_reprojection_error;
-      info.abs_step = rows[k].abs_step;
-      info.abs_gradient = 0;
-      info.damping_term = rows[k].damping_term;
-      info.iter_time = rows[k].iter_time_ms;
-      info.iteration_status = static_cast<IterationStatus>(rows[k].iteration_status);
-      summary->optimization_info_list_.push_back(info);
-    }
+    for (int k = 0; k < n_iter && k < static_cast<int>(rows.size()); ++k)
+      summary->optimization_info_list_.push_back(ToInfo(rows[k]));
     summary->convergence_status_ = converged != 0;
     summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
   }
   return true;  // the reference always returns true (:1043)
+}
+
+bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, Options options,
+                                            std::vector<Summary> *summaries) {
+  timer::StopWatch stopwatch("BundleAdjustmentSolver::SolveBatch");
+  stopwatch.Start();
+  const int B = static_cast<int>(solvers.size());
+  if (summaries != nullptr) summaries->assign(static_cast<size_t>(B), Summary());
+  if (B == 0) return true;
+  std::vector<int32_t> cam_off(1, 0), pose_off(1, 0), pt_off(1, 0), oc, op, oq;
+  std::vector<int64_t> obs_off(1, 0);
+  std::vector<double> intr, T_cj, T, X, uv;
+  std::vector<uint8_t> pose_fixed, point_fixed;
+  for (FullBundleAdjustmentSolver *s : solvers) {
+    if (s == nullptr) throw std::runtime_error("SolveBatch: null solver");
+    if (s->shard_world_ > 1 || s->allreduce_fn_) throw std::runtime_error("SolveBatch: a sharded solver cannot join a batch");
+    if (s->cameras_.empty() || s->poses_.empty() || s->points_.empty())
+      throw std::runtime_error("SolveBatch: cameras, poses and points must be added first");
+    s->CheckPoseAndPointConnectivity();
+    for (size_t c = 0; c < s->cameras_.size(); ++c) {
+      intr.insert(intr.end(), {s->cameras_[c].fx, s->cameras_[c].fy, s->cameras_[c].cx, s->cameras_[c].cy});
+      T_cj.resize(T_cj.size() + 12);
+      Pack12(s->cameras_[c].pose_this_to_cam0, &T_cj[T_cj.size() - 12]);
+    }
+    for (size_t p = 0; p < s->poses_.size(); ++p) {
+      T.resize(T.size() + 12);
+      Pack12(s->T_jw_[p], &T[T.size() - 12]);
+      pose_fixed.push_back(s->fixed_poses_.count(static_cast<int>(p)) > 0);
+    }
+    for (size_t q = 0; q < s->points_.size(); ++q) {
+      for (int r = 0; r < 3; ++r) X.push_back(s->X_[q](r));
+      point_fixed.push_back(s->fixed_points_.count(static_cast<int>(q)) > 0);
+    }
+    for (const Observation &o : s->observations_) {  // insertion order matters (:826)
+      oc.push_back(o.camera_index);
+      op.push_back(o.pose_index);
+      oq.push_back(o.point_index);
+      uv.push_back(o.u);
+      uv.push_back(o.v);
+    }
+    cam_off.push_back(static_cast<int32_t>(intr.size() / 4));
+    pose_off.push_back(static_cast<int32_t>(pose_fixed.size()));
+    pt_off.push_back(static_cast<int32_t>(point_fixed.size()));
+    obs_off.push_back(static_cast<int64_t>(oc.size()));
+  }
+  const ba_options o = PackOptions(options, solvers[0]->gauss_newton_);
+  const int cap = std::max(1, o.max_num_iterations);
+  std::vector<ba_iter_info> rows(static_cast<size_t>(B) * cap);
+  std::vector<ba_batch_result> res(static_cast<size_t>(B));
+  ba_handle *h = nullptr;
+  ba_batch *batch = nullptr;
+  Check(ba_create(&h, solvers[0]->device_id_), "ba_create");
+  int rc = ba_batch_create(&batch, h, B, cam_off.data(), pose_off.data(), pt_off.data(), obs_off.data(), intr.data(),
+                           T_cj.data(), T.data(), pose_fixed.data(), X.data(), point_fixed.data(), oc.data(), op.data(),
+                           oq.data(), uv.data());
+  if (rc == 0) rc = ba_batch_solve(batch, &o, rows.data(), cap, res.data());
+  if (rc == 0) rc = ba_batch_get_poses(batch, T.data());
+  if (rc == 0) rc = ba_batch_get_points(batch, X.data());
+  const std::string err = rc ? ba_last_error() : "";
+  ba_batch_destroy(batch);
+  ba_destroy(h);
+  if (rc) throw std::runtime_error("SolveBatch failed: " + err);
+  bool all_solved = true;
+  for (int b = 0; b < B; ++b) {
+    FullBundleAdjustmentSolver *s = solvers[b];
+    Summary *summary = summaries ? &(*summaries)[b] : nullptr;
+    BeginSummary(summary, options);
+    if (summary != nullptr) summary->convergence_status_ = res[b].status == 0 && res[b].converged != 0;
+    if (res[b].status != 0) {
+      all_solved = false;
+      continue;
+    }
+    const double *Tb = &T[12 * static_cast<size_t>(pose_off[b])], *Xb = &X[3 * static_cast<size_t>(pt_off[b])];
+    const std::vector<uint8_t> valid(s->points_.size(), 1);
+    s->WriteBack(Tb, Xb, valid.data());
+    // a finalized solver continues from the solution, as after Solve
+    if (s->is_parameter_finalized_) Check(ba_update_values(s->handle_, Tb, Xb), "ba_update_values");
+    if (summary != nullptr) {
+      for (int k = 0; k < res[b].n_rows && k < cap; ++k)
+        summary->optimization_info_list_.push_back(ToInfo(rows[static_cast<size_t>(b) * cap + k]));
+      summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
+    }
+  }
+  return all_solved;
 }
 
 }  // namespace analytic_solver

@@ -521,6 +521,92 @@ int ba_pose_only_stereo3_batch_device(ba_handle *h, int B,
 int ba_planar_record(const float *T_bc12, const float *T_wl12, const float *T12,
                      const float *T_lr12, const float *intr_r4, float *rec52);
 
+/* ---- batched full bundle adjustment: many small windows in one launch ------- */
+/* B independent full-BA problems (sliding windows of a few poses and a few hundred
+ * landmarks), ONE persistent 256-thread workgroup each: the whole LM loop of Solve
+ * (reference :705-1008) — linearisation and damping, Schur complement, reduced solve,
+ * back-substitution and trial update, trial cost, model change and trust-region control —
+ * runs in fp64 inside one launch, nothing is launched between iterations and no workgroup
+ * waits on another (any B: a batch larger than the device holds at once drains).  The
+ * arithmetic and every semantic of ba_solve carry over (Huber weights, the last-writer
+ * rule for a (landmark, pose) pair observed more than once — observation order inside a
+ * problem is significant —, multiplicative damping, the 3x3 inverse with its pivoted
+ * fallback, unpivoted Cholesky that zeroes and counts non-positive pivots, the quadratic
+ * model on the damped blocks, previous_cost advanced on SKIPPED, "never converged on the
+ * last allowed iteration", gauss_newton).  No floating-point atomics, fixed summation
+ * order: a problem gives the same bits run to run, alone (B = 1) and at any position of
+ * any batch; its sums are ordered differently from the handle path's, so the two agree to
+ * rounding, not bit for bit.
+ *
+ * Limits per problem (ba_batch_info reports them): at most 16 optimisable poses (6N <= 96
+ * columns: the reduced system is factored in LDS), at most 64 poses in all (accepted and
+ * trial transforms live in LDS), at most 8 cameras; any number of landmarks and
+ * observations (per-landmark blocks, pair records and trial points live in a per-problem
+ * slice of device scratch allocated at creation).  A problem beyond a limit is NOT solved
+ * and reports status 2; every other problem of the batch is solved as if it were absent.
+ *
+ * The object follows the ba_finalize / ba_update_values split: ba_batch_create plans the
+ * structure once (per problem: observations grouped landmark-major with a stable sort,
+ * pair lists, last-writer marks) and uploads everything with one copy; values can be
+ * replaced and re-solved.  Units and layouts are those of ba_set_*: scaled units, 16-double
+ * cameras given as intr4 + T_cj12, 12-double T_jw, problem-LOCAL indices in the
+ * observations.  Problem p owns cameras [cam_off[p], cam_off[p+1]), poses, points and
+ * observations likewise (B+1 offsets each, starting at 0, never decreasing).  The handle
+ * provides the device and the stream; a sharded handle (ba_set_shard world > 1 or an
+ * all-reduce hook) or a streamed one is refused, and there is no batched gradient descent.
+ * Validation (B >= 1, offsets, indices within their problem, then the handle) happens
+ * before anything touches the GPU: -1 and ba_last_error.
+ *
+ * Lifetime: the batch borrows the handle's device and stream and owns no part of it.  The
+ * handle must outlive the batch: ba_batch_destroy first, ba_destroy after; every call on a
+ * batch whose handle is gone is undefined. */
+typedef struct ba_batch ba_batch;
+typedef struct {
+  int n_iter, converged, n_rows, status, dropped_pivots;
+  /* n_rows = rows logged (rows stored: min(n_rows, cap)); status: 0 = solved, 1 = a pose or
+   * point of the problem is not finite on entry (its values are left as given; under LM a
+   * non-finite trial cost rejects the step, so values cannot become non-finite later),
+   * 2 = over a limit, not solved; dropped_pivots = non-positive pivots the problem's
+   * factorisations met (what ba_get_dropped_pivots counts for a handle) */
+} ba_batch_result;
+int ba_batch_create(ba_batch **out, ba_handle *h, int B, const int32_t *cam_off,
+                    const int32_t *pose_off, const int32_t *pt_off,
+                    const int64_t *obs_off, const double *cam_intr4,
+                    const double *cam_T12, const double *pose_T12,
+                    const uint8_t *pose_fixed, const double *pt_X3,
+                    const uint8_t *pt_fixed, const int32_t *obs_cam,
+                    const int32_t *obs_pose, const int32_t *obs_pt,
+                    const double *obs_uv2);
+void ba_batch_destroy(ba_batch *b);
+/* One ba_options for the whole batch; problem p gets rows + p*cap (rows may be NULL).
+ * max_num_iterations <= 0: nothing changes, converged, no rows.  One launch and one
+ * synchronisation on the handle's stream.  The solved values stay in the object: a
+ * following ba_batch_solve starts from them.  Returns 0 when every problem was processed,
+ * whatever its status. */
+int ba_batch_solve(ba_batch *b, const ba_options *opt, ba_iter_info *rows, int cap,
+                   ba_batch_result *res);
+/* new values for the same structure, concatenated user order; NULL = keep */
+int ba_batch_update_values(ba_batch *b, const double *T_jw12, const double *X3);
+int ba_batch_get_poses(ba_batch *b, double *T_jw12);
+int ba_batch_get_points(ba_batch *b, double *X3);
+/* out8 = { device scratch bytes of the largest problem, LDS bytes of a workgroup, limit
+ * of optimisable poses, of poses, of cameras per problem, columns of the LDS image chosen
+ * for this batch (32, 64 or 96), device bytes of the whole object, B } */
+int ba_batch_info(ba_batch *b, int64_t out8[8]);
+/* bytes[p], p < B = device scratch bytes of problem p: the blocks C, b, Cinv, Cinv*b of its
+ * optimisable landmarks, the W records of its pairs and its trial points */
+int ba_batch_scratch_bytes(ba_batch *b, int64_t *bytes);
+/* Host-only (no GPU): the structure ba_batch_create plans for ONE problem.  order[t] =
+ * input index of the t-th observation of the landmark-major list (stable), obs_pair[t] =
+ * its pair or -1 (pose or point fixed), last_writer[t] = 1 where its cross block survives;
+ * pair_lm / pair_pose = optimisable landmark / pose of every pair.  Any output may be NULL.
+ * Returns the number of pairs, or -1. */
+int ba_batch_plan_problem(int n_pose, const uint8_t *pose_fixed, int n_pt,
+                          const uint8_t *pt_fixed, int64_t n_obs,
+                          const int32_t *obs_pose, const int32_t *obs_pt,
+                          int32_t *order, int32_t *obs_pair, uint8_t *last_writer,
+                          int32_t *pair_lm, int32_t *pair_pose);
+
 #ifdef __cplusplus
 }
 #endif
