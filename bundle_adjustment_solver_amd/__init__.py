@@ -8,7 +8,8 @@ package does not touch the GPU, creating a solver does.
 from .solver import (BaProblem, Camera, FullBundleAdjustmentSolver,  # noqa
                      FullBundleAdjustmentSolverRefactor,
                      IterationStatus, OptimizationInfo, Options,
-                     PoseOnlyBundleAdjustmentSolver, SolverType, Summary)
+                     PoseOnlyBundleAdjustmentSolver, SolverType, Summary,
+                     covariance_to_user_units)
 from . import scenes  # noqa
 from . import scene_io  # noqa
 
@@ -16,4 +17,4 @@ __all__ = ["BaProblem", "Camera", "FullBundleAdjustmentSolver",
            "FullBundleAdjustmentSolverRefactor",
            "IterationStatus", "OptimizationInfo", "Options",
            "PoseOnlyBundleAdjustmentSolver", "SolverType", "Summary",
-           "scenes", "scene_io"]
+           "covariance_to_user_units", "scenes", "scene_io"]

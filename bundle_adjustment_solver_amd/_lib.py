@@ -179,6 +179,11 @@ SIGNATURES = {
     "ba_get_mask_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "ba_get_dropped_pivots": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
     "ba_dense_spd_solve": (C.c_int, [_P, C.c_int, _D, _D, _D, _D]),
+    "ba_covariance": (C.c_int, [_P, C.c_double, C.c_int, _I32, _D, C.c_int, _I32, _D,
+                                C.POINTER(C.c_int64)]),
+    "ba_covariance_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "ba_covariance_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _U8, C.c_int, _U8,
+                                      C.c_int, _I32, _D, C.c_int, _I32, _D]),
     "ba_pose_only_mono6": (C.c_int, [_P, _F, _F, C.c_int, C.c_float, C.c_float,
                                      C.c_float, C.c_float, _F, _U8,
                                      C.POINTER(BaOptions), C.POINTER(BaPoIter),

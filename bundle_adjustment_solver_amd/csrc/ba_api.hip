@@ -1597,6 +1597,194 @@ int ba_dense_spd_solve(ba_handle *h, int n, const double *A, const double *b,
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// covariance blocks (kernels: ba_cov.hip)
+int ba_covariance_check(int finalized, int sharded, int streamed, int n_pose, const uint8_t *pose_fixed,
+                        int n_pt, const uint8_t *pt_fixed, int n_pose_sel, const int32_t *pose_sel,
+                        const double *cov_pose36, int n_pt_sel, const int32_t *pt_sel,
+                        const double *cov_pt9) {
+  if (!finalized) return fail("ba_covariance: the handle is not finalized");
+  if (sharded) return fail("ba_covariance: sharded handles (ba_set_shard world > 1, or an all-reduce hook) are not supported");
+  if (streamed) return fail("ba_covariance: streamed handles are not supported");
+  if (n_pose_sel < 0 || n_pt_sel < 0) return fail("ba_covariance: negative selection size");
+  if (n_pose_sel > 0 && !pose_sel) return fail("ba_covariance: pose_sel is NULL for a non-empty selection");
+  if (n_pt_sel > 0 && !pt_sel) return fail("ba_covariance: pt_sel is NULL for a non-empty selection");
+  if (n_pose_sel > 0 && !cov_pose36) return fail("ba_covariance: cov_pose36 is NULL for a non-empty pose selection");
+  if (n_pt_sel > 0 && !cov_pt9) return fail("ba_covariance: cov_pt9 is NULL for a non-empty point selection");
+  for (int s = 0; s < n_pose_sel; ++s) {
+    const int u = pose_sel[s];
+    if (u < 0 || u >= n_pose)
+      return fail("ba_covariance: pose_sel[" + std::to_string(s) + "] = " + std::to_string(u) + " is out of range");
+    if (pose_fixed && pose_fixed[u])
+      return fail("ba_covariance: pose_sel[" + std::to_string(s) + "] = " + std::to_string(u) + " is a fixed pose");
+  }
+  for (int s = 0; s < n_pt_sel; ++s) {
+    const int u = pt_sel[s];
+    if (u < 0 || u >= n_pt)
+      return fail("ba_covariance: pt_sel[" + std::to_string(s) + "] = " + std::to_string(u) + " is out of range");
+    if (pt_fixed && pt_fixed[u])
+      return fail("ba_covariance: pt_sel[" + std::to_string(s) + "] = " + std::to_string(u) + " is a fixed point");
+  }
+  return 0;
+}
+
+// Columns of one batch for an image of npad rows: what fits 256 MiB of workspace, at most
+// 1024 waves' worth, a multiple of the 16 columns of a wave; BA_COV_BATCH overrides.
+static int cov_batch_cols(int npad) {
+  int64_t cols = ((int64_t)256 << 20) / (8 * (int64_t)std::max(npad, 1));
+  if (const char *e = getenv("BA_COV_BATCH")) cols = atoll(e);
+  cols = std::min<int64_t>(cols, 1024 * ba::kCovGroupCols);
+  return (int)std::max<int64_t>(ba::kCovGroupCols, cols / ba::kCovGroupCols * ba::kCovGroupCols);
+}
+
+int ba_covariance_info(ba_handle *h, int64_t out4[4]) {
+  if (!h || !h->finalized || !out4) return fail("ba_covariance_info: bad argument");
+  const int bw = cov_batch_cols(h->d.npad);
+  out4[0] = bw;
+  out4[1] = ba::kCovGroupCols;
+  out4[2] = (int64_t)h->d.npad * bw * (int64_t)sizeof(double);
+  out4[3] = h->cov_batches;
+  return 0;
+}
+
+int ba_covariance(ba_handle *h, double huber, int n_pose_sel, const int32_t *pose_sel, double *cov_pose36,
+                  int n_pt_sel, const int32_t *pt_sel, double *cov_pt9, int64_t *dropped_pivots) {
+  if (!h) return fail("ba_covariance: null handle");
+  if (ba_covariance_check(h->finalized, h->world > 1 || h->ar_fn != nullptr,
+                          h->arena != nullptr || h->dense_owner != nullptr, h->n_pose,
+                          h->pose_fixed.data(), h->n_pt, h->pt_fixed.data(), n_pose_sel, pose_sel,
+                          cov_pose36, n_pt_sel, pt_sel, cov_pt9))
+    return -1;
+  if (use_device(h)) return -1;
+  const ba::Plan &pl = h->plan;
+  const ba::DevProblem &d = h->d;
+  const ba::DenseSchedule &sc = h->sched;
+  const int nb = d.nb, ncb = sc.ncb;
+  // ---- distinct items, ordered by the tile of their first non-zero row, in groups of one wave
+  struct Item {
+    int t0, key, idx;
+  };
+  auto distinct = [](std::vector<Item> &v) {
+    std::sort(v.begin(), v.end(), [](const Item &a, const Item &b) {
+      return a.t0 != b.t0 ? a.t0 < b.t0 : a.key != b.key ? a.key < b.key : a.idx < b.idx;
+    });
+    v.erase(std::unique(v.begin(), v.end(), [](const Item &a, const Item &b) { return a.idx == b.idx; }), v.end());
+  };
+  std::vector<Item> poses, pts;
+  for (int s = 0; s < n_pose_sel; ++s) {
+    const int j = pl.jopt_of_user[pose_sel[s]];
+    poses.push_back({h->pose_col_h[j] / nb, h->pose_col_h[j], j});
+  }
+  for (int s = 0; s < n_pt_sel; ++s) {
+    const int i = pl.pt_int_of_user[pt_sel[s]];
+    if (i < 0 || i >= pl.M) return fail("ba_covariance: pt_sel[" + std::to_string(s) + "] is not an optimisable point of this handle");
+    int t0 = ncb;  // (no pairs: zero right-hand side, nothing to sweep)
+    for (int64_t p = pl.lm_pair_ptr[i]; p < pl.lm_pair_ptr[i + 1]; ++p)
+      t0 = std::min(t0, h->pose_col_h[pl.pair_pose[p]] / nb);
+    pts.push_back({t0, i, i});
+  }
+  distinct(poses);
+  distinct(pts);
+  std::vector<int> slot_pose(pl.N, -1), slot_pt(pl.M, -1);
+  std::vector<ba::CovGroup> groups;
+  auto make_groups = [&](const std::vector<Item> &v, int kind, int per, std::vector<int> &slot) {
+    for (size_t k = 0; k < v.size(); k += per) {
+      ba::CovGroup g{};
+      g.kind = kind;
+      g.n = (int)std::min<size_t>(per, v.size() - k);
+      g.t0 = v[k].t0;
+      for (int a = 0; a < g.n; ++a) {
+        g.item[a] = v[k + a].idx;
+        g.slot[a] = slot[v[k + a].idx] = (int)(k + a);
+      }
+      groups.push_back(g);
+    }
+  };
+  make_groups(poses, 0, 2, slot_pose);
+  make_groups(pts, 1, 5, slot_pt);
+  // per tile position: the positions left of it with a non-zero factor tile
+  std::vector<int> trow_ptr((size_t)ncb + 1, 0), trow;
+  {
+    std::vector<std::vector<int>> by_row((size_t)ncb);
+    for (int p = 0; p < ncb; ++p)
+      for (int a = sc.row_ptr[p]; a < sc.row_ptr[p + 1]; ++a)
+        if (sc.rows[a] < ncb) by_row[sc.rows[a]].push_back(p);
+    for (int t = 0; t < ncb; ++t) {
+      trow.insert(trow.end(), by_row[t].begin(), by_row[t].end());
+      trow_ptr[t + 1] = (int)trow.size();
+    }
+  }
+  // ---- linearise at lambda = 0, Schur complement, scatter, factorise (the stage calls' launches)
+  join_side(h);
+  if (pull_ctrl(h)) return -1;
+  const ba::DevCtrl keep = h->hc;
+  h->hc.done = 0;
+  h->hc.lambda = 0.0;
+  h->hc.huber = huber;
+  if (push_ctrl(h)) return -1;
+  int bad_keep = 0, bad_now = 0;
+  // (the stream is idle: pull_ctrl synchronised it)  the LM loop's count of dropped pivots is set
+  // aside, this call's factorisation counts from zero, and the loop's count comes back below
+  HIP_TRY(hipMemcpy(&bad_keep, h->ddev.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemsetAsync(h->ddev.bad_pivots, 0, sizeof(int), h->stream));
+  enqueue_linearize(h, 0);
+  ba::launch_damp_invert_export(d, h->stream);  // Cinv_i as an array, whatever Schur path the plan uses
+  ba::launch_schur(d, /*direct=*/false, /*with_init=*/true, h->stream);
+  ba::launch_scatter(d, h->stream);
+  {
+    // k_chol_tail keeps its block's factor in LDS (only x leaves): here every level takes
+    // the per-level kernels, which leave the whole factor in the image.  Same arithmetic.
+    ba::DenseDev dd = h->ddev;
+    dd.want_tail = false;
+    ba::dense_factor_solve(d.L, d.npad, d.ld, d.Ldiag, d.x, &d.ctrl->done, sc, dd, h->stream);
+    h->ddev.flow_gen = dd.flow_gen;
+  }
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(&bad_now, h->ddev.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->ddev.bad_pivots, &bad_keep, sizeof(int), hipMemcpyHostToDevice));
+  h->hc = keep;  // the controller as it was: lambda, huber, done, the log position
+  if (push_ctrl(h)) return -1;
+  // ---- the batches; everything below is freed again on every return
+  struct Scratch {
+    ba_handle *h;
+    size_t mark;
+    int kind;
+    ~Scratch() {
+      for (size_t k = mark; k < h->allocs.size(); ++k) (void)hipFree(h->allocs[k]);
+      h->allocs.resize(mark);
+      h->alloc_kind = kind;
+    }
+  } scratch{h, h->allocs.size(), h->alloc_kind};
+  h->alloc_kind = 0;
+  const int bw_max = cov_batch_cols(d.npad);
+  const int gpb = bw_max / ba::kCovGroupCols;  // groups per batch
+  const int bw = (int)std::min<size_t>(gpb, std::max<size_t>(1, groups.size())) * ba::kCovGroupCols;
+  int *d_trow_ptr = nullptr, *d_trow = nullptr;
+  ba::CovGroup *d_groups = nullptr;
+  double *Zw = nullptr, *d_pose = nullptr, *d_pt = nullptr;
+  if (h->upload(&d_trow_ptr, trow_ptr) || h->upload(&d_trow, trow) || h->upload(&d_groups, groups) ||
+      h->dalloc(&Zw, (size_t)d.npad * bw) || h->dalloc(&d_pose, poses.size() * 36) ||
+      h->dalloc(&d_pt, pts.size() * 9))
+    return -1;
+  h->cov_batches = 0;
+  for (size_t g0 = 0; g0 < groups.size(); g0 += gpb) {  // fixed batch order
+    const int ng = (int)std::min<size_t>(gpb, groups.size() - g0);
+    ba::launch_cov_batch(d, keep.lcur, ncb, d_trow_ptr, d_trow, d_groups + g0, ng, Zw, bw, d_pose, d_pt, h->stream);
+    ++h->cov_batches;
+  }
+  std::vector<double> hp, hq;
+  if (download(hp, d_pose, poses.size() * 36, h->stream) || download(hq, d_pt, pts.size() * 9, h->stream)) return -1;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  if (bad_now >= ba::kFlowTimeout) return fail("ba_covariance: a dataflow hand-off of the factorisation timed out");
+  for (int s = 0; s < n_pose_sel; ++s)
+    std::memcpy(cov_pose36 + (size_t)s * 36, &hp[(size_t)slot_pose[pl.jopt_of_user[pose_sel[s]]] * 36], 36 * sizeof(double));
+  for (int s = 0; s < n_pt_sel; ++s)
+    std::memcpy(cov_pt9 + (size_t)s * 9, &hq[(size_t)slot_pt[pl.pt_int_of_user[pt_sel[s]]] * 9], 9 * sizeof(double));
+  if (dropped_pivots) *dropped_pivots = bad_now;
+  return 0;
+}
+
 }  // extern "C" (reopened below)
 
 // One call = one H2D copy, one kernel, one D2H copy, all through ONE pinned

@@ -377,6 +377,26 @@ void launch_dense_init(double *L, int ld, const int *col_x, const int *zt_I,
                        const int *zt_J, int n_zt, int nb, const int *done_flag,
                        hipStream_t s);
 
+// ---- covariance blocks (ba_cov.hip) ----
+// One wave of k_cov_solve owns kCovGroupCols right-hand sides: two poses (kind 0, six
+// identity columns each) or five landmarks (kind 1, three columns each).  item = optimised
+// pose / internal landmark index, slot = row of the output array, t0 = tile position of
+// the first non-zero row of the group's right-hand sides (ncb: none).
+constexpr int kCovGroupCols = 16;
+struct CovGroup {
+  int32_t t0, kind, n, pad_;
+  int32_t item[5], slot[5];
+  int32_t pad2_[2];
+};
+static_assert(sizeof(CovGroup) == 64, "CovGroup is one 64-byte record");
+// One column batch on the factored image of d (d.L, d.Ldiag, lambda = 0 blocks in buffer
+// lcur, d.Cinv): zero the workspace Zw (d.npad x bw doubles, row-major, bw = 16 ng), place
+// the right-hand sides, sweep, write the blocks.  trow_ptr / trow: per tile position t the
+// positions s < t with a structurally non-zero factor tile L(t, s), ascending.  Enqueue only.
+void launch_cov_batch(const DevProblem &d, int lcur, int ncb, const int *trow_ptr, const int *trow,
+                      const CovGroup *groups, int ng, double *Zw, int bw, double *out_pose,
+                      double *out_pt, hipStream_t s);
+
 // ---- pose-only (ba_pose_only.hip) ----
 struct PoIter {
   float cost, cost_change, abs_step;

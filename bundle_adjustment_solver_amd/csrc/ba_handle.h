@@ -101,6 +101,7 @@ struct ba_handle {
   ba::DenseSchedule sched;   // level schedule of the reduced-system Cholesky
   ba::DenseDev ddev;
   std::vector<int> pose_col_h;
+  int cov_batches = 0;       // column batches of the last ba_covariance (ba_covariance_info)
   // gradient descent (ba_gd_*): device state built on the first GD call after
   // ba_finalize (in `allocs`: freed with the problem), and which loop the
   // controller belongs to — ba_lm_iterate and ba_gd_iterate refuse each other's

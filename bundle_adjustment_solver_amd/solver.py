@@ -207,6 +207,25 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def covariance_to_user_units(cov_pose, cov_pt, sigma_px):
+    """Blocks of BaProblem.covariance (scaled units, unit pixel noise) -> covariances
+    in the caller's units for an isotropic pixel noise of sigma_px (numpy only).
+
+    The facade scales lengths and pixels by SCALER = 0.01.  A residual of r pixels
+    is 0.01 r scaled, so a noise of sigma_px is 0.01 sigma_px there and the scaled
+    covariance is (1e-4 sigma_px^2) Sigma_s.  The rotation part omega of the pose
+    tangent xi = [v; omega] (T_jw <- exp(xi) T_jw, world-to-body,
+    left-multiplicative) has no unit, v is a length: xi_user = D xi_scaled with
+    D = diag(100 I3, I3); a point is a length: X_user = 100 X_scaled.  Hence
+        Cov_pose  = sigma_px^2 * 1e-4 * D Sigma_s D
+        Cov_point = sigma_px^2 * 1e-4 * 1e4 * Sigma_s = sigma_px^2 * Sigma_s."""
+    cov_pose = np.asarray(cov_pose, np.float64).reshape(-1, 6, 6)
+    cov_pt = np.asarray(cov_pt, np.float64).reshape(-1, 3, 3)
+    s2 = float(sigma_px) ** 2
+    d = np.r_[np.full(3, INVERSE_SCALER), np.ones(3)]
+    return (s2 * SCALER * SCALER) * (d[None, :, None] * cov_pose * d[None, None, :]), s2 * cov_pt
+
+
 class BaProblem:
     """Thin numpy wrapper over one ba_handle, in the solver's SCALED units.
 
@@ -529,6 +548,35 @@ class BaProblem:
         check(self.lib.ba_get_dropped_pivots(self.h, C.byref(v), int(reset)),
               "ba_get_dropped_pivots")
         return int(v.value)
+
+    def covariance(self, pose_sel, pt_sel, huber):
+        """ba_covariance: blocks of the inverse of the solver's normal matrix
+        [[A, W], [W^T, C]] at the current accepted values, lambda = 0 and the given
+        Huber threshold, in SCALED units.  pose_sel / pt_sel: USER indices of
+        optimisable poses / points (any order, repeats allowed, may be empty).
+        Returns (cov_pose (n, 6, 6), cov_pt (n, 3, 3), dropped pivots of this
+        call's factorisation).  Pose tangent: xi = [v; omega] of
+        T_jw <- exp(xi) T_jw.  Afterwards the stage readers (get_A, get_S, ...)
+        hold the lambda = 0 linearisation; poses, points and the LM state are
+        untouched."""
+        ps = np.ascontiguousarray(pose_sel, np.int32).reshape(-1)
+        qs = np.ascontiguousarray(pt_sel, np.int32).reshape(-1)
+        cp = np.zeros((ps.size, 6, 6))
+        cq = np.zeros((qs.size, 3, 3))
+        dropped = C.c_int64(0)
+        check(self.lib.ba_covariance(self.h, float(huber), ps.size, _ip(ps) if ps.size else None,
+                                     _dp(cp) if ps.size else None, qs.size,
+                                     _ip(qs) if qs.size else None, _dp(cq) if qs.size else None,
+                                     C.byref(dropped)), "ba_covariance")
+        return cp, cq, int(dropped.value)
+
+    def covariance_info(self):
+        """Column batches of ba_covariance on this handle (BA_COV_BATCH overrides
+        the width)."""
+        v = (C.c_int64 * 4)()
+        check(self.lib.ba_covariance_info(self.h, v), "ba_covariance_info")
+        return dict(batch_cols=int(v[0]), cols_per_wave=int(v[1]), workspace_bytes=int(v[2]),
+                    last_batches=int(v[3]))
 
     def dense_spd_solve(self, A, b):
         A = np.ascontiguousarray(A, np.float64)
@@ -1594,6 +1642,39 @@ class FullBundleAdjustmentSolver:
         finally:
             batch.close()
         return res
+
+    def ComputeCovariance(self, poses, points, sigma_pixel=1.0, options=None):
+        """(new; the reference has no counterpart) Covariance blocks of the CURRENT
+        solver state — after Solve: of the solution — for the given pose and point
+        objects (or integer handles), all optimisable, in any order, repeats allowed.
+
+        Returns (cov_pose (n, 6, 6), cov_point (n, 3, 3)) in the caller's units for an
+        isotropic pixel noise of `sigma_pixel`: blocks of sigma^2 (J^T W J)^-1, W the
+        Huber weights of `options` (default Options()).  A pose block is the
+        covariance of the tangent xi = [v; omega] of the WORLD-TO-BODY pose
+        T_jw = inverse(registered pose), left-multiplicative: T_jw <- exp(xi) T_jw,
+        v in the caller's length unit, omega in radians.  A point block is the
+        covariance of the world point.  Stereo: the solver's own normal matrix is
+        inverted (last-writer rule of the cross block, see include/ba_hip.h)."""
+        self.FinalizeParameters()
+        hp, hq = [], []
+        for pose in poses:
+            h = self._pose_handle(pose)
+            if h is None:
+                raise RuntimeError("There is no pointer in the BA pose pool.")
+            if h in self._pose_fixed:
+                raise RuntimeError("ComputeCovariance: a fixed pose has no covariance.")
+            hp.append(h)
+        for point in points:
+            h = self._point_handle(point)
+            if h is None:
+                raise RuntimeError("There is no pointer in the BA point pool.")
+            if h in self._pt_fixed:
+                raise RuntimeError("ComputeCovariance: a fixed point has no covariance.")
+            hq.append(h)
+        huber = (options or Options()).outlier_handle.threshold_huber_loss
+        cp, cq, _ = self._problem.covariance(hp, hq, huber)
+        return covariance_to_user_units(cp, cq, sigma_pixel)
 
     def _finish_solve(self, rows, converged, summary, t0):
         """Write the solution back through the user's objects (reference

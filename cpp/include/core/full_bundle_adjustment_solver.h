@@ -96,6 +96,27 @@ class FullBundleAdjustmentSolver {
   // internal state.
   void ReloadParameterValues();
 
+  // (new; the reference has no counterpart) Covariance blocks of the CURRENT solver
+  // state — after Solve: of the solution — for the given registered, optimisable poses
+  // and points (any order, repeats allowed; either list may be empty), through
+  // ba_covariance of include/ba_hip.h.  The blocks are those of sigma_pixel^2 (J^T W J)^-1
+  // in the caller's units, W the Huber weights of a default Options (threshold 1.0): a pose
+  // block is the covariance of the tangent xi = [v; omega] of the WORLD-TO-BODY pose
+  // T_jw = inverse(*pose), left-multiplicative, T_jw <- exp(xi) T_jw (v in the caller's
+  // length unit, omega in radians); a point block that of the world point.  With
+  // D = diag(100 I3, I3) and the raw blocks Sigma_s of the scaled problem:
+  // Cov_pose = sigma^2 1e-4 D Sigma_s D, Cov_point = sigma^2 Sigma_s.  Stereo: the solver's
+  // own normal matrix is inverted (last-writer rule of the cross block, see ba_hip.h).
+  // An unknown or fixed pointer throws std::runtime_error, as MakePoseFixed does.
+  // Finalizes the parameters if that has not happened.  Returns true when the
+  // factorisation met no non-positive pivot (false: S is singular, e.g. no fixed pose).
+  bool ComputeCovariance(const std::vector<_BA_Pose *> &poses, const std::vector<_BA_Point *> &points,
+                         double sigma_pixel, std::vector<Eigen::Matrix<double, 6, 6>> *cov_poses,
+                         std::vector<Eigen::Matrix<double, 3, 3>> *cov_points);
+  // the C-ABI handle behind the finalized problem (nullptr before FinalizeParameters):
+  // for the readers of include/ba_hip.h; indices there are registration order
+  ba_handle *GetHandle() const { return handle_; }
+
   std::string GetSolverStatistics() const;
 
   // GPU selection / console chatter (not in the reference)

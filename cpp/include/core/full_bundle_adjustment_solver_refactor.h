@@ -72,6 +72,15 @@ class FullBundleAdjustmentSolverRefactor {
   // solver_type and the lambda ratios are ignored, damping_term = initial_lambda
   bool SolveByGradientDescent(Options options, Summary *summary = nullptr);
 
+  // (new) covariance blocks of the current state, see FullBundleAdjustmentSolver::ComputeCovariance:
+  // same units, same tangent convention (world-to-body T_jw = inverse(*pose), T_jw <- exp(xi) T_jw)
+  bool ComputeCovariance(const std::vector<Pose *> &poses, const std::vector<Point *> &points, double sigma_pixel,
+                         std::vector<Eigen::Matrix<double, 6, 6>> *cov_poses,
+                         std::vector<Eigen::Matrix<double, 3, 3>> *cov_points) {
+    return impl_.ComputeCovariance(poses, points, sigma_pixel, cov_poses, cov_points);
+  }
+  ba_handle *GetHandle() const { return impl_.GetHandle(); }
+
   std::string GetSolverStatistics() const;
 
   void AddObservation(const Index camera_id, Pose *related_pose, Point *related_point, const Pixel &pixel);

@@ -391,6 +391,56 @@ bool FullBundleAdjustmentSolver::Run(Options options, Summary *summary, bool gra
   return true;  // the reference always returns true (:1043)
 }
 
+bool FullBundleAdjustmentSolver::ComputeCovariance(const std::vector<_BA_Pose *> &poses,
+                                                   const std::vector<_BA_Point *> &points, double sigma_pixel,
+                                                   std::vector<Eigen::Matrix<double, 6, 6>> *cov_poses,
+                                                   std::vector<Eigen::Matrix<double, 3, 3>> *cov_points) {
+  std::vector<int32_t> ps, qs;
+  for (_BA_Pose *p : poses) {
+    const auto it = pose_index_.find(p);
+    if (it == pose_index_.end()) throw std::runtime_error("There is no pointer in the BA pose pool.");
+    if (fixed_poses_.count(it->second)) throw std::runtime_error("ComputeCovariance: a fixed pose has no covariance.");
+    ps.push_back(it->second);
+  }
+  for (_BA_Point *q : points) {
+    const auto it = point_index_.find(q);
+    if (it == point_index_.end()) throw std::runtime_error("There is no pointer in the BA point pool.");
+    if (fixed_points_.count(it->second)) throw std::runtime_error("ComputeCovariance: a fixed point has no covariance.");
+    qs.push_back(it->second);
+  }
+  if ((!ps.empty() && cov_poses == nullptr) || (!qs.empty() && cov_points == nullptr))
+    throw std::runtime_error("ComputeCovariance: null output for a non-empty selection");
+  FinalizeParameters();
+  std::vector<double> cp(36 * ps.size()), cq(9 * qs.size());
+  int64_t dropped = 0;
+  const Options defaults;
+  Check(ba_covariance(handle_, static_cast<double>(defaults.outlier_handle.threshold_huber_loss),
+                      static_cast<int>(ps.size()), ps.empty() ? nullptr : ps.data(), ps.empty() ? nullptr : cp.data(),
+                      static_cast<int>(qs.size()), qs.empty() ? nullptr : qs.data(), qs.empty() ? nullptr : cq.data(),
+                      &dropped),
+        "ba_covariance");
+  // scaled units, unit pixel noise -> the caller's units (see the header)
+  const double s2 = sigma_pixel * sigma_pixel;
+  const double k_pose = s2 * static_cast<double>(scaler_) * static_cast<double>(scaler_);
+  if (cov_poses != nullptr) {
+    cov_poses->resize(ps.size());
+    for (size_t s = 0; s < ps.size(); ++s)
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) {
+          const double dr = r < 3 ? static_cast<double>(inverse_scaler_) : 1.0;
+          const double dc = c < 3 ? static_cast<double>(inverse_scaler_) : 1.0;
+          (*cov_poses)[s](r, c) = k_pose * (dr * cp[36 * s + 6 * r + c] * dc);
+        }
+  }
+  if (cov_points != nullptr) {
+    cov_points->resize(qs.size());
+    for (size_t s = 0; s < qs.size(); ++s)
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) (*cov_points)[s](r, c) = s2 * cq[9 * s + 3 * r + c];
+  }
+  return dropped == 0;
+}
+
 bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, Options options,
                                             std::vector<Summary> *summaries) {
   timer::StopWatch stopwatch("BundleAdjustmentSolver::SolveBatch");

@@ -346,6 +346,62 @@ int ba_stream_info(ba_stream *s, int64_t out6[6]);
 int ba_dense_spd_solve(ba_handle *h, int n, const double *A, const double *b,
                        double *x, double *ms);
 
+/* ---- covariance blocks from the factored reduced camera system ---------- */
+/* How well the current accepted values are determined (the reference has no
+ * counterpart; Ceres' Covariance, g2o's computeMarginals, GTSAM's Marginals).
+ * The call linearises at the current accepted values with lambda = 0 and the
+ * given Huber threshold, forms, scatters and factorises the Schur complement S
+ * with the launches of ba_stage_linearize(0, huber), ba_stage_schur and the
+ * factor half of ba_stage_solve_reduced, and reads the blocks off the factor
+ * S = L L^T (csrc/ba_cov.hip, fp64 MFMA, no atomics: the same bits every run):
+ *   cov_pose36[s]  the 6x6 row-major block [S^-1]_jj of pose pose_sel[s];
+ *   cov_pt9[s]     Sigma_ii = Cinv_i + Cinv_i W_i^T Sigma_P(i) W_i Cinv_i of point
+ *                  pt_sel[s], Sigma_P(i) = ALL blocks of S^-1, off-diagonal ones
+ *                  included, among the poses paired with landmark i.
+ * Both are blocks of the inverse of the solver's own normal matrix
+ * [[A, W], [W^T, C]], in the solver's scaled units; pose tangent xi = [v; omega]
+ * of T_jw <- exp(xi) T_jw (world-to-body, left-multiplicative).  pose_sel /
+ * pt_sel are USER indices of optimisable poses / points, in any order, repeats
+ * allowed; either selection may be empty and its output pointer then NULL.
+ * dropped_pivots (may be NULL) receives the non-positive pivots THIS call's
+ * factorisation met; the count of ba_get_dropped_pivots is not disturbed.
+ *  - Poses, points, the accepted-buffer index and the LM / GD controller are
+ *    untouched: ba_solve after ba_covariance gives the bits it gives without.
+ *    The stage intermediates (ba_get_A, ba_get_C, ba_get_pairs, ba_get_S, ...)
+ *    hold the lambda = 0 linearisation afterwards (ba_get_A / ba_get_C apply
+ *    the controller's lambda, which the call restores).
+ *  - Stereo: the matrix inverted is the solver's normal matrix, with the
+ *    last-writer rule of the cross block W_ji (one camera's J^T W J plus
+ *    block-diagonal terms: positive semi-definite, but not the full two-camera
+ *    J^T W J).  In mono the two coincide.
+ *  - A never-observed landmark has Cinv = 0 and no pairs: its block is exactly
+ *    zero.  A rank-deficient C_i gets what the solver's pseudo-inverse yields.
+ *  - Without a fixed pose S is singular at lambda = 0 and the result
+ *    meaningless: dropped_pivots > 0 is how the caller learns of it.
+ * Returns -1 (ba_last_error), before anything touches the device, if the handle
+ * is not finalized, is sharded (ba_set_shard world > 1 or an all-reduce hook) or
+ * streamed, an index is out of range or names a fixed pose / point, or an output
+ * pointer is NULL for a non-empty selection.
+ * The right-hand sides (6 per distinct pose, 3 per distinct point, 16 per wave)
+ * are processed in column batches; the workspace, npad x batch x 8 bytes, is
+ * allocated on the handle and freed on return. */
+int ba_covariance(ba_handle *h, double huber,
+                  int n_pose_sel, const int32_t *pose_sel, double *cov_pose36,
+                  int n_pt_sel, const int32_t *pt_sel, double *cov_pt9,
+                  int64_t *dropped_pivots);
+/* out4 = { columns of one batch on this handle (what fits 256 MiB of workspace,
+ * at most 16384; BA_COV_BATCH=<columns> overrides), columns per wave (16: two
+ * poses or five points), bytes of the workspace at that width, batches the last
+ * ba_covariance ran } */
+int ba_covariance_info(ba_handle *h, int64_t out4[4]);
+/* The argument checks of ba_covariance on plain values (host only, no device):
+ * finalized / sharded / streamed flags, the fixed masks of the n_pose poses and
+ * n_pt points (NULL: none fixed), the selections and output pointers.  0 or -1. */
+int ba_covariance_check(int finalized, int sharded, int streamed, int n_pose,
+                        const uint8_t *pose_fixed, int n_pt, const uint8_t *pt_fixed,
+                        int n_pose_sel, const int32_t *pose_sel, const double *cov_pose36,
+                        int n_pt_sel, const int32_t *pt_sel, const double *cov_pt9);
+
 /* ---- pose-only, monocular 6-DoF (fp32) --------------------------------- */
 /* Solve_Monocular_6Dof, reference
  * core/pose_only_bundle_adjustment_solver.cpp:8-170.  T12 in/out is
