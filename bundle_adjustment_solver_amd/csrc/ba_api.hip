@@ -184,8 +184,8 @@ int download(std::vector<T> &out, const T *dev, size_t n, hipStream_t s) {
 // Device set-up of a dense schedule: the work lists of `dd`, its column -> x map col_x
 // (npad entries), the solution in column order xc, the dropped-pivot counter, the order,
 // flags and tickets of the dataflow sweeps and the k_chol_dag / k_chol_look items and
-// counters; reads the dense knobs.  Everything is allocated on the handle (h->upload /
-// h->dalloc, in h->allocs).
+// counters; reads the dense knobs and fixes the launch plans.  Everything is allocated on
+// the handle (h->upload / h->dalloc, in h->allocs).
 int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::vector<int> &col_x,
                           ba::DenseDev &dd) {
   const size_t npad = col_x.size(), ncb = (size_t)std::max(1, sc.ncb);
@@ -199,10 +199,11 @@ int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::
     return -1;
   HIP_TRY(hipMemset(dd.xc, 0, npad * sizeof(double)));
   HIP_TRY(hipMemset(dd.bad_pivots, 0, sizeof(int)));
-  dd.read_env();
+  dd.knobs = ba::DenseKnobs::from_env();
+  for (int flow_ok = 0; flow_ok < 2; ++flow_ok) dd.plan[flow_ok] = ba::dense_launch_plan(sc, dd.knobs, flow_ok != 0);
+  const ba::DenseLaunchPlan &plan = dd.plan[1];  // (plan[0] has the same tail and lists: it only launches per level)
   std::vector<int> order;
-  dd.flow_tail_t0 = ba::dense_flow_order(sc, dd, order);
-  dd.n_flow = (int)order.size();
+  ba::dense_flow_order(sc, plan, order);
   dd.flow_gen = 0;
   if (h->upload(&dd.flow_order, order) || h->dalloc(&dd.flow_flags, ncb) || h->dalloc(&dd.flow_ticket, (size_t)1) ||
       h->dalloc(&dd.fwd_flags, ncb) || h->dalloc(&dd.fwd_ticket, (size_t)1))
@@ -211,9 +212,9 @@ int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::
   HIP_TRY(hipMemset(dd.flow_ticket, 0, sizeof(int)));
   HIP_TRY(hipMemset(dd.fwd_flags, 0, ncb * sizeof(int)));
   HIP_TRY(hipMemset(dd.fwd_ticket, 0, sizeof(int)));
-  std::vector<int> items, pre, need, ntrsm, lneed;
-  if (ba::dense_dag_items(sc, dd, items, pre, need, ntrsm, lneed)) {
-    dd.n_dag_items = (int)items.size() / 2;
+  if (plan.n_dag_items > 0) {
+    std::vector<int> items, pre, need, ntrsm, lneed;
+    ba::dense_dag_items(sc, plan, items, pre, need, ntrsm, lneed);
     dd.n_fwd_cnt = (int)need.size();
     if (h->upload(&dd.dag_items, items) || h->upload(&dd.upd_pre, pre) || h->upload(&dd.col_need, need) ||
         h->upload(&dd.dag_ntrsm, ntrsm) || h->upload(&dd.look_need, lneed) || h->dalloc(&dd.fwd_cnt, need.size()) ||
@@ -609,16 +610,13 @@ int ba_finalize(ba_handle *h) {
   if (h->dalloc(&d.log, (size_t)d.log_cap)) return -1;
 
   lap("block storage");
-  // dense reduced system: tiles of 5 poses (32 columns) or 10 poses (64
-  // columns), eliminated in the order of the level schedule.  Both schedules are
-  // built.  NARROW patterns (every column tile has at most five row tiles below it
-  // besides the rhs block: windows of <= ~15 poses) are latency-bound chains of
-  // dependent launches, one set per level, whose cost is a fixed latency plus a term
-  // proportional to the tile order (measured on MI355X: 16 us per level at 32, 30 us
-  // at 64): the cheaper chain wins.  Wider and dense patterns are bound by the work
-  // per level (row tiles per column, MFMA tile size) and run 1.1-1.9x faster at 64
-  // (W20: 1.08 vs 1.21 ms per iteration, DENSE1K: 10.0 vs 19.0).  BA_DENSE_NB=32|64
-  // forces one.
+  // dense reduced system: tiles of 5 poses (32 columns) or 10 poses (64 columns), eliminated
+  // in the order of the level schedule.  Both schedules are built; dense_pick_tile_order chooses.
+  h->xbuf_n[0] = pl.B * 36 + 6 * (int64_t)pl.N;
+  h->xbuf_n[1] = 4;
+  h->xbuf_n[2] = 3 * (int64_t)pl.n_pt_global;
+  if (h->dalloc(&d.Spk, (size_t)h->xbuf_n[0])) return -1;
+  HIP_TRY(hipMemset(d.Spk, 0, (size_t)h->xbuf_n[0] * sizeof(double)));
   if (h->dense_owner) {
     // streaming (ba_stream.hip): the reduced system is scattered, factorised and solved
     // ONCE per iteration, by the owner; this handle aliases its dense image, schedule
@@ -634,46 +632,29 @@ int ba_finalize(ba_handle *h) {
     d.L = o->d.L; d.Ldiag = o->d.Ldiag; d.pose_col = o->d.pose_col; d.col_x = o->d.col_x;
     d.zt_I = o->d.zt_I; d.zt_J = o->d.zt_J; d.n_zt = o->d.n_zt;
     d.x = o->d.x;
-    h->xbuf_n[0] = pl.B * 36 + 6 * (int64_t)pl.N;
-    h->xbuf_n[1] = 4;
-    h->xbuf_n[2] = 3 * (int64_t)pl.n_pt_global;
-    if (h->dalloc(&d.Spk, (size_t)h->xbuf_n[0])) return -1;
-    HIP_TRY(hipMemset(d.Spk, 0, (size_t)h->xbuf_n[0] * sizeof(double)));
   } else {
-    const char *nat = getenv("BA_DENSE_NATURAL");
-    const char *full = getenv("BA_DENSE_FULL");
-    const char *force = getenv("BA_DENSE_NB");
+    const ba::DenseKnobs knobs = ba::DenseKnobs::from_env();
     ba::DenseSchedule cand[2];
-    double cost[2];
     const int orders[2] = {32, 64};
-    const double level_us[2] = {16.0, 30.0};
     for (int k = 0; k < 2; ++k) {
       int ncb_k = 0;
       std::vector<uint8_t> adj;
       ba::tile_pattern(pl, ba::dense_poses_per_tile(orders[k]), ncb_k, adj);
-      if (full && atoi(full) != 0) std::fill(adj.begin(), adj.end(), 1);
-      ba::build_dense_schedule(ncb_k, adj, nat && atoi(nat) != 0, orders[k], cand[k]);
-      cost[k] = cand[k].nlev * level_us[k];
+      if (knobs.full) std::fill(adj.begin(), adj.end(), 1);
+      ba::build_dense_schedule(ncb_k, adj, knobs.natural, orders[k], cand[k]);
     }
-    if (getenv("BA_PLAN_STATS"))
+    const bool stats = getenv("BA_PLAN_STATS") != nullptr;
+    if (stats)
       fprintf(stderr, "dense schedules: nb32 %d tiles %d levels max_rows %d fill %.3f | nb64 %d tiles %d levels max_rows %d fill %.3f\n",
               cand[0].ncb, cand[0].nlev, cand[0].max_rows, cand[0].fill, cand[1].ncb, cand[1].nlev, cand[1].max_rows,
               cand[1].fill);
-    const bool narrow = cand[0].max_rows <= 6;
-    int pick = (narrow && cost[0] <= cost[1]) ? 0 : 1;
-    if (force && atoi(force) == 32) pick = 0;
-    if (force && atoi(force) == 64) pick = 1;
-    h->sched = cand[pick];
+    h->sched = cand[ba::dense_pick_tile_order(cand[0], cand[1], knobs.nb)];
     const int nb = h->sched.nb;
     const int ppt = ba::dense_poses_per_tile(nb);
     const int ncb = h->sched.ncb;
     d.nb = nb;
     d.npad = ncb * nb;
     d.ld = d.npad + nb;
-    h->xbuf_n[0] = pl.B * 36 + 6 * (int64_t)pl.N;
-    h->xbuf_n[1] = 4;
-    h->xbuf_n[2] = 3 * (int64_t)pl.n_pt_global;
-    if (h->dalloc(&d.Spk, (size_t)h->xbuf_n[0])) return -1;
     if (h->dalloc(&d.L, (size_t)d.npad * d.ld)) return -1;
     if (h->dalloc(&d.Ldiag, (size_t)ncb * ba::dense_ws_per_block(nb))) return -1;
     h->pose_col_h.assign(pl.N, 0);
@@ -687,7 +668,11 @@ int ba_finalize(ba_handle *h) {
     ba::DenseDev &dd = h->ddev;
     if (h->upload(&d.pose_col, h->pose_col_h) || upload_dense_schedule(h, sc, col_x, dd)) return -1;
     d.col_x = dd.col_x;
-    if (times && dd.dag_items) fprintf(stderr, "[finalize] k_chol_dag: %d items\n", dd.n_dag_items);
+    if (times && dd.dag_items) fprintf(stderr, "[finalize] k_chol_dag: %d items\n", dd.plan[1].n_dag_items);
+    if (stats)
+      fprintf(stderr, "dense launch plan: nb%d forward %s backward %s tail %d columns%s\n", nb,
+              ba::dense_fwd_name(dd.plan[1].fwd), ba::dense_back_name(dd.plan[1].back), dd.plan[1].tail_cols,
+              dd.plan[1].tail_pair ? " (pair)" : "");
     // tiles (re)initialised per iteration: factor pattern + diagonal + rhs row
     std::vector<int> ztI, ztJ;
     for (int p = 0; p < ncb; ++p) {
@@ -701,7 +686,6 @@ int ba_finalize(ba_handle *h) {
     d.n_zt = (int)ztI.size();
     if (h->upload(&d.zt_I, ztI) || h->upload(&d.zt_J, ztJ)) return -1;
     HIP_TRY(hipMemset(d.L, 0, (size_t)d.npad * d.ld * sizeof(double)));
-    HIP_TRY(hipMemset(d.Spk, 0, (size_t)h->xbuf_n[0] * sizeof(double)));
   }
 
   lap("dense schedule + image");
@@ -1541,8 +1525,7 @@ int ba_dense_spd_solve(ba_handle *h, int n, const double *A, const double *b,
       adj[(size_t)I * ncb + J] = adj[(size_t)J * ncb + I] = any;
     }
   ba::DenseSchedule sc;
-  const char *nat = getenv("BA_DENSE_NATURAL");
-  ba::build_dense_schedule(ncb, adj, nat && atoi(nat) != 0, nb, sc);
+  ba::build_dense_schedule(ncb, adj, ba::DenseKnobs::from_env().natural, nb, sc);
   std::vector<int> colmap(npad), col_x(npad, -1);  // original column -> dense column
   for (int c = 0; c < npad; ++c) colmap[c] = sc.pos_of_tile[c / nb] * nb + c % nb;
   std::vector<double> L((size_t)npad * ld, 0.0);
@@ -1581,7 +1564,7 @@ int ba_dense_spd_solve(ba_handle *h, int n, const double *A, const double *b,
   HIP_TRY(hipEventCreate(&e0));
   HIP_TRY(hipEventCreate(&e1));
   HIP_TRY(hipEventRecord(e0, h->stream));
-  ba::dense_factor_solve(dL, npad, ld, dD, dx, nullptr, sc, dd, h->stream);
+  ba::dense_factor_solve(dL, npad, ld, dD, dx, nullptr, sc, dd, dd.plan[dd.flow_ok], h->stream);
   HIP_TRY(hipEventRecord(e1, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   float t = 0.f;
@@ -1732,12 +1715,11 @@ int ba_covariance(ba_handle *h, double huber, int n_pose_sel, const int32_t *pos
   ba::launch_schur(d, /*direct=*/false, /*with_init=*/true, h->stream);
   ba::launch_scatter(d, h->stream);
   {
-    // k_chol_tail keeps its block's factor in LDS (only x leaves): here every level takes
-    // the per-level kernels, which leave the whole factor in the image.  Same arithmetic.
-    ba::DenseDev dd = h->ddev;
-    dd.want_tail = false;
-    ba::dense_factor_solve(d.L, d.npad, d.ld, d.Ldiag, d.x, &d.ctrl->done, sc, dd, h->stream);
-    h->ddev.flow_gen = dd.flow_gen;
+    // k_chol_tail keeps its block's factor in LDS (only x leaves): here no level goes to it, so
+    // that the whole factor is left in the image.  Same arithmetic.
+    const ba::DenseDev &dd = h->ddev;
+    ba::dense_factor_solve(d.L, d.npad, d.ld, d.Ldiag, d.x, &d.ctrl->done, sc, dd,
+                           ba::dense_launch_plan_no_tail(sc, dd.knobs, dd.flow_ok, dd.plan[1]), h->stream);
   }
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(&bad_now, h->ddev.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));

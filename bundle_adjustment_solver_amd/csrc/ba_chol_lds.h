@@ -10,7 +10,7 @@
 
 namespace ba {
 
-constexpr int kTailCols = 96;
+// (kTailCols: ba_dense_sched.h)
 constexpr int kTailLS = kTailCols + 16 + 1;  // column stride of the LDS image (rows + rhs block + pad)
 constexpr int kTailES = 17;
 

@@ -17,9 +17,6 @@
 #include "ba_tile16.h"
 #include "ba_chol_lds.h"
 
-#include <cstdlib>
-#include <vector>
-
 namespace ba {
 
 namespace {
@@ -134,227 +131,146 @@ void launch_dense_init(double *L, int ld, const int *col_x, const int *zt_I,
                        zt_I, zt_J, nb, done_flag);
 }
 
-// Level-scheduled, structure-aware blocked Cholesky (see ba_dense_sched.h):
-// per level one batched diagonal launch, one batched TRSM launch and one
-// target-centric update launch; then one backward launch per level.
-// NS = nb32 or nb64 (the kernels of the schedule's tile order).
-#define BA_DENSE_RUN(NS)                                                                    \
-  if (look2) {                                                                              \
-    /* dense patterns: lookahead inside one launch per level (k_chol_look) */               \
-    const int nlv = sc.nlev - tail_levels;                                                  \
-    {                                                                                       \
-      const int t0 = sc.lev_ptr[0], nt = sc.lev_ptr[1] - t0;                                \
-      const int it0 = sc.item_ptr[0], ni = sc.item_ptr[1] - it0;                            \
-      BA_LAUNCH(K_CHOL_DIAG, NS::k_chol_diag, dim3(nt), dim3(256), s, L, ld, t0, Ldiag, done, bad); \
-      if (ni > 0)                                                                           \
-        BA_LAUNCH(K_CHOL_TRSM, NS::k_chol_trsm, dim3(ni), dim3(NS::NP * 64), s, L, ld,      \
-                  row_limit, it0, dd.item_t, dd.item_I, Ldiag, done);                       \
-    }                                                                                       \
-    for (int l = 0; l < nlv; ++l) {                                                         \
-      const int tg0 = sc.tgt_ptr[l], ng = sc.tgt_ptr[l + 1] - tg0, nf = sc.tgt_first[l];    \
-      if (l + 1 < nlv) {                                                                    \
-        const int t1 = sc.lev_ptr[l + 1], nt1 = sc.lev_ptr[l + 2] - t1;                     \
-        const int it1 = sc.item_ptr[l + 1], ni1 = sc.item_ptr[l + 2] - it1;                 \
-        BA_LAUNCH(K_CHOL_UPDATE, NS::k_chol_look, dim3(nt1 + ni1 + ng), dim3(256), s, L,    \
-                  ld, row_limit, nf, t1, nt1, it1, ni1, tg0, dd.item_t, dd.item_I, Ldiag,   \
-                  dd.tgt_desc, dd.src_t, dd.look_need, done, bad, dd.dag_dflags,            \
-                  dd.fwd_cnt, gen_now);                                                     \
-      } else if (ng > 0) {                                                                  \
-        BA_LAUNCH(K_CHOL_UPDATE, NS::k_chol_update, dim3(ng), dim3(256), s, L, ld, tg0,     \
-                  dd.tgt_desc, dd.src_t, done);                                             \
-      }                                                                                     \
-    }                                                                                       \
-  } else if (dag) {                                                                         \
-    /* three-kernel path: every non-tail level in ONE dataflow launch with lookahead */     \
-    BA_LAUNCH(K_CHOL_UPDATE, NS::k_chol_dag, dim3(dd.n_dag_items), dim3(256), s, L, ld,     \
-              row_limit, (const int2 *)dd.dag_items, dd.n_dag_items, dd.item_t, dd.item_I,  \
-              dd.dag_ntrsm, Ldiag, dd.tgt_desc, dd.src_t, dd.upd_pre, dd.col_need, done,    \
-              bad, dd.fwd_flags, dd.dag_dflags, dd.dag_tcnt, dd.fwd_cnt, dd.fwd_ticket,     \
-              gen_now);                                                                     \
-  } else                                                                                    \
-  for (int l = 0; l < sc.nlev - tail_levels; ++l) {                                         \
-    const int t0 = sc.lev_ptr[l], nt = sc.lev_ptr[l + 1] - t0;                              \
-    const int it0 = sc.item_ptr[l], ni = sc.item_ptr[l + 1] - it0;                          \
-    if (split) {                                                                            \
-      BA_LAUNCH(K_CHOL_DIAG, NS::k_chol_diag, dim3(nt), dim3(256), s, L, ld, t0, Ldiag, done, bad); \
-      if (ni > 0)                                                                           \
-        BA_LAUNCH(K_CHOL_TRSM, NS::k_chol_trsm, dim3(ni), dim3(NS::NP * 64), s, L, ld,      \
-                  row_limit, it0, dd.item_t, dd.item_I, Ldiag, done);                       \
-    } else if (flow && dd.fwd_flags) {                                                      \
-      /* factorisation + TRSM and the updates that consume them: ONE dataflow launch */     \
-      const int tg0f = sc.tgt_ptr[l], ngf = sc.tgt_ptr[l + 1] - tg0f;                       \
-      BA_LAUNCH(K_CHOL_DIAG_TRSM, NS::k_chol_level_flow, dim3(nt + ngf), dim3(256), s, L,   \
-                ld, npad, t0, nt, tg0f, ngf, dd.row_desc, dd.rows, Ldiag, dd.tgt_desc,      \
-                dd.src_t, done, bad, dd.fwd_flags,                                          \
-                (nt + ngf <= kFlowResident && !dd.force_ticket) ? nullptr : dd.fwd_ticket, gen_now); \
-      continue;                                                                             \
-    } else {                                                                                \
-      BA_LAUNCH(K_CHOL_DIAG_TRSM, NS::k_chol_diag_trsm, dim3(nt), dim3(256), s, L, ld,      \
-                npad, t0, dd.row_desc, dd.rows, Ldiag, done, bad);                              \
-    }                                                                                       \
-    const int tg0 = sc.tgt_ptr[l], ng = sc.tgt_ptr[l + 1] - tg0;                            \
-    if (ng > 0)                                                                             \
-      BA_LAUNCH(K_CHOL_UPDATE, NS::k_chol_update, dim3(ng), dim3(256), s, L, ld, tg0,       \
-                dd.tgt_desc, dd.src_t, done);                                               \
-  }                                                                                         \
-  if (tail_cols == 64)                                                                      \
-    BA_LAUNCH(K_CHOL_TAIL, (k_chol_tail<4, false>), dim3(1), dim3(256), s, L, ld, npad,     \
-              tail_c0, dd.xc, x, dd.col_x, done, bad);                                        \
-  if (tail_cols == 96 && !tail_pair)                                                        \
-    BA_LAUNCH(K_CHOL_TAIL, (k_chol_tail<6, false>), dim3(1), dim3(256), s, L, ld, npad,     \
-              tail_c0, dd.xc, x, dd.col_x, done, bad);                                        \
-  if (tail_cols == 96 && tail_pair)                                                         \
-    BA_LAUNCH(K_CHOL_TAIL, (k_chol_tail<6, true>), dim3(1), dim3(256), s, L, ld, npad,      \
-              tail_c0, dd.xc, x, dd.col_x, done, bad);                                        \
-  if (flow && !flow_back && n_back > 0) {                                                   \
-    BA_LAUNCH(K_CHOL_BACK, NS::k_chol_back_flow<true>, dim3(n_back), dim3(256), s, L, ld,   \
-              npad, dd.flow_order, n_back, back_t_end, dd.back_desc, dd.rows, Ldiag, dd.xc, \
-              x, dd.col_x, done, dd.flow_flags,                                             \
-              (n_back <= kFlowResident && !dd.force_ticket) ? nullptr : dd.flow_ticket, gen_now, bad, \
-              (dag || look2) ? dd.fwd_cnt : nullptr, dd.n_fwd_cnt);                               \
-  } else if (flow_back && n_back > 0) {                                                     \
-    BA_LAUNCH(K_CHOL_BACK, NS::k_chol_back_flow<false>, dim3(n_back), dim3(256), s, L, ld, npad, \
-              dd.flow_order, n_back, back_t_end, dd.back_desc, dd.rows, Ldiag, dd.xc, x,    \
-              dd.col_x, done, dd.flow_flags,                                                \
-              (n_back <= kFlowResident && !dd.force_ticket) ? nullptr : dd.flow_ticket, gen_now, bad, \
-              (dag || look2) ? dd.fwd_cnt : nullptr, dd.n_fwd_cnt);                               \
-  } else                                                                                    \
-  for (int l = sc.nlev - tail_levels - 1; l >= 0; --l) {                                    \
-    const int t0 = sc.lev_ptr[l], nt = sc.lev_ptr[l + 1] - t0;                              \
-    BA_LAUNCH(K_CHOL_BACK, NS::k_chol_back, dim3(nt), dim3(256), s, L, ld, npad, t0,        \
-              dd.back_desc, dd.rows, Ldiag, dd.xc, x, dd.col_x, done);                      \
-  }
-
-// Workgroups of a dataflow launch that are certainly resident at once on the part (256
-// CUs x 2 workgroups of 256 threads at the kernels' register budgets, with a margin):
-// up to here the role is the block index, beyond it a ticket (ba_dense_tile.inc).
-constexpr int kFlowResident = 448;
-
-// Levels handed to k_chol_tail (the last ones, together 64 or 96 columns, at least two).
-static int dense_tail_levels(const DenseSchedule &sc, const DenseDev &dd, int *cols_out) {
-  int tail_levels = 0, tail_cols = 0;
-  if (dd.want_tail) {
-    for (int l = sc.nlev - 1; l >= 0; --l) {
-      const int cols = (sc.lev_ptr[l + 1] - sc.lev_ptr[l]) * sc.nb;
-      if (tail_cols + cols > kTailCols) break;
-      tail_cols += cols;
-      ++tail_levels;
-    }
-    if (tail_levels < 2 || (tail_cols != 64 && tail_cols != 96)) tail_levels = tail_cols = 0;
-  }
-  if (cols_out) *cols_out = tail_cols;
-  return tail_levels;
-}
-// Positions of the backward sweep's dataflow launch, top level first; returns the first
-// position of the tail block (= their number).
-int dense_flow_order(const DenseSchedule &sc, const DenseDev &dd, std::vector<int> &order) {
-  const int tail_levels = dense_tail_levels(sc, dd, nullptr);
-  order.clear();
-  for (int l = sc.nlev - tail_levels - 1; l >= 0; --l)
-    for (int t = sc.lev_ptr[l]; t < sc.lev_ptr[l + 1]; ++t) order.push_back(t);
-  return sc.lev_ptr[sc.nlev - tail_levels];
+namespace {
+// NPt is a compile-time parameter of k_chol_tail: 64 columns, 96, or 96 with a paired first level.
+auto tail_kernel(const DenseLaunchPlan &pl) {
+  if (pl.tail_cols == 64) return k_chol_tail<4, false>;
+  return !pl.tail_pair ? k_chol_tail<6, false> : k_chol_tail<6, true>;
 }
 
-bool dense_dag_items(const DenseSchedule &sc, const DenseDev &dd, std::vector<int> &items,
-                     std::vector<int> &pre, std::vector<int> &need, std::vector<int> &ntrsm,
-                     std::vector<int> &look_need) {
-  const bool split = dd.want_split || !dd.row_desc || sc.max_rows > 4 * (4 / (sc.nb / 16));
-  const int tail_levels = dense_tail_levels(sc, dd, nullptr);
-  const int nlv = sc.nlev - tail_levels;
-  items.clear();
-  pre.assign(std::max<size_t>(1, sc.tgt_J.size()), 0);
-  need.assign((size_t)sc.ncb + 1, 0);
-  ntrsm.assign((size_t)sc.ncb + 1, 0);
-  look_need.assign((size_t)sc.ncb + 1, 0);
-  if (!split || nlv < 2 || (int)sc.tgt_first.size() < sc.nlev) return false;
-  for (size_t q = 0; q < sc.item_t.size(); ++q) ++ntrsm[sc.item_t[q]];
-  auto push = [&](int kind, int id) {
-    items.push_back(kind);
-    items.push_back(id);
-  };
-  auto tiles_of = [&](int l) {
-    for (int t = sc.lev_ptr[l]; t < sc.lev_ptr[l + 1]; ++t) push(0, t);
-    for (int q = sc.item_ptr[l]; q < sc.item_ptr[l + 1]; ++q) push(1, q);
-  };
-  tiles_of(0);
-  for (int l = 0; l < nlv; ++l) {
-    const int tg0 = sc.tgt_ptr[l], tg1 = sc.tgt_ptr[l + 1], nf = sc.tgt_first[l];
-    for (int tg = tg0; tg < tg1; ++tg) pre[tg] = need[sc.tgt_J[tg]];  // (updates of EARLIER levels)
-    for (int tg = tg0; tg < tg0 + nf; ++tg) {
-      push(2, tg);
-      ++look_need[sc.tgt_J[tg]];  // (k_chol_look: the "first" targets of the level before the tile's)
-    }
-    if (l + 1 < nlv) tiles_of(l + 1);  // the next level's tiles beside the bulk of this level's update
-    for (int tg = tg0 + nf; tg < tg1; ++tg) push(2, tg);
-    for (int tg = tg0; tg < tg1; ++tg) ++need[sc.tgt_J[tg]];
-  }
-  return true;
-}
+// The kernels of one tile order (ba_dense_tile.inc, compiled once per order).
+struct Nb32 {
+  static constexpr int NP = nb32::NP;
+  static constexpr auto diag = nb32::k_chol_diag;
+  static constexpr auto trsm = nb32::k_chol_trsm;
+  static constexpr auto update = nb32::k_chol_update;
+  static constexpr auto look = nb32::k_chol_look;
+  static constexpr auto dag = nb32::k_chol_dag;
+  static constexpr auto level_flow = nb32::k_chol_level_flow;
+  static constexpr auto diag_trsm = nb32::k_chol_diag_trsm;
+  static constexpr auto back_flow_ordered = nb32::k_chol_back_flow<true>;
+  static constexpr auto back_flow_gather = nb32::k_chol_back_flow<false>;
+  static constexpr auto back = nb32::k_chol_back;
+};
+struct Nb64 {
+  static constexpr int NP = nb64::NP;
+  static constexpr auto diag = nb64::k_chol_diag;
+  static constexpr auto trsm = nb64::k_chol_trsm;
+  static constexpr auto update = nb64::k_chol_update;
+  static constexpr auto look = nb64::k_chol_look;
+  static constexpr auto dag = nb64::k_chol_dag;
+  static constexpr auto level_flow = nb64::k_chol_level_flow;
+  static constexpr auto diag_trsm = nb64::k_chol_diag_trsm;
+  static constexpr auto back_flow_ordered = nb64::k_chol_back_flow<true>;
+  static constexpr auto back_flow_gather = nb64::k_chol_back_flow<false>;
+  static constexpr auto back = nb64::k_chol_back;
+};
 
-void dense_factor_solve(double *L, int npad, int ld, double *Ldiag, double *x,
-                        const int *done, const DenseSchedule &sc,
-                        const DenseDev &dd, hipStream_t s) {
+// Level-scheduled, structure-aware blocked Cholesky (see ba_dense_sched.h): the forward
+// sweep over the non-tail levels, k_chol_tail, the backward sweep, as `pl` says.
+template <class K>
+void run_plan(double *L, int npad, int ld, double *Ldiag, double *x, const int *done,
+              const DenseSchedule &sc, const DenseDev &dd, const DenseLaunchPlan &pl, hipStream_t s) {
   int *bad = dd.bad_pivots;
   const int row_limit = npad + 16;  // rows that carry data (rhs = row npad)
-  // (the knobs are read when the schedule is uploaded, not once per LM iteration)
-  // BA_DENSE_SPLIT=1: separate diagonal and TRSM launches (the TRSM then spreads
-  // over one workgroup per row tile: better for dense patterns with many row
-  // tiles per column); default: the tile's workgroup also solves its row tiles
-  // (all row tiles of a column must fit the prefetched passes: 4 passes x
-  //  (4 waves / (nb/16)) tiles)
-  // (measured: letting the tile's workgroup fetch further passes as it goes — up to twice
-  //  the prefetched capacity — and running the level as one dataflow launch LOSES against
-  //  the three launches: C1 0.324 vs 0.316 ms, W20 1.148 vs 1.034 ms per iteration)
-  const bool split = dd.want_split || !dd.row_desc || sc.max_rows > 4 * (4 / (sc.nb / 16));
-  (void)row_limit;
-  // the last levels (at least two, together at most kTailCols columns) are
-  // handed to k_chol_tail: one launch instead of three per level (BA_DENSE_TAIL=0: off)
-  int tail_cols = 0;
-  const int tail_levels = dense_tail_levels(sc, dd, &tail_cols);
-  const int tail_c0 = tail_levels > 0 ? sc.lev_ptr[sc.nlev - tail_levels] * sc.nb : 0;
-  // two (independent) tiles in the first level of the block: their panels go side by side
-  const bool tail_pair = tail_levels > 0 && sc.nb == 32 &&
-                         sc.lev_ptr[sc.nlev - tail_levels + 1] - sc.lev_ptr[sc.nlev - tail_levels] == 2;
-  (void)tail_pair;
-  // one dataflow launch for the backward sweep (BA_DENSE_FLOW=0: one launch per level): the
-  // non-tail positions [0, back_t_end), uploaded top level first in dd.flow_order
-  const int back_t_end = sc.lev_ptr[sc.nlev - tail_levels];
-  const int n_back = back_t_end;
-  const bool flow = dd.want_flow && dd.flow_ok && dd.flow_order && dd.n_flow == n_back &&
-                    dd.flow_tail_t0 == back_t_end;
+  const int nlv = sc.nlev - pl.tail_levels;
   const int gen_now = ++dd.flow_gen;  // generation number of this solve (flags are never reset)
-  // Two forms of the dataflow BACKWARD sweep.  Narrow patterns: wait for all row tiles,
-  // then gather (their factor tiles prefetched).  Many row tiles per column (dense
-  // patterns: DENSE1K, up to ncb of them): that form puts a 3 MB gather behind the last
-  // hand-off (5.0 ms against 3.5 ms for one launch per level); the ORDERED form consumes
-  // the row tiles one by one as their flags come up.
-  const bool flow_back = flow && sc.max_rows <= 12;
-  // the three-kernel path (dense patterns) as one dataflow launch with lookahead (BA_DENSE_DAG=0:
-  // three launches per level)
-  const bool dag = flow && split && dd.want_dag && dd.dag_items && dd.n_dag_items > 0 &&
-                   (dd.n_dag_items <= DenseDev::kDagMaxItems || dd.force_dag) && !dd.force_look2 &&
-                   dd.fwd_flags && dd.fwd_cnt && dd.dag_dflags && dd.dag_tcnt && n_back > 0;
-  // ... and beyond that item count: lookahead inside one launch per level (BA_DENSE_LOOK2=0: off)
-  // (its waiting roles take their place from the block index: all of them — first targets, tiles
-  //  and TRSM items of a level — must be resident at once, whatever the dispatch order)
-  bool look2_fits = true;
-  for (int l = 0; l + 1 < sc.nlev - tail_levels && look2_fits; ++l)
-    look2_fits = (int)sc.tgt_first.size() > l &&
-                 sc.tgt_first[l] + (sc.lev_ptr[l + 2] - sc.lev_ptr[l + 1]) + (sc.item_ptr[l + 2] - sc.item_ptr[l + 1]) <= kFlowResident;
-  const bool look2 = flow && split && !dag && dd.want_look2 && look2_fits && dd.dag_dflags && dd.look_need &&
-                     dd.fwd_cnt &&
-                     sc.nlev - tail_levels >= 3 &&
-                     (int)sc.tgt_first.size() >= sc.nlev;
-  if (sc.nb == 32) {
-    BA_DENSE_RUN(nb32)
-  } else {
-    BA_DENSE_RUN(nb64)
+  // the role in a dataflow launch: the block index while the grid is resident, else a ticket
+  auto ticket = [&](int workgroups, int *counter) {
+    return (workgroups <= kFlowResident && !pl.force_ticket) ? nullptr : counter;
+  };
+  auto diag_and_trsm = [&](int l) {
+    const int t0 = sc.lev_ptr[l], nt = sc.lev_ptr[l + 1] - t0;
+    const int it0 = sc.item_ptr[l], ni = sc.item_ptr[l + 1] - it0;
+    BA_LAUNCH(K_CHOL_DIAG, K::diag, dim3(nt), dim3(256), s, L, ld, t0, Ldiag, done, bad);
+    if (ni > 0)
+      BA_LAUNCH(K_CHOL_TRSM, K::trsm, dim3(ni), dim3(K::NP * 64), s, L, ld, row_limit, it0, dd.item_t,
+                dd.item_I, Ldiag, done);
+  };
+  auto update = [&](int l) {
+    const int tg0 = sc.tgt_ptr[l], ng = sc.tgt_ptr[l + 1] - tg0;
+    if (ng > 0)
+      BA_LAUNCH(K_CHOL_UPDATE, K::update, dim3(ng), dim3(256), s, L, ld, tg0, dd.tgt_desc, dd.src_t, done);
+  };
+  switch (pl.fwd) {
+    case DenseFwd::kLook:
+      diag_and_trsm(0);
+      for (int l = 0; l + 1 < nlv; ++l) {
+        const int tg0 = sc.tgt_ptr[l], ng = sc.tgt_ptr[l + 1] - tg0, nf = sc.tgt_first[l];
+        const int t1 = sc.lev_ptr[l + 1], nt1 = sc.lev_ptr[l + 2] - t1;
+        const int it1 = sc.item_ptr[l + 1], ni1 = sc.item_ptr[l + 2] - it1;
+        BA_LAUNCH(K_CHOL_UPDATE, K::look, dim3(nt1 + ni1 + ng), dim3(256), s, L, ld, row_limit, nf, t1, nt1,
+                  it1, ni1, tg0, dd.item_t, dd.item_I, Ldiag, dd.tgt_desc, dd.src_t, dd.look_need, done, bad,
+                  dd.dag_dflags, dd.fwd_cnt, gen_now);
+      }
+      update(nlv - 1);
+      break;
+    case DenseFwd::kDag:
+      BA_LAUNCH(K_CHOL_UPDATE, K::dag, dim3(pl.n_dag_items), dim3(256), s, L, ld, row_limit,
+                (const int2 *)dd.dag_items, pl.n_dag_items, dd.item_t, dd.item_I, dd.dag_ntrsm, Ldiag,
+                dd.tgt_desc, dd.src_t, dd.upd_pre, dd.col_need, done, bad, dd.fwd_flags, dd.dag_dflags,
+                dd.dag_tcnt, dd.fwd_cnt, dd.fwd_ticket, gen_now);
+      break;
+    case DenseFwd::kLevelFlow:  // factorisation + TRSM and the updates that consume them
+      for (int l = 0; l < nlv; ++l) {
+        const int t0 = sc.lev_ptr[l], nt = sc.lev_ptr[l + 1] - t0;
+        const int tg0 = sc.tgt_ptr[l], ng = sc.tgt_ptr[l + 1] - tg0;
+        BA_LAUNCH(K_CHOL_DIAG_TRSM, K::level_flow, dim3(nt + ng), dim3(256), s, L, ld, npad, t0, nt, tg0, ng,
+                  dd.row_desc, dd.rows, Ldiag, dd.tgt_desc, dd.src_t, done, bad, dd.fwd_flags,
+                  ticket(nt + ng, dd.fwd_ticket), gen_now);
+      }
+      break;
+    case DenseFwd::kDiagTrsm:
+      for (int l = 0; l < nlv; ++l) {
+        const int t0 = sc.lev_ptr[l], nt = sc.lev_ptr[l + 1] - t0;
+        BA_LAUNCH(K_CHOL_DIAG_TRSM, K::diag_trsm, dim3(nt), dim3(256), s, L, ld, npad, t0, dd.row_desc,
+                  dd.rows, Ldiag, done, bad);
+        update(l);
+      }
+      break;
+    case DenseFwd::kSplit:
+      for (int l = 0; l < nlv; ++l) {
+        diag_and_trsm(l);
+        update(l);
+      }
+      break;
   }
+  if (pl.tail_levels > 0)
+    BA_LAUNCH(K_CHOL_TAIL, tail_kernel(pl), dim3(1), dim3(256), s, L, ld, npad, pl.tail_c0, dd.xc, x, dd.col_x,
+              done, bad);
+  const int n_back = pl.back_t_end;  // positions of the dataflow launch, top level first in dd.flow_order
+  const bool counted = pl.fwd == DenseFwd::kLook || pl.fwd == DenseFwd::kDag;  // (the sweep resets fwd_cnt)
+  switch (pl.back) {
+    case DenseBack::kFlowGather:
+    case DenseBack::kFlowOrdered:
+      BA_LAUNCH(K_CHOL_BACK, pl.back == DenseBack::kFlowOrdered ? K::back_flow_ordered : K::back_flow_gather,
+                dim3(n_back), dim3(256), s, L, ld, npad, dd.flow_order, n_back, pl.back_t_end, dd.back_desc,
+                dd.rows, Ldiag, dd.xc, x, dd.col_x, done, dd.flow_flags, ticket(n_back, dd.flow_ticket), gen_now,
+                bad, counted ? dd.fwd_cnt : nullptr, dd.n_fwd_cnt);
+      break;
+    case DenseBack::kPerLevel:
+      for (int l = nlv - 1; l >= 0; --l) {
+        const int t0 = sc.lev_ptr[l], nt = sc.lev_ptr[l + 1] - t0;
+        BA_LAUNCH(K_CHOL_BACK, K::back, dim3(nt), dim3(256), s, L, ld, npad, t0, dd.back_desc, dd.rows, Ldiag,
+                  dd.xc, x, dd.col_x, done);
+      }
+      break;
+  }
+}
+}  // namespace
+
+void dense_factor_solve(double *L, int npad, int ld, double *Ldiag, double *x, const int *done,
+                        const DenseSchedule &sc, const DenseDev &dd, const DenseLaunchPlan &plan,
+                        hipStream_t s) {
+  if (sc.nb == 32)
+    run_plan<Nb32>(L, npad, ld, Ldiag, x, done, sc, dd, plan, s);
+  else
+    run_plan<Nb64>(L, npad, ld, Ldiag, x, done, sc, dd, plan, s);
 }
 
 void launch_dense_solve(const DevProblem &d, const DenseSchedule &sc,
                         const DenseDev &dd, hipStream_t s) {
-  dense_factor_solve(d.L, d.npad, d.ld, d.Ldiag, d.x, &d.ctrl->done, sc, dd, s);
+  dense_factor_solve(d.L, d.npad, d.ld, d.Ldiag, d.x, &d.ctrl->done, sc, dd, dd.plan[dd.flow_ok], s);
 }
 
 }  // namespace ba

@@ -190,12 +190,12 @@ void build_one(int ncb, const std::vector<uint8_t> &adj_in, bool natural_order, 
 
 void build_dense_schedule(int ncb, const std::vector<uint8_t> &adj, bool natural_order, int nb,
                           DenseSchedule &s) {
-  const char *force = getenv("BA_DENSE_ORDER");  // "strict" | "relaxed" (developer knob)
-  if (natural_order || (force && force[0] == 's')) {
+  const char force = DenseKnobs::from_env().order;
+  if (natural_order || force == 's') {
     build_one(ncb, adj, natural_order, nb, false, s);
     return;
   }
-  if (force && force[0] == 'r') {
+  if (force == 'r') {
     build_one(ncb, adj, false, nb, true, s);
     return;
   }
@@ -206,6 +206,136 @@ void build_dense_schedule(int ncb, const std::vector<uint8_t> &adj, bool natural
   build_one(ncb, adj, false, nb, true, relaxed);
   auto chain = [](const DenseSchedule &q) { return q.nlev * (1.0 + 0.1 * q.max_rows); };
   if (chain(relaxed) < chain(s)) s = relaxed;
+}
+
+DenseKnobs DenseKnobs::from_env() {
+  auto value = [](const char *name) { const char *v = getenv(name); return v ? v : ""; };
+  auto first = [&](const char *name) { return value(name)[0]; };
+  auto number = [&](const char *name) { return atoi(value(name)); };
+  DenseKnobs k;
+  k.want_split = first("BA_DENSE_SPLIT") == '1';
+  k.want_tail = first("BA_DENSE_TAIL") != '0';
+  k.want_flow = first("BA_DENSE_FLOW") != '0';
+  k.want_dag = first("BA_DENSE_DAG") != '0';
+  k.force_dag = first("BA_DENSE_DAG") == '1';
+  k.want_look2 = first("BA_DENSE_LOOK2") != '0';
+  k.force_look2 = first("BA_DENSE_LOOK2") == '1';
+  k.force_ticket = first("BA_DENSE_TICKET") == '1';
+  k.natural = number("BA_DENSE_NATURAL") != 0;
+  k.full = number("BA_DENSE_FULL") != 0;
+  k.nb = number("BA_DENSE_NB");
+  const char o = first("BA_DENSE_ORDER");
+  k.order = (o == 's' || o == 'r') ? o : '\0';
+  return k;
+}
+
+const char *dense_fwd_name(DenseFwd f) {
+  static const char *const names[] = {"look", "dag", "level_flow", "diag_trsm", "split"};
+  return names[(int)f];
+}
+const char *dense_back_name(DenseBack b) {
+  static const char *const names[] = {"flow_gather", "flow_ordered", "per_level"};
+  return names[(int)b];
+}
+
+DenseLaunchPlan dense_launch_plan(const DenseSchedule &sc, const DenseKnobs &knobs, bool flow_allowed,
+                                  bool lists_fit) {
+  DenseLaunchPlan p;
+  p.force_ticket = knobs.force_ticket;
+  p.split = knobs.want_split || sc.max_rows > dense_fused_max_rows(sc.nb);
+  if (knobs.want_tail) {
+    for (int l = sc.nlev - 1; l >= 0; --l) {
+      const int cols = (sc.lev_ptr[l + 1] - sc.lev_ptr[l]) * sc.nb;
+      if (p.tail_cols + cols > kTailCols) break;
+      p.tail_cols += cols;
+      ++p.tail_levels;
+    }
+    if (p.tail_levels < 2 || (p.tail_cols != 64 && p.tail_cols != 96)) p.tail_levels = p.tail_cols = 0;
+  }
+  const int nlv = sc.nlev - p.tail_levels;  // levels of the sweeps
+  p.back_t_end = sc.lev_ptr[nlv];
+  if (p.tail_levels > 0) {
+    p.tail_c0 = p.back_t_end * sc.nb;
+    p.tail_pair = sc.nb == 32 && sc.lev_ptr[nlv + 1] - sc.lev_ptr[nlv] == 2;
+  }
+  const bool lookahead_lists = p.split && nlv >= 2 && (int)sc.tgt_first.size() >= sc.nlev;
+  // (dense_dag_items: level 0's tiles and TRSM items, then per level its targets and the next level's)
+  if (lookahead_lists) p.n_dag_items = sc.lev_ptr[nlv] + sc.item_ptr[nlv] + sc.tgt_ptr[nlv];
+  const bool flow = knobs.want_flow && flow_allowed && lists_fit;
+  const bool dag = flow && lookahead_lists && knobs.want_dag && !knobs.force_look2 &&
+                   (p.n_dag_items <= kDagMaxItems || knobs.force_dag);
+  // k_chol_look's waiting roles take their place from the block index: all of them — first
+  // targets, tiles and TRSM items of a level — must be resident at once, whatever the dispatch order
+  bool look_fits = lookahead_lists && nlv >= 3;
+  for (int l = 0; l + 1 < nlv && look_fits; ++l)
+    look_fits = sc.tgt_first[l] + (sc.lev_ptr[l + 2] - sc.lev_ptr[l + 1]) +
+                    (sc.item_ptr[l + 2] - sc.item_ptr[l + 1]) <= kFlowResident;
+  const bool look = flow && !dag && knobs.want_look2 && look_fits;
+  p.fwd = look ? DenseFwd::kLook
+        : dag ? DenseFwd::kDag
+        : p.split ? DenseFwd::kSplit
+        : flow ? DenseFwd::kLevelFlow : DenseFwd::kDiagTrsm;
+  p.back = !flow || p.back_t_end == 0 ? DenseBack::kPerLevel
+         : sc.max_rows <= kBackGatherMaxRows ? DenseBack::kFlowGather : DenseBack::kFlowOrdered;
+  return p;
+}
+
+DenseLaunchPlan dense_launch_plan_no_tail(const DenseSchedule &sc, DenseKnobs knobs, bool flow_allowed,
+                                          const DenseLaunchPlan &uploaded) {
+  knobs.want_tail = false;
+  return dense_launch_plan(sc, knobs, flow_allowed, /*lists_fit=*/uploaded.tail_levels == 0);
+}
+
+void dense_flow_order(const DenseSchedule &sc, const DenseLaunchPlan &plan, std::vector<int> &order) {
+  order.clear();
+  for (int l = sc.nlev - plan.tail_levels - 1; l >= 0; --l)
+    for (int t = sc.lev_ptr[l]; t < sc.lev_ptr[l + 1]; ++t) order.push_back(t);
+}
+
+void dense_dag_items(const DenseSchedule &sc, const DenseLaunchPlan &plan, std::vector<int> &items,
+                     std::vector<int> &pre, std::vector<int> &need, std::vector<int> &ntrsm,
+                     std::vector<int> &look_need) {
+  const int nlv = sc.nlev - plan.tail_levels;
+  items.clear();
+  pre.assign(std::max<size_t>(1, sc.tgt_J.size()), 0);
+  need.assign((size_t)sc.ncb + 1, 0);
+  ntrsm.assign((size_t)sc.ncb + 1, 0);
+  look_need.assign((size_t)sc.ncb + 1, 0);
+  for (size_t q = 0; q < sc.item_t.size(); ++q) ++ntrsm[sc.item_t[q]];
+  auto push = [&](int kind, int id) {
+    items.push_back(kind);
+    items.push_back(id);
+  };
+  auto tiles_of = [&](int l) {
+    for (int t = sc.lev_ptr[l]; t < sc.lev_ptr[l + 1]; ++t) push(0, t);
+    for (int q = sc.item_ptr[l]; q < sc.item_ptr[l + 1]; ++q) push(1, q);
+  };
+  tiles_of(0);
+  for (int l = 0; l < nlv; ++l) {
+    const int tg0 = sc.tgt_ptr[l], tg1 = sc.tgt_ptr[l + 1], nf = sc.tgt_first[l];
+    for (int tg = tg0; tg < tg1; ++tg) pre[tg] = need[sc.tgt_J[tg]];  // (updates of EARLIER levels)
+    for (int tg = tg0; tg < tg0 + nf; ++tg) {
+      push(2, tg);
+      ++look_need[sc.tgt_J[tg]];  // (k_chol_look: the "first" targets of the level before the tile's)
+    }
+    if (l + 1 < nlv) tiles_of(l + 1);  // the next level's tiles beside the bulk of this level's update
+    for (int tg = tg0 + nf; tg < tg1; ++tg) push(2, tg);
+    for (int tg = tg0; tg < tg1; ++tg) ++need[sc.tgt_J[tg]];
+  }
+}
+
+int dense_pick_tile_order(const DenseSchedule &s32, const DenseSchedule &s64, int force_nb) {
+  // NARROW patterns (every column tile has at most five row tiles below it besides the rhs
+  // block: windows of <= ~15 poses) are latency-bound chains of dependent launches, one set
+  // per level, whose cost is a fixed latency plus a term proportional to the tile order: the
+  // cheaper chain wins.  Wider and dense patterns are bound by the work per level (row tiles
+  // per column, MFMA tile size) and run faster at 64.
+  const double level_us[2] = {16.0, 30.0};
+  const bool narrow = s32.max_rows <= 6;
+  int pick = (narrow && s32.nlev * level_us[0] <= s64.nlev * level_us[1]) ? 0 : 1;
+  if (force_nb == 32) pick = 0;
+  if (force_nb == 64) pick = 1;
+  return pick;
 }
 
 }  // namespace ba

@@ -62,5 +62,91 @@ struct DenseSchedule {
 void build_dense_schedule(int ncb, const std::vector<uint8_t> &adj,
                           bool natural_order, int nb, DenseSchedule &s);
 
+// ---- which kernels run a schedule (launched by dense_factor_solve, ba_dense.hip) ----
+// DESIGN.md ("launch paths of the dense solve") has the measurements behind the defaults.
+
+// Columns of the block that k_chol_tail factors in LDS (ba_chol_lds.h).
+constexpr int kTailCols = 96;
+// Workgroups of a dataflow launch that are certainly resident at once on the part (256
+// CUs x 2 workgroups of 256 threads at the kernels' register budgets, with a margin):
+// up to here the role is the block index, beyond it a ticket (ba_dense_tile.inc).
+constexpr int kFlowResident = 448;
+// k_chol_dag takes the forward sweep up to this many items, k_chol_look beyond.
+constexpr int kDagMaxItems = 16384;
+// The backward dataflow sweep gathers up to this many row tiles per column (incl. the rhs
+// block) and consumes them in order beyond.
+constexpr int kBackGatherMaxRows = 12;
+// Row tiles per column (incl. the rhs block) that a tile's own workgroup solves: they must
+// fit its prefetched passes, 4 passes x (4 waves / (nb / 16)) tiles.
+inline int dense_fused_max_rows(int nb) { return 4 * (4 / (nb / 16)); }
+
+// The BA_DENSE_* environment variables.
+struct DenseKnobs {
+  bool want_split = false;                      // SPLIT=1: separate diagonal and TRSM launches
+  bool want_tail = true;                        // TAIL=0: no k_chol_tail
+  bool want_flow = true;                        // FLOW=0: no dataflow launch
+  bool want_dag = true, force_dag = false;      // DAG=0: no k_chol_dag; =1: also beyond kDagMaxItems
+  bool want_look2 = true, force_look2 = false;  // LOOK2=0: no k_chol_look; =1: instead of k_chol_dag too
+  bool force_ticket = false;                    // TICKET=1: tickets even when the grid is resident (test knob)
+  bool natural = false, full = false;           // NATURAL=1, FULL=1: debug orderings / patterns
+  int nb = 0;                                   // NB=32|64: tile order (0: dense_pick_tile_order decides)
+  char order = 0;                               // ORDER=strict|relaxed: 's' / 'r' (developer knob)
+  static DenseKnobs from_env();
+};
+
+enum class DenseFwd {
+  kLook,       // k_chol_look: one launch per level with lookahead into the next
+  kDag,        // k_chol_dag: every non-tail level in one dataflow launch
+  kLevelFlow,  // k_chol_level_flow: one dataflow launch per level
+  kDiagTrsm,   // k_chol_diag_trsm + k_chol_update per level
+  kSplit       // k_chol_diag + k_chol_trsm + k_chol_update per level
+};
+enum class DenseBack {
+  kFlowGather,   // k_chol_back_flow<false>: one launch, waits for all row tiles, then gathers
+  kFlowOrdered,  // k_chol_back_flow<true>: one launch, consumes the row tiles as their flags come up
+  kPerLevel      // k_chol_back per level
+};
+const char *dense_fwd_name(DenseFwd f);
+const char *dense_back_name(DenseBack b);
+
+struct DenseLaunchPlan {
+  bool split = false;  // the tile's workgroup does not solve its own row tiles
+  // the last levels (at least two, together 64 or 96 columns) go to k_chol_tail
+  int tail_levels = 0, tail_cols = 0, tail_c0 = 0;
+  bool tail_pair = false;  // two (independent) 32-column tiles in the block's first level: panels side by side
+  int back_t_end = 0;      // the sweeps cover the positions [0, back_t_end): the non-tail levels
+  int n_dag_items = 0;     // items of dense_dag_items for this tail; 0: k_chol_dag / k_chol_look do not apply
+  DenseFwd fwd = DenseFwd::kSplit;
+  DenseBack back = DenseBack::kPerLevel;
+  bool force_ticket = false;
+};
+
+// The one place that decides.  `flow_allowed`: false while a captured graph is in use (the
+// generation number of a dataflow launch is a kernel argument).  `lists_fit`: the uploaded
+// dataflow lists (dense_flow_order, dense_dag_items) were built for this plan's tail; a plan
+// whose tail differs from the uploaded one takes no dataflow launch.
+DenseLaunchPlan dense_launch_plan(const DenseSchedule &sc, const DenseKnobs &knobs, bool flow_allowed,
+                                  bool lists_fit = true);
+// The plan that hands no level to k_chol_tail (which keeps its block's factor in LDS: only
+// x leaves), for a caller that needs the whole factor in the image.  `uploaded`: the plan
+// the device lists were built for.
+DenseLaunchPlan dense_launch_plan_no_tail(const DenseSchedule &sc, DenseKnobs knobs, bool flow_allowed,
+                                          const DenseLaunchPlan &uploaded);
+
+// Positions of the backward sweep's dataflow launch, top level first (plan.back_t_end of them).
+void dense_flow_order(const DenseSchedule &sc, const DenseLaunchPlan &plan, std::vector<int> &order);
+// Work list of the three-kernel path as one dataflow launch (k_chol_dag): items = {kind, index}
+// pairs in lookahead order (kind 0: tile position, 1: TRSM item, 2: update target), pre[tg] =
+// updates of earlier levels on the target's column, need[p] = all updates on position p's column,
+// ntrsm[p] = TRSM items of position p, look_need[p] = the previous level's first targets in
+// p's column (k_chol_look).  Call only if plan.n_dag_items > 0.
+void dense_dag_items(const DenseSchedule &sc, const DenseLaunchPlan &plan, std::vector<int> &items,
+                     std::vector<int> &pre, std::vector<int> &need, std::vector<int> &ntrsm,
+                     std::vector<int> &look_need);
+
+// Tile order of a problem from its two candidate schedules: 0 (nb32) or 1 (nb64); force_nb
+// = 32 | 64 overrides (DenseKnobs::nb).
+int dense_pick_tile_order(const DenseSchedule &s32, const DenseSchedule &s64, int force_nb);
+
 }  // namespace ba
 #endif

@@ -9,6 +9,8 @@
 
 #include <vector>
 
+#include "ba_dense_sched.h"
+
 namespace ba {
 
 // LM controller state, resident in device memory so that a whole batch of
@@ -323,56 +325,19 @@ struct DenseDev {
   int n_fwd_cnt = 0;
   int *dag_items = nullptr, *dag_ntrsm = nullptr, *dag_dflags = nullptr, *dag_tcnt = nullptr;
   int *look_need = nullptr;  // k_chol_look: per position, the previous level's targets in its column
-  int n_dag_items = 0;
-  // BA_DENSE_DAG=0: three launches per level; =1: also beyond kDagMaxItems.  Measured (MI355X):
-  // moderately filled patterns gain — C1 0.304 -> 0.286 ms per iteration (forward sweep 188 ->
-  // 145 us), W20 367 -> 303 us —, DENSE patterns LOSE: DENSE1K 5.5 -> 7.1 ms, n = 5 970 5.1 ->
-  // 6.2 ms: 145 k update workgroups of ~3 us each pay ticket + descriptor + poll + late
-  // target load (~5 us of dependent latency) at 2-3 workgroups per CU (the launch carries
-  // the tile kernel's registers and LDS) against 4+ for the plain update kernel
-  bool want_look2 = true, force_look2 = false;  // BA_DENSE_LOOK2=0: no in-launch lookahead on dense patterns; =1: instead of k_chol_dag too
-  bool want_dag = true, force_dag = false;
-  static constexpr int kDagMaxItems = 16384;
-  int n_flow = 0, flow_tail_t0 = 0;
   mutable int flow_gen = 0;
+  // what dense_factor_solve launches (ba_dense_sched.h), as decided when the schedule was
+  // uploaded: plan[flow_ok]
+  DenseKnobs knobs;
+  DenseLaunchPlan plan[2];
   bool flow_ok = true;  // false while a hipGraph is captured / replayed (the generation is a kernel argument)
-  bool want_flow = true;
-  bool force_ticket = false;  // BA_DENSE_TICKET=1: tickets even when the grid is resident (test knob)
-  // BA_DENSE_SPLIT / BA_DENSE_TAIL as found when the schedule was uploaded
-  bool want_split = false, want_tail = true;
-  void read_env() {
-    const char *s = getenv("BA_DENSE_SPLIT"), *t = getenv("BA_DENSE_TAIL");
-    want_split = s && s[0] == '1';
-    want_tail = !(t && t[0] == '0');
-    const char *fl = getenv("BA_DENSE_FLOW");
-    want_flow = !(fl && fl[0] == '0');
-    const char *dg = getenv("BA_DENSE_DAG");
-    want_dag = !(dg && dg[0] == '0');
-    force_dag = dg && dg[0] == '1';
-    const char *l2 = getenv("BA_DENSE_LOOK2");
-    want_look2 = !(l2 && l2[0] == '0');
-    force_look2 = l2 && l2[0] == '1';
-    const char *tk = getenv("BA_DENSE_TICKET");
-    force_ticket = tk && tk[0] == '1';
-  }
 };
-struct DenseSchedule;
 void launch_dense_solve(const DevProblem &d, const DenseSchedule &sc,
                         const DenseDev &dd, hipStream_t s);
-// stand-alone form for ba_dense_spd_solve (x receives n_x entries via col_x)
+// stand-alone form for ba_dense_spd_solve (x receives n_x entries via col_x) and ba_covariance
 void dense_factor_solve(double *L, int npad, int ld, double *Ldiag, double *x,
                         const int *done_flag, const DenseSchedule &sc,
-                        const DenseDev &dd, hipStream_t s);
-// positions of the dataflow backward sweep (top level first); returns the tail block's first position
-int dense_flow_order(const DenseSchedule &sc, const DenseDev &dd, std::vector<int> &order);
-// work list of the three-kernel path as one dataflow launch (k_chol_dag): items = {kind, index}
-// pairs in lookahead order (kind 0: tile position, 1: TRSM item, 2: update target), pre[tg] =
-// updates of earlier levels on the target's column, need[p] = all updates on position p's column,
-// ntrsm[p] = TRSM items of position p, look_need[p] = the previous level's first targets in
-// p's column (k_chol_look); false if the path does not apply
-bool dense_dag_items(const DenseSchedule &sc, const DenseDev &dd, std::vector<int> &items,
-                     std::vector<int> &pre, std::vector<int> &need, std::vector<int> &ntrsm,
-                     std::vector<int> &look_need);
+                        const DenseDev &dd, const DenseLaunchPlan &plan, hipStream_t s);
 void launch_dense_init(double *L, int ld, const int *col_x, const int *zt_I,
                        const int *zt_J, int n_zt, int nb, const int *done_flag,
                        hipStream_t s);

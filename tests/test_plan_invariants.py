@@ -80,3 +80,21 @@ def test_dense_level_schedule_executes_to_the_dense_solution(tmp_path):
                     os.path.join(CSRC, "ba_dense_sched.cpp"), "-o", exe], check=True)
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0 and "DENSE SCHEDULE CHECK OK" in r.stdout, r.stdout[-3000:]
+
+
+def test_dense_launch_plan_equals_the_launch_macro_it_replaced(tmp_path):
+    """csrc/ba_dense_sched.cpp dense_launch_plan / dense_flow_order / dense_dag_items /
+    dense_pick_tile_order: for band / dense / random / disconnected tile patterns at both
+    tile orders, crossed with every BA_DENSE_* setting, "dataflow not allowed" and the
+    no-tail variant ba_covariance asks for, the plan equals line by line the table in
+    tests/cpp/dense_launch_expected.txt.  The table was produced by the decision expressions
+    of the launch macro the plan replaced, lifted verbatim into a stand-alone program (not
+    by the code under test).  The check also asserts the plan's invariants and that its
+    cases reach every forward sweep, backward sweep and tail form."""
+    exe = str(tmp_path / "dense_launch_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I", CSRC,
+                    os.path.join(ROOT, "tests", "cpp", "dense_launch_check.cpp"),
+                    os.path.join(CSRC, "ba_dense_sched.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe, os.path.join(ROOT, "tests", "cpp", "dense_launch_expected.txt")],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and "DENSE LAUNCH CHECK OK" in r.stdout, r.stdout[-3000:]
