@@ -21,6 +21,7 @@ int ba::fail(const std::string &m) {
   return -1;
 }
 using ba::fail;
+using ba::Mem;
 
 namespace {
 
@@ -189,13 +190,14 @@ int download(std::vector<T> &out, const T *dev, size_t n, hipStream_t s) {
 int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::vector<int> &col_x,
                           ba::DenseDev &dd) {
   const size_t npad = col_x.size(), ncb = (size_t)std::max(1, sc.ncb);
-  if (h->upload(&dd.row_ptr, sc.row_ptr) || h->upload(&dd.rows, sc.rows) ||
-      h->upload(&dd.item_t, sc.item_t) || h->upload(&dd.item_I, sc.item_I) ||
-      h->upload(&dd.tgt_I, sc.tgt_I) || h->upload(&dd.tgt_J, sc.tgt_J) ||
-      h->upload(&dd.tgt_src_ptr, sc.tgt_src_ptr) || h->upload(&dd.src_t, sc.src_t) ||
-      h->upload(&dd.tgt_desc, sc.tgt_desc) || h->upload(&dd.back_desc, sc.back_desc) ||
-      h->upload(&dd.row_desc, sc.row_desc) || h->upload(&dd.col_x, col_x) ||
-      h->dalloc(&dd.xc, npad) || h->dalloc(&dd.bad_pivots, (size_t)1))
+  constexpr Mem R = Mem::Resident;  // a dense system is pose-sized and shared by every chunk
+  if (h->upload(R, &dd.row_ptr, sc.row_ptr) || h->upload(R, &dd.rows, sc.rows) ||
+      h->upload(R, &dd.item_t, sc.item_t) || h->upload(R, &dd.item_I, sc.item_I) ||
+      h->upload(R, &dd.tgt_I, sc.tgt_I) || h->upload(R, &dd.tgt_J, sc.tgt_J) ||
+      h->upload(R, &dd.tgt_src_ptr, sc.tgt_src_ptr) || h->upload(R, &dd.src_t, sc.src_t) ||
+      h->upload(R, &dd.tgt_desc, sc.tgt_desc) || h->upload(R, &dd.back_desc, sc.back_desc) ||
+      h->upload(R, &dd.row_desc, sc.row_desc) || h->upload(R, &dd.col_x, col_x) ||
+      h->dalloc(R, &dd.xc, npad) || h->dalloc(R, &dd.bad_pivots, (size_t)1))
     return -1;
   HIP_TRY(hipMemset(dd.xc, 0, npad * sizeof(double)));
   HIP_TRY(hipMemset(dd.bad_pivots, 0, sizeof(int)));
@@ -205,8 +207,8 @@ int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::
   std::vector<int> order;
   ba::dense_flow_order(sc, plan, order);
   dd.flow_gen = 0;
-  if (h->upload(&dd.flow_order, order) || h->dalloc(&dd.flow_flags, ncb) || h->dalloc(&dd.flow_ticket, (size_t)1) ||
-      h->dalloc(&dd.fwd_flags, ncb) || h->dalloc(&dd.fwd_ticket, (size_t)1))
+  if (h->upload(R, &dd.flow_order, order) || h->dalloc(R, &dd.flow_flags, ncb) || h->dalloc(R, &dd.flow_ticket, (size_t)1) ||
+      h->dalloc(R, &dd.fwd_flags, ncb) || h->dalloc(R, &dd.fwd_ticket, (size_t)1))
     return -1;
   HIP_TRY(hipMemset(dd.flow_flags, 0, ncb * sizeof(int)));
   HIP_TRY(hipMemset(dd.flow_ticket, 0, sizeof(int)));
@@ -216,15 +218,325 @@ int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::
     std::vector<int> items, pre, need, ntrsm, lneed;
     ba::dense_dag_items(sc, plan, items, pre, need, ntrsm, lneed);
     dd.n_fwd_cnt = (int)need.size();
-    if (h->upload(&dd.dag_items, items) || h->upload(&dd.upd_pre, pre) || h->upload(&dd.col_need, need) ||
-        h->upload(&dd.dag_ntrsm, ntrsm) || h->upload(&dd.look_need, lneed) || h->dalloc(&dd.fwd_cnt, need.size()) ||
-        h->dalloc(&dd.dag_dflags, need.size()) || h->dalloc(&dd.dag_tcnt, need.size()))
+    if (h->upload(R, &dd.dag_items, items) || h->upload(R, &dd.upd_pre, pre) || h->upload(R, &dd.col_need, need) ||
+        h->upload(R, &dd.dag_ntrsm, ntrsm) || h->upload(R, &dd.look_need, lneed) || h->dalloc(R, &dd.fwd_cnt, need.size()) ||
+        h->dalloc(R, &dd.dag_dflags, need.size()) || h->dalloc(R, &dd.dag_tcnt, need.size()))
       return -1;
     HIP_TRY(hipMemset(dd.fwd_cnt, 0, need.size() * sizeof(int)));
     HIP_TRY(hipMemset(dd.dag_dflags, 0, need.size() * sizeof(int)));
     HIP_TRY(hipMemset(dd.dag_tcnt, 0, need.size() * sizeof(int)));
   }
   return 0;
+}
+
+// ---- the steps of ba_finalize, in the order it runs them.  Every dalloc / upload names
+// its residency (ba_handle.h: Mem); the ORDER of the chunk allocations fixes the layout
+// of a streamed chunk's host image (ba_stream.hip).
+
+// The plan of this handle's shard, and the sizes the device code reads from it.
+int finalize_plan(ba_handle *h) {
+  ba::PlanInput in;
+  in.n_cam = h->n_cam;
+  in.n_pose = h->n_pose;
+  in.pose_fixed = h->pose_fixed.data();
+  in.n_pt = h->n_pt;
+  in.pt_fixed = h->pt_fixed.data();
+  in.n_obs = h->n_obs;
+  in.obs_cam = h->obs_cam.data();
+  in.obs_pose = h->obs_pose.data();
+  in.obs_pt = h->obs_pt.data();
+  in.obs_uv = h->obs_uv.data();
+  in.rank = h->rank;
+  in.world = h->world;
+  std::string err = ba::build_plan(in, h->plan);
+  if (!err.empty()) return fail("ba_finalize: " + err);
+  const ba::Plan &pl = h->plan;
+  ba::DevProblem &d = h->d;
+  std::memset(&d, 0, sizeof(d));
+  d.n_cam = pl.n_cam; d.n_pose = pl.n_pose; d.N = pl.N; d.n_pt = pl.n_pt;
+  d.M = pl.M; d.M_global = pl.M_global; d.n_obs = pl.n_obs;
+  d.n_obs_opt = pl.n_obs_opt; d.n_obs_global = pl.n_obs_global; d.P = pl.P;
+  d.n_pobs = pl.n_pobs; d.T = pl.T; d.B = pl.B;
+  d.n_achunk = (int)pl.achunk_pose.size();
+  d.n_tchunk = (int)pl.tchunk_blk.size();
+  return 0;
+}
+
+// Cameras, poses and points in the internal order (both parameter buffers).
+int upload_parameters(ba_handle *h) {
+  const ba::Plan &pl = h->plan;
+  ba::DevProblem &d = h->d;
+  std::vector<double> cams((size_t)pl.n_cam * 16);
+  for (int c = 0; c < pl.n_cam; ++c) {
+    std::memcpy(&cams[(size_t)c * 16], &h->cam_intr[(size_t)c * 4], 4 * sizeof(double));
+    std::memcpy(&cams[(size_t)c * 16 + 4], &h->cam_T[(size_t)c * 12], 12 * sizeof(double));
+  }
+  if (h->upload(Mem::Resident, &d.cams, cams)) return -1;
+  std::vector<double> poses((size_t)pl.n_pose * 12);
+  for (int p = 0; p < pl.n_pose; ++p)
+    std::memcpy(&poses[(size_t)p * 12], &h->pose_T[(size_t)pl.pose_user_of_int[p] * 12],
+                12 * sizeof(double));
+  if (h->upload(Mem::Resident, &d.poses[0], poses) || h->upload(Mem::Resident, &d.poses[1], poses)) return -1;
+  std::vector<double> pts((size_t)pl.n_pt * 3);
+  for (int q = 0; q < pl.n_pt; ++q)
+    std::memcpy(&pts[(size_t)q * 3], &h->pt_X[(size_t)pl.pt_user_of_int[q] * 3],
+                3 * sizeof(double));
+  if (h->upload(Mem::ChunkState, &d.pts[0], pts) || h->upload(Mem::ChunkState, &d.pts[1], pts)) return -1;
+  return 0;
+}
+
+// 16-int record per S block: its pose pair, its slot contributions (the first 8 inline)
+// and its triangle chunks
+std::vector<int32_t> make_blk_desc(const ba::Plan &pl) {
+  std::vector<int32_t> bd((size_t)pl.B * 16, 0);
+  for (int64_t bk = 0; bk < pl.B; ++bk) {
+    int32_t *r = bd.data() + 16 * bk;
+    const int64_t c0 = pl.blk_contrib_ptr[bk], c1 = pl.blk_contrib_ptr[bk + 1];
+    r[0] = pl.sblk_j[bk];
+    r[1] = pl.sblk_k[bk];
+    r[2] = (int32_t)c0;
+    r[3] = (int32_t)(c1 - c0);
+    r[4] = pl.sblk_tchunk_ptr[bk];
+    r[5] = pl.sblk_tchunk_ptr[bk + 1] - pl.sblk_tchunk_ptr[bk];
+    for (int t = 0; t < 8; ++t) r[8 + t] = c0 + t < c1 ? pl.contrib_slot[c0 + t] : 0;
+  }
+  return bd;
+}
+
+// first pair / observation / landmark and the counts of every landmark chunk
+std::vector<ba::DevProblem::LmChunk> make_lm_chunks(const ba::Plan &pl) {
+  std::vector<ba::DevProblem::LmChunk> lc(pl.bchunk_lm.size() - 1);
+  for (size_t c = 0; c < lc.size(); ++c) {
+    const int l0 = pl.bchunk_lm[c], l1 = pl.bchunk_lm[c + 1];
+    lc[c].pb = pl.lm_pair_ptr[l0];
+    lc[c].ob = pl.lm_obs_ptr[l0];
+    lc[c].l0 = l0;
+    lc[c].nl = l1 - l0;
+    lc[c].np = (int32_t)(pl.lm_pair_ptr[l1] - pl.lm_pair_ptr[l0]);
+    lc[c].no = (int32_t)(pl.lm_obs_ptr[l1] - pl.lm_obs_ptr[l0]);
+  }
+  return lc;
+}
+
+// Structure, first half: observations and the index lists over them.  Where the planner's
+// element type differs from the device's (flat int32 / double vectors, its own mirror of a
+// descriptor) the static_asserts pin the layout and the upload takes the host pointer and
+// the record count.
+int upload_observation_lists(ba_handle *h) {
+  const ba::Plan &pl = h->plan;
+  ba::DevProblem &d = h->d;
+  static_assert(sizeof(int4) == 16 && sizeof(double2) == 16 && sizeof(int2) == 8, "layout");
+  if (h->upload(Mem::ChunkConst, &d.obs_idx, pl.obs_idx.data(), (size_t)pl.n_obs) ||
+      h->upload(Mem::ChunkConst, &d.obs_uv, pl.obs_uv.data(), (size_t)pl.n_obs))
+    return -1;
+  // slim landmark-major record for the cost kernel (no pair id, 8 bytes)
+  const char *wide = getenv("BA_COST_WIDE");  // test knob: keep k_cost on the 16-byte records
+  if (!pl.obs_cp.empty() && pl.n_obs > 0 && !(wide && wide[0] == '1'))  // (filled by the planner's threaded pass)
+    if (h->upload(Mem::ChunkConst, &d.obs_cp, pl.obs_cp.data(), (size_t)pl.n_obs)) return -1;
+  if (h->upload(Mem::ChunkConst, &d.pobs_idx, pl.pobs_idx.data(), (size_t)pl.n_pobs) ||
+      h->upload(Mem::ChunkConst, &d.pobs_uv, pl.pobs_uv.data(), (size_t)pl.n_pobs) ||
+      h->upload(Mem::ChunkConst, &d.lm_obs_ptr, pl.lm_obs_ptr) ||
+      h->upload(Mem::ChunkConst, &d.lm_pair_ptr, pl.lm_pair_ptr) ||
+      h->upload(Mem::ChunkConst, &d.pair_pose, pl.pair_pose) || h->upload(Mem::ChunkConst, &d.pair_lm, pl.pair_lm) ||
+      h->upload(Mem::ChunkConst, &d.achunk_pose, pl.achunk_pose) ||
+      h->upload(Mem::ChunkConst, &d.achunk_begin, pl.achunk_begin) ||
+      h->upload(Mem::ChunkConst, &d.achunk_end, pl.achunk_end) ||
+      h->upload(Mem::ChunkConst, &d.pose_achunk_ptr, pl.pose_achunk_ptr))
+    return -1;
+  // the block numbering of S is global and k_scatter reads it while no particular chunk
+  // is resident: DESIGN.md §6b "Residency"
+  if (h->upload(Mem::Resident, &d.sblk_j, pl.sblk_j) || h->upload(Mem::Resident, &d.diag_blk, pl.diag_blk) ||
+      h->upload(Mem::Resident, &d.sblk_k, pl.sblk_k))
+    return -1;
+  if (pl.contrib_slot.size() >= (size_t)INT32_MAX) return fail("too many slot contributions for int32 indices");
+  if (h->upload(Mem::ChunkConst, &d.tri_p, pl.tri_p) || h->upload(Mem::ChunkConst, &d.tri_q, pl.tri_q) ||
+      h->upload(Mem::ChunkConst, &d.tchunk_blk, pl.tchunk_blk) ||
+      h->upload(Mem::ChunkConst, &d.tchunk_begin, pl.tchunk_begin) ||
+      h->upload(Mem::ChunkConst, &d.tchunk_end, pl.tchunk_end) ||
+      h->upload(Mem::ChunkConst, &d.sblk_tchunk_ptr, pl.sblk_tchunk_ptr) ||
+      h->upload(Mem::ChunkConst, &d.ltri, pl.ltri) || h->upload(Mem::ChunkConst, &d.chunk_sp, pl.chunk_sp) ||
+      h->upload(Mem::ChunkConst, &d.sup_lane, pl.sup_lane) ||
+      h->upload(Mem::ChunkConst, &d.blk_contrib_ptr, pl.blk_contrib_ptr) ||
+      h->upload(Mem::ChunkConst, &d.contrib_slot, pl.contrib_slot) ||
+      h->upload(Mem::ChunkConst, &d.blk_desc, make_blk_desc(pl)) ||
+      h->upload(Mem::ChunkConst, &d.bchunk_lm, pl.bchunk_lm) ||
+      h->upload(Mem::ChunkConst, &d.lm_chunk, make_lm_chunks(pl)))
+    return -1;
+  return 0;
+}
+
+// Structure, second half: the descriptors of super-runs, chunks and covisibility groups
+// and the slot partials that go with them.
+int upload_descriptors_and_groups(ba_handle *h) {
+  const ba::Plan &pl = h->plan;
+  ba::DevProblem &d = h->d;
+  d.n_sup = (int)pl.sup_desc.size();
+  d.n_bchunk = (int)pl.bchunk_lm.size() - 1;
+  d.n_slot = (int)pl.slot_blk.size();
+  static_assert(sizeof(ba::Plan::SupDesc) == sizeof(ba::DevProblem::SupDesc), "desc layout");
+  static_assert(sizeof(ba::Plan::ChunkDesc) == sizeof(ba::DevProblem::ChunkDesc), "desc layout");
+  static_assert(sizeof(ba::Plan::GrpDesc) == sizeof(ba::DevProblem::GrpDesc) && sizeof(ba::Plan::GrpDesc) == 128,
+                "group descriptor layout");
+  static_assert(sizeof(ba::Plan::LinDesc) == sizeof(ba::DevProblem::LinDesc) && sizeof(ba::Plan::LinDesc) == 48,
+                "group linearisation descriptor layout");
+  d.n_grp32 = (int)pl.grp32.size();
+  d.n_grp64 = (int)pl.grp64.size();
+  d.n_grp128 = (int)pl.grp128.size();
+  // k_lin_grp: observation patterns, pose-side partial sums of the group pieces
+  d.lin_chunk0 = pl.lin_groups ? pl.n_bchunk_grp : 0;
+  d.n_lin_desc = (int)pl.lin_desc.size();
+  d.n_lin_plain = pl.n_lin_plain;
+  d.n_bs_grp = d.n_lin_desc;
+  d.n_lm_part = d.n_bs_grp + (d.n_bchunk - d.lin_chunk0 + ba::kBsChunks - 1) / ba::kBsChunks;
+  d.n_lin_cost = d.n_bchunk + d.n_lin_desc;
+  if (h->upload(Mem::ChunkConst, &d.sup_desc, pl.sup_desc.data(), pl.sup_desc.size()) ||
+      h->upload(Mem::ChunkConst, &d.chunk_desc, pl.chunk_desc.data(), pl.chunk_desc.size()) ||
+      h->dalloc(Mem::ChunkState, &d.spart2, (size_t)d.n_slot * ba::kSlotStride) ||
+      h->upload(Mem::ChunkConst, &d.grp32, pl.grp32.data(), pl.grp32.size()) ||
+      h->upload(Mem::ChunkConst, &d.grp64, pl.grp64.data(), pl.grp64.size()) ||
+      h->upload(Mem::ChunkConst, &d.grp128, pl.grp128.data(), pl.grp128.size()) ||
+      h->upload(Mem::ChunkConst, &d.lin_desc, pl.lin_desc.data(), pl.lin_desc.size()) ||
+      h->upload(Mem::ChunkConst, &d.grp_pat, pl.grp_pat.data(), pl.grp_pat.size() / 2) ||  // (2 ints per slot)
+      h->upload(Mem::ChunkConst, &d.pose_gpart_ptr, pl.pose_gpart_ptr) ||
+      h->upload(Mem::ChunkConst, &d.pose_gpart, pl.pose_gpart) ||
+      h->dalloc(Mem::ChunkState, &d.Apart2, (size_t)pl.n_apart2 * 27) ||
+      h->dalloc(Mem::ChunkState, &d.lin_dump, (size_t)ba::kLinDump))
+    return -1;
+  if (pl.n_apart2 > 0) HIP_TRY(hipMemset(d.Apart2, 0, (size_t)pl.n_apart2 * 27 * sizeof(double)));
+  return 0;
+}
+
+// Per-iteration storage: both block buffers, the landmark-side and pose-side scratch, the
+// solution, the partial sums, the controller and its iteration log.
+int alloc_iteration_storage(ba_handle *h) {
+  const ba::Plan &pl = h->plan;
+  ba::DevProblem &d = h->d;
+  for (int k = 0; k < 2; ++k) {
+    if (h->dalloc(Mem::ChunkState, &d.Cu[k], (size_t)pl.M * 6) || h->dalloc(Mem::ChunkState, &d.b[k], (size_t)pl.M * 3) ||
+        h->dalloc(Mem::ChunkState, &d.W[k], std::max<size_t>(2, (size_t)pl.P * ba::kWStride)) ||
+        h->dalloc(Mem::Resident, &d.A[k], (size_t)pl.N * 36) || h->dalloc(Mem::Resident, &d.a[k], (size_t)pl.N * 6))
+      return -1;
+    HIP_TRY(hipMemset(d.W[k], 0, std::max<size_t>(1, (size_t)pl.P * ba::kWStride) * sizeof(double)));
+    HIP_TRY(hipMemset(d.A[k], 0, std::max<size_t>(1, (size_t)pl.N * 36) * sizeof(double)));
+    HIP_TRY(hipMemset(d.a[k], 0, std::max<size_t>(1, (size_t)pl.N * 6) * sizeof(double)));
+  }
+  d.n_obs_lm = pl.M > 0 ? pl.lm_obs_ptr[pl.M] : 0;
+  if (h->dalloc(Mem::ChunkState, &d.Cd, (size_t)pl.M * 6) || h->dalloc(Mem::ChunkState, &d.Cinv, (size_t)pl.M * 6) ||
+      h->dalloc(Mem::ChunkState, &d.lin_cost_part, (size_t)std::max(1, d.n_lin_cost)) ||
+      h->dalloc(Mem::ChunkState, &d.Apart, (size_t)d.n_achunk * 27) ||
+      h->dalloc(Mem::ChunkState, &d.spart, (size_t)d.n_tchunk * ba::kSlotStride) ||
+      h->dalloc(Mem::ChunkState, &d.y, (size_t)pl.M * 3) ||
+      h->dalloc(Mem::ChunkState, &d.lm_part, (size_t)std::max(1, d.n_lm_part) * 2))
+    return -1;
+  d.log_cap = 4096;
+  if (h->dalloc(Mem::Resident, &d.x, (size_t)pl.N * 6 + 64) ||
+      h->dalloc(Mem::Resident, &d.cost_part, (size_t)ba::kCostGrid) ||
+      h->dalloc(Mem::Resident, &d.pose_part, (size_t)2 + 2 * ba::kPoseGrid) ||
+      h->dalloc(Mem::Resident, &d.scal, (size_t)4) || h->dalloc(Mem::Resident, &d.ctrl, (size_t)1) ||
+      h->dalloc(Mem::Resident, &d.log, (size_t)d.log_cap))
+    return -1;
+  HIP_TRY(hipMemset(d.lin_cost_part, 0, (size_t)std::max(1, d.n_lin_cost) * sizeof(double)));
+  HIP_TRY(hipMemset(d.x, 0, ((size_t)pl.N * 6 + 64) * sizeof(double)));
+  HIP_TRY(hipMemset(d.y, 0, std::max<size_t>(1, (size_t)pl.M * 3) * sizeof(double)));
+  HIP_TRY(hipMemset(d.cost_part, 0, ba::kCostGrid * sizeof(double)));
+  HIP_TRY(hipMemset(d.lm_part, 0, (size_t)std::max(1, d.n_lm_part) * 2 * sizeof(double)));
+  HIP_TRY(hipMemset(d.pose_part, 0, (2 + 2 * ba::kPoseGrid) * sizeof(double)));
+  HIP_TRY(hipMemset(d.scal, 0, 4 * sizeof(double)));
+  return 0;
+}
+
+// Streaming (ba_stream.hip): the reduced system is scattered, factorised and solved ONCE
+// per iteration, by the owner; this handle aliases its dense image, schedule and solution
+// (the S-block numbering and the tile schedule are global: identical on every landmark
+// chunk) and keeps only its own packed partial S||rhs.
+int alias_dense_owner(ba_handle *h) {
+  const ba_handle *o = h->dense_owner;
+  ba::DevProblem &d = h->d;
+  if (!o->finalized || o->plan.N != h->plan.N || o->plan.B != h->plan.B)
+    return fail("ba_finalize: the dense owner belongs to a different problem");
+  h->sched = o->sched;
+  h->ddev = o->ddev;
+  h->pose_col_h = o->pose_col_h;
+  d.nb = o->d.nb; d.npad = o->d.npad; d.ld = o->d.ld;
+  d.L = o->d.L; d.Ldiag = o->d.Ldiag; d.pose_col = o->d.pose_col; d.col_x = o->d.col_x;
+  d.zt_I = o->d.zt_I; d.zt_J = o->d.zt_J; d.n_zt = o->d.n_zt;
+  d.x = o->d.x;
+  return 0;
+}
+
+// The dense reduced system of this handle: tiles of 5 poses (32 columns) or 10 poses (64
+// columns), eliminated in the order of the level schedule.  Both schedules are built;
+// dense_pick_tile_order chooses.  Then the image, the schedule's device lists and the
+// lists of the tiles that every iteration resets.
+int build_dense_system(ba_handle *h, bool times) {
+  const ba::Plan &pl = h->plan;
+  ba::DevProblem &d = h->d;
+  const ba::DenseKnobs knobs = ba::DenseKnobs::from_env();
+  ba::DenseSchedule cand[2];
+  const int orders[2] = {32, 64};
+  for (int k = 0; k < 2; ++k) {
+    int ncb_k = 0;
+    std::vector<uint8_t> adj;
+    ba::tile_pattern(pl, ba::dense_poses_per_tile(orders[k]), ncb_k, adj);
+    if (knobs.full) std::fill(adj.begin(), adj.end(), 1);
+    ba::build_dense_schedule(ncb_k, adj, knobs.natural, orders[k], cand[k]);
+  }
+  const bool stats = getenv("BA_PLAN_STATS") != nullptr;
+  if (stats)
+    fprintf(stderr, "dense schedules: nb32 %d tiles %d levels max_rows %d fill %.3f | nb64 %d tiles %d levels max_rows %d fill %.3f\n",
+            cand[0].ncb, cand[0].nlev, cand[0].max_rows, cand[0].fill, cand[1].ncb, cand[1].nlev, cand[1].max_rows,
+            cand[1].fill);
+  h->sched = cand[ba::dense_pick_tile_order(cand[0], cand[1], knobs.nb)];
+  const ba::DenseSchedule &sc = h->sched;
+  ba::DenseDev &dd = h->ddev;
+  const int nb = sc.nb;
+  const int ppt = ba::dense_poses_per_tile(nb);
+  const int ncb = sc.ncb;
+  d.nb = nb;
+  d.npad = ncb * nb;
+  d.ld = d.npad + nb;
+  if (h->dalloc(Mem::Resident, &d.L, (size_t)d.npad * d.ld) ||
+      h->dalloc(Mem::Resident, &d.Ldiag, (size_t)ncb * ba::dense_ws_per_block(nb)))
+    return -1;
+  h->pose_col_h.assign(pl.N, 0);
+  std::vector<int> col_x((size_t)d.npad, -1);
+  for (int j = 0; j < pl.N; ++j) {
+    const int c0 = sc.pos_of_tile[j / ppt] * nb + 6 * (j % ppt);
+    h->pose_col_h[j] = c0;
+    for (int r = 0; r < 6; ++r) col_x[c0 + r] = 6 * j + r;
+  }
+  if (h->upload(Mem::Resident, &d.pose_col, h->pose_col_h) || upload_dense_schedule(h, sc, col_x, dd)) return -1;
+  d.col_x = dd.col_x;
+  if (times && dd.dag_items) fprintf(stderr, "[finalize] k_chol_dag: %d items\n", dd.plan[1].n_dag_items);
+  if (stats)
+    fprintf(stderr, "dense launch plan: nb%d forward %s backward %s tail %d columns%s\n", nb,
+            ba::dense_fwd_name(dd.plan[1].fwd), ba::dense_back_name(dd.plan[1].back), dd.plan[1].tail_cols,
+            dd.plan[1].tail_pair ? " (pair)" : "");
+  // tiles (re)initialised per iteration: factor pattern + diagonal + rhs row
+  std::vector<int> ztI, ztJ;
+  for (int p = 0; p < ncb; ++p) {
+    ztI.push_back(p);
+    ztJ.push_back(p);
+    for (int q = sc.row_ptr[p]; q < sc.row_ptr[p + 1]; ++q) {
+      ztI.push_back(sc.rows[q]);  // includes the rhs row block (== ncb)
+      ztJ.push_back(p);
+    }
+  }
+  d.n_zt = (int)ztI.size();
+  if (h->upload(Mem::Resident, &d.zt_I, ztI) || h->upload(Mem::Resident, &d.zt_J, ztJ)) return -1;
+  HIP_TRY(hipMemset(d.L, 0, (size_t)d.npad * d.ld * sizeof(double)));
+  return 0;
+}
+
+// The packed partial S||rhs (exchange buffer 0) and the dense reduced system behind it.
+int setup_reduced_system(ba_handle *h, bool times) {
+  const ba::Plan &pl = h->plan;
+  h->xbuf_n[0] = pl.B * 36 + 6 * (int64_t)pl.N;
+  h->xbuf_n[1] = 4;
+  h->xbuf_n[2] = 3 * (int64_t)pl.n_pt_global;
+  if (h->dalloc(Mem::Resident, &h->d.Spk, (size_t)h->xbuf_n[0])) return -1;
+  HIP_TRY(hipMemset(h->d.Spk, 0, (size_t)h->xbuf_n[0] * sizeof(double)));
+  return h->dense_owner ? alias_dense_owner(h) : build_dense_system(h, times);
 }
 
 }  // namespace
@@ -381,19 +693,6 @@ int ba_finalize(ba_handle *h) {
   if (h->n_cam <= 0 || h->n_pose <= 0 || h->n_pt <= 0)
     return fail("ba_finalize: cameras, poses and points must be set first");
   if (use_device(h)) return -1;
-  ba::PlanInput in;
-  in.n_cam = h->n_cam;
-  in.n_pose = h->n_pose;
-  in.pose_fixed = h->pose_fixed.data();
-  in.n_pt = h->n_pt;
-  in.pt_fixed = h->pt_fixed.data();
-  in.n_obs = h->n_obs;
-  in.obs_cam = h->obs_cam.data();
-  in.obs_pose = h->obs_pose.data();
-  in.obs_pt = h->obs_pt.data();
-  in.obs_uv = h->obs_uv.data();
-  in.rank = h->rank;
-  in.world = h->world;
   const bool times = getenv("BA_PLAN_TIMES") != nullptr;
   h->up_times = times;
   h->up_alloc_s = h->up_copy_s = 0;
@@ -408,292 +707,19 @@ int ba_finalize(ba_handle *h) {
             h->up_alloc_s * 1e3, h->up_copy_s * 1e3);
     t_last = n;
   };
-  std::string err = ba::build_plan(in, h->plan);
-  if (!err.empty()) return fail("ba_finalize: " + err);
+  if (finalize_plan(h)) return -1;
   lap("host plan");
-  const ba::Plan &pl = h->plan;
-  ba::DevProblem &d = h->d;
-  std::memset(&d, 0, sizeof(d));
-  d.n_cam = pl.n_cam; d.n_pose = pl.n_pose; d.N = pl.N; d.n_pt = pl.n_pt;
-  d.M = pl.M; d.M_global = pl.M_global; d.n_obs = pl.n_obs;
-  d.n_obs_opt = pl.n_obs_opt; d.n_obs_global = pl.n_obs_global; d.P = pl.P;
-  d.n_pobs = pl.n_pobs; d.T = pl.T; d.B = pl.B;
-  d.n_achunk = (int)pl.achunk_pose.size();
-  d.n_tchunk = (int)pl.tchunk_blk.size();
-
-  // parameters
-  std::vector<double> cams((size_t)pl.n_cam * 16);
-  for (int c = 0; c < pl.n_cam; ++c) {
-    std::memcpy(&cams[(size_t)c * 16], &h->cam_intr[(size_t)c * 4], 4 * sizeof(double));
-    std::memcpy(&cams[(size_t)c * 16 + 4], &h->cam_T[(size_t)c * 12], 12 * sizeof(double));
-  }
-  // Allocation kinds (ba_handle.h): with a device arena (ba_stream.hip) the arrays
-  // that scale with the landmark chunk live in it — structure / observations as
-  // kind 1 (restored only), blocks / points / partial sums as kind 2 (saved and
-  // restored); everything pose-sized stays resident (kind 0).  Without an arena
-  // every kind is a plain hipMalloc.
-  h->kind(0);
-  if (h->upload(&d.cams, cams)) return -1;
-  std::vector<double> poses((size_t)pl.n_pose * 12);
-  for (int p = 0; p < pl.n_pose; ++p)
-    std::memcpy(&poses[(size_t)p * 12], &h->pose_T[(size_t)pl.pose_user_of_int[p] * 12],
-                12 * sizeof(double));
-  if (h->upload(&d.poses[0], poses) || h->upload(&d.poses[1], poses)) return -1;
-  std::vector<double> pts((size_t)pl.n_pt * 3);
-  for (int q = 0; q < pl.n_pt; ++q)
-    std::memcpy(&pts[(size_t)q * 3], &h->pt_X[(size_t)pl.pt_user_of_int[q] * 3],
-                3 * sizeof(double));
-  h->kind(2);
-  if (h->upload(&d.pts[0], pts) || h->upload(&d.pts[1], pts)) return -1;
-  h->kind(1);
-
-  // structure
-  static_assert(sizeof(int4) == 16 && sizeof(double2) == 16, "layout");
-  if (h->dalloc(&d.obs_idx, (size_t)pl.n_obs)) return -1;
-  if (h->dalloc(&d.obs_uv, (size_t)pl.n_obs)) return -1;
-  if (pl.n_obs > 0) {
-    HIP_TRY(hipMemcpy(d.obs_idx, pl.obs_idx.data(), (size_t)pl.n_obs * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.obs_uv, pl.obs_uv.data(), (size_t)pl.n_obs * 16, hipMemcpyHostToDevice));
-  }
-  // slim landmark-major record for the cost kernel (no pair id, 8 bytes)
-  d.obs_cp = nullptr;
-  const char *wide = getenv("BA_COST_WIDE");  // test knob: keep k_cost on the 16-byte records
-  if (!pl.obs_cp.empty() && pl.n_obs > 0 && !(wide && wide[0] == '1')) {  // (filled by the planner's threaded pass)
-    static_assert(sizeof(int2) == 8, "layout");
-    if (h->dalloc(&d.obs_cp, (size_t)pl.n_obs)) return -1;
-    HIP_TRY(hipMemcpy(d.obs_cp, pl.obs_cp.data(), (size_t)pl.n_obs * 8, hipMemcpyHostToDevice));
-  }
-  if (h->dalloc(&d.pobs_idx, (size_t)pl.n_pobs)) return -1;
-  if (h->dalloc(&d.pobs_uv, (size_t)pl.n_pobs)) return -1;
-  if (pl.n_pobs > 0) {
-    HIP_TRY(hipMemcpy(d.pobs_idx, pl.pobs_idx.data(), (size_t)pl.n_pobs * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.pobs_uv, pl.pobs_uv.data(), (size_t)pl.n_pobs * 16, hipMemcpyHostToDevice));
-  }
-  if (h->upload(&d.lm_obs_ptr, pl.lm_obs_ptr) || h->upload(&d.lm_pair_ptr, pl.lm_pair_ptr) ||
-      h->upload(&d.pair_pose, pl.pair_pose) || h->upload(&d.pair_lm, pl.pair_lm) ||
-      h->upload(&d.achunk_pose, pl.achunk_pose) || h->upload(&d.achunk_begin, pl.achunk_begin) ||
-      h->upload(&d.achunk_end, pl.achunk_end) || h->upload(&d.pose_achunk_ptr, pl.pose_achunk_ptr))
-    return -1;
-  // the block numbering of S is global (identical on every chunk) and k_scatter reads it
-  // when no particular chunk is resident: never in the arena
-  h->kind(0);
-  if (h->upload(&d.sblk_j, pl.sblk_j) || h->upload(&d.diag_blk, pl.diag_blk) || h->upload(&d.sblk_k, pl.sblk_k))
-    return -1;
-  h->kind(1);
-  if (h->upload(&d.tri_p, pl.tri_p) ||
-      h->upload(&d.tri_q, pl.tri_q) || h->upload(&d.tchunk_blk, pl.tchunk_blk) ||
-      h->upload(&d.tchunk_begin, pl.tchunk_begin) || h->upload(&d.tchunk_end, pl.tchunk_end) ||
-      h->upload(&d.sblk_tchunk_ptr, pl.sblk_tchunk_ptr) ||
-      h->upload(&d.ltri, pl.ltri) || h->upload(&d.chunk_sp, pl.chunk_sp) ||
-      h->upload(&d.sup_lane, pl.sup_lane) ||
-      h->upload(&d.blk_contrib_ptr, pl.blk_contrib_ptr) || h->upload(&d.contrib_slot, pl.contrib_slot))
-    return -1;
-  {
-    std::vector<int32_t> bd((size_t)pl.B * 16, 0);
-    for (int64_t bk = 0; bk < pl.B; ++bk) {
-      int32_t *r = bd.data() + 16 * bk;
-      const int64_t c0 = pl.blk_contrib_ptr[bk], c1 = pl.blk_contrib_ptr[bk + 1];
-      r[0] = pl.sblk_j[bk];
-      r[1] = pl.sblk_k[bk];
-      r[2] = (int32_t)c0;
-      r[3] = (int32_t)(c1 - c0);
-      r[4] = pl.sblk_tchunk_ptr[bk];
-      r[5] = pl.sblk_tchunk_ptr[bk + 1] - pl.sblk_tchunk_ptr[bk];
-      for (int t = 0; t < 8; ++t) r[8 + t] = c0 + t < c1 ? pl.contrib_slot[c0 + t] : 0;
-    }
-    if (pl.contrib_slot.size() >= (size_t)INT32_MAX) return fail("too many slot contributions for int32 indices");
-    if (h->upload(&d.blk_desc, bd)) return -1;
-  }
-  d.n_sup = (int)pl.sup_desc.size();
-  d.n_bchunk = (int)pl.bchunk_lm.size() - 1;
-  if (h->upload(&d.bchunk_lm, pl.bchunk_lm)) return -1;
-  {
-    std::vector<ba::DevProblem::LmChunk> lc((size_t)d.n_bchunk);
-    for (int c = 0; c < d.n_bchunk; ++c) {
-      const int l0 = pl.bchunk_lm[c], l1 = pl.bchunk_lm[c + 1];
-      lc[c].pb = pl.lm_pair_ptr[l0];
-      lc[c].ob = pl.lm_obs_ptr[l0];
-      lc[c].l0 = l0;
-      lc[c].nl = l1 - l0;
-      lc[c].np = (int32_t)(pl.lm_pair_ptr[l1] - pl.lm_pair_ptr[l0]);
-      lc[c].no = (int32_t)(pl.lm_obs_ptr[l1] - pl.lm_obs_ptr[l0]);
-    }
-    if (h->upload(&d.lm_chunk, lc)) return -1;
-  }
-  d.n_slot = (int)pl.slot_blk.size();
-  {
-    static_assert(sizeof(ba::Plan::SupDesc) == sizeof(ba::DevProblem::SupDesc), "desc layout");
-    static_assert(sizeof(ba::Plan::ChunkDesc) == sizeof(ba::DevProblem::ChunkDesc), "desc layout");
-    if (h->dalloc(&d.sup_desc, pl.sup_desc.size()) || h->dalloc(&d.chunk_desc, pl.chunk_desc.size()))
-      return -1;
-    if (!pl.sup_desc.empty())
-      HIP_TRY(hipMemcpy(d.sup_desc, pl.sup_desc.data(), pl.sup_desc.size() * sizeof(ba::Plan::SupDesc),
-                        hipMemcpyHostToDevice));
-    if (!pl.chunk_desc.empty())
-      HIP_TRY(hipMemcpy(d.chunk_desc, pl.chunk_desc.data(),
-                        pl.chunk_desc.size() * sizeof(ba::Plan::ChunkDesc), hipMemcpyHostToDevice));
-  }
-  h->kind(2);
-  if (h->dalloc(&d.spart2, (size_t)d.n_slot * ba::kSlotStride)) return -1;
-  h->kind(1);
-  {
-    static_assert(sizeof(ba::Plan::GrpDesc) == sizeof(ba::DevProblem::GrpDesc) && sizeof(ba::Plan::GrpDesc) == 128,
-                  "group descriptor layout");
-    static_assert(sizeof(ba::Plan::LinDesc) == sizeof(ba::DevProblem::LinDesc) && sizeof(ba::Plan::LinDesc) == 48,
-                  "group linearisation descriptor layout");
-    d.n_grp32 = (int)pl.grp32.size();
-    d.n_grp64 = (int)pl.grp64.size();
-    d.n_grp128 = (int)pl.grp128.size();
-    if (h->dalloc(&d.grp32, pl.grp32.size()) || h->dalloc(&d.grp64, pl.grp64.size()) ||
-        h->dalloc(&d.grp128, pl.grp128.size()))
-      return -1;
-    if (d.n_grp128)
-      HIP_TRY(hipMemcpy(d.grp128, pl.grp128.data(), pl.grp128.size() * sizeof(ba::Plan::GrpDesc), hipMemcpyHostToDevice));
-    if (d.n_grp32)
-      HIP_TRY(hipMemcpy(d.grp32, pl.grp32.data(), pl.grp32.size() * sizeof(ba::Plan::GrpDesc), hipMemcpyHostToDevice));
-    if (d.n_grp64)
-      HIP_TRY(hipMemcpy(d.grp64, pl.grp64.data(), pl.grp64.size() * sizeof(ba::Plan::GrpDesc), hipMemcpyHostToDevice));
-    // k_lin_grp: observation patterns, pose-side partial sums of the group pieces
-    d.lin_chunk0 = pl.lin_groups ? pl.n_bchunk_grp : 0;
-    d.n_lin_desc = (int)pl.lin_desc.size();
-    d.n_lin_plain = pl.n_lin_plain;
-    d.n_bs_grp = d.n_lin_desc;
-    d.n_lm_part = d.n_bs_grp + (d.n_bchunk - d.lin_chunk0 + ba::kBsChunks - 1) / ba::kBsChunks;
-    d.n_lin_cost = d.n_bchunk + d.n_lin_desc;
-    if (h->dalloc(&d.lin_desc, pl.lin_desc.size())) return -1;
-    if (d.n_lin_desc)
-      HIP_TRY(hipMemcpy(d.lin_desc, pl.lin_desc.data(), pl.lin_desc.size() * sizeof(ba::Plan::LinDesc), hipMemcpyHostToDevice));
-    if (h->dalloc(&d.grp_pat, pl.grp_pat.size() / 2) || h->upload(&d.pose_gpart_ptr, pl.pose_gpart_ptr) ||
-        h->upload(&d.pose_gpart, pl.pose_gpart))
-      return -1;
-    h->kind(2);
-    if (h->dalloc(&d.Apart2, (size_t)pl.n_apart2 * 27) || h->dalloc(&d.lin_dump, (size_t)ba::kLinDump)) return -1;
-    if (!pl.grp_pat.empty())
-      HIP_TRY(hipMemcpy(d.grp_pat, pl.grp_pat.data(), pl.grp_pat.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (pl.n_apart2 > 0) HIP_TRY(hipMemset(d.Apart2, 0, (size_t)pl.n_apart2 * 27 * sizeof(double)));
-  }
-
+  if (upload_parameters(h) || upload_observation_lists(h) || upload_descriptors_and_groups(h)) return -1;
   lap("structure uploads");
-  // per-iteration storage
-  for (int k = 0; k < 2; ++k) {
-    h->kind(2);
-    if (h->dalloc(&d.Cu[k], (size_t)pl.M * 6) || h->dalloc(&d.b[k], (size_t)pl.M * 3) ||
-        h->dalloc(&d.W[k], std::max<size_t>(2, (size_t)pl.P * ba::kWStride)))
-      return -1;
-    h->kind(0);
-    if (h->dalloc(&d.A[k], (size_t)pl.N * 36) || h->dalloc(&d.a[k], (size_t)pl.N * 6)) return -1;
-    HIP_TRY(hipMemset(d.W[k], 0, std::max<size_t>(1, (size_t)pl.P * ba::kWStride) * sizeof(double)));
-    HIP_TRY(hipMemset(d.A[k], 0, std::max<size_t>(1, (size_t)pl.N * 36) * sizeof(double)));
-    HIP_TRY(hipMemset(d.a[k], 0, std::max<size_t>(1, (size_t)pl.N * 6) * sizeof(double)));
-  }
-  d.n_obs_lm = pl.M > 0 ? pl.lm_obs_ptr[pl.M] : 0;
-  h->kind(2);
-  if (h->dalloc(&d.Cd, (size_t)pl.M * 6) || h->dalloc(&d.Cinv, (size_t)pl.M * 6) ||
-      h->dalloc(&d.lin_cost_part, (size_t)std::max(1, d.n_lin_cost)) ||
-      h->dalloc(&d.Apart, (size_t)d.n_achunk * 27) ||
-      h->dalloc(&d.spart, (size_t)d.n_tchunk * ba::kSlotStride) ||
-      h->dalloc(&d.y, (size_t)pl.M * 3) || h->dalloc(&d.lm_part, (size_t)std::max(1, d.n_lm_part) * 2))
-    return -1;
-  h->kind(0);
-  if (h->dalloc(&d.x, (size_t)pl.N * 6 + 64) || h->dalloc(&d.cost_part, (size_t)ba::kCostGrid) ||
-      h->dalloc(&d.pose_part, (size_t)2 + 2 * ba::kPoseGrid) ||
-      h->dalloc(&d.scal, (size_t)4) || h->dalloc(&d.ctrl, (size_t)1))
-    return -1;
-  HIP_TRY(hipMemset(d.lin_cost_part, 0, (size_t)std::max(1, d.n_lin_cost) * sizeof(double)));
-  HIP_TRY(hipMemset(d.x, 0, ((size_t)pl.N * 6 + 64) * sizeof(double)));
-  HIP_TRY(hipMemset(d.y, 0, std::max<size_t>(1, (size_t)pl.M * 3) * sizeof(double)));
-  HIP_TRY(hipMemset(d.cost_part, 0, ba::kCostGrid * sizeof(double)));
-  HIP_TRY(hipMemset(d.lm_part, 0, (size_t)std::max(1, d.n_lm_part) * 2 * sizeof(double)));
-  HIP_TRY(hipMemset(d.pose_part, 0, (2 + 2 * ba::kPoseGrid) * sizeof(double)));
-  HIP_TRY(hipMemset(d.scal, 0, 4 * sizeof(double)));
-  d.log_cap = 4096;
-  if (h->dalloc(&d.log, (size_t)d.log_cap)) return -1;
-
+  if (alloc_iteration_storage(h)) return -1;
   lap("block storage");
-  // dense reduced system: tiles of 5 poses (32 columns) or 10 poses (64 columns), eliminated
-  // in the order of the level schedule.  Both schedules are built; dense_pick_tile_order chooses.
-  h->xbuf_n[0] = pl.B * 36 + 6 * (int64_t)pl.N;
-  h->xbuf_n[1] = 4;
-  h->xbuf_n[2] = 3 * (int64_t)pl.n_pt_global;
-  if (h->dalloc(&d.Spk, (size_t)h->xbuf_n[0])) return -1;
-  HIP_TRY(hipMemset(d.Spk, 0, (size_t)h->xbuf_n[0] * sizeof(double)));
-  if (h->dense_owner) {
-    // streaming (ba_stream.hip): the reduced system is scattered, factorised and solved
-    // ONCE per iteration, by the owner; this handle aliases its dense image, schedule
-    // and solution (the S-block numbering and the tile schedule are global: identical
-    // on every landmark chunk) and keeps only its own packed partial S||rhs
-    const ba_handle *o = h->dense_owner;
-    if (!o->finalized || o->plan.N != pl.N || o->plan.B != pl.B)
-      return fail("ba_finalize: the dense owner belongs to a different problem");
-    h->sched = o->sched;
-    h->ddev = o->ddev;
-    h->pose_col_h = o->pose_col_h;
-    d.nb = o->d.nb; d.npad = o->d.npad; d.ld = o->d.ld;
-    d.L = o->d.L; d.Ldiag = o->d.Ldiag; d.pose_col = o->d.pose_col; d.col_x = o->d.col_x;
-    d.zt_I = o->d.zt_I; d.zt_J = o->d.zt_J; d.n_zt = o->d.n_zt;
-    d.x = o->d.x;
-  } else {
-    const ba::DenseKnobs knobs = ba::DenseKnobs::from_env();
-    ba::DenseSchedule cand[2];
-    const int orders[2] = {32, 64};
-    for (int k = 0; k < 2; ++k) {
-      int ncb_k = 0;
-      std::vector<uint8_t> adj;
-      ba::tile_pattern(pl, ba::dense_poses_per_tile(orders[k]), ncb_k, adj);
-      if (knobs.full) std::fill(adj.begin(), adj.end(), 1);
-      ba::build_dense_schedule(ncb_k, adj, knobs.natural, orders[k], cand[k]);
-    }
-    const bool stats = getenv("BA_PLAN_STATS") != nullptr;
-    if (stats)
-      fprintf(stderr, "dense schedules: nb32 %d tiles %d levels max_rows %d fill %.3f | nb64 %d tiles %d levels max_rows %d fill %.3f\n",
-              cand[0].ncb, cand[0].nlev, cand[0].max_rows, cand[0].fill, cand[1].ncb, cand[1].nlev, cand[1].max_rows,
-              cand[1].fill);
-    h->sched = cand[ba::dense_pick_tile_order(cand[0], cand[1], knobs.nb)];
-    const int nb = h->sched.nb;
-    const int ppt = ba::dense_poses_per_tile(nb);
-    const int ncb = h->sched.ncb;
-    d.nb = nb;
-    d.npad = ncb * nb;
-    d.ld = d.npad + nb;
-    if (h->dalloc(&d.L, (size_t)d.npad * d.ld)) return -1;
-    if (h->dalloc(&d.Ldiag, (size_t)ncb * ba::dense_ws_per_block(nb))) return -1;
-    h->pose_col_h.assign(pl.N, 0);
-    std::vector<int> col_x((size_t)d.npad, -1);
-    for (int j = 0; j < pl.N; ++j) {
-      const int c0 = h->sched.pos_of_tile[j / ppt] * nb + 6 * (j % ppt);
-      h->pose_col_h[j] = c0;
-      for (int r = 0; r < 6; ++r) col_x[c0 + r] = 6 * j + r;
-    }
-    const ba::DenseSchedule &sc = h->sched;
-    ba::DenseDev &dd = h->ddev;
-    if (h->upload(&d.pose_col, h->pose_col_h) || upload_dense_schedule(h, sc, col_x, dd)) return -1;
-    d.col_x = dd.col_x;
-    if (times && dd.dag_items) fprintf(stderr, "[finalize] k_chol_dag: %d items\n", dd.plan[1].n_dag_items);
-    if (stats)
-      fprintf(stderr, "dense launch plan: nb%d forward %s backward %s tail %d columns%s\n", nb,
-              ba::dense_fwd_name(dd.plan[1].fwd), ba::dense_back_name(dd.plan[1].back), dd.plan[1].tail_cols,
-              dd.plan[1].tail_pair ? " (pair)" : "");
-    // tiles (re)initialised per iteration: factor pattern + diagonal + rhs row
-    std::vector<int> ztI, ztJ;
-    for (int p = 0; p < ncb; ++p) {
-      ztI.push_back(p);
-      ztJ.push_back(p);
-      for (int q = sc.row_ptr[p]; q < sc.row_ptr[p + 1]; ++q) {
-        ztI.push_back(sc.rows[q]);  // includes the rhs row block (== ncb)
-        ztJ.push_back(p);
-      }
-    }
-    d.n_zt = (int)ztI.size();
-    if (h->upload(&d.zt_I, ztI) || h->upload(&d.zt_J, ztJ)) return -1;
-    HIP_TRY(hipMemset(d.L, 0, (size_t)d.npad * d.ld * sizeof(double)));
-  }
-
+  if (setup_reduced_system(h, times)) return -1;
   lap("dense schedule + image");
   std::memset(&h->hc, 0, sizeof(h->hc));
   h->hc.lambda = 100.0;
   h->hc.huber = 1.0;
   h->hc.max_iter = 1;
-  HIP_TRY(hipMemcpy(d.ctrl, &h->hc, sizeof(ba::DevCtrl), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->d.ctrl, &h->hc, sizeof(ba::DevCtrl), hipMemcpyHostToDevice));
   HIP_TRY(hipDeviceSynchronize());
   h->finalized = true;
   return 0;
@@ -766,13 +792,10 @@ int ba_bind_reduce_buffer(ba_handle *h, int which, void *dev_ptr, int64_t n) {
 // starts (max_num_iterations <= 0).  Shared with ba_stream.hip.
 int ba::lm_prepare_ctrl(ba_handle *h, const ba_options *opt, int *done_after) {
   if (opt->max_num_iterations > h->d.log_cap) {
-    // grow the device-side iteration log
+    // grow the device-side iteration log.  k_control writes it while no chunk of a
+    // streamed problem is resident: Resident, like the log it replaces
     ba::DevIterRec *nl = nullptr;
-    const int keep = h->alloc_kind;
-    h->alloc_kind = 0;
-    const int rc = h->dalloc(&nl, (size_t)opt->max_num_iterations);
-    h->alloc_kind = keep;
-    if (rc) return -1;
+    if (h->dalloc(Mem::Resident, &nl, (size_t)opt->max_num_iterations)) return -1;
     h->drop_graph();  // the captured kernels hold the old pointer
     h->d.log = nl;
     h->d.log_cap = opt->max_num_iterations;
@@ -968,18 +991,17 @@ static int gd_prepare(ba_handle *h, const char *who) {
   g.n_cost_part = d.n_bchunk + g.n_fix_blk;
   g.n_upd_pose_blk = (N + 255) / 256;
   g.n_upd_blk = g.n_upd_pose_blk + (d.M + 255) / 256;
-  h->kind(0);
   static_assert(sizeof(int2) == 8 && sizeof(double2) == 16, "layout");
-  if (h->dalloc(&g.pobs, (size_t)n) || h->dalloc(&g.puv, (size_t)n) || h->upload(&g.chunk_pose, chunk_pose) ||
-      h->upload(&g.chunk_begin, chunk_begin) || h->upload(&g.chunk_end, chunk_end) ||
-      h->upload(&g.pose_chunk_ptr, pose_chunk_ptr) || h->dalloc(&g.ppart, (size_t)g.n_chunk * 6) ||
-      h->dalloc(&g.a, (size_t)N * 6) || h->dalloc(&g.b, (size_t)d.M * 3) ||
-      h->dalloc(&g.cost_part, (size_t)g.n_cost_part) || h->dalloc(&g.step_part, (size_t)g.n_upd_blk * 2))
+  if (h->upload(Mem::Resident, &g.pobs, pobs.data(), (size_t)n) ||
+      h->upload(Mem::Resident, &g.puv, puv.data(), (size_t)n) ||
+      h->upload(Mem::Resident, &g.chunk_pose, chunk_pose) || h->upload(Mem::Resident, &g.chunk_begin, chunk_begin) ||
+      h->upload(Mem::Resident, &g.chunk_end, chunk_end) ||
+      h->upload(Mem::Resident, &g.pose_chunk_ptr, pose_chunk_ptr) ||
+      h->dalloc(Mem::Resident, &g.ppart, (size_t)g.n_chunk * 6) || h->dalloc(Mem::Resident, &g.a, (size_t)N * 6) ||
+      h->dalloc(Mem::Resident, &g.b, (size_t)d.M * 3) ||
+      h->dalloc(Mem::Resident, &g.cost_part, (size_t)g.n_cost_part) ||
+      h->dalloc(Mem::Resident, &g.step_part, (size_t)g.n_upd_blk * 2))
     return -1;
-  if (n > 0) {
-    HIP_TRY(hipMemcpy(g.pobs, pobs.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(g.puv, puv.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-  }
   HIP_TRY(hipMemset(g.a, 0, std::max<size_t>(1, (size_t)N * 6) * sizeof(double)));
   HIP_TRY(hipMemset(g.b, 0, std::max<size_t>(1, (size_t)d.M * 3) * sizeof(double)));
   h->gd_ready = true;
@@ -1224,8 +1246,8 @@ int ba_gather_points(ba_handle *h) {
   if (!h->ar_fn || h->world <= 1) return 0;  // one shard owns every point: nothing to gather
   const ba::Plan &pl = h->plan;
   const size_t n3 = (size_t)pl.n_pt_global * 3;
-  if (!h->gbuf && h->dalloc(&h->gbuf, n3)) return -1;
-  if (!h->pt_user_dev && h->upload(&h->pt_user_dev, pl.pt_user_of_int)) return -1;
+  if (!h->gbuf && h->dalloc(Mem::Resident, &h->gbuf, n3)) return -1;
+  if (!h->pt_user_dev && h->upload(Mem::Resident, &h->pt_user_dev, pl.pt_user_of_int)) return -1;
   if (pull_ctrl(h)) return -1;  // `cur` (synchronises the stream)
   join_side(h);
   HIP_TRY(hipMemsetAsync(h->gbuf, 0, n3 * sizeof(double), h->stream));
@@ -1544,21 +1566,11 @@ int ba_dense_spd_solve(ba_handle *h, int n, const double *A, const double *b,
   }
   // everything below is allocated on the handle and freed again on every return, so that
   // repeated calls do not grow the handle's memory
-  struct Scratch {
-    ba_handle *h;
-    size_t mark;
-    int kind;
-    ~Scratch() {
-      for (size_t k = mark; k < h->allocs.size(); ++k) (void)hipFree(h->allocs[k]);
-      h->allocs.resize(mark);
-      h->alloc_kind = kind;
-    }
-  } scratch{h, h->allocs.size(), h->alloc_kind};
-  h->alloc_kind = 0;  // (resident allocations, also on a streaming handle)
+  ba::ScratchAllocs scratch(h);
   ba::DenseDev dd;
   double *dL = nullptr, *dD = nullptr, *dx = nullptr;
-  if (upload_dense_schedule(h, sc, col_x, dd) || h->upload(&dL, L) ||
-      h->dalloc(&dD, (size_t)ncb * ba::dense_ws_per_block(nb)) || h->dalloc(&dx, (size_t)npad))
+  if (upload_dense_schedule(h, sc, col_x, dd) || h->upload(Mem::Resident, &dL, L) ||
+      h->dalloc(Mem::Resident, &dD, (size_t)ncb * ba::dense_ws_per_block(nb)) || h->dalloc(Mem::Resident, &dx, (size_t)npad))
     return -1;
   hipEvent_t e0, e1;
   HIP_TRY(hipEventCreate(&e0));
@@ -1727,26 +1739,17 @@ int ba_covariance(ba_handle *h, double huber, int n_pose_sel, const int32_t *pos
   h->hc = keep;  // the controller as it was: lambda, huber, done, the log position
   if (push_ctrl(h)) return -1;
   // ---- the batches; everything below is freed again on every return
-  struct Scratch {
-    ba_handle *h;
-    size_t mark;
-    int kind;
-    ~Scratch() {
-      for (size_t k = mark; k < h->allocs.size(); ++k) (void)hipFree(h->allocs[k]);
-      h->allocs.resize(mark);
-      h->alloc_kind = kind;
-    }
-  } scratch{h, h->allocs.size(), h->alloc_kind};
-  h->alloc_kind = 0;
+  ba::ScratchAllocs scratch(h);
   const int bw_max = cov_batch_cols(d.npad);
   const int gpb = bw_max / ba::kCovGroupCols;  // groups per batch
   const int bw = (int)std::min<size_t>(gpb, std::max<size_t>(1, groups.size())) * ba::kCovGroupCols;
   int *d_trow_ptr = nullptr, *d_trow = nullptr;
   ba::CovGroup *d_groups = nullptr;
   double *Zw = nullptr, *d_pose = nullptr, *d_pt = nullptr;
-  if (h->upload(&d_trow_ptr, trow_ptr) || h->upload(&d_trow, trow) || h->upload(&d_groups, groups) ||
-      h->dalloc(&Zw, (size_t)d.npad * bw) || h->dalloc(&d_pose, poses.size() * 36) ||
-      h->dalloc(&d_pt, pts.size() * 9))
+  if (h->upload(Mem::Resident, &d_trow_ptr, trow_ptr) || h->upload(Mem::Resident, &d_trow, trow) ||
+      h->upload(Mem::Resident, &d_groups, groups) ||
+      h->dalloc(Mem::Resident, &Zw, (size_t)d.npad * bw) || h->dalloc(Mem::Resident, &d_pose, poses.size() * 36) ||
+      h->dalloc(Mem::Resident, &d_pt, pts.size() * 9))
     return -1;
   h->cov_batches = 0;
   for (size_t g0 = 0; g0 < groups.size(); g0 += gpb) {  // fixed batch order
@@ -1834,7 +1837,7 @@ int po_run(ba_handle *h, bool stereo, const float *X3, const float *uv2, const f
   const int icap = std::max(1, std::max(cap, max_it));
   const PoLayout L = po_layout(n, icap, stereo);
   if (po_reserve(h, L.end)) return -1;
-  if (!h->po_part && h->dalloc(&h->po_part, (size_t)ba::pose_only_partial_floats())) return -1;
+  if (!h->po_part && h->dalloc(Mem::Resident, &h->po_part, (size_t)ba::pose_only_partial_floats())) return -1;
   uint8_t *hb = h->po_host, *db = h->po_dev;
   std::memcpy(hb + L.X, X3, (size_t)n * 3 * sizeof(float));
   std::memcpy(hb + L.uv, uv2, (size_t)n * 2 * sizeof(float));

@@ -29,6 +29,15 @@ struct DeviceArena {
   char *base = nullptr;
   size_t cap = 0;
 };
+
+// Where a device array of a handle lives: the first argument of ba_handle::dalloc /
+// upload.  With a device arena the arrays that scale with the landmark chunk live in
+// it: structure / observations as ChunkConst (restored only), blocks / points /
+// partial sums as ChunkState (saved and restored).  Everything pose-sized, and every
+// array that a launch touches while the chunk may be swapped out (DESIGN.md §6b,
+// "Residency"), is Resident: its own hipMalloc, never moved.  Without an arena all
+// three are a plain hipMalloc.
+enum class Mem { Resident, ChunkConst, ChunkState };
 }  // namespace ba
 
 #define HIP_TRY(expr)                                                        \
@@ -117,22 +126,20 @@ struct ba_handle {
   // ---- streaming (ba_stream.hip): chunk-resident arrays live in a shared arena ----
   ba::DeviceArena *arena = nullptr;
   size_t arena_imm = 0, arena_mut = 0;  // bytes used from the bottom / from the top
-  int alloc_kind = 0;                   // 0 resident (hipMalloc), 1 arena immutable, 2 arena mutable
   // the handle whose dense image / schedule / solution this handle aliases (the
   // reduced system is solved ONCE per iteration, by the owner), or null
   ba_handle *dense_owner = nullptr;
-  void kind(int k) { alloc_kind = arena ? k : 0; }
 
   template <class T>
-  int dalloc(T **p, size_t n) {
+  int dalloc(ba::Mem where, T **p, size_t n) {
     *p = nullptr;
     if (n == 0) n = 1;
-    if (arena && alloc_kind != 0) {
+    if (arena && where != ba::Mem::Resident) {
       const size_t sz = (n * sizeof(T) + 255) & ~(size_t)255;
       if (arena_imm + arena_mut + sz > arena->cap)
         return ::ba::fail("the landmark chunk does not fit the device arena (" + std::to_string(arena->cap >> 20) +
                           " MiB): use more chunks or a larger arena");
-      if (alloc_kind == 1) {
+      if (where == ba::Mem::ChunkConst) {
         *p = (T *)(arena->base + arena_imm);
         arena_imm += sz;
       } else {
@@ -151,14 +158,15 @@ struct ba_handle {
   bool up_times = false;
   double up_alloc_s = 0, up_copy_s = 0;
   size_t up_bytes = 0, up_calls = 0;
-  template <class T, class A>
-  int upload(T **p, const std::vector<T, A> &v) {
+  // `host` holds n records with the layout of T (the planner keeps some of them as flat
+  // int32 / double vectors or as its own mirror of a device struct)
+  template <class T>
+  int upload(ba::Mem where, T **p, const void *host, size_t n) {
     const auto t0 = up_times ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
-    if (dalloc(p, v.size())) return -1;
+    if (dalloc(where, p, n)) return -1;
     const auto t1 = up_times ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
-    if (!v.empty()) {
-      hipError_t e = hipMemcpy(*p, v.data(), v.size() * sizeof(T),
-                               hipMemcpyHostToDevice);
+    if (n > 0) {
+      hipError_t e = hipMemcpy(*p, host, n * sizeof(T), hipMemcpyHostToDevice);
       if (e != hipSuccess)
         return ::ba::fail(std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
     }
@@ -166,10 +174,14 @@ struct ba_handle {
       const auto t2 = std::chrono::steady_clock::now();
       up_alloc_s += std::chrono::duration<double>(t1 - t0).count();
       up_copy_s += std::chrono::duration<double>(t2 - t1).count();
-      up_bytes += v.size() * sizeof(T);
+      up_bytes += n * sizeof(T);
       ++up_calls;
     }
     return 0;
+  }
+  template <class T, class A>
+  int upload(ba::Mem where, T **p, const std::vector<T, A> &v) {
+    return upload(where, p, v.data(), v.size());
   }
   void free_device() {
     for (void *p : allocs) (void)hipFree(p);
@@ -191,6 +203,19 @@ struct ba_handle {
 };
 
 namespace ba {
+// Frees, when it goes out of scope, what was allocated on the handle since its
+// construction: scratch of one call, so that repeated calls do not grow the handle.
+struct ScratchAllocs {
+  ba_handle *h;
+  size_t mark;
+  explicit ScratchAllocs(ba_handle *handle) : h(handle), mark(handle->allocs.size()) {}
+  ScratchAllocs(const ScratchAllocs &) = delete;
+  ~ScratchAllocs() {
+    for (size_t k = mark; k < h->allocs.size(); ++k) (void)hipFree(h->allocs[k]);
+    h->allocs.resize(mark);
+  }
+};
+
 int lm_prepare_ctrl(ba_handle *h, const ba_options *opt, int *done_after);
 int ctrl_pull(ba_handle *h);  // device controller state -> h->hc (synchronises the stream)
 int ctrl_push(ba_handle *h);

@@ -5,9 +5,9 @@
 // The landmarks are cut into K chunks with the sharding rule of the multi-GPU path
 // (ba_set_shard: contiguous ranges of the locality order, balanced by observation
 // count); every chunk is a shard handle whose chunk-sized arrays are carved from a
-// shared DEVICE ARENA instead of hipMalloc (ba_handle.h: kind 1 = structure /
-// observations, restored only; kind 2 = blocks / points / partial sums, saved and
-// restored).  Two arenas ping-pong: while the kernels of chunk k run in one, the
+// shared DEVICE ARENA instead of hipMalloc (ba_handle.h: Mem::ChunkConst = structure /
+// observations, restored only; Mem::ChunkState = blocks / points / partial sums, saved
+// and restored).  Two arenas ping-pong: while the kernels of chunk k run in one, the
 // copy stream saves the previous occupant of the other and restores chunk k + 1
 // into it from its pinned host image.  Everything pose-sized (poses, A_j, a_j, the
 // controller, the packed partial S||rhs) stays resident per chunk; the dense image,
@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "ba_handle.h"
+#include "ba_residency.h"
 
 using ba::fail;
 
@@ -44,7 +45,7 @@ struct ba_stream {
   hipStream_t s_comp = nullptr, s_copy = nullptr;
   ba::DeviceArena arena[2];
   std::vector<ba_handle *> h;
-  std::vector<char *> img;          // pinned host image of chunk k: [kind 1 | kind 2]
+  std::vector<char *> img;          // pinned host image of chunk k: [ChunkConst | ChunkState]
   std::vector<hipEvent_t> ev_in, ev_comp;
   std::vector<uint8_t> in_pending, dirty, computed;
   int resident[2] = {-1, -1};
@@ -145,6 +146,40 @@ int sum_scalars_to_all(ba_stream *s) {
   for (int k = 0; k < s->K; ++k)
     HIP_TRY(hipMemcpyAsync(s->h[k]->d.scal, s->scal_sum, 4 * sizeof(double), hipMemcpyDeviceToDevice, s->s_comp));
   return 0;
+}
+
+// The device arrays of chunk handle `h` that a launch touches OUTSIDE the chunk's acquire /
+// release window, when the arena may hold another chunk: the arguments of launch_dense_init,
+// launch_scatter (k_scatter), launch_dense_solve (run_plan), launch_control and
+// launch_init_ctrl_cost (k_control, k_init_ctrl_cost), of add_into on Spk and scal and of
+// sum_scalars_to_all.  (lm_prepare_ctrl and the *_sync calls touch ctrl, log and bad_pivots
+// only.)  Keep it in step with those wrappers: check_residency below is the fence.
+std::vector<ba::NamedPtr> pointers_used_outside_window(const ba_handle *h) {
+  const ba::DevProblem &d = h->d;
+  const ba::DenseDev &dd = h->ddev;
+#define BA_PTR(x) ba::NamedPtr{#x, (const void *)(x)}
+  return {BA_PTR(d.L), BA_PTR(d.Ldiag), BA_PTR(d.col_x), BA_PTR(d.zt_I), BA_PTR(d.zt_J), BA_PTR(d.pose_col),
+          BA_PTR(d.Spk), BA_PTR(d.sblk_j), BA_PTR(d.sblk_k), BA_PTR(d.x), BA_PTR(d.scal), BA_PTR(d.ctrl),
+          BA_PTR(d.log), BA_PTR(d.pose_part),
+          // every array of the dense schedule (launch_dense_solve reads most, none is chunk data)
+          BA_PTR(dd.row_ptr), BA_PTR(dd.rows), BA_PTR(dd.item_t), BA_PTR(dd.item_I), BA_PTR(dd.tgt_I),
+          BA_PTR(dd.tgt_J), BA_PTR(dd.tgt_src_ptr), BA_PTR(dd.src_t), BA_PTR(dd.tgt_desc), BA_PTR(dd.back_desc),
+          BA_PTR(dd.row_desc), BA_PTR(dd.col_x), BA_PTR(dd.xc), BA_PTR(dd.bad_pivots), BA_PTR(dd.flow_order),
+          BA_PTR(dd.flow_flags), BA_PTR(dd.flow_ticket), BA_PTR(dd.fwd_flags), BA_PTR(dd.fwd_ticket),
+          BA_PTR(dd.upd_pre), BA_PTR(dd.col_need), BA_PTR(dd.fwd_cnt), BA_PTR(dd.dag_items), BA_PTR(dd.dag_ntrsm),
+          BA_PTR(dd.dag_dflags), BA_PTR(dd.dag_tcnt), BA_PTR(dd.look_need)};
+#undef BA_PTR
+}
+
+// DESIGN.md §6b "Residency": none of them may lie in an arena.
+int check_residency(const ba_stream *s, int k) {
+  const ba::AddrRange a0{s->arena[0].base, s->arena[0].cap}, a1{s->arena[1].base, s->arena[1].cap};
+  const std::vector<std::string> bad = ba::pointers_in_arena(pointers_used_outside_window(s->h[k]), a0, a1);
+  if (bad.empty()) return 0;
+  std::string names;
+  for (const std::string &n : bad) names += (names.empty() ? "" : ", ") + n;
+  return fail("ba_stream_finalize: chunk " + std::to_string(k) + ": " + names +
+              " live in a chunk arena but are used while the chunk may be swapped out (allocate them Mem::Resident)");
 }
 
 int stream_begin(ba_stream *s, const ba_options *opt, int *done_after) {
@@ -333,7 +368,7 @@ int ba_stream_finalize(ba_stream *s) {
         ba_set_shard(h, k, s->K))
       return -1;
     // the previous occupant of this arena was imaged before this finalize overwrites it
-    if (ba_finalize(h)) return -1;
+    if (ba_finalize(h) || check_residency(s, k)) return -1;
     // the handle's host copy of the full problem is not needed again (it never re-plans)
     std::vector<int32_t>().swap(h->obs_cam);
     std::vector<int32_t>().swap(h->obs_pose);

@@ -98,3 +98,17 @@ def test_dense_launch_plan_equals_the_launch_macro_it_replaced(tmp_path):
     r = subprocess.run([exe, os.path.join(ROOT, "tests", "cpp", "dense_launch_expected.txt")],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0 and "DENSE LAUNCH CHECK OK" in r.stdout, r.stdout[-3000:]
+
+
+def test_residency_check_names_exactly_the_pointers_inside_an_arena(tmp_path):
+    """csrc/ba_residency.h pointers_in_arena, the check ba_stream_finalize runs on every
+    chunk handle (DESIGN.md §6b "Residency": an array that a launch touches outside a
+    chunk's acquire / release window is never in a chunk arena).  Compiled against that
+    header alone, with made-up addresses and two made-up arenas: a pointer at base and at
+    base + cap - 1 is reported by name, one at base - 1 and at base + cap is not, the
+    single-arena case (both ranges the same) reports once, a null pointer is ignored."""
+    exe = str(tmp_path / "residency_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", CSRC,
+                    os.path.join(ROOT, "tests", "cpp", "residency_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and "RESIDENCY CHECK OK" in r.stdout, r.stdout[-3000:]
