@@ -83,6 +83,12 @@ class BaBatchResult(C.Structure):
                 ("dropped_pivots", C.c_int)]
 
 
+class BaBatchCovResult(C.Structure):
+    """ba_batch_cov_result — one problem of ba_batch_covariance (status as
+    BaBatchResult; dropped_pivots > 0: S was singular at lambda = 0)."""
+    _fields_ = [("status", C.c_int), ("dropped_pivots", C.c_int)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                            C.c_int64, C.c_void_p)
 
@@ -239,6 +245,7 @@ SIGNATURES = {
     "ba_batch_destroy": (None, [_P]),
     "ba_batch_solve": (C.c_int, [_P, C.POINTER(BaOptions), C.POINTER(BaIterInfo),
                                  C.c_int, C.POINTER(BaBatchResult)]),
+    "ba_batch_covariance": (C.c_int, [_P, C.c_double, _D, _D, C.POINTER(BaBatchCovResult)]),
     "ba_batch_update_values": (C.c_int, [_P, _D, _D]),
     "ba_batch_get_poses": (C.c_int, [_P, _D]),
     "ba_batch_get_points": (C.c_int, [_P, _D]),

@@ -21,6 +21,11 @@
 //   reduced solve   chol_lds_factor_solve on the LDS image (<= 96 columns + rhs block)
 //   back-substitution, trial point, quadratic model, step norms; trial cost; control step
 //
+// k_ba_batch_cov (ba_batch_covariance) reuses the first half — the two linearisation passes,
+// damp / invert with lambda = 0, Schur and the factorisation, shared as device functions —
+// and then inverts the factor in LDS (chol_lds_inverse) and reads the covariance blocks of
+// every pose and landmark of the problem off S^-1.
+//
 // Host side: ba_batch_create plans the structure once (stable landmark-major grouping,
 // pair lists, last-writer marks, one upload); ba_batch_solve is one launch and one sync.
 #include <hip/hip_runtime.h>
@@ -109,6 +114,198 @@ __device__ __forceinline__ double batch_cost(const BatchDev &d, const BatchProb 
     acc += sqrt(g.r0 * g.r0 + g.r1 * g.r1);
   }
   return block_sum(acc, s.red);
+}
+
+// ---- the steps of one linearisation, shared by k_ba_batch and k_ba_batch_cov --------------
+// landmark side (reference :811-828): one thread per optimisable landmark, its observations
+// in insertion order; C_i, b_i and the cross block of a pair's LAST observation
+__device__ __forceinline__ void batch_landmark_pass(const int M, const int32_t *opt_lm, const int32_t *lm_ptr,
+                                                    const int4 *ob, const double2 *uvp, const double *cams,
+                                                    const double *Pc, const double *X, const double huber,
+                                                    double *C6, double *b3, double *Wg) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < M; i += kBatchBlock) {
+    const int q = opt_lm[i];
+    const double x0 = X[q * 3 + 0], x1 = X[q * 3 + 1], x2 = X[q * 3 + 2];
+    double C[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
+    const int o1 = lm_ptr[q + 1];
+    for (int t = lm_ptr[q]; t < o1; ++t) {
+      const int4 r = ob[t];
+      const double2 u = uvp[t];
+      const double *cam = cams + r.x * 16;
+      const double *T = Pc + r.y * 12;
+      ObsGeom g;
+      project(cam, T, x0, x1, x2, u.x, u.y, g);
+      double w, G[6], Rm[6];
+      weight_and_G(cam, g, huber, w, G);
+      make_R(G, T, Rm);
+      const double wr0 = w * g.r0, wr1 = w * g.r1;
+      C[0] += w * (Rm[0] * Rm[0] + Rm[3] * Rm[3]);
+      C[1] += w * (Rm[0] * Rm[1] + Rm[3] * Rm[4]);
+      C[2] += w * (Rm[0] * Rm[2] + Rm[3] * Rm[5]);
+      C[3] += w * (Rm[1] * Rm[1] + Rm[4] * Rm[4]);
+      C[4] += w * (Rm[1] * Rm[2] + Rm[4] * Rm[5]);
+      C[5] += w * (Rm[2] * Rm[2] + Rm[5] * Rm[5]);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) b[c] -= Rm[c] * wr0 + Rm[3 + c] * wr1;
+      if (r.w >= 0 && (r.w & 1)) {  // the pair's last observation: B_ji = w Q^T R survives
+        double Q[12];
+        make_Q(G, g.Xij, Q);
+        double *Wp = Wg + (size_t)(r.w >> 1) * 18;
+#pragma unroll
+        for (int rr = 0; rr < 6; ++rr)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) Wp[rr * 3 + c] = w * (Q[rr] * Rm[c] + Q[6 + rr] * Rm[3 + c]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) C6[(size_t)i * 6 + k] = C[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) b3[(size_t)i * 3 + k] = b[k];
+  }
+}
+
+// pose side (reference :789-809): one wave per optimisable pose, 27 wave sums -> A_j, a_j in LDS
+__device__ __forceinline__ void batch_pose_pass(const int N, const int32_t *pp0, const int32_t *po, const int4 *ob,
+                                                const double2 *uvp, const double *cams, const double *Pc,
+                                                const double *X, const double huber, double *A, double *a) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int j = wv; j < N; j += kBatchBlock / 64) {
+    const int32_t *pp = pp0 + j;
+    double acc[27];
+#pragma unroll
+    for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+    const int e1 = pp[1];
+    for (int t = pp[0] + lane; t < e1; t += 64) {
+      const int so = po[t];
+      const int4 r = ob[so];
+      const double2 u = uvp[so];
+      const double *cam = cams + r.x * 16;
+      const double *Xp = X + (size_t)r.z * 3;
+      ObsGeom g;
+      project(cam, Pc + r.y * 12, Xp[0], Xp[1], Xp[2], u.x, u.y, g);
+      double w, G[6], Q[12];
+      weight_and_G(cam, g, huber, w, G);
+      make_Q(G, g.Xij, Q);
+      const double wr0 = w * g.r0, wr1 = w * g.r1;
+      int k = 0;
+#pragma unroll
+      for (int rr = 0; rr < 6; ++rr)
+#pragma unroll
+        for (int c = rr; c < 6; ++c, ++k) acc[k] += (w * Q[rr]) * Q[c] + (w * Q[6 + rr]) * Q[6 + c];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) acc[21 + c] -= Q[c] * wr0 + Q[6 + c] * wr1;
+    }
+#pragma unroll
+    for (int k = 0; k < 27; ++k) acc[k] = wave_sum(acc[k]);
+    if (lane == 0) {
+      int k = 0;
+#pragma unroll
+      for (int rr = 0; rr < 6; ++rr)
+#pragma unroll
+        for (int c = rr; c < 6; ++c, ++k) {
+          A[j * 36 + rr * 6 + c] = acc[k];
+          A[j * 36 + c * 6 + rr] = acc[k];
+        }
+#pragma unroll
+      for (int c = 0; c < 6; ++c) a[j * 6 + c] = acc[21 + c];
+    }
+  }
+}
+
+// damp and invert (reference :846-856): C_i (1 + lambda) -> Cinv_i, Cinv_i b_i
+__device__ __forceinline__ void batch_damp_invert(const int M, const double lp1, const double *C6, const double *b3,
+                                                  double *Ci6, double *Cib3) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < M; i += kBatchBlock) {
+    double cd[6], ci[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) cd[k] = C6[(size_t)i * 6 + k];
+    cd[0] *= lp1;
+    cd[3] *= lp1;
+    cd[5] *= lp1;
+    spd3_inverse(cd, ci);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) Ci6[(size_t)i * 6 + k] = ci[k];
+    const double b0 = b3[(size_t)i * 3], b1 = b3[(size_t)i * 3 + 1], b2 = b3[(size_t)i * 3 + 2];
+    Cib3[(size_t)i * 3 + 0] = ci[0] * b0 + ci[1] * b1 + ci[2] * b2;
+    Cib3[(size_t)i * 3 + 1] = ci[1] * b0 + ci[3] * b1 + ci[4] * b2;
+    Cib3[(size_t)i * 3 + 2] = ci[2] * b0 + ci[4] * b1 + ci[5] * b2;
+  }
+}
+
+// reset the LDS image: zero, unit diagonal on the padding columns
+template <int nbt, int LS>
+__device__ __forceinline__ void batch_reset_image(double *Lb, const int n6) {
+  const int tid = threadIdx.x;
+  for (int e = tid; e < nbt * LS; e += kBatchBlock) {
+    const int c = e / LS, r = e - c * LS;
+    Lb[e] = (r == c && c >= n6) ? 1.0 : 0.0;  // unit diagonal on padding columns
+  }
+}
+
+// Schur complement (reference :858-888): lower triangle of S and the reduced right-hand side
+// into the LDS image; one thread per half 6x6 block, the landmarks in ascending order
+template <int nbt, int LS>
+__device__ __forceinline__ void batch_schur(const int N, const int M, const double lp1, const int32_t *tab,
+                                            const double *Ci6, const double *Cib3, const double *Wg,
+                                            const uint8_t *blk_j, const uint8_t *blk_k, const double *A,
+                                            const double *a, double *Lb) {
+  const int tid = threadIdx.x, n6 = 6 * N;
+  const int n_task = N * (N + 1);  // (block, half): rows 3h .. 3h+2 of block (j, k), j >= k
+  for (int task = tid; task < n_task; task += kBatchBlock) {
+    const int blk = task >> 1, h3 = (task & 1) * 3;
+    const int j = blk_j[blk], k = blk_k[blk];
+    double acc[18];
+#pragma unroll
+    for (int e = 0; e < 18; ++e) acc[e] = 0.0;
+    for (int i = 0; i < M; ++i) {
+      const int pj = tab[(size_t)i * N + j];
+      const int pk = tab[(size_t)i * N + k];
+      if (pj < 0 || pk < 0) continue;
+      const double *I = Ci6 + (size_t)i * 6;
+      const double i00 = I[0], i01 = I[1], i02 = I[2], i11 = I[3], i12 = I[4], i22 = I[5];
+      const double *Wj = Wg + (size_t)pj * 18 + h3 * 3;
+      double Wk[18];
+#pragma unroll
+      for (int e = 0; e < 18; ++e) Wk[e] = Wg[(size_t)pk * 18 + e];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const double w0 = Wj[r * 3 + 0], w1 = Wj[r * 3 + 1], w2 = Wj[r * 3 + 2];
+        // V_ji = B_ji Cinv_i (reference :862), never stored
+        const double v0 = w0 * i00 + w1 * i01 + w2 * i02;
+        const double v1 = w0 * i01 + w1 * i11 + w2 * i12;
+        const double v2 = w0 * i02 + w1 * i12 + w2 * i22;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) acc[r * 6 + c] += v0 * Wk[c * 3 + 0] + v1 * Wk[c * 3 + 1] + v2 * Wk[c * 3 + 2];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        const int row = 6 * j + h3 + r, col = 6 * k + c;
+        if (row < col) continue;
+        double av = 0.0;
+        if (j == k) {
+          av = A[j * 36 + (h3 + r) * 6 + c];
+          if (h3 + r == c) av *= lp1;  // damped A_j (reference :833-844)
+        }
+        Lb[col * LS + row] = av - acc[r * 6 + c];
+      }
+  }
+  for (int t = tid; t < n6; t += kBatchBlock) {  // rhs_j = a_j - sum_i B_ji (Cinv_i b_i)
+    const int j = t / 6, r = t - 6 * j;
+    double acc = 0.0;
+    for (int i = 0; i < M; ++i) {
+      const int pj = tab[(size_t)i * N + j];
+      if (pj < 0) continue;
+      const double *Wj = Wg + (size_t)pj * 18 + r * 3;
+      const double *cb = Cib3 + (size_t)i * 3;
+      acc += Wj[0] * cb[0] + Wj[1] * cb[1] + Wj[2] * cb[2];
+    }
+    Lb[t * LS + nbt] = a[t] - acc;
+  }
 }
 
 template <int NPt>
@@ -210,167 +407,16 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch(BatchDev d) {
     double *Pt = s.P[cur ^ 1];
     const double lp1 = 1.0 + s.ctrl.lambda;
     if (need_lin) {
-      // ---- landmark side (reference :811-828) -----------------------------------------
-      for (int i = tid; i < M; i += kBatchBlock) {
-        const int q = opt_lm[i];
-        const double x0 = X[q * 3 + 0], x1 = X[q * 3 + 1], x2 = X[q * 3 + 2];
-        double C[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
-        const int o1 = lm_ptr[q + 1];
-        for (int t = lm_ptr[q]; t < o1; ++t) {
-          const int4 r = ob[t];
-          const double2 u = uvp[t];
-          const double *cam = s.cams + r.x * 16;
-          const double *T = Pc + r.y * 12;
-          ObsGeom g;
-          project(cam, T, x0, x1, x2, u.x, u.y, g);
-          double w, G[6], Rm[6];
-          weight_and_G(cam, g, huber, w, G);
-          make_R(G, T, Rm);
-          const double wr0 = w * g.r0, wr1 = w * g.r1;
-          C[0] += w * (Rm[0] * Rm[0] + Rm[3] * Rm[3]);
-          C[1] += w * (Rm[0] * Rm[1] + Rm[3] * Rm[4]);
-          C[2] += w * (Rm[0] * Rm[2] + Rm[3] * Rm[5]);
-          C[3] += w * (Rm[1] * Rm[1] + Rm[4] * Rm[4]);
-          C[4] += w * (Rm[1] * Rm[2] + Rm[4] * Rm[5]);
-          C[5] += w * (Rm[2] * Rm[2] + Rm[5] * Rm[5]);
-#pragma unroll
-          for (int c = 0; c < 3; ++c) b[c] -= Rm[c] * wr0 + Rm[3 + c] * wr1;
-          if (r.w >= 0 && (r.w & 1)) {  // the pair's last observation: B_ji = w Q^T R survives
-            double Q[12];
-            make_Q(G, g.Xij, Q);
-            double *Wp = Wg + (size_t)(r.w >> 1) * 18;
-#pragma unroll
-            for (int rr = 0; rr < 6; ++rr)
-#pragma unroll
-              for (int c = 0; c < 3; ++c) Wp[rr * 3 + c] = w * (Q[rr] * Rm[c] + Q[6 + rr] * Rm[3 + c]);
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) C6[(size_t)i * 6 + k] = C[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) b3[(size_t)i * 3 + k] = b[k];
-      }
-      // ---- pose side (reference :789-809): one wave per optimisable pose ----------------
-      for (int j = wv; j < N; j += kBatchBlock / 64) {
-        const int32_t *pp = d.pobs_ptr + pr.pptr0 + j;
-        const int32_t *po = d.pobs + pr.pobs0;
-        double acc[27];
-#pragma unroll
-        for (int k = 0; k < 27; ++k) acc[k] = 0.0;
-        const int e1 = pp[1];
-        for (int t = pp[0] + lane; t < e1; t += 64) {
-          const int so = po[t];
-          const int4 r = ob[so];
-          const double2 u = uvp[so];
-          const double *cam = s.cams + r.x * 16;
-          const double *Xp = X + (size_t)r.z * 3;
-          ObsGeom g;
-          project(cam, Pc + r.y * 12, Xp[0], Xp[1], Xp[2], u.x, u.y, g);
-          double w, G[6], Q[12];
-          weight_and_G(cam, g, huber, w, G);
-          make_Q(G, g.Xij, Q);
-          const double wr0 = w * g.r0, wr1 = w * g.r1;
-          int k = 0;
-#pragma unroll
-          for (int rr = 0; rr < 6; ++rr)
-#pragma unroll
-            for (int c = rr; c < 6; ++c, ++k) acc[k] += (w * Q[rr]) * Q[c] + (w * Q[6 + rr]) * Q[6 + c];
-#pragma unroll
-          for (int c = 0; c < 6; ++c) acc[21 + c] -= Q[c] * wr0 + Q[6 + c] * wr1;
-        }
-#pragma unroll
-        for (int k = 0; k < 27; ++k) acc[k] = wave_sum(acc[k]);
-        if (lane == 0) {
-          int k = 0;
-#pragma unroll
-          for (int rr = 0; rr < 6; ++rr)
-#pragma unroll
-            for (int c = rr; c < 6; ++c, ++k) {
-              s.A[j * 36 + rr * 6 + c] = acc[k];
-              s.A[j * 36 + c * 6 + rr] = acc[k];
-            }
-#pragma unroll
-          for (int c = 0; c < 6; ++c) s.a[j * 6 + c] = acc[21 + c];
-        }
-      }
+      batch_landmark_pass(M, opt_lm, lm_ptr, ob, uvp, s.cams, Pc, X, huber, C6, b3, Wg);
+      batch_pose_pass(N, d.pobs_ptr + pr.pptr0, d.pobs + pr.pobs0, ob, uvp, s.cams, Pc, X, huber, s.A, s.a);
       __syncthreads();
     }
     // ---- damp and invert (reference :846-856); reset the LDS image --------------------
-    for (int i = tid; i < M; i += kBatchBlock) {
-      double cd[6], ci[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) cd[k] = C6[(size_t)i * 6 + k];
-      cd[0] *= lp1;
-      cd[3] *= lp1;
-      cd[5] *= lp1;
-      spd3_inverse(cd, ci);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) Ci6[(size_t)i * 6 + k] = ci[k];
-      const double b0 = b3[(size_t)i * 3], b1 = b3[(size_t)i * 3 + 1], b2 = b3[(size_t)i * 3 + 2];
-      Cib3[(size_t)i * 3 + 0] = ci[0] * b0 + ci[1] * b1 + ci[2] * b2;
-      Cib3[(size_t)i * 3 + 1] = ci[1] * b0 + ci[3] * b1 + ci[4] * b2;
-      Cib3[(size_t)i * 3 + 2] = ci[2] * b0 + ci[4] * b1 + ci[5] * b2;
-    }
-    for (int e = tid; e < nbt * LS; e += kBatchBlock) {
-      const int c = e / LS, r = e - c * LS;
-      s.Lb[e] = (r == c && c >= n6) ? 1.0 : 0.0;  // unit diagonal on padding columns
-    }
+    batch_damp_invert(M, lp1, C6, b3, Ci6, Cib3);
+    batch_reset_image<nbt, LS>(s.Lb, n6);
     __syncthreads();
     // ---- Schur complement (reference :858-888), lower triangle, into the LDS image ----
-    const int n_task = N * (N + 1);  // (block, half): rows 3h .. 3h+2 of block (j, k), j >= k
-    for (int task = tid; task < n_task; task += kBatchBlock) {
-      const int blk = task >> 1, h3 = (task & 1) * 3;
-      const int j = s.blk_j[blk], k = s.blk_k[blk];
-      double acc[18];
-#pragma unroll
-      for (int e = 0; e < 18; ++e) acc[e] = 0.0;
-      for (int i = 0; i < M; ++i) {
-        const int pj = tab[(size_t)i * N + j];
-        const int pk = tab[(size_t)i * N + k];
-        if (pj < 0 || pk < 0) continue;
-        const double *I = Ci6 + (size_t)i * 6;
-        const double i00 = I[0], i01 = I[1], i02 = I[2], i11 = I[3], i12 = I[4], i22 = I[5];
-        const double *Wj = Wg + (size_t)pj * 18 + h3 * 3;
-        double Wk[18];
-#pragma unroll
-        for (int e = 0; e < 18; ++e) Wk[e] = Wg[(size_t)pk * 18 + e];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          const double w0 = Wj[r * 3 + 0], w1 = Wj[r * 3 + 1], w2 = Wj[r * 3 + 2];
-          // V_ji = B_ji Cinv_i (reference :862), never stored
-          const double v0 = w0 * i00 + w1 * i01 + w2 * i02;
-          const double v1 = w0 * i01 + w1 * i11 + w2 * i12;
-          const double v2 = w0 * i02 + w1 * i12 + w2 * i22;
-#pragma unroll
-          for (int c = 0; c < 6; ++c) acc[r * 6 + c] += v0 * Wk[c * 3 + 0] + v1 * Wk[c * 3 + 1] + v2 * Wk[c * 3 + 2];
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-          const int row = 6 * j + h3 + r, col = 6 * k + c;
-          if (row < col) continue;
-          double av = 0.0;
-          if (j == k) {
-            av = s.A[j * 36 + (h3 + r) * 6 + c];
-            if (h3 + r == c) av *= lp1;  // damped A_j (reference :833-844)
-          }
-          s.Lb[col * LS + row] = av - acc[r * 6 + c];
-        }
-    }
-    for (int t = tid; t < n6; t += kBatchBlock) {  // rhs_j = a_j - sum_i B_ji (Cinv_i b_i)
-      const int j = t / 6, r = t - 6 * j;
-      double acc = 0.0;
-      for (int i = 0; i < M; ++i) {
-        const int pj = tab[(size_t)i * N + j];
-        if (pj < 0) continue;
-        const double *Wj = Wg + (size_t)pj * 18 + r * 3;
-        const double *cb = Cib3 + (size_t)i * 3;
-        acc += Wj[0] * cb[0] + Wj[1] * cb[1] + Wj[2] * cb[2];
-      }
-      s.Lb[t * LS + nbt] = s.a[t] - acc;
-    }
+    batch_schur<nbt, LS>(N, M, lp1, tab, Ci6, Cib3, Wg, s.blk_j, s.blk_k, s.A, s.a, s.Lb);
     __syncthreads();
     // ---- reduced solve (reference :905) ------------------------------------------------
     chol_lds_factor_solve<NPt, false, LS>(s.Lb, s.Eb, s.xs, &res->dropped_pivots);
@@ -477,6 +523,174 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch(BatchDev d) {
   }
 }
 
+// ---- covariance blocks of every problem (ba_batch_covariance) -----------------------------
+// The LDS of the covariance kernel: the image, the tile inverses and one pose set; neither
+// the trial poses nor the controller of BatchLds.
+template <int NPt>
+struct BatchCovLds {
+  static constexpr int nbt = 16 * NPt;
+  static constexpr int LS = nbt + 16 + 1;
+  double Lb[nbt * LS];
+  double Eb[NPt][16 * kTailES];
+  double xs[kTailCols];
+  double cams[kCamLds * 16];
+  double P[kBatchMaxPoses * 12];
+  double A[kBatchMaxOpt * 36];
+  double a[kBatchMaxOpt * 6];
+  int32_t jopt[kBatchMaxPoses];
+  uint8_t blk_j[kBatchMaxBlk], blk_k[kBatchMaxBlk];
+};
+
+struct BatchCovOut {
+  double *pose36;  // 36 per pose of the batch (zeroed before the launch)
+  double *pt9;     // 9 per point of the batch, or nullptr
+  ba_batch_cov_result *res;
+  double huber;
+};
+
+// One workgroup per problem: linearise at the held values with lambda = 0, Schur complement
+// and Cholesky factor in LDS as k_ba_batch does, S^-1 in place (chol_lds_inverse), then
+//   pose block      [S^-1]_jj                                   one thread per element
+//   landmark block  Cinv_i + sum_jk Y_j^T [S^-1]_jk Y_k,        one thread per landmark,
+//                   Y_j = W_ji Cinv_i                           its pairs in ascending pose order
+// Every block is read from the lower triangle of S^-1 and mirrored: symmetric to the bit.
+// The outputs were zeroed by the host: fixed members, and every block of a problem that is
+// not processed (status 1 or 2), stay exactly zero.  Y_j overwrites W_ji in the scratch.
+template <int NPt>
+__global__ __launch_bounds__(kBatchBlock) void k_ba_batch_cov(BatchDev d, BatchCovOut o) {
+  using LDS = BatchCovLds<NPt>;
+  constexpr int nbt = LDS::nbt, LS = LDS::LS;
+  __shared__ LDS s;
+  const int tid = threadIdx.x;
+  const BatchProb pr = d.prob[blockIdx.x];
+  ba_batch_cov_result *res = o.res + blockIdx.x;
+  if (pr.status != 0) {
+    if (tid == 0) {
+      res->status = pr.status;
+      res->dropped_pivots = 0;
+    }
+    return;
+  }
+  const int N = pr.N, M = pr.M, n6 = 6 * N;
+  const double *Pg = d.poses + pr.pose0 * 12;
+  const double *X = d.pts[0] + pr.pt0 * 3;
+  // ---- stage the problem; refuse non-finite parameters -------------------------------
+  int bad_val = 0;
+  for (int k = tid; k < pr.n_cam * 16; k += kBatchBlock) s.cams[k] = d.cams[pr.cam0 * 16 + k];
+  for (int k = tid; k < pr.n_pose * 12; k += kBatchBlock) {
+    const double v = Pg[k];
+    s.P[k] = v;
+    bad_val |= !isfinite(v);
+  }
+  for (int k = tid; k < pr.n_pose; k += kBatchBlock) s.jopt[k] = d.jopt[pr.pose0 + k];
+  for (int k = tid; k < pr.n_pt * 3; k += kBatchBlock) bad_val |= !isfinite(X[k]);
+  for (int k = tid; k < (int)(sizeof(s.Eb) / sizeof(double)); k += kBatchBlock) (&s.Eb[0][0])[k] = 0.0;
+  if (tid == 0) {
+    int b = 0;
+    for (int j = 0; j < N; ++j)
+      for (int k = 0; k <= j; ++k, ++b) {
+        s.blk_j[b] = (uint8_t)j;
+        s.blk_k[b] = (uint8_t)k;
+      }
+    res->dropped_pivots = 0;
+  }
+  if (__syncthreads_or(bad_val)) {
+    if (tid == 0) res->status = 1;
+    return;
+  }
+  const int4 *ob = d.lobs + pr.obs0;
+  const double2 *uvp = d.luv + pr.obs0;
+  const int32_t *lm_ptr = d.lm_ptr + pr.pt0 + blockIdx.x;
+  const int32_t *opt_lm = d.opt_lm + pr.m0;
+  const int32_t *pair_ptr = d.pair_ptr + pr.m0 + blockIdx.x;
+  const int32_t *pair_j = d.pair_j + pr.pair0;
+  double *C6 = d.C6 + pr.m0 * 6, *b3 = d.b3 + pr.m0 * 3;
+  double *Ci6 = d.Cinv6 + pr.m0 * 6, *Cib3 = d.Cinvb3 + pr.m0 * 3;
+  double *Wg = d.W18 + pr.pair0 * 18;
+  // ---- linearise, lambda = 0; Schur complement; factor; invert --------------------------
+  batch_landmark_pass(M, opt_lm, lm_ptr, ob, uvp, s.cams, s.P, X, o.huber, C6, b3, Wg);
+  batch_pose_pass(N, d.pobs_ptr + pr.pptr0, d.pobs + pr.pobs0, ob, uvp, s.cams, s.P, X, o.huber, s.A, s.a);
+  __syncthreads();
+  batch_damp_invert(M, 1.0, C6, b3, Ci6, Cib3);
+  batch_reset_image<nbt, LS>(s.Lb, n6);
+  __syncthreads();
+  batch_schur<nbt, LS>(N, M, 1.0, d.tab + pr.tab0, Ci6, Cib3, Wg, s.blk_j, s.blk_k, s.A, s.a, s.Lb);
+  __syncthreads();
+  chol_lds_factor_solve<NPt, false, LS>(s.Lb, s.Eb, s.xs, &res->dropped_pivots);
+  __syncthreads();
+  chol_lds_inverse<NPt, LS>(s.Lb, s.Eb);  // ends with a barrier: the lower triangle holds S^-1
+  // ---- pose blocks: the diagonal of S^-1 ------------------------------------------------
+  for (int e = tid; e < pr.n_pose * 36; e += kBatchBlock) {
+    const int p = e / 36, rc = e - 36 * p, r = rc / 6, c = rc - 6 * r;
+    const int j = s.jopt[p];
+    if (j < 0) continue;
+    const int lo = r < c ? r : c, hi = r < c ? c : r;
+    o.pose36[(size_t)(pr.pose0 + p) * 36 + rc] = s.Lb[(6 * j + lo) * LS + 6 * j + hi];
+  }
+  if (!o.pt9) {
+    if (tid == 0) res->status = 0;
+    return;
+  }
+  // ---- landmark blocks ------------------------------------------------------------------
+  for (int i = tid; i < M; i += kBatchBlock) {
+    const double *I = Ci6 + (size_t)i * 6;
+    const double i00 = I[0], i01 = I[1], i02 = I[2], i11 = I[3], i12 = I[4], i22 = I[5];
+    const int p0 = pair_ptr[i], p1 = pair_ptr[i + 1];
+    for (int p = p0; p < p1; ++p) {  // Y_j = W_ji Cinv_i in place
+      double *W = Wg + (size_t)p * 18;
+#pragma unroll
+      for (int r = 0; r < 6; ++r) {
+        const double w0 = W[r * 3 + 0], w1 = W[r * 3 + 1], w2 = W[r * 3 + 2];
+        W[r * 3 + 0] = w0 * i00 + w1 * i01 + w2 * i02;
+        W[r * 3 + 1] = w0 * i01 + w1 * i11 + w2 * i12;
+        W[r * 3 + 2] = w0 * i02 + w1 * i12 + w2 * i22;
+      }
+    }
+    double acc[6] = {0, 0, 0, 0, 0, 0};  // (00 01 02 11 12 22)
+    for (int pa = p0; pa < p1; ++pa) {
+      const int j6 = 6 * pair_j[pa];
+      double T[18];  // sum_k [S^-1]_jk Y_k
+#pragma unroll
+      for (int e = 0; e < 18; ++e) T[e] = 0.0;
+      for (int pb = p0; pb < p1; ++pb) {
+        const int k6 = 6 * pair_j[pb];
+        double Y[18];
+#pragma unroll
+        for (int e = 0; e < 18; ++e) Y[e] = Wg[(size_t)pb * 18 + e];
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+          for (int c = 0; c < 6; ++c) {
+            const int row = j6 + r, col = k6 + c;
+            const double sv = row >= col ? s.Lb[col * LS + row] : s.Lb[row * LS + col];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) T[r * 3 + q] += sv * Y[c * 3 + q];
+          }
+      }
+      double Y[18];
+#pragma unroll
+      for (int e = 0; e < 18; ++e) Y[e] = Wg[(size_t)pa * 18 + e];
+      int k = 0;
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b, ++k) {
+          double v = 0.0;
+#pragma unroll
+          for (int r = 0; r < 6; ++r) v += Y[r * 3 + a] * T[r * 3 + b];
+          acc[k] += v;
+        }
+    }
+    double *out = o.pt9 + (size_t)(pr.pt0 + opt_lm[i]) * 9;
+    const double c00 = i00 + acc[0], c01 = i01 + acc[1], c02 = i02 + acc[2];
+    const double c11 = i11 + acc[3], c12 = i12 + acc[4], c22 = i22 + acc[5];
+    out[0] = c00; out[1] = c01; out[2] = c02;
+    out[3] = c01; out[4] = c11; out[5] = c12;
+    out[6] = c02; out[7] = c12; out[8] = c22;
+  }
+  if (tid == 0) res->status = 0;
+}
+
 }  // namespace
 }  // namespace ba
 
@@ -498,6 +712,8 @@ struct ba_batch {
   ba::BatchDev d{};
   ba::DevIterRec *rows = nullptr;
   size_t rows_cap = 0;  // records
+  char *cov = nullptr;  // outputs of ba_batch_covariance (allocated by its first call)
+  size_t cov_bytes = 0, cov_pt_off = 0, cov_res_off = 0;
 };
 
 namespace {
@@ -786,6 +1002,7 @@ void ba_batch_destroy(ba_batch *b) {
   if (!b) return;
   if (b->dev) (void)hipFree(b->dev);
   if (b->rows) (void)hipFree(b->rows);
+  if (b->cov) (void)hipFree(b->cov);
   delete b;
 }
 
@@ -880,6 +1097,42 @@ int ba_batch_solve(ba_batch *b, const ba_options *opt, ba_iter_info *rows, int c
   HIP_TRY(hipMemcpyAsync(res, d.res, (size_t)B * sizeof(ba_batch_result), hipMemcpyDeviceToHost, s));
   if (dcap > 0)
     HIP_TRY(hipMemcpyAsync(rows, b->rows, n_rows * sizeof(ba_iter_info), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ba_batch_covariance(ba_batch *b, double huber, double *cov_pose36, double *cov_pt9, ba_batch_cov_result *res) {
+  if (!b) return fail("ba_batch_covariance: null batch");
+  if (!cov_pose36) return fail("ba_batch_covariance: null cov_pose36");
+  if (!res) return fail("ba_batch_covariance: null result array");
+  const int B = b->B;
+  HIP_TRY(hipSetDevice(b->h->device));
+  hipStream_t s = b->h->stream;
+  if (!b->cov) {  // outputs of the call, kept with the object: pose blocks | point blocks | results
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    b->cov_pt_off = al((size_t)b->n_pose * 36 * sizeof(double));
+    b->cov_res_off = b->cov_pt_off + al((size_t)b->n_pt * 9 * sizeof(double));
+    b->cov_bytes = b->cov_res_off + al((size_t)B * sizeof(ba_batch_cov_result));
+    HIP_TRY(hipMalloc((void **)&b->cov, b->cov_bytes));
+  }
+  ba::BatchCovOut o;
+  o.pose36 = (double *)b->cov;
+  o.pt9 = cov_pt9 ? (double *)(b->cov + b->cov_pt_off) : nullptr;
+  o.res = (ba_batch_cov_result *)(b->cov + b->cov_res_off);
+  o.huber = huber;
+  HIP_TRY(hipMemsetAsync(b->cov, 0, b->cov_bytes, s));  // fixed members and unprocessed problems: exact zeros
+  if (b->npt_class == 2)
+    hipLaunchKernelGGL(ba::k_ba_batch_cov<2>, dim3(B), dim3(ba::kBatchBlock), 0, s, b->d, o);
+  else if (b->npt_class == 4)
+    hipLaunchKernelGGL(ba::k_ba_batch_cov<4>, dim3(B), dim3(ba::kBatchBlock), 0, s, b->d, o);
+  else
+    hipLaunchKernelGGL(ba::k_ba_batch_cov<6>, dim3(B), dim3(ba::kBatchBlock), 0, s, b->d, o);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(res, o.res, (size_t)B * sizeof(ba_batch_cov_result), hipMemcpyDeviceToHost, s));
+  if (b->n_pose > 0)
+    HIP_TRY(hipMemcpyAsync(cov_pose36, o.pose36, (size_t)b->n_pose * 36 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (cov_pt9 && b->n_pt > 0)
+    HIP_TRY(hipMemcpyAsync(cov_pt9, o.pt9, (size_t)b->n_pt * 9 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return 0;
 }

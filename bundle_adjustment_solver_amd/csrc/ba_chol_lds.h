@@ -1,7 +1,7 @@
 // ba_chol_lds.h — Cholesky factorisation and solve of a small SPD system held in LDS by
 // ONE 256-thread workgroup: the tail block of the level-scheduled reduced solve
 // (k_chol_tail, ba_dense.hip) and the whole reduced camera system of a batched window
-// problem (ba_batch.hip).  Internal.
+// problem (ba_batch.hip), and the inverse of that system from its factor.  Internal.
 #ifndef BA_CHOL_LDS_H_
 #define BA_CHOL_LDS_H_
 
@@ -132,6 +132,68 @@ __device__ __forceinline__ void chol_lds_factor_solve(double *Lb, double (*Eb)[1
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
   }
+}
+
+// S^-1 = L^-T L^-1 of the system chol_lds_factor_solve left in the image, in place.  On
+// entry the lower triangle of Lb holds L and Eb[p] = L_pp^-T; the off-diagonal tiles of the
+// upper triangle are free.
+//   (1) Z = L^-1 by block triangular inversion, Z_pp = E_pp^T and
+//         Z_tp = -E_tt^T sum_{p <= u < t} L_tu Z_up            (t > p),
+//       stored as tile (p, t) of the upper triangle: Z_tp(a, b) at Lb[(16 t + a) LS + 16 p + b].
+//       Tiles of one distance t - p depend on smaller distances only: one level per distance,
+//       its tiles dealt to the four waves.
+//   (2) [S^-1]_pq = sum_{u >= p} Z_up^T Z_uq (p >= q) into the lower triangle, the diagonal
+//       tiles in full.  L is gone afterwards; Eb is kept.
+// Every sum is an MFMA chain in ascending tile order, so a padding tile (unit diagonal,
+// Z = identity there) adds exact zeros after the last real term: the same bits at any NPt.
+// Starts after a barrier of the caller and ends with one.
+template <int NPt, int LS>
+__device__ __forceinline__ void chol_lds_inverse(double *Lb, double (*Eb)[16 * kTailES]) {
+  typedef double v4f64 __attribute__((ext_vector_type(4)));
+  constexpr int ES = kTailES;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+  // operand maps: A[i = lr][k = lk + 4 s], B[k = lk + 4 s][j = lr], D register g = D[lk + 4 g][lr]
+#pragma unroll
+  for (int dist = 1; dist < NPt; ++dist) {
+    for (int p = wv; p + dist < NPt; p += 4) {
+      const int t = p + dist;
+      v4f64 acc = (v4f64){0.0, 0.0, 0.0, 0.0};  // R(a, b) = sum_u L_tu Z_up, i = a, j = b
+      for (int u = p; u < t; ++u)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int k = lk + 4 * s;
+          const double a = Lb[(16 * u + k) * LS + 16 * t + lr];
+          const double b = (u == p) ? Eb[p][lr * ES + k] : Lb[(16 * u + k) * LS + 16 * p + lr];
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+        }
+      v4f64 z = (v4f64){0.0, 0.0, 0.0, 0.0};  // Z_tp = -E_tt^T R: an accumulator is the next B operand
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        z = __builtin_amdgcn_mfma_f64_16x16x4f64(-Eb[t][(lk + 4 * s) * ES + lr], acc[s], z, 0, 0, 0);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) Lb[(16 * t + lk + 4 * g) * LS + 16 * p + lr] = z[g];
+    }
+    __syncthreads();
+  }
+  // (2) D[b][a] = sum_u sum_k Z_uq(k, b) Z_up(k, a) -> Lb[(16 q + b) LS + 16 p + a]
+  for (int task = wv; task < NPt * (NPt + 1) / 2; task += 4) {
+    int p = 0;
+    while ((p + 1) * (p + 2) / 2 <= task) ++p;
+    const int q = task - p * (p + 1) / 2;
+    v4f64 acc = (v4f64){0.0, 0.0, 0.0, 0.0};
+    for (int u = p; u < NPt; ++u)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int k = lk + 4 * s;
+        const double a = (u == q) ? Eb[q][lr * ES + k] : Lb[(16 * u + k) * LS + 16 * q + lr];
+        const double b = (u == p) ? Eb[p][lr * ES + k] : Lb[(16 * u + k) * LS + 16 * p + lr];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+      }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) Lb[(16 * q + lk + 4 * g) * LS + 16 * p + lr] = acc[g];
+  }
+  __syncthreads();
 }
 
 }  // namespace ba

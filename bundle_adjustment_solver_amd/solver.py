@@ -1091,6 +1091,25 @@ class BaBatch:
                for p in range(self.B)]
         return out, [res[p] for p in range(self.B)]
 
+    def covariance(self, huber, points=True):
+        """-> (cov_pose [n_pose, 6, 6], cov_pt [n_pt, 3, 3] or None, results): the
+        covariance blocks of every problem at the values the object holds, one
+        launch (ba_batch_covariance; scaled units, concatenated user order, blocks
+        of fixed members zero), results[p] = its BaBatchCovResult."""
+        cp = np.zeros((self.n_pose, 6, 6))
+        cq = np.zeros((self.n_pt, 3, 3)) if points else None
+        res = (_lib.BaBatchCovResult * self.B)()
+        check(self.lib.ba_batch_covariance(self.b, float(huber), _dp(cp),
+                                           _dp(cq) if points else None, res),
+              "ba_batch_covariance")
+        return cp, cq, [res[p] for p in range(self.B)]
+
+    def cov_poses_of(self, p, cov_pose):
+        return cov_pose[self.pose_off[p]:self.pose_off[p + 1]]
+
+    def cov_points_of(self, p, cov_pt):
+        return cov_pt[self.pt_off[p]:self.pt_off[p + 1]]
+
     def update_values(self, T_jw12=None, X3=None):
         T = None if T_jw12 is None else np.ascontiguousarray(T_jw12, np.float64).reshape(-1, 12)
         X = None if X3 is None else np.ascontiguousarray(X3, np.float64).reshape(-1, 3)
@@ -1642,6 +1661,40 @@ class FullBundleAdjustmentSolver:
         finally:
             batch.close()
         return res
+
+    @staticmethod
+    def ComputeCovarianceBatch(solvers, sigma_pixel=1.0, options=None, points=True):
+        """(new) Covariance blocks of the CURRENT registered values of several
+        solver objects in ONE launch (ba_batch_covariance; see BaBatch for the
+        limits).  Returns one (cov_pose (n_pose, 6, 6), cov_point (n_pt, 3, 3) or
+        None, BaBatchCovResult) per solver: ALL poses and points in registration
+        order, the blocks of fixed members zero, units and conventions those of
+        ComputeCovariance.  A result whose status is not 0 (over a limit,
+        non-finite input) has zero blocks; dropped_pivots > 0 means S was singular."""
+        solvers = list(solvers)
+        if not solvers:
+            return []
+        if any(sv._shard[1] > 1 or sv._allreduce is not None for sv in solvers):
+            raise RuntimeError("ComputeCovarianceBatch: a solver with a shard or an "
+                               "all-reduce configured cannot be part of a batch")
+        probs = []
+        for sv in solvers:
+            intr, camT, T_jw, X, pf, qf, ocam, opose, opt, ouv = sv._host_arrays()
+            probs.append(dict(cam_intr=intr, cam_T=camT, pose_T=T_jw, pose_fixed=pf, pt_X=X,
+                              pt_fixed=qf, obs_cam=ocam, obs_pose=opose, obs_pt=opt, obs_uv=ouv))
+        huber = (options or Options()).outlier_handle.threshold_huber_loss
+        batch = BaBatch(probs, solvers[0].device)
+        try:
+            cp, cq, res = batch.covariance(huber, points)
+            out = []
+            for k in range(len(solvers)):
+                cp_k = batch.cov_poses_of(k, cp)
+                cq_k = batch.cov_points_of(k, cq) if points else np.zeros((0, 3, 3))
+                up, uq = covariance_to_user_units(cp_k, cq_k, sigma_pixel)
+                out.append((up, uq if points else None, res[k]))
+        finally:
+            batch.close()
+        return out
 
     def ComputeCovariance(self, poses, points, sigma_pixel=1.0, options=None):
         """(new; the reference has no counterpart) Covariance blocks of the CURRENT

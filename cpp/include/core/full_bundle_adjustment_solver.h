@@ -19,6 +19,7 @@
 #include "utility/timer.h"
 
 struct ba_handle;  // include/ba_hip.h
+struct ba_batch;
 
 namespace visual_navigation {
 namespace analytic_solver {
@@ -113,6 +114,17 @@ class FullBundleAdjustmentSolver {
   bool ComputeCovariance(const std::vector<_BA_Pose *> &poses, const std::vector<_BA_Point *> &points,
                          double sigma_pixel, std::vector<Eigen::Matrix<double, 6, 6>> *cov_poses,
                          std::vector<Eigen::Matrix<double, 3, 3>> *cov_points);
+  // (new) The covariance blocks of several solver objects in ONE launch
+  // (ba_batch_covariance of include/ba_hip.h; the limits of SolveBatch per problem): for
+  // solver b, cov_poses[b] holds one block per registered pose and cov_points[b] (null:
+  // skipped) one per registered point, in registration order, at the solvers' CURRENT
+  // values; blocks of fixed members are zero.  Units and conventions are those of
+  // ComputeCovariance.  The solvers need not be finalized; the first solver's device is
+  // used; sharded solvers are refused (std::runtime_error).  Returns true when every
+  // problem has status 0 and its factorisation met no non-positive pivot.
+  static bool ComputeCovarianceBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, double sigma_pixel,
+                                     std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
+                                     std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points);
   // the C-ABI handle behind the finalized problem (nullptr before FinalizeParameters):
   // for the readers of include/ba_hip.h; indices there are registration order
   ba_handle *GetHandle() const { return handle_; }
@@ -150,6 +162,19 @@ class FullBundleAdjustmentSolver {
   // copies and through the caller's pointers (:1011-1022); fixed members and points with
   // valid[q] == 0 are skipped.  Shared by Run and SolveBatch.
   void WriteBack(const double *T_jw12, const double *X3, const uint8_t *valid);
+  // the concatenated arrays of ba_batch_create for a list of solvers (registered values,
+  // not finalized state); shared by SolveBatch and ComputeCovarianceBatch
+  struct BatchArrays {
+    std::vector<int32_t> cam_off, pose_off, pt_off, oc, op, oq;
+    std::vector<int64_t> obs_off;
+    std::vector<double> intr, T_cj, T, X, uv;
+    std::vector<uint8_t> pose_fixed, point_fixed;
+  };
+  static void PackBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, const char *who,
+                        bool check_connectivity, BatchArrays *out);
+  // ba_create + ba_batch_create on `device`; returns ba_batch_create's code (the caller
+  // destroys both objects)
+  static int CreateBatch(const BatchArrays &a, int device, ba_handle **h, ba_batch **batch);
   // the options' thresholds and iteration limit into a Summary (nullptr: nothing)
   static void BeginSummary(Summary *summary, const Options &options);
   // stderr warnings about weakly connected poses / points (reference

@@ -79,6 +79,16 @@ class FullBundleAdjustmentSolverRefactor {
                          std::vector<Eigen::Matrix<double, 3, 3>> *cov_points) {
     return impl_.ComputeCovariance(poses, points, sigma_pixel, cov_poses, cov_points);
   }
+  // (new) the blocks of several solvers in one launch, see
+  // FullBundleAdjustmentSolver::ComputeCovarianceBatch
+  static bool ComputeCovarianceBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers,
+                                     double sigma_pixel,
+                                     std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
+                                     std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points) {
+    std::vector<FullBundleAdjustmentSolver *> impls;
+    for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
+    return FullBundleAdjustmentSolver::ComputeCovarianceBatch(impls, sigma_pixel, cov_poses, cov_points);
+  }
   ba_handle *GetHandle() const { return impl_.GetHandle(); }
 
   std::string GetSolverStatistics() const;

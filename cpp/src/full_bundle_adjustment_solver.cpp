@@ -441,6 +441,56 @@ bool FullBundleAdjustmentSolver::ComputeCovariance(const std::vector<_BA_Pose *>
   return dropped == 0;
 }
 
+void FullBundleAdjustmentSolver::PackBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, const char *who,
+                                           bool check_connectivity, BatchArrays *out) {
+  BatchArrays &a = *out;
+  a.cam_off.assign(1, 0);
+  a.pose_off.assign(1, 0);
+  a.pt_off.assign(1, 0);
+  a.obs_off.assign(1, 0);
+  const std::string name(who);
+  for (FullBundleAdjustmentSolver *s : solvers) {
+    if (s == nullptr) throw std::runtime_error(name + ": null solver");
+    if (s->shard_world_ > 1 || s->allreduce_fn_) throw std::runtime_error(name + ": a sharded solver cannot join a batch");
+    if (s->cameras_.empty() || s->poses_.empty() || s->points_.empty())
+      throw std::runtime_error(name + ": cameras, poses and points must be added first");
+    if (check_connectivity) s->CheckPoseAndPointConnectivity();
+    for (size_t c = 0; c < s->cameras_.size(); ++c) {
+      a.intr.insert(a.intr.end(), {s->cameras_[c].fx, s->cameras_[c].fy, s->cameras_[c].cx, s->cameras_[c].cy});
+      a.T_cj.resize(a.T_cj.size() + 12);
+      Pack12(s->cameras_[c].pose_this_to_cam0, &a.T_cj[a.T_cj.size() - 12]);
+    }
+    for (size_t p = 0; p < s->poses_.size(); ++p) {
+      a.T.resize(a.T.size() + 12);
+      Pack12(s->T_jw_[p], &a.T[a.T.size() - 12]);
+      a.pose_fixed.push_back(s->fixed_poses_.count(static_cast<int>(p)) > 0);
+    }
+    for (size_t q = 0; q < s->points_.size(); ++q) {
+      for (int r = 0; r < 3; ++r) a.X.push_back(s->X_[q](r));
+      a.point_fixed.push_back(s->fixed_points_.count(static_cast<int>(q)) > 0);
+    }
+    for (const Observation &o : s->observations_) {  // insertion order matters (:826)
+      a.oc.push_back(o.camera_index);
+      a.op.push_back(o.pose_index);
+      a.oq.push_back(o.point_index);
+      a.uv.push_back(o.u);
+      a.uv.push_back(o.v);
+    }
+    a.cam_off.push_back(static_cast<int32_t>(a.intr.size() / 4));
+    a.pose_off.push_back(static_cast<int32_t>(a.pose_fixed.size()));
+    a.pt_off.push_back(static_cast<int32_t>(a.point_fixed.size()));
+    a.obs_off.push_back(static_cast<int64_t>(a.oc.size()));
+  }
+}
+
+int FullBundleAdjustmentSolver::CreateBatch(const BatchArrays &a, int device, ba_handle **h, ba_batch **batch) {
+  Check(ba_create(h, device), "ba_create");
+  return ba_batch_create(batch, *h, static_cast<int>(a.obs_off.size()) - 1, a.cam_off.data(), a.pose_off.data(),
+                         a.pt_off.data(), a.obs_off.data(), a.intr.data(), a.T_cj.data(), a.T.data(),
+                         a.pose_fixed.data(), a.X.data(), a.point_fixed.data(), a.oc.data(), a.op.data(), a.oq.data(),
+                         a.uv.data());
+}
+
 bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, Options options,
                                             std::vector<Summary> *summaries) {
   timer::StopWatch stopwatch("BundleAdjustmentSolver::SolveBatch");
@@ -448,52 +498,17 @@ bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustme
   const int B = static_cast<int>(solvers.size());
   if (summaries != nullptr) summaries->assign(static_cast<size_t>(B), Summary());
   if (B == 0) return true;
-  std::vector<int32_t> cam_off(1, 0), pose_off(1, 0), pt_off(1, 0), oc, op, oq;
-  std::vector<int64_t> obs_off(1, 0);
-  std::vector<double> intr, T_cj, T, X, uv;
-  std::vector<uint8_t> pose_fixed, point_fixed;
-  for (FullBundleAdjustmentSolver *s : solvers) {
-    if (s == nullptr) throw std::runtime_error("SolveBatch: null solver");
-    if (s->shard_world_ > 1 || s->allreduce_fn_) throw std::runtime_error("SolveBatch: a sharded solver cannot join a batch");
-    if (s->cameras_.empty() || s->poses_.empty() || s->points_.empty())
-      throw std::runtime_error("SolveBatch: cameras, poses and points must be added first");
-    s->CheckPoseAndPointConnectivity();
-    for (size_t c = 0; c < s->cameras_.size(); ++c) {
-      intr.insert(intr.end(), {s->cameras_[c].fx, s->cameras_[c].fy, s->cameras_[c].cx, s->cameras_[c].cy});
-      T_cj.resize(T_cj.size() + 12);
-      Pack12(s->cameras_[c].pose_this_to_cam0, &T_cj[T_cj.size() - 12]);
-    }
-    for (size_t p = 0; p < s->poses_.size(); ++p) {
-      T.resize(T.size() + 12);
-      Pack12(s->T_jw_[p], &T[T.size() - 12]);
-      pose_fixed.push_back(s->fixed_poses_.count(static_cast<int>(p)) > 0);
-    }
-    for (size_t q = 0; q < s->points_.size(); ++q) {
-      for (int r = 0; r < 3; ++r) X.push_back(s->X_[q](r));
-      point_fixed.push_back(s->fixed_points_.count(static_cast<int>(q)) > 0);
-    }
-    for (const Observation &o : s->observations_) {  // insertion order matters (:826)
-      oc.push_back(o.camera_index);
-      op.push_back(o.pose_index);
-      oq.push_back(o.point_index);
-      uv.push_back(o.u);
-      uv.push_back(o.v);
-    }
-    cam_off.push_back(static_cast<int32_t>(intr.size() / 4));
-    pose_off.push_back(static_cast<int32_t>(pose_fixed.size()));
-    pt_off.push_back(static_cast<int32_t>(point_fixed.size()));
-    obs_off.push_back(static_cast<int64_t>(oc.size()));
-  }
+  BatchArrays a;
+  PackBatch(solvers, "SolveBatch", true, &a);
+  std::vector<int32_t> &pose_off = a.pose_off, &pt_off = a.pt_off;
+  std::vector<double> &T = a.T, &X = a.X;
   const ba_options o = PackOptions(options, solvers[0]->gauss_newton_);
   const int cap = std::max(1, o.max_num_iterations);
   std::vector<ba_iter_info> rows(static_cast<size_t>(B) * cap);
   std::vector<ba_batch_result> res(static_cast<size_t>(B));
   ba_handle *h = nullptr;
   ba_batch *batch = nullptr;
-  Check(ba_create(&h, solvers[0]->device_id_), "ba_create");
-  int rc = ba_batch_create(&batch, h, B, cam_off.data(), pose_off.data(), pt_off.data(), obs_off.data(), intr.data(),
-                           T_cj.data(), T.data(), pose_fixed.data(), X.data(), point_fixed.data(), oc.data(), op.data(),
-                           oq.data(), uv.data());
+  int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
   if (rc == 0) rc = ba_batch_solve(batch, &o, rows.data(), cap, res.data());
   if (rc == 0) rc = ba_batch_get_poses(batch, T.data());
   if (rc == 0) rc = ba_batch_get_points(batch, X.data());
@@ -523,6 +538,60 @@ bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustme
     }
   }
   return all_solved;
+}
+
+bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
+    const std::vector<FullBundleAdjustmentSolver *> &solvers, double sigma_pixel,
+    std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
+    std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points) {
+  const int B = static_cast<int>(solvers.size());
+  if (cov_poses != nullptr) cov_poses->assign(static_cast<size_t>(B), std::vector<Eigen::Matrix<double, 6, 6>>());
+  if (cov_points != nullptr) cov_points->assign(static_cast<size_t>(B), std::vector<Eigen::Matrix<double, 3, 3>>());
+  if (B == 0) return true;
+  if (cov_poses == nullptr) throw std::runtime_error("ComputeCovarianceBatch: null output for the pose blocks");
+  BatchArrays a;
+  PackBatch(solvers, "ComputeCovarianceBatch", false, &a);
+  std::vector<double> cp(36 * a.pose_fixed.size()), cq(cov_points ? 9 * a.point_fixed.size() : 0);
+  std::vector<ba_batch_cov_result> res(static_cast<size_t>(B));
+  const Options defaults;
+  ba_handle *h = nullptr;
+  ba_batch *batch = nullptr;
+  int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
+  if (rc == 0)
+    rc = ba_batch_covariance(batch, static_cast<double>(defaults.outlier_handle.threshold_huber_loss), cp.data(),
+                             cov_points ? cq.data() : nullptr, res.data());
+  const std::string err = rc ? ba_last_error() : "";
+  ba_batch_destroy(batch);
+  ba_destroy(h);
+  if (rc) throw std::runtime_error("ComputeCovarianceBatch failed: " + err);
+  // scaled units, unit pixel noise -> the caller's units (see ComputeCovariance)
+  bool all_good = true;
+  for (int b = 0; b < B; ++b) {
+    const FullBundleAdjustmentSolver *s = solvers[b];
+    const double s2 = sigma_pixel * sigma_pixel;
+    const double k_pose = s2 * static_cast<double>(s->scaler_) * static_cast<double>(s->scaler_);
+    all_good = all_good && res[b].status == 0 && res[b].dropped_pivots == 0;
+    auto &out_p = (*cov_poses)[b];
+    out_p.resize(static_cast<size_t>(a.pose_off[b + 1] - a.pose_off[b]));
+    for (size_t k = 0; k < out_p.size(); ++k) {
+      const double *src = &cp[36 * (static_cast<size_t>(a.pose_off[b]) + k)];
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) {
+          const double dr = r < 3 ? static_cast<double>(s->inverse_scaler_) : 1.0;
+          const double dc = c < 3 ? static_cast<double>(s->inverse_scaler_) : 1.0;
+          out_p[k](r, c) = k_pose * (dr * src[6 * r + c] * dc);
+        }
+    }
+    if (cov_points == nullptr) continue;
+    auto &out_q = (*cov_points)[b];
+    out_q.resize(static_cast<size_t>(a.pt_off[b + 1] - a.pt_off[b]));
+    for (size_t k = 0; k < out_q.size(); ++k) {
+      const double *src = &cq[9 * (static_cast<size_t>(a.pt_off[b]) + k)];
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) out_q[k](r, c) = s2 * src[3 * r + c];
+    }
+  }
+  return all_good;
 }
 
 }  // namespace analytic_solver

@@ -641,6 +641,32 @@ void ba_batch_destroy(ba_batch *b);
  * whatever its status. */
 int ba_batch_solve(ba_batch *b, const ba_options *opt, ba_iter_info *rows, int cap,
                    ba_batch_result *res);
+/* Covariance blocks of EVERY problem of the batch at the values the object holds (after
+ * ba_batch_solve: the solution), one launch and one synchronisation on the handle's stream.
+ * Per problem the semantics are those of ba_covariance: linearised with lambda = 0 and the
+ * given Huber threshold (last-writer rule of the cross block, the 3x3 inverse with its
+ * fallback), S formed and factored unpivoted in LDS, S^-1 = L^-T L^-1 built in place by
+ * block triangular inversion (fp64 MFMA), then
+ *   cov_pose36  36 per pose of the batch, concatenated user order: [S^-1]_jj, row-major 6x6;
+ *   cov_pt9     9 per point of the batch, concatenated user order (NULL: skipped):
+ *               Cinv_i + Cinv_i W_i^T Sigma_P(i) W_i Cinv_i, Sigma_P(i) = ALL blocks of S^-1,
+ *               off-diagonal ones included, among the poses paired with landmark i.
+ * Scaled units, pose tangent xi = [v; omega] of T_jw <- exp(xi) T_jw.  Blocks of fixed poses
+ * and fixed points are exactly zero, and so is the block of a never-observed landmark.
+ * Every block is symmetric to the bit.  res[p].status follows ba_batch_result (0 = done,
+ * 1 = a non-finite value on entry, 2 = over a limit; for 1 and 2 every block of the problem
+ * is zero and the other problems are unaffected); res[p].dropped_pivots > 0 tells that S was
+ * singular at lambda = 0 (no fixed pose, for example) and the blocks meaningless.
+ * Nothing a later call can see changes: poses, points and the bits of a following
+ * ba_batch_solve; the per-landmark scratch is overwritten, which ba_batch_solve rebuilds.
+ * No floating-point atomics, fixed summation order per problem: the same bits run to run,
+ * alone and at any position of any batch, at any image width.  b, cov_pose36 and res are
+ * checked for NULL before anything touches the GPU: -1 and ba_last_error. */
+typedef struct {
+  int status, dropped_pivots;
+} ba_batch_cov_result;
+int ba_batch_covariance(ba_batch *b, double huber, double *cov_pose36, double *cov_pt9,
+                        ba_batch_cov_result *res);
 /* new values for the same structure, concatenated user order; NULL = keep */
 int ba_batch_update_values(ba_batch *b, const double *T_jw12, const double *X3);
 int ba_batch_get_poses(ba_batch *b, double *T_jw12);
