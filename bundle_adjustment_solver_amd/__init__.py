@@ -9,7 +9,7 @@ from .solver import (BaProblem, Camera, FullBundleAdjustmentSolver,  # noqa
                      FullBundleAdjustmentSolverRefactor,
                      IterationStatus, OptimizationInfo, Options,
                      PoseOnlyBundleAdjustmentSolver, SolverType, Summary,
-                     covariance_to_user_units)
+                     covariance_to_user_units, marginal_to_user_units)
 from . import scenes  # noqa
 from . import scene_io  # noqa
 
@@ -17,4 +17,4 @@ __all__ = ["BaProblem", "Camera", "FullBundleAdjustmentSolver",
            "FullBundleAdjustmentSolverRefactor",
            "IterationStatus", "OptimizationInfo", "Options",
            "PoseOnlyBundleAdjustmentSolver", "SolverType", "Summary",
-           "covariance_to_user_units", "scenes", "scene_io"]
+           "covariance_to_user_units", "marginal_to_user_units", "scenes", "scene_io"]

@@ -89,6 +89,13 @@ class BaBatchCovResult(C.Structure):
     _fields_ = [("status", C.c_int), ("dropped_pivots", C.c_int)]
 
 
+class BaBatchMargResult(C.Structure):
+    """ba_batch_marg_result — one problem of ba_batch_marginalize (status as
+    BaBatchResult; dropped_pivots > 0: the marked block was singular)."""
+    _fields_ = [("status", C.c_int), ("dropped_pivots", C.c_int), ("n_kept", C.c_int),
+                ("n_marg_pose", C.c_int), ("n_marg_pt", C.c_int)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                            C.c_int64, C.c_void_p)
 
@@ -246,6 +253,11 @@ SIGNATURES = {
     "ba_batch_solve": (C.c_int, [_P, C.POINTER(BaOptions), C.POINTER(BaIterInfo),
                                  C.c_int, C.POINTER(BaBatchResult)]),
     "ba_batch_covariance": (C.c_int, [_P, C.c_double, _D, _D, C.POINTER(BaBatchCovResult)]),
+    "ba_batch_marginalize": (C.c_int, [_P, C.c_double, _U8, _D, _D, _U8,
+                                       C.POINTER(BaBatchMargResult)]),
+    "ba_batch_marg_layout": (C.c_int, [_P, _U8, _I64, _I64]),
+    "ba_batch_marg_plan_problem": (C.c_int, [C.c_int, _U8, _U8, C.c_int, _U8, C.c_int64,
+                                             _I32, _I32, _I32, _U8]),
     "ba_batch_update_values": (C.c_int, [_P, _D, _D]),
     "ba_batch_get_poses": (C.c_int, [_P, _D]),
     "ba_batch_get_points": (C.c_int, [_P, _D]),

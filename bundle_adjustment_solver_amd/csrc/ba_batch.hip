@@ -26,6 +26,11 @@
 // and then inverts the factor in LDS (chol_lds_inverse) and reads the covariance blocks of
 // every pose and landmark of the problem off S^-1.
 //
+// k_ba_batch_marg (ba_batch_marginalize) runs the same first half over the landmarks the
+// marked poses observe only, with the marked poses' columns first in the image, and stops
+// the factorisation after them (chol_lds_partial): the trailing update is the prior the
+// window leaves on its kept poses.
+//
 // Host side: ba_batch_create plans the structure once (stable landmark-major grouping,
 // pair lists, last-writer marks, one upload); ba_batch_solve is one launch and one sync.
 #include <hip/hip_runtime.h>
@@ -118,14 +123,18 @@ __device__ __forceinline__ double batch_cost(const BatchDev &d, const BatchProb 
 
 // ---- the steps of one linearisation, shared by k_ba_batch and k_ba_batch_cov --------------
 // landmark side (reference :811-828): one thread per optimisable landmark, its observations
-// in insertion order; C_i, b_i and the cross block of a pair's LAST observation
+// in insertion order; C_i, b_i and the cross block of a pair's LAST observation.
+// sel (here and in the steps below): nullptr, or one byte per point of the problem; a
+// landmark whose byte is 0 is left out of the linearisation (k_ba_batch_marg)
 __device__ __forceinline__ void batch_landmark_pass(const int M, const int32_t *opt_lm, const int32_t *lm_ptr,
                                                     const int4 *ob, const double2 *uvp, const double *cams,
                                                     const double *Pc, const double *X, const double huber,
-                                                    double *C6, double *b3, double *Wg) {
+                                                    double *C6, double *b3, double *Wg,
+                                                    const uint8_t *sel = nullptr) {
   const int tid = threadIdx.x;
   for (int i = tid; i < M; i += kBatchBlock) {
     const int q = opt_lm[i];
+    if (sel && !sel[q]) continue;
     const double x0 = X[q * 3 + 0], x1 = X[q * 3 + 1], x2 = X[q * 3 + 2];
     double C[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
     const int o1 = lm_ptr[q + 1];
@@ -168,7 +177,8 @@ __device__ __forceinline__ void batch_landmark_pass(const int M, const int32_t *
 // pose side (reference :789-809): one wave per optimisable pose, 27 wave sums -> A_j, a_j in LDS
 __device__ __forceinline__ void batch_pose_pass(const int N, const int32_t *pp0, const int32_t *po, const int4 *ob,
                                                 const double2 *uvp, const double *cams, const double *Pc,
-                                                const double *X, const double huber, double *A, double *a) {
+                                                const double *X, const double huber, double *A, double *a,
+                                                const uint8_t *sel = nullptr) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int j = wv; j < N; j += kBatchBlock / 64) {
     const int32_t *pp = pp0 + j;
@@ -179,6 +189,7 @@ __device__ __forceinline__ void batch_pose_pass(const int N, const int32_t *pp0,
     for (int t = pp[0] + lane; t < e1; t += 64) {
       const int so = po[t];
       const int4 r = ob[so];
+      if (sel && !sel[r.z]) continue;
       const double2 u = uvp[so];
       const double *cam = cams + r.x * 16;
       const double *Xp = X + (size_t)r.z * 3;
@@ -215,9 +226,11 @@ __device__ __forceinline__ void batch_pose_pass(const int N, const int32_t *pp0,
 
 // damp and invert (reference :846-856): C_i (1 + lambda) -> Cinv_i, Cinv_i b_i
 __device__ __forceinline__ void batch_damp_invert(const int M, const double lp1, const double *C6, const double *b3,
-                                                  double *Ci6, double *Cib3) {
+                                                  double *Ci6, double *Cib3, const int32_t *opt_lm = nullptr,
+                                                  const uint8_t *sel = nullptr) {
   const int tid = threadIdx.x;
   for (int i = tid; i < M; i += kBatchBlock) {
+    if (sel && !sel[opt_lm[i]]) continue;
     double cd[6], ci[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) cd[k] = C6[(size_t)i * 6 + k];
@@ -245,12 +258,16 @@ __device__ __forceinline__ void batch_reset_image(double *Lb, const int n6) {
 }
 
 // Schur complement (reference :858-888): lower triangle of S and the reduced right-hand side
-// into the LDS image; one thread per half 6x6 block, the landmarks in ascending order
-template <int nbt, int LS>
+// into the LDS image; one thread per half 6x6 block, the landmarks in ascending order.
+// PERM: col0 gives the first column of every optimisable pose in a permuted image (else pose
+// j owns columns 6 j ..); a block whose poses j >= k land above the diagonal there is stored
+// transposed, so that the lower triangle is complete either way
+template <int nbt, int LS, bool PERM = false>
 __device__ __forceinline__ void batch_schur(const int N, const int M, const double lp1, const int32_t *tab,
                                             const double *Ci6, const double *Cib3, const double *Wg,
                                             const uint8_t *blk_j, const uint8_t *blk_k, const double *A,
-                                            const double *a, double *Lb) {
+                                            const double *a, double *Lb, const int32_t *opt_lm = nullptr,
+                                            const uint8_t *sel = nullptr, const uint8_t *col0 = nullptr) {
   const int tid = threadIdx.x, n6 = 6 * N;
   const int n_task = N * (N + 1);  // (block, half): rows 3h .. 3h+2 of block (j, k), j >= k
   for (int task = tid; task < n_task; task += kBatchBlock) {
@@ -260,6 +277,7 @@ __device__ __forceinline__ void batch_schur(const int N, const int M, const doub
 #pragma unroll
     for (int e = 0; e < 18; ++e) acc[e] = 0.0;
     for (int i = 0; i < M; ++i) {
+      if (sel && !sel[opt_lm[i]]) continue;
       const int pj = tab[(size_t)i * N + j];
       const int pk = tab[(size_t)i * N + k];
       if (pj < 0 || pk < 0) continue;
@@ -284,27 +302,28 @@ __device__ __forceinline__ void batch_schur(const int N, const int M, const doub
     for (int r = 0; r < 3; ++r)
 #pragma unroll
       for (int c = 0; c < 6; ++c) {
-        const int row = 6 * j + h3 + r, col = 6 * k + c;
-        if (row < col) continue;
+        const int row = (PERM ? col0[j] : 6 * j) + h3 + r, col = (PERM ? col0[k] : 6 * k) + c;
+        if (row < col && (!PERM || j == k)) continue;
         double av = 0.0;
         if (j == k) {
           av = A[j * 36 + (h3 + r) * 6 + c];
           if (h3 + r == c) av *= lp1;  // damped A_j (reference :833-844)
         }
-        Lb[col * LS + row] = av - acc[r * 6 + c];
+        Lb[PERM && row < col ? row * LS + col : col * LS + row] = av - acc[r * 6 + c];
       }
   }
   for (int t = tid; t < n6; t += kBatchBlock) {  // rhs_j = a_j - sum_i B_ji (Cinv_i b_i)
     const int j = t / 6, r = t - 6 * j;
     double acc = 0.0;
     for (int i = 0; i < M; ++i) {
+      if (sel && !sel[opt_lm[i]]) continue;
       const int pj = tab[(size_t)i * N + j];
       if (pj < 0) continue;
       const double *Wj = Wg + (size_t)pj * 18 + r * 3;
       const double *cb = Cib3 + (size_t)i * 3;
       acc += Wj[0] * cb[0] + Wj[1] * cb[1] + Wj[2] * cb[2];
     }
-    Lb[t * LS + nbt] = a[t] - acc;
+    Lb[(PERM ? col0[j] + r : t) * LS + nbt] = a[t] - acc;
   }
 }
 
@@ -691,6 +710,163 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch_cov(BatchDev d, BatchC
   if (tid == 0) res->status = 0;
 }
 
+// ---- marginalisation prior of every problem (ba_batch_marginalize) ------------------------
+// The LDS of the marginalisation kernel: BatchCovLds without the solution vector, plus the
+// marking and the column map.  NPt = 7 (112 columns) holds the widest image a problem within
+// the limits can ask for: 16 ceil(6 m / 16) + 6 (N - m) <= 110 for N <= 16.
+template <int NPt>
+struct BatchMargLds {
+  static constexpr int nbt = 16 * NPt;
+  static constexpr int LS = nbt + 16 + 1;
+  double Lb[nbt * LS];
+  double Eb[NPt][16 * kTailES];
+  double cams[kCamLds * 16];
+  double P[kBatchMaxPoses * 12];
+  double A[kBatchMaxOpt * 36];
+  double a[kBatchMaxOpt * 6];
+  int32_t jopt[kBatchMaxPoses];
+  int32_t n_sel;
+  uint8_t marg[kBatchMaxPoses];
+  uint8_t col0[kBatchMaxOpt];
+  uint8_t blk_j[kBatchMaxBlk], blk_k[kBatchMaxBlk];
+};
+
+struct BatchMargProb {  // the host's plan of one problem for this marking
+  int64_t H_off, b_off;  // element offsets of its outputs
+  int32_t K, m;          // kept poses; marked optimisable poses
+};
+
+struct BatchMargOut {
+  const BatchMargProb *mp;
+  const uint8_t *marg;  // per pose of the batch: marked
+  double *H, *bvec;     // zeroed before the launch
+  uint8_t *sel;         // per point of the batch: in L (zeroed before the launch)
+  ba_batch_marg_result *res;
+  double huber;
+};
+
+// One workgroup per problem.  L = the optimisable landmarks a marked pose observes, decided
+// by the thread that owns the landmark; the linearisation of k_ba_batch_cov restricted to L
+// (lambda = 0); the Schur complement into a permuted image: the m marked optimisable poses
+// first, padded with unit-diagonal columns to T = ceil(6 m / 16) tiles, the K kept poses from
+// column 16 T on in ascending order.  chol_lds_partial eliminates the T tiles; what it leaves
+// from column 16 T on is the prior: H is read from the lower triangle and mirrored, b from
+// the rhs row.  The outputs were zeroed by the host: a problem that is not processed
+// (status 1 or 2) leaves them zero.
+template <int NPt>
+__global__ __launch_bounds__(kBatchBlock) void k_ba_batch_marg(BatchDev d, BatchMargOut o) {
+  using LDS = BatchMargLds<NPt>;
+  constexpr int nbt = LDS::nbt, LS = LDS::LS;
+  __shared__ LDS s;
+  const int tid = threadIdx.x;
+  const BatchProb pr = d.prob[blockIdx.x];
+  const BatchMargProb mp = o.mp[blockIdx.x];
+  ba_batch_marg_result *res = o.res + blockIdx.x;
+  if (tid == 0) {
+    res->dropped_pivots = 0;
+    res->n_kept = mp.K;
+    res->n_marg_pose = mp.m;
+    res->n_marg_pt = 0;
+  }
+  if (pr.status != 0) {
+    if (tid == 0) res->status = pr.status;
+    return;
+  }
+  const int N = pr.N, M = pr.M, K = mp.K, K6 = 6 * K;
+  const int T = (6 * mp.m + 15) >> 4;
+  const double *Pg = d.poses + pr.pose0 * 12;
+  const double *X = d.pts[0] + pr.pt0 * 3;
+  // ---- stage the problem; refuse non-finite parameters -------------------------------
+  int bad_val = 0;
+  for (int k = tid; k < pr.n_cam * 16; k += kBatchBlock) s.cams[k] = d.cams[pr.cam0 * 16 + k];
+  for (int k = tid; k < pr.n_pose * 12; k += kBatchBlock) {
+    const double v = Pg[k];
+    s.P[k] = v;
+    bad_val |= !isfinite(v);
+  }
+  for (int k = tid; k < pr.n_pose; k += kBatchBlock) {
+    s.jopt[k] = d.jopt[pr.pose0 + k];
+    s.marg[k] = o.marg[pr.pose0 + k];
+  }
+  for (int k = tid; k < pr.n_pt * 3; k += kBatchBlock) bad_val |= !isfinite(X[k]);
+  for (int k = tid; k < (int)(sizeof(s.Eb) / sizeof(double)); k += kBatchBlock) (&s.Eb[0][0])[k] = 0.0;
+  if (tid == 0) s.n_sel = 0;
+  if (__syncthreads_or(bad_val)) {
+    if (tid == 0) res->status = 1;
+    return;
+  }
+  if (tid == 0) {
+    int b = 0;
+    for (int j = 0; j < N; ++j)
+      for (int k = 0; k <= j; ++k, ++b) {
+        s.blk_j[b] = (uint8_t)j;
+        s.blk_k[b] = (uint8_t)k;
+      }
+    int cm = 0, ck = 16 * T;  // the column map: marked poses from 0, kept poses from 16 T
+    for (int p = 0; p < pr.n_pose; ++p) {
+      const int j = s.jopt[p];
+      if (j < 0) continue;
+      if (s.marg[p]) {
+        s.col0[j] = (uint8_t)cm;
+        cm += 6;
+      } else {
+        s.col0[j] = (uint8_t)ck;
+        ck += 6;
+      }
+    }
+  }
+  const int4 *ob = d.lobs + pr.obs0;
+  const double2 *uvp = d.luv + pr.obs0;
+  const int32_t *lm_ptr = d.lm_ptr + pr.pt0 + blockIdx.x;
+  const int32_t *opt_lm = d.opt_lm + pr.m0;
+  uint8_t *sel = o.sel + pr.pt0;
+  // ---- L: an optimisable landmark with an observation from a marked pose -----------------
+  int n_sel = 0;
+  for (int i = tid; i < M; i += kBatchBlock) {
+    const int q = opt_lm[i];
+    const int o1 = lm_ptr[q + 1];
+    int in = 0;
+    for (int t = lm_ptr[q]; t < o1; ++t) in |= s.marg[ob[t].y];
+    if (in) {
+      sel[q] = 1;
+      ++n_sel;
+    }
+  }
+  if (n_sel) atomicAdd(&s.n_sel, n_sel);
+  __syncthreads();
+  if (tid == 0) res->n_marg_pt = s.n_sel;
+  if (K == 0) {  // nothing is kept: no output
+    if (tid == 0) res->status = 0;
+    return;
+  }
+  double *C6 = d.C6 + pr.m0 * 6, *b3 = d.b3 + pr.m0 * 3;
+  double *Ci6 = d.Cinv6 + pr.m0 * 6, *Cib3 = d.Cinvb3 + pr.m0 * 3;
+  double *Wg = d.W18 + pr.pair0 * 18;
+  // ---- linearise over L, lambda = 0; Schur complement; partial factorisation -------------
+  batch_landmark_pass(M, opt_lm, lm_ptr, ob, uvp, s.cams, s.P, X, o.huber, C6, b3, Wg, sel);
+  batch_pose_pass(N, d.pobs_ptr + pr.pptr0, d.pobs + pr.pobs0, ob, uvp, s.cams, s.P, X, o.huber, s.A, s.a, sel);
+  __syncthreads();
+  batch_damp_invert(M, 1.0, C6, b3, Ci6, Cib3, opt_lm, sel);
+  for (int e = tid; e < nbt * LS; e += kBatchBlock) {  // zero; unit diagonal on the padding of the marked tiles
+    const int c = e / LS, r = e - c * LS;
+    s.Lb[e] = (r == c && c >= 6 * mp.m && c < 16 * T) ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  batch_schur<nbt, LS, true>(N, M, 1.0, d.tab + pr.tab0, Ci6, Cib3, Wg, s.blk_j, s.blk_k, s.A, s.a, s.Lb, opt_lm,
+                             sel, s.col0);
+  __syncthreads();
+  chol_lds_partial<NPt, LS>(s.Lb, s.Eb, T, &res->dropped_pivots);  // ends with a barrier
+  // ---- the prior: one triangle, mirrored -------------------------------------------------
+  double *H = o.H + mp.H_off;
+  for (int e = tid; e < K6 * K6; e += kBatchBlock) {
+    const int r = e / K6, c = e - r * K6;
+    const int lo = r < c ? r : c, hi = r < c ? c : r;
+    H[e] = s.Lb[(16 * T + lo) * LS + 16 * T + hi];
+  }
+  for (int t = tid; t < K6; t += kBatchBlock) o.bvec[mp.b_off + t] = s.Lb[(16 * T + t) * LS + nbt];
+  if (tid == 0) res->status = 0;
+}
+
 }  // namespace
 }  // namespace ba
 
@@ -714,6 +890,9 @@ struct ba_batch {
   size_t rows_cap = 0;  // records
   char *cov = nullptr;  // outputs of ba_batch_covariance (allocated by its first call)
   size_t cov_bytes = 0, cov_pt_off = 0, cov_res_off = 0;
+  std::vector<int32_t> jopt;  // per pose of the batch: optimisable index or -1 (host copy)
+  char *marg = nullptr;       // inputs and outputs of ba_batch_marginalize (grown on demand)
+  size_t marg_bytes = 0;
 };
 
 namespace {
@@ -816,6 +995,25 @@ int batch_check_offsets(const char *name, int B, const int64_t *off, bool strict
       return fail(std::string("ba_batch_create: ") + name + " must " + (strict ? "increase" : "not decrease") +
                   " (problem " + std::to_string(b) + ")");
   return 0;
+}
+
+// the host's plan of every problem for one marking, and the 16-column panels of the widest
+// image among the problems that will be processed
+int marg_plan_batch(const ba_batch *b, const uint8_t *marg_pose, std::vector<ba::BatchMargProb> &mp) {
+  mp.resize(b->B);
+  int64_t ho = 0, bo = 0;
+  int tiles = 1;
+  for (int p = 0; p < b->B; ++p) {
+    const ba::BatchProb &P = b->prob[p];
+    int K = 0, m = 0;
+    for (int q = 0; q < P.n_pose; ++q)
+      if (b->jopt[P.pose0 + q] >= 0) (marg_pose[P.pose0 + q] ? m : K)++;
+    mp[p] = ba::BatchMargProb{ho, bo, K, m};
+    ho += (int64_t)36 * K * K;
+    bo += (int64_t)6 * K;
+    if (P.status == 0) tiles = std::max(tiles, (16 * ((6 * m + 15) / 16) + 6 * K + 15) / 16);
+  }
+  return tiles;
 }
 
 size_t lds_bytes_of(int npt) {
@@ -942,6 +1140,7 @@ int ba_batch_create(ba_batch **out, ba_handle *h, int B, const int32_t *cam_off,
   }
   bt->n_pair = (int64_t)pair_j.size();
   bt->n_m = (int64_t)opt_lm.size();
+  bt->jopt = jopt;
   bt->npt_class = bt->max_N <= 5 ? 2 : bt->max_N <= 10 ? 4 : 6;
 
   // one host image, one upload: structure | parameters; the scratch follows it on the device
@@ -1003,6 +1202,7 @@ void ba_batch_destroy(ba_batch *b) {
   if (b->dev) (void)hipFree(b->dev);
   if (b->rows) (void)hipFree(b->rows);
   if (b->cov) (void)hipFree(b->cov);
+  if (b->marg) (void)hipFree(b->marg);
   delete b;
 }
 
@@ -1097,6 +1297,101 @@ int ba_batch_solve(ba_batch *b, const ba_options *opt, ba_iter_info *rows, int c
   HIP_TRY(hipMemcpyAsync(res, d.res, (size_t)B * sizeof(ba_batch_result), hipMemcpyDeviceToHost, s));
   if (dcap > 0)
     HIP_TRY(hipMemcpyAsync(rows, b->rows, n_rows * sizeof(ba_iter_info), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ba_batch_marg_plan_problem(int n_pose, const uint8_t *pose_fixed, const uint8_t *marg_pose, int n_pt,
+                               const uint8_t *pt_fixed, int64_t n_obs, const int32_t *obs_pose, const int32_t *obs_pt,
+                               int32_t *kept_pose, uint8_t *marg_pt) {
+  if (n_pose < 0 || n_pt < 0 || n_obs < 0 || n_obs > INT32_MAX) return fail("ba_batch_marg_plan_problem: bad sizes");
+  if (n_pose > 0 && !marg_pose) return fail("ba_batch_marg_plan_problem: null marg_pose");
+  if (n_obs > 0 && (!obs_pose || !obs_pt)) return fail("ba_batch_marg_plan_problem: null observations");
+  for (int64_t k = 0; k < n_obs; ++k)
+    if (obs_pose[k] < 0 || obs_pose[k] >= n_pose || obs_pt[k] < 0 || obs_pt[k] >= n_pt)
+      return fail("ba_batch_marg_plan_problem: observation " + std::to_string(k) + " out of range");
+  int K = 0;
+  for (int p = 0; p < n_pose; ++p)
+    if (!(pose_fixed && pose_fixed[p]) && !marg_pose[p]) {
+      if (kept_pose) kept_pose[K] = p;
+      ++K;
+    }
+  if (marg_pt) {
+    for (int q = 0; q < n_pt; ++q) marg_pt[q] = 0;
+    for (int64_t k = 0; k < n_obs; ++k)
+      if (marg_pose[obs_pose[k]] && !(pt_fixed && pt_fixed[obs_pt[k]])) marg_pt[obs_pt[k]] = 1;
+  }
+  return K;
+}
+
+int ba_batch_marg_layout(ba_batch *b, const uint8_t *marg_pose, int64_t *H_off, int64_t *b_off) {
+  if (!b) return fail("ba_batch_marg_layout: null batch");
+  if (!marg_pose && b->n_pose > 0) return fail("ba_batch_marg_layout: null marg_pose");
+  if (!H_off || !b_off) return fail("ba_batch_marg_layout: null offsets");
+  std::vector<ba::BatchMargProb> mp;
+  marg_plan_batch(b, marg_pose, mp);
+  for (int p = 0; p < b->B; ++p) {
+    H_off[p] = mp[p].H_off;
+    b_off[p] = mp[p].b_off;
+  }
+  H_off[b->B] = mp.back().H_off + (int64_t)36 * mp.back().K * mp.back().K;
+  b_off[b->B] = mp.back().b_off + (int64_t)6 * mp.back().K;
+  return 0;
+}
+
+int ba_batch_marginalize(ba_batch *b, double huber, const uint8_t *marg_pose, double *H, double *bvec,
+                         uint8_t *marg_pt, ba_batch_marg_result *res) {
+  if (!b) return fail("ba_batch_marginalize: null batch");
+  if (!marg_pose && b->n_pose > 0) return fail("ba_batch_marginalize: null marg_pose");
+  if (!res) return fail("ba_batch_marginalize: null result array");
+  const int B = b->B;
+  std::vector<ba::BatchMargProb> mp;
+  const int tiles = marg_plan_batch(b, marg_pose, mp);
+  const size_t nH = (size_t)(mp.back().H_off + (int64_t)36 * mp.back().K * mp.back().K);
+  const size_t nb = (size_t)(mp.back().b_off + (int64_t)6 * mp.back().K);
+  if (nH > 0 && !H) return fail("ba_batch_marginalize: null H");
+  if (nb > 0 && !bvec) return fail("ba_batch_marginalize: null bvec");
+  HIP_TRY(hipSetDevice(b->h->device));
+  hipStream_t s = b->h->stream;
+  // one buffer: H | b | marg_pt (zeroed) | marg_pose | plan (uploaded) | results
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_b = al(nH * sizeof(double)), o_sel = o_b + al(nb * sizeof(double));
+  const size_t o_in = o_sel + al((size_t)b->n_pt), o_mp = al((size_t)b->n_pose);
+  const size_t in_bytes = o_mp + al((size_t)B * sizeof(ba::BatchMargProb));
+  const size_t o_res = o_in + in_bytes, bytes = o_res + al((size_t)B * sizeof(ba_batch_marg_result));
+  if (bytes > b->marg_bytes) {
+    if (b->marg) (void)hipFree(b->marg);
+    b->marg = nullptr;
+    b->marg_bytes = 0;
+    HIP_TRY(hipMalloc((void **)&b->marg, bytes));
+    b->marg_bytes = bytes;
+  }
+  std::vector<char> in(in_bytes, 0);
+  if (b->n_pose > 0) std::memcpy(in.data(), marg_pose, (size_t)b->n_pose);
+  std::memcpy(in.data() + o_mp, mp.data(), (size_t)B * sizeof(ba::BatchMargProb));
+  ba::BatchMargOut o;
+  o.H = (double *)b->marg;
+  o.bvec = (double *)(b->marg + o_b);
+  o.sel = (uint8_t *)(b->marg + o_sel);
+  o.marg = (const uint8_t *)(b->marg + o_in);
+  o.mp = (const ba::BatchMargProb *)(b->marg + o_in + o_mp);
+  o.res = (ba_batch_marg_result *)(b->marg + o_res);
+  o.huber = huber;
+  HIP_TRY(hipMemsetAsync(b->marg, 0, o_in, s));  // unprocessed problems and unseen poses: exact zeros
+  HIP_TRY(hipMemcpyAsync(b->marg + o_in, in.data(), in_bytes, hipMemcpyHostToDevice, s));
+  if (tiles <= 2)
+    hipLaunchKernelGGL(ba::k_ba_batch_marg<2>, dim3(B), dim3(ba::kBatchBlock), 0, s, b->d, o);
+  else if (tiles <= 4)
+    hipLaunchKernelGGL(ba::k_ba_batch_marg<4>, dim3(B), dim3(ba::kBatchBlock), 0, s, b->d, o);
+  else if (tiles <= 6)
+    hipLaunchKernelGGL(ba::k_ba_batch_marg<6>, dim3(B), dim3(ba::kBatchBlock), 0, s, b->d, o);
+  else
+    hipLaunchKernelGGL(ba::k_ba_batch_marg<7>, dim3(B), dim3(ba::kBatchBlock), 0, s, b->d, o);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(res, o.res, (size_t)B * sizeof(ba_batch_marg_result), hipMemcpyDeviceToHost, s));
+  if (nH > 0) HIP_TRY(hipMemcpyAsync(H, o.H, nH * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (nb > 0) HIP_TRY(hipMemcpyAsync(bvec, o.bvec, nb * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (marg_pt && b->n_pt > 0) HIP_TRY(hipMemcpyAsync(marg_pt, o.sel, (size_t)b->n_pt, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return 0;
 }

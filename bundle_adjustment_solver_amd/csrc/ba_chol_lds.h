@@ -196,5 +196,100 @@ __device__ __forceinline__ void chol_lds_inverse(double *Lb, double (*Eb)[16 * k
   __syncthreads();
 }
 
+// Partial factorisation of the image of chol_lds_factor_solve: eliminate the first T
+// 16-column panels (T <= NPt, uniform over the workgroup) and leave the Schur complement of
+// the rest in place.
+//   panels p < T    steps (1)-(3) of chol_lds_factor_solve, the rhs row tile included;
+//   panels p >= T   only the left-looking update (1) over the eliminated columns kc < 16 T,
+//                   tiles p .. NPt.  These panels read columns below 16 T only and write
+//                   their own, so they need no barrier between them: their tiles are dealt
+//                   to the four waves as one list.
+// Afterwards the lower triangle from column 16 T on holds S_kk - S_km S_mm^-1 S_mk (the
+// diagonal tiles are full 16x16 MFMA results of a lower-only image: read row >= column
+// only), and row nbt of those columns r_k - S_km S_mm^-1 r_m.  Every tile is one MFMA chain
+// over kc ascending from 0, whose length depends on T and not on NPt, and trailing padding
+// tiles add nothing to another tile: the same bits at any NPt.  Pivots as in
+// chol_lds_factor_solve, counted for the eliminated panels only.  Eb (zeroed by the caller)
+// receives E_pp for p < T.  Starts after a barrier of the caller and ends with one.
+template <int NPt, int LS>
+__device__ __forceinline__ void chol_lds_partial(double *Lb, double (*Eb)[16 * kTailES], const int T, int *bad) {
+  typedef double v4f64 __attribute__((ext_vector_type(4)));
+  constexpr int ES = kTailES;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+  for (int p = 0; p < T; ++p) {
+    if (p > 0) {
+      for (int ti = p + wv; ti <= NPt; ti += 4) {
+        v4f64 acc;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[g] = Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr];
+        for (int kc = 0; kc < 16 * p; kc += 4) {
+          const double a = -Lb[(kc + lk) * LS + 16 * p + lr];
+          const double b = Lb[(kc + lk) * LS + 16 * ti + lr];
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr] = acc[g];
+      }
+      __syncthreads();
+    }
+    if (wv == 0) {
+      const int r = lr, q = lk;
+      double g[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = 4 * j + q;
+        g[j] = (r >= c) ? Lb[(16 * p + c) * LS + 16 * p + r] : 0.0;
+      }
+      double dinv;
+      count_bad_pivots(bad, tile16::tile16_potrf_inv2(g, lane, dinv), lane);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = 4 * j + q;
+        if (r >= c) Lb[(16 * p + c) * LS + 16 * p + r] = g[j];
+        if (r < c) Eb[p][r * ES + c] = g[j];
+        if (r == c) Eb[p][r * ES + c] = dinv;
+      }
+    }
+    __syncthreads();
+    for (int ti = p + 1 + wv; ti <= NPt; ti += 4) {
+      v4f64 acc = (v4f64){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const double a = Eb[p][(lk + 4 * g) * ES + lr];
+        const double b = Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+      }
+      // all reads of this tile precede the writes within the wave
+#pragma unroll
+      for (int g = 0; g < 4; ++g) Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr] = acc[g];
+    }
+    __syncthreads();
+  }
+  if (T > 0) {
+    // trailing update: tile (ti, p), T <= p <= ti <= NPt with p < NPt, row-major task list
+    const int R = NPt - T, n_task = R * (R + 1) / 2 + R;
+    for (int task = wv; task < n_task; task += 4) {
+      int pr = 0, rem = task;
+      while (rem >= R + 1 - pr) {
+        rem -= R + 1 - pr;
+        ++pr;
+      }
+      const int p = T + pr, ti = p + rem;
+      v4f64 acc;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g] = Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr];
+      for (int kc = 0; kc < 16 * T; kc += 4) {
+        const double a = -Lb[(kc + lk) * LS + 16 * p + lr];
+        const double b = Lb[(kc + lk) * LS + 16 * ti + lr];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) Lb[(16 * p + lk + 4 * g) * LS + 16 * ti + lr] = acc[g];
+    }
+  }
+  __syncthreads();
+}
+
 }  // namespace ba
 #endif  // BA_CHOL_LDS_H_

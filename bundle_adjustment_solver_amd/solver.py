@@ -226,6 +226,22 @@ def covariance_to_user_units(cov_pose, cov_pt, sigma_px):
     return (s2 * SCALER * SCALER) * (d[None, :, None] * cov_pose * d[None, None, :]), s2 * cov_pt
 
 
+def marginal_to_user_units(H, b, sigma_px):
+    """A prior of BaBatch.marginalize (scaled units, unit pixel noise) -> information
+    matrix and vector in the caller's units for an isotropic pixel noise of sigma_px
+    (numpy only): the inverse of covariance_to_user_units.  With xi_user = D xi_scaled
+    per pose, D = diag(100 I3, I3), and a noise of 0.01 sigma_px in scaled pixels,
+        H_u = D^-1 H D^-1 / (1e-4 sigma_px^2),    b_u = D^-1 b / (1e-4 sigma_px^2),
+    so that H_u delta_u = b_u is the same step and 1/2 d^T H_u d - b_u^T d the energy
+    in units of that noise."""
+    H = np.asarray(H, np.float64)
+    b = np.asarray(b, np.float64)
+    K = b.shape[0] // 6
+    di = np.tile(np.r_[np.full(3, SCALER), np.ones(3)], K)
+    w = 1.0 / (float(sigma_px) ** 2 * SCALER * SCALER)
+    return w * (di[:, None] * H.reshape(6 * K, 6 * K) * di[None, :]), w * (di * b)
+
+
 class BaProblem:
     """Thin numpy wrapper over one ba_handle, in the solver's SCALED units.
 
@@ -1057,6 +1073,7 @@ class BaBatch:
                  obs_cam=cat("obs_cam", np.int32, ()), obs_pose=cat("obs_pose", np.int32, ()),
                  obs_pt=cat("obs_pt", np.int32, ()), obs_uv=cat("obs_uv", np.float64, (2,)))
         self.n_pose, self.n_pt = a["pose_T"].shape[0], a["pt_X"].shape[0]
+        self.pose_fixed = a["pose_fixed"]
         b = C.c_void_p()
         check(self.lib.ba_batch_create(
             C.byref(b), self._owner.h, self.B, _ip(self.cam_off), _ip(self.pose_off),
@@ -1103,6 +1120,48 @@ class BaBatch:
                                            _dp(cq) if points else None, res),
               "ba_batch_covariance")
         return cp, cq, [res[p] for p in range(self.B)]
+
+    def _marking(self, marg_pose):
+        m = np.ascontiguousarray(np.asarray(marg_pose).reshape(-1) != 0, np.uint8)
+        if m.shape[0] != self.n_pose:
+            raise ValueError("marg_pose: one byte per pose of the batch (%d)" % self.n_pose)
+        return m
+
+    def marg_layout(self, marg_pose):
+        """-> (H_off, b_off): element offsets (B + 1 each) of every problem's prior
+        in the outputs of ba_batch_marginalize for this marking (host only)."""
+        m = self._marking(marg_pose)
+        Ho, bo = np.zeros(self.B + 1, np.int64), np.zeros(self.B + 1, np.int64)
+        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        check(self.lib.ba_batch_marg_layout(self.b, _up(m), i64(Ho), i64(bo)),
+              "ba_batch_marg_layout")
+        return Ho, bo
+
+    def marginalize(self, marg_pose, huber):
+        """-> (H_list, b_list, kept_list, results): the marginalisation prior of every
+        problem at the values the object holds, one launch (ba_batch_marginalize;
+        scaled units).  marg_pose: one byte per pose of the batch, concatenated user
+        order.  H_list[p] (6K, 6K) and b_list[p] (6K,) are views of the two output
+        arrays, kept_list[p] the kept poses (problem-local user indices, ascending),
+        results[p] its BaBatchMargResult.  self.marg_pt holds the landmark set L of
+        the call (one byte per point of the batch)."""
+        m = self._marking(marg_pose)
+        Ho, bo = self.marg_layout(m)
+        H = np.zeros(int(Ho[-1]))
+        bv = np.zeros(int(bo[-1]))
+        self.marg_pt = np.zeros(self.n_pt, np.uint8)
+        res = (_lib.BaBatchMargResult * self.B)()
+        check(self.lib.ba_batch_marginalize(
+            self.b, float(huber), _up(m), _dp(H) if H.size else None,
+            _dp(bv) if bv.size else None, _up(self.marg_pt), res), "ba_batch_marginalize")
+        Hl, bl, kl = [], [], []
+        for p in range(self.B):
+            K6 = int(bo[p + 1] - bo[p])
+            Hl.append(H[Ho[p]:Ho[p + 1]].reshape(K6, K6))
+            bl.append(bv[bo[p]:bo[p + 1]])
+            sl = slice(self.pose_off[p], self.pose_off[p + 1])
+            kl.append(np.flatnonzero((self.pose_fixed[sl] == 0) & (m[sl] == 0)).astype(np.int32))
+        return Hl, bl, kl, [res[p] for p in range(self.B)]
 
     def cov_poses_of(self, p, cov_pose):
         return cov_pose[self.pose_off[p]:self.pose_off[p + 1]]
@@ -1692,6 +1751,53 @@ class FullBundleAdjustmentSolver:
                 cq_k = batch.cov_points_of(k, cq) if points else np.zeros((0, 3, 3))
                 up, uq = covariance_to_user_units(cp_k, cq_k, sigma_pixel)
                 out.append((up, uq if points else None, res[k]))
+        finally:
+            batch.close()
+        return out
+
+    @staticmethod
+    def MarginalizeBatch(solvers, marg_poses, sigma_pixel=1.0, options=None):
+        """(new) Marginalisation priors of several solver objects in ONE launch
+        (ba_batch_marginalize; see BaBatch for the limits), at the CURRENT registered
+        values.  marg_poses[k]: the pose objects (or integer handles) of solver k that
+        leave its window; the landmarks they observe leave with them.  Returns per
+        solver (H (6K, 6K), b (6K,), kept pose handles, marginalised point handles,
+        BaBatchMargResult): the Gaussian 1/2 d^T H d - b^T d left on the K kept
+        (optimisable, unmarked) poses in registration order, d the stacked tangents
+        xi = [v; omega] of the WORLD-TO-BODY poses as in ComputeCovariance, in the
+        caller's units for an isotropic pixel noise of `sigma_pixel`
+        (marginal_to_user_units).  H is singular where the gauge is free.  A result
+        whose status is not 0 is zero; dropped_pivots > 0 means the marked block
+        was singular and the prior meaningless."""
+        solvers = list(solvers)
+        if not solvers:
+            return []
+        if len(marg_poses) != len(solvers):
+            raise ValueError("MarginalizeBatch: one list of poses per solver")
+        if any(sv._shard[1] > 1 or sv._allreduce is not None for sv in solvers):
+            raise RuntimeError("MarginalizeBatch: a solver with a shard or an "
+                               "all-reduce configured cannot be part of a batch")
+        probs, marks = [], []
+        for sv, poses in zip(solvers, marg_poses):
+            intr, camT, T_jw, X, pf, qf, ocam, opose, opt, ouv = sv._host_arrays()
+            probs.append(dict(cam_intr=intr, cam_T=camT, pose_T=T_jw, pose_fixed=pf, pt_X=X,
+                              pt_fixed=qf, obs_cam=ocam, obs_pose=opose, obs_pt=opt, obs_uv=ouv))
+            mk = np.zeros(len(pf), np.uint8)
+            for pose in poses:
+                h = sv._pose_handle(pose)
+                if h is None:
+                    raise RuntimeError("There is no pointer in the BA pose pool.")
+                mk[h] = 1
+            marks.append(mk)
+        huber = (options or Options()).outlier_handle.threshold_huber_loss
+        batch = BaBatch(probs, solvers[0].device)
+        try:
+            Hl, bl, kl, res = batch.marginalize(np.concatenate(marks), huber)
+            out = []
+            for k in range(len(solvers)):
+                Hu, bu = marginal_to_user_units(Hl[k], bl[k], sigma_pixel)
+                mq = np.flatnonzero(batch.points_of(k, batch.marg_pt))
+                out.append((Hu, bu, [int(h) for h in kl[k]], [int(h) for h in mq], res[k]))
         finally:
             batch.close()
         return out

@@ -125,6 +125,34 @@ class FullBundleAdjustmentSolver {
   static bool ComputeCovarianceBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, double sigma_pixel,
                                      std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
                                      std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points);
+  // (new) The marginalisation prior one solver's window leaves on its kept poses: the
+  // Gaussian 1/2 d^T H d - b^T d, d the stacked tangents xi = [v; omega] of the kept poses'
+  // WORLD-TO-BODY transforms (the convention of ComputeCovariance), so that H d = b is their
+  // Gauss-Newton step.  H is row-major dim x dim, dim = 6 * kept_poses.size(), symmetric to
+  // the bit and in general singular (the gauge, poses that share no landmark with a marked one).
+  struct MarginalPrior {
+    int dim{0};
+    std::vector<double> H, b;
+    std::vector<_BA_Pose *> kept_poses;           // optimisable, unmarked; registration order
+    std::vector<_BA_Point *> marginalized_points;  // the landmarks that leave with the marked poses
+    int status{0}, dropped_pivots{0};              // ba_batch_marg_result of include/ba_hip.h
+    double operator()(int r, int c) const { return H[static_cast<size_t>(r) * dim + c]; }
+  };
+  // (new) The marginalisation priors of several solver objects in ONE launch
+  // (ba_batch_marginalize of include/ba_hip.h; the limits of SolveBatch per problem), at the
+  // solvers' CURRENT values: marg_poses[b] are the registered poses of solver b that leave
+  // its window (fixed ones allowed: they own no columns but select their landmarks), every
+  // optimisable landmark one of them observes leaves with them, and priors[b] is what the
+  // observations of those landmarks leave on the other optimisable poses.  Units: the
+  // caller's, for an isotropic pixel noise of sigma_pixel and the Huber weights of a default
+  // Options; with D = diag(100 I3, I3) per pose and the raw H_s, b_s of the scaled problem,
+  // H = D^-1 H_s D^-1 / (1e-4 sigma^2), b = D^-1 b_s / (1e-4 sigma^2): the inverse of the
+  // conversion of ComputeCovariance.  An unknown pointer throws std::runtime_error; sharded
+  // solvers are refused.  Returns true when every problem has status 0 and the elimination
+  // of its marked poses met no non-positive pivot.
+  static bool MarginalizeBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers,
+                               const std::vector<std::vector<_BA_Pose *>> &marg_poses, double sigma_pixel,
+                               std::vector<MarginalPrior> *priors);
   // the C-ABI handle behind the finalized problem (nullptr before FinalizeParameters):
   // for the readers of include/ba_hip.h; indices there are registration order
   ba_handle *GetHandle() const { return handle_; }
@@ -163,7 +191,7 @@ class FullBundleAdjustmentSolver {
   // valid[q] == 0 are skipped.  Shared by Run and SolveBatch.
   void WriteBack(const double *T_jw12, const double *X3, const uint8_t *valid);
   // the concatenated arrays of ba_batch_create for a list of solvers (registered values,
-  // not finalized state); shared by SolveBatch and ComputeCovarianceBatch
+  // not finalized state); shared by SolveBatch, ComputeCovarianceBatch and MarginalizeBatch
   struct BatchArrays {
     std::vector<int32_t> cam_off, pose_off, pt_off, oc, op, oq;
     std::vector<int64_t> obs_off;

@@ -89,6 +89,16 @@ class FullBundleAdjustmentSolverRefactor {
     for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
     return FullBundleAdjustmentSolver::ComputeCovarianceBatch(impls, sigma_pixel, cov_poses, cov_points);
   }
+  // (new) the marginalisation priors of several solvers in one launch, see
+  // FullBundleAdjustmentSolver::MarginalizeBatch
+  using MarginalPrior = FullBundleAdjustmentSolver::MarginalPrior;
+  static bool MarginalizeBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers,
+                               const std::vector<std::vector<Pose *>> &marg_poses, double sigma_pixel,
+                               std::vector<MarginalPrior> *priors) {
+    std::vector<FullBundleAdjustmentSolver *> impls;
+    for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
+    return FullBundleAdjustmentSolver::MarginalizeBatch(impls, marg_poses, sigma_pixel, priors);
+  }
   ba_handle *GetHandle() const { return impl_.GetHandle(); }
 
   std::string GetSolverStatistics() const;

@@ -594,5 +594,69 @@ bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
   return all_good;
 }
 
+bool FullBundleAdjustmentSolver::MarginalizeBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers,
+                                                  const std::vector<std::vector<_BA_Pose *>> &marg_poses,
+                                                  double sigma_pixel, std::vector<MarginalPrior> *priors) {
+  const int B = static_cast<int>(solvers.size());
+  if (priors == nullptr) throw std::runtime_error("MarginalizeBatch: null output");
+  priors->assign(static_cast<size_t>(B), MarginalPrior());
+  if (marg_poses.size() != solvers.size()) throw std::runtime_error("MarginalizeBatch: one list of poses per solver");
+  if (B == 0) return true;
+  BatchArrays a;
+  PackBatch(solvers, "MarginalizeBatch", false, &a);
+  std::vector<uint8_t> mark(a.pose_fixed.size(), 0), marg_pt(a.point_fixed.size(), 0);
+  for (int b = 0; b < B; ++b)
+    for (_BA_Pose *pose : marg_poses[b]) {
+      const auto it = solvers[b]->pose_index_.find(pose);
+      if (it == solvers[b]->pose_index_.end())
+        throw std::runtime_error("MarginalizeBatch: there is no pointer in the BA pose pool.");
+      mark[static_cast<size_t>(a.pose_off[b] + it->second)] = 1;
+    }
+  std::vector<int64_t> H_off(static_cast<size_t>(B) + 1), b_off(static_cast<size_t>(B) + 1);
+  std::vector<double> H, bv;
+  std::vector<ba_batch_marg_result> res(static_cast<size_t>(B));
+  const Options defaults;
+  ba_handle *h = nullptr;
+  ba_batch *batch = nullptr;
+  int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
+  if (rc == 0) rc = ba_batch_marg_layout(batch, mark.data(), H_off.data(), b_off.data());
+  if (rc == 0) {
+    H.resize(static_cast<size_t>(H_off[B]));
+    bv.resize(static_cast<size_t>(b_off[B]));
+    rc = ba_batch_marginalize(batch, static_cast<double>(defaults.outlier_handle.threshold_huber_loss), mark.data(),
+                              H.empty() ? nullptr : H.data(), bv.empty() ? nullptr : bv.data(), marg_pt.data(),
+                              res.data());
+  }
+  const std::string err = rc ? ba_last_error() : "";
+  ba_batch_destroy(batch);
+  ba_destroy(h);
+  if (rc) throw std::runtime_error("MarginalizeBatch failed: " + err);
+  // scaled units, unit pixel noise -> the caller's units: the inverse of ComputeCovariance's
+  bool all_good = true;
+  for (int b = 0; b < B; ++b) {
+    const FullBundleAdjustmentSolver *s = solvers[b];
+    MarginalPrior &out = (*priors)[b];
+    out.status = res[b].status;
+    out.dropped_pivots = res[b].dropped_pivots;
+    all_good = all_good && res[b].status == 0 && res[b].dropped_pivots == 0;
+    for (size_t p = 0; p < s->poses_.size(); ++p)
+      if (!a.pose_fixed[a.pose_off[b] + p] && !mark[a.pose_off[b] + p]) out.kept_poses.push_back(s->poses_[p]);
+    for (size_t q = 0; q < s->points_.size(); ++q)
+      if (marg_pt[a.pt_off[b] + q]) out.marginalized_points.push_back(s->points_[q]);
+    out.dim = static_cast<int>(b_off[b + 1] - b_off[b]);
+    const double w = 1.0 / (sigma_pixel * sigma_pixel * static_cast<double>(s->scaler_) * static_cast<double>(s->scaler_));
+    const auto di = [s](int r) { return r % 6 < 3 ? static_cast<double>(s->scaler_) : 1.0; };
+    out.H.resize(static_cast<size_t>(out.dim) * out.dim);
+    out.b.resize(static_cast<size_t>(out.dim));
+    for (int r = 0; r < out.dim; ++r) {
+      for (int c = 0; c < out.dim; ++c)
+        out.H[static_cast<size_t>(r) * out.dim + c] =
+            w * (di(r) * H[static_cast<size_t>(H_off[b]) + static_cast<size_t>(r) * out.dim + c] * di(c));
+      out.b[r] = w * (di(r) * bv[static_cast<size_t>(b_off[b]) + r]);
+    }
+  }
+  return all_good;
+}
+
 }  // namespace analytic_solver
 }  // namespace visual_navigation

@@ -667,6 +667,56 @@ typedef struct {
 } ba_batch_cov_result;
 int ba_batch_covariance(ba_batch *b, double huber, double *cov_pose36, double *cov_pt9,
                         ba_batch_cov_result *res);
+/* Marginalisation prior of EVERY problem of the batch at the values the object holds: the
+ * Gaussian left on the kept poses when the marked poses, and the landmarks they anchor,
+ * leave the window.  One launch and one synchronisation on the handle's stream.
+ *   marg_pose   one byte per pose of the batch, concatenated user order: non-zero = marked;
+ *   L           the optimisable landmarks with at least one observation from a marked pose
+ *               (a marked FIXED pose owns no columns but still selects its landmarks);
+ *   factors     every observation (any pose, any camera) of a landmark in L, nothing else;
+ *   kept set k  the optimisable, unmarked poses in ascending user order, K of them;
+ *   m           the marked optimisable poses.
+ * Linearised as ba_batch_covariance does (lambda = 0, the given Huber threshold, last-writer
+ * rule, the 3x3 inverse with its fallback, fixed poses feeding C_i and b_i only); with S' and
+ * r' the reduced camera system of those factors over the optimisable poses,
+ *   H = S'_kk - S'_km S'_mm^-1 S'_mk        b = r'_k - S'_km S'_mm^-1 r'_m,
+ * formed in LDS by a partial unpivoted Cholesky (fp64 MFMA) of the image with the marked
+ * columns first.  r' has the solver's sign (a_j = -sum Q^T w r): H delta = b is the
+ * Gauss-Newton step of the kept poses and the prior energy is 1/2 delta^T H delta - b^T delta,
+ * delta the stacked tangents xi = [v; omega] of T_jw <- exp(xi) T_jw at the held values,
+ * scaled units, unit pixel noise.
+ *   H      problem p: row-major (6 K_p)^2 at element sum_{q<p} 36 K_q^2, symmetric to the bit;
+ *   bvec   problem p: 6 K_p at element 6 sum_{q<p} K_q       (ba_batch_marg_layout gives both);
+ *   marg_pt  one byte per point of the batch (NULL: skipped): 1 = in L.
+ * The rows and columns of a kept pose that observes no landmark of L are exactly zero.  H is
+ * in general singular (without a fixed pose observing L it carries the gauge null space);
+ * that is not an error.  res[p]: status as ba_batch_cov_result (1 and 2: the problem's output
+ * is zero, n_marg_pt is 0, the other problems are unaffected); dropped_pivots = non-positive
+ * pivots met while eliminating the MARKED columns (> 0: S'_mm was singular, the prior is
+ * meaningless); n_kept = K; n_marg_pose = marked optimisable poses; n_marg_pt = |L|.  A problem
+ * with no marked pose gives H = 0, b = 0, status 0; one with every optimisable pose marked
+ * (K = 0) has no output, status 0.  Nothing a later call can see changes: poses, points, the
+ * bits of a following ba_batch_solve or ba_batch_covariance; the per-landmark scratch is
+ * overwritten.  No floating-point atomics, fixed summation order per problem: the same bits
+ * run to run, alone and at any position of any batch, at any image width (32, 64, 96 or 112
+ * columns, chosen from the widest problem: 16 ceil(6 m / 16) + 6 K).  b, marg_pose, res, and
+ * H and bvec unless every K_p = 0, are checked for NULL before anything touches the GPU: -1
+ * and ba_last_error. */
+typedef struct {
+  int status, dropped_pivots, n_kept, n_marg_pose, n_marg_pt;
+} ba_batch_marg_result;
+int ba_batch_marginalize(ba_batch *b, double huber, const uint8_t *marg_pose, double *H,
+                         double *bvec, uint8_t *marg_pt, ba_batch_marg_result *res);
+/* Host-only: element offsets of every problem's H and bvec for this marking (B+1 each). */
+int ba_batch_marg_layout(ba_batch *b, const uint8_t *marg_pose, int64_t *H_off,
+                         int64_t *b_off);
+/* Host-only (no GPU): the kept poses (ascending user index, up to n_pose entries) and the
+ * landmark set L (one byte per point) of ONE problem under a marking.  kept_pose and marg_pt
+ * may be NULL.  Returns K, or -1. */
+int ba_batch_marg_plan_problem(int n_pose, const uint8_t *pose_fixed,
+                               const uint8_t *marg_pose, int n_pt, const uint8_t *pt_fixed,
+                               int64_t n_obs, const int32_t *obs_pose,
+                               const int32_t *obs_pt, int32_t *kept_pose, uint8_t *marg_pt);
 /* new values for the same structure, concatenated user order; NULL = keep */
 int ba_batch_update_values(ba_batch *b, const double *T_jw12, const double *X3);
 int ba_batch_get_poses(ba_batch *b, double *T_jw12);
