@@ -9,51 +9,59 @@ order than the reference's sequential loop (fp32 sums differ at ~1e-6).
 Quirks kept on purpose: the psi column of the Jacobian uses the INPUT point,
 the update is left-multiplicative while x, y are re-read and psi is summed,
 the Huber branch adds only error_u and the other only error_v, the inlier
-masks are sticky-false, the write-back is pose_b2b1^-1 * base_to_camera."""
+masks are sticky-false, the write-back is pose_b2b1^-1 * base_to_camera.
+
+Every function computes in `dtype` (default float32, the reference's and the
+kernel's precision).  dtype=np.float64 gives the higher-precision statement of
+the same operation on the same float32 inputs, widened exactly; it is the
+reference of tests/test_gpu_pose_only_onestep.py."""
 import numpy as np
 
 F = np.float32
 
 
 # ---- fp32 rigid transforms: (R [3,3], t [3]) -------------------------------
-def iso(T44):
-    T = np.asarray(T44, F)
+def iso(T44, dtype=F):
+    T = np.asarray(T44, np.float32).astype(dtype)
     return T[:3, :3].copy(), T[:3, 3].copy()
 
 
 def iso_mul(A, B):
     (Ra, ta), (Rb, tb) = A, B
+    F = Ra.dtype.type
     return (Ra @ Rb).astype(F), ((Ra @ tb) + ta).astype(F)
 
 
 def iso_inv(A):
     R, t = A
     Rt = R.T.copy()
-    return Rt, (-(Rt @ t)).astype(F)
+    return Rt, (-(Rt @ t)).astype(R.dtype.type)
 
 
 def iso44(A):
-    T = np.eye(4, dtype=F)
+    T = np.eye(4, dtype=A[0].dtype.type)
     T[:3, :3], T[:3, 3] = A
     return T
 
 
 def iso12(A):
-    return np.concatenate([A[0].reshape(9), A[1]]).astype(F)
+    return np.concatenate([A[0].reshape(9), A[1]]).astype(A[0].dtype.type)
 
 
-def planar_iso(x, y, psi):
+def planar_iso(x, y, psi, dtype=F):
     """pose_b2b1 of (x, y, psi) (:484-489)."""
+    F = dtype
     c, s = F(np.cos(F(psi))), F(np.sin(F(psi)))
     R = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]], F)
     return R, np.array([x, y, 0], F)
 
 
-def prior_theta(T_bc, T_wl, T_wc):
+def prior_theta(T_bc, T_wl, T_wc, dtype=F):
     """:446-460 — pose_b2b1 = T_bc * (T_wc^-1 * T_wl) * T_bc^-1, theta from it."""
-    Tbc = iso(T_bc)
+    F = dtype
+    Tbc = iso(T_bc, F)
     Tcb = iso_inv(Tbc)
-    prior = iso_mul(iso_inv(iso(T_wc)), iso(T_wl))
+    prior = iso_mul(iso_inv(iso(T_wc, F)), iso(T_wl, F))
     R, t = iso_mul(iso_mul(Tbc, prior), Tcb)
     return np.array([t[0], t[1], np.arctan2(R[1, 0], R[0, 0])], F)
 
@@ -62,7 +70,8 @@ def prior_theta(T_bc, T_wl, T_wc):
 def jacobian_residual(L, X, uv, fx, fy, cx, cy, R_cb, c, s):
     """:1454-1515, vectorised over points.  L = points in this camera, X = the
     input (base-1) points.  Returns r [n,2], Ju [n,3], Jv [n,3]."""
-    fx, fy, cx, cy = F(fx), F(fy), F(cx), F(cy)
+    F = L.dtype.type
+    fx, fy, cx, cy = (F(np.float32(v)) for v in (fx, fy, cx, cy))
     r11, r12, r21, r22, r31, r32 = (R_cb[0, 0], R_cb[0, 1], R_cb[1, 0], R_cb[1, 1],
                                     R_cb[2, 0], R_cb[2, 1])
     inverse_z = F(1) / L[:, 2]
@@ -92,22 +101,25 @@ def jacobian_residual(L, X, uv, fx, fy, cx, cy, R_cb, c, s):
 def residual(theta, X, uv, fx, fy, cx, cy, T_cam_b1):
     """Reprojection residual at theta for a camera whose pose relative to base-2
     is T_cam_b1(theta) = T_cam_base * pose_b2b1(theta) (no Jacobian)."""
-    L = warp(iso_mul(T_cam_b1, planar_iso(*theta)), X)
+    F = X.dtype.type
+    L = warp(iso_mul(T_cam_b1, planar_iso(*theta, dtype=F)), X)
     iz = F(1) / L[:, 2]
-    return np.stack([F(fx) * (L[:, 0] * iz) + F(cx) - uv[:, 0],
-                     F(fy) * (L[:, 1] * iz) + F(cy) - uv[:, 1]], 1)
+    fx, fy, cx, cy = (F(np.float32(v)) for v in (fx, fy, cx, cy))
+    return np.stack([fx * (L[:, 0] * iz) + cx - uv[:, 0],
+                     fy * (L[:, 1] * iz) + cy - uv[:, 1]], 1)
 
 
 def warp(P, X):
     R, t = P
-    return (X @ R.T + t).astype(F)
+    return (X @ R.T + t).astype(X.dtype.type)
 
 
 def gradient_hessian(r, Ju, Jv, thr_huber):
     """:1516-1583 — per-edge upper H (6: 00 01 02 11 12 22), gradient JtWr (3),
     error (Q9: Huber adds only error_u, otherwise only error_v) and the
     non-weighted error."""
-    thr = F(thr_huber)
+    F = r.dtype.type
+    thr = F(np.float32(thr_huber))
     ru, rv = r[:, 0], r[:, 1]
     ars = np.abs(ru) + np.abs(rv)
     hub = ars >= thr
@@ -124,8 +136,9 @@ def gradient_hessian(r, Ju, Jv, thr_huber):
     return H.astype(F), g.astype(F), err.astype(F), ars.astype(F)
 
 
-def ldlt_solve(A, b):
-    """Eigen's LDLT (pivoted on the largest remaining diagonal) solve, fp32."""
+def ldlt_solve(A, b, dtype=F):
+    """Eigen's LDLT (pivoted on the largest remaining diagonal) solve."""
+    F = dtype
     n = A.shape[0]
     m = np.array(A, F)
     d = np.array(b, F)
@@ -167,36 +180,44 @@ def ldlt_solve(A, b):
 # ---- the solvers ---------------------------------------------------------------
 def solve(X, uv, fx, fy, cx, cy, T_bc, T_wl, T_wc, mask, max_iter=50,
           thr_step=1e-5, thr_cost=1e-5, huber=1.0, outlier=2.0, uv_right=None,
-          intr_r=None, T_lr=None, mask_r=None):
+          intr_r=None, T_lr=None, mask_r=None, dtype=F):
     """Solve_Monocular_Planar3Dof (uv_right None) or Solve_Stereo_Planar3Dof.
     Poses are 4x4; returns the dict the GPU path returns (T12 = the
-    world_to_current written back, or the input when not written)."""
+    world_to_current written back, or the input when not written), and under
+    "edges" the first iteration's per-edge |ru| + |rv| and cost terms (ars_l,
+    err_l, and for the points with a right match has_r, ars_r, err_r) and under
+    "cond" the condition number of the first iteration's damped H."""
+    F = dtype
+    # the thresholds are float32 fields of the options: widened, not re-read
+    huber, outlier, thr_step, thr_cost = (np.float32(v) for v in
+                                          (huber, outlier, thr_step, thr_cost))
     stereo = uv_right is not None
-    X = np.asarray(X, F).reshape(-1, 3)
-    uv = np.asarray(uv, F).reshape(-1, 2)
+    X = np.asarray(X, np.float32).astype(F).reshape(-1, 3)
+    uv = np.asarray(uv, np.float32).astype(F).reshape(-1, 2)
     n = X.shape[0]
     mask = np.asarray(mask, bool).copy()
     inverse_n_pts = F(1) / F(n)
-    Tbc = iso(T_bc)
+    Tbc = iso(T_bc, F)
     Tcb = iso_inv(Tbc)                                   # :446
     R_cb = Tcb[0]
     if stereo:
-        uvr = np.asarray(uv_right, F).reshape(-1, 2)
+        uvr = np.asarray(uv_right, np.float32).astype(F).reshape(-1, 2)
         mask_r = np.asarray(mask_r, bool).copy()
-        Trl = iso_inv(iso(T_lr))                         # :674
+        Trl = iso_inv(iso(T_lr, F))                      # :674
         R_rb = (Trl[0] @ Tcb[0]).astype(F)               # :678-679
         has_r = ~((uvr[:, 0] < 0) | (uvr[:, 1] < 0))     # :785
-    theta = prior_theta(T_bc, T_wl, T_wc)                # :450-466
-    T_out = iso(T_wc)
+    theta = prior_theta(T_bc, T_wl, T_wc, F)             # :450-466
+    T_out = iso(T_wc, F)
     err_prev = F(1e10)
     lam = F(1e-5)
     converged, success = True, True
     rows, debug = [], []
     n_iter = 0
     Pb = None
+    edges = cond = None
     for iteration in range(max_iter):
         c, s = F(np.cos(theta[2])), F(np.sin(theta[2]))   # :484-485
-        Pb = planar_iso(theta[0], theta[1], theta[2])
+        Pb = planar_iso(theta[0], theta[1], theta[2], F)
         Pl = iso_mul(Tcb, Pb)                             # :490 / :724
         Hu, g, err, ars = gradient_hessian(
             *jacobian_residual(warp(Pl, X), X, uv, fx, fy, cx, cy, R_cb, c, s), huber)
@@ -216,14 +237,22 @@ def solve(X, uv, fx, fy, cx, cy, T_bc, T_wl, T_wc, mask, max_iter=50,
             mJtWr = mJtWr - gr.sum(0, dtype=F)
             err_curr = err_curr + er.sum(dtype=F)
             count_r = int(has_r.sum())
+        if edges is None:
+            edges = dict(ars_l=ars, err_l=err)
+            if stereo:
+                edges.update(has_r=has_r, ars_r=arr, err_r=er)
         H = np.zeros((3, 3), F)
         H[np.triu_indices(3)] = JtWJ
         H = np.triu(H) + np.triu(H, 1).T                  # :531
         for i in range(3):
             H[i, i] *= F(1) + lam                         # :532
-        delta = ldlt_solve(H, mJtWr)                      # :534
+        if cond is None:
+            with np.errstate(all="ignore"):
+                cond = float(np.linalg.cond(H.astype(np.float64))) \
+                    if np.isfinite(H).all() else np.inf
+        delta = ldlt_solve(H, mJtWr, F)                   # :534
         dx, dy, dpsi = delta
-        D = planar_iso(dx, dy, dpsi)                      # :536-542
+        D = planar_iso(dx, dy, dpsi, F)                   # :536-542
         Pb = iso_mul(D, Pb)                               # :543
         theta = np.array([Pb[1][0], Pb[1][1], theta[2] + dpsi], F)   # :545-547
         W = iso_mul(iso_inv(Pb), Tbc)                     # :549-550
@@ -243,7 +272,7 @@ def solve(X, uv, fx, fy, cx, cy, T_bc, T_wl, T_wc, mask, max_iter=50,
             converged = False
         rows.append((float(err_curr), float(delta_error), float(step)))
         err_prev = err_curr
-    T12_in = iso12(iso(T_wc))
+    T12_in = iso12(iso(T_wc, F))
     if Pb is None:                      # max_iter = 0 (undefined in the reference)
         T12 = T12_in
     elif np.isnan(np.linalg.norm(Pb[0])):
@@ -251,7 +280,8 @@ def solve(X, uv, fx, fy, cx, cy, T_bc, T_wl, T_wc, mask, max_iter=50,
     else:
         T12 = iso12(T_out)
     out = dict(T12=T12, n_iter=n_iter, converged=converged, success=success,
-               rows=rows, debug=np.array(debug, F).reshape(-1, 12), theta=theta)
+               rows=rows, debug=np.array(debug, F).reshape(-1, 12), theta=theta,
+               edges=edges, cond=cond)
     if stereo:
         out.update(mask_l=mask, mask_r=mask_r)
     else:
