@@ -90,8 +90,7 @@ int enqueue_iteration(ba_handle *h) {
   // pose in a covisibility group (no pose-major pass), no cost pass — the reset of the
   // factor tiles rides in the back-substitution launch (the solve is over by then),
   // the pose-side sums in the k_scalars launch: no fork / join gaps (6 + 8 us at C4).
-  static const bool no_side_env = !(getenv("BA_FORCE_SIDE") && getenv("BA_FORCE_SIDE")[0] == '1');
-  const bool no_side = no_side_env && !h->ar_fn && d.lin_chunk0 > 0 && d.n_achunk == 0 && d.n_obs_lm == d.n_obs;
+  const bool no_side = !h->knobs.run.force_side && !h->ar_fn && d.lin_chunk0 > 0 && d.n_achunk == 0 && d.n_obs_lm == d.n_obs;
   ba::launch_schur_accumulate(d, s);
   join_side(h);  // A_j, a_j of this point and the reset factor tiles come from the side stream
   ba::launch_schur_final(d, direct, s);
@@ -108,27 +107,19 @@ int enqueue_iteration(ba_handle *h) {
     ba::launch_lin_landmarks(d, 1, s);
   } else if (ov) {
     // pose side of the trial-point linearisation and the reset of the factor
-    // tiles: first needed by the NEXT iteration's k_schur_final.  BA_POSE_LATE=1
-    // (default) starts them after k_lin_landmarks, beside the control step, the
-    // damping kernel and the first part of k_schur_lds; 0 beside k_lin_landmarks.
+    // tiles: first needed by the NEXT iteration's k_schur_final.  They start after
+    // k_lin_landmarks, beside the control step, the damping kernel and the first
+    // part of k_schur_lds.
     // (with covisibility groups linearised by k_lin_grp the pose-side sums of the
-    //  side stream's k_pose_finalize read that kernel's rows: always "late")
-    static const bool late_env = !(getenv("BA_POSE_LATE") && getenv("BA_POSE_LATE")[0] == '0');
-    const bool late = late_env || d.lin_chunk0 > 0;
-    if (late) {
-      ba::launch_lin_landmarks(d, 1, s);
-      if (d.n_obs_lm < d.n_obs) ba::launch_cost(d, 2, d.n_obs_lm, s);
-    }
+    //  side stream's k_pose_finalize read that kernel's rows)
+    ba::launch_lin_landmarks(d, 1, s);
+    if (d.n_obs_lm < d.n_obs) ba::launch_cost(d, 2, d.n_obs_lm, s);
     (void)hipEventRecord(h->ev_fork, s);
     (void)hipStreamWaitEvent(h->side_stream, h->ev_fork, 0);
     ba::launch_dense_init(d.L, d.ld, d.col_x, d.zt_I, d.zt_J, d.n_zt, d.nb, &d.ctrl->done, h->side_stream);
     ba::launch_lin_poses(d, 1, h->side_stream);
     (void)hipEventRecord(h->ev_join, h->side_stream);
     h->side_pending = true;
-    if (!late) {
-      ba::launch_lin_landmarks(d, 1, s);
-      if (d.n_obs_lm < d.n_obs) ba::launch_cost(d, 2, d.n_obs_lm, s);
-    }
   } else {
     enqueue_linearize(h, 1);
   }
@@ -185,7 +176,7 @@ int download(std::vector<T> &out, const T *dev, size_t n, hipStream_t s) {
 // Device set-up of a dense schedule: the work lists of `dd`, its column -> x map col_x
 // (npad entries), the solution in column order xc, the dropped-pivot counter, the order,
 // flags and tickets of the dataflow sweeps and the k_chol_dag / k_chol_look items and
-// counters; reads the dense knobs and fixes the launch plans.  Everything is allocated on
+// counters; fixes the launch plans from the handle's dense knobs.  Everything is allocated on
 // the handle (h->upload / h->dalloc, in h->allocs).
 int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::vector<int> &col_x,
                           ba::DenseDev &dd) {
@@ -201,8 +192,7 @@ int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::
     return -1;
   HIP_TRY(hipMemset(dd.xc, 0, npad * sizeof(double)));
   HIP_TRY(hipMemset(dd.bad_pivots, 0, sizeof(int)));
-  dd.knobs = ba::DenseKnobs::from_env();
-  for (int flow_ok = 0; flow_ok < 2; ++flow_ok) dd.plan[flow_ok] = ba::dense_launch_plan(sc, dd.knobs, flow_ok != 0);
+  for (int flow_ok = 0; flow_ok < 2; ++flow_ok) dd.plan[flow_ok] = ba::dense_launch_plan(sc, h->knobs.dense, flow_ok != 0);
   const ba::DenseLaunchPlan &plan = dd.plan[1];  // (plan[0] has the same tail and lists: it only launches per level)
   std::vector<int> order;
   ba::dense_flow_order(sc, plan, order);
@@ -248,7 +238,7 @@ int finalize_plan(ba_handle *h) {
   in.obs_uv = h->obs_uv.data();
   in.rank = h->rank;
   in.world = h->world;
-  std::string err = ba::build_plan(in, h->plan);
+  std::string err = ba::build_plan(in, h->knobs.plan, h->plan);
   if (!err.empty()) return fail("ba_finalize: " + err);
   const ba::Plan &pl = h->plan;
   ba::DevProblem &d = h->d;
@@ -330,8 +320,7 @@ int upload_observation_lists(ba_handle *h) {
       h->upload(Mem::ChunkConst, &d.obs_uv, pl.obs_uv.data(), (size_t)pl.n_obs))
     return -1;
   // slim landmark-major record for the cost kernel (no pair id, 8 bytes)
-  const char *wide = getenv("BA_COST_WIDE");  // test knob: keep k_cost on the 16-byte records
-  if (!pl.obs_cp.empty() && pl.n_obs > 0 && !(wide && wide[0] == '1'))  // (filled by the planner's threaded pass)
+  if (!pl.obs_cp.empty() && pl.n_obs > 0 && !h->knobs.run.cost_wide)  // (filled by the planner's threaded pass)
     if (h->upload(Mem::ChunkConst, &d.obs_cp, pl.obs_cp.data(), (size_t)pl.n_obs)) return -1;
   if (h->upload(Mem::ChunkConst, &d.pobs_idx, pl.pobs_idx.data(), (size_t)pl.n_pobs) ||
       h->upload(Mem::ChunkConst, &d.pobs_uv, pl.pobs_uv.data(), (size_t)pl.n_pobs) ||
@@ -468,10 +457,10 @@ int alias_dense_owner(ba_handle *h) {
 // columns), eliminated in the order of the level schedule.  Both schedules are built;
 // dense_pick_tile_order chooses.  Then the image, the schedule's device lists and the
 // lists of the tiles that every iteration resets.
-int build_dense_system(ba_handle *h, bool times) {
+int build_dense_system(ba_handle *h) {
   const ba::Plan &pl = h->plan;
   ba::DevProblem &d = h->d;
-  const ba::DenseKnobs knobs = ba::DenseKnobs::from_env();
+  const ba::DenseKnobs &knobs = h->knobs.dense;
   ba::DenseSchedule cand[2];
   const int orders[2] = {32, 64};
   for (int k = 0; k < 2; ++k) {
@@ -479,9 +468,9 @@ int build_dense_system(ba_handle *h, bool times) {
     std::vector<uint8_t> adj;
     ba::tile_pattern(pl, ba::dense_poses_per_tile(orders[k]), ncb_k, adj);
     if (knobs.full) std::fill(adj.begin(), adj.end(), 1);
-    ba::build_dense_schedule(ncb_k, adj, knobs.natural, orders[k], cand[k]);
+    ba::build_dense_schedule(ncb_k, adj, knobs.natural, orders[k], cand[k], knobs.order);
   }
-  const bool stats = getenv("BA_PLAN_STATS") != nullptr;
+  const bool stats = h->knobs.plan.stats;
   if (stats)
     fprintf(stderr, "dense schedules: nb32 %d tiles %d levels max_rows %d fill %.3f | nb64 %d tiles %d levels max_rows %d fill %.3f\n",
             cand[0].ncb, cand[0].nlev, cand[0].max_rows, cand[0].fill, cand[1].ncb, cand[1].nlev, cand[1].max_rows,
@@ -507,7 +496,7 @@ int build_dense_system(ba_handle *h, bool times) {
   }
   if (h->upload(Mem::Resident, &d.pose_col, h->pose_col_h) || upload_dense_schedule(h, sc, col_x, dd)) return -1;
   d.col_x = dd.col_x;
-  if (times && dd.dag_items) fprintf(stderr, "[finalize] k_chol_dag: %d items\n", dd.plan[1].n_dag_items);
+  if (h->knobs.plan.times && dd.dag_items) fprintf(stderr, "[finalize] k_chol_dag: %d items\n", dd.plan[1].n_dag_items);
   if (stats)
     fprintf(stderr, "dense launch plan: nb%d forward %s backward %s tail %d columns%s\n", nb,
             ba::dense_fwd_name(dd.plan[1].fwd), ba::dense_back_name(dd.plan[1].back), dd.plan[1].tail_cols,
@@ -529,14 +518,14 @@ int build_dense_system(ba_handle *h, bool times) {
 }
 
 // The packed partial S||rhs (exchange buffer 0) and the dense reduced system behind it.
-int setup_reduced_system(ba_handle *h, bool times) {
+int setup_reduced_system(ba_handle *h) {
   const ba::Plan &pl = h->plan;
   h->xbuf_n[0] = pl.B * 36 + 6 * (int64_t)pl.N;
   h->xbuf_n[1] = 4;
   h->xbuf_n[2] = 3 * (int64_t)pl.n_pt_global;
   if (h->dalloc(Mem::Resident, &h->d.Spk, (size_t)h->xbuf_n[0])) return -1;
   HIP_TRY(hipMemset(h->d.Spk, 0, (size_t)h->xbuf_n[0] * sizeof(double)));
-  return h->dense_owner ? alias_dense_owner(h) : build_dense_system(h, times);
+  return h->dense_owner ? alias_dense_owner(h) : build_dense_system(h);
 }
 
 }  // namespace
@@ -565,8 +554,9 @@ int ba_create(ba_handle **out, int device_id) {
     return fail("ba_create: cannot create stream");
   }
   h->stream = h->own_stream;
-  if (const char *e2 = getenv("BA_NO_OVERLAP")) h->overlap = !(e2[0] == '1');
-  if (const char *e3 = getenv("BA_GRAPH")) h->use_graph = (e3[0] == '1');
+  h->knobs = ba::Knobs::from_env();
+  h->overlap = h->knobs.run.overlap;
+  h->use_graph = h->knobs.run.graph;
   std::memset(&h->d, 0, sizeof(h->d));
   std::memset(&h->hc, 0, sizeof(h->hc));
   *out = h;
@@ -681,7 +671,7 @@ int ba_partition_points(int n_pose, const uint8_t *pose_fixed, int n_pt,
     if (obs_pose[k] < 0 || obs_pose[k] >= n_pose || obs_pt[k] < 0 || obs_pt[k] >= n_pt)
       return fail("ba_partition_points: observation index out of range");
   std::vector<int32_t> owner;
-  ba::partition_points(in, owner);
+  ba::partition_points(in, ba::Knobs::from_env().plan.threads, owner);  // (no handle: read per call)
   std::memcpy(owner_out, owner.data(), sizeof(int32_t) * (size_t)n_pt);
   return 0;
 }
@@ -693,8 +683,7 @@ int ba_finalize(ba_handle *h) {
   if (h->n_cam <= 0 || h->n_pose <= 0 || h->n_pt <= 0)
     return fail("ba_finalize: cameras, poses and points must be set first");
   if (use_device(h)) return -1;
-  const bool times = getenv("BA_PLAN_TIMES") != nullptr;
-  h->up_times = times;
+  const bool times = h->knobs.plan.times;
   h->up_alloc_s = h->up_copy_s = 0;
   h->up_bytes = h->up_calls = 0;
   auto t_last = std::chrono::steady_clock::now();
@@ -713,7 +702,7 @@ int ba_finalize(ba_handle *h) {
   lap("structure uploads");
   if (alloc_iteration_storage(h)) return -1;
   lap("block storage");
-  if (setup_reduced_system(h, times)) return -1;
+  if (setup_reduced_system(h)) return -1;
   lap("dense schedule + image");
   std::memset(&h->hc, 0, sizeof(h->hc));
   h->hc.lambda = 100.0;
@@ -1547,7 +1536,7 @@ int ba_dense_spd_solve(ba_handle *h, int n, const double *A, const double *b,
       adj[(size_t)I * ncb + J] = adj[(size_t)J * ncb + I] = any;
     }
   ba::DenseSchedule sc;
-  ba::build_dense_schedule(ncb, adj, ba::DenseKnobs::from_env().natural, nb, sc);
+  ba::build_dense_schedule(ncb, adj, h->knobs.dense.natural, nb, sc, h->knobs.dense.order);
   std::vector<int> colmap(npad), col_x(npad, -1);  // original column -> dense column
   for (int c = 0; c < npad; ++c) colmap[c] = sc.pos_of_tile[c / nb] * nb + c % nb;
   std::vector<double> L((size_t)npad * ld, 0.0);
@@ -1624,17 +1613,17 @@ int ba_covariance_check(int finalized, int sharded, int streamed, int n_pose, co
 }
 
 // Columns of one batch for an image of npad rows: what fits 256 MiB of workspace, at most
-// 1024 waves' worth, a multiple of the 16 columns of a wave; BA_COV_BATCH overrides.
-static int cov_batch_cols(int npad) {
+// 1024 waves' worth, a multiple of the 16 columns of a wave; RunKnobs::cov_batch overrides.
+static int cov_batch_cols(int npad, const ba::RunKnobs &knobs) {
   int64_t cols = ((int64_t)256 << 20) / (8 * (int64_t)std::max(npad, 1));
-  if (const char *e = getenv("BA_COV_BATCH")) cols = atoll(e);
+  if (knobs.cov_batch > 0) cols = knobs.cov_batch;
   cols = std::min<int64_t>(cols, 1024 * ba::kCovGroupCols);
   return (int)std::max<int64_t>(ba::kCovGroupCols, cols / ba::kCovGroupCols * ba::kCovGroupCols);
 }
 
 int ba_covariance_info(ba_handle *h, int64_t out4[4]) {
   if (!h || !h->finalized || !out4) return fail("ba_covariance_info: bad argument");
-  const int bw = cov_batch_cols(h->d.npad);
+  const int bw = cov_batch_cols(h->d.npad, h->knobs.run);
   out4[0] = bw;
   out4[1] = ba::kCovGroupCols;
   out4[2] = (int64_t)h->d.npad * bw * (int64_t)sizeof(double);
@@ -1731,7 +1720,7 @@ int ba_covariance(ba_handle *h, double huber, int n_pose_sel, const int32_t *pos
     // that the whole factor is left in the image.  Same arithmetic.
     const ba::DenseDev &dd = h->ddev;
     ba::dense_factor_solve(d.L, d.npad, d.ld, d.Ldiag, d.x, &d.ctrl->done, sc, dd,
-                           ba::dense_launch_plan_no_tail(sc, dd.knobs, dd.flow_ok, dd.plan[1]), h->stream);
+                           ba::dense_launch_plan_no_tail(sc, h->knobs.dense, dd.flow_ok, dd.plan[1]), h->stream);
   }
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(&bad_now, h->ddev.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
@@ -1740,7 +1729,7 @@ int ba_covariance(ba_handle *h, double huber, int n_pose_sel, const int32_t *pos
   if (push_ctrl(h)) return -1;
   // ---- the batches; everything below is freed again on every return
   ba::ScratchAllocs scratch(h);
-  const int bw_max = cov_batch_cols(d.npad);
+  const int bw_max = cov_batch_cols(d.npad, h->knobs.run);
   const int gpb = bw_max / ba::kCovGroupCols;  // groups per batch
   const int bw = (int)std::min<size_t>(gpb, std::max<size_t>(1, groups.size())) * ba::kCovGroupCols;
   int *d_trow_ptr = nullptr, *d_trow = nullptr;

@@ -189,13 +189,12 @@ void build_one(int ncb, const std::vector<uint8_t> &adj_in, bool natural_order, 
 }  // namespace
 
 void build_dense_schedule(int ncb, const std::vector<uint8_t> &adj, bool natural_order, int nb,
-                          DenseSchedule &s) {
-  const char force = DenseKnobs::from_env().order;
-  if (natural_order || force == 's') {
+                          DenseSchedule &s, char order) {
+  if (natural_order || order == 's') {
     build_one(ncb, adj, natural_order, nb, false, s);
     return;
   }
-  if (force == 'r') {
+  if (order == 'r') {
     build_one(ncb, adj, false, nb, true, s);
     return;
   }

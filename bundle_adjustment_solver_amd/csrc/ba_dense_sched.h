@@ -58,9 +58,11 @@ struct DenseSchedule {
 
 // `adj` is the symmetric ncb x ncb tile adjacency (non-zero off-diagonal
 // tiles), row-major bytes.  `natural_order` = keep the given order and put
-// every tile in its own level (debug / dense comparison).
+// every tile in its own level (debug / dense comparison).  `order` = 's': the strict
+// ordering, 'r': the relaxed one, 0: whichever gives the shorter chain of launches
+// (DenseKnobs::natural, DenseKnobs::order).
 void build_dense_schedule(int ncb, const std::vector<uint8_t> &adj,
-                          bool natural_order, int nb, DenseSchedule &s);
+                          bool natural_order, int nb, DenseSchedule &s, char order = 0);
 
 // ---- which kernels run a schedule (launched by dense_factor_solve, ba_dense.hip) ----
 // DESIGN.md ("launch paths of the dense solve") has the measurements behind the defaults.
@@ -80,7 +82,7 @@ constexpr int kBackGatherMaxRows = 12;
 // fit its prefetched passes, 4 passes x (4 waves / (nb / 16)) tiles.
 inline int dense_fused_max_rows(int nb) { return 4 * (4 / (nb / 16)); }
 
-// The BA_DENSE_* environment variables.
+// The BA_DENSE_* environment variables (part of Knobs, ba_knobs.h: read once per handle).
 struct DenseKnobs {
   bool want_split = false;                      // SPLIT=1: separate diagonal and TRSM launches
   bool want_tail = true;                        // TAIL=0: no k_chol_tail

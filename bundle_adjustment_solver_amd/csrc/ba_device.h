@@ -328,7 +328,6 @@ struct DenseDev {
   mutable int flow_gen = 0;
   // what dense_factor_solve launches (ba_dense_sched.h), as decided when the schedule was
   // uploaded: plan[flow_ok]
-  DenseKnobs knobs;
   DenseLaunchPlan plan[2];
   bool flow_ok = true;  // false while a hipGraph is captured / replayed (the generation is a kernel argument)
 };

@@ -51,6 +51,7 @@ enum Stage { ST_BUILD = 0, ST_SCHUR, ST_SOLVE, ST_BACKSUB, ST_COST, ST_CTRL, ST_
 
 struct ba_handle {
   int device = 0;
+  ba::Knobs knobs;  // the BA_* environment as ba_create found it: read once, for the handle's life
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   // second stream for work that is independent inside one LM iteration
@@ -58,7 +59,7 @@ struct ba_handle {
   // pose update beside the back-substitution), joined with events
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool overlap = true;
+  bool overlap = true;  // (seeded from knobs.run.overlap; ba_stream turns it off on its chunk handles)
   // the side stream holds work of the last enqueued iteration (pose-side
   // linearisation at the trial point, reset of the factor tiles) that the main
   // stream has not joined yet
@@ -70,7 +71,7 @@ struct ba_handle {
   // replayed by ba_lm_iterate instead of ~50 separate launches.  Opt-in
   // (BA_GRAPH=1): on ROCm 7.2 / MI355X the replay measured 2.5 % SLOWER than
   // plain launches on C4 (993 vs 969 us per iteration), see DESIGN.md.
-  bool use_graph = false;
+  bool use_graph = false;  // (seeded from knobs.run.graph; cleared when the capture fails)
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   void drop_graph() {
@@ -154,14 +155,14 @@ struct ba_handle {
     allocs.push_back((void *)*p);
     return 0;
   }
-  // BA_PLAN_TIMES: bytes / seconds spent in upload() (allocation and copy apart)
-  bool up_times = false;
+  // knobs.plan.times: bytes / seconds spent in upload() (allocation and copy apart)
   double up_alloc_s = 0, up_copy_s = 0;
   size_t up_bytes = 0, up_calls = 0;
   // `host` holds n records with the layout of T (the planner keeps some of them as flat
   // int32 / double vectors or as its own mirror of a device struct)
   template <class T>
   int upload(ba::Mem where, T **p, const void *host, size_t n) {
+    const bool up_times = knobs.plan.times;
     const auto t0 = up_times ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
     if (dalloc(where, p, n)) return -1;
     const auto t1 = up_times ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();

@@ -27,9 +27,9 @@ void plan_big_free(void *p, size_t) { free(p); }
 
 namespace {
 
-// BA_PLAN_TIMES=1: wall time of the planner's phases on stderr (developer knob)
+// PlanKnobs::times: wall time of the planner's phases on stderr (developer knob)
 struct PhaseClock {
-  const bool on = getenv("BA_PLAN_TIMES") != nullptr;
+  const bool on;
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   void lap(const char *what) {
     if (!on) return;
@@ -39,23 +39,19 @@ struct PhaseClock {
   }
 };
 
-// Static-chunk parallel loop over [0, n) on host threads (BA_PLAN_THREADS, default:
-// the hardware's, at most 16).  Every use below writes disjoint outputs per index
-// and all prefix sums stay sequential, so the plan is identical for every thread
-// count (tests/cpp/plan_check.cpp compares it with the one-thread build).
-int plan_threads() {
-  static const int n = [] {
-    const char *e = getenv("BA_PLAN_THREADS");
-    int v = e ? atoi(e) : (int)std::thread::hardware_concurrency();
-    return std::max(1, std::min(v, 16));
-  }();
-  return n;
+// Host threads of the planner: PlanKnobs::threads, or the hardware's, at most 16.
+int plan_threads(int knob) {
+  return knob > 0 ? knob : std::max(1, std::min((int)std::thread::hardware_concurrency(), 16));
 }
+// Static-chunk parallel loop over [0, n) on at most `threads` host threads.  Every use
+// below writes disjoint outputs per index and all prefix sums stay sequential, so the
+// plan is identical for every thread count (tests/cpp/plan_check.cpp compares it with
+// the one-thread build).
 // (grain: indices a thread should at least get — 4096 for per-landmark loops; loops over
 //  runs / buckets of hundreds of landmarks pass a small one)
 template <class F>
-void parallel_for(int64_t n, const F &fn, int64_t grain = 4096) {
-  const int nt = (int)std::min<int64_t>(plan_threads(), std::max<int64_t>(1, n / grain));
+void parallel_for(int threads, int64_t n, const F &fn, int64_t grain = 4096) {
+  const int nt = (int)std::min<int64_t>(threads, std::max<int64_t>(1, n / grain));
   if (nt <= 1) {
     fn((int64_t)0, n);
     return;
@@ -89,14 +85,14 @@ void order_poses(const PlanInput &in, std::vector<int32_t> &int_of_user,
 }
 
 // Locality order of all points: (first observing internal pose, input index).
-void locality_order(const PlanInput &in,
+void locality_order(const PlanInput &in, int threads,
                     const std::vector<int32_t> &pose_int_of_user,
                     std::vector<int32_t> &order,
                     std::vector<int64_t> &obs_count) {
   std::vector<int32_t> first_pose(in.n_pt, in.n_pose);
   obs_count.assign(in.n_pt, 0);
   // (threaded by point range: every thread scans the whole list and keeps its own points)
-  parallel_for(in.n_pt, [&](int64_t q0, int64_t q1) {
+  parallel_for(threads, in.n_pt, [&](int64_t q0, int64_t q1) {
     for (int64_t k = 0; k < in.n_obs; ++k) {
       const int64_t q = in.obs_pt[k];
       if (q < q0 || q >= q1) continue;
@@ -118,16 +114,15 @@ void locality_order(const PlanInput &in,
 // whole number of such rounds (C4: 500 k landmarks -> 2 rounds of 326 instead
 // of 2.5 rounds of 256), at most kSchurSuperLandmarks and at least
 // kSchurSuperMin each.
-int schur_run_cap(int64_t M) {
+int schur_run_cap(int64_t M, int knob) {
   const int64_t rounds = std::max<int64_t>(
       1, (M + (int64_t)kSchurRunTarget * kSchurSuperLandmarks - 1) /
              ((int64_t)kSchurRunTarget * kSchurSuperLandmarks));
-  int cap = (int)std::min<int64_t>(
+  if (knob > 0) return knob;  // PlanKnobs::sup_cap (tuning knob)
+  return (int)std::min<int64_t>(
       kSchurSuperLandmarks,
       std::max<int64_t>(kSchurSuperMin,
                         (M + kSchurRunTarget * rounds - 1) / (kSchurRunTarget * rounds)));
-  if (const char *e = getenv("BA_SUP_CAP")) cap = std::max(1, atoi(e));  // tuning knob
-  return cap;
 }
 
 void assign_owner(const PlanInput &in, const std::vector<int32_t> &order,
@@ -222,28 +217,29 @@ void deal_lanes(const std::vector<int64_t> &tcount, std::vector<uint32_t> &out) 
   }
 }
 
-void partition_points(const PlanInput &in, std::vector<int32_t> &owner) {
+void partition_points(const PlanInput &in, int threads, std::vector<int32_t> &owner) {
   std::vector<int32_t> piu, pui, jou;
   int N = 0;
   order_poses(in, piu, pui, jou, N);
   std::vector<int32_t> order;
   std::vector<int64_t> cnt;
-  locality_order(in, piu, order, cnt);
+  locality_order(in, plan_threads(threads), piu, order, cnt);
   assign_owner(in, order, cnt, owner);
 }
 
-std::string build_plan(const PlanInput &in, Plan &pl) {
+std::string build_plan(const PlanInput &in, const PlanKnobs &knobs, Plan &pl) {
   if (in.n_cam <= 0) return "no cameras";
   if (in.n_pose <= 0) return "no poses";
   if (in.n_pt <= 0) return "no points";
   if (in.world < 1 || in.rank < 0 || in.rank >= in.world)
     return "bad rank/world";
-  PhaseClock clk;
+  PhaseClock clk{knobs.times};
+  const int threads = plan_threads(knobs.threads);
   {
     // first offending observation (the smallest index, whatever the thread count)
-    std::vector<int64_t> bad((size_t)plan_threads() + 1, INT64_MAX);
+    std::vector<int64_t> bad((size_t)threads + 1, INT64_MAX);
     std::atomic<int> slot{0};
-    parallel_for(in.n_obs, [&](int64_t k0, int64_t k1) {
+    parallel_for(threads, in.n_obs, [&](int64_t k0, int64_t k1) {
       const int me = slot.fetch_add(1);
       for (int64_t k = k0; k < k1; ++k)
         if (in.obs_cam[k] < 0 || in.obs_cam[k] >= in.n_cam || in.obs_pose[k] < 0 || in.obs_pose[k] >= in.n_pose ||
@@ -275,7 +271,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
     if (!in.pt_fixed[q]) pl.iopt_of_user[q] = pl.M_global++;
   std::vector<int32_t> order;
   std::vector<int64_t> cnt;
-  locality_order(in, pl.pose_int_of_user, order, cnt);
+  locality_order(in, threads, pl.pose_int_of_user, order, cnt);
   assign_owner(in, order, cnt, pl.owner);
 
   pl.pt_int_of_user.assign(in.n_pt, -1);
@@ -306,7 +302,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
   //  observation list — a sequential read — and files the observations of its own points,
   //  in input order: the result does not depend on the thread count)
   std::vector<int64_t> uo_ptr((size_t)in.n_pt + 1, 0);
-  parallel_for(in.n_pt, [&](int64_t q0, int64_t q1) {
+  parallel_for(threads, in.n_pt, [&](int64_t q0, int64_t q1) {
     for (int64_t k = 0; k < in.n_obs; ++k) {
       const int64_t q = in.obs_pt[k];
       if (q >= q0 && q < q1 && pl.owner[q] == in.rank) uo_ptr[q + 1]++;
@@ -322,7 +318,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
   pvec<ObsRecP> uo_rec((size_t)uo_ptr[in.n_pt]);
   {
     pvec<int64_t> cur((size_t)in.n_pt);
-    parallel_for(in.n_pt, [&](int64_t q0, int64_t q1) {
+    parallel_for(threads, in.n_pt, [&](int64_t q0, int64_t q1) {
       for (int64_t q = q0; q < q1; ++q) cur[q] = uo_ptr[q];
       for (int64_t k = 0; k < in.n_obs; ++k) {
         const int64_t q = in.obs_pt[k];
@@ -335,7 +331,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
       }
     });
   }
-  parallel_for(in.n_pt, [&](int64_t q0, int64_t q1) {
+  parallel_for(threads, in.n_pt, [&](int64_t q0, int64_t q1) {
     for (int64_t q = q0; q < q1; ++q) {
       // stable insertion sort by pose (lists are short and nearly sorted: the usual
       // insertion order is pose-major)
@@ -356,9 +352,9 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
   clk.lap("per-point observation lists");
   pl.M_grp = 0;
   pl.grp_range.clear();
-  pl.lin_groups = !(getenv("BA_NO_LINGRP") && getenv("BA_NO_LINGRP")[0] == '1');
+  pl.lin_groups = knobs.lin_groups;
   if (pl.n_cam >= 65536) pl.lin_groups = false;  // (the pattern record packs the camera into 16 bits)
-  if (pl.M > 0 && !(getenv("BA_NO_GROUPS") && getenv("BA_NO_GROUPS")[0] == '1')) {
+  if (pl.M > 0 && knobs.groups) {
     const int M0 = pl.M;
     std::vector<int64_t> kp(M0 + 1, 0);
     for (int i = 0; i < M0; ++i) {
@@ -366,7 +362,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
       kp[i + 1] = kp[i] + (uo_ptr[q + 1] - uo_ptr[q]);
     }
     pvec<uint64_t> pat((size_t)kp[M0]);  // (pose << 32) | camera, per point in (pose, insertion) order
-    parallel_for(M0, [&](int64_t i0, int64_t i1) {
+    parallel_for(threads, M0, [&](int64_t i0, int64_t i1) {
       for (int64_t i = i0; i < i1; ++i) {
         const int q = pl.pt_user_of_int[i];
         int64_t w = kp[i];
@@ -422,7 +418,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
       if (!monotone) {
         std::stable_sort(cand.begin(), cand.end(), less_sig);
       } else {
-        parallel_for((int64_t)run0.size() - 1, [&](int64_t r0, int64_t r1) {
+        parallel_for(threads, (int64_t)run0.size() - 1, [&](int64_t r0, int64_t r1) {
           for (int64_t r = r0; r < r1; ++r)  // (regular scenes: one pattern per run, nothing to sort)
             if (!std::is_sorted(cand.begin() + run0[r], cand.begin() + run0[r + 1], less_sig))
               std::stable_sort(cand.begin() + run0[r], cand.begin() + run0[r + 1], less_sig);
@@ -449,13 +445,12 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
     };
     std::vector<GroupBuild> groups;
     std::vector<int32_t> group_of(M0, -1);
-    const bool no_superset_env = getenv("BA_NO_SUPERSET") && getenv("BA_NO_SUPERSET")[0] == '1';
-    const bool superset = pl.lin_groups && !no_superset_env;
+    const bool superset = pl.lin_groups && knobs.superset;
     // the pose SPAN of a landmark in USER pose indices (the registration order of the
     // poses is normally the trajectory; the internal order puts the fixed poses last,
     // which would throw every window that touches a fixed pose into one bucket)
     std::vector<int32_t> span_lo(M0, 0), span_hi(M0, 0);
-    parallel_for(M0, [&](int64_t i0, int64_t i1) {
+    parallel_for(threads, M0, [&](int64_t i0, int64_t i1) {
       for (int64_t i = i0; i < i1; ++i) {
         int32_t lo = INT32_MAX, hi = -1;
         for (int64_t t = kp[i]; t < kp[i + 1]; ++t) {
@@ -540,7 +535,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
       bkt.push_back(cand.size());
       const size_t nbkt = cand.empty() ? 0 : bkt.size() - 1;
       std::vector<std::vector<GroupBuild>> bout(nbkt);
-      parallel_for((int64_t)nbkt, [&](int64_t k0, int64_t k1) {
+      parallel_for(threads, (int64_t)nbkt, [&](int64_t k0, int64_t k1) {
         std::vector<uint64_t> uni;
         for (int64_t k = k0; k < k1; ++k) {
           const size_t a = bkt[k], b = bkt[k + 1];
@@ -636,8 +631,8 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
   // r + 2S, ...), so that every chunk of consecutive landmarks samples the
   // WHOLE window and touches the run's S blocks in the run's proportions
   // (the lanes of the Schur kernel are dealt to the blocks in those proportions).
-  if (!(getenv("BA_NO_INTERLEAVE") && getenv("BA_NO_INTERLEAVE")[0] == '1')) {
-    const int W = schur_run_cap(pl.M - pl.M_grp);
+  if (knobs.interleave) {
+    const int W = schur_run_cap(pl.M - pl.M_grp, knobs.sup_cap);
     std::vector<int32_t> tmp;
     for (int base = pl.M_grp; base < pl.M; base += W) {
       const int n = std::min(W, pl.M - base);
@@ -677,7 +672,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
       const Plan::GrpRange &gr = pl.grp_range[lm_grp[pi]];
       return gr.masked ? &gr : nullptr;
     };
-    parallel_for(n_own, [&](int64_t a0, int64_t a1) {
+    parallel_for(threads, n_own, [&](int64_t a0, int64_t a1) {
       for (int64_t pi = a0; pi < a1; ++pi) {
         const int q = pl.pt_user_of_int[pi];
         if (const Plan::GrpRange *gr = masked_group(pi)) {
@@ -714,7 +709,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
     pl.pair_pose.resize((size_t)pptr[n_own]);
     pl.pair_lm.resize((size_t)pptr[n_own]);
     pl.pair_pad.assign((size_t)pptr[n_own], 0);
-    parallel_for(n_own, [&](int64_t a0, int64_t a1) {
+    parallel_for(threads, n_own, [&](int64_t a0, int64_t a1) {
       for (int64_t pi = a0; pi < a1; ++pi) {
         const int q = pl.pt_user_of_int[pi];
         if (const Plan::GrpRange *gr = masked_group(pi)) {
@@ -933,10 +928,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
              d > kSchurPairs;
     };
     // ... and cannot be split into classes either (its pairs exceed the LDS staging): global list
-    auto is_list = [&](int64_t d) {
-      static const bool no_split = getenv("BA_NO_SPLIT") && getenv("BA_NO_SPLIT")[0] == '1';
-      return is_big(d) && (d > kSchurPairs || no_split);
-    };
+    auto is_list = [&](int64_t d) { return is_big(d) && (d > kSchurPairs || !knobs.split); };
     // (a) big landmarks -> global triple list sorted by (block, landmark)
     int64_t Tbig = 0, Tall = 0;
     for (int i = 0; i < M; ++i) {
@@ -987,7 +979,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
     std::vector<int32_t> sup_blocks;
     std::vector<std::pair<int32_t, uint32_t>> loc;
     std::vector<int64_t> tcount;  // triples per slot of the current run
-    double sum_max = 0, sum_ideal = 0, sum_mean_active = 0;  // BA_PLAN_STATS
+    double sum_max = 0, sum_ideal = 0, sum_mean_active = 0;  // PlanKnobs::stats
     long n_ch = 0;
     pl.sup_lane.clear();
     // (a') covisibility groups: one k_schur_grp workgroup per (piece of a) group,
@@ -1024,10 +1016,10 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
       // k_lin_grp pieces: runs of `steps` wave steps (4 waves x nlw landmarks each), the
       // pieces of a group equal up to one step
       {
-        const int steps_env = getenv("BA_LIN_STEPS") ? std::max(1, atoi(getenv("BA_LIN_STEPS"))) : kLinGrpSteps;
+        const int steps = knobs.lin_steps > 0 ? knobs.lin_steps : kLinGrpSteps;
         const int per_step = 4 * lin_grp_nlw(gr.no);
         const int nstep = (gr.nl + per_step - 1) / per_step;
-        const int npiece = (nstep + steps_env - 1) / steps_env;
+        const int npiece = (nstep + steps - 1) / steps;
         for (int c = 0; c < npiece; ++c) {
           const int s0 = (int)((int64_t)nstep * c / npiece), s1 = (int)((int64_t)nstep * (c + 1) / npiece);
           Plan::LinDesc ld;
@@ -1047,11 +1039,10 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
         }
       }
       if (gr.d == 0) continue;  // no pair, no Schur contribution: no k_schur_grp workgroup
-      static const int grp_max = getenv("BA_GRP_MAX") ? std::max(12, atoi(getenv("BA_GRP_MAX"))) : kGrpMaxLandmarks;
       // (wide groups, d > 10: k_schur_grp_wide is bound by the fp64 matrix pipe — 27 MFMAs per
       //  landmark — and a 20-pose window of a few hundred landmarks is one long workgroup:
       //  pieces of <= kGrpWidePiece landmarks spread them over the CUs)
-      const int cap = gr.d > 10 ? std::min(grp_max, kGrpWidePiece) : grp_max;
+      const int cap = gr.d > 10 ? kGrpWidePiece : kGrpMaxLandmarks;
       const int pieces = (gr.nl + cap - 1) / cap;
       const int per = (gr.nl + pieces - 1) / pieces;
       for (int c0 = 0; c0 < gr.nl; c0 += per) {
@@ -1071,7 +1062,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
         (gr.d <= 5 ? pl.grp32 : gr.d <= 10 ? pl.grp64 : pl.grp128).push_back(gd);
       }
     }
-    const int sup_cap = schur_run_cap(M - pl.M_grp);
+    const int sup_cap = schur_run_cap(M - pl.M_grp, knobs.sup_cap);
     // Landmark kinds: 0 = fits a super-run whole; 1 = SPLIT: its pairs fit the LDS
     // staging (<= kSchurPairs) but its d (d + 1) / 2 blocks exceed the kSchurSlots
     // register slots of a run: the pose list is cut into g groups of <= kSplit
@@ -1230,7 +1221,7 @@ std::string build_plan(const PlanInput &in, Plan &pl) {
       }
       pl.sup_desc.push_back(sd);
       deal_lanes(tcount, pl.sup_lane);
-      if (getenv("BA_PLAN_STATS")) {  // balance of the triple loop (developer knob)
+      if (knobs.stats) {  // balance of the triple loop (developer knob)
         const uint32_t *lw = &pl.sup_lane[pl.sup_lane.size() - 256];
         std::vector<int> tps2(ns, 1);
         for (int q = 0; q < 256; ++q)

@@ -18,6 +18,8 @@
 #include <utility>
 #include <vector>
 
+#include "ba_knobs.h"
+
 namespace ba {
 
 // std::vector whose resize() leaves trivially constructible elements uninitialised:
@@ -217,11 +219,14 @@ void tile_pattern(const Plan &pl, int poses_per_tile, int &ncb,
                   std::vector<uint8_t> &adj);
 
 // Owner rank of every point: locality order (first observing optimised pose,
-// then input index), contiguous chunks balanced by observation count.
-void partition_points(const PlanInput &in, std::vector<int32_t> &owner);
+// then input index), contiguous chunks balanced by observation count.  The result does
+// not depend on `threads` (PlanKnobs::threads).
+void partition_points(const PlanInput &in, int threads, std::vector<int32_t> &owner);
 
 // Returns empty string on success, otherwise an error message.
-std::string build_plan(const PlanInput &in, Plan &plan);
+std::string build_plan(const PlanInput &in, const PlanKnobs &knobs, Plan &plan);
+// For a stand-alone caller without a handle: the knobs of the environment at this call.
+inline std::string build_plan(const PlanInput &in, Plan &plan) { return build_plan(in, Knobs::from_env().plan, plan); }
 
 }  // namespace ba
 #endif

@@ -40,6 +40,7 @@
 using ba::fail;
 
 struct ba_stream {
+  ba::Knobs knobs;  // the BA_* environment as ba_stream_create found it (the stream consults run.stream_sync)
   int device = 0, K = 1;
   int64_t arena_bytes = 0;
   hipStream_t s_comp = nullptr, s_copy = nullptr;
@@ -104,12 +105,9 @@ int prefetch(ba_stream *s, int k) {
   return 0;
 }
 
-// BA_STREAM_SYNC=1 (developer knob): a device synchronisation after every transfer and
+// RunKnobs::stream_sync (developer knob): a device synchronisation after every transfer and
 // every chunk's kernels — no overlap; separates ordering bugs from logic bugs
-bool sync_mode() {
-  static const bool on = getenv("BA_STREAM_SYNC") && getenv("BA_STREAM_SYNC")[0] == '1';
-  return on;
-}
+bool sync_mode(const ba_stream *s) { return s->knobs.run.stream_sync; }
 
 int acquire(ba_stream *s, int k) {
   if (prefetch(s, k)) return -1;
@@ -117,7 +115,7 @@ int acquire(ba_stream *s, int k) {
     HIP_TRY(hipStreamWaitEvent(s->s_comp, s->ev_in[k], 0));
     s->in_pending[k] = 0;
   }
-  if (sync_mode()) HIP_TRY(hipDeviceSynchronize());
+  if (sync_mode(s)) HIP_TRY(hipDeviceSynchronize());
   return 0;
 }
 
@@ -126,7 +124,7 @@ int release(ba_stream *s, int k, bool wrote) {
   HIP_TRY(hipEventRecord(s->ev_comp[k], s->s_comp));
   s->computed[k] = 1;
   if (wrote) s->dirty[k] = 1;
-  if (sync_mode()) HIP_TRY(hipDeviceSynchronize());
+  if (sync_mode(s)) HIP_TRY(hipDeviceSynchronize());
   return 0;
 }
 
@@ -262,6 +260,7 @@ int ba_stream_create(ba_stream **out, int device_id, int n_chunks, int64_t arena
     return fail("ba_stream_create: no HIP device available (the HIP path has no CPU fallback)");
   if (device_id < 0 || device_id >= ndev) return fail("ba_stream_create: bad device id");
   ba_stream *s = new ba_stream();
+  s->knobs = ba::Knobs::from_env();
   s->device = device_id;
   s->K = n_chunks;
   s->arena_bytes = (arena_bytes + 255) & ~(int64_t)255;

@@ -46,8 +46,9 @@ int main(int argc, char **argv) {
   ba::PlanInput in;
   in.n_cam = n_cam; in.n_pose = n_pose; in.pose_fixed = pf.data(); in.n_pt = n_pt; in.pt_fixed = qf.data();
   in.n_obs = (int64_t)oc.size(); in.obs_cam = oc.data(); in.obs_pose = op.data(); in.obs_pt = oq.data(); in.obs_uv = uv.data();
+  const ba::PlanKnobs knobs = ba::Knobs::from_env().plan;  // (the test sets BA_* variables per run)
   ba::Plan pl;
-  const std::string err = ba::build_plan(in, pl);
+  const std::string err = ba::build_plan(in, knobs, pl);
   CHECK(err.empty(), "build_plan: %s", err.c_str());
   if (!err.empty()) return 1;
 
@@ -203,7 +204,7 @@ int main(int argc, char **argv) {
         nextl = gd.l0 + gd.nl;
         CHECK(gd.no >= gd.d && gd.no >= 1 && gd.no <= ba::kGrpMaxObs && gd.o0 == pl.lm_obs_ptr[gd.l0] && gd.p0 == pl.lm_pair_ptr[gd.l0],
               "piece observation / pair base");
-        CHECK(gd.nl <= ba::kLinGrpSteps * 4 * ba::lin_grp_nlw(gd.no) || getenv("BA_LIN_STEPS"), "piece size");
+        CHECK(gd.nl <= ba::kLinGrpSteps * 4 * ba::lin_grp_nlw(gd.no) || knobs.lin_steps > 0, "piece size");
         CHECK(gd.pat0 >= 0 && (size_t)(gd.pat0 + gd.no) * 2 <= pl.grp_pat.size(), "group pattern range");
         int pose_valid[ba::kGrpMaxPoses] = {0};
         for (int l = gd.l0; l < gd.l0 + gd.nl; ++l) {
@@ -236,7 +237,7 @@ int main(int argc, char **argv) {
       CHECK(nextl == (pl.lin_groups ? pl.M_grp : 0), "k_lin_grp pieces cover the grouped landmarks");
       std::printf("masked groups: %d pieces of %zu, %lld padded slots, %lld padded pairs\n",
                   (int)pl.lin_desc.size() - pl.n_lin_plain, pl.lin_desc.size(), n_masked_slots, (long long)pl.n_pair_pad);
-      if (drop_pct > 0 && !getenv("BA_NO_SUPERSET") && pl.lin_groups)
+      if (drop_pct > 0 && knobs.superset && pl.lin_groups)
         CHECK((int)pl.lin_desc.size() > pl.n_lin_plain && n_masked_slots > 0, "the dropout scene must produce masked groups");
     }
     for (int l = 0; l < pl.M; ++l) {

@@ -376,6 +376,40 @@ def test_one_stream_iteration_and_dataflow_sweep_equal_their_fallbacks(built):
     for other in runs[1:]:
         assert other[0] == runs[0][0]
         assert (other[1] == runs[0][1]).all() and (other[2] == runs[0][2]).all()
+    # BA_FORCE_SIDE=1 reached its handles (every handle reads the environment at its own
+    # ba_create, so a setting does not depend on what ran earlier in the process): the launch
+    # counts of timing mode, which covers the kernels of enqueue_iteration.  On one stream an
+    # iteration never calls launch_lin_poses (k_scalars sums the pose side) and calls
+    # launch_dense_init only while no k_backsub_update has reset the tiles yet, i.e. in the
+    # first iteration after lm_begin.  With the knob every iteration calls both once: one
+    # k_pose_finalize (and no k_lin_poses: the scene has no pose-major list) and one
+    # k_dense_init.  So from the second iteration on the counts stand still without the knob
+    # and grow by one per iteration with it.  (Timing mode serialises the streams: these
+    # handles are for the counts only.)
+    growth = {}
+    for env in ({}, {"BA_FORCE_SIDE": "1"}):
+        for k, v in env.items():
+            os.environ[k] = v
+        try:
+            g = make_gpu(pr)
+        finally:
+            for k in env:
+                os.environ.pop(k, None)
+        g.enable_stage_timing(True)
+        g.lm_begin(make_options(max_iter=10, thr_step=0, thr_cost=0))
+        seen, done = [], 0
+        for n in (1, 2):
+            g.lm_iterate(n)
+            done += n
+            assert g.lm_sync()[1] == done
+            km = g.get_kernel_ms(reset=False)
+            seen.append({k: km[k][1] for k in ("k_pose_finalize", "k_dense_init", "k_lin_poses")})
+        print("launches after 1 and 3 iterations", env, seen)
+        assert seen[1]["k_lin_poses"] == 0
+        growth[bool(env)] = {k: seen[1][k] - seen[0][k] for k in ("k_pose_finalize", "k_dense_init")}
+    later_iterations = 2
+    assert growth[False] == {"k_pose_finalize": 0, "k_dense_init": 0}
+    assert growth[True] == {"k_pose_finalize": later_iterations, "k_dense_init": later_iterations}
 
 
 def _compare_solve(pr, iters=6, tol_cost=1e-7, tol_par=1e-6):

@@ -112,3 +112,19 @@ def test_residency_check_names_exactly_the_pointers_inside_an_arena(tmp_path):
                     os.path.join(ROOT, "tests", "cpp", "residency_check.cpp"), "-o", exe], check=True)
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0 and "RESIDENCY CHECK OK" in r.stdout, r.stdout[-3000:]
+
+
+def test_knob_record_follows_the_environment_at_every_read(tmp_path):
+    """csrc/ba_knobs.h Knobs::from_env, the one read of the BA_* variables that ba_create
+    keeps on the handle: in ONE process (tests/cpp/knobs_check.cpp, which first unsets the
+    BA_* variables it was started with), a clean environment gives the default-constructed
+    record, each variable in turn changes exactly its own
+    field, and after unsetenv the default is back — no value survives in a static from an
+    earlier read."""
+    exe = str(tmp_path / "knobs_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", CSRC,
+                    os.path.join(ROOT, "tests", "cpp", "knobs_check.cpp"),
+                    os.path.join(CSRC, "ba_dense_sched.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], env=dict(os.environ, BA_FORCE_SIDE="1", BA_DENSE_NB="32"),
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and "KNOBS CHECK OK" in r.stdout, r.stdout[-3000:]

@@ -1,6 +1,6 @@
 """Developer aid: where ba_finalize spends its time (BA_PLAN_TIMES laps) at a bench
 configuration.  python tools/finalize_probe.py [C4 | C4@12 (scale)] [passes ...]
-(BA_PLAN_THREADS is read once per process: set it in the environment.)"""
+(BA_PLAN_THREADS is read at ba_create: every pass below runs with its own thread count.)"""
 import os
 import sys
 import time
