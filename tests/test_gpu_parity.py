@@ -12,6 +12,7 @@ from bundle_adjustment_solver_amd import scenes
 from bundle_adjustment_solver_amd._lib import make_options
 from bundle_adjustment_solver_amd.solver import BaProblem
 from oracle import oracle_py as O
+from split_cases import ragged_duplicate_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -453,20 +454,7 @@ def test_ragged_and_duplicate_observations(built):
     """Landmarks with one observation, several observations of one
     (camera, pose, landmark) triple, three cameras: the last-writer rule picks
     the W block, everything else sums."""
-    sc = scenes.hover_scene(20, 200, 3, seed=23, visible_frac=0.15)
-    # duplicate 50 observations (appended: they become the last writers)
-    rng = np.random.default_rng(5)
-    dup = rng.integers(0, sc["obs_pt"].size, 50)
-    for k in ("obs_cam", "obs_pose", "obs_pt", "obs_uv"):
-        sc[k] = np.concatenate([sc[k], sc[k][dup]])
-    # landmarks 0..9 keep a single observation, landmark 10 none at all
-    keep = np.ones(sc["obs_pt"].size, bool)
-    for i in range(10):
-        idx = np.nonzero(sc["obs_pt"] == i)[0]
-        keep[idx[1:]] = False
-    keep[sc["obs_pt"] == 10] = False
-    for k in ("obs_cam", "obs_pose", "obs_pt", "obs_uv"):
-        sc[k] = sc[k][keep]
+    sc = ragged_duplicate_scene()
     pr = scenes.scaled_problem(sc)
     cnt = np.bincount(pr["obs_pt"], minlength=200)
     assert (cnt[:10] == 1).all() and cnt[10] == 0

@@ -1,12 +1,15 @@
 """Observation streaming (include/ba_hip.h ba_stream_*): the LM
 loop over landmark chunks that pass through a bounded device arena, against the
-resident solve of the same problem."""
+resident solve of the same problem and, on the small scenes, against the CPU oracle
+(tests/test_gpu_split_parity.py runs the streamed loop on the harder scenes)."""
 import numpy as np
 import pytest
 
+import split_cases
 from bundle_adjustment_solver_amd import scenes
 from bundle_adjustment_solver_amd._lib import BaError, make_options
 from bundle_adjustment_solver_amd.solver import BaProblem, BaStream
+from oracle import oracle_py as O
 
 pytestmark = pytest.mark.gpu
 
@@ -33,9 +36,21 @@ def same_rows(rows, frows, rtol=1e-11):
         assert abs(a.cost - b.cost) <= rtol * abs(b.cost), k
 
 
+def same_as_oracle(st, rows, conv, pr, **opt):
+    """The streamed run against the oracle's solve of the same problem: the trajectory
+    check of test_gpu_parity.assert_same_trajectory plus the converged flag, final
+    poses and points to 1e-6."""
+    o = O.Oracle(pr)
+    orows, oconv = o.solve(O.make_options(**opt))
+    ref = split_cases.Result(split_cases.to_rows(orows), oconv, o.get_poses(), o.get_points())
+    res = split_cases.Result(split_cases.to_rows(rows), conv, st.get_poses(), st.get_points())
+    split_cases.check_against_oracle(res, ref, 1e-6)
+
+
 def test_streamed_chunks_with_masked_groups(built):
     """Streaming over a scene with irregular visibility (15 % of the observations dropped:
-    superset groups with padded slots / pairs in every chunk) equals the resident solve."""
+    superset groups with padded slots / pairs in every chunk) equals the resident solve
+    and the oracle's."""
     sc = scenes.synthetic_ba_scene(40, 6000, 5, True, seed=43, pixel_sigma=0.2, dropout=0.15)
     pr = scenes.scaled_problem(sc)
     opt = make_options(max_iter=10, thr_step=0, thr_cost=0)
@@ -43,18 +58,21 @@ def test_streamed_chunks_with_masked_groups(built):
     assert full.get_mask_info()["masked_landmarks"] > 0
     frows, _ = full.solve(opt)
     st = load(BaStream(0, 3, 64 << 20), pr)
-    rows, _ = st.solve(opt)
+    rows, conv = st.solve(opt)
     same_rows(rows, frows)
     assert relerr(st.get_poses(), full.get_poses()) < 1e-9
     assert relerr(st.get_points(), full.get_points()[0]) < 1e-9
+    same_as_oracle(st, rows, conv, pr, max_iter=10, thr_step=0, thr_cost=0)
 
 
 @pytest.mark.parametrize("chunks", [1, 2, 5])
 def test_streamed_chunks_match_resident_solve_small(chunks, built):
-    """Small stereo scene with pixel noise (rejected steps on the way), a fixed and an
-    unobserved landmark: 1, 2 and 5 chunks (odd / even arena assignment, a chunk
-    count above the number of arenas) reproduce the resident trajectory to 1e-11 and
-    the final parameters to 1e-9."""
+    """Small stereo scene with pixel noise, a fixed and an unobserved landmark: 1, 2
+    and 5 chunks (odd / even arena assignment, a chunk count above the number of
+    arenas) reproduce the resident trajectory to 1e-11 and the final parameters to
+    1e-9, and the oracle's trajectory and parameters.  Every one of the 14 steps is
+    accepted on this scene; rejected steps under a split are cases A and B of
+    tests/split_cases.py (test_gpu_split_parity.py)."""
     sc = scenes.synthetic_ba_scene(30, 2000, 5, True, seed=23, pixel_sigma=0.3)
     sc["pt_fixed"][5] = True
     pr = scenes.scaled_problem(sc)
@@ -65,10 +83,11 @@ def test_streamed_chunks_match_resident_solve_small(chunks, built):
     full = load(BaProblem(0), pr)
     frows, _ = full.solve(opt)
     st = load(BaStream(0, chunks, 32 << 20), pr)
-    rows, _ = st.solve(opt)
+    rows, conv = st.solve(opt)
     same_rows(rows, frows)
     assert relerr(st.get_poses(), full.get_poses()) < 1e-9
     assert relerr(st.get_points(), full.get_points()[0]) < 1e-9
+    same_as_oracle(st, rows, conv, pr, max_iter=14, thr_step=0, thr_cost=0)
     # a second solve continues from the streamed state, like the resident handle does
     rows2, _ = st.solve(make_options(max_iter=3, thr_step=0, thr_cost=0))
     frows2, _ = full.solve(make_options(max_iter=3, thr_step=0, thr_cost=0))
