@@ -9,7 +9,8 @@ from .solver import (BaProblem, Camera, FullBundleAdjustmentSolver,  # noqa
                      FullBundleAdjustmentSolverRefactor,
                      IterationStatus, OptimizationInfo, Options,
                      PoseOnlyBundleAdjustmentSolver, SolverType, Summary,
-                     covariance_to_user_units, marginal_to_user_units)
+                     covariance_to_user_units, marginal_to_user_units,
+                     prior_constant, prior_to_scaled_units, se3_log)
 from . import scenes  # noqa
 from . import scene_io  # noqa
 
@@ -17,4 +18,5 @@ __all__ = ["BaProblem", "Camera", "FullBundleAdjustmentSolver",
            "FullBundleAdjustmentSolverRefactor",
            "IterationStatus", "OptimizationInfo", "Options",
            "PoseOnlyBundleAdjustmentSolver", "SolverType", "Summary",
-           "covariance_to_user_units", "marginal_to_user_units", "scenes", "scene_io"]
+           "covariance_to_user_units", "marginal_to_user_units", "prior_constant",
+           "prior_to_scaled_units", "se3_log", "scenes", "scene_io"]

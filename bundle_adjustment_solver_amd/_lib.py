@@ -258,6 +258,9 @@ SIGNATURES = {
     "ba_batch_marg_layout": (C.c_int, [_P, _U8, _I64, _I64]),
     "ba_batch_marg_plan_problem": (C.c_int, [C.c_int, _U8, _U8, C.c_int, _U8, C.c_int64,
                                              _I32, _I32, _I32, _U8]),
+    "ba_batch_set_prior": (C.c_int, [_P, _I32, _I32, _D, _D, _D, _D]),
+    "ba_batch_prior_check": (C.c_int, [C.c_int, _I32, _U8, _I32, _I32, _D, _D, _D, _D]),
+    "ba_batch_prior_info": (C.c_int, [_P, _I64]),
     "ba_batch_update_values": (C.c_int, [_P, _D, _D]),
     "ba_batch_get_poses": (C.c_int, [_P, _D]),
     "ba_batch_get_points": (C.c_int, [_P, _D]),
@@ -296,8 +299,11 @@ def _preload_shared_hip_runtime():
                 return
 
 
-def load():
-    """Load libba_hip.so and attach the C-ABI signatures (raises if absent)."""
+def load(optional=()):
+    """Load libba_hip.so and attach the C-ABI signatures (raises if absent).
+    optional: names of SIGNATURES that the library may lack (a tool that times a library
+    built from an earlier commit, named by BA_HIP_LIB); a missing one is skipped and
+    has_symbol tells which are there.  Every other missing symbol is an error."""
     global _lib
     if _lib is not None:
         return _lib
@@ -310,11 +316,18 @@ def load():
     _preload_shared_hip_runtime()
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
+        if name in optional and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
         fn.restype = res
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def has_symbol(name):
+    """whether the loaded library exports `name`"""
+    return hasattr(load(), name)
 
 
 class BaError(RuntimeError):

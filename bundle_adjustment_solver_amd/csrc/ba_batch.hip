@@ -31,6 +31,12 @@
 // the factorisation after them (chol_lds_partial): the trailing update is the prior the
 // window leaves on its kept poses.
 //
+// A pose prior per problem (ba_batch_set_prior): the Gaussian 1/2 d^T H d - b^T d + c / 2 on
+// K of its optimisable poses, d_j = se3_log(T_j T_lin,j^-1), is one more factor of all three
+// kernels (batch_prior_lin / batch_prior_offdiag / batch_prior_cost below).  H stays in
+// global memory; the branch is uniform per workgroup and a problem without a prior executes
+// none of it.
+//
 // Host side: ba_batch_create plans the structure once (stable landmark-major grouping,
 // pair lists, last-writer marks, one upload); ba_batch_solve is one launch and one sync.
 #include <hip/hip_runtime.h>
@@ -60,6 +66,12 @@ struct BatchProb {  // one problem: sizes and element offsets into the concatena
   int64_t m0, tab0, pobs0, pptr0;         // opt landmarks, M*N table, pose-major list, its N+1 pointers
 };
 
+struct BatchPrior {  // the prior of one problem: K poses from pose k0 of the prior arrays
+  int64_t H_off, k0;
+  double c;
+  int32_t K, pad_;
+};
+
 struct BatchDev {
   const BatchProb *prob;
   const double *cams;    // 16 per camera: fx fy cx cy R_cj t_cj
@@ -75,6 +87,11 @@ struct BatchDev {
   const int32_t *tab;      // per (optimisable landmark, optimisable pose): pair or -1
   const int32_t *pobs;     // per optimisable pose, landmark-major: observation (problem-local)
   const int32_t *pobs_ptr;
+  // the pose priors (ba_batch_set_prior); prior == nullptr: none set
+  const BatchPrior *prior;  // per problem
+  const int2 *prior_j;      // per prior pose: {pose (problem-local), optimisable index}
+  const double *prior_T;    // 12 per prior pose: T_lin
+  const double *prior_H, *prior_b;
   // scratch
   double *C6, *b3, *Cinv6, *Cinvb3, *W18;
   DevIterRec *rows;
@@ -96,6 +113,7 @@ struct BatchLds {
   double P[2][kBatchMaxPoses * 12];
   double A[kBatchMaxOpt * 36];
   double a[kBatchMaxOpt * 6];
+  double pd[kTailCols], pg[kTailCols];  // prior: tangents delta, gradient g = b - H delta
   double red[8];
   double bc[4];  // trial cost, model estimate, sum |y|, sum |x| (thread 0 -> control step)
   DevCtrl ctrl;
@@ -327,6 +345,106 @@ __device__ __forceinline__ void batch_schur(const int N, const int M, const doub
   }
 }
 
+// ---- the pose prior of one problem, shared by the three kernels ---------------------------
+// H(r, c) of the symmetric prior matrix, n = 6 K columns: only the lower triangle is read
+__device__ __forceinline__ double prior_h(const double *H, const int n, const int r, const int c) {
+  return r >= c ? H[(size_t)r * n + c] : H[(size_t)c * n + r];
+}
+
+// delta_t = se3_log(T_j T_lin,t^-1) of every prior pose at the poses P -> pd (no barrier)
+__device__ __forceinline__ void batch_prior_delta(const int K, const int2 *pj, const double *Tl, const double *P,
+                                                  double *pd) {
+  for (int t = threadIdx.x; t < K; t += kBatchBlock) {
+    const double *T = P + pj[t].x * 12, *L = Tl + (size_t)t * 12;
+    double R[9], tt[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)  // R_j R_lin^T
+        R[r * 3 + c] = T[r * 3 + 0] * L[c * 3 + 0] + T[r * 3 + 1] * L[c * 3 + 1] + T[r * 3 + 2] * L[c * 3 + 2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) tt[r] = T[9 + r] - (R[r * 3 + 0] * L[9] + R[r * 3 + 1] * L[10] + R[r * 3 + 2] * L[11]);
+    se3_log(R, tt, pd + 6 * t);
+  }
+}
+
+// Part 1, after batch_pose_pass: delta and g = b - H delta into LDS (one thread per row, the
+// columns in ascending order), then H_jj into A_j and g_j into a_j: the prior's diagonal is
+// damped with the rest of A_j.  Ends with a barrier.
+__device__ __forceinline__ void batch_prior_lin(const int K, const int2 *pj, const double *Tl, const double *H,
+                                                const double *b, const double *P, double *pd, double *pg, double *A,
+                                                double *a) {
+  const int tid = threadIdx.x, n = 6 * K;
+  batch_prior_delta(K, pj, Tl, P, pd);
+  __syncthreads();
+  for (int r = tid; r < n; r += kBatchBlock) {
+    double acc = 0.0;
+    for (int c = 0; c < n; ++c) acc += prior_h(H, n, r, c) * pd[c];
+    pg[r] = b[r] - acc;
+  }
+  __syncthreads();
+  for (int e = tid; e < 36 * K; e += kBatchBlock) {
+    const int t = e / 36, rc = e - 36 * t, r = rc / 6, c = rc - 6 * r;
+    A[pj[t].y * 36 + rc] += prior_h(H, n, 6 * t + r, 6 * t + c);
+  }
+  for (int r = tid; r < n; r += kBatchBlock) {
+    const int t = r / 6;
+    a[pj[t].y * 6 + r - 6 * t] += pg[r];
+  }
+  __syncthreads();
+}
+
+// Part 2, after batch_schur and a barrier: the off-diagonal blocks H_tu, t > u, undamped,
+// into the lower triangle of the image; one thread per element.  The prior poses ascend, so
+// without a column map the block lies below the diagonal; with one (PERM) an element the
+// map puts above it is stored transposed, as batch_schur<PERM> does.
+template <int LS, bool PERM>
+__device__ __forceinline__ void batch_prior_offdiag(const int K, const int2 *pj, const double *H, double *Lb,
+                                                    const uint8_t *col0 = nullptr) {
+  const int n = 6 * K, n_el = 18 * K * (K - 1);
+  for (int e = threadIdx.x; e < n_el; e += kBatchBlock) {
+    const int blk = e / 36, rc = e - 36 * blk, r = rc / 6, c = rc - 6 * r;
+    int t = 1;
+    while ((t * (t + 1)) / 2 <= blk) ++t;  // blk = t (t - 1) / 2 + u, u < t
+    const int u = blk - (t * (t - 1)) / 2;
+    const int jt = pj[t].y, ju = pj[u].y;
+    const int row = (PERM ? col0[jt] : 6 * jt) + r, col = (PERM ? col0[ju] : 6 * ju) + c;
+    Lb[PERM && row < col ? row * LS + col : col * LS + row] += H[(size_t)(6 * t + r) * n + 6 * u + c];
+  }
+}
+
+// The prior's residual norm sqrt(max(0, d^T H d - 2 b^T d + c)) at the poses P; the rows are
+// dealt to the threads, one block_sum; valid in thread 0.  pd is overwritten.
+__device__ __forceinline__ double batch_prior_cost(const int K, const int2 *pj, const double *Tl, const double *H,
+                                                   const double *b, const double c, const double *P, double *pd,
+                                                   double *red) {
+  const int n = 6 * K;
+  __syncthreads();
+  batch_prior_delta(K, pj, Tl, P, pd);
+  __syncthreads();
+  double e = 0.0;
+  for (int r = threadIdx.x; r < n; r += kBatchBlock) {
+    double acc = 0.0;
+    for (int cc = 0; cc < n; ++cc) acc += prior_h(H, n, r, cc) * pd[cc];
+    e += pd[r] * acc - 2.0 * (b[r] * pd[r]);
+  }
+  const double q = block_sum(e, red);
+  return sqrt(fmax(0.0, q + c));
+}
+
+// the cross term 2 sum_{t > u} x_t^T H_tu x_u of the quadratic model, one row per thread
+__device__ __forceinline__ double batch_prior_cross(const int K, const int2 *pj, const double *H, const double *xs) {
+  const int n = 6 * K;
+  double est = 0.0;
+  for (int r = threadIdx.x; r < n; r += kBatchBlock) {
+    const int t = r / 6;
+    double acc = 0.0;
+    for (int cc = 0; cc < 6 * t; ++cc) acc += H[(size_t)r * n + cc] * xs[6 * pj[cc / 6].y + cc % 6];
+    est += 2.0 * (xs[6 * pj[t].y + r - 6 * t] * acc);
+  }
+  return est;
+}
+
 template <int NPt>
 __global__ __launch_bounds__(kBatchBlock) void k_ba_batch(BatchDev d) {
   using LDS = BatchLds<NPt>;
@@ -346,6 +464,11 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch(BatchDev d) {
     return;
   }
   const int N = pr.N, M = pr.M, n6 = 6 * N;
+  // the prior of this problem (uniform per workgroup); Kp = 0: none
+  const BatchPrior pp = d.prior ? d.prior[blockIdx.x] : BatchPrior{0, 0, 0.0, 0, 0};
+  const int Kp = pp.K;
+  const int2 *pj = d.prior_j + pp.k0;
+  const double *pTl = d.prior_T + pp.k0 * 12, *pH = d.prior_H + pp.H_off, *pb = d.prior_b + pp.k0 * 6;
   double *Pg = d.poses + pr.pose0 * 12;
   double *X0 = d.pts[0] + pr.pt0 * 3, *X1 = d.pts[1] + pr.pt0 * 3;
   // ---- stage the problem; refuse non-finite parameters -------------------------------
@@ -399,7 +522,11 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch(BatchDev d) {
   }
   // ---- initial cost (reference :707-708) ----------------------------------------------
   {
-    const double c0 = batch_cost(d, pr, s, 0);
+    double c0 = batch_cost(d, pr, s, 0);
+    if (Kp) {
+      const double pc = batch_prior_cost(Kp, pj, pTl, pH, pb, pp.c, s.P[0], s.pd, s.red);
+      c0 += pc;
+    }
     if (tid == 0) {
       s.ctrl.prev_cost = c0;
       s.ctrl.t_last = wall_clock64();
@@ -429,6 +556,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch(BatchDev d) {
       batch_landmark_pass(M, opt_lm, lm_ptr, ob, uvp, s.cams, Pc, X, huber, C6, b3, Wg);
       batch_pose_pass(N, d.pobs_ptr + pr.pptr0, d.pobs + pr.pobs0, ob, uvp, s.cams, Pc, X, huber, s.A, s.a);
       __syncthreads();
+      if (Kp) batch_prior_lin(Kp, pj, pTl, pH, pb, Pc, s.pd, s.pg, s.A, s.a);
     }
     // ---- damp and invert (reference :846-856); reset the LDS image --------------------
     batch_damp_invert(M, lp1, C6, b3, Ci6, Cib3);
@@ -437,6 +565,10 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch(BatchDev d) {
     // ---- Schur complement (reference :858-888), lower triangle, into the LDS image ----
     batch_schur<nbt, LS>(N, M, lp1, tab, Ci6, Cib3, Wg, s.blk_j, s.blk_k, s.A, s.a, s.Lb);
     __syncthreads();
+    if (Kp > 1) {
+      batch_prior_offdiag<LS, false>(Kp, pj, pH, s.Lb);
+      __syncthreads();
+    }
     // ---- reduced solve (reference :905) ------------------------------------------------
     chol_lds_factor_solve<NPt, false, LS>(s.Lb, s.Eb, s.xs, &res->dropped_pivots);
     __syncthreads();
@@ -506,6 +638,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch(BatchDev d) {
       estp += e + qd;
       sx += sqrt(v0 * v0 + v1 * v1 + v2 * v2 + w0 * w0 + w1 * w1 + w2 * w2);
     }
+    if (Kp > 1) estp += batch_prior_cross(Kp, pj, pH, s.xs);
     block_sum2(est, sy, s.red);
     if (tid == 0) {
       s.bc[1] = est;
@@ -518,7 +651,11 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch(BatchDev d) {
     }
     __syncthreads();  // the trial parameters are complete
     // ---- trial cost, trust region, convergence, log row (reference :928-1007) ---------
-    const double tc = batch_cost(d, pr, s, cur ^ 1);
+    double tc = batch_cost(d, pr, s, cur ^ 1);
+    if (Kp) {
+      const double pc = batch_prior_cost(Kp, pj, pTl, pH, pb, pp.c, Pt, s.pd, s.red);
+      tc += pc;
+    }
     if (tid == 0)
       lm_control_step(&s.ctrl, d.rows + (size_t)blockIdx.x * d.cap, d.cap, (double)pr.n_obs, N + M, tc, s.bc[1],
                       s.bc[2], s.bc[3]);
@@ -556,6 +693,7 @@ struct BatchCovLds {
   double P[kBatchMaxPoses * 12];
   double A[kBatchMaxOpt * 36];
   double a[kBatchMaxOpt * 6];
+  double pd[kTailCols], pg[kTailCols];  // prior: tangents delta, gradient g = b - H delta
   int32_t jopt[kBatchMaxPoses];
   uint8_t blk_j[kBatchMaxBlk], blk_k[kBatchMaxBlk];
 };
@@ -591,6 +729,11 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch_cov(BatchDev d, BatchC
     return;
   }
   const int N = pr.N, M = pr.M, n6 = 6 * N;
+  // the prior of this problem (uniform per workgroup); Kp = 0: none
+  const BatchPrior pp = d.prior ? d.prior[blockIdx.x] : BatchPrior{0, 0, 0.0, 0, 0};
+  const int Kp = pp.K;
+  const int2 *pj = d.prior_j + pp.k0;
+  const double *pTl = d.prior_T + pp.k0 * 12, *pH = d.prior_H + pp.H_off, *pb = d.prior_b + pp.k0 * 6;
   const double *Pg = d.poses + pr.pose0 * 12;
   const double *X = d.pts[0] + pr.pt0 * 3;
   // ---- stage the problem; refuse non-finite parameters -------------------------------
@@ -630,11 +773,16 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch_cov(BatchDev d, BatchC
   batch_landmark_pass(M, opt_lm, lm_ptr, ob, uvp, s.cams, s.P, X, o.huber, C6, b3, Wg);
   batch_pose_pass(N, d.pobs_ptr + pr.pptr0, d.pobs + pr.pobs0, ob, uvp, s.cams, s.P, X, o.huber, s.A, s.a);
   __syncthreads();
+  if (Kp) batch_prior_lin(Kp, pj, pTl, pH, pb, s.P, s.pd, s.pg, s.A, s.a);
   batch_damp_invert(M, 1.0, C6, b3, Ci6, Cib3);
   batch_reset_image<nbt, LS>(s.Lb, n6);
   __syncthreads();
   batch_schur<nbt, LS>(N, M, 1.0, d.tab + pr.tab0, Ci6, Cib3, Wg, s.blk_j, s.blk_k, s.A, s.a, s.Lb);
   __syncthreads();
+  if (Kp > 1) {
+    batch_prior_offdiag<LS, false>(Kp, pj, pH, s.Lb);
+    __syncthreads();
+  }
   chol_lds_factor_solve<NPt, false, LS>(s.Lb, s.Eb, s.xs, &res->dropped_pivots);
   __syncthreads();
   chol_lds_inverse<NPt, LS>(s.Lb, s.Eb);  // ends with a barrier: the lower triangle holds S^-1
@@ -724,6 +872,7 @@ struct BatchMargLds {
   double P[kBatchMaxPoses * 12];
   double A[kBatchMaxOpt * 36];
   double a[kBatchMaxOpt * 6];
+  double pd[kTailCols], pg[kTailCols];  // prior: tangents delta, gradient g = b - H delta
   int32_t jopt[kBatchMaxPoses];
   int32_t n_sel;
   uint8_t marg[kBatchMaxPoses];
@@ -773,6 +922,11 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch_marg(BatchDev d, Batch
     return;
   }
   const int N = pr.N, M = pr.M, K = mp.K, K6 = 6 * K;
+  // the prior of this problem (uniform per workgroup); Kp = 0: none
+  const BatchPrior pp = d.prior ? d.prior[blockIdx.x] : BatchPrior{0, 0, 0.0, 0, 0};
+  const int Kp = pp.K;
+  const int2 *pj = d.prior_j + pp.k0;
+  const double *pTl = d.prior_T + pp.k0 * 12, *pH = d.prior_H + pp.H_off, *pb = d.prior_b + pp.k0 * 6;
   const int T = (6 * mp.m + 15) >> 4;
   const double *Pg = d.poses + pr.pose0 * 12;
   const double *X = d.pts[0] + pr.pt0 * 3;
@@ -846,6 +1000,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch_marg(BatchDev d, Batch
   batch_landmark_pass(M, opt_lm, lm_ptr, ob, uvp, s.cams, s.P, X, o.huber, C6, b3, Wg, sel);
   batch_pose_pass(N, d.pobs_ptr + pr.pptr0, d.pobs + pr.pobs0, ob, uvp, s.cams, s.P, X, o.huber, s.A, s.a, sel);
   __syncthreads();
+  if (Kp) batch_prior_lin(Kp, pj, pTl, pH, pb, s.P, s.pd, s.pg, s.A, s.a);
   batch_damp_invert(M, 1.0, C6, b3, Ci6, Cib3, opt_lm, sel);
   for (int e = tid; e < nbt * LS; e += kBatchBlock) {  // zero; unit diagonal on the padding of the marked tiles
     const int c = e / LS, r = e - c * LS;
@@ -855,6 +1010,10 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch_marg(BatchDev d, Batch
   batch_schur<nbt, LS, true>(N, M, 1.0, d.tab + pr.tab0, Ci6, Cib3, Wg, s.blk_j, s.blk_k, s.A, s.a, s.Lb, opt_lm,
                              sel, s.col0);
   __syncthreads();
+  if (Kp > 1) {
+    batch_prior_offdiag<LS, true>(Kp, pj, pH, s.Lb, s.col0);
+    __syncthreads();
+  }
   chol_lds_partial<NPt, LS>(s.Lb, s.Eb, T, &res->dropped_pivots);  // ends with a barrier
   // ---- the prior: one triangle, mirrored -------------------------------------------------
   double *H = o.H + mp.H_off;
@@ -866,6 +1025,11 @@ __global__ __launch_bounds__(kBatchBlock) void k_ba_batch_marg(BatchDev d, Batch
   for (int t = tid; t < K6; t += kBatchBlock) o.bvec[mp.b_off + t] = s.Lb[(16 * T + t) * LS + nbt];
   if (tid == 0) res->status = 0;
 }
+
+// the widest instances must fit the 160 KiB of LDS a gfx950 workgroup can hold
+static_assert(sizeof(BatchLds<6>) <= 160 * 1024, "k_ba_batch<6> exceeds the LDS of a workgroup");
+static_assert(sizeof(BatchCovLds<6>) <= 160 * 1024, "k_ba_batch_cov<6> exceeds the LDS of a workgroup");
+static_assert(sizeof(BatchMargLds<7>) <= 160 * 1024, "k_ba_batch_marg<7> exceeds the LDS of a workgroup");
 
 }  // namespace
 }  // namespace ba
@@ -893,6 +1057,9 @@ struct ba_batch {
   std::vector<int32_t> jopt;  // per pose of the batch: optimisable index or -1 (host copy)
   char *marg = nullptr;       // inputs and outputs of ba_batch_marginalize (grown on demand)
   size_t marg_bytes = 0;
+  char *prior = nullptr;  // the pose priors (ba_batch_set_prior): records | poses | T_lin | H | b
+  size_t prior_bytes = 0;
+  int64_t prior_n = 0, prior_K = 0;  // problems with a prior in effect, their poses
 };
 
 namespace {
@@ -1014,6 +1181,41 @@ int marg_plan_batch(const ba_batch *b, const uint8_t *marg_pose, std::vector<ba:
     if (P.status == 0) tiles = std::max(tiles, (16 * ((6 * m + 15) / 16) + 6 * K + 15) / 16);
   }
   return tiles;
+}
+
+// Validation shared by ba_batch_set_prior and ba_batch_prior_check (host only).  n_pose_of(p)
+// and fixed(p, q) describe the batch; who prefixes the message.
+template <class NP, class FX>
+int prior_validate(const char *who, int B, NP n_pose_of, FX fixed, const int32_t *prior_off,
+                   const int32_t *prior_pose, const double *T_lin12, const double *H, const double *bvec,
+                   const double *c) {
+  const std::string w = std::string(who) + ": ";
+  if (!prior_off) return fail(w + "null prior_off");
+  if (prior_off[0] != 0) return fail(w + "prior_off[0] must be 0");
+  for (int p = 0; p < B; ++p)
+    if (prior_off[p + 1] < prior_off[p])
+      return fail(w + "prior_off must not decrease (problem " + std::to_string(p) + ")");
+  if (prior_off[B] > 0 && (!prior_pose || !T_lin12 || !H || !bvec)) return fail(w + "null prior array");
+  int64_t ho = 0;
+  for (int p = 0; p < B; ++p) {
+    const int k0 = prior_off[p], K = prior_off[p + 1] - k0;
+    const std::string at = " (problem " + std::to_string(p) + ")";
+    for (int t = 0; t < K; ++t) {
+      const int q = prior_pose[k0 + t];
+      if (q < 0 || q >= n_pose_of(p)) return fail(w + "prior pose " + std::to_string(q) + " out of range" + at);
+      if (t > 0 && q <= prior_pose[k0 + t - 1]) return fail(w + "prior poses must ascend strictly" + at);
+      if (fixed(p, q)) return fail(w + "prior pose " + std::to_string(q) + " is fixed" + at);
+    }
+    for (int64_t e = 0; e < (int64_t)12 * K; ++e)
+      if (!std::isfinite(T_lin12[(int64_t)12 * k0 + e])) return fail(w + "T_lin is not finite" + at);
+    for (int64_t e = 0; e < (int64_t)36 * K * K; ++e)
+      if (!std::isfinite(H[ho + e])) return fail(w + "H is not finite" + at);
+    for (int64_t e = 0; e < (int64_t)6 * K; ++e)
+      if (!std::isfinite(bvec[(int64_t)6 * k0 + e])) return fail(w + "b is not finite" + at);
+    if (c && !(std::isfinite(c[p]) && c[p] >= 0.0)) return fail(w + "c must be finite and >= 0" + at);
+    ho += (int64_t)36 * K * K;
+  }
+  return 0;
 }
 
 size_t lds_bytes_of(int npt) {
@@ -1203,6 +1405,7 @@ void ba_batch_destroy(ba_batch *b) {
   if (b->rows) (void)hipFree(b->rows);
   if (b->cov) (void)hipFree(b->cov);
   if (b->marg) (void)hipFree(b->marg);
+  if (b->prior) (void)hipFree(b->prior);
   delete b;
 }
 
@@ -1233,6 +1436,93 @@ int ba_batch_get_points(ba_batch *b, double *X3) {
   HIP_TRY(hipMemcpyAsync(X3, b->d.pts[0], (size_t)b->n_pt * 3 * sizeof(double), hipMemcpyDeviceToHost,
                          b->h->stream));
   HIP_TRY(hipStreamSynchronize(b->h->stream));
+  return 0;
+}
+
+int ba_batch_prior_check(int B, const int32_t *pose_off, const uint8_t *pose_fixed, const int32_t *prior_off,
+                         const int32_t *prior_pose, const double *T_lin12, const double *H, const double *bvec,
+                         const double *c) {
+  if (B < 1) return fail("ba_batch_prior_check: B must be >= 1");
+  if (!pose_off) return fail("ba_batch_prior_check: null pose_off");
+  for (int p = 0; p < B; ++p)
+    if (pose_off[p + 1] < pose_off[p]) return fail("ba_batch_prior_check: pose_off must not decrease");
+  return prior_validate(
+      "ba_batch_prior_check", B, [&](int p) { return pose_off[p + 1] - pose_off[p]; },
+      [&](int p, int q) { return pose_fixed && pose_fixed[pose_off[p] + q] != 0; }, prior_off, prior_pose, T_lin12, H,
+      bvec, c);
+}
+
+int ba_batch_set_prior(ba_batch *b, const int32_t *prior_off, const int32_t *prior_pose, const double *T_lin12,
+                       const double *H, const double *bvec, const double *c) {
+  if (!b) return fail("ba_batch_set_prior: null batch");
+  const int B = b->B;
+  if (prior_off &&
+      prior_validate(
+          "ba_batch_set_prior", B, [&](int p) { return (int)b->prob[p].n_pose; },
+          [&](int p, int q) { return b->jopt[b->prob[p].pose0 + q] < 0; }, prior_off, prior_pose, T_lin12, H, bvec, c))
+    return -1;
+  HIP_TRY(hipSetDevice(b->h->device));
+  if (b->prior) (void)hipFree(b->prior);
+  b->prior = nullptr;
+  b->prior_bytes = 0;
+  b->prior_n = b->prior_K = 0;
+  b->d.prior = nullptr;
+  b->d.prior_j = nullptr;
+  b->d.prior_T = b->d.prior_H = b->d.prior_b = nullptr;
+  if (!prior_off) return 0;
+  // the priors in effect (a problem over a limit keeps none), packed: one host image, one upload
+  std::vector<ba::BatchPrior> rec(B);
+  std::vector<int2> pj;
+  std::vector<double> Tl, Hh, bb;
+  int64_t ho = 0, n_on = 0, K_on = 0;
+  for (int p = 0; p < B; ++p) {
+    const int k0 = prior_off[p], K = prior_off[p + 1] - k0;
+    const bool on = K > 0 && b->prob[p].status == 0;
+    rec[p] = ba::BatchPrior{(int64_t)Hh.size(), (int64_t)pj.size(), on && c ? c[p] : 0.0, on ? K : 0, 0};
+    if (on) {
+      for (int t = 0; t < K; ++t) {
+        const int q = prior_pose[k0 + t];
+        pj.push_back(make_int2(q, b->jopt[b->prob[p].pose0 + q]));
+      }
+      Tl.insert(Tl.end(), T_lin12 + (int64_t)12 * k0, T_lin12 + (int64_t)12 * (k0 + K));
+      Hh.insert(Hh.end(), H + ho, H + ho + (int64_t)36 * K * K);
+      bb.insert(bb.end(), bvec + (int64_t)6 * k0, bvec + (int64_t)6 * (k0 + K));
+      n_on += 1;
+      K_on += K;
+    }
+    ho += (int64_t)36 * K * K;
+  }
+  if (n_on == 0) return 0;
+  std::vector<char> blob;
+  const size_t o_rec = put(blob, rec), o_pj = put(blob, pj), o_T = put(blob, Tl), o_H = put(blob, Hh),
+               o_b = put(blob, bb);
+  // the counts and the pointers are set last: after a failure below no prior is in effect
+  if (hipMalloc((void **)&b->prior, blob.size()) != hipSuccess) {
+    b->prior = nullptr;
+    return fail("ba_batch_set_prior: device allocation of " + std::to_string(blob.size()) + " bytes failed");
+  }
+  if (hipMemcpy(b->prior, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(b->prior);
+    b->prior = nullptr;
+    return fail("ba_batch_set_prior: upload failed");
+  }
+  b->prior_bytes = blob.size();
+  b->prior_n = n_on;
+  b->prior_K = K_on;
+  b->d.prior = (const ba::BatchPrior *)(b->prior + o_rec);
+  b->d.prior_j = (const int2 *)(b->prior + o_pj);
+  b->d.prior_T = (const double *)(b->prior + o_T);
+  b->d.prior_H = (const double *)(b->prior + o_H);
+  b->d.prior_b = (const double *)(b->prior + o_b);
+  return 0;
+}
+
+int ba_batch_prior_info(ba_batch *b, int64_t out4[4]) {
+  if (!b || !out4) return fail("ba_batch_prior_info: null argument");
+  out4[0] = b->prior_n;
+  out4[1] = b->prior_K;
+  out4[2] = (int64_t)b->prior_bytes;
+  out4[3] = 0;
   return 0;
 }
 

@@ -331,6 +331,37 @@ __device__ __forceinline__ void se3_exp(const double v0, const double v1, const 
     dt[r] = V[r * 3 + 0] * v0 + V[r * 3 + 1] * v1 + V[r * 3 + 2] * v2;
 }
 
+// se3 logarithm, the inverse of se3_exp: x = (v, w) with exp(x) = [R, t].  theta from
+// atan2(|vee(R - R^T)| / 2, (tr R - 1) / 2), w = theta / (2 sin theta) vee(R - R^T),
+// v = V^-1 t with V^-1 = I - wx / 2 + k wx^2, k = (1 - theta sin theta / (2 (1 - cos theta)))
+// / theta^2 (evaluated from theta, not from the trace, which cancels at small angles); below se3_exp's threshold theta < 1e-7 the series w = vee(R - R^T) / 2,
+// k = 1 / 12.  Defined for theta < pi (sin theta -> 0 at pi): callers keep the tangent small.
+__device__ __forceinline__ void se3_log(const double R[9], const double t[3], double x[6]) {
+  const double a0 = R[7] - R[5], a1 = R[2] - R[6], a2 = R[3] - R[1];  // vee(R - R^T)
+  const double sn = 0.5 * sqrt(a0 * a0 + a1 * a1 + a2 * a2);
+  const double cs = 0.5 * (R[0] + R[4] + R[8] - 1.0);
+  const double theta = atan2(sn, cs);
+  double f, k;
+  if (theta < 1e-7) {
+    f = 0.5;
+    k = 0.08333333333333333333333333;
+  } else {
+    const double hf = 0.5 * theta;  // theta sin theta / (2 (1 - cos theta)) = hf cot hf, from theta
+    f = theta / (2.0 * sn);
+    k = (1.0 - hf * cos(hf) / sin(hf)) / (theta * theta);
+  }
+  const double w0 = f * a0, w1 = f * a1, w2 = f * a2;
+  // wx t = w x t, wx^2 t = w x (w x t)
+  const double c0 = w1 * t[2] - w2 * t[1], c1 = w2 * t[0] - w0 * t[2], c2 = w0 * t[1] - w1 * t[0];
+  const double e0 = w1 * c2 - w2 * c1, e1 = w2 * c0 - w0 * c2, e2 = w0 * c1 - w1 * c0;
+  x[0] = t[0] - 0.5 * c0 + k * e0;
+  x[1] = t[1] - 0.5 * c1 + k * e1;
+  x[2] = t[2] - 0.5 * c2 + k * e2;
+  x[3] = w0;
+  x[4] = w1;
+  x[5] = w2;
+}
+
 // Trust region, convergence and iteration log (reference :928-1007) of ONE problem; one
 // thread.  c: the problem's controller, log / log_cap: its iteration rows, n_obs_all: every
 // observation of the problem, n_blocks: optimisable poses + optimisable landmarks.

@@ -242,6 +242,67 @@ def marginal_to_user_units(H, b, sigma_px):
     return w * (di[:, None] * H.reshape(6 * K, 6 * K) * di[None, :]), w * (di * b)
 
 
+def prior_to_scaled_units(H_u, b_u, c_u, sigma_px):
+    """A prior in the caller's units (what MarginalizeBatch returns, plus its constant)
+    -> (H, b, c) in scaled units with unit pixel noise, the input of BaBatch.set_prior:
+    the exact inverse of marginal_to_user_units.  With D^-1 = diag(0.01 I3, I3) per pose and
+    the weight w = 1 / (1e-4 sigma_px^2) of that function,
+        H = D H_u D / w,    b = D b_u / w,    c = c_u / w
+    (c is an energy like d^T H_u d: it carries the weight and no D)."""
+    H_u = np.asarray(H_u, np.float64)
+    b_u = np.asarray(b_u, np.float64)
+    K = b_u.shape[0] // 6
+    d = np.tile(np.r_[np.full(3, INVERSE_SCALER), np.ones(3)], K)
+    w = 1.0 / (float(sigma_px) ** 2 * SCALER * SCALER)
+    return (d[:, None] * H_u.reshape(6 * K, 6 * K) * d[None, :]) / w, (d * b_u) / w, float(c_u) / w
+
+
+PRIOR_RCOND = 1e-12
+
+
+def prior_constant(H, b, rcond=PRIOR_RCOND):
+    """c = b^T H^+ b of a prior (numpy, symmetric eigendecomposition of (H + H^T) / 2):
+    with it the prior's cost term sqrt(d^T H d - 2 b^T d + c) is zero at the prior's own
+    minimum.  H^+ inverts the eigenvalues above rcond * (the largest eigenvalue) and drops
+    the others (the gauge null space of a marginal; default rcond = 1e-12, four decades
+    above the rounding of the eigenvalues)."""
+    H = np.asarray(H, np.float64)
+    b = np.asarray(b, np.float64).reshape(-1)
+    if b.size == 0:
+        return 0.0
+    w, V = np.linalg.eigh(0.5 * (H + H.T))
+    keep = w > rcond * max(w.max(), 0.0)
+    y = V[:, keep].T @ b
+    return float(np.sum(y * y / w[keep]))
+
+
+def se3_log(T12):
+    """The device se3_log (csrc/ba_device_fn.h) restated in numpy: T12 = [R row-major, t]
+    -> x = [v; omega] with se3_exp(x) = T; defined for a rotation angle below pi."""
+    T12 = np.asarray(T12, np.float64).reshape(12)
+    R, t = T12[:9].reshape(3, 3), T12[9:]
+    a = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    sn = 0.5 * np.sqrt(a @ a)
+    cs = 0.5 * (np.trace(R) - 1.0)
+    theta = np.arctan2(sn, cs)
+    if theta < 1e-7:
+        f, k = 0.5, 1.0 / 12.0
+    else:
+        hf = 0.5 * theta
+        f = theta / (2.0 * sn)
+        k = (1.0 - hf * np.cos(hf) / np.sin(hf)) / (theta * theta)
+    w = f * a
+    c = np.cross(w, t)
+    return np.r_[t - 0.5 * c + k * np.cross(w, c), w]
+
+
+def prior_delta(T12, T_lin12):
+    """delta = se3_log(T T_lin^-1), the tangent the prior of BaBatch.set_prior acts on."""
+    T = _T12_to_44(T12)[0]
+    L = _T12_to_44(T_lin12)[0]
+    return se3_log(_T44_to_12(T @ rigid_inverse(L))[0])
+
+
 class BaProblem:
     """Thin numpy wrapper over one ba_handle, in the solver's SCALED units.
 
@@ -1163,6 +1224,49 @@ class BaBatch:
             kl.append(np.flatnonzero((self.pose_fixed[sl] == 0) & (m[sl] == 0)).astype(np.int32))
         return Hl, bl, kl, [res[p] for p in range(self.B)]
 
+    def set_prior(self, priors):
+        """One pose prior per problem (ba_batch_set_prior; scaled units).  priors: a list
+        with one entry per problem, each None or a dict with the keys
+          poses  problem-local user indices of K optimisable poses, strictly ascending,
+          H      (6K, 6K), only the lower triangle is read,   b  (6K,),
+          T_lin  (K, 12) the poses at which H and b were formed,   c  >= 0 (default 0).
+        The prior stays with the object until clear_prior or the next set_prior."""
+        if len(priors) != self.B:
+            raise ValueError("set_prior: one entry (or None) per problem (%d)" % self.B)
+        off = np.zeros(self.B + 1, np.int32)
+        pose, Tl, Hs, bs = [], [], [], []
+        c = np.zeros(self.B)
+        for p, pr in enumerate(priors):
+            K = 0
+            if pr is not None:
+                idx = np.asarray(pr["poses"], np.int32).reshape(-1)
+                K = idx.shape[0]
+                H = np.asarray(pr["H"], np.float64)
+                b = np.asarray(pr["b"], np.float64).reshape(-1)
+                T = np.asarray(pr["T_lin"], np.float64).reshape(-1, 12)
+                if H.shape != (6 * K, 6 * K) or b.shape != (6 * K,) or T.shape != (K, 12):
+                    raise ValueError("set_prior: problem %d needs H (6K, 6K), b (6K,), "
+                                     "T_lin (K, 12) for its K = %d poses" % (p, K))
+                pose.append(idx)
+                Tl.append(T.reshape(-1))
+                Hs.append(H.reshape(-1))
+                bs.append(b)
+                c[p] = float(pr.get("c", 0.0))
+            off[p + 1] = off[p] + K
+        cat = lambda xs, dt: np.ascontiguousarray(np.concatenate(xs or [np.zeros(0, dt)]), dt)
+        pose, Tl, Hs, bs = cat(pose, np.int32), cat(Tl, np.float64), cat(Hs, np.float64), cat(bs, np.float64)
+        check(self.lib.ba_batch_set_prior(self.b, _ip(off), _ip(pose), _dp(Tl), _dp(Hs), _dp(bs), _dp(c)),
+              "ba_batch_set_prior")
+
+    def clear_prior(self):
+        check(self.lib.ba_batch_set_prior(self.b, None, None, None, None, None, None),
+              "ba_batch_set_prior")
+
+    def prior_info(self):
+        o = (C.c_int64 * 4)()
+        check(self.lib.ba_batch_prior_info(self.b, o), "ba_batch_prior_info")
+        return dict(n_prior=int(o[0]), total_K=int(o[1]), device_bytes=int(o[2]))
+
     def cov_poses_of(self, p, cov_pose):
         return cov_pose[self.pose_off[p]:self.pose_off[p + 1]]
 
@@ -1670,13 +1774,51 @@ class FullBundleAdjustmentSolver:
         return self._finish_solve(rows, converged, summary, t0)
 
     @staticmethod
-    def SolveBatch(solvers, options, summaries=None):
+    def _scaled_priors(what, solvers, priors, sigma_pixel):
+        """priors of SolveBatch / ComputeCovarianceBatch / MarginalizeBatch -> the list
+        BaBatch.set_prior takes (scaled units), or None.  priors[k]: None, or a dict with
+        poses (pose objects or handles, optimisable; sorted here into registration order
+        together with the blocks of H and b), H and b (units of MarginalizeBatch for
+        `sigma_pixel`), lin_poses (one per pose, the convention of AddPose, converted as
+        AddPose converts) and c (default 0)."""
+        if priors is None:
+            return None
+        if len(priors) != len(solvers):
+            raise ValueError("%s: one prior (or None) per solver" % what)
+        out = []
+        for sv, pr in zip(solvers, priors):
+            if pr is None:
+                out.append(None)
+                continue
+            hs = []
+            for pose in pr["poses"]:
+                h = sv._pose_handle(pose)
+                if h is None:
+                    raise RuntimeError("There is no pointer in the BA pose pool.")
+                hs.append(h)
+            K = len(hs)
+            order = np.argsort(np.asarray(hs, np.int64), kind="stable")
+            cols = (6 * order[:, None] + np.arange(6)[None, :]).reshape(-1)
+            H, b, c = prior_to_scaled_units(np.asarray(pr["H"], np.float64).reshape(6 * K, 6 * K),
+                                            np.asarray(pr["b"], np.float64).reshape(6 * K),
+                                            pr.get("c", 0.0), sigma_pixel)
+            T_lin = rigid_inverse(np.asarray(pr["lin_poses"], np.float64).reshape(K, 4, 4))
+            T_lin[:, :3, 3] *= SCALER
+            out.append(dict(poses=np.asarray(hs, np.int32)[order], H=H[np.ix_(cols, cols)], b=b[cols],
+                            T_lin=_T44_to_12(T_lin)[order], c=c))
+        return out
+
+    @staticmethod
+    def SolveBatch(solvers, options, summaries=None, priors=None, sigma_pixel=1.0):
         """Solve the registered problems of several solver objects in ONE launch
         (ba_batch_solve: one persistent workgroup per problem, see BaBatch for the
         limits), write every solver's poses and points back as Solve does and fill
         one Summary each (summaries: a list as long as `solvers`, or None).  Returns
         the per-problem BaBatchResult list; a problem whose status is not 0 (over a
-        limit, non-finite input) is left untouched."""
+        limit, non-finite input) is left untouched.  priors (default None: none):
+        one pose prior per solver taken in as one more factor (BaBatch.set_prior), see
+        _scaled_priors for the dict; H and b in the units MarginalizeBatch returns for
+        `sigma_pixel`."""
         t0 = time.perf_counter()
         solvers = list(solvers)
         if not solvers:
@@ -1694,8 +1836,11 @@ class FullBundleAdjustmentSolver:
             sv.CheckPoseAndPointConnectivity()
         c_opt = options.to_c()
         c_opt.gauss_newton = 1 if solvers[0]._use_gauss_newton(options) else 0
+        sp = FullBundleAdjustmentSolver._scaled_priors("SolveBatch", solvers, priors, sigma_pixel)
         batch = BaBatch(probs, solvers[0].device)
         try:
+            if sp is not None:
+                batch.set_prior(sp)
             rows, res = batch.solve(c_opt)
             T_all, X_all = batch.get_poses(), batch.get_points()
             for k, sv in enumerate(solvers):
@@ -1722,14 +1867,15 @@ class FullBundleAdjustmentSolver:
         return res
 
     @staticmethod
-    def ComputeCovarianceBatch(solvers, sigma_pixel=1.0, options=None, points=True):
+    def ComputeCovarianceBatch(solvers, sigma_pixel=1.0, options=None, points=True, priors=None):
         """(new) Covariance blocks of the CURRENT registered values of several
         solver objects in ONE launch (ba_batch_covariance; see BaBatch for the
         limits).  Returns one (cov_pose (n_pose, 6, 6), cov_point (n_pt, 3, 3) or
         None, BaBatchCovResult) per solver: ALL poses and points in registration
         order, the blocks of fixed members zero, units and conventions those of
         ComputeCovariance.  A result whose status is not 0 (over a limit,
-        non-finite input) has zero blocks; dropped_pivots > 0 means S was singular."""
+        non-finite input) has zero blocks; dropped_pivots > 0 means S was singular.
+        priors: as in SolveBatch; the covariance then includes the past."""
         solvers = list(solvers)
         if not solvers:
             return []
@@ -1742,8 +1888,11 @@ class FullBundleAdjustmentSolver:
             probs.append(dict(cam_intr=intr, cam_T=camT, pose_T=T_jw, pose_fixed=pf, pt_X=X,
                               pt_fixed=qf, obs_cam=ocam, obs_pose=opose, obs_pt=opt, obs_uv=ouv))
         huber = (options or Options()).outlier_handle.threshold_huber_loss
+        sp = FullBundleAdjustmentSolver._scaled_priors("ComputeCovarianceBatch", solvers, priors, sigma_pixel)
         batch = BaBatch(probs, solvers[0].device)
         try:
+            if sp is not None:
+                batch.set_prior(sp)
             cp, cq, res = batch.covariance(huber, points)
             out = []
             for k in range(len(solvers)):
@@ -1756,7 +1905,7 @@ class FullBundleAdjustmentSolver:
         return out
 
     @staticmethod
-    def MarginalizeBatch(solvers, marg_poses, sigma_pixel=1.0, options=None):
+    def MarginalizeBatch(solvers, marg_poses, sigma_pixel=1.0, options=None, priors=None):
         """(new) Marginalisation priors of several solver objects in ONE launch
         (ba_batch_marginalize; see BaBatch for the limits), at the CURRENT registered
         values.  marg_poses[k]: the pose objects (or integer handles) of solver k that
@@ -1768,7 +1917,9 @@ class FullBundleAdjustmentSolver:
         caller's units for an isotropic pixel noise of `sigma_pixel`
         (marginal_to_user_units).  H is singular where the gauge is free.  A result
         whose status is not 0 is zero; dropped_pivots > 0 means the marked block
-        was singular and the prior meaningless."""
+        was singular and the prior meaningless.  priors: as in SolveBatch; the old
+        prior joins the factors, so priors chain from window to window (the returned b is
+        at the current values, which are the lin_poses of the next prior)."""
         solvers = list(solvers)
         if not solvers:
             return []
@@ -1790,8 +1941,11 @@ class FullBundleAdjustmentSolver:
                 mk[h] = 1
             marks.append(mk)
         huber = (options or Options()).outlier_handle.threshold_huber_loss
+        sp = FullBundleAdjustmentSolver._scaled_priors("MarginalizeBatch", solvers, priors, sigma_pixel)
         batch = BaBatch(probs, solvers[0].device)
         try:
+            if sp is not None:
+                batch.set_prior(sp)
             Hl, bl, kl, res = batch.marginalize(np.concatenate(marks), huber)
             out = []
             for k in range(len(solvers)):

@@ -86,8 +86,13 @@ class FullBundleAdjustmentSolver {
   // convergence_status_ = false.  Returns true when every problem was solved.  The
   // solvers need not be finalized and are not finalized by this call; the first
   // solver's device is used.  Sharded solvers are refused (std::runtime_error).
+  // in_priors (null: none): one PosePrior per solver, taken in as one more factor of its
+  // problem (ba_batch_set_prior of include/ba_hip.h), H and b in the units MarginalizeBatch
+  // returns for sigma_pixel.
+  struct PosePrior;
   static bool SolveBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, Options options,
-                         std::vector<Summary> *summaries = nullptr);
+                         std::vector<Summary> *summaries = nullptr,
+                         const std::vector<PosePrior> *in_priors = nullptr, double sigma_pixel = 1.0);
 
   // (new) Read the CURRENT values behind every registered pose / point pointer again
   // and hand them to the finalized problem (ba_update_values): re-optimising the same
@@ -124,7 +129,8 @@ class FullBundleAdjustmentSolver {
   // problem has status 0 and its factorisation met no non-positive pivot.
   static bool ComputeCovarianceBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, double sigma_pixel,
                                      std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
-                                     std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points);
+                                     std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points,
+                                     const std::vector<PosePrior> *in_priors = nullptr);
   // (new) The marginalisation prior one solver's window leaves on its kept poses: the
   // Gaussian 1/2 d^T H d - b^T d, d the stacked tangents xi = [v; omega] of the kept poses'
   // WORLD-TO-BODY transforms (the convention of ComputeCovariance), so that H d = b is their
@@ -152,7 +158,29 @@ class FullBundleAdjustmentSolver {
   // of its marked poses met no non-positive pivot.
   static bool MarginalizeBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers,
                                const std::vector<std::vector<_BA_Pose *>> &marg_poses, double sigma_pixel,
-                               std::vector<MarginalPrior> *priors);
+                               std::vector<MarginalPrior> *priors,
+                               const std::vector<PosePrior> *in_priors = nullptr);
+  // (new) A prior taken back IN by SolveBatch, ComputeCovarianceBatch and MarginalizeBatch
+  // (in_priors, one per solver; an empty `poses` means none for that solver): the Gaussian
+  // 1/2 d^T H d - b^T d + c / 2 on the registered, optimisable `poses`, in any order (the
+  // blocks of H and b follow that order), d_j = log(T_jw inverse(T_jw at lin_poses[j])).
+  // H (row-major, dim = 6 * poses.size()) and b in the units MarginalizeBatch returns for the
+  // same sigma_pixel, c in the same units of energy (0, or b^T H^+ b); lin_poses are the
+  // values at which H and b were formed, in the convention of AddPose and converted as
+  // AddPose converts.  The derivative of d with respect to the update is taken as the
+  // identity (first order, exact at d = 0): the caller keeps d small.  With a prior given,
+  // MarginalizeBatch chains: the old prior joins the factors of the new one.
+  struct PosePrior {
+    std::vector<_BA_Pose *> poses;
+    std::vector<double> H, b;
+    std::vector<_BA_Pose> lin_poses;
+    double c{0.0};
+    PosePrior() = default;
+    // what MarginalizeBatch returned, linearised at the CURRENT values of its kept poses
+    explicit PosePrior(const MarginalPrior &m, double c_ = 0.0) : poses(m.kept_poses), H(m.H), b(m.b), c(c_) {
+      for (const _BA_Pose *p : poses) lin_poses.push_back(*p);
+    }
+  };
   // the C-ABI handle behind the finalized problem (nullptr before FinalizeParameters):
   // for the readers of include/ba_hip.h; indices there are registration order
   ba_handle *GetHandle() const { return handle_; }
@@ -203,6 +231,16 @@ class FullBundleAdjustmentSolver {
   // ba_create + ba_batch_create on `device`; returns ba_batch_create's code (the caller
   // destroys both objects)
   static int CreateBatch(const BatchArrays &a, int device, ba_handle **h, ba_batch **batch);
+  // in_priors (may be null: out->set stays false) into the arrays of ba_batch_set_prior:
+  // scaled units, registration order.  Throws std::runtime_error on a malformed prior.
+  struct PriorArrays {
+    bool set{false};
+    std::vector<int32_t> off, pose;
+    std::vector<double> T_lin, H, b, c;
+  };
+  static void PackPriors(const std::vector<FullBundleAdjustmentSolver *> &solvers, const char *who,
+                         const std::vector<PosePrior> *in_priors, double sigma_pixel, PriorArrays *out);
+  static int SetPriors(ba_batch *batch, const PriorArrays &p);
   // the options' thresholds and iteration limit into a Summary (nullptr: nothing)
   static void BeginSummary(Summary *summary, const Options &options);
   // stderr warnings about weakly connected poses / points (reference

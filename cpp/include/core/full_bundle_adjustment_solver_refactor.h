@@ -89,6 +89,17 @@ class FullBundleAdjustmentSolverRefactor {
     for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
     return FullBundleAdjustmentSolver::ComputeCovarianceBatch(impls, sigma_pixel, cov_poses, cov_points);
   }
+  // the same with one pose prior per solver taken in, see FullBundleAdjustmentSolver::PosePrior
+  using PosePrior = FullBundleAdjustmentSolver::PosePrior;
+  static bool ComputeCovarianceBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers,
+                                     double sigma_pixel,
+                                     std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
+                                     std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points,
+                                     const std::vector<PosePrior> *in_priors) {
+    std::vector<FullBundleAdjustmentSolver *> impls;
+    for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
+    return FullBundleAdjustmentSolver::ComputeCovarianceBatch(impls, sigma_pixel, cov_poses, cov_points, in_priors);
+  }
   // (new) the marginalisation priors of several solvers in one launch, see
   // FullBundleAdjustmentSolver::MarginalizeBatch
   using MarginalPrior = FullBundleAdjustmentSolver::MarginalPrior;
@@ -98,6 +109,13 @@ class FullBundleAdjustmentSolverRefactor {
     std::vector<FullBundleAdjustmentSolver *> impls;
     for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
     return FullBundleAdjustmentSolver::MarginalizeBatch(impls, marg_poses, sigma_pixel, priors);
+  }
+  static bool MarginalizeBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers,
+                               const std::vector<std::vector<Pose *>> &marg_poses, double sigma_pixel,
+                               std::vector<MarginalPrior> *priors, const std::vector<PosePrior> *in_priors) {
+    std::vector<FullBundleAdjustmentSolver *> impls;
+    for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
+    return FullBundleAdjustmentSolver::MarginalizeBatch(impls, marg_poses, sigma_pixel, priors, in_priors);
   }
   ba_handle *GetHandle() const { return impl_.GetHandle(); }
 

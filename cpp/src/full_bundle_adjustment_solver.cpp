@@ -491,8 +491,61 @@ int FullBundleAdjustmentSolver::CreateBatch(const BatchArrays &a, int device, ba
                          a.uv.data());
 }
 
+int FullBundleAdjustmentSolver::SetPriors(ba_batch *batch, const PriorArrays &p) {
+  if (!p.set) return 0;
+  return ba_batch_set_prior(batch, p.off.data(), p.pose.data(), p.T_lin.data(), p.H.data(), p.b.data(), p.c.data());
+}
+
+void FullBundleAdjustmentSolver::PackPriors(const std::vector<FullBundleAdjustmentSolver *> &solvers, const char *who,
+                                            const std::vector<PosePrior> *in_priors, double sigma_pixel,
+                                            PriorArrays *out) {
+  if (in_priors == nullptr) return;
+  const std::string name(who);
+  if (in_priors->size() != solvers.size()) throw std::runtime_error(name + ": one prior per solver");
+  out->set = true;
+  std::vector<int32_t> &off = out->off, &pose = out->pose;
+  std::vector<double> &Tl = out->T_lin, &H = out->H, &bv = out->b, &cs = out->c;
+  off.assign(1, 0);
+  for (size_t k = 0; k < solvers.size(); ++k) {
+    const FullBundleAdjustmentSolver *s = solvers[k];
+    const PosePrior &p = (*in_priors)[k];
+    const size_t K = p.poses.size(), n = 6 * K;
+    if (p.H.size() != n * n || p.b.size() != n || p.lin_poses.size() != K)
+      throw std::runtime_error(name + ": a prior needs H (6K x 6K), b (6K) and K lin_poses");
+    // registration order (ascending index), the blocks of H and b permuted with the poses
+    std::vector<std::pair<int, int>> order;  // (registration index, position in the prior)
+    for (size_t t = 0; t < K; ++t) {
+      const auto it = s->pose_index_.find(p.poses[t]);
+      if (it == s->pose_index_.end()) throw std::runtime_error(name + ": there is no pointer in the BA pose pool.");
+      order.emplace_back(it->second, static_cast<int>(t));
+    }
+    std::sort(order.begin(), order.end());
+    // the caller's units -> scaled units, unit pixel noise: the inverse of MarginalizeBatch's
+    const double w = 1.0 / (sigma_pixel * sigma_pixel * static_cast<double>(s->scaler_) * static_cast<double>(s->scaler_));
+    const auto d = [s](size_t r) { return r % 6 < 3 ? static_cast<double>(s->inverse_scaler_) : 1.0; };
+    for (size_t t = 0; t < K; ++t) {
+      pose.push_back(order[t].first);
+      _BA_Pose T_jw = p.lin_poses[static_cast<size_t>(order[t].second)].inverse();
+      T_jw.translation() = T_jw.translation() * s->scaler_;
+      Tl.resize(Tl.size() + 12);
+      Pack12(T_jw, &Tl[Tl.size() - 12]);
+    }
+    for (size_t r = 0; r < n; ++r) {
+      const size_t sr = 6 * static_cast<size_t>(order[r / 6].second) + r % 6;
+      for (size_t c = 0; c < n; ++c) {
+        const size_t sc = 6 * static_cast<size_t>(order[c / 6].second) + c % 6;
+        H.push_back((d(r) * p.H[sr * n + sc] * d(c)) / w);
+      }
+      bv.push_back((d(r) * p.b[sr]) / w);
+    }
+    cs.push_back(p.c / w);
+    off.push_back(static_cast<int32_t>(pose.size()));
+  }
+}
+
 bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, Options options,
-                                            std::vector<Summary> *summaries) {
+                                            std::vector<Summary> *summaries, const std::vector<PosePrior> *in_priors,
+                                            double sigma_pixel) {
   timer::StopWatch stopwatch("BundleAdjustmentSolver::SolveBatch");
   stopwatch.Start();
   const int B = static_cast<int>(solvers.size());
@@ -500,6 +553,8 @@ bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustme
   if (B == 0) return true;
   BatchArrays a;
   PackBatch(solvers, "SolveBatch", true, &a);
+  PriorArrays pa;
+  PackPriors(solvers, "SolveBatch", in_priors, sigma_pixel, &pa);
   std::vector<int32_t> &pose_off = a.pose_off, &pt_off = a.pt_off;
   std::vector<double> &T = a.T, &X = a.X;
   const ba_options o = PackOptions(options, solvers[0]->gauss_newton_);
@@ -509,6 +564,7 @@ bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustme
   ba_handle *h = nullptr;
   ba_batch *batch = nullptr;
   int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
+  if (rc == 0) rc = SetPriors(batch, pa);
   if (rc == 0) rc = ba_batch_solve(batch, &o, rows.data(), cap, res.data());
   if (rc == 0) rc = ba_batch_get_poses(batch, T.data());
   if (rc == 0) rc = ba_batch_get_points(batch, X.data());
@@ -543,7 +599,7 @@ bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustme
 bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
     const std::vector<FullBundleAdjustmentSolver *> &solvers, double sigma_pixel,
     std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
-    std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points) {
+    std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points, const std::vector<PosePrior> *in_priors) {
   const int B = static_cast<int>(solvers.size());
   if (cov_poses != nullptr) cov_poses->assign(static_cast<size_t>(B), std::vector<Eigen::Matrix<double, 6, 6>>());
   if (cov_points != nullptr) cov_points->assign(static_cast<size_t>(B), std::vector<Eigen::Matrix<double, 3, 3>>());
@@ -551,12 +607,15 @@ bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
   if (cov_poses == nullptr) throw std::runtime_error("ComputeCovarianceBatch: null output for the pose blocks");
   BatchArrays a;
   PackBatch(solvers, "ComputeCovarianceBatch", false, &a);
+  PriorArrays pa;
+  PackPriors(solvers, "ComputeCovarianceBatch", in_priors, sigma_pixel, &pa);
   std::vector<double> cp(36 * a.pose_fixed.size()), cq(cov_points ? 9 * a.point_fixed.size() : 0);
   std::vector<ba_batch_cov_result> res(static_cast<size_t>(B));
   const Options defaults;
   ba_handle *h = nullptr;
   ba_batch *batch = nullptr;
   int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
+  if (rc == 0) rc = SetPriors(batch, pa);
   if (rc == 0)
     rc = ba_batch_covariance(batch, static_cast<double>(defaults.outlier_handle.threshold_huber_loss), cp.data(),
                              cov_points ? cq.data() : nullptr, res.data());
@@ -596,7 +655,8 @@ bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
 
 bool FullBundleAdjustmentSolver::MarginalizeBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers,
                                                   const std::vector<std::vector<_BA_Pose *>> &marg_poses,
-                                                  double sigma_pixel, std::vector<MarginalPrior> *priors) {
+                                                  double sigma_pixel, std::vector<MarginalPrior> *priors,
+                                                  const std::vector<PosePrior> *in_priors) {
   const int B = static_cast<int>(solvers.size());
   if (priors == nullptr) throw std::runtime_error("MarginalizeBatch: null output");
   priors->assign(static_cast<size_t>(B), MarginalPrior());
@@ -604,6 +664,8 @@ bool FullBundleAdjustmentSolver::MarginalizeBatch(const std::vector<FullBundleAd
   if (B == 0) return true;
   BatchArrays a;
   PackBatch(solvers, "MarginalizeBatch", false, &a);
+  PriorArrays pa;
+  PackPriors(solvers, "MarginalizeBatch", in_priors, sigma_pixel, &pa);
   std::vector<uint8_t> mark(a.pose_fixed.size(), 0), marg_pt(a.point_fixed.size(), 0);
   for (int b = 0; b < B; ++b)
     for (_BA_Pose *pose : marg_poses[b]) {
@@ -619,6 +681,7 @@ bool FullBundleAdjustmentSolver::MarginalizeBatch(const std::vector<FullBundleAd
   ba_handle *h = nullptr;
   ba_batch *batch = nullptr;
   int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
+  if (rc == 0) rc = SetPriors(batch, pa);
   if (rc == 0) rc = ba_batch_marg_layout(batch, mark.data(), H_off.data(), b_off.data());
   if (rc == 0) {
     H.resize(static_cast<size_t>(H_off[B]));

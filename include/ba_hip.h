@@ -638,7 +638,15 @@ void ba_batch_destroy(ba_batch *b);
  * max_num_iterations <= 0: nothing changes, converged, no rows.  One launch and one
  * synchronisation on the handle's stream.  The solved values stay in the object: a
  * following ba_batch_solve starts from them.  Returns 0 when every problem was processed,
- * whatever its status. */
+ * whatever its status.
+ * With a prior set (ba_batch_set_prior): the prior of a problem is one more factor of its
+ * LM loop.  With g = b - H delta at the accepted poses, H_jj joins A_j and g_j joins a_j
+ * before damping (the prior's diagonal is damped by 1 + lambda like the rest of A_j), the
+ * off-diagonal blocks H_jk join S_jk undamped, the quadratic model gains the cross term
+ * 2 sum_{j>k} x_j^T H_jk x_k, and the initial and every trial cost gain the prior's residual
+ * norm sqrt(max(0, delta^T H delta - 2 b^T delta + c)).  n_obs (average error) and the block
+ * count of the average step are unchanged: a prior is neither an observation nor a
+ * parameter block. */
 int ba_batch_solve(ba_batch *b, const ba_options *opt, ba_iter_info *rows, int cap,
                    ba_batch_result *res);
 /* Covariance blocks of EVERY problem of the batch at the values the object holds (after
@@ -661,7 +669,9 @@ int ba_batch_solve(ba_batch *b, const ba_options *opt, ba_iter_info *rows, int c
  * ba_batch_solve; the per-landmark scratch is overwritten, which ba_batch_solve rebuilds.
  * No floating-point atomics, fixed summation order per problem: the same bits run to run,
  * alone and at any position of any batch, at any image width.  b, cov_pose36 and res are
- * checked for NULL before anything touches the GPU: -1 and ba_last_error. */
+ * checked for NULL before anything touches the GPU: -1 and ba_last_error.
+ * With a prior set (ba_batch_set_prior): S includes the prior's H (lambda = 0) before it is
+ * factored, so the blocks are the covariance given the window AND its past. */
 typedef struct {
   int status, dropped_pivots;
 } ba_batch_cov_result;
@@ -701,7 +711,12 @@ int ba_batch_covariance(ba_batch *b, double huber, double *cov_pose36, double *c
  * run to run, alone and at any position of any batch, at any image width (32, 64, 96 or 112
  * columns, chosen from the widest problem: 16 ceil(6 m / 16) + 6 K).  b, marg_pose, res, and
  * H and bvec unless every K_p = 0, are checked for NULL before anything touches the GPU: -1
- * and ba_last_error. */
+ * and ba_last_error.
+ * With a prior set (ba_batch_set_prior): the whole prior of a problem, linearised at the held
+ * values (H, g = b - H delta), joins the factors before the partial Cholesky, whichever of its
+ * poses are marked or kept, so priors chain from window to window.  The output b is then at
+ * the held values, which are the T_lin of the next prior.  The rows of a kept pose that
+ * touches neither L nor the prior stay exactly zero; the layout and the plan are unchanged. */
 typedef struct {
   int status, dropped_pivots, n_kept, n_marg_pose, n_marg_pt;
 } ba_batch_marg_result;
@@ -717,6 +732,47 @@ int ba_batch_marg_plan_problem(int n_pose, const uint8_t *pose_fixed,
                                const uint8_t *marg_pose, int n_pt, const uint8_t *pt_fixed,
                                int64_t n_obs, const int32_t *obs_pose,
                                const int32_t *obs_pt, int32_t *kept_pose, uint8_t *marg_pt);
+/* One pose prior per problem: the Gaussian 1/2 delta^T H delta - b^T delta (+ c / 2) that
+ * ba_batch_marginalize returns, taken back in as one more factor of ba_batch_solve,
+ * ba_batch_covariance and ba_batch_marginalize.  The prior of problem p acts on
+ * K_p = prior_off[p+1] - prior_off[p] of its OPTIMISABLE poses:
+ *   prior_pose  problem-local user indices, strictly ascending per problem (the order of the
+ *               kept set of ba_batch_marginalize);
+ *   T_lin12     12 per prior pose, layout of ba_set_poses: the values at which H and b were formed;
+ *   H           problem p: row-major (6 K_p)^2 at element sum_{q<p} 36 K_q^2; only the lower
+ *               triangle (row >= column) is ever read;
+ *   bvec        problem p: 6 K_p at element 6 sum_{q<p} K_q;
+ *   c           one per problem, >= 0 (NULL: zeros): the squared residual of the eliminated
+ *               factors at the linearisation point.  With c = b^T H^+ b the prior's cost term is
+ *               zero at the prior's own minimum; with c = 0 wherever its energy is not positive.
+ * Scaled units and the conventions of ba_batch_marginalize: tangent xi = [v; omega] of
+ * T_jw <- exp(xi) T_jw, the solver's sign of b, unit pixel noise.  The tangent of pose j is
+ * delta_j = se3_log(T_j T_lin,j^-1), the inverse of the solver's se3 exponential; it is defined
+ * for a rotation angle below pi and the caller keeps delta small.  The derivative of delta with
+ * respect to the update is taken as the identity: first order, exact at delta = 0, the usual
+ * choice of a fixed-lag smoother (no right-Jacobian correction, no first-estimate Jacobians).
+ * The arrays are copied to the device once; prior_off == NULL clears the prior.  A batch
+ * without a prior, and a problem with K_p = 0 whatever its neighbours hold, computes exactly
+ * what it computed before: same results, same bits.  One writer per element, fixed summation
+ * order, no floating-point atomics: a problem with a prior gives the same bits run to run,
+ * alone and at any position of any batch.  A prior given to a problem whose status is 2 is
+ * accepted and ignored.  Validation happens before anything touches the GPU (-1 and
+ * ba_last_error): offsets start at 0 and never decrease; indices in range, strictly ascending
+ * and optimisable; every value finite; c >= 0.  A call refused by the validation changes
+ * nothing: the prior set before it stays in effect.  A call that fails later (device
+ * allocation, upload) leaves the batch without a prior. */
+int ba_batch_set_prior(ba_batch *b, const int32_t *prior_off /* B+1 */, const int32_t *prior_pose,
+                       const double *T_lin12, const double *H, const double *bvec,
+                       const double *c /* B, NULL = zeros */);
+/* Host-only (no GPU): the validation of ba_batch_set_prior for a batch described by pose_off
+ * (B+1) and pose_fixed (NULL: none fixed).  0, or -1 and ba_last_error. */
+int ba_batch_prior_check(int B, const int32_t *pose_off, const uint8_t *pose_fixed,
+                         const int32_t *prior_off, const int32_t *prior_pose,
+                         const double *T_lin12, const double *H, const double *bvec,
+                         const double *c);
+/* out4 = { problems with a prior in effect, their prior poses in all (total K), device bytes
+ * of the priors, 0 } */
+int ba_batch_prior_info(ba_batch *b, int64_t out4[4]);
 /* new values for the same structure, concatenated user order; NULL = keep */
 int ba_batch_update_values(ba_batch *b, const double *T_jw12, const double *X3);
 int ba_batch_get_poses(ba_batch *b, double *T_jw12);
