@@ -261,6 +261,10 @@ SIGNATURES = {
     "ba_batch_set_prior": (C.c_int, [_P, _I32, _I32, _D, _D, _D, _D]),
     "ba_batch_prior_check": (C.c_int, [C.c_int, _I32, _U8, _I32, _I32, _D, _D, _D, _D]),
     "ba_batch_prior_info": (C.c_int, [_P, _I64]),
+    "ba_batch_set_relative": (C.c_int, [_P, _I32, _I32, _I32, _D, _D]),
+    "ba_batch_relative_check": (C.c_int, [C.c_int, _I32, _U8, _I32, _I32, _I32, _D, _D]),
+    "ba_batch_relative_info": (C.c_int, [_P, _I64]),
+    "ba_batch_relative_marg_plan": (C.c_int, [_P, _U8, _U8]),
     "ba_batch_update_values": (C.c_int, [_P, _D, _D]),
     "ba_batch_get_poses": (C.c_int, [_P, _D]),
     "ba_batch_get_points": (C.c_int, [_P, _D]),

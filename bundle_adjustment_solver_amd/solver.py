@@ -303,6 +303,15 @@ def prior_delta(T12, T_lin12):
     return se3_log(_T44_to_12(T @ rigid_inverse(L))[0])
 
 
+def relative_residual(T_j12, T_k12, Z12):
+    """r = se3_log(T_j T_k^-1 Z^-1), the residual of a relative-pose factor of
+    BaBatch.set_relative: prior_delta with T_lin = Z T_k."""
+    Tj = _T12_to_44(T_j12)[0]
+    Tk = _T12_to_44(T_k12)[0]
+    Z = _T12_to_44(Z12)[0]
+    return se3_log(_T44_to_12(Tj @ rigid_inverse(Tk) @ rigid_inverse(Z))[0])
+
+
 class BaProblem:
     """Thin numpy wrapper over one ba_handle, in the solver's SCALED units.
 
@@ -1134,6 +1143,7 @@ class BaBatch:
                  obs_cam=cat("obs_cam", np.int32, ()), obs_pose=cat("obs_pose", np.int32, ()),
                  obs_pt=cat("obs_pt", np.int32, ()), obs_uv=cat("obs_uv", np.float64, (2,)))
         self.n_pose, self.n_pt = a["pose_T"].shape[0], a["pt_X"].shape[0]
+        self._n_rel = 0   # factors given to set_relative (the length of relative_marg_plan's output)
         self.pose_fixed = a["pose_fixed"]
         b = C.c_void_p()
         check(self.lib.ba_batch_create(
@@ -1266,6 +1276,65 @@ class BaBatch:
         o = (C.c_int64 * 4)()
         check(self.lib.ba_batch_prior_info(self.b, o), "ba_batch_prior_info")
         return dict(n_prior=int(o[0]), total_K=int(o[1]), device_bytes=int(o[2]))
+
+    def set_relative(self, rels):
+        """Relative-pose factors per problem (ba_batch_set_relative; scaled units).  rels:
+        a list with one entry per problem, each None or a dict with the keys
+          j, k    (F,) problem-local user indices of two distinct poses, at least one of
+                  them optimisable (a fixed pose receives nothing),
+          Z       (F, 12) the measurement of T_j T_k^-1,
+          Omega   (F, 6, 6) information matrices, only the lower triangle is read.
+        Residual se3_log(T_j T_k^-1 Z^-1), first-order Jacobians I and -Ad(T_j T_k^-1); no
+        robust weight.  Several factors may name one pair.  The factors stay with the
+        object until clear_relative or the next set_relative."""
+        if len(rels) != self.B:
+            raise ValueError("set_relative: one entry (or None) per problem (%d)" % self.B)
+        off = np.zeros(self.B + 1, np.int32)
+        js, ks, Zs, Os = [], [], [], []
+        for p, rl in enumerate(rels):
+            F = 0
+            if rl is not None:
+                j = np.asarray(rl["j"], np.int32).reshape(-1)
+                k = np.asarray(rl["k"], np.int32).reshape(-1)
+                F = j.shape[0]
+                Z = np.asarray(rl["Z"], np.float64).reshape(-1, 12)
+                Om = np.asarray(rl["Omega"], np.float64).reshape(-1, 36)
+                if k.shape != (F,) or Z.shape != (F, 12) or Om.shape != (F, 36):
+                    raise ValueError("set_relative: problem %d needs j (F,), k (F,), Z (F, 12), "
+                                     "Omega (F, 6, 6) for its F = %d factors" % (p, F))
+                js.append(j)
+                ks.append(k)
+                Zs.append(Z.reshape(-1))
+                Os.append(Om.reshape(-1))
+            off[p + 1] = off[p] + F
+        cat = lambda xs, dt: np.ascontiguousarray(np.concatenate(xs or [np.zeros(0, dt)]), dt)
+        js, ks, Zs, Os = cat(js, np.int32), cat(ks, np.int32), cat(Zs, np.float64), cat(Os, np.float64)
+        # the validation first, on the host: a refusal leaves the factors set before in effect
+        check(self.lib.ba_batch_relative_check(self.B, _ip(self.pose_off), _up(self.pose_fixed), _ip(off), _ip(js),
+                                               _ip(ks), _dp(Zs), _dp(Os)), "ba_batch_relative_check")
+        rc = self.lib.ba_batch_set_relative(self.b, _ip(off), _ip(js), _ip(ks), _dp(Zs), _dp(Os))
+        self._n_rel = int(off[-1]) if rc == 0 else 0   # a call that fails now leaves the batch without factors
+        check(rc, "ba_batch_set_relative")
+
+    def clear_relative(self):
+        check(self.lib.ba_batch_set_relative(self.b, None, None, None, None, None),
+              "ba_batch_set_relative")
+        self._n_rel = 0
+
+    def relative_info(self):
+        o = (C.c_int64 * 4)()
+        check(self.lib.ba_batch_relative_info(self.b, o), "ba_batch_relative_info")
+        return dict(n_problems=int(o[0]), n_factors=int(o[1]), device_bytes=int(o[2]))
+
+    def relative_marg_plan(self, marg_pose):
+        """-> one byte per factor given to set_relative, input order: 1 where the factor
+        joins marginalize under this marking (one of its poses is marked) and leaves with
+        the marked poses, 0 where the caller carries it into the next window."""
+        m = self._marking(marg_pose)
+        out = np.zeros(self._n_rel, np.uint8)
+        check(self.lib.ba_batch_relative_marg_plan(self.b, _up(m), _up(out)),
+              "ba_batch_relative_marg_plan")
+        return out
 
     def cov_poses_of(self, p, cov_pose):
         return cov_pose[self.pose_off[p]:self.pose_off[p + 1]]
@@ -1809,7 +1878,44 @@ class FullBundleAdjustmentSolver:
         return out
 
     @staticmethod
-    def SolveBatch(solvers, options, summaries=None, priors=None, sigma_pixel=1.0):
+    def _scaled_relatives(what, solvers, relatives, sigma_pixel):
+        """relatives of SolveBatch / ComputeCovarianceBatch / MarginalizeBatch -> the list
+        BaBatch.set_relative takes (scaled units), or None.  relatives[k]: None, or a list of
+        factors of solver k, each a dict with
+          pose_j, pose_k  two registered poses (objects or integer handles), distinct, not
+                          both fixed,
+          measurement     (4, 4) the measured pose_j^-1 * pose_k in the convention and units
+                          of AddPose (T_jw T_kw^-1 after AddPose's conversion),
+          information     (6, 6) of the tangent [v; omega] of the world-to-body poses in the
+                          caller's units, the units MarginalizeBatch returns for `sigma_pixel`
+                          (converted as prior_to_scaled_units converts a 6x6 H)."""
+        if relatives is None:
+            return None
+        if len(relatives) != len(solvers):
+            raise ValueError("%s: one list of relative-pose factors (or None) per solver" % what)
+        out = []
+        for sv, fs in zip(solvers, relatives):
+            if fs is None:
+                out.append(None)
+                continue
+            j, k = [], []
+            Z, Om = np.zeros((len(fs), 12)), np.zeros((len(fs), 6, 6))
+            for f, fac in enumerate(fs):
+                hj, hk = sv._pose_handle(fac["pose_j"]), sv._pose_handle(fac["pose_k"])
+                if hj is None or hk is None:
+                    raise RuntimeError("There is no pointer in the BA pose pool.")
+                j.append(hj)
+                k.append(hk)
+                M = np.array(fac["measurement"], np.float64).reshape(1, 4, 4)
+                M[:, :3, 3] *= SCALER
+                Z[f] = _T44_to_12(M)[0]
+                Om[f] = prior_to_scaled_units(np.asarray(fac["information"], np.float64).reshape(6, 6),
+                                              np.zeros(6), 0.0, sigma_pixel)[0]
+            out.append(dict(j=np.asarray(j, np.int32), k=np.asarray(k, np.int32), Z=Z, Omega=Om))
+        return out
+
+    @staticmethod
+    def SolveBatch(solvers, options, summaries=None, priors=None, sigma_pixel=1.0, relatives=None):
         """Solve the registered problems of several solver objects in ONE launch
         (ba_batch_solve: one persistent workgroup per problem, see BaBatch for the
         limits), write every solver's poses and points back as Solve does and fill
@@ -1818,7 +1924,8 @@ class FullBundleAdjustmentSolver:
         limit, non-finite input) is left untouched.  priors (default None: none):
         one pose prior per solver taken in as one more factor (BaBatch.set_prior), see
         _scaled_priors for the dict; H and b in the units MarginalizeBatch returns for
-        `sigma_pixel`."""
+        `sigma_pixel`.  relatives (default None: none): one list of relative-pose factors
+        per solver (BaBatch.set_relative), see _scaled_relatives for the dict."""
         t0 = time.perf_counter()
         solvers = list(solvers)
         if not solvers:
@@ -1837,10 +1944,13 @@ class FullBundleAdjustmentSolver:
         c_opt = options.to_c()
         c_opt.gauss_newton = 1 if solvers[0]._use_gauss_newton(options) else 0
         sp = FullBundleAdjustmentSolver._scaled_priors("SolveBatch", solvers, priors, sigma_pixel)
+        sr = FullBundleAdjustmentSolver._scaled_relatives("SolveBatch", solvers, relatives, sigma_pixel)
         batch = BaBatch(probs, solvers[0].device)
         try:
             if sp is not None:
                 batch.set_prior(sp)
+            if sr is not None:
+                batch.set_relative(sr)
             rows, res = batch.solve(c_opt)
             T_all, X_all = batch.get_poses(), batch.get_points()
             for k, sv in enumerate(solvers):
@@ -1867,7 +1977,8 @@ class FullBundleAdjustmentSolver:
         return res
 
     @staticmethod
-    def ComputeCovarianceBatch(solvers, sigma_pixel=1.0, options=None, points=True, priors=None):
+    def ComputeCovarianceBatch(solvers, sigma_pixel=1.0, options=None, points=True, priors=None,
+                               relatives=None):
         """(new) Covariance blocks of the CURRENT registered values of several
         solver objects in ONE launch (ba_batch_covariance; see BaBatch for the
         limits).  Returns one (cov_pose (n_pose, 6, 6), cov_point (n_pt, 3, 3) or
@@ -1875,7 +1986,8 @@ class FullBundleAdjustmentSolver:
         order, the blocks of fixed members zero, units and conventions those of
         ComputeCovariance.  A result whose status is not 0 (over a limit,
         non-finite input) has zero blocks; dropped_pivots > 0 means S was singular.
-        priors: as in SolveBatch; the covariance then includes the past."""
+        priors: as in SolveBatch; the covariance then includes the past.  relatives: as
+        in SolveBatch; every factor joins."""
         solvers = list(solvers)
         if not solvers:
             return []
@@ -1889,10 +2001,14 @@ class FullBundleAdjustmentSolver:
                               pt_fixed=qf, obs_cam=ocam, obs_pose=opose, obs_pt=opt, obs_uv=ouv))
         huber = (options or Options()).outlier_handle.threshold_huber_loss
         sp = FullBundleAdjustmentSolver._scaled_priors("ComputeCovarianceBatch", solvers, priors, sigma_pixel)
+        sr = FullBundleAdjustmentSolver._scaled_relatives("ComputeCovarianceBatch", solvers, relatives,
+                                                          sigma_pixel)
         batch = BaBatch(probs, solvers[0].device)
         try:
             if sp is not None:
                 batch.set_prior(sp)
+            if sr is not None:
+                batch.set_relative(sr)
             cp, cq, res = batch.covariance(huber, points)
             out = []
             for k in range(len(solvers)):
@@ -1905,7 +2021,7 @@ class FullBundleAdjustmentSolver:
         return out
 
     @staticmethod
-    def MarginalizeBatch(solvers, marg_poses, sigma_pixel=1.0, options=None, priors=None):
+    def MarginalizeBatch(solvers, marg_poses, sigma_pixel=1.0, options=None, priors=None, relatives=None):
         """(new) Marginalisation priors of several solver objects in ONE launch
         (ba_batch_marginalize; see BaBatch for the limits), at the CURRENT registered
         values.  marg_poses[k]: the pose objects (or integer handles) of solver k that
@@ -1919,7 +2035,10 @@ class FullBundleAdjustmentSolver:
         whose status is not 0 is zero; dropped_pivots > 0 means the marked block
         was singular and the prior meaningless.  priors: as in SolveBatch; the old
         prior joins the factors, so priors chain from window to window (the returned b is
-        at the current values, which are the lin_poses of the next prior)."""
+        at the current values, which are the lin_poses of the next prior).  relatives: as
+        in SolveBatch; a factor joins exactly when one of its two poses is marked and then
+        leaves with it, and every tuple gains a sixth entry: one 0 / 1 per factor of that
+        solver, 1 where it left (the others go into the next window with the prior)."""
         solvers = list(solvers)
         if not solvers:
             return []
@@ -1942,16 +2061,23 @@ class FullBundleAdjustmentSolver:
             marks.append(mk)
         huber = (options or Options()).outlier_handle.threshold_huber_loss
         sp = FullBundleAdjustmentSolver._scaled_priors("MarginalizeBatch", solvers, priors, sigma_pixel)
+        sr = FullBundleAdjustmentSolver._scaled_relatives("MarginalizeBatch", solvers, relatives, sigma_pixel)
         batch = BaBatch(probs, solvers[0].device)
         try:
             if sp is not None:
                 batch.set_prior(sp)
+            if sr is not None:
+                batch.set_relative(sr)
+                left = batch.relative_marg_plan(np.concatenate(marks))
+                roff = np.concatenate([[0], np.cumsum([0 if r is None else len(r["j"]) for r in sr])])
             Hl, bl, kl, res = batch.marginalize(np.concatenate(marks), huber)
             out = []
             for k in range(len(solvers)):
                 Hu, bu = marginal_to_user_units(Hl[k], bl[k], sigma_pixel)
                 mq = np.flatnonzero(batch.points_of(k, batch.marg_pt))
                 out.append((Hu, bu, [int(h) for h in kl[k]], [int(h) for h in mq], res[k]))
+                if sr is not None:
+                    out[-1] += ([int(v) for v in left[roff[k]:roff[k + 1]]],)
         finally:
             batch.close()
         return out

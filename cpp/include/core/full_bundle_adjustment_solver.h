@@ -88,11 +88,14 @@ class FullBundleAdjustmentSolver {
   // solver's device is used.  Sharded solvers are refused (std::runtime_error).
   // in_priors (null: none): one PosePrior per solver, taken in as one more factor of its
   // problem (ba_batch_set_prior of include/ba_hip.h), H and b in the units MarginalizeBatch
-  // returns for sigma_pixel.
+  // returns for sigma_pixel.  in_relatives (null: none): one list of RelativePose factors per
+  // solver (ba_batch_set_relative of include/ba_hip.h).
   struct PosePrior;
+  struct RelativePose;
   static bool SolveBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, Options options,
                          std::vector<Summary> *summaries = nullptr,
-                         const std::vector<PosePrior> *in_priors = nullptr, double sigma_pixel = 1.0);
+                         const std::vector<PosePrior> *in_priors = nullptr, double sigma_pixel = 1.0,
+                         const std::vector<std::vector<RelativePose>> *in_relatives = nullptr);
 
   // (new) Read the CURRENT values behind every registered pose / point pointer again
   // and hand them to the finalized problem (ba_update_values): re-optimising the same
@@ -130,7 +133,8 @@ class FullBundleAdjustmentSolver {
   static bool ComputeCovarianceBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, double sigma_pixel,
                                      std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
                                      std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points,
-                                     const std::vector<PosePrior> *in_priors = nullptr);
+                                     const std::vector<PosePrior> *in_priors = nullptr,
+                                     const std::vector<std::vector<RelativePose>> *in_relatives = nullptr);
   // (new) The marginalisation prior one solver's window leaves on its kept poses: the
   // Gaussian 1/2 d^T H d - b^T d, d the stacked tangents xi = [v; omega] of the kept poses'
   // WORLD-TO-BODY transforms (the convention of ComputeCovariance), so that H d = b is their
@@ -142,6 +146,9 @@ class FullBundleAdjustmentSolver {
     std::vector<_BA_Pose *> kept_poses;           // optimisable, unmarked; registration order
     std::vector<_BA_Point *> marginalized_points;  // the landmarks that leave with the marked poses
     int status{0}, dropped_pivots{0};              // ba_batch_marg_result of include/ba_hip.h
+    // with in_relatives: one byte per factor of this solver, 1 where it joined and left with
+    // the marked poses, 0 where the caller carries it into the next window
+    std::vector<uint8_t> relatives_left;
     double operator()(int r, int c) const { return H[static_cast<size_t>(r) * dim + c]; }
   };
   // (new) The marginalisation priors of several solver objects in ONE launch
@@ -159,7 +166,8 @@ class FullBundleAdjustmentSolver {
   static bool MarginalizeBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers,
                                const std::vector<std::vector<_BA_Pose *>> &marg_poses, double sigma_pixel,
                                std::vector<MarginalPrior> *priors,
-                               const std::vector<PosePrior> *in_priors = nullptr);
+                               const std::vector<PosePrior> *in_priors = nullptr,
+                               const std::vector<std::vector<RelativePose>> *in_relatives = nullptr);
   // (new) A prior taken back IN by SolveBatch, ComputeCovarianceBatch and MarginalizeBatch
   // (in_priors, one per solver; an empty `poses` means none for that solver): the Gaussian
   // 1/2 d^T H d - b^T d + c / 2 on the registered, optimisable `poses`, in any order (the
@@ -180,6 +188,23 @@ class FullBundleAdjustmentSolver {
     explicit PosePrior(const MarginalPrior &m, double c_ = 0.0) : poses(m.kept_poses), H(m.H), b(m.b), c(c_) {
       for (const _BA_Pose *p : poses) lin_poses.push_back(*p);
     }
+  };
+  // (new) A relative-pose factor between two registered poses of one solver, taken in by
+  // SolveBatch, ComputeCovarianceBatch and MarginalizeBatch (in_relatives, one list per solver):
+  // odometry between keyframes, a loop closure, the pose part of an inertial delta.
+  // measurement is the measured inverse(*pose_j) * (*pose_k) in the convention and units of
+  // AddPose, that is T_jw T_kw^-1 of the world-to-body transforms after AddPose's conversion;
+  // information is the row-major 6x6 information matrix of the tangent [v; omega] of those
+  // transforms in the units MarginalizeBatch returns for the same sigma_pixel (only its lower
+  // triangle is read).  Residual log(T_jw T_kw^-1 measurement^-1), Jacobians of first order
+  // (identity and -Ad(T_jw T_kw^-1); exact at a zero residual), no robust weight.  The two
+  // poses are distinct and not both fixed; a fixed pose receives nothing.  MarginalizeBatch
+  // takes a factor in exactly when one of its poses is marked (MarginalPrior::relatives_left).
+  struct RelativePose {
+    _BA_Pose *pose_j{nullptr};
+    _BA_Pose *pose_k{nullptr};
+    _BA_Pose measurement;
+    double information[36] = {0.0};
   };
   // the C-ABI handle behind the finalized problem (nullptr before FinalizeParameters):
   // for the readers of include/ba_hip.h; indices there are registration order
@@ -241,6 +266,17 @@ class FullBundleAdjustmentSolver {
   static void PackPriors(const std::vector<FullBundleAdjustmentSolver *> &solvers, const char *who,
                          const std::vector<PosePrior> *in_priors, double sigma_pixel, PriorArrays *out);
   static int SetPriors(ba_batch *batch, const PriorArrays &p);
+  // in_relatives (may be null: out->set stays false) into the arrays of ba_batch_set_relative:
+  // scaled units, registration indices.  Throws std::runtime_error on an unknown pointer.
+  struct RelativeArrays {
+    bool set{false};
+    std::vector<int32_t> off, j, k;
+    std::vector<double> Z, Omega;
+  };
+  static void PackRelatives(const std::vector<FullBundleAdjustmentSolver *> &solvers, const char *who,
+                            const std::vector<std::vector<RelativePose>> *in_relatives, double sigma_pixel,
+                            RelativeArrays *out);
+  static int SetRelatives(ba_batch *batch, const RelativeArrays &r);
   // the options' thresholds and iteration limit into a Summary (nullptr: nothing)
   static void BeginSummary(Summary *summary, const Options &options);
   // stderr warnings about weakly connected poses / points (reference

@@ -117,6 +117,36 @@ class FullBundleAdjustmentSolverRefactor {
     for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
     return FullBundleAdjustmentSolver::MarginalizeBatch(impls, marg_poses, sigma_pixel, priors, in_priors);
   }
+  // (new) relative-pose factors between registered poses, see
+  // FullBundleAdjustmentSolver::RelativePose; one list per solver.  SolveBatch: see
+  // FullBundleAdjustmentSolver::SolveBatch; options.solver_type selects Levenberg-Marquardt
+  // or Gauss-Newton as in Solve (anything else throws std::runtime_error), for this call only:
+  // what an earlier Solve selected is put back afterwards.
+  using RelativePose = FullBundleAdjustmentSolver::RelativePose;
+  static bool SolveBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers, Options options,
+                         std::vector<Summary> *summaries = nullptr,
+                         const std::vector<PosePrior> *in_priors = nullptr, double sigma_pixel = 1.0,
+                         const std::vector<std::vector<RelativePose>> *in_relatives = nullptr);
+  static bool ComputeCovarianceBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers,
+                                     double sigma_pixel,
+                                     std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
+                                     std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points,
+                                     const std::vector<PosePrior> *in_priors,
+                                     const std::vector<std::vector<RelativePose>> *in_relatives) {
+    std::vector<FullBundleAdjustmentSolver *> impls;
+    for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
+    return FullBundleAdjustmentSolver::ComputeCovarianceBatch(impls, sigma_pixel, cov_poses, cov_points, in_priors,
+                                                              in_relatives);
+  }
+  static bool MarginalizeBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers,
+                               const std::vector<std::vector<Pose *>> &marg_poses, double sigma_pixel,
+                               std::vector<MarginalPrior> *priors, const std::vector<PosePrior> *in_priors,
+                               const std::vector<std::vector<RelativePose>> *in_relatives) {
+    std::vector<FullBundleAdjustmentSolver *> impls;
+    for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
+    return FullBundleAdjustmentSolver::MarginalizeBatch(impls, marg_poses, sigma_pixel, priors, in_priors,
+                                                        in_relatives);
+  }
   ba_handle *GetHandle() const { return impl_.GetHandle(); }
 
   std::string GetSolverStatistics() const;

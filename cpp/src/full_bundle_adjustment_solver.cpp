@@ -543,9 +543,54 @@ void FullBundleAdjustmentSolver::PackPriors(const std::vector<FullBundleAdjustme
   }
 }
 
+int FullBundleAdjustmentSolver::SetRelatives(ba_batch *batch, const RelativeArrays &r) {
+  if (!r.set) return 0;
+  return ba_batch_set_relative(batch, r.off.data(), r.j.data(), r.k.data(), r.Z.data(), r.Omega.data());
+}
+
+void FullBundleAdjustmentSolver::PackRelatives(const std::vector<FullBundleAdjustmentSolver *> &solvers,
+                                               const char *who,
+                                               const std::vector<std::vector<RelativePose>> *in_relatives,
+                                               double sigma_pixel, RelativeArrays *out) {
+  if (in_relatives == nullptr) return;
+  const std::string name(who);
+  if (in_relatives->size() != solvers.size())
+    throw std::runtime_error(name + ": one list of relative-pose factors per solver");
+  out->set = true;
+  out->off.assign(1, 0);
+  for (size_t b = 0; b < solvers.size(); ++b) {
+    const FullBundleAdjustmentSolver *s = solvers[b];
+    // the caller's units -> scaled units, unit pixel noise: as PackPriors converts a 6x6 H
+    const double w = 1.0 / (sigma_pixel * sigma_pixel * static_cast<double>(s->scaler_) * static_cast<double>(s->scaler_));
+    const auto d = [s](int r) { return r < 3 ? static_cast<double>(s->inverse_scaler_) : 1.0; };
+    for (const RelativePose &f : (*in_relatives)[b]) {
+      const auto ij = s->pose_index_.find(f.pose_j), ik = s->pose_index_.find(f.pose_k);
+      if (ij == s->pose_index_.end() || ik == s->pose_index_.end())
+        throw std::runtime_error(name + ": there is no pointer in the BA pose pool.");
+      out->j.push_back(ij->second);
+      out->k.push_back(ik->second);
+      _BA_Pose Z = f.measurement;
+      Z.translation() = Z.translation() * s->scaler_;
+      out->Z.resize(out->Z.size() + 12);
+      Pack12(Z, &out->Z[out->Z.size() - 12]);
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) out->Omega.push_back((d(r) * f.information[6 * r + c] * d(c)) / w);
+    }
+    out->off.push_back(static_cast<int32_t>(out->j.size()));
+  }
+  // a batch without any factor still needs addressable arrays
+  if (out->j.empty()) {
+    out->j.assign(1, 0);
+    out->k.assign(1, 0);
+    out->Z.assign(12, 0.0);
+    out->Omega.assign(36, 0.0);
+  }
+}
+
 bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, Options options,
                                             std::vector<Summary> *summaries, const std::vector<PosePrior> *in_priors,
-                                            double sigma_pixel) {
+                                            double sigma_pixel,
+                                            const std::vector<std::vector<RelativePose>> *in_relatives) {
   timer::StopWatch stopwatch("BundleAdjustmentSolver::SolveBatch");
   stopwatch.Start();
   const int B = static_cast<int>(solvers.size());
@@ -555,6 +600,8 @@ bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustme
   PackBatch(solvers, "SolveBatch", true, &a);
   PriorArrays pa;
   PackPriors(solvers, "SolveBatch", in_priors, sigma_pixel, &pa);
+  RelativeArrays ra;
+  PackRelatives(solvers, "SolveBatch", in_relatives, sigma_pixel, &ra);
   std::vector<int32_t> &pose_off = a.pose_off, &pt_off = a.pt_off;
   std::vector<double> &T = a.T, &X = a.X;
   const ba_options o = PackOptions(options, solvers[0]->gauss_newton_);
@@ -565,6 +612,7 @@ bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustme
   ba_batch *batch = nullptr;
   int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
   if (rc == 0) rc = SetPriors(batch, pa);
+  if (rc == 0) rc = SetRelatives(batch, ra);
   if (rc == 0) rc = ba_batch_solve(batch, &o, rows.data(), cap, res.data());
   if (rc == 0) rc = ba_batch_get_poses(batch, T.data());
   if (rc == 0) rc = ba_batch_get_points(batch, X.data());
@@ -599,7 +647,8 @@ bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustme
 bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
     const std::vector<FullBundleAdjustmentSolver *> &solvers, double sigma_pixel,
     std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
-    std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points, const std::vector<PosePrior> *in_priors) {
+    std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points, const std::vector<PosePrior> *in_priors,
+    const std::vector<std::vector<RelativePose>> *in_relatives) {
   const int B = static_cast<int>(solvers.size());
   if (cov_poses != nullptr) cov_poses->assign(static_cast<size_t>(B), std::vector<Eigen::Matrix<double, 6, 6>>());
   if (cov_points != nullptr) cov_points->assign(static_cast<size_t>(B), std::vector<Eigen::Matrix<double, 3, 3>>());
@@ -609,6 +658,8 @@ bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
   PackBatch(solvers, "ComputeCovarianceBatch", false, &a);
   PriorArrays pa;
   PackPriors(solvers, "ComputeCovarianceBatch", in_priors, sigma_pixel, &pa);
+  RelativeArrays ra;
+  PackRelatives(solvers, "ComputeCovarianceBatch", in_relatives, sigma_pixel, &ra);
   std::vector<double> cp(36 * a.pose_fixed.size()), cq(cov_points ? 9 * a.point_fixed.size() : 0);
   std::vector<ba_batch_cov_result> res(static_cast<size_t>(B));
   const Options defaults;
@@ -616,6 +667,7 @@ bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
   ba_batch *batch = nullptr;
   int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
   if (rc == 0) rc = SetPriors(batch, pa);
+  if (rc == 0) rc = SetRelatives(batch, ra);
   if (rc == 0)
     rc = ba_batch_covariance(batch, static_cast<double>(defaults.outlier_handle.threshold_huber_loss), cp.data(),
                              cov_points ? cq.data() : nullptr, res.data());
@@ -656,7 +708,8 @@ bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
 bool FullBundleAdjustmentSolver::MarginalizeBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers,
                                                   const std::vector<std::vector<_BA_Pose *>> &marg_poses,
                                                   double sigma_pixel, std::vector<MarginalPrior> *priors,
-                                                  const std::vector<PosePrior> *in_priors) {
+                                                  const std::vector<PosePrior> *in_priors,
+                                                  const std::vector<std::vector<RelativePose>> *in_relatives) {
   const int B = static_cast<int>(solvers.size());
   if (priors == nullptr) throw std::runtime_error("MarginalizeBatch: null output");
   priors->assign(static_cast<size_t>(B), MarginalPrior());
@@ -666,6 +719,9 @@ bool FullBundleAdjustmentSolver::MarginalizeBatch(const std::vector<FullBundleAd
   PackBatch(solvers, "MarginalizeBatch", false, &a);
   PriorArrays pa;
   PackPriors(solvers, "MarginalizeBatch", in_priors, sigma_pixel, &pa);
+  RelativeArrays ra;
+  PackRelatives(solvers, "MarginalizeBatch", in_relatives, sigma_pixel, &ra);
+  std::vector<uint8_t> left(ra.set ? ra.j.size() : 0, 0);
   std::vector<uint8_t> mark(a.pose_fixed.size(), 0), marg_pt(a.point_fixed.size(), 0);
   for (int b = 0; b < B; ++b)
     for (_BA_Pose *pose : marg_poses[b]) {
@@ -682,6 +738,8 @@ bool FullBundleAdjustmentSolver::MarginalizeBatch(const std::vector<FullBundleAd
   ba_batch *batch = nullptr;
   int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
   if (rc == 0) rc = SetPriors(batch, pa);
+  if (rc == 0) rc = SetRelatives(batch, ra);
+  if (rc == 0 && ra.set) rc = ba_batch_relative_marg_plan(batch, mark.data(), left.data());
   if (rc == 0) rc = ba_batch_marg_layout(batch, mark.data(), H_off.data(), b_off.data());
   if (rc == 0) {
     H.resize(static_cast<size_t>(H_off[B]));
@@ -706,6 +764,7 @@ bool FullBundleAdjustmentSolver::MarginalizeBatch(const std::vector<FullBundleAd
       if (!a.pose_fixed[a.pose_off[b] + p] && !mark[a.pose_off[b] + p]) out.kept_poses.push_back(s->poses_[p]);
     for (size_t q = 0; q < s->points_.size(); ++q)
       if (marg_pt[a.pt_off[b] + q]) out.marginalized_points.push_back(s->points_[q]);
+    if (ra.set) out.relatives_left.assign(left.begin() + ra.off[b], left.begin() + ra.off[b + 1]);
     out.dim = static_cast<int>(b_off[b + 1] - b_off[b]);
     const double w = 1.0 / (sigma_pixel * sigma_pixel * static_cast<double>(s->scaler_) * static_cast<double>(s->scaler_));
     const auto di = [s](int r) { return r % 6 < 3 ? static_cast<double>(s->scaler_) : 1.0; };

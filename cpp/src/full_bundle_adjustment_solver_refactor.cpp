@@ -47,6 +47,36 @@ bool FullBundleAdjustmentSolverRefactor::Solve(Options options, Summary *summary
   return impl_.Solve(options, summary);
 }
 
+bool FullBundleAdjustmentSolverRefactor::SolveBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers,
+                                                    Options options, std::vector<Summary> *summaries,
+                                                    const std::vector<PosePrior> *in_priors, double sigma_pixel,
+                                                    const std::vector<std::vector<RelativePose>> *in_relatives) {
+  if (options.solver_type != SolverType::LEVENBERG_MARQUARDT && options.solver_type != SolverType::GAUSS_NEWTON)
+    throw std::runtime_error(
+        "FullBundleAdjustmentSolverRefactor::SolveBatch: solver_type must be GAUSS_NEWTON or LEVENBERG_MARQUARDT");
+  // the mode holds for this call only: what Solve set before stays for the next Solve
+  std::vector<FullBundleAdjustmentSolver *> impls;
+  std::vector<bool> before;
+  for (FullBundleAdjustmentSolverRefactor *s : solvers) {
+    impls.push_back(s ? &s->impl_ : nullptr);
+    before.push_back(s ? s->impl_.gauss_newton_ : false);
+    if (s) s->impl_.SetGaussNewton(options.solver_type == SolverType::GAUSS_NEWTON);
+  }
+  const auto restore = [&] {
+    for (size_t k = 0; k < impls.size(); ++k)
+      if (impls[k]) impls[k]->SetGaussNewton(before[k]);
+  };
+  bool ok = false;
+  try {
+    ok = FullBundleAdjustmentSolver::SolveBatch(impls, options, summaries, in_priors, sigma_pixel, in_relatives);
+  } catch (...) {
+    restore();
+    throw;
+  }
+  restore();
+  return ok;
+}
+
 bool FullBundleAdjustmentSolverRefactor::SolveByGradientDescent(Options options, Summary *summary) {  // :1075-1367
   return impl_.Run(options, summary, true);
 }

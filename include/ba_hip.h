@@ -646,7 +646,10 @@ void ba_batch_destroy(ba_batch *b);
  * 2 sum_{j>k} x_j^T H_jk x_k, and the initial and every trial cost gain the prior's residual
  * norm sqrt(max(0, delta^T H delta - 2 b^T delta + c)).  n_obs (average error) and the block
  * count of the average step are unchanged: a prior is neither an observation nor a
- * parameter block. */
+ * parameter block.
+ * With relative-pose factors set (ba_batch_set_relative): their blocks are rebuilt from the
+ * accepted poses at every linearisation and join A_j, a_j, S_jk, the model and the costs the
+ * same way; see there. */
 int ba_batch_solve(ba_batch *b, const ba_options *opt, ba_iter_info *rows, int cap,
                    ba_batch_result *res);
 /* Covariance blocks of EVERY problem of the batch at the values the object holds (after
@@ -671,7 +674,8 @@ int ba_batch_solve(ba_batch *b, const ba_options *opt, ba_iter_info *rows, int c
  * alone and at any position of any batch, at any image width.  b, cov_pose36 and res are
  * checked for NULL before anything touches the GPU: -1 and ba_last_error.
  * With a prior set (ba_batch_set_prior): S includes the prior's H (lambda = 0) before it is
- * factored, so the blocks are the covariance given the window AND its past. */
+ * factored, so the blocks are the covariance given the window AND its past.
+ * With relative-pose factors set (ba_batch_set_relative): every factor joins S (lambda = 0). */
 typedef struct {
   int status, dropped_pivots;
 } ba_batch_cov_result;
@@ -716,7 +720,11 @@ int ba_batch_covariance(ba_batch *b, double huber, double *cov_pose36, double *c
  * values (H, g = b - H delta), joins the factors before the partial Cholesky, whichever of its
  * poses are marked or kept, so priors chain from window to window.  The output b is then at
  * the held values, which are the T_lin of the next prior.  The rows of a kept pose that
- * touches neither L nor the prior stay exactly zero; the layout and the plan are unchanged. */
+ * touches neither L nor the prior stay exactly zero; the layout and the plan are unchanged.
+ * With relative-pose factors set (ba_batch_set_relative): a factor joins exactly when at least
+ * one of its two poses is marked (see there); S'_mm may then be well conditioned where it was
+ * singular.  The rows of a kept pose that touches neither L, the prior nor a joining factor
+ * stay exactly zero. */
 typedef struct {
   int status, dropped_pivots, n_kept, n_marg_pose, n_marg_pt;
 } ba_batch_marg_result;
@@ -773,6 +781,68 @@ int ba_batch_prior_check(int B, const int32_t *pose_off, const uint8_t *pose_fix
 /* out4 = { problems with a prior in effect, their prior poses in all (total K), device bytes
  * of the priors, 0 } */
 int ba_batch_prior_info(ba_batch *b, int64_t out4[4]);
+/* Relative-pose factors between poses of a problem: odometry between keyframes, a loop closure
+ * between two keyframes that share no landmark, the pose part of a pre-integrated inertial
+ * delta.  They are more factors of ba_batch_solve, ba_batch_covariance and
+ * ba_batch_marginalize, next to the reprojections and the prior.  Problem p carries the
+ * factors rel_off[p] .. rel_off[p+1] - 1; several may name the same pair (summed in input
+ * order).  Factor f:
+ *   rel_j, rel_k  two DISTINCT poses of its problem, problem-local user indices; at least one
+ *                 of them optimisable.  A fixed pose receives nothing: the factor is then a
+ *                 unary factor on the other pose;
+ *   Z12           12 per factor, layout of ba_set_poses: the measurement of T_j T_k^-1;
+ *   Omega36       36 per factor, row-major 6x6 information matrix; only the lower triangle
+ *                 (row >= column) is ever read.
+ * Scaled units and the conventions of ba_batch_set_prior: T = T_jw, tangent xi = [v; omega] of
+ * T <- exp(xi) T, unit pixel noise.  Residual r = se3_log(T_j T_k^-1 Z^-1): the prior's delta
+ * with T_lin = Z T_k.  Jacobians, first order (exact at r = 0, no left-Jacobian correction:
+ * the approximation the prior makes): dr/dxi_j = I, dr/dxi_k = -Ad(T_j T_k^-1), where for
+ * T = (R, t) Ad = [[R, [t]x R], [0, R]].  With the solver's sign a = -J^T Omega r:
+ *   A_j += Omega,  A_k += Ad^T Omega Ad,  S_jk += -Omega Ad,  a_j += -Omega r,  a_k += Ad^T Omega r.
+ * The blocks depend on the poses and are rebuilt at every linearisation.  The diagonal
+ * contributions join A_j before the damping (their diagonal is multiplied by 1 + lambda with
+ * the rest of A_j), the off-diagonal block joins S undamped, the quadratic model gains
+ * 2 x_j^T S_jk x_k.  Every cost (initial and trial) gains sqrt(max(0, r^T Omega r)) per
+ * factor: one residual, its norm added as an observation's is; n_obs and the block count of
+ * the average step do not change.  There is NO robust weight on relative factors: the Huber
+ * threshold acts on reprojections only.  Mind the weights in an LM run: the controller compares a
+ * difference of residual NORMS, which grows like sqrt(w) with a factor's weight w, with the
+ * quadratic model, which grows like w; one factor some 1e6 times heavier than the reprojection
+ * blocks makes the gain ratio about 1e-2 for a perfect step, and every step is rejected.  Scale
+ * Omega to the problem, or run such a batch in Gauss-Newton mode.
+ * ba_batch_marginalize: a factor joins exactly when at least one of its two poses is marked
+ * (optimisable or fixed): it leaves the window with that pose, linearised at the held values,
+ * its blocks in S' and r' before the partial factorisation.  A factor between two unmarked
+ * poses does not join: the caller carries it into the next window
+ * (ba_batch_relative_marg_plan).  Relative factors select no landmarks.  The rows and columns
+ * of a kept pose that touches L, the prior or a joining factor are non-zero, those of every
+ * other kept pose stay exactly zero.
+ * The arrays are copied to the device once, with a scratch of 1008 bytes per factor;
+ * rel_off == NULL clears the factors; they survive ba_batch_update_values.  There is no limit
+ * on the number of factors of a problem.  A batch without factors, and a problem without
+ * factors whatever its neighbours hold, computes exactly what it computed before: same
+ * results, same bits.  One writer per element, fixed summation order, no floating-point
+ * atomics: the same bits run to run, alone and at any position of any batch.  Factors given
+ * to a problem whose status is 2 are accepted and ignored.  Validation happens before anything
+ * touches the GPU (-1 and ba_last_error, naming the problem and the factor): offsets start at
+ * 0 and never decrease; indices in range; j != k; not both fixed; every value finite.  A call
+ * refused by the validation changes nothing: the factors set before it stay in effect.  A
+ * call that fails later (device allocation, upload) leaves the batch without factors. */
+int ba_batch_set_relative(ba_batch *b, const int32_t *rel_off /* B+1 */, const int32_t *rel_j,
+                          const int32_t *rel_k, const double *Z12, const double *Omega36);
+/* Host-only (no GPU): the validation of ba_batch_set_relative for a batch described by
+ * pose_off (B+1) and pose_fixed (NULL: none fixed).  0, or -1 and ba_last_error. */
+int ba_batch_relative_check(int B, const int32_t *pose_off, const uint8_t *pose_fixed,
+                            const int32_t *rel_off, const int32_t *rel_j, const int32_t *rel_k,
+                            const double *Z12, const double *Omega36);
+/* out4 = { problems with factors in effect, factors in effect, device bytes of the factor
+ * records plus their scratch, 0 } */
+int ba_batch_relative_info(ba_batch *b, int64_t out4[4]);
+/* Host-only: rel_leaves[f] = 1, one byte per factor given to ba_batch_set_relative in input
+ * order, where factor f joins ba_batch_marginalize under this marking and leaves with the
+ * marked poses; 0 where the caller carries it into the next window (and for the ignored
+ * factors of a problem whose status is 2). */
+int ba_batch_relative_marg_plan(ba_batch *b, const uint8_t *marg_pose, uint8_t *rel_leaves);
 /* new values for the same structure, concatenated user order; NULL = keep */
 int ba_batch_update_values(ba_batch *b, const double *T_jw12, const double *X3);
 int ba_batch_get_poses(ba_batch *b, double *T_jw12);
