@@ -175,8 +175,8 @@ int download(std::vector<T> &out, const T *dev, size_t n, hipStream_t s) {
 
 // Device set-up of a dense schedule: the work lists of `dd`, its column -> x map col_x
 // (npad entries), the solution in column order xc, the dropped-pivot counter, the order,
-// flags and tickets of the dataflow sweeps and the k_chol_dag / k_chol_look items and
-// counters; fixes the launch plans from the handle's dense knobs.  Everything is allocated on
+// flags and tickets of the dataflow sweeps, the k_chol_dag / k_chol_look items and
+// counters and the step records of the cone sweep; fixes the launch plans from the handle's dense knobs.  Everything is allocated on
 // the handle (h->upload / h->dalloc, in h->allocs).
 int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::vector<int> &col_x,
                           ba::DenseDev &dd) {
@@ -192,8 +192,8 @@ int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::
     return -1;
   HIP_TRY(hipMemset(dd.xc, 0, npad * sizeof(double)));
   HIP_TRY(hipMemset(dd.bad_pivots, 0, sizeof(int)));
-  for (int flow_ok = 0; flow_ok < 2; ++flow_ok) dd.plan[flow_ok] = ba::dense_launch_plan(sc, h->knobs.dense, flow_ok != 0);
-  const ba::DenseLaunchPlan &plan = dd.plan[1];  // (plan[0] has the same tail and lists: it only launches per level)
+  for (int flow_ok = 0; flow_ok < 2; ++flow_ok) dd.plan[flow_ok] = ba::dense_launch_plan(sc, h->knobs.dense, flow_ok != 0, /*lists_fit=*/true, h->knobs.cone.want);
+  const ba::DenseLaunchPlan &plan = dd.plan[1];  // (plan[0] has the same tail, lists and cone sweep: its other launches are per level)
   std::vector<int> order;
   ba::dense_flow_order(sc, plan, order);
   dd.flow_gen = 0;
@@ -215,6 +215,11 @@ int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::
     HIP_TRY(hipMemset(dd.fwd_cnt, 0, need.size() * sizeof(int)));
     HIP_TRY(hipMemset(dd.dag_dflags, 0, need.size() * sizeof(int)));
     HIP_TRY(hipMemset(dd.dag_tcnt, 0, need.size() * sizeof(int)));
+  }
+  if (plan.back_cone) {
+    ba::DenseCone cone;
+    ba::dense_cone_lists(sc, plan, cone);
+    if (h->upload(R, &dd.cone_rec, cone.rec)) return -1;
   }
   return 0;
 }
@@ -497,10 +502,14 @@ int build_dense_system(ba_handle *h) {
   if (h->upload(Mem::Resident, &d.pose_col, h->pose_col_h) || upload_dense_schedule(h, sc, col_x, dd)) return -1;
   d.col_x = dd.col_x;
   if (h->knobs.plan.times && dd.dag_items) fprintf(stderr, "[finalize] k_chol_dag: %d items\n", dd.plan[1].n_dag_items);
-  if (stats)
+  if (stats) {
     fprintf(stderr, "dense launch plan: nb%d forward %s backward %s tail %d columns%s\n", nb,
             ba::dense_fwd_name(dd.plan[1].fwd), ba::dense_back_name(dd.plan[1].back), dd.plan[1].tail_cols,
             dd.plan[1].tail_pair ? " (pair)" : "");
+    fprintf(stderr, "dense cone sweep: %s (%d leaves, longest cone %d, %d steps for %d non-tail tiles, max_rows %d)\n",
+            dd.plan[1].back_cone ? "taken instead" : "not taken", dd.plan[1].cone_leaves, dd.plan[1].cone_max,
+            dd.plan[1].cone_steps, dd.plan[1].back_t_end, sc.max_rows);
+  }
   // tiles (re)initialised per iteration: factor pattern + diagonal + rhs row
   std::vector<int> ztI, ztJ;
   for (int p = 0; p < ncb; ++p) {
@@ -1522,7 +1531,9 @@ int ba_dense_spd_solve(ba_handle *h, int n, const double *A, const double *b,
                        double *x, double *ms) {
   if (!h || n <= 0 || !A || !b || !x) return fail("ba_dense_spd_solve: bad argument");
   if (use_device(h)) return -1;
-  const int nb = 64;  // a dense matrix has one tile per level either way: fewer, larger tiles
+  // a dense matrix has one tile per level either way: fewer, larger tiles (BA_DENSE_NB=32 for a
+  // sparse system, or to test the 32-column kernels alone)
+  const int nb = h->knobs.dense.nb == 32 ? 32 : 64;
   const int ncb = (n + nb - 1) / nb;
   const int npad = ncb * nb;
   const int ld = npad + nb;
@@ -1720,7 +1731,7 @@ int ba_covariance(ba_handle *h, double huber, int n_pose_sel, const int32_t *pos
     // that the whole factor is left in the image.  Same arithmetic.
     const ba::DenseDev &dd = h->ddev;
     ba::dense_factor_solve(d.L, d.npad, d.ld, d.Ldiag, d.x, &d.ctrl->done, sc, dd,
-                           ba::dense_launch_plan_no_tail(sc, h->knobs.dense, dd.flow_ok, dd.plan[1]), h->stream);
+                           ba::dense_launch_plan_no_tail(sc, h->knobs.dense, dd.flow_ok, dd.plan[1], h->knobs.cone.want), h->stream);
   }
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(&bad_now, h->ddev.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));

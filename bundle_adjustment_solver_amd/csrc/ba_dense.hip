@@ -151,6 +151,7 @@ struct Nb32 {
   static constexpr auto back_flow_ordered = nb32::k_chol_back_flow<true>;
   static constexpr auto back_flow_gather = nb32::k_chol_back_flow<false>;
   static constexpr auto back = nb32::k_chol_back;
+  static constexpr auto back_cone = nb32::k_chol_back_cone;
 };
 struct Nb64 {
   static constexpr int NP = nb64::NP;
@@ -164,6 +165,7 @@ struct Nb64 {
   static constexpr auto back_flow_ordered = nb64::k_chol_back_flow<true>;
   static constexpr auto back_flow_gather = nb64::k_chol_back_flow<false>;
   static constexpr auto back = nb64::k_chol_back;
+  static constexpr auto back_cone = nb64::k_chol_back_cone;
 };
 
 // Level-scheduled, structure-aware blocked Cholesky (see ba_dense_sched.h): the forward
@@ -240,6 +242,12 @@ void run_plan(double *L, int npad, int ld, double *Ldiag, double *x, const int *
               done, bad);
   const int n_back = pl.back_t_end;  // positions of the dataflow launch, top level first in dd.flow_order
   const bool counted = pl.fwd == DenseFwd::kLook || pl.fwd == DenseFwd::kDag;  // (the sweep resets fwd_cnt)
+  if (pl.back_cone) {  // (decided with back_t_end > 0: an empty sweep launches nothing)
+    BA_LAUNCH(K_CHOL_BACK, K::back_cone, dim3(pl.cone_leaves), dim3(256), s, L, ld, npad, dd.cone_rec, pl.cone_max,
+              pl.back_t_end, (sc.ncb - pl.back_t_end) * sc.nb, Ldiag, dd.xc, x, dd.col_x, done,
+              counted ? dd.fwd_cnt : nullptr, dd.n_fwd_cnt);
+    return;
+  }
   switch (pl.back) {
     case DenseBack::kFlowGather:
     case DenseBack::kFlowOrdered:

@@ -186,6 +186,41 @@ void build_one(int ncb, const std::vector<uint8_t> &adj_in, bool natural_order, 
   }
 }
 
+// Leaves and cones of the non-tail positions [0, t_end) (see DenseCone): calls
+// visit(index of the leaf, cone) per leaf in ascending position, the cone in descending
+// position.  Stops and returns false at the first cone of more than max_len steps.
+template <class Visit>
+bool walk_cones(const DenseSchedule &sc, int t_end, int max_len, Visit visit) {
+  std::vector<uint8_t> is_row((size_t)t_end, 0);
+  for (int q = 0; q < t_end; ++q)
+    for (int a = sc.row_ptr[q]; a < sc.row_ptr[q + 1]; ++a)
+      if (sc.rows[a] < t_end) is_row[sc.rows[a]] = 1;
+  std::vector<int> seen((size_t)t_end, -1), cone, stack;
+  int n_leaf = 0;
+  for (int p = 0; p < t_end; ++p) {
+    if (is_row[p]) continue;
+    cone.clear();
+    stack.assign(1, p);
+    seen[p] = p;
+    while (!stack.empty()) {
+      const int q = stack.back();
+      stack.pop_back();
+      cone.push_back(q);
+      if ((int)cone.size() > max_len) return false;
+      for (int a = sc.row_ptr[q]; a < sc.row_ptr[q + 1]; ++a) {
+        const int I = sc.rows[a];
+        if (I < t_end && seen[I] != p) {
+          seen[I] = p;
+          stack.push_back(I);
+        }
+      }
+    }
+    std::sort(cone.begin(), cone.end(), [](int a, int b) { return a > b; });
+    visit(n_leaf++, cone);
+  }
+  return true;
+}
+
 }  // namespace
 
 void build_dense_schedule(int ncb, const std::vector<uint8_t> &adj, bool natural_order, int nb,
@@ -228,6 +263,13 @@ DenseKnobs DenseKnobs::from_env() {
   return k;
 }
 
+ConeKnobs ConeKnobs::from_env() {
+  const char *v = getenv("BA_DENSE_CONE");
+  ConeKnobs k;
+  k.want = !(v && v[0] == '0');
+  return k;
+}
+
 const char *dense_fwd_name(DenseFwd f) {
   static const char *const names[] = {"look", "dag", "level_flow", "diag_trsm", "split"};
   return names[(int)f];
@@ -238,7 +280,7 @@ const char *dense_back_name(DenseBack b) {
 }
 
 DenseLaunchPlan dense_launch_plan(const DenseSchedule &sc, const DenseKnobs &knobs, bool flow_allowed,
-                                  bool lists_fit) {
+                                  bool lists_fit, bool cone_allowed) {
   DenseLaunchPlan p;
   p.force_ticket = knobs.force_ticket;
   p.split = knobs.want_split || sc.max_rows > dense_fused_max_rows(sc.nb);
@@ -276,13 +318,57 @@ DenseLaunchPlan dense_launch_plan(const DenseSchedule &sc, const DenseKnobs &kno
         : flow ? DenseFwd::kLevelFlow : DenseFwd::kDiagTrsm;
   p.back = !flow || p.back_t_end == 0 ? DenseBack::kPerLevel
          : sc.max_rows <= kBackGatherMaxRows ? DenseBack::kFlowGather : DenseBack::kFlowOrdered;
+  // the cone sweep: measured on the schedule itself, not assumed from its pattern
+  if (cone_allowed && lists_fit && p.back_t_end > 0 && sc.max_rows <= kBackGatherMaxRows) {
+    const bool short_cones = walk_cones(sc, p.back_t_end, kConeMaxLen, [&](int, const std::vector<int> &cone) {
+      ++p.cone_leaves;
+      p.cone_max = std::max(p.cone_max, (int)cone.size());
+      p.cone_steps += (int)cone.size();
+    });
+    if (!short_cones) p.cone_leaves = p.cone_max = p.cone_steps = 0;
+    p.back_cone = short_cones && p.cone_steps <= kConeMaxWork * p.back_t_end;
+  }
   return p;
 }
 
+static_assert(4 + kBackGatherMaxRows - 1 <= kConeRec, "a cone record holds every row tile of a gathered column");
+static_assert(kConeTailSlots * 32 >= kTailCols, "a slot per tile of the tail block");
+
+void dense_cone_lists(const DenseSchedule &sc, const DenseLaunchPlan &plan, DenseCone &cone) {
+  const int t_end = plan.back_t_end, stride = plan.cone_max;
+  cone = DenseCone();
+  cone.writer.assign((size_t)t_end, -1);
+  std::vector<int> step_of((size_t)t_end, -1);  // position -> step in the current cone
+  walk_cones(sc, t_end, stride, [&](int leaf, const std::vector<int> &c) {
+    const int len = (int)c.size();
+    cone.leaf.push_back(c.back());
+    cone.len.push_back(len);
+    cone.rec.resize((size_t)(leaf + 1) * stride * kConeRec, -1);
+    for (int k = 0; k < len; ++k) step_of[c[k]] = k;
+    for (int k = 0; k < len; ++k) {
+      const int q = c[k];
+      int *r = &cone.rec[((size_t)leaf * stride + k) * kConeRec];
+      int nrow = 0;
+      for (int a = sc.row_ptr[q]; a < sc.row_ptr[q + 1] && sc.rows[a] < sc.ncb; ++a, ++nrow) {
+        const int I = sc.rows[a];
+        const int slot = I < t_end ? kConeTailSlots + step_of[I] : I - t_end;
+        r[4 + nrow] = I | (slot << kConeSlotShift);
+      }
+      r[0] = q;
+      r[1] = nrow;
+      r[2] = cone.writer[q] < 0 ? 1 : 0;
+      r[3] = len;
+      if (cone.writer[q] < 0) cone.writer[q] = leaf;
+      const int fill = nrow > 0 ? r[4 + nrow - 1] : (q | ((kConeTailSlots + k) << kConeSlotShift));
+      for (int a = nrow; a < kBackGatherMaxRows - 1; ++a) r[4 + a] = fill;
+    }
+  });
+}
+
 DenseLaunchPlan dense_launch_plan_no_tail(const DenseSchedule &sc, DenseKnobs knobs, bool flow_allowed,
-                                          const DenseLaunchPlan &uploaded) {
+                                          const DenseLaunchPlan &uploaded, bool cone_allowed) {
   knobs.want_tail = false;
-  return dense_launch_plan(sc, knobs, flow_allowed, /*lists_fit=*/uploaded.tail_levels == 0);
+  return dense_launch_plan(sc, knobs, flow_allowed, /*lists_fit=*/uploaded.tail_levels == 0, cone_allowed);
 }
 
 void dense_flow_order(const DenseSchedule &sc, const DenseLaunchPlan &plan, std::vector<int> &order) {

@@ -81,6 +81,18 @@ constexpr int kBackGatherMaxRows = 12;
 // Row tiles per column (incl. the rhs block) that a tile's own workgroup solves: they must
 // fit its prefetched passes, 4 passes x (4 waves / (nb / 16)) tiles.
 inline int dense_fused_max_rows(int nb) { return 4 * (4 / (nb / 16)); }
+// The cone sweep (k_chol_back_cone: one workgroup per leaf solves its own chain of ancestors,
+// no hand-off between workgroups) is taken while the longest cone has at most kConeMaxLen
+// steps and the steps of all cones together are at most kConeMaxWork times the non-tail tiles
+// (launch-path table, has the numbers behind both).
+constexpr int kConeMaxLen = 8;
+constexpr double kConeMaxWork = 4.0;
+// One step of a cone is a record of kConeRec ints (see DenseCone); a row tile is packed as
+// position | slot << kConeSlotShift.
+constexpr int kConeRec = 16;
+constexpr int kConeSlotShift = 20;
+// Slots of x in front of a cone's own steps: the tiles of the tail block (kTailCols / 32).
+constexpr int kConeTailSlots = 3;
 
 // The BA_DENSE_* environment variables (part of Knobs, ba_knobs.h: read once per handle).
 struct DenseKnobs {
@@ -94,6 +106,14 @@ struct DenseKnobs {
   int nb = 0;                                   // NB=32|64: tile order (0: dense_pick_tile_order decides)
   char order = 0;                               // ORDER=strict|relaxed: 's' / 'r' (developer knob)
   static DenseKnobs from_env();
+};
+
+// BA_DENSE_CONE=0 forbids the cone sweep (k_chol_back_cone).  A record of its own beside
+// DenseKnobs (Knobs::cone, ba_knobs.h: read once per handle), handed to dense_launch_plan
+// as `cone_allowed`.
+struct ConeKnobs {
+  bool want = true;
+  static ConeKnobs from_env();
 };
 
 enum class DenseFwd {
@@ -121,22 +141,48 @@ struct DenseLaunchPlan {
   DenseFwd fwd = DenseFwd::kSplit;
   DenseBack back = DenseBack::kPerLevel;
   bool force_ticket = false;
+  // The backward sweep is ONE k_chol_back_cone launch of cone_leaves workgroups instead of
+  // `back` (which keeps its value: the form taken when the cone sweep is forbidden).  It has no
+  // generation number and no flags, so it does not depend on `flow_allowed`.
+  bool back_cone = false;
+  int cone_leaves = 0, cone_max = 0, cone_steps = 0;  // leaves, steps of the longest cone, of all cones
 };
 
 // The one place that decides.  `flow_allowed`: false while a captured graph is in use (the
 // generation number of a dataflow launch is a kernel argument).  `lists_fit`: the uploaded
-// dataflow lists (dense_flow_order, dense_dag_items) were built for this plan's tail; a plan
-// whose tail differs from the uploaded one takes no dataflow launch.
+// dataflow lists (dense_flow_order, dense_dag_items) and cone lists (dense_cone_lists) were
+// built for this plan's tail; a plan whose tail differs from the uploaded one takes no
+// dataflow launch and no cone sweep.
+// `cone_allowed`: ConeKnobs::want.
 DenseLaunchPlan dense_launch_plan(const DenseSchedule &sc, const DenseKnobs &knobs, bool flow_allowed,
-                                  bool lists_fit = true);
+                                  bool lists_fit = true, bool cone_allowed = true);
 // The plan that hands no level to k_chol_tail (which keeps its block's factor in LDS: only
 // x leaves), for a caller that needs the whole factor in the image.  `uploaded`: the plan
 // the device lists were built for.
 DenseLaunchPlan dense_launch_plan_no_tail(const DenseSchedule &sc, DenseKnobs knobs, bool flow_allowed,
-                                          const DenseLaunchPlan &uploaded);
+                                          const DenseLaunchPlan &uploaded, bool cone_allowed = true);
 
 // Positions of the backward sweep's dataflow launch, top level first (plan.back_t_end of them).
 void dense_flow_order(const DenseSchedule &sc, const DenseLaunchPlan &plan, std::vector<int> &order);
+// Lists of the cone sweep (k_chol_back_cone).  A LEAF is a non-tail position that is no row
+// tile of another non-tail position; its CONE is the closure of rows[] over the non-tail
+// positions, in descending position, the leaf itself last: every row tile of a step is an
+// earlier step of the same cone or a tile of the tail block.  A workgroup keeps x in slots of
+// LDS: slot I - back_t_end for a tail tile I (read from xc), slot kConeTailSlots + k for step k.
+//   rec[kConeRec * (leaf * plan.cone_max + k) ..] = { position, nrow (without the rhs block),
+//       1 if this leaf stores the position's x, steps of the cone,
+//       row tiles as position | slot << kConeSlotShift (entries beyond nrow repeat the last
+//       one; with no row tile: the step itself), -1 pad }
+// — a fixed stride per leaf, so that a workgroup reaches a step after ONE load that depends
+// on nothing but its block index.  Exactly one leaf, the lowest whose cone holds it, stores a
+// position: writer[position] = index of that leaf.  Call only if plan.back_cone.
+struct DenseCone {
+  std::vector<int> leaf;    // positions of the leaves, ascending
+  std::vector<int> len;     // steps per leaf
+  std::vector<int> rec;
+  std::vector<int> writer;  // per non-tail position
+};
+void dense_cone_lists(const DenseSchedule &sc, const DenseLaunchPlan &plan, DenseCone &cone);
 // Work list of the three-kernel path as one dataflow launch (k_chol_dag): items = {kind, index}
 // pairs in lookahead order (kind 0: tile position, 1: TRSM item, 2: update target), pre[tg] =
 // updates of earlier levels on the target's column, need[p] = all updates on position p's column,

@@ -1017,3 +1017,192 @@ __global__ __launch_bounds__(256) void k_chol_back_flow(const double *L, int ld,
   }
 }
 
+// ---- backward sweep without hand-offs: one workgroup per LEAF --------------------------
+// On narrow patterns the dataflow sweep above is a chain of hops between workgroups (store,
+// drain, flag, poll, load: ~3.8 us each at C4) around a few hundred flops.  Here the
+// workgroup of a leaf solves its whole CONE itself (ba_dense_sched.h: DenseCone), top
+// ancestor first, starting from the x that k_chol_tail left a launch ago: ancestors shared
+// by several leaves are solved redundantly, x between steps stays in LDS, and nothing waits
+// for another workgroup — no flags, no tickets, no polls, no generation number.  A step is
+// the gather and the wave-0 block back substitution of k_chol_back, operation by operation
+// (row tiles in list order, the same fma chain, the same butterfly per value, the same panel
+// loop): x is bit-identical to the other sweeps.
+// Everything a step reads besides x is factor data of earlier launches, written on other
+// CUs: a load of it takes ~3 us, three times the arithmetic of a step.  The leaf's records
+// go to LDS first; the operands of the first kConeDepth steps are requested before the
+// first step, those of step k + kConeDepth as soon as step k has released its registers.
+// A request is unconditional (every thread loads the wave-0 operands, the first PF row tiles
+// are always loaded: the records repeat the last one; past the last step the last step is
+// requested once more): under a branch the compiler waits for ALL loads in flight at the
+// next use, i.e. for the request it has just issued.  Exactly one leaf stores a position's x
+// (plain stores, after the loop).
+// (registers: a step in flight holds 60 VGPRs at order 32 and 120 at order 64; two steps with two row tiles spill at order 64)
+constexpr int kConeDepth = NB == 32 ? 4 : 2;  // steps in flight
+constexpr int kConePF = NB == 32 ? 4 : 1;     // row tiles of a step that are requested with it
+struct ConeOps {
+  double lop[NP][NP][4];  // [p][u][rr], u > p
+  double eop[NP][4], zv[NP];
+  double lpre[kConePF][BR];
+};
+__global__ __launch_bounds__(256) void k_chol_back_cone(const double *L, int ld, int npad,
+                                                        const int *__restrict__ cone_rec, int stride,
+                                                        int tail_t0, int n_tail_cols,
+                                                        const double *__restrict__ ws_all,
+                                                        double *xc, double *x,
+                                                        const int *__restrict__ col_x,
+                                                        const int *done, int *fwd_cnt, int n_cnt) {
+  using ::ba::kConeMaxLen;
+  using ::ba::kConeRec;
+  using ::ba::kConeSlotShift;
+  using ::ba::kConeTailSlots;
+  constexpr int PF = kConePF, D = kConeDepth;
+  constexpr int kSlotMask = (1 << kConeSlotShift) - 1;
+  static_assert(kConeMaxLen * kConeRec <= 256, "one pass of the workgroup fetches a leaf's records");
+  __shared__ double xsl[(kConeTailSlots + kConeMaxLen) * NB];  // x per slot: tail tiles, then the steps
+  __shared__ double part[NB];
+  __shared__ int s_rec[kConeMaxLen * kConeRec];    // the records of this leaf's steps
+  const int tid = threadIdx.x;
+  const int i = tid & 15, q = (tid >> 4) & 3;      // (wave 0's operand lanes; the other waves load the same)
+  const int r = tid % NB, cg = tid / NB;
+  const int dn = done ? *done : 0;
+  if (tid < stride * kConeRec) s_rec[tid] = cone_rec[(size_t)blockIdx.x * stride * kConeRec + tid];
+  if (tid < n_tail_cols) xsl[tid] = xc[tail_t0 * NB + tid];  // x of the tail block (k_chol_tail)
+  if (dn) return;
+  // (the forward sweep's column counters: zero again for the next solve, as in k_chol_back_flow)
+  if (fwd_cnt && blockIdx.x == 0)
+    for (int e = tid; e < n_cnt; e += 256) fwd_cnt[e] = 0;
+  __syncthreads();
+  const int nstep = s_rec[3];
+  auto request = [&](ConeOps &o, int k) {
+    const int *rk = s_rec + kConeRec * k;
+    const int t = rk[0], k0 = t * NB;
+    const double *Ld = ws_all + (size_t)t * WS;
+    const double *Et = Ld + NB * NB;
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int u = p + 1; u < NP; ++u)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr)
+          o.lop[p][u][rr] = Ld[(16 * p + i) * NB + 16 * u + 4 * q + rr];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc) o.eop[p][cc] = Et[p * 256 + i * 16 + 4 * q + cc];
+      o.zv[p] = L[(size_t)(k0 + 16 * p + i) * ld + npad];
+    }
+#pragma unroll
+    for (int a = 0; a < PF; ++a) {
+      const double *src = L + (size_t)(k0 + BR * cg) * ld + (rk[4 + a] & kSlotMask) * NB + r;
+#pragma unroll
+      for (int u = 0; u < BR; ++u) o.lpre[a][u] = src[(size_t)u * ld];
+    }
+  };
+  // (where the stores after the loop go in x: asked for now, not between the last step and the
+  //  stores — at order 32; at order 64 the registers are all taken)
+  constexpr int kOut = (kConeMaxLen * NB + 255) / 256;
+  constexpr bool kOutAhead = NB == 32;
+  int xi[kOut];
+#pragma unroll
+  for (int j = 0; j < kOut; ++j) {
+    const int e = tid + 256 * j, k = e / NB < nstep ? e / NB : nstep - 1;
+    xi[j] = kOutAhead ? col_x[s_rec[kConeRec * k] * NB + e % NB] : -1;
+  }
+  ConeOps ring[D];
+#pragma unroll
+  for (int d = 0; d < D; ++d) request(ring[d], d < nstep ? d : nstep - 1);
+  // (straight-line code, one exit per step: across a loop's back edge the compiler's count of the
+  //  loads in flight is a worst case, and every D-th step waited for the request just issued)
+  static_assert(kConeMaxLen % D == 0, "whole turns of the ring");
+#pragma unroll
+  for (int kb = 0; kb < kConeMaxLen; kb += D) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const int k = kb + d;
+      if (k >= nstep) break;
+      ConeOps &o = ring[d];
+      const int *rk = s_rec + kConeRec * k;
+      const int t = rk[0], nrow = rk[1], k0 = t * NB;
+      double *xs = xsl + (kConeTailSlots + k) * NB;
+      {
+        double s[BR];
+#pragma unroll
+        for (int u = 0; u < BR; ++u) s[u] = 0.0;
+        double xv[PF];
+#pragma unroll
+        for (int a = 0; a < PF; ++a) xv[a] = xsl[(rk[4 + a] >> kConeSlotShift) * NB + r];
+#pragma unroll
+        for (int a = 0; a < PF; ++a)
+          if (a < nrow) {
+#pragma unroll
+            for (int u = 0; u < BR; ++u) s[u] = fma(o.lpre[a][u], xv[a], s[u]);
+          }
+        for (int a = PF; a < nrow; ++a) {
+          const int cd = rk[4 + a];
+          const double *src = L + (size_t)(k0 + BR * cg) * ld + (cd & kSlotMask) * NB + r;
+          const double xa = xsl[(cd >> kConeSlotShift) * NB + r];
+          double lv[BR];
+#pragma unroll
+          for (int u = 0; u < BR; ++u) lv[u] = src[(size_t)u * ld];
+#pragma unroll
+          for (int u = 0; u < BR; ++u) s[u] = fma(lv[u], xa, s[u]);
+        }
+        // fold the NB row lanes of a group (xor butterfly: fixed order per value; the BR values of a
+        // thread go through it side by side), lane r == 0 keeps the sums
+#pragma unroll
+        for (int off = NB / 2; off >= 1; off >>= 1)
+#pragma unroll
+          for (int u = 0; u < BR; ++u) s[u] += __shfl_xor(s[u], off, 64);
+        if (r == 0) {
+#pragma unroll
+          for (int u = 0; u < BR; ++u) part[BR * cg + u] = s[u];
+        }
+      }
+      __syncthreads();
+      if (tid < 64) {
+#pragma unroll
+        for (int p = NP - 1; p >= 0; --p) {
+          double acc = 0.0;
+#pragma unroll
+          for (int u = p + 1; u < NP; ++u)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+              const int row = 16 * u + 4 * q + rr;
+              acc += o.lop[p][u][rr] * xs[row];
+            }
+          acc += __shfl_xor(acc, 16, 64);
+          acc += __shfl_xor(acc, 32, 64);
+          const int col = 16 * p + i;
+          const double below = part[col];
+          const double wv = (o.zv[p] - below) - acc;
+          double px = 0.0;
+#pragma unroll
+          for (int cc = 0; cc < 4; ++cc) {
+            const int c2 = 4 * q + cc;
+            px += o.eop[p][cc] * __shfl(wv, c2, 64);
+          }
+          px += __shfl_xor(px, 16, 64);
+          px += __shfl_xor(px, 32, 64);
+          if (q == 0) xs[16 * p + i] = px;
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+      }
+      request(o, k + D < nstep ? k + D : nstep - 1);  // (past the end: the last step's once more, not a branch)
+      __syncthreads();
+    }
+  }
+  // the x this leaf is the writer of, in column order and in pose order
+#pragma unroll
+  for (int j = 0; j < kOut; ++j) {
+    const int e = tid + 256 * j, k = e / NB, col = e % NB;
+    if (e < nstep * NB && s_rec[kConeRec * k + 2]) {
+      const int t = s_rec[kConeRec * k];
+      const double v = xsl[(kConeTailSlots + k) * NB + col];
+      xc[t * NB + col] = v;
+      const int xo = kOutAhead ? xi[j] : col_x[t * NB + col];
+      if (xo >= 0) x[xo] = v;
+    }
+  }
+}

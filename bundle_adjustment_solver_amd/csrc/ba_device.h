@@ -325,6 +325,7 @@ struct DenseDev {
   int n_fwd_cnt = 0;
   int *dag_items = nullptr, *dag_ntrsm = nullptr, *dag_dflags = nullptr, *dag_tcnt = nullptr;
   int *look_need = nullptr;  // k_chol_look: per position, the previous level's targets in its column
+  int *cone_rec = nullptr;   // k_chol_back_cone: the step records of every leaf (DenseCone::rec), if plan[1].back_cone
   mutable int flow_gen = 0;
   // what dense_factor_solve launches (ba_dense_sched.h), as decided when the schedule was
   // uploaded: plan[flow_ok]

@@ -39,6 +39,7 @@ struct RunKnobs {
 struct Knobs {
   PlanKnobs plan;
   DenseKnobs dense;
+  ConeKnobs cone;
   RunKnobs run;
   static Knobs from_env();
 };
@@ -63,6 +64,7 @@ inline Knobs Knobs::from_env() {
   k.plan.stats = is_set("BA_PLAN_STATS");
   k.plan.times = is_set("BA_PLAN_TIMES");
   k.dense = DenseKnobs::from_env();
+  k.cone = ConeKnobs::from_env();
   k.run.force_side = is_one("BA_FORCE_SIDE");
   k.run.overlap = !is_one("BA_NO_OVERLAP");
   k.run.graph = is_one("BA_GRAPH");

@@ -165,7 +165,7 @@ std::vector<ba::NamedPtr> pointers_used_outside_window(const ba_handle *h) {
           BA_PTR(dd.row_desc), BA_PTR(dd.col_x), BA_PTR(dd.xc), BA_PTR(dd.bad_pivots), BA_PTR(dd.flow_order),
           BA_PTR(dd.flow_flags), BA_PTR(dd.flow_ticket), BA_PTR(dd.fwd_flags), BA_PTR(dd.fwd_ticket),
           BA_PTR(dd.upd_pre), BA_PTR(dd.col_need), BA_PTR(dd.fwd_cnt), BA_PTR(dd.dag_items), BA_PTR(dd.dag_ntrsm),
-          BA_PTR(dd.dag_dflags), BA_PTR(dd.dag_tcnt), BA_PTR(dd.look_need)};
+          BA_PTR(dd.dag_dflags), BA_PTR(dd.dag_tcnt), BA_PTR(dd.look_need), BA_PTR(dd.cone_rec)};
 #undef BA_PTR
 }
 
