@@ -96,6 +96,14 @@ class BaBatchMargResult(C.Structure):
                 ("n_marg_pose", C.c_int), ("n_marg_pt", C.c_int)]
 
 
+class BaPointResult(C.Structure):
+    """ba_point_result — one landmark of ba_point_only (status 0 = solved, 1 = non-finite
+    input, 2 = no observations, 3 = degenerate triangulation; X left as given unless 0)."""
+    _fields_ = [("n_iter", C.c_int), ("converged", C.c_int), ("n_rows", C.c_int),
+                ("status", C.c_int), ("n_behind", C.c_int), ("dropped_pivots", C.c_int),
+                ("cost0", C.c_double), ("cost", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                            C.c_int64, C.c_void_p)
 
@@ -272,6 +280,12 @@ SIGNATURES = {
     "ba_batch_scratch_bytes": (C.c_int, [_P, _I64]),
     "ba_batch_plan_problem": (C.c_int, [C.c_int, _U8, C.c_int, _U8, C.c_int64, _I32,
                                         _I32, _I32, _I32, _U8, _I32, _I32]),
+    "ba_point_only": (C.c_int, [_P, C.c_int, _D, _D, C.c_int, _D, C.c_int, _I64, _I32, _I32,
+                                _D, _U8, _D, C.POINTER(BaOptions), C.POINTER(BaIterInfo),
+                                C.c_int, C.POINTER(BaPointResult)]),
+    "ba_point_only_check": (C.c_int, [C.c_int, C.c_int, C.c_int, _I64, _I32, _I32]),
+    "ba_point_only_team": (C.c_int, [C.c_int]),
+    "ba_point_only_last_ms": (C.c_int, [_D]),
 }
 
 _lib = None

@@ -18,7 +18,8 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import BaIterInfo, BaOptions, BaPoIter, BaPoResult, check
+from ._lib import (BaIterInfo, BaOptions, BaPointResult, BaPoIter, BaPoResult,
+                   check)
 
 SCALER = 0.01          # reference core/full_bundle_adjustment_solver.cpp:38
 INVERSE_SCALER = 1.0 / SCALER
@@ -1116,6 +1117,96 @@ class BaProblem:
                                    n_it, conv, cap, dbg)
 
 
+def _i64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _point_only_structure(what, n_pt, obs_cam, obs_pose, obs_pt, obs_uv):
+    """Observations in any order -> the landmark-major lists of ba_point_only: a stable
+    sort by point (a landmark keeps the caller's order of its observations) and the
+    offsets.  Returns (obs_off, cam, pose, uv, order)."""
+    pt = np.asarray(obs_pt, np.int64).reshape(-1)
+    cam = np.asarray(obs_cam, np.int32).reshape(-1)
+    pose = np.asarray(obs_pose, np.int32).reshape(-1)
+    uv = np.asarray(obs_uv, np.float64).reshape(-1, 2)
+    if not (pt.size == cam.size == pose.size == uv.shape[0]):
+        raise ValueError("%s: observation arrays differ in length" % what)
+    if pt.size and (pt.min() < 0 or pt.max() >= n_pt):
+        k = int(np.nonzero((pt < 0) | (pt >= n_pt))[0][0])
+        raise ValueError("%s: point index %d out of range at observation %d" % (what, pt[k], k))
+    order = np.argsort(pt, kind="stable")
+    off = np.zeros(n_pt + 1, np.int64)
+    np.cumsum(np.bincount(pt, minlength=n_pt), out=off[1:])
+    return (off, np.ascontiguousarray(cam[order]), np.ascontiguousarray(pose[order]),
+            np.ascontiguousarray(uv[order]), order)
+
+
+def point_only_check(n_cam, n_pose, n_pt, obs_off, obs_cam, obs_pose):
+    """ba_point_only_check: the host-side validation of ba_point_only's structure (no
+    GPU).  Raises BaError naming the landmark / observation."""
+    off = np.ascontiguousarray(obs_off, np.int64).reshape(-1)
+    cam = np.ascontiguousarray(obs_cam, np.int32).reshape(-1)
+    pose = np.ascontiguousarray(obs_pose, np.int32).reshape(-1)
+    if off.size != max(n_pt, 0) + 1:
+        raise ValueError("point_only_check: obs_off must hold n_pt + 1 entries")
+    if off.size and (cam.size < off[-1] or pose.size < off[-1]):
+        raise ValueError("point_only_check: fewer observations than obs_off[-1]")
+    check(_lib.load().ba_point_only_check(n_cam, n_pose, n_pt, _i64p(off), _ip(cam), _ip(pose)),
+          "ba_point_only_check")
+    return True
+
+
+def point_only_team(width=0):
+    """ba_point_only_team: lanes per landmark of the point-only kernel (8 or 16; 0 asks)."""
+    return check(_lib.load().ba_point_only_team(int(width)), "ba_point_only_team")
+
+
+def point_only_last_ms():
+    """device time of this thread's last point_only launch (hipEvents), milliseconds"""
+    ms = C.c_double(0.0)
+    check(_lib.load().ba_point_only_last_ms(C.byref(ms)), "ba_point_only_last_ms")
+    return ms.value
+
+
+def point_only(handle, cam_intr, cam_T, pose_T, X3, obs_cam, obs_pose, obs_pt, obs_uv, opt,
+               triangulate=None, cap=None):
+    """ba_point_only on the device and stream of `handle` (a BaProblem): every pose fixed,
+    every landmark solved on its own, all in one launch; scaled units.  Observations come
+    in any order and are stable-sorted by point.  triangulate: None, or n_pt flags.
+    cap: iteration rows kept per landmark (None: max_num_iterations; 0: none).
+    Returns (X (n_pt, 3), results, rows): results a numpy record array with the fields
+    of ba_point_result, rows one list of BaIterInfo per landmark (None when cap is 0)."""
+    K = np.ascontiguousarray(cam_intr, np.float64).reshape(-1, 4)
+    Tc = np.ascontiguousarray(cam_T, np.float64).reshape(-1, 12)
+    Tp = np.ascontiguousarray(pose_T, np.float64).reshape(-1, 12)
+    X = np.ascontiguousarray(X3, np.float64).reshape(-1, 3).copy()
+    if K.shape[0] != Tc.shape[0]:
+        raise ValueError("point_only: cam_intr and cam_T differ in length")
+    n_pt = X.shape[0]
+    off, cam, pose, uv, _ = _point_only_structure("point_only", n_pt, obs_cam, obs_pose,
+                                                  obs_pt, obs_uv)
+    tri = None
+    if triangulate is not None:
+        tri = np.ascontiguousarray(triangulate, np.uint8).reshape(-1)
+        if tri.size != n_pt:
+            raise ValueError("point_only: triangulate must hold one flag per point")
+    if cap is None:
+        cap = max(0, opt.max_num_iterations)
+    rows = (BaIterInfo * (max(n_pt, 1) * cap))() if cap > 0 else None
+    res = (BaPointResult * max(n_pt, 1))()
+    check(handle.lib.ba_point_only(
+        handle.h, K.shape[0], _dp(K), _dp(Tc), Tp.shape[0], _dp(Tp), n_pt, _i64p(off),
+        _ip(cam), _ip(pose), _dp(uv), _up(tri) if tri is not None else None, _dp(X),
+        C.byref(opt), rows, cap, res), "ba_point_only")
+    rec = np.frombuffer(res, dtype=np.dtype(BaPointResult), count=max(n_pt, 1))[:n_pt]
+    rec = rec.view(np.recarray)
+    out_rows = None
+    if rows is not None:
+        out_rows = [[rows[i * cap + k] for k in range(min(int(rec.n_rows[i]), cap))]
+                    for i in range(n_pt)]
+    return X, rec, out_rows
+
+
 class BaBatch:
     """B independent small full-BA problems solved in ONE launch, one persistent
     workgroup each (ba_batch_* of include/ba_hip.h).  `problems`: a list of dicts in
@@ -2115,6 +2206,64 @@ class FullBundleAdjustmentSolver:
         cp, cq, _ = self._problem.covariance(hp, hq, huber)
         return covariance_to_user_units(cp, cq, sigma_pixel)
 
+    def SolvePointsOnly(self, options, triangulate=()):
+        """(new; the reference has no counterpart) Structure-only solve: every registered
+        pose is treated as FIXED and every non-fixed registered point is solved on its own
+        against its observations, all in one launch (ba_point_only).  triangulate: point
+        objects or integer handles whose current value is replaced by a linear
+        triangulation first (it may be anything, NaN included).  The current values of
+        the solver are used (after Solve: the solution), units are converted as Solve
+        does, the new points are written back through the user's objects and become the
+        solver's values.  Returns the per-point results (ba_point_result fields) of the
+        non-fixed points in registration order; a point whose status is not 0 is left
+        as it was."""
+        intr, camT, T_jw, X, pf, qf, ocam, opose, opt, ouv = self._host_arrays()
+        if self._shard[1] > 1:
+            raise RuntimeError("SolvePointsOnly: not available on a sharded solver")
+        p = self._problem
+        tmp = None
+        if p is not None:           # continue from the solver's state, as Solve does
+            T_jw, X = p.get_poses(), p.get_points()[0]
+        else:
+            p = tmp = BaProblem(self.device)
+        try:
+            sel = np.nonzero(qf == 0)[0]
+            tri_all = np.zeros(self.num_total_points_, np.uint8)
+            for point in triangulate:
+                h = self._point_handle(point)
+                if h is None:
+                    raise RuntimeError("There is no pointer in the BA point pool.")
+                if h in self._pt_fixed:
+                    raise RuntimeError("SolvePointsOnly: a fixed point is not triangulated.")
+                tri_all[h] = 1
+            if sel.size == 0:
+                return np.zeros(0, np.dtype(BaPointResult)).view(np.recarray)
+            new_of = np.full(self.num_total_points_, -1, np.int64)
+            new_of[sel] = np.arange(sel.size)
+            keep = new_of[opt] >= 0
+            c_opt = options.to_c()
+            c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
+            Xs, res, _ = point_only(p, intr, camT, T_jw, X[sel], ocam[keep], opose[keep],
+                                    new_of[opt[keep]], ouv[keep], c_opt,
+                                    triangulate=tri_all[sel], cap=0)
+            X = X.copy()
+            done = res.status == 0
+            X[sel[done]] = Xs[done]
+            owned = np.zeros(self.num_total_points_, bool)
+            owned[sel[done]] = True
+            self._write_points(X, owned)     # no pose is touched
+            # the solver's values follow what the user now holds (the value a fresh
+            # solver would register from the written point), as after SolveBatch
+            X[sel[done]] = (X[sel[done]] * INVERSE_SCALER) * SCALER
+            self._pose_T_jw = [np.ascontiguousarray(T_jw)]
+            self._pt_X = [X]
+            if self._problem is not None:
+                self._problem.update_values(None, X)
+            return res
+        finally:
+            if tmp is not None:
+                tmp.close()
+
     def _finish_solve(self, rows, converged, summary, t0):
         """Write the solution back through the user's objects (reference
         :1011-1022) and fill the Summary rows; shared by Solve and
@@ -2127,6 +2276,21 @@ class FullBundleAdjustmentSolver:
             p.gather_points()
         X, owned = p.get_points()
         return self._write_back(T_jw, X, owned, rows, converged, summary, t0)
+
+    def _write_points(self, X, owned):
+        """X [n_pt, 3] (scaled units) into the user's point objects: the non-fixed
+        points among `owned`."""
+        Xu = X * INVERSE_SCALER
+        opt_mask = np.ones(self.num_total_points_, bool)
+        opt_mask[list(self._pt_fixed)] = False
+        opt_mask &= owned
+        for obj, base, cnt in self._pt_objs:
+            if cnt == 0:      # single AddPoint object
+                if opt_mask[base]:
+                    obj[...] = Xu[base].reshape(np.shape(obj))
+            else:             # AddPointArray block
+                m = opt_mask[base:base + cnt]
+                obj[m] = Xu[base:base + cnt][m]
 
     def _write_back(self, T_jw, X, owned, rows, converged, summary, t0):
         """The second half of _finish_solve on given arrays (scaled units): T_jw
@@ -2141,17 +2305,7 @@ class FullBundleAdjustmentSolver:
                 obj[...] = T_wj[h]
             else:
                 obj[row] = T_wj[h]
-        Xu = X * INVERSE_SCALER
-        opt_mask = np.ones(self.num_total_points_, bool)
-        opt_mask[list(self._pt_fixed)] = False
-        opt_mask &= owned
-        for obj, base, cnt in self._pt_objs:
-            if cnt == 0:      # single AddPoint object
-                if opt_mask[base]:
-                    obj[...] = Xu[base].reshape(np.shape(obj))
-            else:             # AddPointArray block
-                m = opt_mask[base:base + cnt]
-                obj[m] = Xu[base:base + cnt][m]
+        self._write_points(X, owned)
         if summary is not None:
             for r in rows:
                 info = OptimizationInfo()

@@ -97,6 +97,27 @@ class FullBundleAdjustmentSolver {
                          const std::vector<PosePrior> *in_priors = nullptr, double sigma_pixel = 1.0,
                          const std::vector<std::vector<RelativePose>> *in_relatives = nullptr);
 
+  // (new; the reference has no counterpart) Structure-only solve: EVERY registered pose is
+  // treated as fixed and every non-fixed registered point is solved on its own against its
+  // observations, all of them in one GPU launch (ba_point_only of include/ba_hip.h: its own
+  // lambda, decisions and stop per point; options as in Solve).  The solver's current values
+  // are used (after Solve: the solution).  triangulate: registered, non-fixed points whose
+  // value is first replaced by a linear triangulation (it may be anything, NaN included); an
+  // unknown or fixed pointer throws std::runtime_error.  A point with status 0 is written
+  // back through the caller's pointer and becomes the solver's value (a finalized solver
+  // continues from it); any other point is left as it was.  results (null: not wanted) gets
+  // one entry per non-fixed point in registration order; costs are in the solver's scaled
+  // units, as the rows of a Summary.  Poses are never touched.  The solver need not be
+  // finalized and is not finalized by this call; sharded solvers are refused.  Returns true
+  // when every point has status 0.
+  struct PointOnlyResult {
+    _BA_Point *point{nullptr};
+    int n_iter{0}, converged{0}, status{0}, n_behind{0}, dropped_pivots{0};  // ba_point_result
+    double cost0{0.0}, cost{0.0};
+  };
+  bool SolvePointsOnly(Options options, std::vector<PointOnlyResult> *results = nullptr,
+                       const std::vector<_BA_Point *> &triangulate = std::vector<_BA_Point *>());
+
   // (new) Read the CURRENT values behind every registered pose / point pointer again
   // and hand them to the finalized problem (ba_update_values): re-optimising the same
   // graph with new values costs no second FinalizeParameters.  The reference keeps its

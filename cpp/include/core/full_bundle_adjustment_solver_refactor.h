@@ -147,6 +147,12 @@ class FullBundleAdjustmentSolverRefactor {
     return FullBundleAdjustmentSolver::MarginalizeBatch(impls, marg_poses, sigma_pixel, priors, in_priors,
                                                         in_relatives);
   }
+  // (new) structure-only solve, see FullBundleAdjustmentSolver::SolvePointsOnly;
+  // options.solver_type selects Levenberg-Marquardt or Gauss-Newton as in Solve (anything
+  // else throws std::runtime_error), for this call only
+  using PointOnlyResult = FullBundleAdjustmentSolver::PointOnlyResult;
+  bool SolvePointsOnly(Options options, std::vector<PointOnlyResult> *results = nullptr,
+                       const std::vector<Point *> &triangulate = std::vector<Point *>());
   ba_handle *GetHandle() const { return impl_.GetHandle(); }
 
   std::string GetSolverStatistics() const;

@@ -644,6 +644,102 @@ bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustme
   return all_solved;
 }
 
+bool FullBundleAdjustmentSolver::SolvePointsOnly(Options options, std::vector<PointOnlyResult> *results,
+                                                 const std::vector<_BA_Point *> &triangulate) {
+  if (results != nullptr) results->clear();
+  if (shard_world_ > 1 || allreduce_fn_) throw std::runtime_error("SolvePointsOnly: not available on a sharded solver");
+  if (cameras_.empty() || poses_.empty() || points_.empty())
+    throw std::runtime_error("SolvePointsOnly: cameras, poses and points must be added first");
+  std::vector<uint8_t> tri_all(points_.size(), 0);
+  for (_BA_Point *q : triangulate) {
+    const auto it = point_index_.find(q);
+    if (it == point_index_.end()) throw std::runtime_error("There is no pointer in the BA point pool.");
+    if (fixed_points_.count(it->second)) throw std::runtime_error("SolvePointsOnly: a fixed point is not triangulated.");
+    tri_all[static_cast<size_t>(it->second)] = 1;
+  }
+  // the non-fixed points in registration order, their observations landmark-major (stable)
+  std::vector<int> sel, new_of(points_.size(), -1);
+  for (size_t q = 0; q < points_.size(); ++q)
+    if (!fixed_points_.count(static_cast<int>(q))) {
+      new_of[q] = static_cast<int>(sel.size());
+      sel.push_back(static_cast<int>(q));
+    }
+  const int n_pt = static_cast<int>(sel.size());
+  if (n_pt == 0) return true;
+  std::vector<int64_t> off(static_cast<size_t>(n_pt) + 1, 0);
+  for (const Observation &o : observations_)
+    if (new_of[o.point_index] >= 0) ++off[static_cast<size_t>(new_of[o.point_index]) + 1];
+  for (int i = 0; i < n_pt; ++i) off[i + 1] += off[i];
+  const size_t n_obs = static_cast<size_t>(off[n_pt]);
+  std::vector<int32_t> oc(std::max<size_t>(n_obs, 1)), op(std::max<size_t>(n_obs, 1));
+  std::vector<double> uv(2 * std::max<size_t>(n_obs, 1));
+  std::vector<int64_t> at(off.begin(), off.end() - 1);
+  for (const Observation &o : observations_) {
+    const int i = new_of[o.point_index];
+    if (i < 0) continue;
+    const size_t k = static_cast<size_t>(at[i]++);
+    oc[k] = o.camera_index;
+    op[k] = o.pose_index;
+    uv[2 * k] = o.u;
+    uv[2 * k + 1] = o.v;
+  }
+  std::vector<double> intr(4 * cameras_.size()), T_cj(12 * cameras_.size()), T(12 * poses_.size()),
+      X(3 * static_cast<size_t>(n_pt));
+  for (size_t c = 0; c < cameras_.size(); ++c) {
+    intr[4 * c + 0] = cameras_[c].fx;
+    intr[4 * c + 1] = cameras_[c].fy;
+    intr[4 * c + 2] = cameras_[c].cx;
+    intr[4 * c + 3] = cameras_[c].cy;
+    Pack12(cameras_[c].pose_this_to_cam0, &T_cj[12 * c]);
+  }
+  for (size_t p = 0; p < poses_.size(); ++p) Pack12(T_jw_[p], &T[12 * p]);
+  std::vector<uint8_t> tri(static_cast<size_t>(n_pt));
+  for (int i = 0; i < n_pt; ++i) {
+    for (int r = 0; r < 3; ++r) X[3 * i + r] = X_[sel[i]](r);
+    tri[i] = tri_all[sel[i]];
+  }
+  const ba_options o = PackOptions(options, gauss_newton_);
+  std::vector<ba_point_result> res(static_cast<size_t>(n_pt));
+  ba_handle *h = handle_;
+  if (h == nullptr && ba_create(&h, device_id_) != 0)
+    throw std::runtime_error(std::string("SolvePointsOnly: ba_create failed: ") + ba_last_error());
+  const int rc = ba_point_only(h, static_cast<int>(cameras_.size()), intr.data(), T_cj.data(),
+                               static_cast<int>(poses_.size()), T.data(), n_pt, off.data(), oc.data(), op.data(),
+                               uv.data(), tri.data(), X.data(), &o, nullptr, 0, res.data());
+  const std::string err = rc ? ba_last_error() : "";
+  if (h != handle_) ba_destroy(h);
+  if (rc) throw std::runtime_error("SolvePointsOnly failed: " + err);
+  bool all_solved = true;
+  for (int i = 0; i < n_pt; ++i) {
+    const size_t q = static_cast<size_t>(sel[i]);
+    if (res[i].status == 0) {
+      X_[q] = _BA_Point(X[3 * i], X[3 * i + 1], X[3 * i + 2]);
+      *points_[q] = X_[q] * inverse_scaler_;
+    } else {
+      all_solved = false;
+    }
+    if (results != nullptr) {
+      PointOnlyResult r;
+      r.point = points_[q];
+      r.n_iter = res[i].n_iter;
+      r.converged = res[i].converged;
+      r.status = res[i].status;
+      r.n_behind = res[i].n_behind;
+      r.dropped_pivots = res[i].dropped_pivots;
+      r.cost0 = res[i].cost0;
+      r.cost = res[i].cost;
+      results->push_back(r);
+    }
+  }
+  if (is_parameter_finalized_) {  // a finalized solver continues from the new points
+    std::vector<double> Xall(3 * points_.size());
+    for (size_t q = 0; q < points_.size(); ++q)
+      for (int r = 0; r < 3; ++r) Xall[3 * q + r] = X_[q](r);
+    Check(ba_update_values(handle_, nullptr, Xall.data()), "ba_update_values");
+  }
+  return all_solved;
+}
+
 bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
     const std::vector<FullBundleAdjustmentSolver *> &solvers, double sigma_pixel,
     std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,

@@ -77,6 +77,24 @@ bool FullBundleAdjustmentSolverRefactor::SolveBatch(const std::vector<FullBundle
   return ok;
 }
 
+bool FullBundleAdjustmentSolverRefactor::SolvePointsOnly(Options options, std::vector<PointOnlyResult> *results,
+                                                         const std::vector<Point *> &triangulate) {
+  if (options.solver_type != SolverType::LEVENBERG_MARQUARDT && options.solver_type != SolverType::GAUSS_NEWTON)
+    throw std::runtime_error(
+        "FullBundleAdjustmentSolverRefactor::SolvePointsOnly: solver_type must be GAUSS_NEWTON or LEVENBERG_MARQUARDT");
+  const bool before = impl_.gauss_newton_;  // the mode holds for this call only
+  impl_.SetGaussNewton(options.solver_type == SolverType::GAUSS_NEWTON);
+  bool ok = false;
+  try {
+    ok = impl_.SolvePointsOnly(options, results, triangulate);
+  } catch (...) {
+    impl_.SetGaussNewton(before);
+    throw;
+  }
+  impl_.SetGaussNewton(before);
+  return ok;
+}
+
 bool FullBundleAdjustmentSolverRefactor::SolveByGradientDescent(Options options, Summary *summary) {  // :1075-1367
   return impl_.Run(options, summary, true);
 }

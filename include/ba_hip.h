@@ -865,6 +865,72 @@ int ba_batch_plan_problem(int n_pose, const uint8_t *pose_fixed, int n_pt,
                           int32_t *order, int32_t *obs_pair, uint8_t *last_writer,
                           int32_t *pair_lm, int32_t *pair_pose);
 
+/* ---- point-only ("structure-only") solves: every landmark in one launch ------ */
+/* The mirror of pose-only: ALL poses are fixed and every landmark is solved on its own.
+ * For landmark i with the observations obs_off[i] .. obs_off[i+1]-1 (each a camera, a
+ * pose and a pixel, in the caller's order) the result is what ba_solve defines for the
+ * problem {all the given cameras and poses, every pose fixed; that one point, optimisable;
+ * those observations}: fp64, cost = sum of residual norms, Huber weight on |r_x|+|r_y|,
+ * damping diag*(1+lambda), the 3x3 inverse with its fallback, the quadratic model on the
+ * damped block, the accept / reject and lambda update of the full solver, previous cost
+ * advanced on SKIPPED, "never converged on the last allowed iteration", gauss_newton.
+ * In the control step the observation count is the landmark's and the block count is 1.
+ * Each landmark has its own lambda, its own decisions and its own stop.
+ *
+ * triangulate (n_pt bytes, or NULL): a set byte replaces the incoming X by a linear
+ * triangulation first: with (R, t) = T_cj o T_jw, x = (u-cx)/fx, y = (v-cy)/fy every
+ * observation gives the rows (r1 - x r3).X = -(t1 - x t3), (r2 - y r3).X = -(t2 - y t3);
+ * X solves the 3x3 normal equations of all rows (LDL^T in the given order).  The incoming
+ * X of such a landmark may be anything, NaN included; the refinement (if
+ * max_num_iterations > 0) starts from the triangulated value.
+ *
+ * Units and layouts are those of ba_set_* (scaled units).  The handle gives the device
+ * and the stream only.  One upload, one launch, one download, one synchronisation.
+ * rows: n_pt * cap iteration rows (landmark i owns rows[i*cap ..]; n_rows of them are
+ * written), or NULL.
+ *
+ * status: 0 solved.
+ *         1 a non-finite value among the landmark's inputs (X when not triangulated, one
+ *           of its pixels, cameras or poses): X left as given.
+ *         2 no observations: X left as given, no rows (the full solver would log one
+ *           SKIPPED row of cost 0 — deliberate deviation).  Decided before status 1.
+ *         3 triangulation asked for but degenerate: fewer than two observations, or a
+ *           pivot of the normal equations not above 1e-12 of their largest diagonal entry
+ *           (a parallax of about 1e-6 rad; exact rank deficiency leaves ~1e-16).  X left
+ *           as given, no refinement.
+ * n_behind: observations with non-positive depth in their camera at the returned X (0
+ * for status 1 and 2).  cost0 / cost: the first previous cost and the accepted cost at
+ * the end.  dropped_pivots: iterations whose inverse of the damped block had a diagonal
+ * entry that was not positive (the block was not positive definite).
+ * max_num_iterations <= 0: triangulation only, where asked; otherwise X unchanged;
+ * converged = 1, no rows.
+ * One writer per value, fixed summation order per landmark, no atomics: a landmark gives
+ * the same bits run to run, alone and at any position of any call (for one team width).
+ * Everything is validated on the host before anything touches the GPU (-1 and
+ * ba_last_error naming the landmark / observation): n_cam, n_pose, n_pt >= 1, offsets
+ * starting at 0 and never decreasing, camera and pose indices in range, non-NULL
+ * pointers (triangulate and rows may be NULL), cap >= 0. */
+typedef struct {
+  int n_iter, converged, n_rows, status, n_behind, dropped_pivots;
+  double cost0, cost;
+} ba_point_result;
+int ba_point_only(ba_handle *h, int n_cam, const double *intr4, const double *T_cj12,
+                  int n_pose, const double *T_jw12, int n_pt, const int64_t *obs_off /* n_pt+1 */,
+                  const int32_t *obs_cam, const int32_t *obs_pose, const double *obs_uv2,
+                  const uint8_t *triangulate /* n_pt or NULL */, double *X3 /* in/out */,
+                  const ba_options *opt, ba_iter_info *rows /* n_pt*cap or NULL */, int cap,
+                  ba_point_result *res);
+/* Host-only (no GPU): the validation of the structure arguments of ba_point_only. */
+int ba_point_only_check(int n_cam, int n_pose, int n_pt, const int64_t *obs_off,
+                        const int32_t *obs_cam, const int32_t *obs_pose);
+/* Lanes per landmark of the kernel: 8 or 16 (two instantiations; the sums of a landmark
+ * are associated differently, so the last bits differ between the widths).  width = 0
+ * asks; 8 / 16 sets it for the process.  Returns the width in force, or -1.  The default
+ * is the width measured faster at 10 observations per landmark. */
+int ba_point_only_team(int width);
+/* Device time (hipEvents around the launch) of the calling thread's last ba_point_only. */
+int ba_point_only_last_ms(double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
