@@ -127,6 +127,10 @@ SIGNATURES = {
     "ba_set_shard": (C.c_int, [_P, C.c_int, C.c_int]),
     "ba_finalize": (C.c_int, [_P]),
     "ba_update_values": (C.c_int, [_P, _D, _D]),
+    "ba_set_relative": (C.c_int, [_P, C.c_int64, _I32, _I32, _D, _D]),
+    "ba_update_relative": (C.c_int, [_P, _D, _D]),
+    "ba_relative_check": (C.c_int, [C.c_int, _U8, C.c_int64, _I32, _I32, _D, _D]),
+    "ba_relative_info": (C.c_int, [_P, _I64]),
     "ba_partition_points": (C.c_int, [C.c_int, _U8, C.c_int, _U8, C.c_int64,
                                       _I32, _I32, C.c_int, _I32]),
     "ba_set_allreduce": (C.c_int, [_P, ALLREDUCE_FN, _P]),

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "ba_handle.h"
+#include "ba_rel_host.h"
 
 namespace {
 thread_local std::string g_err;
@@ -77,7 +78,10 @@ int enqueue_iteration(ba_handle *h) {
   ba::g_ktimer = h->timing ? &h->kt : nullptr;
   // per-kernel / per-stage timing needs the serial order on one stream; a captured
   // graph cannot wait for an event of the previous replay
-  const bool ov = h->overlap && !h->timing && !h->use_graph;
+  // relative-pose factors (ba_set_relative): their launches sit between the others in
+  // stream order, so a handle with factors keeps everything on the main stream
+  const bool rel = h->rel.F > 0;
+  const bool ov = h->overlap && !h->timing && !h->use_graph && !rel;
   const bool direct = !h->ar_fn;  // single GPU: S, rhs are placed in the dense matrix at once
   h->ddev.flow_ok = !h->use_graph;  // (the dataflow sweep's generation number is a kernel argument)
   mark(h, 0);
@@ -90,10 +94,11 @@ int enqueue_iteration(ba_handle *h) {
   // pose in a covisibility group (no pose-major pass), no cost pass — the reset of the
   // factor tiles rides in the back-substitution launch (the solve is over by then),
   // the pose-side sums in the k_scalars launch: no fork / join gaps (6 + 8 us at C4).
-  const bool no_side = !h->knobs.run.force_side && !h->ar_fn && d.lin_chunk0 > 0 && d.n_achunk == 0 && d.n_obs_lm == d.n_obs;
+  const bool no_side = !rel && !h->knobs.run.force_side && !h->ar_fn && d.lin_chunk0 > 0 && d.n_achunk == 0 && d.n_obs_lm == d.n_obs;
   ba::launch_schur_accumulate(d, s);
   join_side(h);  // A_j, a_j of this point and the reset factor tiles come from the side stream
   ba::launch_schur_final(d, direct, s);
+  if (rel) ba::launch_rel_offdiag(d, h->rel, direct, s);  // S_jk += -Omega Ad of the accepted point, undamped
   mark(h, 1);
   if (xchg(h, 0)) return -1;
   mark(h, 2);
@@ -101,6 +106,8 @@ int enqueue_iteration(ba_handle *h) {
   ba::launch_dense_solve(d, h->sched, h->ddev, s);
   mark(h, 3);
   ba::launch_backsub_update(d, s, no_side);  // trial parameters, model terms, step norms
+  // the factors' cross term of the model, their linearisation at the trial poses, their norms there
+  if (rel) ba::launch_rel_lin(d, h->rel, 1, 3, s);
   mark(h, 4);
   if (no_side) {
     h->tiles_ready = true;
@@ -124,10 +131,13 @@ int enqueue_iteration(ba_handle *h) {
     enqueue_linearize(h, 1);
   }
   mark(h, 5);
-  if (h->ar_fn) {
+  if (h->ar_fn || rel) {
     ba::launch_scalars(d, 1, s);
     mark(h, 6);
     if (xchg(h, 1)) return -1;
+    // A_j, a_j of the trial point gain the factors' blocks (k_pose_finalize has run), the
+    // scalars their norms and cross term: the decision comes after
+    if (rel) ba::launch_rel_gather(d, h->rel, 1, 7, s);
     mark(h, 7);
     ba::launch_control(d, s);
   } else {  // nothing to exchange: the reduction workgroup also takes the LM decision
@@ -243,6 +253,9 @@ int finalize_plan(ba_handle *h) {
   in.obs_uv = h->obs_uv.data();
   in.rank = h->rank;
   in.world = h->world;
+  in.n_rel = (int64_t)h->rel_j.size();
+  in.rel_j = h->rel_j.data();
+  in.rel_k = h->rel_k.data();
   std::string err = ba::build_plan(in, h->knobs.plan, h->plan);
   if (!err.empty()) return fail("ba_finalize: " + err);
   const ba::Plan &pl = h->plan;
@@ -537,6 +550,48 @@ int setup_reduced_system(ba_handle *h) {
   return h->dense_owner ? alias_dense_owner(h) : build_dense_system(h);
 }
 
+// The relative-pose factors (ba_set_relative): the planner's lists, the packed values and
+// both scratch buffers.  Pose-sized and read while no chunk is resident: Resident.
+int upload_relative(ba_handle *h) {
+  const ba::Plan &pl = h->plan;
+  ba::RelDev &r = h->rel;
+  r = ba::RelDev{};
+  h->rel_bytes = 0;
+  const size_t F = (size_t)pl.n_rel;
+  if (F == 0) return 0;
+  constexpr Mem R = Mem::Resident;
+  static_assert(sizeof(int4) == 16, "layout");
+  int4 *jk = nullptr;
+  double *val = nullptr;
+  int32_t *pptr = nullptr, *plist = nullptr, *blk = nullptr, *bptr = nullptr, *blist = nullptr;
+  const int n_part = (int)((F + ba::kRelFpb - 1) / ba::kRelFpb);
+  if (h->upload(R, &jk, pl.rel_jk.data(), F) || h->upload(R, &val, h->rel_val) || h->upload(R, &pptr, pl.rel_pptr) ||
+      h->upload(R, &plist, pl.rel_plist) || h->upload(R, &blk, pl.rel_blk) || h->upload(R, &bptr, pl.rel_bptr) ||
+      h->upload(R, &blist, pl.rel_blist) || h->dalloc(R, &r.scr[0], F * ba::kRelScrDoubles) ||
+      h->dalloc(R, &r.scr[1], F * ba::kRelScrDoubles) || h->dalloc(R, &r.part, (size_t)2 * n_part))
+    return -1;
+  for (int k = 0; k < 2; ++k) HIP_TRY(hipMemset(r.scr[k], 0, F * ba::kRelScrDoubles * sizeof(double)));
+  HIP_TRY(hipMemset(r.part, 0, (size_t)2 * n_part * sizeof(double)));
+  r.F = (int)F;
+  r.nblk = (int)pl.rel_blk.size();
+  r.n_part = n_part;
+  r.jk = jk;
+  r.val = val;
+  r.pptr = pptr;
+  r.plist = plist;
+  r.blk = blk;
+  r.bptr = bptr;
+  r.blist = blist;
+  h->rel_bytes = F * (16 + ba::kRelVal * 8 + 2 * ba::kRelScrDoubles * 8) + (pl.rel_pptr.size() + pl.rel_plist.size() +
+                 pl.rel_blk.size() + pl.rel_bptr.size() + pl.rel_blist.size()) * 4 + (size_t)2 * n_part * 8;
+  return 0;
+}
+
+// why a handle that holds relative-pose factors cannot be sharded (ba_set_shard,
+// ba_set_allreduce, ba_set_relative: whichever comes second is refused)
+const char *kRelNoShard = "relative-pose factors run on one GPU: a handle that holds them cannot be sharded "
+                          "(ba_set_shard with world > 1, or an all-reduce hook)";
+
 }  // namespace
 
 extern "C" {
@@ -654,8 +709,70 @@ int ba_set_observations(ba_handle *h, int64_t n_obs, const int32_t *cam,
 int ba_set_shard(ba_handle *h, int rank, int world) {
   if (!h || world < 1 || rank < 0 || rank >= world) return fail("ba_set_shard: bad argument");
   if (h->finalized) return fail("ba_set_shard: already finalized");
+  if (world > 1 && !h->rel_j.empty()) return fail(std::string("ba_set_shard: ") + kRelNoShard);
   h->rank = rank;
   h->world = world;
+  return 0;
+}
+
+int ba_relative_check(int n_pose, const uint8_t *pose_fixed, int64_t n_rel, const int32_t *rel_j,
+                      const int32_t *rel_k, const double *Z12, const double *Omega36) {
+  std::string err;
+  if (ba::relative_validate_host(ba::kRelPairs | ba::kRelValues, n_pose, pose_fixed, n_rel, rel_j, rel_k, Z12,
+                                 Omega36, &err))
+    return fail("ba_relative_check: " + err);
+  return 0;
+}
+
+int ba_set_relative(ba_handle *h, int64_t n_rel, const int32_t *rel_j, const int32_t *rel_k, const double *Z12,
+                    const double *Omega36) {
+  if (!h) return fail("ba_set_relative: null handle");
+  if (h->finalized) return fail("ba_set_relative: already finalized (the factors change the structure; "
+                                "ba_update_relative takes new values for the same pairs)");
+  if (n_rel == 0 || (!rel_j && !rel_k && !Z12 && !Omega36)) {
+    h->rel_j.clear();
+    h->rel_k.clear();
+    h->rel_val.clear();
+    return 0;
+  }
+  if (h->arena || h->dense_owner) return fail("ba_set_relative: not available on a streamed chunk");
+  if (h->world > 1 || h->ar_fn) return fail(std::string("ba_set_relative: ") + kRelNoShard);
+  if (h->use_graph)
+    return fail("ba_set_relative: BA_GRAPH=1 replay is not available with relative-pose factors");
+  if (h->n_pose <= 0) return fail("ba_set_relative: the poses must be set first (ba_set_poses)");
+  std::string err;
+  if (ba::relative_validate_host(ba::kRelPairs | ba::kRelValues, h->n_pose, h->pose_fixed.data(), n_rel, rel_j, rel_k,
+                                 Z12, Omega36, &err))
+    return fail("ba_set_relative: " + err);
+  h->rel_j.assign(rel_j, rel_j + n_rel);
+  h->rel_k.assign(rel_k, rel_k + n_rel);
+  ba::relative_pack_values(n_rel, Z12, Omega36, &h->rel_val);
+  return 0;
+}
+
+int ba_update_relative(ba_handle *h, const double *Z12, const double *Omega36) {
+  if (!h || !h->finalized) return fail("ba_update_relative: not finalized");
+  if (h->rel.F <= 0) return fail("ba_update_relative: the handle holds no relative-pose factors (ba_set_relative)");
+  std::string err;
+  if (ba::relative_validate_host(ba::kRelValues, h->n_pose, nullptr, h->rel.F, nullptr, nullptr, Z12, Omega36, &err))
+    return fail("ba_update_relative: " + err);
+  if (use_device(h)) return -1;
+  join_side(h);
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  ba::relative_pack_values(h->rel.F, Z12, Omega36, &h->rel_val);
+  HIP_TRY(hipMemcpy(const_cast<double *>(h->rel.val), h->rel_val.data(), h->rel_val.size() * sizeof(double),
+                    hipMemcpyHostToDevice));
+  h->lm_begun = false;  // the blocks on the device belong to the old values: ba_lm_begin linearises again
+  h->tiles_ready = false;
+  return 0;
+}
+
+int ba_relative_info(ba_handle *h, int64_t out4[4]) {
+  if (!h || !out4) return fail("ba_relative_info: bad argument");
+  out4[0] = (int64_t)h->rel_j.size();
+  out4[1] = h->finalized ? (int64_t)h->plan.rel_blk.size() : 0;
+  out4[2] = h->finalized ? h->plan.n_rel_only : 0;
+  out4[3] = h->finalized ? (int64_t)h->rel_bytes : 0;
   return 0;
 }
 
@@ -705,6 +822,15 @@ int ba_finalize(ba_handle *h) {
             h->up_alloc_s * 1e3, h->up_copy_s * 1e3);
     t_last = n;
   };
+  if (!h->rel_j.empty()) {
+    // the poses may have been set again since ba_set_relative: no index reaches the planner
+    // or a kernel unchecked
+    std::string err;
+    if (ba::relative_validate_host(ba::kRelPairs, h->n_pose, h->pose_fixed.data(), (int64_t)h->rel_j.size(),
+                                   h->rel_j.data(), h->rel_k.data(), nullptr, nullptr, &err))
+      return fail("ba_finalize: relative-pose factors: " + err);
+    if (h->world > 1 || h->ar_fn) return fail(std::string("ba_finalize: ") + kRelNoShard);
+  }
   if (finalize_plan(h)) return -1;
   lap("host plan");
   if (upload_parameters(h) || upload_observation_lists(h) || upload_descriptors_and_groups(h)) return -1;
@@ -713,6 +839,7 @@ int ba_finalize(ba_handle *h) {
   lap("block storage");
   if (setup_reduced_system(h)) return -1;
   lap("dense schedule + image");
+  if (upload_relative(h)) return -1;
   std::memset(&h->hc, 0, sizeof(h->hc));
   h->hc.lambda = 100.0;
   h->hc.huber = 1.0;
@@ -756,6 +883,7 @@ int ba_update_values(ba_handle *h, const double *T_jw12, const double *X3) {
 
 int ba_set_allreduce(ba_handle *h, ba_allreduce_fn fn, void *user) {
   if (!h) return fail("null handle");
+  if (fn && !h->rel_j.empty()) return fail(std::string("ba_set_allreduce: ") + kRelNoShard);
   h->ar_fn = fn;
   h->ar_user = user;
   return 0;
@@ -835,7 +963,10 @@ int ba_lm_begin(ba_handle *h, const ba_options *opt) {
   // first linearisation, at the starting point; previous_cost =
   // EvaluateCurrentCost() (reference :707) is the sum of its residual norms
   enqueue_linearize(h, 0);
+  const bool rel = h->rel.F > 0;
+  if (rel) ba::launch_rel_lin(h->d, h->rel, 0, 1, h->stream);
   ba::launch_scalars_cost_only(h->d, 1, h->stream);
+  if (rel) ba::launch_rel_gather(h->d, h->rel, 0, 3, h->stream);  // A_j, a_j and the cost gain the factors
   if (xchg(h, 1)) return -1;
   ba::launch_init_ctrl_cost(h->d, h->stream);
   if (done_after) {
@@ -945,6 +1076,9 @@ static int gd_prepare(ba_handle *h, const char *who) {
   if (h->world > 1 || h->ar_fn)
     return fail(std::string(who) + ": gradient descent runs on one GPU; this handle is sharded "
                 "(ba_set_shard with world > 1, or an all-reduce hook is set)");
+  if (h->rel.F > 0)
+    return fail(std::string(who) + ": gradient descent takes reprojections only; this handle holds relative-pose "
+                "factors (ba_set_relative)");
   if (h->gd_ready) return 0;
   const ba::Plan &pl = h->plan;
   const ba::DevProblem &d = h->d;
@@ -1104,6 +1238,10 @@ int ba_stage_cost(ba_handle *h, double *cost) {
   join_side(h);
   ba::launch_cost(h->d, 0, 0, h->stream);
   ba::launch_scalars_cost_only(h->d, 0, h->stream);
+  if (h->rel.F > 0) {  // + the factors' norms at the accepted poses
+    ba::launch_rel_lin(h->d, h->rel, 0, 0, h->stream);
+    ba::launch_rel_gather(h->d, h->rel, 0, 2, h->stream);
+  }
   if (xchg(h, 1)) return -1;
   HIP_TRY(hipMemcpyAsync(cost, h->d.scal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1120,6 +1258,10 @@ int ba_stage_linearize(ba_handle *h, double lambda, double huber) {
   if (push_ctrl(h)) return -1;
   join_side(h);
   enqueue_linearize(h, 0);
+  if (h->rel.F > 0) {
+    ba::launch_rel_lin(h->d, h->rel, 0, 1, h->stream);
+    ba::launch_rel_gather(h->d, h->rel, 0, 1, h->stream);
+  }
   ba::launch_damp_invert(h->d, h->stream);
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipGetLastError());
@@ -1131,6 +1273,7 @@ int ba_stage_schur(ba_handle *h) {
   if (use_device(h)) return -1;
   join_side(h);
   ba::launch_schur(h->d, /*direct=*/false, /*with_init=*/true, h->stream);
+  if (h->rel.F > 0) ba::launch_rel_offdiag(h->d, h->rel, false, h->stream);
   if (xchg(h, 0)) return -1;
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipGetLastError());
@@ -1151,6 +1294,7 @@ int ba_stage_backsub_update(ba_handle *h) {
   if (!h || !h->finalized) return fail("ba_stage_backsub_update: not finalized");
   if (use_device(h)) return -1;
   ba::launch_backsub_update(h->d, h->stream);
+  if (h->rel.F > 0) ba::launch_rel_lin(h->d, h->rel, 1, 2, h->stream);  // norms at the trial poses, cross term
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1162,6 +1306,7 @@ int ba_stage_scalars(ba_handle *h, double *trial_cost, double *model_change,
   if (use_device(h)) return -1;
   ba::launch_cost(h->d, 1, 0, h->stream);
   ba::launch_scalars(h->d, 0, h->stream);
+  if (h->rel.F > 0) ba::launch_rel_gather(h->d, h->rel, 1, 6, h->stream);
   if (xchg(h, 1)) return -1;
   double sc[4], pp[2];
   HIP_TRY(hipMemcpyAsync(sc, h->d.scal, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
@@ -1438,7 +1583,8 @@ const char *ba_kernel_name(int id) {
       "k_cost", "k_lin_landmarks", "k_lin_poses", "k_pose_finalize", "k_dense_init",
       "k_schur_lds", "k_schur_partial", "k_schur_final", "k_scatter",
       "k_chol_diag", "k_chol_trsm", "k_chol_update", "k_chol_back", "k_chol_diag_trsm", "k_chol_tail", "k_backsub_update",
-      "k_pose_update", "k_scalars", "k_control", "k_damp_invert", "k_schur_grp", "k_lin_grp"};
+      "k_pose_update", "k_scalars", "k_control", "k_damp_invert", "k_schur_grp", "k_lin_grp",
+      "k_rel_lin", "k_rel_gather", "k_rel_offdiag"};
   return (id >= 0 && id < ba::K_COUNT) ? names[id] : "";
 }
 
@@ -1723,8 +1869,13 @@ int ba_covariance(ba_handle *h, double huber, int n_pose_sel, const int32_t *pos
   HIP_TRY(hipMemcpy(&bad_keep, h->ddev.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemsetAsync(h->ddev.bad_pivots, 0, sizeof(int), h->stream));
   enqueue_linearize(h, 0);
+  if (h->rel.F > 0) {
+    ba::launch_rel_lin(d, h->rel, 0, 1, h->stream);
+    ba::launch_rel_gather(d, h->rel, 0, 1, h->stream);
+  }
   ba::launch_damp_invert_export(d, h->stream);  // Cinv_i as an array, whatever Schur path the plan uses
   ba::launch_schur(d, /*direct=*/false, /*with_init=*/true, h->stream);
+  if (h->rel.F > 0) ba::launch_rel_offdiag(d, h->rel, false, h->stream);
   ba::launch_scatter(d, h->stream);
   {
     // k_chol_tail keeps its block's factor in LDS (only x leaves): here no level goes to it, so

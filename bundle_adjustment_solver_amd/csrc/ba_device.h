@@ -208,7 +208,8 @@ enum KernelId {
   K_COST = 0, K_LIN_LANDMARKS, K_LIN_POSES, K_POSE_FINALIZE, K_DENSE_INIT,
   K_SCHUR_LDS, K_SCHUR_PARTIAL, K_SCHUR_FINAL, K_SCATTER,
   K_CHOL_DIAG, K_CHOL_TRSM, K_CHOL_UPDATE, K_CHOL_BACK, K_CHOL_DIAG_TRSM, K_CHOL_TAIL, K_BACKSUB_UPDATE,
-  K_POSE_UPDATE, K_SCALARS, K_CONTROL, K_DAMP_INVERT, K_SCHUR_GRP, K_LIN_GRP, K_COUNT
+  K_POSE_UPDATE, K_SCALARS, K_CONTROL, K_DAMP_INVERT, K_SCHUR_GRP, K_LIN_GRP,
+  K_REL_LIN, K_REL_GATHER, K_REL_OFFDIAG, K_COUNT
 };
 struct KernelTimer {
   bool on = false;
@@ -262,6 +263,35 @@ void launch_scalars_and_control(const DevProblem &d, int cost_src, hipStream_t s
                                 int finalize_sel = -1);  // single GPU; finalize_sel >= 0: + k_pose_finalize workgroups
 void launch_control(const DevProblem &d, hipStream_t s);
 void launch_init_ctrl_cost(const DevProblem &d, hipStream_t s);
+
+// ---- relative-pose factors of the handle path (ba_rel.hip, ba_set_relative) ----
+// The factor arrays have a record of their own, an argument of the k_rel_* kernels only:
+// DevProblem, which every hot kernel takes by value, does not grow.  F = 0: no factors, and
+// nothing of this is launched.
+constexpr int kRelFpb = 64;  // factors per k_rel_lin workgroup
+constexpr int kRelScrDoubles = 126;  // scratch record of one factor (= kRelScr of ba_batch_kernels.h)
+struct RelDev {
+  int F;                  // factors
+  int nblk;               // coupled blocks of S (two optimisable poses)
+  int n_part;             // workgroups of k_rel_lin = cdiv(F, kRelFpb)
+  int pad_;
+  const int4 *jk;         // per factor: {pose j, pose k (internal), optimised index of j or -1, of k or -1}
+  const double *val;      // per factor: Z (12), Omega (36, mirrored by the host)
+  const int32_t *pptr, *plist;  // per optimised pose, input order: factor << 1 | (1: it is the factor's k)
+  const int32_t *blk;           // per coupled block: its id in sblk_j / sblk_k
+  const int32_t *bptr, *blist;  // per coupled block, input order: factor << 1 | (1: S_jk lies transposed)
+  double *scr[2];         // 126 doubles per factor (the record of the batch path), one per block buffer
+  double *part;           // 2 per k_rel_lin workgroup: sum of the factors' norms, cross term of the model
+};
+// mode bit 0: linearise at the `sel` poses into the scratch of that block buffer; bit 1: the
+// model's cross term from the accepted point's Omega Ad (scratch lcur) and x.  Always: the
+// factors' norms at the `sel` poses.  Both sums go to r.part.
+void launch_rel_lin(const DevProblem &d, const RelDev &r, int sel, int mode, hipStream_t s);
+// flags bit 0: add the factors' diagonal blocks and gradients to A_j, a_j of the `sel` block
+// buffer; bit 1: scal[0] += the norms; bit 2: scal[1] += the cross term (workgroup 0)
+void launch_rel_gather(const DevProblem &d, const RelDev &r, int sel, int flags, hipStream_t s);
+// S_jk += -Omega Ad of every coupled block into Spk (direct: and into the dense image)
+void launch_rel_offdiag(const DevProblem &d, const RelDev &r, bool direct, hipStream_t s);
 
 // ---- gradient descent (FullBundleAdjustmentSolverRefactor::SolveByGradientDescent) ----
 // Device state of the first-order loop (ba_gd_*), allocated on the first GD call after

@@ -118,6 +118,13 @@ struct ba_handle {
   bool gd_ready = false;
   bool gd_begun = false;
   ba::GdDev gd{};
+  // relative-pose factors (ba_set_relative): the pairs by user index and the packed values
+  // (ba_rel_host.h) as given; rel.F > 0 once ba_finalize has put them on the device (in
+  // `allocs`: freed with the problem)
+  std::vector<int32_t> rel_j, rel_k;
+  std::vector<double> rel_val;
+  ba::RelDev rel{};
+  size_t rel_bytes = 0;  // device bytes of the factor records and both scratch buffers
   // pose-only scratch (grown on demand, reused across calls)
   // pose-only: one device buffer + its pinned host mirror (po_run), barrier scratch
   uint8_t *po_dev = nullptr, *po_host = nullptr;
@@ -199,6 +206,8 @@ struct ba_handle {
     gd_ready = false;
     gd_begun = false;
     gd = ba::GdDev{};
+    rel = ba::RelDev{};
+    rel_bytes = 0;
     finalized = false;
   }
 };

@@ -900,6 +900,29 @@ std::string build_plan(const PlanInput &in, const PlanKnobs &knobs, Plan &pl) {
         a = b;
       }
     }
+    // relative-pose factors (PlanInput::rel_j / rel_k): every pair of two optimisable
+    // poses is an upper block too, added once when covisibility did not produce it —
+    // such a block has no slot contribution and no triple
+    std::vector<uint64_t> rel_new;  // (j << 32 | k) of the blocks that only a factor asks for
+    if (in.n_rel > 0) {
+      for (int j = 0; j < N; ++j) {
+        auto &rk = rowk[j];
+        std::sort(rk.begin(), rk.end());
+        rk.erase(std::unique(rk.begin(), rk.end()), rk.end());
+      }
+      for (int64_t f = 0; f < in.n_rel; ++f) {
+        const int32_t a = pl.pose_int_of_user[in.rel_j[f]], b = pl.pose_int_of_user[in.rel_k[f]];
+        if (a >= N || b >= N) continue;
+        const int32_t j = std::min(a, b), k = std::max(a, b);
+        if (!std::binary_search(rowk[j].begin(), rowk[j].end(), k))
+          rel_new.push_back(((uint64_t)(uint32_t)j << 32) | (uint32_t)k);
+      }
+      std::sort(rel_new.begin(), rel_new.end());
+      rel_new.erase(std::unique(rel_new.begin(), rel_new.end()), rel_new.end());
+      for (uint64_t key : rel_new) rowk[(int)(key >> 32)].push_back((int32_t)(uint32_t)key);
+    }
+    pl.n_rel = in.n_rel;
+    pl.n_rel_only = (int64_t)rel_new.size();
     std::vector<int64_t> blk_row_ptr(N + 1, 0);
     pl.sblk_j.clear();
     pl.sblk_k.clear();
@@ -921,6 +944,47 @@ std::string build_plan(const PlanInput &in, const PlanKnobs &knobs, Plan &pl) {
       const int32_t *e0 = &pl.sblk_k[blk_row_ptr[j + 1]];
       return (int32_t)(std::lower_bound(b0, e0, k) - &pl.sblk_k[0]);
     };
+    // the factors of every optimisable pose and of every coupled block, in input order
+    pl.rel_jk.clear();
+    pl.rel_pptr.clear();
+    pl.rel_plist.clear();
+    pl.rel_blk.clear();
+    pl.rel_bptr.clear();
+    pl.rel_blist.clear();
+    if (in.n_rel > 0) {
+      pl.rel_jk.resize((size_t)in.n_rel * 4);
+      pl.rel_pptr.assign((size_t)N + 1, 0);
+      std::vector<std::pair<int32_t, int32_t>> by_blk;  // (block, factor << 1 | transposed)
+      for (int64_t f = 0; f < in.n_rel; ++f) {
+        const int32_t a = pl.pose_int_of_user[in.rel_j[f]], b = pl.pose_int_of_user[in.rel_k[f]];
+        int32_t *r = &pl.rel_jk[(size_t)f * 4];
+        r[0] = a;
+        r[1] = b;
+        r[2] = a < N ? a : -1;
+        r[3] = b < N ? b : -1;
+        if (a < N) pl.rel_pptr[a + 1]++;
+        if (b < N) pl.rel_pptr[b + 1]++;
+        if (a < N && b < N)
+          by_blk.push_back({block_of(std::min(a, b), std::max(a, b)), (int32_t)(f << 1) | (a > b ? 1 : 0)});
+      }
+      for (int j = 0; j < N; ++j) pl.rel_pptr[j + 1] += pl.rel_pptr[j];
+      pl.rel_plist.resize((size_t)pl.rel_pptr[N]);
+      std::vector<int32_t> cur(pl.rel_pptr.begin(), pl.rel_pptr.end() - 1);
+      for (int64_t f = 0; f < in.n_rel; ++f) {
+        const int32_t *r = &pl.rel_jk[(size_t)f * 4];
+        if (r[2] >= 0) pl.rel_plist[cur[r[2]]++] = (int32_t)(f << 1);
+        if (r[3] >= 0) pl.rel_plist[cur[r[3]]++] = (int32_t)(f << 1) | 1;
+      }
+      std::stable_sort(by_blk.begin(), by_blk.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+      for (size_t t = 0; t < by_blk.size(); ++t) {
+        if (t == 0 || by_blk[t].first != by_blk[t - 1].first) {
+          pl.rel_blk.push_back(by_blk[t].first);
+          pl.rel_bptr.push_back((int32_t)t);
+        }
+        pl.rel_blist.push_back(by_blk[t].second);
+      }
+      pl.rel_bptr.push_back((int32_t)by_blk.size());
+    }
 
     // does not fit a super-run whole ...
     auto is_big = [&](int64_t d) {

@@ -70,6 +70,11 @@ struct PlanInput {
   const double *obs_uv = nullptr;
   int rank = 0;
   int world = 1;
+  // relative-pose factors (ba_set_relative): the two poses of every factor by user index,
+  // validated by the caller (in range, distinct, not both fixed)
+  int64_t n_rel = 0;
+  const int32_t *rel_j = nullptr;
+  const int32_t *rel_k = nullptr;
 };
 
 // Work-item granularities (shared with the kernels).
@@ -210,6 +215,13 @@ struct Plan {
   int64_t n_apart2 = 0;                  // rows (27 doubles) of Apart2 = sum of d over the k_lin_grp pieces
   std::vector<int32_t> pose_gpart_ptr, pose_gpart;  // N+1 / rows of Apart2 that belong to pose j
   int n_bchunk_grp = 0;                  // back-substitution chunks that cover the grouped landmarks
+  // ---- relative-pose factors (all empty without factors) ----
+  int64_t n_rel = 0;                     // factors
+  int64_t n_rel_only = 0;                // blocks of S that exist only because a factor names their pair
+  std::vector<int32_t> rel_jk;           // 4 per factor: internal pose j, k, optimised index of j or -1, of k or -1
+  std::vector<int32_t> rel_pptr, rel_plist;  // N+1 / per optimised pose, input order: factor << 1 | (1: it is the factor's k)
+  std::vector<int32_t> rel_blk;          // coupled blocks (ids into sblk_j/k), ascending
+  std::vector<int32_t> rel_bptr, rel_blist;  // per coupled block, input order: factor << 1 | (1: S_jk lies transposed)
 };
 
 // Tile pattern of the GLOBAL reduced camera matrix (all shards) for tiles of

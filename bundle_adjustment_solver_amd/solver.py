@@ -397,6 +397,40 @@ class BaProblem:
         check(self.lib.ba_update_values(self.h, None if T is None else _dp(T),
                                         None if X is None else _dp(X)), "ba_update_values")
 
+    def set_relative(self, rels):
+        """Relative-pose factors of the handle (ba_set_relative; scaled units), before
+        finalize.  rels: None (clears) or a dict j (F,), k (F,) user pose indices, Z (F, 12)
+        the measurement of T_j T_k^-1, Omega (F, 6, 6) of which the lower triangle counts."""
+        if rels is None or len(np.asarray(rels["j"]).reshape(-1)) == 0:
+            check(self.lib.ba_set_relative(self.h, 0, None, None, None, None), "ba_set_relative")
+            self._n_rel = 0
+            return
+        j = np.ascontiguousarray(rels["j"], np.int32).reshape(-1)
+        k = np.ascontiguousarray(rels["k"], np.int32).reshape(-1)
+        Z = np.ascontiguousarray(rels["Z"], np.float64).reshape(-1, 12)
+        Om = np.ascontiguousarray(rels["Omega"], np.float64).reshape(-1, 36)
+        if not (len(k) == len(j) and Z.shape[0] == len(j) and Om.shape[0] == len(j)):
+            raise ValueError("set_relative: needs j (F,), k (F,), Z (F, 12), Omega (F, 6, 6)")
+        check(self.lib.ba_set_relative(self.h, len(j), _ip(j), _ip(k), _dp(Z), _dp(Om)), "ba_set_relative")
+        self._n_rel = len(j)
+
+    def update_relative(self, Z, Omega):
+        """New Z (F, 12) and Omega (F, 6, 6) for the same pairs on the finalized handle
+        (ba_update_relative: no re-planning)."""
+        Z = np.ascontiguousarray(Z, np.float64).reshape(-1, 12)
+        Om = np.ascontiguousarray(Omega, np.float64).reshape(-1, 36)
+        n = getattr(self, "_n_rel", 0)
+        if Z.shape[0] != n or Om.shape[0] != n:
+            raise ValueError("update_relative: one Z and one Omega per factor of set_relative (%d)" % n)
+        check(self.lib.ba_update_relative(self.h, _dp(Z), _dp(Om)), "ba_update_relative")
+
+    def relative_info(self):
+        """-> dict: factors, blocks of S that carry a factor, blocks that exist only because
+        of a factor, device bytes of the factor records and scratch (ba_relative_info)"""
+        out = (C.c_int64 * 4)()
+        check(self.lib.ba_relative_info(self.h, out), "ba_relative_info")
+        return dict(factors=int(out[0]), blocks=int(out[1]), blocks_only=int(out[2]), bytes=int(out[3]))
+
     def set_allreduce(self, pyfunc):
         """pyfunc(which:int, dev_ptr:int, n_doubles:int, stream:int) -> int"""
         def _cb(user, which, ptr, n, stream):
@@ -1603,6 +1637,7 @@ class FullBundleAdjustmentSolver:
         self._pt_fixed = set()
         self._obs_cam, self._obs_pose, self._obs_pt, self._obs_uv = \
             [], [], [], []
+        self._relatives = []      # AddRelativePose: one scaled dict (F = 1) per factor, input order
         self.num_total_poses_ = 0
         self.num_total_points_ = 0
         self.num_fixed_poses_ = 0
@@ -1772,6 +1807,27 @@ class FullBundleAdjustmentSolver:
         self._obs_uv.append(uv * SCALER)
         self.num_total_observations_ += cam.shape[0]
 
+    def AddRelativePose(self, pose_j, pose_k, measurement, information, sigma_pixel=1.0):
+        """(new) A relative-pose factor between two registered poses (objects or integer
+        handles; distinct, not both fixed): an odometry or loop-closure edge of the problem
+        that Solve and ComputeCovariance then include (BaProblem.set_relative).  measurement,
+        information and sigma_pixel are those of a factor of SolveBatch's `relatives`
+        (_scaled_relatives): the measured pose_j^-1 * pose_k in AddPose's convention and
+        units, the 6x6 information of the tangent [v; omega] in the caller's units.  Call
+        before FinalizeParameters; afterwards it warns and is ignored, as AddPose.
+        ReloadParameterValues keeps the factors, Reset drops them."""
+        if self.is_parameter_finalized_:
+            self._finalized_warning()
+            return
+        fac = dict(pose_j=pose_j, pose_k=pose_k, measurement=measurement, information=information)
+        self._relatives.append(self._scaled_relatives("AddRelativePose", [self], [[fac]], sigma_pixel)[0])
+
+    def _relative_arrays(self):
+        """the factors of AddRelativePose as the dict BaProblem.set_relative takes, or None"""
+        if not self._relatives:
+            return None
+        return {key: np.concatenate([r[key] for r in self._relatives], axis=0) for key in ("j", "k", "Z", "Omega")}
+
     def ReloadParameterValues(self):
         """(new) Read the CURRENT values of every registered pose / point object again
         and hand them to the finalized problem (ba_update_values): a SLAM back end that
@@ -1850,6 +1906,10 @@ class FullBundleAdjustmentSolver:
             p.set_shard(*self._shard)
         if self._stream is not None:
             p.set_stream(self._stream)
+        if self._relatives:
+            if self._allreduce is not None:
+                raise _lib.BaError("relative-pose factors (AddRelativePose) run on one GPU; this solver is sharded")
+            p.set_relative(self._relative_arrays())
         p.finalize()
         if self._allreduce is not None:
             if hasattr(self._allreduce, "attach"):   # an exchange object (sharding.py)

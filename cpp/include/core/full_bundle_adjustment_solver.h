@@ -227,6 +227,15 @@ class FullBundleAdjustmentSolver {
     _BA_Pose measurement;
     double information[36] = {0.0};
   };
+  // (new) A relative-pose factor of THIS solver's problem: an odometry or loop-closure edge
+  // between two registered poses that Solve and ComputeCovariance then include
+  // (ba_set_relative: any number of poses and factors, one GPU).  Units and conventions are
+  // those of a factor of SolveBatch's in_relatives, converted for sigma_pixel in the same way.
+  // Call before FinalizeParameters; afterwards it warns and is ignored, as AddPose.
+  // ReloadParameterValues keeps the factors, Reset drops them.  Throws std::runtime_error on
+  // a pose that was never registered; what the library refuses (the same pose twice, both
+  // fixed, a non-finite value, a sharded solver) throws at FinalizeParameters.
+  void AddRelativePose(const RelativePose &factor, double sigma_pixel = 1.0);
   // the C-ABI handle behind the finalized problem (nullptr before FinalizeParameters):
   // for the readers of include/ba_hip.h; indices there are registration order
   ba_handle *GetHandle() const { return handle_; }
@@ -298,6 +307,7 @@ class FullBundleAdjustmentSolver {
                             const std::vector<std::vector<RelativePose>> *in_relatives, double sigma_pixel,
                             RelativeArrays *out);
   static int SetRelatives(ba_batch *batch, const RelativeArrays &r);
+  RelativeArrays relatives_;  // AddRelativePose: j, k, Z, Omega of this solver's factors (off unused)
   // the options' thresholds and iteration limit into a Summary (nullptr: nothing)
   static void BeginSummary(Summary *summary, const Options &options);
   // stderr warnings about weakly connected poses / points (reference

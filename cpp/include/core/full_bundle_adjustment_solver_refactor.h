@@ -123,6 +123,11 @@ class FullBundleAdjustmentSolverRefactor {
   // or Gauss-Newton as in Solve (anything else throws std::runtime_error), for this call only:
   // what an earlier Solve selected is put back afterwards.
   using RelativePose = FullBundleAdjustmentSolver::RelativePose;
+  // (new) a relative-pose factor of this solver's own problem, see
+  // FullBundleAdjustmentSolver::AddRelativePose
+  void AddRelativePose(const RelativePose &factor, double sigma_pixel = 1.0) {
+    impl_.AddRelativePose(factor, sigma_pixel);
+  }
   static bool SolveBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers, Options options,
                          std::vector<Summary> *summaries = nullptr,
                          const std::vector<PosePrior> *in_priors = nullptr, double sigma_pixel = 1.0,

@@ -54,6 +54,7 @@ void FullBundleAdjustmentSolver::Reset() {  // :44-70
   X_.clear();
   fixed_points_.clear();
   observations_.clear();
+  relatives_ = RelativeArrays();
   num_fixed_poses_ = num_fixed_points_ = 0;
 }
 
@@ -84,6 +85,20 @@ void FullBundleAdjustmentSolver::AddPose(_BA_Pose *original_pose) {  // :87-101
   pose_index_[original_pose] = static_cast<int>(poses_.size());
   poses_.push_back(original_pose);
   T_jw_.push_back(T_jw);
+}
+
+void FullBundleAdjustmentSolver::AddRelativePose(const RelativePose &factor, double sigma_pixel) {
+  if (is_parameter_finalized_) {
+    std::cerr << TEXT_YELLOW("Cannot enroll parameter. (is_parameter_finalized_ == true)") << std::endl;
+    return;
+  }
+  const std::vector<std::vector<RelativePose>> one(1, std::vector<RelativePose>(1, factor));
+  RelativeArrays a;
+  PackRelatives({this}, "AddRelativePose", &one, sigma_pixel, &a);
+  relatives_.j.push_back(a.j[0]);
+  relatives_.k.push_back(a.k[0]);
+  relatives_.Z.insert(relatives_.Z.end(), a.Z.begin(), a.Z.begin() + 12);
+  relatives_.Omega.insert(relatives_.Omega.end(), a.Omega.begin(), a.Omega.begin() + 36);
 }
 
 void FullBundleAdjustmentSolver::AddPoint(_BA_Point *original_point) {  // :103-117
@@ -188,6 +203,10 @@ void FullBundleAdjustmentSolver::FinalizeParameters() {  // :182-206, :243-308, 
   Check(ba_set_observations(handle_, static_cast<int64_t>(oc.size()), oc.data(), op.data(), oq.data(), uv.data()),
         "ba_set_observations");
   if (shard_world_ > 1) Check(ba_set_shard(handle_, shard_rank_, shard_world_), "ba_set_shard");
+  if (!relatives_.j.empty())
+    Check(ba_set_relative(handle_, static_cast<int64_t>(relatives_.j.size()), relatives_.j.data(), relatives_.k.data(),
+                          relatives_.Z.data(), relatives_.Omega.data()),
+          "ba_set_relative");
   Check(ba_finalize(handle_), "ba_finalize");
   if (allreduce_fn_) Check(ba_set_allreduce(handle_, allreduce_fn_, allreduce_user_), "ba_set_allreduce");
   is_parameter_finalized_ = true;

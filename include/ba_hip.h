@@ -108,6 +108,50 @@ int ba_finalize(ba_handle *h);
  * to re-seed it short of Reset.) */
 int ba_update_values(ba_handle *h, const double *T_jw12, const double *X3);
 
+/* Relative-pose factors on the handle path: odometry and loop-closure edges between the
+ * poses of a resident problem of any size.  The definition is
+ * ba_batch_set_relative's, word for word: factor f names two distinct poses rel_j[f],
+ * rel_k[f] by user index, at least one of them optimisable, a measurement Z (12 doubles,
+ * scaled units) of T_j T_k^-1 and a 6x6 information matrix Omega (36 doubles, row-major; only
+ * the lower triangle is read and mirrored).  r = se3_log(T_j T_k^-1 Z^-1), Jacobians I and
+ * -Ad(T_j T_k^-1):
+ *   A_j += Omega,  A_k += Ad^T Omega Ad,  S_jk += -Omega Ad,  a_j += -Omega r,  a_k += Ad^T Omega r.
+ * A fixed pose receives nothing.  The diagonal contributions join A_j before the damping, the
+ * off-diagonal block joins S undamped, the model gains 2 x_j^T S_jk x_k, every cost (initial,
+ * trial, ba_stage_cost) gains sqrt(max(0, r^T Omega r)) per factor; n_obs and the block count
+ * of the average step do not change; no robust weight.  Several factors may name one pair, in
+ * either orientation: they are summed in input order.  No cap on factors.  Every pair of two
+ * optimisable poses becomes a block of S (and couples their tiles in the factor's pattern)
+ * whether or not the two poses share a landmark; a pose without observations is held by its
+ * factors alone.  ba_solve / ba_lm_*, every ba_stage_* call and ba_covariance include the
+ * factors; ba_get_A / ba_get_S show the blocks with them.
+ * Call before ba_finalize (the factors change the structure); afterwards the call is refused.
+ * n_rel == 0, or every array NULL, clears.  Validation happens before anything touches the GPU,
+ * with the rules and messages of ba_batch_set_relative (-1 and ba_last_error, naming the
+ * factor): indices in range (ba_set_poses comes first), j != k, not both fixed, every value
+ * finite.  A refused call changes nothing.  ba_finalize checks the pairs once more against
+ * the poses it finds.
+ * Refused on a handle that holds factors, in whichever order the calls arrive: sharding
+ * (ba_set_shard with world > 1, ba_set_allreduce), gradient descent (ba_gd_*, ba_solve_gd) and
+ * BA_GRAPH=1 replay.  ba_stream_* takes no factors.  A handle without factors launches exactly
+ * the kernels it launched before.  One writer per element, fixed summation order, no
+ * floating-point atomics: the same bits run to run. */
+int ba_set_relative(ba_handle *h, int64_t n_rel, const int32_t *rel_j, const int32_t *rel_k,
+                    const double *Z12, const double *Omega36);
+/* New VALUES (Z, Omega) for the same pairs on a finalized handle, without planning again: the
+ * companion of ba_update_values, which keeps the factors.  Both arrays hold one entry per
+ * factor given to ba_set_relative; validated as there.  The next ba_solve / ba_lm_begin
+ * linearises with the new values. */
+int ba_update_relative(ba_handle *h, const double *Z12, const double *Omega36);
+/* Host-only (no GPU): the validation of ba_set_relative for n_pose poses with the flags
+ * pose_fixed (NULL: none fixed).  0, or -1 and ba_last_error. */
+int ba_relative_check(int n_pose, const uint8_t *pose_fixed, int64_t n_rel, const int32_t *rel_j,
+                      const int32_t *rel_k, const double *Z12, const double *Omega36);
+/* out4 = { factors, blocks of S that carry a factor, blocks of S that exist only because of a
+ * factor, device bytes of the factor records plus both scratch buffers }; before ba_finalize
+ * the last three are 0. */
+int ba_relative_info(ba_handle *h, int64_t out4[4]);
+
 /* Host-only helper (no GPU needed): owner rank of every point under the
  * sharding rule used by ba_finalize. */
 int ba_partition_points(int n_pose, const uint8_t *pose_fixed, int n_pt,
