@@ -7,7 +7,6 @@
 //   * landmark-major observation list (C/b/W side),
 //   * pose-major observation list (A/a side),
 //   * (landmark, pose) pair CSR for the cross blocks W_ji,
-//   * pose-major pair permutation (rhs side),
 //   * (j,k)-sorted triple list for the Schur complement blocks.
 #ifndef BA_PLAN_H_
 #define BA_PLAN_H_
@@ -146,7 +145,6 @@ struct Plan {
   std::vector<int64_t> achunk_begin;     // nchunk+1 style: begin of each
   std::vector<int64_t> achunk_end;
   std::vector<int32_t> pose_achunk_ptr;  // N+1
-  // ---- pose-major pair permutation ----
   // ---- Schur triples ----
   std::vector<int32_t> sblk_j, sblk_k;   // B
   std::vector<int32_t> diag_blk;         // N: block id of (j,j)
@@ -237,8 +235,6 @@ void partition_points(const PlanInput &in, int threads, std::vector<int32_t> &ow
 
 // Returns empty string on success, otherwise an error message.
 std::string build_plan(const PlanInput &in, const PlanKnobs &knobs, Plan &plan);
-// For a stand-alone caller without a handle: the knobs of the environment at this call.
-inline std::string build_plan(const PlanInput &in, Plan &plan) { return build_plan(in, Knobs::from_env().plan, plan); }
 
 }  // namespace ba
 #endif

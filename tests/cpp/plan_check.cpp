@@ -5,11 +5,11 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <set>
 #include <vector>
 
 #include "ba_plan.h"
+#include "plan_digest.h"
 
 static int g_fail = 0;
 #define CHECK(cond, ...)                                  \
@@ -301,28 +301,9 @@ int main(int argc, char **argv) {
   for (int64_t k = 0; k < pl.n_obs; ++k)
     CHECK(pl.obs_cp[2 * k] == (pl.obs_idx[4 * k] | (pl.obs_idx[4 * k + 1] << 16)) && pl.obs_cp[2 * k + 1] == pl.obs_idx[4 * k + 2],
           "slim record differs from the landmark-major record");
-  // ---- checksum of every array the kernels consume: the test runs this program with
-  // BA_PLAN_THREADS = 1 and = 7 and requires the same plan ----
-  {
-    auto mix = [](uint64_t h, uint64_t v) { return (h ^ v) * 0x100000001b3ull + (h >> 29); };
-    uint64_t h = 1469598103934665603ull;
-    for (auto v : pl.obs_idx) h = mix(h, (uint64_t)(uint32_t)v);
-    for (auto v : pl.obs_cp) h = mix(h, (uint64_t)(uint32_t)v);
-    for (auto v : pl.obs_uv) { uint64_t b; memcpy(&b, &v, 8); h = mix(h, b); }
-    for (auto v : pl.pair_pose) h = mix(h, (uint64_t)(uint32_t)v);
-    for (auto v : pl.pair_lm) h = mix(h, (uint64_t)(uint32_t)v);
-    for (auto v : pl.lm_obs_ptr) h = mix(h, (uint64_t)v);
-    for (auto v : pl.lm_pair_ptr) h = mix(h, (uint64_t)v);
-    for (auto v : pl.pt_user_of_int) h = mix(h, (uint64_t)(uint32_t)v);
-    for (auto v : pl.pobs_idx) h = mix(h, (uint64_t)(uint32_t)v);
-    for (auto v : pl.sblk_j) h = mix(h, (uint64_t)(uint32_t)v);
-    for (auto v : pl.sblk_k) h = mix(h, (uint64_t)(uint32_t)v);
-    for (auto v : pl.ltri) h = mix(h, (uint64_t)v);
-    for (auto v : pl.grp_pat) h = mix(h, (uint64_t)(uint32_t)v);
-    for (auto v : pl.contrib_slot) h = mix(h, (uint64_t)(uint32_t)v);
-    for (auto &g : pl.lin_desc) h = mix(mix(mix(h, (uint64_t)g.p0), (uint64_t)g.o0), (uint64_t)(uint32_t)g.l0);
-    std::printf("plan checksum %016llx\n", (unsigned long long)h);
-  }
+  // ---- digest of EVERY member of the plan (tests/cpp/plan_digest.h): the test runs this
+  // program with BA_PLAN_THREADS = 1 and = 7 and requires the same plan ----
+  std::printf("plan checksum %016llx\n", (unsigned long long)plan_digest::of(pl));
   std::printf("plan: M=%d (grouped %d in %zu+%zu pieces) P=%lld runs=%zu chunks=%zu triples=%lld (%lld in groups, +%lld big)  %s\n",
               pl.M, pl.M_grp, pl.grp32.size(), pl.grp64.size() + pl.grp128.size(), (long long)pl.P, pl.sup_desc.size(),
               pl.chunk_desc.size(), (long long)triples, (long long)grp_triples, (long long)big_triples,

@@ -17,7 +17,7 @@ CSRC = os.path.join(ROOT, "bundle_adjustment_solver_amd", "csrc")
 @pytest.fixture(scope="module")
 def plan_check(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("plan") / "plan_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-I", CSRC,
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I", CSRC, "-I", os.path.join(ROOT, "tests", "cpp"),
                     os.path.join(ROOT, "tests", "cpp", "plan_check.cpp"),
                     os.path.join(CSRC, "ba_plan.cpp"),
                     os.path.join(CSRC, "ba_dense_sched.cpp"), "-o", exe, "-pthread"], check=True)
@@ -57,9 +57,9 @@ def test_plan_invariants(plan_check, args, env):
                                   ["300", "100000", "5", "2"]])
 def test_threaded_plan_equals_the_serial_plan(plan_check, args):
     """The planner's per-landmark passes run on host threads (csrc/ba_plan.cpp
-    parallel_for; replaces reference :182-206, :243-308, :668-700).  Every array the
-    kernels consume must be identical for 1 and 7 threads (checksum printed by
-    tests/cpp/plan_check.cpp), and the invariants hold for both."""
+    parallel_for; replaces reference :182-206, :243-308, :668-700).  Every member of the
+    plan must be identical for 1 and 7 threads (the digest of tests/cpp/plan_digest.h,
+    printed by tests/cpp/plan_check.cpp), and the invariants hold for both."""
     sums = []
     for nt in ("1", "7"):
         r = subprocess.run([plan_check] + args, env=dict(os.environ, BA_PLAN_THREADS=nt),
@@ -67,6 +67,34 @@ def test_threaded_plan_equals_the_serial_plan(plan_check, args):
         assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout
         sums.append([l for l in r.stdout.splitlines() if l.startswith("plan checksum")])
     assert sums[0] and sums[0] == sums[1], sums
+
+
+def test_plan_digest_equals_the_recorded_plan(tmp_path):
+    """csrc/ba_plan.cpp build_plan decides the layout of every index array the kernels
+    stream (replaces reference :182-206, :243-308, :668-700).  tests/cpp/plan_digest.cpp
+    hashes EVERY member of the plan (tests/cpp/plan_digest.h) over a fixed list of cases:
+    the shapes of test_plan_invariants, world 2 and 3 at every rank (one shard without an
+    optimisable landmark), relative-pose factors of every kind, 1 and 7 threads, 65536
+    cameras, every planner knob off or set once, and the error paths with the string they
+    return.  Its output must equal, line by line, tests/cpp/plan_digest_expected.txt: the
+    output of the same program compiled against the planner of the commit named in that
+    file's first line (not the code under test).  The program itself fails when its list
+    no longer reaches masked groups, joined leftovers, all three group widths, super-runs,
+    split-class runs, the global triple list or factor-only blocks."""
+    exe = str(tmp_path / "plan_digest")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I", CSRC, "-I", os.path.join(ROOT, "tests", "cpp"),
+                    os.path.join(ROOT, "tests", "cpp", "plan_digest.cpp"),
+                    os.path.join(CSRC, "ba_plan.cpp"),
+                    os.path.join(CSRC, "ba_dense_sched.cpp"), "-o", exe, "-pthread"], check=True)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and r.stdout.strip().endswith("PLAN DIGEST OK"), r.stdout[-3000:]
+    with open(os.path.join(ROOT, "tests", "cpp", "plan_digest_expected.txt")) as fh:
+        want = [l.rstrip("\n") for l in fh if not l.startswith("#")]
+    got = r.stdout.splitlines()
+    assert len(want) > 80 and sum(l.startswith("case ") for l in want) > 50
+    for g, w in zip(got, want):
+        assert g == w
+    assert len(got) == len(want)
 
 
 def test_dense_level_schedule_executes_to_the_dense_solution(tmp_path):
