@@ -290,6 +290,18 @@ SIGNATURES = {
     "ba_point_only_check": (C.c_int, [C.c_int, C.c_int, C.c_int, _I64, _I32, _I32]),
     "ba_point_only_team": (C.c_int, [C.c_int]),
     "ba_point_only_last_ms": (C.c_int, [_D]),
+    "ba_pgraph_create": (C.c_int, [C.POINTER(_P), _P, C.c_int, _D, _U8, C.c_int64, _I32, _I32,
+                                   _D, _D]),
+    "ba_pgraph_destroy": (None, [_P]),
+    "ba_pgraph_update_values": (C.c_int, [_P, _D, _D, _D]),
+    "ba_pgraph_solve": (C.c_int, [_P, C.POINTER(BaOptions), C.POINTER(BaIterInfo), C.c_int,
+                                  C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ba_pgraph_get_poses": (C.c_int, [_P, _D]),
+    "ba_pgraph_cost": (C.c_int, [_P, _D]),
+    "ba_pgraph_get_system": (C.c_int, [_P, _D, _D]),
+    "ba_pgraph_info": (C.c_int, [_P, _I64]),
+    "ba_pgraph_last_ms": (C.c_int, [_P, _D]),
+    "ba_pgraph_check": (C.c_int, [C.c_int, _D, _U8, C.c_int64, _I32, _I32, _D, _D]),
 }
 
 _lib = None

@@ -187,9 +187,10 @@ int download(std::vector<T> &out, const T *dev, size_t n, hipStream_t s) {
 // (npad entries), the solution in column order xc, the dropped-pivot counter, the order,
 // flags and tickets of the dataflow sweeps, the k_chol_dag / k_chol_look items and
 // counters and the step records of the cone sweep; fixes the launch plans from the handle's dense knobs.  Everything is allocated on
-// the handle (h->upload / h->dalloc, in h->allocs).
-int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::vector<int> &col_x,
-                          ba::DenseDev &dd) {
+// the handle (h->upload / h->dalloc, in h->allocs).  Also used by ba_pgraph.hip.
+}  // namespace
+int ba::upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::vector<int> &col_x,
+                              ba::DenseDev &dd) {
   const size_t npad = col_x.size(), ncb = (size_t)std::max(1, sc.ncb);
   constexpr Mem R = Mem::Resident;  // a dense system is pose-sized and shared by every chunk
   if (h->upload(R, &dd.row_ptr, sc.row_ptr) || h->upload(R, &dd.rows, sc.rows) ||
@@ -233,6 +234,8 @@ int upload_dense_schedule(ba_handle *h, const ba::DenseSchedule &sc, const std::
   }
   return 0;
 }
+namespace {
+using ba::upload_dense_schedule;
 
 // ---- the steps of ba_finalize, in the order it runs them.  Every dalloc / upload names
 // its residency (ba_handle.h: Mem); the ORDER of the chunk allocations fixes the layout
@@ -1584,7 +1587,8 @@ const char *ba_kernel_name(int id) {
       "k_schur_lds", "k_schur_partial", "k_schur_final", "k_scatter",
       "k_chol_diag", "k_chol_trsm", "k_chol_update", "k_chol_back", "k_chol_diag_trsm", "k_chol_tail", "k_backsub_update",
       "k_pose_update", "k_scalars", "k_control", "k_damp_invert", "k_schur_grp", "k_lin_grp",
-      "k_rel_lin", "k_rel_gather", "k_rel_offdiag"};
+      "k_rel_lin", "k_rel_gather", "k_rel_offdiag",
+      "k_pg_lin", "k_pg_assemble", "k_pg_trial", "k_pg_control"};
   return (id >= 0 && id < ba::K_COUNT) ? names[id] : "";
 }
 

@@ -209,7 +209,8 @@ enum KernelId {
   K_SCHUR_LDS, K_SCHUR_PARTIAL, K_SCHUR_FINAL, K_SCATTER,
   K_CHOL_DIAG, K_CHOL_TRSM, K_CHOL_UPDATE, K_CHOL_BACK, K_CHOL_DIAG_TRSM, K_CHOL_TAIL, K_BACKSUB_UPDATE,
   K_POSE_UPDATE, K_SCALARS, K_CONTROL, K_DAMP_INVERT, K_SCHUR_GRP, K_LIN_GRP,
-  K_REL_LIN, K_REL_GATHER, K_REL_OFFDIAG, K_COUNT
+  K_REL_LIN, K_REL_GATHER, K_REL_OFFDIAG,
+  K_PG_LIN, K_PG_ASSEMBLE, K_PG_TRIAL, K_PG_CONTROL, K_COUNT
 };
 struct KernelTimer {
   bool on = false;
@@ -292,6 +293,59 @@ void launch_rel_lin(const DevProblem &d, const RelDev &r, int sel, int mode, hip
 void launch_rel_gather(const DevProblem &d, const RelDev &r, int sel, int flags, hipStream_t s);
 // S_jk += -Omega Ad of every coupled block into Spk (direct: and into the dense image)
 void launch_rel_offdiag(const DevProblem &d, const RelDev &r, bool direct, hipStream_t s);
+
+// ---- pose-graph optimisation (ba_pgraph.hip, ba_pgraph_*) ----
+// LM over relative-pose factors alone: chi2 = sum_f r_f^T Omega_f r_f, no landmark in the
+// problem.  The controller lives on the device, as DevCtrl does for the handle path, so that
+// max_num_iterations iterations are enqueued without a host round trip; `done` is the control
+// word that dense_factor_solve and every k_pg_* kernel test first.
+struct PgCtrl {
+  double lambda;
+  double chi2;      // chi-square at the accepted poses
+  double thr_step, thr_cost, dec_ratio, inc_ratio;
+  double aux;       // k_pg_control, mode 1: chi-square of the last cost-only pass
+  unsigned long long t_last;
+  int cur;          // which pose buffer holds the accepted poses
+  int done;
+  int iter, converged, max_iter, gn;
+  int relin;        // the records belong to another point than the accepted one
+  int pad_;
+};
+constexpr int kPgFpb = 64;   // factors per k_pg_lin workgroup
+constexpr int kPgRec = 84;   // record of one factor: Omega r (6), Ad^T Omega r (6), Omega Ad (36), Ad^T Omega Ad (36)
+constexpr int kPgOr = 0, kPgGk = 6, kPgOA = 12, kPgBk = 48;
+struct PgDev {
+  int n_pose, N, F, nblk;
+  int n_part;             // workgroups of k_pg_lin = cdiv(F, kPgFpb)
+  int n_tpart;            // workgroups of k_pg_trial = cdiv(N, 256)
+  int npad, ld;           // the dense image: npad columns of ld rows, g in row npad
+  double *poses[2];       // 12 per pose (user order); a fixed pose has the same bits in both
+  const int4 *jk;         // per factor: {pose j, pose k, optimisable index of j or -1, of k or -1}
+  const double *val;      // per factor: Z (12), Omega (36, mirrored by the host)
+  const int32_t *pptr, *plist;  // per optimisable pose, input order: factor << 1 | (1: it is the factor's k)
+  const int2 *blk;              // per coupled block: optimisable poses {hi, lo}, hi > lo
+  const int32_t *bptr, *blist;  // per coupled block, input order: factor << 1 | (1: H_jk lies transposed)
+  const int32_t *opt_pose;      // per optimisable pose: its pose
+  const int *pose_col;          // per optimisable pose: its first column of the image
+  double *rec;            // kPgRec doubles per factor
+  double *dH, *g;         // 6N each: diag(H) and g of the last assembly
+  double *x;              // 6N (+ 64)
+  double *part[2];        // n_part each: chi-square partials of the linearisation / of a cost-only pass
+  double *tpart;          // 2 n_tpart: partials of sum |x_j| and of pred
+  double *L;
+  PgCtrl *ctrl;
+  DevIterRec *log;
+  int log_cap;
+};
+// cost_only = 0: linearise at the accepted poses (records + part[0]; skipped while !ctrl->relin);
+// 1: chi-square partials at the trial poses -> part[1]; 2: at the accepted poses -> part[1]
+void launch_pg_lin(const PgDev &p, int cost_only, hipStream_t s);
+// H + lambda diag(H) and g into the image (Hout == nullptr), or the undamped H (6N x 6N,
+// both triangles) and g into Hout / gout
+void launch_pg_assemble(const PgDev &p, double *Hout, double *gout, hipStream_t s);
+void launch_pg_trial(const PgDev &p, hipStream_t s);
+// mode 0: the trust-region step of one iteration; 1: ctrl->aux = sum of part[1]
+void launch_pg_control(const PgDev &p, int mode, hipStream_t s);
 
 // ---- gradient descent (FullBundleAdjustmentSolverRefactor::SolveByGradientDescent) ----
 // Device state of the first-order loop (ba_gd_*), allocated on the first GD call after

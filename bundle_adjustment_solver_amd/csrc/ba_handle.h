@@ -229,6 +229,9 @@ struct ScratchAllocs {
 int lm_prepare_ctrl(ba_handle *h, const ba_options *opt, int *done_after);
 int ctrl_pull(ba_handle *h);  // device controller state -> h->hc (synchronises the stream)
 int ctrl_push(ba_handle *h);
+// Device set-up of a dense schedule (ba_api.hip): the work lists of `dd`, the column -> x map,
+// the launch plans from the handle's dense knobs.  Allocated on the handle (h->allocs).
+int upload_dense_schedule(ba_handle *h, const DenseSchedule &sc, const std::vector<int> &col_x, DenseDev &dd);
 }  // namespace ba
 
 #endif  // BA_HANDLE_H_

@@ -1,0 +1,115 @@
+// ba_pgraph_host.h — host side of the pose-graph optimisation (ba_pgraph_*, ba_pgraph.hip;
+// DESIGN.md §6k): validation of the caller's arrays, the per-pose and per-block factor
+// lists and the tile adjacency of the dense image.  Plain C++ with no HIP call, so that it
+// also builds into a stand-alone program under the host sanitizers
+// (tools/pgraph_host_check.cpp).  Internal.
+#ifndef BA_PGRAPH_HOST_H_
+#define BA_PGRAPH_HOST_H_
+
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "ba_rel_host.h"
+
+namespace ba {
+
+// Everything ba_pgraph_check refuses: empty inputs, then the rules and the wording of
+// ba_relative_check (*err names the factor), then an optimisable pose that no factor names
+// (*err names the pose: its diagonal block would be zero).  pose_fixed may be null.
+inline int pgraph_validate_host(int n_pose, const double *T_jw12, const uint8_t *pose_fixed, int64_t n_rel,
+                                const int32_t *rel_j, const int32_t *rel_k, const double *Z12,
+                                const double *Omega36, std::string *err) {
+  auto bad = [&](const std::string &m) {
+    *err = m;
+    return -1;
+  };
+  if (n_pose <= 0) return bad("n_pose must be >= 1");
+  if (n_rel <= 0) return bad("n_rel must be >= 1: a pose graph needs a factor");
+  if (!T_jw12) return bad("null pose array");
+  if (relative_validate_host(kRelPairs | kRelValues, n_pose, pose_fixed, n_rel, rel_j, rel_k, Z12, Omega36, err))
+    return -1;
+  for (int64_t e = 0; e < (int64_t)n_pose * 12; ++e)
+    if (!std::isfinite(T_jw12[e])) return bad("T_jw is not finite (pose " + std::to_string(e / 12) + ")");
+  std::vector<uint8_t> named((size_t)n_pose, 0);
+  for (int64_t f = 0; f < n_rel; ++f) named[rel_j[f]] = named[rel_k[f]] = 1;
+  for (int p = 0; p < n_pose; ++p)
+    if (!(pose_fixed && pose_fixed[p]) && !named[p])
+      return bad("pose " + std::to_string(p) + " is optimisable but no factor names it");
+  return 0;
+}
+
+// The structure of a validated graph.  The optimisable poses keep the user's order:
+// optimisable index = rank among the optimisable poses.
+struct PgraphLists {
+  int N = 0;
+  std::vector<int32_t> opt_of_pose;   // per pose: optimisable index or -1
+  std::vector<int32_t> opt_pose;      // per optimisable pose: its pose
+  std::vector<int32_t> jk;            // 4 per factor: {pose j, pose k, optimisable index of j or -1, of k or -1}
+  std::vector<int32_t> pptr, plist;   // per optimisable pose, input order: factor << 1 | (1: it is the factor's k)
+  std::vector<int32_t> blk;           // 2 per coupled block: optimisable poses {hi, lo}, hi > lo, ascending (hi, lo)
+  std::vector<int32_t> bptr, blist;   // per coupled block, input order: factor << 1 | (1: H_jk lies transposed)
+};
+
+inline void pgraph_build_lists(int n_pose, const uint8_t *pose_fixed, int64_t n_rel, const int32_t *rel_j,
+                               const int32_t *rel_k, PgraphLists *out) {
+  PgraphLists &l = *out;
+  l = PgraphLists();
+  l.opt_of_pose.assign((size_t)n_pose, -1);
+  for (int p = 0; p < n_pose; ++p)
+    if (!(pose_fixed && pose_fixed[p])) {
+      l.opt_of_pose[p] = l.N++;
+      l.opt_pose.push_back(p);
+    }
+  const int N = l.N;
+  l.jk.resize((size_t)n_rel * 4);
+  l.pptr.assign((size_t)N + 1, 0);
+  std::vector<std::pair<int64_t, int32_t>> by_blk;  // (hi * N + lo, factor << 1 | transposed)
+  for (int64_t f = 0; f < n_rel; ++f) {
+    const int32_t a = l.opt_of_pose[rel_j[f]], b = l.opt_of_pose[rel_k[f]];
+    int32_t *r = &l.jk[(size_t)f * 4];
+    r[0] = rel_j[f];
+    r[1] = rel_k[f];
+    r[2] = a;
+    r[3] = b;
+    if (a >= 0) l.pptr[a + 1]++;
+    if (b >= 0) l.pptr[b + 1]++;
+    if (a >= 0 && b >= 0)  // H_jk is block (j, k): below the diagonal as it is when j > k
+      by_blk.push_back({(int64_t)std::max(a, b) * N + std::min(a, b), (int32_t)(f << 1) | (a < b ? 1 : 0)});
+  }
+  for (int j = 0; j < N; ++j) l.pptr[j + 1] += l.pptr[j];
+  l.plist.resize((size_t)l.pptr[N]);
+  std::vector<int32_t> cur(l.pptr.begin(), l.pptr.end() - 1);
+  for (int64_t f = 0; f < n_rel; ++f) {
+    const int32_t *r = &l.jk[(size_t)f * 4];
+    if (r[2] >= 0) l.plist[cur[r[2]]++] = (int32_t)(f << 1);
+    if (r[3] >= 0) l.plist[cur[r[3]]++] = (int32_t)(f << 1) | 1;
+  }
+  std::stable_sort(by_blk.begin(), by_blk.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+  for (size_t t = 0; t < by_blk.size(); ++t) {
+    if (t == 0 || by_blk[t].first != by_blk[t - 1].first) {
+      l.blk.push_back((int32_t)(by_blk[t].first / N));
+      l.blk.push_back((int32_t)(by_blk[t].first % N));
+      l.bptr.push_back((int32_t)t);
+    }
+    l.blist.push_back(by_blk[t].second);
+  }
+  l.bptr.push_back((int32_t)by_blk.size());
+}
+
+// Symmetric ncb x ncb tile adjacency (row-major bytes, zero diagonal) of the coupled blocks
+// with poses_per_tile optimisable poses per tile, in the order of their indices.
+inline void pgraph_tile_adjacency(const PgraphLists &l, int poses_per_tile, int *ncb, std::vector<uint8_t> *adj) {
+  const int n = std::max(1, (l.N + poses_per_tile - 1) / poses_per_tile);
+  *ncb = n;
+  adj->assign((size_t)n * n, 0);
+  for (size_t b = 0; b + 1 < l.blk.size(); b += 2) {
+    const int I = l.blk[b] / poses_per_tile, J = l.blk[b + 1] / poses_per_tile;
+    if (I != J) (*adj)[(size_t)I * n + J] = (*adj)[(size_t)J * n + I] = 1;
+  }
+}
+
+}  // namespace ba
+#endif  // BA_PGRAPH_HOST_H_

@@ -1507,6 +1507,118 @@ class BaBatch:
         return out
 
 
+def pgraph_check(pose_T, pose_fixed, rels):
+    """Host-only validation of BaPoseGraph's inputs (ba_pgraph_check); raises BaError."""
+    T = np.ascontiguousarray(pose_T, np.float64).reshape(-1, 12)
+    fx = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
+    j = np.ascontiguousarray(rels["j"], np.int32).reshape(-1)
+    k = np.ascontiguousarray(rels["k"], np.int32).reshape(-1)
+    Z = np.ascontiguousarray(rels["Z"], np.float64).reshape(-1, 12)
+    Om = np.ascontiguousarray(rels["Omega"], np.float64).reshape(-1, 36)
+    check(_lib.load().ba_pgraph_check(T.shape[0], _dp(T) if T.size else None, None if fx is None else _up(fx),
+                                      len(j), _ip(j), _ip(k), _dp(Z), _dp(Om)), "ba_pgraph_check")
+
+
+class BaPoseGraph:
+    """Pose-graph optimisation (ba_pgraph_* of include/ba_hip.h): chi-square
+    Levenberg-Marquardt over relative-pose factors alone.  pose_T (n, 12) T_jw in scaled
+    units, pose_fixed (n,) or None, rels the dict of BaProblem.set_relative.  The structure
+    (lists, tile schedule, dense image) is planned once; update_values + solve re-optimise
+    new values.  owner: a BaProblem whose handle (device, stream, BA_DENSE_* knobs) is
+    borrowed, or None for a handle of its own."""
+
+    def __init__(self, pose_T, pose_fixed, rels, device=0, owner=None):
+        self.lib = _lib.load()
+        self.g = None
+        self._own = owner is None
+        self._owner = None
+        T = np.ascontiguousarray(pose_T, np.float64).reshape(-1, 12)
+        fx = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
+        j = np.ascontiguousarray(rels["j"], np.int32).reshape(-1)
+        k = np.ascontiguousarray(rels["k"], np.int32).reshape(-1)
+        Z = np.ascontiguousarray(rels["Z"], np.float64).reshape(-1, 12)
+        Om = np.ascontiguousarray(rels["Omega"], np.float64).reshape(-1, 36)
+        if not (len(k) == len(j) and Z.shape[0] == len(j) and Om.shape[0] == len(j)) or \
+                (fx is not None and len(fx) != T.shape[0]):
+            raise ValueError("BaPoseGraph: needs pose_T (n, 12), pose_fixed (n,), j (F,), k (F,), Z (F, 12), "
+                             "Omega (F, 6, 6)")
+        pgraph_check(T, fx, dict(j=j, k=k, Z=Z, Omega=Om))   # refusals need no device
+        self.n_pose, self.n_rel = T.shape[0], len(j)
+        self._owner = BaProblem(device) if owner is None else owner
+        g = C.c_void_p()
+        check(self.lib.ba_pgraph_create(C.byref(g), self._owner.h, self.n_pose, _dp(T),
+                                        None if fx is None else _up(fx), self.n_rel, _ip(j), _ip(k),
+                                        _dp(Z), _dp(Om)), "ba_pgraph_create")
+        self.g = g
+
+    def close(self):
+        if self.g:
+            self.lib.ba_pgraph_destroy(self.g)
+            self.g = None
+        if self._owner is not None and self._own:
+            self._owner.close()
+        self._owner = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update_values(self, pose_T=None, Z=None, Omega=None):
+        """New values for the same structure (ba_pgraph_update_values); None keeps."""
+        T = None if pose_T is None else np.ascontiguousarray(pose_T, np.float64).reshape(-1, 12)
+        Zs = None if Z is None else np.ascontiguousarray(Z, np.float64).reshape(-1, 12)
+        Om = None if Omega is None else np.ascontiguousarray(Omega, np.float64).reshape(-1, 36)
+        if (T is not None and T.shape[0] != self.n_pose) or (Zs is not None and Zs.shape[0] != self.n_rel) or \
+                (Om is not None and Om.shape[0] != self.n_rel):
+            raise ValueError("update_values: the structure is fixed (same number of poses / factors)")
+        check(self.lib.ba_pgraph_update_values(self.g, None if T is None else _dp(T),
+                                               None if Zs is None else _dp(Zs),
+                                               None if Om is None else _dp(Om)), "ba_pgraph_update_values")
+
+    def solve(self, opt, cap=None, rows=None):
+        """-> (rows, converged): the logged ba_iter_info rows.  rows: a BaIterInfo array to
+        write into (then all `cap` entries are returned), or None."""
+        cap = max(1, opt.max_num_iterations) if cap is None else cap
+        given = rows is not None
+        rows = (BaIterInfo * max(1, cap))() if rows is None else rows
+        n_iter, conv = C.c_int(0), C.c_int(0)
+        check(self.lib.ba_pgraph_solve(self.g, C.byref(opt), rows, cap, C.byref(n_iter), C.byref(conv)),
+              "ba_pgraph_solve")
+        self.n_iter = n_iter.value
+        n = cap if given else min(n_iter.value, cap)
+        return [rows[i] for i in range(n)], bool(conv.value)
+
+    def poses(self):
+        T = np.zeros((self.n_pose, 12))
+        check(self.lib.ba_pgraph_get_poses(self.g, _dp(T)), "ba_pgraph_get_poses")
+        return T
+
+    def cost(self):
+        v = C.c_double(0.0)
+        check(self.lib.ba_pgraph_cost(self.g, C.byref(v)), "ba_pgraph_cost")
+        return v.value
+
+    def system(self):
+        """-> (H (6N, 6N), g (6N,)): the undamped system at the poses the object holds"""
+        N = self.info()["N"]
+        H, g = np.zeros((6 * N, 6 * N)), np.zeros(6 * N)
+        check(self.lib.ba_pgraph_get_system(self.g, _dp(H), _dp(g)), "ba_pgraph_get_system")
+        return H, g
+
+    def info(self):
+        out = (C.c_int64 * 8)()
+        check(self.lib.ba_pgraph_info(self.g, out), "ba_pgraph_info")
+        keys = ("N", "factors", "blocks", "nb", "tiles", "levels", "image_bytes", "bad_pivots")
+        return {key: int(out[i]) for i, key in enumerate(keys)}
+
+    def last_ms(self):
+        v = C.c_double(0.0)
+        check(self.lib.ba_pgraph_last_ms(self.g, C.byref(v)), "ba_pgraph_last_ms")
+        return v.value
+
+
 class BaStream:
     """Observation streaming (include/ba_hip.h ba_stream_*): the
     same problem-construction calls and LM loop as BaProblem for a problem whose
@@ -1992,6 +2104,39 @@ class FullBundleAdjustmentSolver:
         c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
         rows, converged = p.solve(c_opt)
         return self._finish_solve(rows, converged, summary, t0)
+
+    def SolvePoseGraph(self, options, summary=None):
+        """(new) Pose-graph optimisation: Levenberg-Marquardt over the factors of
+        AddRelativePose ALONE, on the registered poses with their fixed flags (BaPoseGraph,
+        ba_pgraph_*; chi-square LM).  Needs no camera, point, observation or
+        FinalizeParameters.  options.solver_type GAUSS_NEWTON is honoured by the refactored
+        class as in its Solve.  Fills `summary` from the rows and writes the poses back into
+        the registered pose objects as Solve does; the solver's own copies follow, so that a
+        second call continues from the first.  A finalized problem of the same solver takes
+        the new poses with ReloadParameterValues."""
+        t0 = time.perf_counter()
+        if summary is not None:
+            summary.max_iteration_ = options.iteration_handle.max_num_iterations
+            summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change
+            summary.threshold_step_size_ = options.convergence_handle.threshold_step_size
+            summary.convergence_status_ = True
+        rels = self._relative_arrays()
+        if rels is None or not self.num_total_poses_:
+            raise RuntimeError("SolvePoseGraph: poses (AddPose) and factors (AddRelativePose) must be added first")
+        T_jw = np.concatenate(self._pose_T_jw, axis=0)
+        pf = np.zeros(self.num_total_poses_, np.uint8)
+        pf[list(self._pose_fixed)] = 1
+        c_opt = options.to_c()
+        c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
+        g = BaPoseGraph(T_jw, pf, rels, self.device)
+        try:
+            rows, converged = g.solve(c_opt)
+            T_new = g.poses()
+        finally:
+            g.close()
+        self._pose_T_jw = [T_new]
+        n_pt = self.num_total_points_
+        return self._write_back(T_new, np.zeros((n_pt, 3)), np.zeros(n_pt, bool), rows, converged, summary, t0)
 
     @staticmethod
     def _scaled_priors(what, solvers, priors, sigma_pixel):

@@ -77,6 +77,16 @@ class FullBundleAdjustmentSolver {
 
   bool Solve(Options options, Summary *summary = nullptr);
 
+  // (new; the reference has no counterpart) Pose-graph optimisation: Levenberg-Marquardt over
+  // the factors of AddRelativePose ALONE, on the registered poses with their fixed flags
+  // (ba_pgraph_* of include/ba_hip.h: chi-square LM, the definition is there).  Needs no
+  // camera, point, observation or FinalizeParameters; the solver's current values are used and
+  // the solved poses become them, written back through the caller's pointers as Solve writes
+  // them.  The rows of `summary` are those of ba_pgraph_solve.  A finalized problem of the same
+  // solver takes the new poses with ReloadParameterValues.  Throws std::runtime_error without
+  // poses or factors, and on every refusal of ba_pgraph_create.
+  bool SolvePoseGraph(Options options, Summary *summary = nullptr);
+
   // (new) Solve the registered problems of several solver objects in ONE GPU launch
   // (ba_batch_solve of include/ba_hip.h: one persistent workgroup per problem runs the
   // whole LM loop; per problem at most 16 optimisable poses, 64 poses, 8 cameras).

@@ -71,6 +71,10 @@ class FullBundleAdjustmentSolverRefactor {
   // point block clipped to norm 1e-3 in the solver's scaled units, every step taken;
   // solver_type and the lambda ratios are ignored, damping_term = initial_lambda
   bool SolveByGradientDescent(Options options, Summary *summary = nullptr);
+  // (new) pose-graph optimisation over the factors of AddRelativePose alone, see
+  // FullBundleAdjustmentSolver::SolvePoseGraph; solver_type selects Levenberg-Marquardt or
+  // Gauss-Newton as in Solve, for this call only
+  bool SolvePoseGraph(Options options, Summary *summary = nullptr);
 
   // (new) covariance blocks of the current state, see FullBundleAdjustmentSolver::ComputeCovariance:
   // same units, same tangent convention (world-to-body T_jw = inverse(*pose), T_jw <- exp(xi) T_jw)

@@ -410,6 +410,52 @@ bool FullBundleAdjustmentSolver::Run(Options options, Summary *summary, bool gra
   return true;  // the reference always returns true (:1043)
 }
 
+bool FullBundleAdjustmentSolver::SolvePoseGraph(Options options, Summary *summary) {
+  timer::StopWatch stopwatch("BundleAdjustmentSolver::SolvePoseGraph");
+  stopwatch.Start();
+  BeginSummary(summary, options);
+  if (poses_.empty() || relatives_.j.empty())
+    throw std::runtime_error("SolvePoseGraph: poses (AddPose) and factors (AddRelativePose) must be added first");
+  std::vector<double> T(12 * poses_.size());
+  std::vector<uint8_t> pose_fixed(poses_.size(), 0);
+  for (size_t p = 0; p < poses_.size(); ++p) {
+    Pack12(T_jw_[p], &T[12 * p]);
+    pose_fixed[p] = fixed_poses_.count(static_cast<int>(p)) > 0;
+  }
+  const ba_options o = PackOptions(options, gauss_newton_);
+  std::vector<ba_iter_info> rows(static_cast<size_t>(std::max(1, o.max_num_iterations)));
+  int n_iter = 0, converged = 0;
+  // the graph borrows a handle for its device and stream: the finalized problem's, or one of its own
+  ba_handle *h = handle_;
+  if (h == nullptr) Check(ba_create(&h, device_id_), "ba_create");
+  ba_pgraph *g = nullptr;
+  int rc = ba_pgraph_create(&g, h, static_cast<int>(poses_.size()), T.data(), pose_fixed.data(),
+                            static_cast<int64_t>(relatives_.j.size()), relatives_.j.data(), relatives_.k.data(),
+                            relatives_.Z.data(), relatives_.Omega.data());
+  const char *what = "ba_pgraph_create";
+  if (rc == 0) {
+    rc = ba_pgraph_solve(g, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged);
+    what = "ba_pgraph_solve";
+  }
+  if (rc == 0) {
+    rc = ba_pgraph_get_poses(g, T.data());
+    what = "ba_pgraph_get_poses";
+  }
+  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
+  ba_pgraph_destroy(g);
+  if (h != handle_) ba_destroy(h);
+  if (rc != 0) throw std::runtime_error(std::string(what) + ": " + err);
+  const std::vector<uint8_t> no_point(points_.size(), 0);
+  WriteBack(T.data(), nullptr, no_point.data());
+  if (summary != nullptr) {
+    for (int k = 0; k < n_iter && k < static_cast<int>(rows.size()); ++k)
+      summary->optimization_info_list_.push_back(ToInfo(rows[k]));
+    summary->convergence_status_ = converged != 0;
+    summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
+  }
+  return true;
+}
+
 bool FullBundleAdjustmentSolver::ComputeCovariance(const std::vector<_BA_Pose *> &poses,
                                                    const std::vector<_BA_Point *> &points, double sigma_pixel,
                                                    std::vector<Eigen::Matrix<double, 6, 6>> *cov_poses,

@@ -95,6 +95,23 @@ bool FullBundleAdjustmentSolverRefactor::SolvePointsOnly(Options options, std::v
   return ok;
 }
 
+bool FullBundleAdjustmentSolverRefactor::SolvePoseGraph(Options options, Summary *summary) {
+  if (options.solver_type != SolverType::LEVENBERG_MARQUARDT && options.solver_type != SolverType::GAUSS_NEWTON)
+    throw std::runtime_error(
+        "FullBundleAdjustmentSolverRefactor::SolvePoseGraph: solver_type must be GAUSS_NEWTON or LEVENBERG_MARQUARDT");
+  const bool before = impl_.gauss_newton_;  // the mode holds for this call only
+  impl_.SetGaussNewton(options.solver_type == SolverType::GAUSS_NEWTON);
+  bool ok = false;
+  try {
+    ok = impl_.SolvePoseGraph(options, summary);
+  } catch (...) {
+    impl_.SetGaussNewton(before);
+    throw;
+  }
+  impl_.SetGaussNewton(before);
+  return ok;
+}
+
 bool FullBundleAdjustmentSolverRefactor::SolveByGradientDescent(Options options, Summary *summary) {  // :1075-1367
   return impl_.Run(options, summary, true);
 }

@@ -975,6 +975,82 @@ int ba_point_only_team(int width);
 /* Device time (hipEvents around the launch) of the calling thread's last ba_point_only. */
 int ba_point_only_last_ms(double *kernel_ms);
 
+/* ---- pose-graph optimisation ----------------------------------------------
+ * Levenberg-Marquardt over relative-pose factors ALONE: keyframe poses, odometry and
+ * loop-closure edges, no camera, landmark or observation.  The reference project has no
+ * counterpart; this comment is the definition.
+ *
+ * Inputs: n_pose poses T_jw (12 doubles each, scaled units), their fixed flags (NULL: none
+ * fixed) and n_rel factors exactly as ba_set_relative defines them: r_f = se3_log(T_j T_k^-1
+ * Z_f^-1), first-order Jacobians I and -Ad(T_j T_k^-1), Omega read from its lower triangle,
+ * several factors may name one pair in either orientation, summed in input order.
+ *
+ * System over the N optimisable poses: chi2(T) = sum_f r_f^T Omega_f r_f (no square root, no
+ * sum of norms),
+ *   H_jj += Omega,  H_kk += Ad^T Omega Ad,  H_jk += -Omega Ad,  g_j += -Omega r,  g_k += Ad^T Omega r;
+ * a fixed pose receives nothing.  Step (H + lambda diag(H)) x = g, trial poses
+ * T_j <- se3_exp(x_j) T_j.
+ *
+ * Gain ratio: pred = g^T x + lambda x^T diag(H) x, rho = (chi2_accepted - chi2_trial) / pred.
+ * rho > 0.25 accepts (status 0); otherwise the step is rejected (status 2) and the accepted
+ * chi-square stays the comparison value.  rho > 0.5: lambda = max(1e-10, lambda *
+ * decrease_ratio_lambda), status 1.  rho <= 0.25: lambda = min(1e10, lambda *
+ * increase_ratio_lambda).  gauss_newton = 1: every step accepted, lambda stays at
+ * initial_lambda, rho = pred = 0.
+ *
+ * Stop: the mean over the optimisable poses of |x_j| < threshold_step_size, or |chi2_accepted
+ * - chi2_trial| < threshold_cost_change; never in the last allowed iteration.
+ * threshold_huber_loss and threshold_outlier_rejection are unused: no robust weight.
+ *
+ * Rows: cost = accepted chi-square after the iteration, trial_cost, cost_change (0 on a
+ * rejection), average_reprojection_error = sqrt(cost / factors), abs_step = the mean step,
+ * damping_term = lambda after the update, rho, model_change = pred, iteration_status.
+ *
+ * The object keeps the structure (lists, the level schedule of the tile Cholesky, the dense
+ * image of npad x (npad + nb) doubles) across re-solves, as ba_batch does.  It borrows the
+ * handle's device, stream and BA_DENSE_* knobs: ba_pgraph_destroy first, ba_destroy after.
+ * The handle needs no problem of its own, and a problem it holds is not touched.
+ *
+ * Validation happens before anything touches the GPU, with the rules and messages of
+ * ba_relative_check (-1 and ba_last_error naming the factor); also refused: n_pose <= 0,
+ * n_rel <= 0, a non-finite pose, and an optimisable pose that no factor names (the message
+ * names the pose; its diagonal would be zero).  A graph without a fixed pose is NOT refused:
+ * the damping holds it, and ba_pgraph_info reports the non-positive pivots.  If the image
+ * cannot be allocated the call fails with its size in the message, before any launch.  A
+ * refused call changes nothing.
+ *
+ * One writer per element, fixed summation order, no floating-point atomics: the same bits
+ * run to run. */
+typedef struct ba_pgraph ba_pgraph;
+int ba_pgraph_create(ba_pgraph **out, ba_handle *h, int n_pose, const double *T_jw12,
+                     const uint8_t *pose_fixed, int64_t n_rel, const int32_t *rel_j,
+                     const int32_t *rel_k, const double *Z12, const double *Omega36);
+void ba_pgraph_destroy(ba_pgraph *g);
+/* New VALUES for the same structure; NULL = keep.  Validated as at creation. */
+int ba_pgraph_update_values(ba_pgraph *g, const double *T_jw12, const double *Z12,
+                            const double *Omega36);
+/* The whole loop is enqueued for max_num_iterations without a host round trip; one
+ * synchronisation at the end.  At most cap rows are written (rows may be NULL); rows beyond
+ * *n_iter are untouched.  The solved poses stay in the object.  max_num_iterations <= 0:
+ * nothing changes, *n_iter = 0, *converged = 1. */
+int ba_pgraph_solve(ba_pgraph *g, const ba_options *opt, ba_iter_info *rows, int cap,
+                    int *n_iter, int *converged);
+int ba_pgraph_get_poses(ba_pgraph *g, double *T_jw12);
+/* chi-square at the poses the object holds */
+int ba_pgraph_cost(ba_pgraph *g, double *chi2);
+/* The undamped system at the poses the object holds, for tests: H (6N x 6N, row-major, both
+ * triangles) and g (6N); optimisable poses in the user's order.  Either may be NULL. */
+int ba_pgraph_get_system(ba_pgraph *g, double *H, double *g6N);
+/* out8 = { N, factors, coupled blocks, tile order, tiles, levels, bytes of the dense image,
+ * non-positive pivots of the last solve } */
+int ba_pgraph_info(ba_pgraph *g, int64_t out8[8]);
+/* Device time of the last ba_pgraph_solve, from events around the enqueued loop. */
+int ba_pgraph_last_ms(ba_pgraph *g, double *ms);
+/* Host-only (no GPU): the validation of ba_pgraph_create. */
+int ba_pgraph_check(int n_pose, const double *T_jw12, const uint8_t *pose_fixed, int64_t n_rel,
+                    const int32_t *rel_j, const int32_t *rel_k, const double *Z12,
+                    const double *Omega36);
+
 #ifdef __cplusplus
 }
 #endif
