@@ -302,6 +302,9 @@ SIGNATURES = {
     "ba_pgraph_info": (C.c_int, [_P, _I64]),
     "ba_pgraph_last_ms": (C.c_int, [_P, _D]),
     "ba_pgraph_check": (C.c_int, [C.c_int, _D, _U8, C.c_int64, _I32, _I32, _D, _D]),
+    "ba_pgraph_set_robust": (C.c_int, [_P, _I32, _D]),
+    "ba_pgraph_robust_check": (C.c_int, [C.c_int64, _I32, _D]),
+    "ba_pgraph_factor_report": (C.c_int, [_P, _D, _D]),
 }
 
 _lib = None

@@ -210,6 +210,7 @@ enum KernelId {
   K_CHOL_DIAG, K_CHOL_TRSM, K_CHOL_UPDATE, K_CHOL_BACK, K_CHOL_DIAG_TRSM, K_CHOL_TAIL, K_BACKSUB_UPDATE,
   K_POSE_UPDATE, K_SCALARS, K_CONTROL, K_DAMP_INVERT, K_SCHUR_GRP, K_LIN_GRP,
   K_REL_LIN, K_REL_GATHER, K_REL_OFFDIAG,
+  K_PG_LIN_ROBUST, K_PG_ASSEMBLE_ROBUST,
   K_PG_LIN, K_PG_ASSEMBLE, K_PG_TRIAL, K_PG_CONTROL, K_COUNT
 };
 struct KernelTimer {
@@ -337,9 +338,20 @@ struct PgDev {
   DevIterRec *log;
   int log_cap;
 };
+// Robust kernels of the factors (ba_pgraph_set_robust): a record of their own, an
+// argument of the robust instantiations only, so that PgDev and the plain kernels stay as they are.
+struct PgRobust {
+  const int32_t *kind;    // per factor: 0 none, 1 Huber, 2 Cauchy, 3 Geman-McClure
+  const double *scale;    // per factor: c (a Mahalanobis distance); unread where kind is 0
+  double *s, *w;          // per factor: s = r^T Omega r and w = rho'(s) of the pass that wrote them
+};
 // cost_only = 0: linearise at the accepted poses (records + part[0]; skipped while !ctrl->relin);
 // 1: chi-square partials at the trial poses -> part[1]; 2: at the accepted poses -> part[1]
 void launch_pg_lin(const PgDev &p, int cost_only, hipStream_t s);
+// the same with sum rho(s) for chi-square and w Omega for Omega; rb.s and rb.w are written by
+// cost_only = 0 (they belong to the records) and by cost_only = 3 (= 2 plus the report)
+void launch_pg_lin_robust(const PgDev &p, const PgRobust &rb, int cost_only, hipStream_t s);
+void launch_pg_assemble_robust(const PgDev &p, const PgRobust &rb, double *Hout, double *gout, hipStream_t s);
 // H + lambda diag(H) and g into the image (Hout == nullptr), or the undamped H (6N x 6N,
 // both triangles) and g into Hout / gout
 void launch_pg_assemble(const PgDev &p, double *Hout, double *gout, hipStream_t s);

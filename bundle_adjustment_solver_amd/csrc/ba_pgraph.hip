@@ -16,8 +16,12 @@
 //   k_pg_control   one workgroup: the sums, rho, status, lambda, the buffer swap, the stop test,
 //                  the log row
 // One writer per element, fixed trees, no floating-point atomics: the same bits run to run.
+// Robust kernels (ba_pgraph_set_robust): k_pg_lin_robust and k_pg_assemble_robust
+// are second instantiations of the two bodies with sum rho(s) for chi-square and w Omega for
+// Omega; a graph whose kinds are all 0 launches the plain ones.
 #include <cstddef>
 #include <cstring>
+#include <type_traits>
 
 #include "ba_batch_kernels.h"
 #include "ba_pgraph_host.h"
@@ -29,9 +33,43 @@ constexpr int kPgBlock = 256;
 constexpr int kPgAdS = 37, kPgRS = 7;  // odd strides of the per-factor LDS rows: no bank conflicts
 inline int pg_cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
 
-__global__ __launch_bounds__(kPgBlock) void k_pg_lin(PgDev p, int cost_only) {
+// rho(s) and w = rho'(s) of one factor (include/ba_hip.h); s = 0 gives w = 1 for every kind
+__device__ __forceinline__ double pg_rho(int kind, double c, double s, double *w) {
+  const double c2 = c * c;
+  if (kind == 1) {
+    if (s <= c2) {
+      *w = 1.0;
+      return s;
+    }
+    const double rs = sqrt(s);
+    *w = c / rs;
+    return 2.0 * c * rs - c2;
+  }
+  if (kind == 2) {
+    const double u = s / c2;
+    *w = 1.0 / (1.0 + u);
+    return c2 * log1p(u);
+  }
+  if (kind == 3) {
+    const double t = c2 / (c2 + s);
+    *w = t * t;
+    return t * s;
+  }
+  *w = 1.0;
+  return s;
+}
+
+// The robust record as a kernel argument: an empty struct for the plain instantiation
+struct PgNoRobust {};
+template <bool kRobust>
+using PgRobustArg = typename std::conditional<kRobust, PgRobust, PgNoRobust>::type;
+
+// kRobust = false is the kernel of §6k: every robust line is compiled out
+template <bool kRobust>
+__global__ __launch_bounds__(kPgBlock) void k_pg_lin_t(PgDev p, int cost_only, PgRobustArg<kRobust> rb) {
   __shared__ double sAd[kPgFpb * kPgAdS], sOA[kPgFpb * kPgAdS], sR[kPgFpb * kPgRS], sOr[kPgFpb * kPgRS];
   __shared__ double sm[4];
+  __shared__ double sW[kRobust ? kPgFpb : 1];
   const PgCtrl *c = p.ctrl;
   if (c->done) return;
   if (!cost_only && !c->relin) return;  // a rejected step: the records still belong to the accepted poses
@@ -53,6 +91,16 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_lin(PgDev p, int cost_only) {
 #pragma unroll
       for (int cc = 0; cc < 6; ++cc) row += Om[a * 6 + cc] * rr[cc];
       q += rr[a] * row;
+    }
+    if constexpr (kRobust) {  // the partial is sum rho(s); w rides through LDS to the element threads
+      double w;
+      const double s = q;
+      q = pg_rho(rb.kind[f0 + tid], rb.scale[f0 + tid], s, &w);
+      if (!cost_only) sW[tid] = w;
+      if (cost_only == 0 || cost_only == 3) {
+        rb.s[f0 + tid] = s;
+        rb.w[f0 + tid] = w;
+      }
     }
     if (!cost_only) {  // r and Ad = [[R_E, [t_E]x R_E], [0, R_E]]
       double *Ad = sAd + tid * kPgAdS;
@@ -83,11 +131,13 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_lin(PgDev p, int cost_only) {
       if (k < 36) {
         const int a = k / 6, cc = k - 6 * a;
         for (int m = 0; m < 6; ++m) acc += Om[a * 6 + m] * sAd[f * kPgAdS + m * 6 + cc];
+        if constexpr (kRobust) acc *= sW[f];
         sOA[f * kPgAdS + k] = acc;
         rec[(size_t)f * kPgRec + kPgOA + k] = acc;
       } else {
         const int a = k - 36;
         for (int m = 0; m < 6; ++m) acc += Om[a * 6 + m] * sR[f * kPgRS + m];
+        if constexpr (kRobust) acc *= sW[f];
         sOr[f * kPgRS + a] = acc;
         rec[(size_t)f * kPgRec + kPgOr + a] = acc;
       }
@@ -115,7 +165,9 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_lin(PgDev p, int cost_only) {
   if (tid == 0) p.part[cost_only ? 1 : 0][blockIdx.x] = tot;
 }
 
-__global__ __launch_bounds__(kPgBlock) void k_pg_assemble(PgDev p, double *Hout, double *gout) {
+template <bool kRobust>
+__global__ __launch_bounds__(kPgBlock) void k_pg_assemble_t(PgDev p, double *Hout, double *gout,
+                                                            PgRobustArg<kRobust> rb) {
   const PgCtrl *c = p.ctrl;
   if (c->done) return;
   const int64_t e = (int64_t)blockIdx.x * kPgBlock + threadIdx.x;
@@ -129,7 +181,10 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_assemble(PgDev p, double *Hout,
       const int w = p.plist[l], f = w >> 1;
       const double *rec = p.rec + (size_t)f * kPgRec;
       if (q < 36)
-        acc += (w & 1) ? rec[kPgBk + q] : p.val[(size_t)f * 48 + 12 + q];
+        if constexpr (kRobust)  // H_jj += w Omega: the one term that is not read from the records
+          acc += (w & 1) ? rec[kPgBk + q] : rb.w[f] * p.val[(size_t)f * 48 + 12 + q];
+        else
+          acc += (w & 1) ? rec[kPgBk + q] : p.val[(size_t)f * 48 + 12 + q];
       else
         acc += (w & 1) ? rec[kPgGk + q - 36] : -rec[kPgOr + q - 36];
     }
@@ -176,6 +231,12 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_assemble(PgDev p, double *Hout,
   const int row = p.pose_col[hl.x] + r, col = p.pose_col[hl.y] + cc;
   p.L[row > col ? (size_t)col * p.ld + row : (size_t)row * p.ld + col] = acc;
 }
+
+// the names the kernel table lists: k_pg_lin / k_pg_assemble and their robust instantiations
+constexpr auto k_pg_lin = k_pg_lin_t<false>;
+constexpr auto k_pg_lin_robust = k_pg_lin_t<true>;
+constexpr auto k_pg_assemble = k_pg_assemble_t<false>;
+constexpr auto k_pg_assemble_robust = k_pg_assemble_t<true>;
 
 __global__ __launch_bounds__(kPgBlock) void k_pg_trial(PgDev p) {
   __shared__ double sm[8];
@@ -290,11 +351,18 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_control(PgDev p, int mode) {
 }  // namespace
 
 void launch_pg_lin(const PgDev &p, int cost_only, hipStream_t s) {
-  BA_LAUNCH(K_PG_LIN, k_pg_lin, dim3(p.n_part), dim3(kPgBlock), s, p, cost_only);
+  BA_LAUNCH(K_PG_LIN, k_pg_lin, dim3(p.n_part), dim3(kPgBlock), s, p, cost_only, PgNoRobust{});
 }
 void launch_pg_assemble(const PgDev &p, double *Hout, double *gout, hipStream_t s) {
   const int grid = pg_cdiv((int64_t)42 * p.N + (int64_t)36 * p.nblk, kPgBlock);
-  BA_LAUNCH(K_PG_ASSEMBLE, k_pg_assemble, dim3(grid), dim3(kPgBlock), s, p, Hout, gout);
+  BA_LAUNCH(K_PG_ASSEMBLE, k_pg_assemble, dim3(grid), dim3(kPgBlock), s, p, Hout, gout, PgNoRobust{});
+}
+void launch_pg_lin_robust(const PgDev &p, const PgRobust &rb, int cost_only, hipStream_t s) {
+  BA_LAUNCH(K_PG_LIN_ROBUST, k_pg_lin_robust, dim3(p.n_part), dim3(kPgBlock), s, p, cost_only, rb);
+}
+void launch_pg_assemble_robust(const PgDev &p, const PgRobust &rb, double *Hout, double *gout, hipStream_t s) {
+  const int grid = pg_cdiv((int64_t)42 * p.N + (int64_t)36 * p.nblk, kPgBlock);
+  BA_LAUNCH(K_PG_ASSEMBLE_ROBUST, k_pg_assemble_robust, dim3(grid), dim3(kPgBlock), s, p, Hout, gout, rb);
 }
 void launch_pg_trial(const PgDev &p, hipStream_t s) {
   BA_LAUNCH(K_PG_TRIAL, k_pg_trial, dim3(p.n_tpart), dim3(kPgBlock), s, p);
@@ -322,6 +390,14 @@ struct ba_pgraph {
   ba::PgDev d{};
   ba::PgCtrl hc{};
   double *Ldiag = nullptr, *val = nullptr;
+  // robust kernels: the host copy as given, the device arrays (allocated by the first
+  // ba_pgraph_set_robust or ba_pgraph_factor_report), and whether any kind is not 0
+  std::vector<int32_t> rkind;
+  std::vector<double> rscale;
+  int32_t *d_rkind = nullptr;
+  double *d_rscale = nullptr, *d_rep_s = nullptr, *d_rep_w = nullptr;
+  ba::PgRobust rb{};
+  bool robust = false;
   int *zt_I = nullptr, *zt_J = nullptr, *col_x = nullptr;
   int n_zt = 0, nb = 0, ncb = 0;
   size_t image_bytes = 0;
@@ -475,6 +551,41 @@ int begin_pass(ba_pgraph *g) {
   return push_ctrl(g);
 }
 
+// the device arrays of the robust kernels: kinds 0 and the weights' arrays, once per graph
+int ensure_robust_arrays(ba_pgraph *g) {
+  if (g->d_rkind) return 0;
+  ba_handle *h = g->h;
+  constexpr Mem R = Mem::Resident;
+  const size_t F = (size_t)g->F, mark = h->allocs.size();
+  const int rc = h->dalloc(R, &g->d_rkind, F) || h->dalloc(R, &g->d_rscale, F) || h->dalloc(R, &g->rb.s, F) ||
+                 h->dalloc(R, &g->rb.w, F) || h->dalloc(R, &g->d_rep_s, F) || h->dalloc(R, &g->d_rep_w, F);
+  adopt_allocs(g, mark);
+  if (rc) {
+    g->d_rkind = nullptr;  // what was allocated goes with the graph
+    return -1;
+  }
+  g->rb.kind = g->d_rkind;
+  g->rb.scale = g->d_rscale;
+  HIP_TRY(hipMemset(g->d_rkind, 0, F * sizeof(int32_t)));
+  HIP_TRY(hipMemset(g->d_rscale, 0, F * sizeof(double)));
+  return 0;
+}
+
+// the linearisation / cost pass and the assembly of the graph: the robust instantiations only
+// where a kernel is set
+void pg_lin(const ba_pgraph *g, int cost_only, hipStream_t s) {
+  if (g->robust)
+    ba::launch_pg_lin_robust(g->d, g->rb, cost_only, s);
+  else
+    ba::launch_pg_lin(g->d, cost_only, s);
+}
+void pg_assemble(const ba_pgraph *g, double *Hout, double *gout, hipStream_t s) {
+  if (g->robust)
+    ba::launch_pg_assemble_robust(g->d, g->rb, Hout, gout, s);
+  else
+    ba::launch_pg_assemble(g->d, Hout, gout, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -557,7 +668,63 @@ int ba_pgraph_update_values(ba_pgraph *g, const double *T_jw12, const double *Z1
   return 0;
 }
 
-int ba_pgraph_solve(ba_pgraph *g, const ba_options *opt, ba_iter_info *rows, int cap, int *n_iter, int *converged) {
+int ba_pgraph_robust_check(int64_t n_rel, const int32_t *kind, const double *scale) {
+  std::string err;
+  if (ba::pgraph_robust_validate_host(n_rel, kind, scale, &err)) return fail("ba_pgraph_set_robust: " + err);
+  return 0;
+}
+
+int ba_pgraph_set_robust(ba_pgraph *g, const int32_t *kind, const double *scale) {
+  if (!g) return fail("ba_pgraph_set_robust: null graph");
+  if (ba_pgraph_robust_check(g->F, kind, scale)) return -1;
+  const size_t F = (size_t)g->F;
+  std::vector<int32_t> k(F, 0);
+  std::vector<double> c(F, 0.0);
+  bool any = false;
+  for (size_t f = 0; kind && f < F; ++f)
+    if (kind[f] != 0) {
+      k[f] = kind[f];
+      c[f] = scale[f];
+      any = true;
+    }
+  if (!any && !g->d_rkind) {  // never robust, and stays so: nothing to allocate
+    g->robust = false;
+    return 0;
+  }
+  ba_handle *h = g->h;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (ensure_robust_arrays(g)) return -1;
+  HIP_TRY(hipMemcpy(g->d_rkind, k.data(), F * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(g->d_rscale, c.data(), F * sizeof(double), hipMemcpyHostToDevice));
+  g->rkind.swap(k);
+  g->rscale.swap(c);
+  g->robust = any;
+  return 0;
+}
+
+int ba_pgraph_factor_report(ba_pgraph *g, double *s, double *w) {
+  if (!g) return fail("ba_pgraph_factor_report: null graph");
+  ba_handle *h = g->h;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (ensure_robust_arrays(g)) return -1;
+  if (begin_pass(g)) return -1;
+  // one cost-only pass at the accepted poses; the report has arrays of its own, so that rb.s and
+  // rb.w stay those of the records
+  ba::PgRobust rep = g->rb;
+  rep.s = g->d_rep_s;
+  rep.w = g->d_rep_w;
+  ba::launch_pg_lin_robust(g->d, rep, 3, h->stream);
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  const size_t bytes = (size_t)g->F * sizeof(double);
+  if (s) HIP_TRY(hipMemcpy(s, g->d_rep_s, bytes, hipMemcpyDeviceToHost));
+  if (w) HIP_TRY(hipMemcpy(w, g->d_rep_w, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int ba_pgraph_solve(ba_pgraph *g, const ba_options *opt,ba_iter_info *rows, int cap, int *n_iter, int *converged) {
   if (!g || !opt) return fail("ba_pgraph_solve: bad argument");
   if (cap < 0 || (cap > 0 && !rows)) return fail("ba_pgraph_solve: rows is NULL for cap > 0");
   ba_handle *h = g->h;
@@ -585,12 +752,12 @@ int ba_pgraph_solve(ba_pgraph *g, const ba_options *opt, ba_iter_info *rows, int
   const int *done = done_flag(g);
   HIP_TRY(hipEventRecord(g->e0, s));
   for (int it = 0; it < opt->max_num_iterations; ++it) {
-    ba::launch_pg_lin(d, 0, s);
+    pg_lin(g, 0, s);
     ba::launch_dense_init(d.L, d.ld, g->col_x, g->zt_I, g->zt_J, g->n_zt, g->nb, done, s);
-    ba::launch_pg_assemble(d, nullptr, nullptr, s);
+    pg_assemble(g, nullptr, nullptr, s);
     ba::dense_factor_solve(d.L, d.npad, d.ld, g->Ldiag, d.x, done, g->sched, g->dd, g->dd.plan[g->dd.flow_ok], s);
     ba::launch_pg_trial(d, s);
-    ba::launch_pg_lin(d, 1, s);
+    pg_lin(g, 1, s);
     ba::launch_pg_control(d, 0, s);
   }
   HIP_TRY(hipEventRecord(g->e1, s));
@@ -625,7 +792,7 @@ int ba_pgraph_cost(ba_pgraph *g, double *chi2) {
   if (!g || !chi2) return fail("ba_pgraph_cost: bad argument");
   HIP_TRY(hipSetDevice(g->h->device));
   if (begin_pass(g)) return -1;
-  ba::launch_pg_lin(g->d, 2, g->h->stream);
+  pg_lin(g, 2, g->h->stream);
   ba::launch_pg_control(g->d, 1, g->h->stream);
   if (pull_ctrl(g)) return -1;
   HIP_TRY(hipGetLastError());
@@ -647,8 +814,8 @@ int ba_pgraph_get_system(ba_pgraph *g, double *H, double *g6N) {
   int rc = 0;
   if (hipMemsetAsync(dH, 0, n6 * n6 * sizeof(double), h->stream) != hipSuccess || begin_pass(g)) rc = -1;
   if (!rc) {
-    ba::launch_pg_lin(g->d, 0, h->stream);
-    ba::launch_pg_assemble(g->d, dH, dg, h->stream);
+    pg_lin(g, 0, h->stream);
+    pg_assemble(g, dH, dg, h->stream);
     if (hipStreamSynchronize(h->stream) != hipSuccess || hipGetLastError() != hipSuccess ||
         (H && hipMemcpy(H, dH, n6 * n6 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
         (g6N && hipMemcpy(g6N, dg, n6 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))

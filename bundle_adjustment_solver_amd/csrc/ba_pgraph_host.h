@@ -2,7 +2,7 @@
 // DESIGN.md §6k): validation of the caller's arrays, the per-pose and per-block factor
 // lists and the tile adjacency of the dense image.  Plain C++ with no HIP call, so that it
 // also builds into a stand-alone program under the host sanitizers
-// (tools/pgraph_host_check.cpp).  Internal.
+// (tools/pgraph_host_check.cpp, tools/pgraph_robust_host_check.cpp).  Internal.
 #ifndef BA_PGRAPH_HOST_H_
 #define BA_PGRAPH_HOST_H_
 
@@ -41,7 +41,31 @@ inline int pgraph_validate_host(int n_pose, const double *T_jw12, const uint8_t 
   return 0;
 }
 
-// The structure of a validated graph.  The optimisable poses keep the user's order:
+// Everything ba_pgraph_robust_check refuses: a kind outside 0..3, and on a factor whose kind is
+// not 0 a scale that is not finite or not positive (*err names the factor).  kind == nullptr
+// clears every kernel and is accepted; the scale of a kind-0 factor is never read.
+constexpr int kPgKinds = 4;  // 0 none, 1 Huber, 2 Cauchy, 3 Geman-McClure
+inline int pgraph_robust_validate_host(int64_t n_rel, const int32_t *kind, const double *scale, std::string *err) {
+  auto bad = [&](const std::string &m, int64_t f) {
+    *err = m + " (factor " + std::to_string(f) + ")";
+    return -1;
+  };
+  if (n_rel < 0) {
+    *err = "n_rel must be >= 0";
+    return -1;
+  }
+  if (!kind) return 0;
+  for (int64_t f = 0; f < n_rel; ++f) {
+    if (kind[f] < 0 || kind[f] >= kPgKinds) return bad("kind = " + std::to_string(kind[f]) + " is not one of 0..3", f);
+    if (kind[f] == 0) continue;
+    if (!scale) return bad("null scale array", f);
+    if (!std::isfinite(scale[f])) return bad("scale is not finite", f);
+    if (!(scale[f] > 0.0)) return bad("scale must be > 0", f);
+  }
+  return 0;
+}
+
+// The structure of a validated graph. The optimisable poses keep the user's order:
 // optimisable index = rank among the optimisable poses.
 struct PgraphLists {
   int N = 0;

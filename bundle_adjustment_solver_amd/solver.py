@@ -401,6 +401,7 @@ class BaProblem:
         """Relative-pose factors of the handle (ba_set_relative; scaled units), before
         finalize.  rels: None (clears) or a dict j (F,), k (F,) user pose indices, Z (F, 12)
         the measurement of T_j T_k^-1, Omega (F, 6, 6) of which the lower triangle counts."""
+        refuse_robust("set_relative", rels)
         if rels is None or len(np.asarray(rels["j"]).reshape(-1)) == 0:
             check(self.lib.ba_set_relative(self.h, 0, None, None, None, None), "ba_set_relative")
             self._n_rel = 0
@@ -1419,6 +1420,7 @@ class BaBatch:
         for p, rl in enumerate(rels):
             F = 0
             if rl is not None:
+                refuse_robust("set_relative: problem %d" % p, rl)
                 j = np.asarray(rl["j"], np.int32).reshape(-1)
                 k = np.asarray(rl["k"], np.int32).reshape(-1)
                 F = j.shape[0]
@@ -1507,6 +1509,38 @@ class BaBatch:
         return out
 
 
+ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_GEMAN_MCCLURE = 0, 1, 2, 3
+
+
+def _robust_arrays(kind, scale, n_rel=None):
+    """kind (F,) int32 or None, scale (F,) float64 (None: zeros, for kinds that are all 0)"""
+    if kind is None:
+        return None, None
+    kd = np.ascontiguousarray(kind, np.int32).reshape(-1)
+    sc = np.zeros(len(kd)) if scale is None else np.ascontiguousarray(scale, np.float64).reshape(-1)
+    if len(sc) != len(kd) or (n_rel is not None and len(kd) != n_rel):
+        raise ValueError("robust kernels: one kind and one scale per factor")
+    return kd, sc
+
+
+def pgraph_robust_check(kind, scale):
+    """Host-only validation of BaPoseGraph.set_robust's inputs (ba_pgraph_robust_check); raises BaError."""
+    kd, sc = _robust_arrays(kind, scale)
+    n = 0 if kd is None else len(kd)
+    check(_lib.load().ba_pgraph_robust_check(n, None if kd is None else _ip(kd), None if sc is None else _dp(sc)),
+          "ba_pgraph_robust_check")
+
+
+def refuse_robust(what, rels):
+    """The BA paths (handle, batch) take no robust kernel: a factor dict that carries one is
+    refused, not silently solved with full weight."""
+    kd = None if rels is None else rels.get("robust_kind")
+    if kd is not None and np.any(np.asarray(kd) != 0):
+        f = int(np.flatnonzero(np.asarray(kd).reshape(-1) != 0)[0])
+        raise _lib.BaError("%s: factor %d carries a robust kernel; robust factors are pose-graph only "
+                           "(SolvePoseGraph, BaPoseGraph.set_robust)" % (what, f))
+
+
 def pgraph_check(pose_T, pose_fixed, rels):
     """Host-only validation of BaPoseGraph's inputs (ba_pgraph_check); raises BaError."""
     T = np.ascontiguousarray(pose_T, np.float64).reshape(-1, 12)
@@ -1550,6 +1584,24 @@ class BaPoseGraph:
                                         None if fx is None else _up(fx), self.n_rel, _ip(j), _ip(k),
                                         _dp(Z), _dp(Om)), "ba_pgraph_create")
         self.g = g
+        if rels.get("robust_kind") is not None:   # a factor dict that carries kernels
+            self.set_robust(rels["robust_kind"], rels.get("robust_scale"))
+
+    def set_robust(self, kind, scale=None):
+        """Robust kernels of the factors (ba_pgraph_set_robust): kind (F,) of
+        ROBUST_NONE / HUBER / CAUCHY / GEMAN_MCCLURE, scale (F,) the Mahalanobis distance c > 0
+        of each factor whose kind is not 0.  kind None clears every kernel.  No re-planning:
+        call it between solves as often as needed."""
+        kd, sc = _robust_arrays(kind, scale, self.n_rel)
+        check(self.lib.ba_pgraph_set_robust(self.g, None if kd is None else _ip(kd), None if sc is None else _dp(sc)),
+              "ba_pgraph_set_robust")
+
+    def factor_report(self):
+        """-> (s (F,), w (F,)): s_f = r_f^T Omega_f r_f and the robust weight w_f of every
+        factor at the poses the object holds (ba_pgraph_factor_report)"""
+        s, w = np.zeros(self.n_rel), np.zeros(self.n_rel)
+        check(self.lib.ba_pgraph_factor_report(self.g, _dp(s), _dp(w)), "ba_pgraph_factor_report")
+        return s, w
 
     def close(self):
         if self.g:
@@ -1750,6 +1802,8 @@ class FullBundleAdjustmentSolver:
         self._obs_cam, self._obs_pose, self._obs_pt, self._obs_uv = \
             [], [], [], []
         self._relatives = []      # AddRelativePose: one scaled dict (F = 1) per factor, input order
+        self._relative_units = []  # per factor: sigma_pixel SCALER, the unit of its Mahalanobis distance
+        self._relative_report = None
         self.num_total_poses_ = 0
         self.num_total_points_ = 0
         self.num_fixed_poses_ = 0
@@ -1919,7 +1973,7 @@ class FullBundleAdjustmentSolver:
         self._obs_uv.append(uv * SCALER)
         self.num_total_observations_ += cam.shape[0]
 
-    def AddRelativePose(self, pose_j, pose_k, measurement, information, sigma_pixel=1.0):
+    def AddRelativePose(self, pose_j, pose_k, measurement, information, sigma_pixel=1.0, robust=None):
         """(new) A relative-pose factor between two registered poses (objects or integer
         handles; distinct, not both fixed): an odometry or loop-closure edge of the problem
         that Solve and ComputeCovariance then include (BaProblem.set_relative).  measurement,
@@ -1927,18 +1981,28 @@ class FullBundleAdjustmentSolver:
         (_scaled_relatives): the measured pose_j^-1 * pose_k in AddPose's convention and
         units, the 6x6 information of the tangent [v; omega] in the caller's units.  Call
         before FinalizeParameters; afterwards it warns and is ignored, as AddPose.
-        ReloadParameterValues keeps the factors, Reset drops them."""
+        ReloadParameterValues keeps the factors, Reset drops them.
+        robust (default None: none): (kind, scale), a robust kernel for SolvePoseGraph
+        (ROBUST_HUBER / ROBUST_CAUCHY / ROBUST_GEMAN_MCCLURE).  scale is the
+        Mahalanobis distance c against `information` as given, in the caller's units with
+        `sigma_pixel`.  Robust factors are pose-graph only: Solve, SolveBatch and
+        ComputeCovariance refuse a factor that carries one."""
         if self.is_parameter_finalized_:
             self._finalized_warning()
             return
-        fac = dict(pose_j=pose_j, pose_k=pose_k, measurement=measurement, information=information)
+        fac = dict(pose_j=pose_j, pose_k=pose_k, measurement=measurement, information=information, robust=robust)
         self._relatives.append(self._scaled_relatives("AddRelativePose", [self], [[fac]], sigma_pixel)[0])
+        self._relative_units.append(float(sigma_pixel) * SCALER)
 
     def _relative_arrays(self):
         """the factors of AddRelativePose as the dict BaProblem.set_relative takes, or None"""
         if not self._relatives:
             return None
-        return {key: np.concatenate([r[key] for r in self._relatives], axis=0) for key in ("j", "k", "Z", "Omega")}
+        out = {key: np.concatenate([r[key] for r in self._relatives], axis=0) for key in ("j", "k", "Z", "Omega")}
+        if any("robust_kind" in r for r in self._relatives):
+            for key, dt in (("robust_kind", np.int32), ("robust_scale", np.float64)):
+                out[key] = np.concatenate([r.get(key, np.zeros(len(r["j"]), dt)) for r in self._relatives])
+        return out
 
     def ReloadParameterValues(self):
         """(new) Read the CURRENT values of every registered pose / point object again
@@ -2008,6 +2072,7 @@ class FullBundleAdjustmentSolver:
     def FinalizeParameters(self):   # reference :182-206 (private there)
         if self.is_parameter_finalized_:
             return
+        refuse_robust("FinalizeParameters", self._relative_arrays())   # before anything is allocated
         intr, camT, T_jw, X, pf, qf, ocam, opose, opt, ouv = self._host_arrays()
         p = BaProblem(self.device)
         p.set_cameras(intr, camT)
@@ -2021,7 +2086,7 @@ class FullBundleAdjustmentSolver:
         if self._relatives:
             if self._allreduce is not None:
                 raise _lib.BaError("relative-pose factors (AddRelativePose) run on one GPU; this solver is sharded")
-            p.set_relative(self._relative_arrays())
+            p.set_relative(self._relative_arrays())   # refuses a factor that carries a robust kernel
         p.finalize()
         if self._allreduce is not None:
             if hasattr(self._allreduce, "attach"):   # an exchange object (sharding.py)
@@ -2113,7 +2178,9 @@ class FullBundleAdjustmentSolver:
         class as in its Solve.  Fills `summary` from the rows and writes the poses back into
         the registered pose objects as Solve does; the solver's own copies follow, so that a
         second call continues from the first.  A finalized problem of the same solver takes
-        the new poses with ReloadParameterValues."""
+        the new poses with ReloadParameterValues.  Factors added with robust=(kind, scale) are
+        solved with their kernels; GetRelativeWeights returns every factor's
+        s and weight at the solved poses."""
         t0 = time.perf_counter()
         if summary is not None:
             summary.max_iteration_ = options.iteration_handle.max_num_iterations
@@ -2128,15 +2195,28 @@ class FullBundleAdjustmentSolver:
         pf[list(self._pose_fixed)] = 1
         c_opt = options.to_c()
         c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
-        g = BaPoseGraph(T_jw, pf, rels, self.device)
+        g = BaPoseGraph(T_jw, pf, rels, self.device)   # applies the kernels that the factors carry
         try:
             rows, converged = g.solve(c_opt)
             T_new = g.poses()
+            s, w = g.factor_report()
         finally:
             g.close()
+        unit = np.asarray(self._relative_units)   # s in scaled units = s in the caller's times unit^2
+        self._relative_report = (s / (unit * unit), w)
         self._pose_T_jw = [T_new]
         n_pt = self.num_total_points_
         return self._write_back(T_new, np.zeros((n_pt, 3)), np.zeros(n_pt, bool), rows, converged, summary, t0)
+
+    def GetRelativeWeights(self):
+        """(new) -> (s, w) of the last SolvePoseGraph, one entry per factor in the order of
+        AddRelativePose, at the solved poses: s = r^T information r in the caller's units
+        (the Mahalanobis distance squared that a robust scale is compared with) and the
+        robust weight w (1 for a factor without a kernel).  A closure with a small w is the one to drop."""
+        if getattr(self, "_relative_report", None) is None:
+            raise RuntimeError("GetRelativeWeights: SolvePoseGraph has not run")
+        s, w = self._relative_report
+        return s.copy(), w.copy()
 
     @staticmethod
     def _scaled_priors(what, solvers, priors, sigma_pixel):
@@ -2184,7 +2264,11 @@ class FullBundleAdjustmentSolver:
                           of AddPose (T_jw T_kw^-1 after AddPose's conversion),
           information     (6, 6) of the tangent [v; omega] of the world-to-body poses in the
                           caller's units, the units MarginalizeBatch returns for `sigma_pixel`
-                          (converted as prior_to_scaled_units converts a 6x6 H)."""
+                          (converted as prior_to_scaled_units converts a 6x6 H).
+        A factor with robust=(kind, scale), kind not 0, is taken by AddRelativePose alone
+        (s in scaled units is s in the caller's units times (sigma_pixel SCALER)^2, so the
+        scale goes in times sigma_pixel SCALER); every other caller refuses it: robust factors
+        are pose-graph only."""
         if relatives is None:
             return None
         if len(relatives) != len(solvers):
@@ -2196,7 +2280,15 @@ class FullBundleAdjustmentSolver:
                 continue
             j, k = [], []
             Z, Om = np.zeros((len(fs), 12)), np.zeros((len(fs), 6, 6))
+            kind, scale = np.zeros(len(fs), np.int32), np.zeros(len(fs))
             for f, fac in enumerate(fs):
+                rb = fac.get("robust")
+                if rb is not None and int(rb[0]) != 0:
+                    if what != "AddRelativePose":
+                        raise _lib.BaError("%s: factor %d carries a robust kernel; robust factors are pose-graph "
+                                           "only (AddRelativePose + SolvePoseGraph)" % (what, f))
+                    pgraph_robust_check([int(rb[0])], [float(rb[1])])
+                    kind[f], scale[f] = int(rb[0]), float(rb[1]) * float(sigma_pixel) * SCALER
                 hj, hk = sv._pose_handle(fac["pose_j"]), sv._pose_handle(fac["pose_k"])
                 if hj is None or hk is None:
                     raise RuntimeError("There is no pointer in the BA pose pool.")
@@ -2208,6 +2300,8 @@ class FullBundleAdjustmentSolver:
                 Om[f] = prior_to_scaled_units(np.asarray(fac["information"], np.float64).reshape(6, 6),
                                               np.zeros(6), 0.0, sigma_pixel)[0]
             out.append(dict(j=np.asarray(j, np.int32), k=np.asarray(k, np.int32), Z=Z, Omega=Om))
+            if kind.any():
+                out[-1].update(robust_kind=kind, robust_scale=scale)
         return out
 
     @staticmethod

@@ -84,8 +84,16 @@ class FullBundleAdjustmentSolver {
   // the solved poses become them, written back through the caller's pointers as Solve writes
   // them.  The rows of `summary` are those of ba_pgraph_solve.  A finalized problem of the same
   // solver takes the new poses with ReloadParameterValues.  Throws std::runtime_error without
-  // poses or factors, and on every refusal of ba_pgraph_create.
+  // poses or factors, and on every refusal of ba_pgraph_create.  A factor that carries a robust
+  // kernel (RelativePose::robust_kind) is solved with it (ba_pgraph_set_robust).
   bool SolvePoseGraph(Options options, Summary *summary = nullptr);
+  // (new) The factor report of the last SolvePoseGraph at the solved poses, one entry per
+  // factor in the order of AddRelativePose (ba_pgraph_factor_report): s = r^T information r in
+  // the caller's units, the Mahalanobis distance squared that a robust scale is compared with,
+  // and the robust weight w (1 for a factor without a kernel).  A closure with a small w is
+  // the one to drop.  Either output may be null.  Throws std::runtime_error before the first
+  // SolvePoseGraph.
+  void GetRelativeWeights(std::vector<double> *s, std::vector<double> *w) const;
 
   // (new) Solve the registered problems of several solver objects in ONE GPU launch
   // (ba_batch_solve of include/ba_hip.h: one persistent workgroup per problem runs the
@@ -236,6 +244,14 @@ class FullBundleAdjustmentSolver {
     _BA_Pose *pose_k{nullptr};
     _BA_Pose measurement;
     double information[36] = {0.0};
+    // A robust kernel for SolvePoseGraph (include/ba_hip.h, ba_pgraph_set_robust): 0 none,
+    // 1 Huber, 2 Cauchy, 3 Geman-McClure; robust_scale is the Mahalanobis distance c > 0 against
+    // `information` in the caller's units.  Robust factors are pose-graph only: AddRelativePose
+    // takes one (and throws on a kind outside 0..3 or a scale that is not finite or <= 0);
+    // FinalizeParameters (Solve, ComputeCovariance) and the batch entry points throw
+    // std::runtime_error on a factor that carries one.
+    int robust_kind{0};
+    double robust_scale{0.0};
   };
   // (new) A relative-pose factor of THIS solver's problem: an odometry or loop-closure edge
   // between two registered poses that Solve and ComputeCovariance then include
@@ -312,12 +328,17 @@ class FullBundleAdjustmentSolver {
     bool set{false};
     std::vector<int32_t> off, j, k;
     std::vector<double> Z, Omega;
+    // AddRelativePose only: the robust kernels (scale in scaled units) and, per factor,
+    // sigma_pixel * scaler, the unit of its Mahalanobis distance
+    std::vector<int32_t> kind;
+    std::vector<double> scale, unit;
   };
   static void PackRelatives(const std::vector<FullBundleAdjustmentSolver *> &solvers, const char *who,
                             const std::vector<std::vector<RelativePose>> *in_relatives, double sigma_pixel,
                             RelativeArrays *out);
   static int SetRelatives(ba_batch *batch, const RelativeArrays &r);
   RelativeArrays relatives_;  // AddRelativePose: j, k, Z, Omega of this solver's factors (off unused)
+  std::vector<double> report_s_, report_w_;  // the factor report of the last SolvePoseGraph
   // the options' thresholds and iteration limit into a Summary (nullptr: nothing)
   static void BeginSummary(Summary *summary, const Options &options);
   // stderr warnings about weakly connected poses / points (reference

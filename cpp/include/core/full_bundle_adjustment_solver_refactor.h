@@ -75,6 +75,8 @@ class FullBundleAdjustmentSolverRefactor {
   // FullBundleAdjustmentSolver::SolvePoseGraph; solver_type selects Levenberg-Marquardt or
   // Gauss-Newton as in Solve, for this call only
   bool SolvePoseGraph(Options options, Summary *summary = nullptr);
+  // (new) see FullBundleAdjustmentSolver::GetRelativeWeights
+  void GetRelativeWeights(std::vector<double> *s, std::vector<double> *w) const { impl_.GetRelativeWeights(s, w); }
 
   // (new) covariance blocks of the current state, see FullBundleAdjustmentSolver::ComputeCovariance:
   // same units, same tangent convention (world-to-body T_jw = inverse(*pose), T_jw <- exp(xi) T_jw)

@@ -55,6 +55,8 @@ void FullBundleAdjustmentSolver::Reset() {  // :44-70
   fixed_points_.clear();
   observations_.clear();
   relatives_ = RelativeArrays();
+  report_s_.clear();
+  report_w_.clear();
   num_fixed_poses_ = num_fixed_points_ = 0;
 }
 
@@ -99,6 +101,9 @@ void FullBundleAdjustmentSolver::AddRelativePose(const RelativePose &factor, dou
   relatives_.k.push_back(a.k[0]);
   relatives_.Z.insert(relatives_.Z.end(), a.Z.begin(), a.Z.begin() + 12);
   relatives_.Omega.insert(relatives_.Omega.end(), a.Omega.begin(), a.Omega.begin() + 36);
+  relatives_.kind.push_back(a.kind[0]);
+  relatives_.scale.push_back(a.scale[0]);
+  relatives_.unit.push_back(a.unit[0]);
 }
 
 void FullBundleAdjustmentSolver::AddPoint(_BA_Point *original_point) {  // :103-117
@@ -170,6 +175,10 @@ void FullBundleAdjustmentSolver::AddObservation(const _BA_Index camera_index, _B
 
 void FullBundleAdjustmentSolver::FinalizeParameters() {  // :182-206, :243-308, :668-700
   if (is_parameter_finalized_) return;
+  for (size_t f = 0; f < relatives_.kind.size(); ++f)
+    if (relatives_.kind[f] != 0)
+      throw std::runtime_error("FinalizeParameters: factor " + std::to_string(f) +
+                               " carries a robust kernel; robust factors are pose-graph only (SolvePoseGraph)");
   if (cameras_.empty() || poses_.empty() || points_.empty())
     throw std::runtime_error("FinalizeParameters: cameras, poses and points must be added first");
   Check(ba_create(&handle_, device_id_), "ba_create");
@@ -434,6 +443,10 @@ bool FullBundleAdjustmentSolver::SolvePoseGraph(Options options, Summary *summar
                             relatives_.Z.data(), relatives_.Omega.data());
   const char *what = "ba_pgraph_create";
   if (rc == 0) {
+    rc = ba_pgraph_set_robust(g, relatives_.kind.data(), relatives_.scale.data());
+    what = "ba_pgraph_set_robust";
+  }
+  if (rc == 0) {
     rc = ba_pgraph_solve(g, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged);
     what = "ba_pgraph_solve";
   }
@@ -441,10 +454,18 @@ bool FullBundleAdjustmentSolver::SolvePoseGraph(Options options, Summary *summar
     rc = ba_pgraph_get_poses(g, T.data());
     what = "ba_pgraph_get_poses";
   }
+  std::vector<double> rep_s(relatives_.j.size()), rep_w(relatives_.j.size());
+  if (rc == 0) {
+    rc = ba_pgraph_factor_report(g, rep_s.data(), rep_w.data());
+    what = "ba_pgraph_factor_report";
+  }
   const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
   ba_pgraph_destroy(g);
   if (h != handle_) ba_destroy(h);
   if (rc != 0) throw std::runtime_error(std::string(what) + ": " + err);
+  for (size_t f = 0; f < rep_s.size(); ++f) rep_s[f] /= relatives_.unit[f] * relatives_.unit[f];
+  report_s_.swap(rep_s);
+  report_w_.swap(rep_w);
   const std::vector<uint8_t> no_point(points_.size(), 0);
   WriteBack(T.data(), nullptr, no_point.data());
   if (summary != nullptr) {
@@ -454,6 +475,12 @@ bool FullBundleAdjustmentSolver::SolvePoseGraph(Options options, Summary *summar
     summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
   }
   return true;
+}
+
+void FullBundleAdjustmentSolver::GetRelativeWeights(std::vector<double> *s, std::vector<double> *w) const {
+  if (report_w_.empty()) throw std::runtime_error("GetRelativeWeights: SolvePoseGraph has not run");
+  if (s != nullptr) *s = report_s_;
+  if (w != nullptr) *w = report_w_;
 }
 
 bool FullBundleAdjustmentSolver::ComputeCovariance(const std::vector<_BA_Pose *> &poses,
@@ -629,6 +656,23 @@ void FullBundleAdjustmentSolver::PackRelatives(const std::vector<FullBundleAdjus
     const double w = 1.0 / (sigma_pixel * sigma_pixel * static_cast<double>(s->scaler_) * static_cast<double>(s->scaler_));
     const auto d = [s](int r) { return r < 3 ? static_cast<double>(s->inverse_scaler_) : 1.0; };
     for (const RelativePose &f : (*in_relatives)[b]) {
+      // s in scaled units = s in the caller's units times unit^2: the scale goes in times unit
+      const double unit = sigma_pixel * static_cast<double>(s->scaler_);
+      int32_t kind = 0;
+      double scale = 0.0;
+      if (f.robust_kind != 0) {
+        if (name != "AddRelativePose")
+          throw std::runtime_error(name + ": factor " + std::to_string(out->j.size() - out->off.back()) +
+                                   " carries a robust kernel; robust factors are pose-graph only (AddRelativePose + "
+                                   "SolvePoseGraph)");
+        kind = f.robust_kind;
+        if (ba_pgraph_robust_check(1, &kind, &f.robust_scale) != 0)
+          throw std::runtime_error(name + ": " + ba_last_error());
+        scale = f.robust_scale * unit;
+      }
+      out->kind.push_back(kind);
+      out->scale.push_back(scale);
+      out->unit.push_back(unit);
       const auto ij = s->pose_index_.find(f.pose_j), ik = s->pose_index_.find(f.pose_k);
       if (ij == s->pose_index_.end() || ik == s->pose_index_.end())
         throw std::runtime_error(name + ": there is no pointer in the BA pose pool.");

@@ -1000,7 +1000,8 @@ int ba_point_only_last_ms(double *kernel_ms);
  *
  * Stop: the mean over the optimisable poses of |x_j| < threshold_step_size, or |chi2_accepted
  * - chi2_trial| < threshold_cost_change; never in the last allowed iteration.
- * threshold_huber_loss and threshold_outlier_rejection are unused: no robust weight.
+ * threshold_huber_loss and threshold_outlier_rejection are unused: robust weights are per
+ * factor (ba_pgraph_set_robust below), none by default.
  *
  * Rows: cost = accepted chi-square after the iteration, trial_cost, cost_change (0 on a
  * rejection), average_reprojection_error = sqrt(cost / factors), abs_step = the mean step,
@@ -1039,7 +1040,8 @@ int ba_pgraph_get_poses(ba_pgraph *g, double *T_jw12);
 /* chi-square at the poses the object holds */
 int ba_pgraph_cost(ba_pgraph *g, double *chi2);
 /* The undamped system at the poses the object holds, for tests: H (6N x 6N, row-major, both
- * triangles) and g (6N); optimisable poses in the user's order.  Either may be NULL. */
+ * triangles) and g (6N); optimisable poses in the user's order.  Either may be NULL.  With
+ * robust kernels set: the weighted system. */
 int ba_pgraph_get_system(ba_pgraph *g, double *H, double *g6N);
 /* out8 = { N, factors, coupled blocks, tile order, tiles, levels, bytes of the dense image,
  * non-positive pivots of the last solve } */
@@ -1050,6 +1052,46 @@ int ba_pgraph_last_ms(ba_pgraph *g, double *ms);
 int ba_pgraph_check(int n_pose, const double *T_jw12, const uint8_t *pose_fixed, int64_t n_rel,
                     const int32_t *rel_j, const int32_t *rel_k, const double *Z12,
                     const double *Omega36);
+
+/* ---- robust kernels on the factors of a pose graph ------------------------
+ * Every factor has a kernel kind and a scale c > 0, a Mahalanobis distance.  With
+ * s_f = r_f^T Omega_f r_f:
+ *
+ *   kind              rho(s)                                  w(s) = rho'(s)
+ *   0 none            s                                       1
+ *   1 Huber           s if s <= c^2, else 2 c sqrt(s) - c^2   1 if s <= c^2, else c / sqrt(s)
+ *   2 Cauchy          c^2 log1p(s / c^2)                      1 / (1 + s / c^2)
+ *   3 Geman-McClure   c^2 s / (c^2 + s)                       (c^2 / (c^2 + s))^2
+ *
+ * Geman-McClure is the closed form of switchable constraints with Phi = c^2.  s = 0 gives
+ * w = 1 for every kind; nothing divides by s except Huber beyond its knee, where s > c^2 > 0.
+ *
+ * Cost: the solver's chi-square is sum_f rho_f(s_f): the accepted cost, the trial cost,
+ * ba_pgraph_cost and every row field derived from them (cost, trial_cost, cost_change,
+ * average_reprojection_error, rho).
+ * System: H and g exactly as above with w_f Omega_f in place of Omega_f, w_f taken at the
+ * poses of the linearisation, which are the accepted poses; after a rejected step the records
+ * and the weights stay.  The weighted Gauss-Newton model has exactly the gradient of
+ * sum rho(s), so pred = g^T x + lambda x^T diag(H) x stays the matching model.  There is NO
+ * second-order (Triggs) correction: the term 2 rho''(s) (J^T Omega r)(J^T Omega r)^T is left out.
+ * Control, stop test, Gauss-Newton mode and the log rows are unchanged.
+ *
+ * kind == NULL clears every kernel; the scale of a kind-0 factor is ignored (scale may be NULL
+ * if every kind is 0).  May be called between solves any number of times without re-planning:
+ * shrinking c from solve to solve is the caller's graduated non-convexity.
+ * ba_pgraph_update_values keeps the kernels.  A graph with no kernel set, or with all kinds 0,
+ * launches exactly the kernels of the section above (k_pg_lin, k_pg_assemble); otherwise their
+ * robust instantiations (k_pg_lin_robust, k_pg_assemble_robust) run in their place.
+ * Refused (-1, ba_last_error names the factor; nothing changes): a kind outside 0..3, and on a
+ * factor whose kind is not 0 a scale that is not finite or <= 0. */
+int ba_pgraph_set_robust(ba_pgraph *g, const int32_t *kind /* F or NULL */,
+                         const double *scale /* F */);
+/* Host-only (no GPU): the validation of ba_pgraph_set_robust. */
+int ba_pgraph_robust_check(int64_t n_rel, const int32_t *kind, const double *scale);
+/* s_f and w_f of every factor (F doubles each, input order) at the poses the object holds,
+ * from one pass like ba_pgraph_cost; a factor without a kernel reports w = 1.  Either output
+ * may be NULL.  This is how a caller finds the closures to drop. */
+int ba_pgraph_factor_report(ba_pgraph *g, double *s, double *w);
 
 #ifdef __cplusplus
 }
