@@ -193,6 +193,7 @@ SIGNATURES = {
     "ba_get_C": (C.c_int, [_P, _D, _D]),
     "ba_get_Cinv": (C.c_int, [_P, _D, _D]),
     "ba_get_pairs": (C.c_int, [_P, _I32, _I32, _D]),
+    "ba_expand_pair_slim": (None, [_D, _D, _D, _D]),
     "ba_get_S": (C.c_int, [_P, _D, _D]),
     "ba_get_xy": (C.c_int, [_P, _D, _D]),
     "ba_kernel_count": (C.c_int, []),
@@ -201,6 +202,7 @@ SIGNATURES = {
     "ba_get_dense_info": (C.c_int, [_P, _D]),
     "ba_get_schur_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "ba_get_lin_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "ba_get_pair_record_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "ba_get_mask_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "ba_get_dropped_pivots": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
     "ba_dense_spd_solve": (C.c_int, [_P, C.c_int, _D, _D, _D, _D]),

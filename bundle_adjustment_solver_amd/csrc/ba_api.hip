@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "ba_device_fn.h"
 #include "ba_handle.h"
 #include "ba_rel_host.h"
 
@@ -399,6 +400,11 @@ int upload_descriptors_and_groups(ba_handle *h) {
   d.n_bs_grp = d.n_lin_desc;
   d.n_lm_part = d.n_bs_grp + (d.n_bchunk - d.lin_chunk0 + ba::kBsChunks - 1) / ba::kBsChunks;
   d.n_lin_cost = d.n_bchunk + d.n_lin_desc;
+  // the grouped pairs — the first lm_pair_ptr[M_grp] — keep the slim record {G, w} when all
+  // three group kernels handle them: k_lin_grp writes, k_schur_grp and the group role of
+  // k_backsub_update read (ba_device.h kWSlim)
+  d.pair_slim = h->knobs.layout.pair_slim && pl.lin_groups && d.n_lin_desc > 0 ? 1 : 0;
+  d.P_slim = d.pair_slim ? pl.lm_pair_ptr[pl.M_grp] : 0;
   if (h->upload(Mem::ChunkConst, &d.sup_desc, pl.sup_desc.data(), pl.sup_desc.size()) ||
       h->upload(Mem::ChunkConst, &d.chunk_desc, pl.chunk_desc.data(), pl.chunk_desc.size()) ||
       h->dalloc(Mem::ChunkState, &d.spart2, (size_t)d.n_slot * ba::kSlotStride) ||
@@ -1499,6 +1505,10 @@ int ba_get_Cinv(ba_handle *h, double *Cinv9, double *Cinvb3) {
   return 0;
 }
 
+void ba_expand_pair_slim(const double *rec8, const double *T12, const double *X3, double *k12) {
+  ba::pair_from_G(rec8, rec8[6], T12, X3[0], X3[1], X3[2], k12, k12 + 9);
+}
+
 int ba_get_pairs(ba_handle *h, int32_t *pair_i, int32_t *pair_j, double *W18) {
   if (!h || !h->finalized) return fail("ba_get_pairs: not finalized");
   if (use_device(h)) return -1;
@@ -1519,10 +1529,25 @@ int ba_get_pairs(ba_handle *h, int32_t *pair_i, int32_t *pair_j, double *W18) {
     std::vector<double> w12((size_t)pl.P * ba::kWStride);
     if (pl.P > 0)
       HIP_TRY(hipMemcpy(w12.data(), h->d.W[h->hc.lcur], w12.size() * sizeof(double), hipMemcpyDeviceToHost));
+    // the slim pairs ({G, w}, ba_device.h kWSlim) first become {K, X_ij}, from the poses and
+    // points the blocks were linearised at: the accepted ones (cur flips together with lcur)
+    const int64_t P_slim = h->d.P_slim;
+    std::vector<double> Th, Xh;
+    if (P_slim > 0) {
+      Th.resize((size_t)pl.n_pose * 12);
+      Xh.resize((size_t)pl.M * 3);
+      HIP_TRY(hipMemcpy(Th.data(), h->d.poses[h->hc.cur], Th.size() * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(Xh.data(), h->d.pts[h->hc.cur], Xh.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
     int64_t o = 0;
     for (int64_t p = 0; p < pl.P; ++p) {
       if (padded(p)) continue;
+      double k12[12];
       const double *k = &w12[(size_t)p * ba::kWStride];
+      if (p < P_slim) {
+        ba_expand_pair_slim(&w12[(size_t)p * ba::kWSlim], &Th[(size_t)pl.pair_pose[p] * 12], &Xh[(size_t)pl.pair_lm[p] * 3], k12);
+        k = k12;
+      }
       double *W = W18 + (size_t)o * 18;
       for (int e = 0; e < 9; ++e) W[e] = k[e];
       for (int c = 0; c < 3; ++c) {
@@ -1647,6 +1672,13 @@ int ba_get_lin_info(ba_handle *h, int64_t out4[4]) {
   out4[1] = obs;
   out4[2] = (int64_t)pl.bchunk_lm.size() - 1 - (pl.lin_groups ? pl.n_bchunk_grp : 0);
   out4[3] = pl.n_pobs;
+  return 0;
+}
+
+int ba_get_pair_record_info(ba_handle *h, int64_t out2[2]) {
+  if (!h || !h->finalized || !out2) return fail("ba_get_pair_record_info: bad argument");
+  out2[0] = h->d.P_slim;
+  out2[1] = h->plan.P;
   return 0;
 }
 
@@ -1910,7 +1942,7 @@ int ba_covariance(ba_handle *h, double huber, int n_pose_sel, const int32_t *pos
   h->cov_batches = 0;
   for (size_t g0 = 0; g0 < groups.size(); g0 += gpb) {  // fixed batch order
     const int ng = (int)std::min<size_t>(gpb, groups.size() - g0);
-    ba::launch_cov_batch(d, keep.lcur, ncb, d_trow_ptr, d_trow, d_groups + g0, ng, Zw, bw, d_pose, d_pt, h->stream);
+    ba::launch_cov_batch(d, keep.lcur, keep.cur, ncb, d_trow_ptr, d_trow, d_groups + g0, ng, Zw, bw, d_pose, d_pt, h->stream);
     ++h->cov_batches;
   }
   std::vector<double> hp, hq;

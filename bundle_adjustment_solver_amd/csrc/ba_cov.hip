@@ -22,6 +22,7 @@
 // No atomics; every sum is an MFMA chain in tile order: the same bits run to run and
 // whatever else is selected in the same call.
 #include "ba_device.h"
+#include "ba_device_fn.h"
 
 namespace ba {
 
@@ -30,13 +31,17 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 // Right-hand sides of the batch into the (zeroed) workspace: identity columns of the
 // group's poses, or W_ji Cinv_i (6x3, W expanded from the compact {K, X_ij} record as
-// ba_get_pairs does) in the rows of pose j for every pair of the group's landmarks.
+// ba_get_pairs does) in the rows of pose j for every pair of the group's landmarks.  The
+// pairs below P_slim hold {G, w} (ba_device.h kWSlim): {K, X_ij} by pair_from_G, from the
+// poses and points of the linearisation.
 __global__ __launch_bounds__(64) void k_cov_rhs(const CovGroup *__restrict__ groups, double *Zw, int bw,
                                                 const int *__restrict__ pose_col,
                                                 const int64_t *__restrict__ lm_pair_ptr,
                                                 const int32_t *__restrict__ pair_pose,
                                                 const double *__restrict__ W,
-                                                const double *__restrict__ Cinv) {
+                                                const double *__restrict__ Cinv, const int64_t P_slim,
+                                                const double *__restrict__ poses,
+                                                const double *__restrict__ pts) {
   const CovGroup g = groups[blockIdx.x];
   const int lane = threadIdx.x;
   const int cb = kCovGroupCols * blockIdx.x;
@@ -51,6 +56,14 @@ __global__ __launch_bounds__(64) void k_cov_rhs(const CovGroup *__restrict__ gro
     const double c00 = ci[0], c01 = ci[1], c02 = ci[2], c11 = ci[3], c12 = ci[4], c22 = ci[5];
     for (int64_t p = lm_pair_ptr[i] + lane; p < lm_pair_ptr[i + 1]; p += 64) {
       const double *k = W + (size_t)p * kWStride;
+      double k12[12];
+      if (p < P_slim) {
+        const double *rec = W + (size_t)p * kWSlim;
+        const double G[6] = {rec[0], rec[1], rec[2], rec[3], rec[4], rec[5]};
+        const double *X = pts + (size_t)i * 3;
+        pair_from_G(G, rec[6], poses + (size_t)pair_pose[p] * 12, X[0], X[1], X[2], k12, k12 + 9);
+        k = k12;
+      }
       double w[6][3];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
@@ -156,13 +169,13 @@ __global__ __launch_bounds__(64) void k_cov_solve(const double *__restrict__ L, 
 
 }  // namespace
 
-void launch_cov_batch(const DevProblem &d, int lcur, int ncb, const int *trow_ptr, const int *trow,
+void launch_cov_batch(const DevProblem &d, int lcur, int cur, int ncb, const int *trow_ptr, const int *trow,
                       const CovGroup *groups, int ng, double *Zw, int bw, double *out_pose,
                       double *out_pt, hipStream_t s) {
   if (ng <= 0) return;
   (void)hipMemsetAsync(Zw, 0, (size_t)d.npad * bw * sizeof(double), s);
   hipLaunchKernelGGL(k_cov_rhs, dim3(ng), dim3(64), 0, s, groups, Zw, bw, d.pose_col, d.lm_pair_ptr,
-                     d.pair_pose, d.W[lcur], d.Cinv);
+                     d.pair_pose, d.W[lcur], d.Cinv, d.P_slim, d.poses[cur], d.pts[cur]);
   if (d.nb == 32)
     hipLaunchKernelGGL(k_cov_solve<32>, dim3(ng), dim3(64), 0, s, d.L, d.ld, d.Ldiag, ncb, trow_ptr, trow,
                        groups, Zw, bw, d.Cinv, out_pose, out_pt);

@@ -54,6 +54,13 @@ struct DevIterRec {  // layout-identical to ba_iter_info
 // X_ij} per pair (96 B instead of 144); consumers rebuild rows 3..5 as
 // X_ij x (column of K), or use B^T x = K^T (x_t + x_r x X_ij) directly.
 constexpr int kWStride = 12;
+// Pairs of covisibility groups that k_lin_grp linearises (DevProblem::pair_slim) keep less:
+// {G (2x3 row-major), w, 0} of the pair's last writer, 8 doubles.  K = G^T (w G R_jw) and
+// X_ij = R_jw X_i + t_jw are rebuilt by the readers (pair_from_G, ba_device_fn.h), for which
+// the pose is a lane constant and the point a per-landmark load.  The grouped pairs are the
+// first P_slim pairs; slim record p lies at double p * kWSlim of the same array W[], i.e.
+// inside the grouped pairs' own 96-byte range, and pair p >= P_slim stays at p * kWStride.
+constexpr int kWSlim = 8;
 
 struct DevProblem {
   // sizes
@@ -124,6 +131,8 @@ struct DevProblem {
   int n_lin_cost;            // entries of lin_cost_part: n_bchunk + k_lin_grp pieces
   int n_bs_grp;              // group-role workgroups of k_backsub_update (= n_lin_desc, or 0)
   int n_lm_part;             // entries of lm_part: n_bs_grp + chunk workgroups behind lin_chunk0
+  int pair_slim;             // 1: the pairs [0, P_slim) are kept as kWSlim records (see kWSlim)
+  int64_t P_slim;            // pairs of the grouped landmarks when pair_slim, else 0
   SupDesc *sup_desc;
   uint32_t *sup_lane;  // n_sup*256: lane -> (slot, half, position, lanes per half) of k_schur_lds
   ChunkDesc *chunk_desc;
@@ -145,7 +154,7 @@ struct DevProblem {
   // scaling of the diagonals (reference :833-852) is applied where they are read.
   double *Cu[2];   // M*6   C_i upper (00 01 02 11 12 22), undamped
   double *b[2];    // M*3
-  double *W[2];    // P*kWStride  compact B_ji (see kWStride)
+  double *W[2];    // P*kWStride  compact B_ji (see kWStride); its first P_slim pairs as kWSlim records when pair_slim
   double *A[2];    // N*36  full (mirrored), undamped
   double *a[2];    // N*6
   double *Cinv;    // M*6   inverse of the damped C_i (k_damp_invert, after the control step)
@@ -451,10 +460,10 @@ struct CovGroup {
 };
 static_assert(sizeof(CovGroup) == 64, "CovGroup is one 64-byte record");
 // One column batch on the factored image of d (d.L, d.Ldiag, lambda = 0 blocks in buffer
-// lcur, d.Cinv): zero the workspace Zw (d.npad x bw doubles, row-major, bw = 16 ng), place
+// lcur, linearised at the poses and points of buffer cur, d.Cinv): zero the workspace Zw (d.npad x bw doubles, row-major, bw = 16 ng), place
 // the right-hand sides, sweep, write the blocks.  trow_ptr / trow: per tile position t the
 // positions s < t with a structurally non-zero factor tile L(t, s), ascending.  Enqueue only.
-void launch_cov_batch(const DevProblem &d, int lcur, int ncb, const int *trow_ptr, const int *trow,
+void launch_cov_batch(const DevProblem &d, int lcur, int cur, int ncb, const int *trow_ptr, const int *trow,
                       const CovGroup *groups, int ng, double *Zw, int bw, double *out_pose,
                       double *out_pt, hipStream_t s);
 

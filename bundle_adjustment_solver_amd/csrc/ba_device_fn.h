@@ -166,6 +166,34 @@ __device__ __forceinline__ void expand_W(const double *__restrict__ k12, double 
   }
 }
 
+// The compact record {K (9), X_ij (3)} of a pair from its slim one (ba_device.h kWSlim):
+// G (2x3) and w of the pair's last writer, the pose T = {R_jw row-major, t_jw} and the
+// point X_i.  K = G^T (w (G R_jw)), X_ij = R_jw X_i + t_jw — with the operations and the
+// roundings of the writer's own expressions (project, make_R and the K of k_lin_grp as the
+// compiler contracts them: a sum of products fuses its first product onto the rounded
+// second, a further product is fused onto the sum, "+ t" is an addition of its own), spelled
+// out with fma() so that no reader depends on a contraction setting: kernels and the host's
+// block getter get the bits the 96-byte record holds.  A zero record (w = 0, G = 0: masked
+// pair without an observation) gives K = 0 exactly.
+__host__ __device__ __forceinline__ void pair_from_G(const double G[6], const double w, const double *__restrict__ T,
+                                                     const double X0, const double X1, const double X2, double K[9],
+                                                     double Xij[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    Xij[r] = fma(T[r * 3 + 2], X2, fma(T[r * 3 + 0], X0, T[r * 3 + 1] * X1)) + T[9 + r];
+  double wR[6];
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      wR[m * 3 + c] = w * fma(G[m * 3 + 2], T[6 + c], fma(G[m * 3 + 0], T[c], G[m * 3 + 1] * T[3 + c]));
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) K[r * 3 + c] = fma(G[r], wR[c], G[3 + r] * wR[3 + c]);
+}
+
 // Symmetric 3x3 inverse by diagonally pivoted LDL^T with D pseudo-inverted —
 // the behaviour of Eigen's C.ldlt().solve(I) (reference :854): an all-zero
 // C_i (never-observed landmark) yields Cinv = 0, not NaN.

@@ -430,9 +430,12 @@ __device__ long long g_lg_dbg[64];
 // pose in this landmark, found from a ballot of the step's valid lanes; when a pose has
 // no valid slot at all its static last slot stores the (zero-K) record, so that the W
 // image never keeps a previous step's entry.
+// SLIM: the pair record is {G, w, 0} (ba_device.h kWSlim) instead of {K, X_ij}: four 16-byte
+// pieces per pair instead of six, and K is not formed here at all.
 // per wave: step transposition [64][9] + W image of the step; at the end [14][64]
-constexpr int kLgArea = 64 * 9 + 7 * 10 * 12;
-template <bool LDSCAM, bool MASKED>
+template <bool SLIM>
+constexpr int kLgArea = 64 * 9 + 7 * 10 * (SLIM ? kWSlim : kWStride);
+template <bool LDSCAM, bool MASKED, bool SLIM>
 __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel, const int bid, double *red,
                                              double *cams_s, double *smc, int *slot_b, int *slot_e) {
 #ifdef BA_LG_DBG
@@ -494,7 +497,7 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
   double *__restrict__ Wg = d.W[lb];
   double *__restrict__ Cg = d.Cu[lb];
   double *__restrict__ bg = d.b[lb];
-  double *cbw = red + wv * kLgArea;
+  double *cbw = red + wv * kLgArea<SLIM>;
   double acc[27];
 #pragma unroll
   for (int k = 0; k < 27; ++k) acc[k] = 0.0;
@@ -526,10 +529,11 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
   double2 *dumpW = (double2 *)(d.lin_dump + (size_t)((bid & 63) * 4 + wv) * 4);
   double *dumpC = (double *)dumpW + 2;
   // LDS image of the W records of a wave step (behind the transposition area):
-  // nlw * d <= 7 * 10 records of 6 double2
+  // nlw * d <= 7 * 10 records of RW double2
+  constexpr int RW = (SLIM ? kWSlim : kWStride) / 2;
   double2 *stgW = (double2 *)(cbw + 64 * 9);
-  double2 *stgW_mine = stgW + (ilw * dd + jj) * 6;
-  constexpr int kLgPass = (7 * 10 * 6 + 63) / 64;
+  double2 *stgW_mine = stgW + (ilw * dd + jj) * RW;
+  constexpr int kLgPass = (7 * 10 * RW + 63) / 64;
   // A step is software-pipelined against the previous one: the step's terms go to
   // the wave's LDS area at its END; the per-landmark sums and the W image of step
   // st - 1 are READ from LDS at the start of step st (requests in flight during the
@@ -545,8 +549,8 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
   {                                                                                 \
     _Pragma("unroll") for (int u_ = 0; u_ < 8; ++u_) vv[u_] = sum_p[(u_ < no ? u_ : 0) * 9]; \
     const int nls_ = nl - il0p < nlw ? nl - il0p : nlw;                             \
-    const int n2_ = nls_ * dd * 6;                                                  \
-    dstWp = n2_ > 0 ? (double2 *)(Wg + (size_t)(p0 + (int64_t)il0p * dd) * kWStride) : dumpW; \
+    const int n2_ = nls_ * dd * RW;                                                 \
+    dstWp = n2_ > 0 ? (double2 *)(Wg + (size_t)(p0 + (int64_t)il0p * dd) * (2 * RW)) : dumpW; \
     lastp = n2_ > 0 ? n2_ - 1 : 0;                                                  \
     _Pragma("unroll") for (int k_ = 0; k_ < kLgPass; ++k_) wvv[k_] = stgW[min(lane + 64 * k_, lastp)]; \
   }
@@ -612,11 +616,18 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
       cbv[7] = wR[1] * g.r0 + wR[4] * g.r1;                                         \
       cbv[8] = wR[2] * g.r0 + wR[5] * g.r1;                                         \
       /* B_ji = w Q^T R of the pair's last-inserted observation (reference :826), */ \
-      /* compact: K = w G^T R and X_ij (ba_device.h kWStride)                     */ \
-      _Pragma("unroll") for (int r = 0; r < 3; ++r)                                 \
-      _Pragma("unroll") for (int c = 0; c < 3; ++c)                                 \
-        kk[r * 3 + c] = G[r] * wR[c] + G[3 + r] * wR[3 + c];                        \
-      _Pragma("unroll") for (int r = 0; r < 3; ++r) kk[9 + r] = g.Xij[r];           \
+      /* compact: K = w G^T R and X_ij (ba_device.h kWStride); SLIM: G and w, the */ \
+      /* zero record for a slot without an observation (ba_device.h kWSlim)       */ \
+      if (SLIM) {                                                                   \
+        _Pragma("unroll") for (int e_ = 0; e_ < 6; ++e_) kk[e_] = (!MASKED || valid_) ? G[e_] : 0.0; \
+        kk[6] = w;                                                                  \
+        kk[7] = 0.0;                                                                \
+      } else {                                                                      \
+        _Pragma("unroll") for (int r = 0; r < 3; ++r)                               \
+        _Pragma("unroll") for (int c = 0; c < 3; ++c)                               \
+          kk[r * 3 + c] = G[r] * wR[c] + G[3 + r] * wR[3 + c];                      \
+        _Pragma("unroll") for (int r = 0; r < 3; ++r) kk[9 + r] = g.Xij[r];         \
+      }                                                                             \
     }                                                                               \
     {                                                                               \
       /* pose side (reference :519-556, :809); fixed poses accumulate zeros */       \
@@ -643,7 +654,7 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
       double *cb = cbw + lane * 9;                                                  \
       _Pragma("unroll") for (int e_ = 0; e_ < 9; ++e_) cb[e_] = cbv[e_];            \
       if (wr_ && lane_on) {                                                         \
-        _Pragma("unroll") for (int r = 0; r < 6; ++r)                               \
+        _Pragma("unroll") for (int r = 0; r < RW; ++r)                              \
           stgW_mine[r] = make_double2(kk[2 * r], kk[2 * r + 1]);                    \
       }                                                                             \
     }                                                                               \
@@ -688,7 +699,7 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
       double sacc = 0.0;
       for (int w4 = 0; w4 < 4; ++w4)
         for (int li = 0; li < nlw; ++li)
-          for (int q = sb; q < se; ++q) sacc += red[w4 * kLgArea + k * 64 + li * no + q];
+          for (int q = sb; q < se; ++q) sacc += red[w4 * kLgArea<SLIM> + k * 64 + li * no + q];
       d.Apart2[(size_t)(apart0 + pj) * 27 + e] = sacc;
     }
   }
@@ -698,13 +709,13 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
 #endif
 }
 
-template <bool LDSCAM, bool MASKED>
+template <bool LDSCAM, bool MASKED, bool SLIM>
 __global__ __launch_bounds__(kBlock, 2) void k_lin_grp(DevProblem d, int sel, int piece0) {
-  __shared__ __attribute__((aligned(16))) double red[4 * kLgArea];
+  __shared__ __attribute__((aligned(16))) double red[4 * kLgArea<SLIM>];
   __shared__ double cams_s[kCamLds * 16];
   __shared__ double smc[4];
   __shared__ int slot_b[kGrpMaxPoses], slot_e[kGrpMaxPoses];  // pattern slots of pose jj of the group
-  lin_grp_body<LDSCAM, MASKED>(d, sel, piece0 + blockIdx.x, red, cams_s, smc, slot_b, slot_e);
+  lin_grp_body<LDSCAM, MASKED, SLIM>(d, sel, piece0 + blockIdx.x, red, cams_s, smc, slot_b, slot_e);
 }
 
 // Damping and landmark inverse (reference :846-856): Cinv_i = (C_i with its
@@ -1211,7 +1222,10 @@ __device__ long long g_grp_dbg[256];
 #else
 #define GRP_STAMP()
 #endif
-template <int NT>
+// SLIM: the pair records are {G, w, 0} (ba_device.h kWSlim): the ring holds four 16-byte
+// pieces and the landmark's point, the lane's pose is loaded once per workgroup, and the
+// lane rebuilds {K, X_ij} (pair_from_G) before it proceeds as with the 96-byte record.
+template <int NT, bool SLIM>
 __global__ __launch_bounds__(kBlock, (NT == 2 && BA_GRP_KRW <= 24) ? 3 : 2) void k_schur_grp(DevProblem d, const DevProblem::GrpDesc *grps) {
   constexpr int TW = 16 * NT;             // padded width: 6 d (+ 1 for b) <= TW
 #ifndef BA_GRP_KRW
@@ -1256,25 +1270,41 @@ __global__ __launch_bounds__(kBlock, (NT == 2 && BA_GRP_KRW <= 24) ? 3 : 2) void
     wb[e] = 0.0;
   }
   // operands of a chunk, requested two chunks ahead (register ring; the loop is
-  // unrolled by two so that the ring index is static)
+  // unrolled by two so that the ring index is static).  SLIM with NT = 4: ONE chunk ahead,
+  // one buffer — 80 registers of accumulators and a two-deep ring leave no room for the
+  // pose (24), and the second buffer bought no lead: a stage starts by waiting for every
+  // request in flight, so its operands had one matrix phase to arrive either way.
+  constexpr int RD = (SLIM && NT == 4) ? 1 : 2;  // ring depth
+  constexpr int RW = (SLIM ? kWSlim : kWStride) / 2;  // 16-byte pieces of a pair record
   double2 rw[2][6], rc[2][3];
-  double rb[2][3];
+  double rb[2][3], rx[2][3];
+  // SLIM: this lane's pose (a lane constant) and the points of the linearisation.
+  double T[12];
+  const double *__restrict__ ptg = d.pts[d.ctrl->cur];
+  if (SLIM) {
+    const double *Tp = d.poses[d.ctrl->cur] + (size_t)grps[blockIdx.x].pose[jj] * 12;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = Tp[k];
+  }
 #define GRP_PREFETCH(B, ch_)                                                        \
   {                                                                                 \
     const int c0_ = (ch_) * nlw;                                                    \
     const bool on_ = il < min(nlw, gd.nl - c0_);                                    \
-    const double2 *wp_ = (const double2 *)(Wg + (size_t)(gd.p0 + (int64_t)c0_ * dd + (on_ ? lane : 0)) * kWStride); \
+    const double2 *wp_ = (const double2 *)(Wg + (size_t)(gd.p0 + (int64_t)c0_ * dd + (on_ ? lane : 0)) * (2 * RW)); \
     const int lm_ = gd.l0 + c0_ + (on_ ? il : 0);                                   \
     const double2 *cp_ = (const double2 *)(Cug + (size_t)lm_ * 6);                  \
-    _Pragma("unroll") for (int k_ = 0; k_ < 6; ++k_) rw[B][k_] = wp_[k_];           \
+    _Pragma("unroll") for (int k_ = 0; k_ < RW; ++k_) rw[B][k_] = wp_[k_];          \
     _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) rc[B][k_] = cp_[k_];           \
     _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) rb[B][k_] = bg[(size_t)lm_ * 3 + k_]; \
+    if (SLIM) {                                                                     \
+      _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) rx[B][k_] = ptg[(size_t)lm_ * 3 + k_]; \
+    }                                                                               \
   }
   v4f64 acc[NTILE];
 #pragma unroll
   for (int t = 0; t < NTILE; ++t) acc[t] = (v4f64){0.0, 0.0, 0.0, 0.0};
   if (wv < nch) GRP_PREFETCH(0, wv)
-  if (wv + 4 < nch) GRP_PREFETCH(1, wv + 4)
+  if (RD == 2 && wv + 4 < nch) GRP_PREFETCH(1, wv + 4)
 #define GRP_IDX(k_, col_) (((k_) >> 1) * RS + (col_) * 2 + ((k_) & 1))
 #define GRP_STAGE(B)                                                                \
   if (ch < nch) {                                                                   \
@@ -1284,9 +1314,16 @@ __global__ __launch_bounds__(kBlock, (NT == 2 && BA_GRP_KRW <= 24) ? 3 : 2) void
       /* W_p (6x3) from its compact record, V_p = W_p Cinv_i (fused multiply-adds: the fp64 \
          VALU shares its pipe with the fp64 MFMA on this part, every instruction counts) */ \
       _Pragma("clang fp contract(fast)")                                            \
-      const double k9[9] = {rw[B][0].x, rw[B][0].y, rw[B][1].x, rw[B][1].y, rw[B][2].x, \
-                            rw[B][2].y, rw[B][3].x, rw[B][3].y, rw[B][4].x};        \
-      const double x0 = rw[B][4].y, x1 = rw[B][5].x, x2 = rw[B][5].y;               \
+      double k9[9], xij[3];                                                         \
+      if (SLIM) {                                                                   \
+        const double G_[6] = {rw[B][0].x, rw[B][0].y, rw[B][1].x, rw[B][1].y, rw[B][2].x, rw[B][2].y}; \
+        pair_from_G(G_, rw[B][3].x, T, rx[B][0], rx[B][1], rx[B][2], k9, xij);      \
+      } else {                                                                      \
+        k9[0] = rw[B][0].x; k9[1] = rw[B][0].y; k9[2] = rw[B][1].x; k9[3] = rw[B][1].y; k9[4] = rw[B][2].x; \
+        k9[5] = rw[B][2].y; k9[6] = rw[B][3].x; k9[7] = rw[B][3].y; k9[8] = rw[B][4].x; \
+        xij[0] = rw[B][4].y; xij[1] = rw[B][5].x; xij[2] = rw[B][5].y;              \
+      }                                                                             \
+      const double x0 = xij[0], x1 = xij[1], x2 = xij[2];                           \
       /* damping and the 3x3 inverse (reference :846-856) in the lane: the d lanes of a \
          landmark repeat it, which is cheaper than a kernel + an array for Cinv */    \
       const double cd_[6] = {rc[B][0].x * lp1, rc[B][0].y, rc[B][1].x, rc[B][1].y * lp1, rc[B][2].x, rc[B][2].y * lp1}; \
@@ -1325,7 +1362,7 @@ __global__ __launch_bounds__(kBlock, (NT == 2 && BA_GRP_KRW <= 24) ? 3 : 2) void
       }                                                                             \
     }                                                                               \
     GRP_STAMP()                                                                     \
-    if (ch + 8 < nch) GRP_PREFETCH(B, ch + 8)                                       \
+    if (ch + 4 * RD < nch) GRP_PREFETCH(B, ch + 4 * RD)                             \
     GRP_STAMP()                                                                     \
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                          \
     __builtin_amdgcn_wave_barrier();                                                \
@@ -1365,7 +1402,7 @@ __global__ __launch_bounds__(kBlock, (NT == 2 && BA_GRP_KRW <= 24) ? 3 : 2) void
   }
   for (int ch = wv; ch < nch;) {
     GRP_STAGE(0)
-    GRP_STAGE(1)
+    GRP_STAGE(RD - 1)
   }
 #undef GRP_STAGE
 #undef GRP_IDX
@@ -1422,6 +1459,8 @@ __global__ __launch_bounds__(kBlock, (NT == 2 && BA_GRP_KRW <= 24) ? 3 : 2) void
 // MFMAs, and there is no final sum over waves: a wave scatters its tiles to the group's
 // slots itself.  Same arithmetic as k_schur_grp per entry; the k order is the landmark
 // order (deterministic).
+// SLIM: as in k_schur_grp.
+template <bool SLIM>
 __global__ __launch_bounds__(kBlock, 2) void k_schur_grp_wide(DevProblem d, const DevProblem::GrpDesc *grps) {
   constexpr int TW = 128;
   constexpr int LPW = 2;            // landmarks a wave stages per stage
@@ -1462,19 +1501,31 @@ __global__ __launch_bounds__(kBlock, 2) void k_schur_grp_wide(DevProblem d, cons
   }
   // operands of the NEXT stage, requested while this one is multiplied (one buffer: a two-
   // deep ring made the compiler copy in-flight registers across the loop and wait for them)
+  constexpr int RW = (SLIM ? kWSlim : kWStride) / 2;  // 16-byte pieces of a pair record
   double2 rw[1][6], rc[1][3];
-  double rb[1][3];
+  double rb[1][3], rx[1][3];
+  // SLIM: this lane's pose (a lane constant) and the points of the linearisation
+  double T[12];
+  const double *__restrict__ ptg = d.pts[d.ctrl->cur];
+  if (SLIM) {
+    const double *Tp = d.poses[d.ctrl->cur] + (size_t)gp->pose[jj] * 12;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = Tp[k];
+  }
 #define GW_PREFETCH(B, st_)                                                         \
   {                                                                                 \
     const int c0_ = (st_) * per_stage;                                              \
     const bool on_ = il < nlw && c0_ + li < gnl;                                     \
-    const double2 *wp_ = (const double2 *)(Wg + (size_t)(gp0 + (int64_t)(c0_ + wv * nlw) * dd + (on_ ? lane : 0)) * kWStride); \
+    const double2 *wp_ = (const double2 *)(Wg + (size_t)(gp0 + (int64_t)(c0_ + wv * nlw) * dd + (on_ ? lane : 0)) * (2 * RW)); \
     const int lm_ = gl0 + (on_ ? c0_ + li : 0);                                     \
     const double2 *cp_ = (const double2 *)(Cug + (size_t)lm_ * 6);                  \
-    if (!on_) wp_ = (const double2 *)(Wg + (size_t)gp0 * kWStride);                 \
-    _Pragma("unroll") for (int k_ = 0; k_ < 6; ++k_) rw[B][k_] = wp_[k_];           \
+    if (!on_) wp_ = (const double2 *)(Wg + (size_t)gp0 * (2 * RW));                 \
+    _Pragma("unroll") for (int k_ = 0; k_ < RW; ++k_) rw[B][k_] = wp_[k_];          \
     _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) rc[B][k_] = cp_[k_];           \
     _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) rb[B][k_] = bg[(size_t)lm_ * 3 + k_]; \
+    if (SLIM) {                                                                     \
+      _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) rx[B][k_] = ptg[(size_t)lm_ * 3 + k_]; \
+    }                                                                               \
   }
   v4f64 acc[9];
 #pragma unroll
@@ -1490,13 +1541,23 @@ __global__ __launch_bounds__(kBlock, 2) void k_schur_grp_wide(DevProblem d, cons
     /* the stage's operands are waited for HERE, on every path: consumed only under \
        the branch below, they would count as still in flight behind it and the next \
        prefetch (which reuses their registers) would wait for ALL loads */           \
-    _Pragma("unroll") for (int k_ = 0; k_ < 6; ++k_) asm volatile("" : "+v"(rw[B][k_].x), "+v"(rw[B][k_].y)); \
+    _Pragma("unroll") for (int k_ = 0; k_ < RW; ++k_) asm volatile("" : "+v"(rw[B][k_].x), "+v"(rw[B][k_].y)); \
     _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) asm volatile("" : "+v"(rc[B][k_].x), "+v"(rc[B][k_].y), "+v"(rb[B][k_])); \
+    if (SLIM) {                                                                     \
+      _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) asm volatile("" : "+v"(rx[B][k_])); \
+    }                                                                               \
     if (il < nlw && li < nlc) {                                                     \
       _Pragma("clang fp contract(fast)")                                            \
-      const double k9[9] = {rw[B][0].x, rw[B][0].y, rw[B][1].x, rw[B][1].y, rw[B][2].x, \
-                            rw[B][2].y, rw[B][3].x, rw[B][3].y, rw[B][4].x};        \
-      const double x0 = rw[B][4].y, x1 = rw[B][5].x, x2 = rw[B][5].y;               \
+      double k9[9], xij[3];                                                         \
+      if (SLIM) {                                                                   \
+        const double G_[6] = {rw[B][0].x, rw[B][0].y, rw[B][1].x, rw[B][1].y, rw[B][2].x, rw[B][2].y}; \
+        pair_from_G(G_, rw[B][3].x, T, rx[B][0], rx[B][1], rx[B][2], k9, xij);      \
+      } else {                                                                      \
+        k9[0] = rw[B][0].x; k9[1] = rw[B][0].y; k9[2] = rw[B][1].x; k9[3] = rw[B][1].y; k9[4] = rw[B][2].x; \
+        k9[5] = rw[B][2].y; k9[6] = rw[B][3].x; k9[7] = rw[B][3].y; k9[8] = rw[B][4].x; \
+        xij[0] = rw[B][4].y; xij[1] = rw[B][5].x; xij[2] = rw[B][5].y;              \
+      }                                                                             \
+      const double x0 = xij[0], x1 = xij[1], x2 = xij[2];                           \
       const double cd_[6] = {rc[B][0].x * lp1, rc[B][0].y, rc[B][1].x, rc[B][1].y * lp1, rc[B][2].x, rc[B][2].y * lp1}; \
       double c6[6];                                                                 \
       spd3_inverse(cd_, c6);                                                        \
@@ -2071,6 +2132,10 @@ __device__ __forceinline__ void backsub_chunk_body(const DevProblem &d, const in
 // redistributed through the wave's LDS image.  u = B_ji^T x_j per lane; one lane per
 // landmark adds its d vectors in pair order, inverts the damped C_i and updates the
 // point (reference :846-856, :907-925, :443-452).
+// SLIM: the records are {G, w, 0} (ba_device.h kWSlim), four 16-byte pieces per pair; the
+// lane's pose is one more lane constant, the point comes from the block's landmark image
+// and the lane rebuilds {K, X_ij} (pair_from_G) before it forms u as with the 96-byte record.
+template <bool SLIM>
 __device__ __forceinline__ void backsub_grp_body(const DevProblem &d, const int piece, const int part, double *lds,
                                                  double *sm) {
   const DevProblem::LinDesc *gp = d.lin_desc + piece;
@@ -2096,8 +2161,15 @@ __device__ __forceinline__ void backsub_grp_body(const DevProblem &d, const int 
   }
   double *__restrict__ Xt = d.pts[cur ^ 1];
   const double2 *__restrict__ Wg2 = (const double2 *)d.W[lbs];
-  double *Wim = lds + wv * kBgArea;  // 64 * kWStride: W image of the step
-  double *Us = Wim + 64 * kWStride;  // 64 * 3: u per pair
+  constexpr int RW = (SLIM ? kWSlim : kWStride) / 2;  // 16-byte pieces of a pair record
+  double T[12];
+  if (SLIM) {
+    const double *Tp = d.poses[cur] + (size_t)pose * 12;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = Tp[k];
+  }
+  double *Wim = lds + wv * kBgArea;  // 64 * 2 RW: W image of the step
+  double *Us = Wim + 64 * 2 * RW;    // 64 * 3: u per pair
   double *Lm = Us + 64 * 3;          // per step of a block: C_i (6), b_i (3), X_i (3) of its landmarks
   double *Bx = Lm + 64 * 12;         // 64 * 3: sum_j W_ji^T x_j of the block's landmarks
   // The landmark arithmetic (3x3 inverse, y_i, model terms: ~250 instructions) runs
@@ -2135,16 +2207,18 @@ __device__ __forceinline__ void backsub_grp_body(const DevProblem &d, const int 
   {                                                                                 \
     const int il0_ = il0_of(ST);                                                    \
     const int nls_ = max(0, min(nlwb, nl - il0_));                                  \
-    const int last_ = max(0, nls_ * dd * 6 - 1);                                    \
+    const int last_ = max(0, nls_ * dd * RW - 1);                                   \
     const int ilb_ = nls_ > 0 ? il0_ : 0;                                           \
     const int lml_ = max(0, nls_ - 1);                                              \
-    const double2 *src_ = Wg2 + (dd > 0 ? (size_t)(p0 + (int64_t)ilb_ * dd) * 6 : (size_t)0); \
+    const double2 *src_ = Wg2 + (dd > 0 ? (size_t)(p0 + (int64_t)ilb_ * dd) * RW : (size_t)0); \
     R##0 = src_[min(lane, last_)];                                                  \
     R##1 = src_[min(lane + 64, last_)];                                             \
     R##2 = src_[min(lane + 128, last_)];                                            \
     R##3 = src_[min(lane + 192, last_)];                                            \
-    R##4 = src_[min(lane + 256, last_)];                                            \
-    R##5 = src_[min(lane + 320, last_)];                                            \
+    if (!SLIM) {                                                                    \
+      R##4 = src_[min(lane + 256, last_)];                                          \
+      R##5 = src_[min(lane + 320, last_)];                                          \
+    }                                                                               \
     L##0 = lm_p[0][(size_t)(ilb_ + min(lm_l[0], lml_)) * lm_m[0]];                  \
     L##1 = lm_p[1][(size_t)(ilb_ + min(lm_l[1], lml_)) * lm_m[1]];                  \
     L##2 = lm_p[2][(size_t)(ilb_ + min(lm_l[2], lml_)) * lm_m[2]];                  \
@@ -2169,14 +2243,33 @@ __device__ __forceinline__ void backsub_grp_body(const DevProblem &d, const int 
     ((double2 *)Wim)[lane + 64] = R##1;                                             \
     ((double2 *)Wim)[lane + 128] = R##2;                                            \
     ((double2 *)Wim)[lane + 192] = R##3;                                            \
-    ((double2 *)Wim)[lane + 256] = R##4;                                            \
-    ((double2 *)Wim)[lane + 320] = R##5;                                            \
+    if (!SLIM) {                                                                    \
+      ((double2 *)Wim)[lane + 256] = R##4;                                          \
+      ((double2 *)Wim)[lane + 320] = R##5;                                          \
+    }                                                                               \
     Lm[sb * nlwb * 12 + lm_q[0]] = L##0;                                            \
     Lm[sb * nlwb * 12 + lm_q[1]] = L##1;                                            \
     Lm[sb * nlwb * 12 + lm_q[2]] = L##2;                                            \
     BSG_ISSUE(R, L, st + 2)                                                         \
     BSG_WAVE_SYNC()                                                                 \
-    if (lane_on) {                                                                  \
+    if (SLIM && lane_on) {                                                          \
+      /* {K, X_ij} from {G, w}, the lane's pose and the landmark's point, then as below */ \
+      const double2 *w2 = (const double2 *)(Wim + lane * kWSlim);                   \
+      const double2 g01 = w2[0], g23 = w2[1], g45 = w2[2], w_ = w2[3];              \
+      const double G_[6] = {g01.x, g01.y, g23.x, g23.y, g45.x, g45.y};              \
+      const double *Xi_ = Lm + sb * nlwb * 12 + nlwb * 9 + ilw * 3;                 \
+      double k_[9], x_[3];                                                          \
+      pair_from_G(G_, w_.x, T, Xi_[0], Xi_[1], Xi_[2], k_, x_);                     \
+      const double X0 = x_[0], X1 = x_[1], X2 = x_[2];                              \
+      const double e0 = xj[0] + (xj[4] * X2 - xj[5] * X1);                          \
+      const double e1 = xj[1] + (xj[5] * X0 - xj[3] * X2);                          \
+      const double e2 = xj[2] + (xj[3] * X1 - xj[4] * X0);                          \
+      double *u = Us + lane * 3;                                                    \
+      u[0] = fma(k_[6], e2, fma(k_[3], e1, k_[0] * e0));                            \
+      u[1] = fma(k_[7], e2, fma(k_[4], e1, k_[1] * e0));                            \
+      u[2] = fma(k_[8], e2, fma(k_[5], e1, k_[2] * e0));                            \
+    }                                                                               \
+    if (!SLIM && lane_on) {                                                         \
       /* u_c = sum_r B_ji[r][c] x_j[r] = K[:,c] . (x_t + x_r x X_ij) */             \
       const double2 *w2 = (const double2 *)(Wim + lane * kWStride);                 \
       const double2 k01 = w2[0], k23 = w2[1], k45 = w2[2], k67 = w2[3], k8x = w2[4], xx = w2[5]; \
@@ -2280,7 +2373,8 @@ __device__ __forceinline__ void backsub_grp_body(const DevProblem &d, const int 
 // of lm_part = blockIdx - kPoseGrid.
 // GROUPS = false: problems without covisibility groups (chunk role only): the LDS of
 // the chunk role alone and four workgroups per CU instead of two.
-template <bool GROUPS>
+// SLIM (with GROUPS only): the record form of the grouped pairs, the host's choice.
+template <bool GROUPS, bool SLIM>
 __global__ __launch_bounds__(kBlock, GROUPS ? 2 : 4) void k_backsub_update(DevProblem d) {
   __shared__ __attribute__((aligned(16))) double lds[GROUPS ? kBsLds : kSchurPairs * (kWStride + 6 + 3)];
   __shared__ double sm[8];
@@ -2302,7 +2396,7 @@ __global__ __launch_bounds__(kBlock, GROUPS ? 2 : 4) void k_backsub_update(DevPr
     return;
   }
   if (GROUPS && part < d.n_bs_grp)
-    backsub_grp_body(d, part, part, lds, sm);
+    backsub_grp_body<SLIM>(d, part, part, lds, sm);
   else
     backsub_chunk_body(d, part - d.n_bs_grp, part, lds, sm, recs);
 }
@@ -2753,13 +2847,17 @@ void launch_cost(const DevProblem &d, int sel, int64_t begin, hipStream_t s) {
 void launch_lin_landmarks(const DevProblem &d, int sel, hipStream_t s) {
   if (d.lin_chunk0 > 0) {  // covisibility groups: landmark and pose side in one pass
     const int n_plain = d.n_lin_plain, n_mask = d.n_lin_desc - d.n_lin_plain;
+#define BA_LIN_GRP_LAUNCH(LDS, SLIM)                                                                                  \
+  {                                                                                                                   \
+    if (n_plain > 0) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<LDS, false, SLIM>), dim3(n_plain), dim3(kBlock), s, d, sel, 0);   \
+    if (n_mask > 0) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<LDS, true, SLIM>), dim3(n_mask), dim3(kBlock), s, d, sel, n_plain); \
+  }
     if (d.n_cam <= kCamLds) {
-      if (n_plain > 0) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<true, false>), dim3(n_plain), dim3(kBlock), s, d, sel, 0);
-      if (n_mask > 0) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<true, true>), dim3(n_mask), dim3(kBlock), s, d, sel, n_plain);
+      if (d.pair_slim) BA_LIN_GRP_LAUNCH(true, true) else BA_LIN_GRP_LAUNCH(true, false)
     } else {
-      if (n_plain > 0) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<false, false>), dim3(n_plain), dim3(kBlock), s, d, sel, 0);
-      if (n_mask > 0) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<false, true>), dim3(n_mask), dim3(kBlock), s, d, sel, n_plain);
+      if (d.pair_slim) BA_LIN_GRP_LAUNCH(false, true) else BA_LIN_GRP_LAUNCH(false, false)
     }
+#undef BA_LIN_GRP_LAUNCH
   }
   const int nch = d.n_bchunk - d.lin_chunk0;
   if (nch <= 0) return;
@@ -2813,12 +2911,22 @@ extern "C" int ba_debug_read(long long *out) {
 }
 #endif
 void launch_schur_accumulate(const DevProblem &d, hipStream_t s) {
-  if (d.n_grp32 > 0)
-    BA_LAUNCH(K_SCHUR_GRP, k_schur_grp<2>, dim3(d.n_grp32), dim3(kBlock), s, d, d.grp32);
-  if (d.n_grp64 > 0)
-    BA_LAUNCH(K_SCHUR_GRP, k_schur_grp<4>, dim3(d.n_grp64), dim3(kBlock), s, d, d.grp64);
-  if (d.n_grp128 > 0)
-    BA_LAUNCH(K_SCHUR_GRP, k_schur_grp_wide, dim3(d.n_grp128), dim3(kBlock), s, d, d.grp128);
+  // (the record form of the grouped pairs is the host's choice: a template parameter)
+  if (d.pair_slim) {
+    if (d.n_grp32 > 0)
+      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<2, true>), dim3(d.n_grp32), dim3(kBlock), s, d, d.grp32);
+    if (d.n_grp64 > 0)
+      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<4, true>), dim3(d.n_grp64), dim3(kBlock), s, d, d.grp64);
+    if (d.n_grp128 > 0)
+      BA_LAUNCH(K_SCHUR_GRP, k_schur_grp_wide<true>, dim3(d.n_grp128), dim3(kBlock), s, d, d.grp128);
+  } else {
+    if (d.n_grp32 > 0)
+      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<2, false>), dim3(d.n_grp32), dim3(kBlock), s, d, d.grp32);
+    if (d.n_grp64 > 0)
+      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<4, false>), dim3(d.n_grp64), dim3(kBlock), s, d, d.grp64);
+    if (d.n_grp128 > 0)
+      BA_LAUNCH(K_SCHUR_GRP, k_schur_grp_wide<false>, dim3(d.n_grp128), dim3(kBlock), s, d, d.grp128);
+  }
   if (d.n_sup > 0)
     BA_LAUNCH(K_SCHUR_LDS, k_schur_lds, dim3(d.n_sup), dim3(kBlock), s, d);
   if (d.n_tchunk > 0)
@@ -2849,10 +2957,12 @@ void launch_scatter(const DevProblem &d, hipStream_t s) {
 void launch_backsub_update(const DevProblem &d, hipStream_t s, bool zero_tiles) {
   // pose workgroups, covisibility-group pieces, chunk workgroups, [factor-tile reset] (see the kernel)
   const dim3 grid(kPoseGrid + d.n_lm_part + (zero_tiles ? d.n_zt : 0));
-  if (d.n_bs_grp > 0)
-    BA_LAUNCH(K_BACKSUB_UPDATE, k_backsub_update<true>, grid, dim3(kBlock), s, d);
+  if (d.n_bs_grp > 0 && d.pair_slim)
+    BA_LAUNCH(K_BACKSUB_UPDATE, (k_backsub_update<true, true>), grid, dim3(kBlock), s, d);
+  else if (d.n_bs_grp > 0)
+    BA_LAUNCH(K_BACKSUB_UPDATE, (k_backsub_update<true, false>), grid, dim3(kBlock), s, d);
   else
-    BA_LAUNCH(K_BACKSUB_UPDATE, k_backsub_update<false>, grid, dim3(kBlock), s, d);
+    BA_LAUNCH(K_BACKSUB_UPDATE, (k_backsub_update<false, false>), grid, dim3(kBlock), s, d);
 }
 
 void launch_scalars(const DevProblem &d, int cost_src, hipStream_t s) {

@@ -36,11 +36,17 @@ struct RunKnobs {
   bool stream_sync = false;  // BA_STREAM_SYNC=1: ba_stream synchronises the device after every transfer and chunk
 };
 
+// How the blocks are laid out in device memory.
+struct LayoutKnobs {
+  bool pair_slim = true;  // BA_PAIR_SLIM=0: the pairs of k_lin_grp's groups keep the 96-byte record {K, X_ij}, not {G, w}
+};
+
 struct Knobs {
   PlanKnobs plan;
   DenseKnobs dense;
   ConeKnobs cone;
   RunKnobs run;
+  LayoutKnobs layout;
   static Knobs from_env();
 };
 
@@ -71,6 +77,10 @@ inline Knobs Knobs::from_env() {
   k.run.cost_wide = is_one("BA_COST_WIDE");
   k.run.cov_batch = number("BA_COV_BATCH", 1, 1 << 30);
   k.run.stream_sync = is_one("BA_STREAM_SYNC");
+  {
+    const char *v = getenv("BA_PAIR_SLIM");
+    k.layout.pair_slim = !(v && v[0] == '0');
+  }
   return k;
 }
 

@@ -655,6 +655,13 @@ class BaProblem:
         return dict(group_pieces=int(v[0]), group_observations=int(v[1]), chunks=int(v[2]),
                     pose_major_observations=int(v[3]))
 
+    def get_pair_record_info(self):
+        """Pair records of this shard: how many are kept as the 64-byte record {G, w}
+        (the pairs of the covisibility groups) and how many pairs there are."""
+        v = (C.c_int64 * 2)()
+        check(self.lib.ba_get_pair_record_info(self.h, v), "ba_get_pair_record_info")
+        return dict(slim_pairs=int(v[0]), pairs=int(v[1]))
+
     def get_mask_info(self):
         """Superset (masked) covisibility groups of this shard."""
         v = (C.c_int64 * 4)()

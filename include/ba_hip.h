@@ -295,6 +295,12 @@ int ba_get_Cinv(ba_handle *h, double *Cinv9, double *Cinvb3);
 /* pairs (global i_opt, j_opt) in internal order with W = B_ji (6x3, row-major; the
  * device keeps it compact as {K, X_ij} and this call expands it) */
 int ba_get_pairs(ba_handle *h, int32_t *pair_i, int32_t *pair_j, double *W18);
+/* Host-side step of ba_get_pairs, no device involved: the pairs of covisibility groups
+ * are kept as rec8 = {G (2x3 row-major), w, 0} of the pair's last writer; with the pose
+ * T12 = {R_jw row-major, t_jw} and the point X3 the blocks were linearised at this gives
+ * k12 = {K = G^T w G R_jw (3x3 row-major), X_ij = R_jw X + t_jw}, the compact form of
+ * every other pair.  The group kernels rebuild K and X_ij by the same expression. */
+void ba_expand_pair_slim(const double *rec8, const double *T12, const double *X3, double *k12);
 /* reduced camera system, (6N)^2 row-major, and rhs, in opt-pose order */
 int ba_get_S(ba_handle *h, double *S, double *rhs);
 int ba_get_xy(ba_handle *h, double *x6, double *y3);
@@ -328,6 +334,10 @@ int ba_get_schur_info(ba_handle *h, int64_t out8[8]);
  * cover, landmark chunks left to the chunk kernel, observations on the
  * pose-major list }. */
 int ba_get_lin_info(ba_handle *h, int64_t out4[4]);
+/* Pair records of this shard: out2 = { pairs kept as the 64-byte record {G, w} (the pairs of
+ * the covisibility groups, when k_lin_grp linearises them and BA_PAIR_SLIM is not 0), all
+ * pairs, padded ones included }.  The others keep the 96-byte record {K, X_ij}. */
+int ba_get_pair_record_info(ba_handle *h, int64_t out2[2]);
 
 /* Superset ("masked") covisibility groups — landmarks of one pose span whose
  * observation patterns differ (occlusion, image borders, track loss) share the UNION
