@@ -100,11 +100,19 @@ def test_blocks_match_the_host_inverse(built, kind):
 
 
 def test_shapes_cover_one_tile_and_a_banded_schedule(built):
+    """The three scenes of this module: one tile of 32; five banded tiles of 32; and, for
+    stereo12, ONE tile of 64 — npad 64 is one tile of 64 or two of 32, and the single level
+    of the schedule says which.  So no scene here takes k_cov_solve<64> past its first
+    tile: tile order 64 with several tiles, fill-in and long landmarks are the subject of
+    test_gpu_covariance_shapes.py."""
     dense, N, _ = case("onetile")[7]
     assert N == 2 and dense["npad"] == 32            # 12 columns + 20 padding columns
     dense, N, _ = case("mono28")[7]
     assert N == 23 and dense["npad"] == 160          # 138 columns, 5 tiles of 32
     assert dense["fill"] < 1.0                       # zero tiles in the schedule
+    dense, N, _ = case("stereo12")[7]
+    assert N == 7 and dense["npad"] == 64            # 42 columns + 22 padding columns
+    assert dense["levels"] == 1 and dense["fill"] == 1.0
 
 
 def test_more_than_one_column_batch(built, monkeypatch):
