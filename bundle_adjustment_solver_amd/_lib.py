@@ -203,6 +203,9 @@ SIGNATURES = {
     "ba_get_schur_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "ba_get_lin_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "ba_get_pair_record_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "ba_get_pair_form": (C.c_int, [_P]),
+    "ba_get_slim_records": (C.c_int, [_P, _I32, _I32, _I32, _D, _D]),
+    "ba_pair_G_from_obs": (None, [_D, _D, _D, _D, C.c_double, _D]),
     "ba_get_mask_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "ba_get_dropped_pivots": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
     "ba_dense_spd_solve": (C.c_int, [_P, C.c_int, _D, _D, _D, _D]),

@@ -376,6 +376,69 @@ int upload_observation_lists(ba_handle *h) {
   return 0;
 }
 
+// The "from the observation" form of the grouped pairs (ba_device.h PairObs), taken by a slim
+// handle whose groups are all 32 wide and none of them masked, outside streaming (the chunk
+// handles of ba_stream.hip keep the slim form).  Builds and uploads one PairObs per
+// k_lin_grp piece and per k_schur_grp workgroup from lin_desc / grp_pat; a plan the side
+// arrays cannot describe keeps the slim form.
+int choose_pair_obs(ba_handle *h) {
+  const ba::Plan &pl = h->plan;
+  ba::DevProblem &d = h->d;
+  d.pair_obs = 0;
+  if (!d.pair_slim || !h->knobs.layout.pair_obs || h->arena || !pl.grp64.empty() || !pl.grp128.empty() ||
+      pl.n_lin_plain != (int)pl.lin_desc.size() || pl.grp32.empty())
+    return 0;
+  std::vector<ba::PairObs> lin_obs(pl.lin_desc.size()), grp_obs(pl.grp32.size());
+  std::vector<int> by_l0(pl.lin_desc.size());
+  for (size_t k = 0; k < pl.lin_desc.size(); ++k) {
+    const auto &g = pl.lin_desc[k];
+    if (g.d > ba::kPairObsPoses || g.no > 255) return 0;
+    ba::PairObs &po = lin_obs[k];
+    po.o0 = g.o0;
+    po.no = g.no;
+    for (int jj = 0; jj < ba::kPairObsPoses; ++jj) po.sc[jj] = -1;
+    for (int oo = 0; oo < g.no; ++oo) {
+      const int y = pl.grp_pat[2 * ((size_t)g.pat0 + oo) + 1];
+      if (!((y >> 30) & 1)) continue;  // (last writer of its pair: the last slot of an optimisable pose)
+      const int jj = (y >> 16) & 0xff;
+      if (jj >= g.d) return 0;
+      po.sc[jj] = oo | (y & 0xffff) << 8;
+    }
+    for (int jj = 0; jj < ba::kPairObsPoses; ++jj) {
+      if (jj < g.d && po.sc[jj] < 0) return 0;
+      if (jj >= g.d) po.sc[jj] = 0;
+    }
+    by_l0[k] = (int)k;
+  }
+  std::sort(by_l0.begin(), by_l0.end(), [&](int a, int b) { return pl.lin_desc[a].l0 < pl.lin_desc[b].l0; });
+  // the piece that holds landmark l, or -1
+  auto piece_of = [&](int l) {
+    auto it = std::upper_bound(by_l0.begin(), by_l0.end(), l, [&](int v, int k) { return v < pl.lin_desc[k].l0; });
+    if (it == by_l0.begin()) return -1;
+    const int k = *(it - 1);
+    return l < pl.lin_desc[k].l0 + pl.lin_desc[k].nl ? k : -1;
+  };
+  for (size_t k = 0; k < pl.grp32.size(); ++k) {
+    // a k_schur_grp workgroup lies inside ONE group: its first and last landmark are in pieces
+    // of the same pattern whose observations are one run
+    const auto &g = pl.grp32[k];
+    const int ka = piece_of(g.l0), kb = piece_of(g.l0 + g.nl - 1);
+    if (ka < 0 || kb < 0) return 0;
+    const auto &a = pl.lin_desc[ka], &b = pl.lin_desc[kb];
+    if (a.pat0 != b.pat0 || a.d != g.d || a.no != b.no || g.p0 != a.p0 + (int64_t)(g.l0 - a.l0) * a.d ||
+        b.o0 != a.o0 + (int64_t)(b.l0 - a.l0) * a.no)
+      return 0;
+    grp_obs[k] = lin_obs[ka];
+    grp_obs[k].o0 = a.o0 + (int64_t)(g.l0 - a.l0) * a.no;
+  }
+  static_assert(sizeof(ba::PairObs) == 32, "side array layout");
+  if (h->upload(Mem::ChunkConst, &d.lin_obs, lin_obs.data(), lin_obs.size()) ||
+      h->upload(Mem::ChunkConst, &d.grp_obs, grp_obs.data(), grp_obs.size()))
+    return -1;
+  d.pair_obs = 1;
+  return 0;
+}
+
 // Structure, second half: the descriptors of super-runs, chunks and covisibility groups
 // and the slot partials that go with them.
 int upload_descriptors_and_groups(ba_handle *h) {
@@ -405,6 +468,7 @@ int upload_descriptors_and_groups(ba_handle *h) {
   // k_backsub_update read (ba_device.h kWSlim)
   d.pair_slim = h->knobs.layout.pair_slim && pl.lin_groups && d.n_lin_desc > 0 ? 1 : 0;
   d.P_slim = d.pair_slim ? pl.lm_pair_ptr[pl.M_grp] : 0;
+  if (choose_pair_obs(h)) return -1;
   if (h->upload(Mem::ChunkConst, &d.sup_desc, pl.sup_desc.data(), pl.sup_desc.size()) ||
       h->upload(Mem::ChunkConst, &d.chunk_desc, pl.chunk_desc.data(), pl.chunk_desc.size()) ||
       h->dalloc(Mem::ChunkState, &d.spart2, (size_t)d.n_slot * ba::kSlotStride) ||
@@ -1509,6 +1573,55 @@ void ba_expand_pair_slim(const double *rec8, const double *T12, const double *X3
   ba::pair_from_G(rec8, rec8[6], T12, X3[0], X3[1], X3[2], k12, k12 + 9);
 }
 
+void ba_pair_G_from_obs(const double *cam16, const double *T12, const double *X3, const double *uv2, double huber,
+                        double *rec8) {
+  ba::pair_G_from_obs(cam16, T12, X3[0], X3[1], X3[2], uv2[0], uv2[1], huber, rec8, rec8[6]);
+  rec8[7] = 0.0;
+}
+
+int ba_get_pair_form(ba_handle *h) {
+  if (!h || !h->finalized) return fail("ba_get_pair_form: not finalized");
+  return h->d.pair_obs ? 2 : (h->d.pair_slim ? 1 : 0);
+}
+
+int ba_get_slim_records(ba_handle *h, int32_t *pose, int32_t *lm, int32_t *cam, double *uv2, double *rec8) {
+  if (!h || !h->finalized) return fail("ba_get_slim_records: not finalized");
+  if (use_device(h)) return -1;
+  const ba::Plan &pl = h->plan;
+  const int64_t n = h->d.P_slim;
+  if (pull_ctrl(h)) return -1;  // synchronises the stream
+  if (rec8 && n > 0) {
+    if (h->d.pair_obs) {
+      ba::launch_pair_records(h->d, h->stream);
+      HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    HIP_TRY(hipMemcpy(rec8, h->d.W[h->hc.lcur], (size_t)n * ba::kWSlim * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  for (int64_t p = 0; p < n; ++p) {
+    if (pose) pose[p] = pl.pose_user_of_int[pl.pair_pose[p]];
+    if (lm) lm[p] = pl.pt_user_of_int[pl.pair_lm[p]];
+  }
+  if (cam || uv2) {
+    // the last writer of every grouped pair, from the patterns of the group pieces
+    for (const auto &g : pl.lin_desc)
+      for (int oo = 0; oo < g.no; ++oo) {
+        const int y = pl.grp_pat[2 * ((size_t)g.pat0 + oo) + 1];
+        if (!((y >> 30) & 1)) continue;
+        const int jj = (y >> 16) & 0xff;
+        for (int il = 0; il < g.nl; ++il) {
+          const int64_t p = g.p0 + (int64_t)il * g.d + jj, o = g.o0 + (int64_t)il * g.no + oo;
+          if (p >= n) continue;
+          if (cam) cam[p] = y & 0xffff;
+          if (uv2) {
+            uv2[2 * p] = pl.obs_uv[2 * o];
+            uv2[2 * p + 1] = pl.obs_uv[2 * o + 1];
+          }
+        }
+      }
+  }
+  return 0;
+}
+
 int ba_get_pairs(ba_handle *h, int32_t *pair_i, int32_t *pair_j, double *W18) {
   if (!h || !h->finalized) return fail("ba_get_pairs: not finalized");
   if (use_device(h)) return -1;
@@ -1527,6 +1640,10 @@ int ba_get_pairs(ba_handle *h, int32_t *pair_i, int32_t *pair_j, double *W18) {
     if (pull_ctrl(h)) return -1;  // synchronises the stream
     // the device keeps B_ji compact ({K, X_ij}, ba_device.h kWStride): expand
     std::vector<double> w12((size_t)pl.P * ba::kWStride);
+    if (h->d.pair_obs) {  // the iteration keeps no record of the grouped pairs: fill the slim ones
+      ba::launch_pair_records(h->d, h->stream);
+      HIP_TRY(hipStreamSynchronize(h->stream));
+    }
     if (pl.P > 0)
       HIP_TRY(hipMemcpy(w12.data(), h->d.W[h->hc.lcur], w12.size() * sizeof(double), hipMemcpyDeviceToHost));
     // the slim pairs ({G, w}, ba_device.h kWSlim) first become {K, X_ij}, from the poses and
@@ -1906,6 +2023,7 @@ int ba_covariance(ba_handle *h, double huber, int n_pose_sel, const int32_t *pos
   HIP_TRY(hipMemcpy(&bad_keep, h->ddev.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemsetAsync(h->ddev.bad_pivots, 0, sizeof(int), h->stream));
   enqueue_linearize(h, 0);
+  ba::launch_pair_records(d, h->stream);  // (pair_obs: k_cov_rhs reads slim records, the iteration keeps none)
   if (h->rel.F > 0) {
     ba::launch_rel_lin(d, h->rel, 0, 1, h->stream);
     ba::launch_rel_gather(d, h->rel, 0, 1, h->stream);

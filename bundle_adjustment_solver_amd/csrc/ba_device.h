@@ -61,6 +61,22 @@ constexpr int kWStride = 12;
 // first P_slim pairs; slim record p lies at double p * kWSlim of the same array W[], i.e.
 // inside the grouped pairs' own 96-byte range, and pair p >= P_slim stays at p * kWStride.
 constexpr int kWSlim = 8;
+// "From the observation" (DevProblem::pair_obs): a slim handle whose groups are all 32 wide
+// (at most kPairObsPoses free poses) and none of them masked keeps NO record of the grouped
+// pairs in the iteration.  {G, w} is a function of the last writer's observation (16 bytes),
+// its camera, the pose and the point at the linearisation point (pair_G_from_obs,
+// ba_device_fn.h): k_lin_grp writes nothing, k_schur_grp<2> and the group role of
+// k_backsub_update fetch that observation and rebuild {G, w}, then {K, X_ij}.  Readers off the
+// hot path (ba_get_pairs, ba_covariance) first have k_pair_records fill the slim records of
+// buffer ctrl->lcur and then run as with the slim form.  Per group piece (LinDesc) and per
+// k_schur_grp workgroup (GrpDesc) one PairObs: obs(il, last slot of pose jj) = o0 + no * il +
+// (sc[jj] & 0xff), through camera sc[jj] >> 8.
+constexpr int kPairObsPoses = 5;
+struct PairObs {
+  int64_t o0;
+  int32_t no;
+  int32_t sc[kPairObsPoses];
+};
 
 struct DevProblem {
   // sizes
@@ -133,6 +149,8 @@ struct DevProblem {
   int n_lm_part;             // entries of lm_part: n_bs_grp + chunk workgroups behind lin_chunk0
   int pair_slim;             // 1: the pairs [0, P_slim) are kept as kWSlim records (see kWSlim)
   int64_t P_slim;            // pairs of the grouped landmarks when pair_slim, else 0
+  int pair_obs;              // 1: the iteration keeps no record of the pairs [0, P_slim) (see PairObs)
+  PairObs *lin_obs, *grp_obs;  // when pair_obs: per lin_desc piece / per grp32 workgroup
   SupDesc *sup_desc;
   uint32_t *sup_lane;  // n_sup*256: lane -> (slot, half, position, lanes per half) of k_schur_lds
   ChunkDesc *chunk_desc;
@@ -259,6 +277,8 @@ void launch_cost(const DevProblem &d, int sel, int64_t begin, hipStream_t s);
 void launch_lin_poses(const DevProblem &d, int sel, hipStream_t s);
 void launch_lin_landmarks(const DevProblem &d, int sel, hipStream_t s);
 void launch_damp_invert(const DevProblem &d, hipStream_t s);
+// pair_obs handles: the slim records of the grouped pairs of buffer ctrl->lcur, from the observations
+void launch_pair_records(const DevProblem &d, hipStream_t s);
 // dense_init + Schur accumulation + finalisation; direct: single GPU, S and rhs are
 // also placed in the dense matrix (no k_scatter); with_init: also reset the factor tiles
 void launch_schur(const DevProblem &d, bool direct, bool with_init, hipStream_t s);

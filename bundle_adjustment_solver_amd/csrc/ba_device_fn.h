@@ -194,6 +194,42 @@ __host__ __device__ __forceinline__ void pair_from_G(const double G[6], const do
     for (int c = 0; c < 3; ++c) K[r * 3 + c] = fma(G[r], wR[c], G[3 + r] * wR[3 + c]);
 }
 
+// The slim record {G, w} of a pair from the observation of its last writer: what k_lin_grp
+// computes for that observation through project() and weight_and_G(), with the operations
+// and the roundings of the kernel's generated code (a sum of three products starts from the
+// rounded MIDDLE product and fuses the first, then the third; "+ t" is an addition of its own;
+// fx (x / z) + cx is one fma, "- u" a subtraction; a row of G fuses f / z * R onto the rounded
+// product with R's third row; both divisions are IEEE divisions), spelled out with fma() like
+// pair_from_G.  The readers of the "from the observation" record form (ba_device.h PairObs)
+// call it in front of pair_from_G; the observation is a valid one (no masked slot).
+__host__ __device__ __forceinline__ void pair_G_from_obs(const double *__restrict__ cam, const double *__restrict__ T,
+                                                         const double X0, const double X1, const double X2,
+                                                         const double u, const double v, const double huber,
+                                                         double G[6], double &w) {
+#pragma clang fp contract(off)
+  double Xij[3], Xc[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    Xij[r] = fma(T[r * 3 + 2], X2, fma(T[r * 3 + 0], X0, T[r * 3 + 1] * X1)) + T[9 + r];
+  const double *Rc = cam + 4;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    Xc[r] = fma(Rc[r * 3 + 2], Xij[2], fma(Rc[r * 3 + 0], Xij[0], Rc[r * 3 + 1] * Xij[1])) + cam[13 + r];
+  const double invz = 1.0 / Xc[2];
+  const double xinvz = Xc[0] * invz, yinvz = Xc[1] * invz;
+  const double r0 = fma(cam[0], xinvz, cam[2]) - u;
+  const double r1 = fma(cam[1], yinvz, cam[3]) - v;
+  const double absr = fabs(r0) + fabs(r1);
+  w = (absr > huber) ? (huber / absr) : 1.0;
+  const double fxinvz = cam[0] * invz, fyinvz = cam[1] * invz;
+  const double nx = -(fxinvz * xinvz), ny = -(fyinvz * yinvz);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    G[c] = fma(fxinvz, Rc[c], nx * Rc[6 + c]);
+    G[3 + c] = fma(fyinvz, Rc[3 + c], ny * Rc[6 + c]);
+  }
+}
+
 // Symmetric 3x3 inverse by diagonally pivoted LDL^T with D pseudo-inverted —
 // the behaviour of Eigen's C.ldlt().solve(I) (reference :854): an all-zero
 // C_i (never-observed landmark) yields Cinv = 0, not NaN.

@@ -433,11 +433,16 @@ __device__ long long g_lg_dbg[64];
 // SLIM: the pair record is {G, w, 0} (ba_device.h kWSlim) instead of {K, X_ij}: four 16-byte
 // pieces per pair instead of six, and K is not formed here at all.
 // per wave: step transposition [64][9] + W image of the step; at the end [14][64]
-template <bool SLIM>
-constexpr int kLgArea = 64 * 9 + 7 * 10 * (SLIM ? kWSlim : kWStride);
-template <bool LDSCAM, bool MASKED, bool SLIM>
+// REC: the record form of the pairs: 0 = {K, X_ij}, 1 = SLIM, 2 = none (ba_device.h PairObs:
+// the readers rebuild {G, w} from the observation): no record is formed or staged, the area
+// is what the sums at the end need.
+template <int REC>
+constexpr int kLgArea = REC == 2 ? 14 * 64 : 64 * 9 + 7 * 10 * (REC == 1 ? kWSlim : kWStride);
+template <bool LDSCAM, bool MASKED, int REC>
 __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel, const int bid, double *red,
                                              double *cams_s, double *smc, int *slot_b, int *slot_e) {
+  constexpr bool SLIM = REC == 1;
+  static_assert(REC != 2 || !MASKED, "a masked piece keeps its records");
 #ifdef BA_LG_DBG
   __shared__ long long lg_s[64];
   const bool lg_on = blockIdx.x == 300 && threadIdx.x == 0;
@@ -497,7 +502,7 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
   double *__restrict__ Wg = d.W[lb];
   double *__restrict__ Cg = d.Cu[lb];
   double *__restrict__ bg = d.b[lb];
-  double *cbw = red + wv * kLgArea<SLIM>;
+  double *cbw = red + wv * kLgArea<REC>;
   double acc[27];
 #pragma unroll
   for (int k = 0; k < 27; ++k) acc[k] = 0.0;
@@ -533,7 +538,7 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
   constexpr int RW = (SLIM ? kWSlim : kWStride) / 2;
   double2 *stgW = (double2 *)(cbw + 64 * 9);
   double2 *stgW_mine = stgW + (ilw * dd + jj) * RW;
-  constexpr int kLgPass = (7 * 10 * RW + 63) / 64;
+  constexpr int kLgPass = REC == 2 ? 1 : (7 * 10 * RW + 63) / 64;
   // A step is software-pipelined against the previous one: the step's terms go to
   // the wave's LDS area at its END; the per-landmark sums and the W image of step
   // st - 1 are READ from LDS at the start of step st (requests in flight during the
@@ -548,11 +553,13 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
 #define LING_FLUSH_ISSUE()                                                          \
   {                                                                                 \
     _Pragma("unroll") for (int u_ = 0; u_ < 8; ++u_) vv[u_] = sum_p[(u_ < no ? u_ : 0) * 9]; \
-    const int nls_ = nl - il0p < nlw ? nl - il0p : nlw;                             \
-    const int n2_ = nls_ * dd * RW;                                                 \
-    dstWp = n2_ > 0 ? (double2 *)(Wg + (size_t)(p0 + (int64_t)il0p * dd) * (2 * RW)) : dumpW; \
-    lastp = n2_ > 0 ? n2_ - 1 : 0;                                                  \
-    _Pragma("unroll") for (int k_ = 0; k_ < kLgPass; ++k_) wvv[k_] = stgW[min(lane + 64 * k_, lastp)]; \
+    if (REC != 2) {                                                                 \
+      const int nls_ = nl - il0p < nlw ? nl - il0p : nlw;                           \
+      const int n2_ = nls_ * dd * RW;                                               \
+      dstWp = n2_ > 0 ? (double2 *)(Wg + (size_t)(p0 + (int64_t)il0p * dd) * (2 * RW)) : dumpW; \
+      lastp = n2_ > 0 ? n2_ - 1 : 0;                                                \
+      _Pragma("unroll") for (int k_ = 0; k_ < kLgPass; ++k_) wvv[k_] = stgW[min(lane + 64 * k_, lastp)]; \
+    }                                                                               \
   }
   // per-landmark sums in insertion order (one lane per (landmark, value)) and the W
   // image -> global.  A FIXED number of store instructions, none under a branch (a
@@ -567,7 +574,9 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
     const int ils_ = il0p + sum_li;                                                 \
     double *dst_ = (sum_on && ils_ < nl) ? sum_g + (size_t)ils_ * sum_stride : dumpC; \
     *dst_ = sum_neg ? -sacc_ : sacc_;                                               \
-    _Pragma("unroll") for (int k_ = 0; k_ < kLgPass; ++k_) dstWp[min(lane + 64 * k_, lastp)] = wvv[k_]; \
+    if (REC != 2) {                                                                 \
+      _Pragma("unroll") for (int k_ = 0; k_ < kLgPass; ++k_) dstWp[min(lane + 64 * k_, lastp)] = wvv[k_]; \
+    }                                                                               \
   }
 #define LING_STEP(CUR, NXT2)                                                        \
   {                                                                                 \
@@ -618,7 +627,8 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
       /* B_ji = w Q^T R of the pair's last-inserted observation (reference :826), */ \
       /* compact: K = w G^T R and X_ij (ba_device.h kWStride); SLIM: G and w, the */ \
       /* zero record for a slot without an observation (ba_device.h kWSlim)       */ \
-      if (SLIM) {                                                                   \
+      if (REC == 2) {                                                               \
+      } else if (SLIM) {                                                            \
         _Pragma("unroll") for (int e_ = 0; e_ < 6; ++e_) kk[e_] = (!MASKED || valid_) ? G[e_] : 0.0; \
         kk[6] = w;                                                                  \
         kk[7] = 0.0;                                                                \
@@ -653,7 +663,7 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
     {                                                                               \
       double *cb = cbw + lane * 9;                                                  \
       _Pragma("unroll") for (int e_ = 0; e_ < 9; ++e_) cb[e_] = cbv[e_];            \
-      if (wr_ && lane_on) {                                                         \
+      if (REC != 2 && wr_ && lane_on) {                                             \
         _Pragma("unroll") for (int r = 0; r < RW; ++r)                              \
           stgW_mine[r] = make_double2(kk[2 * r], kk[2 * r + 1]);                    \
       }                                                                             \
@@ -699,7 +709,7 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
       double sacc = 0.0;
       for (int w4 = 0; w4 < 4; ++w4)
         for (int li = 0; li < nlw; ++li)
-          for (int q = sb; q < se; ++q) sacc += red[w4 * kLgArea<SLIM> + k * 64 + li * no + q];
+          for (int q = sb; q < se; ++q) sacc += red[w4 * kLgArea<REC> + k * 64 + li * no + q];
       d.Apart2[(size_t)(apart0 + pj) * 27 + e] = sacc;
     }
   }
@@ -709,13 +719,13 @@ __device__ __forceinline__ void lin_grp_body(const DevProblem &d, const int sel,
 #endif
 }
 
-template <bool LDSCAM, bool MASKED, bool SLIM>
+template <bool LDSCAM, bool MASKED, int REC>
 __global__ __launch_bounds__(kBlock, 2) void k_lin_grp(DevProblem d, int sel, int piece0) {
-  __shared__ __attribute__((aligned(16))) double red[4 * kLgArea<SLIM>];
+  __shared__ __attribute__((aligned(16))) double red[4 * kLgArea<REC>];
   __shared__ double cams_s[kCamLds * 16];
   __shared__ double smc[4];
   __shared__ int slot_b[kGrpMaxPoses], slot_e[kGrpMaxPoses];  // pattern slots of pose jj of the group
-  lin_grp_body<LDSCAM, MASKED, SLIM>(d, sel, piece0 + blockIdx.x, red, cams_s, smc, slot_b, slot_e);
+  lin_grp_body<LDSCAM, MASKED, REC>(d, sel, piece0 + blockIdx.x, red, cams_s, smc, slot_b, slot_e);
 }
 
 // Damping and landmark inverse (reference :846-856): Cinv_i = (C_i with its
@@ -1225,8 +1235,14 @@ __device__ long long g_grp_dbg[256];
 // SLIM: the pair records are {G, w, 0} (ba_device.h kWSlim): the ring holds four 16-byte
 // pieces and the landmark's point, the lane's pose is loaded once per workgroup, and the
 // lane rebuilds {K, X_ij} (pair_from_G) before it proceeds as with the 96-byte record.
-template <int NT, bool SLIM>
+// REC = 2 (NT = 2 only; ba_device.h PairObs): no record at all — the ring holds the uv of the
+// pair's last observation, the lane's camera is read from the LDS table at its use (LDSCAM;
+// 1 KiB, which still fits two workgroups per CU) or from the global table, and the lane
+// rebuilds {G, w} (pair_G_from_obs) in front of pair_from_G.
+template <int NT, int REC, bool LDSCAM = true>
 __global__ __launch_bounds__(kBlock, (NT == 2 && BA_GRP_KRW <= 24) ? 3 : 2) void k_schur_grp(DevProblem d, const DevProblem::GrpDesc *grps) {
+  constexpr bool OBS = REC == 2, SLIM = REC >= 1;  // (OBS proceeds as SLIM once {G, w} is there)
+  static_assert(!OBS || NT == 2, "from the observation: 32-wide groups only");
   constexpr int TW = 16 * NT;             // padded width: 6 d (+ 1 for b) <= TW
 #ifndef BA_GRP_KRW
 #define BA_GRP_KRW 36
@@ -1243,6 +1259,7 @@ __global__ __launch_bounds__(kBlock, (NT == 2 && BA_GRP_KRW <= 24) ? 3 : 2) void
   __shared__ __attribute__((aligned(16))) double VA[4][IMG];
   __shared__ __attribute__((aligned(16))) double WB[4][IMG];
   static_assert(IMG >= 256, "the final reduction uses VA as 4 x 256 doubles");
+  __shared__ double cams_s[(OBS && LDSCAM) ? kCamLds * 16 : 1];
 #ifdef BA_GRP_DBG
   __shared__ long long gdbg_s[256];
   const bool gdbg_on = blockIdx.x == 600 && threadIdx.x == 0;
@@ -1275,7 +1292,7 @@ __global__ __launch_bounds__(kBlock, (NT == 2 && BA_GRP_KRW <= 24) ? 3 : 2) void
   // pose (24), and the second buffer bought no lead: a stage starts by waiting for every
   // request in flight, so its operands had one matrix phase to arrive either way.
   constexpr int RD = (SLIM && NT == 4) ? 1 : 2;  // ring depth
-  constexpr int RW = (SLIM ? kWSlim : kWStride) / 2;  // 16-byte pieces of a pair record
+  constexpr int RW = OBS ? 1 : (SLIM ? kWSlim : kWStride) / 2;  // 16-byte pieces of a pair record (OBS: the uv)
   double2 rw[2][6], rc[2][3];
   double rb[2][3], rx[2][3];
   // SLIM: this lane's pose (a lane constant) and the points of the linearisation.
@@ -1286,11 +1303,29 @@ __global__ __launch_bounds__(kBlock, (NT == 2 && BA_GRP_KRW <= 24) ? 3 : 2) void
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = Tp[k];
   }
+  // OBS: where this lane's observations lie (il-th landmark of the group: uvp[il * ono]) and
+  // its camera; jj < d <= kPairObsPoses in every lane
+  const double2 *__restrict__ uvp = nullptr;
+  int ono = 0, ocam = 0;
+  double huber = 0.0;
+  if (OBS) {
+    const PairObs *po = d.grp_obs + blockIdx.x;
+    const int sc = po->sc[jj];
+    ono = po->no;
+    uvp = d.obs_uv + po->o0 + (sc & 0xff);
+    ocam = sc >> 8;
+    huber = d.ctrl->huber;
+    if (LDSCAM) {
+      stage_cams(d, cams_s);
+      __syncthreads();
+    }
+  }
 #define GRP_PREFETCH(B, ch_)                                                        \
   {                                                                                 \
     const int c0_ = (ch_) * nlw;                                                    \
     const bool on_ = il < min(nlw, gd.nl - c0_);                                    \
-    const double2 *wp_ = (const double2 *)(Wg + (size_t)(gd.p0 + (int64_t)c0_ * dd + (on_ ? lane : 0)) * (2 * RW)); \
+    const double2 *wp_ = OBS ? uvp + (int64_t)(c0_ + (on_ ? il : 0)) * ono          \
+                             : (const double2 *)(Wg + (size_t)(gd.p0 + (int64_t)c0_ * dd + (on_ ? lane : 0)) * (2 * RW)); \
     const int lm_ = gd.l0 + c0_ + (on_ ? il : 0);                                   \
     const double2 *cp_ = (const double2 *)(Cug + (size_t)lm_ * 6);                  \
     _Pragma("unroll") for (int k_ = 0; k_ < RW; ++k_) rw[B][k_] = wp_[k_];          \
@@ -1315,7 +1350,12 @@ __global__ __launch_bounds__(kBlock, (NT == 2 && BA_GRP_KRW <= 24) ? 3 : 2) void
          VALU shares its pipe with the fp64 MFMA on this part, every instruction counts) */ \
       _Pragma("clang fp contract(fast)")                                            \
       double k9[9], xij[3];                                                         \
-      if (SLIM) {                                                                   \
+      if (OBS) {                                                                    \
+        double cam_[16], G_[6], w_;                                                 \
+        load_cam<LDSCAM>(d, cams_s, ocam, cam_);                                    \
+        pair_G_from_obs(cam_, T, rx[B][0], rx[B][1], rx[B][2], rw[B][0].x, rw[B][0].y, huber, G_, w_); \
+        pair_from_G(G_, w_, T, rx[B][0], rx[B][1], rx[B][2], k9, xij);              \
+      } else if (SLIM) {                                                            \
         const double G_[6] = {rw[B][0].x, rw[B][0].y, rw[B][1].x, rw[B][1].y, rw[B][2].x, rw[B][2].y}; \
         pair_from_G(G_, rw[B][3].x, T, rx[B][0], rx[B][1], rx[B][2], k9, xij);      \
       } else {                                                                      \
@@ -2135,9 +2175,13 @@ __device__ __forceinline__ void backsub_chunk_body(const DevProblem &d, const in
 // SLIM: the records are {G, w, 0} (ba_device.h kWSlim), four 16-byte pieces per pair; the
 // lane's pose is one more lane constant, the point comes from the block's landmark image
 // and the lane rebuilds {K, X_ij} (pair_from_G) before it forms u as with the 96-byte record.
-template <bool SLIM>
+// REC = 2 (ba_device.h PairObs): no record — a step requests, per lane, the uv of the pair's
+// last observation (16 bytes; the camera is one more lane constant) and the lane rebuilds
+// {G, w} (pair_G_from_obs) in front of pair_from_G; nothing goes through the W image.
+template <int REC>
 __device__ __forceinline__ void backsub_grp_body(const DevProblem &d, const int piece, const int part, double *lds,
                                                  double *sm) {
+  constexpr bool OBS = REC == 2, SLIM = REC >= 1;  // (OBS proceeds as SLIM once {G, w} is there)
   const DevProblem::LinDesc *gp = d.lin_desc + piece;
   const int64_t p0 = gp->p0;
   const int l0 = gp->l0, nl = gp->nl, dd = gp->d;
@@ -2167,6 +2211,20 @@ __device__ __forceinline__ void backsub_grp_body(const DevProblem &d, const int 
     const double *Tp = d.poses[cur] + (size_t)pose * 12;
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = Tp[k];
+  }
+  // OBS: where this lane's observations lie (landmark il of the piece: uvp[il * ono]), its camera
+  const double2 *__restrict__ uvp = d.obs_uv;
+  int ono = 0;
+  double cam[16], huber = 0.0;
+  if (OBS) {
+    const PairObs *po = d.lin_obs + piece;
+    const int sc = po->sc[jj < kPairObsPoses ? jj : 0];  // (dd == 0: every lane is its own "pose")
+    ono = po->no;
+    uvp = d.obs_uv + po->o0 + (sc & 0xff);
+    huber = d.ctrl->huber;
+    const double *cp = d.cams + (size_t)(sc >> 8) * 16;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) cam[k] = cp[k];
   }
   double *Wim = lds + wv * kBgArea;  // 64 * 2 RW: W image of the step
   double *Us = Wim + 64 * 2 * RW;    // 64 * 3: u per pair
@@ -2211,10 +2269,14 @@ __device__ __forceinline__ void backsub_grp_body(const DevProblem &d, const int 
     const int ilb_ = nls_ > 0 ? il0_ : 0;                                           \
     const int lml_ = max(0, nls_ - 1);                                              \
     const double2 *src_ = Wg2 + (dd > 0 ? (size_t)(p0 + (int64_t)ilb_ * dd) * RW : (size_t)0); \
-    R##0 = src_[min(lane, last_)];                                                  \
-    R##1 = src_[min(lane + 64, last_)];                                             \
-    R##2 = src_[min(lane + 128, last_)];                                            \
-    R##3 = src_[min(lane + 192, last_)];                                            \
+    if (OBS) {                                                                      \
+      R##0 = uvp[(int64_t)(ilb_ + min(ilw, lml_)) * ono];                           \
+    } else {                                                                        \
+      R##0 = src_[min(lane, last_)];                                                \
+      R##1 = src_[min(lane + 64, last_)];                                           \
+      R##2 = src_[min(lane + 128, last_)];                                          \
+      R##3 = src_[min(lane + 192, last_)];                                          \
+    }                                                                               \
     if (!SLIM) {                                                                    \
       R##4 = src_[min(lane + 256, last_)];                                          \
       R##5 = src_[min(lane + 320, last_)];                                          \
@@ -2239,10 +2301,13 @@ __device__ __forceinline__ void backsub_grp_body(const DevProblem &d, const int 
     /* (the two instances must stay two code paths) */                              \
     asm volatile("; k_backsub_update group step " TAG);                             \
     /* registers -> the wave's LDS images (linear) */                               \
-    ((double2 *)Wim)[lane] = R##0;                                                  \
-    ((double2 *)Wim)[lane + 64] = R##1;                                             \
-    ((double2 *)Wim)[lane + 128] = R##2;                                            \
-    ((double2 *)Wim)[lane + 192] = R##3;                                            \
+    const double2 uv_ = R##0;                                                       \
+    if (!OBS) {                                                                     \
+      ((double2 *)Wim)[lane] = R##0;                                                \
+      ((double2 *)Wim)[lane + 64] = R##1;                                           \
+      ((double2 *)Wim)[lane + 128] = R##2;                                          \
+      ((double2 *)Wim)[lane + 192] = R##3;                                          \
+    }                                                                               \
     if (!SLIM) {                                                                    \
       ((double2 *)Wim)[lane + 256] = R##4;                                          \
       ((double2 *)Wim)[lane + 320] = R##5;                                          \
@@ -2254,12 +2319,17 @@ __device__ __forceinline__ void backsub_grp_body(const DevProblem &d, const int 
     BSG_WAVE_SYNC()                                                                 \
     if (SLIM && lane_on) {                                                          \
       /* {K, X_ij} from {G, w}, the lane's pose and the landmark's point, then as below */ \
-      const double2 *w2 = (const double2 *)(Wim + lane * kWSlim);                   \
-      const double2 g01 = w2[0], g23 = w2[1], g45 = w2[2], w_ = w2[3];              \
-      const double G_[6] = {g01.x, g01.y, g23.x, g23.y, g45.x, g45.y};              \
       const double *Xi_ = Lm + sb * nlwb * 12 + nlwb * 9 + ilw * 3;                 \
-      double k_[9], x_[3];                                                          \
-      pair_from_G(G_, w_.x, T, Xi_[0], Xi_[1], Xi_[2], k_, x_);                     \
+      double G_[6], gw_, k_[9], x_[3];                                              \
+      if (OBS) {                                                                    \
+        pair_G_from_obs(cam, T, Xi_[0], Xi_[1], Xi_[2], uv_.x, uv_.y, huber, G_, gw_); \
+      } else {                                                                      \
+        const double2 *w2 = (const double2 *)(Wim + lane * kWSlim);                 \
+        const double2 g01 = w2[0], g23 = w2[1], g45 = w2[2], w_ = w2[3];            \
+        G_[0] = g01.x; G_[1] = g01.y; G_[2] = g23.x; G_[3] = g23.y; G_[4] = g45.x; G_[5] = g45.y; \
+        gw_ = w_.x;                                                                 \
+      }                                                                             \
+      pair_from_G(G_, gw_, T, Xi_[0], Xi_[1], Xi_[2], k_, x_);                      \
       const double X0 = x_[0], X1 = x_[1], X2 = x_[2];                              \
       const double e0 = xj[0] + (xj[4] * X2 - xj[5] * X1);                          \
       const double e1 = xj[1] + (xj[5] * X0 - xj[3] * X2);                          \
@@ -2373,8 +2443,9 @@ __device__ __forceinline__ void backsub_grp_body(const DevProblem &d, const int 
 // of lm_part = blockIdx - kPoseGrid.
 // GROUPS = false: problems without covisibility groups (chunk role only): the LDS of
 // the chunk role alone and four workgroups per CU instead of two.
-// SLIM (with GROUPS only): the record form of the grouped pairs, the host's choice.
-template <bool GROUPS, bool SLIM>
+// REC (with GROUPS only): the record form of the grouped pairs (0: {K, X_ij}, 1: slim, 2: none,
+// see backsub_grp_body), the host's choice.
+template <bool GROUPS, int REC>
 __global__ __launch_bounds__(kBlock, GROUPS ? 2 : 4) void k_backsub_update(DevProblem d) {
   __shared__ __attribute__((aligned(16))) double lds[GROUPS ? kBsLds : kSchurPairs * (kWStride + 6 + 3)];
   __shared__ double sm[8];
@@ -2396,9 +2467,38 @@ __global__ __launch_bounds__(kBlock, GROUPS ? 2 : 4) void k_backsub_update(DevPr
     return;
   }
   if (GROUPS && part < d.n_bs_grp)
-    backsub_grp_body<SLIM>(d, part, part, lds, sm);
+    backsub_grp_body<REC>(d, part, part, lds, sm);
   else
     backsub_chunk_body(d, part - d.n_bs_grp, part, lds, sm, recs);
+}
+
+// pair_obs handles (ba_device.h PairObs): the slim records {G, w, 0} of the grouped pairs of
+// block buffer ctrl->lcur, rebuilt from the observations at the accepted point — what
+// k_lin_grp's slim form holds there.  For the readers off the hot path (ba_get_pairs,
+// ba_covariance), launched on their demand.  One workgroup per group piece, one thread per pair.
+__global__ __launch_bounds__(kBlock) void k_pair_records(DevProblem d) {
+  const DevProblem::LinDesc *gp = d.lin_desc + blockIdx.x;
+  const PairObs *po = d.lin_obs + blockIdx.x;
+  const int dd = gp->d, np = gp->nl * dd;
+  const double huber = d.ctrl->huber;
+  const double *__restrict__ poses = d.poses[d.ctrl->cur];
+  const double *__restrict__ pts = d.pts[d.ctrl->cur];
+  double *__restrict__ Wg = d.W[d.ctrl->lcur];
+  for (int q = threadIdx.x; q < np; q += kBlock) {
+    const int il = q / dd, jj = q - il * dd;
+    const int sc = po->sc[jj];
+    const double2 uv = d.obs_uv[po->o0 + (int64_t)il * po->no + (sc & 0xff)];
+    const double *cam = d.cams + (size_t)(sc >> 8) * 16;
+    const double *T = poses + (size_t)d.pair_pose[gp->p0 + jj] * 12;
+    const double *X = pts + (size_t)(gp->l0 + il) * 3;
+    double G[6], w;
+    pair_G_from_obs(cam, T, X[0], X[1], X[2], uv.x, uv.y, huber, G, w);
+    double *o = Wg + (size_t)(gp->p0 + q) * kWSlim;
+#pragma unroll
+    for (int e = 0; e < 6; ++e) o[e] = G[e];
+    o[6] = w;
+    o[7] = 0.0;
+  }
 }
 
 #ifdef BA_BS_DBG
@@ -2847,15 +2947,18 @@ void launch_cost(const DevProblem &d, int sel, int64_t begin, hipStream_t s) {
 void launch_lin_landmarks(const DevProblem &d, int sel, hipStream_t s) {
   if (d.lin_chunk0 > 0) {  // covisibility groups: landmark and pose side in one pass
     const int n_plain = d.n_lin_plain, n_mask = d.n_lin_desc - d.n_lin_plain;
-#define BA_LIN_GRP_LAUNCH(LDS, SLIM)                                                                                  \
+#define BA_LIN_GRP_LAUNCH(LDS, REC)                                                                                   \
   {                                                                                                                   \
-    if (n_plain > 0) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<LDS, false, SLIM>), dim3(n_plain), dim3(kBlock), s, d, sel, 0);   \
-    if (n_mask > 0) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<LDS, true, SLIM>), dim3(n_mask), dim3(kBlock), s, d, sel, n_plain); \
+    if (n_plain > 0) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<LDS, false, REC>), dim3(n_plain), dim3(kBlock), s, d, sel, 0);    \
+    if (n_mask > 0) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<LDS, true, REC>), dim3(n_mask), dim3(kBlock), s, d, sel, n_plain); \
   }
+    // (pair_obs: no masked piece, ba_finalize; no record is written)
     if (d.n_cam <= kCamLds) {
-      if (d.pair_slim) BA_LIN_GRP_LAUNCH(true, true) else BA_LIN_GRP_LAUNCH(true, false)
+      if (d.pair_obs) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<true, false, 2>), dim3(n_plain), dim3(kBlock), s, d, sel, 0);
+      else if (d.pair_slim) BA_LIN_GRP_LAUNCH(true, 1) else BA_LIN_GRP_LAUNCH(true, 0)
     } else {
-      if (d.pair_slim) BA_LIN_GRP_LAUNCH(false, true) else BA_LIN_GRP_LAUNCH(false, false)
+      if (d.pair_obs) BA_LAUNCH(K_LIN_GRP, (k_lin_grp<false, false, 2>), dim3(n_plain), dim3(kBlock), s, d, sel, 0);
+      else if (d.pair_slim) BA_LIN_GRP_LAUNCH(false, 1) else BA_LIN_GRP_LAUNCH(false, 0)
     }
 #undef BA_LIN_GRP_LAUNCH
   }
@@ -2883,6 +2986,9 @@ void launch_damp_invert(const DevProblem &d, hipStream_t s) {
   // the covisibility-group kernel and the back-substitution invert in registers
   if (d.M > 0 && (d.n_sup > 0 || d.n_tchunk > 0))
     BA_LAUNCH(K_DAMP_INVERT, k_damp_invert, dim3(cdiv(d.M, kBlock)), dim3(kBlock), s, d, 0);
+}
+void launch_pair_records(const DevProblem &d, hipStream_t s) {
+  if (d.pair_obs && d.n_lin_desc > 0) hipLaunchKernelGGL(k_pair_records, dim3(d.n_lin_desc), dim3(kBlock), 0, s, d);
 }
 // reader variant: also stores the damped C_i (ba_get_C)
 void launch_damp_invert_export(const DevProblem &d, hipStream_t s) {
@@ -2912,18 +3018,23 @@ extern "C" int ba_debug_read(long long *out) {
 #endif
 void launch_schur_accumulate(const DevProblem &d, hipStream_t s) {
   // (the record form of the grouped pairs is the host's choice: a template parameter)
-  if (d.pair_slim) {
+  if (d.pair_obs) {  // (32-wide groups only: ba_finalize)
+    if (d.n_grp32 > 0 && d.n_cam <= kCamLds)
+      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<2, 2, true>), dim3(d.n_grp32), dim3(kBlock), s, d, d.grp32);
+    else if (d.n_grp32 > 0)
+      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<2, 2, false>), dim3(d.n_grp32), dim3(kBlock), s, d, d.grp32);
+  } else if (d.pair_slim) {
     if (d.n_grp32 > 0)
-      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<2, true>), dim3(d.n_grp32), dim3(kBlock), s, d, d.grp32);
+      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<2, 1>), dim3(d.n_grp32), dim3(kBlock), s, d, d.grp32);
     if (d.n_grp64 > 0)
-      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<4, true>), dim3(d.n_grp64), dim3(kBlock), s, d, d.grp64);
+      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<4, 1>), dim3(d.n_grp64), dim3(kBlock), s, d, d.grp64);
     if (d.n_grp128 > 0)
       BA_LAUNCH(K_SCHUR_GRP, k_schur_grp_wide<true>, dim3(d.n_grp128), dim3(kBlock), s, d, d.grp128);
   } else {
     if (d.n_grp32 > 0)
-      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<2, false>), dim3(d.n_grp32), dim3(kBlock), s, d, d.grp32);
+      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<2, 0>), dim3(d.n_grp32), dim3(kBlock), s, d, d.grp32);
     if (d.n_grp64 > 0)
-      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<4, false>), dim3(d.n_grp64), dim3(kBlock), s, d, d.grp64);
+      BA_LAUNCH(K_SCHUR_GRP, (k_schur_grp<4, 0>), dim3(d.n_grp64), dim3(kBlock), s, d, d.grp64);
     if (d.n_grp128 > 0)
       BA_LAUNCH(K_SCHUR_GRP, k_schur_grp_wide<false>, dim3(d.n_grp128), dim3(kBlock), s, d, d.grp128);
   }
@@ -2957,12 +3068,14 @@ void launch_scatter(const DevProblem &d, hipStream_t s) {
 void launch_backsub_update(const DevProblem &d, hipStream_t s, bool zero_tiles) {
   // pose workgroups, covisibility-group pieces, chunk workgroups, [factor-tile reset] (see the kernel)
   const dim3 grid(kPoseGrid + d.n_lm_part + (zero_tiles ? d.n_zt : 0));
-  if (d.n_bs_grp > 0 && d.pair_slim)
-    BA_LAUNCH(K_BACKSUB_UPDATE, (k_backsub_update<true, true>), grid, dim3(kBlock), s, d);
+  if (d.n_bs_grp > 0 && d.pair_obs)
+    BA_LAUNCH(K_BACKSUB_UPDATE, (k_backsub_update<true, 2>), grid, dim3(kBlock), s, d);
+  else if (d.n_bs_grp > 0 && d.pair_slim)
+    BA_LAUNCH(K_BACKSUB_UPDATE, (k_backsub_update<true, 1>), grid, dim3(kBlock), s, d);
   else if (d.n_bs_grp > 0)
-    BA_LAUNCH(K_BACKSUB_UPDATE, (k_backsub_update<true, false>), grid, dim3(kBlock), s, d);
+    BA_LAUNCH(K_BACKSUB_UPDATE, (k_backsub_update<true, 0>), grid, dim3(kBlock), s, d);
   else
-    BA_LAUNCH(K_BACKSUB_UPDATE, (k_backsub_update<false, false>), grid, dim3(kBlock), s, d);
+    BA_LAUNCH(K_BACKSUB_UPDATE, (k_backsub_update<false, 0>), grid, dim3(kBlock), s, d);
 }
 
 void launch_scalars(const DevProblem &d, int cost_src, hipStream_t s) {

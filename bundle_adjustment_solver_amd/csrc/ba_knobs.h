@@ -39,6 +39,7 @@ struct RunKnobs {
 // How the blocks are laid out in device memory.
 struct LayoutKnobs {
   bool pair_slim = true;  // BA_PAIR_SLIM=0: the pairs of k_lin_grp's groups keep the 96-byte record {K, X_ij}, not {G, w}
+  bool pair_obs = true;   // BA_PAIR_OBS=0: no "from the observation" form (ba_device.h PairObs): the slim record stays
 };
 
 struct Knobs {
@@ -80,6 +81,8 @@ inline Knobs Knobs::from_env() {
   {
     const char *v = getenv("BA_PAIR_SLIM");
     k.layout.pair_slim = !(v && v[0] == '0');
+    const char *o = getenv("BA_PAIR_OBS");
+    k.layout.pair_obs = !(o && o[0] == '0');
   }
   return k;
 }

@@ -662,6 +662,24 @@ class BaProblem:
         check(self.lib.ba_get_pair_record_info(self.h, v), "ba_get_pair_record_info")
         return dict(slim_pairs=int(v[0]), pairs=int(v[1]))
 
+    def get_pair_form(self):
+        """Record form of the grouped pairs: 0 = 96-byte, 1 = slim {G, w}, 2 = from the
+        observation (no record in the iteration)."""
+        f = self.lib.ba_get_pair_form(self.h)
+        if f < 0:
+            check(f, "ba_get_pair_form")
+        return int(f)
+
+    def get_slim_records(self):
+        """The slim records of the grouped pairs as the device holds them (form 2: filled on
+        demand), with pose, landmark, camera and uv of each pair's last writer."""
+        n = self.get_pair_record_info()["slim_pairs"]
+        pose, lm, cam = (np.zeros(n, np.int32) for _ in range(3))
+        uv, rec = np.zeros((n, 2)), np.zeros((n, 8))
+        check(self.lib.ba_get_slim_records(self.h, _ip(pose), _ip(lm), _ip(cam), _dp(uv), _dp(rec)),
+              "ba_get_slim_records")
+        return dict(pose=pose, lm=lm, cam=cam, uv=uv, rec=rec)
+
     def get_mask_info(self):
         """Superset (masked) covisibility groups of this shard."""
         v = (C.c_int64 * 4)()

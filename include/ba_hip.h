@@ -338,6 +338,21 @@ int ba_get_lin_info(ba_handle *h, int64_t out4[4]);
  * the covisibility groups, when k_lin_grp linearises them and BA_PAIR_SLIM is not 0), all
  * pairs, padded ones included }.  The others keep the 96-byte record {K, X_ij}. */
 int ba_get_pair_record_info(ba_handle *h, int64_t out2[2]);
+/* The record form of the grouped pairs that this handle took at ba_finalize: 0 = the 96-byte
+ * record, 1 = the slim record {G, w}, 2 = "from the observation": the iteration keeps no
+ * record of them, the group kernels rebuild {G, w} from the observation of the pair's last
+ * writer (slim handles whose groups are all 32 wide and unmasked; BA_PAIR_OBS=0 keeps 1). */
+int ba_get_pair_form(ba_handle *h);
+/* The slim records rec8 (8 doubles each) of the first out2[0] pairs of
+ * ba_get_pair_record_info as the device holds them (form 2: as k_pair_records fills them on
+ * demand), with each pair's pose and point (the caller's indices) and, for the pairs of unmasked
+ * groups, the camera and uv of its last writer.  Any output may be NULL. */
+int ba_get_slim_records(ba_handle *h, int32_t *pose, int32_t *lm, int32_t *cam, double *uv2, double *rec8);
+/* Host side of form 2, no device involved: rec8 = {G, w, 0} of one observation from its
+ * camera (16 doubles), the pose T12, the point X3, uv2 and the Huber threshold, with the
+ * bits k_lin_grp computes for that observation. */
+void ba_pair_G_from_obs(const double *cam16, const double *T12, const double *X3, const double *uv2, double huber,
+                        double *rec8);
 
 /* Superset ("masked") covisibility groups — landmarks of one pose span whose
  * observation patterns differ (occlusion, image borders, track loss) share the UNION
