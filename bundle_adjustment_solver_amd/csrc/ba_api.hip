@@ -640,10 +640,10 @@ int upload_relative(ba_handle *h) {
   const int n_part = (int)((F + ba::kRelFpb - 1) / ba::kRelFpb);
   if (h->upload(R, &jk, pl.rel_jk.data(), F) || h->upload(R, &val, h->rel_val) || h->upload(R, &pptr, pl.rel_pptr) ||
       h->upload(R, &plist, pl.rel_plist) || h->upload(R, &blk, pl.rel_blk) || h->upload(R, &bptr, pl.rel_bptr) ||
-      h->upload(R, &blist, pl.rel_blist) || h->dalloc(R, &r.scr[0], F * ba::kRelScrDoubles) ||
-      h->dalloc(R, &r.scr[1], F * ba::kRelScrDoubles) || h->dalloc(R, &r.part, (size_t)2 * n_part))
+      h->upload(R, &blist, pl.rel_blist) || h->dalloc(R, &r.scr[0], F * ba::kRelScr) ||
+      h->dalloc(R, &r.scr[1], F * ba::kRelScr) || h->dalloc(R, &r.part, (size_t)2 * n_part))
     return -1;
-  for (int k = 0; k < 2; ++k) HIP_TRY(hipMemset(r.scr[k], 0, F * ba::kRelScrDoubles * sizeof(double)));
+  for (int k = 0; k < 2; ++k) HIP_TRY(hipMemset(r.scr[k], 0, F * ba::kRelScr * sizeof(double)));
   HIP_TRY(hipMemset(r.part, 0, (size_t)2 * n_part * sizeof(double)));
   r.F = (int)F;
   r.nblk = (int)pl.rel_blk.size();
@@ -655,7 +655,7 @@ int upload_relative(ba_handle *h) {
   r.blk = blk;
   r.bptr = bptr;
   r.blist = blist;
-  h->rel_bytes = F * (16 + ba::kRelVal * 8 + 2 * ba::kRelScrDoubles * 8) + (pl.rel_pptr.size() + pl.rel_plist.size() +
+  h->rel_bytes = F * (16 + ba::kRelVal * 8 + 2 * ba::kRelScr * 8) + (pl.rel_pptr.size() + pl.rel_plist.size() +
                  pl.rel_blk.size() + pl.rel_bptr.size() + pl.rel_blist.size()) * 4 + (size_t)2 * n_part * 8;
   return 0;
 }

@@ -39,7 +39,8 @@
 //
 // Relative-pose factors per problem (ba_batch_set_relative): r = se3_log(T_j T_k^-1 Z^-1)
 // against a measurement Z of T_j T_k^-1 with a 6x6 information matrix, Jacobians of first order
-// (I and -Ad(T_j T_k^-1)), no robust weight.  Their blocks depend on the poses and are rebuilt
+// (I and -Ad(T_j T_k^-1)), no robust weight; the factor is defined once for all three paths, on
+// the device in ba_rel_fn.h and on the host in ba_rel_host.h.  Their blocks depend on the poses and are rebuilt
 // per linearisation into global scratch (batch_rel_lin / batch_rel_offdiag / batch_rel_cross /
 // batch_rel_cost); nothing per factor lives in LDS.  Each kernel exists with and without that
 // code; this file compiles the instances without, which a batch without factors launches, and
@@ -56,6 +57,7 @@
 #include <vector>
 
 #include "ba_batch_kernels.h"
+#include "ba_rel_host.h"
 
 // ===========================================================================================
 // host side
@@ -255,24 +257,21 @@ int relative_validate(const char *who, int B, NP n_pose_of, FX fixed, const int3
   if (rel_off[0] != 0) return fail(w + "rel_off[0] must be 0 (problem 0)");
   for (int p = 0; p < B; ++p)
     if (rel_off[p + 1] < rel_off[p]) return fail(w + "rel_off must not decrease (problem " + std::to_string(p) + ")");
-  if (rel_off[B] > 0 && (!rel_j || !rel_k || !Z12 || !Omega36)) {
-    int p = 0;
-    while (rel_off[p + 1] == 0) ++p;  // the first problem with a factor
-    return fail(w + "null factor array (problem " + std::to_string(p) + ", factor 0)");
+  // the rules of a factor are relative_validate_host's, per problem with factors (the first reports a null array)
+  std::vector<uint8_t> fx;
+  std::string err;
+  for (int p = 0; p < B; ++p) {
+    const int64_t f0 = rel_off[p];
+    if (rel_off[p + 1] == f0) continue;
+    const int np = n_pose_of(p);
+    fx.resize((size_t)np);
+    for (int q = 0; q < np; ++q) fx[q] = fixed(p, q) ? 1 : 0;
+    auto at = [f0](const auto *a, int per) { return a ? a + per * f0 : a; };
+    const int what = ba::kRelPairs | ba::kRelValues | ba::kRelNoPoseOk;
+    if (ba::relative_validate_host(what, np, fx.data(), rel_off[p + 1] - f0, at(rel_j, 1), at(rel_k, 1), at(Z12, 12),
+                                   at(Omega36, 36), &err, "problem " + std::to_string(p) + ", "))
+      return fail(w + err);
   }
-  for (int p = 0; p < B; ++p)
-    for (int f = rel_off[p]; f < rel_off[p + 1]; ++f) {
-      const std::string at = " (problem " + std::to_string(p) + ", factor " + std::to_string(f - rel_off[p]) + ")";
-      const int j = rel_j[f], k = rel_k[f], np = n_pose_of(p);
-      if (j < 0 || j >= np) return fail(w + "pose j = " + std::to_string(j) + " out of range" + at);
-      if (k < 0 || k >= np) return fail(w + "pose k = " + std::to_string(k) + " out of range" + at);
-      if (j == k) return fail(w + "j == k: a factor needs two distinct poses" + at);
-      if (fixed(p, j) && fixed(p, k)) return fail(w + "both poses are fixed" + at);
-      for (int e = 0; e < 12; ++e)
-        if (!std::isfinite(Z12[(int64_t)12 * f + e])) return fail(w + "Z is not finite" + at);
-      for (int e = 0; e < 36; ++e)
-        if (!std::isfinite(Omega36[(int64_t)36 * f + e])) return fail(w + "Omega is not finite" + at);
-    }
   return 0;
 }
 
@@ -627,8 +626,7 @@ int ba_batch_set_relative(ba_batch *b, const int32_t *rel_off, const int32_t *re
   std::vector<double> Zs, Om;
   std::vector<int32_t> pptr, plist, bptr, blist;
   std::vector<int2> blk;
-  std::vector<std::vector<int32_t>> per_pose, per_blk;
-  std::vector<int32_t> blk_of;  // N x N: block of the pair (hi, lo), or -1
+  ba::RelLists l;
   int64_t n_on = 0;
   for (int p = 0; p < B; ++p) {
     const ba::BatchProb &P = b->prob[p];
@@ -636,43 +634,26 @@ int ba_batch_set_relative(ba_batch *b, const int32_t *rel_off, const int32_t *re
     rec[p] = ba::BatchRel{(int64_t)jk.size(), (int64_t)pptr.size(), (int64_t)plist.size(), (int64_t)blk.size(),
                           (int64_t)bptr.size(), (int64_t)blist.size(), F, 0};
     if (F == 0) continue;
-    const int N = P.N;
-    per_pose.assign(N, {});
-    per_blk.clear();
-    blk_of.assign((size_t)N * N, -1);
-    const size_t blk0 = blk.size();
-    for (int f = 0; f < F; ++f) {
-      const int qj = rel_j[f0 + f], qk = rel_k[f0 + f];
-      const int oj = b->jopt[P.pose0 + qj], ok = b->jopt[P.pose0 + qk];
-      jk.push_back(make_int4(qj, qk, oj, ok));
-      Zs.insert(Zs.end(), Z12 + (int64_t)12 * (f0 + f), Z12 + (int64_t)12 * (f0 + f + 1));
-      const double *O = Omega36 + (int64_t)36 * (f0 + f);
-      for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c) Om.push_back(r >= c ? O[r * 6 + c] : O[c * 6 + r]);
-      if (oj >= 0) per_pose[oj].push_back(f << 1);
-      if (ok >= 0) per_pose[ok].push_back(f << 1 | 1);
-      if (oj >= 0 && ok >= 0) {
-        const int hi = std::max(oj, ok), lo = std::min(oj, ok);
-        int32_t &bi = blk_of[(size_t)hi * N + lo];
-        if (bi < 0) {
-          bi = (int32_t)per_blk.size();
-          per_blk.emplace_back();
-          blk.push_back(make_int2(hi, lo));
-        }
-        per_blk[bi].push_back(f << 1 | (oj < ok ? 1 : 0));  // H_jk is the block (j, k): transposed where k is hi
-      }
-    }
-    rec[p].nblk = (int32_t)(blk.size() - blk0);
-    pptr.push_back(0);
-    for (int j = 0; j < N; ++j) {
-      plist.insert(plist.end(), per_pose[j].begin(), per_pose[j].end());
-      pptr.push_back((int32_t)(plist.size() - (size_t)rec[p].pl0));
-    }
-    bptr.push_back(0);
-    for (const auto &l : per_blk) {
-      blist.insert(blist.end(), l.begin(), l.end());
-      bptr.push_back((int32_t)(blist.size() - (size_t)rec[p].bl0));
-    }
+    // the problem's lists, local to it; a coupled block's key is hi * N + lo, and H_jk is the
+    // block (j, k): transposed where k is hi
+    const int64_t N = P.N;
+    ba::relative_build_lists(
+        F, rel_j + f0, rel_k + f0, P.N, b->jopt.data() + P.pose0,
+        [N](int32_t oj, int32_t ok) {
+          return std::pair<int64_t, bool>(std::max(oj, ok) * N + std::min(oj, ok), oj < ok);
+        },
+        &l);
+    for (int f = 0; f < F; ++f) jk.push_back(make_int4(l.jk[4 * f], l.jk[4 * f + 1], l.jk[4 * f + 2], l.jk[4 * f + 3]));
+    Zs.insert(Zs.end(), Z12 + (int64_t)12 * f0, Z12 + (int64_t)12 * (f0 + F));
+    Om.resize(Om.size() + (size_t)36 * F);
+    for (int f = 0; f < F; ++f)
+      ba::relative_mirror_omega(Omega36 + (int64_t)36 * (f0 + f), Om.data() + Om.size() - (size_t)36 * (F - f));
+    rec[p].nblk = (int32_t)l.bkey.size();
+    for (int64_t key : l.bkey) blk.push_back(make_int2((int)(key / N), (int)(key % N)));
+    pptr.insert(pptr.end(), l.pptr.begin(), l.pptr.end());
+    plist.insert(plist.end(), l.plist.begin(), l.plist.end());
+    bptr.insert(bptr.end(), l.bptr.begin(), l.bptr.end());
+    blist.insert(blist.end(), l.blist.begin(), l.blist.end());
     n_on += 1;
   }
   b->rel_off.assign(rel_off, rel_off + B + 1);

@@ -10,6 +10,7 @@
 #include "ba_chol_lds.h"
 #include "ba_device_fn.h"
 #include "ba_handle.h"
+#include "ba_rel_fn.h"
 
 namespace ba {
 namespace {
@@ -40,9 +41,6 @@ struct BatchRel {
   int64_t b0, bp0, bl0;  // coupled blocks: records, nblk + 1 pointers, list entries
   int32_t F, nblk;
 };
-
-// scratch of one factor, in doubles: r, Omega r, Ad^T Omega r, Ad, Omega Ad, Ad^T Omega Ad
-constexpr int kRelR = 0, kRelOr = 6, kRelGk = 12, kRelAd = 18, kRelOA = 54, kRelBk = 90, kRelScr = 126;
 
 // the arrays of the relative-pose factors (ba_batch_set_relative), one record on the device;
 // a pointer to it is the last argument of the REL instances of the kernels, which no other
@@ -430,9 +428,9 @@ __device__ __forceinline__ double batch_prior_cross(const int K, const int2 *pj,
 }
 
 // ---- the relative-pose factors of one problem, shared by the three kernels ----------------
-// Factor f between the poses j and k: r = se3_log(T_j T_k^-1 Z^-1), first-order Jacobians
-// dr/dxi_j = I, dr/dxi_k = -Ad(T_j T_k^-1).  Unlike the prior's H its blocks depend on the
-// poses, so they are rebuilt per linearisation into the problem's slice of global scratch
+// The factor itself is ba_rel_fn.h's; here is what belongs to a batch.  Unlike the prior's H
+// the factor's blocks depend on the poses, so they are rebuilt per linearisation into the
+// problem's slice of global scratch
 // (kRelScr doubles per factor, nothing in LDS) and then gathered by one thread per element
 // of A_j, a_j and of every coupled block, each walking its list in input order.
 // on (here and below): nullptr, or one byte per pose of the problem; a factor joins when one
@@ -474,31 +472,11 @@ __device__ __forceinline__ int rel_blocks(const BatchRelDev &d) { return d.rel[b
 __device__ __forceinline__ const BatchRelDev &rel_arg(const BatchRelDev *r) { return *r; }
 
 __device__ __forceinline__ bool rel_on(const int4 jk, const uint8_t *on) { return !on || on[jk.x] || on[jk.y]; }
-
-// E = T_j T_k^-1 = [RE, tE] of one factor at the poses P
-__device__ __forceinline__ void rel_E(const int4 jk, const double *P, double RE[9], double tE[3]) {
-  const double *Tj = P + jk.x * 12, *Tk = P + jk.y * 12;
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int c = 0; c < 3; ++c)  // R_j R_k^T
-      RE[a * 3 + c] = Tj[a * 3 + 0] * Tk[c * 3 + 0] + Tj[a * 3 + 1] * Tk[c * 3 + 1] + Tj[a * 3 + 2] * Tk[c * 3 + 2];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) tE[a] = Tj[9 + a] - (RE[a * 3 + 0] * Tk[9] + RE[a * 3 + 1] * Tk[10] + RE[a * 3 + 2] * Tk[11]);
-}
-
-// the residual r = se3_log(E Z^-1)
-__device__ __forceinline__ void rel_log(const double RE[9], const double tE[3], const double *Z, double *r) {
-  double RD[9], tD[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int c = 0; c < 3; ++c)  // R_E R_Z^T
-      RD[a * 3 + c] = RE[a * 3 + 0] * Z[c * 3 + 0] + RE[a * 3 + 1] * Z[c * 3 + 1] + RE[a * 3 + 2] * Z[c * 3 + 2];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) tD[a] = tE[a] - (RD[a * 3 + 0] * Z[9] + RD[a * 3 + 1] * Z[10] + RD[a * 3 + 2] * Z[11]);
-  se3_log(RD, tD, r);
-}
+struct RelOff {  // the skip predicate of the two list walks
+  const int4 *jk;
+  const uint8_t *on;
+  __device__ __forceinline__ bool operator()(int f) const { return !rel_on(jk[f], on); }
+};
 
 // Part 1, after batch_pose_pass (and the prior's part 1): the blocks of every factor into
 // the scratch, then Omega / Ad^T Omega Ad into A_j / A_k and -Omega r / Ad^T Omega r into
@@ -507,29 +485,14 @@ __device__ __forceinline__ void batch_rel_lin(const BatchRelDev &d, const int N,
                                               const uint8_t *on = nullptr) {
   const RelView v = rel_view(d, N);
   const int tid = threadIdx.x;
-  // r and Ad = [[R_E, [t_E]x R_E], [0, R_E]], one thread per factor
+  // r and Ad, one thread per factor
   for (int f = tid; f < v.F; f += kBatchBlock) {
     const int4 jk = v.jk[f];
     if (!rel_on(jk, on)) continue;
     double RE[9], tE[3];
     rel_E(jk, P, RE, tE);
     double *s = v.scr + (size_t)f * kRelScr;
-    double *Ad = s + kRelAd;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double x0 = tE[1] * RE[6 + c] - tE[2] * RE[3 + c];
-      const double x1 = tE[2] * RE[0 + c] - tE[0] * RE[6 + c];
-      const double x2 = tE[0] * RE[3 + c] - tE[1] * RE[0 + c];
-      Ad[0 * 6 + 3 + c] = x0;
-      Ad[1 * 6 + 3 + c] = x1;
-      Ad[2 * 6 + 3 + c] = x2;
-#pragma unroll
-      for (int rr = 0; rr < 3; ++rr) {
-        Ad[rr * 6 + c] = RE[rr * 3 + c];
-        Ad[(3 + rr) * 6 + 3 + c] = RE[rr * 3 + c];
-        Ad[(3 + rr) * 6 + c] = 0.0;
-      }
-    }
+    rel_Ad(RE, tE, s + kRelAd);
     rel_log(RE, tE, v.Z + (size_t)f * 12, s + kRelR);
   }
   __syncthreads();
@@ -539,54 +502,29 @@ __device__ __forceinline__ void batch_rel_lin(const BatchRelDev &d, const int N,
     if (!rel_on(v.jk[f], on)) continue;
     const double *Om = v.Om + (size_t)f * 36;
     double *s = v.scr + (size_t)f * kRelScr;
-    double acc = 0.0;
-    if (q < 36) {
-      const int rr = q / 6, c = q - 6 * rr;
-      for (int m = 0; m < 6; ++m) acc += Om[rr * 6 + m] * s[kRelAd + m * 6 + c];
-      s[kRelOA + q] = acc;
-    } else {
-      const int rr = q - 36;
-      for (int m = 0; m < 6; ++m) acc += Om[rr * 6 + m] * s[kRelR + m];
-      s[kRelOr + rr] = acc;
-    }
+    if (q < 36)
+      s[kRelOA + q] = rel_OA(Om, s + kRelAd, q);
+    else
+      s[kRelOr + q - 36] = rel_Or(Om, s + kRelR, q - 36);
   }
   __syncthreads();
-  // Bk = Ad^T OA (each element from the expression of its lower-triangle twin: symmetric to
-  // the bit) and gk = Ad^T Or, one thread per element
+  // Bk = Ad^T OA and gk = Ad^T Or, one thread per element
   for (int e = tid; e < 42 * v.F; e += kBatchBlock) {
     const int f = e / 42, q = e - 42 * f;
     const int4 jk = v.jk[f];
     if (jk.w < 0 || !rel_on(jk, on)) continue;
     double *s = v.scr + (size_t)f * kRelScr;
-    double acc = 0.0;
-    if (q < 36) {
-      const int r0 = q / 6, c0 = q - 6 * r0;
-      const int rr = r0 > c0 ? r0 : c0, c = r0 > c0 ? c0 : r0;
-      for (int m = 0; m < 6; ++m) acc += s[kRelAd + m * 6 + rr] * s[kRelOA + m * 6 + c];
-      s[kRelBk + q] = acc;
-    } else {
-      const int rr = q - 36;
-      for (int m = 0; m < 6; ++m) acc += s[kRelAd + m * 6 + rr] * s[kRelOr + m];
-      s[kRelGk + rr] = acc;
-    }
+    if (q < 36)
+      s[kRelBk + q] = rel_Bk(s + kRelAd, s + kRelOA, q);
+    else
+      s[kRelGk + q - 36] = rel_gk(s + kRelAd, s + kRelOr, q - 36);
   }
   __syncthreads();
   // gather: one thread per element of A_j and a_j, the pose's factors in input order
   for (int e = tid; e < 42 * v.N; e += kBatchBlock) {
     const int j = e / 42, q = e - 42 * j;
-    const int l1 = v.pptr[j + 1];
-    double acc = 0.0;
     bool any = false;
-    for (int l = v.pptr[j]; l < l1; ++l) {
-      const int w = v.plist[l], f = w >> 1;
-      if (!rel_on(v.jk[f], on)) continue;
-      const double *s = v.scr + (size_t)f * kRelScr;
-      any = true;
-      if (q < 36)
-        acc += (w & 1) ? s[kRelBk + q] : v.Om[(size_t)f * 36 + q];
-      else
-        acc += (w & 1) ? s[kRelGk + q - 36] : -s[kRelOr + q - 36];
-    }
+    const double acc = rel_walk_pose(v.Om, 36, v.scr, v.plist, v.pptr[j], v.pptr[j + 1], q, RelOff{v.jk, on}, &any);
     if (!any) continue;  // a pose without a joining factor keeps its bits (and its exact zeros)
     if (q < 36)
       A[j * 36 + q] += acc;
@@ -607,15 +545,8 @@ __device__ __forceinline__ void batch_rel_offdiag(const BatchRelDev &d, const in
   for (int e = threadIdx.x; e < 36 * v.nblk; e += kBatchBlock) {
     const int b = e / 36, rc = e - 36 * b, r = rc / 6, c = rc - 6 * r;
     const int2 hl = v.blk[b];
-    const int l1 = v.bptr[b + 1];
-    double acc = 0.0;
     bool any = false;
-    for (int l = v.bptr[b]; l < l1; ++l) {
-      const int w = v.blist[l], f = w >> 1;
-      if (!rel_on(v.jk[f], on)) continue;
-      any = true;
-      acc -= v.scr[(size_t)f * kRelScr + kRelOA + ((w & 1) ? c * 6 + r : rc)];
-    }
+    const double acc = rel_walk_block(v.scr, v.blist, v.bptr[b], v.bptr[b + 1], r, c, RelOff{v.jk, on}, &any);
     if (!any) continue;
     const int row = (PERM ? col0[hl.x] : 6 * hl.x) + r, col = (PERM ? col0[hl.y] : 6 * hl.y) + c;
     Lb[PERM && row < col ? row * LS + col : col * LS + row] += acc;
@@ -631,16 +562,7 @@ __device__ __forceinline__ double batch_rel_cost(const BatchRelDev &d, const int
     double RE[9], tE[3], r[6];
     rel_E(v.jk[f], P, RE, tE);
     rel_log(RE, tE, v.Z + (size_t)f * 12, r);
-    const double *Om = v.Om + (size_t)f * 36;
-    double q = 0.0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      double row = 0.0;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) row += Om[a * 6 + c] * r[c];
-      q += r[a] * row;
-    }
-    acc += sqrt(fmax(0.0, q));
+    acc += sqrt(fmax(0.0, rel_quad(v.Om + (size_t)f * 36, r)));
   }
   return block_sum(acc, red);
 }
@@ -653,15 +575,7 @@ __device__ __forceinline__ double batch_rel_cross(const BatchRelDev &d, const in
   for (int f = threadIdx.x; f < v.F; f += kBatchBlock) {
     const int4 jk = v.jk[f];
     if (jk.z < 0 || jk.w < 0) continue;
-    const double *OA = v.scr + (size_t)f * kRelScr + kRelOA;
-    const double *xj = xs + 6 * jk.z, *xk = xs + 6 * jk.w;
-    double q = 0.0;
-    for (int a = 0; a < 6; ++a) {
-      double row = 0.0;
-      for (int c = 0; c < 6; ++c) row += OA[a * 6 + c] * xk[c];
-      q += xj[a] * row;
-    }
-    est -= 2.0 * q;
+    est += rel_cross(v.scr + (size_t)f * kRelScr + kRelOA, xs + 6 * jk.z, xs + 6 * jk.w);
   }
   return est;
 }

@@ -300,7 +300,7 @@ void launch_init_ctrl_cost(const DevProblem &d, hipStream_t s);
 // DevProblem, which every hot kernel takes by value, does not grow.  F = 0: no factors, and
 // nothing of this is launched.
 constexpr int kRelFpb = 64;  // factors per k_rel_lin workgroup
-constexpr int kRelScrDoubles = 126;  // scratch record of one factor (= kRelScr of ba_batch_kernels.h)
+constexpr int kRelScr = 126;  // scratch record of one factor, handle and batch paths (its layout: ba_rel_fn.h)
 struct RelDev {
   int F;                  // factors
   int nblk;               // coupled blocks of S (two optimisable poses)
@@ -311,7 +311,7 @@ struct RelDev {
   const int32_t *pptr, *plist;  // per optimised pose, input order: factor << 1 | (1: it is the factor's k)
   const int32_t *blk;           // per coupled block: its id in sblk_j / sblk_k
   const int32_t *bptr, *blist;  // per coupled block, input order: factor << 1 | (1: S_jk lies transposed)
-  double *scr[2];         // 126 doubles per factor (the record of the batch path), one per block buffer
+  double *scr[2];         // kRelScr doubles per factor, one per block buffer
   double *part;           // 2 per k_rel_lin workgroup: sum of the factors' norms, cross term of the model
 };
 // mode bit 0: linearise at the `sel` poses into the scratch of that block buffer; bit 1: the

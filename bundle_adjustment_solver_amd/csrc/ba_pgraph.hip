@@ -1,8 +1,8 @@
 // ba_pgraph.hip — pose-graph optimisation (ba_pgraph_*, include/ba_hip.h):
 // Levenberg-Marquardt over relative-pose factors alone, chi2 = sum_f r_f^T Omega_f r_f.  The
 // reference project has no counterpart; the definition is the comment in include/ba_hip.h.
-// The factor arithmetic is the batch path's (rel_E, rel_log of ba_batch_kernels.h), the
-// linear solve the level-scheduled tile Cholesky of ba_dense.hip.  Four kernels:
+// The factor arithmetic is defined once, in ba_rel_fn.h, the linear solve is
+// the level-scheduled tile Cholesky of ba_dense.hip.  Four kernels:
 //   k_pg_lin       kPgFpb factors per workgroup: r and Ad per factor into LDS, then one thread
 //                  per element of Omega Ad, Omega r, Ad^T Omega Ad, Ad^T Omega r; the 84-double
 //                  record of a factor leaves in runs of 36 / 6 consecutive doubles (Ad and r
@@ -23,8 +23,9 @@
 #include <cstring>
 #include <type_traits>
 
-#include "ba_batch_kernels.h"
+#include "ba_handle.h"
 #include "ba_pgraph_host.h"
+#include "ba_rel_fn.h"
 
 namespace ba {
 namespace {
@@ -85,13 +86,7 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_lin_t(PgDev p, int cost_only, P
     rel_E(jk, P, RE, tE);
     const double *Z = val + (size_t)tid * 48, *Om = Z + 12;
     rel_log(RE, tE, Z, rr);
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      double row = 0.0;
-#pragma unroll
-      for (int cc = 0; cc < 6; ++cc) row += Om[a * 6 + cc] * rr[cc];
-      q += rr[a] * row;
-    }
+    q = rel_quad(Om, rr);
     if constexpr (kRobust) {  // the partial is sum rho(s); w rides through LDS to the element threads
       double w;
       const double s = q;
@@ -102,20 +97,8 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_lin_t(PgDev p, int cost_only, P
         rb.w[f0 + tid] = w;
       }
     }
-    if (!cost_only) {  // r and Ad = [[R_E, [t_E]x R_E], [0, R_E]]
-      double *Ad = sAd + tid * kPgAdS;
-#pragma unroll
-      for (int cc = 0; cc < 3; ++cc) {
-        Ad[0 * 6 + 3 + cc] = tE[1] * RE[6 + cc] - tE[2] * RE[3 + cc];
-        Ad[1 * 6 + 3 + cc] = tE[2] * RE[0 + cc] - tE[0] * RE[6 + cc];
-        Ad[2 * 6 + 3 + cc] = tE[0] * RE[3 + cc] - tE[1] * RE[0 + cc];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          Ad[a * 6 + cc] = RE[a * 3 + cc];
-          Ad[(3 + a) * 6 + 3 + cc] = RE[a * 3 + cc];
-          Ad[(3 + a) * 6 + cc] = 0.0;
-        }
-      }
+    if (!cost_only) {  // r and Ad
+      rel_Ad(RE, tE, sAd + tid * kPgAdS);
 #pragma unroll
       for (int a = 0; a < 6; ++a) sR[tid * kPgRS + a] = rr[a];
     }
@@ -127,37 +110,29 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_lin_t(PgDev p, int cost_only, P
     for (int e = tid; e < 42 * nf; e += kPgBlock) {
       const int f = e / 42, k = e - 42 * f;
       const double *Om = val + (size_t)f * 48 + 12;
-      double acc = 0.0;
       if (k < 36) {
-        const int a = k / 6, cc = k - 6 * a;
-        for (int m = 0; m < 6; ++m) acc += Om[a * 6 + m] * sAd[f * kPgAdS + m * 6 + cc];
+        double acc = rel_OA(Om, sAd + f * kPgAdS, k);
         if constexpr (kRobust) acc *= sW[f];
         sOA[f * kPgAdS + k] = acc;
         rec[(size_t)f * kPgRec + kPgOA + k] = acc;
       } else {
         const int a = k - 36;
-        for (int m = 0; m < 6; ++m) acc += Om[a * 6 + m] * sR[f * kPgRS + m];
+        double acc = rel_Or(Om, sR + f * kPgRS, a);
         if constexpr (kRobust) acc *= sW[f];
         sOr[f * kPgRS + a] = acc;
         rec[(size_t)f * kPgRec + kPgOr + a] = acc;
       }
     }
     __syncthreads();
-    // Bk = Ad^T OA (each element from the expression of its lower-triangle twin: symmetric to
-    // the bit) and gk = Ad^T Or, for the factors whose k is optimisable
+    // Bk = Ad^T OA and gk = Ad^T Or, for the factors whose k is optimisable
     for (int e = tid; e < 42 * nf; e += kPgBlock) {
       const int f = e / 42, k = e - 42 * f;
       if (p.jk[f0 + f].w < 0) continue;
-      double acc = 0.0;
       if (k < 36) {
-        const int r0 = k / 6, c0 = k - 6 * r0;
-        const int a = r0 > c0 ? r0 : c0, cc = r0 > c0 ? c0 : r0;
-        for (int m = 0; m < 6; ++m) acc += sAd[f * kPgAdS + m * 6 + a] * sOA[f * kPgAdS + m * 6 + cc];
-        rec[(size_t)f * kPgRec + kPgBk + k] = acc;
+        rec[(size_t)f * kPgRec + kPgBk + k] = rel_Bk(sAd + f * kPgAdS, sOA + f * kPgAdS, k);
       } else {
         const int a = k - 36;
-        for (int m = 0; m < 6; ++m) acc += sAd[f * kPgAdS + m * 6 + a] * sOr[f * kPgRS + m];
-        rec[(size_t)f * kPgRec + kPgGk + a] = acc;
+        rec[(size_t)f * kPgRec + kPgGk + a] = rel_gk(sAd + f * kPgAdS, sOr + f * kPgRS, a);
       }
     }
   }
@@ -175,6 +150,8 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_assemble_t(PgDev p, double *Hou
   const size_t n6 = (size_t)6 * p.N;
   if (e < nd) {
     const int j = (int)(e / 42), q = (int)(e - (int64_t)42 * j);
+    // (the two walks are rel_walk_pose / rel_walk_block of ba_rel_fn.h written out: calling
+    // them measured 2 % slower here, see profiles/rel_shared_v1.txt)
     const int l1 = p.pptr[j + 1];
     double acc = 0.0;
     for (int l = p.pptr[j]; l < l1; ++l) {

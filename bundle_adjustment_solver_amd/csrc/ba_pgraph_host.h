@@ -65,16 +65,15 @@ inline int pgraph_robust_validate_host(int64_t n_rel, const int32_t *kind, const
   return 0;
 }
 
-// The structure of a validated graph. The optimisable poses keep the user's order:
-// optimisable index = rank among the optimisable poses.
-struct PgraphLists {
+// The structure of a validated graph: the shared lists (ba_rel_host.h) plus the graph's own
+// numbering.  The optimisable poses keep the user's order: optimisable index = rank among the
+// optimisable poses.  A coupled block's key is hi * N + lo, so the blocks ascend in (hi, lo);
+// H_jk is block (j, k): below the diagonal as it is when j > k, transposed otherwise.
+struct PgraphLists : RelLists {
   int N = 0;
   std::vector<int32_t> opt_of_pose;   // per pose: optimisable index or -1
   std::vector<int32_t> opt_pose;      // per optimisable pose: its pose
-  std::vector<int32_t> jk;            // 4 per factor: {pose j, pose k, optimisable index of j or -1, of k or -1}
-  std::vector<int32_t> pptr, plist;   // per optimisable pose, input order: factor << 1 | (1: it is the factor's k)
-  std::vector<int32_t> blk;           // 2 per coupled block: optimisable poses {hi, lo}, hi > lo, ascending (hi, lo)
-  std::vector<int32_t> bptr, blist;   // per coupled block, input order: factor << 1 | (1: H_jk lies transposed)
+  std::vector<int32_t> blk;           // 2 per coupled block: optimisable poses {hi, lo}, hi > lo
 };
 
 inline void pgraph_build_lists(int n_pose, const uint8_t *pose_fixed, int64_t n_rel, const int32_t *rel_j,
@@ -87,40 +86,14 @@ inline void pgraph_build_lists(int n_pose, const uint8_t *pose_fixed, int64_t n_
       l.opt_of_pose[p] = l.N++;
       l.opt_pose.push_back(p);
     }
-  const int N = l.N;
-  l.jk.resize((size_t)n_rel * 4);
-  l.pptr.assign((size_t)N + 1, 0);
-  std::vector<std::pair<int64_t, int32_t>> by_blk;  // (hi * N + lo, factor << 1 | transposed)
-  for (int64_t f = 0; f < n_rel; ++f) {
-    const int32_t a = l.opt_of_pose[rel_j[f]], b = l.opt_of_pose[rel_k[f]];
-    int32_t *r = &l.jk[(size_t)f * 4];
-    r[0] = rel_j[f];
-    r[1] = rel_k[f];
-    r[2] = a;
-    r[3] = b;
-    if (a >= 0) l.pptr[a + 1]++;
-    if (b >= 0) l.pptr[b + 1]++;
-    if (a >= 0 && b >= 0)  // H_jk is block (j, k): below the diagonal as it is when j > k
-      by_blk.push_back({(int64_t)std::max(a, b) * N + std::min(a, b), (int32_t)(f << 1) | (a < b ? 1 : 0)});
+  const int64_t N = l.N;
+  relative_build_lists(
+      n_rel, rel_j, rel_k, l.N, l.opt_of_pose.data(),
+      [N](int32_t a, int32_t b) { return std::pair<int64_t, bool>(std::max(a, b) * N + std::min(a, b), a < b); }, &l);
+  for (int64_t key : l.bkey) {
+    l.blk.push_back((int32_t)(key / N));
+    l.blk.push_back((int32_t)(key % N));
   }
-  for (int j = 0; j < N; ++j) l.pptr[j + 1] += l.pptr[j];
-  l.plist.resize((size_t)l.pptr[N]);
-  std::vector<int32_t> cur(l.pptr.begin(), l.pptr.end() - 1);
-  for (int64_t f = 0; f < n_rel; ++f) {
-    const int32_t *r = &l.jk[(size_t)f * 4];
-    if (r[2] >= 0) l.plist[cur[r[2]]++] = (int32_t)(f << 1);
-    if (r[3] >= 0) l.plist[cur[r[3]]++] = (int32_t)(f << 1) | 1;
-  }
-  std::stable_sort(by_blk.begin(), by_blk.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
-  for (size_t t = 0; t < by_blk.size(); ++t) {
-    if (t == 0 || by_blk[t].first != by_blk[t - 1].first) {
-      l.blk.push_back((int32_t)(by_blk[t].first / N));
-      l.blk.push_back((int32_t)(by_blk[t].first % N));
-      l.bptr.push_back((int32_t)t);
-    }
-    l.blist.push_back(by_blk[t].second);
-  }
-  l.bptr.push_back((int32_t)by_blk.size());
 }
 
 // Symmetric ncb x ncb tile adjacency (row-major bytes, zero diagonal) of the coupled blocks

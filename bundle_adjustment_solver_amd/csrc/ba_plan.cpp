@@ -2,6 +2,7 @@
 #include "ba_plan.h"
 
 #include "ba_dense_sched.h"
+#include "ba_rel_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1028,38 +1029,28 @@ BlockIndex build_block_set(const PlanInput &in, Plan &pl) {
 // (rel_jk, rel_pptr / rel_plist, rel_blk / rel_bptr / rel_blist; all empty without factors)
 void build_relative_lists(const PlanInput &in, const BlockIndex &blocks, Plan &pl) {
   if (in.n_rel <= 0) return;
+  // the factors name internal poses here (the optimisable ones come first); a coupled block's
+  // key is its id in sblk_j / sblk_k, where S_jk of a factor with j > k lies transposed
   const int N = pl.N;
-  pl.rel_jk.resize((size_t)in.n_rel * 4);
-  pl.rel_pptr.assign((size_t)N + 1, 0);
-  std::vector<std::pair<int32_t, int32_t>> by_blk;  // (block, factor << 1 | transposed)
+  std::vector<int32_t> j((size_t)in.n_rel), k((size_t)in.n_rel), opt_of((size_t)in.n_pose, -1);
   for (int64_t f = 0; f < in.n_rel; ++f) {
-    const int32_t a = pl.pose_int_of_user[in.rel_j[f]], b = pl.pose_int_of_user[in.rel_k[f]];
-    int32_t *r = &pl.rel_jk[(size_t)f * 4];
-    r[0] = a;
-    r[1] = b;
-    r[2] = a < N ? a : -1;
-    r[3] = b < N ? b : -1;
-    if (a < N) pl.rel_pptr[a + 1]++;
-    if (b < N) pl.rel_pptr[b + 1]++;
-    if (a < N && b < N) by_blk.push_back({blocks.block_of(std::min(a, b), std::max(a, b)), (int32_t)(f << 1) | (a > b ? 1 : 0)});
+    j[f] = pl.pose_int_of_user[in.rel_j[f]];
+    k[f] = pl.pose_int_of_user[in.rel_k[f]];
   }
-  for (int j = 0; j < N; ++j) pl.rel_pptr[j + 1] += pl.rel_pptr[j];
-  pl.rel_plist.resize((size_t)pl.rel_pptr[N]);
-  std::vector<int32_t> cur(pl.rel_pptr.begin(), pl.rel_pptr.end() - 1);
-  for (int64_t f = 0; f < in.n_rel; ++f) {
-    const int32_t *r = &pl.rel_jk[(size_t)f * 4];
-    if (r[2] >= 0) pl.rel_plist[cur[r[2]]++] = (int32_t)(f << 1);
-    if (r[3] >= 0) pl.rel_plist[cur[r[3]]++] = (int32_t)(f << 1) | 1;
-  }
-  std::stable_sort(by_blk.begin(), by_blk.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
-  for (size_t t = 0; t < by_blk.size(); ++t) {
-    if (t == 0 || by_blk[t].first != by_blk[t - 1].first) {
-      pl.rel_blk.push_back(by_blk[t].first);
-      pl.rel_bptr.push_back((int32_t)t);
-    }
-    pl.rel_blist.push_back(by_blk[t].second);
-  }
-  pl.rel_bptr.push_back((int32_t)by_blk.size());
+  std::iota(opt_of.begin(), opt_of.begin() + N, 0);
+  RelLists l;
+  relative_build_lists(
+      in.n_rel, j.data(), k.data(), N, opt_of.data(),
+      [&](int32_t a, int32_t b) {
+        return std::pair<int64_t, bool>(blocks.block_of(std::min(a, b), std::max(a, b)), a > b);
+      },
+      &l);
+  pl.rel_jk.swap(l.jk);
+  pl.rel_pptr.swap(l.pptr);
+  pl.rel_plist.swap(l.plist);
+  pl.rel_blk.assign(l.bkey.begin(), l.bkey.end());
+  pl.rel_bptr.swap(l.bptr);
+  pl.rel_blist.swap(l.blist);
 }
 
 // Landmark kinds: 0 = fits a super-run whole; 1 = SPLIT: its pairs fit the LDS

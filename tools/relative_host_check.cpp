@@ -1,9 +1,11 @@
-// Stand-alone host check of the validation and packing of the handle path's relative-pose
-// factors (bundle_adjustment_solver_amd/csrc/ba_rel_host.h), meant for the host sanitizers:
+// Stand-alone host check of the validation, the packing and the shared list builder of the
+// relative-pose factors (bundle_adjustment_solver_amd/csrc/ba_rel_host.h), meant for the host
+// sanitizers (tests/test_relative_host_check.py runs it so):
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       tools/relative_host_check.cpp -o /tmp/relative_host_check && /tmp/relative_host_check
 // No GPU and no HIP.  Every array is sized exactly, so that an access past an end is the
 // sanitizer's to find.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <limits>
@@ -93,10 +95,72 @@ static int one_case(int n_pose, int F) {
   return 0;
 }
 
+// The shared list builder against a brute-force statement of the lists (a loop over the
+// factors per pose and per block): 6 poses, 0 and 3 fixed; 9 factors with one pair twice in
+// one direction (0, 2), one pair in both directions (3, 4), two factors to a fixed pose
+// (5, 6) and pose 5, which is only ever a k (7, 8).
+template <class KeyOf>
+static int builder_case(KeyOf key_of) {
+  const int n_pose = 6, F = 9, N = 4;
+  const std::vector<int32_t> opt_of = {-1, 0, 1, -1, 2, 3};
+  const std::vector<int32_t> j = {1, 4, 1, 2, 4, 0, 4, 1, 2}, k = {2, 1, 2, 4, 2, 1, 3, 5, 5};
+  REQUIRE((int)opt_of.size() == n_pose && (int)j.size() == F && (int)k.size() == F);
+  ba::RelLists l;
+  ba::relative_build_lists(F, j.data(), k.data(), N, opt_of.data(), key_of, &l);
+  REQUIRE(l.jk.size() == (size_t)4 * F && l.pptr.size() == (size_t)N + 1 && l.pptr[0] == 0);
+  for (int f = 0; f < F; ++f)
+    REQUIRE(l.jk[4 * f] == j[f] && l.jk[4 * f + 1] == k[f] && l.jk[4 * f + 2] == opt_of[j[f]] &&
+            l.jk[4 * f + 3] == opt_of[k[f]]);
+  for (int n = 0; n < N; ++n) {
+    std::vector<int32_t> want;
+    for (int f = 0; f < F; ++f) {
+      if (opt_of[j[f]] == n) want.push_back(f << 1);
+      if (opt_of[k[f]] == n) want.push_back(f << 1 | 1);
+    }
+    REQUIRE(l.pptr[n] <= l.pptr[n + 1] && (size_t)l.pptr[n + 1] <= l.plist.size());
+    REQUIRE(want == std::vector<int32_t>(l.plist.begin() + l.pptr[n], l.plist.begin() + l.pptr[n + 1]));
+  }
+  REQUIRE((size_t)l.pptr[N] == l.plist.size() && l.plist.size() == 16);
+  REQUIRE(l.pptr[4] - l.pptr[3] == 2 && (l.plist[l.pptr[3]] & 1) && (l.plist[l.pptr[3] + 1] & 1));  // pose 5
+  std::vector<int64_t> keys;
+  for (int f = 0; f < F; ++f)
+    if (opt_of[j[f]] >= 0 && opt_of[k[f]] >= 0) keys.push_back(key_of(opt_of[j[f]], opt_of[k[f]]).first);
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  REQUIRE(keys.size() == 5 && l.bkey == keys && l.bptr.size() == keys.size() + 1 && l.bptr[0] == 0);
+  for (size_t b = 0; b < keys.size(); ++b) {
+    std::vector<int32_t> want;
+    for (int f = 0; f < F; ++f) {
+      const int32_t a = opt_of[j[f]], c = opt_of[k[f]];
+      if (a < 0 || c < 0) continue;
+      REQUIRE(key_of(a, c).first == key_of(c, a).first && key_of(a, c).second != key_of(c, a).second);
+      if (key_of(a, c).first == keys[b]) want.push_back(f << 1 | (key_of(a, c).second ? 1 : 0));
+    }
+    REQUIRE(l.bptr[b] < l.bptr[b + 1] && (size_t)l.bptr[b + 1] <= l.blist.size());
+    REQUIRE(want == std::vector<int32_t>(l.blist.begin() + l.bptr[b], l.blist.begin() + l.bptr[b + 1]));
+  }
+  REQUIRE((size_t)l.bptr[keys.size()] == l.blist.size() && l.blist.size() == 7);
+  // no factor at all: empty lists with their leading pointers
+  ba::relative_build_lists(0, nullptr, nullptr, N, opt_of.data(), key_of, &l);
+  REQUIRE(l.jk.empty() && l.plist.empty() && l.bkey.empty() && l.blist.empty());
+  REQUIRE(l.pptr == std::vector<int32_t>((size_t)N + 1, 0) && l.bptr == std::vector<int32_t>(1, 0));
+  return 0;
+}
+
 int main() {
   for (int n_pose : {3, 4, 7, 64})
     for (int F : {0, 1, 2, 5, 63, 64, 65, 200})
       if (one_case(n_pose, F)) return 1;
+  // the planner's convention (upper blocks (lo, hi) numbered row by row, transposed where
+  // j > k) and the pose graph's and the batch's (hi * N + lo, transposed where j < k)
+  if (builder_case([](int32_t a, int32_t b) {
+        return std::pair<int64_t, bool>((int64_t)std::min(a, b) * 4 + std::max(a, b), a > b);
+      }))
+    return 1;
+  if (builder_case([](int32_t a, int32_t b) {
+        return std::pair<int64_t, bool>((int64_t)std::max(a, b) * 4 + std::min(a, b), a < b);
+      }))
+    return 1;
   std::printf("RELATIVE HOST CHECK PASSED\n");
   return 0;
 }
