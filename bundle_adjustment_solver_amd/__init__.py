@@ -10,8 +10,8 @@ from .solver import (BaProblem, Camera, FullBundleAdjustmentSolver,  # noqa
                      IterationStatus, OptimizationInfo, Options,
                      PoseOnlyBundleAdjustmentSolver, SolverType, Summary,
                      covariance_to_user_units, marginal_to_user_units,
-                     prior_constant, prior_to_scaled_units, relative_residual,
-                     se3_log)
+                     prior_constant, prior_to_scaled_units, relative_covariance,
+                     relative_residual, se3_log)
 from . import scenes  # noqa
 from . import scene_io  # noqa
 
@@ -20,5 +20,5 @@ __all__ = ["BaProblem", "Camera", "FullBundleAdjustmentSolver",
            "IterationStatus", "OptimizationInfo", "Options",
            "PoseOnlyBundleAdjustmentSolver", "SolverType", "Summary",
            "covariance_to_user_units", "marginal_to_user_units", "prior_constant",
-           "prior_to_scaled_units", "relative_residual", "se3_log", "scenes",
+           "prior_to_scaled_units", "relative_covariance", "relative_residual", "se3_log", "scenes",
            "scene_io"]

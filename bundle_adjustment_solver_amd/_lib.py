@@ -310,6 +310,11 @@ SIGNATURES = {
     "ba_pgraph_set_robust": (C.c_int, [_P, _I32, _D]),
     "ba_pgraph_robust_check": (C.c_int, [C.c_int64, _I32, _D]),
     "ba_pgraph_factor_report": (C.c_int, [_P, _D, _D]),
+    "ba_pgraph_covariance": (C.c_int, [_P, C.c_int, _I32, _D, C.c_int64, _I32, _I32, _D, _D, _I64]),
+    "ba_pgraph_gate": (C.c_int, [_P, C.c_int64, _I32, _I32, _D, _D, _D, _D, _D, _I64]),
+    "ba_pgraph_cov_check": (C.c_int, [C.c_int, _U8, C.c_int, _I32, _D, C.c_int64, _I32, _I32, _D,
+                                      C.c_int64, _I32, _I32, _D, _D, _D]),
+    "ba_pgraph_cov_info": (C.c_int, [_P, _I64]),
 }
 
 _lib = None

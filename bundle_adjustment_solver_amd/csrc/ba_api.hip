@@ -1923,14 +1923,7 @@ int ba_covariance_check(int finalized, int sharded, int streamed, int n_pose, co
   return 0;
 }
 
-// Columns of one batch for an image of npad rows: what fits 256 MiB of workspace, at most
-// 1024 waves' worth, a multiple of the 16 columns of a wave; RunKnobs::cov_batch overrides.
-static int cov_batch_cols(int npad, const ba::RunKnobs &knobs) {
-  int64_t cols = ((int64_t)256 << 20) / (8 * (int64_t)std::max(npad, 1));
-  if (knobs.cov_batch > 0) cols = knobs.cov_batch;
-  cols = std::min<int64_t>(cols, 1024 * ba::kCovGroupCols);
-  return (int)std::max<int64_t>(ba::kCovGroupCols, cols / ba::kCovGroupCols * ba::kCovGroupCols);
-}
+using ba::cov_batch_cols;  // ba_handle.h: shared with ba_pgraph_covariance
 
 int ba_covariance_info(ba_handle *h, int64_t out4[4]) {
   if (!h || !h->finalized || !out4) return fail("ba_covariance_info: bad argument");

@@ -21,13 +21,14 @@
 // skipped through the schedule's row lists.  The diagonal blocks of G are the results.
 // No atomics; every sum is an MFMA chain in tile order: the same bits run to run and
 // whatever else is selected in the same call.
+#include "ba_cov_sweep.h"
 #include "ba_device.h"
 #include "ba_device_fn.h"
 
 namespace ba {
 
 namespace {
-typedef double v4f64 __attribute__((ext_vector_type(4)));
+typedef cov_v4f64 v4f64;
 
 // Right-hand sides of the batch into the (zeroed) workspace: identity columns of the
 // group's poses, or W_ji Cinv_i (6x3, W expanded from the compact {K, X_ij} record as
@@ -85,11 +86,8 @@ __global__ __launch_bounds__(64) void k_cov_rhs(const CovGroup *__restrict__ gro
   }
 }
 
-// MFMA operand maps (v_mfma_f64_16x16x4_f64): lane (lr = lane & 15, lk = lane >> 4) gives
-// A[i = lr][k = lk] and B[k = lk][j = lr]; accumulator register g is D[i = lk + 4 g][j = lr].
-// Here i = row of the tile, j = right-hand side: an accumulator register is 16 consecutive
-// columns of one workspace row (128 contiguous bytes), and — k-step g taken over the rows
-// k = lk + 4 g — the result of one product is the B operand of the next as it stands.
+// The sweep itself is cov_sweep<NB> (ba_cov_sweep.h), shared with the pose graph's kernel; an
+// accumulator register q of the Gram matrix is G[row = lk + 4 q][column = lr].
 template <int NB>
 __global__ __launch_bounds__(64) void k_cov_solve(const double *__restrict__ L, int ld,
                                                   const double *__restrict__ Ldiag, int ncb,
@@ -98,58 +96,10 @@ __global__ __launch_bounds__(64) void k_cov_solve(const double *__restrict__ L, 
                                                   const CovGroup *__restrict__ groups, double *Zw,
                                                   int bw, const double *__restrict__ Cinv,
                                                   double *out_pose, double *out_pt) {
-  constexpr int NP = NB / 16;
-  constexpr int WS = NB * NB + NP * 256;
   const CovGroup g = groups[blockIdx.x];
   const int lane = threadIdx.x, lr = lane & 15, lk = lane >> 4;
   double *Zc = Zw + kCovGroupCols * blockIdx.x + lr;  // this lane's column
-  v4f64 G = (v4f64){0.0, 0.0, 0.0, 0.0};
-  for (int t = g.t0; t < ncb; ++t) {
-    v4f64 acc[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[p][q] = Zc[(size_t)(t * NB + 16 * p + lk + 4 * q) * bw];
-    const int e = trow_ptr[t + 1];
-    for (int a = trow_ptr[t]; a < e; ++a) {
-      const int s = trow[a];
-      if (s < g.t0) continue;  // (wave-uniform) X_s = 0
-      const double *Lc = L + (size_t)s * NB * ld + t * NB + lr;  // column s NB + k, row t NB + r
-      const double *Zs = Zc + (size_t)s * NB * bw;
-#pragma unroll 4
-      for (int kk = 0; kk < NB / 4; ++kk) {
-        const int k = 4 * kk + lk;
-        const double bz = Zs[(size_t)k * bw];
-#pragma unroll
-        for (int p = 0; p < NP; ++p)
-          acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(-Lc[(size_t)k * ld + 16 * p], bz, acc[p], 0, 0, 0);
-      }
-    }
-    // X_p = L_pp^-1 (R_p - sum_{q < p} L_pq X_q): factor tile column-major, zero above the
-    // diagonal; Et[p][k][c] = (L_pp^-T)[k][c], so L_pp^-1[i][k] = Et[p][k][i]
-    const double *Ld = Ldiag + (size_t)t * WS;
-    const double *Et = Ld + NB * NB;
-    v4f64 X[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      v4f64 r = acc[p];
-#pragma unroll
-      for (int q = 0; q < p; ++q)
-#pragma unroll
-        for (int k4 = 0; k4 < 4; ++k4)
-          r = __builtin_amdgcn_mfma_f64_16x16x4f64(-Ld[(16 * q + lk + 4 * k4) * NB + 16 * p + lr], X[q][k4], r, 0, 0, 0);
-      v4f64 o = (v4f64){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int k4 = 0; k4 < 4; ++k4)
-        o = __builtin_amdgcn_mfma_f64_16x16x4f64(Et[p * 256 + (lk + 4 * k4) * 16 + lr], r[k4], o, 0, 0, 0);
-      X[p] = o;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) Zc[(size_t)(t * NB + 16 * p + lk + 4 * q) * bw] = o[q];
-#pragma unroll
-      for (int k4 = 0; k4 < 4; ++k4) G = __builtin_amdgcn_mfma_f64_16x16x4f64(o[k4], o[k4], G, 0, 0, 0);
-    }
-    __syncthreads();  // the rows just stored are read back by other lanes of this wave
-  }
+  const v4f64 G = cov_sweep<NB>(L, ld, Ldiag, ncb, trow_ptr, trow, g.t0, Zc, bw);
   // the diagonal blocks of G: 6x6 per pose, or Cinv_i + 3x3 per landmark
   const int bs = g.kind == 0 ? 6 : 3;
 #pragma unroll

@@ -487,6 +487,21 @@ void launch_cov_batch(const DevProblem &d, int lcur, int cur, int ncb, const int
                       const CovGroup *groups, int ng, double *Zw, int bw, double *out_pose,
                       double *out_pt, hipStream_t s);
 
+// ---- covariance blocks and the gate of a pose graph (ba_pgraph_cov.hip) ----
+struct PgCovGroup;  // ba_pgraph_host.h: one wave's two poses, pair or candidate
+// Device outputs of one call: pose36 per distinct selected pose; rel36 (Sigma_E), cross36
+// (Sigma_jk, or null: not asked for) per pair or candidate; r6 / innov36 (or null) and d2 per candidate.
+struct PgCovOut {
+  double *pose36, *cross36, *rel36, *r6, *innov36, *d2;
+};
+// One column batch on the factored image of the graph (p.L, Ldiag; lambda = 0): zero the workspace
+// Zw (p.npad x bw doubles, row-major, bw = 16 ng), place the identity columns, sweep, write the
+// blocks.  poses: the accepted pose buffer; cand_val: 48 doubles per candidate (ba_rel_host.h) or
+// null; trow_ptr / trow as for launch_cov_batch.  Enqueue only.
+void launch_pgcov_batch(const PgDev &p, const double *Ldiag, int nb, int ncb, const double *poses,
+                        const int *trow_ptr, const int *trow, const PgCovGroup *groups, int ng,
+                        const double *cand_val, double *Zw, int bw, const PgCovOut &out, hipStream_t s);
+
 // ---- pose-only (ba_pose_only.hip) ----
 struct PoIter {
   float cost, cost_change, abs_step;

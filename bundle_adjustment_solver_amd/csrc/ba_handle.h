@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <chrono>
 #include <string>
@@ -225,6 +226,16 @@ struct ScratchAllocs {
     h->allocs.resize(mark);
   }
 };
+
+// Columns of one covariance batch for an image of npad rows (ba_covariance, ba_pgraph_covariance):
+// what fits 256 MiB of workspace, at most 1024 waves' worth, a multiple of the 16 columns of a
+// wave; RunKnobs::cov_batch overrides.
+inline int cov_batch_cols(int npad, const RunKnobs &knobs) {
+  int64_t cols = ((int64_t)256 << 20) / (8 * (int64_t)std::max(npad, 1));
+  if (knobs.cov_batch > 0) cols = knobs.cov_batch;
+  cols = std::min<int64_t>(cols, 1024 * kCovGroupCols);
+  return (int)std::max<int64_t>(kCovGroupCols, cols / kCovGroupCols * kCovGroupCols);
+}
 
 int lm_prepare_ctrl(ba_handle *h, const ba_options *opt, int *done_after);
 int ctrl_pull(ba_handle *h);  // device controller state -> h->hc (synchronises the stream)

@@ -19,6 +19,9 @@
 // Robust kernels (ba_pgraph_set_robust): k_pg_lin_robust and k_pg_assemble_robust
 // are second instantiations of the two bodies with sum rho(s) for chi-square and w Omega for
 // Omega; a graph whose kinds are all 0 launches the plain ones.
+// Covariance blocks and the gate (ba_pgraph_covariance / ba_pgraph_gate): the host
+// side is here (pg_cov_run: the solve's launches at lambda = 0, then column batches), the groups
+// and the validation in ba_pgraph_host.h, the kernels in ba_pgraph_cov.hip.
 #include <cstddef>
 #include <cstring>
 #include <type_traits>
@@ -380,6 +383,8 @@ struct ba_pgraph {
   size_t image_bytes = 0;
   int64_t bad_pivots = 0;
   double last_ms = 0.0;
+  std::vector<int> pose_col_h;  // per optimisable pose: its first column of the image
+  int cov_batches = 0;          // column batches of the last ba_pgraph_covariance / ba_pgraph_gate
   hipEvent_t e0 = nullptr, e1 = nullptr;
   std::vector<void *> allocs;
 };
@@ -474,6 +479,7 @@ int build_device(ba_pgraph *g, const double *T_jw12) {
     }
   }
   g->n_zt = (int)ztI.size();
+  g->pose_col_h = pose_col;
   std::vector<double> val;
   ba::relative_pack_values(g->F, g->Z.data(), g->Om.data(), &val);
   constexpr Mem R = Mem::Resident;
@@ -561,6 +567,115 @@ void pg_assemble(const ba_pgraph *g, double *Hout, double *gout, hipStream_t s) 
     ba::launch_pg_assemble_robust(g->d, g->rb, Hout, gout, s);
   else
     ba::launch_pg_assemble(g->d, Hout, gout, s);
+}
+
+
+template <class T>
+int download(std::vector<T> &out, const T *dev, size_t n, hipStream_t s) {
+  out.resize(n);
+  if (n) HIP_TRY(hipMemcpyAsync(out.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
+  return 0;
+}
+
+// The host arrays of one covariance or gate call (validated): entry_kind = kPgCovPair with
+// Z12 = Omega36 = nullptr, or kPgCovCand.  Outputs that are null are not produced.
+struct PgCovCall {
+  int n_pose_sel = 0;
+  const int32_t *pose_sel = nullptr;
+  double *cov_pose36 = nullptr;
+  int64_t n_entry = 0;
+  int entry_kind = ba::kPgCovPair;
+  const int32_t *entry_j = nullptr, *entry_k = nullptr;
+  const double *Z12 = nullptr, *Omega36 = nullptr;
+  double *cov_cross36 = nullptr, *cov_rel36 = nullptr, *d2 = nullptr, *r6 = nullptr, *innov36 = nullptr;
+};
+
+// Factorise H at lambda = 0 at the accepted poses with the solve's launches, sweep the groups
+// in column batches, copy the blocks out.  The controller, the solve's count of dropped pivots
+// and last_ms are as before on return; the workspace and the lists are freed on every path.
+int pg_cov_run(ba_pgraph *g, const char *what, const PgCovCall &c, int64_t *dropped_pivots) {
+  ba_handle *h = g->h;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const ba::PgDev &d = g->d;
+  const ba::DenseSchedule &sc = g->sched;
+  std::vector<ba::PgCovGroup> groups;
+  std::vector<int32_t> slot_of_opt;
+  int n_pose_rows = 0;
+  ba::pgraph_cov_groups(g->lists, g->pose_col_h, g->nb, c.n_pose_sel, c.pose_sel, c.n_entry, c.entry_j, c.entry_k,
+                        c.entry_kind, &groups, &slot_of_opt, &n_pose_rows);
+  std::vector<int> trow_ptr, trow;
+  ba::pgraph_cov_tile_rows(g->ncb, sc.row_ptr, sc.rows, &trow_ptr, &trow);
+  // ---- the factor of H at lambda = 0, whole in the image (no level goes to k_chol_tail)
+  HIP_TRY(hipStreamSynchronize(s));
+  const ba::PgCtrl keep = g->hc;
+  int bad_keep = 0, bad_now = 0;
+  HIP_TRY(hipMemcpy(&bad_keep, g->dd.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemsetAsync(g->dd.bad_pivots, 0, sizeof(int), s));
+  if (begin_pass(g)) return -1;
+  const int *done = done_flag(g);
+  pg_lin(g, 0, s);
+  ba::launch_dense_init(d.L, d.ld, g->col_x, g->zt_I, g->zt_J, g->n_zt, g->nb, done, s);
+  pg_assemble(g, nullptr, nullptr, s);
+  ba::dense_factor_solve(d.L, d.npad, d.ld, g->Ldiag, d.x, done, sc, g->dd,
+                         ba::dense_launch_plan_no_tail(sc, h->knobs.dense, g->dd.flow_ok, g->dd.plan[1],
+                                                       h->knobs.cone.want),
+                         s);
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(&bad_now, g->dd.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(g->dd.bad_pivots, &bad_keep, sizeof(int), hipMemcpyHostToDevice));
+  g->hc = keep;  // the controller as it was
+  if (push_ctrl(g)) return -1;
+  HIP_TRY(hipStreamSynchronize(s));
+  if (bad_now >= ba::kFlowTimeout) return fail(std::string(what) + ": a dataflow hand-off of the factorisation timed out");
+  // ---- the batches; everything below is freed again on every return
+  ba::ScratchAllocs scratch(h);
+  constexpr Mem R = Mem::Resident;
+  const bool cand = c.entry_kind == ba::kPgCovCand;
+  const size_t ne = (size_t)c.n_entry;
+  const int gpb = ba::cov_batch_cols(d.npad, h->knobs.run) / ba::kCovGroupCols;  // groups per batch
+  const int bw = (int)std::min<size_t>(gpb, std::max<size_t>(1, groups.size())) * ba::kCovGroupCols;
+  int *d_trow_ptr = nullptr, *d_trow = nullptr;
+  ba::PgCovGroup *d_groups = nullptr;
+  double *Zw = nullptr, *d_val = nullptr;
+  ba::PgCovOut out{};
+  g->cov_batches = 0;
+  if (!groups.empty()) {
+    std::vector<double> val;
+    if (cand) ba::relative_pack_values(c.n_entry, c.Z12, c.Omega36, &val);
+    if (h->upload(R, &d_trow_ptr, trow_ptr) || h->upload(R, &d_trow, trow) || h->upload(R, &d_groups, groups) ||
+        h->dalloc(R, &Zw, (size_t)d.npad * bw) || h->dalloc(R, &out.pose36, (size_t)n_pose_rows * 36) ||
+        h->dalloc(R, &out.rel36, ne * 36) || (c.cov_cross36 && h->dalloc(R, &out.cross36, ne * 36)) ||
+        (cand && (h->upload(R, &d_val, val) || h->dalloc(R, &out.d2, ne))) ||
+        (cand && c.r6 && h->dalloc(R, &out.r6, ne * 6)) || (cand && c.innov36 && h->dalloc(R, &out.innov36, ne * 36)))
+      return -1;
+    for (size_t g0 = 0; g0 < groups.size(); g0 += gpb) {  // fixed batch order
+      const int ng = (int)std::min<size_t>(gpb, groups.size() - g0);
+      ba::launch_pgcov_batch(d, g->Ldiag, g->nb, g->ncb, d.poses[keep.cur], d_trow_ptr, d_trow, d_groups + g0, ng, d_val,
+                             Zw, bw, out, s);
+      ++g->cov_batches;
+    }
+  }
+  std::vector<double> hp, hrel, hcross, hd2, hr, hP;
+  if (download(hp, out.pose36, (size_t)n_pose_rows * 36, s) || download(hrel, out.rel36, out.rel36 ? ne * 36 : 0, s) ||
+      download(hcross, out.cross36, out.cross36 ? ne * 36 : 0, s) || download(hd2, out.d2, out.d2 ? ne : 0, s) ||
+      download(hr, out.r6, out.r6 ? ne * 6 : 0, s) || download(hP, out.innov36, out.innov36 ? ne * 36 : 0, s))
+    return -1;
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  for (int q = 0; q < c.n_pose_sel; ++q)
+    std::memcpy(c.cov_pose36 + (size_t)q * 36, &hp[(size_t)slot_of_opt[g->lists.opt_of_pose[c.pose_sel[q]]] * 36],
+                36 * sizeof(double));
+  auto give = [](double *dst, const std::vector<double> &src) {
+    if (dst && !src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(double));
+  };
+  if (!cand) give(c.cov_rel36, hrel);
+  give(c.cov_cross36, hcross);
+  give(c.d2, hd2);
+  give(c.r6, hr);
+  give(c.innov36, hP);
+  if (dropped_pivots) *dropped_pivots = bad_now;
+  return 0;
 }
 
 }  // namespace
@@ -813,6 +928,65 @@ int ba_pgraph_info(ba_pgraph *g, int64_t out8[8]) {
   out8[5] = g->sched.nlev;
   out8[6] = (int64_t)g->image_bytes;
   out8[7] = g->bad_pivots;
+  return 0;
+}
+
+int ba_pgraph_cov_check(int n_pose, const uint8_t *pose_fixed, int n_pose_sel, const int32_t *pose_sel,
+                        const double *cov_pose36, int64_t n_pair, const int32_t *pair_j, const int32_t *pair_k,
+                        const double *cov_rel36, int64_t n_cand, const int32_t *cand_j, const int32_t *cand_k,
+                        const double *Z12, const double *Omega36, const double *d2) {
+  std::string err;
+  if (ba::pgraph_cov_validate_host(n_pose, pose_fixed, n_pose_sel, pose_sel, cov_pose36, n_pair, pair_j, pair_k,
+                                   cov_rel36, n_cand, cand_j, cand_k, Z12, Omega36, d2, &err))
+    return fail(err);
+  return 0;
+}
+
+int ba_pgraph_covariance(ba_pgraph *g, int n_pose_sel, const int32_t *pose_sel, double *cov_pose36, int64_t n_pair,
+                         const int32_t *pair_j, const int32_t *pair_k, double *cov_cross36, double *cov_rel36,
+                         int64_t *dropped_pivots) {
+  if (!g) return fail("ba_pgraph_covariance: null graph");
+  if (ba_pgraph_cov_check(g->n_pose, g->fixed.data(), n_pose_sel, pose_sel, cov_pose36, n_pair, pair_j, pair_k,
+                          cov_rel36, 0, nullptr, nullptr, nullptr, nullptr, nullptr))
+    return -1;
+  PgCovCall c;
+  c.n_pose_sel = n_pose_sel;
+  c.pose_sel = pose_sel;
+  c.cov_pose36 = cov_pose36;
+  c.n_entry = n_pair;
+  c.entry_j = pair_j;
+  c.entry_k = pair_k;
+  c.cov_cross36 = n_pair > 0 ? cov_cross36 : nullptr;
+  c.cov_rel36 = cov_rel36;
+  return pg_cov_run(g, "ba_pgraph_covariance", c, dropped_pivots);
+}
+
+int ba_pgraph_gate(ba_pgraph *g, int64_t n_cand, const int32_t *cand_j, const int32_t *cand_k, const double *Z12,
+                   const double *Omega36, double *d2, double *r6, double *innov36, int64_t *dropped_pivots) {
+  if (!g) return fail("ba_pgraph_gate: null graph");
+  if (ba_pgraph_cov_check(g->n_pose, g->fixed.data(), 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, n_cand,
+                          cand_j, cand_k, Z12, Omega36, d2))
+    return -1;
+  PgCovCall c;
+  c.n_entry = n_cand;
+  c.entry_kind = ba::kPgCovCand;
+  c.entry_j = cand_j;
+  c.entry_k = cand_k;
+  c.Z12 = Z12;
+  c.Omega36 = Omega36;
+  c.d2 = d2;
+  c.r6 = n_cand > 0 ? r6 : nullptr;
+  c.innov36 = n_cand > 0 ? innov36 : nullptr;
+  return pg_cov_run(g, "ba_pgraph_gate", c, dropped_pivots);
+}
+
+int ba_pgraph_cov_info(ba_pgraph *g, int64_t out4[4]) {
+  if (!g || !out4) return fail("ba_pgraph_cov_info: bad argument");
+  const int bw = ba::cov_batch_cols(g->d.npad, g->h->knobs.run);
+  out4[0] = bw;
+  out4[1] = ba::kCovGroupCols;
+  out4[2] = g->cov_batches;
+  out4[3] = (int64_t)g->d.npad * bw * (int64_t)sizeof(double);
   return 0;
 }
 

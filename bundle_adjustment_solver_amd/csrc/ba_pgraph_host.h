@@ -108,5 +108,161 @@ inline void pgraph_tile_adjacency(const PgraphLists &l, int poses_per_tile, int 
   }
 }
 
+// ---- covariance blocks and the chi-square gate (ba_pgraph_covariance / ba_pgraph_gate;
+// ---- DESIGN.md §6m) -------------------------------------------------------------------------
+
+// Cholesky of the 6x6 matrix whose lower triangle is in O (row-major); false at a pivot that is
+// not positive (or not finite).  The same loop as the device's (ba_pgraph_cov.hip).
+inline bool pgraph_chol6_host(const double *O) {
+  double L[36];
+  for (int c = 0; c < 6; ++c) {
+    double d = O[c * 6 + c];
+    for (int m = 0; m < c; ++m) d -= L[c * 6 + m] * L[c * 6 + m];
+    if (!(d > 0.0) || !std::isfinite(d)) return false;
+    const double s = std::sqrt(d);
+    L[c * 6 + c] = s;
+    for (int r = c + 1; r < 6; ++r) {
+      double v = O[r * 6 + c];
+      for (int m = 0; m < c; ++m) v -= L[r * 6 + m] * L[c * 6 + m];
+      L[r * 6 + c] = v / s;
+    }
+  }
+  return true;
+}
+
+// Everything ba_pgraph_cov_check refuses, in the order of the header's list; *err carries the
+// call's name.  The pairs follow the pair rules of ba_relative_check, the candidates the pair and
+// the value rules, in its wording ("(pair 3)", "(candidate 3)" for its "(factor 3)").
+inline int pgraph_cov_validate_host(int n_pose, const uint8_t *pose_fixed, int n_pose_sel, const int32_t *pose_sel,
+                                    const double *cov_pose36, int64_t n_pair, const int32_t *pair_j,
+                                    const int32_t *pair_k, const double *cov_rel36, int64_t n_cand,
+                                    const int32_t *cand_j, const int32_t *cand_k, const double *Z12,
+                                    const double *Omega36, const double *d2, std::string *err) {
+  const std::string cov = "ba_pgraph_covariance: ", gate = "ba_pgraph_gate: ";
+  auto bad = [&](const std::string &m) {
+    *err = m;
+    return -1;
+  };
+  if (n_pose < 1) return bad(cov + "n_pose must be >= 1");
+  if (n_pose_sel < 0 || n_pair < 0) return bad(cov + "negative selection size");
+  if (n_cand < 0) return bad(gate + "negative number of candidates");
+  if (n_pose_sel > 0 && !pose_sel) return bad(cov + "pose_sel is NULL for a non-empty selection");
+  if (n_pose_sel > 0 && !cov_pose36) return bad(cov + "cov_pose36 is NULL for a non-empty pose selection");
+  if (n_pair > 0 && !cov_rel36) return bad(cov + "cov_rel36 is NULL for a non-empty pair selection");
+  if (n_cand > 0 && !d2) return bad(gate + "d2 is NULL for a non-empty candidate list");
+  for (int s = 0; s < n_pose_sel; ++s) {
+    const int u = pose_sel[s];
+    if (u < 0 || u >= n_pose)
+      return bad(cov + "pose_sel[" + std::to_string(s) + "] = " + std::to_string(u) + " is out of range");
+    if (pose_fixed && pose_fixed[u])
+      return bad(cov + "pose_sel[" + std::to_string(s) + "] = " + std::to_string(u) + " is a fixed pose");
+  }
+  // relative_validate_host says "factor"; here the entry is a pair or a candidate
+  auto renamed = [&](const std::string &call, const char *entry) {
+    const size_t at = err->rfind("factor ");
+    if (at != std::string::npos) err->replace(at, 7, std::string(entry) + " ");
+    *err = call + *err;
+    return -1;
+  };
+  if (relative_validate_host(kRelPairs, n_pose, pose_fixed, n_pair, pair_j, pair_k, nullptr, nullptr, err))
+    return renamed(cov, "pair");
+  if (relative_validate_host(kRelPairs | kRelValues, n_pose, pose_fixed, n_cand, cand_j, cand_k, Z12, Omega36, err))
+    return renamed(gate, "candidate");
+  for (int64_t c = 0; c < n_cand; ++c)
+    if (!pgraph_chol6_host(Omega36 + 36 * c))
+      return bad(gate + "Omega is not positive definite (candidate " + std::to_string(c) + ")");
+  return 0;
+}
+
+// One wave of k_pgcov_solve owns 16 right-hand sides: the six identity columns of the pose
+// opt[0] in its columns 0..5 and of opt[1] in 6..11 (optimisable indices; -1: no column, the
+// blocks of that member are zero).  kind 0: two selected poses, slot[a] = row of the pose
+// output; kind 1: the pair (j, k) = (pose[0], pose[1]), slot[0] = row of the pair outputs;
+// kind 2: a candidate likewise.  t0 = tile position of the first non-zero row.
+constexpr int kPgCovPoses = 0, kPgCovPair = 1, kPgCovCand = 2;
+struct PgCovGroup {
+  int32_t t0, kind;
+  int32_t opt[2], slot[2], pose[2];
+  int32_t pad_[8];
+};
+static_assert(sizeof(PgCovGroup) == 64, "PgCovGroup is one 64-byte record");
+
+// The groups of one call on a validated selection, each kind ordered by the tile of its first
+// non-zero row (ties: by column, then by input position): the distinct selected poses two per
+// wave as ba_covariance groups them, then one wave per pair or candidate (entry_kind), repeats
+// included.  pose_col: first image column per optimisable pose; nb: the tile order.
+// slot_of_opt[optimisable index] = row of the pose output or -1; *n_pose_rows = rows of it.
+inline void pgraph_cov_groups(const PgraphLists &l, const std::vector<int> &pose_col, int nb, int n_pose_sel,
+                              const int32_t *pose_sel, int64_t n_entry, const int32_t *entry_j,
+                              const int32_t *entry_k, int entry_kind, std::vector<PgCovGroup> *groups,
+                              std::vector<int32_t> *slot_of_opt, int *n_pose_rows) {
+  struct Item {
+    int t0, col;
+    int64_t idx;
+  };
+  auto less = [](const Item &a, const Item &b) {
+    return a.t0 != b.t0 ? a.t0 < b.t0 : a.col != b.col ? a.col < b.col : a.idx < b.idx;
+  };
+  groups->clear();
+  slot_of_opt->assign((size_t)l.N, -1);
+  std::vector<Item> poses;
+  for (int s = 0; s < n_pose_sel; ++s) {
+    const int j = l.opt_of_pose[pose_sel[s]];
+    poses.push_back({pose_col[j] / nb, pose_col[j], j});
+  }
+  std::sort(poses.begin(), poses.end(), less);
+  poses.erase(std::unique(poses.begin(), poses.end(), [](const Item &a, const Item &b) { return a.idx == b.idx; }),
+              poses.end());
+  *n_pose_rows = (int)poses.size();
+  for (size_t k = 0; k < poses.size(); k += 2) {
+    PgCovGroup g{};
+    g.kind = kPgCovPoses;
+    g.t0 = poses[k].t0;
+    for (int a = 0; a < 2; ++a) {
+      const bool has = k + a < poses.size();
+      g.opt[a] = has ? (int32_t)poses[k + a].idx : -1;
+      g.slot[a] = has ? (int32_t)(k + a) : -1;
+      g.pose[a] = has ? l.opt_pose[(size_t)poses[k + a].idx] : -1;
+      if (has) (*slot_of_opt)[(size_t)poses[k + a].idx] = (int32_t)(k + a);
+    }
+    groups->push_back(g);
+  }
+  std::vector<Item> entries;
+  for (int64_t p = 0; p < n_entry; ++p) {
+    const int a = l.opt_of_pose[entry_j[p]], b = l.opt_of_pose[entry_k[p]];
+    const int ca = a >= 0 ? pose_col[a] : INT32_MAX, cb = b >= 0 ? pose_col[b] : INT32_MAX;
+    const int c0 = std::min(ca, cb);  // (validated: not both fixed)
+    entries.push_back({c0 / nb, c0, p});
+  }
+  std::sort(entries.begin(), entries.end(), less);
+  for (const Item &it : entries) {
+    PgCovGroup g{};
+    g.kind = entry_kind;
+    g.t0 = it.t0;
+    g.pose[0] = entry_j[it.idx];
+    g.pose[1] = entry_k[it.idx];
+    g.opt[0] = l.opt_of_pose[g.pose[0]];
+    g.opt[1] = l.opt_of_pose[g.pose[1]];
+    g.slot[0] = g.slot[1] = (int32_t)it.idx;
+    groups->push_back(g);
+  }
+}
+
+// Per tile position t of a schedule: the positions s < t with a structurally non-zero factor
+// tile L(t, s), ascending (row_ptr / rows: per position its row tiles, the rhs block ncb among them).
+inline void pgraph_cov_tile_rows(int ncb, const std::vector<int> &row_ptr, const std::vector<int> &rows,
+                                 std::vector<int> *trow_ptr, std::vector<int> *trow) {
+  std::vector<std::vector<int>> by_row((size_t)ncb);
+  for (int p = 0; p < ncb; ++p)
+    for (int a = row_ptr[p]; a < row_ptr[p + 1]; ++a)
+      if (rows[a] < ncb) by_row[rows[a]].push_back(p);
+  trow_ptr->assign((size_t)ncb + 1, 0);
+  trow->clear();
+  for (int t = 0; t < ncb; ++t) {
+    trow->insert(trow->end(), by_row[t].begin(), by_row[t].end());
+    (*trow_ptr)[t + 1] = (int)trow->size();
+  }
+}
+
 }  // namespace ba
 #endif  // BA_PGRAPH_HOST_H_

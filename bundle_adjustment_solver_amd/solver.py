@@ -313,6 +313,28 @@ def relative_residual(T_j12, T_k12, Z12):
     return se3_log(_T44_to_12(Tj @ rigid_inverse(Tk) @ rigid_inverse(Z))[0])
 
 
+def relative_adjoint(T_j12, T_k12):
+    """Ad(E) of E = T_j T_k^-1 = [R, t]: [[R, [t]x R], [0, R]] (6, 6), the device's rel_Ad
+    (csrc/ba_rel_fn.h) in numpy; the factor's Jacobian with respect to xi_k is -Ad(E)."""
+    E = _T12_to_44(T_j12)[0] @ rigid_inverse(_T12_to_44(T_k12)[0])
+    R, t = E[:3, :3], E[:3, 3]
+    tx = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+    Ad = np.zeros((6, 6))
+    Ad[:3, :3] = Ad[3:, 3:] = R
+    Ad[:3, 3:] = tx @ R
+    return Ad
+
+
+def relative_covariance(T_j12, T_k12, S_jj, S_jk, S_kk):
+    """Sigma_E of BaPoseGraph.covariance on the host (numpy only): E = T_j T_k^-1 moves to first
+    order by xi_E = xi_j - Ad(E) xi_k, hence
+        Sigma_E = S_jj - S_jk Ad^T - Ad S_jk^T + Ad S_kk Ad^T.
+    A fixed pose has zero blocks: with j fixed this is Ad S_kk Ad^T, with k fixed S_jj."""
+    Ad = relative_adjoint(T_j12, T_k12)
+    S_jj, S_jk, S_kk = (np.asarray(S, np.float64).reshape(6, 6) for S in (S_jj, S_jk, S_kk))
+    return S_jj - S_jk @ Ad.T - Ad @ S_jk.T + Ad @ S_kk @ Ad.T
+
+
 class BaProblem:
     """Thin numpy wrapper over one ba_handle, in the solver's SCALED units.
 
@@ -1578,6 +1600,47 @@ def pgraph_check(pose_T, pose_fixed, rels):
                                       len(j), _ip(j), _ip(k), _dp(Z), _dp(Om)), "ba_pgraph_check")
 
 
+def _pair_arrays(pairs):
+    """pairs: None, or (j, k) index arrays, or an (n, 2) array -> (j, k) int32"""
+    if pairs is None:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32)
+    if isinstance(pairs, tuple) and len(pairs) == 2 and np.ndim(pairs[0]) == 1:
+        j, k = pairs
+    else:
+        jk = np.asarray(pairs, np.int64).reshape(-1, 2)
+        j, k = jk[:, 0], jk[:, 1]
+    j = np.ascontiguousarray(j, np.int32).reshape(-1)
+    k = np.ascontiguousarray(k, np.int32).reshape(-1)
+    if len(j) != len(k):
+        raise ValueError("pairs: one j and one k per pair")
+    return j, k
+
+
+def _candidate_arrays(j, k, Z, Omega):
+    j, k = _pair_arrays((np.atleast_1d(j), np.atleast_1d(k)))
+    Z = np.ascontiguousarray(Z, np.float64).reshape(-1, 12)
+    Om = np.ascontiguousarray(Omega, np.float64).reshape(-1, 36)
+    if Z.shape[0] != len(j) or Om.shape[0] != len(j):
+        raise ValueError("candidates: needs j (n,), k (n,), Z (n, 12), Omega (n, 6, 6)")
+    return j, k, Z, Om
+
+
+def pgraph_cov_check(n_pose, pose_fixed, pose_sel=None, pairs=None, candidates=None):
+    """Host-only validation of BaPoseGraph.covariance / gate (ba_pgraph_cov_check); raises BaError.
+    pose_sel: user indices; pairs: (j, k) arrays or (n, 2); candidates: dict(j, k, Z, Omega)."""
+    fx = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
+    ps = np.zeros(0, np.int32) if pose_sel is None else np.ascontiguousarray(pose_sel, np.int32).reshape(-1)
+    pj, pk = _pair_arrays(pairs)
+    c = candidates
+    cj, ck, Z, Om = _candidate_arrays(c["j"], c["k"], c["Z"], c["Omega"]) if c is not None else \
+        _candidate_arrays([], [], np.zeros((0, 12)), np.zeros((0, 36)))
+    out = np.zeros(1)   # the outputs only have to be there
+    check(_lib.load().ba_pgraph_cov_check(int(n_pose), None if fx is None else _up(fx), len(ps), _ip(ps), _dp(out),
+                                          len(pj), _ip(pj), _ip(pk), _dp(out), len(cj), _ip(cj), _ip(ck),
+                                          _dp(Z) if Z.size else None, _dp(Om) if Om.size else None, _dp(out)),
+          "ba_pgraph_cov_check")
+
+
 class BaPoseGraph:
     """Pose-graph optimisation (ba_pgraph_* of include/ba_hip.h): chi-square
     Levenberg-Marquardt over relative-pose factors alone.  pose_T (n, 12) T_jw in scaled
@@ -1603,6 +1666,7 @@ class BaPoseGraph:
                              "Omega (F, 6, 6)")
         pgraph_check(T, fx, dict(j=j, k=k, Z=Z, Omega=Om))   # refusals need no device
         self.n_pose, self.n_rel = T.shape[0], len(j)
+        self._fixed = np.zeros(self.n_pose, np.uint8) if fx is None else fx.copy()
         self._owner = BaProblem(device) if owner is None else owner
         g = C.c_void_p()
         check(self.lib.ba_pgraph_create(C.byref(g), self._owner.h, self.n_pose, _dp(T),
@@ -1694,6 +1758,44 @@ class BaPoseGraph:
         v = C.c_double(0.0)
         check(self.lib.ba_pgraph_last_ms(self.g, C.byref(v)), "ba_pgraph_last_ms")
         return v.value
+
+    def covariance(self, pose_sel=None, pairs=None):
+        """-> (cov_pose (n, 6, 6), cov_cross (p, 6, 6), cov_rel (p, 6, 6)): blocks of the inverse
+        of system()'s H at the poses the object holds (ba_pgraph_covariance):
+        Sigma_jj per selected pose, Sigma_jk and the covariance Sigma_E of T_j T_k^-1 per pair.
+        pose_sel: user indices of optimisable poses (None: all of them); pairs: (j, k) arrays or
+        (p, 2).  Scaled units.  self.dropped_pivots: non-positive pivots of the factorisation."""
+        ps = np.flatnonzero(self._fixed == 0).astype(np.int32) if pose_sel is None else \
+            np.ascontiguousarray(pose_sel, np.int32).reshape(-1)
+        pj, pk = _pair_arrays(pairs)
+        cp, cc, cr = np.zeros((len(ps), 6, 6)), np.zeros((len(pj), 6, 6)), np.zeros((len(pj), 6, 6))
+        dropped = C.c_int64(0)
+        check(self.lib.ba_pgraph_covariance(self.g, len(ps), _ip(ps) if len(ps) else None,
+                                            _dp(cp) if len(ps) else None, len(pj), _ip(pj) if len(pj) else None,
+                                            _ip(pk) if len(pj) else None, _dp(cc) if len(pj) else None,
+                                            _dp(cr) if len(pj) else None, C.byref(dropped)), "ba_pgraph_covariance")
+        self.dropped_pivots = dropped.value
+        return cp, cc, cr
+
+    def gate(self, j, k, Z, Omega):
+        """-> (d2 (n,), r (n, 6), P (n, 6, 6)) of loop-closure candidates shaped like factors
+        (ba_pgraph_gate): r = se3_log(T_j T_k^-1 Z^-1), P = Sigma_E + Omega^-1, d2 = r^T P^-1 r,
+        to be compared with a chi-square quantile of 6 degrees of freedom (22.46 at 0.999)."""
+        cj, ck, Zs, Om = _candidate_arrays(j, k, Z, Omega)
+        n = len(cj)
+        d2, r, P = np.zeros(n), np.zeros((n, 6)), np.zeros((n, 6, 6))
+        dropped = C.c_int64(0)
+        check(self.lib.ba_pgraph_gate(self.g, n, _ip(cj) if n else None, _ip(ck) if n else None,
+                                      _dp(Zs) if n else None, _dp(Om) if n else None, _dp(d2) if n else None,
+                                      _dp(r) if n else None, _dp(P) if n else None, C.byref(dropped)), "ba_pgraph_gate")
+        self.dropped_pivots = dropped.value
+        return d2, r, P
+
+    def cov_info(self):
+        """Column batches of covariance / gate on this graph (BA_COV_BATCH of the borrowed handle overrides)"""
+        v = (C.c_int64 * 4)()
+        check(self.lib.ba_pgraph_cov_info(self.g, v), "ba_pgraph_cov_info")
+        return dict(batch_cols=int(v[0]), cols_per_wave=int(v[1]), batches=int(v[2]), workspace_bytes=int(v[3]))
 
 
 class BaStream:
@@ -2212,15 +2314,9 @@ class FullBundleAdjustmentSolver:
             summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change
             summary.threshold_step_size_ = options.convergence_handle.threshold_step_size
             summary.convergence_status_ = True
-        rels = self._relative_arrays()
-        if rels is None or not self.num_total_poses_:
-            raise RuntimeError("SolvePoseGraph: poses (AddPose) and factors (AddRelativePose) must be added first")
-        T_jw = np.concatenate(self._pose_T_jw, axis=0)
-        pf = np.zeros(self.num_total_poses_, np.uint8)
-        pf[list(self._pose_fixed)] = 1
         c_opt = options.to_c()
         c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
-        g = BaPoseGraph(T_jw, pf, rels, self.device)   # applies the kernels that the factors carry
+        g = self._pose_graph("SolvePoseGraph")
         try:
             rows, converged = g.solve(c_opt)
             T_new = g.poses()
@@ -2232,6 +2328,72 @@ class FullBundleAdjustmentSolver:
         self._pose_T_jw = [T_new]
         n_pt = self.num_total_points_
         return self._write_back(T_new, np.zeros((n_pt, 3)), np.zeros(n_pt, bool), rows, converged, summary, t0)
+
+    def _pose_graph(self, what):
+        """the registered poses and the factors of AddRelativePose as a BaPoseGraph, robust
+        kernels included; needs no FinalizeParameters"""
+        rels = self._relative_arrays()
+        if rels is None or not self.num_total_poses_:
+            raise RuntimeError("%s: poses (AddPose) and factors (AddRelativePose) must be added first" % what)
+        T_jw = np.concatenate(self._pose_T_jw, axis=0)
+        pf = np.zeros(self.num_total_poses_, np.uint8)
+        pf[list(self._pose_fixed)] = 1
+        return BaPoseGraph(T_jw, pf, rels, self.device)   # applies the kernels that the factors carry
+
+    def _pose_graph_unit(self, what, more=()):
+        """the one unit sigma_pixel SCALER of every factor (and of `more`): Sigma and d2 have
+        caller's units only if there is one"""
+        units = list(self._relative_units) + list(more)
+        for u in units:
+            if u != units[0]:
+                raise RuntimeError("%s: the factors and candidates were given with sigma_pixel = %g and %g; "
+                                   "a covariance in the caller's units needs one value"
+                                   % (what, units[0] / SCALER, u / SCALER))
+        return units[0] if units else SCALER
+
+    def ComputePoseGraphCovariance(self, poses, pairs=()):
+        """(new) -> (cov_pose (n, 6, 6), cov_cross (p, 6, 6), cov_rel (p, 6, 6)) of the pose graph
+        that SolvePoseGraph solves, at the registered poses as they are now (BaPoseGraph.covariance,
+        DESIGN.md §6m; nothing is solved, FinalizeParameters is not needed): the marginal
+        covariance of each pose of `poses` (objects or handles, optimisable), and for each
+        (pose_j, pose_k) of `pairs` the cross block Sigma_jk and the covariance of the relative
+        pose T_jw T_kw^-1.  Caller's units (covariance_to_user_units) for the sigma_pixel the
+        factors were added with; factors with different sigma_pixel raise RuntimeError."""
+        unit = self._pose_graph_unit("ComputePoseGraphCovariance")
+
+        def handles(objs):
+            hs = [self._pose_handle(o) for o in objs]
+            if any(h is None for h in hs):
+                raise RuntimeError("There is no pointer in the BA pose pool.")
+            return np.asarray(hs, np.int32)
+        ps = handles(poses)
+        pj, pk = handles([p[0] for p in pairs]), handles([p[1] for p in pairs])
+        g = self._pose_graph("ComputePoseGraphCovariance")
+        try:
+            blocks = g.covariance(ps, (pj, pk))
+        finally:
+            g.close()
+        return tuple(covariance_to_user_units(b, np.zeros((0, 3, 3)), unit / SCALER)[0] for b in blocks)
+
+    def GateLoopClosures(self, candidates):
+        """(new) -> d2 (n,) of loop-closure candidates against the pose graph at the registered
+        poses, BEFORE they are added (BaPoseGraph.gate): the squared Mahalanobis
+        distance of each candidate's residual under the estimate's own uncertainty plus the
+        candidate's, in the caller's units; accept below a chi-square quantile of 6 degrees of
+        freedom (22.46 at 0.999).  A candidate is a dict with the keys of AddRelativePose
+        (pose_j, pose_k, measurement, information, optionally sigma_pixel = 1.0), and every
+        candidate and factor must have been given with one sigma_pixel (RuntimeError otherwise)."""
+        sig = [float(c.get("sigma_pixel", 1.0)) for c in candidates]
+        unit = self._pose_graph_unit("GateLoopClosures", [v * SCALER for v in sig])
+        facs = [dict(pose_j=c["pose_j"], pose_k=c["pose_k"], measurement=c["measurement"],
+                     information=c["information"], robust=c.get("robust")) for c in candidates]
+        sr = self._scaled_relatives("GateLoopClosures", [self], [facs], unit / SCALER)[0]
+        g = self._pose_graph("GateLoopClosures")
+        try:
+            d2 = g.gate(sr["j"], sr["k"], sr["Z"], sr["Omega"])[0]
+        finally:
+            g.close()
+        return d2 / (unit * unit)
 
     def GetRelativeWeights(self):
         """(new) -> (s, w) of the last SolvePoseGraph, one entry per factor in the order of

@@ -12,6 +12,7 @@
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "core/solver_option_and_summary.h"
@@ -19,6 +20,7 @@
 #include "utility/timer.h"
 
 struct ba_handle;  // include/ba_hip.h
+struct ba_pgraph;
 struct ba_batch;
 
 namespace visual_navigation {
@@ -262,6 +264,25 @@ class FullBundleAdjustmentSolver {
   // a pose that was never registered; what the library refuses (the same pose twice, both
   // fixed, a non-finite value, a sharded solver) throws at FinalizeParameters.
   void AddRelativePose(const RelativePose &factor, double sigma_pixel = 1.0);
+  // (new) Covariance blocks of the pose graph that SolvePoseGraph solves, at the solver's
+  // current values; nothing is solved and FinalizeParameters is not needed
+  // (ba_pgraph_covariance of include/ba_hip.h, the definition is there).  cov_poses[s]: the
+  // marginal covariance of poses[s] (optimisable); for pairs[p] = {pose_j, pose_k}: cov_cross[p]
+  // = Sigma_jk (may be null) and cov_rel[p], the covariance of the relative pose T_jw T_kw^-1,
+  // first order, at lambda = 0.  Tangent and units as ComputeCovariance, for the sigma_pixel the
+  // factors were added with: factors with different sigma_pixel throw std::runtime_error naming
+  // the two values.  Returns false if the factorisation dropped a pivot (no fixed pose).
+  bool ComputePoseGraphCovariance(const std::vector<_BA_Pose *> &poses,
+                                  const std::vector<std::pair<_BA_Pose *, _BA_Pose *>> &pairs,
+                                  std::vector<Eigen::Matrix<double, 6, 6>> *cov_poses,
+                                  std::vector<Eigen::Matrix<double, 6, 6>> *cov_cross,
+                                  std::vector<Eigen::Matrix<double, 6, 6>> *cov_rel);
+  // (new) The chi-square gate for loop-closure candidates BEFORE they are added
+  // (ba_pgraph_gate): (*d2)[c] = r^T (Sigma_E + information^-1)^-1 r of candidate c in the
+  // caller's units, to be compared with a chi-square quantile of 6 degrees of freedom (22.46
+  // at 0.999).  A candidate is a factor of AddRelativePose (no robust kernel), sigma_pixel the
+  // one of the factors (std::runtime_error naming the two values otherwise).
+  bool GateLoopClosures(const std::vector<RelativePose> &candidates, double sigma_pixel, std::vector<double> *d2);
   // the C-ABI handle behind the finalized problem (nullptr before FinalizeParameters):
   // for the readers of include/ba_hip.h; indices there are registration order
   ba_handle *GetHandle() const { return handle_; }
@@ -337,6 +358,11 @@ class FullBundleAdjustmentSolver {
                             const std::vector<std::vector<RelativePose>> *in_relatives, double sigma_pixel,
                             RelativeArrays *out);
   static int SetRelatives(ba_batch *batch, const RelativeArrays &r);
+  // the registered poses and the factors of AddRelativePose as a graph with its kernels set, on
+  // the finalized problem's handle or one of its own (*h); throws on a refusal
+  ba_pgraph *CreatePoseGraph(const char *who, ba_handle **h);
+  // the one unit sigma_pixel scaler_ of the factors and `more` (throws if there are two)
+  double PoseGraphUnit(const char *who, const std::vector<double> &more) const;
   RelativeArrays relatives_;  // AddRelativePose: j, k, Z, Omega of this solver's factors (off unused)
   std::vector<double> report_s_, report_w_;  // the factor report of the last SolvePoseGraph
   // the options' thresholds and iteration limit into a Summary (nullptr: nothing)

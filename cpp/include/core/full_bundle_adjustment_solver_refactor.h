@@ -77,6 +77,17 @@ class FullBundleAdjustmentSolverRefactor {
   bool SolvePoseGraph(Options options, Summary *summary = nullptr);
   // (new) see FullBundleAdjustmentSolver::GetRelativeWeights
   void GetRelativeWeights(std::vector<double> *s, std::vector<double> *w) const { impl_.GetRelativeWeights(s, w); }
+  // (new) see FullBundleAdjustmentSolver::ComputePoseGraphCovariance and GateLoopClosures
+  bool ComputePoseGraphCovariance(const std::vector<Pose *> &poses, const std::vector<std::pair<Pose *, Pose *>> &pairs,
+                                  std::vector<Eigen::Matrix<double, 6, 6>> *cov_poses,
+                                  std::vector<Eigen::Matrix<double, 6, 6>> *cov_cross,
+                                  std::vector<Eigen::Matrix<double, 6, 6>> *cov_rel) {
+    return impl_.ComputePoseGraphCovariance(poses, pairs, cov_poses, cov_cross, cov_rel);
+  }
+  bool GateLoopClosures(const std::vector<FullBundleAdjustmentSolver::RelativePose> &candidates, double sigma_pixel,
+                        std::vector<double> *d2) {
+    return impl_.GateLoopClosures(candidates, sigma_pixel, d2);
+  }
 
   // (new) covariance blocks of the current state, see FullBundleAdjustmentSolver::ComputeCovariance:
   // same units, same tangent convention (world-to-body T_jw = inverse(*pose), T_jw <- exp(xi) T_jw)

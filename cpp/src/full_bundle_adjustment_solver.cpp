@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <array>
+#include <sstream>
 #include <stdexcept>
 
 #include "ba_hip.h"
@@ -423,33 +424,15 @@ bool FullBundleAdjustmentSolver::SolvePoseGraph(Options options, Summary *summar
   timer::StopWatch stopwatch("BundleAdjustmentSolver::SolvePoseGraph");
   stopwatch.Start();
   BeginSummary(summary, options);
-  if (poses_.empty() || relatives_.j.empty())
-    throw std::runtime_error("SolvePoseGraph: poses (AddPose) and factors (AddRelativePose) must be added first");
   std::vector<double> T(12 * poses_.size());
-  std::vector<uint8_t> pose_fixed(poses_.size(), 0);
-  for (size_t p = 0; p < poses_.size(); ++p) {
-    Pack12(T_jw_[p], &T[12 * p]);
-    pose_fixed[p] = fixed_poses_.count(static_cast<int>(p)) > 0;
-  }
   const ba_options o = PackOptions(options, gauss_newton_);
   std::vector<ba_iter_info> rows(static_cast<size_t>(std::max(1, o.max_num_iterations)));
   int n_iter = 0, converged = 0;
   // the graph borrows a handle for its device and stream: the finalized problem's, or one of its own
-  ba_handle *h = handle_;
-  if (h == nullptr) Check(ba_create(&h, device_id_), "ba_create");
-  ba_pgraph *g = nullptr;
-  int rc = ba_pgraph_create(&g, h, static_cast<int>(poses_.size()), T.data(), pose_fixed.data(),
-                            static_cast<int64_t>(relatives_.j.size()), relatives_.j.data(), relatives_.k.data(),
-                            relatives_.Z.data(), relatives_.Omega.data());
-  const char *what = "ba_pgraph_create";
-  if (rc == 0) {
-    rc = ba_pgraph_set_robust(g, relatives_.kind.data(), relatives_.scale.data());
-    what = "ba_pgraph_set_robust";
-  }
-  if (rc == 0) {
-    rc = ba_pgraph_solve(g, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged);
-    what = "ba_pgraph_solve";
-  }
+  ba_handle *h = nullptr;
+  ba_pgraph *g = CreatePoseGraph("SolvePoseGraph", &h);
+  int rc = ba_pgraph_solve(g, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged);
+  const char *what = "ba_pgraph_solve";
   if (rc == 0) {
     rc = ba_pgraph_get_poses(g, T.data());
     what = "ba_pgraph_get_poses";
@@ -481,6 +464,124 @@ void FullBundleAdjustmentSolver::GetRelativeWeights(std::vector<double> *s, std:
   if (report_w_.empty()) throw std::runtime_error("GetRelativeWeights: SolvePoseGraph has not run");
   if (s != nullptr) *s = report_s_;
   if (w != nullptr) *w = report_w_;
+}
+
+ba_pgraph *FullBundleAdjustmentSolver::CreatePoseGraph(const char *who, ba_handle **h) {
+  const std::string name(who);
+  if (poses_.empty() || relatives_.j.empty())
+    throw std::runtime_error(name + ": poses (AddPose) and factors (AddRelativePose) must be added first");
+  std::vector<double> T(12 * poses_.size());
+  std::vector<uint8_t> pose_fixed(poses_.size(), 0);
+  for (size_t p = 0; p < poses_.size(); ++p) {
+    Pack12(T_jw_[p], &T[12 * p]);
+    pose_fixed[p] = fixed_poses_.count(static_cast<int>(p)) > 0;
+  }
+  *h = handle_;
+  if (*h == nullptr) Check(ba_create(h, device_id_), "ba_create");
+  ba_pgraph *g = nullptr;
+  int rc = ba_pgraph_create(&g, *h, static_cast<int>(poses_.size()), T.data(), pose_fixed.data(),
+                            static_cast<int64_t>(relatives_.j.size()), relatives_.j.data(), relatives_.k.data(),
+                            relatives_.Z.data(), relatives_.Omega.data());
+  const char *what = "ba_pgraph_create";
+  if (rc == 0) {
+    rc = ba_pgraph_set_robust(g, relatives_.kind.data(), relatives_.scale.data());
+    what = "ba_pgraph_set_robust";
+  }
+  if (rc != 0) {
+    const std::string err = ba_last_error();
+    ba_pgraph_destroy(g);
+    if (*h != handle_) ba_destroy(*h);
+    throw std::runtime_error(std::string(what) + ": " + err);
+  }
+  return g;
+}
+
+double FullBundleAdjustmentSolver::PoseGraphUnit(const char *who, const std::vector<double> &more) const {
+  std::vector<double> units(relatives_.unit);
+  units.insert(units.end(), more.begin(), more.end());
+  for (double u : units)
+    if (u != units[0]) {
+      std::ostringstream m;
+      m << who << ": the factors and candidates were given with sigma_pixel = " << units[0] / scaler_ << " and "
+        << u / scaler_ << "; a covariance in the caller's units needs one value";
+      throw std::runtime_error(m.str());
+    }
+  return units.empty() ? static_cast<double>(scaler_) : units[0];
+}
+
+bool FullBundleAdjustmentSolver::ComputePoseGraphCovariance(const std::vector<_BA_Pose *> &poses,
+                                                            const std::vector<std::pair<_BA_Pose *, _BA_Pose *>> &pairs,
+                                                            std::vector<Eigen::Matrix<double, 6, 6>> *cov_poses,
+                                                            std::vector<Eigen::Matrix<double, 6, 6>> *cov_cross,
+                                                            std::vector<Eigen::Matrix<double, 6, 6>> *cov_rel) {
+  const char *who = "ComputePoseGraphCovariance";
+  const double unit = PoseGraphUnit(who, {});
+  const auto index = [this](_BA_Pose *p) {
+    const auto it = pose_index_.find(p);
+    if (it == pose_index_.end()) throw std::runtime_error("There is no pointer in the BA pose pool.");
+    return static_cast<int32_t>(it->second);
+  };
+  std::vector<int32_t> ps, pj, pk;
+  for (_BA_Pose *p : poses) ps.push_back(index(p));
+  for (const auto &jk : pairs) {
+    pj.push_back(index(jk.first));
+    pk.push_back(index(jk.second));
+  }
+  if ((!ps.empty() && cov_poses == nullptr) || (!pj.empty() && cov_rel == nullptr))
+    throw std::runtime_error(std::string(who) + ": null output for a non-empty selection");
+  std::vector<double> cp(36 * ps.size()), cc(36 * pj.size()), cr(36 * pj.size());
+  int64_t dropped = 0;
+  ba_handle *h = nullptr;
+  ba_pgraph *g = CreatePoseGraph(who, &h);
+  const int rc = ba_pgraph_covariance(g, static_cast<int>(ps.size()), ps.empty() ? nullptr : ps.data(),
+                                      ps.empty() ? nullptr : cp.data(), static_cast<int64_t>(pj.size()),
+                                      pj.empty() ? nullptr : pj.data(), pj.empty() ? nullptr : pk.data(),
+                                      pj.empty() || cov_cross == nullptr ? nullptr : cc.data(),
+                                      pj.empty() ? nullptr : cr.data(), &dropped);
+  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
+  ba_pgraph_destroy(g);
+  if (h != handle_) ba_destroy(h);
+  if (rc != 0) throw std::runtime_error(err);
+  // scaled units -> the caller's: Sigma_user = unit^2 D Sigma_scaled D, D = diag(100 I, I)
+  const auto to_user = [&](const std::vector<double> &in, std::vector<Eigen::Matrix<double, 6, 6>> *out) {
+    if (out == nullptr) return;
+    out->resize(in.size() / 36);
+    for (size_t s = 0; s < out->size(); ++s)
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) {
+          const double dr = r < 3 ? static_cast<double>(inverse_scaler_) : 1.0;
+          const double dc = c < 3 ? static_cast<double>(inverse_scaler_) : 1.0;
+          (*out)[s](r, c) = (unit * unit) * (dr * in[36 * s + 6 * r + c] * dc);
+        }
+  };
+  to_user(cp, cov_poses);
+  to_user(cc, cov_cross);
+  to_user(cr, cov_rel);
+  return dropped == 0;
+}
+
+bool FullBundleAdjustmentSolver::GateLoopClosures(const std::vector<RelativePose> &candidates, double sigma_pixel,
+                                                  std::vector<double> *d2) {
+  const char *who = "GateLoopClosures";
+  if (d2 == nullptr) throw std::runtime_error(std::string(who) + ": null output");
+  const double unit = PoseGraphUnit(who, std::vector<double>(candidates.size(), sigma_pixel * static_cast<double>(scaler_)));
+  RelativeArrays c;
+  const std::vector<std::vector<RelativePose>> lists(1, candidates);
+  PackRelatives({this}, who, &lists, sigma_pixel, &c);  // throws on a candidate that carries a kernel
+  d2->assign(candidates.size(), 0.0);
+  int64_t dropped = 0;
+  ba_handle *h = nullptr;
+  ba_pgraph *g = CreatePoseGraph(who, &h);
+  const bool any = !candidates.empty();
+  const int rc = ba_pgraph_gate(g, static_cast<int64_t>(candidates.size()), any ? c.j.data() : nullptr,
+                                any ? c.k.data() : nullptr, any ? c.Z.data() : nullptr, any ? c.Omega.data() : nullptr,
+                                any ? d2->data() : nullptr, nullptr, nullptr, &dropped);
+  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
+  ba_pgraph_destroy(g);
+  if (h != handle_) ba_destroy(h);
+  if (rc != 0) throw std::runtime_error(err);
+  for (double &v : *d2) v /= unit * unit;  // d2_user = d2_scaled / unit^2
+  return dropped == 0;
 }
 
 bool FullBundleAdjustmentSolver::ComputeCovariance(const std::vector<_BA_Pose *> &poses,

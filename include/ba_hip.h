@@ -1118,6 +1118,68 @@ int ba_pgraph_robust_check(int64_t n_rel, const int32_t *kind, const double *sca
  * may be NULL.  This is how a caller finds the closures to drop. */
 int ba_pgraph_factor_report(ba_pgraph *g, double *s, double *w);
 
+/* ---- covariance blocks of a pose graph and a chi-square gate ---------------
+ * How well the poses the object holds are determined, and whether a loop-closure candidate is
+ * consistent with them BEFORE it enters the graph (g2o's computeMarginals, GTSAM's Marginals;
+ * the robust kernels above act only after a false closure has bent the solve).
+ *
+ * System: H is exactly what ba_pgraph_get_system returns: lambda = 0, the accepted poses,
+ * w_f Omega_f for a factor with a robust kernel, w_f at those poses.  Sigma = H^-1 over the
+ * optimisable poses, scaled units, tangent xi = [v; omega] of T <- exp(xi) T; a fixed pose has
+ * zero blocks.  The call factorises H with the solve's launches (no level goes to the LDS tail
+ * kernel, so the whole factor stays in the image) and reads the blocks off the factor
+ * (csrc/ba_pgraph_cov.hip, fp64 MFMA, no atomics: the same bits run to run, in any selection
+ * and any batch split).
+ *   cov_pose36[s]   Sigma_jj of pose pose_sel[s] (6x6 row-major)
+ *   cov_cross36[p]  Sigma_jk of the pair (pair_j[p], pair_k[p]); may be NULL
+ *   cov_rel36[p]    Sigma_E, the covariance of the relative pose E = T_j T_k^-1, which moves to
+ *                   first order by xi_E = xi_j - Ad(E) xi_k (the factor's own Jacobians):
+ *                   Sigma_E = Sigma_jj - Sigma_jk Ad^T - Ad Sigma_kj + Ad Sigma_kk Ad^T;
+ *                   with j fixed it is Ad Sigma_kk Ad^T, with k fixed Sigma_jj
+ * pose_sel: USER indices of optimisable poses, any order, repeats allowed.  Pairs: user
+ * indices, the pair rules of ba_relative_check (in range, j != k, not both fixed), repeats and
+ * both orientations allowed; every pair is swept on its own.  Either selection may be empty
+ * (its outputs then NULL); with both empty the call factorises and writes nothing.
+ * dropped_pivots (may be NULL) receives the non-positive pivots THIS call's factorisation met.
+ * A graph without a fixed pose is singular at lambda = 0 and the result meaningless:
+ * dropped_pivots > 0 is how the caller learns of it.
+ *
+ * State: the poses, the controller, the robust kernels, ba_pgraph_last_ms and the pivot count
+ * of ba_pgraph_info are untouched: a solve after the call gives the bits it gives without.
+ * Refused (-1, ba_last_error names the entry, before anything touches the GPU; nothing
+ * changes): a null graph, a NULL output for a non-empty selection, a pose_sel entry out of
+ * range or naming a fixed pose, a pair that ba_relative_check would refuse as a factor.
+ * The right-hand sides (16 per wave: two selected poses, or one pair) go in column batches; the
+ * workspace, npad x batch x 8 bytes, is allocated for the call and freed on return. */
+int ba_pgraph_covariance(ba_pgraph *g, int n_pose_sel, const int32_t *pose_sel, double *cov_pose36,
+                         int64_t n_pair, const int32_t *pair_j, const int32_t *pair_k,
+                         double *cov_cross36 /* or NULL */, double *cov_rel36,
+                         int64_t *dropped_pivots);
+/* The gate.  A candidate (j, k, Z, Omega_z) has the shape of a factor: r = se3_log(E Z^-1),
+ * P = Sigma_E + Omega_z^-1 (the innovation covariance) and d2[c] = r^T P^-1 r, to be compared
+ * with a chi-square quantile of 6 degrees of freedom (22.46 at 0.999).  Sigma_E is first order
+ * and taken at lambda = 0, as above.  Only the lower triangle of Omega_z counts; no robust
+ * weight applies to a candidate.  r6 (6 per candidate) and innov36 (= P) may be NULL.  A P
+ * with a non-positive pivot yields d2 = NaN.  State, batching and dropped_pivots as above.
+ * Refused likewise: what ba_relative_check refuses (same rules, same wording, "candidate" for
+ * "factor"), and a candidate whose Omega_z is not positive definite (6x6 Cholesky of the
+ * mirrored lower triangle on the host; the message names the candidate). */
+int ba_pgraph_gate(ba_pgraph *g, int64_t n_cand, const int32_t *cand_j, const int32_t *cand_k,
+                   const double *Z12, const double *Omega36, double *d2, double *r6 /* or NULL */,
+                   double *innov36 /* or NULL */, int64_t *dropped_pivots);
+/* Host-only (no GPU): the validation of both calls on plain arrays: the fixed mask of the
+ * n_pose poses (NULL: none fixed), the selection and pairs of ba_pgraph_covariance, the
+ * candidates of ba_pgraph_gate, and the output pointers cov_pose36, cov_rel36 and d2.  0 or -1. */
+int ba_pgraph_cov_check(int n_pose, const uint8_t *pose_fixed, int n_pose_sel,
+                        const int32_t *pose_sel, const double *cov_pose36, int64_t n_pair,
+                        const int32_t *pair_j, const int32_t *pair_k, const double *cov_rel36,
+                        int64_t n_cand, const int32_t *cand_j, const int32_t *cand_k,
+                        const double *Z12, const double *Omega36, const double *d2);
+/* out4 = { columns of one batch on this graph (what fits 256 MiB of workspace, at most 16384;
+ * BA_COV_BATCH=<columns> of the borrowed handle overrides), columns per wave (16), batches the
+ * last ba_pgraph_covariance / ba_pgraph_gate ran, bytes of the workspace at that width } */
+int ba_pgraph_cov_info(ba_pgraph *g, int64_t out4[4]);
+
 #ifdef __cplusplus
 }
 #endif

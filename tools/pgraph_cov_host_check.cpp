@@ -1,0 +1,239 @@
+// Stand-alone host check of the covariance and gate calls of the pose graph: the validation
+// (pgraph_cov_validate_host of bundle_adjustment_solver_amd/csrc/ba_pgraph_host.h, the body of
+// ba_pgraph_cov_check) and the group building (pgraph_cov_groups, pgraph_cov_tile_rows), meant for
+// the host sanitizers:
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+//       tools/pgraph_cov_host_check.cpp -o /tmp/pgraph_cov_host_check && /tmp/pgraph_cov_host_check
+// No GPU and no HIP.  Every array is sized exactly, so that an access past an end is the
+// sanitizer's to find; arrays that a call must not read are null pointers.
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <random>
+#include <set>
+#include <vector>
+
+#include "../bundle_adjustment_solver_amd/csrc/ba_pgraph_host.h"
+
+#define REQUIRE(c)                                                        \
+  do {                                                                    \
+    if (!(c)) {                                                           \
+      std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); \
+      return 1;                                                           \
+    }                                                                     \
+  } while (0)
+
+static bool has(const std::string &s, const std::string &t) { return s.find(t) != s.npos; }
+
+// n poses, every third one fixed (pose 0 among them); a chain
+static int one_case(int n, int nb, std::mt19937 &gen) {
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<uint8_t> fixed((size_t)n);
+  for (int p = 0; p < n; ++p) fixed[p] = p % 3 == 0;
+  std::vector<int32_t> opt;
+  for (int p = 0; p < n; ++p)
+    if (!fixed[p]) opt.push_back(p);
+  if (opt.empty()) return 0;
+  std::string err;
+  double out = 0.0;
+  // ---- validation
+  std::vector<int32_t> sel;
+  for (int t = 0; t < 2 * n; ++t) sel.push_back(opt[gen() % opt.size()]);  // repeats, any order
+  std::vector<int32_t> pj, pk;
+  for (int t = 0; t < 3 * n; ++t) {
+    const int a = (int)(gen() % n), b = (int)(gen() % n);
+    if (a == b || (fixed[a] && fixed[b])) continue;
+    pj.push_back(a);
+    pk.push_back(b);
+  }
+  const int64_t P = (int64_t)pj.size();
+  std::vector<double> Z((size_t)12 * P, 0.0), Om((size_t)36 * P, 0.0);
+  for (int64_t c = 0; c < P; ++c)
+    for (int a = 0; a < 6; ++a) {
+      Om[36 * c + 7 * a] = 2.0 + a;
+      for (int b = a + 1; b < 6; ++b) Om[36 * c + 6 * a + b] = -1e30;  // above the diagonal: not read as a value
+    }
+  auto check = [&](int ns, const int32_t *s, const double *o1, int64_t np, const int32_t *j, const int32_t *k,
+                   const double *o2, int64_t nc, const int32_t *cj, const int32_t *ck, const double *z, const double *om,
+                   const double *o3) {
+    return ba::pgraph_cov_validate_host(n, fixed.data(), ns, s, o1, np, j, k, o2, nc, cj, ck, z, om, o3, &err);
+  };
+  REQUIRE(check(0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == 0);
+  REQUIRE(check((int)sel.size(), sel.data(), &out, P, pj.data(), pk.data(), &out, 0, nullptr, nullptr, nullptr, nullptr,
+                nullptr) == 0);
+  REQUIRE(check(0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, P, pj.data(), pk.data(), Z.data(), Om.data(), &out) == 0);
+  REQUIRE(check((int)sel.size(), sel.data(), nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                nullptr) == -1);
+  REQUIRE(has(err, "cov_pose36 is NULL"));
+  REQUIRE(check((int)sel.size(), nullptr, &out, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                nullptr) == -1);
+  if (P > 0) {
+    REQUIRE(check(0, nullptr, nullptr, P, pj.data(), pk.data(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == -1);
+    REQUIRE(has(err, "cov_rel36 is NULL"));
+    REQUIRE(check(0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, P, pj.data(), pk.data(), Z.data(), Om.data(),
+                  nullptr) == -1);
+    REQUIRE(has(err, "d2 is NULL"));
+    REQUIRE(check(0, nullptr, nullptr, P, nullptr, pk.data(), &out, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == -1);
+    REQUIRE(has(err, "null factor array"));
+    REQUIRE(check(0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, P, pj.data(), pk.data(), Z.data(), nullptr, &out) == -1);
+  }
+  // a bad entry at the first, a middle and the last position; the message names it
+  for (size_t s : {(size_t)0, sel.size() / 2, sel.size() - 1}) {
+    const int32_t keep = sel[s];
+    for (int32_t bad : {-1, n, std::numeric_limits<int32_t>::max(), std::numeric_limits<int32_t>::min()}) {
+      sel[s] = bad;
+      REQUIRE(check((int)sel.size(), sel.data(), &out, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                    nullptr, nullptr) == -1);
+      REQUIRE(has(err, "pose_sel[" + std::to_string(s) + "]") && has(err, "out of range"));
+    }
+    sel[s] = 0;
+    REQUIRE(check((int)sel.size(), sel.data(), &out, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                  nullptr) == -1);
+    REQUIRE(has(err, "pose_sel[" + std::to_string(s) + "] = 0 is a fixed pose"));
+    sel[s] = keep;
+  }
+  for (int64_t c : {(int64_t)0, P / 2, P - 1}) {
+    if (P == 0) break;
+    const std::string pair_at = "(pair " + std::to_string(c) + ")", cand_at = "(candidate " + std::to_string(c) + ")";
+    const int32_t j0 = pj[c], k0 = pk[c];
+    auto pairs_refused = [&](const char *why) {
+      if (check(0, nullptr, nullptr, P, pj.data(), pk.data(), &out, 0, nullptr, nullptr, nullptr, nullptr, nullptr) != -1)
+        return false;
+      if (!has(err, "ba_pgraph_covariance: ") || !has(err, why) || !has(err, pair_at)) return false;
+      if (check(0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, P, pj.data(), pk.data(), Z.data(), Om.data(), &out) != -1)
+        return false;
+      return has(err, "ba_pgraph_gate: ") && has(err, why) && has(err, cand_at);
+    };
+    pj[c] = n;
+    REQUIRE(pairs_refused(("pose j = " + std::to_string(n) + " out of range").c_str()));
+    pj[c] = j0;
+    pk[c] = -1;
+    REQUIRE(pairs_refused("pose k = -1 out of range"));
+    pk[c] = j0;
+    REQUIRE(pairs_refused("j == k"));
+    pj[c] = 0;
+    pk[c] = 3 < n ? 3 : 0;
+    if (n > 3) REQUIRE(pairs_refused("both poses are fixed"));
+    pj[c] = j0;
+    pk[c] = k0;
+    auto cands_refused = [&](const char *why) {
+      return check(0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, P, pj.data(), pk.data(), Z.data(), Om.data(),
+                   &out) == -1 &&
+             has(err, why) && has(err, cand_at);
+    };
+    Z[12 * c + 11] = nan;
+    REQUIRE(cands_refused("Z is not finite"));
+    Z[12 * c + 11] = 0.0;
+    const double d0 = Om[36 * c + 35];
+    Om[36 * c + 35] = nan;
+    REQUIRE(cands_refused("Omega is not finite"));
+    for (double bad : {0.0, -1.0}) {
+      Om[36 * c + 35] = bad;
+      REQUIRE(cands_refused("Omega is not positive definite"));
+    }
+    Om[36 * c + 35] = d0;
+    Om[36 * c + 6 * 5 + 0] = 100.0;  // a lower triangle that is not positive definite
+    REQUIRE(cands_refused("Omega is not positive definite"));
+    Om[36 * c + 6 * 5 + 0] = 0.0;
+  }
+  REQUIRE(check((int)sel.size(), sel.data(), &out, P, pj.data(), pk.data(), &out, P, pj.data(), pk.data(), Z.data(),
+                Om.data(), &out) == 0);
+
+  // ---- groups: a chain's lists, the columns of a schedule that reverses the tiles
+  std::vector<int32_t> rj, rk;
+  for (int p = 0; p + 1 < n; ++p) {
+    rj.push_back(p + 1);
+    rk.push_back(p);
+  }
+  ba::PgraphLists l;
+  ba::pgraph_build_lists(n, fixed.data(), (int64_t)rj.size(), rj.data(), rk.data(), &l);
+  const int ppt = nb / 6, ncb = (l.N + ppt - 1) / ppt;
+  std::vector<int> pose_col((size_t)l.N);
+  for (int j = 0; j < l.N; ++j) pose_col[j] = (ncb - 1 - j / ppt) * nb + 6 * (j % ppt);
+  for (int kind : {ba::kPgCovPair, ba::kPgCovCand}) {
+    std::vector<ba::PgCovGroup> groups;
+    std::vector<int32_t> slot;
+    int rows = -1;
+    ba::pgraph_cov_groups(l, pose_col, nb, (int)sel.size(), sel.data(), P, pj.data(), pk.data(), kind, &groups, &slot,
+                          &rows);
+    const std::set<int32_t> distinct(sel.begin(), sel.end());
+    REQUIRE(rows == (int)distinct.size() && (int)slot.size() == l.N);
+    REQUIRE((int64_t)groups.size() == (rows + 1) / 2 + P);
+    std::vector<int> seen_row((size_t)rows, 0), seen_entry((size_t)P, 0);
+    int last_t0[3] = {-1, -1, -1};
+    for (const ba::PgCovGroup &g : groups) {
+      REQUIRE(g.kind == ba::kPgCovPoses || g.kind == kind);
+      REQUIRE(g.t0 >= last_t0[g.kind] && g.t0 >= 0 && g.t0 < ncb);  // each kind ascends in t0
+      last_t0[g.kind] = g.t0;
+      int first = std::numeric_limits<int>::max();
+      for (int a = 0; a < 2; ++a) {
+        REQUIRE(g.opt[a] >= -1 && g.opt[a] < l.N);
+        if (g.opt[a] >= 0) {
+          REQUIRE(l.opt_pose[(size_t)g.opt[a]] == g.pose[a]);
+          first = std::min(first, pose_col[(size_t)g.opt[a]] / nb);
+        }
+      }
+      REQUIRE(first == g.t0);  // the sweep may skip exactly the tiles above t0
+      if (g.kind == ba::kPgCovPoses) {
+        REQUIRE(g.opt[0] >= 0 && g.slot[0] >= 0 && g.slot[0] < rows);
+        for (int a = 0; a < 2; ++a)
+          if (g.opt[a] >= 0) {
+            REQUIRE(slot[(size_t)g.opt[a]] == g.slot[a]);
+            ++seen_row[(size_t)g.slot[a]];
+          } else {
+            REQUIRE(g.slot[a] == -1);
+          }
+      } else {
+        REQUIRE(g.slot[0] >= 0 && g.slot[0] < P && g.slot[1] == g.slot[0]);
+        REQUIRE(g.pose[0] == pj[(size_t)g.slot[0]] && g.pose[1] == pk[(size_t)g.slot[0]]);
+        REQUIRE((g.opt[0] < 0) == (fixed[(size_t)g.pose[0]] != 0) && (g.opt[1] < 0) == (fixed[(size_t)g.pose[1]] != 0));
+        ++seen_entry[(size_t)g.slot[0]];
+      }
+    }
+    for (int v : seen_row) REQUIRE(v == 1);     // one writer per output row
+    for (int v : seen_entry) REQUIRE(v == 1);
+    for (int32_t u : sel) REQUIRE(slot[(size_t)l.opt_of_pose[(size_t)u]] >= 0);
+  }
+  // nothing selected: no group
+  {
+    std::vector<ba::PgCovGroup> groups(3);
+    std::vector<int32_t> slot;
+    int rows = -1;
+    ba::pgraph_cov_groups(l, pose_col, nb, 0, nullptr, 0, nullptr, nullptr, ba::kPgCovPair, &groups, &slot, &rows);
+    REQUIRE(groups.empty() && rows == 0);
+  }
+  // ---- tile rows of a chain of tiles: position p has the row tiles p + 1 and the rhs block
+  std::vector<int> row_ptr(1, 0), rows_of;
+  for (int p = 0; p < ncb; ++p) {
+    if (p + 1 < ncb) rows_of.push_back(p + 1);
+    rows_of.push_back(ncb);
+    row_ptr.push_back((int)rows_of.size());
+  }
+  std::vector<int> trow_ptr, trow;
+  ba::pgraph_cov_tile_rows(ncb, row_ptr, rows_of, &trow_ptr, &trow);
+  REQUIRE((int)trow_ptr.size() == ncb + 1 && (int)trow.size() == ncb - 1);
+  for (int t = 1; t < ncb; ++t) REQUIRE(trow_ptr[t + 1] - trow_ptr[t] == 1 && trow[trow_ptr[t]] == t - 1);
+  return 0;
+}
+
+int main() {
+  // the 6x6 Cholesky: the lower triangle alone, every pivot tested
+  {
+    double O[36] = {0.0};
+    for (int a = 0; a < 6; ++a) O[7 * a] = 1.0;
+    REQUIRE(ba::pgraph_chol6_host(O));
+    O[1] = 1e300;  // above the diagonal
+    REQUIRE(ba::pgraph_chol6_host(O));
+    O[6] = 1.0;    // [[1, 1], [1, 1]]: singular
+    REQUIRE(!ba::pgraph_chol6_host(O));
+    O[6] = 0.0;
+    O[35] = std::numeric_limits<double>::infinity();
+    REQUIRE(!ba::pgraph_chol6_host(O));
+  }
+  std::mt19937 gen(7);
+  for (int n : {2, 3, 4, 7, 12, 13, 60, 331})
+    for (int nb : {32, 64})
+      if (one_case(n, nb, gen)) return 1;
+  std::printf("PGRAPH COV HOST CHECK PASSED\n");
+  return 0;
+}
