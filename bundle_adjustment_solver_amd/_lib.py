@@ -96,6 +96,20 @@ class BaBatchMargResult(C.Structure):
                 ("n_marg_pose", C.c_int), ("n_marg_pt", C.c_int)]
 
 
+class BaCullOptions(C.Structure):
+    """ba_cull_options — the cull rule: an on observation goes iff !(e2 <= e2_max), or
+    cull_behind and !(depth > 0)."""
+    _fields_ = [("e2_max", C.c_double), ("cull_behind", C.c_int)]
+
+
+class BaBatchCullResult(C.Structure):
+    """ba_batch_cull_result — one problem of ba_batch_cull (status as BaBatchResult;
+    starved = 1: the rule would have left an optimisable pose without observation, the
+    problem's mask is unchanged)."""
+    _fields_ = [("n_on_before", C.c_int), ("n_culled", C.c_int), ("starved", C.c_int),
+                ("status", C.c_int)]
+
+
 class BaPointResult(C.Structure):
     """ba_point_result — one landmark of ba_point_only (status 0 = solved, 1 = non-finite
     input, 2 = no observations, 3 = degenerate triangulation; X left as given unless 0)."""
@@ -282,6 +296,15 @@ SIGNATURES = {
     "ba_batch_relative_check": (C.c_int, [C.c_int, _I32, _U8, _I32, _I32, _I32, _D, _D]),
     "ba_batch_relative_info": (C.c_int, [_P, _I64]),
     "ba_batch_relative_marg_plan": (C.c_int, [_P, _U8, _U8]),
+    "ba_batch_obs_report": (C.c_int, [_P, C.c_double, _D, _D, _D, _D]),
+    "ba_batch_set_obs_mask": (C.c_int, [_P, _U8]),
+    "ba_batch_get_obs_mask": (C.c_int, [_P, _U8]),
+    "ba_batch_cull": (C.c_int, [_P, C.POINTER(BaCullOptions), C.POINTER(BaBatchCullResult)]),
+    "ba_batch_solve_culled": (C.c_int, [_P, C.POINTER(BaOptions), C.POINTER(BaOptions),
+                                        C.POINTER(BaCullOptions), C.POINTER(BaIterInfo), C.c_int,
+                                        C.POINTER(BaBatchResult), C.POINTER(BaBatchResult),
+                                        C.POINTER(BaBatchCullResult)]),
+    "ba_batch_cull_check": (C.c_int, [C.POINTER(BaCullOptions)]),
     "ba_batch_update_values": (C.c_int, [_P, _D, _D]),
     "ba_batch_get_poses": (C.c_int, [_P, _D]),
     "ba_batch_get_points": (C.c_int, [_P, _D]),

@@ -57,6 +57,8 @@
 #include <vector>
 
 #include "ba_batch_kernels.h"
+#include "ba_batch_obs.h"
+#include "ba_batch_obs_host.h"
 #include "ba_rel_host.h"
 
 // ===========================================================================================
@@ -90,6 +92,15 @@ struct ba_batch {
   int64_t rel_n = 0, rel_F = 0;  // problems with factors in effect, their factors
   const ba::BatchRelDev *relp = nullptr;  // device record of their arrays, the argument of the REL instances
   std::vector<int32_t> rel_off, rel_j, rel_k;  // the factors as given (ba_batch_relative_marg_plan)
+  // the observation mask (ba_batch_set_obs_mask, ba_batch_cull): allocated by the first call that needs it
+  std::vector<int32_t> order;  // per planned observation: its user index (problem-local)
+  char *mask = nullptr;        // order | flags | shadow lists | cull results | first-stage results
+  size_t mask_bytes = 0;
+  bool masked = false;         // d points at the shadow lists
+  ba::BatchMaskDev md{};
+  ba_batch_result *res_first = nullptr;  // device, B records (ba_batch_solve_culled)
+  ba::BatchDev lists0{};       // d as ba_batch_create left it: the planned lists
+  char *rep = nullptr;         // outputs of ba_batch_obs_report (allocated by its first call)
 };
 
 namespace {
@@ -290,6 +301,136 @@ size_t lds_bytes_of(int npt) {
   return npt == 2 ? sizeof(ba::BatchLds<2>) : npt == 4 ? sizeof(ba::BatchLds<4>) : sizeof(ba::BatchLds<6>);
 }
 
+// the device rows of a solve: room for n_rows records
+int rows_reserve(ba_batch *b, size_t n_rows) {
+  if (n_rows > b->rows_cap) {
+    if (b->rows) (void)hipFree(b->rows);
+    b->rows = nullptr;
+    b->rows_cap = 0;
+    HIP_TRY(hipMalloc((void **)&b->rows, n_rows * sizeof(ba::DevIterRec)));
+    b->rows_cap = n_rows;
+  }
+  return 0;
+}
+
+// one solve of the batch on the handle's stream: d carries the lists, rows, cap and res of the
+// launch, the options are promoted here
+void solve_launch(ba_batch *b, const ba_options *opt, ba::BatchDev &d) {
+  hipStream_t s = b->h->stream;
+  const int B = b->B;
+  d.lambda0 = (double)opt->initial_lambda;
+  d.huber = (double)opt->threshold_huber_loss;
+  d.thr_step = (double)opt->threshold_step_size;
+  d.thr_cost = (double)opt->threshold_cost_change;
+  d.dec_ratio = (double)opt->decrease_ratio_lambda;
+  d.inc_ratio = (double)opt->increase_ratio_lambda;
+  d.max_iter = opt->max_num_iterations;
+  d.gn = opt->gauss_newton ? 1 : 0;
+  if (b->relp)  // the instances with the factor code, and their arrays, only for a batch that has factors
+    ba::batch_launch_rel(0, b->npt_class, B, s, &d, nullptr, b->relp);
+  else if (b->npt_class == 2)
+    hipLaunchKernelGGL((ba::k_ba_batch<2, false>), dim3(B), dim3(ba::kBatchBlock), 0, s, d);
+  else if (b->npt_class == 4)
+    hipLaunchKernelGGL((ba::k_ba_batch<4, false>), dim3(B), dim3(ba::kBatchBlock), 0, s, d);
+  else
+    hipLaunchKernelGGL((ba::k_ba_batch<6, false>), dim3(B), dim3(ba::kBatchBlock), 0, s, d);
+}
+
+// which lists the kernels read: the planned ones, or their shadows without the off observations
+void mask_point(ba_batch *b, bool shadow) {
+  const ba::BatchMaskDev &m = b->md;
+  b->d.prob = shadow ? m.prob_s : b->lists0.prob;
+  b->d.lobs = shadow ? m.lobs_s : b->lists0.lobs;
+  b->d.luv = shadow ? m.luv_s : b->lists0.luv;
+  b->d.lm_ptr = shadow ? m.lm_ptr_s : b->lists0.lm_ptr;
+  b->d.pobs = shadow ? m.pobs_s : b->lists0.pobs;
+  b->d.pobs_ptr = shadow ? m.pobs_ptr_s : b->lists0.pobs_ptr;
+  b->masked = shadow;
+}
+
+// the device side of the mask, allocated once: the permutation uploaded, every flag on
+int mask_ensure(ba_batch *b) {
+  if (b->mask) return 0;
+  const size_t nobs = (size_t)b->n_obs, B = (size_t)b->B;
+  const size_t n_pptr = (size_t)b->prob.back().pptr0 + b->prob.back().N + 1;
+  const size_t n_po = nobs;  // the pose-major list holds the observations of optimisable poses: never more
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  size_t o = 0;
+  const size_t o_ord = o;   o = al(o + nobs * sizeof(int32_t));
+  const size_t o_on = o;    o = al(o + nobs);
+  const size_t o_try = o;   o = al(o + nobs);
+  const size_t o_pre = o;   o = al(o + (nobs + B) * sizeof(int32_t));
+  const size_t o_lobs = o;  o = al(o + nobs * sizeof(int4));
+  const size_t o_luv = o;   o = al(o + nobs * sizeof(double2));
+  const size_t o_lm = o;    o = al(o + ((size_t)b->n_pt + B) * sizeof(int32_t));
+  const size_t o_po = o;    o = al(o + n_po * sizeof(int32_t));
+  const size_t o_pp = o;    o = al(o + n_pptr * sizeof(int32_t));
+  const size_t o_prob = o;  o = al(o + B * sizeof(ba::BatchProb));
+  const size_t o_cres = o;  o = al(o + B * sizeof(ba_batch_cull_result));
+  const size_t o_res1 = o;  o = al(o + B * sizeof(ba_batch_result));
+  char *M = nullptr;
+  if (hipMalloc((void **)&M, o) != hipSuccess)
+    return fail("ba_batch: device allocation of " + std::to_string(o) + " bytes for the observation mask failed");
+  hipStream_t s = b->h->stream;
+  if (hipMemsetAsync(M, 0, o, s) != hipSuccess || hipMemsetAsync(M + o_on, 1, nobs, s) != hipSuccess ||
+      (nobs && hipMemcpyAsync(M + o_ord, b->order.data(), nobs * sizeof(int32_t), hipMemcpyHostToDevice, s) !=
+                   hipSuccess) ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    (void)hipFree(M);
+    return fail("ba_batch: upload of the observation order failed");
+  }
+  b->mask = M;
+  b->mask_bytes = o;
+  ba::BatchMaskDev &m = b->md;
+  const ba::BatchDev &l = b->lists0;
+  m.prob = l.prob;
+  m.cams = l.cams;
+  m.poses = l.poses;
+  m.pts = l.pts[0];
+  m.jopt = l.jopt;
+  m.opt_lm = l.opt_lm;
+  m.order = (const int32_t *)(M + o_ord);
+  m.lobs = l.lobs;
+  m.luv = l.luv;
+  m.lm_ptr = l.lm_ptr;
+  m.pair_ptr = l.pair_ptr;
+  m.pobs = l.pobs;
+  m.pobs_ptr = l.pobs_ptr;
+  m.on = (uint8_t *)(M + o_on);
+  m.on_try = (uint8_t *)(M + o_try);
+  m.pre = (int32_t *)(M + o_pre);
+  m.lobs_s = (int4 *)(M + o_lobs);
+  m.luv_s = (double2 *)(M + o_luv);
+  m.lm_ptr_s = (int32_t *)(M + o_lm);
+  m.pobs_s = (int32_t *)(M + o_po);
+  m.pobs_ptr_s = (int32_t *)(M + o_pp);
+  m.prob_s = (ba::BatchProb *)(M + o_prob);
+  m.W18 = l.W18;
+  m.cres = (ba_batch_cull_result *)(M + o_cres);
+  b->res_first = (ba_batch_result *)(M + o_res1);
+  return 0;
+}
+
+void mask_apply_launch(ba_batch *b) {
+  hipLaunchKernelGGL(ba::k_ba_batch_mask_apply, dim3(b->B), dim3(ba::kBatchBlock), 0, b->h->stream, b->md);
+  mask_point(b, true);
+}
+
+void cull_launch(ba_batch *b, const ba_cull_options *c) {
+  hipLaunchKernelGGL(ba::k_ba_batch_cull, dim3(b->B), dim3(ba::kBatchBlock), 0, b->h->stream, b->md, c->e2_max,
+                     c->cull_behind ? 1 : 0);
+  mask_apply_launch(b);
+}
+
+int cull_refuse(const char *who, const ba_batch *b, const ba_cull_options *c, const ba_batch_cull_result *cres) {
+  const std::string w = std::string(who) + ": ";
+  if (!b) return fail(w + "null batch");
+  std::string err;
+  if (ba::cull_validate_host(c ? &c->e2_max : nullptr, &err)) return fail(w + err);
+  if (!cres) return fail(w + "null cres");
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -392,6 +533,7 @@ int ba_batch_create(ba_batch **out, ba_handle *h, int B, const int32_t *cam_off,
     P.pobs0 = (int64_t)pobs.size();
     P.pptr0 = (int64_t)pobs_ptr.size();
     for (int p = 0; p < P.n_pose; ++p) jopt[P.pose0 + p] = pl.jopt[p];
+    bt->order.insert(bt->order.end(), pl.order.begin(), pl.order.end());
     for (int t = 0; t < P.n_obs; ++t) {
       const int64_t k = P.obs0 + pl.order[t];
       const int32_t pid = pl.obs_pair[t];
@@ -463,6 +605,7 @@ int ba_batch_create(ba_batch **out, ba_handle *h, int B, const int32_t *cam_off,
   d.Cinvb3 = (double *)(D + o_Cib);
   d.W18 = (double *)(D + o_W);
   d.res = (ba_batch_result *)(D + o_res);
+  bt->lists0 = d;
   *out = bt;
   return 0;
 }
@@ -475,6 +618,8 @@ void ba_batch_destroy(ba_batch *b) {
   if (b->marg) (void)hipFree(b->marg);
   if (b->prior) (void)hipFree(b->prior);
   if (b->rel) (void)hipFree(b->rel);
+  if (b->mask) (void)hipFree(b->mask);
+  if (b->rep) (void)hipFree(b->rep);
   delete b;
 }
 
@@ -752,32 +897,11 @@ int ba_batch_solve(ba_batch *b, const ba_options *opt, ba_iter_info *rows, int c
   hipStream_t s = b->h->stream;
   const int dcap = rows ? cap : 0;
   const size_t n_rows = (size_t)B * (size_t)dcap;
-  if (n_rows > b->rows_cap) {
-    if (b->rows) (void)hipFree(b->rows);
-    b->rows = nullptr;
-    b->rows_cap = 0;
-    HIP_TRY(hipMalloc((void **)&b->rows, n_rows * sizeof(ba::DevIterRec)));
-    b->rows_cap = n_rows;
-  }
+  if (rows_reserve(b, n_rows)) return -1;
   ba::BatchDev d = b->d;
   d.rows = b->rows;
   d.cap = dcap;
-  d.lambda0 = (double)opt->initial_lambda;
-  d.huber = (double)opt->threshold_huber_loss;
-  d.thr_step = (double)opt->threshold_step_size;
-  d.thr_cost = (double)opt->threshold_cost_change;
-  d.dec_ratio = (double)opt->decrease_ratio_lambda;
-  d.inc_ratio = (double)opt->increase_ratio_lambda;
-  d.max_iter = opt->max_num_iterations;
-  d.gn = opt->gauss_newton ? 1 : 0;
-  if (b->relp)  // the instances with the factor code, and their arrays, only for a batch that has factors
-    ba::batch_launch_rel(0, b->npt_class, B, s, &d, nullptr, b->relp);
-  else if (b->npt_class == 2)
-    hipLaunchKernelGGL((ba::k_ba_batch<2, false>), dim3(B), dim3(ba::kBatchBlock), 0, s, d);
-  else if (b->npt_class == 4)
-    hipLaunchKernelGGL((ba::k_ba_batch<4, false>), dim3(B), dim3(ba::kBatchBlock), 0, s, d);
-  else
-    hipLaunchKernelGGL((ba::k_ba_batch<6, false>), dim3(B), dim3(ba::kBatchBlock), 0, s, d);
+  solve_launch(b, opt, d);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(res, d.res, (size_t)B * sizeof(ba_batch_result), hipMemcpyDeviceToHost, s));
   if (dcap > 0)
@@ -918,6 +1042,131 @@ int ba_batch_covariance(ba_batch *b, double huber, double *cov_pose36, double *c
   if (cov_pt9 && b->n_pt > 0)
     HIP_TRY(hipMemcpyAsync(cov_pt9, o.pt9, (size_t)b->n_pt * 9 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ba_batch_cull_check(const ba_cull_options *c) {
+  std::string err;
+  if (ba::cull_validate_host(c ? &c->e2_max : nullptr, &err)) return fail("ba_batch_cull_check: " + err);
+  return 0;
+}
+
+int ba_batch_obs_report(ba_batch *b, double huber, double *r2, double *e2, double *w, double *depth) {
+  if (!b) return fail("ba_batch_obs_report: null batch");
+  if (!r2 && !e2 && !w && !depth) return fail("ba_batch_obs_report: every output is null");
+  if (b->n_obs == 0) return 0;
+  HIP_TRY(hipSetDevice(b->h->device));
+  hipStream_t s = b->h->stream;
+  if (mask_ensure(b)) return -1;
+  const size_t n = (size_t)b->n_obs;
+  if (!b->rep) HIP_TRY(hipMalloc((void **)&b->rep, n * 5 * sizeof(double)));  // r2 | e2 | w | depth
+  double *R = (double *)b->rep;
+  hipLaunchKernelGGL(ba::k_ba_batch_obs_report, dim3((unsigned)((n + ba::kBatchBlock - 1) / ba::kBatchBlock)),
+                     dim3(ba::kBatchBlock), 0, s, b->md, b->B, (int64_t)n, huber, r2 ? R : nullptr,
+                     e2 ? R + 2 * n : nullptr, w ? R + 3 * n : nullptr, depth ? R + 4 * n : nullptr);
+  HIP_TRY(hipGetLastError());
+  if (r2) HIP_TRY(hipMemcpyAsync(r2, R, 2 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (e2) HIP_TRY(hipMemcpyAsync(e2, R + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (w) HIP_TRY(hipMemcpyAsync(w, R + 3 * n, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (depth) HIP_TRY(hipMemcpyAsync(depth, R + 4 * n, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ba_batch_set_obs_mask(ba_batch *b, const uint8_t *obs_on) {
+  if (!b) return fail("ba_batch_set_obs_mask: null batch");
+  HIP_TRY(hipSetDevice(b->h->device));
+  hipStream_t s = b->h->stream;
+  if (!obs_on) {  // the planned lists again; the flags read all on
+    if (!b->mask) return 0;
+    mask_point(b, false);
+    HIP_TRY(hipMemsetAsync(b->md.on, 1, (size_t)b->n_obs, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+  }
+  if (mask_ensure(b)) return -1;
+  std::vector<uint8_t> on((size_t)b->n_obs);
+  for (int64_t k = 0; k < b->n_obs; ++k) on[k] = obs_on[k] ? 1 : 0;
+  if (b->n_obs > 0) HIP_TRY(hipMemcpyAsync(b->md.on, on.data(), on.size(), hipMemcpyHostToDevice, s));
+  mask_apply_launch(b);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ba_batch_get_obs_mask(ba_batch *b, uint8_t *obs_on) {
+  if (!b || !obs_on) return fail("ba_batch_get_obs_mask: null argument");
+  if (!b->mask) {
+    std::memset(obs_on, 1, (size_t)b->n_obs);
+    return 0;
+  }
+  if (b->n_obs == 0) return 0;
+  HIP_TRY(hipSetDevice(b->h->device));
+  HIP_TRY(hipMemcpyAsync(obs_on, b->md.on, (size_t)b->n_obs, hipMemcpyDeviceToHost, b->h->stream));
+  HIP_TRY(hipStreamSynchronize(b->h->stream));
+  return 0;
+}
+
+int ba_batch_cull(ba_batch *b, const ba_cull_options *c, ba_batch_cull_result *cres) {
+  if (cull_refuse("ba_batch_cull", b, c, cres)) return -1;
+  HIP_TRY(hipSetDevice(b->h->device));
+  hipStream_t s = b->h->stream;
+  if (mask_ensure(b)) return -1;
+  cull_launch(b, c);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(cres, b->md.cres, (size_t)b->B * sizeof(ba_batch_cull_result), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ba_batch_solve_culled(ba_batch *b, const ba_options *first, const ba_options *second, const ba_cull_options *c,
+                          ba_iter_info *rows, int cap, ba_batch_result *res_first, ba_batch_result *res,
+                          ba_batch_cull_result *cres) {
+  const char *who = "ba_batch_solve_culled";
+  if (!b) return fail(std::string(who) + ": null batch");
+  if (!first || !second) return fail(std::string(who) + ": null options");
+  if (!res) return fail(std::string(who) + ": null result array");
+  if (cull_refuse(who, b, c, cres)) return -1;
+  std::string err;
+  if (ba::solve_culled_validate_host(first->max_num_iterations, second->max_num_iterations, rows != nullptr, cap,
+                                     &err))
+    return fail(std::string(who) + ": " + err);
+  const int B = b->B;
+  HIP_TRY(hipSetDevice(b->h->device));
+  hipStream_t s = b->h->stream;
+  if (mask_ensure(b)) return -1;
+  const int dcap = rows ? cap : 0, off = first->max_num_iterations;
+  const size_t n_rows = (size_t)B * (size_t)dcap;
+  if (rows_reserve(b, n_rows)) return -1;
+  // stage 1 on the lists in effect, its results beside the mask; the cull; stage 2 on the
+  // shadow lists, its rows after those of stage 1
+  ba::BatchDev d = b->d;
+  d.rows = b->rows;
+  d.cap = dcap;
+  d.res = b->res_first;
+  solve_launch(b, first, d);
+  HIP_TRY(hipGetLastError());
+  cull_launch(b, c);
+  HIP_TRY(hipGetLastError());
+  d = b->d;
+  d.rows = dcap ? b->rows + off : b->rows;
+  d.cap = dcap;
+  solve_launch(b, second, d);
+  HIP_TRY(hipGetLastError());
+  std::vector<ba_batch_result> r1((size_t)B);
+  std::vector<ba_iter_info> hr(n_rows);
+  HIP_TRY(hipMemcpyAsync(r1.data(), b->res_first, (size_t)B * sizeof(ba_batch_result), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(res, d.res, (size_t)B * sizeof(ba_batch_result), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(cres, b->md.cres, (size_t)B * sizeof(ba_batch_cull_result), hipMemcpyDeviceToHost, s));
+  if (n_rows > 0) HIP_TRY(hipMemcpyAsync(hr.data(), b->rows, n_rows * sizeof(ba_iter_info), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int p = 0; p < B && dcap > 0; ++p) {  // the rows each stage wrote; those in between stay the caller's
+    const size_t r0 = (size_t)p * dcap;
+    const int n1 = std::min(r1[p].n_rows, off), n2 = std::min(res[p].n_rows, dcap - off);
+    std::copy(hr.begin() + r0, hr.begin() + r0 + std::max(n1, 0), rows + r0);
+    std::copy(hr.begin() + r0 + off, hr.begin() + r0 + off + std::max(n2, 0), rows + r0 + off);
+  }
+  if (res_first) std::copy(r1.begin(), r1.end(), res_first);
   return 0;
 }
 

@@ -93,6 +93,22 @@ class Options:
         return o
 
 
+class CullOptions:
+    """The two-stage local BA of SolveBatch(..., cull=...): `first` are the Options of the
+    first solve; an observation is then switched off when its squared reprojection error
+    exceeds chi2 * sigma_pixel^2 pixels^2 (5.991: 95 % of a chi-square of two degrees of
+    freedom) or, with cull_behind, when it lies behind its camera."""
+
+    def __init__(self, first=None, chi2=5.991, cull_behind=True):
+        self.first = Options() if first is None else first
+        self.chi2 = chi2
+        self.cull_behind = cull_behind
+
+    def e2_max_scaled(self, sigma_pixel=1.0):
+        """the threshold in the library's units (pixels x SCALER, squared)"""
+        return float(self.chi2) * float(sigma_pixel) ** 2 * SCALER * SCALER
+
+
 def _yellow(s):
     return "\033[0;33m" + s + "\033[0m"
 
@@ -1510,6 +1526,104 @@ class BaBatch:
               "ba_batch_relative_marg_plan")
         return out
 
+    # ---- observation report, mask and cull (ba_batch_obs_report, ba_batch_set_obs_mask,
+    # ba_batch_cull, ba_batch_solve_culled); observations in user order throughout
+    @property
+    def n_obs(self):
+        return int(self.obs_off[-1])
+
+    def obs_of(self, p, a):
+        """the entries of problem p in a per-observation array of the batch"""
+        return a[int(self.obs_off[p]):int(self.obs_off[p + 1])]
+
+    def obs_report(self, huber):
+        """-> per problem a dict of views {r2 (n, 2), e2, w, depth}: every observation at the
+        values the object holds, user order, scaled units; off observations included."""
+        n = self.n_obs
+        r2, e2, w, dp = np.zeros((n, 2)), np.zeros(n), np.zeros(n), np.zeros(n)
+        check(self.lib.ba_batch_obs_report(self.b, float(huber), _dp(r2), _dp(e2), _dp(w), _dp(dp)),
+              "ba_batch_obs_report")
+        return [dict(r2=self.obs_of(p, r2), e2=self.obs_of(p, e2), w=self.obs_of(p, w),
+                     depth=self.obs_of(p, dp)) for p in range(self.B)]
+
+    def _obs_flags(self, what, masks):
+        """one flag per observation of the batch from a flat array or one array per problem"""
+        if isinstance(masks, (list, tuple)) and len(masks) == self.B and not np.isscalar(masks[0]):
+            for p, m in enumerate(masks):
+                want = int(self.obs_off[p + 1] - self.obs_off[p])
+                if np.asarray(m).reshape(-1).shape[0] != want:
+                    raise ValueError("%s: problem %d has %d observations, its mask %d flags"
+                                     % (what, p, want, np.asarray(m).reshape(-1).shape[0]))
+            masks = np.concatenate([np.asarray(m).reshape(-1) != 0 for m in masks] or [np.zeros(0, bool)])
+        m = np.ascontiguousarray(np.asarray(masks).reshape(-1) != 0, np.uint8)
+        if m.shape[0] != self.n_obs:
+            raise ValueError("%s: one flag per observation of the batch (%d), got %d"
+                             % (what, self.n_obs, m.shape[0]))
+        return m
+
+    def set_obs_mask(self, masks):
+        """masks: None (clears the mask), one flag per observation of the batch, or a list
+        with one flag array per problem; non-zero = on."""
+        if masks is None:
+            check(self.lib.ba_batch_set_obs_mask(self.b, None), "ba_batch_set_obs_mask")
+            return
+        m = self._obs_flags("set_obs_mask", masks)
+        check(self.lib.ba_batch_set_obs_mask(self.b, _up(m)), "ba_batch_set_obs_mask")
+
+    def get_obs_mask(self):
+        """-> per problem a bool view of the mask in effect (all True without one)"""
+        m = np.ones(self.n_obs, np.uint8)
+        check(self.lib.ba_batch_get_obs_mask(self.b, _up(m)), "ba_batch_get_obs_mask")
+        m = m != 0
+        return [self.obs_of(p, m) for p in range(self.B)]
+
+    @staticmethod
+    def cull_options(e2_max, cull_behind=True):
+        """-> BaCullOptions, refused as ba_batch_cull_check refuses (host only)"""
+        c = _lib.BaCullOptions(float(e2_max), 1 if cull_behind else 0)
+        check(_lib.load().ba_batch_cull_check(C.byref(c)), "ba_batch_cull_check")
+        return c
+
+    def cull(self, e2_max, cull_behind=True):
+        """Switches off every on observation with !(e2 <= e2_max), or behind its camera, at
+        the held values; -> one BaBatchCullResult per problem."""
+        c = self.cull_options(e2_max, cull_behind)
+        cres = (_lib.BaBatchCullResult * self.B)()
+        check(self.lib.ba_batch_cull(self.b, C.byref(c), cres), "ba_batch_cull")
+        return [cres[p] for p in range(self.B)]
+
+    @staticmethod
+    def solve_culled_cap(first, second, cap=None):
+        """the row capacity of solve_culled, refused as ba_batch_solve_culled refuses it"""
+        if first is None or second is None:
+            raise ValueError("solve_culled: null options")
+        n1, n2 = int(first.max_num_iterations), int(second.max_num_iterations)
+        if n1 <= 0 or n2 <= 0:
+            raise ValueError("solve_culled: both stages need max_num_iterations >= 1")
+        cap = n1 + n2 if cap is None else int(cap)
+        if cap < n1 + n2:
+            raise ValueError("solve_culled: cap = %d is less than the iterations of both stages "
+                             "(%d + %d)" % (cap, n1, n2))
+        return cap
+
+    def solve_culled(self, first, second, e2_max, cull_behind=True, cap=None):
+        """solve(first); cull; solve(second) in one go, no host synchronisation in between.
+        -> (rows_first, results_first, rows, results, cull_results), each per problem."""
+        cap = self.solve_culled_cap(first, second, cap)
+        c = self.cull_options(e2_max, cull_behind)
+        rows = (BaIterInfo * max(1, self.B * cap))()
+        r1 = (_lib.BaBatchResult * self.B)()
+        r2 = (_lib.BaBatchResult * self.B)()
+        cres = (_lib.BaBatchCullResult * self.B)()
+        check(self.lib.ba_batch_solve_culled(self.b, C.byref(first), C.byref(second), C.byref(c), rows,
+                                             cap, r1, r2, cres), "ba_batch_solve_culled")
+        off = int(first.max_num_iterations)
+        rows1 = [[rows[p * cap + i] for i in range(min(r1[p].n_rows, off))] for p in range(self.B)]
+        rows2 = [[rows[p * cap + off + i] for i in range(min(r2[p].n_rows, cap - off))]
+                 for p in range(self.B)]
+        B = range(self.B)
+        return rows1, [r1[p] for p in B], rows2, [r2[p] for p in B], [cres[p] for p in B]
+
     def cov_poses_of(self, p, cov_pose):
         return cov_pose[self.pose_off[p]:self.pose_off[p + 1]]
 
@@ -2492,7 +2606,30 @@ class FullBundleAdjustmentSolver:
         return out
 
     @staticmethod
-    def SolveBatch(solvers, options, summaries=None, priors=None, sigma_pixel=1.0, relatives=None):
+    def _obs_masks(what, solvers, probs, obs_masks):
+        """obs_masks of SolveBatch / ComputeCovarianceBatch / MarginalizeBatch -> one bool array
+        per solver (all True for a None entry), or None.  obs_masks[k]: one flag per observation
+        solver k registered, in registration order; non-zero = the observation takes part."""
+        if obs_masks is None:
+            return None
+        if len(obs_masks) != len(solvers):
+            raise ValueError("%s: one observation mask (or None) per solver" % what)
+        out = []
+        for k, (pr, m) in enumerate(zip(probs, obs_masks)):
+            n = len(pr["obs_pt"])
+            if m is None:
+                out.append(np.ones(n, bool))
+                continue
+            m = np.asarray(m).reshape(-1) != 0
+            if m.shape[0] != n:
+                raise ValueError("%s: solver %d registered %d observations, its mask holds %d flags"
+                                 % (what, k, n, m.shape[0]))
+            out.append(m)
+        return out
+
+    @staticmethod
+    def SolveBatch(solvers, options, summaries=None, priors=None, sigma_pixel=1.0, relatives=None,
+                   obs_masks=None, cull=None):
         """Solve the registered problems of several solver objects in ONE launch
         (ba_batch_solve: one persistent workgroup per problem, see BaBatch for the
         limits), write every solver's poses and points back as Solve does and fill
@@ -2502,7 +2639,17 @@ class FullBundleAdjustmentSolver:
         one pose prior per solver taken in as one more factor (BaBatch.set_prior), see
         _scaled_priors for the dict; H and b in the units MarginalizeBatch returns for
         `sigma_pixel`.  relatives (default None: none): one list of relative-pose factors
-        per solver (BaBatch.set_relative), see _scaled_relatives for the dict."""
+        per solver (BaBatch.set_relative), see _scaled_relatives for the dict.
+        obs_masks (default None: none): one flag array per solver (or None), one flag per
+        registered observation in registration order; an observation whose flag is 0 takes
+        no part (BaBatch.set_obs_mask).  cull (default None: none): a CullOptions; the
+        batch is solved with cull.first, every observation with a squared error above
+        cull.chi2 * sigma_pixel^2 px^2 (or behind its camera) is switched off, and the
+        batch is solved again with `options`, all in one go (BaBatch.solve_culled).  The
+        return value is then (results, reports): reports[k] = dict(inliers (bool per
+        registered observation: hand it on as obs_masks of ComputeCovarianceBatch and
+        MarginalizeBatch), n_culled, starved, n_iter_first); the Summary rows are those of
+        both stages."""
         t0 = time.perf_counter()
         solvers = list(solvers)
         if not solvers:
@@ -2522,13 +2669,31 @@ class FullBundleAdjustmentSolver:
         c_opt.gauss_newton = 1 if solvers[0]._use_gauss_newton(options) else 0
         sp = FullBundleAdjustmentSolver._scaled_priors("SolveBatch", solvers, priors, sigma_pixel)
         sr = FullBundleAdjustmentSolver._scaled_relatives("SolveBatch", solvers, relatives, sigma_pixel)
+        om = FullBundleAdjustmentSolver._obs_masks("SolveBatch", solvers, probs, obs_masks)
+        if cull is not None:
+            c_first = cull.first.to_c()
+            c_first.gauss_newton = 1 if solvers[0]._use_gauss_newton(cull.first) else 0
+            e2_max = cull.e2_max_scaled(sigma_pixel)
+            BaBatch.cull_options(e2_max, cull.cull_behind)
+            BaBatch.solve_culled_cap(c_first, c_opt)
         batch = BaBatch(probs, solvers[0].device)
         try:
             if sp is not None:
                 batch.set_prior(sp)
             if sr is not None:
                 batch.set_relative(sr)
-            rows, res = batch.solve(c_opt)
+            if om is not None:
+                batch.set_obs_mask(om)
+            reports = None
+            if cull is None:
+                rows, res = batch.solve(c_opt)
+            else:
+                rows1, res1, rows, res, cres = batch.solve_culled(c_first, c_opt, e2_max, cull.cull_behind)
+                rows = [a + b for a, b in zip(rows1, rows)]
+                inl = batch.get_obs_mask()
+                reports = [dict(inliers=inl[k].copy(), n_culled=int(cres[k].n_culled),
+                                starved=int(cres[k].starved), n_iter_first=int(res1[k].n_iter))
+                           for k in range(len(solvers))]
             T_all, X_all = batch.get_poses(), batch.get_points()
             for k, sv in enumerate(solvers):
                 summary = None if summaries is None else summaries[k]
@@ -2551,11 +2716,11 @@ class FullBundleAdjustmentSolver:
                     sv._problem.update_values(sv._pose_T_jw[0], sv._pt_X[0])
         finally:
             batch.close()
-        return res
+        return res if reports is None else (res, reports)
 
     @staticmethod
     def ComputeCovarianceBatch(solvers, sigma_pixel=1.0, options=None, points=True, priors=None,
-                               relatives=None):
+                               relatives=None, obs_masks=None):
         """(new) Covariance blocks of the CURRENT registered values of several
         solver objects in ONE launch (ba_batch_covariance; see BaBatch for the
         limits).  Returns one (cov_pose (n_pose, 6, 6), cov_point (n_pt, 3, 3) or
@@ -2564,7 +2729,8 @@ class FullBundleAdjustmentSolver:
         ComputeCovariance.  A result whose status is not 0 (over a limit,
         non-finite input) has zero blocks; dropped_pivots > 0 means S was singular.
         priors: as in SolveBatch; the covariance then includes the past.  relatives: as
-        in SolveBatch; every factor joins."""
+        in SolveBatch; every factor joins.  obs_masks: as in SolveBatch (the `inliers` it
+        reports): observations that are off take no part."""
         solvers = list(solvers)
         if not solvers:
             return []
@@ -2580,12 +2746,15 @@ class FullBundleAdjustmentSolver:
         sp = FullBundleAdjustmentSolver._scaled_priors("ComputeCovarianceBatch", solvers, priors, sigma_pixel)
         sr = FullBundleAdjustmentSolver._scaled_relatives("ComputeCovarianceBatch", solvers, relatives,
                                                           sigma_pixel)
+        om = FullBundleAdjustmentSolver._obs_masks("ComputeCovarianceBatch", solvers, probs, obs_masks)
         batch = BaBatch(probs, solvers[0].device)
         try:
             if sp is not None:
                 batch.set_prior(sp)
             if sr is not None:
                 batch.set_relative(sr)
+            if om is not None:
+                batch.set_obs_mask(om)
             cp, cq, res = batch.covariance(huber, points)
             out = []
             for k in range(len(solvers)):
@@ -2598,7 +2767,8 @@ class FullBundleAdjustmentSolver:
         return out
 
     @staticmethod
-    def MarginalizeBatch(solvers, marg_poses, sigma_pixel=1.0, options=None, priors=None, relatives=None):
+    def MarginalizeBatch(solvers, marg_poses, sigma_pixel=1.0, options=None, priors=None, relatives=None,
+                         obs_masks=None):
         """(new) Marginalisation priors of several solver objects in ONE launch
         (ba_batch_marginalize; see BaBatch for the limits), at the CURRENT registered
         values.  marg_poses[k]: the pose objects (or integer handles) of solver k that
@@ -2615,7 +2785,9 @@ class FullBundleAdjustmentSolver:
         at the current values, which are the lin_poses of the next prior).  relatives: as
         in SolveBatch; a factor joins exactly when one of its two poses is marked and then
         leaves with it, and every tuple gains a sixth entry: one 0 / 1 per factor of that
-        solver, 1 where it left (the others go into the next window with the prior)."""
+        solver, 1 where it left (the others go into the next window with the prior).
+        obs_masks: as in SolveBatch; the landmarks that leave are those the marked poses
+        observe through observations that are on."""
         solvers = list(solvers)
         if not solvers:
             return []
@@ -2639,8 +2811,11 @@ class FullBundleAdjustmentSolver:
         huber = (options or Options()).outlier_handle.threshold_huber_loss
         sp = FullBundleAdjustmentSolver._scaled_priors("MarginalizeBatch", solvers, priors, sigma_pixel)
         sr = FullBundleAdjustmentSolver._scaled_relatives("MarginalizeBatch", solvers, relatives, sigma_pixel)
+        om = FullBundleAdjustmentSolver._obs_masks("MarginalizeBatch", solvers, probs, obs_masks)
         batch = BaBatch(probs, solvers[0].device)
         try:
+            if om is not None:
+                batch.set_obs_mask(om)
             if sp is not None:
                 batch.set_prior(sp)
             if sr is not None:

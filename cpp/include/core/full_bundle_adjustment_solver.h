@@ -109,13 +109,33 @@ class FullBundleAdjustmentSolver {
   // in_priors (null: none): one PosePrior per solver, taken in as one more factor of its
   // problem (ba_batch_set_prior of include/ba_hip.h), H and b in the units MarginalizeBatch
   // returns for sigma_pixel.  in_relatives (null: none): one list of RelativePose factors per
-  // solver (ba_batch_set_relative of include/ba_hip.h).
+  // solver (ba_batch_set_relative of include/ba_hip.h).  obs_masks (null: none): one flag
+  // vector per solver (an empty one: none for that solver), one flag per observation the
+  // solver registered, in registration order; an observation whose flag is 0 takes no part
+  // (ba_batch_set_obs_mask of include/ba_hip.h).  cull (null: none): the two-stage local BA
+  // in one go (ba_batch_solve_culled): the batch is solved with cull->first, every observation
+  // whose squared error exceeds cull->chi2 * sigma_pixel^2 pixels^2 (or, with cull_behind,
+  // that lies behind its camera) is switched off, and the batch is solved again with
+  // `options`; cull_reports (null: not wanted) then gets one CullReport per solver, whose
+  // `inliers` can be handed on as obs_masks of ComputeCovarianceBatch and MarginalizeBatch.
+  // The Summary rows are those of both stages.
   struct PosePrior;
   struct RelativePose;
+  struct CullOptions {
+    Options first;
+    double chi2 = 5.991;  // 95 % of a chi-square of two degrees of freedom
+    bool cull_behind = true;
+  };
+  struct CullReport {
+    std::vector<uint8_t> inliers;  // one per registered observation: 1 = still on
+    int n_culled{0}, starved{0}, n_iter_first{0};
+  };
   static bool SolveBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, Options options,
                          std::vector<Summary> *summaries = nullptr,
                          const std::vector<PosePrior> *in_priors = nullptr, double sigma_pixel = 1.0,
-                         const std::vector<std::vector<RelativePose>> *in_relatives = nullptr);
+                         const std::vector<std::vector<RelativePose>> *in_relatives = nullptr,
+                         const std::vector<std::vector<uint8_t>> *obs_masks = nullptr,
+                         const CullOptions *cull = nullptr, std::vector<CullReport> *cull_reports = nullptr);
 
   // (new; the reference has no counterpart) Structure-only solve: EVERY registered pose is
   // treated as fixed and every non-fixed registered point is solved on its own against its
@@ -175,7 +195,8 @@ class FullBundleAdjustmentSolver {
                                      std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
                                      std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points,
                                      const std::vector<PosePrior> *in_priors = nullptr,
-                                     const std::vector<std::vector<RelativePose>> *in_relatives = nullptr);
+                                     const std::vector<std::vector<RelativePose>> *in_relatives = nullptr,
+                                     const std::vector<std::vector<uint8_t>> *obs_masks = nullptr);
   // (new) The marginalisation prior one solver's window leaves on its kept poses: the
   // Gaussian 1/2 d^T H d - b^T d, d the stacked tangents xi = [v; omega] of the kept poses'
   // WORLD-TO-BODY transforms (the convention of ComputeCovariance), so that H d = b is their
@@ -208,7 +229,8 @@ class FullBundleAdjustmentSolver {
                                const std::vector<std::vector<_BA_Pose *>> &marg_poses, double sigma_pixel,
                                std::vector<MarginalPrior> *priors,
                                const std::vector<PosePrior> *in_priors = nullptr,
-                               const std::vector<std::vector<RelativePose>> *in_relatives = nullptr);
+                               const std::vector<std::vector<RelativePose>> *in_relatives = nullptr,
+                               const std::vector<std::vector<uint8_t>> *obs_masks = nullptr);
   // (new) A prior taken back IN by SolveBatch, ComputeCovarianceBatch and MarginalizeBatch
   // (in_priors, one per solver; an empty `poses` means none for that solver): the Gaussian
   // 1/2 d^T H d - b^T d + c / 2 on the registered, optimisable `poses`, in any order (the
@@ -333,6 +355,10 @@ class FullBundleAdjustmentSolver {
   // ba_create + ba_batch_create on `device`; returns ba_batch_create's code (the caller
   // destroys both objects)
   static int CreateBatch(const BatchArrays &a, int device, ba_handle **h, ba_batch **batch);
+  // obs_masks (may be null: returns false) into one flag per observation of the batch (an
+  // empty vector of a solver: all on).  Throws std::runtime_error on a wrong size.
+  static bool PackMasks(const BatchArrays &a, const char *who, const std::vector<std::vector<uint8_t>> *obs_masks,
+                        std::vector<uint8_t> *flat);
   // in_priors (may be null: out->set stays false) into the arrays of ba_batch_set_prior:
   // scaled units, registration order.  Throws std::runtime_error on a malformed prior.
   struct PriorArrays {

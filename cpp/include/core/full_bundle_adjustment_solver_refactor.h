@@ -140,6 +140,9 @@ class FullBundleAdjustmentSolverRefactor {
   // or Gauss-Newton as in Solve (anything else throws std::runtime_error), for this call only:
   // what an earlier Solve selected is put back afterwards.
   using RelativePose = FullBundleAdjustmentSolver::RelativePose;
+  // (new) the two-stage local BA of SolveBatch, see FullBundleAdjustmentSolver::CullOptions
+  using CullOptions = FullBundleAdjustmentSolver::CullOptions;
+  using CullReport = FullBundleAdjustmentSolver::CullReport;
   // (new) a relative-pose factor of this solver's own problem, see
   // FullBundleAdjustmentSolver::AddRelativePose
   void AddRelativePose(const RelativePose &factor, double sigma_pixel = 1.0) {
@@ -148,26 +151,32 @@ class FullBundleAdjustmentSolverRefactor {
   static bool SolveBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers, Options options,
                          std::vector<Summary> *summaries = nullptr,
                          const std::vector<PosePrior> *in_priors = nullptr, double sigma_pixel = 1.0,
-                         const std::vector<std::vector<RelativePose>> *in_relatives = nullptr);
+                         const std::vector<std::vector<RelativePose>> *in_relatives = nullptr,
+                         const std::vector<std::vector<uint8_t>> *obs_masks = nullptr,
+                         const CullOptions *cull = nullptr, std::vector<CullReport> *cull_reports = nullptr);
+  // obs_masks (last, null: none): one flag per registered observation of every solver, see
+  // FullBundleAdjustmentSolver::SolveBatch
   static bool ComputeCovarianceBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers,
                                      double sigma_pixel,
                                      std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
                                      std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points,
                                      const std::vector<PosePrior> *in_priors,
-                                     const std::vector<std::vector<RelativePose>> *in_relatives) {
+                                     const std::vector<std::vector<RelativePose>> *in_relatives,
+                                     const std::vector<std::vector<uint8_t>> *obs_masks = nullptr) {
     std::vector<FullBundleAdjustmentSolver *> impls;
     for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
     return FullBundleAdjustmentSolver::ComputeCovarianceBatch(impls, sigma_pixel, cov_poses, cov_points, in_priors,
-                                                              in_relatives);
+                                                              in_relatives, obs_masks);
   }
   static bool MarginalizeBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers,
                                const std::vector<std::vector<Pose *>> &marg_poses, double sigma_pixel,
                                std::vector<MarginalPrior> *priors, const std::vector<PosePrior> *in_priors,
-                               const std::vector<std::vector<RelativePose>> *in_relatives) {
+                               const std::vector<std::vector<RelativePose>> *in_relatives,
+                               const std::vector<std::vector<uint8_t>> *obs_masks = nullptr) {
     std::vector<FullBundleAdjustmentSolver *> impls;
     for (FullBundleAdjustmentSolverRefactor *s : solvers) impls.push_back(s ? &s->impl_ : nullptr);
     return FullBundleAdjustmentSolver::MarginalizeBatch(impls, marg_poses, sigma_pixel, priors, in_priors,
-                                                        in_relatives);
+                                                        in_relatives, obs_masks);
   }
   // (new) structure-only solve, see FullBundleAdjustmentSolver::SolvePointsOnly;
   // options.solver_type selects Levenberg-Marquardt or Gauss-Newton as in Solve (anything

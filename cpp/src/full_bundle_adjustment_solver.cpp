@@ -797,10 +797,32 @@ void FullBundleAdjustmentSolver::PackRelatives(const std::vector<FullBundleAdjus
   }
 }
 
+bool FullBundleAdjustmentSolver::PackMasks(const BatchArrays &a, const char *who,
+                                           const std::vector<std::vector<uint8_t>> *obs_masks,
+                                           std::vector<uint8_t> *flat) {
+  if (obs_masks == nullptr) return false;
+  const size_t B = a.obs_off.size() - 1;
+  if (obs_masks->size() != B) throw std::runtime_error(std::string(who) + ": one observation mask per solver");
+  flat->assign(static_cast<size_t>(a.obs_off[B]), 1);
+  for (size_t b = 0; b < B; ++b) {
+    const std::vector<uint8_t> &m = (*obs_masks)[b];
+    const size_t n = static_cast<size_t>(a.obs_off[b + 1] - a.obs_off[b]);
+    if (m.empty()) continue;
+    if (m.size() != n)
+      throw std::runtime_error(std::string(who) + ": solver " + std::to_string(b) + " registered " +
+                               std::to_string(n) + " observations, its mask holds " + std::to_string(m.size()) +
+                               " flags");
+    for (size_t k = 0; k < n; ++k) (*flat)[static_cast<size_t>(a.obs_off[b]) + k] = m[k] ? 1 : 0;
+  }
+  return true;
+}
+
 bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustmentSolver *> &solvers, Options options,
                                             std::vector<Summary> *summaries, const std::vector<PosePrior> *in_priors,
                                             double sigma_pixel,
-                                            const std::vector<std::vector<RelativePose>> *in_relatives) {
+                                            const std::vector<std::vector<RelativePose>> *in_relatives,
+                                            const std::vector<std::vector<uint8_t>> *obs_masks,
+                                            const CullOptions *cull, std::vector<CullReport> *cull_reports) {
   timer::StopWatch stopwatch("BundleAdjustmentSolver::SolveBatch");
   stopwatch.Start();
   const int B = static_cast<int>(solvers.size());
@@ -814,16 +836,49 @@ bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustme
   PackRelatives(solvers, "SolveBatch", in_relatives, sigma_pixel, &ra);
   std::vector<int32_t> &pose_off = a.pose_off, &pt_off = a.pt_off;
   std::vector<double> &T = a.T, &X = a.X;
+  std::vector<uint8_t> mask;
+  const bool masked = PackMasks(a, "SolveBatch", obs_masks, &mask);
   const ba_options o = PackOptions(options, solvers[0]->gauss_newton_);
-  const int cap = std::max(1, o.max_num_iterations);
+  // with cull: the rows of stage 1, then those of stage 2 from row `first_iters` on
+  ba_options o_first = o;
+  ba_cull_options co{0.0, 0};
+  int first_iters = 0;
+  if (cull != nullptr) {
+    o_first = PackOptions(cull->first, solvers[0]->gauss_newton_);
+    const double sc = static_cast<double>(solvers[0]->scaler_);
+    co.e2_max = cull->chi2 * sigma_pixel * sigma_pixel * sc * sc;
+    co.cull_behind = cull->cull_behind ? 1 : 0;
+    if (ba_batch_cull_check(&co) != 0) throw std::runtime_error(std::string("SolveBatch failed: ") + ba_last_error());
+    if (o_first.max_num_iterations <= 0 || o.max_num_iterations <= 0)
+      throw std::runtime_error("SolveBatch: with cull both stages need max_num_iterations >= 1");
+    first_iters = o_first.max_num_iterations;
+  }
+  if (cull_reports != nullptr) cull_reports->assign(static_cast<size_t>(cull ? B : 0), CullReport());
+  const int cap = first_iters + std::max(1, o.max_num_iterations);
   std::vector<ba_iter_info> rows(static_cast<size_t>(B) * cap);
-  std::vector<ba_batch_result> res(static_cast<size_t>(B));
+  std::vector<ba_batch_result> res(static_cast<size_t>(B)), res_first(static_cast<size_t>(B));
+  std::vector<ba_batch_cull_result> cres(static_cast<size_t>(B));
   ba_handle *h = nullptr;
   ba_batch *batch = nullptr;
   int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
   if (rc == 0) rc = SetPriors(batch, pa);
   if (rc == 0) rc = SetRelatives(batch, ra);
-  if (rc == 0) rc = ba_batch_solve(batch, &o, rows.data(), cap, res.data());
+  if (rc == 0 && masked) rc = ba_batch_set_obs_mask(batch, mask.data());
+  if (rc == 0 && cull == nullptr) rc = ba_batch_solve(batch, &o, rows.data(), cap, res.data());
+  if (rc == 0 && cull != nullptr) {
+    rc = ba_batch_solve_culled(batch, &o_first, &o, &co, rows.data(), cap, res_first.data(), res.data(), cres.data());
+    if (rc == 0 && cull_reports != nullptr) {
+      mask.assign(static_cast<size_t>(a.obs_off[B]), 1);
+      rc = ba_batch_get_obs_mask(batch, mask.data());
+      for (int b = 0; rc == 0 && b < B; ++b) {
+        CullReport &r = (*cull_reports)[b];
+        r.inliers.assign(mask.begin() + a.obs_off[b], mask.begin() + a.obs_off[b + 1]);
+        r.n_culled = cres[b].n_culled;
+        r.starved = cres[b].starved;
+        r.n_iter_first = res_first[b].n_iter;
+      }
+    }
+  }
   if (rc == 0) rc = ba_batch_get_poses(batch, T.data());
   if (rc == 0) rc = ba_batch_get_points(batch, X.data());
   const std::string err = rc ? ba_last_error() : "";
@@ -846,8 +901,10 @@ bool FullBundleAdjustmentSolver::SolveBatch(const std::vector<FullBundleAdjustme
     // a finalized solver continues from the solution, as after Solve
     if (s->is_parameter_finalized_) Check(ba_update_values(s->handle_, Tb, Xb), "ba_update_values");
     if (summary != nullptr) {
-      for (int k = 0; k < res[b].n_rows && k < cap; ++k)
+      for (int k = 0; cull != nullptr && k < res_first[b].n_rows && k < first_iters; ++k)
         summary->optimization_info_list_.push_back(ToInfo(rows[static_cast<size_t>(b) * cap + k]));
+      for (int k = 0; k < res[b].n_rows && first_iters + k < cap; ++k)
+        summary->optimization_info_list_.push_back(ToInfo(rows[static_cast<size_t>(b) * cap + first_iters + k]));
       summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
     }
   }
@@ -954,7 +1011,7 @@ bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
     const std::vector<FullBundleAdjustmentSolver *> &solvers, double sigma_pixel,
     std::vector<std::vector<Eigen::Matrix<double, 6, 6>>> *cov_poses,
     std::vector<std::vector<Eigen::Matrix<double, 3, 3>>> *cov_points, const std::vector<PosePrior> *in_priors,
-    const std::vector<std::vector<RelativePose>> *in_relatives) {
+    const std::vector<std::vector<RelativePose>> *in_relatives, const std::vector<std::vector<uint8_t>> *obs_masks) {
   const int B = static_cast<int>(solvers.size());
   if (cov_poses != nullptr) cov_poses->assign(static_cast<size_t>(B), std::vector<Eigen::Matrix<double, 6, 6>>());
   if (cov_points != nullptr) cov_points->assign(static_cast<size_t>(B), std::vector<Eigen::Matrix<double, 3, 3>>());
@@ -966,6 +1023,8 @@ bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
   PackPriors(solvers, "ComputeCovarianceBatch", in_priors, sigma_pixel, &pa);
   RelativeArrays ra;
   PackRelatives(solvers, "ComputeCovarianceBatch", in_relatives, sigma_pixel, &ra);
+  std::vector<uint8_t> mask;
+  const bool masked = PackMasks(a, "ComputeCovarianceBatch", obs_masks, &mask);
   std::vector<double> cp(36 * a.pose_fixed.size()), cq(cov_points ? 9 * a.point_fixed.size() : 0);
   std::vector<ba_batch_cov_result> res(static_cast<size_t>(B));
   const Options defaults;
@@ -974,6 +1033,7 @@ bool FullBundleAdjustmentSolver::ComputeCovarianceBatch(
   int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
   if (rc == 0) rc = SetPriors(batch, pa);
   if (rc == 0) rc = SetRelatives(batch, ra);
+  if (rc == 0 && masked) rc = ba_batch_set_obs_mask(batch, mask.data());
   if (rc == 0)
     rc = ba_batch_covariance(batch, static_cast<double>(defaults.outlier_handle.threshold_huber_loss), cp.data(),
                              cov_points ? cq.data() : nullptr, res.data());
@@ -1015,7 +1075,8 @@ bool FullBundleAdjustmentSolver::MarginalizeBatch(const std::vector<FullBundleAd
                                                   const std::vector<std::vector<_BA_Pose *>> &marg_poses,
                                                   double sigma_pixel, std::vector<MarginalPrior> *priors,
                                                   const std::vector<PosePrior> *in_priors,
-                                                  const std::vector<std::vector<RelativePose>> *in_relatives) {
+                                                  const std::vector<std::vector<RelativePose>> *in_relatives,
+                                                  const std::vector<std::vector<uint8_t>> *obs_masks) {
   const int B = static_cast<int>(solvers.size());
   if (priors == nullptr) throw std::runtime_error("MarginalizeBatch: null output");
   priors->assign(static_cast<size_t>(B), MarginalPrior());
@@ -1027,6 +1088,8 @@ bool FullBundleAdjustmentSolver::MarginalizeBatch(const std::vector<FullBundleAd
   PackPriors(solvers, "MarginalizeBatch", in_priors, sigma_pixel, &pa);
   RelativeArrays ra;
   PackRelatives(solvers, "MarginalizeBatch", in_relatives, sigma_pixel, &ra);
+  std::vector<uint8_t> mask;
+  const bool masked = PackMasks(a, "MarginalizeBatch", obs_masks, &mask);
   std::vector<uint8_t> left(ra.set ? ra.j.size() : 0, 0);
   std::vector<uint8_t> mark(a.pose_fixed.size(), 0), marg_pt(a.point_fixed.size(), 0);
   for (int b = 0; b < B; ++b)
@@ -1045,6 +1108,7 @@ bool FullBundleAdjustmentSolver::MarginalizeBatch(const std::vector<FullBundleAd
   int rc = CreateBatch(a, solvers[0]->device_id_, &h, &batch);
   if (rc == 0) rc = SetPriors(batch, pa);
   if (rc == 0) rc = SetRelatives(batch, ra);
+  if (rc == 0 && masked) rc = ba_batch_set_obs_mask(batch, mask.data());
   if (rc == 0 && ra.set) rc = ba_batch_relative_marg_plan(batch, mark.data(), left.data());
   if (rc == 0) rc = ba_batch_marg_layout(batch, mark.data(), H_off.data(), b_off.data());
   if (rc == 0) {

@@ -50,7 +50,9 @@ bool FullBundleAdjustmentSolverRefactor::Solve(Options options, Summary *summary
 bool FullBundleAdjustmentSolverRefactor::SolveBatch(const std::vector<FullBundleAdjustmentSolverRefactor *> &solvers,
                                                     Options options, std::vector<Summary> *summaries,
                                                     const std::vector<PosePrior> *in_priors, double sigma_pixel,
-                                                    const std::vector<std::vector<RelativePose>> *in_relatives) {
+                                                    const std::vector<std::vector<RelativePose>> *in_relatives,
+                                                    const std::vector<std::vector<uint8_t>> *obs_masks,
+                                                    const CullOptions *cull, std::vector<CullReport> *cull_reports) {
   if (options.solver_type != SolverType::LEVENBERG_MARQUARDT && options.solver_type != SolverType::GAUSS_NEWTON)
     throw std::runtime_error(
         "FullBundleAdjustmentSolverRefactor::SolveBatch: solver_type must be GAUSS_NEWTON or LEVENBERG_MARQUARDT");
@@ -68,7 +70,8 @@ bool FullBundleAdjustmentSolverRefactor::SolveBatch(const std::vector<FullBundle
   };
   bool ok = false;
   try {
-    ok = FullBundleAdjustmentSolver::SolveBatch(impls, options, summaries, in_priors, sigma_pixel, in_relatives);
+    ok = FullBundleAdjustmentSolver::SolveBatch(impls, options, summaries, in_priors, sigma_pixel, in_relatives,
+                                                obs_masks, cull, cull_reports);
   } catch (...) {
     restore();
     throw;

@@ -934,6 +934,71 @@ int ba_batch_plan_problem(int n_pose, const uint8_t *pose_fixed, int n_pt,
                           int32_t *order, int32_t *obs_pair, uint8_t *last_writer,
                           int32_t *pair_lm, int32_t *pair_pose);
 
+/* ---- batched full BA: observation report, mask and in-stream outlier cull ------ */
+/* Observations are addressed in USER order throughout: the concatenated order of the arrays
+ * given to ba_batch_create (observation k of problem p at obs_off[p] + k), never the planned
+ * landmark-major order.  Units are those of obs_uv and of the points as given.
+ *
+ * ba_batch_obs_report: every observation of the batch at the values the object holds, one
+ * launch (one thread per observation, no atomics) and one synchronisation:
+ *   r2     two doubles per observation: r0, r1 as the solve defines them (projection - uv);
+ *   e2     r0^2 + r1^2;
+ *   w      the solve's Huber weight for the given threshold: huber / (|r0| + |r1|) where
+ *          that sum exceeds huber, else 1;
+ *   depth  Xc[2], the depth in the observing camera.
+ * Any output may be NULL, not all of them.  Observations that are switched off are reported
+ * like the others, and so are problems of status 1 or 2: the values are what the arithmetic
+ * gives (non-finite input gives non-finite output).
+ *
+ * ba_batch_set_obs_mask: obs_on holds one byte per observation, non-zero = on; NULL clears
+ * the mask (the original lists are in effect again).  With a mask set, every result of the
+ * batch (ba_batch_solve, ba_batch_covariance, ba_batch_marginalize, with or without a prior
+ * and relative-pose factors) agrees with the same call on a fresh batch created from the
+ * same arrays with the off observations removed, to rounding (a pair of the full structure
+ * left without observation adds zeros to the sums): the last-writer rule holds among the on
+ * observations of a (landmark, pose) pair, a landmark without on observation has C_i = 0
+ * and stays where it is, n_obs of the average error counts the on observations, and the L
+ * set of a marginalisation is decided from the on observations.  Nothing is refused for
+ * leaving a pose without observations; dropped_pivots reports it.  The mask survives
+ * ba_batch_update_values and re-solves.  A problem whose flags are all on gives the bits it
+ * gives without a mask.  Mechanism: one launch of k_ba_batch_mask_apply (one workgroup per
+ * problem) writes compacted copies of the per-problem observation lists; the solve kernels
+ * are the ones a batch without a mask launches.  ba_batch_get_obs_mask returns the mask in
+ * effect (all ones without one), also after ba_batch_cull.
+ *
+ * ba_batch_cull: evaluates the rule at the held values and updates the mask on the device
+ * (k_ba_batch_cull, one workgroup per problem, then the mask application).  An observation
+ * that is on is switched off iff !(e2 <= e2_max) (a non-finite e2 is culled) or
+ * cull_behind != 0 && !(depth > 0).  Observations already off stay off.  Starvation rule: if
+ * the rule would leave an optimisable pose of a problem with no on observation although it
+ * had one before, that problem's mask is left as it was and it reports starved = 1,
+ * n_culled = 0.  A problem of status 1 or 2 is not culled and reports that status (its
+ * counts are 0).  A batch that never had a mask gets one by this call.
+ *
+ * ba_batch_solve_culled: ba_batch_solve with `first`, the cull, ba_batch_solve with `second`,
+ * enqueued on the handle's stream with no host synchronisation in between and one at the
+ * end.  Stage 2 is an ordinary solve of the masked batch.  Rows: stage 1 writes
+ * rows[p*cap + 0 ..], stage 2 from rows[p*cap + first->max_num_iterations] on (res_first[p]
+ * .n_rows and res[p].n_rows of them); rows in between are untouched.  rows may be NULL;
+ * res_first may be NULL.
+ *
+ * Refused (-1, ba_last_error, nothing changed, before anything touches the GPU): a null
+ * batch, options, result array or cres; e2_max not finite or <= 0; with rows,
+ * cap < first->max_num_iterations + second->max_num_iterations; a stage with
+ * max_num_iterations <= 0; a report with every output NULL. */
+typedef struct { double e2_max; int cull_behind; } ba_cull_options;
+typedef struct { int n_on_before, n_culled, starved, status; } ba_batch_cull_result;
+int ba_batch_obs_report(ba_batch *b, double huber, double *r2, double *e2, double *w, double *depth);
+int ba_batch_set_obs_mask(ba_batch *b, const uint8_t *obs_on);
+int ba_batch_get_obs_mask(ba_batch *b, uint8_t *obs_on);
+int ba_batch_cull(ba_batch *b, const ba_cull_options *c, ba_batch_cull_result *cres);
+int ba_batch_solve_culled(ba_batch *b, const ba_options *first, const ba_options *second,
+                          const ba_cull_options *c, ba_iter_info *rows, int cap,
+                          ba_batch_result *res_first, ba_batch_result *res,
+                          ba_batch_cull_result *cres);
+/* Host-only (no GPU): the validation of the cull options. */
+int ba_batch_cull_check(const ba_cull_options *c);
+
 /* ---- point-only ("structure-only") solves: every landmark in one launch ------ */
 /* The mirror of pose-only: ALL poses are fixed and every landmark is solved on its own.
  * For landmark i with the observations obs_off[i] .. obs_off[i+1]-1 (each a camera, a
