@@ -338,6 +338,21 @@ SIGNATURES = {
     "ba_pgraph_cov_check": (C.c_int, [C.c_int, _U8, C.c_int, _I32, _D, C.c_int64, _I32, _I32, _D,
                                       C.c_int64, _I32, _I32, _D, _D, _D]),
     "ba_pgraph_cov_info": (C.c_int, [_P, _I64]),
+    "ba_sim3_create": (C.c_int, [C.POINTER(_P), _P, C.c_int, _D, _U8, C.c_int64, _I32, _I32, _D, _D]),
+    "ba_sim3_destroy": (None, [_P]),
+    "ba_sim3_update_values": (C.c_int, [_P, _D, _D, _D]),
+    "ba_sim3_solve": (C.c_int, [_P, C.POINTER(BaOptions), C.POINTER(BaIterInfo), C.c_int,
+                                C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ba_sim3_get_poses": (C.c_int, [_P, _D]),
+    "ba_sim3_cost": (C.c_int, [_P, _D]),
+    "ba_sim3_get_system": (C.c_int, [_P, _D, _D]),
+    "ba_sim3_factor_report": (C.c_int, [_P, _D]),
+    "ba_sim3_info": (C.c_int, [_P, _I64]),
+    "ba_sim3_last_ms": (C.c_int, [_P, _D]),
+    "ba_sim3_check": (C.c_int, [C.c_int, _D, _U8, C.c_int64, _I32, _I32, _D, _D]),
+    "ba_sim3_exp": (None, [_D, _D]),
+    "ba_sim3_log": (None, [_D, _D]),
+    "ba_sim3_adjoint": (None, [_D, _D]),
 }
 
 _lib = None

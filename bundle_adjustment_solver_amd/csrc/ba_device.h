@@ -237,6 +237,7 @@ enum KernelId {
   K_CHOL_DIAG, K_CHOL_TRSM, K_CHOL_UPDATE, K_CHOL_BACK, K_CHOL_DIAG_TRSM, K_CHOL_TAIL, K_BACKSUB_UPDATE,
   K_POSE_UPDATE, K_SCALARS, K_CONTROL, K_DAMP_INVERT, K_SCHUR_GRP, K_LIN_GRP,
   K_REL_LIN, K_REL_GATHER, K_REL_OFFDIAG,
+  K_S3_LIN, K_S3_ASSEMBLE, K_S3_TRIAL,
   K_PG_LIN_ROBUST, K_PG_ASSEMBLE_ROBUST,
   K_PG_LIN, K_PG_ASSEMBLE, K_PG_TRIAL, K_PG_CONTROL, K_COUNT
 };
@@ -387,6 +388,22 @@ void launch_pg_assemble(const PgDev &p, double *Hout, double *gout, hipStream_t 
 void launch_pg_trial(const PgDev &p, hipStream_t s);
 // mode 0: the trust-region step of one iteration; 1: ctrl->aux = sum of part[1]
 void launch_pg_control(const PgDev &p, int mode, hipStream_t s);
+
+// ---- Sim(3) pose graph (ba_sim3.hip, ba_sim3_*) ----
+// The 7-DoF graph has the pose graph's device record and controller: PgDev with 13 doubles per
+// pose (R, t, s), 62 per factor in val (Z 13, Omega 49 mirrored), kS3Rec per factor in rec, and
+// 7N where PgDev says 6N.  k_pg_control knows nothing of a pose's width and runs as it is.
+constexpr int kS3Fpb = 32;   // factors per k_s3_lin workgroup
+constexpr int kS3Rec = 112;  // record of one factor: Omega r (7), Ad^T Omega r (7), Omega Ad (49), Ad^T Omega Ad (49)
+constexpr int kS3Or = 0, kS3Gk = 7, kS3OA = 14, kS3Bk = 63;
+// cost_only = 0: linearise at the accepted poses (records + part[0]; skipped while !ctrl->relin);
+// 1: chi-square partials at the trial poses -> part[1]; 2: at the accepted poses -> part[1];
+// rep != nullptr: also s_f = r^T Omega r per factor into rep
+void launch_s3_lin(const PgDev &p, int cost_only, double *rep, hipStream_t s);
+// H + lambda diag(H) and g into the image (Hout == nullptr), or the undamped H (7N x 7N, both
+// triangles) and g into Hout / gout
+void launch_s3_assemble(const PgDev &p, double *Hout, double *gout, hipStream_t s);
+void launch_s3_trial(const PgDev &p, hipStream_t s);
 
 // ---- gradient descent (FullBundleAdjustmentSolverRefactor::SolveByGradientDescent) ----
 // Device state of the first-order loop (ba_gd_*), allocated on the first GD call after

@@ -1,0 +1,594 @@
+// ba_sim3.hip — Sim(3) pose-graph optimisation (ba_sim3_*, include/ba_hip.h):
+// Levenberg-Marquardt over relative-similarity factors alone, 7 DoF per pose, chi2 = sum_f
+// r_f^T Omega_f r_f.  The 7-DoF loop closing of a monocular map; the reference project has no
+// counterpart, the definition is the comment of ba_sim3_create.  The factor arithmetic is
+// defined once, in ba_sim3_fn.h; the lists are the pose graph's (ba_pgraph_host.h), the linear
+// solve is the level-scheduled tile Cholesky of ba_dense.hip with seven columns per pose, and
+// the controller is k_pg_control of ba_pgraph.hip, which knows nothing of a pose's width.
+// Three kernels of its own:
+//   k_s3_lin       kS3Fpb factors per workgroup: E, r and Ad7 per factor into LDS, then one
+//                  thread per element of Omega Ad, Omega r, Ad^T Omega Ad, Ad^T Omega r; the
+//                  112-double record of a factor leaves in runs of 49 / 7 consecutive doubles
+//                  (Ad and r never leave LDS); the workgroup's chi-square partial.  Cost-only
+//                  mode: the partial alone (and s_f per factor for ba_sim3_factor_report)
+//   k_s3_assemble  one thread per element of H_jj / g_j walks the pose's list, one per element
+//                  of a coupled block the block's list, in input order; H + lambda diag(H) and
+//                  g go straight into the dense image, diag(H) and g are kept for pred
+//   k_s3_trial     one thread per optimisable pose: S_j <- sim3_exp(x_j) S_j into the other pose
+//                  buffer; partials of sum |x_j| and of pred
+// One writer per element, fixed trees, no floating-point atomics: the same bits run to run.
+#include <cstddef>
+#include <cstring>
+
+#include "ba_handle.h"
+#include "ba_sim3_host.h"
+#include "ba_device_fn.h"
+#include "ba_sim3_fn.h"
+
+namespace ba {
+namespace {
+
+constexpr int kS3Block = 256;
+// the per-factor LDS rows keep their natural strides: 49 and 7 doubles are odd, so the 32
+// factor threads of the first phase write 32 different bank pairs, and the element threads of
+// the later phases read and write consecutive doubles
+constexpr int kS3AdS = 49, kS3RS = 7;
+inline int s3_cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
+
+__global__ __launch_bounds__(kS3Block) void k_s3_lin(PgDev p, int cost_only, double *rep) {
+  __shared__ double sAd[kS3Fpb * kS3AdS], sOA[kS3Fpb * kS3AdS], sR[kS3Fpb * kS3RS], sOr[kS3Fpb * kS3RS];
+  __shared__ double sm[4];
+  const PgCtrl *c = p.ctrl;
+  if (c->done) return;
+  if (!cost_only && !c->relin) return;  // a rejected step: the records still belong to the accepted poses
+  const double *P = p.poses[cost_only == 1 ? c->cur ^ 1 : c->cur];
+  const int f0 = blockIdx.x * kS3Fpb;
+  const int nf = min(kS3Fpb, p.F - f0);
+  const int tid = threadIdx.x;
+  const double *val = p.val + (size_t)f0 * kS3Val;
+  double q = 0.0;
+  if (tid < nf) {
+    const int4 jk = p.jk[f0 + tid];
+    double E[13], rr[7];
+    sim3_E(jk.x, jk.y, P, E);
+    const double *Z = val + (size_t)tid * kS3Val, *Om = Z + 13;
+    sim3_res(E, Z, rr);
+    q = sim3_quad(Om, rr);
+    if (rep) rep[f0 + tid] = q;
+    if (!cost_only) {  // r and Ad
+      sim3_Ad(E, sAd + tid * kS3AdS);
+#pragma unroll
+      for (int a = 0; a < 7; ++a) sR[tid * kS3RS + a] = rr[a];
+    }
+  }
+  if (!cost_only) {
+    double *rec = p.rec + (size_t)f0 * kS3Rec;
+    __syncthreads();
+    // OA = Omega Ad and Or = Omega r, one thread per element
+    for (int e = tid; e < 56 * nf; e += kS3Block) {
+      const int f = e / 56, k = e - 56 * f;
+      const double *Om = val + (size_t)f * kS3Val + 13;
+      if (k < 49) {
+        const double acc = sim3_OA(Om, sAd + f * kS3AdS, k);
+        sOA[f * kS3AdS + k] = acc;
+        rec[(size_t)f * kS3Rec + kS3OA + k] = acc;
+      } else {
+        const int a = k - 49;
+        const double acc = sim3_Or(Om, sR + f * kS3RS, a);
+        sOr[f * kS3RS + a] = acc;
+        rec[(size_t)f * kS3Rec + kS3Or + a] = acc;
+      }
+    }
+    __syncthreads();
+    // Bk = Ad^T OA and gk = Ad^T Or, for the factors whose k is optimisable
+    for (int e = tid; e < 56 * nf; e += kS3Block) {
+      const int f = e / 56, k = e - 56 * f;
+      if (p.jk[f0 + f].w < 0) continue;
+      if (k < 49) {
+        rec[(size_t)f * kS3Rec + kS3Bk + k] = sim3_Bk(sAd + f * kS3AdS, sOA + f * kS3AdS, k);
+      } else {
+        const int a = k - 49;
+        rec[(size_t)f * kS3Rec + kS3Gk + a] = sim3_gk(sAd + f * kS3AdS, sOr + f * kS3RS, a);
+      }
+    }
+  }
+  const double tot = block_sum(q, sm);
+  if (tid == 0) p.part[cost_only ? 1 : 0][blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(kS3Block) void k_s3_assemble(PgDev p, double *Hout, double *gout) {
+  const PgCtrl *c = p.ctrl;
+  if (c->done) return;
+  const int64_t e = (int64_t)blockIdx.x * kS3Block + threadIdx.x;
+  const int64_t nd = (int64_t)56 * p.N;
+  const size_t n7 = (size_t)7 * p.N;
+  if (e < nd) {
+    const int j = (int)(e / 56), q = (int)(e - (int64_t)56 * j);
+    const int l1 = p.pptr[j + 1];
+    double acc = 0.0;
+    for (int l = p.pptr[j]; l < l1; ++l) {
+      const int w = p.plist[l], f = w >> 1;
+      const double *rec = p.rec + (size_t)f * kS3Rec;
+      if (q < 49)
+        acc += (w & 1) ? rec[kS3Bk + q] : p.val[(size_t)f * kS3Val + 13 + q];
+      else
+        acc += (w & 1) ? rec[kS3Gk + q - 49] : -rec[kS3Or + q - 49];
+    }
+    const int pc = p.pose_col[j];
+    if (q < 49) {
+      const int rw = q / 7, cc = q - 7 * rw;
+      if (Hout) {
+        Hout[((size_t)7 * j + rw) * n7 + (size_t)7 * j + cc] = acc;
+      } else {
+        if (rw == cc) {
+          p.dH[7 * j + rw] = acc;
+          acc = acc + c->lambda * acc;
+        }
+        if (rw >= cc) p.L[(size_t)(pc + cc) * p.ld + pc + rw] = acc;
+      }
+    } else {
+      const int r = q - 49;
+      if (Hout) {
+        gout[7 * j + r] = acc;
+      } else {
+        p.g[7 * j + r] = acc;
+        p.L[(size_t)(pc + r) * p.ld + p.npad] = acc;  // the right-hand side rides as row npad
+      }
+    }
+    return;
+  }
+  const int64_t eb = e - nd;
+  if (eb >= (int64_t)49 * p.nblk) return;
+  const int b = (int)(eb / 49), rc = (int)(eb - (int64_t)49 * b), r = rc / 7, cc = rc - 7 * r;
+  const int2 hl = p.blk[b];
+  const int l1 = p.bptr[b + 1];
+  double acc = 0.0;
+  for (int l = p.bptr[b]; l < l1; ++l) {
+    const int w = p.blist[l], f = w >> 1;
+    acc -= p.rec[(size_t)f * kS3Rec + kS3OA + ((w & 1) ? cc * 7 + r : rc)];
+  }
+  if (Hout) {
+    Hout[((size_t)7 * hl.x + r) * n7 + (size_t)7 * hl.y + cc] = acc;
+    Hout[((size_t)7 * hl.y + cc) * n7 + (size_t)7 * hl.x + r] = acc;
+    return;
+  }
+  // element (r, cc) of H_hi,lo; where the column map puts it above the diagonal it is stored
+  // transposed, so that the lower triangle of the image is complete
+  const int row = p.pose_col[hl.x] + r, col = p.pose_col[hl.y] + cc;
+  p.L[row > col ? (size_t)col * p.ld + row : (size_t)row * p.ld + col] = acc;
+}
+
+__global__ __launch_bounds__(kS3Block) void k_s3_trial(PgDev p) {
+  __shared__ double sm[8];
+  const PgCtrl *c = p.ctrl;
+  if (c->done) return;
+  const int j = blockIdx.x * kS3Block + threadIdx.x;
+  double sx = 0.0, pr = 0.0;
+  if (j < p.N) {
+    double xj[7], dS[13], So[13];
+#pragma unroll
+    for (int r = 0; r < 7; ++r) xj[r] = p.x[(size_t)7 * j + r];
+    sim3_exp(xj, dS);
+    const int ps = p.opt_pose[j];
+    sim3_mul(dS, p.poses[c->cur] + (size_t)ps * 13, So);
+    double *out = p.poses[c->cur ^ 1] + (size_t)ps * 13;
+#pragma unroll
+    for (int r = 0; r < 13; ++r) out[r] = So[r];
+    double gx = 0.0, dx = 0.0, n2 = 0.0;
+#pragma unroll
+    for (int r = 0; r < 7; ++r) {
+      gx += p.g[7 * j + r] * xj[r];
+      dx += (xj[r] * p.dH[7 * j + r]) * xj[r];
+      n2 += xj[r] * xj[r];
+    }
+    pr = gx + c->lambda * dx;  // pred = g^T x + lambda x^T diag(H) x
+    sx = sqrt(n2);
+  }
+  block_sum2(sx, pr, sm);
+  if (threadIdx.x == 0) {
+    p.tpart[2 * blockIdx.x + 0] = sx;
+    p.tpart[2 * blockIdx.x + 1] = pr;
+  }
+}
+
+}  // namespace
+
+void launch_s3_lin(const PgDev &p, int cost_only, double *rep, hipStream_t s) {
+  BA_LAUNCH(K_S3_LIN, k_s3_lin, dim3(p.n_part), dim3(kS3Block), s, p, cost_only, rep);
+}
+void launch_s3_assemble(const PgDev &p, double *Hout, double *gout, hipStream_t s) {
+  const int grid = s3_cdiv((int64_t)56 * p.N + (int64_t)49 * p.nblk, kS3Block);
+  BA_LAUNCH(K_S3_ASSEMBLE, k_s3_assemble, dim3(grid), dim3(kS3Block), s, p, Hout, gout);
+}
+void launch_s3_trial(const PgDev &p, hipStream_t s) {
+  BA_LAUNCH(K_S3_TRIAL, k_s3_trial, dim3(p.n_tpart), dim3(kS3Block), s, p);
+}
+
+}  // namespace ba
+
+// ---- host side ------------------------------------------------------------------------------
+using ba::fail;
+using ba::Mem;
+
+struct ba_sim3 {
+  ba_handle *h = nullptr;
+  int n_pose = 0;
+  int64_t F = 0;
+  std::vector<uint8_t> fixed;
+  std::vector<double> Z, Om;  // the factor values as given (ba_sim3_update_values replaces one or both)
+  ba::PgraphLists lists;
+  ba::DenseSchedule sched;
+  ba::DenseDev dd;
+  ba::PgDev d{};
+  ba::PgCtrl hc{};
+  double *Ldiag = nullptr, *val = nullptr, *rep = nullptr;
+  int *zt_I = nullptr, *zt_J = nullptr, *col_x = nullptr;
+  int n_zt = 0, nb = 0, ncb = 0;
+  size_t image_bytes = 0;
+  int64_t bad_pivots = 0;
+  double last_ms = 0.0;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  std::vector<void *> allocs;
+};
+
+namespace {
+
+// what was allocated on the handle since `mark` belongs to the graph from here on
+void adopt_allocs(ba_sim3 *g, size_t mark) {
+  ba_handle *h = g->h;
+  g->allocs.insert(g->allocs.end(), h->allocs.begin() + mark, h->allocs.end());
+  h->allocs.resize(mark);
+}
+
+void free_graph(ba_sim3 *g) {
+  for (void *p : g->allocs) (void)hipFree(p);
+  if (g->e0) (void)hipEventDestroy(g->e0);
+  if (g->e1) (void)hipEventDestroy(g->e1);
+  delete g;
+}
+
+int push_ctrl(ba_sim3 *g) {
+  HIP_TRY(hipMemcpyAsync(g->d.ctrl, &g->hc, sizeof(ba::PgCtrl), hipMemcpyHostToDevice, g->h->stream));
+  return 0;
+}
+int pull_ctrl(ba_sim3 *g) {
+  HIP_TRY(hipMemcpyAsync(&g->hc, g->d.ctrl, sizeof(ba::PgCtrl), hipMemcpyDeviceToHost, g->h->stream));
+  HIP_TRY(hipStreamSynchronize(g->h->stream));
+  return 0;
+}
+const int *done_flag(const ba_sim3 *g) {
+  return (const int *)((const char *)g->d.ctrl + offsetof(ba::PgCtrl, done));
+}
+
+// the device side of a validated graph; on failure the caller frees what `g` holds
+int build_device(ba_sim3 *g, const double *S13) {
+  ba_handle *h = g->h;
+  const ba::PgraphLists &l = g->lists;
+  const ba::DenseKnobs &knobs = h->knobs.dense;
+  ba::PgDev &d = g->d;
+  const int N = l.N;
+  // both tile orders, as ba_pgraph_create builds them
+  ba::DenseSchedule cand[2];
+  const int orders[2] = {32, 64};
+  for (int k = 0; k < 2; ++k) {
+    int ncb_k = 0;
+    std::vector<uint8_t> adj;
+    ba::sim3_tile_adjacency(l, orders[k], &ncb_k, &adj);
+    if (knobs.full) std::fill(adj.begin(), adj.end(), 1);
+    ba::build_dense_schedule(ncb_k, adj, knobs.natural, orders[k], cand[k], knobs.order);
+  }
+  g->sched = cand[ba::dense_pick_tile_order(cand[0], cand[1], knobs.nb)];
+  const ba::DenseSchedule &sc = g->sched;
+  const int nb = sc.nb, ppt = ba::dense_sim3_per_tile(nb), ncb = sc.ncb;
+  g->nb = nb;
+  g->ncb = ncb;
+  d.n_pose = g->n_pose;
+  d.N = N;
+  d.F = (int)g->F;
+  d.nblk = (int)(l.blk.size() / 2);
+  d.n_part = (int)((g->F + ba::kS3Fpb - 1) / ba::kS3Fpb);
+  d.n_tpart = (N + 255) / 256;
+  d.npad = ncb * nb;
+  d.ld = d.npad + nb;
+  d.log_cap = 4096;
+  // the image first: nothing is launched, and nothing else allocated, if it does not fit
+  g->image_bytes = (size_t)d.npad * d.ld * sizeof(double);
+  {
+    hipError_t e = hipMalloc((void **)&d.L, g->image_bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      d.L = nullptr;
+      return fail("ba_sim3_create: cannot allocate the dense image of " + std::to_string(d.npad) + " x " +
+                  std::to_string(d.ld) + " doubles (" + std::to_string(g->image_bytes) + " bytes): " +
+                  hipGetErrorString(e));
+    }
+    g->allocs.push_back((void *)d.L);
+  }
+  // seven columns per pose; the nb - 7 ppt columns at the end of a tile are padding (col_x < 0:
+  // k_dense_init gives them a unit diagonal)
+  std::vector<int> pose_col((size_t)N, 0), col_x((size_t)d.npad, -1);
+  for (int j = 0; j < N; ++j) {
+    const int c0 = sc.pos_of_tile[j / ppt] * nb + 7 * (j % ppt);
+    pose_col[j] = c0;
+    for (int r = 0; r < 7; ++r) col_x[c0 + r] = 7 * j + r;
+  }
+  // tiles (re)initialised per iteration: factor pattern + diagonal + rhs row
+  std::vector<int> ztI, ztJ;
+  for (int p = 0; p < ncb; ++p) {
+    ztI.push_back(p);
+    ztJ.push_back(p);
+    for (int q = sc.row_ptr[p]; q < sc.row_ptr[p + 1]; ++q) {
+      ztI.push_back(sc.rows[q]);  // includes the rhs row block (== ncb)
+      ztJ.push_back(p);
+    }
+  }
+  g->n_zt = (int)ztI.size();
+  std::vector<double> val;
+  ba::sim3_pack_values(g->F, g->Z.data(), g->Om.data(), &val);
+  constexpr Mem R = Mem::Resident;
+  static_assert(sizeof(int4) == 16 && sizeof(int2) == 8, "layout");
+  int4 *jk = nullptr;
+  int2 *blk = nullptr;
+  int32_t *pptr = nullptr, *plist = nullptr, *bptr = nullptr, *blist = nullptr, *opt_pose = nullptr;
+  int *pc = nullptr;
+  const size_t n7 = (size_t)7 * N;
+  if (ba::upload_dense_schedule(h, sc, col_x, g->dd) ||
+      h->dalloc(R, &g->Ldiag, (size_t)ncb * ba::dense_ws_per_block(nb)) || h->upload(R, &pc, pose_col) ||
+      h->upload(R, &g->zt_I, ztI) || h->upload(R, &g->zt_J, ztJ) ||
+      h->upload(R, &d.poses[0], S13, (size_t)g->n_pose * 13) ||
+      h->upload(R, &d.poses[1], S13, (size_t)g->n_pose * 13) || h->upload(R, &jk, l.jk.data(), (size_t)g->F) ||
+      h->upload(R, &g->val, val) || h->upload(R, &pptr, l.pptr) || h->upload(R, &plist, l.plist) ||
+      h->upload(R, &blk, l.blk.data(), l.blk.size() / 2) || h->upload(R, &bptr, l.bptr) ||
+      h->upload(R, &blist, l.blist) || h->upload(R, &opt_pose, l.opt_pose) ||
+      h->dalloc(R, &d.rec, (size_t)g->F * ba::kS3Rec) || h->dalloc(R, &d.dH, n7) || h->dalloc(R, &d.g, n7) ||
+      h->dalloc(R, &d.x, n7 + 64) || h->dalloc(R, &d.part[0], (size_t)d.n_part) ||
+      h->dalloc(R, &d.part[1], (size_t)d.n_part) || h->dalloc(R, &d.tpart, (size_t)2 * d.n_tpart) ||
+      h->dalloc(R, &g->rep, (size_t)g->F) || h->dalloc(R, &d.ctrl, (size_t)1) ||
+      h->dalloc(R, &d.log, (size_t)d.log_cap))
+    return -1;
+  g->col_x = g->dd.col_x;
+  d.jk = jk;
+  d.val = g->val;
+  d.pptr = pptr;
+  d.plist = plist;
+  d.blk = blk;
+  d.bptr = bptr;
+  d.blist = blist;
+  d.opt_pose = opt_pose;
+  d.pose_col = pc;
+  HIP_TRY(hipMemset(d.L, 0, g->image_bytes));
+  HIP_TRY(hipMemset(d.rec, 0, (size_t)g->F * ba::kS3Rec * sizeof(double)));
+  HIP_TRY(hipMemset(d.dH, 0, n7 * sizeof(double)));
+  HIP_TRY(hipMemset(d.g, 0, n7 * sizeof(double)));
+  HIP_TRY(hipMemset(d.x, 0, (n7 + 64) * sizeof(double)));
+  HIP_TRY(hipMemset(d.part[0], 0, (size_t)d.n_part * sizeof(double)));
+  HIP_TRY(hipMemset(d.part[1], 0, (size_t)d.n_part * sizeof(double)));
+  HIP_TRY(hipMemset(d.tpart, 0, (size_t)2 * d.n_tpart * sizeof(double)));
+  HIP_TRY(hipMemset(g->rep, 0, (size_t)g->F * sizeof(double)));
+  HIP_TRY(hipMemset(d.ctrl, 0, sizeof(ba::PgCtrl)));
+  HIP_TRY(hipEventCreate(&g->e0));
+  HIP_TRY(hipEventCreate(&g->e1));
+  return 0;
+}
+
+// the controller for a pass outside the LM loop: the accepted buffer stays
+int begin_pass(ba_sim3 *g) {
+  g->hc.done = 0;
+  g->hc.relin = 1;
+  g->hc.lambda = 0.0;
+  return push_ctrl(g);
+}
+
+}  // namespace
+
+extern "C" {
+
+void ba_sim3_exp(const double *xi7, double *S13) { ba::sim3_exp(xi7, S13); }
+void ba_sim3_log(const double *S13, double *xi7) { ba::sim3_log(S13, xi7); }
+void ba_sim3_adjoint(const double *S13, double *Ad49) { ba::sim3_Ad(S13, Ad49); }
+
+int ba_sim3_check(int n_pose, const double *S13, const uint8_t *pose_fixed, int64_t n_rel, const int32_t *rel_j,
+                  const int32_t *rel_k, const double *Z13, const double *Omega49) {
+  std::string err;
+  if (ba::sim3_validate_host(n_pose, S13, pose_fixed, n_rel, rel_j, rel_k, Z13, Omega49, &err))
+    return fail("ba_sim3_create: " + err);
+  return 0;
+}
+
+int ba_sim3_create(ba_sim3 **out, ba_handle *h, int n_pose, const double *S13, const uint8_t *pose_fixed,
+                   int64_t n_rel, const int32_t *rel_j, const int32_t *rel_k, const double *Z13,
+                   const double *Omega49) {
+  if (!out) return fail("ba_sim3_create: null out pointer");
+  *out = nullptr;
+  if (ba_sim3_check(n_pose, S13, pose_fixed, n_rel, rel_j, rel_k, Z13, Omega49)) return -1;
+  if (!h) return fail("ba_sim3_create: null handle");
+  HIP_TRY(hipSetDevice(h->device));
+  ba_sim3 *g = new ba_sim3();
+  g->h = h;
+  g->n_pose = n_pose;
+  g->F = n_rel;
+  if (pose_fixed)
+    g->fixed.assign(pose_fixed, pose_fixed + n_pose);
+  else
+    g->fixed.assign((size_t)n_pose, 0);
+  g->Z.assign(Z13, Z13 + 13 * (size_t)n_rel);
+  g->Om.assign(Omega49, Omega49 + 49 * (size_t)n_rel);
+  ba::pgraph_build_lists(n_pose, g->fixed.data(), n_rel, rel_j, rel_k, &g->lists);
+  const size_t mark = h->allocs.size();
+  const int rc = build_device(g, S13);
+  adopt_allocs(g, mark);
+  if (rc) {
+    free_graph(g);
+    return -1;
+  }
+  *out = g;
+  return 0;
+}
+
+void ba_sim3_destroy(ba_sim3 *g) {
+  if (!g) return;
+  (void)hipSetDevice(g->h->device);
+  (void)hipStreamSynchronize(g->h->stream);
+  free_graph(g);
+}
+
+int ba_sim3_update_values(ba_sim3 *g, const double *S13, const double *Z13, const double *Omega49) {
+  if (!g) return fail("ba_sim3_update_values: null graph");
+  ba_handle *h = g->h;
+  std::string err;
+  if (ba::sim3_validate_values(g->n_pose, S13, g->F, Z13, Omega49, &err))
+    return fail("ba_sim3_update_values: " + err);
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (Z13 || Omega49) {
+    if (Z13) g->Z.assign(Z13, Z13 + 13 * (size_t)g->F);
+    if (Omega49) g->Om.assign(Omega49, Omega49 + 49 * (size_t)g->F);
+    std::vector<double> val;
+    ba::sim3_pack_values(g->F, g->Z.data(), g->Om.data(), &val);
+    HIP_TRY(hipMemcpy(g->val, val.data(), val.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (S13) {
+    const size_t bytes = (size_t)g->n_pose * 13 * sizeof(double);
+    HIP_TRY(hipMemcpy(g->d.poses[0], S13, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g->d.poses[1], S13, bytes, hipMemcpyHostToDevice));
+    g->hc.cur = 0;
+  }
+  return 0;
+}
+
+int ba_sim3_factor_report(ba_sim3 *g, double *s) {
+  if (!g || !s) return fail("ba_sim3_factor_report: bad argument");
+  ba_handle *h = g->h;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (begin_pass(g)) return -1;
+  ba::launch_s3_lin(g->d, 2, g->rep, h->stream);
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(s, g->rep, (size_t)g->F * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int ba_sim3_solve(ba_sim3 *g, const ba_options *opt, ba_iter_info *rows, int cap, int *n_iter, int *converged) {
+  if (!g || !opt) return fail("ba_sim3_solve: bad argument");
+  if (cap < 0 || (cap > 0 && !rows)) return fail("ba_sim3_solve: rows is NULL for cap > 0");
+  ba_handle *h = g->h;
+  if (n_iter) *n_iter = 0;
+  if (converged) *converged = 1;
+  if (opt->max_num_iterations <= 0) return 0;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const ba::PgDev &d = g->d;
+  ba::PgCtrl &c = g->hc;
+  const int cur = c.cur;
+  std::memset(&c, 0, sizeof(c));
+  c.cur = cur;
+  c.lambda = (double)opt->initial_lambda;
+  c.thr_step = (double)opt->threshold_step_size;
+  c.thr_cost = (double)opt->threshold_cost_change;
+  c.dec_ratio = (double)opt->decrease_ratio_lambda;
+  c.inc_ratio = (double)opt->increase_ratio_lambda;
+  c.max_iter = opt->max_num_iterations;
+  c.gn = opt->gauss_newton ? 1 : 0;
+  c.relin = 1;
+  if (push_ctrl(g)) return -1;
+  HIP_TRY(hipMemsetAsync(g->dd.bad_pivots, 0, sizeof(int), s));
+  ba::g_ktimer = h->timing ? &h->kt : nullptr;
+  const int *done = done_flag(g);
+  HIP_TRY(hipEventRecord(g->e0, s));
+  for (int it = 0; it < opt->max_num_iterations; ++it) {
+    ba::launch_s3_lin(d, 0, nullptr, s);
+    ba::launch_dense_init(d.L, d.ld, g->col_x, g->zt_I, g->zt_J, g->n_zt, g->nb, done, s);
+    ba::launch_s3_assemble(d, nullptr, nullptr, s);
+    ba::dense_factor_solve(d.L, d.npad, d.ld, g->Ldiag, d.x, done, g->sched, g->dd, g->dd.plan[g->dd.flow_ok], s);
+    ba::launch_s3_trial(d, s);
+    ba::launch_s3_lin(d, 1, nullptr, s);
+    ba::launch_pg_control(d, 0, s);
+  }
+  HIP_TRY(hipEventRecord(g->e1, s));
+  ba::g_ktimer = nullptr;
+  if (pull_ctrl(g)) return -1;
+  if (h->timing) h->kt.collect();
+  HIP_TRY(hipGetLastError());
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, g->e0, g->e1);
+  g->last_ms = ms;
+  int bad = 0;
+  HIP_TRY(hipMemcpy(&bad, g->dd.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
+  if (bad >= ba::kFlowTimeout) return fail("ba_sim3_solve: a dataflow hand-off timed out");
+  g->bad_pivots = bad;
+  static_assert(sizeof(ba::DevIterRec) == sizeof(ba_iter_info), "row layout");
+  const int n = std::min(std::min(c.iter, cap), d.log_cap);
+  if (n > 0) HIP_TRY(hipMemcpy(rows, d.log, (size_t)n * sizeof(ba_iter_info), hipMemcpyDeviceToHost));
+  if (n_iter) *n_iter = c.iter;
+  if (converged) *converged = c.converged;
+  return 0;
+}
+
+int ba_sim3_get_poses(ba_sim3 *g, double *S13) {
+  if (!g || !S13) return fail("ba_sim3_get_poses: bad argument");
+  HIP_TRY(hipSetDevice(g->h->device));
+  HIP_TRY(hipStreamSynchronize(g->h->stream));
+  HIP_TRY(hipMemcpy(S13, g->d.poses[g->hc.cur], (size_t)g->n_pose * 13 * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int ba_sim3_cost(ba_sim3 *g, double *chi2) {
+  if (!g || !chi2) return fail("ba_sim3_cost: bad argument");
+  HIP_TRY(hipSetDevice(g->h->device));
+  if (begin_pass(g)) return -1;
+  ba::launch_s3_lin(g->d, 2, nullptr, g->h->stream);
+  ba::launch_pg_control(g->d, 1, g->h->stream);
+  if (pull_ctrl(g)) return -1;
+  HIP_TRY(hipGetLastError());
+  *chi2 = g->hc.aux;
+  return 0;
+}
+
+int ba_sim3_get_system(ba_sim3 *g, double *H, double *g7N) {
+  if (!g) return fail("ba_sim3_get_system: null graph");
+  ba_handle *h = g->h;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t n7 = (size_t)7 * g->d.N;
+  double *dH = nullptr, *dg = nullptr;
+  HIP_TRY(hipMalloc((void **)&dH, n7 * n7 * sizeof(double)));
+  if (hipMalloc((void **)&dg, n7 * sizeof(double)) != hipSuccess) {
+    (void)hipFree(dH);
+    return fail("ba_sim3_get_system: hipMalloc");
+  }
+  int rc = 0;
+  if (hipMemsetAsync(dH, 0, n7 * n7 * sizeof(double), h->stream) != hipSuccess || begin_pass(g)) rc = -1;
+  if (!rc) {
+    ba::launch_s3_lin(g->d, 0, nullptr, h->stream);
+    ba::launch_s3_assemble(g->d, dH, dg, h->stream);
+    if (hipStreamSynchronize(h->stream) != hipSuccess || hipGetLastError() != hipSuccess ||
+        (H && hipMemcpy(H, dH, n7 * n7 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+        (g7N && hipMemcpy(g7N, dg, n7 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+      rc = fail("ba_sim3_get_system: device error");
+  }
+  (void)hipFree(dH);
+  (void)hipFree(dg);
+  return rc;
+}
+
+int ba_sim3_info(ba_sim3 *g, int64_t out9[9]) {
+  if (!g || !out9) return fail("ba_sim3_info: bad argument");
+  out9[0] = g->d.N;
+  out9[1] = g->F;
+  out9[2] = g->d.nblk;
+  out9[3] = g->nb;
+  out9[4] = g->ncb;
+  out9[5] = g->sched.nlev;
+  out9[6] = (int64_t)g->image_bytes;
+  out9[7] = g->bad_pivots;
+  out9[8] = ba::kS3Fpb;
+  return 0;
+}
+
+int ba_sim3_last_ms(ba_sim3 *g, double *ms) {
+  if (!g || !ms) return fail("ba_sim3_last_ms: bad argument");
+  *ms = g->last_ms;
+  return 0;
+}
+
+}  // extern "C"

@@ -1912,6 +1912,144 @@ class BaPoseGraph:
         return dict(batch_cols=int(v[0]), cols_per_wave=int(v[1]), batches=int(v[2]), workspace_bytes=int(v[3]))
 
 
+def _sim3_arrays(pose_S, pose_fixed, rels):
+    S = np.ascontiguousarray(pose_S, np.float64).reshape(-1, 13)
+    fx = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
+    j = np.ascontiguousarray(rels["j"], np.int32).reshape(-1)
+    k = np.ascontiguousarray(rels["k"], np.int32).reshape(-1)
+    Z = np.ascontiguousarray(rels["Z"], np.float64).reshape(-1, 13)
+    Om = np.ascontiguousarray(rels["Omega"], np.float64).reshape(-1, 49)
+    return S, fx, j, k, Z, Om
+
+
+def sim3_check(pose_S, pose_fixed, rels):
+    """Host-only validation of BaSim3Graph's inputs (ba_sim3_check); raises BaError."""
+    S, fx, j, k, Z, Om = _sim3_arrays(pose_S, pose_fixed, rels)
+    check(_lib.load().ba_sim3_check(S.shape[0], _dp(S) if S.size else None, None if fx is None else _up(fx),
+                                    len(j), _ip(j), _ip(k), _dp(Z), _dp(Om)), "ba_sim3_check")
+
+
+def sim3_exp(xi):
+    """The library's sim3_exp (csrc/ba_sim3_fn.h, on the host): xi = [v; omega; sigma] -> S13"""
+    xi, S = np.ascontiguousarray(xi, np.float64).reshape(7), np.zeros(13)
+    _lib.load().ba_sim3_exp(_dp(xi), _dp(S))
+    return S
+
+
+def sim3_log(S13):
+    """The library's sim3_log (on the host): S13 = [R row-major, t, s] -> xi = [v; omega; sigma]"""
+    S, xi = np.ascontiguousarray(S13, np.float64).reshape(13), np.zeros(7)
+    _lib.load().ba_sim3_log(_dp(S), _dp(xi))
+    return xi
+
+
+def sim3_adjoint(S13):
+    """The library's Ad7 (on the host): [[sR, hat(t) R, -t], [0, R, 0], [0, 0, 1]] (7, 7)"""
+    S, Ad = np.ascontiguousarray(S13, np.float64).reshape(13), np.zeros((7, 7))
+    _lib.load().ba_sim3_adjoint(_dp(S), _dp(Ad))
+    return Ad
+
+
+class BaSim3Graph:
+    """Sim(3) pose-graph optimisation (ba_sim3_* of include/ba_hip.h): the 7-DoF
+    loop closing of a monocular map, chi-square Levenberg-Marquardt over relative-similarity
+    factors alone.  pose_S (n, 13) S_jw = [R row-major, t, s] in scaled units, pose_fixed (n,)
+    or None, rels = dict(j (F,), k (F,), Z (F, 13), Omega (F, 7, 7)).  The structure is planned
+    once; update_values + solve re-optimise new values.  owner: a BaProblem whose handle is
+    borrowed, or None for a handle of its own."""
+
+    def __init__(self, pose_S, pose_fixed, rels, device=0, owner=None):
+        self.lib = _lib.load()
+        self.g = None
+        self._own = owner is None
+        self._owner = None
+        S, fx, j, k, Z, Om = _sim3_arrays(pose_S, pose_fixed, rels)
+        if not (len(k) == len(j) and Z.shape[0] == len(j) and Om.shape[0] == len(j)) or \
+                (fx is not None and len(fx) != S.shape[0]):
+            raise ValueError("BaSim3Graph: needs pose_S (n, 13), pose_fixed (n,), j (F,), k (F,), Z (F, 13), "
+                             "Omega (F, 7, 7)")
+        sim3_check(S, fx, dict(j=j, k=k, Z=Z, Omega=Om))   # refusals need no device
+        self.n_pose, self.n_rel = S.shape[0], len(j)
+        self._owner = BaProblem(device) if owner is None else owner
+        g = C.c_void_p()
+        check(self.lib.ba_sim3_create(C.byref(g), self._owner.h, self.n_pose, _dp(S),
+                                      None if fx is None else _up(fx), self.n_rel, _ip(j), _ip(k),
+                                      _dp(Z), _dp(Om)), "ba_sim3_create")
+        self.g = g
+
+    def close(self):
+        if self.g:
+            self.lib.ba_sim3_destroy(self.g)
+            self.g = None
+        if self._owner is not None and self._own:
+            self._owner.close()
+        self._owner = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update_values(self, pose_S=None, Z=None, Omega=None):
+        """New values for the same structure (ba_sim3_update_values); None keeps."""
+        S = None if pose_S is None else np.ascontiguousarray(pose_S, np.float64).reshape(-1, 13)
+        Zs = None if Z is None else np.ascontiguousarray(Z, np.float64).reshape(-1, 13)
+        Om = None if Omega is None else np.ascontiguousarray(Omega, np.float64).reshape(-1, 49)
+        if (S is not None and S.shape[0] != self.n_pose) or (Zs is not None and Zs.shape[0] != self.n_rel) or \
+                (Om is not None and Om.shape[0] != self.n_rel):
+            raise ValueError("update_values: the structure is fixed (same number of poses / factors)")
+        check(self.lib.ba_sim3_update_values(self.g, None if S is None else _dp(S),
+                                             None if Zs is None else _dp(Zs),
+                                             None if Om is None else _dp(Om)), "ba_sim3_update_values")
+
+    def solve(self, opt, cap=None, rows=None):
+        """-> (rows, converged), as BaPoseGraph.solve"""
+        cap = max(1, opt.max_num_iterations) if cap is None else cap
+        given = rows is not None
+        rows = (BaIterInfo * max(1, cap))() if rows is None else rows
+        n_iter, conv = C.c_int(0), C.c_int(0)
+        check(self.lib.ba_sim3_solve(self.g, C.byref(opt), rows, cap, C.byref(n_iter), C.byref(conv)),
+              "ba_sim3_solve")
+        self.n_iter = n_iter.value
+        n = cap if given else min(n_iter.value, cap)
+        return [rows[i] for i in range(n)], bool(conv.value)
+
+    def poses(self):
+        S = np.zeros((self.n_pose, 13))
+        check(self.lib.ba_sim3_get_poses(self.g, _dp(S)), "ba_sim3_get_poses")
+        return S
+
+    def cost(self):
+        v = C.c_double(0.0)
+        check(self.lib.ba_sim3_cost(self.g, C.byref(v)), "ba_sim3_cost")
+        return v.value
+
+    def system(self):
+        """-> (H (7N, 7N), g (7N,)): the undamped system at the poses the object holds"""
+        N = self.info()["N"]
+        H, g = np.zeros((7 * N, 7 * N)), np.zeros(7 * N)
+        check(self.lib.ba_sim3_get_system(self.g, _dp(H), _dp(g)), "ba_sim3_get_system")
+        return H, g
+
+    def factor_report(self):
+        """-> s (F,): s_f = r_f^T Omega_f r_f of every factor at the poses the object holds"""
+        s = np.zeros(self.n_rel)
+        check(self.lib.ba_sim3_factor_report(self.g, _dp(s)), "ba_sim3_factor_report")
+        return s
+
+    def info(self):
+        out = (C.c_int64 * 9)()
+        check(self.lib.ba_sim3_info(self.g, out), "ba_sim3_info")
+        keys = ("N", "factors", "blocks", "nb", "tiles", "levels", "image_bytes", "bad_pivots", "fpb")
+        return {key: int(out[i]) for i, key in enumerate(keys)}
+
+    def last_ms(self):
+        v = C.c_double(0.0)
+        check(self.lib.ba_sim3_last_ms(self.g, C.byref(v)), "ba_sim3_last_ms")
+        return v.value
+
+
 class BaStream:
     """Observation streaming (include/ba_hip.h ba_stream_*): the
     same problem-construction calls and LM loop as BaProblem for a problem whose
@@ -2045,6 +2183,7 @@ class FullBundleAdjustmentSolver:
         self._relatives = []      # AddRelativePose: one scaled dict (F = 1) per factor, input order
         self._relative_units = []  # per factor: sigma_pixel SCALER, the unit of its Mahalanobis distance
         self._relative_report = None
+        self._sim3_relatives = []  # AddRelativeSim3: (j, k, Z13, Omega 7x7) scaled, input order; SolveSim3Graph only
         self.num_total_poses_ = 0
         self.num_total_points_ = 0
         self.num_fixed_poses_ = 0
@@ -2442,6 +2581,92 @@ class FullBundleAdjustmentSolver:
         self._pose_T_jw = [T_new]
         n_pt = self.num_total_points_
         return self._write_back(T_new, np.zeros((n_pt, 3)), np.zeros(n_pt, bool), rows, converged, summary, t0)
+
+    def AddRelativeSim3(self, pose_j, pose_k, measurement, information, sigma_pixel=1.0):
+        """(new) A relative-similarity factor between two registered poses (objects or integer
+        handles; distinct, not both fixed) for SolveSim3Graph, the 7-DoF loop closing of a
+        monocular map.  measurement: a 4x4 similarity [[sR, t], [0, 1]], the
+        measured pose_j^-1 * pose_k in AddPose's convention and units (s = 1: a rigid edge).
+        information: the 7x7 of the tangent [v; omega; sigma] in the caller's units, scaled as
+        _scaled_relatives scales the 6x6 (sigma, like omega, has no unit).  Solve, SolveBatch,
+        ComputeCovariance and SolvePoseGraph never see these factors; SolveSim3Graph sees no
+        factor of AddRelativePose.  May be called at any time; Reset drops the factors."""
+        hj, hk = self._pose_handle(pose_j), self._pose_handle(pose_k)
+        if hj is None or hk is None:
+            raise RuntimeError("There is no pointer in the BA pose pool.")
+        M = np.array(measurement, np.float64).reshape(4, 4)
+        with np.errstate(all="ignore"):
+            s = float(np.cbrt(np.linalg.det(M[:3, :3])))
+            Z = np.r_[(M[:3, :3] / s).reshape(9), M[:3, 3] * SCALER, s]
+        d = np.r_[np.full(3, INVERSE_SCALER), np.ones(4)]
+        w = 1.0 / (float(sigma_pixel) ** 2 * SCALER * SCALER)
+        Om = (d[:, None] * np.asarray(information, np.float64).reshape(7, 7) * d[None, :]) / w
+        self._sim3_relatives.append((hj, hk, Z, Om))
+
+    def _sim3_arrays(self):
+        f = self._sim3_relatives
+        return dict(j=np.array([r[0] for r in f], np.int32), k=np.array([r[1] for r in f], np.int32),
+                    Z=np.array([r[2] for r in f]).reshape(-1, 13), Omega=np.array([r[3] for r in f]).reshape(-1, 7, 7))
+
+    def SolveSim3Graph(self, options, summary=None, point_anchors=None):
+        """(new) Sim(3) pose-graph optimisation over the factors of AddRelativeSim3 ALONE, on the
+        registered poses with their fixed flags (BaSim3Graph, ba_sim3_*).  Every
+        registered pose starts as the similarity (R, t, s = 1) of its rigid pose.  Fills `summary`
+        as SolvePoseGraph does and writes each pose back RIGID, T_jw = [R, t / s]; returns the
+        scale s per registered pose (1 for a fixed pose).
+        point_anchors: None, or one entry per registered point: a registered pose (object or
+        handle), or None / a negative handle to leave the point.  An anchored, non-fixed point
+        moves to S_new,a^-1 (T_old,a X), so that its projection into its anchor keyframe is
+        unchanged.  The solver's own copies follow; a finalized problem of the same solver takes
+        poses and points with ReloadParameterValues."""
+        t0 = time.perf_counter()
+        if summary is not None:
+            summary.max_iteration_ = options.iteration_handle.max_num_iterations
+            summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change
+            summary.threshold_step_size_ = options.convergence_handle.threshold_step_size
+            summary.convergence_status_ = True
+        if not self._sim3_relatives or not self.num_total_poses_:
+            raise RuntimeError("SolveSim3Graph: poses (AddPose) and factors (AddRelativeSim3) must be added first")
+        n_pt = self.num_total_points_
+        anchors = np.full(n_pt, -1, np.int64)
+        if point_anchors is not None:
+            if len(point_anchors) != n_pt:
+                raise ValueError("SolveSim3Graph: one anchor (or None) per registered point")
+            for i, a in enumerate(point_anchors):
+                if a is None or (isinstance(a, (int, np.integer)) and a < 0):
+                    continue
+                h = self._pose_handle(a)
+                if h is None:
+                    raise RuntimeError("There is no pointer in the BA pose pool.")
+                anchors[i] = h
+        c_opt = options.to_c()
+        c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
+        T_old = np.concatenate(self._pose_T_jw, axis=0)
+        pf = np.zeros(self.num_total_poses_, np.uint8)
+        pf[list(self._pose_fixed)] = 1
+        g = BaSim3Graph(np.c_[T_old, np.ones(len(T_old))], pf, self._sim3_arrays(), self.device)
+        try:
+            rows, converged = g.solve(c_opt)
+            S_new = g.poses()
+        finally:
+            g.close()
+        scales = S_new[:, 12].copy()
+        T_new = S_new[:, :12].copy()
+        T_new[:, 9:12] /= scales[:, None]
+        X = np.concatenate(self._pt_X, axis=0) if n_pt else np.zeros((0, 3))
+        moved = anchors >= 0
+        moved[list(self._pt_fixed)] = False
+        if moved.any():
+            a = anchors[moved]
+            Ro, to = T_old[a, :9].reshape(-1, 3, 3), T_old[a, 9:12]
+            Rn, tn, sn = S_new[a, :9].reshape(-1, 3, 3), S_new[a, 9:12], scales[a]
+            Y = np.einsum("nij,nj->ni", Ro, X[moved]) + to
+            X = X.copy()
+            X[moved] = np.einsum("nji,nj->ni", Rn, (Y - tn) / sn[:, None])
+            self._pt_X = [X]
+        self._pose_T_jw = [T_new]
+        self._write_back(T_new, X, moved, rows, converged, summary, t0)
+        return scales
 
     def _pose_graph(self, what):
         """the registered poses and the factors of AddRelativePose as a BaPoseGraph, robust

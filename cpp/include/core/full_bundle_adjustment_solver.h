@@ -97,6 +97,36 @@ class FullBundleAdjustmentSolver {
   // SolvePoseGraph.
   void GetRelativeWeights(std::vector<double> *s, std::vector<double> *w) const;
 
+  // (new) A relative-similarity factor between two registered poses for SolveSim3Graph, the
+  // 7-DoF loop closing of a monocular map (ba_sim3_* of include/ba_hip.h; the definition is
+  // there).  measurement: the row-major 4x4 similarity [[sR, t], [0, 1]], the measured
+  // inverse(*pose_j) * (*pose_k) in the convention and units of AddPose (s = 1: a rigid edge).
+  // information: the row-major 7x7 of the tangent [v; omega; sigma] in the caller's units,
+  // converted for sigma_pixel as RelativePose::information is (sigma, like omega, has no unit);
+  // only its lower triangle is read.
+  struct RelativeSim3 {
+    _BA_Pose *pose_j{nullptr};
+    _BA_Pose *pose_k{nullptr};
+    double measurement[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    double information[49] = {0.0};
+  };
+  // (new) May be called at any time; Reset drops the factors.  Solve, SolveBatch,
+  // ComputeCovariance and SolvePoseGraph never see them, and SolveSim3Graph sees no factor of
+  // AddRelativePose.  Throws std::runtime_error on a pose that was never registered.
+  void AddRelativeSim3(const RelativeSim3 &factor, double sigma_pixel = 1.0);
+  // (new) Sim(3) pose-graph optimisation over the factors of AddRelativeSim3 ALONE.  Every
+  // registered pose starts as the similarity (R, t, s = 1) of its rigid pose; the rows of
+  // `summary` are those of ba_sim3_solve.  Each pose is written back RIGID, T_jw = [R, t / s];
+  // *scales (may be null) receives s per registered pose (1 for a fixed pose).
+  // point_anchors (null: no point moves): one entry per registered point in registration order,
+  // the registration index of a pose or -1.  An anchored, non-fixed point moves to
+  // S_new,a^-1 (T_old,a X), so that its projection into its anchor keyframe is unchanged (on the
+  // host).  The solver's own copies follow; a finalized problem of the same solver takes poses
+  // and points with ReloadParameterValues.  Throws std::runtime_error without poses or
+  // factors, on a wrong anchor and on every refusal of ba_sim3_create.
+  bool SolveSim3Graph(Options options, Summary *summary = nullptr, const std::vector<int> *point_anchors = nullptr,
+                      std::vector<double> *scales = nullptr);
+
   // (new) Solve the registered problems of several solver objects in ONE GPU launch
   // (ba_batch_solve of include/ba_hip.h: one persistent workgroup per problem runs the
   // whole LM loop; per problem at most 16 optimisable poses, 64 poses, 8 cameras).
@@ -391,6 +421,9 @@ class FullBundleAdjustmentSolver {
   double PoseGraphUnit(const char *who, const std::vector<double> &more) const;
   RelativeArrays relatives_;  // AddRelativePose: j, k, Z, Omega of this solver's factors (off unused)
   std::vector<double> report_s_, report_w_;  // the factor report of the last SolvePoseGraph
+  // AddRelativeSim3: j, k, Z (13 per factor) and Omega (49) in scaled units, input order
+  std::vector<int32_t> sim3_j_, sim3_k_;
+  std::vector<double> sim3_Z_, sim3_Omega_;
   // the options' thresholds and iteration limit into a Summary (nullptr: nothing)
   static void BeginSummary(Summary *summary, const Options &options);
   // stderr warnings about weakly connected poses / points (reference

@@ -75,6 +75,15 @@ class FullBundleAdjustmentSolverRefactor {
   // FullBundleAdjustmentSolver::SolvePoseGraph; solver_type selects Levenberg-Marquardt or
   // Gauss-Newton as in Solve, for this call only
   bool SolvePoseGraph(Options options, Summary *summary = nullptr);
+  // (new) the Sim(3) pose graph, see FullBundleAdjustmentSolver::AddRelativeSim3 and
+  // SolveSim3Graph; solver_type selects Levenberg-Marquardt or Gauss-Newton as in Solve, for
+  // this call only
+  using RelativeSim3 = FullBundleAdjustmentSolver::RelativeSim3;
+  void AddRelativeSim3(const RelativeSim3 &factor, double sigma_pixel = 1.0) {
+    impl_.AddRelativeSim3(factor, sigma_pixel);
+  }
+  bool SolveSim3Graph(Options options, Summary *summary = nullptr, const std::vector<int> *point_anchors = nullptr,
+                      std::vector<double> *scales = nullptr);
   // (new) see FullBundleAdjustmentSolver::GetRelativeWeights
   void GetRelativeWeights(std::vector<double> *s, std::vector<double> *w) const { impl_.GetRelativeWeights(s, w); }
   // (new) see FullBundleAdjustmentSolver::ComputePoseGraphCovariance and GateLoopClosures

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <sstream>
 #include <stdexcept>
 
@@ -58,6 +59,10 @@ void FullBundleAdjustmentSolver::Reset() {  // :44-70
   relatives_ = RelativeArrays();
   report_s_.clear();
   report_w_.clear();
+  sim3_j_.clear();
+  sim3_k_.clear();
+  sim3_Z_.clear();
+  sim3_Omega_.clear();
   num_fixed_poses_ = num_fixed_points_ = 0;
 }
 
@@ -451,6 +456,103 @@ bool FullBundleAdjustmentSolver::SolvePoseGraph(Options options, Summary *summar
   report_w_.swap(rep_w);
   const std::vector<uint8_t> no_point(points_.size(), 0);
   WriteBack(T.data(), nullptr, no_point.data());
+  if (summary != nullptr) {
+    for (int k = 0; k < n_iter && k < static_cast<int>(rows.size()); ++k)
+      summary->optimization_info_list_.push_back(ToInfo(rows[k]));
+    summary->convergence_status_ = converged != 0;
+    summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
+  }
+  return true;
+}
+
+void FullBundleAdjustmentSolver::AddRelativeSim3(const RelativeSim3 &f, double sigma_pixel) {
+  const auto ij = pose_index_.find(f.pose_j), ik = pose_index_.find(f.pose_k);
+  if (ij == pose_index_.end() || ik == pose_index_.end())
+    throw std::runtime_error("AddRelativeSim3: there is no pointer in the BA pose pool.");
+  const double *M = f.measurement;
+  const double det = M[0] * (M[5] * M[10] - M[6] * M[9]) - M[1] * (M[4] * M[10] - M[6] * M[8]) +
+                     M[2] * (M[4] * M[9] - M[5] * M[8]);
+  const double s = std::cbrt(det);
+  sim3_j_.push_back(ij->second);
+  sim3_k_.push_back(ik->second);
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) sim3_Z_.push_back(M[4 * r + c] / s);
+  for (int r = 0; r < 3; ++r) sim3_Z_.push_back(M[4 * r + 3] * static_cast<double>(scaler_));
+  sim3_Z_.push_back(s);
+  // the caller's units -> scaled units, unit pixel noise: as PackRelatives converts the 6x6
+  const double w = 1.0 / (sigma_pixel * sigma_pixel * static_cast<double>(scaler_) * static_cast<double>(scaler_));
+  const auto d = [this](int r) { return r < 3 ? static_cast<double>(inverse_scaler_) : 1.0; };
+  for (int r = 0; r < 7; ++r)
+    for (int c = 0; c < 7; ++c) sim3_Omega_.push_back((d(r) * f.information[7 * r + c] * d(c)) / w);
+}
+
+bool FullBundleAdjustmentSolver::SolveSim3Graph(Options options, Summary *summary,
+                                                const std::vector<int> *point_anchors, std::vector<double> *scales) {
+  timer::StopWatch stopwatch("BundleAdjustmentSolver::SolveSim3Graph");
+  stopwatch.Start();
+  BeginSummary(summary, options);
+  if (poses_.empty() || sim3_j_.empty())
+    throw std::runtime_error("SolveSim3Graph: poses (AddPose) and factors (AddRelativeSim3) must be added first");
+  const size_t n_pose = poses_.size(), n_pt = points_.size();
+  if (point_anchors != nullptr) {
+    if (point_anchors->size() != n_pt) throw std::runtime_error("SolveSim3Graph: one anchor (or -1) per registered point");
+    for (int a : *point_anchors)
+      if (a >= static_cast<int>(n_pose)) throw std::runtime_error("SolveSim3Graph: an anchor is no registered pose");
+  }
+  std::vector<double> S(13 * n_pose), S_new(13 * n_pose);
+  std::vector<uint8_t> pose_fixed(n_pose, 0);
+  for (size_t p = 0; p < n_pose; ++p) {
+    Pack12(T_jw_[p], &S[13 * p]);
+    S[13 * p + 12] = 1.0;
+    pose_fixed[p] = fixed_poses_.count(static_cast<int>(p)) > 0;
+  }
+  const ba_options o = PackOptions(options, gauss_newton_);
+  std::vector<ba_iter_info> rows(static_cast<size_t>(std::max(1, o.max_num_iterations)));
+  int n_iter = 0, converged = 0;
+  // the graph borrows a handle for its device and stream: the finalized problem's, or one of its own
+  ba_handle *h = handle_;
+  if (h == nullptr) Check(ba_create(&h, device_id_), "ba_create");
+  ba_sim3 *g = nullptr;
+  int rc = ba_sim3_create(&g, h, static_cast<int>(n_pose), S.data(), pose_fixed.data(),
+                          static_cast<int64_t>(sim3_j_.size()), sim3_j_.data(), sim3_k_.data(), sim3_Z_.data(),
+                          sim3_Omega_.data());
+  const char *what = "ba_sim3_create";
+  if (rc == 0) {
+    rc = ba_sim3_solve(g, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged);
+    what = "ba_sim3_solve";
+  }
+  if (rc == 0) {
+    rc = ba_sim3_get_poses(g, S_new.data());
+    what = "ba_sim3_get_poses";
+  }
+  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
+  ba_sim3_destroy(g);
+  if (h != handle_) ba_destroy(h);
+  if (rc != 0) throw std::runtime_error(std::string(what) + ": " + err);
+  // rigid poses T_jw = [R, t / s]; the anchored points follow their keyframes
+  std::vector<double> T(12 * n_pose), X(3 * n_pt, 0.0);
+  std::vector<uint8_t> moved(n_pt, 0);
+  for (size_t p = 0; p < n_pose; ++p) {
+    const double s = S_new[13 * p + 12];
+    for (int e = 0; e < 9; ++e) T[12 * p + e] = S_new[13 * p + e];
+    for (int e = 9; e < 12; ++e) T[12 * p + e] = S_new[13 * p + e] / s;
+  }
+  for (size_t q = 0; point_anchors != nullptr && q < n_pt; ++q) {
+    const int a = (*point_anchors)[q];
+    if (a < 0 || fixed_points_.count(static_cast<int>(q))) continue;
+    const double *So = &S[13 * static_cast<size_t>(a)], *Sn = &S_new[13 * static_cast<size_t>(a)];
+    double Y[3];
+    for (int r = 0; r < 3; ++r)  // T_old,a X, then over the new scale
+      Y[r] = ((So[3 * r] * X_[q](0) + So[3 * r + 1] * X_[q](1) + So[3 * r + 2] * X_[q](2) + So[9 + r]) - Sn[9 + r]) /
+             Sn[12];
+    for (int r = 0; r < 3; ++r) X[3 * q + r] = Sn[r] * Y[0] + Sn[3 + r] * Y[1] + Sn[6 + r] * Y[2];  // R_new^T
+    moved[q] = 1;
+  }
+  WriteBack(T.data(), X.data(), moved.data());
+  if (scales != nullptr) {
+    scales->resize(n_pose);
+    for (size_t p = 0; p < n_pose; ++p) (*scales)[p] = S_new[13 * p + 12];
+  }
   if (summary != nullptr) {
     for (int k = 0; k < n_iter && k < static_cast<int>(rows.size()); ++k)
       summary->optimization_info_list_.push_back(ToInfo(rows[k]));

@@ -115,6 +115,25 @@ bool FullBundleAdjustmentSolverRefactor::SolvePoseGraph(Options options, Summary
   return ok;
 }
 
+bool FullBundleAdjustmentSolverRefactor::SolveSim3Graph(Options options, Summary *summary,
+                                                        const std::vector<int> *point_anchors,
+                                                        std::vector<double> *scales) {
+  if (options.solver_type != SolverType::LEVENBERG_MARQUARDT && options.solver_type != SolverType::GAUSS_NEWTON)
+    throw std::runtime_error(
+        "FullBundleAdjustmentSolverRefactor::SolveSim3Graph: solver_type must be GAUSS_NEWTON or LEVENBERG_MARQUARDT");
+  const bool before = impl_.gauss_newton_;  // the mode holds for this call only
+  impl_.SetGaussNewton(options.solver_type == SolverType::GAUSS_NEWTON);
+  bool ok = false;
+  try {
+    ok = impl_.SolveSim3Graph(options, summary, point_anchors, scales);
+  } catch (...) {
+    impl_.SetGaussNewton(before);
+    throw;
+  }
+  impl_.SetGaussNewton(before);
+  return ok;
+}
+
 bool FullBundleAdjustmentSolverRefactor::SolveByGradientDescent(Options options, Summary *summary) {  // :1075-1367
   return impl_.Run(options, summary, true);
 }

@@ -1245,6 +1245,85 @@ int ba_pgraph_cov_check(int n_pose, const uint8_t *pose_fixed, int n_pose_sel,
  * last ba_pgraph_covariance / ba_pgraph_gate ran, bytes of the workspace at that width } */
 int ba_pgraph_cov_info(ba_pgraph *g, int64_t out4[4]);
 
+/* ---- Sim(3) pose-graph optimisation ----------------------------------------
+ * The 7-DoF loop closing of a monocular map: Levenberg-Marquardt over relative-similarity
+ * factors ALONE.  A monocular map drifts in scale, and a rigid graph spreads that drift into
+ * translation; here every keyframe carries a scale as well.  The reference project has no
+ * counterpart; this comment is the definition.
+ *
+ * Pose: S_jw = (R, t, s), stored as 13 doubles S13 = { R row-major (9), t (3), s }, s > 0,
+ * translation in scaled units.  It maps x_j = s R x_w + t; as a matrix [[sR, t], [0, 1]].
+ *
+ * Tangent: xi = [v; omega; sigma] (7), algebra element [[hat(omega) + sigma I, v], [0, 0]].
+ *   sim3_exp(xi) = (exp(hat(omega)), W v, e^sigma),
+ *   W = integral_0^1 e^(tau sigma) exp(tau hat(omega)) d tau;
+ * sim3_log is its inverse on rotation angles below pi.
+ *
+ * Update: S_j <- sim3_exp(x_j) S_j, the left perturbation of the SE(3) graph.
+ *
+ * Factor: (j, k, Z13, Omega49).  Z measures E = S_j S_k^-1; r = sim3_log(E Z^-1); the
+ * first-order Jacobians are I on j and -Ad7(E) on k, where for E = (R, t, s)
+ *   Ad7(E) = [[sR, hat(t) R, -t], [0, R, 0], [0, 0, 1]].
+ * Omega is read from its lower triangle.  Several factors may name one pair in either
+ * orientation; they are summed in input order.
+ *
+ * Cost and system over the N optimisable poses: chi2 = sum_f r_f^T Omega_f r_f,
+ *   H_jj += Omega,  H_kk += Ad7^T Omega Ad7,  H_jk += -Omega Ad7,
+ *   g_j += -Omega r,  g_k += Ad7^T Omega r,
+ * with 7x7 blocks; a fixed pose (all seven components) receives nothing.  Step
+ * (H + lambda diag(H)) x = g.
+ *
+ * Control: step, gain ratio, lambda update, Gauss-Newton mode, stop test and rows are those of
+ * ba_pgraph_solve above, word for word; the mean step is the mean of |x_j| over 7 components.
+ *
+ * The object keeps the structure (lists, level schedule, the dense image of npad x (npad + nb)
+ * doubles with seven columns per pose: 4 poses per tile of order 32, 9 per tile of order 64)
+ * across re-solves and borrows the handle's device, stream and BA_DENSE_* knobs:
+ * ba_sim3_destroy first, ba_destroy after.  A problem or an SE(3) graph on the same handle is
+ * not touched.
+ *
+ * Validation happens before anything touches the GPU, with the rules and messages of
+ * ba_pgraph_check ("S_jw" for "T_jw"); also refused: a scale of a pose or of Z that is not
+ * finite or not positive, and a rotation part of a pose or of Z that is not finite (the
+ * message names the pose or the factor).  If the image cannot be allocated the call fails with
+ * its size in the message, before any launch.  A refused call changes nothing.
+ *
+ * One writer per element, fixed summation order, no floating-point atomics: the same bits run
+ * to run.  No robust kernels, covariance blocks or gate here: those are the SE(3) graph's. */
+typedef struct ba_sim3 ba_sim3;
+int ba_sim3_create(ba_sim3 **out, ba_handle *h, int n_pose, const double *S13,
+                   const uint8_t *pose_fixed, int64_t n_rel, const int32_t *rel_j,
+                   const int32_t *rel_k, const double *Z13, const double *Omega49);
+void ba_sim3_destroy(ba_sim3 *g);
+/* New VALUES for the same structure; NULL = keep.  Validated as at creation. */
+int ba_sim3_update_values(ba_sim3 *g, const double *S13, const double *Z13, const double *Omega49);
+/* As ba_pgraph_solve: the whole loop is enqueued, one synchronisation at the end; at most cap
+ * rows are written, rows beyond *n_iter are untouched; the solved poses stay in the object. */
+int ba_sim3_solve(ba_sim3 *g, const ba_options *opt, ba_iter_info *rows, int cap, int *n_iter,
+                  int *converged);
+int ba_sim3_get_poses(ba_sim3 *g, double *S13);
+/* chi-square at the poses the object holds */
+int ba_sim3_cost(ba_sim3 *g, double *chi2);
+/* The undamped system at the poses the object holds, for tests: H (7N x 7N, row-major, both
+ * triangles) and g (7N); optimisable poses in the user's order.  Either may be NULL. */
+int ba_sim3_get_system(ba_sim3 *g, double *H, double *g7N);
+/* s_f = r_f^T Omega_f r_f of every factor at the poses the object holds (n_rel doubles) */
+int ba_sim3_factor_report(ba_sim3 *g, double *s);
+/* out9 = { N, factors, coupled blocks, tile order, tiles, levels, bytes of the dense image,
+ * non-positive pivots of the last solve, factors per k_s3_lin workgroup } */
+int ba_sim3_info(ba_sim3 *g, int64_t out9[9]);
+/* Device time of the last ba_sim3_solve, from events around the enqueued loop. */
+int ba_sim3_last_ms(ba_sim3 *g, double *ms);
+/* Host-only (no GPU): the validation of ba_sim3_create. */
+int ba_sim3_check(int n_pose, const double *S13, const uint8_t *pose_fixed, int64_t n_rel,
+                  const int32_t *rel_j, const int32_t *rel_k, const double *Z13,
+                  const double *Omega49);
+/* Host-only (no GPU): the functions the kernels call (csrc/ba_sim3_fn.h), for tests of the
+ * arithmetic.  xi7 = [v; omega; sigma]; Ad49 row-major. */
+void ba_sim3_exp(const double *xi7, double *S13);
+void ba_sim3_log(const double *S13, double *xi7);
+void ba_sim3_adjoint(const double *S13, double *Ad49);
+
 #ifdef __cplusplus
 }
 #endif
