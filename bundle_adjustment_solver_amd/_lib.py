@@ -353,6 +353,14 @@ SIGNATURES = {
     "ba_sim3_exp": (None, [_D, _D]),
     "ba_sim3_log": (None, [_D, _D]),
     "ba_sim3_adjoint": (None, [_D, _D]),
+    "ba_sim3_set_robust": (C.c_int, [_P, _I32, _D]),
+    "ba_sim3_robust_check": (C.c_int, [C.c_int64, _I32, _D]),
+    "ba_sim3_factor_weights": (C.c_int, [_P, _D, _D]),
+    "ba_sim3_covariance": (C.c_int, [_P, C.c_int, _I32, _D, C.c_int64, _I32, _I32, _D, _D, _I64]),
+    "ba_sim3_gate": (C.c_int, [_P, C.c_int64, _I32, _I32, _D, _D, _D, _D, _D, _I64]),
+    "ba_sim3_cov_check": (C.c_int, [C.c_int, _U8, C.c_int, _I32, _D, C.c_int64, _I32, _I32, _D,
+                                    C.c_int64, _I32, _I32, _D, _D, _D]),
+    "ba_sim3_cov_info": (C.c_int, [_P, _I64]),
 }
 
 _lib = None

@@ -1730,7 +1730,7 @@ const char *ba_kernel_name(int id) {
       "k_chol_diag", "k_chol_trsm", "k_chol_update", "k_chol_back", "k_chol_diag_trsm", "k_chol_tail", "k_backsub_update",
       "k_pose_update", "k_scalars", "k_control", "k_damp_invert", "k_schur_grp", "k_lin_grp",
       "k_rel_lin", "k_rel_gather", "k_rel_offdiag",
-      "k_s3_lin", "k_s3_assemble", "k_s3_trial",
+      "k_s3_lin", "k_s3_assemble", "k_s3_trial", "k_s3_lin_robust", "k_s3_assemble_robust",
       "k_pg_lin_robust", "k_pg_assemble_robust",
       "k_pg_lin", "k_pg_assemble", "k_pg_trial", "k_pg_control"};
   return (id >= 0 && id < ba::K_COUNT) ? names[id] : "";

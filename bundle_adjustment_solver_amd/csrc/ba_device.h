@@ -237,7 +237,7 @@ enum KernelId {
   K_CHOL_DIAG, K_CHOL_TRSM, K_CHOL_UPDATE, K_CHOL_BACK, K_CHOL_DIAG_TRSM, K_CHOL_TAIL, K_BACKSUB_UPDATE,
   K_POSE_UPDATE, K_SCALARS, K_CONTROL, K_DAMP_INVERT, K_SCHUR_GRP, K_LIN_GRP,
   K_REL_LIN, K_REL_GATHER, K_REL_OFFDIAG,
-  K_S3_LIN, K_S3_ASSEMBLE, K_S3_TRIAL,
+  K_S3_LIN, K_S3_ASSEMBLE, K_S3_TRIAL, K_S3_LIN_ROBUST, K_S3_ASSEMBLE_ROBUST,
   K_PG_LIN_ROBUST, K_PG_ASSEMBLE_ROBUST,
   K_PG_LIN, K_PG_ASSEMBLE, K_PG_TRIAL, K_PG_CONTROL, K_COUNT
 };
@@ -404,6 +404,23 @@ void launch_s3_lin(const PgDev &p, int cost_only, double *rep, hipStream_t s);
 // triangles) and g into Hout / gout
 void launch_s3_assemble(const PgDev &p, double *Hout, double *gout, hipStream_t s);
 void launch_s3_trial(const PgDev &p, hipStream_t s);
+// Robust kernels on Sim(3) factors (ba_sim3_set_robust): k_s3_lin written out a
+// second time and the assembly's body instantiated a second time, with sum rho(s) for chi-square
+// and w Omega for Omega; PgRobust is their extra argument as it is the SE(3) graph's.  rb.s and rb.w are written by cost_only = 0 (they belong
+// to the records) and by cost_only = 3 (= 2 plus the report).
+void launch_s3_lin_robust(const PgDev &p, const PgRobust &rb, int cost_only, hipStream_t s);
+void launch_s3_assemble_robust(const PgDev &p, const PgRobust &rb, double *Hout, double *gout, hipStream_t s);
+
+// ---- covariance blocks and the gate of a Sim(3) graph (ba_sim3_cov.hip) ----
+// launch_pgcov_batch at width 7: 49 doubles per block, 7 per residual, cand_val 62 doubles per
+// candidate (ba_sim3_host.h), poses 13 doubles each.  The groups are the pose graph's.
+struct PgCovGroup;
+struct S3CovOut {
+  double *pose49, *cross49, *rel49, *r7, *innov49, *d2;
+};
+void launch_s3cov_batch(const PgDev &p, const double *Ldiag, int nb, int ncb, const double *poses,
+                        const int *trow_ptr, const int *trow, const PgCovGroup *groups, int ng,
+                        const double *cand_val, double *Zw, int bw, const S3CovOut &out, hipStream_t s);
 
 // ---- gradient descent (FullBundleAdjustmentSolverRefactor::SolveByGradientDescent) ----
 // Device state of the first-order loop (ba_gd_*), allocated on the first GD call after

@@ -29,6 +29,7 @@
 #include "ba_handle.h"
 #include "ba_pgraph_host.h"
 #include "ba_rel_fn.h"
+#include "ba_robust_fn.h"
 
 namespace ba {
 namespace {
@@ -37,31 +38,7 @@ constexpr int kPgBlock = 256;
 constexpr int kPgAdS = 37, kPgRS = 7;  // odd strides of the per-factor LDS rows: no bank conflicts
 inline int pg_cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
 
-// rho(s) and w = rho'(s) of one factor (include/ba_hip.h); s = 0 gives w = 1 for every kind
-__device__ __forceinline__ double pg_rho(int kind, double c, double s, double *w) {
-  const double c2 = c * c;
-  if (kind == 1) {
-    if (s <= c2) {
-      *w = 1.0;
-      return s;
-    }
-    const double rs = sqrt(s);
-    *w = c / rs;
-    return 2.0 * c * rs - c2;
-  }
-  if (kind == 2) {
-    const double u = s / c2;
-    *w = 1.0 / (1.0 + u);
-    return c2 * log1p(u);
-  }
-  if (kind == 3) {
-    const double t = c2 / (c2 + s);
-    *w = t * t;
-    return t * s;
-  }
-  *w = 1.0;
-  return s;
-}
+// (rho(s) and w = rho'(s) of one factor: pg_rho of ba_robust_fn.h, shared with ba_sim3.hip)
 
 // The robust record as a kernel argument: an empty struct for the plain instantiation
 struct PgNoRobust {};

@@ -1929,6 +1929,39 @@ def sim3_check(pose_S, pose_fixed, rels):
                                     len(j), _ip(j), _ip(k), _dp(Z), _dp(Om)), "ba_sim3_check")
 
 
+def sim3_robust_check(kind, scale):
+    """Host-only validation of BaSim3Graph.set_robust's inputs (ba_sim3_robust_check); raises BaError."""
+    kd, sc = _robust_arrays(kind, scale)
+    n = 0 if kd is None else len(kd)
+    check(_lib.load().ba_sim3_robust_check(n, None if kd is None else _ip(kd), None if sc is None else _dp(sc)),
+          "ba_sim3_robust_check")
+
+
+def _sim3_candidate_arrays(j, k, Z, Omega):
+    j, k = _pair_arrays((np.atleast_1d(j), np.atleast_1d(k)))
+    Z = np.ascontiguousarray(Z, np.float64).reshape(-1, 13)
+    Om = np.ascontiguousarray(Omega, np.float64).reshape(-1, 49)
+    if Z.shape[0] != len(j) or Om.shape[0] != len(j):
+        raise ValueError("candidates: needs j (n,), k (n,), Z (n, 13), Omega (n, 7, 7)")
+    return j, k, Z, Om
+
+
+def sim3_cov_check(n_pose, pose_fixed, pose_sel=None, pairs=None, candidates=None):
+    """Host-only validation of BaSim3Graph.covariance / gate (ba_sim3_cov_check); raises BaError.
+    pose_sel: user indices; pairs: (j, k) arrays or (n, 2); candidates: dict(j, k, Z, Omega)."""
+    fx = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
+    ps = np.zeros(0, np.int32) if pose_sel is None else np.ascontiguousarray(pose_sel, np.int32).reshape(-1)
+    pj, pk = _pair_arrays(pairs)
+    c = candidates
+    cj, ck, Z, Om = _sim3_candidate_arrays(c["j"], c["k"], c["Z"], c["Omega"]) if c is not None else \
+        _sim3_candidate_arrays([], [], np.zeros((0, 13)), np.zeros((0, 49)))
+    out = np.zeros(1)   # the outputs only have to be there
+    check(_lib.load().ba_sim3_cov_check(int(n_pose), None if fx is None else _up(fx), len(ps), _ip(ps), _dp(out),
+                                        len(pj), _ip(pj), _ip(pk), _dp(out), len(cj), _ip(cj), _ip(ck),
+                                        _dp(Z) if Z.size else None, _dp(Om) if Om.size else None, _dp(out)),
+          "ba_sim3_cov_check")
+
+
 def sim3_exp(xi):
     """The library's sim3_exp (csrc/ba_sim3_fn.h, on the host): xi = [v; omega; sigma] -> S13"""
     xi, S = np.ascontiguousarray(xi, np.float64).reshape(7), np.zeros(13)
@@ -1970,12 +2003,70 @@ class BaSim3Graph:
                              "Omega (F, 7, 7)")
         sim3_check(S, fx, dict(j=j, k=k, Z=Z, Omega=Om))   # refusals need no device
         self.n_pose, self.n_rel = S.shape[0], len(j)
+        self._fixed = np.zeros(self.n_pose, np.uint8) if fx is None else fx.copy()
         self._owner = BaProblem(device) if owner is None else owner
         g = C.c_void_p()
         check(self.lib.ba_sim3_create(C.byref(g), self._owner.h, self.n_pose, _dp(S),
                                       None if fx is None else _up(fx), self.n_rel, _ip(j), _ip(k),
                                       _dp(Z), _dp(Om)), "ba_sim3_create")
         self.g = g
+        if rels.get("robust_kind") is not None:   # a factor dict that carries kernels
+            self.set_robust(rels["robust_kind"], rels.get("robust_scale"))
+
+    def set_robust(self, kind, scale=None):
+        """Robust kernels of the factors (ba_sim3_set_robust), as
+        BaPoseGraph.set_robust: kind (F,) of ROBUST_NONE / HUBER / CAUCHY / GEMAN_MCCLURE, scale
+        (F,) the Mahalanobis distance c > 0 of each factor whose kind is not 0.  kind None clears
+        every kernel.  No re-planning: call it between solves as often as needed."""
+        kd, sc = _robust_arrays(kind, scale, self.n_rel)
+        check(self.lib.ba_sim3_set_robust(self.g, None if kd is None else _ip(kd), None if sc is None else _dp(sc)),
+              "ba_sim3_set_robust")
+
+    def factor_weights(self):
+        """-> (s (F,), w (F,)): s_f = r_f^T Omega_f r_f and the robust weight w_f of every factor
+        at the poses the object holds (ba_sim3_factor_weights); w = 1 without a kernel"""
+        s, w = np.zeros(self.n_rel), np.zeros(self.n_rel)
+        check(self.lib.ba_sim3_factor_weights(self.g, _dp(s), _dp(w)), "ba_sim3_factor_weights")
+        return s, w
+
+    def covariance(self, pose_sel=None, pairs=None):
+        """-> (cov_pose (n, 7, 7), cov_cross (p, 7, 7), cov_rel (p, 7, 7)): blocks of the inverse
+        of system()'s H at the poses the object holds (ba_sim3_covariance):
+        Sigma_jj per selected pose, Sigma_jk and the covariance Sigma_E of S_j S_k^-1 per pair,
+        tangent [v; omega; sigma].  pose_sel: user indices of optimisable poses (None: all of
+        them); pairs: (j, k) arrays or (p, 2).  Scaled units.  self.dropped_pivots: non-positive
+        pivots of the factorisation."""
+        ps = np.flatnonzero(self._fixed == 0).astype(np.int32) if pose_sel is None else \
+            np.ascontiguousarray(pose_sel, np.int32).reshape(-1)
+        pj, pk = _pair_arrays(pairs)
+        cp, cc, cr = np.zeros((len(ps), 7, 7)), np.zeros((len(pj), 7, 7)), np.zeros((len(pj), 7, 7))
+        dropped = C.c_int64(0)
+        check(self.lib.ba_sim3_covariance(self.g, len(ps), _ip(ps) if len(ps) else None,
+                                          _dp(cp) if len(ps) else None, len(pj), _ip(pj) if len(pj) else None,
+                                          _ip(pk) if len(pj) else None, _dp(cc) if len(pj) else None,
+                                          _dp(cr) if len(pj) else None, C.byref(dropped)), "ba_sim3_covariance")
+        self.dropped_pivots = dropped.value
+        return cp, cc, cr
+
+    def gate(self, j, k, Z, Omega):
+        """-> (d2 (n,), r (n, 7), P (n, 7, 7)) of loop-closure candidates shaped like factors
+        (ba_sim3_gate): r = sim3_log(S_j S_k^-1 Z^-1), P = Sigma_E + Omega^-1, d2 = r^T P^-1 r, to
+        be compared with a chi-square quantile of 7 degrees of freedom (24.32 at 0.999)."""
+        cj, ck, Zs, Om = _sim3_candidate_arrays(j, k, Z, Omega)
+        n = len(cj)
+        d2, r, P = np.zeros(n), np.zeros((n, 7)), np.zeros((n, 7, 7))
+        dropped = C.c_int64(0)
+        check(self.lib.ba_sim3_gate(self.g, n, _ip(cj) if n else None, _ip(ck) if n else None,
+                                    _dp(Zs) if n else None, _dp(Om) if n else None, _dp(d2) if n else None,
+                                    _dp(r) if n else None, _dp(P) if n else None, C.byref(dropped)), "ba_sim3_gate")
+        self.dropped_pivots = dropped.value
+        return d2, r, P
+
+    def cov_info(self):
+        """Column batches of covariance / gate on this graph (BA_COV_BATCH of the borrowed handle overrides)"""
+        v = (C.c_int64 * 4)()
+        check(self.lib.ba_sim3_cov_info(self.g, v), "ba_sim3_cov_info")
+        return dict(batch_cols=int(v[0]), cols_per_wave=int(v[1]), batches=int(v[2]), workspace_bytes=int(v[3]))
 
     def close(self):
         if self.g:
@@ -2184,6 +2275,9 @@ class FullBundleAdjustmentSolver:
         self._relative_units = []  # per factor: sigma_pixel SCALER, the unit of its Mahalanobis distance
         self._relative_report = None
         self._sim3_relatives = []  # AddRelativeSim3: (j, k, Z13, Omega 7x7) scaled, input order; SolveSim3Graph only
+        self._sim3_robust = []     # per Sim(3) factor: (kind, scale in scaled units)
+        self._sim3_units = []      # per Sim(3) factor: sigma_pixel SCALER, the unit of its Mahalanobis distance
+        self._sim3_report = None
         self.num_total_poses_ = 0
         self.num_total_points_ = 0
         self.num_fixed_poses_ = 0
@@ -2582,7 +2676,7 @@ class FullBundleAdjustmentSolver:
         n_pt = self.num_total_points_
         return self._write_back(T_new, np.zeros((n_pt, 3)), np.zeros(n_pt, bool), rows, converged, summary, t0)
 
-    def AddRelativeSim3(self, pose_j, pose_k, measurement, information, sigma_pixel=1.0):
+    def AddRelativeSim3(self, pose_j, pose_k, measurement, information, sigma_pixel=1.0, robust=None):
         """(new) A relative-similarity factor between two registered poses (objects or integer
         handles; distinct, not both fixed) for SolveSim3Graph, the 7-DoF loop closing of a
         monocular map.  measurement: a 4x4 similarity [[sR, t], [0, 1]], the
@@ -2590,10 +2684,26 @@ class FullBundleAdjustmentSolver:
         information: the 7x7 of the tangent [v; omega; sigma] in the caller's units, scaled as
         _scaled_relatives scales the 6x6 (sigma, like omega, has no unit).  Solve, SolveBatch,
         ComputeCovariance and SolvePoseGraph never see these factors; SolveSim3Graph sees no
-        factor of AddRelativePose.  May be called at any time; Reset drops the factors."""
+        factor of AddRelativePose.  May be called at any time; Reset drops the factors.
+        robust (default None: none): (kind, scale) as AddRelativePose takes it, a robust kernel
+        for SolveSim3Graph; scale is the Mahalanobis distance c against
+        `information` as given, in the caller's units with `sigma_pixel`."""
         hj, hk = self._pose_handle(pose_j), self._pose_handle(pose_k)
         if hj is None or hk is None:
             raise RuntimeError("There is no pointer in the BA pose pool.")
+        kind, scale = 0, 0.0
+        if robust is not None and int(robust[0]) != 0:
+            sim3_robust_check([int(robust[0])], [float(robust[1])])
+            # s in scaled units is s in the caller's units times (sigma_pixel SCALER)^2
+            kind, scale = int(robust[0]), float(robust[1]) * float(sigma_pixel) * SCALER
+        Z, Om = self._scaled_sim3(measurement, information, sigma_pixel)
+        self._sim3_relatives.append((hj, hk, Z, Om))
+        self._sim3_robust.append((kind, scale))
+        self._sim3_units.append(float(sigma_pixel) * SCALER)
+
+    @staticmethod
+    def _scaled_sim3(measurement, information, sigma_pixel):
+        """a 4x4 similarity and a 7x7 information in the caller's units -> (Z13, Omega 7x7) scaled"""
         M = np.array(measurement, np.float64).reshape(4, 4)
         with np.errstate(all="ignore"):
             s = float(np.cbrt(np.linalg.det(M[:3, :3])))
@@ -2601,12 +2711,26 @@ class FullBundleAdjustmentSolver:
         d = np.r_[np.full(3, INVERSE_SCALER), np.ones(4)]
         w = 1.0 / (float(sigma_pixel) ** 2 * SCALER * SCALER)
         Om = (d[:, None] * np.asarray(information, np.float64).reshape(7, 7) * d[None, :]) / w
-        self._sim3_relatives.append((hj, hk, Z, Om))
+        return Z, Om
 
     def _sim3_arrays(self):
         f = self._sim3_relatives
-        return dict(j=np.array([r[0] for r in f], np.int32), k=np.array([r[1] for r in f], np.int32),
-                    Z=np.array([r[2] for r in f]).reshape(-1, 13), Omega=np.array([r[3] for r in f]).reshape(-1, 7, 7))
+        out = dict(j=np.array([r[0] for r in f], np.int32), k=np.array([r[1] for r in f], np.int32),
+                   Z=np.array([r[2] for r in f]).reshape(-1, 13), Omega=np.array([r[3] for r in f]).reshape(-1, 7, 7))
+        if any(kd for kd, _ in self._sim3_robust):   # the kernels the factors carry; none: the dict of before
+            out.update(robust_kind=np.array([kd for kd, _ in self._sim3_robust], np.int32),
+                       robust_scale=np.array([c for _, c in self._sim3_robust], np.float64))
+        return out
+
+    def _sim3_graph(self, what):
+        """the registered poses, each the similarity (R, t, s = 1) of its rigid pose, and the factors
+        of AddRelativeSim3 as a BaSim3Graph, robust kernels included"""
+        if not self._sim3_relatives or not self.num_total_poses_:
+            raise RuntimeError("%s: poses (AddPose) and factors (AddRelativeSim3) must be added first" % what)
+        T = np.concatenate(self._pose_T_jw, axis=0)
+        pf = np.zeros(self.num_total_poses_, np.uint8)
+        pf[list(self._pose_fixed)] = 1
+        return BaSim3Graph(np.c_[T, np.ones(len(T))], pf, self._sim3_arrays(), self.device)
 
     def SolveSim3Graph(self, options, summary=None, point_anchors=None):
         """(new) Sim(3) pose-graph optimisation over the factors of AddRelativeSim3 ALONE, on the
@@ -2618,14 +2742,16 @@ class FullBundleAdjustmentSolver:
         handle), or None / a negative handle to leave the point.  An anchored, non-fixed point
         moves to S_new,a^-1 (T_old,a X), so that its projection into its anchor keyframe is
         unchanged.  The solver's own copies follow; a finalized problem of the same solver takes
-        poses and points with ReloadParameterValues."""
+        poses and points with ReloadParameterValues.  Factors added with robust=(kind, scale) are
+        solved with their kernels; GetRelativeSim3Weights returns every factor's s
+        and weight at the solved poses."""
         t0 = time.perf_counter()
         if summary is not None:
             summary.max_iteration_ = options.iteration_handle.max_num_iterations
             summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change
             summary.threshold_step_size_ = options.convergence_handle.threshold_step_size
             summary.convergence_status_ = True
-        if not self._sim3_relatives or not self.num_total_poses_:
+        if not self._sim3_relatives or not self.num_total_poses_:   # before the anchors are looked at, as ever
             raise RuntimeError("SolveSim3Graph: poses (AddPose) and factors (AddRelativeSim3) must be added first")
         n_pt = self.num_total_points_
         anchors = np.full(n_pt, -1, np.int64)
@@ -2641,15 +2767,20 @@ class FullBundleAdjustmentSolver:
                 anchors[i] = h
         c_opt = options.to_c()
         c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
+        g = self._sim3_graph("SolveSim3Graph")
         T_old = np.concatenate(self._pose_T_jw, axis=0)
-        pf = np.zeros(self.num_total_poses_, np.uint8)
-        pf[list(self._pose_fixed)] = 1
-        g = BaSim3Graph(np.c_[T_old, np.ones(len(T_old))], pf, self._sim3_arrays(), self.device)
         try:
             rows, converged = g.solve(c_opt)
             S_new = g.poses()
+            if any(kd for kd, _ in self._sim3_robust):
+                s, w = g.factor_weights()
+            else:   # no kernel: the report of before, nothing robust is allocated or launched
+                s = g.factor_report()
+                w = np.ones(len(s))
         finally:
             g.close()
+        unit = np.asarray(self._sim3_units)   # s in scaled units = s in the caller's times unit^2
+        self._sim3_report = (s / (unit * unit), w)
         scales = S_new[:, 12].copy()
         T_new = S_new[:, :12].copy()
         T_new[:, 9:12] /= scales[:, None]
@@ -2730,6 +2861,79 @@ class FullBundleAdjustmentSolver:
         g = self._pose_graph("GateLoopClosures")
         try:
             d2 = g.gate(sr["j"], sr["k"], sr["Z"], sr["Omega"])[0]
+        finally:
+            g.close()
+        return d2 / (unit * unit)
+
+    def GetRelativeSim3Weights(self):
+        """(new) -> (s, w) of the last SolveSim3Graph, one entry per factor in the order of
+        AddRelativeSim3, at the solved similarities: s = r^T information r in the caller's units
+        and the robust weight w (1 for a factor without a kernel)."""
+        if getattr(self, "_sim3_report", None) is None:
+            raise RuntimeError("GetRelativeSim3Weights: SolveSim3Graph has not run")
+        s, w = self._sim3_report
+        return s.copy(), w.copy()
+
+    def _sim3_graph_unit(self, what, more=()):
+        """_pose_graph_unit for the factors of AddRelativeSim3"""
+        units = list(self._sim3_units) + list(more)
+        for u in units:
+            if u != units[0]:
+                raise RuntimeError("%s: the factors and candidates were given with sigma_pixel = %g and %g; "
+                                   "a covariance in the caller's units needs one value"
+                                   % (what, units[0] / SCALER, u / SCALER))
+        return units[0] if units else SCALER
+
+    def ComputeSim3GraphCovariance(self, poses, pairs=()):
+        """(new) -> (cov_pose (n, 7, 7), cov_cross (p, 7, 7), cov_rel (p, 7, 7)) of the Sim(3) graph
+        that SolveSim3Graph solves, at the registered poses as they are now, each the similarity
+        (R, t, s = 1) (BaSim3Graph.covariance; nothing is solved): the marginal
+        covariance of each pose of `poses` (objects or handles, optimisable) in the tangent
+        [v; omega; sigma], and for each (pose_j, pose_k) of `pairs` the cross block Sigma_jk and
+        the covariance of S_jw S_kw^-1.  Caller's units for the sigma_pixel the factors were added
+        with: (sigma_pixel SCALER)^2 D Sigma D with D = diag(100 I3, I4), the vector d of
+        AddRelativeSim3 (omega and sigma have no unit); factors with different sigma_pixel raise
+        RuntimeError."""
+        unit = self._sim3_graph_unit("ComputeSim3GraphCovariance")
+
+        def handles(objs):
+            hs = [self._pose_handle(o) for o in objs]
+            if any(h is None for h in hs):
+                raise RuntimeError("There is no pointer in the BA pose pool.")
+            return np.asarray(hs, np.int32)
+        ps = handles(poses)
+        pj, pk = handles([p[0] for p in pairs]), handles([p[1] for p in pairs])
+        g = self._sim3_graph("ComputeSim3GraphCovariance")
+        try:
+            blocks = g.covariance(ps, (pj, pk))
+        finally:
+            g.close()
+        d = np.r_[np.full(3, INVERSE_SCALER), np.ones(4)]
+        return tuple((unit * unit) * (d[None, :, None] * b * d[None, None, :]) for b in blocks)
+
+    def GateSim3LoopClosures(self, candidates):
+        """(new) -> d2 (n,) of Sim(3) loop-closure candidates against the Sim(3) graph at the
+        registered poses, BEFORE they are added (BaSim3Graph.gate), in the caller's
+        units; accept below a chi-square quantile of 7 degrees of freedom (24.32 at 0.999).  A
+        candidate is a dict with the keys of AddRelativeSim3 (pose_j, pose_k, measurement,
+        information, optionally sigma_pixel = 1.0); every candidate and factor must have been
+        given with one sigma_pixel (RuntimeError otherwise).  No robust weight applies to a candidate."""
+        sig = [float(c.get("sigma_pixel", 1.0)) for c in candidates]
+        unit = self._sim3_graph_unit("GateSim3LoopClosures", [v * SCALER for v in sig])
+        hj, hk, Z, Om = [], [], [], []
+        for c, sg in zip(candidates, sig):
+            a, b = self._pose_handle(c["pose_j"]), self._pose_handle(c["pose_k"])
+            if a is None or b is None:
+                raise RuntimeError("There is no pointer in the BA pose pool.")
+            z, om = self._scaled_sim3(c["measurement"], c["information"], sg)   # its own sigma_pixel: the factors'
+            hj.append(a)
+            hk.append(b)
+            Z.append(z)
+            Om.append(om)
+        g = self._sim3_graph("GateSim3LoopClosures")
+        try:
+            d2 = g.gate(np.asarray(hj, np.int32), np.asarray(hk, np.int32), np.array(Z).reshape(-1, 13),
+                        np.array(Om).reshape(-1, 7, 7))[0]
         finally:
             g.close()
         return d2 / (unit * unit)

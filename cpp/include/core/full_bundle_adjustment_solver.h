@@ -21,6 +21,7 @@
 
 struct ba_handle;  // include/ba_hip.h
 struct ba_pgraph;
+struct ba_sim3;
 struct ba_batch;
 
 namespace visual_navigation {
@@ -109,6 +110,12 @@ class FullBundleAdjustmentSolver {
     _BA_Pose *pose_k{nullptr};
     double measurement[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     double information[49] = {0.0};
+    // (new) a robust kernel for SolveSim3Graph, as RelativePose::robust_kind / robust_scale:
+    // 0 none (the default; robust_scale is then unread), 1 Huber, 2 Cauchy, 3 Geman-McClure;
+    // robust_scale is the Mahalanobis distance c > 0 against `information` as given, in the
+    // caller's units with sigma_pixel
+    int robust_kind{0};
+    double robust_scale{0.0};
   };
   // (new) May be called at any time; Reset drops the factors.  Solve, SolveBatch,
   // ComputeCovariance and SolvePoseGraph never see them, and SolveSim3Graph sees no factor of
@@ -126,6 +133,25 @@ class FullBundleAdjustmentSolver {
   // factors, on a wrong anchor and on every refusal of ba_sim3_create.
   bool SolveSim3Graph(Options options, Summary *summary = nullptr, const std::vector<int> *point_anchors = nullptr,
                       std::vector<double> *scales = nullptr);
+  // (new) s and w of the last SolveSim3Graph at the solved similarities, one entry per factor in
+  // the order of AddRelativeSim3 (ba_sim3_factor_weights), as GetRelativeWeights: s in the
+  // caller's units, w = 1 for a factor without a kernel.  Either output may be null.  Throws
+  // std::runtime_error before the first SolveSim3Graph.
+  void GetRelativeSim3Weights(std::vector<double> *s, std::vector<double> *w) const;
+  // (new) ComputePoseGraphCovariance at width 7, on the graph that SolveSim3Graph solves at the
+  // solver's current values, each pose the similarity (R, t, s = 1) (ba_sim3_covariance): tangent
+  // [v; omega; sigma], the caller's units (sigma_pixel scaler)^2 D Sigma D with D = diag(100 I3,
+  // I4), for the sigma_pixel the factors were added with (two values throw).  Returns false if
+  // the factorisation dropped a pivot.
+  bool ComputeSim3GraphCovariance(const std::vector<_BA_Pose *> &poses,
+                                  const std::vector<std::pair<_BA_Pose *, _BA_Pose *>> &pairs,
+                                  std::vector<Eigen::Matrix<double, 7, 7>> *cov_poses,
+                                  std::vector<Eigen::Matrix<double, 7, 7>> *cov_cross,
+                                  std::vector<Eigen::Matrix<double, 7, 7>> *cov_rel);
+  // (new) GateLoopClosures at width 7 (ba_sim3_gate): (*d2)[c] in the caller's units, to be
+  // compared with a chi-square quantile of 7 degrees of freedom (24.32 at 0.999).  A candidate
+  // is a factor of AddRelativeSim3; its robust kernel, if any, is not read.
+  bool GateSim3LoopClosures(const std::vector<RelativeSim3> &candidates, double sigma_pixel, std::vector<double> *d2);
 
   // (new) Solve the registered problems of several solver objects in ONE GPU launch
   // (ba_batch_solve of include/ba_hip.h: one persistent workgroup per problem runs the
@@ -424,6 +450,16 @@ class FullBundleAdjustmentSolver {
   // AddRelativeSim3: j, k, Z (13 per factor) and Omega (49) in scaled units, input order
   std::vector<int32_t> sim3_j_, sim3_k_;
   std::vector<double> sim3_Z_, sim3_Omega_;
+  // per Sim(3) factor: the robust kernel (scale in scaled units) and sigma_pixel * scaler, the
+  // unit of its Mahalanobis distance; s and w of the last SolveSim3Graph
+  std::vector<int32_t> sim3_kind_;
+  std::vector<double> sim3_scale_, sim3_unit_, sim3_report_s_, sim3_report_w_;
+  // one Sim(3) factor or candidate into scaled units: Z (13) and Omega (49) appended
+  void PackSim3(const RelativeSim3 &f, double sigma_pixel, std::vector<double> *Z, std::vector<double> *Omega) const;
+  // the registered poses as similarities (s = 1) and the factors of AddRelativeSim3 as a graph
+  // with its kernels set, on the finalized problem's handle or one of its own (*h); throws on a refusal
+  ba_sim3 *CreateSim3Graph(const char *who, ba_handle **h, std::vector<double> *S13 = nullptr);
+  double Sim3GraphUnit(const char *who, const std::vector<double> &more) const;
   // the options' thresholds and iteration limit into a Summary (nullptr: nothing)
   static void BeginSummary(Summary *summary, const Options &options);
   // stderr warnings about weakly connected poses / points (reference

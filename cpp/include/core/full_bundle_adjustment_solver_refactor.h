@@ -84,6 +84,20 @@ class FullBundleAdjustmentSolverRefactor {
   }
   bool SolveSim3Graph(Options options, Summary *summary = nullptr, const std::vector<int> *point_anchors = nullptr,
                       std::vector<double> *scales = nullptr);
+  // (new) see FullBundleAdjustmentSolver::GetRelativeSim3Weights, ComputeSim3GraphCovariance and
+  // GateSim3LoopClosures
+  void GetRelativeSim3Weights(std::vector<double> *s, std::vector<double> *w) const {
+    impl_.GetRelativeSim3Weights(s, w);
+  }
+  bool ComputeSim3GraphCovariance(const std::vector<Pose *> &poses, const std::vector<std::pair<Pose *, Pose *>> &pairs,
+                                  std::vector<Eigen::Matrix<double, 7, 7>> *cov_poses,
+                                  std::vector<Eigen::Matrix<double, 7, 7>> *cov_cross,
+                                  std::vector<Eigen::Matrix<double, 7, 7>> *cov_rel) {
+    return impl_.ComputeSim3GraphCovariance(poses, pairs, cov_poses, cov_cross, cov_rel);
+  }
+  bool GateSim3LoopClosures(const std::vector<RelativeSim3> &candidates, double sigma_pixel, std::vector<double> *d2) {
+    return impl_.GateSim3LoopClosures(candidates, sigma_pixel, d2);
+  }
   // (new) see FullBundleAdjustmentSolver::GetRelativeWeights
   void GetRelativeWeights(std::vector<double> *s, std::vector<double> *w) const { impl_.GetRelativeWeights(s, w); }
   // (new) see FullBundleAdjustmentSolver::ComputePoseGraphCovariance and GateLoopClosures

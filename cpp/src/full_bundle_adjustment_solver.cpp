@@ -63,6 +63,11 @@ void FullBundleAdjustmentSolver::Reset() {  // :44-70
   sim3_k_.clear();
   sim3_Z_.clear();
   sim3_Omega_.clear();
+  sim3_kind_.clear();
+  sim3_scale_.clear();
+  sim3_unit_.clear();
+  sim3_report_s_.clear();
+  sim3_report_w_.clear();
   num_fixed_poses_ = num_fixed_points_ = 0;
 }
 
@@ -465,25 +470,177 @@ bool FullBundleAdjustmentSolver::SolvePoseGraph(Options options, Summary *summar
   return true;
 }
 
-void FullBundleAdjustmentSolver::AddRelativeSim3(const RelativeSim3 &f, double sigma_pixel) {
-  const auto ij = pose_index_.find(f.pose_j), ik = pose_index_.find(f.pose_k);
-  if (ij == pose_index_.end() || ik == pose_index_.end())
-    throw std::runtime_error("AddRelativeSim3: there is no pointer in the BA pose pool.");
+void FullBundleAdjustmentSolver::PackSim3(const RelativeSim3 &f, double sigma_pixel, std::vector<double> *Z,
+                                          std::vector<double> *Omega) const {
   const double *M = f.measurement;
   const double det = M[0] * (M[5] * M[10] - M[6] * M[9]) - M[1] * (M[4] * M[10] - M[6] * M[8]) +
                      M[2] * (M[4] * M[9] - M[5] * M[8]);
   const double s = std::cbrt(det);
-  sim3_j_.push_back(ij->second);
-  sim3_k_.push_back(ik->second);
   for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) sim3_Z_.push_back(M[4 * r + c] / s);
-  for (int r = 0; r < 3; ++r) sim3_Z_.push_back(M[4 * r + 3] * static_cast<double>(scaler_));
-  sim3_Z_.push_back(s);
+    for (int c = 0; c < 3; ++c) Z->push_back(M[4 * r + c] / s);
+  for (int r = 0; r < 3; ++r) Z->push_back(M[4 * r + 3] * static_cast<double>(scaler_));
+  Z->push_back(s);
   // the caller's units -> scaled units, unit pixel noise: as PackRelatives converts the 6x6
   const double w = 1.0 / (sigma_pixel * sigma_pixel * static_cast<double>(scaler_) * static_cast<double>(scaler_));
   const auto d = [this](int r) { return r < 3 ? static_cast<double>(inverse_scaler_) : 1.0; };
   for (int r = 0; r < 7; ++r)
-    for (int c = 0; c < 7; ++c) sim3_Omega_.push_back((d(r) * f.information[7 * r + c] * d(c)) / w);
+    for (int c = 0; c < 7; ++c) Omega->push_back((d(r) * f.information[7 * r + c] * d(c)) / w);
+}
+
+void FullBundleAdjustmentSolver::AddRelativeSim3(const RelativeSim3 &f, double sigma_pixel) {
+  const auto ij = pose_index_.find(f.pose_j), ik = pose_index_.find(f.pose_k);
+  if (ij == pose_index_.end() || ik == pose_index_.end())
+    throw std::runtime_error("AddRelativeSim3: there is no pointer in the BA pose pool.");
+  const double unit = sigma_pixel * static_cast<double>(scaler_);
+  int32_t kind = 0;
+  double scale = 0.0;
+  if (f.robust_kind != 0) {
+    kind = f.robust_kind;
+    if (ba_sim3_robust_check(1, &kind, &f.robust_scale) != 0)
+      throw std::runtime_error(std::string("AddRelativeSim3: ") + ba_last_error());
+    scale = f.robust_scale * unit;  // s in scaled units is s in the caller's units times unit^2
+  }
+  sim3_j_.push_back(ij->second);
+  sim3_k_.push_back(ik->second);
+  PackSim3(f, sigma_pixel, &sim3_Z_, &sim3_Omega_);
+  sim3_kind_.push_back(kind);
+  sim3_scale_.push_back(scale);
+  sim3_unit_.push_back(unit);
+}
+
+ba_sim3 *FullBundleAdjustmentSolver::CreateSim3Graph(const char *who, ba_handle **h, std::vector<double> *S13) {
+  const std::string name(who);
+  if (poses_.empty() || sim3_j_.empty())
+    throw std::runtime_error(name + ": poses (AddPose) and factors (AddRelativeSim3) must be added first");
+  const size_t n_pose = poses_.size();
+  std::vector<double> S(13 * n_pose);
+  std::vector<uint8_t> pose_fixed(n_pose, 0);
+  for (size_t p = 0; p < n_pose; ++p) {
+    Pack12(T_jw_[p], &S[13 * p]);
+    S[13 * p + 12] = 1.0;
+    pose_fixed[p] = fixed_poses_.count(static_cast<int>(p)) > 0;
+  }
+  // the graph borrows a handle for its device and stream: the finalized problem's, or one of its own
+  *h = handle_;
+  if (*h == nullptr) Check(ba_create(h, device_id_), "ba_create");
+  ba_sim3 *g = nullptr;
+  int rc = ba_sim3_create(&g, *h, static_cast<int>(n_pose), S.data(), pose_fixed.data(),
+                          static_cast<int64_t>(sim3_j_.size()), sim3_j_.data(), sim3_k_.data(), sim3_Z_.data(),
+                          sim3_Omega_.data());
+  const char *what = "ba_sim3_create";
+  if (rc == 0) {
+    rc = ba_sim3_set_robust(g, sim3_kind_.data(), sim3_scale_.data());
+    what = "ba_sim3_set_robust";
+  }
+  if (rc != 0) {
+    const std::string err = ba_last_error();
+    ba_sim3_destroy(g);
+    if (*h != handle_) ba_destroy(*h);
+    throw std::runtime_error(std::string(what) + ": " + err);
+  }
+  if (S13 != nullptr) S13->swap(S);
+  return g;
+}
+
+double FullBundleAdjustmentSolver::Sim3GraphUnit(const char *who, const std::vector<double> &more) const {
+  std::vector<double> units(sim3_unit_);
+  units.insert(units.end(), more.begin(), more.end());
+  for (double u : units)
+    if (u != units[0]) {
+      std::ostringstream m;
+      m << who << ": the factors and candidates were given with sigma_pixel = " << units[0] / scaler_ << " and "
+        << u / scaler_ << "; a covariance in the caller's units needs one value";
+      throw std::runtime_error(m.str());
+    }
+  return units.empty() ? static_cast<double>(scaler_) : units[0];
+}
+
+void FullBundleAdjustmentSolver::GetRelativeSim3Weights(std::vector<double> *s, std::vector<double> *w) const {
+  if (sim3_report_w_.empty()) throw std::runtime_error("GetRelativeSim3Weights: SolveSim3Graph has not run");
+  if (s != nullptr) *s = sim3_report_s_;
+  if (w != nullptr) *w = sim3_report_w_;
+}
+
+bool FullBundleAdjustmentSolver::ComputeSim3GraphCovariance(const std::vector<_BA_Pose *> &poses,
+                                                            const std::vector<std::pair<_BA_Pose *, _BA_Pose *>> &pairs,
+                                                            std::vector<Eigen::Matrix<double, 7, 7>> *cov_poses,
+                                                            std::vector<Eigen::Matrix<double, 7, 7>> *cov_cross,
+                                                            std::vector<Eigen::Matrix<double, 7, 7>> *cov_rel) {
+  const char *who = "ComputeSim3GraphCovariance";
+  const double unit = Sim3GraphUnit(who, {});
+  const auto index = [this](_BA_Pose *p) {
+    const auto it = pose_index_.find(p);
+    if (it == pose_index_.end()) throw std::runtime_error("There is no pointer in the BA pose pool.");
+    return static_cast<int32_t>(it->second);
+  };
+  std::vector<int32_t> ps, pj, pk;
+  for (_BA_Pose *p : poses) ps.push_back(index(p));
+  for (const auto &jk : pairs) {
+    pj.push_back(index(jk.first));
+    pk.push_back(index(jk.second));
+  }
+  if ((!ps.empty() && cov_poses == nullptr) || (!pj.empty() && cov_rel == nullptr))
+    throw std::runtime_error(std::string(who) + ": null output for a non-empty selection");
+  std::vector<double> cp(49 * ps.size()), cc(49 * pj.size()), cr(49 * pj.size());
+  int64_t dropped = 0;
+  ba_handle *h = nullptr;
+  ba_sim3 *g = CreateSim3Graph(who, &h);
+  const int rc = ba_sim3_covariance(g, static_cast<int>(ps.size()), ps.empty() ? nullptr : ps.data(),
+                                    ps.empty() ? nullptr : cp.data(), static_cast<int64_t>(pj.size()),
+                                    pj.empty() ? nullptr : pj.data(), pj.empty() ? nullptr : pk.data(),
+                                    pj.empty() || cov_cross == nullptr ? nullptr : cc.data(),
+                                    pj.empty() ? nullptr : cr.data(), &dropped);
+  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
+  ba_sim3_destroy(g);
+  if (h != handle_) ba_destroy(h);
+  if (rc != 0) throw std::runtime_error(err);
+  // scaled units -> the caller's: Sigma_user = unit^2 D Sigma_scaled D, D = diag(100 I3, I4)
+  const auto to_user = [&](const std::vector<double> &in, std::vector<Eigen::Matrix<double, 7, 7>> *out) {
+    if (out == nullptr) return;
+    out->resize(in.size() / 49);
+    for (size_t s = 0; s < out->size(); ++s)
+      for (int r = 0; r < 7; ++r)
+        for (int c = 0; c < 7; ++c) {
+          const double dr = r < 3 ? static_cast<double>(inverse_scaler_) : 1.0;
+          const double dc = c < 3 ? static_cast<double>(inverse_scaler_) : 1.0;
+          (*out)[s](r, c) = (unit * unit) * (dr * in[49 * s + 7 * r + c] * dc);
+        }
+  };
+  to_user(cp, cov_poses);
+  to_user(cc, cov_cross);
+  to_user(cr, cov_rel);
+  return dropped == 0;
+}
+
+bool FullBundleAdjustmentSolver::GateSim3LoopClosures(const std::vector<RelativeSim3> &candidates, double sigma_pixel,
+                                                      std::vector<double> *d2) {
+  const char *who = "GateSim3LoopClosures";
+  if (d2 == nullptr) throw std::runtime_error(std::string(who) + ": null output");
+  const double unit = Sim3GraphUnit(who, std::vector<double>(candidates.size(), sigma_pixel * static_cast<double>(scaler_)));
+  std::vector<int32_t> cj, ck;
+  std::vector<double> Z, Omega;
+  for (const RelativeSim3 &c : candidates) {
+    const auto ij = pose_index_.find(c.pose_j), ik = pose_index_.find(c.pose_k);
+    if (ij == pose_index_.end() || ik == pose_index_.end())
+      throw std::runtime_error("There is no pointer in the BA pose pool.");
+    cj.push_back(ij->second);
+    ck.push_back(ik->second);
+    PackSim3(c, sigma_pixel, &Z, &Omega);
+  }
+  d2->assign(candidates.size(), 0.0);
+  int64_t dropped = 0;
+  ba_handle *h = nullptr;
+  ba_sim3 *g = CreateSim3Graph(who, &h);
+  const bool any = !candidates.empty();
+  const int rc = ba_sim3_gate(g, static_cast<int64_t>(candidates.size()), any ? cj.data() : nullptr,
+                              any ? ck.data() : nullptr, any ? Z.data() : nullptr, any ? Omega.data() : nullptr,
+                              any ? d2->data() : nullptr, nullptr, nullptr, &dropped);
+  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
+  ba_sim3_destroy(g);
+  if (h != handle_) ba_destroy(h);
+  if (rc != 0) throw std::runtime_error(err);
+  for (double &v : *d2) v /= unit * unit;  // d2_user = d2_scaled / unit^2
+  return dropped == 0;
 }
 
 bool FullBundleAdjustmentSolver::SolveSim3Graph(Options options, Summary *summary,
@@ -499,36 +656,35 @@ bool FullBundleAdjustmentSolver::SolveSim3Graph(Options options, Summary *summar
     for (int a : *point_anchors)
       if (a >= static_cast<int>(n_pose)) throw std::runtime_error("SolveSim3Graph: an anchor is no registered pose");
   }
-  std::vector<double> S(13 * n_pose), S_new(13 * n_pose);
-  std::vector<uint8_t> pose_fixed(n_pose, 0);
-  for (size_t p = 0; p < n_pose; ++p) {
-    Pack12(T_jw_[p], &S[13 * p]);
-    S[13 * p + 12] = 1.0;
-    pose_fixed[p] = fixed_poses_.count(static_cast<int>(p)) > 0;
-  }
+  std::vector<double> S, S_new(13 * n_pose), rep_s(sim3_j_.size()), rep_w(sim3_j_.size());
   const ba_options o = PackOptions(options, gauss_newton_);
   std::vector<ba_iter_info> rows(static_cast<size_t>(std::max(1, o.max_num_iterations)));
   int n_iter = 0, converged = 0;
-  // the graph borrows a handle for its device and stream: the finalized problem's, or one of its own
-  ba_handle *h = handle_;
-  if (h == nullptr) Check(ba_create(&h, device_id_), "ba_create");
-  ba_sim3 *g = nullptr;
-  int rc = ba_sim3_create(&g, h, static_cast<int>(n_pose), S.data(), pose_fixed.data(),
-                          static_cast<int64_t>(sim3_j_.size()), sim3_j_.data(), sim3_k_.data(), sim3_Z_.data(),
-                          sim3_Omega_.data());
-  const char *what = "ba_sim3_create";
-  if (rc == 0) {
-    rc = ba_sim3_solve(g, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged);
-    what = "ba_sim3_solve";
-  }
+  ba_handle *h = nullptr;
+  ba_sim3 *g = CreateSim3Graph("SolveSim3Graph", &h, &S);
+  int rc = ba_sim3_solve(g, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged);
+  const char *what = "ba_sim3_solve";
   if (rc == 0) {
     rc = ba_sim3_get_poses(g, S_new.data());
     what = "ba_sim3_get_poses";
+  }
+  bool any_kernel = false;
+  for (int32_t kd : sim3_kind_) any_kernel = any_kernel || kd != 0;
+  if (rc == 0 && any_kernel) {
+    rc = ba_sim3_factor_weights(g, rep_s.data(), rep_w.data());
+    what = "ba_sim3_factor_weights";
+  } else if (rc == 0) {  // no kernel: the report of before, nothing robust is allocated or launched
+    rc = ba_sim3_factor_report(g, rep_s.data());
+    what = "ba_sim3_factor_report";
+    rep_w.assign(rep_w.size(), 1.0);
   }
   const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
   ba_sim3_destroy(g);
   if (h != handle_) ba_destroy(h);
   if (rc != 0) throw std::runtime_error(std::string(what) + ": " + err);
+  for (size_t f = 0; f < rep_s.size(); ++f) rep_s[f] /= sim3_unit_[f] * sim3_unit_[f];  // the caller's units
+  sim3_report_s_.swap(rep_s);
+  sim3_report_w_.swap(rep_w);
   // rigid poses T_jw = [R, t / s]; the anchored points follow their keyframes
   std::vector<double> T(12 * n_pose), X(3 * n_pt, 0.0);
   std::vector<uint8_t> moved(n_pt, 0);

@@ -1289,7 +1289,7 @@ int ba_pgraph_cov_info(ba_pgraph *g, int64_t out4[4]);
  * its size in the message, before any launch.  A refused call changes nothing.
  *
  * One writer per element, fixed summation order, no floating-point atomics: the same bits run
- * to run.  No robust kernels, covariance blocks or gate here: those are the SE(3) graph's. */
+ * to run.  Robust kernels, covariance blocks and the 7-DoF gate: the two sections below. */
 typedef struct ba_sim3 ba_sim3;
 int ba_sim3_create(ba_sim3 **out, ba_handle *h, int n_pose, const double *S13,
                    const uint8_t *pose_fixed, int64_t n_rel, const int32_t *rel_j,
@@ -1323,6 +1323,70 @@ int ba_sim3_check(int n_pose, const double *S13, const uint8_t *pose_fixed, int6
 void ba_sim3_exp(const double *xi7, double *S13);
 void ba_sim3_log(const double *S13, double *xi7);
 void ba_sim3_adjoint(const double *S13, double *Ad49);
+
+/* ---- robust kernels on the factors of a Sim(3) graph -----------------------
+ * The block of ba_pgraph_set_robust above, word for word, at width 7: the same kinds 0..3 with
+ * the same rho and w table, s_f = r_f^T Omega_f r_f with r of 7 components.  Chi-square is
+ * sum_f rho_f(s_f) in the accepted cost, the trial cost, ba_sim3_cost and every row field derived
+ * from them.  H and g use w_f Omega_f, w_f taken at the accepted poses; after a rejected step the
+ * records and the weights stay.  No second-order (Triggs) term.  Control, stop test,
+ * Gauss-Newton mode and rows are unchanged.
+ *
+ * kind == NULL clears every kernel; the scale of a kind-0 factor is ignored (scale may be NULL
+ * if every kind is 0).  May be called between solves any number of times without re-planning.
+ * ba_sim3_update_values keeps the kernels.  A graph with no kernel set, or with all kinds 0,
+ * launches exactly k_s3_lin and k_s3_assemble; otherwise k_s3_lin_robust and
+ * k_s3_assemble_robust run in their place.  Refused (-1, ba_last_error names the factor; nothing
+ * changes): what ba_pgraph_set_robust refuses, in its wording. */
+int ba_sim3_set_robust(ba_sim3 *g, const int32_t *kind /* F or NULL */, const double *scale /* F */);
+/* Host-only (no GPU): the validation of ba_sim3_set_robust. */
+int ba_sim3_robust_check(int64_t n_rel, const int32_t *kind, const double *scale);
+/* s_f and w_f of every factor (F doubles each, input order) at the poses the object holds, from
+ * one pass like ba_sim3_cost; a factor without a kernel reports w = 1.  Either output may be
+ * NULL.  ba_sim3_factor_report above keeps its signature and its bits. */
+int ba_sim3_factor_weights(ba_sim3 *g, double *s, double *w);
+
+/* ---- covariance blocks of a Sim(3) graph and the 7-DoF chi-square gate ------
+ * The block of ba_pgraph_covariance / ba_pgraph_gate above at width 7.
+ *
+ * System: H is exactly what ba_sim3_get_system returns: lambda = 0, the poses the object holds,
+ * w_f Omega_f where a robust kernel is set.  Sigma = H^-1 over the optimisable poses, scaled
+ * units, tangent xi = [v; omega; sigma] of S <- sim3_exp(xi) S; a fixed pose has zero blocks.
+ *   cov_pose49[s]   Sigma_jj of pose pose_sel[s] (7x7 row-major)
+ *   cov_cross49[p]  Sigma_jk of the pair (pair_j[p], pair_k[p]); may be NULL
+ *   cov_rel49[p]    Sigma_E = Sigma_jj - Sigma_jk Ad7^T - Ad7 Sigma_kj + Ad7 Sigma_kk Ad7^T, the
+ *                   covariance of E = S_j S_k^-1 with Ad7 = Ad7(E); with j fixed it is
+ *                   Ad7 Sigma_kk Ad7^T, with k fixed Sigma_jj
+ * Selections, repeats, both orientations, empty selections, dropped_pivots, batching and the
+ * treatment of the object's state (the poses, the controller, the robust kernels,
+ * ba_sim3_last_ms and the pivot count of ba_sim3_info are untouched) are those of
+ * ba_pgraph_covariance.  The kernels are csrc/ba_sim3_cov.hip: fp64 MFMA sweep, no atomics, the
+ * same bits run to run, in any selection and any batch split. */
+int ba_sim3_covariance(ba_sim3 *g, int n_pose_sel, const int32_t *pose_sel, double *cov_pose49,
+                       int64_t n_pair, const int32_t *pair_j, const int32_t *pair_k,
+                       double *cov_cross49 /* or NULL */, double *cov_rel49,
+                       int64_t *dropped_pivots);
+/* The gate.  A candidate (j, k, Z13, Omega49) has the shape of a factor: r = sim3_log(E Z^-1),
+ * P = Sigma_E + Omega_z^-1 and d2[c] = r^T P^-1 r, to be compared with a chi-square quantile of
+ * 7 degrees of freedom (24.32 at 0.999).  Only the lower triangle of Omega_z counts; no robust
+ * weight applies to a candidate.  r7 (7 per candidate) and innov49 (= P) may be NULL.  A P with
+ * a non-positive pivot yields d2 = NaN.  Refused before anything touches the GPU: what
+ * ba_pgraph_gate refuses ("candidate" for "factor"), a candidate whose scale is not finite or
+ * not positive or whose rotation is not finite (the wording of ba_sim3_check), and a candidate
+ * whose Omega_z is not positive definite (7x7 Cholesky of the mirrored lower triangle on the
+ * host; the message names the candidate). */
+int ba_sim3_gate(ba_sim3 *g, int64_t n_cand, const int32_t *cand_j, const int32_t *cand_k,
+                 const double *Z13, const double *Omega49, double *d2, double *r7 /* or NULL */,
+                 double *innov49 /* or NULL */, int64_t *dropped_pivots);
+/* Host-only (no GPU): the validation of both calls on plain arrays, as ba_pgraph_cov_check. */
+int ba_sim3_cov_check(int n_pose, const uint8_t *pose_fixed, int n_pose_sel,
+                      const int32_t *pose_sel, const double *cov_pose49, int64_t n_pair,
+                      const int32_t *pair_j, const int32_t *pair_k, const double *cov_rel49,
+                      int64_t n_cand, const int32_t *cand_j, const int32_t *cand_k,
+                      const double *Z13, const double *Omega49, const double *d2);
+/* out4 as ba_pgraph_cov_info: { columns of one batch on this graph, columns per wave (16),
+ * batches the last ba_sim3_covariance / ba_sim3_gate ran, bytes of the workspace at that width } */
+int ba_sim3_cov_info(ba_sim3 *g, int64_t out4[4]);
 
 #ifdef __cplusplus
 }
