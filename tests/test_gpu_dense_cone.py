@@ -31,15 +31,17 @@ class environment:
             os.environ.pop(k, None)
 
 
-def block_tridiagonal_spd(tiles, nb, rng):
+def block_tridiagonal_spd(tiles, nb, rng, shift=None):
     """SPD, non-zero exactly on the block tridiagonal of nb x nb tiles; the last tile is
-    five columns short (padding columns in the dense image)."""
+    five columns short (padding columns in the dense image).  shift: what is added to the
+    diagonal (default 4 nb; 0 leaves a matrix that need not be definite)."""
+    shift = 4.0 * nb if shift is None else shift
     n = tiles * nb - 5
     A = np.zeros((n, n))
     for t in range(tiles):
         a, b = t * nb, min(n, (t + 1) * nb)
         Q = rng.standard_normal((b - a, b - a))
-        A[a:b, a:b] = Q @ Q.T + 4.0 * nb * np.eye(b - a)
+        A[a:b, a:b] = Q @ Q.T + shift * np.eye(b - a)
         if t + 1 < tiles:
             c = min(n, (t + 2) * nb)
             A[b:c, a:b] = rng.standard_normal((c - b, b - a))
