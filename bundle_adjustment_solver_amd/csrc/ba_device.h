@@ -329,7 +329,9 @@ void launch_rel_offdiag(const DevProblem &d, const RelDev &r, bool direct, hipSt
 // LM over relative-pose factors alone: chi2 = sum_f r_f^T Omega_f r_f, no landmark in the
 // problem.  The controller lives on the device, as DevCtrl does for the handle path, so that
 // max_num_iterations iterations are enqueued without a host round trip; `done` is the control
-// word that dense_factor_solve and every k_pg_* kernel test first.
+// word that dense_factor_solve and every k_pg_* kernel test first.  The host side is the graph
+// driver of ba_graph.hip: it holds a PgDev and a PgCtrl per graph and reaches the launchers below
+// through the graph kind's GraphSpec (ba_graph.h), the SE(3) kind's in ba_pgraph.hip.
 struct PgCtrl {
   double lambda;
   double chi2;      // chi-square at the accepted poses
@@ -392,7 +394,9 @@ void launch_pg_control(const PgDev &p, int mode, hipStream_t s);
 // ---- Sim(3) pose graph (ba_sim3.hip, ba_sim3_*) ----
 // The 7-DoF graph has the pose graph's device record and controller: PgDev with 13 doubles per
 // pose (R, t, s), 62 per factor in val (Z 13, Omega 49 mirrored), kS3Rec per factor in rec, and
-// 7N where PgDev says 6N.  k_pg_control knows nothing of a pose's width and runs as it is.
+// 7N where PgDev says 6N.  k_pg_control knows nothing of a pose's width and runs as it is, and so
+// does the host driver (ba_graph.hip): the widths and the launchers below are the Sim(3) kind's
+// GraphSpec in ba_sim3.hip.
 constexpr int kS3Fpb = 32;   // factors per k_s3_lin workgroup
 constexpr int kS3Rec = 112;  // record of one factor: Omega r (7), Ad^T Omega r (7), Omega Ad (49), Ad^T Omega Ad (49)
 constexpr int kS3Or = 0, kS3Gk = 7, kS3OA = 14, kS3Bk = 63;
@@ -413,7 +417,8 @@ void launch_s3_assemble_robust(const PgDev &p, const PgRobust &rb, double *Hout,
 
 // ---- covariance blocks and the gate of a Sim(3) graph (ba_sim3_cov.hip) ----
 // launch_pgcov_batch at width 7: 49 doubles per block, 7 per residual, cand_val 62 doubles per
-// candidate (ba_sim3_host.h), poses 13 doubles each.  The groups are the pose graph's.
+// candidate (ba_sim3_host.h), poses 13 doubles each.  The groups are the pose graph's, and the
+// caller is the same graph_cov_run of ba_graph.hip, which fills S3CovOut from its six pointers.
 struct PgCovGroup;
 struct S3CovOut {
   double *pose49, *cross49, *rel49, *r7, *innov49, *d2;
@@ -531,7 +536,8 @@ struct PgCovOut {
 // One column batch on the factored image of the graph (p.L, Ldiag; lambda = 0): zero the workspace
 // Zw (p.npad x bw doubles, row-major, bw = 16 ng), place the identity columns, sweep, write the
 // blocks.  poses: the accepted pose buffer; cand_val: 48 doubles per candidate (ba_rel_host.h) or
-// null; trow_ptr / trow as for launch_cov_batch.  Enqueue only.
+// null; trow_ptr / trow as for launch_cov_batch.  Enqueue only.  (Called by graph_cov_run of
+// ba_graph.hip through the SE(3) kind's GraphSpec, which fills PgCovOut from its six pointers.)
 void launch_pgcov_batch(const PgDev &p, const double *Ldiag, int nb, int ncb, const double *poses,
                         const int *trow_ptr, const int *trow, const PgCovGroup *groups, int ng,
                         const double *cand_val, double *Zw, int bw, const PgCovOut &out, hipStream_t s);

@@ -19,15 +19,15 @@
 // Robust kernels (ba_pgraph_set_robust): k_pg_lin_robust and k_pg_assemble_robust
 // are second instantiations of the two bodies with sum rho(s) for chi-square and w Omega for
 // Omega; a graph whose kinds are all 0 launches the plain ones.
-// Covariance blocks and the gate (ba_pgraph_covariance / ba_pgraph_gate): the host
-// side is here (pg_cov_run: the solve's launches at lambda = 0, then column batches), the groups
-// and the validation in ba_pgraph_host.h, the kernels in ba_pgraph_cov.hip.
-#include <cstddef>
-#include <cstring>
+// The host side is the graph driver of ba_graph.hip, which this graph shares with the Sim(3) one
+// (ba_sim3.hip): below the kernels this file has the driver's description of an SE(3) graph
+// (kPgSpec: the widths, these launchers) and the ba_pgraph_* entry points, which validate and call
+// the driver.  Covariance blocks and the gate (ba_pgraph_covariance / ba_pgraph_gate; DESIGN.md
+// §6m): the driver's graph_cov_run (the solve's launches at lambda = 0, then column batches), the
+// groups and the validation in ba_pgraph_host.h, the kernels in ba_pgraph_cov.hip.
 #include <type_traits>
 
-#include "ba_handle.h"
-#include "ba_pgraph_host.h"
+#include "ba_graph.h"
 #include "ba_rel_fn.h"
 #include "ba_robust_fn.h"
 
@@ -331,329 +331,38 @@ void launch_pg_control(const PgDev &p, int mode, hipStream_t s) {
 }  // namespace ba
 
 // ---- host side ------------------------------------------------------------------------------
+// The driver is ba_graph.hip; here are the SE(3) graph's spec and its entry points, which check
+// their pointers, validate the caller's arrays and call the driver.
 using ba::fail;
-using ba::Mem;
 
-struct ba_pgraph {
-  ba_handle *h = nullptr;
-  int n_pose = 0;
-  int64_t F = 0;
-  std::vector<uint8_t> fixed;
-  std::vector<int32_t> rel_j, rel_k;
-  std::vector<double> Z, Om;  // the factor values as given (ba_pgraph_update_values replaces one or both)
-  ba::PgraphLists lists;
-  ba::DenseSchedule sched;
-  ba::DenseDev dd;
-  ba::PgDev d{};
-  ba::PgCtrl hc{};
-  double *Ldiag = nullptr, *val = nullptr;
-  // robust kernels: the host copy as given, the device arrays (allocated by the first
-  // ba_pgraph_set_robust or ba_pgraph_factor_report), and whether any kind is not 0
-  std::vector<int32_t> rkind;
-  std::vector<double> rscale;
-  int32_t *d_rkind = nullptr;
-  double *d_rscale = nullptr, *d_rep_s = nullptr, *d_rep_w = nullptr;
-  ba::PgRobust rb{};
-  bool robust = false;
-  int *zt_I = nullptr, *zt_J = nullptr, *col_x = nullptr;
-  int n_zt = 0, nb = 0, ncb = 0;
-  size_t image_bytes = 0;
-  int64_t bad_pivots = 0;
-  double last_ms = 0.0;
-  std::vector<int> pose_col_h;  // per optimisable pose: its first column of the image
-  int cov_batches = 0;          // column batches of the last ba_pgraph_covariance / ba_pgraph_gate
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  std::vector<void *> allocs;
-};
+struct ba_pgraph : ba::GraphHost {};
 
 namespace {
 
-// what was allocated on the handle since `mark` belongs to the graph from here on
-void adopt_allocs(ba_pgraph *g, size_t mark) {
-  ba_handle *h = g->h;
-  g->allocs.insert(g->allocs.end(), h->allocs.begin() + mark, h->allocs.end());
-  h->allocs.resize(mark);
+void pg_cov_batch(const ba::PgDev &p, const double *Ldiag, int nb, int ncb, const double *poses, const int *trow_ptr,
+                  const int *trow, const ba::PgCovGroup *groups, int ng, const double *cand_val, double *Zw, int bw,
+                  const ba::GraphCovOut &o, hipStream_t s) {
+  const ba::PgCovOut out{o.pose, o.cross, o.rel, o.r, o.innov, o.d2};
+  ba::launch_pgcov_batch(p, Ldiag, nb, ncb, poses, trow_ptr, trow, groups, ng, cand_val, Zw, bw, out, s);
 }
 
-void free_graph(ba_pgraph *g) {
-  for (void *p : g->allocs) (void)hipFree(p);
-  if (g->e0) (void)hipEventDestroy(g->e0);
-  if (g->e1) (void)hipEventDestroy(g->e1);
-  delete g;
-}
-
-int push_ctrl(ba_pgraph *g) {
-  HIP_TRY(hipMemcpyAsync(g->d.ctrl, &g->hc, sizeof(ba::PgCtrl), hipMemcpyHostToDevice, g->h->stream));
-  return 0;
-}
-int pull_ctrl(ba_pgraph *g) {
-  HIP_TRY(hipMemcpyAsync(&g->hc, g->d.ctrl, sizeof(ba::PgCtrl), hipMemcpyDeviceToHost, g->h->stream));
-  HIP_TRY(hipStreamSynchronize(g->h->stream));
-  return 0;
-}
-const int *done_flag(const ba_pgraph *g) {
-  return (const int *)((const char *)g->d.ctrl + offsetof(ba::PgCtrl, done));
-}
-
-// the device side of a validated graph; on failure the caller frees what `g` holds
-int build_device(ba_pgraph *g, const double *T_jw12) {
-  ba_handle *h = g->h;
-  const ba::PgraphLists &l = g->lists;
-  const ba::DenseKnobs &knobs = h->knobs.dense;
-  ba::PgDev &d = g->d;
-  const int N = l.N;
-  // both tile orders, as ba_finalize builds them for the reduced camera system
-  ba::DenseSchedule cand[2];
-  const int orders[2] = {32, 64};
-  for (int k = 0; k < 2; ++k) {
-    int ncb_k = 0;
-    std::vector<uint8_t> adj;
-    ba::pgraph_tile_adjacency(l, ba::dense_poses_per_tile(orders[k]), &ncb_k, &adj);
-    if (knobs.full) std::fill(adj.begin(), adj.end(), 1);
-    ba::build_dense_schedule(ncb_k, adj, knobs.natural, orders[k], cand[k], knobs.order);
-  }
-  g->sched = cand[ba::dense_pick_tile_order(cand[0], cand[1], knobs.nb)];
-  const ba::DenseSchedule &sc = g->sched;
-  const int nb = sc.nb, ppt = ba::dense_poses_per_tile(nb), ncb = sc.ncb;
-  g->nb = nb;
-  g->ncb = ncb;
-  d.n_pose = g->n_pose;
-  d.N = N;
-  d.F = (int)g->F;
-  d.nblk = (int)(l.blk.size() / 2);
-  d.n_part = (int)((g->F + ba::kPgFpb - 1) / ba::kPgFpb);
-  d.n_tpart = (N + 255) / 256;
-  d.npad = ncb * nb;
-  d.ld = d.npad + nb;
-  d.log_cap = 4096;
-  // the image first: nothing is launched, and nothing else allocated, if it does not fit
-  g->image_bytes = (size_t)d.npad * d.ld * sizeof(double);
-  {
-    hipError_t e = hipMalloc((void **)&d.L, g->image_bytes);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      d.L = nullptr;
-      return fail("ba_pgraph_create: cannot allocate the dense image of " + std::to_string(d.npad) + " x " +
-                  std::to_string(d.ld) + " doubles (" + std::to_string(g->image_bytes) + " bytes): " +
-                  hipGetErrorString(e));
-    }
-    g->allocs.push_back((void *)d.L);
-  }
-  std::vector<int> pose_col((size_t)N, 0), col_x((size_t)d.npad, -1);
-  for (int j = 0; j < N; ++j) {
-    const int c0 = sc.pos_of_tile[j / ppt] * nb + 6 * (j % ppt);
-    pose_col[j] = c0;
-    for (int r = 0; r < 6; ++r) col_x[c0 + r] = 6 * j + r;
-  }
-  // tiles (re)initialised per iteration: factor pattern + diagonal + rhs row
-  std::vector<int> ztI, ztJ;
-  for (int p = 0; p < ncb; ++p) {
-    ztI.push_back(p);
-    ztJ.push_back(p);
-    for (int q = sc.row_ptr[p]; q < sc.row_ptr[p + 1]; ++q) {
-      ztI.push_back(sc.rows[q]);  // includes the rhs row block (== ncb)
-      ztJ.push_back(p);
-    }
-  }
-  g->n_zt = (int)ztI.size();
-  g->pose_col_h = pose_col;
-  std::vector<double> val;
-  ba::relative_pack_values(g->F, g->Z.data(), g->Om.data(), &val);
-  constexpr Mem R = Mem::Resident;
-  static_assert(sizeof(int4) == 16 && sizeof(int2) == 8, "layout");
-  int4 *jk = nullptr;
-  int2 *blk = nullptr;
-  int32_t *pptr = nullptr, *plist = nullptr, *bptr = nullptr, *blist = nullptr, *opt_pose = nullptr;
-  int *pc = nullptr;
-  const size_t n6 = (size_t)6 * N;
-  if (ba::upload_dense_schedule(h, sc, col_x, g->dd) ||
-      h->dalloc(R, &g->Ldiag, (size_t)ncb * ba::dense_ws_per_block(nb)) || h->upload(R, &pc, pose_col) ||
-      h->upload(R, &g->zt_I, ztI) || h->upload(R, &g->zt_J, ztJ) ||
-      h->upload(R, &d.poses[0], T_jw12, (size_t)g->n_pose * 12) ||
-      h->upload(R, &d.poses[1], T_jw12, (size_t)g->n_pose * 12) || h->upload(R, &jk, l.jk.data(), (size_t)g->F) ||
-      h->upload(R, &g->val, val) || h->upload(R, &pptr, l.pptr) || h->upload(R, &plist, l.plist) ||
-      h->upload(R, &blk, l.blk.data(), l.blk.size() / 2) || h->upload(R, &bptr, l.bptr) ||
-      h->upload(R, &blist, l.blist) || h->upload(R, &opt_pose, l.opt_pose) ||
-      h->dalloc(R, &d.rec, (size_t)g->F * ba::kPgRec) || h->dalloc(R, &d.dH, n6) || h->dalloc(R, &d.g, n6) ||
-      h->dalloc(R, &d.x, n6 + 64) || h->dalloc(R, &d.part[0], (size_t)d.n_part) ||
-      h->dalloc(R, &d.part[1], (size_t)d.n_part) || h->dalloc(R, &d.tpart, (size_t)2 * d.n_tpart) ||
-      h->dalloc(R, &d.ctrl, (size_t)1) || h->dalloc(R, &d.log, (size_t)d.log_cap))
-    return -1;
-  g->col_x = g->dd.col_x;
-  d.jk = jk;
-  d.val = g->val;
-  d.pptr = pptr;
-  d.plist = plist;
-  d.blk = blk;
-  d.bptr = bptr;
-  d.blist = blist;
-  d.opt_pose = opt_pose;
-  d.pose_col = pc;
-  HIP_TRY(hipMemset(d.L, 0, g->image_bytes));
-  HIP_TRY(hipMemset(d.rec, 0, (size_t)g->F * ba::kPgRec * sizeof(double)));
-  HIP_TRY(hipMemset(d.dH, 0, n6 * sizeof(double)));
-  HIP_TRY(hipMemset(d.g, 0, n6 * sizeof(double)));
-  HIP_TRY(hipMemset(d.x, 0, (n6 + 64) * sizeof(double)));
-  HIP_TRY(hipMemset(d.part[0], 0, (size_t)d.n_part * sizeof(double)));
-  HIP_TRY(hipMemset(d.part[1], 0, (size_t)d.n_part * sizeof(double)));
-  HIP_TRY(hipMemset(d.tpart, 0, (size_t)2 * d.n_tpart * sizeof(double)));
-  HIP_TRY(hipMemset(d.ctrl, 0, sizeof(ba::PgCtrl)));
-  HIP_TRY(hipEventCreate(&g->e0));
-  HIP_TRY(hipEventCreate(&g->e1));
-  return 0;
-}
-
-// the controller for a pass outside the LM loop: the accepted buffer stays
-int begin_pass(ba_pgraph *g) {
-  g->hc.done = 0;
-  g->hc.relin = 1;
-  g->hc.lambda = 0.0;
-  return push_ctrl(g);
-}
-
-// the device arrays of the robust kernels: kinds 0 and the weights' arrays, once per graph
-int ensure_robust_arrays(ba_pgraph *g) {
-  if (g->d_rkind) return 0;
-  ba_handle *h = g->h;
-  constexpr Mem R = Mem::Resident;
-  const size_t F = (size_t)g->F, mark = h->allocs.size();
-  const int rc = h->dalloc(R, &g->d_rkind, F) || h->dalloc(R, &g->d_rscale, F) || h->dalloc(R, &g->rb.s, F) ||
-                 h->dalloc(R, &g->rb.w, F) || h->dalloc(R, &g->d_rep_s, F) || h->dalloc(R, &g->d_rep_w, F);
-  adopt_allocs(g, mark);
-  if (rc) {
-    g->d_rkind = nullptr;  // what was allocated goes with the graph
-    return -1;
-  }
-  g->rb.kind = g->d_rkind;
-  g->rb.scale = g->d_rscale;
-  HIP_TRY(hipMemset(g->d_rkind, 0, F * sizeof(int32_t)));
-  HIP_TRY(hipMemset(g->d_rscale, 0, F * sizeof(double)));
-  return 0;
-}
-
-// the linearisation / cost pass and the assembly of the graph: the robust instantiations only
-// where a kernel is set
-void pg_lin(const ba_pgraph *g, int cost_only, hipStream_t s) {
-  if (g->robust)
-    ba::launch_pg_lin_robust(g->d, g->rb, cost_only, s);
-  else
-    ba::launch_pg_lin(g->d, cost_only, s);
-}
-void pg_assemble(const ba_pgraph *g, double *Hout, double *gout, hipStream_t s) {
-  if (g->robust)
-    ba::launch_pg_assemble_robust(g->d, g->rb, Hout, gout, s);
-  else
-    ba::launch_pg_assemble(g->d, Hout, gout, s);
-}
-
-
-template <class T>
-int download(std::vector<T> &out, const T *dev, size_t n, hipStream_t s) {
-  out.resize(n);
-  if (n) HIP_TRY(hipMemcpyAsync(out.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
-  return 0;
-}
-
-// The host arrays of one covariance or gate call (validated): entry_kind = kPgCovPair with
-// Z12 = Omega36 = nullptr, or kPgCovCand.  Outputs that are null are not produced.
-struct PgCovCall {
-  int n_pose_sel = 0;
-  const int32_t *pose_sel = nullptr;
-  double *cov_pose36 = nullptr;
-  int64_t n_entry = 0;
-  int entry_kind = ba::kPgCovPair;
-  const int32_t *entry_j = nullptr, *entry_k = nullptr;
-  const double *Z12 = nullptr, *Omega36 = nullptr;
-  double *cov_cross36 = nullptr, *cov_rel36 = nullptr, *d2 = nullptr, *r6 = nullptr, *innov36 = nullptr;
+const ba::GraphSpec kPgSpec = {
+    "ba_pgraph",
+    6,   // W
+    12,  // pose_doubles: T_jw and Z as [R row-major, t]
+    ba::kRelVal,
+    ba::kPgRec,
+    ba::kPgFpb,
+    ba::dense_poses_per_tile,
+    ba::relative_pack_values,
+    ba::pgraph_validate_values,
+    ba::launch_pg_lin,
+    ba::launch_pg_lin_robust,
+    ba::launch_pg_assemble,
+    ba::launch_pg_assemble_robust,
+    ba::launch_pg_trial,
+    pg_cov_batch,
 };
-
-// Factorise H at lambda = 0 at the accepted poses with the solve's launches, sweep the groups
-// in column batches, copy the blocks out.  The controller, the solve's count of dropped pivots
-// and last_ms are as before on return; the workspace and the lists are freed on every path.
-int pg_cov_run(ba_pgraph *g, const char *what, const PgCovCall &c, int64_t *dropped_pivots) {
-  ba_handle *h = g->h;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  const ba::PgDev &d = g->d;
-  const ba::DenseSchedule &sc = g->sched;
-  std::vector<ba::PgCovGroup> groups;
-  std::vector<int32_t> slot_of_opt;
-  int n_pose_rows = 0;
-  ba::pgraph_cov_groups(g->lists, g->pose_col_h, g->nb, c.n_pose_sel, c.pose_sel, c.n_entry, c.entry_j, c.entry_k,
-                        c.entry_kind, &groups, &slot_of_opt, &n_pose_rows);
-  std::vector<int> trow_ptr, trow;
-  ba::pgraph_cov_tile_rows(g->ncb, sc.row_ptr, sc.rows, &trow_ptr, &trow);
-  // ---- the factor of H at lambda = 0, whole in the image (no level goes to k_chol_tail)
-  HIP_TRY(hipStreamSynchronize(s));
-  const ba::PgCtrl keep = g->hc;
-  int bad_keep = 0, bad_now = 0;
-  HIP_TRY(hipMemcpy(&bad_keep, g->dd.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemsetAsync(g->dd.bad_pivots, 0, sizeof(int), s));
-  if (begin_pass(g)) return -1;
-  const int *done = done_flag(g);
-  pg_lin(g, 0, s);
-  ba::launch_dense_init(d.L, d.ld, g->col_x, g->zt_I, g->zt_J, g->n_zt, g->nb, done, s);
-  pg_assemble(g, nullptr, nullptr, s);
-  ba::dense_factor_solve(d.L, d.npad, d.ld, g->Ldiag, d.x, done, sc, g->dd,
-                         ba::dense_launch_plan_no_tail(sc, h->knobs.dense, g->dd.flow_ok, g->dd.plan[1],
-                                                       h->knobs.cone.want),
-                         s);
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipMemcpy(&bad_now, g->dd.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(g->dd.bad_pivots, &bad_keep, sizeof(int), hipMemcpyHostToDevice));
-  g->hc = keep;  // the controller as it was
-  if (push_ctrl(g)) return -1;
-  HIP_TRY(hipStreamSynchronize(s));
-  if (bad_now >= ba::kFlowTimeout) return fail(std::string(what) + ": a dataflow hand-off of the factorisation timed out");
-  // ---- the batches; everything below is freed again on every return
-  ba::ScratchAllocs scratch(h);
-  constexpr Mem R = Mem::Resident;
-  const bool cand = c.entry_kind == ba::kPgCovCand;
-  const size_t ne = (size_t)c.n_entry;
-  const int gpb = ba::cov_batch_cols(d.npad, h->knobs.run) / ba::kCovGroupCols;  // groups per batch
-  const int bw = (int)std::min<size_t>(gpb, std::max<size_t>(1, groups.size())) * ba::kCovGroupCols;
-  int *d_trow_ptr = nullptr, *d_trow = nullptr;
-  ba::PgCovGroup *d_groups = nullptr;
-  double *Zw = nullptr, *d_val = nullptr;
-  ba::PgCovOut out{};
-  g->cov_batches = 0;
-  if (!groups.empty()) {
-    std::vector<double> val;
-    if (cand) ba::relative_pack_values(c.n_entry, c.Z12, c.Omega36, &val);
-    if (h->upload(R, &d_trow_ptr, trow_ptr) || h->upload(R, &d_trow, trow) || h->upload(R, &d_groups, groups) ||
-        h->dalloc(R, &Zw, (size_t)d.npad * bw) || h->dalloc(R, &out.pose36, (size_t)n_pose_rows * 36) ||
-        h->dalloc(R, &out.rel36, ne * 36) || (c.cov_cross36 && h->dalloc(R, &out.cross36, ne * 36)) ||
-        (cand && (h->upload(R, &d_val, val) || h->dalloc(R, &out.d2, ne))) ||
-        (cand && c.r6 && h->dalloc(R, &out.r6, ne * 6)) || (cand && c.innov36 && h->dalloc(R, &out.innov36, ne * 36)))
-      return -1;
-    for (size_t g0 = 0; g0 < groups.size(); g0 += gpb) {  // fixed batch order
-      const int ng = (int)std::min<size_t>(gpb, groups.size() - g0);
-      ba::launch_pgcov_batch(d, g->Ldiag, g->nb, g->ncb, d.poses[keep.cur], d_trow_ptr, d_trow, d_groups + g0, ng, d_val,
-                             Zw, bw, out, s);
-      ++g->cov_batches;
-    }
-  }
-  std::vector<double> hp, hrel, hcross, hd2, hr, hP;
-  if (download(hp, out.pose36, (size_t)n_pose_rows * 36, s) || download(hrel, out.rel36, out.rel36 ? ne * 36 : 0, s) ||
-      download(hcross, out.cross36, out.cross36 ? ne * 36 : 0, s) || download(hd2, out.d2, out.d2 ? ne : 0, s) ||
-      download(hr, out.r6, out.r6 ? ne * 6 : 0, s) || download(hP, out.innov36, out.innov36 ? ne * 36 : 0, s))
-    return -1;
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipGetLastError());
-  for (int q = 0; q < c.n_pose_sel; ++q)
-    std::memcpy(c.cov_pose36 + (size_t)q * 36, &hp[(size_t)slot_of_opt[g->lists.opt_of_pose[c.pose_sel[q]]] * 36],
-                36 * sizeof(double));
-  auto give = [](double *dst, const std::vector<double> &src) {
-    if (dst && !src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(double));
-  };
-  if (!cand) give(c.cov_rel36, hrel);
-  give(c.cov_cross36, hcross);
-  give(c.d2, hd2);
-  give(c.r6, hr);
-  give(c.innov36, hP);
-  if (dropped_pivots) *dropped_pivots = bad_now;
-  return 0;
-}
 
 }  // namespace
 
@@ -674,25 +383,9 @@ int ba_pgraph_create(ba_pgraph **out, ba_handle *h, int n_pose, const double *T_
   *out = nullptr;
   if (ba_pgraph_check(n_pose, T_jw12, pose_fixed, n_rel, rel_j, rel_k, Z12, Omega36)) return -1;
   if (!h) return fail("ba_pgraph_create: null handle");
-  HIP_TRY(hipSetDevice(h->device));
   ba_pgraph *g = new ba_pgraph();
-  g->h = h;
-  g->n_pose = n_pose;
-  g->F = n_rel;
-  if (pose_fixed)
-    g->fixed.assign(pose_fixed, pose_fixed + n_pose);
-  else
-    g->fixed.assign((size_t)n_pose, 0);
-  g->rel_j.assign(rel_j, rel_j + n_rel);
-  g->rel_k.assign(rel_k, rel_k + n_rel);
-  g->Z.assign(Z12, Z12 + 12 * (size_t)n_rel);
-  g->Om.assign(Omega36, Omega36 + 36 * (size_t)n_rel);
-  ba::pgraph_build_lists(n_pose, g->fixed.data(), n_rel, rel_j, rel_k, &g->lists);
-  const size_t mark = h->allocs.size();
-  const int rc = build_device(g, T_jw12);
-  adopt_allocs(g, mark);
-  if (rc) {
-    free_graph(g);
+  if (ba::graph_create(kPgSpec, g, h, n_pose, T_jw12, pose_fixed, n_rel, rel_j, rel_k, Z12, Omega36)) {
+    delete g;
     return -1;
   }
   *out = g;
@@ -701,40 +394,13 @@ int ba_pgraph_create(ba_pgraph **out, ba_handle *h, int n_pose, const double *T_
 
 void ba_pgraph_destroy(ba_pgraph *g) {
   if (!g) return;
-  (void)hipSetDevice(g->h->device);
-  (void)hipStreamSynchronize(g->h->stream);
-  free_graph(g);
+  ba::graph_destroy(g);
+  delete g;
 }
 
 int ba_pgraph_update_values(ba_pgraph *g, const double *T_jw12, const double *Z12, const double *Omega36) {
   if (!g) return fail("ba_pgraph_update_values: null graph");
-  ba_handle *h = g->h;
-  std::string err;
-  if (T_jw12)
-    for (int64_t e = 0; e < (int64_t)g->n_pose * 12; ++e)
-      if (!std::isfinite(T_jw12[e]))
-        return fail("ba_pgraph_update_values: T_jw is not finite (pose " + std::to_string(e / 12) + ")");
-  if (Z12 || Omega36) {
-    const double *Zn = Z12 ? Z12 : g->Z.data(), *On = Omega36 ? Omega36 : g->Om.data();
-    if (ba::relative_validate_host(ba::kRelValues, g->n_pose, g->fixed.data(), g->F, nullptr, nullptr, Zn, On, &err))
-      return fail("ba_pgraph_update_values: " + err);
-  }
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (Z12 || Omega36) {
-    if (Z12) g->Z.assign(Z12, Z12 + 12 * (size_t)g->F);
-    if (Omega36) g->Om.assign(Omega36, Omega36 + 36 * (size_t)g->F);
-    std::vector<double> val;
-    ba::relative_pack_values(g->F, g->Z.data(), g->Om.data(), &val);
-    HIP_TRY(hipMemcpy(g->val, val.data(), val.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  if (T_jw12) {
-    const size_t bytes = (size_t)g->n_pose * 12 * sizeof(double);
-    HIP_TRY(hipMemcpy(g->d.poses[0], T_jw12, bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(g->d.poses[1], T_jw12, bytes, hipMemcpyHostToDevice));
-    g->hc.cur = 0;
-  }
-  return 0;
+  return ba::graph_update_values(kPgSpec, g, T_jw12, Z12, Omega36);
 }
 
 int ba_pgraph_robust_check(int64_t n_rel, const int32_t *kind, const double *scale) {
@@ -746,165 +412,38 @@ int ba_pgraph_robust_check(int64_t n_rel, const int32_t *kind, const double *sca
 int ba_pgraph_set_robust(ba_pgraph *g, const int32_t *kind, const double *scale) {
   if (!g) return fail("ba_pgraph_set_robust: null graph");
   if (ba_pgraph_robust_check(g->F, kind, scale)) return -1;
-  const size_t F = (size_t)g->F;
-  std::vector<int32_t> k(F, 0);
-  std::vector<double> c(F, 0.0);
-  bool any = false;
-  for (size_t f = 0; kind && f < F; ++f)
-    if (kind[f] != 0) {
-      k[f] = kind[f];
-      c[f] = scale[f];
-      any = true;
-    }
-  if (!any && !g->d_rkind) {  // never robust, and stays so: nothing to allocate
-    g->robust = false;
-    return 0;
-  }
-  ba_handle *h = g->h;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (ensure_robust_arrays(g)) return -1;
-  HIP_TRY(hipMemcpy(g->d_rkind, k.data(), F * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(g->d_rscale, c.data(), F * sizeof(double), hipMemcpyHostToDevice));
-  g->rkind.swap(k);
-  g->rscale.swap(c);
-  g->robust = any;
-  return 0;
+  return ba::graph_set_robust(g, kind, scale);
 }
 
 int ba_pgraph_factor_report(ba_pgraph *g, double *s, double *w) {
   if (!g) return fail("ba_pgraph_factor_report: null graph");
-  ba_handle *h = g->h;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (ensure_robust_arrays(g)) return -1;
-  if (begin_pass(g)) return -1;
-  // one cost-only pass at the accepted poses; the report has arrays of its own, so that rb.s and
-  // rb.w stay those of the records
-  ba::PgRobust rep = g->rb;
-  rep.s = g->d_rep_s;
-  rep.w = g->d_rep_w;
-  ba::launch_pg_lin_robust(g->d, rep, 3, h->stream);
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipGetLastError());
-  const size_t bytes = (size_t)g->F * sizeof(double);
-  if (s) HIP_TRY(hipMemcpy(s, g->d_rep_s, bytes, hipMemcpyDeviceToHost));
-  if (w) HIP_TRY(hipMemcpy(w, g->d_rep_w, bytes, hipMemcpyDeviceToHost));
-  return 0;
+  return ba::graph_factor_weights(kPgSpec, g, s, w);
 }
 
-int ba_pgraph_solve(ba_pgraph *g, const ba_options *opt,ba_iter_info *rows, int cap, int *n_iter, int *converged) {
+int ba_pgraph_solve(ba_pgraph *g, const ba_options *opt, ba_iter_info *rows, int cap, int *n_iter, int *converged) {
   if (!g || !opt) return fail("ba_pgraph_solve: bad argument");
   if (cap < 0 || (cap > 0 && !rows)) return fail("ba_pgraph_solve: rows is NULL for cap > 0");
-  ba_handle *h = g->h;
-  if (n_iter) *n_iter = 0;
-  if (converged) *converged = 1;
-  if (opt->max_num_iterations <= 0) return 0;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  const ba::PgDev &d = g->d;
-  ba::PgCtrl &c = g->hc;
-  const int cur = c.cur;
-  std::memset(&c, 0, sizeof(c));
-  c.cur = cur;
-  c.lambda = (double)opt->initial_lambda;
-  c.thr_step = (double)opt->threshold_step_size;
-  c.thr_cost = (double)opt->threshold_cost_change;
-  c.dec_ratio = (double)opt->decrease_ratio_lambda;
-  c.inc_ratio = (double)opt->increase_ratio_lambda;
-  c.max_iter = opt->max_num_iterations;
-  c.gn = opt->gauss_newton ? 1 : 0;
-  c.relin = 1;
-  if (push_ctrl(g)) return -1;
-  HIP_TRY(hipMemsetAsync(g->dd.bad_pivots, 0, sizeof(int), s));
-  ba::g_ktimer = h->timing ? &h->kt : nullptr;
-  const int *done = done_flag(g);
-  HIP_TRY(hipEventRecord(g->e0, s));
-  for (int it = 0; it < opt->max_num_iterations; ++it) {
-    pg_lin(g, 0, s);
-    ba::launch_dense_init(d.L, d.ld, g->col_x, g->zt_I, g->zt_J, g->n_zt, g->nb, done, s);
-    pg_assemble(g, nullptr, nullptr, s);
-    ba::dense_factor_solve(d.L, d.npad, d.ld, g->Ldiag, d.x, done, g->sched, g->dd, g->dd.plan[g->dd.flow_ok], s);
-    ba::launch_pg_trial(d, s);
-    pg_lin(g, 1, s);
-    ba::launch_pg_control(d, 0, s);
-  }
-  HIP_TRY(hipEventRecord(g->e1, s));
-  ba::g_ktimer = nullptr;
-  if (pull_ctrl(g)) return -1;
-  if (h->timing) h->kt.collect();
-  HIP_TRY(hipGetLastError());
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, g->e0, g->e1);
-  g->last_ms = ms;
-  int bad = 0;
-  HIP_TRY(hipMemcpy(&bad, g->dd.bad_pivots, sizeof(int), hipMemcpyDeviceToHost));
-  if (bad >= ba::kFlowTimeout) return fail("ba_pgraph_solve: a dataflow hand-off timed out");
-  g->bad_pivots = bad;
-  static_assert(sizeof(ba::DevIterRec) == sizeof(ba_iter_info), "row layout");
-  const int n = std::min(std::min(c.iter, cap), d.log_cap);
-  if (n > 0) HIP_TRY(hipMemcpy(rows, d.log, (size_t)n * sizeof(ba_iter_info), hipMemcpyDeviceToHost));
-  if (n_iter) *n_iter = c.iter;
-  if (converged) *converged = c.converged;
-  return 0;
+  return ba::graph_solve(kPgSpec, g, opt, rows, cap, n_iter, converged);
 }
 
 int ba_pgraph_get_poses(ba_pgraph *g, double *T_jw12) {
   if (!g || !T_jw12) return fail("ba_pgraph_get_poses: bad argument");
-  HIP_TRY(hipSetDevice(g->h->device));
-  HIP_TRY(hipStreamSynchronize(g->h->stream));
-  HIP_TRY(hipMemcpy(T_jw12, g->d.poses[g->hc.cur], (size_t)g->n_pose * 12 * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
+  return ba::graph_get_poses(kPgSpec, g, T_jw12);
 }
 
 int ba_pgraph_cost(ba_pgraph *g, double *chi2) {
   if (!g || !chi2) return fail("ba_pgraph_cost: bad argument");
-  HIP_TRY(hipSetDevice(g->h->device));
-  if (begin_pass(g)) return -1;
-  pg_lin(g, 2, g->h->stream);
-  ba::launch_pg_control(g->d, 1, g->h->stream);
-  if (pull_ctrl(g)) return -1;
-  HIP_TRY(hipGetLastError());
-  *chi2 = g->hc.aux;
-  return 0;
+  return ba::graph_cost(kPgSpec, g, chi2);
 }
 
 int ba_pgraph_get_system(ba_pgraph *g, double *H, double *g6N) {
   if (!g) return fail("ba_pgraph_get_system: null graph");
-  ba_handle *h = g->h;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t n6 = (size_t)6 * g->d.N;
-  double *dH = nullptr, *dg = nullptr;
-  HIP_TRY(hipMalloc((void **)&dH, n6 * n6 * sizeof(double)));
-  if (hipMalloc((void **)&dg, n6 * sizeof(double)) != hipSuccess) {
-    (void)hipFree(dH);
-    return fail("ba_pgraph_get_system: hipMalloc");
-  }
-  int rc = 0;
-  if (hipMemsetAsync(dH, 0, n6 * n6 * sizeof(double), h->stream) != hipSuccess || begin_pass(g)) rc = -1;
-  if (!rc) {
-    pg_lin(g, 0, h->stream);
-    pg_assemble(g, dH, dg, h->stream);
-    if (hipStreamSynchronize(h->stream) != hipSuccess || hipGetLastError() != hipSuccess ||
-        (H && hipMemcpy(H, dH, n6 * n6 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
-        (g6N && hipMemcpy(g6N, dg, n6 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
-      rc = fail("ba_pgraph_get_system: device error");
-  }
-  (void)hipFree(dH);
-  (void)hipFree(dg);
-  return rc;
+  return ba::graph_get_system(kPgSpec, g, H, g6N);
 }
 
 int ba_pgraph_info(ba_pgraph *g, int64_t out8[8]) {
   if (!g || !out8) return fail("ba_pgraph_info: bad argument");
-  out8[0] = g->d.N;
-  out8[1] = g->F;
-  out8[2] = g->d.nblk;
-  out8[3] = g->nb;
-  out8[4] = g->ncb;
-  out8[5] = g->sched.nlev;
-  out8[6] = (int64_t)g->image_bytes;
-  out8[7] = g->bad_pivots;
+  ba::graph_info(g, out8);
   return 0;
 }
 
@@ -926,16 +465,8 @@ int ba_pgraph_covariance(ba_pgraph *g, int n_pose_sel, const int32_t *pose_sel, 
   if (ba_pgraph_cov_check(g->n_pose, g->fixed.data(), n_pose_sel, pose_sel, cov_pose36, n_pair, pair_j, pair_k,
                           cov_rel36, 0, nullptr, nullptr, nullptr, nullptr, nullptr))
     return -1;
-  PgCovCall c;
-  c.n_pose_sel = n_pose_sel;
-  c.pose_sel = pose_sel;
-  c.cov_pose36 = cov_pose36;
-  c.n_entry = n_pair;
-  c.entry_j = pair_j;
-  c.entry_k = pair_k;
-  c.cov_cross36 = n_pair > 0 ? cov_cross36 : nullptr;
-  c.cov_rel36 = cov_rel36;
-  return pg_cov_run(g, "ba_pgraph_covariance", c, dropped_pivots);
+  return ba::graph_covariance(kPgSpec, g, n_pose_sel, pose_sel, cov_pose36, n_pair, pair_j, pair_k, cov_cross36,
+                              cov_rel36, dropped_pivots);
 }
 
 int ba_pgraph_gate(ba_pgraph *g, int64_t n_cand, const int32_t *cand_j, const int32_t *cand_k, const double *Z12,
@@ -944,32 +475,18 @@ int ba_pgraph_gate(ba_pgraph *g, int64_t n_cand, const int32_t *cand_j, const in
   if (ba_pgraph_cov_check(g->n_pose, g->fixed.data(), 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, n_cand,
                           cand_j, cand_k, Z12, Omega36, d2))
     return -1;
-  PgCovCall c;
-  c.n_entry = n_cand;
-  c.entry_kind = ba::kPgCovCand;
-  c.entry_j = cand_j;
-  c.entry_k = cand_k;
-  c.Z12 = Z12;
-  c.Omega36 = Omega36;
-  c.d2 = d2;
-  c.r6 = n_cand > 0 ? r6 : nullptr;
-  c.innov36 = n_cand > 0 ? innov36 : nullptr;
-  return pg_cov_run(g, "ba_pgraph_gate", c, dropped_pivots);
+  return ba::graph_gate(kPgSpec, g, n_cand, cand_j, cand_k, Z12, Omega36, d2, r6, innov36, dropped_pivots);
 }
 
 int ba_pgraph_cov_info(ba_pgraph *g, int64_t out4[4]) {
   if (!g || !out4) return fail("ba_pgraph_cov_info: bad argument");
-  const int bw = ba::cov_batch_cols(g->d.npad, g->h->knobs.run);
-  out4[0] = bw;
-  out4[1] = ba::kCovGroupCols;
-  out4[2] = g->cov_batches;
-  out4[3] = (int64_t)g->d.npad * bw * (int64_t)sizeof(double);
+  ba::graph_cov_info(g, out4);
   return 0;
 }
 
 int ba_pgraph_last_ms(ba_pgraph *g, double *ms) {
   if (!g || !ms) return fail("ba_pgraph_last_ms: bad argument");
-  *ms = g->last_ms;
+  *ms = ba::graph_last_ms(g);
   return 0;
 }
 

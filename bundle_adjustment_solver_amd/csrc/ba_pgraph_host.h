@@ -2,7 +2,8 @@
 // DESIGN.md §6k): validation of the caller's arrays, the per-pose and per-block factor
 // lists and the tile adjacency of the dense image.  Plain C++ with no HIP call, so that it
 // also builds into a stand-alone program under the host sanitizers
-// (tools/pgraph_host_check.cpp, tools/pgraph_robust_host_check.cpp).  Internal.
+// (tools/pgraph_host_check.cpp, tools/pgraph_robust_host_check.cpp).  The lists, the robust rules
+// and the covariance / gate validation serve the Sim(3) graph too (ba_sim3_host.h).  Internal.
 #ifndef BA_PGRAPH_HOST_H_
 #define BA_PGRAPH_HOST_H_
 
@@ -38,6 +39,26 @@ inline int pgraph_validate_host(int n_pose, const double *T_jw12, const uint8_t 
   for (int p = 0; p < n_pose; ++p)
     if (!(pose_fixed && pose_fixed[p]) && !named[p])
       return bad("pose " + std::to_string(p) + " is optimisable but no factor names it");
+  return 0;
+}
+
+// The values of ba_pgraph_update_values: what ba_pgraph_check refuses about the poses and about
+// the factor values, in its wording (any array may be null: not checked).
+inline int pgraph_validate_values(int n_pose, const double *T_jw12, int64_t n_rel, const double *Z12,
+                                  const double *Omega36, std::string *err) {
+  auto bad = [&](const std::string &m) {
+    *err = m;
+    return -1;
+  };
+  for (int64_t e = 0; e < (int64_t)n_pose * 12 && T_jw12; ++e)
+    if (!std::isfinite(T_jw12[e])) return bad("T_jw is not finite (pose " + std::to_string(e / 12) + ")");
+  for (int64_t f = 0; f < n_rel && (Z12 || Omega36); ++f) {
+    const std::string at = " (factor " + std::to_string(f) + ")";
+    for (int e = 0; e < 12 && Z12; ++e)
+      if (!std::isfinite(Z12[12 * f + e])) return bad("Z is not finite" + at);
+    for (int e = 0; e < 36 && Omega36; ++e)
+      if (!std::isfinite(Omega36[36 * f + e])) return bad("Omega is not finite" + at);
+  }
   return 0;
 }
 
@@ -111,34 +132,45 @@ inline void pgraph_tile_adjacency(const PgraphLists &l, int poses_per_tile, int 
 // ---- covariance blocks and the chi-square gate (ba_pgraph_covariance / ba_pgraph_gate;
 // ---- DESIGN.md §6m) -------------------------------------------------------------------------
 
-// Cholesky of the 6x6 matrix whose lower triangle is in O (row-major); false at a pivot that is
-// not positive (or not finite).  The same loop as the device's (ba_pgraph_cov.hip).
-inline bool pgraph_chol6_host(const double *O) {
-  double L[36];
-  for (int c = 0; c < 6; ++c) {
-    double d = O[c * 6 + c];
-    for (int m = 0; m < c; ++m) d -= L[c * 6 + m] * L[c * 6 + m];
+// Cholesky of the W x W matrix (W <= 7) whose lower triangle is in O (row-major); false at a
+// pivot that is not positive (or not finite).  The same loop as the device's (ba_pgraph_cov.hip,
+// ba_sim3_cov.hip).
+inline bool chol_host(const double *O, int W) {
+  double L[49];
+  for (int c = 0; c < W; ++c) {
+    double d = O[c * W + c];
+    for (int m = 0; m < c; ++m) d -= L[c * W + m] * L[c * W + m];
     if (!(d > 0.0) || !std::isfinite(d)) return false;
     const double s = std::sqrt(d);
-    L[c * 6 + c] = s;
-    for (int r = c + 1; r < 6; ++r) {
-      double v = O[r * 6 + c];
-      for (int m = 0; m < c; ++m) v -= L[r * 6 + m] * L[c * 6 + m];
-      L[r * 6 + c] = v / s;
+    L[c * W + c] = s;
+    for (int r = c + 1; r < W; ++r) {
+      double v = O[r * W + c];
+      for (int m = 0; m < c; ++m) v -= L[r * W + m] * L[c * W + m];
+      L[r * W + c] = v / s;
     }
   }
   return true;
 }
 
-// Everything ba_pgraph_cov_check refuses, in the order of the header's list; *err carries the
-// call's name.  The pairs follow the pair rules of ba_relative_check, the candidates the pair and
-// the value rules, in its wording ("(pair 3)", "(candidate 3)" for its "(factor 3)").
-inline int pgraph_cov_validate_host(int n_pose, const uint8_t *pose_fixed, int n_pose_sel, const int32_t *pose_sel,
-                                    const double *cov_pose36, int64_t n_pair, const int32_t *pair_j,
-                                    const int32_t *pair_k, const double *cov_rel36, int64_t n_cand,
-                                    const int32_t *cand_j, const int32_t *cand_k, const double *Z12,
-                                    const double *Omega36, const double *d2, std::string *err) {
-  const std::string cov = "ba_pgraph_covariance: ", gate = "ba_pgraph_gate: ";
+// The names a graph kind gives the covariance / gate validation: its two calls, its output arrays
+// as the messages spell them, and the rules of its candidates: pairs and values, in the wording
+// of a factor ("(factor 3)").
+struct GraphCovNames {
+  const char *covariance, *gate, *cov_pose, *cov_rel;
+  int (*check_candidates)(int n_pose, const uint8_t *pose_fixed, int64_t n_cand, const int32_t *cand_j,
+                          const int32_t *cand_k, const double *Z, const double *Omega, std::string *err);
+};
+
+// Everything ba_pgraph_cov_check and ba_sim3_cov_check refuse at tangent width W, in the order of
+// the header's list; *err carries the call's name.  The pairs follow the pair rules of
+// ba_relative_check, the candidates the kind's pair and value rules, in their wording ("(pair 3)",
+// "(candidate 3)" for "(factor 3)"); then a candidate whose Omega is not positive definite.
+inline int graph_cov_validate_host(int W, const GraphCovNames &names, int n_pose, const uint8_t *pose_fixed,
+                                   int n_pose_sel, const int32_t *pose_sel, const double *cov_pose, int64_t n_pair,
+                                   const int32_t *pair_j, const int32_t *pair_k, const double *cov_rel,
+                                   int64_t n_cand, const int32_t *cand_j, const int32_t *cand_k, const double *Z,
+                                   const double *Omega, const double *d2, std::string *err) {
+  const std::string cov = std::string(names.covariance) + ": ", gate = std::string(names.gate) + ": ";
   auto bad = [&](const std::string &m) {
     *err = m;
     return -1;
@@ -147,8 +179,8 @@ inline int pgraph_cov_validate_host(int n_pose, const uint8_t *pose_fixed, int n
   if (n_pose_sel < 0 || n_pair < 0) return bad(cov + "negative selection size");
   if (n_cand < 0) return bad(gate + "negative number of candidates");
   if (n_pose_sel > 0 && !pose_sel) return bad(cov + "pose_sel is NULL for a non-empty selection");
-  if (n_pose_sel > 0 && !cov_pose36) return bad(cov + "cov_pose36 is NULL for a non-empty pose selection");
-  if (n_pair > 0 && !cov_rel36) return bad(cov + "cov_rel36 is NULL for a non-empty pair selection");
+  if (n_pose_sel > 0 && !cov_pose) return bad(cov + names.cov_pose + " is NULL for a non-empty pose selection");
+  if (n_pair > 0 && !cov_rel) return bad(cov + names.cov_rel + " is NULL for a non-empty pair selection");
   if (n_cand > 0 && !d2) return bad(gate + "d2 is NULL for a non-empty candidate list");
   for (int s = 0; s < n_pose_sel; ++s) {
     const int u = pose_sel[s];
@@ -157,7 +189,7 @@ inline int pgraph_cov_validate_host(int n_pose, const uint8_t *pose_fixed, int n
     if (pose_fixed && pose_fixed[u])
       return bad(cov + "pose_sel[" + std::to_string(s) + "] = " + std::to_string(u) + " is a fixed pose");
   }
-  // relative_validate_host says "factor"; here the entry is a pair or a candidate
+  // the shared validations say "factor"; here the entry is a pair or a candidate
   auto renamed = [&](const std::string &call, const char *entry) {
     const size_t at = err->rfind("factor ");
     if (at != std::string::npos) err->replace(at, 7, std::string(entry) + " ");
@@ -166,12 +198,29 @@ inline int pgraph_cov_validate_host(int n_pose, const uint8_t *pose_fixed, int n
   };
   if (relative_validate_host(kRelPairs, n_pose, pose_fixed, n_pair, pair_j, pair_k, nullptr, nullptr, err))
     return renamed(cov, "pair");
-  if (relative_validate_host(kRelPairs | kRelValues, n_pose, pose_fixed, n_cand, cand_j, cand_k, Z12, Omega36, err))
+  if (names.check_candidates(n_pose, pose_fixed, n_cand, cand_j, cand_k, Z, Omega, err))
     return renamed(gate, "candidate");
   for (int64_t c = 0; c < n_cand; ++c)
-    if (!pgraph_chol6_host(Omega36 + 36 * c))
+    if (!chol_host(Omega + (size_t)W * W * c, W))
       return bad(gate + "Omega is not positive definite (candidate " + std::to_string(c) + ")");
   return 0;
+}
+
+// The SE(3) graph's: the candidates follow the pair and the value rules of ba_relative_check
+inline int pgraph_check_candidates(int n_pose, const uint8_t *pose_fixed, int64_t n_cand, const int32_t *cand_j,
+                                   const int32_t *cand_k, const double *Z12, const double *Omega36,
+                                   std::string *err) {
+  return relative_validate_host(kRelPairs | kRelValues, n_pose, pose_fixed, n_cand, cand_j, cand_k, Z12, Omega36, err);
+}
+inline int pgraph_cov_validate_host(int n_pose, const uint8_t *pose_fixed, int n_pose_sel, const int32_t *pose_sel,
+                                    const double *cov_pose36, int64_t n_pair, const int32_t *pair_j,
+                                    const int32_t *pair_k, const double *cov_rel36, int64_t n_cand,
+                                    const int32_t *cand_j, const int32_t *cand_k, const double *Z12,
+                                    const double *Omega36, const double *d2, std::string *err) {
+  const GraphCovNames names = {"ba_pgraph_covariance", "ba_pgraph_gate", "cov_pose36", "cov_rel36",
+                               pgraph_check_candidates};
+  return graph_cov_validate_host(6, names, n_pose, pose_fixed, n_pose_sel, pose_sel, cov_pose36, n_pair, pair_j,
+                                 pair_k, cov_rel36, n_cand, cand_j, cand_k, Z12, Omega36, d2, err);
 }
 
 // One wave of k_pgcov_solve owns 16 right-hand sides: the six identity columns of the pose

@@ -105,70 +105,25 @@ inline void sim3_tile_adjacency(const PgraphLists &l, int nb, int *ncb, std::vec
 // ---- covariance blocks and the chi-square gate (ba_sim3_covariance / ba_sim3_gate;
 // ---- DESIGN.md §6p) -------------------------------------------------------------------------
 
-// Cholesky of the 7x7 matrix whose lower triangle is in O (row-major); false at a pivot that is
-// not positive (or not finite).  The same loop as the device's (ba_sim3_cov.hip).
-inline bool sim3_chol7_host(const double *O) {
-  double L[49];
-  for (int c = 0; c < 7; ++c) {
-    double d = O[c * 7 + c];
-    for (int m = 0; m < c; ++m) d -= L[c * 7 + m] * L[c * 7 + m];
-    if (!(d > 0.0) || !std::isfinite(d)) return false;
-    const double s = std::sqrt(d);
-    L[c * 7 + c] = s;
-    for (int r = c + 1; r < 7; ++r) {
-      double v = O[r * 7 + c];
-      for (int m = 0; m < c; ++m) v -= L[r * 7 + m] * L[c * 7 + m];
-      L[r * 7 + c] = v / s;
-    }
+// graph_cov_validate_host (ba_pgraph_host.h) at width 7.  The candidates follow the pair rules of
+// ba_relative_check and the value rules of ba_sim3_check.
+inline int sim3_check_candidates(int n_pose, const uint8_t *pose_fixed, int64_t n_cand, const int32_t *cand_j,
+                                 const int32_t *cand_k, const double *Z13, const double *Omega49, std::string *err) {
+  if (n_cand > 0 && (!Z13 || !Omega49)) {
+    *err = "null factor array (factor 0)";
+    return -1;
   }
-  return true;
+  if (relative_validate_host(kRelPairs, n_pose, pose_fixed, n_cand, cand_j, cand_k, nullptr, nullptr, err)) return -1;
+  return sim3_validate_values(0, nullptr, n_cand, Z13, Omega49, err);
 }
-
-// Everything ba_sim3_cov_check refuses, in the order of pgraph_cov_validate_host; *err carries
-// the call's name.  The pairs follow the pair rules of ba_relative_check, the candidates the pair
-// rules and the value rules of ba_sim3_check, in their wording ("(pair 3)", "(candidate 3)" for
-// "(factor 3)"); then a candidate whose Omega_z is not positive definite.
 inline int sim3_cov_validate_host(int n_pose, const uint8_t *pose_fixed, int n_pose_sel, const int32_t *pose_sel,
                                   const double *cov_pose49, int64_t n_pair, const int32_t *pair_j,
                                   const int32_t *pair_k, const double *cov_rel49, int64_t n_cand,
                                   const int32_t *cand_j, const int32_t *cand_k, const double *Z13,
                                   const double *Omega49, const double *d2, std::string *err) {
-  const std::string cov = "ba_sim3_covariance: ", gate = "ba_sim3_gate: ";
-  auto bad = [&](const std::string &m) {
-    *err = m;
-    return -1;
-  };
-  if (n_pose < 1) return bad(cov + "n_pose must be >= 1");
-  if (n_pose_sel < 0 || n_pair < 0) return bad(cov + "negative selection size");
-  if (n_cand < 0) return bad(gate + "negative number of candidates");
-  if (n_pose_sel > 0 && !pose_sel) return bad(cov + "pose_sel is NULL for a non-empty selection");
-  if (n_pose_sel > 0 && !cov_pose49) return bad(cov + "cov_pose49 is NULL for a non-empty pose selection");
-  if (n_pair > 0 && !cov_rel49) return bad(cov + "cov_rel49 is NULL for a non-empty pair selection");
-  if (n_cand > 0 && !d2) return bad(gate + "d2 is NULL for a non-empty candidate list");
-  for (int s = 0; s < n_pose_sel; ++s) {
-    const int u = pose_sel[s];
-    if (u < 0 || u >= n_pose)
-      return bad(cov + "pose_sel[" + std::to_string(s) + "] = " + std::to_string(u) + " is out of range");
-    if (pose_fixed && pose_fixed[u])
-      return bad(cov + "pose_sel[" + std::to_string(s) + "] = " + std::to_string(u) + " is a fixed pose");
-  }
-  // the shared validations say "factor"; here the entry is a pair or a candidate
-  auto renamed = [&](const std::string &call, const char *entry) {
-    const size_t at = err->rfind("factor ");
-    if (at != std::string::npos) err->replace(at, 7, std::string(entry) + " ");
-    *err = call + *err;
-    return -1;
-  };
-  if (relative_validate_host(kRelPairs, n_pose, pose_fixed, n_pair, pair_j, pair_k, nullptr, nullptr, err))
-    return renamed(cov, "pair");
-  if (n_cand > 0 && (!Z13 || !Omega49)) return bad(gate + "null factor array (candidate 0)");
-  if (relative_validate_host(kRelPairs, n_pose, pose_fixed, n_cand, cand_j, cand_k, nullptr, nullptr, err))
-    return renamed(gate, "candidate");
-  if (sim3_validate_values(0, nullptr, n_cand, Z13, Omega49, err)) return renamed(gate, "candidate");
-  for (int64_t c = 0; c < n_cand; ++c)
-    if (!sim3_chol7_host(Omega49 + 49 * c))
-      return bad(gate + "Omega is not positive definite (candidate " + std::to_string(c) + ")");
-  return 0;
+  const GraphCovNames names = {"ba_sim3_covariance", "ba_sim3_gate", "cov_pose49", "cov_rel49", sim3_check_candidates};
+  return graph_cov_validate_host(7, names, n_pose, pose_fixed, n_pose_sel, pose_sel, cov_pose49, n_pair, pair_j,
+                                 pair_k, cov_rel49, n_cand, cand_j, cand_k, Z13, Omega49, d2, err);
 }
 
 }  // namespace ba

@@ -1702,16 +1702,27 @@ def refuse_robust(what, rels):
                            "(SolvePoseGraph, BaPoseGraph.set_robust)" % (what, f))
 
 
-def pgraph_check(pose_T, pose_fixed, rels):
-    """Host-only validation of BaPoseGraph's inputs (ba_pgraph_check); raises BaError."""
-    T = np.ascontiguousarray(pose_T, np.float64).reshape(-1, 12)
+def _graph_arrays(pose, pose_fixed, rels, W):
+    """The arrays of a graph of tangent width W as the library reads them: poses (n, W + 6), pose_fixed
+    (n,) uint8 or None, j (F,), k (F,), Z (F, W + 6), Omega (F, W W)"""
+    P = np.ascontiguousarray(pose, np.float64).reshape(-1, W + 6)
     fx = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
     j = np.ascontiguousarray(rels["j"], np.int32).reshape(-1)
     k = np.ascontiguousarray(rels["k"], np.int32).reshape(-1)
-    Z = np.ascontiguousarray(rels["Z"], np.float64).reshape(-1, 12)
-    Om = np.ascontiguousarray(rels["Omega"], np.float64).reshape(-1, 36)
-    check(_lib.load().ba_pgraph_check(T.shape[0], _dp(T) if T.size else None, None if fx is None else _up(fx),
-                                      len(j), _ip(j), _ip(k), _dp(Z), _dp(Om)), "ba_pgraph_check")
+    Z = np.ascontiguousarray(rels["Z"], np.float64).reshape(-1, W + 6)
+    Om = np.ascontiguousarray(rels["Omega"], np.float64).reshape(-1, W * W)
+    return P, fx, j, k, Z, Om
+
+
+def _graph_check(abi, W, pose, pose_fixed, rels):
+    P, fx, j, k, Z, Om = _graph_arrays(pose, pose_fixed, rels, W)
+    check(getattr(_lib.load(), abi + "_check")(P.shape[0], _dp(P) if P.size else None, None if fx is None else _up(fx),
+                                                len(j), _ip(j), _ip(k), _dp(Z), _dp(Om)), abi + "_check")
+
+
+def pgraph_check(pose_T, pose_fixed, rels):
+    """Host-only validation of BaPoseGraph's inputs (ba_pgraph_check); raises BaError."""
+    _graph_check("ba_pgraph", 6, pose_T, pose_fixed, rels)
 
 
 def _pair_arrays(pairs):
@@ -1730,85 +1741,86 @@ def _pair_arrays(pairs):
     return j, k
 
 
-def _candidate_arrays(j, k, Z, Omega):
+def _candidate_arrays(j, k, Z, Omega, W):
     j, k = _pair_arrays((np.atleast_1d(j), np.atleast_1d(k)))
-    Z = np.ascontiguousarray(Z, np.float64).reshape(-1, 12)
-    Om = np.ascontiguousarray(Omega, np.float64).reshape(-1, 36)
+    Z = np.ascontiguousarray(Z, np.float64).reshape(-1, W + 6)
+    Om = np.ascontiguousarray(Omega, np.float64).reshape(-1, W * W)
     if Z.shape[0] != len(j) or Om.shape[0] != len(j):
-        raise ValueError("candidates: needs j (n,), k (n,), Z (n, 12), Omega (n, 6, 6)")
+        raise ValueError("candidates: needs j (n,), k (n,), Z (n, %d), Omega (n, %d, %d)" % (W + 6, W, W))
     return j, k, Z, Om
+
+
+def _graph_cov_check(abi, W, n_pose, pose_fixed, pose_sel, pairs, candidates):
+    fx = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
+    ps = np.zeros(0, np.int32) if pose_sel is None else np.ascontiguousarray(pose_sel, np.int32).reshape(-1)
+    pj, pk = _pair_arrays(pairs)
+    c = candidates
+    cj, ck, Z, Om = _candidate_arrays(c["j"], c["k"], c["Z"], c["Omega"], W) if c is not None else \
+        _candidate_arrays([], [], np.zeros((0, W + 6)), np.zeros((0, W * W)), W)
+    out = np.zeros(1)   # the outputs only have to be there
+    check(getattr(_lib.load(), abi + "_cov_check")(int(n_pose), None if fx is None else _up(fx), len(ps), _ip(ps),
+                                                    _dp(out), len(pj), _ip(pj), _ip(pk), _dp(out), len(cj), _ip(cj),
+                                                    _ip(ck), _dp(Z) if Z.size else None, _dp(Om) if Om.size else None,
+                                                    _dp(out)), abi + "_cov_check")
 
 
 def pgraph_cov_check(n_pose, pose_fixed, pose_sel=None, pairs=None, candidates=None):
     """Host-only validation of BaPoseGraph.covariance / gate (ba_pgraph_cov_check); raises BaError.
     pose_sel: user indices; pairs: (j, k) arrays or (n, 2); candidates: dict(j, k, Z, Omega)."""
-    fx = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
-    ps = np.zeros(0, np.int32) if pose_sel is None else np.ascontiguousarray(pose_sel, np.int32).reshape(-1)
-    pj, pk = _pair_arrays(pairs)
-    c = candidates
-    cj, ck, Z, Om = _candidate_arrays(c["j"], c["k"], c["Z"], c["Omega"]) if c is not None else \
-        _candidate_arrays([], [], np.zeros((0, 12)), np.zeros((0, 36)))
-    out = np.zeros(1)   # the outputs only have to be there
-    check(_lib.load().ba_pgraph_cov_check(int(n_pose), None if fx is None else _up(fx), len(ps), _ip(ps), _dp(out),
-                                          len(pj), _ip(pj), _ip(pk), _dp(out), len(cj), _ip(cj), _ip(ck),
-                                          _dp(Z) if Z.size else None, _dp(Om) if Om.size else None, _dp(out)),
-          "ba_pgraph_cov_check")
+    _graph_cov_check("ba_pgraph", 6, n_pose, pose_fixed, pose_sel, pairs, candidates)
 
 
-class BaPoseGraph:
-    """Pose-graph optimisation (ba_pgraph_* of include/ba_hip.h, DESIGN.md §6k): chi-square
-    Levenberg-Marquardt over relative-pose factors alone.  pose_T (n, 12) T_jw in scaled
-    units, pose_fixed (n,) or None, rels the dict of BaProblem.set_relative.  The structure
-    (lists, tile schedule, dense image) is planned once; update_values + solve re-optimise
-    new values.  owner: a BaProblem whose handle (device, stream, BA_DENSE_* knobs) is
-    borrowed, or None for a handle of its own."""
+class _BaGraph:
+    """What BaPoseGraph and BaSim3Graph share: every method but the ones that carry a kind's own
+    argument names.  A kind is its ABI prefix, its tangent width W (W + 6 doubles per pose and per
+    measurement Z, W x W per Omega and per covariance block) and the keys of its info() words; the
+    library behind it is one driver too (csrc/ba_graph.hip)."""
 
-    def __init__(self, pose_T, pose_fixed, rels, device=0, owner=None):
+    _abi, _W, _pose_arg = None, 0, None
+    _info_keys = ("N", "factors", "blocks", "nb", "tiles", "levels", "image_bytes", "bad_pivots")
+
+    def _call(self, entry, *args):
+        name = "%s_%s" % (self._abi, entry)
+        check(getattr(self.lib, name)(*args), name)
+
+    def __init__(self, pose, pose_fixed, rels, device=0, owner=None):
         self.lib = _lib.load()
         self.g = None
         self._own = owner is None
         self._owner = None
-        T = np.ascontiguousarray(pose_T, np.float64).reshape(-1, 12)
-        fx = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
-        j = np.ascontiguousarray(rels["j"], np.int32).reshape(-1)
-        k = np.ascontiguousarray(rels["k"], np.int32).reshape(-1)
-        Z = np.ascontiguousarray(rels["Z"], np.float64).reshape(-1, 12)
-        Om = np.ascontiguousarray(rels["Omega"], np.float64).reshape(-1, 36)
+        W = self._W
+        P, fx, j, k, Z, Om = _graph_arrays(pose, pose_fixed, rels, W)
         if not (len(k) == len(j) and Z.shape[0] == len(j) and Om.shape[0] == len(j)) or \
-                (fx is not None and len(fx) != T.shape[0]):
-            raise ValueError("BaPoseGraph: needs pose_T (n, 12), pose_fixed (n,), j (F,), k (F,), Z (F, 12), "
-                             "Omega (F, 6, 6)")
-        pgraph_check(T, fx, dict(j=j, k=k, Z=Z, Omega=Om))   # refusals need no device
-        self.n_pose, self.n_rel = T.shape[0], len(j)
+                (fx is not None and len(fx) != P.shape[0]):
+            raise ValueError("%s: needs %s (n, %d), pose_fixed (n,), j (F,), k (F,), Z (F, %d), Omega (F, %d, %d)"
+                             % (type(self).__name__, self._pose_arg, W + 6, W + 6, W, W))
+        _graph_check(self._abi, W, P, fx, dict(j=j, k=k, Z=Z, Omega=Om))   # refusals need no device
+        self.n_pose, self.n_rel = P.shape[0], len(j)
         self._fixed = np.zeros(self.n_pose, np.uint8) if fx is None else fx.copy()
         self._owner = BaProblem(device) if owner is None else owner
         g = C.c_void_p()
-        check(self.lib.ba_pgraph_create(C.byref(g), self._owner.h, self.n_pose, _dp(T),
-                                        None if fx is None else _up(fx), self.n_rel, _ip(j), _ip(k),
-                                        _dp(Z), _dp(Om)), "ba_pgraph_create")
+        self._call("create", C.byref(g), self._owner.h, self.n_pose, _dp(P), None if fx is None else _up(fx),
+                   self.n_rel, _ip(j), _ip(k), _dp(Z), _dp(Om))
         self.g = g
         if rels.get("robust_kind") is not None:   # a factor dict that carries kernels
             self.set_robust(rels["robust_kind"], rels.get("robust_scale"))
 
     def set_robust(self, kind, scale=None):
-        """Robust kernels of the factors (ba_pgraph_set_robust): kind (F,) of
-        ROBUST_NONE / HUBER / CAUCHY / GEMAN_MCCLURE, scale (F,) the Mahalanobis distance c > 0
-        of each factor whose kind is not 0.  kind None clears every kernel.  No re-planning:
-        call it between solves as often as needed."""
+        """Robust kernels of the factors (ba_pgraph_set_robust; ba_sim3_set_robust,
+        §6p): kind (F,) of ROBUST_NONE / HUBER / CAUCHY / GEMAN_MCCLURE, scale (F,) the Mahalanobis
+        distance c > 0 of each factor whose kind is not 0.  kind None clears every kernel.  No
+        re-planning: call it between solves as often as needed."""
         kd, sc = _robust_arrays(kind, scale, self.n_rel)
-        check(self.lib.ba_pgraph_set_robust(self.g, None if kd is None else _ip(kd), None if sc is None else _dp(sc)),
-              "ba_pgraph_set_robust")
+        self._call("set_robust", self.g, None if kd is None else _ip(kd), None if sc is None else _dp(sc))
 
-    def factor_report(self):
-        """-> (s (F,), w (F,)): s_f = r_f^T Omega_f r_f and the robust weight w_f of every
-        factor at the poses the object holds (ba_pgraph_factor_report)"""
+    def _factor_sw(self, entry):
         s, w = np.zeros(self.n_rel), np.zeros(self.n_rel)
-        check(self.lib.ba_pgraph_factor_report(self.g, _dp(s), _dp(w)), "ba_pgraph_factor_report")
+        self._call(entry, self.g, _dp(s), _dp(w))
         return s, w
 
     def close(self):
         if self.g:
-            self.lib.ba_pgraph_destroy(self.g)
+            getattr(self.lib, self._abi + "_destroy")(self.g)
             self.g = None
         if self._owner is not None and self._own:
             self._owner.close()
@@ -1820,17 +1832,16 @@ class BaPoseGraph:
         except Exception:
             pass
 
-    def update_values(self, pose_T=None, Z=None, Omega=None):
-        """New values for the same structure (ba_pgraph_update_values); None keeps."""
-        T = None if pose_T is None else np.ascontiguousarray(pose_T, np.float64).reshape(-1, 12)
-        Zs = None if Z is None else np.ascontiguousarray(Z, np.float64).reshape(-1, 12)
-        Om = None if Omega is None else np.ascontiguousarray(Omega, np.float64).reshape(-1, 36)
-        if (T is not None and T.shape[0] != self.n_pose) or (Zs is not None and Zs.shape[0] != self.n_rel) or \
+    def _update_values(self, pose, Z, Omega):
+        W = self._W
+        P = None if pose is None else np.ascontiguousarray(pose, np.float64).reshape(-1, W + 6)
+        Zs = None if Z is None else np.ascontiguousarray(Z, np.float64).reshape(-1, W + 6)
+        Om = None if Omega is None else np.ascontiguousarray(Omega, np.float64).reshape(-1, W * W)
+        if (P is not None and P.shape[0] != self.n_pose) or (Zs is not None and Zs.shape[0] != self.n_rel) or \
                 (Om is not None and Om.shape[0] != self.n_rel):
             raise ValueError("update_values: the structure is fixed (same number of poses / factors)")
-        check(self.lib.ba_pgraph_update_values(self.g, None if T is None else _dp(T),
-                                               None if Zs is None else _dp(Zs),
-                                               None if Om is None else _dp(Om)), "ba_pgraph_update_values")
+        self._call("update_values", self.g, None if P is None else _dp(P), None if Zs is None else _dp(Zs),
+                   None if Om is None else _dp(Om))
 
     def solve(self, opt, cap=None, rows=None):
         """-> (rows, converged): the logged ba_iter_info rows.  rows: a BaIterInfo array to
@@ -1839,94 +1850,107 @@ class BaPoseGraph:
         given = rows is not None
         rows = (BaIterInfo * max(1, cap))() if rows is None else rows
         n_iter, conv = C.c_int(0), C.c_int(0)
-        check(self.lib.ba_pgraph_solve(self.g, C.byref(opt), rows, cap, C.byref(n_iter), C.byref(conv)),
-              "ba_pgraph_solve")
+        self._call("solve", self.g, C.byref(opt), rows, cap, C.byref(n_iter), C.byref(conv))
         self.n_iter = n_iter.value
         n = cap if given else min(n_iter.value, cap)
         return [rows[i] for i in range(n)], bool(conv.value)
 
     def poses(self):
-        T = np.zeros((self.n_pose, 12))
-        check(self.lib.ba_pgraph_get_poses(self.g, _dp(T)), "ba_pgraph_get_poses")
-        return T
+        P = np.zeros((self.n_pose, self._W + 6))
+        self._call("get_poses", self.g, _dp(P))
+        return P
 
     def cost(self):
         v = C.c_double(0.0)
-        check(self.lib.ba_pgraph_cost(self.g, C.byref(v)), "ba_pgraph_cost")
+        self._call("cost", self.g, C.byref(v))
         return v.value
 
     def system(self):
-        """-> (H (6N, 6N), g (6N,)): the undamped system at the poses the object holds"""
-        N = self.info()["N"]
-        H, g = np.zeros((6 * N, 6 * N)), np.zeros(6 * N)
-        check(self.lib.ba_pgraph_get_system(self.g, _dp(H), _dp(g)), "ba_pgraph_get_system")
+        """-> (H (W N, W N), g (W N,)): the undamped system at the poses the object holds (W = 6 on
+        BaPoseGraph, 7 on BaSim3Graph)"""
+        n = self._W * self.info()["N"]
+        H, g = np.zeros((n, n)), np.zeros(n)
+        self._call("get_system", self.g, _dp(H), _dp(g))
         return H, g
 
     def info(self):
-        out = (C.c_int64 * 8)()
-        check(self.lib.ba_pgraph_info(self.g, out), "ba_pgraph_info")
-        keys = ("N", "factors", "blocks", "nb", "tiles", "levels", "image_bytes", "bad_pivots")
-        return {key: int(out[i]) for i, key in enumerate(keys)}
+        out = (C.c_int64 * len(self._info_keys))()
+        self._call("info", self.g, out)
+        return {key: int(out[i]) for i, key in enumerate(self._info_keys)}
 
     def last_ms(self):
         v = C.c_double(0.0)
-        check(self.lib.ba_pgraph_last_ms(self.g, C.byref(v)), "ba_pgraph_last_ms")
+        self._call("last_ms", self.g, C.byref(v))
         return v.value
 
     def covariance(self, pose_sel=None, pairs=None):
-        """-> (cov_pose (n, 6, 6), cov_cross (p, 6, 6), cov_rel (p, 6, 6)): blocks of the inverse
-        of system()'s H at the poses the object holds (ba_pgraph_covariance):
-        Sigma_jj per selected pose, Sigma_jk and the covariance Sigma_E of T_j T_k^-1 per pair.
-        pose_sel: user indices of optimisable poses (None: all of them); pairs: (j, k) arrays or
-        (p, 2).  Scaled units.  self.dropped_pivots: non-positive pivots of the factorisation."""
+        """-> (cov_pose (n, W, W), cov_cross (p, W, W), cov_rel (p, W, W)): blocks of the inverse of
+        system()'s H at the poses the object holds (ba_pgraph_covariance, DESIGN.md §6m, W = 6;
+        ba_sim3_covariance, §6p, W = 7 and tangent [v; omega; sigma]): Sigma_jj per selected pose,
+        Sigma_jk and the covariance Sigma_E of T_j T_k^-1 (S_j S_k^-1) per pair.  pose_sel: user
+        indices of optimisable poses (None: all of them); pairs: (j, k) arrays or (p, 2).  Scaled
+        units.  self.dropped_pivots: non-positive pivots of the factorisation."""
+        W = self._W
         ps = np.flatnonzero(self._fixed == 0).astype(np.int32) if pose_sel is None else \
             np.ascontiguousarray(pose_sel, np.int32).reshape(-1)
         pj, pk = _pair_arrays(pairs)
-        cp, cc, cr = np.zeros((len(ps), 6, 6)), np.zeros((len(pj), 6, 6)), np.zeros((len(pj), 6, 6))
+        cp, cc, cr = np.zeros((len(ps), W, W)), np.zeros((len(pj), W, W)), np.zeros((len(pj), W, W))
         dropped = C.c_int64(0)
-        check(self.lib.ba_pgraph_covariance(self.g, len(ps), _ip(ps) if len(ps) else None,
-                                            _dp(cp) if len(ps) else None, len(pj), _ip(pj) if len(pj) else None,
-                                            _ip(pk) if len(pj) else None, _dp(cc) if len(pj) else None,
-                                            _dp(cr) if len(pj) else None, C.byref(dropped)), "ba_pgraph_covariance")
+        self._call("covariance", self.g, len(ps), _ip(ps) if len(ps) else None, _dp(cp) if len(ps) else None,
+                   len(pj), _ip(pj) if len(pj) else None, _ip(pk) if len(pj) else None,
+                   _dp(cc) if len(pj) else None, _dp(cr) if len(pj) else None, C.byref(dropped))
         self.dropped_pivots = dropped.value
         return cp, cc, cr
 
     def gate(self, j, k, Z, Omega):
-        """-> (d2 (n,), r (n, 6), P (n, 6, 6)) of loop-closure candidates shaped like factors
-        (ba_pgraph_gate): r = se3_log(T_j T_k^-1 Z^-1), P = Sigma_E + Omega^-1, d2 = r^T P^-1 r,
-        to be compared with a chi-square quantile of 6 degrees of freedom (22.46 at 0.999)."""
-        cj, ck, Zs, Om = _candidate_arrays(j, k, Z, Omega)
+        """-> (d2 (n,), r (n, W), P (n, W, W)) of loop-closure candidates shaped like factors
+        (ba_pgraph_gate: r = se3_log(T_j T_k^-1 Z^-1); ba_sim3_gate: r = sim3_log(S_j S_k^-1 Z^-1)):
+        P = Sigma_E + Omega^-1, d2 = r^T P^-1 r, to be compared with a chi-square quantile of W
+        degrees of freedom (at 0.999: 22.46 for 6, 24.32 for 7)."""
+        W = self._W
+        cj, ck, Zs, Om = _candidate_arrays(j, k, Z, Omega, W)
         n = len(cj)
-        d2, r, P = np.zeros(n), np.zeros((n, 6)), np.zeros((n, 6, 6))
+        d2, r, P = np.zeros(n), np.zeros((n, W)), np.zeros((n, W, W))
         dropped = C.c_int64(0)
-        check(self.lib.ba_pgraph_gate(self.g, n, _ip(cj) if n else None, _ip(ck) if n else None,
-                                      _dp(Zs) if n else None, _dp(Om) if n else None, _dp(d2) if n else None,
-                                      _dp(r) if n else None, _dp(P) if n else None, C.byref(dropped)), "ba_pgraph_gate")
+        self._call("gate", self.g, n, _ip(cj) if n else None, _ip(ck) if n else None, _dp(Zs) if n else None,
+                   _dp(Om) if n else None, _dp(d2) if n else None, _dp(r) if n else None, _dp(P) if n else None,
+                   C.byref(dropped))
         self.dropped_pivots = dropped.value
         return d2, r, P
 
     def cov_info(self):
         """Column batches of covariance / gate on this graph (BA_COV_BATCH of the borrowed handle overrides)"""
         v = (C.c_int64 * 4)()
-        check(self.lib.ba_pgraph_cov_info(self.g, v), "ba_pgraph_cov_info")
+        self._call("cov_info", self.g, v)
         return dict(batch_cols=int(v[0]), cols_per_wave=int(v[1]), batches=int(v[2]), workspace_bytes=int(v[3]))
 
 
-def _sim3_arrays(pose_S, pose_fixed, rels):
-    S = np.ascontiguousarray(pose_S, np.float64).reshape(-1, 13)
-    fx = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
-    j = np.ascontiguousarray(rels["j"], np.int32).reshape(-1)
-    k = np.ascontiguousarray(rels["k"], np.int32).reshape(-1)
-    Z = np.ascontiguousarray(rels["Z"], np.float64).reshape(-1, 13)
-    Om = np.ascontiguousarray(rels["Omega"], np.float64).reshape(-1, 49)
-    return S, fx, j, k, Z, Om
+class BaPoseGraph(_BaGraph):
+    """Pose-graph optimisation (ba_pgraph_* of include/ba_hip.h, DESIGN.md §6k): chi-square
+    Levenberg-Marquardt over relative-pose factors alone.  pose_T (n, 12) T_jw in scaled
+    units, pose_fixed (n,) or None, rels the dict of BaProblem.set_relative.  The structure
+    (lists, tile schedule, dense image) is planned once; update_values + solve re-optimise
+    new values.  owner: a BaProblem whose handle (device, stream, BA_DENSE_* knobs) is
+    borrowed, or None for a handle of its own."""
+
+    _abi, _W, _pose_arg = "ba_pgraph", 6, "pose_T"
+
+    def __init__(self, pose_T, pose_fixed, rels, device=0, owner=None):
+        super().__init__(pose_T, pose_fixed, rels, device, owner)
+
+    def update_values(self, pose_T=None, Z=None, Omega=None):
+        """New values for the same structure (ba_pgraph_update_values); None keeps."""
+        self._update_values(pose_T, Z, Omega)
+
+    def factor_report(self):
+        """-> (s (F,), w (F,)): s_f = r_f^T Omega_f r_f and the robust weight w_f of every
+        factor at the poses the object holds (ba_pgraph_factor_report)"""
+        return self._factor_sw("factor_report")
 
 
 def sim3_check(pose_S, pose_fixed, rels):
     """Host-only validation of BaSim3Graph's inputs (ba_sim3_check); raises BaError."""
-    S, fx, j, k, Z, Om = _sim3_arrays(pose_S, pose_fixed, rels)
-    check(_lib.load().ba_sim3_check(S.shape[0], _dp(S) if S.size else None, None if fx is None else _up(fx),
-                                    len(j), _ip(j), _ip(k), _dp(Z), _dp(Om)), "ba_sim3_check")
+    _graph_check("ba_sim3", 7, pose_S, pose_fixed, rels)
 
 
 def sim3_robust_check(kind, scale):
@@ -1937,29 +1961,10 @@ def sim3_robust_check(kind, scale):
           "ba_sim3_robust_check")
 
 
-def _sim3_candidate_arrays(j, k, Z, Omega):
-    j, k = _pair_arrays((np.atleast_1d(j), np.atleast_1d(k)))
-    Z = np.ascontiguousarray(Z, np.float64).reshape(-1, 13)
-    Om = np.ascontiguousarray(Omega, np.float64).reshape(-1, 49)
-    if Z.shape[0] != len(j) or Om.shape[0] != len(j):
-        raise ValueError("candidates: needs j (n,), k (n,), Z (n, 13), Omega (n, 7, 7)")
-    return j, k, Z, Om
-
-
 def sim3_cov_check(n_pose, pose_fixed, pose_sel=None, pairs=None, candidates=None):
     """Host-only validation of BaSim3Graph.covariance / gate (ba_sim3_cov_check); raises BaError.
     pose_sel: user indices; pairs: (j, k) arrays or (n, 2); candidates: dict(j, k, Z, Omega)."""
-    fx = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
-    ps = np.zeros(0, np.int32) if pose_sel is None else np.ascontiguousarray(pose_sel, np.int32).reshape(-1)
-    pj, pk = _pair_arrays(pairs)
-    c = candidates
-    cj, ck, Z, Om = _sim3_candidate_arrays(c["j"], c["k"], c["Z"], c["Omega"]) if c is not None else \
-        _sim3_candidate_arrays([], [], np.zeros((0, 13)), np.zeros((0, 49)))
-    out = np.zeros(1)   # the outputs only have to be there
-    check(_lib.load().ba_sim3_cov_check(int(n_pose), None if fx is None else _up(fx), len(ps), _ip(ps), _dp(out),
-                                        len(pj), _ip(pj), _ip(pk), _dp(out), len(cj), _ip(cj), _ip(ck),
-                                        _dp(Z) if Z.size else None, _dp(Om) if Om.size else None, _dp(out)),
-          "ba_sim3_cov_check")
+    _graph_cov_check("ba_sim3", 7, n_pose, pose_fixed, pose_sel, pairs, candidates)
 
 
 def sim3_exp(xi):
@@ -1983,7 +1988,7 @@ def sim3_adjoint(S13):
     return Ad
 
 
-class BaSim3Graph:
+class BaSim3Graph(_BaGraph):
     """Sim(3) pose-graph optimisation (ba_sim3_* of include/ba_hip.h): the 7-DoF
     loop closing of a monocular map, chi-square Levenberg-Marquardt over relative-similarity
     factors alone.  pose_S (n, 13) S_jw = [R row-major, t, s] in scaled units, pose_fixed (n,)
@@ -1991,154 +1996,26 @@ class BaSim3Graph:
     once; update_values + solve re-optimise new values.  owner: a BaProblem whose handle is
     borrowed, or None for a handle of its own."""
 
-    def __init__(self, pose_S, pose_fixed, rels, device=0, owner=None):
-        self.lib = _lib.load()
-        self.g = None
-        self._own = owner is None
-        self._owner = None
-        S, fx, j, k, Z, Om = _sim3_arrays(pose_S, pose_fixed, rels)
-        if not (len(k) == len(j) and Z.shape[0] == len(j) and Om.shape[0] == len(j)) or \
-                (fx is not None and len(fx) != S.shape[0]):
-            raise ValueError("BaSim3Graph: needs pose_S (n, 13), pose_fixed (n,), j (F,), k (F,), Z (F, 13), "
-                             "Omega (F, 7, 7)")
-        sim3_check(S, fx, dict(j=j, k=k, Z=Z, Omega=Om))   # refusals need no device
-        self.n_pose, self.n_rel = S.shape[0], len(j)
-        self._fixed = np.zeros(self.n_pose, np.uint8) if fx is None else fx.copy()
-        self._owner = BaProblem(device) if owner is None else owner
-        g = C.c_void_p()
-        check(self.lib.ba_sim3_create(C.byref(g), self._owner.h, self.n_pose, _dp(S),
-                                      None if fx is None else _up(fx), self.n_rel, _ip(j), _ip(k),
-                                      _dp(Z), _dp(Om)), "ba_sim3_create")
-        self.g = g
-        if rels.get("robust_kind") is not None:   # a factor dict that carries kernels
-            self.set_robust(rels["robust_kind"], rels.get("robust_scale"))
+    _abi, _W, _pose_arg = "ba_sim3", 7, "pose_S"
+    _info_keys = _BaGraph._info_keys + ("fpb",)
 
-    def set_robust(self, kind, scale=None):
-        """Robust kernels of the factors (ba_sim3_set_robust), as
-        BaPoseGraph.set_robust: kind (F,) of ROBUST_NONE / HUBER / CAUCHY / GEMAN_MCCLURE, scale
-        (F,) the Mahalanobis distance c > 0 of each factor whose kind is not 0.  kind None clears
-        every kernel.  No re-planning: call it between solves as often as needed."""
-        kd, sc = _robust_arrays(kind, scale, self.n_rel)
-        check(self.lib.ba_sim3_set_robust(self.g, None if kd is None else _ip(kd), None if sc is None else _dp(sc)),
-              "ba_sim3_set_robust")
+    def __init__(self, pose_S, pose_fixed, rels, device=0, owner=None):
+        super().__init__(pose_S, pose_fixed, rels, device, owner)
+
+    def update_values(self, pose_S=None, Z=None, Omega=None):
+        """New values for the same structure (ba_sim3_update_values); None keeps."""
+        self._update_values(pose_S, Z, Omega)
 
     def factor_weights(self):
         """-> (s (F,), w (F,)): s_f = r_f^T Omega_f r_f and the robust weight w_f of every factor
         at the poses the object holds (ba_sim3_factor_weights); w = 1 without a kernel"""
-        s, w = np.zeros(self.n_rel), np.zeros(self.n_rel)
-        check(self.lib.ba_sim3_factor_weights(self.g, _dp(s), _dp(w)), "ba_sim3_factor_weights")
-        return s, w
-
-    def covariance(self, pose_sel=None, pairs=None):
-        """-> (cov_pose (n, 7, 7), cov_cross (p, 7, 7), cov_rel (p, 7, 7)): blocks of the inverse
-        of system()'s H at the poses the object holds (ba_sim3_covariance):
-        Sigma_jj per selected pose, Sigma_jk and the covariance Sigma_E of S_j S_k^-1 per pair,
-        tangent [v; omega; sigma].  pose_sel: user indices of optimisable poses (None: all of
-        them); pairs: (j, k) arrays or (p, 2).  Scaled units.  self.dropped_pivots: non-positive
-        pivots of the factorisation."""
-        ps = np.flatnonzero(self._fixed == 0).astype(np.int32) if pose_sel is None else \
-            np.ascontiguousarray(pose_sel, np.int32).reshape(-1)
-        pj, pk = _pair_arrays(pairs)
-        cp, cc, cr = np.zeros((len(ps), 7, 7)), np.zeros((len(pj), 7, 7)), np.zeros((len(pj), 7, 7))
-        dropped = C.c_int64(0)
-        check(self.lib.ba_sim3_covariance(self.g, len(ps), _ip(ps) if len(ps) else None,
-                                          _dp(cp) if len(ps) else None, len(pj), _ip(pj) if len(pj) else None,
-                                          _ip(pk) if len(pj) else None, _dp(cc) if len(pj) else None,
-                                          _dp(cr) if len(pj) else None, C.byref(dropped)), "ba_sim3_covariance")
-        self.dropped_pivots = dropped.value
-        return cp, cc, cr
-
-    def gate(self, j, k, Z, Omega):
-        """-> (d2 (n,), r (n, 7), P (n, 7, 7)) of loop-closure candidates shaped like factors
-        (ba_sim3_gate): r = sim3_log(S_j S_k^-1 Z^-1), P = Sigma_E + Omega^-1, d2 = r^T P^-1 r, to
-        be compared with a chi-square quantile of 7 degrees of freedom (24.32 at 0.999)."""
-        cj, ck, Zs, Om = _sim3_candidate_arrays(j, k, Z, Omega)
-        n = len(cj)
-        d2, r, P = np.zeros(n), np.zeros((n, 7)), np.zeros((n, 7, 7))
-        dropped = C.c_int64(0)
-        check(self.lib.ba_sim3_gate(self.g, n, _ip(cj) if n else None, _ip(ck) if n else None,
-                                    _dp(Zs) if n else None, _dp(Om) if n else None, _dp(d2) if n else None,
-                                    _dp(r) if n else None, _dp(P) if n else None, C.byref(dropped)), "ba_sim3_gate")
-        self.dropped_pivots = dropped.value
-        return d2, r, P
-
-    def cov_info(self):
-        """Column batches of covariance / gate on this graph (BA_COV_BATCH of the borrowed handle overrides)"""
-        v = (C.c_int64 * 4)()
-        check(self.lib.ba_sim3_cov_info(self.g, v), "ba_sim3_cov_info")
-        return dict(batch_cols=int(v[0]), cols_per_wave=int(v[1]), batches=int(v[2]), workspace_bytes=int(v[3]))
-
-    def close(self):
-        if self.g:
-            self.lib.ba_sim3_destroy(self.g)
-            self.g = None
-        if self._owner is not None and self._own:
-            self._owner.close()
-        self._owner = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def update_values(self, pose_S=None, Z=None, Omega=None):
-        """New values for the same structure (ba_sim3_update_values); None keeps."""
-        S = None if pose_S is None else np.ascontiguousarray(pose_S, np.float64).reshape(-1, 13)
-        Zs = None if Z is None else np.ascontiguousarray(Z, np.float64).reshape(-1, 13)
-        Om = None if Omega is None else np.ascontiguousarray(Omega, np.float64).reshape(-1, 49)
-        if (S is not None and S.shape[0] != self.n_pose) or (Zs is not None and Zs.shape[0] != self.n_rel) or \
-                (Om is not None and Om.shape[0] != self.n_rel):
-            raise ValueError("update_values: the structure is fixed (same number of poses / factors)")
-        check(self.lib.ba_sim3_update_values(self.g, None if S is None else _dp(S),
-                                             None if Zs is None else _dp(Zs),
-                                             None if Om is None else _dp(Om)), "ba_sim3_update_values")
-
-    def solve(self, opt, cap=None, rows=None):
-        """-> (rows, converged), as BaPoseGraph.solve"""
-        cap = max(1, opt.max_num_iterations) if cap is None else cap
-        given = rows is not None
-        rows = (BaIterInfo * max(1, cap))() if rows is None else rows
-        n_iter, conv = C.c_int(0), C.c_int(0)
-        check(self.lib.ba_sim3_solve(self.g, C.byref(opt), rows, cap, C.byref(n_iter), C.byref(conv)),
-              "ba_sim3_solve")
-        self.n_iter = n_iter.value
-        n = cap if given else min(n_iter.value, cap)
-        return [rows[i] for i in range(n)], bool(conv.value)
-
-    def poses(self):
-        S = np.zeros((self.n_pose, 13))
-        check(self.lib.ba_sim3_get_poses(self.g, _dp(S)), "ba_sim3_get_poses")
-        return S
-
-    def cost(self):
-        v = C.c_double(0.0)
-        check(self.lib.ba_sim3_cost(self.g, C.byref(v)), "ba_sim3_cost")
-        return v.value
-
-    def system(self):
-        """-> (H (7N, 7N), g (7N,)): the undamped system at the poses the object holds"""
-        N = self.info()["N"]
-        H, g = np.zeros((7 * N, 7 * N)), np.zeros(7 * N)
-        check(self.lib.ba_sim3_get_system(self.g, _dp(H), _dp(g)), "ba_sim3_get_system")
-        return H, g
+        return self._factor_sw("factor_weights")
 
     def factor_report(self):
         """-> s (F,): s_f = r_f^T Omega_f r_f of every factor at the poses the object holds"""
         s = np.zeros(self.n_rel)
-        check(self.lib.ba_sim3_factor_report(self.g, _dp(s)), "ba_sim3_factor_report")
+        self._call("factor_report", self.g, _dp(s))
         return s
-
-    def info(self):
-        out = (C.c_int64 * 9)()
-        check(self.lib.ba_sim3_info(self.g, out), "ba_sim3_info")
-        keys = ("N", "factors", "blocks", "nb", "tiles", "levels", "image_bytes", "bad_pivots", "fpb")
-        return {key: int(out[i]) for i, key in enumerate(keys)}
-
-    def last_ms(self):
-        v = C.c_double(0.0)
-        check(self.lib.ba_sim3_last_ms(self.g, C.byref(v)), "ba_sim3_last_ms")
-        return v.value
 
 
 class BaStream:

@@ -209,8 +209,43 @@ def test_same_bits_run_to_run_and_after_update_values(built):
     q.close()
 
 
+HUBER = 1   # ba_hip.h: BA_ROBUST_HUBER
+
+
+def graph_calls(p, g, opt, opt1, huber):
+    """The calls of one graph between the solves of the others, one per step, each returning what
+    it computed: solve, covariance (three poses, two pairs) and gate (two candidates) at the solved
+    poses; then Huber on every factor (huber) or nothing, a one-iteration solve, and covariance,
+    gate and the poses again, and the dropped pivots of the last solve and of the last gate.  The pairs and the candidates are the graph's first two factors."""
+    r = g["rels"]
+    sel = np.flatnonzero(np.asarray(g["pose_fixed"]) == 0)[:3].astype(np.int32)
+    pairs = (np.asarray(r["j"][:2], np.int32), np.asarray(r["k"][:2], np.int32))
+    cand = (r["j"][:2], r["k"][:2], r["Z"][:2], r["Omega"][:2])
+    return [lambda: row_bits(p.solve(opt)[0]),
+            lambda: p.covariance(sel, pairs),
+            lambda: p.gate(*cand),
+            lambda: p.set_robust(np.full(p.n_rel, HUBER, np.int32), np.full(p.n_rel, 1.5)) if huber else None,
+            lambda: row_bits(p.solve(opt1)[0]),
+            lambda: p.covariance(sel, pairs),
+            lambda: p.gate(*cand),
+            lambda: p.poses(),
+            lambda: (p.info()["bad_pivots"], p.dropped_pivots)]
+
+
+def same_bits(a, b):
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(same_bits(x, y) for x, y in zip(a, b))
+    return np.array_equal(a, b) if isinstance(a, np.ndarray) else a == b
+
+
 def test_a_solve_leaves_the_other_users_of_a_handle_alone(built):
-    """a full-BA trajectory on a second handle, and an SE(3) BaPoseGraph on the SAME handle, to the bit"""
+    """a full-BA trajectory on a second handle, and an SE(3) BaPoseGraph on the SAME handle, to the
+    bit; and two Sim(3) graphs and an SE(3) graph that borrow one handle and take turns at solve,
+    covariance, gate and set_robust each return the bits of the same calls on a graph alone on a
+    fresh handle.  The two kinds share the code that moves allocations between the handle and a
+    graph (the graph's own, the robust arrays, the scratch of a covariance call) and the code that
+    saves and restores the controller and the count of dropped pivots.  n10 and g12: 12 poses;
+    g30_33: two or more tiles at order 32, k_s3_lin workgroups of 32 factors."""
     sc = scenes.synthetic_ba_scene(12, 300, 5, True, seed=7)
     pr = scenes.scaled_problem(sc)
 
@@ -226,6 +261,23 @@ def test_a_solve_leaves_the_other_users_of_a_handle_alone(built):
     def se3(owner):
         g = pgo_cases.scene("g12")
         return BaPoseGraph(g["pose_T"], g["pose_fixed"], g["rels"], owner=owner)
+
+    # (make the graph, its scene, its options, Huber in the middle): Huber on one graph of each
+    # kind, the third stays plain
+    users = [(lambda o: make("n10", owner=o), cases.scene("n10"), cases.options, "n10", True),
+             (se3, pgo_cases.scene("g12"), pgo_cases.options, "g12", True),
+             (lambda o: make("g30_33", owner=o), cases.scene("g30_33"), cases.options, "g30_33", False)]
+
+    def calls_of(user, owner):
+        mk, g, options, name, huber = user
+        p = mk(owner)
+        return p, graph_calls(p, g, options(name), options(name, max_iter=1), huber)
+
+    alone = []
+    for user in users:   # each graph alone on a fresh handle of its own
+        p, calls = calls_of(user, None)
+        alone.append([c() for c in calls])
+        p.close()
 
     opt = make_options(max_iter=4, thr_step=0.0, thr_cost=0.0)
     a = ba()
@@ -244,10 +296,21 @@ def test_a_solve_leaves_the_other_users_of_a_handle_alone(built):
     q.solve(cases.options("n10"))
     rows_f, _ = f.solve(pgo_cases.options("g12"))
     q.solve(cases.options("n10"))
-    rows_b, _ = b.solve(opt)
     assert row_bits(rows_e) == row_bits(rows_f) and np.array_equal(Te, f.poses())
+    # the three users on the problem's handle, one call each in turn
+    shared = [calls_of(user, b) for user in users]
+    got = [[] for _ in users]
+    for step in range(len(shared[0][1])):
+        for u, (_, calls) in enumerate(shared):
+            got[u].append(calls[step]())
+    for u, (g, _) in enumerate(shared):
+        for step, (x, y) in enumerate(zip(got[u], alone[u])):
+            assert same_bits(x, y), (users[u][3], step)
+    rows_b, _ = b.solve(opt)
     assert [(r.trial_cost, r.iteration_status) for r in rows_a] == [(r.trial_cost, r.iteration_status) for r in rows_b]
     assert np.array_equal(Ta, b.get_poses()) and np.array_equal(Xa, b.get_points()[0])
+    for g, _ in shared:
+        g.close()
     f.close()
     q.close()
     p.close()

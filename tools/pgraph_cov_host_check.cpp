@@ -221,14 +221,14 @@ int main() {
   {
     double O[36] = {0.0};
     for (int a = 0; a < 6; ++a) O[7 * a] = 1.0;
-    REQUIRE(ba::pgraph_chol6_host(O));
+    REQUIRE(ba::chol_host(O, 6));
     O[1] = 1e300;  // above the diagonal
-    REQUIRE(ba::pgraph_chol6_host(O));
+    REQUIRE(ba::chol_host(O, 6));
     O[6] = 1.0;    // [[1, 1], [1, 1]]: singular
-    REQUIRE(!ba::pgraph_chol6_host(O));
+    REQUIRE(!ba::chol_host(O, 6));
     O[6] = 0.0;
     O[35] = std::numeric_limits<double>::infinity();
-    REQUIRE(!ba::pgraph_chol6_host(O));
+    REQUIRE(!ba::chol_host(O, 6));
   }
   std::mt19937 gen(7);
   for (int n : {2, 3, 4, 7, 12, 13, 60, 331})

@@ -2,7 +2,7 @@
 // kernels, the covariance blocks and the gate of the Sim(3) graph:
 //   pg_rho (csrc/ba_robust_fn.h): rho and w of every kind against long-double restatements of the
 //       table of include/ba_hip.h, w against a central difference of rho, w(0) = 1;
-//   sim3_chol7_host (csrc/ba_sim3_host.h): accepts J^T J of random 9x7 J and reproduces it from
+//   chol_host at width 7 (csrc/ba_pgraph_host.h): accepts J^T J of random 9x7 J and reproduces it from
 //       a long-double Cholesky to 1e-12, refuses a zero, an indefinite, a rank-6 and a NaN matrix,
 //       reads the lower triangle only;
 //   sim3_cov_validate_host: one refusal of each family and an accepted call.
@@ -81,7 +81,7 @@ int main() {
         for (int m = 0; m < 9; ++m) a += J[7 * m + r] * J[7 * m + c];
         O[7 * r + c] = r >= c ? a : 1e300;  // the upper triangle is never read
       }
-    EXPECT(ba::sim3_chol7_host(O));
+    EXPECT(ba::chol_host(O, 7));
     long double L[49] = {0.0L};
     bool ok = true;
     for (int c = 0; c < 7 && ok; ++c) {
@@ -106,16 +106,16 @@ int main() {
   std::printf("L L^T against Omega: %.2e relative\n", worst_c);
   EXPECT(worst_c <= 1e-12);
   double Zr[49] = {0.0};
-  EXPECT(!ba::sim3_chol7_host(Zr));
+  EXPECT(!ba::chol_host(Zr, 7));
   for (int r = 0; r < 7; ++r) Zr[8 * r] = 1.0;
-  EXPECT(ba::sim3_chol7_host(Zr));
+  EXPECT(ba::chol_host(Zr, 7));
   Zr[8 * 3] = -1.0;
-  EXPECT(!ba::sim3_chol7_host(Zr));
+  EXPECT(!ba::chol_host(Zr, 7));
   Zr[8 * 3] = 1.0;
   Zr[8 * 6] = 0.0;  // rank 6
-  EXPECT(!ba::sim3_chol7_host(Zr));
+  EXPECT(!ba::chol_host(Zr, 7));
   Zr[8 * 6] = std::nan("");
-  EXPECT(!ba::sim3_chol7_host(Zr));
+  EXPECT(!ba::chol_host(Zr, 7));
   // ---- the validation
   const uint8_t fixed[4] = {1, 0, 0, 0};
   const int32_t sel[2] = {1, 3}, bad_sel[2] = {1, 0}, pj[2] = {1, 0}, pk[2] = {2, 3}, same[2] = {2, 0};
