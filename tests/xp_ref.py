@@ -559,3 +559,162 @@ def passes():
 
 def huber_of(name):
     return HUBER.get(name, 1.0)
+
+
+# ---------------------------------------------------------------------------------------
+# the batched path (test_batch_rounding_ref.py, test_gpu_batch_rounding.py): it has no stage
+# getters, so it is judged on what it returns: the step of a one-iteration solve must solve
+# the full damped normal equations, the output of a marginalisation that eliminates nothing
+# is the reduced camera system.  The bounds are those above (BOUND_FACTOR, SUM_CAP) and so is their
+# LIMIT: with one Newton step taken out of rcp_newton every batched test still passes (largest rises
+# on the MI355X: landmark rows of M257 at lambda 1e-3 from 8.0 to 11.9 units, bound 56; S of N5 from
+# 1.2 to 3.0, bound 43).  An intermediate of the landmark pass through float (S at 1e6 .. 5e7 units)
+# and a wave-sum term of the pose pass dropped for lane 63 (pose rows at 4e6 units and more, wherever
+# a pose has 64 observations) are far outside.
+# ---------------------------------------------------------------------------------------
+def se3_log(dR, dt):
+    """(v (n, 3), w (n, 3)) in long double with se3_exp((v, w)) = (dR (n, 3, 3), dt (n, 3)).
+    theta = atan2(|vee(dR - dR^T)| / 2, (tr dR - 1) / 2), w = theta / (2 sin theta) vee(dR - dR^T),
+    v = (I - wx / 2 + k wx^2) dt, k = (1 - (theta / 2) cot(theta / 2)) / theta^2; below
+    theta = 1e-6 the series theta / (2 sin theta) = (1 + theta^2 / 6) / 2, k = 1 / 12 + theta^2 / 720
+    (their next terms are below 1e-25 there).  Below 1e-7 it inverts what se3_exp's small-angle
+    branch really applies, dR = I + wx + wx^2 / 2 and V = I + wx / 2 + fl64(1 / 3) wx^2 (the
+    reference's coefficient; the limit of the closed form is 1 / 6): w = vee(dR - dR^T) / 2 and
+    k = 1 / 4 - fl64(1 / 3), next term theta^3 |dt|."""
+    dR, dt = np.asarray(dR, LD), np.asarray(dt, LD)
+    a = np.stack([dR[:, 2, 1] - dR[:, 1, 2], dR[:, 0, 2] - dR[:, 2, 0], dR[:, 1, 0] - dR[:, 0, 1]], 1)
+    sn = np.sqrt((a * a).sum(axis=1)) / 2
+    cs = (dR[:, 0, 0] + dR[:, 1, 1] + dR[:, 2, 2] - 1) / 2
+    th = np.arctan2(sn, cs)
+    small = th < LD(1e-6)
+    ths = np.where(small, LD(1), th)
+    sns = np.where(small, LD(1), sn)
+    hf = ths / 2
+    f = np.where(small, (1 + th * th / 6) / 2, ths / (2 * sns))
+    k = np.where(small, LD(1) / 12 + th * th / 720, (1 - hf * np.cos(hf) / np.sin(hf)) / (ths * ths))
+    tiny = th < LD(1e-7)
+    f = np.where(tiny, LD(1) / 2, f)
+    k = np.where(tiny, LD(1) / 4 - LD(np.float64(0.33333333333333333333333333)), k)
+    w = a * f[:, None]
+    c = np.cross(w, dt)
+    e = np.cross(w, c)
+    return dt - c / 2 + e * k[:, None], w
+
+
+def recover_step(pr, st, poses, points):
+    """(x (N, 6), y (M, 3)) in long double: the step that takes the problem's own parameters to
+    `poses`, `points`: x_j = se3_log(T'_j T_j^-1) (T_j^-1 the inverse of the stored matrix, which
+    is orthogonal to rounding only), y_i = X'_i - X_i."""
+    T0 = np.asarray(pr["pose_T"], LD)[st.pose_of_j]
+    T1 = np.asarray(poses, LD)[st.pose_of_j]
+    R0i = pinv3(T0[:, :9].reshape(-1, 3, 3), LD, newton=3)[0]
+    dR = T1[:, :9].reshape(-1, 3, 3) @ R0i
+    dt = T1[:, 9:] - np.einsum("nij,nj->ni", dR, T0[:, 9:])
+    v, w = se3_log(dR, dt)
+    y = np.asarray(points, LD)[st.pt_of_i] - np.asarray(pr["pt_X"], LD)[st.pt_of_i]
+    return np.concatenate([v, w], 1), y
+
+
+def _units_max(res):
+    z = res.s == 0
+    if z.all():
+        return 0.0
+    return float((np.abs(res.v[~z]) / (LD(U) * res.s[~z])).max())
+
+
+def full_system_units(pr, st, lam, huber, poses, points, lin=None):
+    """(pose rows, landmark rows): how well the step from the problem's parameters to `poses`,
+    `points` solves the damped normal equations of the problem, linearised in long double at its
+    own parameters: max |a_j - A_j x_j - sum_i B_ji y_i| / (u (|a| + |A||x| + |B||y|)) and
+    max |b_i - sum_j B_ji^T x_j - C_i y_i| / (u (|b| + |B^T||x| + |C||y|)), A and C damped by
+    fl64(1 + lam), the magnitudes carried by VS.  A row whose scale is 0 (a landmark nobody
+    observes, C_i = 0) has no equation: its parameters must be bit-equal to the input, as those
+    of fixed poses and fixed points must.  `lin`: linearize(pr, st, huber, lam, LD), if at hand."""
+    poses, points = np.asarray(poses, np.float64), np.asarray(points, np.float64)
+    assert np.isfinite(poses).all() and np.isfinite(points).all()
+    fp, fq = pr["pose_fixed"] != 0, pr["pt_fixed"] != 0
+    assert np.array_equal(poses[fp], pr["pose_T"][fp]) and np.array_equal(points[fq], pr["pt_X"][fq])
+    lin = linearize(pr, st, huber, lam, LD) if lin is None else lin
+    xv, yv = recover_step(pr, st, poses, points)
+    x, y, B = VS(xv), VS(yv), lin["B"]
+    By = scatter(ein("pkc,pc->pk", B, y[st.pair_i]), st.pair_j, st.N)
+    rp = lin["a"] - ein("nrc,nc->nr", lin["A"], x) - By
+    rl = lin["b"] - _Btx(B, st.pair_i, st.pair_j, x, st.M) - ein("nrc,nc->nr", lin["C"], y)
+    for res, idx, new, old in ((rp, st.pose_of_j, poses, pr["pose_T"]), (rl, st.pt_of_i, points, pr["pt_X"])):
+        none = (res.s == 0).all(axis=1)
+        assert np.array_equal(new[idx[none]], old[idx[none]]), "a parameter block without an equation moved"
+    return _units_max(rp), _units_max(rl)
+
+
+def yardstick_step(pr, st, lam, huber):
+    """(poses, points) after one step of xp_ref's own float64 chain: linearize -> pinv3 -> schur
+    -> LAPACK -> backsub -> update."""
+    f64 = np.float64
+    lin = linearize(pr, st, huber, lam, f64)
+    Cinv = pinv3(lin["C"].v, f64)[0]
+    S, rhs = schur(lin["A"].v, lin["a"].v, lin["B"].v, st.pair_i, st.pair_j, Cinv, lin["b"].v, f64)[:2]
+    x = lapack_solve(S.v, rhs.v).reshape(-1, 6)
+    y = backsub(Cinv, lin["b"].v, lin["B"].v, st.pair_i, st.pair_j, x, f64).v
+    P, Xn = update(pr, st, x, y, f64)
+    return P.v, Xn.v
+
+
+def only_landmarks(pr, landmarks):
+    """The problem with the observations of the points in the boolean mask `landmarks` only."""
+    keep = np.asarray(landmarks, bool)[pr["obs_pt"]]
+    out = dict(pr)
+    for k in ("obs_cam", "obs_pose", "obs_pt", "obs_uv"):
+        out[k] = np.ascontiguousarray(np.asarray(pr[k])[keep])
+    return out
+
+
+def reduced_system(pr, st, huber, dt, landmarks):
+    """(S (6N, 6N) VS, rhs (6N,) VS, n_terms, n_terms_rhs) of the reduced camera system at lambda 0
+    over the observations of the landmarks in the boolean mask `landmarks` (one flag per point:
+    the set L ba_batch_marginalize reports; observations of fixed points, which are never in L, are
+    left out, as its header says): linearize -> pinv3 -> schur, all in `dt`.  The scale of an
+    element of S is |A| + |B||Cinv||B^T| of the values of that chain.  That of rhs is
+    s(a) + |B||Cinv| s(b) with the scales s(a), s(b) the linearisation carries: a and b are sums of
+    J^T w r, and r = projection + c - measurement cancels (to 1e-9 of its terms on the small-step
+    scene), so |a| and |b| are no measure of the rounding error any evaluation of them commits; A, B
+    and C hold no residual."""
+    assert not (np.asarray(landmarks, bool) & (pr["pt_fixed"] != 0)).any()
+    sub = only_landmarks(pr, landmarks)
+    ss = Structure(sub)
+    assert (ss.N, ss.M) == (st.N, st.M)
+    lin = linearize(sub, ss, huber, 0.0, dt)
+    Cinv = pinv3(lin["C"].v, dt)[0]
+    args = (lin["B"].v, ss.pair_i, ss.pair_j, Cinv)
+    S, rhs, nS, nr = schur(lin["A"].v, lin["a"].v, *args, lin["b"].v, dt)
+    rhs_scale = schur(lin["A"].v, lin["a"].s, *args, lin["b"].s, dt)[1].s
+    return S, VS(rhs.v, rhs_scale), nS, nr
+
+
+def reduced_reference(pr, st, huber, landmarks):
+    """reduced_system in long double and in float64 (its yardstick), for reduced_figures."""
+    return reduced_system(pr, st, huber, LD, landmarks) + reduced_system(pr, st, huber, np.float64, landmarks)[:2]
+
+
+def reduced_figures(H, bvec, ref):
+    """The lower triangle of H and bvec against `ref` = reduced_reference(...): dict of
+    "S", "rhs": (e, e64) in rounding units, "S cap", "rhs cap": (max(e - n_terms), SUM_CAP);
+    elements without a term must be exactly 0 (units_array)."""
+    S, rhs, nS, nr, S64, rhs64 = ref
+    low = np.tril(np.ones(S.v.shape, bool))
+    out = {}
+    for k, dev, r, y64, nt in (("S", np.asarray(H)[low], S[low], S64.v[low], nS[low]),
+                               ("rhs", np.asarray(bvec), rhs, rhs64.v, nr)):
+        e = units_array(dev, r)
+        out[k] = (float(e.max()), rounding_units(y64, r))
+        out[k + " cap"] = (float((e - nt).max()), float(SUM_CAP))
+    return out
+
+
+def reduced_failures(fig):
+    bad = []
+    for k in ("S", "rhs"):
+        if not within(*fig[k]):
+            bad.append("%s: e = %.3g > 8 max(e64 = %.3g, 1)" % ((k,) + fig[k]))
+        if fig[k + " cap"][0] > fig[k + " cap"][1]:
+            bad.append("%s: e - n_terms = %.3g > %g" % ((k,) + fig[k + " cap"]))
+    return bad
