@@ -503,9 +503,9 @@ __device__ __forceinline__ void batch_rel_lin(const BatchRelDev &d, const int N,
     const double *Om = v.Om + (size_t)f * 36;
     double *s = v.scr + (size_t)f * kRelScr;
     if (q < 36)
-      s[kRelOA + q] = rel_OA(Om, s + kRelAd, q);
+      s[kRelOA + q] = factor_OA<6>(Om, s + kRelAd, q);
     else
-      s[kRelOr + q - 36] = rel_Or(Om, s + kRelR, q - 36);
+      s[kRelOr + q - 36] = factor_Or<6>(Om, s + kRelR, q - 36);
   }
   __syncthreads();
   // Bk = Ad^T OA and gk = Ad^T Or, one thread per element
@@ -515,9 +515,9 @@ __device__ __forceinline__ void batch_rel_lin(const BatchRelDev &d, const int N,
     if (jk.w < 0 || !rel_on(jk, on)) continue;
     double *s = v.scr + (size_t)f * kRelScr;
     if (q < 36)
-      s[kRelBk + q] = rel_Bk(s + kRelAd, s + kRelOA, q);
+      s[kRelBk + q] = factor_Bk<6>(s + kRelAd, s + kRelOA, q);
     else
-      s[kRelGk + q - 36] = rel_gk(s + kRelAd, s + kRelOr, q - 36);
+      s[kRelGk + q - 36] = factor_gk<6>(s + kRelAd, s + kRelOr, q - 36);
   }
   __syncthreads();
   // gather: one thread per element of A_j and a_j, the pose's factors in input order
@@ -562,7 +562,7 @@ __device__ __forceinline__ double batch_rel_cost(const BatchRelDev &d, const int
     double RE[9], tE[3], r[6];
     rel_E(v.jk[f], P, RE, tE);
     rel_log(RE, tE, v.Z + (size_t)f * 12, r);
-    acc += sqrt(fmax(0.0, rel_quad(v.Om + (size_t)f * 36, r)));
+    acc += sqrt(fmax(0.0, factor_quad<6>(v.Om + (size_t)f * 36, r)));
   }
   return block_sum(acc, red);
 }

@@ -1,5 +1,5 @@
 // ba_cov_sweep.h — the forward sweep of the covariance kernels, once: k_cov_solve<NB>
-// (ba_cov.hip, the handle path) and k_pgcov_solve<NB> (ba_pgraph_cov.hip, the pose graph)
+// (ba_cov.hip, the handle path) and k_graph_cov_solve<G, NB> (ba_graph_kernels.hip, the pose graphs)
 // call it and differ only in what they do with the Gram matrix.  Device only, forced inline.
 #ifndef BA_COV_SWEEP_H_
 #define BA_COV_SWEEP_H_

@@ -325,7 +325,7 @@ void launch_rel_gather(const DevProblem &d, const RelDev &r, int sel, int flags,
 // S_jk += -Omega Ad of every coupled block into Spk (direct: and into the dense image)
 void launch_rel_offdiag(const DevProblem &d, const RelDev &r, bool direct, hipStream_t s);
 
-// ---- pose-graph optimisation (ba_pgraph.hip, ba_pgraph_*) ----
+// ---- pose-graph optimisation (ba_graph_kernels.hip, ba_pgraph_*) ----
 // LM over relative-pose factors alone: chi2 = sum_f r_f^T Omega_f r_f, no landmark in the
 // problem.  The controller lives on the device, as DevCtrl does for the handle path, so that
 // max_num_iterations iterations are enqueued without a host round trip; `done` is the control
@@ -377,55 +377,41 @@ struct PgRobust {
   const double *scale;    // per factor: c (a Mahalanobis distance); unread where kind is 0
   double *s, *w;          // per factor: s = r^T Omega r and w = rho'(s) of the pass that wrote them
 };
+// The launchers of the graph kernels (ba_graph_kernels.hip), one template per kernel, instantiated
+// there for the two groups of ba_graph_fn.h; W is the group's tangent width.
+struct Se3Graph;
+struct Sim3Graph;
 // cost_only = 0: linearise at the accepted poses (records + part[0]; skipped while !ctrl->relin);
 // 1: chi-square partials at the trial poses -> part[1]; 2: at the accepted poses -> part[1]
-void launch_pg_lin(const PgDev &p, int cost_only, hipStream_t s);
+template <class G>
+void launch_graph_lin(const PgDev &p, int cost_only, hipStream_t s);
 // the same with sum rho(s) for chi-square and w Omega for Omega; rb.s and rb.w are written by
 // cost_only = 0 (they belong to the records) and by cost_only = 3 (= 2 plus the report)
-void launch_pg_lin_robust(const PgDev &p, const PgRobust &rb, int cost_only, hipStream_t s);
-void launch_pg_assemble_robust(const PgDev &p, const PgRobust &rb, double *Hout, double *gout, hipStream_t s);
-// H + lambda diag(H) and g into the image (Hout == nullptr), or the undamped H (6N x 6N,
+template <class G>
+void launch_graph_lin_robust(const PgDev &p, const PgRobust &rb, int cost_only, hipStream_t s);
+// H + lambda diag(H) and g into the image (Hout == nullptr), or the undamped H (W N x W N,
 // both triangles) and g into Hout / gout
-void launch_pg_assemble(const PgDev &p, double *Hout, double *gout, hipStream_t s);
-void launch_pg_trial(const PgDev &p, hipStream_t s);
+template <class G>
+void launch_graph_assemble(const PgDev &p, double *Hout, double *gout, hipStream_t s);
+template <class G>
+void launch_graph_assemble_robust(const PgDev &p, const PgRobust &rb, double *Hout, double *gout, hipStream_t s);
+template <class G>
+void launch_graph_trial(const PgDev &p, hipStream_t s);
 // mode 0: the trust-region step of one iteration; 1: ctrl->aux = sum of part[1]
 void launch_pg_control(const PgDev &p, int mode, hipStream_t s);
 
-// ---- Sim(3) pose graph (ba_sim3.hip, ba_sim3_*) ----
+// ---- Sim(3) pose graph (ba_graph_kernels.hip, ba_sim3_*) ----
 // The 7-DoF graph has the pose graph's device record and controller: PgDev with 13 doubles per
 // pose (R, t, s), 62 per factor in val (Z 13, Omega 49 mirrored), kS3Rec per factor in rec, and
 // 7N where PgDev says 6N.  k_pg_control knows nothing of a pose's width and runs as it is, and so
-// does the host driver (ba_graph.hip): the widths and the launchers below are the Sim(3) kind's
-// GraphSpec in ba_sim3.hip.
+// does the host driver (ba_graph.hip): the widths and the launchers above at Sim3Graph are the
+// Sim(3) kind's GraphSpec in ba_sim3.hip.
 constexpr int kS3Fpb = 32;   // factors per k_s3_lin workgroup
 constexpr int kS3Rec = 112;  // record of one factor: Omega r (7), Ad^T Omega r (7), Omega Ad (49), Ad^T Omega Ad (49)
 constexpr int kS3Or = 0, kS3Gk = 7, kS3OA = 14, kS3Bk = 63;
-// cost_only = 0: linearise at the accepted poses (records + part[0]; skipped while !ctrl->relin);
-// 1: chi-square partials at the trial poses -> part[1]; 2: at the accepted poses -> part[1];
-// rep != nullptr: also s_f = r^T Omega r per factor into rep
+// launch_graph_lin<Sim3Graph> with rep != nullptr: also s_f = r^T Omega r per factor into rep
+// (ba_sim3_factor_report)
 void launch_s3_lin(const PgDev &p, int cost_only, double *rep, hipStream_t s);
-// H + lambda diag(H) and g into the image (Hout == nullptr), or the undamped H (7N x 7N, both
-// triangles) and g into Hout / gout
-void launch_s3_assemble(const PgDev &p, double *Hout, double *gout, hipStream_t s);
-void launch_s3_trial(const PgDev &p, hipStream_t s);
-// Robust kernels on Sim(3) factors (ba_sim3_set_robust): k_s3_lin written out a
-// second time and the assembly's body instantiated a second time, with sum rho(s) for chi-square
-// and w Omega for Omega; PgRobust is their extra argument as it is the SE(3) graph's.  rb.s and rb.w are written by cost_only = 0 (they belong
-// to the records) and by cost_only = 3 (= 2 plus the report).
-void launch_s3_lin_robust(const PgDev &p, const PgRobust &rb, int cost_only, hipStream_t s);
-void launch_s3_assemble_robust(const PgDev &p, const PgRobust &rb, double *Hout, double *gout, hipStream_t s);
-
-// ---- covariance blocks and the gate of a Sim(3) graph (ba_sim3_cov.hip) ----
-// launch_pgcov_batch at width 7: 49 doubles per block, 7 per residual, cand_val 62 doubles per
-// candidate (ba_sim3_host.h), poses 13 doubles each.  The groups are the pose graph's, and the
-// caller is the same graph_cov_run of ba_graph.hip, which fills S3CovOut from its six pointers.
-struct PgCovGroup;
-struct S3CovOut {
-  double *pose49, *cross49, *rel49, *r7, *innov49, *d2;
-};
-void launch_s3cov_batch(const PgDev &p, const double *Ldiag, int nb, int ncb, const double *poses,
-                        const int *trow_ptr, const int *trow, const PgCovGroup *groups, int ng,
-                        const double *cand_val, double *Zw, int bw, const S3CovOut &out, hipStream_t s);
 
 // ---- gradient descent (FullBundleAdjustmentSolverRefactor::SolveByGradientDescent) ----
 // Device state of the first-order loop (ba_gd_*), allocated on the first GD call after
@@ -526,21 +512,24 @@ void launch_cov_batch(const DevProblem &d, int lcur, int cur, int ncb, const int
                       const CovGroup *groups, int ng, double *Zw, int bw, double *out_pose,
                       double *out_pt, hipStream_t s);
 
-// ---- covariance blocks and the gate of a pose graph (ba_pgraph_cov.hip) ----
+// ---- covariance blocks and the gate of a pose graph (ba_graph_kernels.hip) ----
 struct PgCovGroup;  // ba_pgraph_host.h: one wave's two poses, pair or candidate
-// Device outputs of one call: pose36 per distinct selected pose; rel36 (Sigma_E), cross36
-// (Sigma_jk, or null: not asked for) per pair or candidate; r6 / innov36 (or null) and d2 per candidate.
-struct PgCovOut {
-  double *pose36, *cross36, *rel36, *r6, *innov36, *d2;
+// Device outputs of one call, W x W doubles per block and W per residual: pose per distinct selected
+// pose; rel (Sigma_E), cross (Sigma_jk, or null: not asked for) per pair or candidate; r / innov
+// (or null) and d2 per candidate.
+struct GraphCovOut {
+  double *pose, *cross, *rel, *r, *innov, *d2;
 };
 // One column batch on the factored image of the graph (p.L, Ldiag; lambda = 0): zero the workspace
 // Zw (p.npad x bw doubles, row-major, bw = 16 ng), place the identity columns, sweep, write the
-// blocks.  poses: the accepted pose buffer; cand_val: 48 doubles per candidate (ba_rel_host.h) or
-// null; trow_ptr / trow as for launch_cov_batch.  Enqueue only.  (Called by graph_cov_run of
-// ba_graph.hip through the SE(3) kind's GraphSpec, which fills PgCovOut from its six pointers.)
-void launch_pgcov_batch(const PgDev &p, const double *Ldiag, int nb, int ncb, const double *poses,
-                        const int *trow_ptr, const int *trow, const PgCovGroup *groups, int ng,
-                        const double *cand_val, double *Zw, int bw, const PgCovOut &out, hipStream_t s);
+// blocks.  poses: the accepted pose buffer; cand_val: the group's doubles per candidate as its
+// pack_values lays them out (ba_rel_host.h, ba_sim3_host.h) or null; trow_ptr / trow as for
+// launch_cov_batch.  Enqueue only.  (Called by graph_cov_run of ba_graph.hip through the kind's
+// GraphSpec.)
+template <class G>
+void launch_graph_cov_batch(const PgDev &p, const double *Ldiag, int nb, int ncb, const double *poses,
+                            const int *trow_ptr, const int *trow, const PgCovGroup *groups, int ng,
+                            const double *cand_val, double *Zw, int bw, const GraphCovOut &out, hipStream_t s);
 
 // ---- pose-only (ba_pose_only.hip) ----
 struct PoIter {

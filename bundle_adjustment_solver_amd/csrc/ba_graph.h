@@ -47,12 +47,6 @@ struct GraphHost {
   std::vector<void *> allocs;
 };
 
-// The device outputs of one covariance batch, W x W doubles per block and W per residual: what
-// the cov-batch launcher of a kind puts into its kernels' argument struct (PgCovOut, S3CovOut).
-struct GraphCovOut {
-  double *pose, *cross, *rel, *r, *innov, *d2;
-};
-
 // One kind of graph.  Everything the driver has to know about the kind is a field here; the
 // driver never asks which kind it serves.
 struct GraphSpec {

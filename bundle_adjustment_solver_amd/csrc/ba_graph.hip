@@ -1,8 +1,8 @@
 // ba_graph.hip — the host driver of the pose graphs (ba_graph.h): creation
 // and the device set-up, the LM loop, the passes outside it, the robust arrays, and the
 // covariance / gate driver (§6m, §6p), once for the SE(3) graph (ba_pgraph_*) and the Sim(3) graph
-// (ba_sim3_*).  Host code only: the kernels and their launchers are in ba_pgraph.hip /
-// ba_pgraph_cov.hip and ba_sim3.hip / ba_sim3_cov.hip, and reach this file through a GraphSpec.
+// (ba_sim3_*).  Host code only: the kernels and their launchers are in ba_graph_kernels.hip, and
+// reach this file through the GraphSpec of a kind (ba_pgraph.hip, ba_sim3.hip).
 #include <cstddef>
 #include <cstring>
 

@@ -133,8 +133,8 @@ inline void pgraph_tile_adjacency(const PgraphLists &l, int poses_per_tile, int 
 // ---- DESIGN.md §6m) -------------------------------------------------------------------------
 
 // Cholesky of the W x W matrix (W <= 7) whose lower triangle is in O (row-major); false at a
-// pivot that is not positive (or not finite).  The same loop as the device's (ba_pgraph_cov.hip,
-// ba_sim3_cov.hip).
+// pivot that is not positive (or not finite).  The same loop as the device's (cholw of
+// ba_graph_kernels.hip).
 inline bool chol_host(const double *O, int W) {
   double L[49];
   for (int c = 0; c < W; ++c) {
@@ -223,7 +223,7 @@ inline int pgraph_cov_validate_host(int n_pose, const uint8_t *pose_fixed, int n
                                  pair_k, cov_rel36, n_cand, cand_j, cand_k, Z12, Omega36, d2, err);
 }
 
-// One wave of k_pgcov_solve owns 16 right-hand sides: the six identity columns of the pose
+// One wave of k_graph_cov_solve owns 16 right-hand sides: the six identity columns of the pose
 // opt[0] in its columns 0..5 and of opt[1] in 6..11 (optimisable indices; -1: no column, the
 // blocks of that member are zero).  kind 0: two selected poses, slot[a] = row of the pose
 // output; kind 1: the pair (j, k) = (pose[0], pose[1]), slot[0] = row of the pair outputs;

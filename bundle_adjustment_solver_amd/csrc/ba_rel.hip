@@ -41,7 +41,7 @@ __global__ __launch_bounds__(kRelBlock) void k_rel_lin(DevProblem d, RelDev r, i
     rel_E(jk, P, RE, tE);
     const double *Z = val + (size_t)tid * 48, *Om = Z + 12;
     rel_log(RE, tE, Z, rr);
-    cost = sqrt(fmax(0.0, rel_quad(Om, rr)));
+    cost = sqrt(fmax(0.0, factor_quad<6>(Om, rr)));
     if (mode & 1) {  // r and Ad
       double *s = scr + (size_t)tid * kRelScr;
       rel_Ad(RE, tE, s + kRelAd);
@@ -57,9 +57,9 @@ __global__ __launch_bounds__(kRelBlock) void k_rel_lin(DevProblem d, RelDev r, i
       const double *Om = val + (size_t)f * 48 + 12;
       double *s = scr + (size_t)f * kRelScr;
       if (q < 36)
-        s[kRelOA + q] = rel_OA(Om, s + kRelAd, q);
+        s[kRelOA + q] = factor_OA<6>(Om, s + kRelAd, q);
       else
-        s[kRelOr + q - 36] = rel_Or(Om, s + kRelR, q - 36);
+        s[kRelOr + q - 36] = factor_Or<6>(Om, s + kRelR, q - 36);
     }
     __syncthreads();
     // Bk = Ad^T OA and gk = Ad^T Or, for the factors whose k is optimisable
@@ -68,9 +68,9 @@ __global__ __launch_bounds__(kRelBlock) void k_rel_lin(DevProblem d, RelDev r, i
       if (r.jk[f0 + f].w < 0) continue;
       double *s = scr + (size_t)f * kRelScr;
       if (q < 36)
-        s[kRelBk + q] = rel_Bk(s + kRelAd, s + kRelOA, q);
+        s[kRelBk + q] = factor_Bk<6>(s + kRelAd, s + kRelOA, q);
       else
-        s[kRelGk + q - 36] = rel_gk(s + kRelAd, s + kRelOr, q - 36);
+        s[kRelGk + q - 36] = factor_gk<6>(s + kRelAd, s + kRelOr, q - 36);
     }
   }
   block_sum2(cost, cross, sm);

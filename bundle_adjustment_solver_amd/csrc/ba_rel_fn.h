@@ -11,6 +11,7 @@
 #define BA_REL_FN_H_
 
 #include "ba_device_fn.h"
+#include "ba_factor_fn.h"
 
 namespace ba {
 
@@ -60,48 +61,9 @@ __device__ __forceinline__ void rel_Ad(const double RE[9], const double tE[3], d
   }
 }
 
-// r^T Omega r
-__device__ __forceinline__ double rel_quad(const double *Om, const double r[6]) {
-  double q = 0.0;
-#pragma unroll
-  for (int a = 0; a < 6; ++a) {
-    double row = 0.0;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) row += Om[a * 6 + c] * r[c];
-    q += r[a] * row;
-  }
-  return q;
-}
-
-// The per-element threads take element e < 42 of a pair {6x6 block, 6-vector}: q = e < 36 of
-// the block, else a = e - 36 of the vector.  Each caller keeps that branch, with its stores in it.
-// element q of OA = Omega Ad and element a of Or = Omega r
-__device__ __forceinline__ double rel_OA(const double *Om, const double *Ad, const int q) {
-  const int a = q / 6, c = q - 6 * a;
-  double acc = 0.0;
-  for (int m = 0; m < 6; ++m) acc += Om[a * 6 + m] * Ad[m * 6 + c];
-  return acc;
-}
-__device__ __forceinline__ double rel_Or(const double *Om, const double *r, const int a) {
-  double acc = 0.0;
-  for (int m = 0; m < 6; ++m) acc += Om[a * 6 + m] * r[m];
-  return acc;
-}
-
-// element q of Bk = Ad^T OA, from the expression of its lower-triangle twin, so that Bk is
-// symmetric to the bit, and element a of gk = Ad^T Or
-__device__ __forceinline__ double rel_Bk(const double *Ad, const double *OA, const int q) {
-  const int r0 = q / 6, c0 = q - 6 * r0;
-  const int a = r0 > c0 ? r0 : c0, c = r0 > c0 ? c0 : r0;
-  double acc = 0.0;
-  for (int m = 0; m < 6; ++m) acc += Ad[m * 6 + a] * OA[m * 6 + c];
-  return acc;
-}
-__device__ __forceinline__ double rel_gk(const double *Ad, const double *Or, const int a) {
-  double acc = 0.0;
-  for (int m = 0; m < 6; ++m) acc += Ad[m * 6 + a] * Or[m];
-  return acc;
-}
+// (r^T Omega r and the elements of Omega Ad, Omega r, Ad^T Omega Ad, Ad^T Omega r that the
+// per-element threads take are factor_quad / factor_OA / factor_Or / factor_Bk / factor_gk of
+// ba_factor_fn.h at width 6; factor_Bk holds the rule that keeps Ad^T Omega Ad symmetric to the bit)
 
 // the cross term 2 x_j^T H_jk x_k = -2 x_j^T OA x_k of the quadratic model
 __device__ __forceinline__ double rel_cross(const double *OA, const double *xj, const double *xk) {
@@ -116,7 +78,7 @@ __device__ __forceinline__ double rel_cross(const double *OA, const double *xj, 
 
 // The two list walks of the handle and batch paths, whose factors keep the kRelScr record in scr and
 // Omega (36 per factor) every om_s doubles of Om.  skip(f): the factor does not join; *any: one did.
-// (k_pg_assemble keeps both written out, its own record and the robust weight in them: these measured slower.)
+// (k_graph_assemble keeps both written out, its own record and the robust weight in them: these measured slower.)
 // Element q < 42 of {H_jj, g_j} of one optimisable pose: its list entries [l0, l1)
 // (factor << 1 | (1: it is the factor's k)) in input order.
 template <class Skip>

@@ -15,6 +15,8 @@
 #include <cmath>
 #include <cstddef>
 
+#include "ba_factor_fn.h"
+
 #if defined(__HIPCC__)
 #define BA_S3_FN __host__ __device__ __forceinline__
 #else
@@ -214,48 +216,8 @@ BA_S3_FN void sim3_Ad(const double E[13], double *Ad) {
   Ad[48] = 1.0;
 }
 
-// r^T Omega r
-BA_S3_FN double sim3_quad(const double *Om, const double r[7]) {
-  double q = 0.0;
-#pragma unroll
-  for (int a = 0; a < 7; ++a) {
-    double row = 0.0;
-#pragma unroll
-    for (int c = 0; c < 7; ++c) row += Om[a * 7 + c] * r[c];
-    q += r[a] * row;
-  }
-  return q;
-}
-
-// The per-element threads take element e < 56 of a pair {7x7 block, 7-vector}: q = e < 49 of
-// the block, else a = e - 49 of the vector.  The products are dense: the zeros of Ad7 are added
-// as zeros, so that a sparse form would have to give these bits.
-// element q of OA = Omega Ad and element a of Or = Omega r
-BA_S3_FN double sim3_OA(const double *Om, const double *Ad, const int q) {
-  const int a = q / 7, c = q - 7 * a;
-  double acc = 0.0;
-  for (int m = 0; m < 7; ++m) acc += Om[a * 7 + m] * Ad[m * 7 + c];
-  return acc;
-}
-BA_S3_FN double sim3_Or(const double *Om, const double *r, const int a) {
-  double acc = 0.0;
-  for (int m = 0; m < 7; ++m) acc += Om[a * 7 + m] * r[m];
-  return acc;
-}
-// element q of Bk = Ad^T OA, from the expression of its lower-triangle twin, so that Bk is
-// symmetric to the bit, and element a of gk = Ad^T Or
-BA_S3_FN double sim3_Bk(const double *Ad, const double *OA, const int q) {
-  const int r0 = q / 7, c0 = q - 7 * r0;
-  const int a = r0 > c0 ? r0 : c0, c = r0 > c0 ? c0 : r0;
-  double acc = 0.0;
-  for (int m = 0; m < 7; ++m) acc += Ad[m * 7 + a] * OA[m * 7 + c];
-  return acc;
-}
-BA_S3_FN double sim3_gk(const double *Ad, const double *Or, const int a) {
-  double acc = 0.0;
-  for (int m = 0; m < 7; ++m) acc += Ad[m * 7 + a] * Or[m];
-  return acc;
-}
+// (r^T Omega r and the elements of Omega Ad7, Omega r, Ad7^T Omega Ad7, Ad7^T Omega r that the
+// per-element threads take are factor_quad / ... / factor_gk of ba_factor_fn.h at width 7)
 
 }  // namespace ba
 #endif  // BA_SIM3_FN_H_

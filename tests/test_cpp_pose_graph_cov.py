@@ -25,7 +25,7 @@ def test_covariance_surface_is_declared_and_hooked_into_the_makefiles():
                  "int ba_pgraph_cov_check(int n_pose", "int ba_pgraph_cov_info(ba_pgraph *g"):
         assert name in abi, name
     lib_mk = open(os.path.join(ROOT, "bundle_adjustment_solver_amd", "csrc", "Makefile")).read()
-    assert "ba_pgraph_cov.o" in lib_mk and "dbg/ba_pgraph_cov.o" in lib_mk
+    assert "ba_graph_kernels.o" in lib_mk and "dbg/ba_graph_kernels.o" in lib_mk
 
 
 @pytest.mark.gpu

@@ -25,7 +25,7 @@ def test_the_calls_are_declared_and_hooked_into_the_makefiles():
     mk = open(os.path.join(CPP, "Makefile")).read()
     assert "build/test_sim3_robust_cov:" in mk and "all: build/test_sim3_robust_cov\n" in mk
     lib_mk = open(os.path.join(ROOT, "bundle_adjustment_solver_amd", "csrc", "Makefile")).read()
-    assert "ba_sim3_cov.o" in lib_mk and "ba_robust_fn.h" in lib_mk
+    assert "ba_graph_kernels.o" in lib_mk and "ba_robust_fn.h" in lib_mk
     abi = open(os.path.join(ROOT, "include", "ba_hip.h")).read()
     for name in ("int ba_sim3_set_robust(ba_sim3 *g", "int ba_sim3_robust_check(int64_t n_rel",
                  "int ba_sim3_factor_weights(ba_sim3 *g", "int ba_sim3_covariance(ba_sim3 *g",

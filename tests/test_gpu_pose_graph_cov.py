@@ -1,6 +1,6 @@
 """GPU tests of the pose graph's covariance blocks and chi-square gate (ba_pgraph_covariance,
 ba_pgraph_gate, BaPoseGraph.covariance / gate, ComputePoseGraphCovariance / GateLoopClosures;
-k_pgcov_rhs and k_pgcov_solve<32|64> of csrc/ba_pgraph_cov.hip).
+k_graph_cov_rhs and k_graph_cov_solve<Se3Graph, 32|64> of csrc/ba_graph_kernels.hip).
 
 Reference: pgo_cov_ref (numpy / scipy fp64) on the seeded scenes of pgo_cases.py, at the start
 poses and after the scene's own solve, at the poses the object holds.  test_pgo_cov_ref.py pins

@@ -1,6 +1,6 @@
 """GPU tests of the Sim(3) graph's covariance blocks and 7-DoF chi-square gate (ba_sim3_covariance,
-ba_sim3_gate, BaSim3Graph.covariance / gate; k_s3cov_rhs and k_s3cov_solve<32|64> of
-csrc/ba_sim3_cov.hip).
+ba_sim3_gate, BaSim3Graph.covariance / gate; k_graph_cov_rhs and k_graph_cov_solve<Sim3Graph, 32|64> of
+csrc/ba_graph_kernels.hip).
 
 Reference: sim3_cov_ref (numpy / scipy fp64) on the seeded scenes of sim3_cases.py and
 sim3_robust_cases.py, at the start poses and after the scene's own solve, at the poses the object

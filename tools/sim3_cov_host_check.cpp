@@ -68,7 +68,7 @@ int main() {
       }
   std::printf("rho and w against long double: %.2e relative\n", worst);
   EXPECT(worst <= 1e-14);
-  // ---- chol7
+  // ---- chol_host at width 7
   std::mt19937 gen(7);
   std::normal_distribution<double> N(0.0, 1.0);
   double O[49], worst_c = 0.0;

@@ -104,10 +104,10 @@ static int check_arithmetic() {
   ba::sim3_exp(xe, E);
   ba::sim3_Ad(E, Ad);
   double quad = 0.0;
-  for (int q = 0; q < 49; ++q) OA[q] = ba::sim3_OA(Om, Ad, q);
-  for (int a = 0; a < 7; ++a) Or[a] = ba::sim3_Or(Om, r7, a);
+  for (int q = 0; q < 49; ++q) OA[q] = ba::factor_OA<7>(Om, Ad, q);
+  for (int a = 0; a < 7; ++a) Or[a] = ba::factor_Or<7>(Om, r7, a);
   for (int a = 0; a < 7; ++a) quad += r7[a] * Or[a];
-  REQUIRE(std::fabs(quad - ba::sim3_quad(Om, r7)) <= 1e-12 * std::fabs(quad));
+  REQUIRE(std::fabs(quad - ba::factor_quad<7>(Om, r7)) <= 1e-12 * std::fabs(quad));
   for (int q = 0; q < 49; ++q) {
     const int a = q / 7, c = q % 7;
     double v = 0.0, vt = 0.0;
@@ -115,14 +115,14 @@ static int check_arithmetic() {
       v += Ad[7 * m + a] * OA[7 * m + c];
       vt += Ad[7 * m + c] * OA[7 * m + a];
     }
-    REQUIRE(std::fabs(ba::sim3_Bk(Ad, OA, q) - v) <= 1e-12 * (1.0 + std::fabs(v)));
-    REQUIRE(ba::sim3_Bk(Ad, OA, q) == ba::sim3_Bk(Ad, OA, 7 * c + a));  // symmetric to the bit
+    REQUIRE(std::fabs(ba::factor_Bk<7>(Ad, OA, q) - v) <= 1e-12 * (1.0 + std::fabs(v)));
+    REQUIRE(ba::factor_Bk<7>(Ad, OA, q) == ba::factor_Bk<7>(Ad, OA, 7 * c + a));  // symmetric to the bit
     (void)vt;
   }
   for (int a = 0; a < 7; ++a) {
     double v = 0.0;
     for (int m = 0; m < 7; ++m) v += Ad[7 * m + a] * Or[m];
-    REQUIRE(ba::sim3_gk(Ad, Or, a) == v);
+    REQUIRE(ba::factor_gk<7>(Ad, Or, a) == v);
   }
   return 0;
 }
