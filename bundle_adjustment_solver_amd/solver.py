@@ -10,6 +10,7 @@ Everything numerical happens in libba_hip.so (include/ba_hip.h); this module
 only does what the reference's facade does on the host: pointer(identity)->
 index maps, the 0.01 scaling, pose inversion and the final write-back.
 """
+import collections
 import ctypes as C
 import enum
 import sys
@@ -1818,6 +1819,12 @@ class _BaGraph:
         self._call(entry, self.g, _dp(s), _dp(w))
         return s, w
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
     def close(self):
         if self.g:
             getattr(self.lib, self._abi + "_destroy")(self.g)
@@ -2113,6 +2120,19 @@ class BaStream:
         check(self.lib.ba_stream_info(self.h, v), "ba_stream_info")
         return dict(arena_bytes=v[0], largest_chunk_bytes=v[1], all_chunks_bytes=v[2],
                     bytes_h2d=v[3], bytes_d2h=v[4], n_chunks=v[5])
+
+
+def _begin_summary(summary, options):
+    """the options' thresholds and iteration limit into a Summary (None: nothing)"""
+    if summary is not None:
+        summary.max_iteration_ = options.iteration_handle.max_num_iterations
+        summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change
+        summary.threshold_step_size_ = options.convergence_handle.threshold_step_size
+        summary.convergence_status_ = True
+
+
+# a kind of pose graph as the facade's shared graph methods see it (FullBundleAdjustmentSolver._graph_kind)
+_GraphKind = collections.namedtuple("_GraphKind", "cls add rels units poses to_user")
 
 
 class FullBundleAdjustmentSolver:
@@ -2504,13 +2524,7 @@ class FullBundleAdjustmentSolver:
 
     def Solve(self, options, summary=None):             # reference :630-1044
         t0 = time.perf_counter()
-        if summary is not None:
-            summary.max_iteration_ = options.iteration_handle.max_num_iterations
-            summary.threshold_cost_change_ = \
-                options.convergence_handle.threshold_cost_change
-            summary.threshold_step_size_ = \
-                options.convergence_handle.threshold_step_size
-            summary.convergence_status_ = True
+        _begin_summary(summary, options)
         self.FinalizeParameters()
         if self.verbose:
             self.GetSolverStatistics()
@@ -2520,6 +2534,83 @@ class FullBundleAdjustmentSolver:
         c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
         rows, converged = p.solve(c_opt)
         return self._finish_solve(rows, converged, summary, t0)
+
+    # ---- the two pose graphs: one path, taking the kind ----
+    def _graph_kind(self, sim3):
+        """What differs between the SE(3) graph of AddRelativePose and the Sim(3) graph of
+        AddRelativeSim3, for the shared graph methods below: the graph class, the word in the
+        messages, the factor arrays (None: no factor), the factors' units, the registered poses as
+        the graph takes them and a covariance block in the caller's units."""
+        if sim3:   # (sigma_pixel SCALER)^2 D Sigma D, D = diag(100 I3, I4): the vector d of _scaled_sim3
+            d = np.r_[np.full(3, INVERSE_SCALER), np.ones(4)]
+            return _GraphKind(BaSim3Graph, "AddRelativeSim3", self._sim3_arrays() if self._sim3_relatives else None,
+                              self._sim3_units, lambda T: np.c_[T, np.ones(len(T))],   # the similarity (R, t, s = 1)
+                              lambda b, unit: (unit * unit) * (d[None, :, None] * b * d[None, None, :]))
+        return _GraphKind(BaPoseGraph, "AddRelativePose", self._relative_arrays(), self._relative_units, lambda T: T,
+                          lambda b, unit: covariance_to_user_units(b, np.zeros((0, 3, 3)), unit / SCALER)[0])
+
+    def _graph(self, kind, what):
+        """the registered poses and the kind's factors as a graph, robust kernels included (the
+        factor dict carries them); needs no FinalizeParameters"""
+        if kind.rels is None or not self.num_total_poses_:
+            raise RuntimeError("%s: poses (AddPose) and factors (%s) must be added first" % (what, kind.add))
+        pf = np.zeros(self.num_total_poses_, np.uint8)
+        pf[list(self._pose_fixed)] = 1
+        return kind.cls(kind.poses(np.concatenate(self._pose_T_jw, axis=0)), pf, kind.rels, self.device)
+
+    @staticmethod
+    def _graph_unit(what, units, more=()):
+        """the one unit sigma_pixel SCALER of every factor (and of `more`): Sigma and d2 have
+        caller's units only if there is one"""
+        units = list(units) + list(more)
+        for u in units:
+            if u != units[0]:
+                raise RuntimeError("%s: the factors and candidates were given with sigma_pixel = %g and %g; "
+                                   "a covariance in the caller's units needs one value"
+                                   % (what, units[0] / SCALER, u / SCALER))
+        return units[0] if units else SCALER
+
+    def _pose_handles(self, objs):
+        hs = [self._pose_handle(o) for o in objs]
+        if any(h is None for h in hs):
+            raise RuntimeError("There is no pointer in the BA pose pool.")
+        return np.asarray(hs, np.int32)
+
+    def _solve_graph(self, kind, what, options, report):
+        """-> rows, converged, the solved poses and (s in the caller's units, w) of report(graph)"""
+        c_opt = options.to_c()
+        c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
+        with self._graph(kind, what) as g:
+            rows, converged = g.solve(c_opt)
+            new = g.poses()
+            s, w = report(g)
+        unit = np.asarray(kind.units)   # s in scaled units = s in the caller's times unit^2
+        return rows, converged, new, (s / (unit * unit), w)
+
+    def _graph_covariance(self, kind, what, poses, pairs):
+        unit = self._graph_unit(what, kind.units)
+        ps = self._pose_handles(poses)
+        pj, pk = self._pose_handles([p[0] for p in pairs]), self._pose_handles([p[1] for p in pairs])
+        with self._graph(kind, what) as g:
+            blocks = g.covariance(ps, (pj, pk))
+        return tuple(kind.to_user(b, unit) for b in blocks)
+
+    def _graph_gate(self, kind, what, candidates, scaled):
+        """scaled(sig, unit) -> j, k, Z, Omega of the candidates in scaled units, the kind's own
+        way; sig: each candidate's sigma_pixel, unit: the one unit of factors and candidates"""
+        sig = [float(c.get("sigma_pixel", 1.0)) for c in candidates]
+        unit = self._graph_unit(what, kind.units, [v * SCALER for v in sig])
+        j, k, Z, Om = scaled(sig, unit)
+        with self._graph(kind, what) as g:
+            d2 = g.gate(j, k, Z, Om)[0]
+        return d2 / (unit * unit)
+
+    @staticmethod
+    def _graph_weights(what, solve, report):
+        if report is None:
+            raise RuntimeError("%s: %s has not run" % (what, solve))
+        s, w = report
+        return s.copy(), w.copy()
 
     def SolvePoseGraph(self, options, summary=None):
         """(new) Pose-graph optimisation: Levenberg-Marquardt over the factors of
@@ -2533,25 +2624,44 @@ class FullBundleAdjustmentSolver:
         solved with their kernels; GetRelativeWeights returns every factor's
         s and weight at the solved poses."""
         t0 = time.perf_counter()
-        if summary is not None:
-            summary.max_iteration_ = options.iteration_handle.max_num_iterations
-            summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change
-            summary.threshold_step_size_ = options.convergence_handle.threshold_step_size
-            summary.convergence_status_ = True
-        c_opt = options.to_c()
-        c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
-        g = self._pose_graph("SolvePoseGraph")
-        try:
-            rows, converged = g.solve(c_opt)
-            T_new = g.poses()
-            s, w = g.factor_report()
-        finally:
-            g.close()
-        unit = np.asarray(self._relative_units)   # s in scaled units = s in the caller's times unit^2
-        self._relative_report = (s / (unit * unit), w)
+        _begin_summary(summary, options)
+        rows, converged, T_new, self._relative_report = self._solve_graph(
+            self._graph_kind(False), "SolvePoseGraph", options, lambda g: g.factor_report())
         self._pose_T_jw = [T_new]
         n_pt = self.num_total_points_
         return self._write_back(T_new, np.zeros((n_pt, 3)), np.zeros(n_pt, bool), rows, converged, summary, t0)
+
+    def GetRelativeWeights(self):
+        """(new) -> (s, w) of the last SolvePoseGraph, one entry per factor in the order of
+        AddRelativePose, at the solved poses: s = r^T information r in the caller's units
+        (the Mahalanobis distance squared that a robust scale is compared with) and the
+        robust weight w (1 for a factor without a kernel).  A closure with a small w is the one to drop."""
+        return self._graph_weights("GetRelativeWeights", "SolvePoseGraph", self._relative_report)
+
+    def ComputePoseGraphCovariance(self, poses, pairs=()):
+        """(new) -> (cov_pose (n, 6, 6), cov_cross (p, 6, 6), cov_rel (p, 6, 6)) of the pose graph
+        that SolvePoseGraph solves, at the registered poses as they are now (BaPoseGraph.covariance,
+        DESIGN.md §6m; nothing is solved, FinalizeParameters is not needed): the marginal
+        covariance of each pose of `poses` (objects or handles, optimisable), and for each
+        (pose_j, pose_k) of `pairs` the cross block Sigma_jk and the covariance of the relative
+        pose T_jw T_kw^-1.  Caller's units (covariance_to_user_units) for the sigma_pixel the
+        factors were added with; factors with different sigma_pixel raise RuntimeError."""
+        return self._graph_covariance(self._graph_kind(False), "ComputePoseGraphCovariance", poses, pairs)
+
+    def GateLoopClosures(self, candidates):
+        """(new) -> d2 (n,) of loop-closure candidates against the pose graph at the registered
+        poses, BEFORE they are added (BaPoseGraph.gate, DESIGN.md §6m): the squared Mahalanobis
+        distance of each candidate's residual under the estimate's own uncertainty plus the
+        candidate's, in the caller's units; accept below a chi-square quantile of 6 degrees of
+        freedom (22.46 at 0.999).  A candidate is a dict with the keys of AddRelativePose
+        (pose_j, pose_k, measurement, information, optionally sigma_pixel = 1.0), and every
+        candidate and factor must have been given with one sigma_pixel (RuntimeError otherwise)."""
+        def scaled(sig, unit):   # all candidates with the one unit; refuses a candidate that carries a kernel
+            facs = [dict(pose_j=c["pose_j"], pose_k=c["pose_k"], measurement=c["measurement"],
+                         information=c["information"], robust=c.get("robust")) for c in candidates]
+            sr = self._scaled_relatives("GateLoopClosures", [self], [facs], unit / SCALER)[0]
+            return sr["j"], sr["k"], sr["Z"], sr["Omega"]
+        return self._graph_gate(self._graph_kind(False), "GateLoopClosures", candidates, scaled)
 
     def AddRelativeSim3(self, pose_j, pose_k, measurement, information, sigma_pixel=1.0, robust=None):
         """(new) A relative-similarity factor between two registered poses (objects or integer
@@ -2599,16 +2709,6 @@ class FullBundleAdjustmentSolver:
                        robust_scale=np.array([c for _, c in self._sim3_robust], np.float64))
         return out
 
-    def _sim3_graph(self, what):
-        """the registered poses, each the similarity (R, t, s = 1) of its rigid pose, and the factors
-        of AddRelativeSim3 as a BaSim3Graph, robust kernels included"""
-        if not self._sim3_relatives or not self.num_total_poses_:
-            raise RuntimeError("%s: poses (AddPose) and factors (AddRelativeSim3) must be added first" % what)
-        T = np.concatenate(self._pose_T_jw, axis=0)
-        pf = np.zeros(self.num_total_poses_, np.uint8)
-        pf[list(self._pose_fixed)] = 1
-        return BaSim3Graph(np.c_[T, np.ones(len(T))], pf, self._sim3_arrays(), self.device)
-
     def SolveSim3Graph(self, options, summary=None, point_anchors=None):
         """(new) Sim(3) pose-graph optimisation over the factors of AddRelativeSim3 ALONE, on the
         registered poses with their fixed flags (BaSim3Graph, ba_sim3_*).  Every
@@ -2623,11 +2723,7 @@ class FullBundleAdjustmentSolver:
         solved with their kernels; GetRelativeSim3Weights returns every factor's s
         and weight at the solved poses."""
         t0 = time.perf_counter()
-        if summary is not None:
-            summary.max_iteration_ = options.iteration_handle.max_num_iterations
-            summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change
-            summary.threshold_step_size_ = options.convergence_handle.threshold_step_size
-            summary.convergence_status_ = True
+        _begin_summary(summary, options)
         if not self._sim3_relatives or not self.num_total_poses_:   # before the anchors are looked at, as ever
             raise RuntimeError("SolveSim3Graph: poses (AddPose) and factors (AddRelativeSim3) must be added first")
         n_pt = self.num_total_points_
@@ -2642,22 +2738,15 @@ class FullBundleAdjustmentSolver:
                 if h is None:
                     raise RuntimeError("There is no pointer in the BA pose pool.")
                 anchors[i] = h
-        c_opt = options.to_c()
-        c_opt.gauss_newton = 1 if self._use_gauss_newton(options) else 0
-        g = self._sim3_graph("SolveSim3Graph")
-        T_old = np.concatenate(self._pose_T_jw, axis=0)
-        try:
-            rows, converged = g.solve(c_opt)
-            S_new = g.poses()
+
+        def report(g):
             if any(kd for kd, _ in self._sim3_robust):
-                s, w = g.factor_weights()
-            else:   # no kernel: the report of before, nothing robust is allocated or launched
-                s = g.factor_report()
-                w = np.ones(len(s))
-        finally:
-            g.close()
-        unit = np.asarray(self._sim3_units)   # s in scaled units = s in the caller's times unit^2
-        self._sim3_report = (s / (unit * unit), w)
+                return g.factor_weights()
+            s = g.factor_report()   # no kernel: the report of before, nothing robust is allocated or launched
+            return s, np.ones(len(s))
+        T_old = np.concatenate(self._pose_T_jw, axis=0)
+        rows, converged, S_new, self._sim3_report = self._solve_graph(
+            self._graph_kind(True), "SolveSim3Graph", options, report)
         scales = S_new[:, 12].copy()
         T_new = S_new[:, :12].copy()
         T_new[:, 9:12] /= scales[:, None]
@@ -2676,90 +2765,11 @@ class FullBundleAdjustmentSolver:
         self._write_back(T_new, X, moved, rows, converged, summary, t0)
         return scales
 
-    def _pose_graph(self, what):
-        """the registered poses and the factors of AddRelativePose as a BaPoseGraph, robust
-        kernels included; needs no FinalizeParameters"""
-        rels = self._relative_arrays()
-        if rels is None or not self.num_total_poses_:
-            raise RuntimeError("%s: poses (AddPose) and factors (AddRelativePose) must be added first" % what)
-        T_jw = np.concatenate(self._pose_T_jw, axis=0)
-        pf = np.zeros(self.num_total_poses_, np.uint8)
-        pf[list(self._pose_fixed)] = 1
-        return BaPoseGraph(T_jw, pf, rels, self.device)   # applies the kernels that the factors carry
-
-    def _pose_graph_unit(self, what, more=()):
-        """the one unit sigma_pixel SCALER of every factor (and of `more`): Sigma and d2 have
-        caller's units only if there is one"""
-        units = list(self._relative_units) + list(more)
-        for u in units:
-            if u != units[0]:
-                raise RuntimeError("%s: the factors and candidates were given with sigma_pixel = %g and %g; "
-                                   "a covariance in the caller's units needs one value"
-                                   % (what, units[0] / SCALER, u / SCALER))
-        return units[0] if units else SCALER
-
-    def ComputePoseGraphCovariance(self, poses, pairs=()):
-        """(new) -> (cov_pose (n, 6, 6), cov_cross (p, 6, 6), cov_rel (p, 6, 6)) of the pose graph
-        that SolvePoseGraph solves, at the registered poses as they are now (BaPoseGraph.covariance,
-        DESIGN.md §6m; nothing is solved, FinalizeParameters is not needed): the marginal
-        covariance of each pose of `poses` (objects or handles, optimisable), and for each
-        (pose_j, pose_k) of `pairs` the cross block Sigma_jk and the covariance of the relative
-        pose T_jw T_kw^-1.  Caller's units (covariance_to_user_units) for the sigma_pixel the
-        factors were added with; factors with different sigma_pixel raise RuntimeError."""
-        unit = self._pose_graph_unit("ComputePoseGraphCovariance")
-
-        def handles(objs):
-            hs = [self._pose_handle(o) for o in objs]
-            if any(h is None for h in hs):
-                raise RuntimeError("There is no pointer in the BA pose pool.")
-            return np.asarray(hs, np.int32)
-        ps = handles(poses)
-        pj, pk = handles([p[0] for p in pairs]), handles([p[1] for p in pairs])
-        g = self._pose_graph("ComputePoseGraphCovariance")
-        try:
-            blocks = g.covariance(ps, (pj, pk))
-        finally:
-            g.close()
-        return tuple(covariance_to_user_units(b, np.zeros((0, 3, 3)), unit / SCALER)[0] for b in blocks)
-
-    def GateLoopClosures(self, candidates):
-        """(new) -> d2 (n,) of loop-closure candidates against the pose graph at the registered
-        poses, BEFORE they are added (BaPoseGraph.gate, DESIGN.md §6m): the squared Mahalanobis
-        distance of each candidate's residual under the estimate's own uncertainty plus the
-        candidate's, in the caller's units; accept below a chi-square quantile of 6 degrees of
-        freedom (22.46 at 0.999).  A candidate is a dict with the keys of AddRelativePose
-        (pose_j, pose_k, measurement, information, optionally sigma_pixel = 1.0), and every
-        candidate and factor must have been given with one sigma_pixel (RuntimeError otherwise)."""
-        sig = [float(c.get("sigma_pixel", 1.0)) for c in candidates]
-        unit = self._pose_graph_unit("GateLoopClosures", [v * SCALER for v in sig])
-        facs = [dict(pose_j=c["pose_j"], pose_k=c["pose_k"], measurement=c["measurement"],
-                     information=c["information"], robust=c.get("robust")) for c in candidates]
-        sr = self._scaled_relatives("GateLoopClosures", [self], [facs], unit / SCALER)[0]
-        g = self._pose_graph("GateLoopClosures")
-        try:
-            d2 = g.gate(sr["j"], sr["k"], sr["Z"], sr["Omega"])[0]
-        finally:
-            g.close()
-        return d2 / (unit * unit)
-
     def GetRelativeSim3Weights(self):
         """(new) -> (s, w) of the last SolveSim3Graph, one entry per factor in the order of
         AddRelativeSim3, at the solved similarities: s = r^T information r in the caller's units
         and the robust weight w (1 for a factor without a kernel)."""
-        if getattr(self, "_sim3_report", None) is None:
-            raise RuntimeError("GetRelativeSim3Weights: SolveSim3Graph has not run")
-        s, w = self._sim3_report
-        return s.copy(), w.copy()
-
-    def _sim3_graph_unit(self, what, more=()):
-        """_pose_graph_unit for the factors of AddRelativeSim3"""
-        units = list(self._sim3_units) + list(more)
-        for u in units:
-            if u != units[0]:
-                raise RuntimeError("%s: the factors and candidates were given with sigma_pixel = %g and %g; "
-                                   "a covariance in the caller's units needs one value"
-                                   % (what, units[0] / SCALER, u / SCALER))
-        return units[0] if units else SCALER
+        return self._graph_weights("GetRelativeSim3Weights", "SolveSim3Graph", self._sim3_report)
 
     def ComputeSim3GraphCovariance(self, poses, pairs=()):
         """(new) -> (cov_pose (n, 7, 7), cov_cross (p, 7, 7), cov_rel (p, 7, 7)) of the Sim(3) graph
@@ -2771,22 +2781,7 @@ class FullBundleAdjustmentSolver:
         with: (sigma_pixel SCALER)^2 D Sigma D with D = diag(100 I3, I4), the vector d of
         AddRelativeSim3 (omega and sigma have no unit); factors with different sigma_pixel raise
         RuntimeError."""
-        unit = self._sim3_graph_unit("ComputeSim3GraphCovariance")
-
-        def handles(objs):
-            hs = [self._pose_handle(o) for o in objs]
-            if any(h is None for h in hs):
-                raise RuntimeError("There is no pointer in the BA pose pool.")
-            return np.asarray(hs, np.int32)
-        ps = handles(poses)
-        pj, pk = handles([p[0] for p in pairs]), handles([p[1] for p in pairs])
-        g = self._sim3_graph("ComputeSim3GraphCovariance")
-        try:
-            blocks = g.covariance(ps, (pj, pk))
-        finally:
-            g.close()
-        d = np.r_[np.full(3, INVERSE_SCALER), np.ones(4)]
-        return tuple((unit * unit) * (d[None, :, None] * b * d[None, None, :]) for b in blocks)
+        return self._graph_covariance(self._graph_kind(True), "ComputeSim3GraphCovariance", poses, pairs)
 
     def GateSim3LoopClosures(self, candidates):
         """(new) -> d2 (n,) of Sim(3) loop-closure candidates against the Sim(3) graph at the
@@ -2795,35 +2790,12 @@ class FullBundleAdjustmentSolver:
         candidate is a dict with the keys of AddRelativeSim3 (pose_j, pose_k, measurement,
         information, optionally sigma_pixel = 1.0); every candidate and factor must have been
         given with one sigma_pixel (RuntimeError otherwise).  No robust weight applies to a candidate."""
-        sig = [float(c.get("sigma_pixel", 1.0)) for c in candidates]
-        unit = self._sim3_graph_unit("GateSim3LoopClosures", [v * SCALER for v in sig])
-        hj, hk, Z, Om = [], [], [], []
-        for c, sg in zip(candidates, sig):
-            a, b = self._pose_handle(c["pose_j"]), self._pose_handle(c["pose_k"])
-            if a is None or b is None:
-                raise RuntimeError("There is no pointer in the BA pose pool.")
-            z, om = self._scaled_sim3(c["measurement"], c["information"], sg)   # its own sigma_pixel: the factors'
-            hj.append(a)
-            hk.append(b)
-            Z.append(z)
-            Om.append(om)
-        g = self._sim3_graph("GateSim3LoopClosures")
-        try:
-            d2 = g.gate(np.asarray(hj, np.int32), np.asarray(hk, np.int32), np.array(Z).reshape(-1, 13),
-                        np.array(Om).reshape(-1, 7, 7))[0]
-        finally:
-            g.close()
-        return d2 / (unit * unit)
-
-    def GetRelativeWeights(self):
-        """(new) -> (s, w) of the last SolvePoseGraph, one entry per factor in the order of
-        AddRelativePose, at the solved poses: s = r^T information r in the caller's units
-        (the Mahalanobis distance squared that a robust scale is compared with) and the
-        robust weight w (1 for a factor without a kernel).  A closure with a small w is the one to drop."""
-        if getattr(self, "_relative_report", None) is None:
-            raise RuntimeError("GetRelativeWeights: SolvePoseGraph has not run")
-        s, w = self._relative_report
-        return s.copy(), w.copy()
+        def scaled(sig, unit):   # each candidate with its own sigma_pixel (the factors'); its kernel is not read
+            hj = self._pose_handles([c["pose_j"] for c in candidates])
+            hk = self._pose_handles([c["pose_k"] for c in candidates])
+            zo = [self._scaled_sim3(c["measurement"], c["information"], sg) for c, sg in zip(candidates, sig)]
+            return hj, hk, np.array([z for z, _ in zo]).reshape(-1, 13), np.array([om for _, om in zo]).reshape(-1, 7, 7)
+        return self._graph_gate(self._graph_kind(True), "GateSim3LoopClosures", candidates, scaled)
 
     @staticmethod
     def _scaled_priors(what, solvers, priors, sigma_pixel):
@@ -3003,11 +2975,7 @@ class FullBundleAdjustmentSolver:
             T_all, X_all = batch.get_poses(), batch.get_points()
             for k, sv in enumerate(solvers):
                 summary = None if summaries is None else summaries[k]
-                if summary is not None:
-                    summary.max_iteration_ = options.iteration_handle.max_num_iterations
-                    summary.threshold_cost_change_ = options.convergence_handle.threshold_cost_change
-                    summary.threshold_step_size_ = options.convergence_handle.threshold_step_size
-                    summary.convergence_status_ = True
+                _begin_summary(summary, options)
                 if res[k].status != 0:
                     if summary is not None:
                         summary.convergence_status_ = False
@@ -3705,13 +3673,7 @@ class FullBundleAdjustmentSolverRefactor(FullBundleAdjustmentSolver):
         taken; rows as documented at ba_solve_gd (include/ba_hip.h).
         solver_type, decrease / increase_ratio_lambda are ignored."""
         t0 = time.perf_counter()
-        if summary is not None:
-            summary.max_iteration_ = options.iteration_handle.max_num_iterations
-            summary.threshold_cost_change_ = \
-                options.convergence_handle.threshold_cost_change
-            summary.threshold_step_size_ = \
-                options.convergence_handle.threshold_step_size
-            summary.convergence_status_ = True
+        _begin_summary(summary, options)
         self.FinalizeParameters()
         if self.verbose:
             self.GetSolverStatistics()

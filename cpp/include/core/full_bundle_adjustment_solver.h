@@ -20,8 +20,6 @@
 #include "utility/timer.h"
 
 struct ba_handle;  // include/ba_hip.h
-struct ba_pgraph;
-struct ba_sim3;
 struct ba_batch;
 
 namespace visual_navigation {
@@ -440,28 +438,25 @@ class FullBundleAdjustmentSolver {
                             const std::vector<std::vector<RelativePose>> *in_relatives, double sigma_pixel,
                             RelativeArrays *out);
   static int SetRelatives(ba_batch *batch, const RelativeArrays &r);
-  // the registered poses and the factors of AddRelativePose as a graph with its kernels set, on
-  // the finalized problem's handle or one of its own (*h); throws on a refusal
-  ba_pgraph *CreatePoseGraph(const char *who, ba_handle **h);
-  // the one unit sigma_pixel scaler_ of the factors and `more` (throws if there are two)
-  double PoseGraphUnit(const char *who, const std::vector<double> &more) const;
-  RelativeArrays relatives_;  // AddRelativePose: j, k, Z, Omega of this solver's factors (off unused)
-  std::vector<double> report_s_, report_w_;  // the factor report of the last SolvePoseGraph
-  // AddRelativeSim3: j, k, Z (13 per factor) and Omega (49) in scaled units, input order
-  std::vector<int32_t> sim3_j_, sim3_k_;
-  std::vector<double> sim3_Z_, sim3_Omega_;
-  // per Sim(3) factor: the robust kernel (scale in scaled units) and sigma_pixel * scaler, the
-  // unit of its Mahalanobis distance; s and w of the last SolveSim3Graph
-  std::vector<int32_t> sim3_kind_;
-  std::vector<double> sim3_scale_, sim3_unit_, sim3_report_s_, sim3_report_w_;
+  // The factors of one graph, of AddRelativePose (Z 12, Omega 36 per factor) or of
+  // AddRelativeSim3 (13, 49), in scaled units and input order (set and off unused), and s and w
+  // of the graph's last solve.
+  struct GraphFactors : RelativeArrays {
+    std::vector<double> report_s, report_w;
+  };
+  GraphFactors relatives_, sim3_;
   // one Sim(3) factor or candidate into scaled units: Z (13) and Omega (49) appended
   void PackSim3(const RelativeSim3 &f, double sigma_pixel, std::vector<double> *Z, std::vector<double> *Omega) const;
-  // the registered poses as similarities (s = 1) and the factors of AddRelativeSim3 as a graph
-  // with its kernels set, on the finalized problem's handle or one of its own (*h); throws on a refusal
-  ba_sim3 *CreateSim3Graph(const char *who, ba_handle **h, std::vector<double> *S13 = nullptr);
-  double Sim3GraphUnit(const char *who, const std::vector<double> &more) const;
-  // the options' thresholds and iteration limit into a Summary (nullptr: nothing)
+  // The graph methods once, at the width of a kind (the traits Se3Abi: SolvePoseGraph and its
+  // companions; Sim3Abi: SolveSim3Graph and its): in the .cpp, beside the traits
+  template <class Abi>
+  struct Graph;
+  // the options' thresholds and iteration limit into a Summary (nullptr: nothing) and, after
+  // the solve, its rows (Row: ba_iter_info of include/ba_hip.h), status and total time
   static void BeginSummary(Summary *summary, const Options &options);
+  template <class Row>
+  static void FinishSummary(Summary *summary, const std::vector<Row> &rows, int n_iter, int converged,
+                            timer::StopWatch &stopwatch);
   // stderr warnings about weakly connected poses / points (reference
   // core/full_bundle_adjustment_solver.cpp:310-341), called by Solve
   void CheckPoseAndPointConnectivity();

@@ -9,6 +9,7 @@
 #include <stdexcept>
 
 #include "ba_hip.h"
+#include "core/graph_session.h"
 
 namespace visual_navigation {
 namespace analytic_solver {
@@ -56,18 +57,8 @@ void FullBundleAdjustmentSolver::Reset() {  // :44-70
   X_.clear();
   fixed_points_.clear();
   observations_.clear();
-  relatives_ = RelativeArrays();
-  report_s_.clear();
-  report_w_.clear();
-  sim3_j_.clear();
-  sim3_k_.clear();
-  sim3_Z_.clear();
-  sim3_Omega_.clear();
-  sim3_kind_.clear();
-  sim3_scale_.clear();
-  sim3_unit_.clear();
-  sim3_report_s_.clear();
-  sim3_report_w_.clear();
+  relatives_ = GraphFactors();
+  sim3_ = GraphFactors();
   num_fixed_poses_ = num_fixed_points_ = 0;
 }
 
@@ -370,6 +361,16 @@ void FullBundleAdjustmentSolver::BeginSummary(Summary *summary, const Options &o
   summary->convergence_status_ = true;
 }
 
+template <class Row>
+void FullBundleAdjustmentSolver::FinishSummary(Summary *summary, const std::vector<Row> &rows, int n_iter, int converged,
+                                               timer::StopWatch &stopwatch) {
+  if (summary == nullptr) return;
+  for (int k = 0; k < n_iter && k < static_cast<int>(rows.size()); ++k)
+    summary->optimization_info_list_.push_back(ToInfo(rows[k]));
+  summary->convergence_status_ = converged != 0;
+  summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
+}
+
 void FullBundleAdjustmentSolver::WriteBack(const double *T_jw12, const double *X3, const uint8_t *valid) {
   for (size_t p = 0; p < poses_.size(); ++p) {
     if (fixed_poses_.count(static_cast<int>(p))) continue;
@@ -421,55 +422,261 @@ bool FullBundleAdjustmentSolver::Run(Options options, Summary *summary, bool gra
     Check(ba_get_points(handle_, X.data(), valid.data()), "ba_get_points");
   }
   WriteBack(T.data(), X.data(), valid.data());
-  if (summary != nullptr) {
-    for (int k = 0; k < n_iter && k < static_cast<int>(rows.size()); ++k)
-      summary->optimization_info_list_.push_back(ToInfo(rows[k]));
-    summary->convergence_status_ = converged != 0;
-    summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
-  }
+  FinishSummary(summary, rows, n_iter, converged, stopwatch);
   return true;  // the reference always returns true (:1043)
 }
 
+// ---- the two pose graphs: one path at the width of Abi ----
+namespace {
+
+// The facade's counterpart of the library's GraphSpec: what a kind of graph is in the C ABI
+// (include/ba_hip.h) and in the messages.  The handle entries are the same for both.
+struct HandleAbi {
+  using Handle = ba_handle;
+  static constexpr const char *kCreateHandle = "ba_create";
+  static constexpr auto create_handle = ba_create;
+  static constexpr auto destroy_handle = ba_destroy;
+  static constexpr auto last_error = ba_last_error;
+};
+
+struct Se3Abi : HandleAbi {
+  using Graph = ba_pgraph;
+  static constexpr int kWidth = 6, kPose = 12;  // tangent width, doubles per pose
+  static constexpr const char *kPrefix = "ba_pgraph_", *kAdd = "AddRelativePose";
+  static constexpr auto create = ba_pgraph_create;
+  static constexpr auto set_robust = ba_pgraph_set_robust;
+  static constexpr auto solve = ba_pgraph_solve;
+  static constexpr auto get_poses = ba_pgraph_get_poses;
+  static constexpr auto covariance = ba_pgraph_covariance;
+  static constexpr auto gate = ba_pgraph_gate;
+  static constexpr auto destroy = ba_pgraph_destroy;
+  static void PackPose(const _BA_Pose &T, double *out) { Pack12(T, out); }
+  // always s and w
+  static int FactorReport(ba_pgraph *g, const std::vector<int32_t> &, double *s, std::vector<double> *w,
+                          const char **entry) {
+    *entry = "factor_report";
+    return ba_pgraph_factor_report(g, s, w->data());
+  }
+};
+
+struct Sim3Abi : HandleAbi {
+  using Graph = ba_sim3;
+  static constexpr int kWidth = 7, kPose = 13;
+  static constexpr const char *kPrefix = "ba_sim3_", *kAdd = "AddRelativeSim3";
+  static constexpr auto create = ba_sim3_create;
+  static constexpr auto set_robust = ba_sim3_set_robust;
+  static constexpr auto solve = ba_sim3_solve;
+  static constexpr auto get_poses = ba_sim3_get_poses;
+  static constexpr auto covariance = ba_sim3_covariance;
+  static constexpr auto gate = ba_sim3_gate;
+  static constexpr auto destroy = ba_sim3_destroy;
+  static void PackPose(const _BA_Pose &T, double *out) {  // the similarity (R, t, s = 1)
+    Pack12(T, out);
+    out[12] = 1.0;
+  }
+  // s and w where a factor carries a kernel; no kernel: the report of before with w = 1, nothing
+  // robust is allocated or launched
+  static int FactorReport(ba_sim3 *g, const std::vector<int32_t> &kind, double *s, std::vector<double> *w,
+                          const char **entry) {
+    if (std::any_of(kind.begin(), kind.end(), [](int32_t kd) { return kd != 0; })) {
+      *entry = "factor_weights";
+      return ba_sim3_factor_weights(g, s, w->data());
+    }
+    *entry = "factor_report";
+    w->assign(w->size(), 1.0);
+    return ba_sim3_factor_report(g, s);
+  }
+};
+
+// what Graph<Abi>::Run leaves: the poses as the graph got them and as it left them (Abi::kPose
+// doubles each), and the rows of the solve
+struct GraphRun {
+  std::vector<double> start, solved;
+  std::vector<ba_iter_info> rows;
+  int n_iter{0}, converged{0};
+};
+
+}  // namespace
+
+template <class Abi>
+struct FullBundleAdjustmentSolver::Graph {
+  using Solver = FullBundleAdjustmentSolver;
+  using Block = Eigen::Matrix<double, Abi::kWidth, Abi::kWidth>;
+
+  static void Require(const Solver &s, const char *who, const GraphFactors &f) {
+    if (s.poses_.empty() || f.j.empty())
+      throw std::runtime_error(std::string(who) + ": poses (AddPose) and factors (" + Abi::kAdd +
+                               ") must be added first");
+  }
+
+  // the registered poses and the factors `f` as a graph with its kernels set, on the finalized
+  // problem's handle or one of the session's own (the graph borrows it for its device and stream);
+  // throws on a refusal.  *poses_out (may be null): the poses as the graph got them.
+  static GraphSession<Abi> Open(const Solver &s, const char *who, const GraphFactors &f,
+                                std::vector<double> *poses_out = nullptr) {
+    Require(s, who, f);
+    const size_t n_pose = s.poses_.size();
+    std::vector<double> P(Abi::kPose * n_pose);
+    std::vector<uint8_t> pose_fixed(n_pose, 0);
+    for (size_t p = 0; p < n_pose; ++p) {
+      Abi::PackPose(s.T_jw_[p], &P[Abi::kPose * p]);
+      pose_fixed[p] = s.fixed_poses_.count(static_cast<int>(p)) > 0;
+    }
+    if (poses_out != nullptr) *poses_out = P;
+    return GraphSession<Abi>(s.handle_, s.device_id_,
+                             {static_cast<int>(n_pose), P.data(), pose_fixed.data(), static_cast<int64_t>(f.j.size()),
+                              f.j.data(), f.k.data(), f.Z.data(), f.Omega.data(), f.kind.data(), f.scale.data()});
+  }
+
+  // the one unit sigma_pixel scaler_ of the factors and `more` (throws if there are two)
+  static double Unit(const Solver &s, const char *who, const GraphFactors &f, const std::vector<double> &more) {
+    std::vector<double> units(f.unit);
+    units.insert(units.end(), more.begin(), more.end());
+    for (double u : units)
+      if (u != units[0]) {
+        std::ostringstream m;
+        m << who << ": the factors and candidates were given with sigma_pixel = " << units[0] / s.scaler_ << " and "
+          << u / s.scaler_ << "; a covariance in the caller's units needs one value";
+        throw std::runtime_error(m.str());
+      }
+    return units.empty() ? static_cast<double>(s.scaler_) : units[0];
+  }
+
+  static int32_t PoseIndex(const Solver &s, _BA_Pose *pose) {
+    const auto it = s.pose_index_.find(pose);
+    if (it == s.pose_index_.end()) throw std::runtime_error("There is no pointer in the BA pose pool.");
+    return static_cast<int32_t>(it->second);
+  }
+
+  // solve, the solved poses, the factor report into f->report_* in the caller's units
+  static void Run(const Solver &s, const char *who, GraphFactors *f, const Options &options, GraphRun *run) {
+    const ba_options o = PackOptions(options, s.gauss_newton_);
+    run->rows.resize(static_cast<size_t>(std::max(1, o.max_num_iterations)));
+    run->solved.resize(Abi::kPose * s.poses_.size());
+    std::vector<double> rep_s(f->j.size()), rep_w(f->j.size());
+    {
+      const GraphSession<Abi> g = Open(s, who, *f, &run->start);
+      g.Check(Abi::solve(g.get(), &o, run->rows.data(), static_cast<int>(run->rows.size()), &run->n_iter,
+                         &run->converged),
+              "solve");
+      g.Check(Abi::get_poses(g.get(), run->solved.data()), "get_poses");
+      const char *entry = nullptr;
+      const int rc = Abi::FactorReport(g.get(), f->kind, rep_s.data(), &rep_w, &entry);
+      g.Check(rc, entry);
+    }
+    for (size_t i = 0; i < rep_s.size(); ++i) rep_s[i] /= f->unit[i] * f->unit[i];  // the caller's units
+    f->report_s.swap(rep_s);
+    f->report_w.swap(rep_w);
+  }
+
+  static bool Covariance(const Solver &s, const char *who, const GraphFactors &f, const std::vector<_BA_Pose *> &poses,
+                         const std::vector<std::pair<_BA_Pose *, _BA_Pose *>> &pairs, std::vector<Block> *cov_poses,
+                         std::vector<Block> *cov_cross, std::vector<Block> *cov_rel) {
+    constexpr int W = Abi::kWidth, WW = W * W;
+    const double unit = Unit(s, who, f, {});
+    std::vector<int32_t> ps, pj, pk;
+    for (_BA_Pose *p : poses) ps.push_back(PoseIndex(s, p));
+    for (const auto &jk : pairs) {
+      pj.push_back(PoseIndex(s, jk.first));
+      pk.push_back(PoseIndex(s, jk.second));
+    }
+    if ((!ps.empty() && cov_poses == nullptr) || (!pj.empty() && cov_rel == nullptr))
+      throw std::runtime_error(std::string(who) + ": null output for a non-empty selection");
+    std::vector<double> cp(WW * ps.size()), cc(WW * pj.size()), cr(WW * pj.size());
+    int64_t dropped = 0;
+    {
+      const GraphSession<Abi> g = Open(s, who, f);
+      if (Abi::covariance(g.get(), static_cast<int>(ps.size()), ps.empty() ? nullptr : ps.data(),
+                          ps.empty() ? nullptr : cp.data(), static_cast<int64_t>(pj.size()),
+                          pj.empty() ? nullptr : pj.data(), pj.empty() ? nullptr : pk.data(),
+                          pj.empty() || cov_cross == nullptr ? nullptr : cc.data(), pj.empty() ? nullptr : cr.data(),
+                          &dropped) != 0)
+        throw std::runtime_error(Abi::last_error());
+    }
+    // scaled units -> the caller's: Sigma_user = unit^2 D Sigma_scaled D, D = diag(100 I3, I)
+    const auto to_user = [&](const std::vector<double> &in, std::vector<Block> *out) {
+      if (out == nullptr) return;
+      out->resize(in.size() / WW);
+      for (size_t b = 0; b < out->size(); ++b)
+        for (int r = 0; r < W; ++r)
+          for (int c = 0; c < W; ++c) {
+            const double dr = r < 3 ? static_cast<double>(s.inverse_scaler_) : 1.0;
+            const double dc = c < 3 ? static_cast<double>(s.inverse_scaler_) : 1.0;
+            (*out)[b](r, c) = (unit * unit) * (dr * in[WW * b + W * r + c] * dc);
+          }
+    };
+    to_user(cp, cov_poses);
+    to_user(cc, cov_cross);
+    to_user(cr, cov_rel);
+    return dropped == 0;
+  }
+
+  // pack(&c): the n candidates into c.j, c.k, c.Z, c.Omega, the kind's own way
+  template <class Pack>
+  static bool Gate(const Solver &s, const char *who, const GraphFactors &f, size_t n, double sigma_pixel,
+                   std::vector<double> *d2, Pack pack) {
+    if (d2 == nullptr) throw std::runtime_error(std::string(who) + ": null output");
+    const double unit = Unit(s, who, f, std::vector<double>(n, sigma_pixel * static_cast<double>(s.scaler_)));
+    RelativeArrays c;
+    pack(&c);
+    d2->assign(n, 0.0);
+    int64_t dropped = 0;
+    {
+      const GraphSession<Abi> g = Open(s, who, f);
+      const bool any = n != 0;
+      if (Abi::gate(g.get(), static_cast<int64_t>(n), any ? c.j.data() : nullptr, any ? c.k.data() : nullptr,
+                    any ? c.Z.data() : nullptr, any ? c.Omega.data() : nullptr, any ? d2->data() : nullptr, nullptr,
+                    nullptr, &dropped) != 0)
+        throw std::runtime_error(Abi::last_error());
+    }
+    for (double &v : *d2) v /= unit * unit;  // d2_user = d2_scaled / unit^2
+    return dropped == 0;
+  }
+
+  static void Weights(const char *who, const char *solve, const GraphFactors &f, std::vector<double> *s,
+                      std::vector<double> *w) {
+    if (f.report_w.empty()) throw std::runtime_error(std::string(who) + ": " + solve + " has not run");
+    if (s != nullptr) *s = f.report_s;
+    if (w != nullptr) *w = f.report_w;
+  }
+};
+
+// ---- SE(3): the factors of AddRelativePose ----
 bool FullBundleAdjustmentSolver::SolvePoseGraph(Options options, Summary *summary) {
   timer::StopWatch stopwatch("BundleAdjustmentSolver::SolvePoseGraph");
   stopwatch.Start();
   BeginSummary(summary, options);
-  std::vector<double> T(12 * poses_.size());
-  const ba_options o = PackOptions(options, gauss_newton_);
-  std::vector<ba_iter_info> rows(static_cast<size_t>(std::max(1, o.max_num_iterations)));
-  int n_iter = 0, converged = 0;
-  // the graph borrows a handle for its device and stream: the finalized problem's, or one of its own
-  ba_handle *h = nullptr;
-  ba_pgraph *g = CreatePoseGraph("SolvePoseGraph", &h);
-  int rc = ba_pgraph_solve(g, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged);
-  const char *what = "ba_pgraph_solve";
-  if (rc == 0) {
-    rc = ba_pgraph_get_poses(g, T.data());
-    what = "ba_pgraph_get_poses";
-  }
-  std::vector<double> rep_s(relatives_.j.size()), rep_w(relatives_.j.size());
-  if (rc == 0) {
-    rc = ba_pgraph_factor_report(g, rep_s.data(), rep_w.data());
-    what = "ba_pgraph_factor_report";
-  }
-  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
-  ba_pgraph_destroy(g);
-  if (h != handle_) ba_destroy(h);
-  if (rc != 0) throw std::runtime_error(std::string(what) + ": " + err);
-  for (size_t f = 0; f < rep_s.size(); ++f) rep_s[f] /= relatives_.unit[f] * relatives_.unit[f];
-  report_s_.swap(rep_s);
-  report_w_.swap(rep_w);
+  GraphRun run;
+  Graph<Se3Abi>::Run(*this, "SolvePoseGraph", &relatives_, options, &run);
   const std::vector<uint8_t> no_point(points_.size(), 0);
-  WriteBack(T.data(), nullptr, no_point.data());
-  if (summary != nullptr) {
-    for (int k = 0; k < n_iter && k < static_cast<int>(rows.size()); ++k)
-      summary->optimization_info_list_.push_back(ToInfo(rows[k]));
-    summary->convergence_status_ = converged != 0;
-    summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
-  }
+  WriteBack(run.solved.data(), nullptr, no_point.data());
+  FinishSummary(summary, run.rows, run.n_iter, run.converged, stopwatch);
   return true;
 }
 
+void FullBundleAdjustmentSolver::GetRelativeWeights(std::vector<double> *s, std::vector<double> *w) const {
+  Graph<Se3Abi>::Weights("GetRelativeWeights", "SolvePoseGraph", relatives_, s, w);
+}
+
+bool FullBundleAdjustmentSolver::ComputePoseGraphCovariance(const std::vector<_BA_Pose *> &poses,
+                                                            const std::vector<std::pair<_BA_Pose *, _BA_Pose *>> &pairs,
+                                                            std::vector<Eigen::Matrix<double, 6, 6>> *cov_poses,
+                                                            std::vector<Eigen::Matrix<double, 6, 6>> *cov_cross,
+                                                            std::vector<Eigen::Matrix<double, 6, 6>> *cov_rel) {
+  return Graph<Se3Abi>::Covariance(*this, "ComputePoseGraphCovariance", relatives_, poses, pairs, cov_poses, cov_cross,
+                                   cov_rel);
+}
+
+bool FullBundleAdjustmentSolver::GateLoopClosures(const std::vector<RelativePose> &candidates, double sigma_pixel,
+                                                  std::vector<double> *d2) {
+  const char *who = "GateLoopClosures";
+  return Graph<Se3Abi>::Gate(*this, who, relatives_, candidates.size(), sigma_pixel, d2, [&](RelativeArrays *c) {
+    const std::vector<std::vector<RelativePose>> lists(1, candidates);
+    PackRelatives({this}, who, &lists, sigma_pixel, c);  // throws on a candidate that carries a kernel
+  });
+}
+
+// ---- Sim(3): the factors of AddRelativeSim3 ----
 void FullBundleAdjustmentSolver::PackSim3(const RelativeSim3 &f, double sigma_pixel, std::vector<double> *Z,
                                           std::vector<double> *Omega) const {
   const double *M = f.measurement;
@@ -500,147 +707,12 @@ void FullBundleAdjustmentSolver::AddRelativeSim3(const RelativeSim3 &f, double s
       throw std::runtime_error(std::string("AddRelativeSim3: ") + ba_last_error());
     scale = f.robust_scale * unit;  // s in scaled units is s in the caller's units times unit^2
   }
-  sim3_j_.push_back(ij->second);
-  sim3_k_.push_back(ik->second);
-  PackSim3(f, sigma_pixel, &sim3_Z_, &sim3_Omega_);
-  sim3_kind_.push_back(kind);
-  sim3_scale_.push_back(scale);
-  sim3_unit_.push_back(unit);
-}
-
-ba_sim3 *FullBundleAdjustmentSolver::CreateSim3Graph(const char *who, ba_handle **h, std::vector<double> *S13) {
-  const std::string name(who);
-  if (poses_.empty() || sim3_j_.empty())
-    throw std::runtime_error(name + ": poses (AddPose) and factors (AddRelativeSim3) must be added first");
-  const size_t n_pose = poses_.size();
-  std::vector<double> S(13 * n_pose);
-  std::vector<uint8_t> pose_fixed(n_pose, 0);
-  for (size_t p = 0; p < n_pose; ++p) {
-    Pack12(T_jw_[p], &S[13 * p]);
-    S[13 * p + 12] = 1.0;
-    pose_fixed[p] = fixed_poses_.count(static_cast<int>(p)) > 0;
-  }
-  // the graph borrows a handle for its device and stream: the finalized problem's, or one of its own
-  *h = handle_;
-  if (*h == nullptr) Check(ba_create(h, device_id_), "ba_create");
-  ba_sim3 *g = nullptr;
-  int rc = ba_sim3_create(&g, *h, static_cast<int>(n_pose), S.data(), pose_fixed.data(),
-                          static_cast<int64_t>(sim3_j_.size()), sim3_j_.data(), sim3_k_.data(), sim3_Z_.data(),
-                          sim3_Omega_.data());
-  const char *what = "ba_sim3_create";
-  if (rc == 0) {
-    rc = ba_sim3_set_robust(g, sim3_kind_.data(), sim3_scale_.data());
-    what = "ba_sim3_set_robust";
-  }
-  if (rc != 0) {
-    const std::string err = ba_last_error();
-    ba_sim3_destroy(g);
-    if (*h != handle_) ba_destroy(*h);
-    throw std::runtime_error(std::string(what) + ": " + err);
-  }
-  if (S13 != nullptr) S13->swap(S);
-  return g;
-}
-
-double FullBundleAdjustmentSolver::Sim3GraphUnit(const char *who, const std::vector<double> &more) const {
-  std::vector<double> units(sim3_unit_);
-  units.insert(units.end(), more.begin(), more.end());
-  for (double u : units)
-    if (u != units[0]) {
-      std::ostringstream m;
-      m << who << ": the factors and candidates were given with sigma_pixel = " << units[0] / scaler_ << " and "
-        << u / scaler_ << "; a covariance in the caller's units needs one value";
-      throw std::runtime_error(m.str());
-    }
-  return units.empty() ? static_cast<double>(scaler_) : units[0];
-}
-
-void FullBundleAdjustmentSolver::GetRelativeSim3Weights(std::vector<double> *s, std::vector<double> *w) const {
-  if (sim3_report_w_.empty()) throw std::runtime_error("GetRelativeSim3Weights: SolveSim3Graph has not run");
-  if (s != nullptr) *s = sim3_report_s_;
-  if (w != nullptr) *w = sim3_report_w_;
-}
-
-bool FullBundleAdjustmentSolver::ComputeSim3GraphCovariance(const std::vector<_BA_Pose *> &poses,
-                                                            const std::vector<std::pair<_BA_Pose *, _BA_Pose *>> &pairs,
-                                                            std::vector<Eigen::Matrix<double, 7, 7>> *cov_poses,
-                                                            std::vector<Eigen::Matrix<double, 7, 7>> *cov_cross,
-                                                            std::vector<Eigen::Matrix<double, 7, 7>> *cov_rel) {
-  const char *who = "ComputeSim3GraphCovariance";
-  const double unit = Sim3GraphUnit(who, {});
-  const auto index = [this](_BA_Pose *p) {
-    const auto it = pose_index_.find(p);
-    if (it == pose_index_.end()) throw std::runtime_error("There is no pointer in the BA pose pool.");
-    return static_cast<int32_t>(it->second);
-  };
-  std::vector<int32_t> ps, pj, pk;
-  for (_BA_Pose *p : poses) ps.push_back(index(p));
-  for (const auto &jk : pairs) {
-    pj.push_back(index(jk.first));
-    pk.push_back(index(jk.second));
-  }
-  if ((!ps.empty() && cov_poses == nullptr) || (!pj.empty() && cov_rel == nullptr))
-    throw std::runtime_error(std::string(who) + ": null output for a non-empty selection");
-  std::vector<double> cp(49 * ps.size()), cc(49 * pj.size()), cr(49 * pj.size());
-  int64_t dropped = 0;
-  ba_handle *h = nullptr;
-  ba_sim3 *g = CreateSim3Graph(who, &h);
-  const int rc = ba_sim3_covariance(g, static_cast<int>(ps.size()), ps.empty() ? nullptr : ps.data(),
-                                    ps.empty() ? nullptr : cp.data(), static_cast<int64_t>(pj.size()),
-                                    pj.empty() ? nullptr : pj.data(), pj.empty() ? nullptr : pk.data(),
-                                    pj.empty() || cov_cross == nullptr ? nullptr : cc.data(),
-                                    pj.empty() ? nullptr : cr.data(), &dropped);
-  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
-  ba_sim3_destroy(g);
-  if (h != handle_) ba_destroy(h);
-  if (rc != 0) throw std::runtime_error(err);
-  // scaled units -> the caller's: Sigma_user = unit^2 D Sigma_scaled D, D = diag(100 I3, I4)
-  const auto to_user = [&](const std::vector<double> &in, std::vector<Eigen::Matrix<double, 7, 7>> *out) {
-    if (out == nullptr) return;
-    out->resize(in.size() / 49);
-    for (size_t s = 0; s < out->size(); ++s)
-      for (int r = 0; r < 7; ++r)
-        for (int c = 0; c < 7; ++c) {
-          const double dr = r < 3 ? static_cast<double>(inverse_scaler_) : 1.0;
-          const double dc = c < 3 ? static_cast<double>(inverse_scaler_) : 1.0;
-          (*out)[s](r, c) = (unit * unit) * (dr * in[49 * s + 7 * r + c] * dc);
-        }
-  };
-  to_user(cp, cov_poses);
-  to_user(cc, cov_cross);
-  to_user(cr, cov_rel);
-  return dropped == 0;
-}
-
-bool FullBundleAdjustmentSolver::GateSim3LoopClosures(const std::vector<RelativeSim3> &candidates, double sigma_pixel,
-                                                      std::vector<double> *d2) {
-  const char *who = "GateSim3LoopClosures";
-  if (d2 == nullptr) throw std::runtime_error(std::string(who) + ": null output");
-  const double unit = Sim3GraphUnit(who, std::vector<double>(candidates.size(), sigma_pixel * static_cast<double>(scaler_)));
-  std::vector<int32_t> cj, ck;
-  std::vector<double> Z, Omega;
-  for (const RelativeSim3 &c : candidates) {
-    const auto ij = pose_index_.find(c.pose_j), ik = pose_index_.find(c.pose_k);
-    if (ij == pose_index_.end() || ik == pose_index_.end())
-      throw std::runtime_error("There is no pointer in the BA pose pool.");
-    cj.push_back(ij->second);
-    ck.push_back(ik->second);
-    PackSim3(c, sigma_pixel, &Z, &Omega);
-  }
-  d2->assign(candidates.size(), 0.0);
-  int64_t dropped = 0;
-  ba_handle *h = nullptr;
-  ba_sim3 *g = CreateSim3Graph(who, &h);
-  const bool any = !candidates.empty();
-  const int rc = ba_sim3_gate(g, static_cast<int64_t>(candidates.size()), any ? cj.data() : nullptr,
-                              any ? ck.data() : nullptr, any ? Z.data() : nullptr, any ? Omega.data() : nullptr,
-                              any ? d2->data() : nullptr, nullptr, nullptr, &dropped);
-  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
-  ba_sim3_destroy(g);
-  if (h != handle_) ba_destroy(h);
-  if (rc != 0) throw std::runtime_error(err);
-  for (double &v : *d2) v /= unit * unit;  // d2_user = d2_scaled / unit^2
-  return dropped == 0;
+  sim3_.j.push_back(ij->second);
+  sim3_.k.push_back(ik->second);
+  PackSim3(f, sigma_pixel, &sim3_.Z, &sim3_.Omega);
+  sim3_.kind.push_back(kind);
+  sim3_.scale.push_back(scale);
+  sim3_.unit.push_back(unit);
 }
 
 bool FullBundleAdjustmentSolver::SolveSim3Graph(Options options, Summary *summary,
@@ -648,43 +720,16 @@ bool FullBundleAdjustmentSolver::SolveSim3Graph(Options options, Summary *summar
   timer::StopWatch stopwatch("BundleAdjustmentSolver::SolveSim3Graph");
   stopwatch.Start();
   BeginSummary(summary, options);
-  if (poses_.empty() || sim3_j_.empty())
-    throw std::runtime_error("SolveSim3Graph: poses (AddPose) and factors (AddRelativeSim3) must be added first");
+  Graph<Sim3Abi>::Require(*this, "SolveSim3Graph", sim3_);  // before the anchors are looked at
   const size_t n_pose = poses_.size(), n_pt = points_.size();
   if (point_anchors != nullptr) {
     if (point_anchors->size() != n_pt) throw std::runtime_error("SolveSim3Graph: one anchor (or -1) per registered point");
     for (int a : *point_anchors)
       if (a >= static_cast<int>(n_pose)) throw std::runtime_error("SolveSim3Graph: an anchor is no registered pose");
   }
-  std::vector<double> S, S_new(13 * n_pose), rep_s(sim3_j_.size()), rep_w(sim3_j_.size());
-  const ba_options o = PackOptions(options, gauss_newton_);
-  std::vector<ba_iter_info> rows(static_cast<size_t>(std::max(1, o.max_num_iterations)));
-  int n_iter = 0, converged = 0;
-  ba_handle *h = nullptr;
-  ba_sim3 *g = CreateSim3Graph("SolveSim3Graph", &h, &S);
-  int rc = ba_sim3_solve(g, &o, rows.data(), static_cast<int>(rows.size()), &n_iter, &converged);
-  const char *what = "ba_sim3_solve";
-  if (rc == 0) {
-    rc = ba_sim3_get_poses(g, S_new.data());
-    what = "ba_sim3_get_poses";
-  }
-  bool any_kernel = false;
-  for (int32_t kd : sim3_kind_) any_kernel = any_kernel || kd != 0;
-  if (rc == 0 && any_kernel) {
-    rc = ba_sim3_factor_weights(g, rep_s.data(), rep_w.data());
-    what = "ba_sim3_factor_weights";
-  } else if (rc == 0) {  // no kernel: the report of before, nothing robust is allocated or launched
-    rc = ba_sim3_factor_report(g, rep_s.data());
-    what = "ba_sim3_factor_report";
-    rep_w.assign(rep_w.size(), 1.0);
-  }
-  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
-  ba_sim3_destroy(g);
-  if (h != handle_) ba_destroy(h);
-  if (rc != 0) throw std::runtime_error(std::string(what) + ": " + err);
-  for (size_t f = 0; f < rep_s.size(); ++f) rep_s[f] /= sim3_unit_[f] * sim3_unit_[f];  // the caller's units
-  sim3_report_s_.swap(rep_s);
-  sim3_report_w_.swap(rep_w);
+  GraphRun run;
+  Graph<Sim3Abi>::Run(*this, "SolveSim3Graph", &sim3_, options, &run);
+  const std::vector<double> &S = run.start, &S_new = run.solved;
   // rigid poses T_jw = [R, t / s]; the anchored points follow their keyframes
   std::vector<double> T(12 * n_pose), X(3 * n_pt, 0.0);
   std::vector<uint8_t> moved(n_pt, 0);
@@ -709,137 +754,33 @@ bool FullBundleAdjustmentSolver::SolveSim3Graph(Options options, Summary *summar
     scales->resize(n_pose);
     for (size_t p = 0; p < n_pose; ++p) (*scales)[p] = S_new[13 * p + 12];
   }
-  if (summary != nullptr) {
-    for (int k = 0; k < n_iter && k < static_cast<int>(rows.size()); ++k)
-      summary->optimization_info_list_.push_back(ToInfo(rows[k]));
-    summary->convergence_status_ = converged != 0;
-    summary->total_time_in_millisecond_ = stopwatch.GetLapTimeFromStart();
-  }
+  FinishSummary(summary, run.rows, run.n_iter, run.converged, stopwatch);
   return true;
 }
 
-void FullBundleAdjustmentSolver::GetRelativeWeights(std::vector<double> *s, std::vector<double> *w) const {
-  if (report_w_.empty()) throw std::runtime_error("GetRelativeWeights: SolvePoseGraph has not run");
-  if (s != nullptr) *s = report_s_;
-  if (w != nullptr) *w = report_w_;
+void FullBundleAdjustmentSolver::GetRelativeSim3Weights(std::vector<double> *s, std::vector<double> *w) const {
+  Graph<Sim3Abi>::Weights("GetRelativeSim3Weights", "SolveSim3Graph", sim3_, s, w);
 }
 
-ba_pgraph *FullBundleAdjustmentSolver::CreatePoseGraph(const char *who, ba_handle **h) {
-  const std::string name(who);
-  if (poses_.empty() || relatives_.j.empty())
-    throw std::runtime_error(name + ": poses (AddPose) and factors (AddRelativePose) must be added first");
-  std::vector<double> T(12 * poses_.size());
-  std::vector<uint8_t> pose_fixed(poses_.size(), 0);
-  for (size_t p = 0; p < poses_.size(); ++p) {
-    Pack12(T_jw_[p], &T[12 * p]);
-    pose_fixed[p] = fixed_poses_.count(static_cast<int>(p)) > 0;
-  }
-  *h = handle_;
-  if (*h == nullptr) Check(ba_create(h, device_id_), "ba_create");
-  ba_pgraph *g = nullptr;
-  int rc = ba_pgraph_create(&g, *h, static_cast<int>(poses_.size()), T.data(), pose_fixed.data(),
-                            static_cast<int64_t>(relatives_.j.size()), relatives_.j.data(), relatives_.k.data(),
-                            relatives_.Z.data(), relatives_.Omega.data());
-  const char *what = "ba_pgraph_create";
-  if (rc == 0) {
-    rc = ba_pgraph_set_robust(g, relatives_.kind.data(), relatives_.scale.data());
-    what = "ba_pgraph_set_robust";
-  }
-  if (rc != 0) {
-    const std::string err = ba_last_error();
-    ba_pgraph_destroy(g);
-    if (*h != handle_) ba_destroy(*h);
-    throw std::runtime_error(std::string(what) + ": " + err);
-  }
-  return g;
-}
-
-double FullBundleAdjustmentSolver::PoseGraphUnit(const char *who, const std::vector<double> &more) const {
-  std::vector<double> units(relatives_.unit);
-  units.insert(units.end(), more.begin(), more.end());
-  for (double u : units)
-    if (u != units[0]) {
-      std::ostringstream m;
-      m << who << ": the factors and candidates were given with sigma_pixel = " << units[0] / scaler_ << " and "
-        << u / scaler_ << "; a covariance in the caller's units needs one value";
-      throw std::runtime_error(m.str());
-    }
-  return units.empty() ? static_cast<double>(scaler_) : units[0];
-}
-
-bool FullBundleAdjustmentSolver::ComputePoseGraphCovariance(const std::vector<_BA_Pose *> &poses,
+bool FullBundleAdjustmentSolver::ComputeSim3GraphCovariance(const std::vector<_BA_Pose *> &poses,
                                                             const std::vector<std::pair<_BA_Pose *, _BA_Pose *>> &pairs,
-                                                            std::vector<Eigen::Matrix<double, 6, 6>> *cov_poses,
-                                                            std::vector<Eigen::Matrix<double, 6, 6>> *cov_cross,
-                                                            std::vector<Eigen::Matrix<double, 6, 6>> *cov_rel) {
-  const char *who = "ComputePoseGraphCovariance";
-  const double unit = PoseGraphUnit(who, {});
-  const auto index = [this](_BA_Pose *p) {
-    const auto it = pose_index_.find(p);
-    if (it == pose_index_.end()) throw std::runtime_error("There is no pointer in the BA pose pool.");
-    return static_cast<int32_t>(it->second);
-  };
-  std::vector<int32_t> ps, pj, pk;
-  for (_BA_Pose *p : poses) ps.push_back(index(p));
-  for (const auto &jk : pairs) {
-    pj.push_back(index(jk.first));
-    pk.push_back(index(jk.second));
-  }
-  if ((!ps.empty() && cov_poses == nullptr) || (!pj.empty() && cov_rel == nullptr))
-    throw std::runtime_error(std::string(who) + ": null output for a non-empty selection");
-  std::vector<double> cp(36 * ps.size()), cc(36 * pj.size()), cr(36 * pj.size());
-  int64_t dropped = 0;
-  ba_handle *h = nullptr;
-  ba_pgraph *g = CreatePoseGraph(who, &h);
-  const int rc = ba_pgraph_covariance(g, static_cast<int>(ps.size()), ps.empty() ? nullptr : ps.data(),
-                                      ps.empty() ? nullptr : cp.data(), static_cast<int64_t>(pj.size()),
-                                      pj.empty() ? nullptr : pj.data(), pj.empty() ? nullptr : pk.data(),
-                                      pj.empty() || cov_cross == nullptr ? nullptr : cc.data(),
-                                      pj.empty() ? nullptr : cr.data(), &dropped);
-  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
-  ba_pgraph_destroy(g);
-  if (h != handle_) ba_destroy(h);
-  if (rc != 0) throw std::runtime_error(err);
-  // scaled units -> the caller's: Sigma_user = unit^2 D Sigma_scaled D, D = diag(100 I, I)
-  const auto to_user = [&](const std::vector<double> &in, std::vector<Eigen::Matrix<double, 6, 6>> *out) {
-    if (out == nullptr) return;
-    out->resize(in.size() / 36);
-    for (size_t s = 0; s < out->size(); ++s)
-      for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c) {
-          const double dr = r < 3 ? static_cast<double>(inverse_scaler_) : 1.0;
-          const double dc = c < 3 ? static_cast<double>(inverse_scaler_) : 1.0;
-          (*out)[s](r, c) = (unit * unit) * (dr * in[36 * s + 6 * r + c] * dc);
-        }
-  };
-  to_user(cp, cov_poses);
-  to_user(cc, cov_cross);
-  to_user(cr, cov_rel);
-  return dropped == 0;
+                                                            std::vector<Eigen::Matrix<double, 7, 7>> *cov_poses,
+                                                            std::vector<Eigen::Matrix<double, 7, 7>> *cov_cross,
+                                                            std::vector<Eigen::Matrix<double, 7, 7>> *cov_rel) {
+  return Graph<Sim3Abi>::Covariance(*this, "ComputeSim3GraphCovariance", sim3_, poses, pairs, cov_poses, cov_cross,
+                                    cov_rel);
 }
 
-bool FullBundleAdjustmentSolver::GateLoopClosures(const std::vector<RelativePose> &candidates, double sigma_pixel,
-                                                  std::vector<double> *d2) {
-  const char *who = "GateLoopClosures";
-  if (d2 == nullptr) throw std::runtime_error(std::string(who) + ": null output");
-  const double unit = PoseGraphUnit(who, std::vector<double>(candidates.size(), sigma_pixel * static_cast<double>(scaler_)));
-  RelativeArrays c;
-  const std::vector<std::vector<RelativePose>> lists(1, candidates);
-  PackRelatives({this}, who, &lists, sigma_pixel, &c);  // throws on a candidate that carries a kernel
-  d2->assign(candidates.size(), 0.0);
-  int64_t dropped = 0;
-  ba_handle *h = nullptr;
-  ba_pgraph *g = CreatePoseGraph(who, &h);
-  const bool any = !candidates.empty();
-  const int rc = ba_pgraph_gate(g, static_cast<int64_t>(candidates.size()), any ? c.j.data() : nullptr,
-                                any ? c.k.data() : nullptr, any ? c.Z.data() : nullptr, any ? c.Omega.data() : nullptr,
-                                any ? d2->data() : nullptr, nullptr, nullptr, &dropped);
-  const std::string err = rc == 0 ? std::string() : std::string(ba_last_error());
-  ba_pgraph_destroy(g);
-  if (h != handle_) ba_destroy(h);
-  if (rc != 0) throw std::runtime_error(err);
-  for (double &v : *d2) v /= unit * unit;  // d2_user = d2_scaled / unit^2
-  return dropped == 0;
+bool FullBundleAdjustmentSolver::GateSim3LoopClosures(const std::vector<RelativeSim3> &candidates, double sigma_pixel,
+                                                      std::vector<double> *d2) {
+  const char *who = "GateSim3LoopClosures";
+  return Graph<Sim3Abi>::Gate(*this, who, sim3_, candidates.size(), sigma_pixel, d2, [&](RelativeArrays *c) {
+    for (const RelativeSim3 &cand : candidates) {  // a candidate's kernel is not read
+      c->j.push_back(Graph<Sim3Abi>::PoseIndex(*this, cand.pose_j));
+      c->k.push_back(Graph<Sim3Abi>::PoseIndex(*this, cand.pose_k));
+      PackSim3(cand, sigma_pixel, &c->Z, &c->Omega);
+    }
+  });
 }
 
 bool FullBundleAdjustmentSolver::ComputeCovariance(const std::vector<_BA_Pose *> &poses,

@@ -1193,7 +1193,7 @@ int ba_pgraph_factor_report(ba_pgraph *g, double *s, double *w);
  * optimisable poses, scaled units, tangent xi = [v; omega] of T <- exp(xi) T; a fixed pose has
  * zero blocks.  The call factorises H with the solve's launches (no level goes to the LDS tail
  * kernel, so the whole factor stays in the image) and reads the blocks off the factor
- * (csrc/ba_pgraph_cov.hip, fp64 MFMA, no atomics: the same bits run to run, in any selection
+ * (csrc/ba_graph_kernels.hip, fp64 MFMA, no atomics: the same bits run to run, in any selection
  * and any batch split).
  *   cov_pose36[s]   Sigma_jj of pose pose_sel[s] (6x6 row-major)
  *   cov_cross36[p]  Sigma_jk of the pair (pair_j[p], pair_k[p]); may be NULL
@@ -1360,7 +1360,7 @@ int ba_sim3_factor_weights(ba_sim3 *g, double *s, double *w);
  * Selections, repeats, both orientations, empty selections, dropped_pivots, batching and the
  * treatment of the object's state (the poses, the controller, the robust kernels,
  * ba_sim3_last_ms and the pivot count of ba_sim3_info are untouched) are those of
- * ba_pgraph_covariance.  The kernels are csrc/ba_sim3_cov.hip: fp64 MFMA sweep, no atomics, the
+ * ba_pgraph_covariance.  The kernels are csrc/ba_graph_kernels.hip: fp64 MFMA sweep, no atomics, the
  * same bits run to run, in any selection and any batch split. */
 int ba_sim3_covariance(ba_sim3 *g, int n_pose_sel, const int32_t *pose_sel, double *cov_pose49,
                        int64_t n_pair, const int32_t *pair_j, const int32_t *pair_k,
